@@ -3,16 +3,21 @@
 estimation of a 3840x2160 8-bit frame against one reference picture, SearchRange 64, CTU 64,
 FEN 1 (encoder_lowdelay_P_main.cfg), all 593 PU shapes per CTU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 2160p|1080p]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 2160p|1080p] [--full] [--dump-outputs DIR]
 
 A *step* = one whole-picture search (2040 CTUs at 2160p) on every rank; ranks hold different
 frames of the sequence (frame sharding, no data-path collective) and the per-step results are
 gathered to rank 0 with RCCL (torch.distributed "nccl": grouped ncclSend / ncclRecv) when N > 1.
 Inputs are resident in HBM before the timed region; the timed region is K steps between
 barrier + synchronize, max over ranks.  Rank 0 prints ONE JSON line: metric GSAD/s (4x4-block SAD
-evaluations per second, whole job), plus `roofline` (algorithmic bytes / measured kernel time
-against 8 TB/s) and `cpu_baseline` (the CPU oracle's exhaustive search and HM's xTZSearch
-restatement timed on this node's cores).
+evaluations per second, whole job), `ms_per_step` and `roofline` (algorithmic bytes / measured kernel
+time against 8 TB/s).  A plain run does only that: set-up, warm-up, the K timed steps, the line.
+--dump-outputs DIR writes the tables of the last timed step (dump_outputs); the inputs are seeded, so
+two builds can be compared output for output.
+
+Everything else below happens under --full only: the refinement kernel (`refine`), the tables checked
+against the CPU oracle (`verified`), `cpu_baseline` (the CPU oracle's exhaustive search and HM's
+xTZSearch restatement timed on this node's cores), the rocprofv3 counter passes, and the following.
 
 N > 1: under torch.distributed.run (RANK / WORLD_SIZE in the environment) this process is one rank.
 Invoked plainly as `python bench.py --gpus N` it starts the N ranks itself -- a child
@@ -133,7 +138,8 @@ def live_pmc(extra_args, kernel_names, budget_s=150.0):
                 return {}
             out = os.path.join(tmp, f"pass{i}")
             r = subprocess.run(["rocprofv3", "--kernel-trace", "--pmc", *group.split(), "--output-format", "csv", "-d", out, "--",
-                                sys.executable, os.path.abspath(__file__), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", *extra_args],
+                                sys.executable, os.path.abspath(__file__), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
+                                *extra_args],
                                capture_output=True, text=True, timeout=120, env=env, cwd=tmp)
             files = glob.glob(os.path.join(out, "**", "*counter_collection.csv"), recursive=True)
             if r.returncode != 0 or not files:
@@ -312,6 +318,30 @@ def cpu_baseline(cur, ref, w, h, sr, lq, bd=8, budget_s=14.0):
     }
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, tables):
+    """--dump-outputs: what a caller of the timed path receives from its last step.  tables: int32 [world, 2, n_refs, n_ctu, 593]
+    (plane 0 TComMv words, plane 1 SAD + MV cost).  Writes mv.npy (float32 [world * n_refs, n_ctu, 593, 2]) and sad.npy (float64
+    [world * n_refs, n_ctu, 593]); when the two would exceed 64 MB, a fixed seeded sample of CTUs (the same for every search) is
+    written instead and its CTU indices go to ctus.npy."""
+    n_ctu = tables.shape[3]
+    mv = np.ascontiguousarray(tables[:, 0]).view(np.int16).reshape(-1, n_ctu, 593, 2)
+    sad = tables[:, 1].view(np.uint32).reshape(-1, n_ctu, 593)
+    per_ctu = mv.shape[0] * 593 * (2 * 4 + 8)
+    os.makedirs(out_dir, exist_ok=True)
+    if per_ctu * n_ctu > DUMP_LIMIT_BYTES:
+        keep = (DUMP_LIMIT_BYTES - 8 * n_ctu) // per_ctu
+        ctus = np.sort(np.random.default_rng(2024).choice(n_ctu, size=keep, replace=False))
+        mv, sad = mv[:, ctus], sad[:, ctus]
+        np.save(os.path.join(out_dir, "ctus.npy"), ctus.astype(np.float64))
+    elif os.path.exists(os.path.join(out_dir, "ctus.npy")):   # not left over from a sampled dump of another configuration
+        os.remove(os.path.join(out_dir, "ctus.npy"))
+    np.save(os.path.join(out_dir, "mv.npy"), mv.astype(np.float32))
+    np.save(os.path.join(out_dir, "sad.npy"), sad.astype(np.float64))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -323,7 +353,13 @@ def parse_args(argv=None):
     ap.add_argument("--refs", type=int, default=1, help="reference pictures searched per step in one launch (lowdelay_P uses 4)")
     ap.add_argument("--pairs", type=int, default=1, help="DIFFERENT (current, reference) picture pairs searched per step in one launch "
                     "(hmme_search_pairs_device: what an open-loop pass over a sequence of small pictures does); excludes --refs")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="headline only: no CPU legs, no oracle check, no extra configurations "
+    ap.add_argument("--full", action="store_true", help="besides the headline, run everything else the benchmark measures and checks: "
+                    "the refinement kernel, the other configurations, the oracle checks, the CPU baselines, the rocprofv3 counter passes and, "
+                    "at N > 1, the multi-GPU evidence (off by default: a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the tables of the last timed step "
+                    "(mv.npy: float32 [searches, n_ctu, 593, 2] integer MVs; sad.npy: float64 [searches, n_ctu, 593] SAD + MV cost) "
+                    "under DIR, at most 64 MB in all (a seeded sample of CTUs beyond that, listed in ctus.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU legs, no oracle check, no extra configurations "
                     "(tools/profile_bench.sh profiles this command)")
     ap.add_argument("--no-extras", action="store_true", help="skip the other BASELINE configurations and the refinement contents")
     ap.add_argument("--no-live-pmc", action="store_true", help="do not run the rocprofv3 --pmc passes of this command after the timed region "
@@ -875,10 +911,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in events]))   # HIP events on the launch stream
+    if args.dump_outputs and rank == 0:       # before anything else reuses the step buffers
+        tables = pipe.last_gathered if use_dist else pipe.last_local.unsqueeze(0)
+        dump_outputs(args.dump_outputs, tables.cpu().numpy())
 
     # ---- evidence of the N-rank run (every rank contributes; rank 0 reports) ----------------------------------------------------
     multi = None
-    if use_dist:
+    if use_dist and args.full:
         last = pipe.last_local
         mine = {"rank": rank, "local_rank": local_rank, "device": device_identity(torch, local_rank), "kernel_ms": round(kernel_ms, 4),
                 "step_ms": round(local_elapsed / args.steps * 1e3, 4), "pid": os.getpid(),
@@ -976,7 +1015,7 @@ def main():
         # counters of THIS run where the profiler is at hand (N = 1, the full default-style run): child rocprofv3 passes of this very
         # command; otherwise the committed summary taken on the library with the same build id
         live, live_all = {}, {}
-        if world == 1 and n_refs == 1 and not args.no_cpu_baseline and not args.no_live_pmc:
+        if world == 1 and n_refs == 1 and args.full and not args.no_cpu_baseline and not args.no_live_pmc:
             passthrough = ["--size", args.size, "--search-range", str(sr), "--bit-depth", str(bd)]
             live_all = live_pmc(passthrough, [search_kernel, "me_frac_kernel"])
             live = live_all.get(search_kernel, {})
@@ -1000,7 +1039,7 @@ def main():
                          # counters: separate rocprofv3 --pmc passes of this command -- started by this very run after its timed region
                          # (true), or taken earlier on the library with the same build id and committed under profiles/ (false)
                          "traffic_same_run": (same_run if traffic is not None else None),
-                         "traffic_source": (("rocprofv3 --kernel-trace --pmc passes (FETCH_SIZE, WRITE_SIZE: one pass each) of `bench.py --steps 3 --no-cpu-baseline` "
+                         "traffic_source": (("rocprofv3 --kernel-trace --pmc passes (FETCH_SIZE, WRITE_SIZE: one pass each) of `bench.py --steps 3 --full --no-cpu-baseline` "
                                              "started by this run, %.0f s" % live["seconds"]) if same_run else
                                             ("profiles/latest_pmc_%s.json" % profile_label(args.size, sr, bd) if traffic is not None else None)),
                          "achieved_is": "ALGORITHMIC bytes per launch (SURVEY 8d: CTU + window + results per CTU-search) / kernel time; "
@@ -1058,99 +1097,100 @@ def main():
                                           "lds_wave_instructions_per_launch": int(kprof["lds_wave_instructions_per_launch"]),
                                           "tb_per_s": round(lds_bytes / (kernel_ms * 1e-3) / 1e12, 2), "peak_tb_per_s": 150.0,
                                           "frac_of_peak": round(lds_bytes / (kernel_ms * 1e-3) / 1e12 / 150.0, 4)}
-        # the step after the path, reported beside the headline, never part of `value`
-        d_q = torch.zeros((n_refs, n_ctu, api.NUM_PARTS, 2), dtype=torch.int16, device=dev)
-        d_c = torch.zeros((n_refs, n_ctu, api.NUM_PARTS), dtype=torch.int32, device=dev)
-        last = pipe.last_local
-        d_mv16 = last[0].view(torch.int16).contiguous()   # TComMv words -> int16 (x, y) pairs
-        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        scratch_tables = torch.zeros((2, n_ctu, api.NUM_PARTS), dtype=torch.int32, device=dev)
-        warm_clock(eng, (pc, pr), fp, scratch_tables, stream, launches=12)   # this process left the GPU to the counter passes above
-        for i in range(7):
-            if i == 2:
-                ev[0].record()
-            eng.refine_pairs_device(cur_planes, ref_planes, fp, None, d_mv16.data_ptr(), 1, d_q.data_ptr(), d_c.data_ptr(), stream)
-        ev[1].record()
-        torch.cuda.synchronize()
-        r_ms = ev[0].elapsed_time(ev[1]) / 5
-        out["refine"] = {"what": "xPatternSearchFracDIF (half + quarter-pel, Hadamard) for all 593 slots of every CTU, on the integer winners",
-                         "kernel": "me_frac_kernel<1, %d>" % (1 if bd == 8 else 2), "ms_per_step": round(r_ms, 4),
-                         "slots_per_s": round(n_ctu * n_refs * api.NUM_PARTS / (r_ms * 1e-3)),
-                         "content": "the bench pictures: one motion per 128x128 region, i.e. the refinement kernel's BEST case "
-                                    "(slots of a CTU share their patches); see by_content for the others"}
-        extras = n_refs == 1 and n_pairs == 1 and world == 1 and not args.no_cpu_baseline
-        # beside the headline, never `value`: the same picture against the FOUR reference pictures a lowdelay_P_main picture searches
-        # (cfg/encoder_lowdelay_P_main.cfg:24-27) in one launch -- what the encoder configuration the metric is quoted on asks of a step
-        # (not under --no-cpu-baseline: tools/profile_bench.sh profiles that command, and launches of another size would enter the
-        # per-kernel averages of its rocprofv3 summaries)
-        if extras:
-            refs4 = [pr] + [eng.plane(w, h, bd) for _ in range(3)]
-            for i, pl in enumerate(refs4[1:]):
-                _, r2, _ = synth.make_pair(w, h, seed=7000 + 13 * i, bit_depth=bd)
-                pl.upload_pel(r2, (synth.MARGIN, synth.MARGIN))
-            b4 = torch.zeros((2, 4, n_ctu, api.NUM_PARTS), dtype=torch.int32, device=dev)
-            reps4 = max(3, min(10, args.steps // 2))
-            for i in range(reps4 + 2):
+        if args.full:   # everything beside the headline: other kernels, configurations, oracle checks, CPU baselines
+            # the step after the path, reported beside the headline, never part of `value`
+            d_q = torch.zeros((n_refs, n_ctu, api.NUM_PARTS, 2), dtype=torch.int16, device=dev)
+            d_c = torch.zeros((n_refs, n_ctu, api.NUM_PARTS), dtype=torch.int32, device=dev)
+            last = pipe.last_local
+            d_mv16 = last[0].view(torch.int16).contiguous()   # TComMv words -> int16 (x, y) pairs
+            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            scratch_tables = torch.zeros((2, n_ctu, api.NUM_PARTS), dtype=torch.int32, device=dev)
+            warm_clock(eng, (pc, pr), fp, scratch_tables, stream, launches=12)   # this process left the GPU to the counter passes above
+            for i in range(7):
                 if i == 2:
                     ev[0].record()
-                eng.search_frame_multi_device(pc, refs4, fp, None, b4[0].data_ptr(), b4[1].data_ptr(), stream)
+                eng.refine_pairs_device(cur_planes, ref_planes, fp, None, d_mv16.data_ptr(), 1, d_q.data_ptr(), d_c.data_ptr(), stream)
             ev[1].record()
             torch.cuda.synchronize()
-            ms4 = ev[0].elapsed_time(ev[1]) / reps4
-            out["four_references_per_launch"] = {"what": "one current picture against 4 reference pictures in ONE launch (hmme_search_frame_multi_device)",
-                                                 "ms_per_launch": round(ms4, 4), "gsad_per_s": round(4 * sads / (ms4 * 1e-3) / 1e9, 1),
-                                                 "ctus_per_s": round(4 * n_ctu / (ms4 * 1e-3), 1)}
-            for pl in refs4[1:]:
-                pl.close()
-        fprof = live_all.get("me_frac_kernel") or prof.get("kernels", {}).get("me_frac_kernel", {})
-        if fprof.get("hbm_traffic_bytes_per_launch") is not None:   # counters of the refinement launches of the same child runs as the search kernel's
-            out["refine"]["counters_same_run"] = "me_frac_kernel" in live_all
-            out["refine"]["hbm_traffic_bytes_per_launch"] = int(fprof["hbm_traffic_bytes_per_launch"])
-            if fprof.get("hbm_write_bytes_per_launch") is not None:
-                out["refine"]["hbm_write_bytes_per_launch"] = int(fprof["hbm_write_bytes_per_launch"])
-                out["refine"]["result_bytes_per_launch"] = n_ctu * n_refs * api.NUM_PARTS * 8
-            if fprof.get("scratch_bytes_per_lane") is not None:
-                out["refine"]["scratch_bytes_per_lane"] = int(fprof["scratch_bytes_per_lane"])
-            out["refine"]["valu_busy_frac"] = round(fprof.get("valu_busy_frac", 0.0), 4)
-            if fprof.get("avg_waves_per_simd") is not None:
-                out["refine"]["avg_waves_per_simd"] = round(fprof["avg_waves_per_simd"], 3)
-            if fprof.get("lds_bank_conflict_frac") is not None:
-                out["refine"]["lds_bank_conflict_frac"] = round(fprof["lds_bank_conflict_frac"], 4)
-        if not args.no_cpu_baseline and world == 1:   # rank 0 at N = 1 only: the other ranks would wait on it
-            # what was timed is what is reported: tables of the LAST timed step against the CPU oracle on a CTU sample
-            # (corner, interior, partial bottom row); a mismatch fails the run
-            res = last.cpu().numpy()
-            out["verified"] = verify_against_oracle(res, cur, ref, w, h, sr, lq, bd)
-        if extras and not args.no_extras and (w, h, bd, sr) == (3840, 2160, 8, 64):
-            # the other single-GPU BASELINE configurations and the refinement kernel's content dependence, each timed with HIP events
-            # and checked against the oracle in this same process (BASELINE.json configs 2, 5 and 4-on-one-GPU)
-            t_x = time.time()
-            out["refine"]["by_content"] = time_refine_contents(torch, api, synth, eng, dev, w, h, bd, sr)
-            out.setdefault("configs", {}).update({
-                "config2_1080p_sr64": time_search_config(torch, api, synth, eng, dev, 1920, 1080, 8, 64, 20, 1234,
-                                                         "1920x1080 8-bit, SearchRange=64 (BASELINE config 2), one reference per launch"),
-                "config5_2160p_10bit_sr128": time_search_config(torch, api, synth, eng, dev, 3840, 2160, 10, 128, 5, 1234,
-                                                                "3840x2160 10-bit, SearchRange=128, packed-u16 SAD path (BASELINE config 5)"),
-                # SURVEY 8d's second measurement: the headline workload with every CTU's window centred on a seeded predictor of up
-                # to +-16 pel, as the encoder's caller centres it on the AMVP predictor
-                "with_random_predictors": time_search_config(torch, api, synth, eng, dev, 3840, 2160, 8, 64, 10, 1234,
-                                                             "3840x2160 8-bit, SearchRange=64, per-CTU random predictors <= +-16 pel (SURVEY 8d)",
-                                                             pred=synth.random_predictors(n_ctu, seed=4242, max_pel=16)),
-                # pictures that do not fill whole rounds of the chip's 512 search workgroups, one pair per launch: 720p is 240 jobs (all "tail": equal
-                # segments of the jobs' task list), 1440p 512 whole jobs + 408 as segments in the same launch (DESIGN.md 4.1 "Tails")
-                "small_pictures_one_pair_per_launch": {
-                    "1280x720": time_search_config(torch, api, synth, eng, dev, 1280, 720, 8, 64, 20, 1234, "1280x720 8-bit, SearchRange=64, one pair per launch (240 CTU searches on 512 workgroup slots)"),
-                    "2560x1440": time_search_config(torch, api, synth, eng, dev, 2560, 1440, 8, 64, 20, 1234, "2560x1440 8-bit, SearchRange=64, one pair per launch (920 CTU searches = 512 + 408)")},
-                "config4_2160p_randomaccess_64_pictures_one_gpu": time_sequence_config(torch, api, synth, eng, dev),
-                "config4_with_refinement": time_sequence_config(torch, api, synth, eng, dev, refine=True),
-            })
-            out["configs"]["seconds"] = round(time.time() - t_x, 1)
-            # the end-to-end figure an encoder integrator needs: integer search + fractional refinement of a 2160p pair, per content
-            out["search_plus_refine"] = {"what": "hmme_search_frame_device then hmme_refine_frame_multi_device (Hadamard) of the same 2160p pair, back to back on one stream "
-                                                 "(TEncSearch.cpp:3749 then :3798 for every PU of every CTU)",
-                                         "by_content": {k: v["search_plus_refine"] for k, v in out["refine"]["by_content"].items()}}
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(cur, ref, w, h, sr, lq, bd)
+            r_ms = ev[0].elapsed_time(ev[1]) / 5
+            out["refine"] = {"what": "xPatternSearchFracDIF (half + quarter-pel, Hadamard) for all 593 slots of every CTU, on the integer winners",
+                             "kernel": "me_frac_kernel<1, %d>" % (1 if bd == 8 else 2), "ms_per_step": round(r_ms, 4),
+                             "slots_per_s": round(n_ctu * n_refs * api.NUM_PARTS / (r_ms * 1e-3)),
+                             "content": "the bench pictures: one motion per 128x128 region, i.e. the refinement kernel's BEST case "
+                                        "(slots of a CTU share their patches); see by_content for the others"}
+            extras = n_refs == 1 and n_pairs == 1 and world == 1 and not args.no_cpu_baseline
+            # beside the headline, never `value`: the same picture against the FOUR reference pictures a lowdelay_P_main picture searches
+            # (cfg/encoder_lowdelay_P_main.cfg:24-27) in one launch -- what the encoder configuration the metric is quoted on asks of a step
+            # (not under --no-cpu-baseline: tools/profile_bench.sh profiles that command, and launches of another size would enter the
+            # per-kernel averages of its rocprofv3 summaries)
+            if extras:
+                refs4 = [pr] + [eng.plane(w, h, bd) for _ in range(3)]
+                for i, pl in enumerate(refs4[1:]):
+                    _, r2, _ = synth.make_pair(w, h, seed=7000 + 13 * i, bit_depth=bd)
+                    pl.upload_pel(r2, (synth.MARGIN, synth.MARGIN))
+                b4 = torch.zeros((2, 4, n_ctu, api.NUM_PARTS), dtype=torch.int32, device=dev)
+                reps4 = max(3, min(10, args.steps // 2))
+                for i in range(reps4 + 2):
+                    if i == 2:
+                        ev[0].record()
+                    eng.search_frame_multi_device(pc, refs4, fp, None, b4[0].data_ptr(), b4[1].data_ptr(), stream)
+                ev[1].record()
+                torch.cuda.synchronize()
+                ms4 = ev[0].elapsed_time(ev[1]) / reps4
+                out["four_references_per_launch"] = {"what": "one current picture against 4 reference pictures in ONE launch (hmme_search_frame_multi_device)",
+                                                     "ms_per_launch": round(ms4, 4), "gsad_per_s": round(4 * sads / (ms4 * 1e-3) / 1e9, 1),
+                                                     "ctus_per_s": round(4 * n_ctu / (ms4 * 1e-3), 1)}
+                for pl in refs4[1:]:
+                    pl.close()
+            fprof = live_all.get("me_frac_kernel") or prof.get("kernels", {}).get("me_frac_kernel", {})
+            if fprof.get("hbm_traffic_bytes_per_launch") is not None:   # counters of the refinement launches of the same child runs as the search kernel's
+                out["refine"]["counters_same_run"] = "me_frac_kernel" in live_all
+                out["refine"]["hbm_traffic_bytes_per_launch"] = int(fprof["hbm_traffic_bytes_per_launch"])
+                if fprof.get("hbm_write_bytes_per_launch") is not None:
+                    out["refine"]["hbm_write_bytes_per_launch"] = int(fprof["hbm_write_bytes_per_launch"])
+                    out["refine"]["result_bytes_per_launch"] = n_ctu * n_refs * api.NUM_PARTS * 8
+                if fprof.get("scratch_bytes_per_lane") is not None:
+                    out["refine"]["scratch_bytes_per_lane"] = int(fprof["scratch_bytes_per_lane"])
+                out["refine"]["valu_busy_frac"] = round(fprof.get("valu_busy_frac", 0.0), 4)
+                if fprof.get("avg_waves_per_simd") is not None:
+                    out["refine"]["avg_waves_per_simd"] = round(fprof["avg_waves_per_simd"], 3)
+                if fprof.get("lds_bank_conflict_frac") is not None:
+                    out["refine"]["lds_bank_conflict_frac"] = round(fprof["lds_bank_conflict_frac"], 4)
+            if not args.no_cpu_baseline and world == 1:   # rank 0 at N = 1 only: the other ranks would wait on it
+                # what was timed is what is reported: tables of the LAST timed step against the CPU oracle on a CTU sample
+                # (corner, interior, partial bottom row); a mismatch fails the run
+                res = last.cpu().numpy()
+                out["verified"] = verify_against_oracle(res, cur, ref, w, h, sr, lq, bd)
+            if extras and not args.no_extras and (w, h, bd, sr) == (3840, 2160, 8, 64):
+                # the other single-GPU BASELINE configurations and the refinement kernel's content dependence, each timed with HIP events
+                # and checked against the oracle in this same process (BASELINE.json configs 2, 5 and 4-on-one-GPU)
+                t_x = time.time()
+                out["refine"]["by_content"] = time_refine_contents(torch, api, synth, eng, dev, w, h, bd, sr)
+                out.setdefault("configs", {}).update({
+                    "config2_1080p_sr64": time_search_config(torch, api, synth, eng, dev, 1920, 1080, 8, 64, 20, 1234,
+                                                             "1920x1080 8-bit, SearchRange=64 (BASELINE config 2), one reference per launch"),
+                    "config5_2160p_10bit_sr128": time_search_config(torch, api, synth, eng, dev, 3840, 2160, 10, 128, 5, 1234,
+                                                                    "3840x2160 10-bit, SearchRange=128, packed-u16 SAD path (BASELINE config 5)"),
+                    # SURVEY 8d's second measurement: the headline workload with every CTU's window centred on a seeded predictor of up
+                    # to +-16 pel, as the encoder's caller centres it on the AMVP predictor
+                    "with_random_predictors": time_search_config(torch, api, synth, eng, dev, 3840, 2160, 8, 64, 10, 1234,
+                                                                 "3840x2160 8-bit, SearchRange=64, per-CTU random predictors <= +-16 pel (SURVEY 8d)",
+                                                                 pred=synth.random_predictors(n_ctu, seed=4242, max_pel=16)),
+                    # pictures that do not fill whole rounds of the chip's 512 search workgroups, one pair per launch: 720p is 240 jobs (all "tail": equal
+                    # segments of the jobs' task list), 1440p 512 whole jobs + 408 as segments in the same launch (DESIGN.md 4.1 "Tails")
+                    "small_pictures_one_pair_per_launch": {
+                        "1280x720": time_search_config(torch, api, synth, eng, dev, 1280, 720, 8, 64, 20, 1234, "1280x720 8-bit, SearchRange=64, one pair per launch (240 CTU searches on 512 workgroup slots)"),
+                        "2560x1440": time_search_config(torch, api, synth, eng, dev, 2560, 1440, 8, 64, 20, 1234, "2560x1440 8-bit, SearchRange=64, one pair per launch (920 CTU searches = 512 + 408)")},
+                    "config4_2160p_randomaccess_64_pictures_one_gpu": time_sequence_config(torch, api, synth, eng, dev),
+                    "config4_with_refinement": time_sequence_config(torch, api, synth, eng, dev, refine=True),
+                })
+                out["configs"]["seconds"] = round(time.time() - t_x, 1)
+                # the end-to-end figure an encoder integrator needs: integer search + fractional refinement of a 2160p pair, per content
+                out["search_plus_refine"] = {"what": "hmme_search_frame_device then hmme_refine_frame_multi_device (Hadamard) of the same 2160p pair, back to back on one stream "
+                                                     "(TEncSearch.cpp:3749 then :3798 for every PU of every CTU)",
+                                             "by_content": {k: v["search_plus_refine"] for k, v in out["refine"]["by_content"].items()}}
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(cur, ref, w, h, sr, lq, bd)
         print(json.dumps(out), flush=True)
     for pl in set(cur_planes) | set(ref_planes):
         pl.close()

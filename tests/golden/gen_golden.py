@@ -16,9 +16,12 @@ Every .npz holds inputs and the reference's outputs -- data only.
   border.npz           TComPicYuv::create + extendPicBorder: small pictures in, the whole padded luma buffer out
   frac_bipred.npz      xPatternSearchFracDIF(..., biPred = true) on bi-prediction origins 2*org - pred_other (samples outside the
                        sample range, TEncSearch.cpp:3702-3712): `python tests/golden/gen_golden.py frac_bipred` makes this file alone
+  oracle_vs_ref.npz    the reference's answers to the questions of tests/test_oracle_vs_ref.py, in the order the tests ask them, recorded
+                       by those tests against the live library: `python tests/golden/gen_golden.py oracle_vs_ref` makes this file alone
 """
 import ctypes as C
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -466,6 +469,13 @@ def main():
     global R
     O.build(ref=True)
     R = O.ref()
+    if sys.argv[1:] == ["oracle_vs_ref"]:
+        path = os.path.join(HERE, "oracle_vs_ref.npz")
+        if os.path.exists(path):
+            os.remove(path)
+        subprocess.run([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", os.path.join(ROOT, "tests", "test_oracle_vs_ref.py")],
+                       env=dict(os.environ, HMME_RECORD_REF_ANSWERS="1"), cwd=ROOT, check=True)
+        return
     if sys.argv[1:] == ["frac_bipred"]:   # this file alone; the slot table comes from the committed slots.npz
         gen_frac_bipred(np.load(os.path.join(HERE, "slots.npz"))["table"])
         return

@@ -1069,7 +1069,7 @@ def test_bench_collective_path_under_torchrun_one_rank(tmp_path):
     env = dict(os.environ, HMME_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                        "--size", "1080p", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env, cwd=str(tmp_path))
+                        "--size", "1080p", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["value"] > 100 and d["roofline"]["kernel_ms"] > 0
@@ -1091,7 +1091,7 @@ def test_bench_starts_its_own_ranks_two_rank_rehearsal_on_one_gpu(tmp_path):
     from conftest import ROOT
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--backend", "gloo", "--steps", "3",
-                        "--warmup", "1", "--size", "512x320", "--search-range", "16"], capture_output=True, text=True, timeout=900, env=env,
+                        "--warmup", "1", "--size", "512x320", "--search-range", "16", "--full"], capture_output=True, text=True, timeout=900, env=env,
                        cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -1138,7 +1138,7 @@ def test_bench_four_rank_rehearsal_deals_config4_raggedly(tmp_path):
     from conftest import ROOT
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--share-gpu", "--backend", "gloo", "--steps", "2",
-                        "--warmup", "1", "--size", "256x192", "--search-range", "16"], capture_output=True, text=True, timeout=900, env=env,
+                        "--warmup", "1", "--size", "256x192", "--search-range", "16", "--full"], capture_output=True, text=True, timeout=900, env=env,
                        cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])

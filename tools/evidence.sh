@@ -9,13 +9,13 @@ TAG=$1; PART=$2; OUT=gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
 if [ "$PART" = measure ]; then
   rm -rf gpurun_out/prof_$TAG
   python -m pytest tests -m gpu -x -q 2>&1 | tail -4 | tee $OUT/gpu_tests.txt
-  python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"
+  python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"
   bash tools/profile_bench.sh $TAG > $OUT/profile.log 2>&1; echo "profile rc=$?"
-  python bench.py > $OUT/bench_default_second_run.json 2> $OUT/bench_default2.err; echo "bench2 rc=$?"
-  python bench.py --gpus 2 --share-gpu --backend gloo --steps 10 --warmup 2 > $OUT/bench_2rank_gloo_rehearsal_one_gpu.json 2> $OUT/bench_2rank.err; echo "2-rank rc=$?"
-  python bench.py --gpus 4 --share-gpu --backend gloo --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_4rank_gloo_rehearsal_one_gpu.json 2> $OUT/bench_4rank.err; echo "4-rank rc=$?"
-  for s in 720p 1080p 1200p 1440p 1600p; do python bench.py --size $s --no-cpu-baseline --steps 20 > $OUT/bench_$s.json 2>> $OUT/bench_sizes.err; done
-  python bench.py --bit-depth 10 --search-range 64 --no-cpu-baseline --steps 10 > $OUT/bench_2160p_10bit_sr64.json 2>> $OUT/bench_sizes.err
+  python bench.py --full > $OUT/bench_default_second_run.json 2> $OUT/bench_default2.err; echo "bench2 rc=$?"
+  python bench.py --gpus 2 --share-gpu --backend gloo --steps 10 --warmup 2 --full > $OUT/bench_2rank_gloo_rehearsal_one_gpu.json 2> $OUT/bench_2rank.err; echo "2-rank rc=$?"
+  python bench.py --gpus 4 --share-gpu --backend gloo --steps 10 --warmup 2 --full --no-cpu-baseline > $OUT/bench_4rank_gloo_rehearsal_one_gpu.json 2> $OUT/bench_4rank.err; echo "4-rank rc=$?"
+  for s in 720p 1080p 1200p 1440p 1600p; do python bench.py --size $s --full --no-cpu-baseline --steps 20 > $OUT/bench_$s.json 2>> $OUT/bench_sizes.err; done
+  python bench.py --bit-depth 10 --search-range 64 --full --no-cpu-baseline --steps 10 > $OUT/bench_2160p_10bit_sr64.json 2>> $OUT/bench_sizes.err
 elif [ "$PART" = validate ]; then
   HMME_FUZZ_CASES=${FUZZ_CASES:-3000} HMME_FUZZ_SEED=${FUZZ_SEED:-99000} HMME_FUZZ_CTU=${FUZZ_CTU:-2000} HMME_FUZZ_BIG=${FUZZ_BIG:-12} HMME_FUZZ_SLOTS=40 \
     python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k fuzz --durations=3 2>&1 | tail -8 | tee $OUT/fuzz_extended.txt

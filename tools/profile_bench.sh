@@ -19,11 +19,11 @@ profile_one() {   # label, bench arguments...
   local out=gpurun_out/prof_$TAG/$label
   mkdir -p $out
   echo "== $label: kernel trace"
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline "$@" > $out/bench_under_rocprof.json 2> $out/trace.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --steps 10 --warmup 2 --full --no-cpu-baseline "$@" > $out/bench_under_rocprof.json 2> $out/trace.err
   for pass in "${PASSES[@]}"; do
     name=$(echo $pass | cut -d' ' -f1)
     echo "== $label: pmc $name"
-    rocprofv3 --kernel-trace --pmc $pass --output-format csv -d $out/pmc_$name -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline "$@" > /dev/null 2> $out/pmc_$name.err || echo "pass $name failed"
+    rocprofv3 --kernel-trace --pmc $pass --output-format csv -d $out/pmc_$name -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline "$@" > /dev/null 2> $out/pmc_$name.err || echo "pass $name failed"
   done
   python3 tools/summarize_profile.py $out $TAG $label
 }
