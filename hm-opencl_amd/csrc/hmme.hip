@@ -36,12 +36,8 @@ static_assert(sizeof(MeJob16) * kCallMaxJobs <= kCallFirst && kCallFracJob + siz
 // pinned result block: 593 MVs, 593 SADs, completion word of the search; 593 quarter-pel MVs, 593 costs, completion word of the refinement
 constexpr size_t kResMv = 0, kResSad = 4 * HMME_NUM_CTU_PARTS, kResDone = 8 * HMME_NUM_CTU_PARTS, kResQmv = kResDone + 64,
                  kResCost = kResQmv + 4 * HMME_NUM_CTU_PARTS, kResDone2 = kResCost + 4 * HMME_NUM_CTU_PARTS, kResBytes = kResDone2 + 64;
-// per workgroup of the 16-bit path -> 2 workgroups per CU (HMME_LDS_BUDGET16: A/B knob in bytes)
-// A value that cannot hold a one-row strip at the larger pitch (or exceeds the 160 KB of a CU) is ignored with a message: strips_for()
-// would otherwise never terminate / every launch would fail.
-constexpr size_t kLdsBudget16Default = 78 * 1024;
-size_t lds_budget16_from_env();
-const size_t kLdsBudget16 = lds_budget16_from_env();
+// per workgroup of the 16-bit path -> 2 workgroups per CU
+constexpr size_t kLdsBudget16 = 78 * 1024;
 // LDS window pitch of the 16-bit kernel in dwords -- a template parameter of the kernel (the odd row of a row pair is addressed by
 // an immediate).  A lane reads dwords 3 * (lane in row) + 0..33 of its window row, lanes-per-row L = ceil(ceil(wx / 2) / 3), so a
 // row needs 3 * (L - 1) + 34 dwords; the pitch also decides which banks the rows of one wave-wide read share (64 lanes cover 1.5 .. 6
@@ -67,17 +63,7 @@ int pick_pdw16(int wx) {
 }
 thread_local std::string g_create_error;   // hmme_last_error(NULL): per host thread, like the contexts themselves
 constexpr size_t lds_bytes16_c(int pdw, int strip_rows) { return (size_t)(2 * 594 + 4 + (strip_rows + 63) * pdw) * 4; }
-size_t lds_budget16_from_env() {
-  const char* e = std::getenv("HMME_LDS_BUDGET16");
-  if (!e) return kLdsBudget16Default;
-  const long v = std::atol(e);
-  if (v < (long)lds_bytes16_c(kPdw16Large, 1) || v > 160 * 1024) {
-    fprintf(stderr, "hmme: HMME_LDS_BUDGET16=%s outside [%zu, %d] bytes: using the default %zu\n", e, lds_bytes16_c(kPdw16Large, 1), 160 * 1024,
-            kLdsBudget16Default);
-    return kLdsBudget16Default;
-  }
-  return (size_t)v;
-}
+static_assert(lds_bytes16_c(kPdw16Large, 1) <= kLdsBudget16, "a one-row strip fits the LDS budget (strips_for terminates)");
 }  // namespace
 
 struct hmme_ctx {
@@ -113,8 +99,8 @@ struct hmme_ctx {
   size_t jobs_bytes = 0;
   // A job table is a function of the picture size, the search range, the CTU range, the number of pairs and the predictors.  Launches
   // WITHOUT predictors (d_pred_q == null: the zero predictor of the reference's own call) of the same geometry on the same stream find
-  // the table of the launch before still in place and skip the kernels that write it -- one kernel launch less per search step
-  // (HMME_NO_TABLE_CACHE=1: always rebuild).  `buf` / `buf2`: the allocations the table lives in (a reallocation invalidates it)
+  // the table of the launch before still in place and skip the kernels that write it -- one kernel launch less per search step.
+  // `buf` / `buf2`: the allocations the table lives in (a reallocation invalidates it)
   struct TableTag {
     bool valid = false;
     int w = 0, h = 0, bit_depth = 0, sr = 0, first = 0, count = 0, pairs = 0;
@@ -252,14 +238,12 @@ RefSet one_ref(const uint8_t* base) {
   return r;
 }
 
-// Progress-based wave priorities of the search kernels (me_search_kernel, ME_FAIR_PRIO): the kernel whose workgroups are whole CTU
+// Progress-based wave priorities of the search kernels (me_search_kernel, me_search16_kernel): the kernel whose workgroups are whole CTU
 // searches always runs with them (+8 % on a single-round 1080p launch, +2 % at 2160p: the lonely ends of each CU's last workgroups);
 // the launches of many small workgroups -- split tasks, window tiles, 16-bit strips -- only while the launch is a few rounds of the
 // chip's workgroup slots (720p +5 %, 1080p 10-bit +5 %; config 5's 16 rounds of strips lost 0.8 % with them:
-// profiles/r05d_fair_priority_ab.txt).  HMME_FAIR_PRIO=0|1 forces one for A/B runs.
+// profiles/r05d_fair_priority_ab.txt).
 int fair_prio(const hmme_ctx* ctx, int workgroups, bool whole_jobs) {
-  static const int force = std::getenv("HMME_FAIR_PRIO") ? std::atoi(std::getenv("HMME_FAIR_PRIO")) : -1;
-  if (force >= 0) return force ? 1 : 0;
   return (whole_jobs || workgroups <= 4 * ctx->wg_slots) ? 1 : 0;
 }
 
@@ -344,7 +328,7 @@ int rows_max16(int pdw) {
 // strips of candidate rows so that one strip's window rows fit the LDS budget
 int strips_for(int pdw, int wy_max) {
   int n = 1;
-  while (n < wy_max && lds_bytes16(pdw, (wy_max + n - 1) / n) > kLdsBudget16) ++n;   // bounded: one-row strips always fit (budget is validated)
+  while (n < wy_max && lds_bytes16(pdw, (wy_max + n - 1) / n) > kLdsBudget16) ++n;   // bounded: one-row strips always fit
   return n;
 }
 
@@ -1192,10 +1176,6 @@ static int prep_jobs(hmme_ctx* ctx, const hmme_plane* cur, const hmme_frame_para
     pl->strip_rows = rmax;
     const int h = hmme::me_strip_rows16(w, w, rmax, n_min + 4);   // up to four strips more than LDS alone needs
     pl->n_strips = (w + h - 1) / h;
-    if (const char* e = std::getenv("HMME_STRIPS16")) {   // A/B knob: that many strips of equal height
-      const int n = std::atoi(e);
-      if (n >= n_min && n <= w) { pl->n_strips = n; pl->strip_rows = (w + n - 1) / n; }
-    }
     // the workgroups beyond the last full round: head jobs give (jobs - tail) * n_strips of them, which need not fill whole rounds
     // either -- the tail is planned on what is left of the last head round
     const int lanes = (((w + 1) >> 1) + 2) / 3;
@@ -1244,9 +1224,8 @@ static int prep_jobs(hmme_ctx* ctx, const hmme_plane* cur, const hmme_frame_para
     ctx->first_strip_cap = (int)(fcap / sizeof(int));
     if (rc) return rc;
   }
-  static const bool no_cache = std::getenv("HMME_NO_TABLE_CACHE") != nullptr;
   hmme_ctx::TableTag tag;
-  tag.valid = !d_pred_q && !no_cache;
+  tag.valid = !d_pred_q;
   tag.w = cur->width; tag.h = cur->height; tag.bit_depth = fp->bit_depth; tag.sr = fp->search_range; tag.first = first; tag.count = count; tag.pairs = n_refs;
   tag.buf = ctx->d_jobs; tag.buf2 = (wide || pl->tile8 || n_tail) ? ctx->d_first_strip : nullptr; tag.stream = (void*)s;
   if (tag.same(ctx->jobs_tag)) return HMME_OK;   // the table of the launch before is this launch's table
@@ -1475,9 +1454,8 @@ int hmme_refine_pairs_device(hmme_ctx* ctx, const hmme_plane* const* curs, const
     const bool walk = grid < jobs;
     const bool packable = pl.count <= 0xffff && pl.first <= 0xffff;   // FracPrep packs the CTU range into 16 + 16 bits (a 16384 x 16384 picture has 65 536 CTUs)
     const bool need_table = walk || table || !packable;
-    static const bool no_cache = std::getenv("HMME_NO_TABLE_CACHE") != nullptr;
     hmme_ctx::TableTag tag;
-    tag.valid = !d_pred_q && !no_cache && !walk;   // (the job-walking mode's prep kernel also resets the job counter: every launch)
+    tag.valid = !d_pred_q && !walk;   // (the job-walking mode's prep kernel also resets the job counter: every launch)
     tag.w = curs[0]->width; tag.h = curs[0]->height; tag.bit_depth = fp->bit_depth; tag.sr = fp->search_range; tag.first = pl.first; tag.count = pl.count;
     tag.pairs = n_pairs; tag.buf = ctx->d_frac_jobs; tag.stream = (void*)s;
     const bool have_table = need_table && tag.same(ctx->frac_jobs_tag);

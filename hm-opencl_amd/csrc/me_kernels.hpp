@@ -32,24 +32,9 @@ constexpr int kGroups = 10;
 // CTU's LDS table; whole-picture launches run 4 per task (measured on 2160p: 1 / 2 / 4 -> 3 252 / 3 256 / 3 284 GSAD/s,
 // profiles/archive/r02f_*), split launches (one CTU dealt to many workgroups, where the number of tasks is the parallelism) 1: the per-CTU
 // call at SR 64 goes from 9 to 17 workgroups of one iteration per wave, 0.086 -> 0.065 ms (profiles/archive/r02l_*)
-#ifndef ME_ITER_PER_TASK
-#define ME_ITER_PER_TASK 4
-#endif
-#ifndef ME_ITER_PER_TASK_SPLIT
-#define ME_ITER_PER_TASK_SPLIT 1
-#endif
-#ifndef ME_GUIDED_TASKS
-#define ME_GUIDED_TASKS 1
-#endif
-#ifndef ME_FRAC_PRIO   // A/B: 0 = the refinement kernel's waves all at the dispatch priority
-#define ME_FRAC_PRIO 1
-#endif
-#ifndef ME_FAIR_PRIO   // A/B: 0 = every wave at the dispatch priority (the SIMD then favours its oldest wave)
-#define ME_FAIR_PRIO 1
-#endif
-constexpr int kIterPerTask = ME_ITER_PER_TASK;
-constexpr int kIterPerTaskSplit = ME_ITER_PER_TASK_SPLIT;
-static_assert(ME_ITER_PER_TASK <= 4 && (!ME_GUIDED_TASKS || ME_ITER_PER_TASK == 4), "2 iteration bits in the key; the guided schedule deals 4 / 2 / 1");
+constexpr int kIterPerTask = 4;
+constexpr int kIterPerTaskSplit = 1;
+static_assert(kIterPerTask == 4 && kIterPerTaskSplit <= 4, "2 iteration bits in the key; the guided schedule deals 4 / 2 / 1");
 constexpr int kThreads = 256;
 
 // one CTU search: everything in integer pels except the quarter-pel predictor
@@ -217,16 +202,11 @@ static_assert(sizeof(MeJob16) == 24, "MeJob16 layout");
 // remain, then 2 at a time while more than T2 (2) remain, the last ones singly.  Large tasks keep the number of flushes low, small last ones keep the four waves of a
 // workgroup level when the task counter runs dry (a wave that finishes a 4-iteration task early leaves its SIMD slot empty until the
 // whole workgroup is done).  n4 / n2 / n1 = number of tasks of each size for `iters` iterations.
-#ifndef ME_GUIDED_T4
-#define ME_GUIDED_T4 8
-#endif
-#ifndef ME_GUIDED_T2
-#define ME_GUIDED_T2 2
-#endif
+constexpr int kGuidedT4 = 8, kGuidedT2 = 2;
 __host__ __device__ inline void me_guided(int iters, int& n4, int& n2, int& n1) {
-  n4 = iters > ME_GUIDED_T4 ? (iters - ME_GUIDED_T4 + 3) >> 2 : 0;
+  n4 = iters > kGuidedT4 ? (iters - kGuidedT4 + 3) >> 2 : 0;
   const int rem = iters - 4 * n4;                    // T4-3..T4, or iters itself when <= T4
-  n2 = rem > ME_GUIDED_T2 ? (rem - ME_GUIDED_T2 + 1) >> 1 : 0;
+  n2 = rem > kGuidedT2 ? (rem - kGuidedT2 + 1) >> 1 : 0;
   n1 = rem - 2 * n2;                                 // T2-1..T2 (0 only for iters == 0)
 }
 __host__ __device__ inline int me_num_tasks_guided(int wx, int wy) {
@@ -382,9 +362,7 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
     }                                  // else: a head job, whole (t_first = 0, t_end = everything; seg_g == seg_end: one pass)
     if (!first_job) __syncthreads();   // every thread has merged the previous job's table; window and table are free again
   }
-#if ME_FAIR_PRIO
   if (fair_prio) __builtin_amdgcn_s_setprio(3);   // a new workgroup comes first: its window loads go out at once, its first tasks run ahead of the older workgroup's last
-#endif
   const uint8_t* __restrict__ ref_base = refs.base[job.ctu_x & 63];
   const uint8_t* __restrict__ cur_base = curs.base[job.ctu_x & 63];
   job.ctu_x &= ~63;
@@ -417,7 +395,7 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
   //       (129 -> 32 + 1); part k lays a wave out as 2^k quads x (64 >> k) rows per iteration.
   const int quads = (wx + 3) >> 2;
   constexpr int kIt = SPLIT ? kIterPerTaskSplit : kIterPerTask;
-  constexpr bool kGuided = !SPLIT && ME_GUIDED_TASKS;
+  constexpr bool kGuided = !SPLIT;
   const int n_tasks = kGuided ? me_num_tasks_guided(wx, wy) : min(me_num_tasks(wx, wy, kIt), t_end);
   const bool fold = me_fold(quads, wy);
   const int wy_low = fold ? wy - 1 : wy;
@@ -425,7 +403,6 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
   const uint32_t mult_a = 1u << kIdxBits;
   const uint32_t mult_e = FEN ? (2u << kIdxBits) : (1u << kIdxBits);
   const bool rb1 = lane & 2, rb0 = lane & 1;
-#if ME_FAIR_PRIO
   // Wave priority falls with the wave's progress (s_setprio 3 .. 0 over its expected share of the workgroup's lane-iterations).  A SIMD
   // holds one wave of each of the CU's two workgroups and issues from the OLDER one whenever it can: of two workgroups that start
   // together the older ran at full speed and the younger in its gaps (a fifth of the rate), then alone -- one wave per SIMD issues at
@@ -445,7 +422,6 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
     }
   }
   int prio_state = prio_quarter << 2;
-#endif
 
   static_assert(SPLIT != 2 || kIterPerTaskSplit == 1, "segment mode counts tasks in lane-iterations");
   int grab_next = 0, grab_end = 0;   // SPLIT = 2: the tasks this wave has drawn and not yet run
@@ -473,14 +449,12 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
       t = __builtin_amdgcn_readfirstlane(t);
       if (t >= n_tasks) break;
     }
-#if ME_FAIR_PRIO
     if (prio_state < 4 && (prio_state & 3) < 3) {   // the level's share is used up: one step down
       prio_state += (prio_quarter << 2) + 1;
       if ((prio_state & 3) == 1) __builtin_amdgcn_s_setprio(2);
       else if ((prio_state & 3) == 2) __builtin_amdgcn_s_setprio(1);
       else __builtin_amdgcn_s_setprio(0);
     }
-#endif
     // decode task t -> (x0, k, first iteration)
     int x0 = 0, k = 0, it0 = 0, n_it = 0;
     {
@@ -520,9 +494,7 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
     uint32_t b0 = ME_MAXKEY, b1 = ME_MAXKEY, b2 = ME_MAXKEY, b3 = ME_MAXKEY, b4 = ME_MAXKEY, b5 = ME_MAXKEY,
              b6 = ME_MAXKEY, b7 = ME_MAXKEY, b8 = ME_MAXKEY, b9 = ME_MAXKEY;
 
-#if ME_FAIR_PRIO
     prio_state -= n_it << 2;
-#endif
     for (int it = 0; it < n_it; ++it) {
       int cx = x0 + 4 * lx, cy = (it0 + it) * ty + ly;
       if (fold_part && cy == wy) { cx += 128; cy = wy - 1; }   // idle second row of the last iteration: leftover quads of the last row
@@ -780,9 +752,7 @@ me_search16_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-#if ME_FAIR_PRIO
   if (fair_prio) __builtin_amdgcn_s_setprio(3);   // wave priority falls with the wave's progress: me_search_kernel
-#endif
 #ifdef ME_SEARCH_T_TIMELINE
   const unsigned long long tl0 = wall_clock64();
   uint32_t tl[8];
@@ -854,7 +824,6 @@ me_search16_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref
     if (t >= n_tasks) break;
     const int it0 = t;
     constexpr int n_it = 1;
-#if ME_FAIR_PRIO
     // Priority by the WORKGROUP's progress (the pass and the half of its iterations the task counter has reached), the same for its
     // four waves: they meet at a barrier after each pass, and per-wave levels (me_search_kernel's scheme) let the wave that had pulled
     // one iteration more fall behind the others by another -- barrier waits of 100 us instead of 35 (profiles/r05q_search16_timeline.txt)
@@ -865,7 +834,6 @@ me_search16_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref
       else if (lvl == 2) __builtin_amdgcn_s_setprio(1);
       else __builtin_amdgcn_s_setprio(0);
     }
-#endif
     uint32_t b0 = ME_MAXKEY, b1 = ME_MAXKEY, b2 = ME_MAXKEY, b3 = ME_MAXKEY, b4 = ME_MAXKEY, b5 = ME_MAXKEY,
              b6 = ME_MAXKEY, b7 = ME_MAXKEY, b8 = ME_MAXKEY, b9 = ME_MAXKEY;
     for (int it = 0; it < n_it; ++it) {
@@ -1171,41 +1139,13 @@ __global__ void me_prep_jobs_tile_kernel(MeJob16* jobs, int* first_strip_of_job,
 // lanes of a wave add to the same large slot: profiles/r05k_frac_phases_before_after.txt).  A field never carries into the next: the largest sum is the
 // 64x64 slot's, 64 8x8 Hadamard blocks of at most 8 * 64 * 255 / 4 = 32 640 each (Parseval) = 2 088 960 < 2^21; SAD 64 * 64 * 255.
 // Wider samples (and the biased ones of bi-prediction origins) keep nine 32-bit sums.
-#ifndef ME_FRAC_PACK3
-#define ME_FRAC_PACK3 1
-#endif
-constexpr bool frac_pack3(int bps) { return ME_FRAC_PACK3 && bps == 1; }
+constexpr bool frac_pack3(int bps) { return bps == 1; }
 constexpr int frac_acc_row(int bps) { return frac_pack3(bps) ? 6 : 9; }   // dwords per slot
 constexpr int frac_acc_dw(int bps) { return (593 * frac_acc_row(bps) + 15) & ~15; }
 static_assert(64 * 32640 < (1 << 21) && 4096 * 255 < (1 << 21), "me_frac_kernel: a packed sum field holds the largest 8-bit slot sum");
 constexpr int frac_threads(int bps) { return 256; }
 // sums [593][9] | slot states | tap tables, counters | the two work lists | current block | cover table (uint16 [64][18] + [256][6])
-#ifndef ME_FRAC_T_LDS_PAD   // timing-only: LDS bytes a workgroup asks for beyond its need (occupancy experiments)
-#define ME_FRAC_T_LDS_PAD 0
-#endif
-// 8-bit planes: + the patch rows of each lane's NEXT item, written by LDS-DMA while the current item is evaluated (me_frac_stage):
-// 12 rows x 16 B x 256 lanes = 48 KiB.  80 KiB a workgroup, two workgroups a CU -- which is what the kernel's registers allow anyway
-#ifdef ME_FRAC_RIDE_ANY
-#define ME_FRAC_RIDE_LISTED 1
-#else
-#define ME_FRAC_RIDE_LISTED 0
-#endif
-// ME_FRAC_TREE=1: the implicit items of a wave whose positions share one key add their sums over groups of positions, one add per (slot,
-// group), instead of every lane adding to every slot of its position (me_frac_tree_add).  Built and measured in round 6, left OFF:
-// on content whose slots share their motion it took the kernel's LDS bank-conflict cycles from 0.63 to 0.19 of its LDS cycles and its LDS
-// activity from 0.19 to 0.10 of the CU cycles -- and its time from 0.133 to 0.136 ms per 2160p pair, because those conflicts never were what
-// the launch waited for: the exchanges, the packing and the designated lanes' slot arithmetic are 12 % more VALU instructions in a kernel
-// whose time follows its instruction count.  10-bit Hadamard gained 3.6 % (nine 32-bit adds per slot saved instead of three 64-bit ones),
-// but the u16 SAD variants went past 256 VGPRs with it (55..96 spilled dwords).  profiles/r06h_frac_tree_ab.txt
-#ifndef ME_FRAC_TREE
-#define ME_FRAC_TREE 0
-#endif
-#ifndef ME_FRAC_GLDS   // measured: no faster than plain loads on any content (profiles/r05j_frac_glds_ab.txt) -- the items do not wait for their rows
-#define ME_FRAC_GLDS 0
-#endif
-constexpr bool frac_glds(int bps) { return ME_FRAC_GLDS && bps == 1; }
-constexpr int frac_pf_dw(int bps) { return frac_glds(bps) ? 12 * 4 * 256 : 0; }
-constexpr size_t frac_lds_bytes(int bps) { return (size_t)(frac_acc_dw(bps) + 600 + 160 + (64 * 18 + 256 * 6) / 2 + 1024 * bps + (64 * 18 + 256 * 6) / 2 + frac_pf_dw(bps)) * 4 + ME_FRAC_T_LDS_PAD; }
+constexpr size_t frac_lds_bytes(int bps) { return (size_t)(frac_acc_dw(bps) + 600 + 160 + (64 * 18 + 256 * 6) / 2 + 1024 * bps + (64 * 18 + 256 * 6) / 2) * 4; }
 
 __device__ __forceinline__ uint32_t me_mv_cost_q(uint32_t lambda_q16, int vx_q, int vy_q, int pred_x, int pred_y) {
   return (lambda_q16 * (me_component_bits(vx_q - pred_x) + me_component_bits(vy_q - pred_y))) >> 16;
@@ -1347,7 +1287,6 @@ __device__ __forceinline__ uint32_t me_frac_dist(const float (&d)[16], float s1,
   return contrib;
 }
 
-#ifndef ME_FRAC_SCALAR_STAGE1   // A/B: the quarter-pel stage one sample per instruction
 // The Hadamard sum of a 4x4 difference block that arrives as pairs of horizontal neighbours (P[r][h]: row r, columns 2h, 2h + 1), two
 // butterflies per instruction (v_pk_add_f32).  Only the sum of the absolute coefficients is wanted, so the transform runs in natural
 // (Sylvester) order -- the same sixteen Walsh functions as xCalcHADs4x4's, in another order and with other signs: three levels pair
@@ -1404,7 +1343,6 @@ __device__ __forceinline__ uint32_t me_frac_had_pk(const v2f (&P)[4][2], float s
   for (int i = 0; i < 8; ++i) { const float t = me_absmax(z[2 * i], z[2 * i + 1]); sum = i ? sum + t : t; }
   return (uint32_t)sum;   // (2 * sum + 1) >> 1
 }
-#endif
 
 // The evaluation of one work item.  Stage 0 (me_frac_eval0): the nine half-pel points around the integer MV; stage 1 (me_frac_eval1):
 // the eight quarter-pel points around the slot's half-pel winner.  P: patch rows of 3 * BPS dwords, 8-bit samples XORed with 0x80
@@ -1476,18 +1414,10 @@ __device__ __forceinline__ void me_frac_eval1(const uint32_t (&P)[kFracRows1][3 
       for (int r = 0; r < kFracRows1; ++r)
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-#ifndef ME_FRAC_CVT_FIRST_PASS
           int a = me_dot4_magic(P[r][0], T[c][0]);
-#else
-          int a = __builtin_amdgcn_sdot4((int)P[r][0], (int)T[c][0], 0, false);
-#endif
           a = __builtin_amdgcn_sdot4((int)P[r][1], (int)T[c][1], a, false);
           if (c > 0) a = __builtin_amdgcn_sdot4((int)P[r][2], (int)T[c][2], a, false);
-#ifndef ME_FRAC_CVT_FIRST_PASS
           tmp[r][c] = __int_as_float(a) - kRoundMagic;
-#else
-          tmp[r][c] = (float)a;
-#endif
         }
     } else {
       typedef short v2s __attribute__((ext_vector_type(2)));
@@ -1519,7 +1449,6 @@ __device__ __forceinline__ void me_frac_eval1(const uint32_t (&P)[kFracRows1][3 
 #pragma unroll
       for (int j = 0; j < 8; ++j) cv[j] = tab_v[(h3y * 3 + dyi) * kFracTabV + j];
       float d[16];
-#ifndef ME_FRAC_SCALAR_STAGE1   // A/B: the quarter-pel stage one sample per instruction
       v2f dp[4][2];
       if constexpr (!WP) {   // two columns per instruction: v_pk_fma_f32 / v_pk_add_f32
 #pragma unroll
@@ -1540,7 +1469,6 @@ __device__ __forceinline__ void me_frac_eval1(const uint32_t (&P)[kFracRows1][3 
           }
         }
       } else
-#endif
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const float4 org = orgM.row(r);
@@ -1555,11 +1483,7 @@ __device__ __forceinline__ void me_frac_eval1(const uint32_t (&P)[kFracRows1][3 
         }
       }
       uint32_t own4 = 0;
-#ifndef ME_FRAC_SCALAR_STAGE1
       const uint32_t contrib = (HAD && !WP) ? me_frac_had_pk<KIND8>(dp, s1, s2, want4, own4) : me_frac_dist<HAD, KIND8>(d, s1, s2, want4, own4);
-#else
-      const uint32_t contrib = me_frac_dist<HAD, KIND8>(d, s1, s2, want4, own4);
-#endif
       out[idxQ[dyi][dxi]] = contrib;
       out4[idxQ[dyi][dxi]] = own4;
     }
@@ -1603,7 +1527,6 @@ __device__ __forceinline__ void me_frac_eval0(const uint32_t (&P)[12][3 * BPS], 
   const float c64 = 64.f * sc2;
   // first pass of patch row r with the tap window of (quarter offset q, output column c)
   auto first = [&](int r, int q, int c) -> float {
-#ifndef ME_FRAC_CVT_FIRST_PASS
     if constexpr (BPS == 1) {
       int a = 0;
       bool started = false;
@@ -1614,20 +1537,16 @@ __device__ __forceinline__ void me_frac_eval0(const uint32_t (&P)[12][3 * BPS], 
         started = true;
       }
       return __int_as_float(a) - kRoundMagic;
-    }
-#endif
-    int a = off1;
+    } else {
+      typedef short v2s __attribute__((ext_vector_type(2)));
+      int a = off1;
 #pragma unroll
-    for (int k = 0; k < PW; ++k) {
-      if (me_htap_dw<BPS>(q, c, k) == 0) continue;
-      if constexpr (BPS == 1) {
-        a = __builtin_amdgcn_sdot4((int)P[r][k], (int)me_htap_dw<BPS>(q, c, k), a, false);
-      } else {
-        typedef short v2s __attribute__((ext_vector_type(2)));
+      for (int k = 0; k < PW; ++k) {
+        if (me_htap_dw<BPS>(q, c, k) == 0) continue;
         a = __builtin_amdgcn_sdot2(__builtin_bit_cast(v2s, P[r][k]), __builtin_bit_cast(v2s, me_htap_dw<BPS>(q, c, k)), a, false);
       }
+      return (float)(a >> sh1);
     }
-    return (float)(BPS == 1 ? a : a >> sh1);
   };
   auto clipround = [&](float a) -> float {
     const float y = __builtin_amdgcn_fmed3f(a, clip_lo, maxv) + kRoundMagic;
@@ -1672,7 +1591,6 @@ __device__ __forceinline__ void me_frac_eval0(const uint32_t (&P)[12][3 * BPS], 
     ME_FRAC_POINT(yZ, 0, 0, 1, 0) ME_FRAC_POINT(yZ, 0, 1, 1, 2)
   }
   // ---- integer columns
-#ifndef ME_FRAC_CVT_FIRST_PASS
   if constexpr (!WP) {
     // the first pass of an integer column is (64 * p - (8192 << sh1)) >> sh1 = p * 2^(6 - sh1) - 8192: the sample itself goes into the
     // vertical filter (v_cvt_f32_ubyteN of the raw byte / a conversion of the 16-bit half), the taps carry the 2^(6 - sh1) and the
@@ -1710,9 +1628,7 @@ __device__ __forceinline__ void me_frac_eval0(const uint32_t (&P)[12][3 * BPS], 
       for (int r = 0; r < 4; ++r) yZ[r][c] = V0[r + 4][c] + kRoundMagic;
     }
     ME_FRAC_POINT(yG, 0, 0, 0, 1) ME_FRAC_POINT(yG, 1, 0, 2, 1) ME_FRAC_POINT(yZ, 0, 0, 1, 1)
-  } else
-#endif
-  {
+  } else {
     float V0[12][4];
 #pragma unroll
     for (int r = 0; r < 12; ++r)
@@ -1736,155 +1652,6 @@ __device__ __forceinline__ void me_frac_eval0(const uint32_t (&P)[12][3 * BPS], 
 #undef ME_FRAC_POINT
 }
 
-// ---- tree-shaped accumulation of a wave whose sixteen implicit items share ONE key -------------------------------------------------------
-// The per-entry walk (me_frac_compute) adds an item's nine distortions to every slot of its position that shares its key, slot by slot:
-// 64 x 18 + 256 x 6 = 2 688 lane adds per CTU and stage, and because the large slots cover many positions up to sixteen lanes of a
-// wave add to the same LDS address in one instruction (0.63 of the kernel's LDS cycles were bank-conflict cycles on content whose slots
-// share their motion, profiles/r05l_frac_counters_by_content.txt).  Where all sixteen 8x8 positions of a wave -- two position rows, a
-// 64 x 16 strip of the CTU -- carry the same key K, what a slot with key K gets from the wave is the SUM of the values of the strip's
-// positions inside it: sums over aligned groups of positions, formed once with six lane exchanges (A .. G below; a .. f for the slots made
-// of 4x4 blocks), each added by ONE lane of its group -- 744 adds per CTU and stage, no two lanes of an instruction at one address.
-// A slot whose key is not K takes nothing here: its positions are listed items of their own (me_frac_dedupe), as before.
-// Lane bits inside the wave: 0 rx, 1 ry (quadrant), 2 x0, 3 x1, 4 x2 (position column), 5 y0 (position row).  The designated lanes and
-// the slot numbers are tools/frac_tree_model.py's, which checks them against the slot table: every slot is tiled exactly once.
-template <int BPS> struct FracSum;
-template <> struct FracSum<1> { unsigned long long p[3]; };     // three 21-bit fields per word (frac_pack3)
-template <> struct FracSum<2> { uint32_t d[9]; };
-template <int BIT>
-__device__ __forceinline__ uint32_t me_lane_xor_get(uint32_t v) {   // the value of lane (l ^ (1 << BIT)), BIT = 0..3
-  if constexpr (BIT == 0) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, false);        // quad_perm [1,0,3,2]
-  else if constexpr (BIT == 1) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, false);   // quad_perm [2,3,0,1]
-  else if constexpr (BIT == 2) return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x101F);                     // bit mode: and 0x1f, or 0, xor 4
-  else return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xf, 0xf, false);                          // row_ror:8
-}
-template <int BIT>
-__device__ __forceinline__ uint32_t me_lane_xor_sum(uint32_t v) {   // v + the value of lane (l ^ (1 << BIT)), BIT = 0..5
-  if constexpr (BIT == 4) { const u32x2_t r = __builtin_amdgcn_permlane16_swap(v, v, false, false); return r.x + r.y; }
-  else if constexpr (BIT == 5) { const u32x2_t r = __builtin_amdgcn_permlane32_swap(v, v, false, false); return r.x + r.y; }
-  else return v + me_lane_xor_get<BIT>(v);
-}
-template <int BIT>
-__device__ __forceinline__ unsigned long long me_lane_xor_sum(unsigned long long v) {
-  const uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-  if constexpr (BIT == 4) {
-    const u32x2_t a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false), b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    return ((unsigned long long)a.x | (unsigned long long)b.x << 32) + ((unsigned long long)a.y | (unsigned long long)b.y << 32);
-  } else if constexpr (BIT == 5) {
-    const u32x2_t a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false), b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-    return ((unsigned long long)a.x | (unsigned long long)b.x << 32) + ((unsigned long long)a.y | (unsigned long long)b.y << 32);
-  } else {
-    return v + ((unsigned long long)me_lane_xor_get<BIT>(lo) | (unsigned long long)me_lane_xor_get<BIT>(hi) << 32);
-  }
-}
-template <int BIT, int STAGE>
-__device__ __forceinline__ FracSum<1> me_frac_xsum(const FracSum<1>& v) {
-  FracSum<1> r;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) r.p[k] = me_lane_xor_sum<BIT>(v.p[k]);
-  return r;
-}
-template <int BIT, int STAGE>
-__device__ __forceinline__ FracSum<2> me_frac_xsum(const FracSum<2>& v) {
-  FracSum<2> r;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) r.d[i] = i < STAGE ? 0u : me_lane_xor_sum<BIT>(v.d[i]);   // stage 1: point 0 is carried over, nothing adds to it
-  return r;
-}
-template <int STAGE, int BPS>
-__device__ __forceinline__ void me_frac_tree_add(const uint32_t (&dist)[9], const uint32_t (&dist4)[9], bool want4, uint32_t key, const uint32_t* st,
-                                                 uint32_t* acc, int tid) {
-  constexpr uint32_t keymask = STAGE ? kFracKey1 : kFracKey0;
-  // everything below depends on the lane's place alone: without this the compiler computes the designated-lane masks and the slot numbers
-  // once per kernel and keeps them -- 28 SGPRs and 16 VGPRs -- across the item evaluation, which has none to spare (56 B of scratch per lane)
-  asm volatile("" : "+v"(tid));
-  const int role = tid & 3, rx = role & 1, ry = role >> 1, x = (tid >> 2) & 7, y = tid >> 5;
-  const int w = y >> 1, x0 = x & 1, y0 = y & 1, r16 = (y >> 1) * 4 + (x >> 1), r32 = (y >> 2) * 2 + (x >> 2);
-  auto amp_row = [](int r) { return (4 - r) & 3; };        // row (of a CU's four) -> 2NxnU.p0, 2NxnU.p1, 2NxnD.p0, 2NxnD.p1 = sub-families 0, 3, 2, 1
-  auto amp_col = [](int c) { return 4 + ((4 - c) & 3); };  // column -> nLx2N.p0, nLx2N.p1, nRx2N.p0, nRx2N.p1 = 4, 7, 6, 5
-  auto pack = [](const uint32_t (&d)[9]) {
-    FracSum<BPS> v;
-    if constexpr (BPS == 1) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-        v.p[k] = (unsigned long long)(d[3 * k] | d[3 * k + 1] << 21) | (unsigned long long)(d[3 * k + 1] >> 11 | d[3 * k + 2] << 10) << 32;
-    } else {
-#pragma unroll
-      for (int i = 0; i < 9; ++i) v.d[i] = d[i];
-    }
-    return v;
-  };
-  auto put = [&](bool mine, int slot, const FracSum<BPS>& v) {   // the designated lane adds the group's sum if the slot shares the wave's key
-    if (mine && ((st[slot] ^ key) & keymask) == 0) {
-      if constexpr (BPS == 1) {
-        unsigned long long* a = (unsigned long long*)acc + slot * 3;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) atomicAdd(&a[k], v.p[k]);
-      } else {
-#pragma unroll
-        for (int i = STAGE; i < 9; ++i) atomicAdd(&acc[slot * 9 + i], v.d[i]);
-      }
-    }
-  };
-  // ---- slots made of 8x8 blocks: the quad's value (the same in its four lanes)
-  const FracSum<BPS> A = pack(dist);
-  put(role == 0, 384 + y * 8 + x, A);                                                            //  8: 2Nx2N
-  const FracSum<BPS> C = me_frac_xsum<5, STAGE>(A);                                              // 8 x 16
-  put(y0 == 0 && role >= 2, role == 2 ? 480 + (y >> 1) * 8 + x                                   // 16: Nx2N part x & 1
-                                      : 512 + amp_col(x & 3) * 4 + r32, C);                      // 32: the AMP part this column belongs to (alone or as a piece)
-  const FracSum<BPS> B = me_frac_xsum<2, STAGE>(A);                                              // 16 x 8
-  put(x0 == 0 && role == 1, 448 + (y >> 1) * 8 + y0 * 4 + (x >> 1), B);                          // 16: 2NxN part y & 1
-  const FracSum<BPS> E = me_frac_xsum<3, STAGE>(B);                                              // 32 x 8
-  put((x & 3) == 1 && role == 1, 512 + amp_row(y & 3) * 4 + r32, E);                             // 32: the AMP part this position row belongs to
-  const FracSum<BPS> D = me_frac_xsum<5, STAGE>(B);                                              // 16 x 16
-  {
-    const int cx = x >> 1;
-    const int slot = role == 0 ? 544 + r16                                                       // 16: 2Nx2N
-                   : role == 1 ? 568 + (y >> 2) * 4 + 2 * (x >> 2) + (cx & 1)                    // 32: Nx2N part
-                   : role == 2 ? 512 + ((cx & 1) ? 7 : 6) * 4 + r32                              // 32: the two-column piece of nLx2N.p1 / nRx2N.p0
-                               : 576 + amp_col(cx);                                              // 64: the AMP part this 16-column belongs to
-    put(x0 == 1 && y0 == 1, slot, D);
-  }
-  const FracSum<BPS> F = me_frac_xsum<3, STAGE>(D);                                              // 32 x 16
-  {
-    const int slot = role == 0 ? 584 + r32                                                       // 32: 2Nx2N
-                   : role == 1 ? 560 + (y >> 2) * 4 + ((y >> 1) & 1) * 2 + (x >> 2)              // 32: 2NxN part
-                   : role == 2 ? 512 + ((w & 1) ? 3 : 2) * 4 + r32                               // 32: the two-row piece of 2NxnU.p1 / 2NxnD.p0
-                               : 590 + (x >> 2);                                                 // 64: Nx2N part
-    put((x & 3) == 2 && y0 == 0, slot, F);
-    put((x & 3) == 3 && y0 == 0 && role == 0, 576 + ((x >> 2) ? 7 : 6), F);                     // 64: the 32-column piece of nLx2N.p1 / nRx2N.p0
-  }
-  const FracSum<BPS> G = me_frac_xsum<4, STAGE>(F);                                              // 64 x 16: the wave's strip
-  {
-    const int slot = role == 0 ? 592 : role == 1 ? 588 + (w >> 1) : role == 2 ? 576 + (w == 0 ? 0 : 3) : 576 + (w == 3 ? 1 : 2);
-    put(x == 7 && y0 == 1, slot, G);
-  }
-  // ---- slots made of 4x4 blocks: the lane's own 4x4 value
-  if (want4) {   // wave-uniform
-    const FracSum<BPS> u = pack(dist4);
-    const FracSum<BPS> a = me_frac_xsum<0, STAGE>(u), b = me_frac_xsum<1, STAGE>(u);             // 8 x 4, 4 x 8
-    {
-      FracSum<BPS> ab;   // element by element: a select between the two structs goes through the stack (56 B of scratch per lane)
-      if constexpr (BPS == 1) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) ab.p[k] = rx == ry ? a.p[k] : b.p[k];
-      } else {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) ab.d[i] = rx == ry ? a.d[i] : b.d[i];
-      }
-      put(true, rx == ry ? y * 16 + ry * 8 + x : 128 + y * 16 + 2 * x + rx, ab);
-    }
-    const int r = 2 * y0 + ry, c = 2 * x0 + rx;                                                  // 4x4 row / column inside the 16x16 CU
-    const FracSum<BPS> cs = me_frac_xsum<2, STAGE>(a);                                           // 16 x 4
-    put(rx == 0 && x0 == 1, 256 + amp_row(r) * 16 + r16, cs);
-    const FracSum<BPS> ds = me_frac_xsum<5, STAGE>(b);                                           // 4 x 16
-    put(ry == 1 && y0 == 1, 256 + amp_col(c) * 16 + r16, ds);
-    const FracSum<BPS> es = me_frac_xsum<1, STAGE>(cs);                                          // 16 x 8: rows 2,3 of 2NxnU.p1 / rows 0,1 of 2NxnD.p0
-    put(rx == 1 && ry == 1 && x0 == 0, 256 + (y0 ? 3 : 2) * 16 + r16, es);
-    const FracSum<BPS> fs = me_frac_xsum<0, STAGE>(ds);                                          // 8 x 16: columns 2,3 of nLx2N.p1 / columns 0,1 of nRx2N.p0
-    put(rx == 1 && ry == 0 && y0 == 0, 256 + (x0 ? 7 : 6) * 16 + r16, fs);
-  }
-}
-
 // One work item = one 4x4 block of one (position, MV) pair; `pair` indexes the cover table (kind-8 pairs first), `role` is the lane's
 // quadrant of an 8x8 Hadamard block.  An item is handled in two steps:
 //   me_frac_fetch    slot state + address -> 12 raw rows of PW + 1 aligned dwords each (global_load_dwordx4 / x3), nothing waited for
@@ -1895,49 +1662,6 @@ struct FracRaw {
   uint32_t sv;      // state word of the item's first slot (the sharing key of the stage)
   uint32_t o;       // byte offset of the patch inside its first dword
 };
-
-// LDS-DMA form of me_frac_fetch (8-bit planes): the rows of the item go from the plane straight into the wave's LDS block
-// (global_load_lds_dwordx4: lane l's 16 bytes of row r land at block + r * 1 KiB + l * 16), no register holds them while they travel.
-// Returns what me_frac_take needs beside the rows: the item's state word and the byte offset of the patch inside its first dword.
-typedef __attribute__((address_space(3))) uint32_t lds_u32_t;
-template <int STAGE, int KIND8>
-__device__ __forceinline__ uint32_t me_frac_prefetch(const uint8_t* __restrict__ src, int gpitch, const uint32_t* st, const uint16_t* cover, int pair, int role,
-                                                     uint32_t* pf_wave) {
-  constexpr int NCOV = KIND8 ? kFracCover8 : kFracCover4;
-  const int q = KIND8 ? pair : pair - kFracPairs8;
-  const int pos = q / NCOV;
-  const uint32_t sv = st[cover[pair]];
-  const int bx = KIND8 ? 2 * (pos & 7) + (role & 1) : (pos & 15), by = KIND8 ? 2 * (pos >> 3) + (role >> 1) : (pos >> 4);
-  const int skip_x = STAGE ? 4 + me_win8_first((int)((sv >> 18) & 3)) : 0, skip_y = STAGE ? 4 + me_win8_first((int)((sv >> 20) & 3)) : 0;
-  const int prow = by * 4 + (int)((sv >> 9) & 0x1ff) + skip_y, pcol = bx * 4 + (int)(sv & 0x1ff) + skip_x;
-  const uint8_t* a = src + (long)prow * gpitch + pcol;
-  const uint32_t o = (uint32_t)(uintptr_t)a & 3u;
-  const uint8_t* rowp = a - o;
-  constexpr int ROWS = STAGE ? kFracRows1 : 12;
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r)
-    __builtin_amdgcn_global_load_lds((const void*)(rowp + (long)r * gpitch), (lds_u32_t*)(pf_wave + r * 256), 16, 0, 0);
-  return (sv & kFracKey1) | o << 30;
-}
-// the rows of the item me_frac_prefetch asked for, out of the wave's LDS block into registers; returns once they are THERE, so the block
-// may be overwritten by the next request
-template <int STAGE>
-__device__ __forceinline__ void me_frac_take(const uint32_t* pf_wave, int lane, uint32_t meta, FracRaw<1>& R) {
-  constexpr int ROWS = STAGE ? kFracRows1 : 12;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // LDS-DMA completion is counted with the vector-memory operations
-#pragma unroll
-  for (int r = 0; r < 12; ++r) {
-    if (r < ROWS) {
-      const uint4 v = *(const uint4*)(pf_wave + r * 256 + lane * 4);
-      R.w[r][0] = v.x; R.w[r][1] = v.y; R.w[r][2] = v.z; R.w[r][3] = v.w;
-    } else {
-      R.w[r][0] = R.w[r][1] = R.w[r][2] = R.w[r][3] = 0u;
-    }
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  R.sv = meta & kFracKey1;
-  R.o = meta >> 30;
-}
 
 template <int STAGE, int BPS, int KIND8>
 __device__ __forceinline__ void me_frac_fetch(const uint8_t* __restrict__ src, int gpitch, const uint32_t* st, const uint16_t* cover, int pair, int role,
@@ -2014,18 +1738,6 @@ __device__ __forceinline__ void me_frac_compute(const FracRaw<BPS>& R, const uin
     if constexpr (STAGE == 0) me_frac_eval0<HAD, BPS, KIND8, WP>(P, org, role, bd, clip_lo, want4, wp, dist, dist4);
     else me_frac_eval1<HAD, BPS, KIND8, WP>(P, org, (int)((sv >> 18) & 3), (int)((sv >> 20) & 3), role, bd, clip_lo, tab_h, tab_v, want4, wp, dist, dist4);
   }
-#ifndef ME_FRAC_T_NOATOMICS   // timing-only builds (tools/r04_frac_breakdown.sh; results are wrong by design): ME_FRAC_T_NOATOMICS, ME_FRAC_T_NOITEMS
-#if ME_FRAC_TREE && !ME_FRAC_RIDE_LISTED   // (with riders on listed items `ride` no longer means "the implicit item")
-  if constexpr (KIND8) {
-    // the implicit items (lane tid = position tid >> 2, quadrant tid & 3) of a wave whose sixteen positions share one key: sums over
-    // groups of positions, one add per (slot, group)
-    static_assert(BPS == 2 || frac_pack3(1), "me_frac_tree_add adds the packed sums of 8-bit planes");
-    if (ride && __all(((sv ^ (uint32_t)__builtin_amdgcn_readfirstlane((int)sv)) & keymask) == 0)) {
-      me_frac_tree_add<STAGE, BPS>(dist, dist4, want4, sv, st, acc, pos * 4 + role);
-      return;
-    }
-  }
-#endif
   // the nine (stage 1: eight, point 0 is carried over, not evaluated -- its distortion here is 0) distortions as they are added to a slot
   unsigned long long pk[3], pk4[3];
   if constexpr (frac_pack3(BPS)) {
@@ -2071,14 +1783,6 @@ __device__ __forceinline__ void me_frac_compute(const FracRaw<BPS>& R, const uin
       if (j2 < NCOV && (j2 == j || ((k2[k] ^ sv) & keymask) == 0)) add_to(s2[k], dist, pk);
     }
   }
-#else   // every distortion still computed, ONE atomic per item: the difference to the product build is what the accumulation costs
-  {
-    uint32_t t = 0;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) t += dist[i] + (KIND8 ? dist4[i] & match4 : 0u);
-    atomicAdd(&acc[(cov[j] * frac_acc_row(BPS) + (t & 3)) % (593 * frac_acc_row(BPS))], t);
-  }
-#endif
 }
 
 // distinct (position, key) pairs of one stage -> work lists; the first slot (lowest index in the cover list) with a given key is the one
@@ -2127,14 +1831,6 @@ __device__ __forceinline__ void me_frac_dedupe4(const uint32_t* st, const uint16
 #pragma unroll
     for (int k = 0; k < j; ++k) first[j] = first[j] && key[k] != key[j];
   }
-#ifdef ME_FRAC_RIDE_ANY   // A/B: riders on listed kind-8 items too (round 4 / early round 5)
-#pragma unroll
-  for (int k = 1; k < kFracCover8; ++k) {
-    const uint32_t k8 = st[cov8[k]] & keymask;
-#pragma unroll
-    for (int j = 0; j < kFracCover4; ++j) first[j] = first[j] && key[j] != k8;
-  }
-#endif
 #pragma unroll
   for (int j = 0; j < kFracCover4; ++j)
     if (first[j]) list[atomicAdd(counter, 1u)] = (uint16_t)(kFracPairs8 + p4 * kFracCover4 + j);
@@ -2168,101 +1864,39 @@ __device__ __forceinline__ void me_frac_stage(const uint8_t* __restrict__ src, i
     }
     me_frac_dedupe4(st, cover, tid, keymask, &counter[1], list4);
   };
-  if constexpr (frac_glds(BPS)) {
-    // 8-bit planes: a lane's NEXT item is requested (LDS-DMA into the wave's block of `pf`) before the current one is evaluated -- the
-    // registers that would have to hold rows in flight do not exist here (round 4's register-pipelined walk was slower on every
-    // content), an LDS block nobody else wants does: the kernel's registers allow two workgroups a CU, which leaves each 80 KiB.
-    uint32_t* pf_wave = pf + (tid >> 6) * (12 * 256);
-    const int lane = tid & 63;
+  // (the listed items in chunks of 64 lanes drawn from a counter by the four waves were measured too: no better than this static walk
+  // on mixed content, 1 % worse on unrelated pictures, and 14-46 spilled dwords in the u16 kernels)
+  int n8 = 0;
+#pragma unroll 1
+  for (int i8 = tid - NT;; i8 += NT) {   // first turn (i8 < 0 in every lane): the implicit item
     int pair = (tid >> 2) * kFracCover8;
-    uint32_t meta = me_frac_prefetch<STAGE, 1>(src, gpitch, st, cover, pair, role, pf_wave);
-    lists();
-    __syncthreads();   // the work lists are complete (the rows asked for have landed as well: the barrier's fence waits for them)
-#if ME_FRAC_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
-    const int n8 = 4 * (int)counter[0], n4 = (int)counter[1];
-    int i8 = tid - NT;
-#pragma unroll 1
-    for (;;) {
-      FracRaw<BPS> R;
-      me_frac_take<STAGE>(pf_wave, lane, meta, R);
-      const int cur = pair;
-      i8 += NT;
-      const bool more = i8 < n8;
-      if (more) {
-        pair = list8[i8 >> 2];
-        meta = me_frac_prefetch<STAGE, 1>(src, gpitch, st, cover, pair, role, pf_wave);
-      }
-#ifndef ME_FRAC_T_NOITEMS
-      me_frac_compute<STAGE, HAD, BPS, 1, WP>(R, curl, st, cover, cur, role, bd, clip_lo, wp, tab_h, tab_v, acc, ME_FRAC_RIDE_LISTED || i8 < NT);
-#endif
-      if (!more) break;
+    if (i8 >= 0) {
+      if (i8 >= n8) break;
+      pair = list8[i8 >> 2];
     }
-    int i4 = tid;
-    if (i4 < n4) {
-      pair = list4[i4];
-      meta = me_frac_prefetch<STAGE, 0>(src, gpitch, st, cover, pair, 0, pf_wave);
-#pragma unroll 1
-      for (;;) {
-        FracRaw<BPS> R;
-        me_frac_take<STAGE>(pf_wave, lane, meta, R);
-        const int cur = pair;
-        i4 += NT;
-        const bool more = i4 < n4;
-        if (more) {
-          pair = list4[i4];
-          meta = me_frac_prefetch<STAGE, 0>(src, gpitch, st, cover, pair, 0, pf_wave);
-        }
-#ifndef ME_FRAC_T_NOITEMS
-        me_frac_compute<STAGE, HAD, BPS, 0, WP>(R, curl, st, cover, cur, 0, bd, clip_lo, wp, tab_h, tab_v, acc, false);
-#endif
-        if (!more) break;
-      }
+    FracRaw<BPS> R;
+    me_frac_fetch<STAGE, BPS, 1>(src, gpitch, st, cover, pair, role, R);
+    if (i8 < 0) {   // the work lists, while the implicit item's rows are on their way
+      lists();
+      __builtin_amdgcn_s_setprio(0);
     }
-  } else {
-    // (the listed items in chunks of 64 lanes drawn from a counter by the four waves were measured too: no better than this static walk
-    // on mixed content, 1 % worse on unrelated pictures, and 14-46 spilled dwords in the u16 kernels)
-    int n8 = 0;
-#pragma unroll 1
-    for (int i8 = tid - NT;; i8 += NT) {   // first turn (i8 < 0 in every lane): the implicit item
-      int pair = (tid >> 2) * kFracCover8;
-      if (i8 >= 0) {
-        if (i8 >= n8) break;
-        pair = list8[i8 >> 2];
-      }
-      FracRaw<BPS> R;
-      me_frac_fetch<STAGE, BPS, 1>(src, gpitch, st, cover, pair, role, R);
-      if (i8 < 0) {   // the work lists, while the implicit item's rows are on their way
-        lists();
-#if ME_FRAC_PRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
-      }
-#ifndef ME_FRAC_T_NOITEMS
-      me_frac_compute<STAGE, HAD, BPS, 1, WP>(R, curl, st, cover, pair, role, bd, clip_lo, wp, tab_h, tab_v, acc, ME_FRAC_RIDE_LISTED || i8 < 0);
-#endif
-      if (i8 < 0) {
-        __syncthreads();   // the work lists are complete
-        n8 = 4 * (int)counter[0];
-      }
+    me_frac_compute<STAGE, HAD, BPS, 1, WP>(R, curl, st, cover, pair, role, bd, clip_lo, wp, tab_h, tab_v, acc, i8 < 0);
+    if (i8 < 0) {
+      __syncthreads();   // the work lists are complete
+      n8 = 4 * (int)counter[0];
     }
-    const int n4 = (int)counter[1];
-#ifndef ME_FRAC_T_NOITEMS
-    // (dealt from the last thread down: the partly filled last turn of the kind-8 walk above falls on the first waves, this one's on
-    // the last -- the waves reach the barrier that ends the stage closer together)
-#pragma unroll 1
-    for (int i4 = NT - 1 - tid; i4 < n4; i4 += NT) {
-      const int pair = list4[i4];
-      FracRaw<BPS> R;
-      me_frac_fetch<STAGE, BPS, 0>(src, gpitch, st, cover, pair, 0, R);
-      me_frac_compute<STAGE, HAD, BPS, 0, WP>(R, curl, st, cover, pair, 0, bd, clip_lo, wp, tab_h, tab_v, acc, false);
-    }
-#endif
   }
-#if ME_FRAC_PRIO
+  const int n4 = (int)counter[1];
+  // (dealt from the last thread down: the partly filled last turn of the kind-8 walk above falls on the first waves, this one's on
+  // the last -- the waves reach the barrier that ends the stage closer together)
+#pragma unroll 1
+  for (int i4 = NT - 1 - tid; i4 < n4; i4 += NT) {
+    const int pair = list4[i4];
+    FracRaw<BPS> R;
+    me_frac_fetch<STAGE, BPS, 0>(src, gpitch, st, cover, pair, 0, R);
+    me_frac_compute<STAGE, HAD, BPS, 0, WP>(R, curl, st, cover, pair, 0, bd, clip_lo, wp, tab_h, tab_v, acc, false);
+  }
   __builtin_amdgcn_s_setprio(3);
-#endif
 }
 
 // Which job the k-th workgroup (or the k-th draw from the job counter) takes.  A launch ends one job time after its last job STARTS, and
@@ -2318,18 +1952,17 @@ me_frac_kernel(const RefSet curs, int cur_pitch, const RefSet refs, int ref_pitc
   uint16_t* list4 = (uint16_t*)(tab_h + 160 + kFracPairs8 / 2);   // distinct (4x4 position, key) pairs
   uint32_t* curl = tab_h + 160 + (kFracPairs8 + kFracPairs4) / 2;   // 64 x 64 current block
   uint16_t* cover = (uint16_t*)(curl + 1024 * BPS);   // the cover table (uint16 [64][18] then [256][6]): read per item and per dedupe, so it lives here
-  uint32_t* pf = (uint32_t*)(cover + kFracPairs8 + kFracPairs4);   // 8-bit planes: [4 waves][12 rows][64 lanes][16 B] patch rows in flight (me_frac_stage)
+  uint32_t* pf = (uint32_t*)(cover + kFracPairs8 + kFracPairs4);   // unused since the patch-row prefetch was removed (dropping it renames IR labels
+                                                                   // in build/*.s: left for a change of its own)
 
   const int tid = threadIdx.x;
   const int bd = BPS == 1 ? 8 : bit_depth;
-#if ME_FRAC_PRIO
   // The short phases of a job -- set-up, work lists, winners: chains of dependent LDS round trips and compares, a few hundred
   // instructions -- run at wave priority 3, the items (thousands of VALU instructions per lane, no waiting) at 0.  A SIMD issues from its
   // oldest ready wave: next to another workgroup's items a short phase got the issue slots those left over and took five times its
   // stand-alone time, half of a job on content whose slots share their motion.  With the priorities the short phases run at their own
   // latency and the items fill every slot they leave, which is nearly all of them.
   __builtin_amdgcn_s_setprio(3);
-#endif
   // tables that do not depend on the job
   static_assert(9 * (kFracTabH + kFracTabV) <= 152, "me_frac_kernel: the tap tables end where the list counters start");
   if (tid < 9 * kFracTabH) tab_h[tid] = (tid & 7) < 2 * BPS ? me_htap8_dw<BPS>((tid >> 3) / 3, (tid >> 3) % 3, tid & 7) : 0u;
@@ -2352,11 +1985,7 @@ me_frac_kernel(const RefSet curs, int cur_pitch, const RefSet refs, int ref_pitc
     deal = (int)*next_job;
   }
   if (deal >= n_jobs || deal < 0) break;
-#ifndef ME_FRAC_FORWARD
   const int jb = me_frac_deal(deal, n_jobs, prep);
-#else
-  const int jb = deal;
-#endif
 #ifdef ME_FRAC_T_TIMELINE   // timing-only build: when does each job start and end (100 MHz wall clock), in which workgroup, and its phases
   const unsigned long long t_job0 = wall_clock64();
   const unsigned long long c_job0 = clock64();   // shader clock: cycles / wall time = the clock the job ran at
