@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -136,6 +137,11 @@ struct hmme_ctx {
   int16_t* d_qmv = nullptr;
   uint32_t* d_fcost = nullptr;
   size_t refine_cap = 0;
+  // weighted whole-picture calls (hmme_search_pairs_w_device / hmme_refine_pairs_w_device): u16 copies of the planes of one launch, one
+  // per pair, grown on demand -- [0] weighted reference planes and [1] biased CTU-blocked current pictures (search); [2] raw reference
+  // planes widened from 8 bit and [3] biased padded current pictures (refinement).  Scratch like the job tables: scratch_acquire / launch_end
+  uint8_t* d_wp[4] = {nullptr, nullptr, nullptr, nullptr};
+  size_t wp_cap[4] = {0, 0, 0, 0};
 };
 
 struct hmme_plane {
@@ -526,6 +532,7 @@ void hmme_destroy(hmme_ctx* ctx) {
   hipFree(ctx->d_jobs); hipFree(ctx->d_frac_jobs); hipFree(ctx->d_first_strip); hipFree(ctx->d_best);
   hipFree(ctx->d_pred); hipFree(ctx->d_mv); hipFree(ctx->d_sad); hipFree(ctx->d_flag);
   hipFree(ctx->d_wwin); hipFree(ctx->d_frac_cover); hipFree(ctx->d_imv); hipFree(ctx->d_qmv); hipFree(ctx->d_fcost);
+  for (int i = 0; i < 4; ++i) hipFree(ctx->d_wp[i]);
   if (ctx->h_call) hipHostFree(ctx->h_call);
   if (ctx->h_res) hipHostFree(ctx->h_res);
   delete ctx;
@@ -1110,6 +1117,7 @@ struct FramePlan {
   int tail_wgs = 0;        // 8-bit: workgroups (= segments) of the tail
   bool one_launch = true;  // 8-bit with a tail: head and tail in one segment launch (else the head whole, then the tail's segments: HMME_TAIL_LAUNCHES=2)
   bool tile8 = false;
+  bool wide = false;       // the 16-bit kernel runs the launch: planes of more than 8 bits, or the u16 copies of a weighted search
   int n_wg16 = 0;          // 16-bit: workgroups of the launch
   size_t tail_jobs_off = 0;   // (8-bit segment launches: the table, me_seg_table_*, starts at ctx->d_jobs)
 };
@@ -1160,8 +1168,9 @@ static bool tail_one_launch(int head, int n_tail, int launches_knob) { return la
 // builds the device job table of a picture search against n_refs reference pictures on `s`; job index =
 // ref * count + ctu.  8-bit: MeJob[head jobs] (+ MeJob16[tail jobs * parts]); 8-bit tiled / 16-bit: MeJob16[workgroups]
 static int prep_jobs(hmme_ctx* ctx, const hmme_plane* cur, const hmme_frame_params* fp, const void* d_pred_q, int first, int count,
-                     int n_refs, hipStream_t s, FramePlan* pl) {
-  const bool wide = fp->bit_depth > 8;
+                     int n_refs, hipStream_t s, FramePlan* pl, bool force16 = false) {
+  const bool wide = fp->bit_depth > 8 || force16;   // force16: a weighted search of 8-bit planes (its u16 copies)
+  pl->wide = wide;
   const int jobs = count * n_refs, slots = ctx->wg_slots, w = 2 * fp->search_range + 1;
   pl->jobs = jobs;
   pl->pdw = pick_pdw16(w);
@@ -1226,7 +1235,7 @@ static int prep_jobs(hmme_ctx* ctx, const hmme_plane* cur, const hmme_frame_para
   }
   hmme_ctx::TableTag tag;
   tag.valid = !d_pred_q;
-  tag.w = cur->width; tag.h = cur->height; tag.bit_depth = fp->bit_depth; tag.sr = fp->search_range; tag.first = first; tag.count = count; tag.pairs = n_refs;
+  tag.w = cur->width; tag.h = cur->height; tag.bit_depth = fp->bit_depth | (wide && fp->bit_depth == 8 ? 0x100 : 0); tag.sr = fp->search_range; tag.first = first; tag.count = count; tag.pairs = n_refs;
   tag.buf = ctx->d_jobs; tag.buf2 = (wide || pl->tile8 || n_tail) ? ctx->d_first_strip : nullptr; tag.stream = (void*)s;
   if (tag.same(ctx->jobs_tag)) return HMME_OK;   // the table of the launch before is this launch's table
   ctx->jobs_tag.valid = false;
@@ -1263,7 +1272,7 @@ static int prep_jobs(hmme_ctx* ctx, const hmme_plane* cur, const hmme_frame_para
 // curs: the CTU-blocked copies of the current pictures (hmme_plane::d_blocks), cur_ctus_x their blocks per block row
 static int run_search(hmme_ctx* ctx, const RefSet& curs, int cur_ctus_x, const RefSet& refs, int ref_pitch, const hmme_frame_params* fp, const FramePlan& pl,
                       int16_t* d_mv, uint32_t* d_sad, hipStream_t s) {
-  if (fp->bit_depth > 8)
+  if (pl.wide)
     return launch_search16(ctx, curs, cur_ctus_x, refs, ref_pitch, (const MeJob16*)ctx->d_jobs, ctx->d_first_strip, pl.jobs, pl.n_wg16,
                            pl.pdw, pl.strip_rows, fp->fen, fp->bit_depth, d_mv, d_sad, s);
   if (pl.tile8)
@@ -1485,6 +1494,18 @@ int hmme_refine_frame_multi_device(hmme_ctx* ctx, const hmme_plane* cur, const h
   return hmme_refine_pairs_device(ctx, curs, refs, n_refs, fp, d_pred_q, d_int_mv, use_hadamard, d_out_qmv, d_out_cost, stream);
 }
 
+// host-facing refinement calls: device staging for the integer MVs, quarter-pel MVs and costs of `slots` (CTU, slot) entries
+static int ensure_refine_buffers(hmme_ctx* ctx, size_t slots) {
+  if (ctx->refine_cap >= slots) return HMME_OK;
+  hipFree(ctx->d_imv); hipFree(ctx->d_qmv); hipFree(ctx->d_fcost);
+  ctx->d_imv = nullptr; ctx->d_qmv = nullptr; ctx->d_fcost = nullptr; ctx->refine_cap = 0;
+  HIP_TRY(ctx, hipMalloc(&ctx->d_imv, sizeof(int16_t) * 2 * slots));
+  HIP_TRY(ctx, hipMalloc(&ctx->d_qmv, sizeof(int16_t) * 2 * slots));
+  HIP_TRY(ctx, hipMalloc(&ctx->d_fcost, sizeof(uint32_t) * slots));
+  ctx->refine_cap = slots;
+  return HMME_OK;
+}
+
 int hmme_refine_frame(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_frame_params* fp, const int16_t* pred_q,
                       const int16_t* int_mv, int use_hadamard, int16_t* out_qmv, uint32_t* out_cost) {
   int first, count;
@@ -1495,14 +1516,8 @@ int hmme_refine_frame(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* re
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int n_ctu = hmme_num_ctus(cur->width, cur->height);
   const size_t slots = (size_t)HMME_NUM_CTU_PARTS * n_ctu;
-  if (ctx->refine_cap < slots) {
-    hipFree(ctx->d_imv); hipFree(ctx->d_qmv); hipFree(ctx->d_fcost);
-    ctx->d_imv = nullptr; ctx->d_qmv = nullptr; ctx->d_fcost = nullptr; ctx->refine_cap = 0;
-    HIP_TRY(ctx, hipMalloc(&ctx->d_imv, sizeof(int16_t) * 2 * slots));
-    HIP_TRY(ctx, hipMalloc(&ctx->d_qmv, sizeof(int16_t) * 2 * slots));
-    HIP_TRY(ctx, hipMalloc(&ctx->d_fcost, sizeof(uint32_t) * slots));
-    ctx->refine_cap = slots;
-  }
+  rc = ensure_refine_buffers(ctx, slots);
+  if (rc) return rc;
   rc = ensure_frame_buffers(ctx, (size_t)n_ctu);   // the predictors travel in the search path's staging buffer
   if (rc) return rc;
   hipStream_t s = ctx->stream;
@@ -1516,6 +1531,344 @@ int hmme_refine_frame(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* re
   HIP_TRY(ctx, hipMemcpyAsync(out_cost, ctx->d_fcost, sizeof(uint32_t) * res, hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipStreamSynchronize(s));
   return HMME_OK;
+}
+
+// ---- explicit weighted prediction on whole pictures -----------------------------------------------------------
+// The picture-level siblings of hmme_search_ctu_w / hmme_refine_ctu_w.  A pair's reference plane is weighted ONCE, margins included, into
+// a u16 plane of the context's scratch (me_weight_plane_kernel); its current picture's CTU-blocked copy is widened / biased into a u16
+// copy where it has to be (8-bit planes, or a weight whose samples go negative); me_search16_kernel<0, PDW> then runs over them through
+// the same job tables, strips and tails as a search of u16 planes.  The refinement interpolates the RAW reference (widened to u16 from
+// an 8-bit plane) and weights the clipped prediction per sample: me_frac_kernel<HAD, 2, 1>, one launch per run of equal weights.
+namespace {
+struct WpInfo { int bias = 0; bool identity = false; };
+
+// what ctu_call decides from the samples it scans, decided from the nominal range [0, 2^bitDepth - 1] of both pictures
+int weight_eval(int bit_depth, const hmme_weight* wp, int refine, WpInfo* info, char* msg, size_t n) {
+  msg[0] = 0;
+  if (!wp) { snprintf(msg, n, "null weight"); return HMME_ERR_ARG; }
+  if (wp->shift < 0 || wp->shift > 15) { snprintf(msg, n, "weighted prediction: shift %d outside 0..15", wp->shift); return HMME_ERR_ARG; }
+  if (bit_depth < 8 || bit_depth > 12) { snprintf(msg, n, "bit depth %d outside 8..12", bit_depth); return HMME_ERR_UNSUPPORTED; }
+  const bool identity = wp->w0 == (1 << wp->shift) && wp->offset == 0 && wp->round == (wp->shift ? 1 << (wp->shift - 1) : 0);
+  const long maxv = (1L << bit_depth) - 1;
+  const long p0 = wp->round, p1 = (long)wp->w0 * maxv + wp->round;   // w0 * ref + round at the two ends of the range (monotonic between)
+  // HM forms it in an Int and the device in 32 bits: beyond that nothing is defined
+  if (std::min(p0, p1) < INT32_MIN || std::max(p0, p1) > INT32_MAX) {
+    snprintf(msg, n, "weighted prediction: w0 * sample + round reaches %ld..%ld, beyond 32 bits", std::min(p0, p1), std::max(p0, p1));
+    return HMME_ERR_UNSUPPORTED;
+  }
+  const long a = (p0 >> wp->shift) + wp->offset, b = (p1 >> wp->shift) + wp->offset;
+  const long wlo = std::min(a, b), whi = std::max(a, b);
+  if (wlo < -32768 || whi > 32767) { snprintf(msg, n, "weighted prediction reaches %ld..%ld, beyond a Pel", wlo, whi); return HMME_ERR_UNSUPPORTED; }
+  const long bias = wlo < 0 ? -wlo : 0;   // the block's lowest nominal sample is 0
+  if (std::max(whi, maxv) + bias > 65535) { snprintf(msg, n, "weighted prediction: samples span more than 16 bits"); return HMME_ERR_UNSUPPORTED; }
+  const long span = std::max(maxv - wlo, whi);   // largest |block - weighted sample| the two ranges admit
+  if (((4096 * span) >> (bit_depth - 8)) + 65535 >= (long)hmme::kInvCost16) {
+    snprintf(msg, n, "weighted SADs of a %d-bit block could reach %ld: beyond the cost field", bit_depth, 4096 * span);
+    return HMME_ERR_UNSUPPORTED;
+  }
+  if (refine) {
+    if (4096 * span >= (1L << 24)) {
+      snprintf(msg, n, "weighted refinement: sample differences up to %ld exceed what the Hadamard sums hold exactly", span);
+      return HMME_ERR_UNSUPPORTED;
+    }
+    // me_frac_eval*: fma(w0 * 2^-shift, p, round * 2^-shift) is (w0 * p + round) / 2^shift exactly while the numerator stays below 2^24
+    // (identity weights never meet it: they run the unweighted kernel)
+    if (!identity && std::max(std::labs(p0), std::labs(p1)) >= (1L << 24)) {
+      snprintf(msg, n, "weighted refinement: w0 * sample + round reaches %ld, beyond what fp32 holds exactly", std::max(std::labs(p0), std::labs(p1)));
+      return HMME_ERR_UNSUPPORTED;
+    }
+  }
+  if (info) { info->bias = (int)bias; info->identity = identity; }
+  return HMME_OK;
+}
+
+// every pair's weight before anything is launched; the message names the pair
+int check_weights(hmme_ctx* ctx, const char* who, const hmme_frame_params* fp, const hmme_weight* wps, int n_pairs, int refine, WpInfo* info, bool* all_identity) {
+  if (!fp) return fail(ctx, HMME_ERR_ARG, "%s: null params", who);
+  if (!wps) return fail(ctx, HMME_ERR_ARG, "%s: null weights", who);
+  if (n_pairs < 1 || n_pairs > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%d picture pairs outside 1..%d", n_pairs, hmme::kMaxRefs);
+  *all_identity = true;
+  char msg[256];
+  for (int r = 0; r < n_pairs; ++r) {
+    const int rc = weight_eval(fp->bit_depth, &wps[r], refine, &info[r], msg, sizeof msg);
+    if (rc) return fail(ctx, rc, "%s: pair %d: %s", who, r, msg);
+    *all_identity = *all_identity && info[r].identity;
+  }
+  return HMME_OK;
+}
+inline bool same_weight(const hmme_weight& a, const hmme_weight& b) { return a.w0 == b.w0 && a.offset == b.offset && a.shift == b.shift && a.round == b.round; }
+
+// geometry of the u16 copies of a launch's planes
+struct WpGeom {
+  int pitch = 0, rows = 0;
+  size_t plane_bytes = 0, origin = 0, blk_bytes = 0;
+  explicit WpGeom(const hmme_plane* pl) {
+    pitch = ((pl->width + 2 * kMarginX) * 2 + 255) & ~255;   // the pitch of a u16 plane of this size (hmme_plane_create_ex)
+    rows = pl->rows;
+    plane_bytes = (size_t)pitch * (rows + 1);
+    origin = (size_t)kMarginY * pitch + (size_t)kMarginX * 2;
+    blk_bytes = (size_t)pl->n_ctu * hmme::kBlkBytes16;
+  }
+};
+
+// rows x cols samples (u8 or u16) -> u16, ((w0 * v + round) >> shift) + offset_bias each
+int weight_pass(hmme_ctx* ctx, int src_bps, const uint8_t* src, int src_pitch, uint8_t* dst, int dst_pitch, long cols, int rows,
+                int w0, int round, int shift, int offset_bias, hipStream_t s) {
+  const long lanes = cols / (src_bps == 1 ? 16 : 8);   // cols is a multiple of 16 (plane pitches are multiples of 256 bytes, a block is 4096 samples)
+  const dim3 grid((unsigned)((lanes + 255) / 256), (unsigned)rows);
+  if (src_bps == 1)
+    hipLaunchKernelGGL(hmme::me_weight_plane_kernel<uint8_t>, grid, dim3(256), 0, s, src, src_pitch, dst, dst_pitch, (int)cols, w0, round, shift, offset_bias);
+  else
+    hipLaunchKernelGGL(hmme::me_weight_plane_kernel<uint16_t>, grid, dim3(256), 0, s, src, src_pitch, dst, dst_pitch, (int)cols, w0, round, shift, offset_bias);
+  HIP_TRY(ctx, hipGetLastError());
+  return HMME_OK;
+}
+// a whole padded plane (margins included) into the u16 plane `dst` of geometry g
+int weight_plane(hmme_ctx* ctx, const hmme_plane* pl, const WpGeom& g, uint8_t* dst, int w0, int round, int shift, int offset_bias, hipStream_t s) {
+  return weight_pass(ctx, pl->bps, pl->d_data, pl->pitch, dst, g.pitch, g.pitch / 2, g.rows, w0, round, shift, offset_bias, s);
+}
+// a plane's CTU-blocked copy into u16 blocks, `bias` added
+int bias_blocks(hmme_ctx* ctx, const hmme_plane* pl, uint8_t* dst, int bias, hipStream_t s) {
+  return weight_pass(ctx, pl->bps, pl->d_blocks, 0, dst, 0, (long)pl->n_ctu * 64 * 64, 1, 1, 0, 0, bias, s);
+}
+}  // namespace
+
+int hmme_weight_check(int bit_depth, const hmme_weight* wp, int refine) {
+  char msg[256];
+  return weight_eval(bit_depth, wp, refine, nullptr, msg, sizeof msg);
+}
+
+int hmme_search_pairs_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, int n_pairs,
+                               const hmme_frame_params* fp, const hmme_weight* wps, const void* d_pred_q, void* d_out_mv, void* d_out_sad,
+                               void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  WpInfo info[hmme::kMaxRefs];
+  bool all_identity = false;
+  int rc = check_weights(ctx, "hmme_search_pairs_w_device", fp, wps, n_pairs, 0, info, &all_identity);
+  if (rc) return rc;
+  if (!d_out_mv || !d_out_sad) return fail(ctx, HMME_ERR_ARG, "null output buffer");
+  hmme_frame_params f = *fp;
+  f.fen = 0;   // xGetSADw reads every row (TComRdCost.cpp:467-469): FEN is not consulted
+  if (all_identity) return hmme_search_pairs_device(ctx, curs, refs, n_pairs, &f, d_pred_q, d_out_mv, d_out_sad, stream);   // the prediction IS the reference
+  hipStream_t s = (hipStream_t)stream;
+  PairLaunch pl;
+  rc = pairs_begin(ctx, curs, refs, n_pairs, &f, s, &pl);
+  if (rc || pl.count == 0) return rc;
+  const WpGeom g(refs[0]);
+  rc = ensure(ctx, &ctx->d_wp[0], &ctx->wp_cap[0], g.plane_bytes * n_pairs);
+  if (rc == HMME_OK) rc = ensure(ctx, &ctx->d_wp[1], &ctx->wp_cap[1], g.blk_bytes * n_pairs);
+  RefSet wrefs = one_ref(nullptr), wcurs = one_ref(nullptr);
+  const uint8_t* cur_copy[hmme::kMaxRefs] = {};   // the u16 copy made for pair r's current picture (null: none made)
+  for (int r = 0; r < n_pairs && rc == HMME_OK; ++r) {
+    const hmme_weight& w = wps[r];
+    int q = 0;   // a pair before this one with the same reference and weight has made this plane already
+    while (q < r && !(refs[q] == refs[r] && same_weight(wps[q], w))) ++q;
+    if (q < r) {
+      wrefs.base[r] = wrefs.base[q];
+    } else {
+      uint8_t* plane = ctx->d_wp[0] + g.plane_bytes * r;
+      rc = weight_plane(ctx, refs[r], g, plane, w.w0, w.round, w.shift, w.offset + info[r].bias, s);
+      wrefs.base[r] = plane + g.origin;
+    }
+    if (rc != HMME_OK) break;
+    if (curs[r]->bps == 2 && info[r].bias == 0) { wcurs.base[r] = curs[r]->d_blocks; continue; }   // the plane's own blocks serve
+    for (q = 0; q < r && !(curs[q] == curs[r] && cur_copy[q] && info[q].bias == info[r].bias); ++q) {}
+    if (q < r) {
+      cur_copy[r] = cur_copy[q];
+    } else {
+      uint8_t* blocks = ctx->d_wp[1] + g.blk_bytes * r;
+      rc = bias_blocks(ctx, curs[r], blocks, info[r].bias, s);
+      cur_copy[r] = blocks;
+    }
+    wcurs.base[r] = cur_copy[r];
+  }
+  FramePlan plan;
+  if (rc == HMME_OK) rc = prep_jobs(ctx, curs[0], &f, d_pred_q, pl.first, pl.count, n_pairs, s, &plan, true);
+  if (rc == HMME_OK) rc = run_search(ctx, wcurs, curs[0]->ctus_x, wrefs, g.pitch, &f, plan, (int16_t*)d_out_mv, (uint32_t*)d_out_sad, s);
+  return pairs_end(ctx, curs, refs, n_pairs, s, rc);
+}
+
+int hmme_search_frame_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_frame_params* fp, const hmme_weight* wp,
+                        const int16_t* pred_q, int16_t* out_mv, uint32_t* out_sad) {
+  if (!ctx) return HMME_ERR_ARG;
+  WpInfo info;
+  bool identity = false;
+  int rc = check_weights(ctx, "hmme_search_frame_w", fp, wp, 1, 0, &info, &identity);
+  if (rc) return rc;
+  int first, count;
+  rc = check_frame_args(ctx, cur, ref, fp, &first, &count);
+  if (rc) return rc;
+  if (!out_mv || !out_sad) return fail(ctx, HMME_ERR_ARG, "null output buffer");
+  if (count == 0) return HMME_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t n_ctu = (size_t)hmme_num_ctus(cur->width, cur->height);
+  rc = ensure_frame_buffers(ctx, n_ctu);
+  if (rc) return rc;
+  hipStream_t s = ctx->stream;
+  if (pred_q) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_pred, pred_q, sizeof(int16_t) * 2 * n_ctu, hipMemcpyHostToDevice, s));
+  rc = hmme_search_pairs_w_device(ctx, &cur, &ref, 1, fp, wp, pred_q ? ctx->d_pred : nullptr, ctx->d_mv, ctx->d_sad, s);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(out_mv, ctx->d_mv, sizeof(int16_t) * 2 * HMME_NUM_CTU_PARTS * (size_t)count, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipMemcpyAsync(out_sad, ctx->d_sad, sizeof(uint32_t) * HMME_NUM_CTU_PARTS * (size_t)count, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  return HMME_OK;
+}
+
+int hmme_refine_pairs_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, int n_pairs,
+                               const hmme_frame_params* fp, const hmme_weight* wps, const void* d_pred_q, const void* d_int_mv, int use_hadamard,
+                               void* d_out_qmv, void* d_out_cost, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  WpInfo info[hmme::kMaxRefs];
+  bool all_identity = false;
+  int rc = check_weights(ctx, "hmme_refine_pairs_w_device", fp, wps, n_pairs, 1, info, &all_identity);
+  if (rc) return rc;
+  if (!d_int_mv || !d_out_qmv || !d_out_cost) return fail(ctx, HMME_ERR_ARG, "null buffer");
+  if (all_identity) return hmme_refine_pairs_device(ctx, curs, refs, n_pairs, fp, d_pred_q, d_int_mv, use_hadamard, d_out_qmv, d_out_cost, stream);
+  hipStream_t s = (hipStream_t)stream;
+  PairLaunch pl;
+  rc = pairs_begin(ctx, curs, refs, n_pairs, fp, s, &pl);
+  if (rc || pl.count == 0) return rc;
+  const int jobs = pl.count * n_pairs, had = use_hadamard ? 1 : 0, src_wide = curs[0]->bps == 2 ? 1 : 0;
+  const int n_ctu = curs[0]->n_ctu;
+  const WpGeom g(refs[0]);
+  rc = build_frac_cover(ctx);
+  if (rc == HMME_OK) {
+    size_t cap = ctx->frac_jobs_bytes;
+    rc = ensure(ctx, (uint8_t**)&ctx->d_frac_jobs, &cap, sizeof(MeJob) * (size_t)jobs + 64, sizeof(MeJob) * (size_t)pl.count * hmme::kMaxRefs + 4096);
+    ctx->frac_jobs_bytes = cap;
+    ctx->frac_jobs_tag.valid = false;   // the runs below write their own tables where they need one
+  }
+  bool need_cur = false;
+  for (int r = 0; r < n_pairs; ++r) need_cur = need_cur || (!info[r].identity && (!src_wide || info[r].bias));
+  if (rc == HMME_OK && !src_wide) rc = ensure(ctx, &ctx->d_wp[2], &ctx->wp_cap[2], g.plane_bytes * n_pairs);
+  if (rc == HMME_OK && need_cur) rc = ensure(ctx, &ctx->d_wp[3], &ctx->wp_cap[3], g.plane_bytes * n_pairs);
+  static const bool table = std::getenv("HMME_FRAC_JOB_TABLE") != nullptr;
+  const bool packable = pl.count <= 0xffff && pl.first <= 0xffff;
+  const uint8_t* raw_copy[hmme::kMaxRefs] = {};   // pair r's reference widened to u16 / its current picture widened and biased (null: none made)
+  const uint8_t* cur_copy[hmme::kMaxRefs] = {};
+  // one launch per run of pairs with equal weights: the weight is one kernel argument (FracWp)
+  for (int a = 0, b; a < n_pairs && rc == HMME_OK; a = b) {
+    for (b = a + 1; b < n_pairs && same_weight(wps[b], wps[a]); ++b) {}
+    const hmme_weight& w = wps[a];
+    const bool ident = info[a].identity;   // the prediction is the reference: the unweighted kernel on the planes themselves
+    const int wide = ident ? src_wide : 1;
+    RefSet c = one_ref(nullptr), rf = one_ref(nullptr);
+    for (int r = a; r < b && rc == HMME_OK; ++r) {
+      if (ident) { c.base[r - a] = pl.curs.base[r]; rf.base[r - a] = pl.refs.base[r]; continue; }
+      // the RAW reference is interpolated; the current samples carry the bias (FracWp::org_sub takes it off again, with the offset)
+      if (src_wide) {
+        rf.base[r - a] = pl.refs.base[r];
+      } else {
+        int q = 0;
+        while (q < r && !(refs[q] == refs[r] && raw_copy[q])) ++q;
+        if (q < r) raw_copy[r] = raw_copy[q];
+        else {
+          uint8_t* plane = ctx->d_wp[2] + g.plane_bytes * r;
+          rc = weight_plane(ctx, refs[r], g, plane, 1, 0, 0, 0, s);
+          raw_copy[r] = plane + g.origin;
+        }
+        rf.base[r - a] = raw_copy[r];
+        if (rc != HMME_OK) break;
+      }
+      if (src_wide && info[r].bias == 0) { c.base[r - a] = pl.curs.base[r]; continue; }
+      int q = 0;
+      while (q < r && !(curs[q] == curs[r] && cur_copy[q] && info[q].bias == info[r].bias)) ++q;
+      if (q < r) cur_copy[r] = cur_copy[q];
+      else {
+        uint8_t* plane = ctx->d_wp[3] + g.plane_bytes * r;
+        rc = weight_plane(ctx, curs[r], g, plane, 1, 0, 0, info[r].bias, s);
+        cur_copy[r] = plane + g.origin;
+      }
+      c.base[r - a] = cur_copy[r];
+    }
+    if (rc != HMME_OK) break;
+    const int run_jobs = (b - a) * pl.count;
+    const int16_t* pred = d_pred_q ? (const int16_t*)d_pred_q + (size_t)a * n_ctu * 2 : nullptr;
+    const size_t res0 = (size_t)a * pl.count * HMME_NUM_CTU_PARTS;
+    const int grid = frac_grid(ctx, wide, had, run_jobs);
+    const bool walk = grid < run_jobs, need_table = walk || table || !packable;
+    uint32_t* counter = (uint32_t*)((uint8_t*)ctx->d_frac_jobs + ((sizeof(MeJob) * (size_t)run_jobs + 15) & ~(size_t)15));
+    if (need_table)
+      hipLaunchKernelGGL(hmme::me_prep_jobs_kernel, dim3((run_jobs + 255) / 256), dim3(256), 0, s, (MeJob*)ctx->d_frac_jobs, pred, pl.first, pl.count,
+                         b - a, curs[0]->width, curs[0]->height, fp->search_range, 0, run_jobs, 0, counter);
+    rc = frac_lds_optin(ctx, wide, had, ident ? 0 : 1);
+    if (rc != HMME_OK) break;
+    const hmme::FracPrep prep = {pred, (uint32_t)pl.first | (uint32_t)pl.count << 16, (uint32_t)curs[0]->width | (uint32_t)curs[0]->height << 16, fp->search_range};
+    const hmme::FracWp fw = ident ? kNoWp : hmme::FracWp{std::ldexp((float)w.w0, -w.shift), std::ldexp((float)w.round, -w.shift), (float)(info[a].bias + w.offset)};
+    const int pitch = ident ? curs[0]->pitch : g.pitch;   // (a u16 plane's own pitch is g.pitch)
+    hipLaunchKernelGGL(frac_kernel(wide, had, ident ? 0 : 1), dim3(grid), dim3(hmme::frac_threads(wide ? 2 : 1)), hmme::frac_lds_bytes(wide ? 2 : 1), s, c, pitch,
+                       rf, ident ? refs[0]->pitch : g.pitch, need_table ? (const MeJob*)ctx->d_frac_jobs : (const MeJob*)nullptr, prep, run_jobs,
+                       walk ? counter : (uint32_t*)nullptr, ctx->d_frac_cover, (const int16_t*)d_int_mv + 2 * res0, ctx->lambda_q16, fp->bit_depth, fw,
+                       (int16_t*)d_out_qmv + 2 * res0, (uint32_t*)d_out_cost + res0);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "weighted refinement launch -> %s", hipGetErrorString(e));
+  }
+  return pairs_end(ctx, curs, refs, n_pairs, s, rc);
+}
+
+int hmme_refine_frame_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_frame_params* fp, const hmme_weight* wp,
+                        const int16_t* pred_q, const int16_t* int_mv, int use_hadamard, int16_t* out_qmv, uint32_t* out_cost) {
+  if (!ctx) return HMME_ERR_ARG;
+  WpInfo info;
+  bool identity = false;
+  int rc = check_weights(ctx, "hmme_refine_frame_w", fp, wp, 1, 1, &info, &identity);
+  if (rc) return rc;
+  int first, count;
+  rc = check_frame_args(ctx, cur, ref, fp, &first, &count);
+  if (rc) return rc;
+  if (!int_mv || !out_qmv || !out_cost) return fail(ctx, HMME_ERR_ARG, "null buffer");
+  if (count == 0) return HMME_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const int n_ctu = hmme_num_ctus(cur->width, cur->height);
+  rc = ensure_refine_buffers(ctx, (size_t)HMME_NUM_CTU_PARTS * n_ctu);
+  if (rc == HMME_OK) rc = ensure_frame_buffers(ctx, (size_t)n_ctu);
+  if (rc) return rc;
+  hipStream_t s = ctx->stream;
+  const size_t res = (size_t)HMME_NUM_CTU_PARTS * count;
+  if (pred_q) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_pred, pred_q, sizeof(int16_t) * 2 * (size_t)n_ctu, hipMemcpyHostToDevice, s));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_imv, int_mv, sizeof(int16_t) * 2 * res, hipMemcpyHostToDevice, s));
+  rc = hmme_refine_pairs_w_device(ctx, &cur, &ref, 1, fp, wp, pred_q ? ctx->d_pred : nullptr, ctx->d_imv, use_hadamard, ctx->d_qmv, ctx->d_fcost, s);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(out_qmv, ctx->d_qmv, sizeof(int16_t) * 2 * res, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipMemcpyAsync(out_cost, ctx->d_fcost, sizeof(uint32_t) * res, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  return HMME_OK;
+}
+
+int hmme_test_time_weight_passes(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_weight* wp, void* stream, int reps,
+                                 float* ref_ms, float* cur_ms) {
+  if (!ctx) return HMME_ERR_ARG;
+  if (!cur || !ref || !wp || !ref_ms || !cur_ms || reps < 1) return fail(ctx, HMME_ERR_ARG, "hmme_test_time_weight_passes: bad argument");
+  WpInfo info;
+  char msg[256];
+  int rc = weight_eval(ref->bit_depth, wp, 0, &info, msg, sizeof msg);
+  if (rc) return fail(ctx, rc, "hmme_test_time_weight_passes: %s", msg);
+  hmme_frame_params fp = {1, 0, ref->bit_depth, 0, -1};
+  hipStream_t s = (hipStream_t)stream;
+  PairLaunch pl;
+  rc = pairs_begin(ctx, &cur, &ref, 1, &fp, s, &pl);
+  if (rc) return rc;
+  const WpGeom g(ref);
+  rc = ensure(ctx, &ctx->d_wp[0], &ctx->wp_cap[0], g.plane_bytes);
+  if (rc == HMME_OK) rc = ensure(ctx, &ctx->d_wp[1], &ctx->wp_cap[1], g.blk_bytes);
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < 3 && rc == HMME_OK && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
+  float ms0 = 0.f, ms1 = 0.f;
+  if (rc == HMME_OK && e == hipSuccess) {
+    e = hipEventRecord(ev[0], s);
+    for (int i = 0; i < reps && rc == HMME_OK; ++i) rc = weight_plane(ctx, ref, g, ctx->d_wp[0], wp->w0, wp->round, wp->shift, wp->offset + info.bias, s);
+    if (e == hipSuccess) e = hipEventRecord(ev[1], s);
+    for (int i = 0; i < reps && rc == HMME_OK; ++i) rc = bias_blocks(ctx, cur, ctx->d_wp[1], info.bias, s);
+    if (e == hipSuccess) e = hipEventRecord(ev[2], s);
+    if (e == hipSuccess) e = hipEventSynchronize(ev[2]);
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms0, ev[0], ev[1]);
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms1, ev[1], ev[2]);
+  }
+  for (int i = 0; i < 3; ++i) if (ev[i]) hipEventDestroy(ev[i]);
+  if (rc == HMME_OK && e != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "timing the weighting passes: %s", hipGetErrorString(e));
+  if (rc == HMME_OK) { *ref_ms = ms0 / reps; *cur_ms = ms1 / reps; }
+  return pairs_end(ctx, &cur, &ref, 1, s, rc);
 }
 
 int hmme_test_time_search_kernel(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_frame_params* fp,

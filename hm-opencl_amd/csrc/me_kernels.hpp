@@ -2129,4 +2129,38 @@ me_frac_kernel(const RefSet curs, int cur_pitch, const RefSet refs, int ref_pitc
   }   // jobs of this workgroup
 }
 
+// ---- explicit weighted prediction on whole pictures (hmme_search_pairs_w_device / hmme_refine_pairs_w_device) ----------------------------
+// The picture-sized form of me_weight_window_kernel: a whole padded plane (u8 or u16 samples, margins included) -> a u16 plane of the
+// same geometry, every sample ((w0 * v + round) >> shift) + offset_bias (offset_bias = the weight's offset + the bias that keeps block
+// and weighted plane unsigned).  Weighting commutes with edge replication, so weighting the margins IS extending the weighted picture.
+// The 16-bit search kernel then runs on the result unchanged.  The same kernel makes the other u16 copies a weighted call needs --
+// w0 = 1, shift = 0, round = 0 widens (and biases) as it copies: the current pictures' CTU-blocked copies (one "row" of n_ctu * 4096
+// samples) and the padded raw copies the weighted refinement reads from 8-bit planes.
+// Bandwidth-bound: one lane loads 16 bytes (16 u8 / 8 u16 samples) and stores 16 bytes at a time, rows addressed by pitch (blockIdx.y),
+// no division.  cols (samples of a row to convert) is a multiple of 16 and cols * sizeof(SrcT) <= src_pitch, 2 * cols <= dst_pitch:
+// every access stays inside its row.
+template <typename SrcT>
+__global__ void __launch_bounds__(256)
+me_weight_plane_kernel(const uint8_t* __restrict__ src, int src_pitch, uint8_t* __restrict__ dst, int dst_pitch, int cols, int w0, int round,
+                       int shift, int offset_bias) {
+  constexpr int N = 16 / (int)sizeof(SrcT);   // samples per lane
+  const long x0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * N;
+  if (x0 >= cols) return;
+  const uint4 in = *(const uint4*)(src + (long)blockIdx.y * src_pitch + x0 * (long)sizeof(SrcT));
+  const uint32_t w[4] = {in.x, in.y, in.z, in.w};
+  uint32_t o[N / 2];
+#pragma unroll
+  for (int i = 0; i < N; i += 2) {
+    int v0, v1;
+    if (sizeof(SrcT) == 1) { v0 = (int)((w[i >> 2] >> (8 * (i & 3))) & 0xff); v1 = (int)((w[i >> 2] >> (8 * (i & 3) + 8)) & 0xff); }
+    else { v0 = (int)(w[i >> 1] & 0xffff); v1 = (int)(w[i >> 1] >> 16); }
+    const uint32_t r0 = (uint32_t)(((w0 * v0 + round) >> shift) + offset_bias) & 0xffffu;
+    const uint32_t r1 = (uint32_t)(((w0 * v1 + round) >> shift) + offset_bias) & 0xffffu;
+    o[i >> 1] = r0 | r1 << 16;
+  }
+  uint4* out = (uint4*)(dst + (long)blockIdx.y * dst_pitch + x0 * 2);
+#pragma unroll
+  for (int q = 0; q < N / 8; ++q) out[q] = make_uint4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
+}
+
 }  // namespace hmme

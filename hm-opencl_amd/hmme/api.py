@@ -22,9 +22,10 @@ SYMBOLS = ["hmme_create", "hmme_destroy", "hmme_last_error", "hmme_device_info",
            "hmme_num_ctus", "hmme_search_frame", "hmme_search_frame_device", "hmme_search_frame_multi",
            "hmme_search_frame_multi_device", "hmme_refine_frame", "hmme_refine_frame_multi_device",
            "hmme_search_pairs_device", "hmme_refine_pairs_device", "hmme_plane_upload_async",
-           "hmme_upload_status", "hmme_abi_version", "hmme_build_id", "hmme_device_index", "hmme_set_error_printing"]
+           "hmme_upload_status", "hmme_abi_version", "hmme_build_id", "hmme_device_index", "hmme_set_error_printing",
+           "hmme_weight_check", "hmme_search_pairs_w_device", "hmme_refine_pairs_w_device", "hmme_search_frame_w", "hmme_refine_frame_w"]
 # test / measurement entry points (include/hmme_test.h): not part of the boundary
-TEST_SYMBOLS = ["hmme_test_time_search_kernel", "hmme_test_device_address", "hmme_test_frac_deal", "hmme_test_tail_plan"]
+TEST_SYMBOLS = ["hmme_test_time_search_kernel", "hmme_test_device_address", "hmme_test_frac_deal", "hmme_test_tail_plan", "hmme_test_time_weight_passes"]
 ABI_VERSION = 6   # HMME_ABI_VERSION of the include/hmme.h these bindings were written against
 
 
@@ -117,6 +118,12 @@ def load():
     L.hmme_search_pairs_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, C.POINTER(FrameParams), vp, vp, vp, vp]
     L.hmme_refine_pairs_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, C.POINTER(FrameParams), vp, vp, i, vp, vp, vp]
     L.hmme_plane_upload_async.argtypes = [vp, vp, i, i, vp]
+    L.hmme_weight_check.argtypes = [i, C.POINTER(Weight), i]
+    L.hmme_search_pairs_w_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, C.POINTER(FrameParams), C.POINTER(Weight), vp, vp, vp, vp]
+    L.hmme_refine_pairs_w_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, C.POINTER(FrameParams), C.POINTER(Weight), vp, vp, i, vp, vp, vp]
+    L.hmme_search_frame_w.argtypes = [vp, vp, vp, C.POINTER(FrameParams), C.POINTER(Weight), vp, vp, vp]
+    L.hmme_refine_frame_w.argtypes = [vp, vp, vp, C.POINTER(FrameParams), C.POINTER(Weight), vp, vp, i, vp, vp]
+    L.hmme_test_time_weight_passes.argtypes = [vp, vp, vp, C.POINTER(Weight), vp, i, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.hmme_upload_status.argtypes = [vp, vp]
     L.hmme_test_device_address.argtypes = [vp, vp]
     L.hmme_test_device_address.restype = C.c_uint64
@@ -366,6 +373,65 @@ class Engine:
         self._check(self.L.hmme_refine_pairs_device(self.h, ca, ra, len(refs), C.byref(fp), d_pred, d_int_mv, int(use_hadamard),
                                                     d_qmv, d_cost, stream))
 
+    def search_frame_w(self, cur, ref, sr, wp, pred_q=None, fen=0, ctu_first=0, ctu_count=-1):
+        """hmme_search_frame_w: the whole-picture search of a slice with explicit weighted prediction, wp = (w0, offset, shift, round)
+        (fen is passed through and not consulted by the engine) -> (mv int16[count,593,2], sad uint32[count,593])"""
+        n = self.L.hmme_num_ctus(cur.width, cur.height)
+        count = n - ctu_first if ctu_count < 0 else ctu_count
+        fp = FrameParams(sr, int(fen), cur.bit_depth, ctu_first, count)
+        mv = np.zeros((count, NUM_PARTS, 2), np.int16)
+        sad = np.zeros((count, NUM_PARTS), np.uint32)
+        pq = None
+        if pred_q is not None:
+            pred_q = np.ascontiguousarray(pred_q, dtype=np.int16)
+            assert pred_q.shape == (n, 2)
+            pq = pred_q.ctypes.data
+        w = Weight(*[int(v) for v in wp])
+        self._check(self.L.hmme_search_frame_w(self.h, cur.h, ref.h, C.byref(fp), C.byref(w), pq, mv.ctypes.data, sad.ctypes.data))
+        return mv, sad
+
+    def refine_frame_w(self, cur, ref, sr, wp, int_mv, pred_q=None, use_hadamard=True, ctu_first=0, ctu_count=-1):
+        """hmme_refine_frame_w: weighted xPatternSearchFracDIF of integer winners -> (qmv int16[count,593,2], cost uint32[count,593])"""
+        n = self.L.hmme_num_ctus(cur.width, cur.height)
+        count = n - ctu_first if ctu_count < 0 else ctu_count
+        fp = FrameParams(sr, 0, cur.bit_depth, ctu_first, count)
+        int_mv = np.ascontiguousarray(int_mv, dtype=np.int16)
+        assert int_mv.shape == (count, NUM_PARTS, 2)
+        qmv = np.zeros((count, NUM_PARTS, 2), np.int16)
+        cost = np.zeros((count, NUM_PARTS), np.uint32)
+        pq = None
+        if pred_q is not None:
+            pred_q = np.ascontiguousarray(pred_q, dtype=np.int16)
+            assert pred_q.shape == (n, 2)
+            pq = pred_q.ctypes.data
+        w = Weight(*[int(v) for v in wp])
+        self._check(self.L.hmme_refine_frame_w(self.h, cur.h, ref.h, C.byref(fp), C.byref(w), pq, int_mv.ctypes.data, int(use_hadamard),
+                                               qmv.ctypes.data, cost.ctypes.data))
+        return qmv, cost
+
+    def search_pairs_w_device(self, curs, refs, fp, weights, d_pred, d_mv, d_sad, stream=0):
+        """hmme_search_pairs_w_device: up to 16 pairs in one launch, weights = one (w0, offset, shift, round) per pair"""
+        assert len(curs) == len(refs) == len(weights)
+        ca = (C.c_void_p * len(curs))(*[c.h for c in curs])
+        ra = (C.c_void_p * len(refs))(*[r.h for r in refs])
+        wa = (Weight * len(weights))(*[Weight(*[int(v) for v in w]) for w in weights])
+        self._check(self.L.hmme_search_pairs_w_device(self.h, ca, ra, len(refs), C.byref(fp), wa, d_pred, d_mv, d_sad, stream))
+
+    def refine_pairs_w_device(self, curs, refs, fp, weights, d_pred, d_int_mv, use_hadamard, d_qmv, d_cost, stream=0):
+        assert len(curs) == len(refs) == len(weights)
+        ca = (C.c_void_p * len(curs))(*[c.h for c in curs])
+        ra = (C.c_void_p * len(refs))(*[r.h for r in refs])
+        wa = (Weight * len(weights))(*[Weight(*[int(v) for v in w]) for w in weights])
+        self._check(self.L.hmme_refine_pairs_w_device(self.h, ca, ra, len(refs), C.byref(fp), wa, d_pred, d_int_mv, int(use_hadamard),
+                                                      d_qmv, d_cost, stream))
+
+    def time_weight_passes(self, cur, ref, wp, stream=0, reps=5):
+        """device time in ms of the two plane passes of a weighted search on their own -> (reference plane, current-picture blocks)"""
+        a, b = C.c_float(), C.c_float()
+        w = Weight(*[int(v) for v in wp])
+        self._check(self.L.hmme_test_time_weight_passes(self.h, cur.h, ref.h, C.byref(w), stream, reps, C.byref(a), C.byref(b)))
+        return float(a.value), float(b.value)
+
     def upload_status(self, stream=0):
         """waits for `stream`; raises if an asynchronous upload carried an out-of-range sample"""
         self._check(self.L.hmme_upload_status(self.h, stream))
@@ -388,6 +454,13 @@ class Engine:
 def build_id():
     """identifies the kernel sources + flags the loaded library was built from (hmme_build_id)"""
     return load().hmme_build_id().decode()
+
+
+def weight_check(bit_depth, wp, refine=False):
+    """hmme_weight_check: 0, or the HMME_ERR_* code with which a whole-picture call refuses the weight wp = (w0, offset, shift, round)
+    at this bit depth (pure host arithmetic: needs no GPU)"""
+    w = Weight(*[int(v) for v in wp])
+    return int(load().hmme_weight_check(int(bit_depth), C.byref(w), 1 if refine else 0))
 
 
 def ocl_compat_params(lt_x, lt_y, sr):

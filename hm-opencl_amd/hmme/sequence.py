@@ -143,16 +143,22 @@ class RankResources:
 
 
 def run_rank(eng, source, pairs, width, height, bit_depth, search_range, *, stream_mode=False, pairs_per_launch=1, refine=False,
-             download=False, n_slots=None, device=None, host_buffers=4, resources=None):
+             download=False, n_slots=None, device=None, host_buffers=4, resources=None, weights=None):
     """searches `pairs` [(cur_poc, ref_poc)] (this rank's share) -> dict with device tensors mv [n, n_ctu, 593, 2] int16,
     sad [n, n_ctu, 593] int32 (+ qmv / cost with refine, + host_* page-locked copies with download) and timings.
     source: .read_into(poc, out) filling a (height, width) uint8 / uint16 array (hmme.yuv.LumaFile, hmme.synth.Sequence).
     resources: a RankResources the caller keeps between passes of one geometry (streaming mode): plane slots, host buffers and streams are
-    then allocated by the first pass only and stay the caller's to close."""
+    then allocated by the first pass only and stay the caller's to close.
+    weights: explicit weighted prediction -- one (w0, offset, shift, round) per pair, in the order of `pairs`; search (and refinement)
+    then go through hmme_search_pairs_w_device / hmme_refine_pairs_w_device.  None: the unweighted calls, as before."""
     import torch
     from . import api
     dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
     n = len(pairs)
+    if weights is not None:
+        weights = [tuple(int(v) for v in w) for w in weights]
+        if len(weights) != n or any(len(w) != 4 for w in weights):
+            raise ValueError(f"weights: {len(weights)} entries for {n} pairs (one (w0, offset, shift, round) per pair)")
     n_ctu = api.load().hmme_num_ctus(width, height)
     fp = api.FrameParams(search_range, 1, bit_depth, 0, n_ctu)
     bps = 1 if bit_depth == 8 else 2
@@ -190,12 +196,20 @@ def run_rank(eng, source, pairs, width, height, bit_depth, search_range, *, stre
         refs = [planes[where_b[pairs[i][1]]] for i in idx]
         i0, i1 = idx[0], idx[-1] + 1
         e = timed("search", compute)
-        eng.search_pairs_device(curs, refs, fp, None, out["mv"][i0:i1].data_ptr(), out["sad"][i0:i1].data_ptr(), compute.cuda_stream)
+        if weights is None:
+            eng.search_pairs_device(curs, refs, fp, None, out["mv"][i0:i1].data_ptr(), out["sad"][i0:i1].data_ptr(), compute.cuda_stream)
+        else:
+            eng.search_pairs_w_device(curs, refs, fp, weights[i0:i1], None, out["mv"][i0:i1].data_ptr(), out["sad"][i0:i1].data_ptr(),
+                                      compute.cuda_stream)
         e.record(compute)
         if refine:
             e = timed("refine", compute)
-            eng.refine_pairs_device(curs, refs, fp, None, out["mv"][i0:i1].data_ptr(), 1, out["qmv"][i0:i1].data_ptr(),
-                                    out["cost"][i0:i1].data_ptr(), compute.cuda_stream)
+            if weights is None:
+                eng.refine_pairs_device(curs, refs, fp, None, out["mv"][i0:i1].data_ptr(), 1, out["qmv"][i0:i1].data_ptr(),
+                                        out["cost"][i0:i1].data_ptr(), compute.cuda_stream)
+            else:
+                eng.refine_pairs_w_device(curs, refs, fp, weights[i0:i1], None, out["mv"][i0:i1].data_ptr(), 1, out["qmv"][i0:i1].data_ptr(),
+                                          out["cost"][i0:i1].data_ptr(), compute.cuda_stream)
             e.record(compute)
         if download:
             done = torch.cuda.Event()

@@ -19,6 +19,9 @@
  *                             CTU from the host, TEncOpenCL.cpp:312-333)
  *   hmme_search_pairs_device, <- the same for up to 16 (current, reference) picture pairs of a GOP in one launch
  *   hmme_refine_pairs_device     (cfg/encoder_randomaccess_main.cfg:28-31, cfg/encoder_lowdelay_P_main.cfg:24-27)
+ *   hmme_search_pairs_w_device, <- the same in a slice with explicit weighted prediction (TEncSearch::setWpScalingDistParam,
+ *   hmme_refine_pairs_w_device,    TEncSearch.cpp:5594-5635; TComRdCostWeightPrediction.cpp:55-90, :407-470), one weight per pair
+ *   hmme_search_frame_w, hmme_refine_frame_w
  *   hmme_plane_*           <- the padded reference plane calcMotionVectors reads
  *                             (TComPicYuv, TLibCommon/TComPicYuv.cpp:91-92, 214-262); hmme_plane_upload_* take what
  *                             TVideoIOYuv::read delivers (TVideoIOYuv.cpp:247, :680: 8-bit or 16-bit little-endian samples)
@@ -275,6 +278,45 @@ int hmme_refine_frame_multi_device(hmme_ctx* ctx, const hmme_plane* cur, const h
 int hmme_refine_pairs_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, int n_pairs,
                              const hmme_frame_params* fp, const void* d_pred_q, const void* d_int_mv, int use_hadamard,
                              void* d_out_qmv, void* d_out_cost, void* stream);
+
+/* ---- explicit weighted prediction on whole pictures and picture pairs ----------------------------------------
+ * The picture-level siblings of hmme_search_ctu_w / hmme_refine_ctu_w (new entry points; no struct and no existing entry point
+ * changed, so HMME_ABI_VERSION stays 6).  For pair i and CTU c the search returns what hmme_search_ctu_w returns for that CTU's
+ * 64x64 block of curs[i] (partial edge CTUs completed by edge replication, as the plane's CTU-blocked copy holds them), the padded
+ * refs[i], the window hmme_set_search_range gives for the CTU's predictor and the weight wps[i]: xGetSADw over EVERY row (fp->fen is
+ * not consulted), the prediction unclipped, the block sum >> (bitDepth-8).  The refinement returns what hmme_refine_ctu_w returns at
+ * the same inputs (xGetHADsw / xGetSADw: the interpolated, clipped prediction weighted sample by sample).  Lambda is the context's.
+ * Array shapes, ctu_first / ctu_count, the limit of 16 pairs, plane ownership and stream ordering are those of
+ * hmme_search_pairs_device / hmme_refine_pairs_device; wps: n_pairs weights in HOST memory, read before the call returns.
+ * The weighted planes live in scratch of the context (one u16 plane per pair, grown on demand: 19 MB per 2160p pair), ordered
+ * across streams like its other scratch.
+ *
+ * Refusal.  A frame call cannot scan its samples on the host the way the per-CTU call does, so hmme_weight_check decides from the
+ * NOMINAL range [0, 2^bitDepth - 1] of both pictures -- the bound is therefore stricter than the per-CTU call's on tame content
+ * (a weight that hmme_search_ctu_w accepts for a dark block may be refused here).  With span = the largest
+ * |block - weighted sample| those ranges admit:
+ *   shift outside 0..15 (or wp == NULL)                                          -> HMME_ERR_ARG
+ *   a weighted sample beyond int16 (or w0 * sample + round beyond 32 bits), or block and
+ *   weighted plane together spanning more than 16 bits                           -> HMME_ERR_UNSUPPORTED
+ *   ((4096 * span) >> (bitDepth-8)) + 65535 >= 8 000 000 (the engine's cost field) -> HMME_ERR_UNSUPPORTED
+ *   refine != 0: 4096 * span >= 2^24, or -- identity weights excepted -- |w0 * sample + round|
+ *   >= 2^24 (the refinement's sums and its weighting are exact in fp32 below that)  -> HMME_ERR_UNSUPPORTED
+ * hmme_weight_check is a pure host function: no context, no GPU.  Every frame call below first runs it for every pair
+ * (refine = 1 in the refinement calls) and launches NOTHING if one pair fails: it returns that code, hmme_last_error names the pair;
+ * no fallback, no partial work.  Identity weights (w0 == 1 << shift, offset 0, round == (shift ? 1 << (shift-1) : 0)) are served
+ * by the unweighted kernels with FEN off. */
+int hmme_weight_check(int bit_depth, const hmme_weight* wp, int refine);
+int hmme_search_pairs_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, int n_pairs,
+                               const hmme_frame_params* fp, const hmme_weight* wps, const void* d_pred_q, void* d_out_mv, void* d_out_sad,
+                               void* stream);
+int hmme_refine_pairs_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, int n_pairs,
+                               const hmme_frame_params* fp, const hmme_weight* wps, const void* d_pred_q, const void* d_int_mv, int use_hadamard,
+                               void* d_out_qmv, void* d_out_cost, void* stream);
+/* synchronous, host results, one pair: the weighted siblings of hmme_search_frame / hmme_refine_frame */
+int hmme_search_frame_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_frame_params* fp, const hmme_weight* wp,
+                        const int16_t* pred_q, int16_t* out_mv, uint32_t* out_sad);
+int hmme_refine_frame_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_frame_params* fp, const hmme_weight* wp,
+                        const int16_t* pred_q, const int16_t* int_mv, int use_hadamard, int16_t* out_qmv, uint32_t* out_cost);
 
 /* ---- environment (diagnostics and A/B measurements; none of these changes a result) ---------
  *   HMME_TRACE=1          one stderr line per context about launch geometry the library derives at run time (with HMME_FRAC_GRID=-1:

@@ -27,6 +27,11 @@ int hmme_test_tail_plan(int width, int height, int search_range, int n_pairs, in
  * edge CTUs of every pair first, then the interiors); host code, needs no device.  -1 for k outside the launch */
 int hmme_test_frac_deal(int k, int n_pairs, int width, int height);
 
+/* average device time in ms of the two plane passes of a weighted whole-picture search on their own, `reps` back-to-back launches each on
+ * `stream`: *ref_ms = weighting the padded reference plane (me_weight_plane_kernel), *cur_ms = the u16 CTU-blocked copy of the current picture */
+int hmme_test_time_weight_passes(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_weight* wp, void* stream, int reps,
+                                 float* ref_ms, float* cur_ms);
+
 #ifdef __cplusplus
 }
 #endif

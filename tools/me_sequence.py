@@ -43,6 +43,9 @@ def main():
     ap.add_argument("--dump-pairs", default=None, help="comma-separated pair indices to dump (default all)")
     ap.add_argument("--dump-ctus", default=None, help="first:count CTU range to dump (default all)")
     ap.add_argument("--repeat", type=int, default=1, help="run the pass this many times, report the last (the first includes allocations)")
+    ap.add_argument("--weights", default=None,
+                    help="explicit weighted prediction: a text file with one line `w0 offset shift round` per pair of the GOP (pair order; # comments); "
+                         "searches and refinements then run through hmme_search_pairs_w_device / hmme_refine_pairs_w_device")
     ap.add_argument("--rank-timeout", type=float, default=600.0,
                     help="N > 1: seconds a rank may take from its start to the end of its first barrier (rendezvous, RCCL communicator) before it "
                          "gives up with exit code 3, naming itself and the stage it hung in; 0 = no limit")
@@ -79,7 +82,15 @@ def main():
     w, h = {"2160p": (3840, 2160), "1080p": (1920, 1080), "720p": (1280, 720)}.get(args.size) or tuple(int(v) for v in args.size.split("x"))
     bd = args.bit_depth
     pairs = shard.gop_pairs(args.frames, args.gop)
-    mine = [pairs[p] for p in shard.pairs_for_rank(len(pairs), rank, world)]
+    mine_idx = list(shard.pairs_for_rank(len(pairs), rank, world))
+    mine = [pairs[p] for p in mine_idx]
+    weights = None
+    if args.weights:
+        rows = [l.split("#")[0].split() for l in open(args.weights)]
+        rows = [tuple(int(v) for v in r) for r in rows if r]
+        if len(rows) != len(pairs) or any(len(r) != 4 for r in rows):
+            raise SystemExit(f"me_sequence.py: --weights {args.weights}: {len(rows)} lines of `w0 offset shift round` for {len(pairs)} pairs")
+        weights = [rows[p] for p in mine_idx]
     eng = api.Engine(local, max(64, args.search_range))
     eng.set_lambda(57.9)
     if args.yuv:
@@ -94,7 +105,7 @@ def main():
             dist.barrier()
         res = sequence.run_rank(eng, source, mine, w, h, bd, args.search_range, stream_mode=args.stream,
                                 pairs_per_launch=args.pairs_per_launch, refine=args.refine, download=args.download,
-                                n_slots=args.slots or None, device=dev)
+                                n_slots=args.slots or None, device=dev, weights=weights)
     dt = res["seconds"]
     if use_dist:   # the slowest rank's time is the job's
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
