@@ -142,6 +142,10 @@ struct hmme_ctx {
   // planes widened from 8 bit and [3] biased padded current pictures (refinement).  Scratch like the job tables: scratch_acquire / launch_end
   uint8_t* d_wp[4] = {nullptr, nullptr, nullptr, nullptr};
   size_t wp_cap[4] = {0, 0, 0, 0};
+  // host-facing bi-prediction / prediction calls (hmme_search_frame_bi, hmme_refine_frame_bi, hmme_predict_frame): device staging for the
+  // motion field and the window centres [0] and for the predicted picture [1]
+  uint8_t* d_bi[2] = {nullptr, nullptr};
+  size_t bi_cap[2] = {0, 0};
 };
 
 struct hmme_plane {
@@ -533,6 +537,7 @@ void hmme_destroy(hmme_ctx* ctx) {
   hipFree(ctx->d_pred); hipFree(ctx->d_mv); hipFree(ctx->d_sad); hipFree(ctx->d_flag);
   hipFree(ctx->d_wwin); hipFree(ctx->d_frac_cover); hipFree(ctx->d_imv); hipFree(ctx->d_qmv); hipFree(ctx->d_fcost);
   for (int i = 0; i < 4; ++i) hipFree(ctx->d_wp[i]);
+  for (int i = 0; i < 2; ++i) hipFree(ctx->d_bi[i]);
   if (ctx->h_call) hipHostFree(ctx->h_call);
   if (ctx->h_res) hipHostFree(ctx->h_res);
   delete ctx;
@@ -1167,8 +1172,9 @@ static bool tail_one_launch(int head, int n_tail, int launches_knob) { return la
 
 // builds the device job table of a picture search against n_refs reference pictures on `s`; job index =
 // ref * count + ctu.  8-bit: MeJob[head jobs] (+ MeJob16[tail jobs * parts]); 8-bit tiled / 16-bit: MeJob16[workgroups]
+// d_center_q (16-bit tables only; null = the predictor): the windows' centres of a bi-prediction pass, laid out like d_pred_q
 static int prep_jobs(hmme_ctx* ctx, const hmme_plane* cur, const hmme_frame_params* fp, const void* d_pred_q, int first, int count,
-                     int n_refs, hipStream_t s, FramePlan* pl, bool force16 = false) {
+                     int n_refs, hipStream_t s, FramePlan* pl, bool force16 = false, const void* d_center_q = nullptr) {
   const bool wide = fp->bit_depth > 8 || force16;   // force16: a weighted search of 8-bit planes (its u16 copies)
   pl->wide = wide;
   const int jobs = count * n_refs, slots = ctx->wg_slots, w = 2 * fp->search_range + 1;
@@ -1234,7 +1240,7 @@ static int prep_jobs(hmme_ctx* ctx, const hmme_plane* cur, const hmme_frame_para
     if (rc) return rc;
   }
   hmme_ctx::TableTag tag;
-  tag.valid = !d_pred_q;
+  tag.valid = !d_pred_q && !d_center_q;
   tag.w = cur->width; tag.h = cur->height; tag.bit_depth = fp->bit_depth | (wide && fp->bit_depth == 8 ? 0x100 : 0); tag.sr = fp->search_range; tag.first = first; tag.count = count; tag.pairs = n_refs;
   tag.buf = ctx->d_jobs; tag.buf2 = (wide || pl->tile8 || n_tail) ? ctx->d_first_strip : nullptr; tag.stream = (void*)s;
   if (tag.same(ctx->jobs_tag)) return HMME_OK;   // the table of the launch before is this launch's table
@@ -1247,12 +1253,12 @@ static int prep_jobs(hmme_ctx* ctx, const hmme_plane* cur, const hmme_frame_para
   else if (wide)
     hipLaunchKernelGGL(hmme::me_prep_jobs16_kernel, grid(jobs), block, 0, s, (MeJob16*)ctx->d_jobs, ctx->d_first_strip,
                        (const int16_t*)d_pred_q, first, count, n_refs, cur->width, cur->height, fp->search_range, pl->n_strips, pl->strip_rows,
-                       pl->tail_first, pl->tail_parts);
+                       pl->tail_first, pl->tail_parts, (const int16_t*)d_center_q);
   else {
     if (!n_tail || !pl->one_launch) {
       if (head)
         hipLaunchKernelGGL(hmme::me_prep_jobs_kernel, grid(head), block, 0, s, (MeJob*)ctx->d_jobs, (const int16_t*)d_pred_q, first, count,
-                           n_refs, cur->width, cur->height, fp->search_range, 0, head, 1, (uint32_t*)nullptr);
+                           n_refs, cur->width, cur->height, fp->search_range, 0, head, 1, (uint32_t*)nullptr, (const int16_t*)nullptr);
       if (n_tail)
         hipLaunchKernelGGL(hmme::me_prep_segments_kernel, dim3(1), dim3(hmme::kSegPrepThreads), 0, s, (void*)((uint8_t*)ctx->d_jobs + pl->tail_jobs_off), ctx->d_first_strip,
                            (const int16_t*)d_pred_q, first, count, n_refs, cur->width, cur->height, fp->search_range, pl->tail_wgs, head, n_tail, 0);
@@ -1321,16 +1327,22 @@ int pairs_begin(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* 
   return rc;
 }
 // after the kernels are enqueued (or an enqueue failed): the planes have a reader on `s`, the scratch a user
-int pairs_end(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, int n_pairs, hipStream_t s, int rc) {
+// others (bi-prediction calls; else null): the planes whose prediction the launch subtracted -- read like a reference
+int pairs_end(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, int n_pairs, hipStream_t s, int rc,
+              const hmme_plane* const* others = nullptr) {
   for (int r = 0; r < n_pairs; ++r) {
     int r2 = (r == 0 || curs[r] != curs[r - 1]) ? plane_read_chain(ctx, curs[r], s) : HMME_OK;
     if (r2 == HMME_OK) r2 = plane_read_chain(ctx, refs[r], s);
+    if (r2 == HMME_OK && others) r2 = plane_read_chain(ctx, others[r], s);
     if (rc == HMME_OK) rc = r2;
   }
   // one event for the whole launch (it was one per plane and one for the scratch: 3 .. 33 packets between two kernels of a stream)
   const int r3 = launch_end(ctx, s);
   if (r3 == HMME_OK)
-    for (int r = 0; r < n_pairs; ++r) { plane_read_mark(ctx, curs[r], s); plane_read_mark(ctx, refs[r], s); }
+    for (int r = 0; r < n_pairs; ++r) {
+      plane_read_mark(ctx, curs[r], s); plane_read_mark(ctx, refs[r], s);
+      if (others) plane_read_mark(ctx, others[r], s);
+    }
   return rc ? rc : r3;
 }
 }  // namespace
@@ -1471,7 +1483,7 @@ int hmme_refine_pairs_device(hmme_ctx* ctx, const hmme_plane* const* curs, const
     if (need_table && !have_table) ctx->frac_jobs_tag = tag;
     if (need_table && !have_table)
       hipLaunchKernelGGL(hmme::me_prep_jobs_kernel, dim3((jobs + 255) / 256), dim3(256), 0, s, (MeJob*)ctx->d_frac_jobs, (const int16_t*)d_pred_q,
-                         pl.first, pl.count, n_pairs, curs[0]->width, curs[0]->height, fp->search_range, 0, jobs, 0, counter);
+                         pl.first, pl.count, n_pairs, curs[0]->width, curs[0]->height, fp->search_range, 0, jobs, 0, counter, (const int16_t*)nullptr);
     rc = frac_lds_optin(ctx, wide, had, 0);
     if (rc != HMME_OK) return pairs_end(ctx, curs, refs, n_pairs, s, rc);
     hipLaunchKernelGGL(frac_kernel(wide, had, 0), dim3(grid), dim3(hmme::frac_threads(wide ? 2 : 1)), hmme::frac_lds_bytes(wide ? 2 : 1), s, pl.curs,
@@ -1790,7 +1802,7 @@ int hmme_refine_pairs_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, con
     uint32_t* counter = (uint32_t*)((uint8_t*)ctx->d_frac_jobs + ((sizeof(MeJob) * (size_t)run_jobs + 15) & ~(size_t)15));
     if (need_table)
       hipLaunchKernelGGL(hmme::me_prep_jobs_kernel, dim3((run_jobs + 255) / 256), dim3(256), 0, s, (MeJob*)ctx->d_frac_jobs, pred, pl.first, pl.count,
-                         b - a, curs[0]->width, curs[0]->height, fp->search_range, 0, run_jobs, 0, counter);
+                         b - a, curs[0]->width, curs[0]->height, fp->search_range, 0, run_jobs, 0, counter, (const int16_t*)nullptr);
     rc = frac_lds_optin(ctx, wide, had, ident ? 0 : 1);
     if (rc != HMME_OK) break;
     const hmme::FracPrep prep = {pred, (uint32_t)pl.first | (uint32_t)pl.count << 16, (uint32_t)curs[0]->width | (uint32_t)curs[0]->height << 16, fp->search_range};
@@ -1833,6 +1845,336 @@ int hmme_refine_frame_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* 
   HIP_TRY(ctx, hipMemcpyAsync(out_cost, ctx->d_fcost, sizeof(uint32_t) * res, hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipStreamSynchronize(s));
   return HMME_OK;
+}
+
+// ---- bi-prediction on whole pictures and picture pairs ----------------------------------------------------------
+// The picture-level form of the bBi pass of the per-CTU calls.  For every pair the other list's prediction is motion-compensated from a
+// motion field and folded into the current picture's CTU blocks as 2 * cur - pred + bias (me_predict_kernel<SrcT, 1>, one launch per pair,
+// bias = 2^bitDepth - 1: the origin lies in [-maxv, 2 * maxv]); the reference gets a u16 copy with the same bias (me_weight_plane_kernel at
+// weight 1, once per distinct plane) and me_search16_kernel runs over the two through the job tables, strips and tails of any u16 search --
+// the window centred on d_center_q where the caller gives one (me_prep_jobs16_kernel).  The refinement writes the origin into a padded u16
+// plane instead (the refinement kernel reads its current block by pitch) and runs me_frac_kernel<HAD, 2, 1> with the identity weight and
+// org_sub = bias on the RAW reference: the plane itself above 8 bits, a widened copy at 8 (DESIGN.md 7 gives the reason for this choice).
+namespace {
+// what the kernels hold, from the nominal sample range: origin in [-maxv, 2 maxv], reference in [0, maxv]
+int bipred_eval(int bit_depth, int refine, char* msg, size_t n) {
+  msg[0] = 0;
+  if (bit_depth < 8 || bit_depth > 12) { snprintf(msg, n, "bit depth %d outside 8..12", bit_depth); return HMME_ERR_ARG; }
+  const long maxv = (1L << bit_depth) - 1;
+  if (3 * maxv > 65535) { snprintf(msg, n, "bi-prediction origins of %d-bit samples span more than 16 bits", bit_depth); return HMME_ERR_UNSUPPORTED; }
+  const long span = 2 * maxv;   // largest |origin - reference sample|
+  if (((4096 * span) >> (bit_depth - 8)) + 65535 >= (long)hmme::kInvCost16) {
+    snprintf(msg, n, "bi-prediction SADs of a %d-bit block could reach %ld: beyond the cost field", bit_depth, 4096 * span);
+    return HMME_ERR_UNSUPPORTED;
+  }
+  if (refine && 4096 * span >= (1L << 24)) {
+    snprintf(msg, n, "bi-prediction refinement at %d bits: sample differences up to %ld exceed what the Hadamard sums hold exactly", bit_depth, span);
+    return HMME_ERR_UNSUPPORTED;
+  }
+  return HMME_OK;
+}
+
+int bi_check(hmme_ctx* ctx, const char* who, const hmme_frame_params* fp, int refine) {
+  if (!fp) return fail(ctx, HMME_ERR_ARG, "%s: null params", who);
+  char msg[256];
+  const int rc = bipred_eval(fp->bit_depth, refine, msg, sizeof msg);
+  return rc ? fail(ctx, rc, "%s: %s", who, msg) : HMME_OK;
+}
+
+// the argument checks of a bi-prediction launch that pairs_begin does not make
+int bi_args(hmme_ctx* ctx, const char* who, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others, int n_pairs,
+            const hmme_frame_params* fp, const void* d_other_mv, int mv_per_ctu) {
+  if (!curs || !refs || !others || n_pairs < 1 || n_pairs > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d picture pairs outside 1..%d (or a null plane list)", who, n_pairs, hmme::kMaxRefs);
+  if (!d_other_mv || (mv_per_ctu != 1 && mv_per_ctu != 64)) return fail(ctx, HMME_ERR_ARG, "%s: null motion field, or %d MVs per CTU (1 or 64)", who, mv_per_ctu);
+  for (int r = 0; r < n_pairs; ++r) {
+    if (!curs[r] || !refs[r] || !others[r]) return fail(ctx, HMME_ERR_ARG, "%s: null plane", who);
+    if (others[r]->ctx != ctx) return fail(ctx, HMME_ERR_ARG, "plane belongs to another context (planes are used with the context that created them)");
+    if (others[r]->width != curs[r]->width || others[r]->height != curs[r]->height) return fail(ctx, HMME_ERR_ARG, "%s: pair %d: the other list's plane differs in size", who, r);
+    if (others[r]->bit_depth != fp->bit_depth) return fail(ctx, HMME_ERR_ARG, "%s: pair %d: the other list's plane holds %d-bit samples, the call asks for %d", who, r, others[r]->bit_depth, fp->bit_depth);
+  }
+  return HMME_OK;
+}
+
+// me_predict_kernel for CTUs [first, first + count) of `src` with its motion field (int16 [n_ctu][mv_per_ctu][2], device)
+int launch_predict(hmme_ctx* ctx, const hmme_plane* src, const int16_t* d_field, int mv_per_ctu, int first, int count, bool origin, const uint8_t* cur_blocks,
+                   int bias, uint8_t* dst, long dst_ctu_x, long dst_ctu_y, int dst_pitch, hipStream_t s) {
+  const dim3 grid((unsigned)count), block(256);
+#define HMME_PREDICT(T, OUT)                                                                                                              \
+  hipLaunchKernelGGL((hmme::me_predict_kernel<T, OUT>), grid, block, 0, s, src->origin(), src->pitch, d_field, mv_per_ctu, first, src->width, \
+                     src->height, src->bit_depth, cur_blocks, bias, dst, dst_ctu_x, dst_ctu_y, dst_pitch)
+  if (src->bps == 1) { if (origin) HMME_PREDICT(uint8_t, 1); else HMME_PREDICT(uint8_t, 0); }
+  else { if (origin) HMME_PREDICT(uint16_t, 1); else HMME_PREDICT(uint16_t, 0); }
+#undef HMME_PREDICT
+  HIP_TRY(ctx, hipGetLastError());
+  return HMME_OK;
+}
+}  // namespace
+
+int hmme_bipred_check(int bit_depth, int refine) {
+  char msg[256];
+  return bipred_eval(bit_depth, refine, msg, sizeof msg);
+}
+
+int hmme_predict_pairs_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_pairs, const hmme_frame_params* fp, const void* d_mv_field,
+                              int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  int rc = bi_check(ctx, "hmme_predict_pairs_device", fp, 0);
+  if (rc) return rc;
+  if (!refs || !d_outs || n_pairs < 1 || n_pairs > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "hmme_predict_pairs_device: %d pictures outside 1..%d (or a null list)", n_pairs, hmme::kMaxRefs);
+  if (!d_mv_field || (mv_per_ctu != 1 && mv_per_ctu != 64)) return fail(ctx, HMME_ERR_ARG, "hmme_predict_pairs_device: null motion field, or %d MVs per CTU (1 or 64)", mv_per_ctu);
+  for (int r = 0; r < n_pairs; ++r)
+    if (!refs[r] || !d_outs[r]) return fail(ctx, HMME_ERR_ARG, "hmme_predict_pairs_device: null plane / output image");
+  if (out_pitch_bytes < refs[0]->width * refs[0]->bps) return fail(ctx, HMME_ERR_ARG, "hmme_predict_pairs_device: output pitch %d below a picture row", out_pitch_bytes);
+  hmme_frame_params f = *fp;
+  f.search_range = 1;   // not consulted: nothing is searched
+  hipStream_t s = (hipStream_t)stream;
+  PairLaunch pl;
+  rc = pairs_begin(ctx, refs, refs, n_pairs, &f, s, &pl);
+  if (rc || pl.count == 0) return rc;
+  const size_t field = (size_t)refs[0]->n_ctu * mv_per_ctu * 2;
+  for (int r = 0; r < n_pairs && rc == HMME_OK; ++r)
+    rc = launch_predict(ctx, refs[r], (const int16_t*)d_mv_field + field * r, mv_per_ctu, pl.first, pl.count, false, nullptr, 0, (uint8_t*)d_outs[r], 0, 0,
+                        out_pitch_bytes, s);
+  return pairs_end(ctx, refs, refs, n_pairs, s, rc);
+}
+
+int hmme_predict_frame(hmme_ctx* ctx, const hmme_plane* ref, const hmme_frame_params* fp, const int16_t* mv_field, int mv_per_ctu, void* out,
+                       int out_stride) {
+  if (!ctx) return HMME_ERR_ARG;
+  int rc = bi_check(ctx, "hmme_predict_frame", fp, 0);
+  if (rc) return rc;
+  if (!ref || !mv_field || !out || (mv_per_ctu != 1 && mv_per_ctu != 64)) return fail(ctx, HMME_ERR_ARG, "hmme_predict_frame: null argument, or %d MVs per CTU (1 or 64)", mv_per_ctu);
+  if (ref->ctx != ctx) return fail(ctx, HMME_ERR_ARG, "plane belongs to another context (planes are used with the context that created them)");
+  if (out_stride < ref->width) return fail(ctx, HMME_ERR_ARG, "hmme_predict_frame: output stride %d below the picture width", out_stride);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t field_bytes = sizeof(int16_t) * 2 * (size_t)ref->n_ctu * mv_per_ctu, row = (size_t)ref->width * ref->bps;
+  rc = ensure(ctx, &ctx->d_bi[0], &ctx->bi_cap[0], field_bytes);
+  if (rc == HMME_OK) rc = ensure(ctx, &ctx->d_bi[1], &ctx->bi_cap[1], row * ref->height);
+  if (rc) return rc;
+  hipStream_t s = ctx->stream;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_bi[0], mv_field, field_bytes, hipMemcpyHostToDevice, s));
+  // the caller's image travels both ways: samples outside the CTU range come back as they were
+  HIP_TRY(ctx, hipMemcpy2DAsync(ctx->d_bi[1], row, out, (size_t)out_stride * ref->bps, row, ref->height, hipMemcpyHostToDevice, s));
+  void* img = ctx->d_bi[1];
+  rc = hmme_predict_pairs_device(ctx, &ref, 1, fp, ctx->d_bi[0], mv_per_ctu, &img, (int)row, s);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemcpy2DAsync(out, (size_t)out_stride * ref->bps, ctx->d_bi[1], row, row, ref->height, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  return HMME_OK;
+}
+
+int hmme_search_pairs_bi_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others,
+                                int n_pairs, const hmme_frame_params* fp, const void* d_other_mv, int mv_per_ctu, const void* d_center_q,
+                                const void* d_pred_q, void* d_out_mv, void* d_out_sad, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  int rc = bi_check(ctx, "hmme_search_pairs_bi_device", fp, 0);
+  if (rc == HMME_OK) rc = bi_args(ctx, "hmme_search_pairs_bi_device", curs, refs, others, n_pairs, fp, d_other_mv, mv_per_ctu);
+  if (rc) return rc;
+  if (!d_out_mv || !d_out_sad) return fail(ctx, HMME_ERR_ARG, "null output buffer");
+  hipStream_t s = (hipStream_t)stream;
+  PairLaunch pl;
+  rc = pairs_begin(ctx, curs, refs, n_pairs, fp, s, &pl);
+  if (rc || pl.count == 0) return rc;
+  for (int r = 0; r < n_pairs && rc == HMME_OK; ++r) rc = plane_wait(ctx, others[r], s);
+  const WpGeom g(refs[0]);
+  const int bias = (1 << fp->bit_depth) - 1, n_ctu = curs[0]->n_ctu, ctus_x = curs[0]->ctus_x;
+  if (rc == HMME_OK) rc = ensure(ctx, &ctx->d_wp[0], &ctx->wp_cap[0], g.plane_bytes * n_pairs);
+  if (rc == HMME_OK) rc = ensure(ctx, &ctx->d_wp[1], &ctx->wp_cap[1], g.blk_bytes * n_pairs);
+  RefSet wrefs = one_ref(nullptr), wcurs = one_ref(nullptr);
+  const size_t field = (size_t)n_ctu * mv_per_ctu * 2;
+  for (int r = 0; r < n_pairs && rc == HMME_OK; ++r) {
+    int q = 0;   // a pair before this one with the same reference has made its biased copy already
+    while (q < r && refs[q] != refs[r]) ++q;
+    if (q < r) {
+      wrefs.base[r] = wrefs.base[q];
+    } else {
+      uint8_t* plane = ctx->d_wp[0] + g.plane_bytes * r;
+      rc = weight_plane(ctx, refs[r], g, plane, 1, 0, 0, bias, s);
+      wrefs.base[r] = plane + g.origin;
+    }
+    if (rc != HMME_OK) break;
+    uint8_t* blocks = ctx->d_wp[1] + g.blk_bytes * r;   // the origin: one per pair (it depends on the pair's field)
+    rc = launch_predict(ctx, others[r], (const int16_t*)d_other_mv + field * r, mv_per_ctu, pl.first, pl.count, true, curs[r]->d_blocks, bias, blocks,
+                        hmme::kBlkBytes16, (long)ctus_x * hmme::kBlkBytes16, 128, s);
+    wcurs.base[r] = blocks;
+  }
+  FramePlan plan;
+  if (rc == HMME_OK) rc = prep_jobs(ctx, curs[0], fp, d_pred_q, pl.first, pl.count, n_pairs, s, &plan, true, d_center_q);
+  if (rc == HMME_OK) rc = run_search(ctx, wcurs, ctus_x, wrefs, g.pitch, fp, plan, (int16_t*)d_out_mv, (uint32_t*)d_out_sad, s);
+  return pairs_end(ctx, curs, refs, n_pairs, s, rc, others);
+}
+
+int hmme_refine_pairs_bi_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others,
+                                int n_pairs, const hmme_frame_params* fp, const void* d_other_mv, int mv_per_ctu, const void* d_center_q,
+                                const void* d_pred_q, const void* d_int_mv, int use_hadamard, void* d_out_qmv, void* d_out_cost, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  int rc = bi_check(ctx, "hmme_refine_pairs_bi_device", fp, 1);
+  if (rc == HMME_OK) rc = bi_args(ctx, "hmme_refine_pairs_bi_device", curs, refs, others, n_pairs, fp, d_other_mv, mv_per_ctu);
+  if (rc) return rc;
+  if (!d_int_mv || !d_out_qmv || !d_out_cost) return fail(ctx, HMME_ERR_ARG, "null buffer");
+  hipStream_t s = (hipStream_t)stream;
+  PairLaunch pl;
+  rc = pairs_begin(ctx, curs, refs, n_pairs, fp, s, &pl);
+  if (rc || pl.count == 0) return rc;
+  for (int r = 0; r < n_pairs && rc == HMME_OK; ++r) rc = plane_wait(ctx, others[r], s);
+  const int jobs = pl.count * n_pairs, had = use_hadamard ? 1 : 0, src_wide = curs[0]->bps == 2 ? 1 : 0;
+  const int bias = (1 << fp->bit_depth) - 1, n_ctu = curs[0]->n_ctu;
+  const WpGeom g(refs[0]);
+  if (rc == HMME_OK) rc = build_frac_cover(ctx);
+  if (rc == HMME_OK) {
+    size_t cap = ctx->frac_jobs_bytes;
+    rc = ensure(ctx, (uint8_t**)&ctx->d_frac_jobs, &cap, sizeof(MeJob) * (size_t)jobs + 64, sizeof(MeJob) * (size_t)pl.count * hmme::kMaxRefs + 4096);
+    ctx->frac_jobs_bytes = cap;
+    ctx->frac_jobs_tag.valid = false;   // this launch writes its own table
+  }
+  if (rc == HMME_OK && !src_wide) rc = ensure(ctx, &ctx->d_wp[2], &ctx->wp_cap[2], g.plane_bytes * n_pairs);
+  if (rc == HMME_OK) rc = ensure(ctx, &ctx->d_wp[3], &ctx->wp_cap[3], g.plane_bytes * n_pairs);
+  RefSet c = one_ref(nullptr), rf = one_ref(nullptr);
+  const size_t field = (size_t)n_ctu * mv_per_ctu * 2;
+  for (int r = 0; r < n_pairs && rc == HMME_OK; ++r) {
+    if (src_wide) {
+      rf.base[r] = pl.refs.base[r];   // the RAW reference is interpolated: a u16 plane serves as it is
+    } else {
+      int q = 0;
+      while (q < r && refs[q] != refs[r]) ++q;
+      if (q < r) rf.base[r] = rf.base[q];
+      else {
+        uint8_t* plane = ctx->d_wp[2] + g.plane_bytes * r;
+        rc = weight_plane(ctx, refs[r], g, plane, 1, 0, 0, 0, s);
+        rf.base[r] = plane + g.origin;
+      }
+      if (rc != HMME_OK) break;
+    }
+    // the origin in a padded plane's layout: only the CTU blocks are written and read (a partial CTU's block ends 63 samples into the
+    // 128 / 80-sample margins at most)
+    uint8_t* plane = ctx->d_wp[3] + g.plane_bytes * r + g.origin;
+    rc = launch_predict(ctx, others[r], (const int16_t*)d_other_mv + field * r, mv_per_ctu, pl.first, pl.count, true, curs[r]->d_blocks, bias, plane, 128,
+                        64L * g.pitch, g.pitch, s);
+    c.base[r] = plane;
+  }
+  if (rc == HMME_OK) {
+    // the job table is always written: it carries the window centres (FracPrep derives windows from predictors only)
+    const int grid = frac_grid(ctx, 1, had, jobs);
+    const bool walk = grid < jobs;
+    uint32_t* counter = (uint32_t*)((uint8_t*)ctx->d_frac_jobs + ((sizeof(MeJob) * (size_t)jobs + 15) & ~(size_t)15));
+    hipLaunchKernelGGL(hmme::me_prep_jobs_kernel, dim3((jobs + 255) / 256), dim3(256), 0, s, (MeJob*)ctx->d_frac_jobs, (const int16_t*)d_pred_q, pl.first,
+                       pl.count, n_pairs, curs[0]->width, curs[0]->height, fp->search_range, 0, jobs, 0, counter, (const int16_t*)d_center_q);
+    rc = frac_lds_optin(ctx, 1, had, 1);
+    if (rc == HMME_OK) {
+      // (prep: the order the jobs are dealt in, me_frac_deal; CTU ranges beyond 16 bits keep the plain order)
+      const bool packable = pl.count <= 0xffff && pl.first <= 0xffff;
+      const hmme::FracPrep prep = packable ? hmme::FracPrep{nullptr, (uint32_t)pl.first | (uint32_t)pl.count << 16, (uint32_t)curs[0]->width | (uint32_t)curs[0]->height << 16, fp->search_range} : kNoPrep;
+      const hmme::FracWp fw = {1.f, 0.f, (float)bias};
+      hipLaunchKernelGGL(frac_kernel(1, had, 1), dim3(grid), dim3(hmme::frac_threads(2)), hmme::frac_lds_bytes(2), s, c, g.pitch, rf, g.pitch,
+                         (const MeJob*)ctx->d_frac_jobs, prep, jobs, walk ? counter : (uint32_t*)nullptr, ctx->d_frac_cover, (const int16_t*)d_int_mv,
+                         ctx->lambda_q16, fp->bit_depth, fw, (int16_t*)d_out_qmv, (uint32_t*)d_out_cost);
+      const hipError_t e = hipGetLastError();
+      if (e != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "bi-prediction refinement launch -> %s", hipGetErrorString(e));
+    }
+  }
+  return pairs_end(ctx, curs, refs, n_pairs, s, rc, others);
+}
+
+namespace {
+// host-facing bi calls: the motion field and the centres go up into d_bi[0], the predictors into d_pred
+int bi_stage(hmme_ctx* ctx, const hmme_plane* cur, const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q, const int16_t* pred_q,
+             const void** d_field, const void** d_center, const void** d_pred, hipStream_t s) {
+  const size_t n_ctu = (size_t)cur->n_ctu, field_bytes = sizeof(int16_t) * 2 * n_ctu * mv_per_ctu, pq_bytes = sizeof(int16_t) * 2 * n_ctu;
+  int rc = ensure(ctx, &ctx->d_bi[0], &ctx->bi_cap[0], field_bytes + pq_bytes);
+  if (rc == HMME_OK) rc = ensure_frame_buffers(ctx, n_ctu);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_bi[0], other_mv, field_bytes, hipMemcpyHostToDevice, s));
+  if (center_q) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_bi[0] + field_bytes, center_q, pq_bytes, hipMemcpyHostToDevice, s));
+  if (pred_q) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_pred, pred_q, pq_bytes, hipMemcpyHostToDevice, s));
+  *d_field = ctx->d_bi[0];
+  *d_center = center_q ? ctx->d_bi[0] + field_bytes : nullptr;
+  *d_pred = pred_q ? ctx->d_pred : nullptr;
+  return HMME_OK;
+}
+}  // namespace
+
+int hmme_search_frame_bi(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
+                         const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q, const int16_t* pred_q, int16_t* out_mv, uint32_t* out_sad) {
+  if (!ctx) return HMME_ERR_ARG;
+  int rc = bi_check(ctx, "hmme_search_frame_bi", fp, 0);
+  if (rc == HMME_OK) rc = bi_args(ctx, "hmme_search_frame_bi", &cur, &ref, &other, 1, fp, other_mv, mv_per_ctu);
+  if (rc) return rc;
+  int first, count;
+  rc = check_frame_args(ctx, cur, ref, fp, &first, &count);
+  if (rc) return rc;
+  if (!out_mv || !out_sad) return fail(ctx, HMME_ERR_ARG, "null output buffer");
+  if (count == 0) return HMME_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const void *d_field, *d_center, *d_pred;
+  rc = bi_stage(ctx, cur, other_mv, mv_per_ctu, center_q, pred_q, &d_field, &d_center, &d_pred, s);
+  if (rc == HMME_OK) rc = hmme_search_pairs_bi_device(ctx, &cur, &ref, &other, 1, fp, d_field, mv_per_ctu, d_center, d_pred, ctx->d_mv, ctx->d_sad, s);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(out_mv, ctx->d_mv, sizeof(int16_t) * 2 * HMME_NUM_CTU_PARTS * (size_t)count, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipMemcpyAsync(out_sad, ctx->d_sad, sizeof(uint32_t) * HMME_NUM_CTU_PARTS * (size_t)count, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  return HMME_OK;
+}
+
+int hmme_refine_frame_bi(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
+                         const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q, const int16_t* pred_q, const int16_t* int_mv,
+                         int use_hadamard, int16_t* out_qmv, uint32_t* out_cost) {
+  if (!ctx) return HMME_ERR_ARG;
+  int rc = bi_check(ctx, "hmme_refine_frame_bi", fp, 1);
+  if (rc == HMME_OK) rc = bi_args(ctx, "hmme_refine_frame_bi", &cur, &ref, &other, 1, fp, other_mv, mv_per_ctu);
+  if (rc) return rc;
+  int first, count;
+  rc = check_frame_args(ctx, cur, ref, fp, &first, &count);
+  if (rc) return rc;
+  if (!int_mv || !out_qmv || !out_cost) return fail(ctx, HMME_ERR_ARG, "null buffer");
+  if (count == 0) return HMME_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  rc = ensure_refine_buffers(ctx, (size_t)HMME_NUM_CTU_PARTS * cur->n_ctu);
+  if (rc) return rc;
+  hipStream_t s = ctx->stream;
+  const void *d_field, *d_center, *d_pred;
+  rc = bi_stage(ctx, cur, other_mv, mv_per_ctu, center_q, pred_q, &d_field, &d_center, &d_pred, s);
+  if (rc) return rc;
+  const size_t res = (size_t)HMME_NUM_CTU_PARTS * count;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_imv, int_mv, sizeof(int16_t) * 2 * res, hipMemcpyHostToDevice, s));
+  rc = hmme_refine_pairs_bi_device(ctx, &cur, &ref, &other, 1, fp, d_field, mv_per_ctu, d_center, d_pred, ctx->d_imv, use_hadamard, ctx->d_qmv, ctx->d_fcost, s);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(out_qmv, ctx->d_qmv, sizeof(int16_t) * 2 * res, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipMemcpyAsync(out_cost, ctx->d_fcost, sizeof(uint32_t) * res, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  return HMME_OK;
+}
+
+int hmme_test_time_bipred_origin(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* other, const void* d_other_mv, int mv_per_ctu, void* stream,
+                                 int reps, float* avg_ms) {
+  if (!ctx) return HMME_ERR_ARG;
+  if (!cur || !other || !d_other_mv || !avg_ms || reps < 1 || (mv_per_ctu != 1 && mv_per_ctu != 64)) return fail(ctx, HMME_ERR_ARG, "hmme_test_time_bipred_origin: bad argument");
+  hmme_frame_params fp = {1, 0, cur->bit_depth, 0, -1};
+  int rc = bi_check(ctx, "hmme_test_time_bipred_origin", &fp, 0);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  PairLaunch pl;
+  rc = pairs_begin(ctx, &cur, &other, 1, &fp, s, &pl);
+  if (rc) return rc;
+  const WpGeom g(cur);
+  rc = ensure(ctx, &ctx->d_wp[1], &ctx->wp_cap[1], g.blk_bytes);
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  hipError_t e = hipSuccess;
+  float ms = 0.f;
+  if (rc == HMME_OK && (e = hipEventCreate(&e0)) == hipSuccess && (e = hipEventCreate(&e1)) == hipSuccess) {
+    e = hipEventRecord(e0, s);
+    for (int i = 0; i < reps && rc == HMME_OK; ++i)
+      rc = launch_predict(ctx, other, (const int16_t*)d_other_mv, mv_per_ctu, 0, cur->n_ctu, true, cur->d_blocks, (1 << cur->bit_depth) - 1, ctx->d_wp[1],
+                          hmme::kBlkBytes16, (long)cur->ctus_x * hmme::kBlkBytes16, 128, s);
+    if (e == hipSuccess) e = hipEventRecord(e1, s);
+    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+  }
+  if (e0) hipEventDestroy(e0);
+  if (e1) hipEventDestroy(e1);
+  if (rc == HMME_OK && e != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "timing the origin pass: %s", hipGetErrorString(e));
+  if (rc == HMME_OK) *avg_ms = ms / reps;
+  return pairs_end(ctx, &cur, &other, 1, s, rc);
 }
 
 int hmme_test_time_weight_passes(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_weight* wp, void* stream, int reps,

@@ -631,7 +631,8 @@ __host__ __device__ inline void set_search_range(int pred_x, int pred_y, int sr,
 // 0 for the refinement kernel, which takes job blockIdx.x
 // job_counter (may be null): the refinement kernel's work counter, reset here for the launch that follows on the same stream
 __global__ void me_prep_jobs_kernel(MeJob* jobs, const int16_t* __restrict__ pred_q, int ctu_first, int ctu_count,
-                                    int n_refs, int pic_w, int pic_h, int sr, int job0, int n_jobs, int xcd_order, uint32_t* job_counter) {
+                                    int n_refs, int pic_w, int pic_h, int sr, int job0, int n_jobs, int xcd_order, uint32_t* job_counter,
+                                    const int16_t* __restrict__ center_q) {
   const int li = blockIdx.x * blockDim.x + threadIdx.x;
   if (li == 0 && job_counter) *job_counter = 0;
   if (li >= n_jobs) return;
@@ -642,8 +643,10 @@ __global__ void me_prep_jobs_kernel(MeJob* jobs, const int16_t* __restrict__ pre
   const int cu_x = (ctu % ctus_x) * 64, cu_y = (ctu / ctus_x) * 64;
   const long pq = 2 * ((long)r * n_ctu + ctu);
   const int px = pred_q ? pred_q[pq] : 0, py = pred_q ? pred_q[pq + 1] : 0;
+  // center_q (null = the predictor): the window's centre of a bi-prediction pass, as in me_prep_jobs16_kernel (the refinement's job table)
+  const int wx_q = center_q ? center_q[pq] : px, wy_q = center_q ? center_q[pq + 1] : py;
   int ltx, lty, rbx, rby;
-  set_search_range(px, py, sr, cu_x, cu_y, pic_w, pic_h, ltx, lty, rbx, rby);
+  set_search_range(wx_q, wy_q, sr, cu_x, cu_y, pic_w, pic_h, ltx, lty, rbx, rby);
   MeJob j;
   j.ctu_x = (int16_t)(cu_x | r); j.ctu_y = (int16_t)cu_y;
   j.lt_x = (int16_t)ltx; j.lt_y = (int16_t)lty; j.rb_x = (int16_t)rbx; j.rb_y = (int16_t)rby;
@@ -974,7 +977,7 @@ __global__ void me_publish_kernel(volatile uint32_t* done_flag, uint32_t seq) {
 // workgroups of a launch is dealt in finer pieces, hmme.hip plan_tail)
 __global__ void me_prep_jobs16_kernel(MeJob16* jobs, int* first_strip_of_job, const int16_t* __restrict__ pred_q,
                                       int ctu_first, int ctu_count, int n_refs, int pic_w, int pic_h, int sr, int n_strips_head, int rows_max,
-                                      int tail_first, int tail_strips) {
+                                      int tail_first, int tail_strips, const int16_t* __restrict__ center_q) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= ctu_count * n_refs) return;
   const int r = i / ctu_count;
@@ -983,8 +986,11 @@ __global__ void me_prep_jobs16_kernel(MeJob16* jobs, int* first_strip_of_job, co
   const int cu_x = (ctu % ctus_x) * 64, cu_y = (ctu / ctus_x) * 64;
   const long pq = 2 * ((long)r * n_ctu + ctu);
   const int px = pred_q ? pred_q[pq] : 0, py = pred_q ? pred_q[pq + 1] : 0;
+  // center_q (same layout as pred_q; null = the predictor): the window's centre where it is not the predictor -- HM's bi-prediction pass
+  // searches around the list's current MV and prices MV bits against the AMVP predictor (TEncSearch.cpp:3726-3737)
+  const int wx_q = center_q ? center_q[pq] : px, wy_q = center_q ? center_q[pq + 1] : py;
   int ltx, lty, rbx, rby;
-  set_search_range(px, py, sr, cu_x, cu_y, pic_w, pic_h, ltx, lty, rbx, rby);
+  set_search_range(wx_q, wy_q, sr, cu_x, cu_y, pic_w, pic_h, ltx, lty, rbx, rby);
   MeJob j;
   j.ctu_x = (int16_t)(cu_x | r); j.ctu_y = (int16_t)cu_y;
   j.lt_x = (int16_t)ltx; j.lt_y = (int16_t)lty; j.rb_x = (int16_t)rbx; j.rb_y = (int16_t)rby;
@@ -2161,6 +2167,90 @@ me_weight_plane_kernel(const uint8_t* __restrict__ src, int src_pitch, uint8_t* 
   uint4* out = (uint4*)(dst + (long)blockIdx.y * dst_pitch + x0 * 2);
 #pragma unroll
   for (int q = 0; q < N / 8; ++q) out[q] = make_uint4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
+}
+
+// ---- motion compensation on whole pictures (hmme_predict_pairs_device) and bi-prediction origins (hmme_search_pairs_bi_device /
+// hmme_refine_pairs_bi_device) -------------------------------------------------------------------------------------------------------------
+// luma DCT-IF taps by quarter-pel phase (TComInterpolationFilter.cpp:57-63); phase 0 is the copy written as a filter: the two-stage formula
+// below then yields the sample itself, which is what HM's filterCopy / single-stage paths produce
+__constant__ int kLumaTaps[4][8] = {{0, 0, 0, 64, 0, 0, 0, 0}, {-1, 4, -10, 58, 17, -5, 1, 0}, {-1, 4, -11, 40, 40, -11, 4, -1}, {0, 1, -5, 17, 58, -10, 4, -1}};
+
+// The luma prediction of one CTU per workgroup from a MOTION FIELD: quarter-pel MVs int16 [n_ctu][mv_per_ctu][2], mv_per_ctu = 1 (one MV
+// for the CTU: HM's 64x64 2Nx2N) or 64 (one per 8x8 block, raster order inside the CTU).  Every MV is first clamped like
+// TComDataCU::clipMv for the CTU's position (clip_mv_q), so the 15 x 15 patch of an 8x8 block -- rows / columns -3 .. +11 around the
+// displaced block -- stays within 75 samples of the picture: inside the plane's 128 / 80-sample margins.  A wave takes one 8x8 block at a
+// time (16 of the CTU's 64): the patch goes through LDS (rows of 15 consecutive samples per load), the horizontal pass writes the 14-bit
+// intermediate (15 rows x 8), the vertical pass rounds and clips -- TComPrediction::xPredInterBlk with bi = false
+// (TComPrediction.cpp:590-594, :669) in integer arithmetic, int32 sums: bit-identical to hmo_pred_block_qpel at every phase.
+//   OUT = 0: the prediction, samples of the plane's type, into a pitched image at the block's picture position; samples beyond the
+//            picture are not written (blocks wholly outside it are skipped)
+//   OUT = 1: the bi-prediction origin 2 * cur - pred + bias as u16 (TEncSearch.cpp:3702-3712, TComYuv::removeHighFreq, unclipped), cur from
+//            the current picture's CTU-blocked copy -- partial edge CTUs are whole blocks there (edge replication), and so they are here.
+//            The block of CTU (cx, cy) starts at dst + cy * dst_ctu_y + cx * dst_ctu_x, its rows dst_pitch bytes apart: the CTU-blocked
+//            layout the search reads (8192, ctus_x * 8192, 128) or a padded plane's (128, 64 * pitch, pitch), which the refinement reads
+// All stores are 8 consecutive samples per block row.  Bandwidth is not tuned further: the pass moves tens of MB beside a search of
+// milliseconds.
+template <typename SrcT, int OUT>
+__global__ void __launch_bounds__(256)
+me_predict_kernel(const uint8_t* __restrict__ ref_origin, int ref_pitch, const int16_t* __restrict__ mv_field, int mv_per_ctu, int ctu_first,
+                  int pic_w, int pic_h, int bit_depth, const uint8_t* __restrict__ cur_blocks, int bias, uint8_t* __restrict__ dst,
+                  long dst_ctu_x, long dst_ctu_y, int dst_pitch) {
+  __shared__ int16_t patch[4][15 * 16];
+  __shared__ int16_t mid[4][15 * 8];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int ctus_x = (pic_w + 63) >> 6;
+  const int ctu = ctu_first + blockIdx.x;
+  const int cx = ctu % ctus_x, cy = ctu / ctus_x, cu_x = cx * 64, cu_y = cy * 64;
+  const int head = 14 - bit_depth > 2 ? 14 - bit_depth : 2;   // headRoom (IF_INTERNAL_PREC - bitDepth, at least 2)
+  const int sh1 = 6 - head, off1 = -(8192 << sh1), sh2 = 6 + head, off2 = (1 << (sh2 - 1)) + (8192 << 6);
+  const int maxv = (1 << bit_depth) - 1;
+#pragma unroll 1
+  for (int it = 0; it < 16; ++it) {
+    const int b = it * 4 + wave, bx = (b & 7) * 8, by = (b >> 3) * 8;   // the four waves: four blocks side by side
+    const int16_t* mv = mv_field + ((long)ctu * mv_per_ctu + (mv_per_ctu == 1 ? 0 : b)) * 2;
+    int mx = mv[0], my = mv[1];
+    clip_mv_q(mx, my, cu_x, cu_y, pic_w, pic_h);
+    const bool live = OUT == 1 || (cu_x + bx < pic_w && cu_y + by < pic_h);   // wave-uniform
+    if (live) {
+      const uint8_t* src = ref_origin + (long)(cu_y + by + (my >> 2) - 3) * ref_pitch + (long)(cu_x + bx + (mx >> 2) - 3) * (long)sizeof(SrcT);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int e = lane + 64 * k, r = e / 15, c = e - r * 15;
+        if (e < 225) patch[wave][r * 16 + c] = (int16_t)((const SrcT*)(src + (long)r * ref_pitch))[c];
+      }
+    }
+    __syncthreads();
+    if (live) {
+      const int* ch = kLumaTaps[mx & 3];
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const int o = lane + 64 * k, r = o >> 3, c = o & 7;
+        if (o < 120) {
+          int sum = 0;
+#pragma unroll
+          for (int t = 0; t < 8; ++t) sum += ch[t] * (int)patch[wave][r * 16 + c + t];
+          mid[wave][o] = (int16_t)((sum + off1) >> sh1);
+        }
+      }
+    }
+    __syncthreads();
+    if (live) {
+      const int* cv = kLumaTaps[my & 3];
+      const int r = lane >> 3, c = lane & 7;
+      int sum = 0;
+#pragma unroll
+      for (int t = 0; t < 8; ++t) sum += cv[t] * (int)mid[wave][(r + t) * 8 + c];
+      int v = (sum + off2) >> sh2;
+      v = v < 0 ? 0 : (v > maxv ? maxv : v);
+      if (OUT == 0) {
+        const int x = cu_x + bx + c, y = cu_y + by + r;
+        if (x < pic_w && y < pic_h) ((SrcT*)(dst + (long)y * dst_pitch))[x] = (SrcT)v;
+      } else {
+        const int cur = (int)((const SrcT*)cur_blocks)[(long)ctu * 4096 + (by + r) * 64 + bx + c];
+        ((uint16_t*)(dst + cy * dst_ctu_y + cx * dst_ctu_x + (long)(by + r) * dst_pitch))[bx + c] = (uint16_t)(2 * cur - v + bias);
+      }
+    }
+  }
 }
 
 }  // namespace hmme

@@ -23,9 +23,11 @@ SYMBOLS = ["hmme_create", "hmme_destroy", "hmme_last_error", "hmme_device_info",
            "hmme_search_frame_multi_device", "hmme_refine_frame", "hmme_refine_frame_multi_device",
            "hmme_search_pairs_device", "hmme_refine_pairs_device", "hmme_plane_upload_async",
            "hmme_upload_status", "hmme_abi_version", "hmme_build_id", "hmme_device_index", "hmme_set_error_printing",
-           "hmme_weight_check", "hmme_search_pairs_w_device", "hmme_refine_pairs_w_device", "hmme_search_frame_w", "hmme_refine_frame_w"]
+           "hmme_weight_check", "hmme_search_pairs_w_device", "hmme_refine_pairs_w_device", "hmme_search_frame_w", "hmme_refine_frame_w",
+           "hmme_bipred_check", "hmme_predict_pairs_device", "hmme_predict_frame", "hmme_search_pairs_bi_device", "hmme_refine_pairs_bi_device",
+           "hmme_search_frame_bi", "hmme_refine_frame_bi"]
 # test / measurement entry points (include/hmme_test.h): not part of the boundary
-TEST_SYMBOLS = ["hmme_test_time_search_kernel", "hmme_test_device_address", "hmme_test_frac_deal", "hmme_test_tail_plan", "hmme_test_time_weight_passes"]
+TEST_SYMBOLS = ["hmme_test_time_search_kernel", "hmme_test_device_address", "hmme_test_frac_deal", "hmme_test_tail_plan", "hmme_test_time_weight_passes", "hmme_test_time_bipred_origin"]
 ABI_VERSION = 6   # HMME_ABI_VERSION of the include/hmme.h these bindings were written against
 
 
@@ -124,6 +126,14 @@ def load():
     L.hmme_search_frame_w.argtypes = [vp, vp, vp, C.POINTER(FrameParams), C.POINTER(Weight), vp, vp, vp]
     L.hmme_refine_frame_w.argtypes = [vp, vp, vp, C.POINTER(FrameParams), C.POINTER(Weight), vp, vp, i, vp, vp]
     L.hmme_test_time_weight_passes.argtypes = [vp, vp, vp, C.POINTER(Weight), vp, i, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.hmme_bipred_check.argtypes = [i, i]
+    L.hmme_predict_pairs_device.argtypes = [vp, C.POINTER(vp), i, C.POINTER(FrameParams), vp, i, C.POINTER(vp), i, vp]
+    L.hmme_predict_frame.argtypes = [vp, vp, C.POINTER(FrameParams), vp, i, vp, i]
+    L.hmme_search_pairs_bi_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, C.POINTER(FrameParams), vp, i, vp, vp, vp, vp, vp]
+    L.hmme_refine_pairs_bi_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, C.POINTER(FrameParams), vp, i, vp, vp, vp, i, vp, vp, vp]
+    L.hmme_search_frame_bi.argtypes = [vp, vp, vp, vp, C.POINTER(FrameParams), vp, i, vp, vp, vp, vp]
+    L.hmme_refine_frame_bi.argtypes = [vp, vp, vp, vp, C.POINTER(FrameParams), vp, i, vp, vp, vp, i, vp, vp]
+    L.hmme_test_time_bipred_origin.argtypes = [vp, vp, vp, vp, i, vp, i, C.POINTER(C.c_float)]
     L.hmme_upload_status.argtypes = [vp, vp]
     L.hmme_test_device_address.argtypes = [vp, vp]
     L.hmme_test_device_address.restype = C.c_uint64
@@ -432,6 +442,97 @@ class Engine:
         self._check(self.L.hmme_test_time_weight_passes(self.h, cur.h, ref.h, C.byref(w), stream, reps, C.byref(a), C.byref(b)))
         return float(a.value), float(b.value)
 
+    # ---- motion compensation and the bi-prediction pass on whole pictures (include/hmme.h, "bi-prediction on whole pictures") ----
+    @staticmethod
+    def _field(mv_field, n_ctu):
+        """a host motion field int16[n_ctu, mv_per_ctu, 2] (or [n_ctu, 2]: one MV per CTU) -> (contiguous array, mv_per_ctu)"""
+        f = np.ascontiguousarray(mv_field, dtype=np.int16)
+        if f.ndim == 2:
+            f = f.reshape(f.shape[0], 1, 2)
+        assert f.shape[0] == n_ctu and f.shape[1] in (1, 64) and f.shape[2] == 2
+        return f, int(f.shape[1])
+
+    @staticmethod
+    def _pq(a, n_ctu):
+        if a is None:
+            return None, None
+        a = np.ascontiguousarray(a, dtype=np.int16)
+        assert a.shape == (n_ctu, 2)
+        return a, a.ctypes.data
+
+    def predict_pairs_device(self, refs, fp, d_mv_field, mv_per_ctu, d_outs, out_pitch_bytes, stream=0):
+        """hmme_predict_pairs_device: the luma prediction of up to 16 pictures from their motion fields; d_outs = one device image address per picture"""
+        assert len(refs) == len(d_outs)
+        ra = (C.c_void_p * len(refs))(*[r.h for r in refs])
+        oa = (C.c_void_p * len(d_outs))(*[int(o) for o in d_outs])
+        self._check(self.L.hmme_predict_pairs_device(self.h, ra, len(refs), C.byref(fp), d_mv_field, int(mv_per_ctu), oa, int(out_pitch_bytes), stream))
+
+    def predict_frame(self, ref, mv_field, out=None, ctu_first=0, ctu_count=-1):
+        """hmme_predict_frame: motion-compensated luma prediction of one picture -> [height, width] array of the plane's sample type (u8 / u16).
+        mv_field: int16[n_ctu, 2] or [n_ctu, 1 | 64, 2] quarter pels; `out` (same shape and type) keeps its samples outside the CTU range"""
+        n = self.L.hmme_num_ctus(ref.width, ref.height)
+        f, per = self._field(mv_field, n)
+        dt = np.uint8 if ref.bit_depth == 8 else np.uint16
+        if out is None:
+            out = np.zeros((ref.height, ref.width), dt)
+        assert out.dtype == dt and out.shape == (ref.height, ref.width) and out.flags.c_contiguous
+        fp = FrameParams(1, 0, ref.bit_depth, ctu_first, ctu_count)
+        self._check(self.L.hmme_predict_frame(self.h, ref.h, C.byref(fp), f.ctypes.data, per, out.ctypes.data, out.shape[1]))
+        return out
+
+    def search_pairs_bi_device(self, curs, refs, others, fp, d_other_mv, mv_per_ctu, d_center, d_pred, d_mv, d_sad, stream=0):
+        """hmme_search_pairs_bi_device: the bi-prediction pass of up to 16 pairs in one launch (origin 2 * cur - prediction of others[i])"""
+        assert len(curs) == len(refs) == len(others)
+        ca = (C.c_void_p * len(curs))(*[c.h for c in curs])
+        ra = (C.c_void_p * len(refs))(*[r.h for r in refs])
+        oa = (C.c_void_p * len(others))(*[o.h for o in others])
+        self._check(self.L.hmme_search_pairs_bi_device(self.h, ca, ra, oa, len(refs), C.byref(fp), d_other_mv, int(mv_per_ctu), d_center, d_pred,
+                                                       d_mv, d_sad, stream))
+
+    def refine_pairs_bi_device(self, curs, refs, others, fp, d_other_mv, mv_per_ctu, d_center, d_pred, d_int_mv, use_hadamard, d_qmv, d_cost, stream=0):
+        assert len(curs) == len(refs) == len(others)
+        ca = (C.c_void_p * len(curs))(*[c.h for c in curs])
+        ra = (C.c_void_p * len(refs))(*[r.h for r in refs])
+        oa = (C.c_void_p * len(others))(*[o.h for o in others])
+        self._check(self.L.hmme_refine_pairs_bi_device(self.h, ca, ra, oa, len(refs), C.byref(fp), d_other_mv, int(mv_per_ctu), d_center, d_pred,
+                                                       d_int_mv, int(use_hadamard), d_qmv, d_cost, stream))
+
+    def search_frame_bi(self, cur, ref, other, sr, other_mv, center_q=None, pred_q=None, fen=1, ctu_first=0, ctu_count=-1):
+        """hmme_search_frame_bi: one pair, host arrays -> (mv int16[count,593,2], sad uint32[count,593]).  other_mv: the motion field of `other`
+        (int16[n_ctu, 2] or [n_ctu, 1 | 64, 2]); center_q: window centres int16[n_ctu, 2] (None: the predictors)"""
+        n = self.L.hmme_num_ctus(cur.width, cur.height)
+        count = n - ctu_first if ctu_count < 0 else ctu_count
+        fp = FrameParams(sr, int(fen), cur.bit_depth, ctu_first, count)
+        f, per = self._field(other_mv, n)
+        cq, cptr = self._pq(center_q, n)
+        pq, pptr = self._pq(pred_q, n)
+        mv = np.zeros((count, NUM_PARTS, 2), np.int16)
+        sad = np.zeros((count, NUM_PARTS), np.uint32)
+        self._check(self.L.hmme_search_frame_bi(self.h, cur.h, ref.h, other.h, C.byref(fp), f.ctypes.data, per, cptr, pptr, mv.ctypes.data, sad.ctypes.data))
+        return mv, sad
+
+    def refine_frame_bi(self, cur, ref, other, sr, other_mv, int_mv, center_q=None, pred_q=None, use_hadamard=True, ctu_first=0, ctu_count=-1):
+        """hmme_refine_frame_bi: xPatternSearchFracDIF of integer winners against the bi-prediction origin -> (qmv int16[count,593,2], cost uint32[count,593])"""
+        n = self.L.hmme_num_ctus(cur.width, cur.height)
+        count = n - ctu_first if ctu_count < 0 else ctu_count
+        fp = FrameParams(sr, 1, cur.bit_depth, ctu_first, count)
+        f, per = self._field(other_mv, n)
+        cq, cptr = self._pq(center_q, n)
+        pq, pptr = self._pq(pred_q, n)
+        int_mv = np.ascontiguousarray(int_mv, dtype=np.int16)
+        assert int_mv.shape == (count, NUM_PARTS, 2)
+        qmv = np.zeros((count, NUM_PARTS, 2), np.int16)
+        cost = np.zeros((count, NUM_PARTS), np.uint32)
+        self._check(self.L.hmme_refine_frame_bi(self.h, cur.h, ref.h, other.h, C.byref(fp), f.ctypes.data, per, cptr, pptr, int_mv.ctypes.data,
+                                                int(use_hadamard), qmv.ctypes.data, cost.ctypes.data))
+        return qmv, cost
+
+    def time_bipred_origin(self, cur, other, d_other_mv, mv_per_ctu, stream=0, reps=5):
+        """device time in ms of the origin pass of a bi-prediction search on its own (whole picture)"""
+        ms = C.c_float()
+        self._check(self.L.hmme_test_time_bipred_origin(self.h, cur.h, other.h, d_other_mv, int(mv_per_ctu), stream, reps, C.byref(ms)))
+        return float(ms.value)
+
     def upload_status(self, stream=0):
         """waits for `stream`; raises if an asynchronous upload carried an out-of-range sample"""
         self._check(self.L.hmme_upload_status(self.h, stream))
@@ -461,6 +562,12 @@ def weight_check(bit_depth, wp, refine=False):
     at this bit depth (pure host arithmetic: needs no GPU)"""
     w = Weight(*[int(v) for v in wp])
     return int(load().hmme_weight_check(int(bit_depth), C.byref(w), 1 if refine else 0))
+
+
+def bipred_check(bit_depth, refine=False):
+    """hmme_bipred_check: 0, or the HMME_ERR_* code with which the whole-picture bi-prediction calls refuse this bit depth
+    (pure host arithmetic: needs no GPU)"""
+    return int(load().hmme_bipred_check(int(bit_depth), 1 if refine else 0))
 
 
 def ocl_compat_params(lt_x, lt_y, sr):

@@ -22,6 +22,9 @@
  *   hmme_search_pairs_w_device, <- the same in a slice with explicit weighted prediction (TEncSearch::setWpScalingDistParam,
  *   hmme_refine_pairs_w_device,    TEncSearch.cpp:5594-5635; TComRdCostWeightPrediction.cpp:55-90, :407-470), one weight per pair
  *   hmme_search_frame_w, hmme_refine_frame_w
+ *   hmme_predict_pairs_device,    <- motion compensation (TComPrediction::xPredInterBlk, TComPrediction.cpp:590-594, :669) and the bi-prediction
+ *   hmme_search_pairs_bi_device,     pass of xMotionEstimation (origin 2*org - pred_other, TEncSearch.cpp:3702-3712; window around the list's
+ *   hmme_refine_pairs_bi_device, ... MV, TEncSearch.cpp:3726-3737) on whole pictures and picture pairs
  *   hmme_plane_*           <- the padded reference plane calcMotionVectors reads
  *                             (TComPicYuv, TLibCommon/TComPicYuv.cpp:91-92, 214-262); hmme_plane_upload_* take what
  *                             TVideoIOYuv::read delivers (TVideoIOYuv.cpp:247, :680: 8-bit or 16-bit little-endian samples)
@@ -317,6 +320,69 @@ int hmme_search_frame_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* 
                         const int16_t* pred_q, int16_t* out_mv, uint32_t* out_sad);
 int hmme_refine_frame_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_frame_params* fp, const hmme_weight* wp,
                         const int16_t* pred_q, const int16_t* int_mv, int use_hadamard, int16_t* out_qmv, uint32_t* out_cost);
+
+/* ---- bi-prediction on whole pictures and picture pairs --------------------------------------------------------
+ * The picture-level siblings of the bBi pass that hmme_search_ctu / hmme_refine_ctu serve one CTU at a time (TEncSearch.cpp:3702-3712,
+ * :3726-3737, :3798; new entry points, no struct and no existing entry point changed, so HMME_ABI_VERSION stays 6), and the
+ * motion compensation they are built on.
+ *
+ * Motion field.  d_mv_field / d_other_mv: quarter-pel MVs int16[n_pairs][n_ctu][mv_per_ctu][2] (hor, ver), n_ctu = ALL CTUs of the
+ * picture in raster order whatever ctu_first / ctu_count select.  mv_per_ctu = 1: one MV per CTU (HM's 64x64 2Nx2N); 64: one per 8x8 block,
+ * raster order inside the CTU (gathered by the caller from the 593-slot tables).  Every MV is first clamped like TComDataCU::clipMv
+ * (TComDataCU.cpp:2907-2920) for its CTU's position -- MVs out of the engine's own tables are never changed by that.
+ *
+ * hmme_predict_pairs_device: for picture i the luma prediction of every 8x8 block from the padded refs[i] at the block's MV: HM's 8-tap
+ * DCT-IF, horizontal into the 14-bit intermediate, then vertical, rounded and clipped to the sample range -- the uni-directional
+ * prediction TComPrediction::xPredInterBlk writes with bi = false (TComPrediction.cpp:590-594, :669), integer arithmetic, bit-exact at
+ * all 16 phases.  d_outs: HOST array of n_pairs device images of out_pitch_bytes per row, samples of the plane's type (u8 for 8-bit
+ * planes, u16 otherwise); only samples inside the picture AND inside the CTUs [ctu_first, ctu_first + ctu_count) are written.
+ * fp->search_range and fp->fen are not consulted.  hmme_predict_frame: synchronous, one picture, host field and host image (out_stride in
+ * samples; samples outside the CTU range keep their values).
+ *
+ * hmme_search_pairs_bi_device: for pair i and CTU c what hmme_search_ctu returns for
+ *   - the 64x64 block O = 2 * B - P (unclipped: DISABLING_CLIP_FOR_BIPREDME), B = the CTU's block of curs[i] (partial edge CTUs completed
+ *     by edge replication, as the plane's CTU-blocked copy holds them), P = the prediction above from others[i] with pair i's field;
+ *   - refs[i] at the CTU origin; the window hmme_set_search_range(centre, fp->search_range, ...) with centre = d_center_q[i][c]
+ *     (int16[n_pairs][n_ctu][2], quarter pels: the list's current MV) or, d_center_q == NULL, the predictor;
+ *   - the predictor d_pred_q[i][c] (NULL: (0,0)) for the MV cost, fp->fen (honoured: the bi pass does not set bApplyWeight) and
+ *     fp->bit_depth.  fp->search_range is the bi-prediction range (HM's BipredSearchRange, default 4); any range the 16-bit path accepts.
+ * hmme_refine_pairs_bi_device: what hmme_refine_ctu returns at the same inputs for the integer MVs d_int_mv; it rebuilds the origin
+ * itself.  As in the per-CTU call and the reference ALL 593 slots are searched against the one origin of their CTU; with
+ * mv_per_ctu = 64 that origin is built block by block from the caller's field -- which slots that makes meaningful (those whose
+ * rectangle the field's MVs describe) is the caller's business.  Lambda is the context's.  Array shapes, ctu_first / ctu_count, the limit
+ * of 16 pairs, plane ownership and stream ordering are those of hmme_search_pairs_device / hmme_refine_pairs_device; others[i] must have
+ * the size and bit depth of its pair and is ordered like a reference.  Origins and u16 copies live in the scratch of the weighted calls.
+ * Combining this with explicit weighted prediction is not offered.
+ *
+ * Refusal.  hmme_bipred_check decides from the NOMINAL sample range: with maxv = 2^bitDepth - 1 the origin lies in [-maxv, 2 * maxv] and is
+ * staged with the bias maxv, so block and reference copy span [0, 3 * maxv]; span = 2 * maxv is the largest |origin - reference sample|:
+ *   bit depth outside 8..12                                                           -> HMME_ERR_ARG
+ *   3 * maxv > 65535 (the 16-bit search's sample span)                                -> HMME_ERR_UNSUPPORTED
+ *   ((4096 * span) >> (bitDepth-8)) + 65535 >= 8 000 000 (the engine's cost field)     -> HMME_ERR_UNSUPPORTED
+ *   refine != 0: 4096 * span >= 2^24 (the refinement's sums are exact in fp32 below)   -> HMME_ERR_UNSUPPORTED
+ * which gives       bit depth      8    9    10   11   12
+ *                   refine = 0     ok   ok   ok   ok   ok
+ *                   refine = 1     ok   ok   ok   ok   HMME_ERR_UNSUPPORTED
+ * (the per-CTU calls scan their samples instead and refuse none of these).  A pure host function: no context, no GPU.  Every call below
+ * runs it first (refine = 1 in the refinement calls, 0 elsewhere) and launches NOTHING when it fails: it returns that code,
+ * hmme_last_error says why; no fallback, no partial work. */
+int hmme_bipred_check(int bit_depth, int refine);
+int hmme_predict_pairs_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_pairs, const hmme_frame_params* fp, const void* d_mv_field,
+                              int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream);
+int hmme_predict_frame(hmme_ctx* ctx, const hmme_plane* ref, const hmme_frame_params* fp, const int16_t* mv_field, int mv_per_ctu, void* out,
+                       int out_stride);
+int hmme_search_pairs_bi_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others,
+                                int n_pairs, const hmme_frame_params* fp, const void* d_other_mv, int mv_per_ctu, const void* d_center_q,
+                                const void* d_pred_q, void* d_out_mv, void* d_out_sad, void* stream);
+int hmme_refine_pairs_bi_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others,
+                                int n_pairs, const hmme_frame_params* fp, const void* d_other_mv, int mv_per_ctu, const void* d_center_q,
+                                const void* d_pred_q, const void* d_int_mv, int use_hadamard, void* d_out_qmv, void* d_out_cost, void* stream);
+/* synchronous, host arrays, one pair: other_mv int16[n_ctu][mv_per_ctu][2]; center_q / pred_q int16[n_ctu][2] or NULL */
+int hmme_search_frame_bi(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
+                         const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q, const int16_t* pred_q, int16_t* out_mv, uint32_t* out_sad);
+int hmme_refine_frame_bi(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
+                         const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q, const int16_t* pred_q, const int16_t* int_mv,
+                         int use_hadamard, int16_t* out_qmv, uint32_t* out_cost);
 
 /* ---- environment (diagnostics and A/B measurements; none of these changes a result) ---------
  *   HMME_TRACE=1          one stderr line per context about launch geometry the library derives at run time (with HMME_FRAC_GRID=-1:

@@ -32,6 +32,11 @@ int hmme_test_frac_deal(int k, int n_pairs, int width, int height);
 int hmme_test_time_weight_passes(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_weight* wp, void* stream, int reps,
                                  float* ref_ms, float* cur_ms);
 
+/* average device time in ms of the origin pass of a bi-prediction search on its own (me_predict_kernel, OUT = 1: the prediction of
+ * `other` from the motion field folded into the CTU blocks of `cur`), `reps` back-to-back launches over the whole picture on `stream` */
+int hmme_test_time_bipred_origin(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* other, const void* d_other_mv, int mv_per_ctu, void* stream,
+                                 int reps, float* avg_ms);
+
 #ifdef __cplusplus
 }
 #endif
