@@ -146,6 +146,9 @@ struct hmme_ctx {
   // motion field and the window centres [0] and for the predicted picture [1]
   uint8_t* d_bi[2] = {nullptr, nullptr};
   size_t bi_cap[2] = {0, 0};
+  // hmme_select_frame: device staging for the tables, the predictors and the three results of one picture
+  uint8_t* d_sel = nullptr;
+  size_t sel_cap = 0;
 };
 
 struct hmme_plane {
@@ -538,6 +541,7 @@ void hmme_destroy(hmme_ctx* ctx) {
   hipFree(ctx->d_wwin); hipFree(ctx->d_frac_cover); hipFree(ctx->d_imv); hipFree(ctx->d_qmv); hipFree(ctx->d_fcost);
   for (int i = 0; i < 4; ++i) hipFree(ctx->d_wp[i]);
   for (int i = 0; i < 2; ++i) hipFree(ctx->d_bi[i]);
+  hipFree(ctx->d_sel);
   if (ctx->h_call) hipHostFree(ctx->h_call);
   if (ctx->h_res) hipHostFree(ctx->h_res);
   delete ctx;
@@ -675,6 +679,25 @@ int hmme_slot_rect(int slot, int* x, int* y, int* w, int* h) {
               default: break;
             }
             *x = cx * s + rx; *y = cy * s + ry; *w = rw; *h = rh;
+            return HMME_OK;
+          }
+  }
+  return HMME_ERR_ARG;
+}
+
+int hmme_slot_key(int slot, int* part_size, int* depth, int* part_idx, int* abs_z_idx) {
+  if (!part_size || !depth || !part_idx || !abs_z_idx || slot < 0 || slot >= HMME_NUM_CTU_PARTS) return HMME_ERR_ARG;
+  static const int part_sizes[7] = {0, 1, 2, 4, 5, 6, 7};
+  for (int d = 0; d < 4; ++d) {
+    const int n = 1 << d, s4 = 16 >> d;
+    for (int cy = 0; cy < n; ++cy)
+      for (int cx = 0; cx < n; ++cx)
+        for (int pi = 0; pi < 7; ++pi)
+          for (int idx = 0; idx < 2; ++idx) {
+            if (slot_of(part_sizes[pi], d, idx, cx, cy) != slot) continue;
+            int z = 0;   // raster (4x4 units) -> z-order
+            for (int b = 0; b < 4; ++b) z |= (((cx * s4) >> b) & 1) << (2 * b) | (((cy * s4) >> b) & 1) << (2 * b + 1);
+            *part_size = part_sizes[pi]; *depth = d; *part_idx = idx; *abs_z_idx = z;
             return HMME_OK;
           }
   }
@@ -2141,6 +2164,89 @@ int hmme_refine_frame_bi(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane*
   if (rc) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(out_qmv, ctx->d_qmv, sizeof(int16_t) * 2 * res, hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipMemcpyAsync(out_cost, ctx->d_fcost, sizeof(uint32_t) * res, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  return HMME_OK;
+}
+
+// ---- partition decision and motion field from the 593-slot tables ---------------------------------------------------------------------
+namespace {
+int select_eval(const hmme_select_params* p, char* msg, size_t cap) {
+  msg[0] = 0;
+  if (!p) { snprintf(msg, cap, "null parameters"); return HMME_ERR_ARG; }
+  if (p->mv_per_ctu != 64 && p->mv_per_ctu != 256) { snprintf(msg, cap, "%d MVs per CTU (64 or 256)", p->mv_per_ctu); return HMME_ERR_ARG; }
+  if ((p->mv_unit != 0 && p->mv_unit != 1) || (p->price_mv != 0 && p->price_mv != 1)) {
+    snprintf(msg, cap, "mv_unit %d / price_mv %d (each 0 or 1)", p->mv_unit, p->price_mv);
+    return HMME_ERR_ARG;
+  }
+  if (!(p->part_mask & 1u) || (p->part_mask & ~0xf7u)) { snprintf(msg, cap, "part_mask 0x%x: bit 0 must be set, only bits 0, 1, 2, 4..7 exist", p->part_mask); return HMME_ERR_ARG; }
+  if (p->min_depth < 0 || p->max_depth > 3 || p->min_depth > p->max_depth) { snprintf(msg, cap, "depths %d..%d (0 <= min <= max <= 3)", p->min_depth, p->max_depth); return HMME_ERR_ARG; }
+  if (p->cu_cost > (1u << 20) || p->pu_cost > (1u << 20)) { snprintf(msg, cap, "cu_cost %u / pu_cost %u above 2^20", p->cu_cost, p->pu_cost); return HMME_ERR_ARG; }
+  return HMME_OK;
+}
+size_t pad16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+}  // namespace
+
+int hmme_select_check(const hmme_select_params* sel) {
+  char msg[256];
+  return select_eval(sel, msg, sizeof msg);
+}
+
+int hmme_select_pairs_device(hmme_ctx* ctx, int width, int height, int n_pairs, const hmme_frame_params* fp, const hmme_select_params* sel,
+                             const void* d_mv, const void* d_cost, const void* d_pred_q, void* d_out_field, void* d_out_slot, void* d_out_cost,
+                             void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  char msg[256];
+  const int bad = select_eval(sel, msg, sizeof msg);
+  if (bad) return fail(ctx, bad, "hmme_select_pairs_device: %s", msg);
+  if (!fp || width < 1 || height < 1) return fail(ctx, HMME_ERR_ARG, "hmme_select_pairs_device: null frame parameters, or a %d x %d picture", width, height);
+  if (n_pairs < 1 || n_pairs > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "hmme_select_pairs_device: %d picture pairs outside 1..%d", n_pairs, hmme::kMaxRefs);
+  if (!d_mv || !d_cost || !d_out_field) return fail(ctx, HMME_ERR_ARG, "hmme_select_pairs_device: null table / field buffer");
+  // the kernel moves MVs as dwords and, with four MVs per 8x8 block, two entries per store
+  if (((uintptr_t)d_mv & 3) || ((uintptr_t)d_cost & 3) || ((uintptr_t)d_out_field & 7) || ((uintptr_t)d_out_slot & 3) || ((uintptr_t)d_out_cost & 3) ||
+      ((uintptr_t)d_pred_q & 1))
+    return fail(ctx, HMME_ERR_ARG, "hmme_select_pairs_device: misaligned buffer (tables and costs 4 bytes, field 8, slots 4)");
+  const int n_ctu = hmme_num_ctus(width, height);
+  const int first = fp->ctu_first, count = fp->ctu_count < 0 ? n_ctu - fp->ctu_first : fp->ctu_count;
+  if (first < 0 || count < 0 || first + count > n_ctu) return fail(ctx, HMME_ERR_ARG, "CTU range [%d, +%d) outside 0..%d", first, count, n_ctu);
+  if (count == 0) return HMME_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const hmme::MeSelect a = {sel->mv_per_ctu, sel->mv_unit, sel->price_mv, sel->part_mask, sel->min_depth, sel->max_depth, sel->cu_cost, sel->pu_cost};
+  const dim3 grid((unsigned)((count + 3) / 4), (unsigned)n_pairs), block(256);
+  hipLaunchKernelGGL(hmme::me_select_kernel, grid, block, 0, (hipStream_t)stream, (const uint32_t*)d_mv, (const uint32_t*)d_cost, (const int16_t*)d_pred_q,
+                     (uint32_t*)d_out_field, (uint16_t*)d_out_slot, (uint32_t*)d_out_cost, a, width, height, n_ctu, first, count, ctx->lambda_q16);
+  HIP_TRY(ctx, hipGetLastError());
+  return HMME_OK;
+}
+
+int hmme_select_frame(hmme_ctx* ctx, int width, int height, const hmme_frame_params* fp, const hmme_select_params* sel, const int16_t* mv,
+                      const uint32_t* cost, const int16_t* pred_q, int16_t* out_field, uint16_t* out_slot, uint32_t* out_cost) {
+  if (!ctx) return HMME_ERR_ARG;
+  char msg[256];
+  const int bad = select_eval(sel, msg, sizeof msg);
+  if (bad) return fail(ctx, bad, "hmme_select_frame: %s", msg);
+  if (!fp || width < 1 || height < 1 || !mv || !cost || !out_field) return fail(ctx, HMME_ERR_ARG, "hmme_select_frame: null argument, or a %d x %d picture", width, height);
+  const int n_ctu = hmme_num_ctus(width, height);
+  const int first = fp->ctu_first, count = fp->ctu_count < 0 ? n_ctu - fp->ctu_first : fp->ctu_count;
+  if (first < 0 || count < 0 || first + count > n_ctu) return fail(ctx, HMME_ERR_ARG, "CTU range [%d, +%d) outside 0..%d", first, count, n_ctu);
+  if (count == 0) return HMME_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t per = (size_t)sel->mv_per_ctu, tab = (size_t)count * HMME_NUM_CTU_PARTS;
+  const size_t o_mv = 0, o_cost = o_mv + pad16(tab * 4), o_pred = o_cost + pad16(tab * 4), o_field = o_pred + pad16((size_t)n_ctu * 4);
+  const size_t o_slot = o_field + pad16((size_t)n_ctu * per * 4), o_ccost = o_slot + pad16((size_t)n_ctu * per * 2), total = o_ccost + pad16((size_t)n_ctu * 4);
+  int rc = ensure(ctx, &ctx->d_sel, &ctx->sel_cap, total);
+  if (rc) return rc;
+  hipStream_t s = ctx->stream;
+  uint8_t* d = ctx->d_sel;
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_mv, mv, tab * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_cost, cost, tab * 4, hipMemcpyHostToDevice, s));
+  if (pred_q) HIP_TRY(ctx, hipMemcpyAsync(d + o_pred, pred_q, (size_t)n_ctu * 4, hipMemcpyHostToDevice, s));
+  rc = hmme_select_pairs_device(ctx, width, height, 1, fp, sel, d + o_mv, d + o_cost, pred_q ? d + o_pred : nullptr, d + o_field, out_slot ? d + o_slot : nullptr,
+                                out_cost ? d + o_ccost : nullptr, s);
+  if (rc) return rc;
+  // only the CTUs of the range come back: the caller's entries outside it keep their values
+  HIP_TRY(ctx, hipMemcpyAsync(out_field + (size_t)first * per * 2, d + o_field + (size_t)first * per * 4, (size_t)count * per * 4, hipMemcpyDeviceToHost, s));
+  if (out_slot) HIP_TRY(ctx, hipMemcpyAsync(out_slot + (size_t)first * per, d + o_slot + (size_t)first * per * 2, (size_t)count * per * 2, hipMemcpyDeviceToHost, s));
+  if (out_cost) HIP_TRY(ctx, hipMemcpyAsync(out_cost + first, d + o_ccost + (size_t)first * 4, (size_t)count * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipStreamSynchronize(s));
   return HMME_OK;
 }

@@ -2253,4 +2253,160 @@ me_predict_kernel(const uint8_t* __restrict__ ref_origin, int ref_pitch, const i
   }
 }
 
+// ---- partition decision and motion field from the 593-slot tables (hmme_select_pairs_device; the rule: include/hmme.h) ------------------
+// hmme_select_params as the kernel takes it
+struct MeSelect {
+  int per;                  // mv_per_ctu: 64 | 256
+  int mv_unit, price_mv;
+  uint32_t part_mask;
+  int min_depth, max_depth;
+  uint32_t cu_cost, pu_cost;
+};
+
+// slot of a PU: the closed form of TComDataCU::getIndexBlock the host uses (hmme.hip slot_of); D = depth, (cx, cy) = the CU at that depth.
+// The caller never asks for AMP at depth 3.
+template <int D>
+__device__ __forceinline__ int me_slot_of(int ps, int idx, int cx, int cy) {
+  constexpr int n = 1 << D;
+  constexpr int b2Nx2N = D == 0 ? 592 : D == 1 ? 584 : D == 2 ? 544 : 384, b2NxN = D == 0 ? 588 : D == 1 ? 560 : D == 2 ? 448 : 0;
+  constexpr int bNx2N = D == 0 ? 590 : D == 1 ? 568 : D == 2 ? 480 : 128, bAMP = D == 0 ? 576 : D == 1 ? 512 : 256;
+  const int r = cy * n + cx;
+  if (ps == 0) return b2Nx2N + r;
+  if (ps == 1) return b2NxN + cy * 2 * n + idx * n + cx;
+  if (ps == 2) return bNx2N + cy * 2 * n + 2 * cx + idx;
+  const int k = ps == 4 ? (idx ? 3 : 0) : ps == 5 ? (idx ? 1 : 2) : ps == 6 ? (idx ? 7 : 4) : (idx ? 5 : 6);   // 2NxnU, 2NxnD, nLx2N, nRx2N
+  return bAMP + k * n * n + r;
+}
+// may PartSize ps be coded for a CU of depth D?  AMP is not tabulated at 8x8; with one MV per 8x8 block every PU rectangle must be 8-aligned
+template <int D>
+__device__ __forceinline__ bool me_select_allowed(const MeSelect& a, int ps) {
+  if (!((a.part_mask >> ps) & 1u)) return false;
+  if (D == 3) return ps == 0 || (ps <= 2 && a.per == 256);
+  if (D == 2) return ps <= 2 || a.per == 256;
+  return true;
+}
+// slot of the PU of a depth-D CU with PartSize ps that covers sample (x, y) of the CTU
+template <int D>
+__device__ __forceinline__ int me_select_pu_slot(int ps, int x, int y) {
+  constexpr int s = 64 >> D;
+  const int lx = x & (s - 1), ly = y & (s - 1);
+  const int idx = ps == 0 ? 0 : ps == 1 ? ly >= s / 2 : ps == 2 ? lx >= s / 2 : ps == 4 ? ly >= s / 4 : ps == 5 ? ly >= 3 * s / 4 : ps == 6 ? lx >= s / 4 : lx >= 3 * s / 4;
+  return me_slot_of<D>(ps, idx, x >> (6 - D), y >> (6 - D));
+}
+__device__ __forceinline__ int me_select_pu_slot_at(int depth, int ps, int x, int y) {
+  return depth == 0 ? me_select_pu_slot<0>(ps, x, y) : depth == 1 ? me_select_pu_slot<1>(ps, x, y) : depth == 2 ? me_select_pu_slot<2>(ps, x, y) : me_select_pu_slot<3>(ps, x, y);
+}
+__device__ __forceinline__ uint64_t me_shfl_xor_u64(uint64_t v, int mask) {
+  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, mask), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), mask);
+  return (uint64_t)hi << 32 | lo;
+}
+
+// what the decision carries for one lane (= one 8x8 block): the resolved cost of the lane's ancestor CU at the depth handled last (the same
+// value in every lane of that CU) and the shallowest ancestor that stayed a leaf so far
+struct MeSelectState {
+  uint64_t resolved;
+  int leaf_depth, leaf_ps;   // leaf_depth < 0: no CU covers the block
+};
+
+// One level of the bottom-up decision, for the lane's ancestor CU at depth D.  Every lane of the CU computes the CU's own best redundantly
+// (LDS broadcast reads, no divergence), the sum of the four children is a quad reduction over the lanes that differ in bit (2 - D) of the
+// block's column and row.  Called for D = 3, 2, 1, 0: a shallower leaf overrides a deeper one, so no decision has to be pushed back down.
+template <int D>
+__device__ __forceinline__ void me_select_level(const MeSelect& a, const uint32_t* s_cost, const uint32_t* s_mv, uint32_t lambda_q16, int pred_x, int pred_y,
+                                                int bx, int by, int ctu_x, int ctu_y, int pic_w, int pic_h, MeSelectState& st) {
+  if (D > a.max_depth) return;   // wave-uniform
+  constexpr int s = 64 >> D;
+  const int cx = bx >> (3 - D), cy = by >> (3 - D), x0 = ctu_x + cx * s, y0 = ctu_y + cy * s;
+  auto pu = [&](int slot) -> uint64_t {   // slot cost (+ HM's MV cost) + pu_cost
+    uint64_t c = (uint64_t)s_cost[slot] + a.pu_cost;
+    if (a.price_mv) {
+      const uint32_t m = s_mv[slot];
+      const int vx = (int16_t)(m & 0xffffu), vy = (int16_t)(m >> 16);
+      c += a.mv_unit ? me_mv_cost(lambda_q16, vx, vy, pred_x, pred_y) : me_mv_cost_q(lambda_q16, vx, vy, pred_x, pred_y);
+    }
+    return c;
+  };
+  uint64_t own = a.cu_cost + pu(me_slot_of<D>(0, 0, cx, cy));   // bit 0 of part_mask is always set
+  int own_ps = 0;
+#pragma unroll
+  for (int ps = 1; ps < 8; ++ps) {
+    if (ps == 3 || (D == 3 && ps > 2)) continue;
+    if (!me_select_allowed<D>(a, ps)) continue;   // wave-uniform
+    const uint64_t c = a.cu_cost + pu(me_slot_of<D>(ps, 0, cx, cy)) + pu(me_slot_of<D>(ps, 1, cx, cy));
+    if (c < own) { own = c; own_ps = ps; }   // strict: the lower enum wins ties
+  }
+  if (D == a.max_depth) {   // exists if and only if its origin lies inside the picture
+    const bool exists = x0 < pic_w && y0 < pic_h;
+    st.resolved = exists ? own : 0;
+    if (exists) { st.leaf_depth = D; st.leaf_ps = own_ps; }
+    return;
+  }
+  uint64_t children = st.resolved + me_shfl_xor_u64(st.resolved, 1 << (2 - D));
+  children += me_shfl_xor_u64(children, 8 << (2 - D));
+  const bool may_leaf = D >= a.min_depth && x0 + s <= pic_w && y0 + s <= pic_h;
+  if (may_leaf && !(children < own)) { st.resolved = own; st.leaf_depth = D; st.leaf_ps = own_ps; }   // the parent wins ties
+  else st.resolved = children;
+}
+
+// One wave per CTU, four CTUs per workgroup; blockIdx.y = picture pair.  The CTU's 593 costs and MVs are loaded coalesced into LDS (4.7 KB
+// per CTU), lane = 8x8 block in RASTER order inside the CTU -- the layout of the field, so that every store of the wave is one contiguous
+// run (256 B of MVs with one MV per 8x8 block; rows of 64 B with four).  mv_tab: int16 [n_pairs][ctu_count][593][2] read as dwords;
+// cost_tab: uint32 [n_pairs][ctu_count][593]; pred_q: int16 [n_pairs][n_ctu][2] or null; out_field: int16 [n_pairs][n_ctu][per][2] written
+// as dwords; out_slot: uint16 [n_pairs][n_ctu][per] or null; out_cost: uint32 [n_pairs][n_ctu] or null.  Bandwidth-sized: nothing tuned
+// beyond coalesced accesses.
+__global__ void __launch_bounds__(256)
+me_select_kernel(const uint32_t* __restrict__ mv_tab, const uint32_t* __restrict__ cost_tab, const int16_t* __restrict__ pred_q,
+                 uint32_t* __restrict__ out_field, uint16_t* __restrict__ out_slot, uint32_t* __restrict__ out_cost, MeSelect a, int pic_w, int pic_h,
+                 int n_ctu, int ctu_first, int ctu_count, uint32_t lambda_q16) {
+  __shared__ uint32_t s_cost[4][kParts + 3];
+  __shared__ uint32_t s_mv[4][kParts + 3];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int c = blockIdx.x * 4 + wave, pair = blockIdx.y;
+  const bool live = c < ctu_count;   // wave-uniform
+  if (live) {
+    const long base = ((long)pair * ctu_count + c) * kParts;
+    for (int i = lane; i < kParts; i += 64) {
+      s_cost[wave][i] = cost_tab[base + i];
+      s_mv[wave][i] = mv_tab[base + i];
+    }
+  }
+  __syncthreads();
+  if (!live) return;
+  const int ctu = ctu_first + c, ctus_x = (pic_w + 63) >> 6;
+  const int ctu_x = (ctu % ctus_x) * 64, ctu_y = (ctu / ctus_x) * 64;
+  const long o = (long)pair * n_ctu + ctu;
+  const int pred_x = pred_q ? pred_q[o * 2] : 0, pred_y = pred_q ? pred_q[o * 2 + 1] : 0;
+  const int bx = lane & 7, by = lane >> 3;
+  MeSelectState st = {0, -1, 0};
+  me_select_level<3>(a, s_cost[wave], s_mv[wave], lambda_q16, pred_x, pred_y, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
+  me_select_level<2>(a, s_cost[wave], s_mv[wave], lambda_q16, pred_x, pred_y, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
+  me_select_level<1>(a, s_cost[wave], s_mv[wave], lambda_q16, pred_x, pred_y, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
+  me_select_level<0>(a, s_cost[wave], s_mv[wave], lambda_q16, pred_x, pred_y, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
+  if (lane == 0 && out_cost) out_cost[o] = st.resolved > 0xffffffffull ? 0xffffffffu : (uint32_t)st.resolved;
+  // integer-pel MVs leave as quarter pels: both halves of the dword << 2, the two bits that cross into the upper half masked off
+  auto field_mv = [&](int slot) -> uint32_t {
+    const uint32_t m = s_mv[wave][slot];
+    return a.mv_unit ? (m << 2) & 0xfffcfffcu : m;
+  };
+  if (a.per == 64) {
+    const int slot = st.leaf_depth < 0 ? 0xffff : me_select_pu_slot_at(st.leaf_depth, st.leaf_ps, bx * 8, by * 8);
+    out_field[o * 64 + lane] = slot == 0xffff ? 0u : field_mv(slot);
+    if (out_slot) out_slot[o * 64 + lane] = (uint16_t)slot;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {   // the block's two rows of two 4x4 blocks
+      int slot[2];
+      uint32_t mv[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        slot[i] = st.leaf_depth < 0 ? 0xffff : me_select_pu_slot_at(st.leaf_depth, st.leaf_ps, bx * 8 + 4 * i, by * 8 + 4 * j);
+        mv[i] = slot[i] == 0xffff ? 0u : field_mv(slot[i]);
+      }
+      const long e = o * 256 + (2 * by + j) * 16 + 2 * bx;   // even: the pair of entries is 8-byte (MVs) / 4-byte (slots) aligned
+      *(uint2*)(out_field + e) = make_uint2(mv[0], mv[1]);
+      if (out_slot) *(uint32_t*)(out_slot + e) = (uint32_t)slot[0] | (uint32_t)slot[1] << 16;
+    }
+  }
+}
+
 }  // namespace hmme

@@ -25,7 +25,8 @@ SYMBOLS = ["hmme_create", "hmme_destroy", "hmme_last_error", "hmme_device_info",
            "hmme_upload_status", "hmme_abi_version", "hmme_build_id", "hmme_device_index", "hmme_set_error_printing",
            "hmme_weight_check", "hmme_search_pairs_w_device", "hmme_refine_pairs_w_device", "hmme_search_frame_w", "hmme_refine_frame_w",
            "hmme_bipred_check", "hmme_predict_pairs_device", "hmme_predict_frame", "hmme_search_pairs_bi_device", "hmme_refine_pairs_bi_device",
-           "hmme_search_frame_bi", "hmme_refine_frame_bi"]
+           "hmme_search_frame_bi", "hmme_refine_frame_bi",
+           "hmme_slot_key", "hmme_select_check", "hmme_select_pairs_device", "hmme_select_frame"]
 # test / measurement entry points (include/hmme_test.h): not part of the boundary
 TEST_SYMBOLS = ["hmme_test_time_search_kernel", "hmme_test_device_address", "hmme_test_frac_deal", "hmme_test_tail_plan", "hmme_test_time_weight_passes", "hmme_test_time_bipred_origin"]
 ABI_VERSION = 6   # HMME_ABI_VERSION of the include/hmme.h these bindings were written against
@@ -44,6 +45,15 @@ class SearchParams(C.Structure):
 class Weight(C.Structure):
     """hmme_weight: luma WPScalingParam of the reference picture"""
     _fields_ = [("w0", C.c_int), ("offset", C.c_int), ("shift", C.c_int), ("round", C.c_int)]
+
+
+class SelectParams(C.Structure):
+    """hmme_select_params: the partition decision over the 593-slot tables (the rule: include/hmme.h)"""
+    _fields_ = [("mv_per_ctu", C.c_int), ("mv_unit", C.c_int), ("price_mv", C.c_int), ("part_mask", C.c_uint),
+                ("min_depth", C.c_int), ("max_depth", C.c_int), ("cu_cost", C.c_uint32), ("pu_cost", C.c_uint32)]
+
+    def __init__(self, mv_per_ctu=64, mv_unit=0, price_mv=0, part_mask=0xF7, min_depth=0, max_depth=3, cu_cost=0, pu_cost=0):
+        super().__init__(int(mv_per_ctu), int(mv_unit), int(price_mv), int(part_mask), int(min_depth), int(max_depth), int(cu_cost), int(pu_cost))
 
 
 class FrameParams(C.Structure):
@@ -134,6 +144,10 @@ def load():
     L.hmme_search_frame_bi.argtypes = [vp, vp, vp, vp, C.POINTER(FrameParams), vp, i, vp, vp, vp, vp]
     L.hmme_refine_frame_bi.argtypes = [vp, vp, vp, vp, C.POINTER(FrameParams), vp, i, vp, vp, vp, i, vp, vp]
     L.hmme_test_time_bipred_origin.argtypes = [vp, vp, vp, vp, i, vp, i, C.POINTER(C.c_float)]
+    L.hmme_slot_key.argtypes = [i] + [C.POINTER(i)] * 4
+    L.hmme_select_check.argtypes = [C.POINTER(SelectParams)]
+    L.hmme_select_pairs_device.argtypes = [vp, i, i, i, C.POINTER(FrameParams), C.POINTER(SelectParams), vp, vp, vp, vp, vp, vp, vp]
+    L.hmme_select_frame.argtypes = [vp, i, i, C.POINTER(FrameParams), C.POINTER(SelectParams), vp, vp, vp, vp, vp, vp]
     L.hmme_upload_status.argtypes = [vp, vp]
     L.hmme_test_device_address.argtypes = [vp, vp]
     L.hmme_test_device_address.restype = C.c_uint64
@@ -527,6 +541,35 @@ class Engine:
                                                 int(use_hadamard), qmv.ctypes.data, cost.ctypes.data))
         return qmv, cost
 
+    # ---- partition decision and motion field from the 593-slot tables (include/hmme.h, "partition decision and motion field") ----
+    def select_pairs_device(self, width, height, n_pairs, fp, sel, d_mv, d_cost, d_pred, d_field, d_slot=None, d_ctu_cost=None, stream=0):
+        """hmme_select_pairs_device: the tables of up to 16 pairs (device, as a search / refinement with the same fp wrote them) -> motion field
+        int16[n_pairs, n_ctu, mv_per_ctu, 2], covering slots uint16[n_pairs, n_ctu, mv_per_ctu] and CTU costs uint32[n_pairs, n_ctu] (device
+        addresses; d_slot / d_ctu_cost may be None)"""
+        self._check(self.L.hmme_select_pairs_device(self.h, int(width), int(height), int(n_pairs), C.byref(fp), C.byref(sel), d_mv, d_cost, d_pred,
+                                                    d_field, d_slot, d_ctu_cost, stream))
+
+    def select_frame(self, width, height, sel, mv, cost, pred_q=None, ctu_first=0, ctu_count=-1, field=None, slot=None, ctu_cost=None):
+        """hmme_select_frame: one pair, host arrays.  mv int16[count, 593, 2], cost uint32[count, 593] -> (field int16[n_ctu, mv_per_ctu, 2],
+        slot uint16[n_ctu, mv_per_ctu], ctu_cost uint32[n_ctu]); entries outside the CTU range keep the values of the arrays passed in (zeros
+        when none is)"""
+        n = self.L.hmme_num_ctus(width, height)
+        count = n - ctu_first if ctu_count < 0 else ctu_count
+        fp = FrameParams(1, 0, 8, ctu_first, count)
+        per = int(sel.mv_per_ctu)
+        mv = np.ascontiguousarray(mv, dtype=np.int16)
+        cost = np.ascontiguousarray(cost, dtype=np.uint32)
+        assert mv.shape == (count, NUM_PARTS, 2) and cost.shape == (count, NUM_PARTS)
+        pq, pptr = self._pq(pred_q, n)
+        field = np.zeros((n, per, 2), np.int16) if field is None else field
+        slot = np.zeros((n, per), np.uint16) if slot is None else slot
+        ctu_cost = np.zeros(n, np.uint32) if ctu_cost is None else ctu_cost
+        for a, dt, shape in ((field, np.int16, (n, per, 2)), (slot, np.uint16, (n, per)), (ctu_cost, np.uint32, (n,))):
+            assert a.dtype == dt and a.shape == shape and a.flags.c_contiguous
+        self._check(self.L.hmme_select_frame(self.h, int(width), int(height), C.byref(fp), C.byref(sel), mv.ctypes.data, cost.ctypes.data, pptr,
+                                             field.ctypes.data, slot.ctypes.data, ctu_cost.ctypes.data))
+        return field, slot, ctu_cost
+
     def time_bipred_origin(self, cur, other, d_other_mv, mv_per_ctu, stream=0, reps=5):
         """device time in ms of the origin pass of a bi-prediction search on its own (whole picture)"""
         ms = C.c_float()
@@ -570,6 +613,11 @@ def bipred_check(bit_depth, refine=False):
     return int(load().hmme_bipred_check(int(bit_depth), 1 if refine else 0))
 
 
+def select_check(sel):
+    """hmme_select_check: 0, or HMME_ERR_ARG when a field of the SelectParams lies outside its range (pure host arithmetic: needs no GPU)"""
+    return int(load().hmme_select_check(C.byref(sel)))
+
+
 def ocl_compat_params(lt_x, lt_y, sr):
     p = SearchParams()
     load().hmme_params_ocl_compat(C.byref(p), lt_x, lt_y, sr)
@@ -590,5 +638,13 @@ def slot_rect(slot):
     out = [C.c_int() for _ in range(4)]
     rc = load().hmme_slot_rect(slot, *[C.byref(o) for o in out])
     if rc != 0:
+        raise HmmeError(f"slot {slot} out of range")
+    return tuple(o.value for o in out)
+
+
+def slot_key(slot):
+    """hmme_slot_key, the inverse of slot_index -> (part_size, depth, part_idx, abs_z_idx)"""
+    out = [C.c_int() for _ in range(4)]
+    if load().hmme_slot_key(int(slot), *[C.byref(o) for o in out]) != 0:
         raise HmmeError(f"slot {slot} out of range")
     return tuple(o.value for o in out)

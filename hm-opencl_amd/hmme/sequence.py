@@ -142,15 +142,33 @@ class RankResources:
         self.close()
 
 
+def _check_select(select, refine):
+    """what run_rank asks of a SelectParams, before anything touches the device"""
+    from . import api
+    if api.select_check(select) != 0:
+        raise ValueError("select: a field of the SelectParams lies outside its range (hmme_select_check)")
+    if refine and select.mv_unit != 0:
+        raise ValueError("select: the refinement's tables hold quarter-pel MVs (mv_unit = 0)")
+    if not refine and (select.price_mv != 1 or select.mv_unit != 1):
+        raise ValueError("select without refine: the search's tables are pure SADs at integer MVs (price_mv = 1, mv_unit = 1)")
+
+
 def run_rank(eng, source, pairs, width, height, bit_depth, search_range, *, stream_mode=False, pairs_per_launch=1, refine=False,
-             download=False, n_slots=None, device=None, host_buffers=4, resources=None, weights=None):
+             download=False, n_slots=None, device=None, host_buffers=4, resources=None, weights=None, select=None):
     """searches `pairs` [(cur_poc, ref_poc)] (this rank's share) -> dict with device tensors mv [n, n_ctu, 593, 2] int16,
     sad [n, n_ctu, 593] int32 (+ qmv / cost with refine, + host_* page-locked copies with download) and timings.
     source: .read_into(poc, out) filling a (height, width) uint8 / uint16 array (hmme.yuv.LumaFile, hmme.synth.Sequence).
     resources: a RankResources the caller keeps between passes of one geometry (streaming mode): plane slots, host buffers and streams are
     then allocated by the first pass only and stay the caller's to close.
     weights: explicit weighted prediction -- one (w0, offset, shift, round) per pair, in the order of `pairs`; search (and refinement)
-    then go through hmme_search_pairs_w_device / hmme_refine_pairs_w_device.  None: the unweighted calls, as before."""
+    then go through hmme_search_pairs_w_device / hmme_refine_pairs_w_device.  None: the unweighted calls, as before.
+    select: an api.SelectParams -- the partition decision (hmme_select_pairs_device) runs on the compute stream behind each launch's refinement
+    (behind its search with refine=False: the pure-SAD tables then need price_mv = 1, and their integer MVs mv_unit = 1).  The result gains the
+    device tensors field [n, n_ctu, mv_per_ctu, 2] int16, slot [n, n_ctu, mv_per_ctu] int16 (the bits of the uint16 slots: -1 = 0xFFFF) and
+    ctu_cost [n, n_ctu] int32 (the bits of the uint32 costs); with download these compact results are what is copied to the host, the tables stay
+    on the device.  None: no selection, as before."""
+    if select is not None:
+        _check_select(select, refine)
     import torch
     from . import api
     dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -170,8 +188,16 @@ def run_rank(eng, source, pairs, width, height, bit_depth, search_range, *, stre
     if refine:
         out["qmv"] = torch.zeros((n, n_ctu, NUM_PARTS, 2), dtype=torch.int16, device=dev)
         out["cost"] = torch.zeros((n, n_ctu, NUM_PARTS), dtype=torch.int32, device=dev)
+    compact = ()
+    if select is not None:
+        per = int(select.mv_per_ctu)
+        out["field"] = torch.zeros((n, n_ctu, per, 2), dtype=torch.int16, device=dev)
+        out["slot"] = torch.zeros((n, n_ctu, per), dtype=torch.int16, device=dev)
+        out["ctu_cost"] = torch.zeros((n, n_ctu), dtype=torch.int32, device=dev)
+        compact = ("field", "slot", "ctu_cost")
+    to_host = compact or (("mv", "sad") + (("qmv", "cost") if refine else ()))
     if download:
-        for k in list(out):
+        for k in to_host:
             out["host_" + k] = torch.empty(out[k].shape, dtype=out[k].dtype, pin_memory=True)
     keep = resources if (resources is not None and stream_mode) else None
     streams = keep.streams if keep is not None else {}
@@ -183,6 +209,9 @@ def run_rank(eng, source, pairs, width, height, bit_depth, search_range, *, stre
     dl = streams["dl"] if download else None
     stages = {"read_s": 0.0, "upload_s": 0.0, "search_s": 0.0, "refine_s": 0.0, "download_s": 0.0}
     ev_pairs = {k: [] for k in ("upload", "search", "refine", "download")}
+    if select is not None:
+        stages["select_s"] = 0.0
+        ev_pairs["select"] = []
 
     def timed(kind, stream):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -211,13 +240,20 @@ def run_rank(eng, source, pairs, width, height, bit_depth, search_range, *, stre
                 eng.refine_pairs_w_device(curs, refs, fp, weights[i0:i1], None, out["mv"][i0:i1].data_ptr(), 1, out["qmv"][i0:i1].data_ptr(),
                                           out["cost"][i0:i1].data_ptr(), compute.cuda_stream)
             e.record(compute)
+        if select is not None:
+            tabs = ("qmv", "cost") if refine else ("mv", "sad")
+            e = timed("select", compute)
+            eng.select_pairs_device(width, height, i1 - i0, fp, select, out[tabs[0]][i0:i1].data_ptr(), out[tabs[1]][i0:i1].data_ptr(), None,
+                                    out["field"][i0:i1].data_ptr(), out["slot"][i0:i1].data_ptr(), out["ctu_cost"][i0:i1].data_ptr(),
+                                    compute.cuda_stream)
+            e.record(compute)
         if download:
             done = torch.cuda.Event()
             done.record(compute)
             dl.wait_event(done)
             e = timed("download", dl)
             with torch.cuda.stream(dl):
-                for k in ("mv", "sad") + (("qmv", "cost") if refine else ()):
+                for k in to_host:
                     out["host_" + k][i0:i1].copy_(out[k][i0:i1], non_blocking=True)
             e.record(dl)
 

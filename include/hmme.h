@@ -144,6 +144,8 @@ void hmme_set_search_range(int pred_x_q, int pred_y_q, int search_range, int cu_
 int hmme_slot_index(int part_size, int depth, int part_idx, int abs_z_idx);
 /* rectangle of a slot inside the 64x64 CTU; returns 0 or HMME_ERR_ARG */
 int hmme_slot_rect(int slot, int* x, int* y, int* w, int* h);
+/* the inverse of hmme_slot_index: the key of slot 0..592 (what a reader of hmme_select_pairs_device's out_slot needs); 0 or HMME_ERR_ARG */
+int hmme_slot_key(int slot, int* part_size, int* depth, int* part_idx, int* abs_z_idx);
 /* The 425-entry table layout of an encoder built with AMP_ENC_SPEEDUP (TypeDef.h:206, :260-261; TComDataCU.cpp:3393-4675; the
  * reference's `calcSAD` kernel, cl/sad.cl:4-138) -- the macro is 0 in the reference tree as shipped, so this is a view for such a
  * build, not a second search: the same rectangles as the 593 layout without the AMP shapes.  hmme_slot_index_amp_off = that build's
@@ -328,7 +330,7 @@ int hmme_refine_frame_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* 
  *
  * Motion field.  d_mv_field / d_other_mv: quarter-pel MVs int16[n_pairs][n_ctu][mv_per_ctu][2] (hor, ver), n_ctu = ALL CTUs of the
  * picture in raster order whatever ctu_first / ctu_count select.  mv_per_ctu = 1: one MV per CTU (HM's 64x64 2Nx2N); 64: one per 8x8 block,
- * raster order inside the CTU (gathered by the caller from the 593-slot tables).  Every MV is first clamped like TComDataCU::clipMv
+ * raster order inside the CTU (hmme_select_pairs_device writes it from the 593-slot tables).  Every MV is first clamped like TComDataCU::clipMv
  * (TComDataCU.cpp:2907-2920) for its CTU's position -- MVs out of the engine's own tables are never changed by that.
  *
  * hmme_predict_pairs_device: for picture i the luma prediction of every 8x8 block from the padded refs[i] at the block's MV: HM's 8-tap
@@ -383,6 +385,66 @@ int hmme_search_frame_bi(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane*
 int hmme_refine_frame_bi(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
                          const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q, const int16_t* pred_q, const int16_t* int_mv,
                          int use_hadamard, int16_t* out_qmv, uint32_t* out_cost);
+
+/* ---- partition decision and motion field from the 593-slot tables ---------------------------------------------
+ * The step between the uni-directional searches and the calls that take a motion field (hmme_predict_pairs_device, hmme_search_pairs_bi_device,
+ * hmme_refine_pairs_bi_device), on the device: per CTU a bottom-up decision over the 593 costs which of the overlapping PU shapes to use -- a CU
+ * quadtree with one PartSize per CU -- written as one MV per block, the slot that covers every block, and the CTU's cost.  The reference has no
+ * counterpart (there the choice is HM's serial RD loop reading the tables one PU at a time), so THIS TEXT IS THE RULE.  New entry points and one
+ * new struct; nothing existing changed, so HMME_ABI_VERSION stays 6.
+ *
+ * Inputs, per pair and per searched CTU: mv[593][2] and cost[593] exactly as a search or refinement call wrote them for the same ctu_first /
+ * ctu_count (d_mv: int16[n_pairs][count][593][2], d_cost: uint32[n_pairs][count][593]), and optionally the CTU's predictor
+ * d_pred_q[i][c] (int16[n_pairs][n_ctu][2], quarter pels, indexed by CTU raster address; NULL: (0,0)).
+ *
+ * Parameters (hmme_select_params; hmme_select_check returns HMME_ERR_ARG for anything outside these ranges):
+ *   mv_per_ctu  64: one MV per 8x8 block, raster order inside the CTU -- the layout of hmme_predict_pairs_device and the _bi_ calls.  A PartSize
+ *               of a CU is then a candidate only if all its PU rectangles are 8-aligned in position and size: 2Nx2N only at 8x8, no AMP at
+ *               16x16, every shape at 32x32 and 64x64.
+ *               256: one MV per 4x4 block, raster order (HM's own motion storage granularity); all 593 slots take part.
+ *   mv_unit     0: the MVs are quarter-pel (out_qmv of a refinement) and are copied; 1: integer-pel (out_mv of a search), written << 2.
+ *   price_mv    1 adds HM's MV cost to every slot's cost before anything is compared, priced against the CTU's predictor with the context's
+ *               lambda: for integer MVs (mv_unit 1) the search's own (lambda_q16 * (bits((x << 2) - px) + bits((y << 2) - py))) >> 16, for
+ *               quarter-pel MVs (lambda_q16 * (bits(qx - px) + bits(qy - py))) >> 16 -- TComRdCost::getCost with cost scale 2 / 0, the product
+ *               wrapping in 32 bits as there.  For the pure-SAD tables of the integer search, which otherwise always split to the bottom;
+ *               refinement costs already contain the MV cost, so callers pass 0 with them.
+ *   part_mask   bit p set: PartSize p (0, 1, 2, 4, 5, 6, 7) is allowed.  Bit 0 must be set; bit 3 and bits above 7 must be clear.
+ *   min_depth <= max_depth, both in 0..3 (CU size 64 >> depth).
+ *   cu_cost, pu_cost   each <= 2^20, added once per coded CU and once per PU: the caller's model of mode bits.
+ *
+ * Decision.
+ *   1. The cost of (CU, PartSize) is cu_cost plus the sum over its PUs of (slot cost + pu_cost).
+ *   2. A CU's own best is the smallest cost over the allowed PartSizes; comparison is strict '<' in the order 0, 1, 2, 4, 5, 6, 7, so the lower
+ *      enum wins ties.
+ *   3. Presence at picture edges.  A CU at depth < max_depth may be a leaf only if depth >= min_depth and it lies wholly inside the picture;
+ *      otherwise it must split.  A CU at max_depth exists if and only if its origin is inside the picture; its cost is over the whole
+ *      rectangle, as the tables have it (edge replication).  A CU that does not exist costs 0 and codes nothing.
+ *   4. Bottom-up: a CU that may be a leaf stays one unless the sum of its four children is strictly smaller -- the parent wins ties.
+ *   5. Sums are carried in 64 bits; out_cost saturates at UINT32_MAX; nothing else is clamped (an integer MV << 2 keeps its low 16 bits).
+ *
+ * Outputs.  d_out_field: int16[n_pairs][n_ctu][mv_per_ctu][2], n_ctu = ALL CTUs of the picture, as the _bi_ calls index their fields; only the
+ * entries of the CTUs in [ctu_first, ctu_first + ctu_count) are written.  d_out_slot (may be NULL): uint16[n_pairs][n_ctu][mv_per_ctu], the slot
+ * whose PU covers the block -- 0xFFFF, with MV (0,0), for blocks of CUs that do not exist.  d_out_cost (may be NULL): uint32[n_pairs][n_ctu].
+ *
+ * hmme_select_pairs_device: asynchronous on `stream`, up to 16 pairs.  It takes no planes -- the picture size comes as two ints -- and of fp only
+ * ctu_first / ctu_count are consulted.  It uses no scratch of the context, so it is ordered like any kernel of the caller on `stream` and
+ * against nothing else.  Buffers: tables, costs and slots 4-byte aligned, the field 8-byte aligned.  It runs hmme_select_check first and
+ * launches nothing when that fails.  hmme_select_frame: synchronous, host arrays of the same shapes with n_pairs = 1, on the context's private
+ * stream; entries outside the CTU range keep their values. */
+typedef struct hmme_select_params {
+  int mv_per_ctu;
+  int mv_unit;
+  int price_mv;
+  unsigned part_mask;
+  int min_depth, max_depth;
+  uint32_t cu_cost, pu_cost;
+} hmme_select_params;
+int hmme_select_check(const hmme_select_params* sel);
+int hmme_select_pairs_device(hmme_ctx* ctx, int width, int height, int n_pairs, const hmme_frame_params* fp, const hmme_select_params* sel,
+                             const void* d_mv, const void* d_cost, const void* d_pred_q, void* d_out_field, void* d_out_slot, void* d_out_cost,
+                             void* stream);
+int hmme_select_frame(hmme_ctx* ctx, int width, int height, const hmme_frame_params* fp, const hmme_select_params* sel, const int16_t* mv,
+                      const uint32_t* cost, const int16_t* pred_q, int16_t* out_field, uint16_t* out_slot, uint32_t* out_cost);
 
 /* ---- environment (diagnostics and A/B measurements; none of these changes a result) ---------
  *   HMME_TRACE=1          one stderr line per context about launch geometry the library derives at run time (with HMME_FRAC_GRID=-1:

@@ -4,7 +4,7 @@
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         tools/me_sequence.py --frames 64 --gop randomaccess --size 2160p [--yuv file.yuv] [--bit-depth 10]
-                             [--stream] [--pairs-per-launch K] [--refine] [--download] [--dump out.npz]
+                             [--stream] [--pairs-per-launch K] [--refine] [--download] [--select 64|256] [--dump out.npz]
 
 Rank r searches pairs r, r+N, ... (hmme/shard.py); the 593-entry tables of all pairs are gathered to rank 0 over RCCL (grouped
 send / receive, one batch per table).  Default: every picture the rank needs is resident in HBM before the clock starts (a 64-picture 2160p sequence is 0.6 GB
@@ -12,7 +12,8 @@ of the 288 GB).  --stream: pictures come from the file (or the generator) throug
 (hmme/sequence.py): reader thread -> page-locked buffers -> copy stream || compute stream || download stream; the clock then
 includes reading and uploading.  --pairs-per-launch K puts K picture pairs into one launch (small pictures do not fill the
 chip one pair at a time).  --dump writes tables (a subset with --dump-pairs / --dump-ctus) for the parity tests; this tool
-itself never touches the CPU oracle.  Rank 0 prints ONE JSON line.
+itself never touches the CPU oracle.  --select N runs the partition decision (hmme_select_pairs_device, N MVs per CTU) behind each launch: the
+motion field, the covering slots and the CTU costs are then what --download copies and what the JSON line summarises.  Rank 0 prints ONE JSON line.
 """
 import argparse
 import json
@@ -39,6 +40,9 @@ def main():
     ap.add_argument("--pairs-per-launch", type=int, default=1)
     ap.add_argument("--refine", action="store_true", help="also run the fractional-pel refinement of every pair (hmme_refine_pairs_device)")
     ap.add_argument("--download", action="store_true", help="bring each batch's tables into page-locked host memory on a third stream")
+    ap.add_argument("--select", type=int, default=0, choices=[0, 64, 256],
+                    help="partition decision and motion field on the device behind each launch, this many MVs per CTU (hmme_select_pairs_device): on the "
+                         "refinement's tables with --refine, else on the search's with the MV cost added (price_mv)")
     ap.add_argument("--dump", default=None, help="rank 0 writes the gathered tables (npz) for the parity tests")
     ap.add_argument("--dump-pairs", default=None, help="comma-separated pair indices to dump (default all)")
     ap.add_argument("--dump-ctus", default=None, help="first:count CTU range to dump (default all)")
@@ -98,6 +102,9 @@ def main():
     else:   # picture t = one texture translated by (3t, 2t)
         source = synth.Sequence(w, h, args.frames, seed=777, bit_depth=bd)
     n_ctu = api.load().hmme_num_ctus(w, h)
+    select = None
+    if args.select:
+        select = api.SelectParams(args.select, mv_unit=0 if args.refine else 1, price_mv=0 if args.refine else 1)
     res = None
     for _ in range(max(1, args.repeat)):
         res = None   # frees the previous pass's tables before the next allocates
@@ -105,7 +112,7 @@ def main():
             dist.barrier()
         res = sequence.run_rank(eng, source, mine, w, h, bd, args.search_range, stream_mode=args.stream,
                                 pairs_per_launch=args.pairs_per_launch, refine=args.refine, download=args.download,
-                                n_slots=args.slots or None, device=dev, weights=weights)
+                                n_slots=args.slots or None, device=dev, weights=weights, select=select)
     dt = res["seconds"]
     if use_dist:   # the slowest rank's time is the job's
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -118,6 +125,10 @@ def main():
     mv, sad = shard.gather_pair_results(res["mv"], res["sad"], len(pairs))
     if args.refine:
         qmv, cost = shard.gather_pair_results(res["qmv"], res["cost"], len(pairs))
+    if select is not None:
+        field, ctu_cost = shard.gather_pair_results(res["field"], res["ctu_cost"], len(pairs))
+        halves = res["slot"].view(res["slot"].shape[0], n_ctu, args.select // 2, 2)   # two uint16 slots travel as one word, like an MV
+        slot = shard.gather_pair_results(halves, res["ctu_cost"], len(pairs))[0]
     torch.cuda.synchronize()
     gather_s = time.perf_counter() - t0
     if rank == 0:
@@ -139,6 +150,9 @@ def main():
                           "size": [w, h], "search_range": args.search_range,
                           "rank0": {"pairs": len(mine), "launches": res["launches"], "plane_slots": res["plane_slots"], "uploads": res["uploads"],
                                     "stages": res["stages"]},
+                          **({"select": {"mv_per_ctu": args.select, "tables": "refinement" if args.refine else "search + MV cost",
+                                         "mean_ctu_cost": round(float(ctu_cost.to(torch.int64).bitwise_and(0xFFFFFFFF).double().mean().item()), 1)}}
+                             if select is not None else {}),
                           "median_mv_64x64": med, "pair_list": pairs,
                           "median_mv_64x64_of_first_pairs": med[:4], "first_pairs": pairs[:4]}))
         if args.dump:
@@ -149,8 +163,13 @@ def main():
             if args.refine:
                 d["qmv"] = qmv[sel, c0:c0 + cn].cpu().numpy()
                 d["cost"] = cost[sel, c0:c0 + cn].cpu().numpy().view(np.uint32)
-            if args.download and world == 1:   # what the download stream delivered must equal the device tables
-                d["host_equal"] = bool(torch.equal(res["host_mv"], res["mv"].cpu()) and torch.equal(res["host_sad"], res["sad"].cpu()))
+            if select is not None:
+                d["field"] = field[sel, c0:c0 + cn].cpu().numpy()
+                d["slot"] = slot[sel, c0:c0 + cn].reshape(len(sel), cn, args.select).cpu().numpy().view(np.uint16)
+                d["ctu_cost"] = ctu_cost[sel, c0:c0 + cn].cpu().numpy().view(np.uint32)
+            if args.download and world == 1:   # what the download stream delivered must equal the device's
+                keys = ("field", "slot", "ctu_cost") if select is not None else ("mv", "sad")
+                d["host_equal"] = bool(all(torch.equal(res["host_" + k], res[k].cpu()) for k in keys))
             np.savez(args.dump, **d)
     eng.close()
     if use_dist:
