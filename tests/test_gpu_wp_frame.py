@@ -5,6 +5,8 @@ bit-exact, MVs and costs.  Pictures are sized so that no case needs more than ab
 import numpy as np
 import pytest
 
+from frame_helpers import ctu_origin, oracle_search_w
+
 pytestmark = pytest.mark.gpu
 
 FADE = (40, 12, 6, 32)          # w0, offset, shift, round
@@ -44,28 +46,6 @@ def planes(engine, cur, ref, w, h, bd):
         pc.upload_pel(cur, (m, m))
         pr.upload_pel(ref, (m, m))
     return pc, pr
-
-
-def ctu_origin(ctu, w):
-    cx = (w + 63) // 64
-    return (ctu % cx) * 64, (ctu // cx) * 64
-
-
-def oracle_search_w(oracle_lib, cur, ref, w, h, sr, pred, lq, bd, wp, ctus):
-    """hmo_search_ctu_w per CTU: the CTU's 64x64 block of the padded current plane (partial CTUs completed by its edge replication), the padded
-    reference, the window of hmme_set_search_range for the CTU's predictor"""
-    from hmme import api, synth
-    m = synth.MARGIN
-    mv = np.zeros((len(ctus), 593, 2), np.int16)
-    sad = np.zeros((len(ctus), 593), np.uint32)
-    for k, ctu in enumerate(ctus):
-        x, y = ctu_origin(ctu, w)
-        px, py = (int(pred[ctu, 0]), int(pred[ctu, 1])) if pred is not None else (0, 0)
-        lt_x, lt_y, rb_x, rb_y = api.set_search_range(px, py, sr, x, y, w, h)
-        p = oracle_lib.make_params((lt_x, lt_y), (rb_x, rb_y), (px, py), lq, 1, bd)   # FEN on: xGetSADw must not consult it
-        ox, oy, osad = oracle_lib.search_ctu_w(cur, (m + x, m + y), ref, (m + x, m + y), p, wp)
-        mv[k, :, 0], mv[k, :, 1], sad[k] = ox, oy, osad
-    return mv, sad
 
 
 def check_search(engine, oracle_lib, w, h, bd, wp, sr, seed, fen=0, cur_ref=None):
