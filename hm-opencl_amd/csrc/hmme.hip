@@ -149,6 +149,8 @@ struct hmme_ctx {
   // hmme_select_frame: device staging for the tables, the predictors and the three results of one picture
   uint8_t* d_sel = nullptr;
   size_t sel_cap = 0;
+  // hmme_plane_stats / hmme_wp_estimate: the 64-bit sums of one call (kWpStat* below), allocated at first use
+  unsigned long long* d_wpest = nullptr;
 };
 
 struct hmme_plane {
@@ -174,6 +176,9 @@ struct hmme_plane {
   mutable hipEvent_t read_done = nullptr;
   mutable hipStream_t read_stream = nullptr;
   mutable bool read_pending = false;
+  // hmme_plane_stats: sum of the picture's samples and of |sample - normDC| of the contents last filled in; every fill drops them
+  mutable bool stats_valid = false;
+  mutable int64_t stats_dc = 0, stats_ac = 0;
   const uint8_t* origin() const { return d_data + (size_t)kMarginY * pitch + (size_t)kMarginX * bps; }
 };
 
@@ -427,6 +432,7 @@ int take_flag(hmme_ctx* ctx, int which, hipStream_t s, int* out) {
 template <typename SrcT, typename DstT>
 int plane_fill(hmme_plane* pl, const SrcT* d_src, int src_pitch_elems, hipStream_t s, bool check) {
   hmme_ctx* ctx = pl->ctx;
+  pl->stats_valid = false;   // hmme_plane_stats: the cached sums describe the previous contents
   int wrc = plane_write_wait(ctx, pl, s);   // the previous fill and the last reader, if on other streams
   if (wrc) return wrc;
   dim3 grid((pl->pitch / 4 + 255) / 256, pl->rows);
@@ -542,6 +548,7 @@ void hmme_destroy(hmme_ctx* ctx) {
   for (int i = 0; i < 4; ++i) hipFree(ctx->d_wp[i]);
   for (int i = 0; i < 2; ++i) hipFree(ctx->d_bi[i]);
   hipFree(ctx->d_sel);
+  hipFree(ctx->d_wpest);
   if (ctx->h_call) hipHostFree(ctx->h_call);
   if (ctx->h_res) hipHostFree(ctx->h_res);
   delete ctx;
@@ -2249,6 +2256,245 @@ int hmme_select_frame(hmme_ctx* ctx, int width, int height, const hmme_frame_par
   if (out_cost) HIP_TRY(ctx, hipMemcpyAsync(out_cost + first, d + o_ccost + (size_t)first * 4, (size_t)count * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipStreamSynchronize(s));
   return HMME_OK;
+}
+
+// ---- estimating explicit weighted-prediction parameters ----------------------------------------------------------------------------------------
+// WeightPredAnalysis::xCalcACDCParamSlice / xEstimateWPParamSlice / xUpdatingWPParameters / xSelectWP / xCalcSADvalueWP
+// (WeightPredAnalysis.cpp:67-120, :172-351) for luma: the whole-picture sums are kernels (me_plane_stats_kernel, me_wp_sad_kernel), the scalar
+// derivation between and behind them runs here in HM's own double / Int64 arithmetic.  Synchronous, on the context's private stream.
+namespace {
+// ctx->d_wpest: [2 i] / [2 i + 1] = sample sum and AC of plane i of the call, then two sums per reference of the SAD pass
+constexpr int kWpStatPlanes = hmme::kMaxRefs + 1;
+constexpr int kWpStatSad = 2 * kWpStatPlanes;
+constexpr int kWpStatWords = kWpStatSad + 2 * hmme::kMaxRefs;
+constexpr int kWpStatBlocks = 1024;   // workgroups of one launch at most: each ends in one atomic add per sum
+
+// lanes per row (log2) and workgroups of a reduction over the picture area of `pl`, n_y of them side by side (me_kernels.hpp: the geometry
+// shared by the two kernels); rows are dealt evenly over the rounds a capped grid needs
+struct StatGrid { int lpr_log2; unsigned blocks; };
+StatGrid stat_grid(const hmme_plane* pl, int n_y) {
+  const int nvec = (pl->width * pl->bps + 15) / 16;
+  int l = 0;
+  while ((1 << l) < nvec && l < 8) ++l;
+  const int rpb = 256 >> l, row_blocks = (pl->height + rpb - 1) / rpb, cap = std::max(1, kWpStatBlocks / n_y);
+  const int rounds = (row_blocks + cap - 1) / cap;
+  return {l, (unsigned)((row_blocks + rounds - 1) / rounds)};
+}
+
+// the two passes of xCalcACDCParamSlice over one plane into sums[0], sums[1] (zero on entry); pass B reads what pass A left, same stream
+int launch_stats(hmme_ctx* ctx, const hmme_plane* pl, unsigned long long* sums, hipStream_t s) {
+  const StatGrid g = stat_grid(pl, 1);
+  if (pl->bps == 1) {
+    hipLaunchKernelGGL((hmme::me_plane_stats_kernel<uint8_t, 0>), dim3(g.blocks), dim3(256), 0, s, pl->origin(), pl->pitch, pl->width, pl->height, g.lpr_log2, sums);
+    hipLaunchKernelGGL((hmme::me_plane_stats_kernel<uint8_t, 1>), dim3(g.blocks), dim3(256), 0, s, pl->origin(), pl->pitch, pl->width, pl->height, g.lpr_log2, sums);
+  } else {
+    hipLaunchKernelGGL((hmme::me_plane_stats_kernel<uint16_t, 0>), dim3(g.blocks), dim3(256), 0, s, pl->origin(), pl->pitch, pl->width, pl->height, g.lpr_log2, sums);
+    hipLaunchKernelGGL((hmme::me_plane_stats_kernel<uint16_t, 1>), dim3(g.blocks), dim3(256), 0, s, pl->origin(), pl->pitch, pl->width, pl->height, g.lpr_log2, sums);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  return HMME_OK;
+}
+
+// xCalcSADvalueWP of `cur` against n_refs references of its size and sample type in one launch, two sums per reference (zero on entry)
+int launch_wp_sad(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme::MeWpSad& a, unsigned long long* sums, hipStream_t s) {
+  const StatGrid g = stat_grid(cur, n_refs);
+  RefSet rs = one_ref(refs[0]->origin());
+  for (int r = 0; r < n_refs; ++r) rs.base[r] = refs[r]->origin();
+  if (cur->bps == 1)
+    hipLaunchKernelGGL(hmme::me_wp_sad_kernel<uint8_t>, dim3(g.blocks, (unsigned)n_refs), dim3(256), 0, s, cur->origin(), rs, cur->pitch, cur->width, cur->height, g.lpr_log2, a, sums);
+  else
+    hipLaunchKernelGGL(hmme::me_wp_sad_kernel<uint16_t>, dim3(g.blocks, (unsigned)n_refs), dim3(256), 0, s, cur->origin(), rs, cur->pitch, cur->width, cur->height, g.lpr_log2, a, sums);
+  HIP_TRY(ctx, hipGetLastError());
+  return HMME_OK;
+}
+
+// kernels on `s` read planes[0 .. n): what pairs_begin / pairs_end do for the planes of picture pairs -- the scratch (d_wpest) and the last fill of
+// every plane before, one event of the context's ring behind, so that a refill of any of them on another stream waits
+int planes_read_begin(hmme_ctx* ctx, const hmme_plane* const* planes, int n, hipStream_t s) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!ctx->d_wpest) HIP_TRY(ctx, hipMalloc((void**)&ctx->d_wpest, sizeof(unsigned long long) * kWpStatWords));
+  int rc = scratch_acquire(ctx, s);
+  for (int i = 0; i < n && rc == HMME_OK; ++i) rc = plane_wait(ctx, planes[i], s);
+  return rc;
+}
+int planes_read_end(hmme_ctx* ctx, const hmme_plane* const* planes, int n, hipStream_t s, int rc) {
+  for (int i = 0; i < n; ++i) {
+    const int r2 = plane_read_chain(ctx, planes[i], s);
+    if (rc == HMME_OK) rc = r2;
+  }
+  const int r3 = launch_end(ctx, s);
+  if (r3 == HMME_OK)
+    for (int i = 0; i < n; ++i) plane_read_mark(ctx, planes[i], s);
+  return rc ? rc : r3;
+}
+
+// the sums of every plane of the list that has none cached: all their passes enqueued, one download, one wait
+int collect_stats(hmme_ctx* ctx, const hmme_plane* const* planes, int n, hipStream_t s) {
+  const hmme_plane* todo[kWpStatPlanes];
+  int n_todo = 0;
+  for (int i = 0; i < n; ++i) {
+    if (planes[i]->stats_valid) continue;
+    int q = 0;
+    while (q < n_todo && todo[q] != planes[i]) ++q;
+    if (q == n_todo) todo[n_todo++] = planes[i];
+  }
+  if (n_todo == 0) return HMME_OK;
+  int rc = planes_read_begin(ctx, todo, n_todo, s);
+  if (rc) return rc;
+  unsigned long long h[2 * kWpStatPlanes];
+  hipError_t e = hipMemsetAsync(ctx->d_wpest, 0, sizeof(unsigned long long) * 2 * n_todo, s);
+  if (e != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "plane statistics: %s", hipGetErrorString(e));
+  for (int j = 0; j < n_todo && rc == HMME_OK; ++j) rc = launch_stats(ctx, todo[j], ctx->d_wpest + 2 * j, s);
+  if (rc == HMME_OK && (e = hipMemcpyAsync(h, ctx->d_wpest, sizeof(unsigned long long) * 2 * n_todo, hipMemcpyDeviceToHost, s)) != hipSuccess)
+    rc = fail(ctx, HMME_ERR_DEVICE, "plane statistics: %s", hipGetErrorString(e));
+  rc = planes_read_end(ctx, todo, n_todo, s, rc);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  for (int j = 0; j < n_todo; ++j) {
+    todo[j]->stats_dc = (int64_t)h[2 * j]; todo[j]->stats_ac = (int64_t)h[2 * j + 1];
+    todo[j]->stats_valid = true;
+  }
+  return HMME_OK;
+}
+
+// what hmme_wp_estimate refuses; fills planes[0] = cur, planes[1 + r] = refs[r]
+int wp_estimate_args(hmme_ctx* ctx, const char* who, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane** planes) {
+  if (!cur || !refs) return fail(ctx, HMME_ERR_ARG, "%s: null plane", who);
+  if (n_refs < 1 || n_refs > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d references outside 1..%d", who, n_refs, hmme::kMaxRefs);
+  if (cur->ctx != ctx) return fail(ctx, HMME_ERR_ARG, "%s: plane belongs to another context", who);
+  planes[0] = cur;
+  for (int r = 0; r < n_refs; ++r) {
+    const hmme_plane* p = refs[r];
+    if (!p) return fail(ctx, HMME_ERR_ARG, "%s: reference %d is null", who, r);
+    if (p->ctx != ctx) return fail(ctx, HMME_ERR_ARG, "%s: reference %d belongs to another context", who, r);
+    if (p->width != cur->width || p->height != cur->height || p->bit_depth != cur->bit_depth)
+      return fail(ctx, HMME_ERR_ARG, "%s: reference %d is %d x %d at %d bits, the current picture %d x %d at %d", who, r, p->width, p->height, p->bit_depth,
+                  cur->width, cur->height, cur->bit_depth);
+    planes[1 + r] = p;
+  }
+  return HMME_OK;
+}
+}  // namespace
+
+int hmme_plane_stats(const hmme_plane* pl, int64_t* dc_sum, int64_t* ac) {
+  if (!pl) return HMME_ERR_ARG;
+  hmme_ctx* ctx = pl->ctx;
+  if (!dc_sum || !ac) return fail(ctx, HMME_ERR_ARG, "hmme_plane_stats: null output");
+  const int rc = collect_stats(ctx, &pl, 1, ctx->stream);
+  if (rc) return rc;
+  *dc_sum = pl->stats_dc; *ac = pl->stats_ac;
+  return HMME_OK;
+}
+
+int hmme_wp_estimate(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, int log2_denom_start, hmme_weight* out_wp,
+                     hmme_wp_info* out_info) {
+  if (!ctx) return HMME_ERR_ARG;
+  if (!out_wp) return fail(ctx, HMME_ERR_ARG, "hmme_wp_estimate: null output");
+  if (log2_denom_start < 3 || log2_denom_start > 7) return fail(ctx, HMME_ERR_ARG, "hmme_wp_estimate: log2_denom_start %d outside 3..7", log2_denom_start);
+  const hmme_plane* planes[kWpStatPlanes];
+  int rc = wp_estimate_args(ctx, "hmme_wp_estimate", cur, refs, n_refs, planes);
+  if (rc) return rc;
+  hipStream_t s = ctx->stream;
+  rc = collect_stats(ctx, planes, 1 + n_refs, s);   // xCalcACDCParamSlice of every picture that has not been through it since its last fill
+  if (rc) return rc;
+
+  // xEstimateWPParamSlice (:172-196): xUpdatingWPParameters (:200-268) from log2_denom_start downwards until every weight is in range
+  const int bd = cur->bit_depth;
+  const int64_t n_samples = (int64_t)cur->width * cur->height;
+  auto norm_dc = [&](int64_t sum) { return (sum + (n_samples >> 1)) / n_samples; };   // :115 without the RExt precision shift
+  const int64_t cur_dc = norm_dc(cur->stats_dc), cur_ac = cur->stats_ac;
+  int d = log2_denom_start, weight[hmme::kMaxRefs], offset[hmme::kMaxRefs];
+  for (;; --d) {   // ends at d = 3 at the latest: dWeight <= 15 puts weight in [0, 120], (1 << 3) - weight in [-112, 8]
+    const int real_d = d + (bd - 8);
+    bool in_range = true;
+    for (int r = 0; r < n_refs && in_range; ++r) {
+      const int64_t ref_dc = norm_dc(refs[r]->stats_dc), ref_ac = refs[r]->stats_ac;
+      const double dw = ref_ac == 0 ? 1.0 : std::min(std::max(-16.0, (double)cur_ac / (double)ref_ac), 15.0);        // :234
+      const int wgt = (int)(0.5 + dw * (double)(1 << d));                                                             // :235
+      const int off = (int)(((cur_dc << d) - (int64_t)wgt * ref_dc + ((int64_t)1 << (real_d - 1))) >> real_d);        // :236
+      weight[r] = wgt;
+      offset[r] = std::min(std::max(-128, off), 127);                                                                  // :248, range = 128
+      const int delta = (1 << d) - wgt;                                                                                // :252-258
+      in_range = !(delta >= 128 || delta < -128);
+    }
+    if (in_range) break;
+  }
+
+  // xSelectWP (:272-320): xCalcSADvalueWP with the estimated and with the default parameters, one read of the planes for both
+  hmme::MeWpSad a = {};
+  for (int r = 0; r < n_refs; ++r) {
+    a.weight[r] = weight[r];
+    a.offset[r] = offset[r] * (1 << (d + bd - 8));   // iOffset << iRealLog2Denom (:344)
+    a.log2_denom[r] = d;
+  }
+  rc = planes_read_begin(ctx, planes, 1 + n_refs, s);
+  if (rc) return rc;
+  unsigned long long h[2 * hmme::kMaxRefs];
+  unsigned long long* d_sums = ctx->d_wpest + kWpStatSad;
+  hipError_t e = hipMemsetAsync(d_sums, 0, sizeof(unsigned long long) * 2 * n_refs, s);
+  if (e != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "hmme_wp_estimate: %s", hipGetErrorString(e));
+  if (rc == HMME_OK) rc = launch_wp_sad(ctx, cur, refs, n_refs, a, d_sums, s);
+  if (rc == HMME_OK && (e = hipMemcpyAsync(h, d_sums, sizeof(unsigned long long) * 2 * n_refs, hipMemcpyDeviceToHost, s)) != hipSuccess)
+    rc = fail(ctx, HMME_ERR_DEVICE, "hmme_wp_estimate: %s", hipGetErrorString(e));
+  rc = planes_read_end(ctx, planes, 1 + n_refs, s, rc);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+
+  for (int r = 0; r < n_refs; ++r) {
+    const int64_t sad_wp = (int64_t)h[2 * r] / n_samples, sad_nowp = (int64_t)(h[2 * r + 1] << d) / n_samples;   // :350
+    const double ratio = (double)sad_wp / (double)sad_nowp;   // :305 -- 0 / 0 is NaN and NaN >= 0.99 is false: identical pictures keep their (identity) weight present
+    int present = 1;
+    if (ratio >= 0.99) {   // DTHRESH (:46); :306-314
+      present = 0;
+      weight[r] = 1 << d;
+      offset[r] = 0;
+    }
+    // TComSlice::initWpScaling (TComSlice.cpp:1487-1512): what the search and the refinement take
+    const hmme_weight wp = {weight[r], offset[r] * (1 << (bd - 8)), d, d ? 1 << (d - 1) : 0};
+    out_wp[r] = wp;
+    if (out_info) {
+      hmme_wp_info& o = out_info[r];
+      o.cur_dc_sum = cur->stats_dc; o.cur_ac = cur_ac; o.ref_dc_sum = refs[r]->stats_dc; o.ref_ac = refs[r]->stats_ac;
+      o.sad_wp = sad_wp; o.sad_nowp = sad_nowp;
+      o.log2_denom = d; o.weight = weight[r]; o.offset = offset[r];
+      o.present = present;
+      o.served_search = hmme_weight_check(bd, &wp, 0) == HMME_OK ? 1 : 0;
+      o.served_refine = hmme_weight_check(bd, &wp, 1) == HMME_OK ? 1 : 0;
+    }
+  }
+  return HMME_OK;
+}
+
+int hmme_test_time_wp_estimate_passes(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_weight* wp, void* stream,
+                                      int reps, float* stats_ms, float* sad_ms) {
+  if (!ctx) return HMME_ERR_ARG;
+  if (!wp || !stats_ms || !sad_ms || reps < 1 || wp->shift < 0 || wp->shift > 7) return fail(ctx, HMME_ERR_ARG, "hmme_test_time_wp_estimate_passes: bad argument");
+  const hmme_plane* planes[kWpStatPlanes];
+  int rc = wp_estimate_args(ctx, "hmme_test_time_wp_estimate_passes", cur, refs, n_refs, planes);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  rc = planes_read_begin(ctx, planes, 1 + n_refs, s);
+  if (rc) return rc;
+  hmme::MeWpSad a = {};
+  for (int r = 0; r < n_refs; ++r) { a.weight[r] = wp->w0; a.offset[r] = wp->offset * (1 << wp->shift); a.log2_denom[r] = wp->shift; }
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  hipError_t e = hipMemsetAsync(ctx->d_wpest, 0, sizeof(unsigned long long) * kWpStatWords, s);
+  for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
+  float ms0 = 0.f, ms1 = 0.f;
+  if (e == hipSuccess) {
+    e = hipEventRecord(ev[0], s);
+    for (int i = 0; i < reps && rc == HMME_OK; ++i) rc = launch_stats(ctx, cur, ctx->d_wpest, s);
+    if (e == hipSuccess) e = hipEventRecord(ev[1], s);
+    for (int i = 0; i < reps && rc == HMME_OK; ++i) rc = launch_wp_sad(ctx, cur, refs, n_refs, a, ctx->d_wpest + kWpStatSad, s);
+    if (e == hipSuccess) e = hipEventRecord(ev[2], s);
+    if (e == hipSuccess) e = hipEventSynchronize(ev[2]);
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms0, ev[0], ev[1]);
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms1, ev[1], ev[2]);
+  }
+  for (int i = 0; i < 3; ++i) if (ev[i]) hipEventDestroy(ev[i]);
+  if (rc == HMME_OK && e != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "timing the estimator's passes: %s", hipGetErrorString(e));
+  if (rc == HMME_OK) { *stats_ms = ms0 / reps; *sad_ms = ms1 / reps; }
+  return planes_read_end(ctx, planes, 1 + n_refs, s, rc);
 }
 
 int hmme_test_time_bipred_origin(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* other, const void* d_other_mv, int mv_per_ctu, void* stream,

@@ -2409,4 +2409,139 @@ me_select_kernel(const uint32_t* __restrict__ mv_tab, const uint32_t* __restrict
   }
 }
 
+// ---- estimating explicit weighted-prediction parameters (hmme_plane_stats / hmme_wp_estimate) ---------------------------------------------
+// The whole-picture reductions of HM's WeightPredAnalysis (WeightPredAnalysis.cpp:67-120 xCalcACDCParamSlice, :324-351 xCalcSADvalueWP) over
+// the PICTURE AREA of padded planes -- no margin, no replicated edge.  Geometry shared by both kernels: a workgroup of 256 lanes is
+// (256 >> lpr_log2) rows of (1 << lpr_log2) lanes, lpr = the smallest power of two that covers a row's 16-byte vectors (at most 256), so narrow
+// pictures keep their lanes busy and nothing is divided; rows advance by gridDim.x * rows-per-workgroup, a row's vectors by lpr.  The picture's
+// left edge is 128 samples into a pitch that is a multiple of 256 bytes, so every vector is a 16-byte aligned load; the last vector of a row
+// may reach into the right margin (128 samples: always inside the row) and is masked to the row's bytes.
+// Sums: one 32-bit partial per vector (bounds at the kernels), widened into a 64-bit lane sum right away; lanes are folded wave by wave with a
+// butterfly, the four wave sums through LDS, and ONE 64-bit atomic add per workgroup and sum reaches memory.  Integer adds only: the result
+// does not depend on the order of workgroups.
+
+// the bytes of dword k that belong to a row of which nb (1..15) bytes lie in the vector
+__device__ __forceinline__ uint32_t me_tail_mask(int nb, int k) {
+  const int vb = nb - 4 * k;
+  return vb >= 4 ? 0xffffffffu : vb <= 0 ? 0u : (1u << (8 * vb)) - 1u;
+}
+// packed sum of absolute differences of one dword of samples + acc: v_sad_u8 (four u8) / v_sad_u16 (two u16)
+template <typename T>
+__device__ __forceinline__ uint32_t me_sad_packed(uint32_t a, uint32_t b, uint32_t acc) {
+  if (sizeof(T) == 1) return __builtin_amdgcn_sad_u8(a, b, acc);
+  return __builtin_amdgcn_sad_u16(a, b, acc);
+}
+template <int NSUM>
+__device__ __forceinline__ void me_block_sum_u64(uint64_t (&v)[NSUM], unsigned long long* out) {
+  __shared__ uint64_t s_part[4][NSUM];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+  for (int k = 0; k < NSUM; ++k) {
+#pragma unroll
+    for (int mask = 32; mask >= 1; mask >>= 1) v[k] += me_shfl_xor_u64(v[k], mask);
+    if (lane == 0) s_part[wave][k] = v[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < NSUM)
+    atomicAdd(out + threadIdx.x, (unsigned long long)(s_part[0][threadIdx.x] + s_part[1][threadIdx.x] + s_part[2][threadIdx.x] + s_part[3][threadIdx.x]));
+}
+
+// xCalcACDCParamSlice in two launches on one stream.  PASS 0: sums[0] += sum of the samples (iOrgDC; v_sad against 0).  PASS 1: reads sums[0]
+// as pass 0 left it, normDC = (iOrgDC + (N >> 1)) / N (:99), sums[1] += sum of |sample - normDC| (iOrgAC; v_sad against the replicated mean).
+// A vector's partial is at most 16 * 255 / 8 * 4095.
+template <typename T, int PASS>
+__global__ void __launch_bounds__(256)
+me_plane_stats_kernel(const uint8_t* __restrict__ origin, int pitch, int w, int h, int lpr_log2, unsigned long long* sums) {
+  __shared__ uint32_t s_mean;
+  uint32_t mean = 0;   // the mean in every sample of a dword
+  if (PASS == 1) {
+    if (threadIdx.x == 0) {
+      const unsigned long long n = (unsigned long long)w * (unsigned long long)h;
+      s_mean = (uint32_t)((sums[0] + (n >> 1)) / n);
+    }
+    __syncthreads();
+    mean = s_mean * (sizeof(T) == 1 ? 0x01010101u : 0x00010001u);
+  }
+  const int lpr = 1 << lpr_log2, lx = threadIdx.x & (lpr - 1), ry = threadIdx.x >> lpr_log2, rpb = 256 >> lpr_log2;
+  const int row_bytes = w * (int)sizeof(T), nvec = (row_bytes + 15) >> 4;
+  uint64_t acc[1] = {0};
+  for (int y = blockIdx.x * rpb + ry; y < h; y += gridDim.x * rpb) {
+    const uint8_t* row = origin + (long)y * pitch;
+    for (int v = lx; v < nvec; v += lpr) {
+      const uint4 in = *(const uint4*)(row + 16 * v);
+      const uint32_t d[4] = {in.x, in.y, in.z, in.w};
+      const int nb = row_bytes - 16 * v;
+      uint32_t part = 0;
+      if (nb >= 16) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) part = me_sad_packed<T>(d[k], mean, part);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const uint32_t m = me_tail_mask(nb, k);
+          part = me_sad_packed<T>(d[k] & m, mean & m, part);
+        }
+      }
+      acc[0] += part;
+    }
+  }
+  me_block_sum_u64<1>(acc, sums + PASS);
+}
+
+// xCalcSADvalueWP for one current picture against up to kMaxRefs references in one launch (blockIdx.y = reference), each with its own
+// (weight, offset, log2Denom); offset arrives as HM's term iOffset << (log2Denom + bitDepth - 8).  Per reference two sums:
+//   sums[2 r]     += sum of |(org << d) - (ref * weight + offset)|      (:344; int32 multiply-add)
+//   sums[2 r + 1] += sum of |org - ref|                                 (packed SAD; HM's unweighted sum is this << d exactly)
+// so one read of the two planes serves both of HM's calls.  Bounds: hmme_wp_estimate hands over weight in [0, 1920] (dWeight clipped to 15, d <= 7),
+// |offset| <= 128 << 11 and d <= 7, so a 12-bit sample's term is below 4095 * 1920 + 2^19 + 2^18 < 2^23 and a vector's partial (8 of them; 16 at
+// 8 bit, each below 2^19) below 2^26 -- far inside 32 bits; the lane sums are 64-bit.
+struct MeWpSad { int weight[kMaxRefs], offset[kMaxRefs], log2_denom[kMaxRefs]; };
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+me_wp_sad_kernel(const uint8_t* __restrict__ cur, RefSet refs, int pitch, int w, int h, int lpr_log2, MeWpSad a, unsigned long long* sums) {
+  constexpr int N = 16 / (int)sizeof(T), PER = 4 / (int)sizeof(T);   // samples per vector / per dword
+  const int r = blockIdx.y;
+  const uint8_t* __restrict__ ref = refs.base[r];
+  const int wt = a.weight[r], off = a.offset[r], d = a.log2_denom[r];
+  const int lpr = 1 << lpr_log2, lx = threadIdx.x & (lpr - 1), ry = threadIdx.x >> lpr_log2, rpb = 256 >> lpr_log2;
+  const int row_bytes = w * (int)sizeof(T), nvec = (row_bytes + 15) >> 4;
+  uint64_t acc[2] = {0, 0};
+  auto sample = [](uint32_t dw, int j) -> int { return sizeof(T) == 1 ? (int)((dw >> (8 * j)) & 0xffu) : (int)((dw >> (16 * j)) & 0xffffu); };
+  for (int y = blockIdx.x * rpb + ry; y < h; y += gridDim.x * rpb) {
+    const long row = (long)y * pitch;
+    for (int v = lx; v < nvec; v += lpr) {
+      const uint4 o4 = *(const uint4*)(cur + row + 16 * v), r4 = *(const uint4*)(ref + row + 16 * v);
+      const uint32_t o[4] = {o4.x, o4.y, o4.z, o4.w}, q[4] = {r4.x, r4.y, r4.z, r4.w};
+      const int nb = row_bytes - 16 * v;
+      uint32_t pw = 0, pn = 0;
+      if (nb >= 16) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          pn = me_sad_packed<T>(o[k], q[k], pn);
+#pragma unroll
+          for (int j = 0; j < PER; ++j) {
+            const int t = (sample(o[k], j) << d) - (sample(q[k], j) * wt + off);
+            pw += (uint32_t)(t < 0 ? -t : t);
+          }
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const uint32_t m = me_tail_mask(nb, k);
+          pn = me_sad_packed<T>(o[k] & m, q[k] & m, pn);
+#pragma unroll
+          for (int j = 0; j < PER; ++j) {
+            const int t = (sample(o[k], j) << d) - (sample(q[k], j) * wt + off);
+            if ((4 * k + j * (int)sizeof(T)) < nb) pw += (uint32_t)(t < 0 ? -t : t);
+          }
+        }
+      }
+      acc[0] += pw;
+      acc[1] += pn;
+    }
+  }
+  me_block_sum_u64<2>(acc, sums + 2 * r);
+}
+
 }  // namespace hmme

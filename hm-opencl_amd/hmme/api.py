@@ -26,9 +26,11 @@ SYMBOLS = ["hmme_create", "hmme_destroy", "hmme_last_error", "hmme_device_info",
            "hmme_weight_check", "hmme_search_pairs_w_device", "hmme_refine_pairs_w_device", "hmme_search_frame_w", "hmme_refine_frame_w",
            "hmme_bipred_check", "hmme_predict_pairs_device", "hmme_predict_frame", "hmme_search_pairs_bi_device", "hmme_refine_pairs_bi_device",
            "hmme_search_frame_bi", "hmme_refine_frame_bi",
-           "hmme_slot_key", "hmme_select_check", "hmme_select_pairs_device", "hmme_select_frame"]
+           "hmme_slot_key", "hmme_select_check", "hmme_select_pairs_device", "hmme_select_frame",
+           "hmme_plane_stats", "hmme_wp_estimate"]
 # test / measurement entry points (include/hmme_test.h): not part of the boundary
-TEST_SYMBOLS = ["hmme_test_time_search_kernel", "hmme_test_device_address", "hmme_test_frac_deal", "hmme_test_tail_plan", "hmme_test_time_weight_passes", "hmme_test_time_bipred_origin"]
+TEST_SYMBOLS = ["hmme_test_time_search_kernel", "hmme_test_device_address", "hmme_test_frac_deal", "hmme_test_tail_plan", "hmme_test_time_weight_passes", "hmme_test_time_bipred_origin",
+                "hmme_test_time_wp_estimate_passes"]
 ABI_VERSION = 6   # HMME_ABI_VERSION of the include/hmme.h these bindings were written against
 
 
@@ -45,6 +47,17 @@ class SearchParams(C.Structure):
 class Weight(C.Structure):
     """hmme_weight: luma WPScalingParam of the reference picture"""
     _fields_ = [("w0", C.c_int), ("offset", C.c_int), ("shift", C.c_int), ("round", C.c_int)]
+
+
+class WpInfo(C.Structure):
+    """hmme_wp_info: how hmme_wp_estimate arrived at one reference's weight (WeightPredAnalysis.cpp; the rule: include/hmme.h)"""
+    _fields_ = [("cur_dc_sum", C.c_int64), ("cur_ac", C.c_int64), ("ref_dc_sum", C.c_int64), ("ref_ac", C.c_int64),
+                ("sad_wp", C.c_int64), ("sad_nowp", C.c_int64),
+                ("log2_denom", C.c_int), ("weight", C.c_int), ("offset", C.c_int), ("present", C.c_int),
+                ("served_search", C.c_int), ("served_refine", C.c_int)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
 class SelectParams(C.Structure):
@@ -148,6 +161,9 @@ def load():
     L.hmme_select_check.argtypes = [C.POINTER(SelectParams)]
     L.hmme_select_pairs_device.argtypes = [vp, i, i, i, C.POINTER(FrameParams), C.POINTER(SelectParams), vp, vp, vp, vp, vp, vp, vp]
     L.hmme_select_frame.argtypes = [vp, i, i, C.POINTER(FrameParams), C.POINTER(SelectParams), vp, vp, vp, vp, vp, vp]
+    L.hmme_plane_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.hmme_wp_estimate.argtypes = [vp, vp, C.POINTER(vp), i, i, C.POINTER(Weight), C.POINTER(WpInfo)]
+    L.hmme_test_time_wp_estimate_passes.argtypes = [vp, vp, C.POINTER(vp), i, C.POINTER(Weight), vp, i, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.hmme_upload_status.argtypes = [vp, vp]
     L.hmme_test_device_address.argtypes = [vp, vp]
     L.hmme_test_device_address.restype = C.c_uint64
@@ -569,6 +585,32 @@ class Engine:
         self._check(self.L.hmme_select_frame(self.h, int(width), int(height), C.byref(fp), C.byref(sel), mv.ctypes.data, cost.ctypes.data, pptr,
                                              field.ctypes.data, slot.ctypes.data, ctu_cost.ctypes.data))
         return field, slot, ctu_cost
+
+    # ---- estimating explicit weighted-prediction parameters (include/hmme.h, "estimating explicit weighted-prediction parameters") ----
+    def plane_stats(self, plane):
+        """hmme_plane_stats: xCalcACDCParamSlice of one picture -> (dc_sum, ac) = (sum of the samples, sum of |sample - normDC|) over the picture
+        area; kept in the plane until its next upload"""
+        dc, ac = C.c_int64(), C.c_int64()
+        self._check(self.L.hmme_plane_stats(plane.h, C.byref(dc), C.byref(ac)))
+        return int(dc.value), int(ac.value)
+
+    def wp_estimate(self, cur, refs, log2_denom_start=6):
+        """hmme_wp_estimate: HM's luma weighted-prediction estimate for one current picture and the references of its slice (HM starts the
+        denominator at 6, at 7 with more than three references) -> (weights, infos): one (w0, offset, shift, round) per reference, as the *_w
+        calls take it, and one WpInfo each"""
+        n = len(refs)
+        ra = (C.c_void_p * n)(*[r.h for r in refs])
+        wa, ia = (Weight * max(n, 1))(), (WpInfo * max(n, 1))()
+        self._check(self.L.hmme_wp_estimate(self.h, cur.h, ra, n, int(log2_denom_start), wa, ia))
+        return [(w.w0, w.offset, w.shift, w.round) for w in wa[:n]], list(ia[:n])
+
+    def time_wp_estimate_passes(self, cur, refs, wp, stream=0, reps=5):
+        """device time in ms of the estimator's passes on their own -> (the two statistics launches over `cur`, the SAD pass against `refs`)"""
+        a, b = C.c_float(), C.c_float()
+        ra = (C.c_void_p * len(refs))(*[r.h for r in refs])
+        w = Weight(*[int(v) for v in wp])
+        self._check(self.L.hmme_test_time_wp_estimate_passes(self.h, cur.h, ra, len(refs), C.byref(w), stream, reps, C.byref(a), C.byref(b)))
+        return float(a.value), float(b.value)
 
     def time_bipred_origin(self, cur, other, d_other_mv, mv_per_ctu, stream=0, reps=5):
         """device time in ms of the origin pass of a bi-prediction search on its own (whole picture)"""

@@ -161,7 +161,10 @@ def run_rank(eng, source, pairs, width, height, bit_depth, search_range, *, stre
     resources: a RankResources the caller keeps between passes of one geometry (streaming mode): plane slots, host buffers and streams are
     then allocated by the first pass only and stay the caller's to close.
     weights: explicit weighted prediction -- one (w0, offset, shift, round) per pair, in the order of `pairs`; search (and refinement)
-    then go through hmme_search_pairs_w_device / hmme_refine_pairs_w_device.  None: the unweighted calls, as before.
+    then go through hmme_search_pairs_w_device / hmme_refine_pairs_w_device.  None: the unweighted calls, as before.  "estimate": every pair is
+    treated as a slice with one reference and its weight estimated on the device (hmme_wp_estimate, denominator start 6) just before the launch
+    that uses it; the result gains "weights" (the list, in the order of `pairs`) and "wp_info" (one dict per pair).  A pair whose estimate the
+    weighted calls do not serve ends the run with an HmmeError that names the pair's index, as a refused weight of a list does.
     select: an api.SelectParams -- the partition decision (hmme_select_pairs_device) runs on the compute stream behind each launch's refinement
     (behind its search with refine=False: the pure-SAD tables then need price_mv = 1, and their integer MVs mv_unit = 1).  The result gains the
     device tensors field [n, n_ctu, mv_per_ctu, 2] int16, slot [n, n_ctu, mv_per_ctu] int16 (the bits of the uint16 slots: -1 = 0xFFFF) and
@@ -173,7 +176,12 @@ def run_rank(eng, source, pairs, width, height, bit_depth, search_range, *, stre
     from . import api
     dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
     n = len(pairs)
-    if weights is not None:
+    estimate = isinstance(weights, str)
+    if estimate:
+        if weights != "estimate":
+            raise ValueError(f"weights: {weights!r} (a list of (w0, offset, shift, round), \"estimate\" or None)")
+        weights, wp_info = [None] * n, [None] * n
+    elif weights is not None:
         weights = [tuple(int(v) for v in w) for w in weights]
         if len(weights) != n or any(len(w) != 4 for w in weights):
             raise ValueError(f"weights: {len(weights)} entries for {n} pairs (one (w0, offset, shift, round) per pair)")
@@ -224,6 +232,13 @@ def run_rank(eng, source, pairs, width, height, bit_depth, search_range, *, stre
         curs = [planes[where_b[pairs[i][0]]] for i in idx]
         refs = [planes[where_b[pairs[i][1]]] for i in idx]
         i0, i1 = idx[0], idx[-1] + 1
+        if estimate:
+            for i, c, r in zip(idx, curs, refs):
+                (weights[i],), (info,) = eng.wp_estimate(c, [r], 6)
+                wp_info[i] = info.as_dict()
+                if not (info.served_refine if refine else info.served_search):
+                    raise api.HmmeError(f"pair {i}: the estimated weight {weights[i]} is not served by the weighted "
+                                        f"{'refinement' if refine else 'search'} at {bit_depth} bits (hmme_weight_check)")
         e = timed("search", compute)
         if weights is None:
             eng.search_pairs_device(curs, refs, fp, None, out["mv"][i0:i1].data_ptr(), out["sad"][i0:i1].data_ptr(), compute.cuda_stream)
@@ -327,6 +342,8 @@ def run_rank(eng, source, pairs, width, height, bit_depth, search_range, *, stre
             stages[kind + "_s"] = sum(a.elapsed_time(b) for a, b in lst) * 1e-3
         out["stages"] = {k: round(v, 5) for k, v in stages.items()}
         out["launches"] = len(batches)
+        if estimate:
+            out["weights"], out["wp_info"] = weights, wp_info
         out["plane_slots"] = len(planes)
         out["uploads"] = len(ev_pairs["upload"]) if stream_mode else len(pocs)
     finally:

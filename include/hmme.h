@@ -22,6 +22,8 @@
  *   hmme_search_pairs_w_device, <- the same in a slice with explicit weighted prediction (TEncSearch::setWpScalingDistParam,
  *   hmme_refine_pairs_w_device,    TEncSearch.cpp:5594-5635; TComRdCostWeightPrediction.cpp:55-90, :407-470), one weight per pair
  *   hmme_search_frame_w, hmme_refine_frame_w
+ *   hmme_plane_stats, hmme_wp_estimate <- WeightPredAnalysis::xCalcACDCParamSlice / xEstimateWPParamSlice (WeightPredAnalysis.cpp:67-120, :172-351):
+ *                                the weights those calls take, estimated from the planes
  *   hmme_predict_pairs_device,    <- motion compensation (TComPrediction::xPredInterBlk, TComPrediction.cpp:590-594, :669) and the bi-prediction
  *   hmme_search_pairs_bi_device,     pass of xMotionEstimation (origin 2*org - pred_other, TEncSearch.cpp:3702-3712; window around the list's
  *   hmme_refine_pairs_bi_device, ... MV, TEncSearch.cpp:3726-3737) on whole pictures and picture pairs
@@ -445,6 +447,52 @@ int hmme_select_pairs_device(hmme_ctx* ctx, int width, int height, int n_pairs, 
                              void* stream);
 int hmme_select_frame(hmme_ctx* ctx, int width, int height, const hmme_frame_params* fp, const hmme_select_params* sel, const int16_t* mv,
                       const uint32_t* cost, const int16_t* pred_q, int16_t* out_field, uint16_t* out_slot, uint32_t* out_cost);
+
+/* ---- estimating explicit weighted-prediction parameters --------------------------------------------------------
+ * Where the weights of the *_w calls come from when the caller has none: the luma part of HM's estimator, WeightPredAnalysis::
+ * xCalcACDCParamSlice, xEstimateWPParamSlice, xUpdatingWPParameters, xSelectWP and xCalcSADvalueWP (source/Lib/TLibEncoder/
+ * WeightPredAnalysis.cpp:67-120, :172-351), bit-identical to what HM computes for a 4:0:0 slice without high-precision weighting.  The
+ * whole-picture sums run on the device over the picture area of the planes (margins are never counted); the scalar steps run on the host in
+ * HM's own double / Int64 arithmetic.  New entry points and one new struct; nothing existing changed, so HMME_ABI_VERSION stays 6.
+ *
+ * hmme_plane_stats: xCalcACDCParamSlice (:67-120) for one picture, N = width * height:
+ *   dc_sum = sum of the samples (:86-97);  ac = sum of |sample - normDC| with normDC = (dc_sum + (N >> 1)) / N (:99-112).
+ * Synchronous.  The two sums are kept in the plane and returned without device work until the next upload / hmme_plane_set_device_u8 into
+ * it, which drops them.
+ *
+ * hmme_wp_estimate: xEstimateWPParamSlice for one current picture and the n_refs (1..16) references of its slice.  With bd = the bit depth
+ * and DC of a picture = (dc_sum + (N >> 1)) / N (:115):
+ *   1. d = log2_denom_start (3..7; HM starts at 6, at 7 with more than three references in list 0, :174-180).
+ *   2. For every reference (:227-258):
+ *        dWeight = refAC == 0 ? 1.0 : Clip3(-16.0, 15.0, (double)curAC / (double)refAC)
+ *        weight  = (int)(0.5 + dWeight * (double)(1 << d))
+ *        offset  = (int)(((curDC << d) - (int64)weight * refDC + (1 << (d + bd - 8 - 1))) >> (d + bd - 8)), then clipped to [-128, 127]
+ *      If (1 << d) - weight lies outside [-128, 128) for ANY reference, d is decremented and step 2 starts again (:182-189): all
+ *      references of a call share the denominator.  It ends at d = 3 at the latest: the clip to 15 keeps weight within [0, 120] there.
+ *   3. For every reference (xSelectWP, :285-316; xCalcSADvalueWP, :336-350), sums over the picture area:
+ *        sad_wp   = (sum of |(org << d) - (ref * weight + (offset << (d + bd - 8)))|) / N
+ *        sad_nowp = (sum of |(org << d) - (ref << d)|) / N
+ *        ratio    = (double)sad_wp / (double)sad_nowp;  ratio >= 0.99 (DTHRESH, :46): not present -- weight = 1 << d, offset = 0.
+ *      HM's corner cases are kept: identical pictures give 0 / 0 = NaN, NaN >= 0.99 is false, the (identity) weight stays PRESENT;
+ *      a positive sad_wp over sad_nowp == 0 is +inf and disables the weight.
+ *   4. out_wp[r] is the reference's luma WPScalingParam after TComSlice::initWpScaling (TComSlice.cpp:1487-1512): w0 = weight,
+ *      offset = offset << (bd - 8), shift = d, round = d ? 1 << (d - 1) : 0 -- what hmme_search_pairs_w_device and its siblings take.
+ * out_info (may be NULL) tells how each came about.  A weight that hmme_weight_check would refuse is still returned, with served_* = 0: the
+ * estimator describes HM's choice, the search calls keep their own refusal.  The same plane given twice gives equal entries.
+ * HMME_ERR_ARG (nothing launched, nothing written to the outputs): a null argument, planes of another context, a reference whose size or bit
+ * depth differs from the current picture's, n_refs outside 1..16, log2_denom_start outside 3..7.
+ * Ordering: the planes are read like any frame call reads them -- after their last fill, and recorded so that a refill on another stream
+ * waits; the work runs on the context's private stream (as hmme_select_frame) and the call returns when the results are there. */
+int hmme_plane_stats(const hmme_plane* plane, int64_t* dc_sum, int64_t* ac);
+typedef struct hmme_wp_info {
+  int64_t cur_dc_sum, cur_ac, ref_dc_sum, ref_ac;   /* xCalcACDCParamSlice */
+  int64_t sad_wp, sad_nowp;                         /* xCalcSADvalueWP: each already divided by W*H */
+  int log2_denom, weight, offset;                   /* iWeight, clipped iOffset (8-bit units), after xSelectWP */
+  int present;                                      /* bPresentFlag after xSelectWP */
+  int served_search, served_refine;                 /* hmme_weight_check(bit_depth, &wp, 0 / 1) == HMME_OK */
+} hmme_wp_info;
+int hmme_wp_estimate(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, int log2_denom_start, hmme_weight* out_wp,
+                     hmme_wp_info* out_info);
 
 /* ---- environment (diagnostics and A/B measurements; none of these changes a result) ---------
  *   HMME_TRACE=1          one stderr line per context about launch geometry the library derives at run time (with HMME_FRAC_GRID=-1:

@@ -37,6 +37,12 @@ int hmme_test_time_weight_passes(hmme_ctx* ctx, const hmme_plane* cur, const hmm
 int hmme_test_time_bipred_origin(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* other, const void* d_other_mv, int mv_per_ctu, void* stream,
                                  int reps, float* avg_ms);
 
+/* average device time in ms of the estimator's passes on their own, `reps` back-to-back launches each on `stream`: *stats_ms = the two launches
+ * of me_plane_stats_kernel over `cur`, *sad_ms = me_wp_sad_kernel of `cur` against the n_refs references, every one with weight wp->w0, offset
+ * wp->offset (8-bit units) and denominator wp->shift (<= 7) */
+int hmme_test_time_wp_estimate_passes(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_weight* wp, void* stream,
+                                      int reps, float* stats_ms, float* sad_ms);
+
 #ifdef __cplusplus
 }
 #endif

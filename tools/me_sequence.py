@@ -48,8 +48,9 @@ def main():
     ap.add_argument("--dump-ctus", default=None, help="first:count CTU range to dump (default all)")
     ap.add_argument("--repeat", type=int, default=1, help="run the pass this many times, report the last (the first includes allocations)")
     ap.add_argument("--weights", default=None,
-                    help="explicit weighted prediction: a text file with one line `w0 offset shift round` per pair of the GOP (pair order; # comments); "
-                         "searches and refinements then run through hmme_search_pairs_w_device / hmme_refine_pairs_w_device")
+                    help="explicit weighted prediction: `estimate` -- every pair's weight is estimated on the device the way HM does (hmme_wp_estimate, one "
+                         "reference per slice) and printed with the result -- or a text file with one line `w0 offset shift round` per pair of the GOP "
+                         "(pair order; # comments); searches and refinements then run through hmme_search_pairs_w_device / hmme_refine_pairs_w_device")
     ap.add_argument("--rank-timeout", type=float, default=600.0,
                     help="N > 1: seconds a rank may take from its start to the end of its first barrier (rendezvous, RCCL communicator) before it "
                          "gives up with exit code 3, naming itself and the stage it hung in; 0 = no limit")
@@ -89,7 +90,9 @@ def main():
     mine_idx = list(shard.pairs_for_rank(len(pairs), rank, world))
     mine = [pairs[p] for p in mine_idx]
     weights = None
-    if args.weights:
+    if args.weights == "estimate":
+        weights = "estimate"
+    elif args.weights:
         rows = [l.split("#")[0].split() for l in open(args.weights)]
         rows = [tuple(int(v) for v in r) for r in rows if r]
         if len(rows) != len(pairs) or any(len(r) != 4 for r in rows):
@@ -123,6 +126,14 @@ def main():
     import time
     t0 = time.perf_counter()
     mv, sad = shard.gather_pair_results(res["mv"], res["sad"], len(pairs))
+    est = None
+    if weights == "estimate":   # every rank's estimates to rank 0, in pair order like the tables
+        rows = list(zip(mine_idx, res["weights"], [d["present"] for d in res["wp_info"]]))
+        if use_dist:
+            parts = [None] * world if rank == 0 else None
+            dist.gather_object(rows, parts, dst=0)
+            rows = [r for p in parts for r in p] if rank == 0 else []
+        est = [{"pair": i, "weight": list(w), "present": p} for i, w, p in sorted(rows)]
     if args.refine:
         qmv, cost = shard.gather_pair_results(res["qmv"], res["cost"], len(pairs))
     if select is not None:
@@ -153,6 +164,7 @@ def main():
                           **({"select": {"mv_per_ctu": args.select, "tables": "refinement" if args.refine else "search + MV cost",
                                          "mean_ctu_cost": round(float(ctu_cost.to(torch.int64).bitwise_and(0xFFFFFFFF).double().mean().item()), 1)}}
                              if select is not None else {}),
+                          **({"estimated_weights": est} if est is not None else {}),
                           "median_mv_64x64": med, "pair_list": pairs,
                           "median_mv_64x64_of_first_pairs": med[:4], "first_pairs": pairs[:4]}))
         if args.dump:
