@@ -130,7 +130,7 @@ struct hmme_ctx {
   bool lds_optin[8] = {false, false, false, false, false, false, false, false};
   int num_cus = 0;
   bool frac_lds_optin[3][2] = {{false, false}, {false, false}, {false, false}};   // [8-bit | u16 | u16 weighted][hadamard]
-  int frac_wg_per_cu[2][2] = {{0, 0}, {0, 0}};   // [wide][hadamard] workgroups of me_frac_kernel a CU holds (runtime occupancy query, first use)
+  int frac_wg_per_cu[3][2] = {{0, 0}, {0, 0}, {0, 0}};   // same index: workgroups of that me_frac_kernel a CU holds (runtime occupancy query, first use)
   uint8_t* d_wwin = nullptr;          // per-CTU calls with weighted prediction: the weighted copy of the staged window (the search's)
   uint16_t* d_frac_cover = nullptr;   // fractional refinement: slots covering each 8x8 / 4x4 position, same for every CTU
   int16_t* d_imv = nullptr;           // host-facing refine call: integer MVs / quarter-pel MVs / costs on the device
@@ -742,21 +742,21 @@ const hmme::FracPrep kNoPrep = {nullptr, 1u << 16, 0, 0};
 // workgroups that take job after job from a counter instead, HMME_FRAC_GRID=-1 as many of those as the chip holds at a time (the
 // runtime's occupancy figure for this kernel with its LDS block x the CUs): round 4's intermediate launch, kept for A/B runs -- once
 // both orders ran last-first it was the slower one on every content (profiles/r04g_frac_grid_both_last_first.txt)
-int frac_grid(hmme_ctx* ctx, int wide, int had, int jobs) {
+int frac_grid(hmme_ctx* ctx, int wide, int had, int wp, int jobs) {
   static const int forced = std::getenv("HMME_FRAC_GRID") ? std::atoi(std::getenv("HMME_FRAC_GRID")) : 0;
   if (forced == 0) return jobs;
   int grid = forced;
   if (forced < 0) {
-    int& per_cu = ctx->frac_wg_per_cu[wide ? 1 : 0][had ? 1 : 0];
+    int& per_cu = ctx->frac_wg_per_cu[wp ? 2 : (wide ? 1 : 0)][had ? 1 : 0];
     if (per_cu == 0) {
       int n = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)frac_kernel(wide, had), hmme::frac_threads(wide ? 2 : 1),
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)frac_kernel(wide, had, wp), hmme::frac_threads(wide ? 2 : 1),
                                                        hmme::frac_lds_bytes(wide ? 2 : 1)) != hipSuccess || n < 1) {
         (void)hipGetLastError();
         n = 2;
       }
       per_cu = n;
-      if (std::getenv("HMME_TRACE")) fprintf(stderr, "hmme: me_frac_kernel<%d, %d>: %d workgroups per CU, %d CUs\n", had ? 1 : 0, wide ? 2 : 1, n, ctx->num_cus);
+      if (std::getenv("HMME_TRACE")) fprintf(stderr, "hmme: me_frac_kernel<%d, %d, %d>: %d workgroups per CU, %d CUs\n", had ? 1 : 0, wide ? 2 : 1, wp ? 1 : 0, n, ctx->num_cus);
     }
     grid = per_cu * ctx->num_cus;
   }
@@ -1417,29 +1417,56 @@ static int ensure_frame_buffers(hmme_ctx* ctx, size_t need) {
   return HMME_OK;
 }
 
+// host-facing refinement calls: device staging for the integer MVs, quarter-pel MVs and costs of `slots` (CTU, slot) entries
+static int ensure_refine_buffers(hmme_ctx* ctx, size_t slots) {
+  if (ctx->refine_cap >= slots) return HMME_OK;
+  hipFree(ctx->d_imv); hipFree(ctx->d_qmv); hipFree(ctx->d_fcost);
+  ctx->d_imv = nullptr; ctx->d_qmv = nullptr; ctx->d_fcost = nullptr; ctx->refine_cap = 0;
+  HIP_TRY(ctx, hipMalloc(&ctx->d_imv, sizeof(int16_t) * 2 * slots));
+  HIP_TRY(ctx, hipMalloc(&ctx->d_qmv, sizeof(int16_t) * 2 * slots));
+  HIP_TRY(ctx, hipMalloc(&ctx->d_fcost, sizeof(uint32_t) * slots));
+  ctx->refine_cap = slots;
+  return HMME_OK;
+}
+
+// The synchronous calls' way in, behind the checks of their own: the CTU range, the output pointers (a refinement's integer MVs too), then
+// -- unless the range is empty: *count == 0, nothing to do -- the device, the staging buffers, the predictors of `n_refs` references up
+// into d_pred (*d_pred: where the device call finds them, null without) and a refinement's integer MVs into d_imv.  On ctx->stream.
+static int stage_in(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_frame_params* fp, int n_refs, const int16_t* pred_q,
+                    bool refine, const int16_t* int_mv, const void* out_mv, const void* out_cost, int* count, const void** d_pred) {
+  int first;
+  int rc = check_frame_args(ctx, cur, ref, fp, &first, count);
+  if (rc) return rc;
+  if (refine ? (!int_mv || !out_mv || !out_cost) : (!out_mv || !out_cost)) return fail(ctx, HMME_ERR_ARG, refine ? "null buffer" : "null output buffer");
+  if (*count == 0) return HMME_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t need = (size_t)hmme_num_ctus(cur->width, cur->height) * n_refs;
+  if (refine) rc = ensure_refine_buffers(ctx, HMME_NUM_CTU_PARTS * need);
+  if (rc == HMME_OK) rc = ensure_frame_buffers(ctx, need);   // (a refinement's predictors travel in the search path's staging buffer)
+  if (rc) return rc;
+  if (pred_q) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_pred, pred_q, sizeof(int16_t) * 2 * need, hipMemcpyHostToDevice, ctx->stream));
+  if (refine) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_imv, int_mv, sizeof(int16_t) * 2 * HMME_NUM_CTU_PARTS * (size_t)*count * n_refs, hipMemcpyHostToDevice, ctx->stream));
+  *d_pred = pred_q ? ctx->d_pred : nullptr;
+  return HMME_OK;
+}
+// ... and out: the `tables` (CTU, reference) result tables of the search (d_mv, d_sad) or the refinement (d_qmv, d_fcost) down, and the wait
+static int stage_out(hmme_ctx* ctx, bool refine, size_t tables, int16_t* out_mv, uint32_t* out_cost) {
+  HIP_TRY(ctx, hipMemcpyAsync(out_mv, refine ? ctx->d_qmv : ctx->d_mv, sizeof(int16_t) * 2 * HMME_NUM_CTU_PARTS * tables, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(out_cost, refine ? ctx->d_fcost : ctx->d_sad, sizeof(uint32_t) * HMME_NUM_CTU_PARTS * tables, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return HMME_OK;
+}
+
 int hmme_search_frame_multi(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs,
                             const hmme_frame_params* fp, const int16_t* pred_q, int16_t* out_mv, uint32_t* out_sad) {
   if (!ctx) return HMME_ERR_ARG;
   if (!refs || n_refs < 1 || n_refs > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "n_refs %d outside 1..%d", n_refs, hmme::kMaxRefs);
-  int first, count;
-  int rc = check_frame_args(ctx, cur, refs[0], fp, &first, &count);
-  if (rc) return rc;
-  if (!out_mv || !out_sad) return fail(ctx, HMME_ERR_ARG, "null output buffer");
-  if (count == 0) return HMME_OK;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const int n_ctu = hmme_num_ctus(cur->width, cur->height);
-  const size_t need = (size_t)n_ctu * n_refs;
-  rc = ensure_frame_buffers(ctx, need);
-  if (rc) return rc;
-  hipStream_t s = ctx->stream;
-  if (pred_q) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_pred, pred_q, sizeof(int16_t) * 2 * need, hipMemcpyHostToDevice, s));
-  rc = hmme_search_frame_multi_device(ctx, cur, refs, n_refs, fp, pred_q ? ctx->d_pred : nullptr, ctx->d_mv, ctx->d_sad, s);
-  if (rc) return rc;
-  const size_t res = (size_t)count * n_refs;
-  HIP_TRY(ctx, hipMemcpyAsync(out_mv, ctx->d_mv, sizeof(int16_t) * 2 * HMME_NUM_CTU_PARTS * res, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(out_sad, ctx->d_sad, sizeof(uint32_t) * HMME_NUM_CTU_PARTS * res, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  return HMME_OK;
+  int count;
+  const void* d_pred;
+  int rc = stage_in(ctx, cur, refs[0], fp, n_refs, pred_q, false, nullptr, out_mv, out_sad, &count, &d_pred);
+  if (rc || count == 0) return rc;
+  rc = hmme_search_frame_multi_device(ctx, cur, refs, n_refs, fp, d_pred, ctx->d_mv, ctx->d_sad, ctx->stream);
+  return rc ? rc : stage_out(ctx, false, (size_t)count * n_refs, out_mv, out_sad);
 }
 
 int hmme_search_frame(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_frame_params* fp,
@@ -1473,6 +1500,80 @@ int build_frac_cover(hmme_ctx* ctx) {
   HIP_TRY(ctx, hipMemcpy(ctx->d_frac_cover, cover.data(), sizeof(uint16_t) * cover.size(), hipMemcpyHostToDevice));
   return HMME_OK;
 }
+
+// One refinement launch, whoever asks for it (plain, weighted, bi-prediction): cover table, job table and counter in d_frac_jobs, the
+// table's kernel where the launch reads one, LDS opt-in, me_frac_kernel.
+// kReuse: a table without predictors may be the one the launch before left (frac_jobs_tag); kAsNeeded: written where the launch reads
+// one; kAlways: written in any case -- the bi-prediction calls, whose table carries the window centres
+enum class FracTable { kReuse, kAsNeeded, kAlways };
+struct RefineLaunch {
+  RefSet curs, refs;   // one entry per pair of THIS launch
+  int cur_pitch = 0, ref_pitch = 0;
+  int wide = 0, had = 0, wp = 0;   // the build: frac_kernel(wide, had, wp)
+  hmme::FracWp fw = kNoWp;
+  const int16_t* d_pred = nullptr;     // [pairs][CTUs of the picture][2], null = zero predictors
+  const int16_t* d_center = nullptr;   // window centres, same layout; null = the predictors
+  int pairs = 0, first = 0, count = 0, width = 0, height = 0, search_range = 0, bit_depth = 0;
+  const int16_t* d_int_mv = nullptr;   // [pairs * count][593][2]
+  int16_t* d_qmv = nullptr;
+  uint32_t* d_cost = nullptr;
+  FracTable table = FracTable::kAsNeeded;
+};
+// what every picture-level refinement takes from its arguments; the caller adds the planes, the build and the predictors
+void refine_common(RefineLaunch& L, const PairLaunch& pl, const hmme_plane* cur, const hmme_frame_params* fp, int use_hadamard, const void* d_int_mv,
+                   void* d_out_qmv, void* d_out_cost) {
+  L.had = use_hadamard ? 1 : 0;
+  L.first = pl.first; L.count = pl.count; L.width = cur->width; L.height = cur->height; L.search_range = fp->search_range; L.bit_depth = fp->bit_depth;
+  L.d_int_mv = (const int16_t*)d_int_mv; L.d_qmv = (int16_t*)d_out_qmv; L.d_cost = (uint32_t*)d_out_cost;
+}
+
+int launch_refine(hmme_ctx* ctx, const RefineLaunch& L, hipStream_t s) {
+  const int jobs = L.count * L.pairs;
+  int rc = build_frac_cover(ctx);
+  if (rc) return rc;
+  // (a scratch that grows, grows to what kMaxRefs pairs of this CTU range need: the shorter and longer runs of one weighted call fit alike)
+  size_t cap = ctx->frac_jobs_bytes;
+  rc = ensure(ctx, (uint8_t**)&ctx->d_frac_jobs, &cap, sizeof(MeJob) * (size_t)jobs + 64,   // + the launch's job counter behind the table
+              sizeof(MeJob) * (size_t)L.count * hmme::kMaxRefs + 4096);
+  if (cap != ctx->frac_jobs_bytes || L.table != FracTable::kReuse) ctx->frac_jobs_tag.valid = false;
+  ctx->frac_jobs_bytes = cap;
+  if (rc) return rc;
+  uint32_t* counter = (uint32_t*)((uint8_t*)ctx->d_frac_jobs + ((sizeof(MeJob) * (size_t)jobs + 15) & ~(size_t)15));
+  const int grid = frac_grid(ctx, L.wide, L.had, L.wp, jobs);
+  // one workgroup per job (the default) on the two-wave builds: every workgroup derives its job itself (FracPrep) -- no job table, no
+  // launch in front of this one (1080p: 0.095 -> 0.090 ms).  A table is read by the job-walking launch of HMME_FRAC_GRID (its prep
+  // kernel is also what resets the job counter: every launch), under the A/B knob HMME_FRAC_JOB_TABLE (the job table and its kernel as
+  // before), by CTU ranges FracPrep cannot pack and by launches with window centres (FracPrep derives windows from predictors only)
+  static const bool table_forced = std::getenv("HMME_FRAC_JOB_TABLE") != nullptr;
+  const bool walk = grid < jobs;
+  const bool packable = L.count <= 0xffff && L.first <= 0xffff;   // FracPrep packs the CTU range into 16 + 16 bits (a 16384 x 16384 picture has 65 536 CTUs)
+  const bool need_table = L.table == FracTable::kAlways || walk || table_forced || !packable || L.d_center;
+  if (need_table) {
+    hmme_ctx::TableTag tag;
+    tag.valid = L.table == FracTable::kReuse && !L.d_pred && !L.d_center && !walk;
+    tag.w = L.width; tag.h = L.height; tag.bit_depth = L.bit_depth; tag.sr = L.search_range; tag.first = L.first; tag.count = L.count;
+    tag.pairs = L.pairs; tag.buf = ctx->d_frac_jobs; tag.stream = (void*)s;
+    if (!tag.same(ctx->frac_jobs_tag)) {
+      ctx->frac_jobs_tag = tag;
+      hipLaunchKernelGGL(hmme::me_prep_jobs_kernel, dim3((jobs + 255) / 256), dim3(256), 0, s, (MeJob*)ctx->d_frac_jobs, L.d_pred, L.first, L.count, L.pairs,
+                         L.width, L.height, L.search_range, 0, jobs, 0, counter, L.d_center);
+    }
+  }
+  rc = frac_lds_optin(ctx, L.wide, L.had, L.wp);
+  if (rc) return rc;
+  // prep: the job of a workgroup without a table (a table carries the predictors itself) and the order the jobs are dealt in
+  // (me_frac_deal).  A CTU range beyond 16 + 16 bits gets kNoPrep and with it the plain last-first order.  That is the order such a
+  // launch had from every caller: its picture has more than 65 535 CTUs, a packed count holds 65 535 at most, so me_frac_deal's test
+  // for a whole picture (count == the picture's CTUs) failed on the overflowed fields too.
+  const hmme::FracPrep prep = packable ? hmme::FracPrep{need_table ? nullptr : L.d_pred, (uint32_t)L.first | (uint32_t)L.count << 16,
+                                                        (uint32_t)L.width | (uint32_t)L.height << 16, L.search_range}
+                                       : kNoPrep;
+  hipLaunchKernelGGL(frac_kernel(L.wide, L.had, L.wp), dim3(grid), dim3(hmme::frac_threads(L.wide ? 2 : 1)), hmme::frac_lds_bytes(L.wide ? 2 : 1), s, L.curs,
+                     L.cur_pitch, L.refs, L.ref_pitch, need_table ? (const MeJob*)ctx->d_frac_jobs : (const MeJob*)nullptr, prep, jobs,
+                     walk ? counter : (uint32_t*)nullptr, ctx->d_frac_cover, L.d_int_mv, ctx->lambda_q16, L.bit_depth, L.fw, L.d_qmv, L.d_cost);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? HMME_OK : fail(ctx, HMME_ERR_DEVICE, "refinement launch -> %s", hipGetErrorString(e));
+}
 }  // namespace
 
 int hmme_refine_pairs_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, int n_pairs,
@@ -1484,46 +1585,13 @@ int hmme_refine_pairs_device(hmme_ctx* ctx, const hmme_plane* const* curs, const
   PairLaunch pl;
   int rc = pairs_begin(ctx, curs, refs, n_pairs, fp, s, &pl);
   if (rc || pl.count == 0) return rc;
-  const int jobs = pl.count * n_pairs;
-  rc = build_frac_cover(ctx);
-  if (rc == HMME_OK) {
-    size_t cap = ctx->frac_jobs_bytes;
-    rc = ensure(ctx, (uint8_t**)&ctx->d_frac_jobs, &cap, sizeof(MeJob) * (size_t)jobs + 64,   // + the launch's job counter behind the table
-                sizeof(MeJob) * (size_t)pl.count * hmme::kMaxRefs + 4096);
-    if (cap != ctx->frac_jobs_bytes) ctx->frac_jobs_tag.valid = false;
-    ctx->frac_jobs_bytes = cap;
-  }
-  if (rc == HMME_OK) {
-    uint32_t* counter = (uint32_t*)((uint8_t*)ctx->d_frac_jobs + ((sizeof(MeJob) * (size_t)jobs + 15) & ~(size_t)15));
-    const int had = use_hadamard ? 1 : 0, wide = curs[0]->bps == 2 ? 1 : 0;
-    const int grid = frac_grid(ctx, wide, had, jobs);
-    // one workgroup per job (the default) on the two-wave builds: every workgroup derives its job itself (FracPrep) -- no job table, no
-    // launch in front of this one (1080p: 0.095 -> 0.090 ms).  A table is read by the
-    // job-walking launch of HMME_FRAC_GRID: its prep kernel is also what resets the job counter
-    const hmme::FracPrep prep = {(const int16_t*)d_pred_q, (uint32_t)pl.first | (uint32_t)pl.count << 16, (uint32_t)curs[0]->width | (uint32_t)curs[0]->height << 16, fp->search_range};
-    static const bool table = std::getenv("HMME_FRAC_JOB_TABLE") != nullptr;   // A/B: the job table and its kernel as before
-    const bool walk = grid < jobs;
-    const bool packable = pl.count <= 0xffff && pl.first <= 0xffff;   // FracPrep packs the CTU range into 16 + 16 bits (a 16384 x 16384 picture has 65 536 CTUs)
-    const bool need_table = walk || table || !packable;
-    hmme_ctx::TableTag tag;
-    tag.valid = !d_pred_q && !walk;   // (the job-walking mode's prep kernel also resets the job counter: every launch)
-    tag.w = curs[0]->width; tag.h = curs[0]->height; tag.bit_depth = fp->bit_depth; tag.sr = fp->search_range; tag.first = pl.first; tag.count = pl.count;
-    tag.pairs = n_pairs; tag.buf = ctx->d_frac_jobs; tag.stream = (void*)s;
-    const bool have_table = need_table && tag.same(ctx->frac_jobs_tag);
-    if (need_table && !have_table) ctx->frac_jobs_tag = tag;
-    if (need_table && !have_table)
-      hipLaunchKernelGGL(hmme::me_prep_jobs_kernel, dim3((jobs + 255) / 256), dim3(256), 0, s, (MeJob*)ctx->d_frac_jobs, (const int16_t*)d_pred_q,
-                         pl.first, pl.count, n_pairs, curs[0]->width, curs[0]->height, fp->search_range, 0, jobs, 0, counter, (const int16_t*)nullptr);
-    rc = frac_lds_optin(ctx, wide, had, 0);
-    if (rc != HMME_OK) return pairs_end(ctx, curs, refs, n_pairs, s, rc);
-    hipLaunchKernelGGL(frac_kernel(wide, had, 0), dim3(grid), dim3(hmme::frac_threads(wide ? 2 : 1)), hmme::frac_lds_bytes(wide ? 2 : 1), s, pl.curs,
-                       curs[0]->pitch, pl.refs, refs[0]->pitch, need_table ? (const MeJob*)ctx->d_frac_jobs : (const MeJob*)nullptr, prep, jobs, walk ? counter : (uint32_t*)nullptr, ctx->d_frac_cover,
-                       (const int16_t*)d_int_mv, ctx->lambda_q16,
-                       fp->bit_depth, kNoWp, (int16_t*)d_out_qmv, (uint32_t*)d_out_cost);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "refinement launch -> %s", hipGetErrorString(e));
-  }
-  return pairs_end(ctx, curs, refs, n_pairs, s, rc);
+  RefineLaunch L;
+  refine_common(L, pl, curs[0], fp, use_hadamard, d_int_mv, d_out_qmv, d_out_cost);
+  L.curs = pl.curs; L.refs = pl.refs; L.cur_pitch = curs[0]->pitch; L.ref_pitch = refs[0]->pitch;
+  L.wide = curs[0]->bps == 2 ? 1 : 0;
+  L.d_pred = (const int16_t*)d_pred_q; L.pairs = n_pairs;
+  L.table = FracTable::kReuse;
+  return pairs_end(ctx, curs, refs, n_pairs, s, launch_refine(ctx, L, s));
 }
 
 int hmme_refine_frame_multi_device(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs,
@@ -1536,43 +1604,14 @@ int hmme_refine_frame_multi_device(hmme_ctx* ctx, const hmme_plane* cur, const h
   return hmme_refine_pairs_device(ctx, curs, refs, n_refs, fp, d_pred_q, d_int_mv, use_hadamard, d_out_qmv, d_out_cost, stream);
 }
 
-// host-facing refinement calls: device staging for the integer MVs, quarter-pel MVs and costs of `slots` (CTU, slot) entries
-static int ensure_refine_buffers(hmme_ctx* ctx, size_t slots) {
-  if (ctx->refine_cap >= slots) return HMME_OK;
-  hipFree(ctx->d_imv); hipFree(ctx->d_qmv); hipFree(ctx->d_fcost);
-  ctx->d_imv = nullptr; ctx->d_qmv = nullptr; ctx->d_fcost = nullptr; ctx->refine_cap = 0;
-  HIP_TRY(ctx, hipMalloc(&ctx->d_imv, sizeof(int16_t) * 2 * slots));
-  HIP_TRY(ctx, hipMalloc(&ctx->d_qmv, sizeof(int16_t) * 2 * slots));
-  HIP_TRY(ctx, hipMalloc(&ctx->d_fcost, sizeof(uint32_t) * slots));
-  ctx->refine_cap = slots;
-  return HMME_OK;
-}
-
 int hmme_refine_frame(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_frame_params* fp, const int16_t* pred_q,
                       const int16_t* int_mv, int use_hadamard, int16_t* out_qmv, uint32_t* out_cost) {
-  int first, count;
-  int rc = check_frame_args(ctx, cur, ref, fp, &first, &count);
-  if (rc) return rc;
-  if (!int_mv || !out_qmv || !out_cost) return fail(ctx, HMME_ERR_ARG, "null buffer");
-  if (count == 0) return HMME_OK;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const int n_ctu = hmme_num_ctus(cur->width, cur->height);
-  const size_t slots = (size_t)HMME_NUM_CTU_PARTS * n_ctu;
-  rc = ensure_refine_buffers(ctx, slots);
-  if (rc) return rc;
-  rc = ensure_frame_buffers(ctx, (size_t)n_ctu);   // the predictors travel in the search path's staging buffer
-  if (rc) return rc;
-  hipStream_t s = ctx->stream;
-  const size_t res = (size_t)HMME_NUM_CTU_PARTS * count;
-  if (pred_q) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_pred, pred_q, sizeof(int16_t) * 2 * (size_t)n_ctu, hipMemcpyHostToDevice, s));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_imv, int_mv, sizeof(int16_t) * 2 * res, hipMemcpyHostToDevice, s));
-  rc = hmme_refine_frame_multi_device(ctx, cur, &ref, 1, fp, pred_q ? ctx->d_pred : nullptr, ctx->d_imv, use_hadamard, ctx->d_qmv,
-                                      ctx->d_fcost, s);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(out_qmv, ctx->d_qmv, sizeof(int16_t) * 2 * res, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(out_cost, ctx->d_fcost, sizeof(uint32_t) * res, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  return HMME_OK;
+  int count;
+  const void* d_pred;
+  int rc = stage_in(ctx, cur, ref, fp, 1, pred_q, true, int_mv, out_qmv, out_cost, &count, &d_pred);
+  if (rc || count == 0) return rc;
+  rc = hmme_refine_frame_multi_device(ctx, cur, &ref, 1, fp, d_pred, ctx->d_imv, use_hadamard, ctx->d_qmv, ctx->d_fcost, ctx->stream);
+  return rc ? rc : stage_out(ctx, true, count, out_qmv, out_cost);
 }
 
 // ---- explicit weighted prediction on whole pictures -----------------------------------------------------------
@@ -1673,6 +1712,31 @@ int weight_plane(hmme_ctx* ctx, const hmme_plane* pl, const WpGeom& g, uint8_t* 
 int bias_blocks(hmme_ctx* ctx, const hmme_plane* pl, uint8_t* dst, int bias, hipStream_t s) {
   return weight_pass(ctx, pl->bps, pl->d_blocks, 0, dst, 0, (long)pl->n_ctu * 64 * 64, 1, 1, 0, 0, bias, s);
 }
+
+// The u16 copies the pairs of one launch take from one scratch buffer (d_wp[k]): pair r's copy goes into slot r, unless a pair before it
+// has made the same copy -- the same plane through the same arithmetic (what weight_pass gets) -- which then serves both.
+struct CopyKey { const hmme_plane* pl; int w0, round, shift, offset_bias; };
+struct CopyCache {
+  uint8_t* scratch; size_t slot_bytes;
+  bool blocks;   // copies of the CTU-blocked picture (bias_blocks) rather than of the padded plane (weight_plane: the copy's address is its origin)
+  CopyKey key[hmme::kMaxRefs]; const uint8_t* copy[hmme::kMaxRefs];   // per pair: what it asked for and got (null: nothing)
+  CopyCache(uint8_t* scratch_, size_t slot_bytes_, bool blocks_) : scratch(scratch_), slot_bytes(slot_bytes_), blocks(blocks_), key{}, copy{} {}
+};
+int cached_copy(hmme_ctx* ctx, CopyCache& cc, const WpGeom& g, int r, const CopyKey& k, hipStream_t s, const uint8_t** out) {
+  int q = 0, rc = HMME_OK;
+  const auto same = [&](const CopyKey& o) { return o.pl == k.pl && o.w0 == k.w0 && o.round == k.round && o.shift == k.shift && o.offset_bias == k.offset_bias; };
+  while (q < r && !(cc.copy[q] && same(cc.key[q]))) ++q;
+  if (q < r) {
+    cc.copy[r] = cc.copy[q];
+  } else {
+    uint8_t* dst = cc.scratch + cc.slot_bytes * r;
+    rc = cc.blocks ? bias_blocks(ctx, k.pl, dst, k.offset_bias, s) : weight_plane(ctx, k.pl, g, dst, k.w0, k.round, k.shift, k.offset_bias, s);
+    cc.copy[r] = cc.blocks ? dst : dst + g.origin;
+  }
+  cc.key[r] = k;
+  *out = cc.copy[r];
+  return rc;
+}
 }  // namespace
 
 int hmme_weight_check(int bit_depth, const hmme_weight* wp, int refine) {
@@ -1700,29 +1764,13 @@ int hmme_search_pairs_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, con
   rc = ensure(ctx, &ctx->d_wp[0], &ctx->wp_cap[0], g.plane_bytes * n_pairs);
   if (rc == HMME_OK) rc = ensure(ctx, &ctx->d_wp[1], &ctx->wp_cap[1], g.blk_bytes * n_pairs);
   RefSet wrefs = one_ref(nullptr), wcurs = one_ref(nullptr);
-  const uint8_t* cur_copy[hmme::kMaxRefs] = {};   // the u16 copy made for pair r's current picture (null: none made)
+  CopyCache wref(ctx->d_wp[0], g.plane_bytes, false), wcur(ctx->d_wp[1], g.blk_bytes, true);
   for (int r = 0; r < n_pairs && rc == HMME_OK; ++r) {
     const hmme_weight& w = wps[r];
-    int q = 0;   // a pair before this one with the same reference and weight has made this plane already
-    while (q < r && !(refs[q] == refs[r] && same_weight(wps[q], w))) ++q;
-    if (q < r) {
-      wrefs.base[r] = wrefs.base[q];
-    } else {
-      uint8_t* plane = ctx->d_wp[0] + g.plane_bytes * r;
-      rc = weight_plane(ctx, refs[r], g, plane, w.w0, w.round, w.shift, w.offset + info[r].bias, s);
-      wrefs.base[r] = plane + g.origin;
-    }
+    rc = cached_copy(ctx, wref, g, r, CopyKey{refs[r], w.w0, w.round, w.shift, w.offset + info[r].bias}, s, &wrefs.base[r]);
     if (rc != HMME_OK) break;
-    if (curs[r]->bps == 2 && info[r].bias == 0) { wcurs.base[r] = curs[r]->d_blocks; continue; }   // the plane's own blocks serve
-    for (q = 0; q < r && !(curs[q] == curs[r] && cur_copy[q] && info[q].bias == info[r].bias); ++q) {}
-    if (q < r) {
-      cur_copy[r] = cur_copy[q];
-    } else {
-      uint8_t* blocks = ctx->d_wp[1] + g.blk_bytes * r;
-      rc = bias_blocks(ctx, curs[r], blocks, info[r].bias, s);
-      cur_copy[r] = blocks;
-    }
-    wcurs.base[r] = cur_copy[r];
+    if (curs[r]->bps == 2 && info[r].bias == 0) wcurs.base[r] = curs[r]->d_blocks;   // the plane's own blocks serve
+    else rc = cached_copy(ctx, wcur, g, r, CopyKey{curs[r], 1, 0, 0, info[r].bias}, s, &wcurs.base[r]);
   }
   FramePlan plan;
   if (rc == HMME_OK) rc = prep_jobs(ctx, curs[0], &f, d_pred_q, pl.first, pl.count, n_pairs, s, &plan, true);
@@ -1737,23 +1785,12 @@ int hmme_search_frame_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* 
   bool identity = false;
   int rc = check_weights(ctx, "hmme_search_frame_w", fp, wp, 1, 0, &info, &identity);
   if (rc) return rc;
-  int first, count;
-  rc = check_frame_args(ctx, cur, ref, fp, &first, &count);
-  if (rc) return rc;
-  if (!out_mv || !out_sad) return fail(ctx, HMME_ERR_ARG, "null output buffer");
-  if (count == 0) return HMME_OK;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t n_ctu = (size_t)hmme_num_ctus(cur->width, cur->height);
-  rc = ensure_frame_buffers(ctx, n_ctu);
-  if (rc) return rc;
-  hipStream_t s = ctx->stream;
-  if (pred_q) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_pred, pred_q, sizeof(int16_t) * 2 * n_ctu, hipMemcpyHostToDevice, s));
-  rc = hmme_search_pairs_w_device(ctx, &cur, &ref, 1, fp, wp, pred_q ? ctx->d_pred : nullptr, ctx->d_mv, ctx->d_sad, s);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(out_mv, ctx->d_mv, sizeof(int16_t) * 2 * HMME_NUM_CTU_PARTS * (size_t)count, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(out_sad, ctx->d_sad, sizeof(uint32_t) * HMME_NUM_CTU_PARTS * (size_t)count, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  return HMME_OK;
+  int count;
+  const void* d_pred;
+  rc = stage_in(ctx, cur, ref, fp, 1, pred_q, false, nullptr, out_mv, out_sad, &count, &d_pred);
+  if (rc || count == 0) return rc;
+  rc = hmme_search_pairs_w_device(ctx, &cur, &ref, 1, fp, wp, d_pred, ctx->d_mv, ctx->d_sad, ctx->stream);
+  return rc ? rc : stage_out(ctx, false, count, out_mv, out_sad);
 }
 
 int hmme_refine_pairs_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, int n_pairs,
@@ -1770,24 +1807,13 @@ int hmme_refine_pairs_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, con
   PairLaunch pl;
   rc = pairs_begin(ctx, curs, refs, n_pairs, fp, s, &pl);
   if (rc || pl.count == 0) return rc;
-  const int jobs = pl.count * n_pairs, had = use_hadamard ? 1 : 0, src_wide = curs[0]->bps == 2 ? 1 : 0;
-  const int n_ctu = curs[0]->n_ctu;
+  const int src_wide = curs[0]->bps == 2 ? 1 : 0, n_ctu = curs[0]->n_ctu;
   const WpGeom g(refs[0]);
-  rc = build_frac_cover(ctx);
-  if (rc == HMME_OK) {
-    size_t cap = ctx->frac_jobs_bytes;
-    rc = ensure(ctx, (uint8_t**)&ctx->d_frac_jobs, &cap, sizeof(MeJob) * (size_t)jobs + 64, sizeof(MeJob) * (size_t)pl.count * hmme::kMaxRefs + 4096);
-    ctx->frac_jobs_bytes = cap;
-    ctx->frac_jobs_tag.valid = false;   // the runs below write their own tables where they need one
-  }
   bool need_cur = false;
   for (int r = 0; r < n_pairs; ++r) need_cur = need_cur || (!info[r].identity && (!src_wide || info[r].bias));
-  if (rc == HMME_OK && !src_wide) rc = ensure(ctx, &ctx->d_wp[2], &ctx->wp_cap[2], g.plane_bytes * n_pairs);
+  if (!src_wide) rc = ensure(ctx, &ctx->d_wp[2], &ctx->wp_cap[2], g.plane_bytes * n_pairs);
   if (rc == HMME_OK && need_cur) rc = ensure(ctx, &ctx->d_wp[3], &ctx->wp_cap[3], g.plane_bytes * n_pairs);
-  static const bool table = std::getenv("HMME_FRAC_JOB_TABLE") != nullptr;
-  const bool packable = pl.count <= 0xffff && pl.first <= 0xffff;
-  const uint8_t* raw_copy[hmme::kMaxRefs] = {};   // pair r's reference widened to u16 / its current picture widened and biased (null: none made)
-  const uint8_t* cur_copy[hmme::kMaxRefs] = {};
+  CopyCache raw(ctx->d_wp[2], g.plane_bytes, false), wcur(ctx->d_wp[3], g.plane_bytes, false);   // references widened to u16 / current pictures widened and biased
   // one launch per run of pairs with equal weights: the weight is one kernel argument (FracWp)
   for (int a = 0, b; a < n_pairs && rc == HMME_OK; a = b) {
     for (b = a + 1; b < n_pairs && same_weight(wps[b], wps[a]); ++b) {}
@@ -1798,52 +1824,23 @@ int hmme_refine_pairs_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, con
     for (int r = a; r < b && rc == HMME_OK; ++r) {
       if (ident) { c.base[r - a] = pl.curs.base[r]; rf.base[r - a] = pl.refs.base[r]; continue; }
       // the RAW reference is interpolated; the current samples carry the bias (FracWp::org_sub takes it off again, with the offset)
-      if (src_wide) {
-        rf.base[r - a] = pl.refs.base[r];
-      } else {
-        int q = 0;
-        while (q < r && !(refs[q] == refs[r] && raw_copy[q])) ++q;
-        if (q < r) raw_copy[r] = raw_copy[q];
-        else {
-          uint8_t* plane = ctx->d_wp[2] + g.plane_bytes * r;
-          rc = weight_plane(ctx, refs[r], g, plane, 1, 0, 0, 0, s);
-          raw_copy[r] = plane + g.origin;
-        }
-        rf.base[r - a] = raw_copy[r];
-        if (rc != HMME_OK) break;
-      }
-      if (src_wide && info[r].bias == 0) { c.base[r - a] = pl.curs.base[r]; continue; }
-      int q = 0;
-      while (q < r && !(curs[q] == curs[r] && cur_copy[q] && info[q].bias == info[r].bias)) ++q;
-      if (q < r) cur_copy[r] = cur_copy[q];
-      else {
-        uint8_t* plane = ctx->d_wp[3] + g.plane_bytes * r;
-        rc = weight_plane(ctx, curs[r], g, plane, 1, 0, 0, info[r].bias, s);
-        cur_copy[r] = plane + g.origin;
-      }
-      c.base[r - a] = cur_copy[r];
+      if (src_wide) rf.base[r - a] = pl.refs.base[r];
+      else rc = cached_copy(ctx, raw, g, r, CopyKey{refs[r], 1, 0, 0, 0}, s, &rf.base[r - a]);
+      if (rc != HMME_OK) break;
+      if (src_wide && info[r].bias == 0) c.base[r - a] = pl.curs.base[r];
+      else rc = cached_copy(ctx, wcur, g, r, CopyKey{curs[r], 1, 0, 0, info[r].bias}, s, &c.base[r - a]);
     }
     if (rc != HMME_OK) break;
-    const int run_jobs = (b - a) * pl.count;
-    const int16_t* pred = d_pred_q ? (const int16_t*)d_pred_q + (size_t)a * n_ctu * 2 : nullptr;
+    // the run's own table and counter, where it reads one, in the same buffer as the run before (on one stream: behind its kernel)
     const size_t res0 = (size_t)a * pl.count * HMME_NUM_CTU_PARTS;
-    const int grid = frac_grid(ctx, wide, had, run_jobs);
-    const bool walk = grid < run_jobs, need_table = walk || table || !packable;
-    uint32_t* counter = (uint32_t*)((uint8_t*)ctx->d_frac_jobs + ((sizeof(MeJob) * (size_t)run_jobs + 15) & ~(size_t)15));
-    if (need_table)
-      hipLaunchKernelGGL(hmme::me_prep_jobs_kernel, dim3((run_jobs + 255) / 256), dim3(256), 0, s, (MeJob*)ctx->d_frac_jobs, pred, pl.first, pl.count,
-                         b - a, curs[0]->width, curs[0]->height, fp->search_range, 0, run_jobs, 0, counter, (const int16_t*)nullptr);
-    rc = frac_lds_optin(ctx, wide, had, ident ? 0 : 1);
-    if (rc != HMME_OK) break;
-    const hmme::FracPrep prep = {pred, (uint32_t)pl.first | (uint32_t)pl.count << 16, (uint32_t)curs[0]->width | (uint32_t)curs[0]->height << 16, fp->search_range};
-    const hmme::FracWp fw = ident ? kNoWp : hmme::FracWp{std::ldexp((float)w.w0, -w.shift), std::ldexp((float)w.round, -w.shift), (float)(info[a].bias + w.offset)};
-    const int pitch = ident ? curs[0]->pitch : g.pitch;   // (a u16 plane's own pitch is g.pitch)
-    hipLaunchKernelGGL(frac_kernel(wide, had, ident ? 0 : 1), dim3(grid), dim3(hmme::frac_threads(wide ? 2 : 1)), hmme::frac_lds_bytes(wide ? 2 : 1), s, c, pitch,
-                       rf, ident ? refs[0]->pitch : g.pitch, need_table ? (const MeJob*)ctx->d_frac_jobs : (const MeJob*)nullptr, prep, run_jobs,
-                       walk ? counter : (uint32_t*)nullptr, ctx->d_frac_cover, (const int16_t*)d_int_mv + 2 * res0, ctx->lambda_q16, fp->bit_depth, fw,
-                       (int16_t*)d_out_qmv + 2 * res0, (uint32_t*)d_out_cost + res0);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "weighted refinement launch -> %s", hipGetErrorString(e));
+    RefineLaunch L;
+    refine_common(L, pl, curs[0], fp, use_hadamard, (const int16_t*)d_int_mv + 2 * res0, (int16_t*)d_out_qmv + 2 * res0, (uint32_t*)d_out_cost + res0);
+    L.curs = c; L.refs = rf;
+    L.cur_pitch = ident ? curs[0]->pitch : g.pitch; L.ref_pitch = ident ? refs[0]->pitch : g.pitch;   // (a u16 plane's own pitch is g.pitch)
+    L.wide = wide; L.wp = ident ? 0 : 1;
+    if (!ident) L.fw = hmme::FracWp{std::ldexp((float)w.w0, -w.shift), std::ldexp((float)w.round, -w.shift), (float)(info[a].bias + w.offset)};
+    L.d_pred = d_pred_q ? (const int16_t*)d_pred_q + (size_t)a * n_ctu * 2 : nullptr; L.pairs = b - a;
+    rc = launch_refine(ctx, L, s);
   }
   return pairs_end(ctx, curs, refs, n_pairs, s, rc);
 }
@@ -1855,26 +1852,12 @@ int hmme_refine_frame_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* 
   bool identity = false;
   int rc = check_weights(ctx, "hmme_refine_frame_w", fp, wp, 1, 1, &info, &identity);
   if (rc) return rc;
-  int first, count;
-  rc = check_frame_args(ctx, cur, ref, fp, &first, &count);
-  if (rc) return rc;
-  if (!int_mv || !out_qmv || !out_cost) return fail(ctx, HMME_ERR_ARG, "null buffer");
-  if (count == 0) return HMME_OK;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const int n_ctu = hmme_num_ctus(cur->width, cur->height);
-  rc = ensure_refine_buffers(ctx, (size_t)HMME_NUM_CTU_PARTS * n_ctu);
-  if (rc == HMME_OK) rc = ensure_frame_buffers(ctx, (size_t)n_ctu);
-  if (rc) return rc;
-  hipStream_t s = ctx->stream;
-  const size_t res = (size_t)HMME_NUM_CTU_PARTS * count;
-  if (pred_q) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_pred, pred_q, sizeof(int16_t) * 2 * (size_t)n_ctu, hipMemcpyHostToDevice, s));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_imv, int_mv, sizeof(int16_t) * 2 * res, hipMemcpyHostToDevice, s));
-  rc = hmme_refine_pairs_w_device(ctx, &cur, &ref, 1, fp, wp, pred_q ? ctx->d_pred : nullptr, ctx->d_imv, use_hadamard, ctx->d_qmv, ctx->d_fcost, s);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(out_qmv, ctx->d_qmv, sizeof(int16_t) * 2 * res, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(out_cost, ctx->d_fcost, sizeof(uint32_t) * res, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  return HMME_OK;
+  int count;
+  const void* d_pred;
+  rc = stage_in(ctx, cur, ref, fp, 1, pred_q, true, int_mv, out_qmv, out_cost, &count, &d_pred);
+  if (rc || count == 0) return rc;
+  rc = hmme_refine_pairs_w_device(ctx, &cur, &ref, 1, fp, wp, d_pred, ctx->d_imv, use_hadamard, ctx->d_qmv, ctx->d_fcost, ctx->stream);
+  return rc ? rc : stage_out(ctx, true, count, out_qmv, out_cost);
 }
 
 // ---- bi-prediction on whole pictures and picture pairs ----------------------------------------------------------
@@ -2012,16 +1995,9 @@ int hmme_search_pairs_bi_device(hmme_ctx* ctx, const hmme_plane* const* curs, co
   if (rc == HMME_OK) rc = ensure(ctx, &ctx->d_wp[1], &ctx->wp_cap[1], g.blk_bytes * n_pairs);
   RefSet wrefs = one_ref(nullptr), wcurs = one_ref(nullptr);
   const size_t field = (size_t)n_ctu * mv_per_ctu * 2;
+  CopyCache wref(ctx->d_wp[0], g.plane_bytes, false);   // the references with the origin's bias
   for (int r = 0; r < n_pairs && rc == HMME_OK; ++r) {
-    int q = 0;   // a pair before this one with the same reference has made its biased copy already
-    while (q < r && refs[q] != refs[r]) ++q;
-    if (q < r) {
-      wrefs.base[r] = wrefs.base[q];
-    } else {
-      uint8_t* plane = ctx->d_wp[0] + g.plane_bytes * r;
-      rc = weight_plane(ctx, refs[r], g, plane, 1, 0, 0, bias, s);
-      wrefs.base[r] = plane + g.origin;
-    }
+    rc = cached_copy(ctx, wref, g, r, CopyKey{refs[r], 1, 0, 0, bias}, s, &wrefs.base[r]);
     if (rc != HMME_OK) break;
     uint8_t* blocks = ctx->d_wp[1] + g.blk_bytes * r;   // the origin: one per pair (it depends on the pair's field)
     rc = launch_predict(ctx, others[r], (const int16_t*)d_other_mv + field * r, mv_per_ctu, pl.first, pl.count, true, curs[r]->d_blocks, bias, blocks,
@@ -2047,34 +2023,18 @@ int hmme_refine_pairs_bi_device(hmme_ctx* ctx, const hmme_plane* const* curs, co
   rc = pairs_begin(ctx, curs, refs, n_pairs, fp, s, &pl);
   if (rc || pl.count == 0) return rc;
   for (int r = 0; r < n_pairs && rc == HMME_OK; ++r) rc = plane_wait(ctx, others[r], s);
-  const int jobs = pl.count * n_pairs, had = use_hadamard ? 1 : 0, src_wide = curs[0]->bps == 2 ? 1 : 0;
-  const int bias = (1 << fp->bit_depth) - 1, n_ctu = curs[0]->n_ctu;
+  const int src_wide = curs[0]->bps == 2 ? 1 : 0, bias = (1 << fp->bit_depth) - 1, n_ctu = curs[0]->n_ctu;
   const WpGeom g(refs[0]);
-  if (rc == HMME_OK) rc = build_frac_cover(ctx);
-  if (rc == HMME_OK) {
-    size_t cap = ctx->frac_jobs_bytes;
-    rc = ensure(ctx, (uint8_t**)&ctx->d_frac_jobs, &cap, sizeof(MeJob) * (size_t)jobs + 64, sizeof(MeJob) * (size_t)pl.count * hmme::kMaxRefs + 4096);
-    ctx->frac_jobs_bytes = cap;
-    ctx->frac_jobs_tag.valid = false;   // this launch writes its own table
-  }
   if (rc == HMME_OK && !src_wide) rc = ensure(ctx, &ctx->d_wp[2], &ctx->wp_cap[2], g.plane_bytes * n_pairs);
   if (rc == HMME_OK) rc = ensure(ctx, &ctx->d_wp[3], &ctx->wp_cap[3], g.plane_bytes * n_pairs);
   RefSet c = one_ref(nullptr), rf = one_ref(nullptr);
   const size_t field = (size_t)n_ctu * mv_per_ctu * 2;
+  CopyCache raw(ctx->d_wp[2], g.plane_bytes, false);
   for (int r = 0; r < n_pairs && rc == HMME_OK; ++r) {
-    if (src_wide) {
-      rf.base[r] = pl.refs.base[r];   // the RAW reference is interpolated: a u16 plane serves as it is
-    } else {
-      int q = 0;
-      while (q < r && refs[q] != refs[r]) ++q;
-      if (q < r) rf.base[r] = rf.base[q];
-      else {
-        uint8_t* plane = ctx->d_wp[2] + g.plane_bytes * r;
-        rc = weight_plane(ctx, refs[r], g, plane, 1, 0, 0, 0, s);
-        rf.base[r] = plane + g.origin;
-      }
-      if (rc != HMME_OK) break;
-    }
+    // the RAW reference is interpolated: a u16 plane serves as it is, an 8-bit one is widened
+    if (src_wide) rf.base[r] = pl.refs.base[r];
+    else rc = cached_copy(ctx, raw, g, r, CopyKey{refs[r], 1, 0, 0, 0}, s, &rf.base[r]);
+    if (rc != HMME_OK) break;
     // the origin in a padded plane's layout: only the CTU blocks are written and read (a partial CTU's block ends 63 samples into the
     // 128 / 80-sample margins at most)
     uint8_t* plane = ctx->d_wp[3] + g.plane_bytes * r + g.origin;
@@ -2083,42 +2043,28 @@ int hmme_refine_pairs_bi_device(hmme_ctx* ctx, const hmme_plane* const* curs, co
     c.base[r] = plane;
   }
   if (rc == HMME_OK) {
-    // the job table is always written: it carries the window centres (FracPrep derives windows from predictors only)
-    const int grid = frac_grid(ctx, 1, had, jobs);
-    const bool walk = grid < jobs;
-    uint32_t* counter = (uint32_t*)((uint8_t*)ctx->d_frac_jobs + ((sizeof(MeJob) * (size_t)jobs + 15) & ~(size_t)15));
-    hipLaunchKernelGGL(hmme::me_prep_jobs_kernel, dim3((jobs + 255) / 256), dim3(256), 0, s, (MeJob*)ctx->d_frac_jobs, (const int16_t*)d_pred_q, pl.first,
-                       pl.count, n_pairs, curs[0]->width, curs[0]->height, fp->search_range, 0, jobs, 0, counter, (const int16_t*)d_center_q);
-    rc = frac_lds_optin(ctx, 1, had, 1);
-    if (rc == HMME_OK) {
-      // (prep: the order the jobs are dealt in, me_frac_deal; CTU ranges beyond 16 bits keep the plain order)
-      const bool packable = pl.count <= 0xffff && pl.first <= 0xffff;
-      const hmme::FracPrep prep = packable ? hmme::FracPrep{nullptr, (uint32_t)pl.first | (uint32_t)pl.count << 16, (uint32_t)curs[0]->width | (uint32_t)curs[0]->height << 16, fp->search_range} : kNoPrep;
-      const hmme::FracWp fw = {1.f, 0.f, (float)bias};
-      hipLaunchKernelGGL(frac_kernel(1, had, 1), dim3(grid), dim3(hmme::frac_threads(2)), hmme::frac_lds_bytes(2), s, c, g.pitch, rf, g.pitch,
-                         (const MeJob*)ctx->d_frac_jobs, prep, jobs, walk ? counter : (uint32_t*)nullptr, ctx->d_frac_cover, (const int16_t*)d_int_mv,
-                         ctx->lambda_q16, fp->bit_depth, fw, (int16_t*)d_out_qmv, (uint32_t*)d_out_cost);
-      const hipError_t e = hipGetLastError();
-      if (e != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "bi-prediction refinement launch -> %s", hipGetErrorString(e));
-    }
+    RefineLaunch L;
+    refine_common(L, pl, curs[0], fp, use_hadamard, d_int_mv, d_out_qmv, d_out_cost);
+    L.curs = c; L.refs = rf; L.cur_pitch = g.pitch; L.ref_pitch = g.pitch;
+    L.wide = 1; L.wp = 1; L.fw = hmme::FracWp{1.f, 0.f, (float)bias};   // the identity weight; org_sub takes the origin's bias off
+    L.d_pred = (const int16_t*)d_pred_q; L.d_center = (const int16_t*)d_center_q; L.pairs = n_pairs;
+    L.table = FracTable::kAlways;   // the table carries the window centres (FracPrep derives windows from predictors only)
+    rc = launch_refine(ctx, L, s);
   }
   return pairs_end(ctx, curs, refs, n_pairs, s, rc, others);
 }
 
 namespace {
-// host-facing bi calls: the motion field and the centres go up into d_bi[0], the predictors into d_pred
-int bi_stage(hmme_ctx* ctx, const hmme_plane* cur, const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q, const int16_t* pred_q,
-             const void** d_field, const void** d_center, const void** d_pred, hipStream_t s) {
+// host-facing bi calls: the motion field and the centres go up into d_bi[0] (the predictors into d_pred: stage_in)
+int bi_stage(hmme_ctx* ctx, const hmme_plane* cur, const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q, const void** d_field,
+             const void** d_center) {
   const size_t n_ctu = (size_t)cur->n_ctu, field_bytes = sizeof(int16_t) * 2 * n_ctu * mv_per_ctu, pq_bytes = sizeof(int16_t) * 2 * n_ctu;
   int rc = ensure(ctx, &ctx->d_bi[0], &ctx->bi_cap[0], field_bytes + pq_bytes);
-  if (rc == HMME_OK) rc = ensure_frame_buffers(ctx, n_ctu);
   if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_bi[0], other_mv, field_bytes, hipMemcpyHostToDevice, s));
-  if (center_q) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_bi[0] + field_bytes, center_q, pq_bytes, hipMemcpyHostToDevice, s));
-  if (pred_q) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_pred, pred_q, pq_bytes, hipMemcpyHostToDevice, s));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_bi[0], other_mv, field_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (center_q) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_bi[0] + field_bytes, center_q, pq_bytes, hipMemcpyHostToDevice, ctx->stream));
   *d_field = ctx->d_bi[0];
   *d_center = center_q ? ctx->d_bi[0] + field_bytes : nullptr;
-  *d_pred = pred_q ? ctx->d_pred : nullptr;
   return HMME_OK;
 }
 }  // namespace
@@ -2129,21 +2075,13 @@ int hmme_search_frame_bi(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane*
   int rc = bi_check(ctx, "hmme_search_frame_bi", fp, 0);
   if (rc == HMME_OK) rc = bi_args(ctx, "hmme_search_frame_bi", &cur, &ref, &other, 1, fp, other_mv, mv_per_ctu);
   if (rc) return rc;
-  int first, count;
-  rc = check_frame_args(ctx, cur, ref, fp, &first, &count);
-  if (rc) return rc;
-  if (!out_mv || !out_sad) return fail(ctx, HMME_ERR_ARG, "null output buffer");
-  if (count == 0) return HMME_OK;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  const void *d_field, *d_center, *d_pred;
-  rc = bi_stage(ctx, cur, other_mv, mv_per_ctu, center_q, pred_q, &d_field, &d_center, &d_pred, s);
-  if (rc == HMME_OK) rc = hmme_search_pairs_bi_device(ctx, &cur, &ref, &other, 1, fp, d_field, mv_per_ctu, d_center, d_pred, ctx->d_mv, ctx->d_sad, s);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(out_mv, ctx->d_mv, sizeof(int16_t) * 2 * HMME_NUM_CTU_PARTS * (size_t)count, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(out_sad, ctx->d_sad, sizeof(uint32_t) * HMME_NUM_CTU_PARTS * (size_t)count, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  return HMME_OK;
+  int count;
+  const void *d_pred, *d_field, *d_center;
+  rc = stage_in(ctx, cur, ref, fp, 1, pred_q, false, nullptr, out_mv, out_sad, &count, &d_pred);
+  if (rc || count == 0) return rc;
+  rc = bi_stage(ctx, cur, other_mv, mv_per_ctu, center_q, &d_field, &d_center);
+  if (rc == HMME_OK) rc = hmme_search_pairs_bi_device(ctx, &cur, &ref, &other, 1, fp, d_field, mv_per_ctu, d_center, d_pred, ctx->d_mv, ctx->d_sad, ctx->stream);
+  return rc ? rc : stage_out(ctx, false, count, out_mv, out_sad);
 }
 
 int hmme_refine_frame_bi(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
@@ -2153,26 +2091,14 @@ int hmme_refine_frame_bi(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane*
   int rc = bi_check(ctx, "hmme_refine_frame_bi", fp, 1);
   if (rc == HMME_OK) rc = bi_args(ctx, "hmme_refine_frame_bi", &cur, &ref, &other, 1, fp, other_mv, mv_per_ctu);
   if (rc) return rc;
-  int first, count;
-  rc = check_frame_args(ctx, cur, ref, fp, &first, &count);
-  if (rc) return rc;
-  if (!int_mv || !out_qmv || !out_cost) return fail(ctx, HMME_ERR_ARG, "null buffer");
-  if (count == 0) return HMME_OK;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  rc = ensure_refine_buffers(ctx, (size_t)HMME_NUM_CTU_PARTS * cur->n_ctu);
-  if (rc) return rc;
-  hipStream_t s = ctx->stream;
-  const void *d_field, *d_center, *d_pred;
-  rc = bi_stage(ctx, cur, other_mv, mv_per_ctu, center_q, pred_q, &d_field, &d_center, &d_pred, s);
-  if (rc) return rc;
-  const size_t res = (size_t)HMME_NUM_CTU_PARTS * count;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_imv, int_mv, sizeof(int16_t) * 2 * res, hipMemcpyHostToDevice, s));
-  rc = hmme_refine_pairs_bi_device(ctx, &cur, &ref, &other, 1, fp, d_field, mv_per_ctu, d_center, d_pred, ctx->d_imv, use_hadamard, ctx->d_qmv, ctx->d_fcost, s);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(out_qmv, ctx->d_qmv, sizeof(int16_t) * 2 * res, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(out_cost, ctx->d_fcost, sizeof(uint32_t) * res, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  return HMME_OK;
+  int count;
+  const void *d_pred, *d_field, *d_center;
+  rc = stage_in(ctx, cur, ref, fp, 1, pred_q, true, int_mv, out_qmv, out_cost, &count, &d_pred);
+  if (rc || count == 0) return rc;
+  rc = bi_stage(ctx, cur, other_mv, mv_per_ctu, center_q, &d_field, &d_center);
+  if (rc == HMME_OK)
+    rc = hmme_refine_pairs_bi_device(ctx, &cur, &ref, &other, 1, fp, d_field, mv_per_ctu, d_center, d_pred, ctx->d_imv, use_hadamard, ctx->d_qmv, ctx->d_fcost, ctx->stream);
+  return rc ? rc : stage_out(ctx, true, count, out_qmv, out_cost);
 }
 
 // ---- partition decision and motion field from the 593-slot tables ---------------------------------------------------------------------
@@ -2465,6 +2391,34 @@ int hmme_wp_estimate(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* con
   return HMME_OK;
 }
 
+namespace {
+// hmme_test_time_*: `reps` runs of `first` and then, where given, `reps` runs of `second` on `s` between events -> the milliseconds of one
+// run of each.  A run that fails ends the measurement with its code; what was enqueued has finished when this returns
+int time_reps(hmme_ctx* ctx, hipStream_t s, int reps, const char* what, const std::function<int()>& first, float* first_ms,
+              const std::function<int()>& second = nullptr, float* second_ms = nullptr) {
+  const std::function<int()>* run[2] = {&first, &second};
+  float* out[2] = {first_ms, second_ms};
+  const int groups = second ? 2 : 1;
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  float ms[2] = {0.f, 0.f};
+  int rc = HMME_OK;
+  hipError_t e = hipSuccess;
+  for (int i = 0; i <= groups && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
+  if (e == hipSuccess) e = hipEventRecord(ev[0], s);
+  for (int g = 0; g < groups && e == hipSuccess; ++g) {
+    for (int i = 0; i < reps && rc == HMME_OK; ++i) rc = (*run[g])();
+    e = hipEventRecord(ev[g + 1], s);
+  }
+  if (e == hipSuccess) e = hipEventSynchronize(ev[groups]);
+  for (int g = 0; g < groups && e == hipSuccess; ++g) e = hipEventElapsedTime(&ms[g], ev[g], ev[g + 1]);
+  for (hipEvent_t v : ev)
+    if (v) hipEventDestroy(v);
+  if (rc == HMME_OK && e != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "timing %s: %s", what, hipGetErrorString(e));
+  for (int g = 0; g < groups && rc == HMME_OK; ++g) *out[g] = ms[g] / reps;
+  return rc;
+}
+}  // namespace
+
 int hmme_test_time_wp_estimate_passes(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_weight* wp, void* stream,
                                       int reps, float* stats_ms, float* sad_ms) {
   if (!ctx) return HMME_ERR_ARG;
@@ -2477,23 +2431,11 @@ int hmme_test_time_wp_estimate_passes(hmme_ctx* ctx, const hmme_plane* cur, cons
   if (rc) return rc;
   hmme::MeWpSad a = {};
   for (int r = 0; r < n_refs; ++r) { a.weight[r] = wp->w0; a.offset[r] = wp->offset * (1 << wp->shift); a.log2_denom[r] = wp->shift; }
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  hipError_t e = hipMemsetAsync(ctx->d_wpest, 0, sizeof(unsigned long long) * kWpStatWords, s);
-  for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
-  float ms0 = 0.f, ms1 = 0.f;
-  if (e == hipSuccess) {
-    e = hipEventRecord(ev[0], s);
-    for (int i = 0; i < reps && rc == HMME_OK; ++i) rc = launch_stats(ctx, cur, ctx->d_wpest, s);
-    if (e == hipSuccess) e = hipEventRecord(ev[1], s);
-    for (int i = 0; i < reps && rc == HMME_OK; ++i) rc = launch_wp_sad(ctx, cur, refs, n_refs, a, ctx->d_wpest + kWpStatSad, s);
-    if (e == hipSuccess) e = hipEventRecord(ev[2], s);
-    if (e == hipSuccess) e = hipEventSynchronize(ev[2]);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms0, ev[0], ev[1]);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms1, ev[1], ev[2]);
-  }
-  for (int i = 0; i < 3; ++i) if (ev[i]) hipEventDestroy(ev[i]);
-  if (rc == HMME_OK && e != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "timing the estimator's passes: %s", hipGetErrorString(e));
-  if (rc == HMME_OK) { *stats_ms = ms0 / reps; *sad_ms = ms1 / reps; }
+  const hipError_t e = hipMemsetAsync(ctx->d_wpest, 0, sizeof(unsigned long long) * kWpStatWords, s);
+  if (e != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "hmme_test_time_wp_estimate_passes: %s", hipGetErrorString(e));
+  if (rc == HMME_OK)
+    rc = time_reps(ctx, s, reps, "the estimator's passes", [&] { return launch_stats(ctx, cur, ctx->d_wpest, s); }, stats_ms,
+                   [&] { return launch_wp_sad(ctx, cur, refs, n_refs, a, ctx->d_wpest + kWpStatSad, s); }, sad_ms);
   return planes_read_end(ctx, planes, 1 + n_refs, s, rc);
 }
 
@@ -2510,22 +2452,11 @@ int hmme_test_time_bipred_origin(hmme_ctx* ctx, const hmme_plane* cur, const hmm
   if (rc) return rc;
   const WpGeom g(cur);
   rc = ensure(ctx, &ctx->d_wp[1], &ctx->wp_cap[1], g.blk_bytes);
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipError_t e = hipSuccess;
-  float ms = 0.f;
-  if (rc == HMME_OK && (e = hipEventCreate(&e0)) == hipSuccess && (e = hipEventCreate(&e1)) == hipSuccess) {
-    e = hipEventRecord(e0, s);
-    for (int i = 0; i < reps && rc == HMME_OK; ++i)
-      rc = launch_predict(ctx, other, (const int16_t*)d_other_mv, mv_per_ctu, 0, cur->n_ctu, true, cur->d_blocks, (1 << cur->bit_depth) - 1, ctx->d_wp[1],
-                          hmme::kBlkBytes16, (long)cur->ctus_x * hmme::kBlkBytes16, 128, s);
-    if (e == hipSuccess) e = hipEventRecord(e1, s);
-    if (e == hipSuccess) e = hipEventSynchronize(e1);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-  }
-  if (e0) hipEventDestroy(e0);
-  if (e1) hipEventDestroy(e1);
-  if (rc == HMME_OK && e != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "timing the origin pass: %s", hipGetErrorString(e));
-  if (rc == HMME_OK) *avg_ms = ms / reps;
+  if (rc == HMME_OK)
+    rc = time_reps(ctx, s, reps, "the origin pass", [&] {
+      return launch_predict(ctx, other, (const int16_t*)d_other_mv, mv_per_ctu, 0, cur->n_ctu, true, cur->d_blocks, (1 << cur->bit_depth) - 1, ctx->d_wp[1],
+                            hmme::kBlkBytes16, (long)cur->ctus_x * hmme::kBlkBytes16, 128, s);
+    }, avg_ms);
   return pairs_end(ctx, &cur, &other, 1, s, rc);
 }
 
@@ -2545,23 +2476,9 @@ int hmme_test_time_weight_passes(hmme_ctx* ctx, const hmme_plane* cur, const hmm
   const WpGeom g(ref);
   rc = ensure(ctx, &ctx->d_wp[0], &ctx->wp_cap[0], g.plane_bytes);
   if (rc == HMME_OK) rc = ensure(ctx, &ctx->d_wp[1], &ctx->wp_cap[1], g.blk_bytes);
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < 3 && rc == HMME_OK && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
-  float ms0 = 0.f, ms1 = 0.f;
-  if (rc == HMME_OK && e == hipSuccess) {
-    e = hipEventRecord(ev[0], s);
-    for (int i = 0; i < reps && rc == HMME_OK; ++i) rc = weight_plane(ctx, ref, g, ctx->d_wp[0], wp->w0, wp->round, wp->shift, wp->offset + info.bias, s);
-    if (e == hipSuccess) e = hipEventRecord(ev[1], s);
-    for (int i = 0; i < reps && rc == HMME_OK; ++i) rc = bias_blocks(ctx, cur, ctx->d_wp[1], info.bias, s);
-    if (e == hipSuccess) e = hipEventRecord(ev[2], s);
-    if (e == hipSuccess) e = hipEventSynchronize(ev[2]);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms0, ev[0], ev[1]);
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms1, ev[1], ev[2]);
-  }
-  for (int i = 0; i < 3; ++i) if (ev[i]) hipEventDestroy(ev[i]);
-  if (rc == HMME_OK && e != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "timing the weighting passes: %s", hipGetErrorString(e));
-  if (rc == HMME_OK) { *ref_ms = ms0 / reps; *cur_ms = ms1 / reps; }
+  if (rc == HMME_OK)
+    rc = time_reps(ctx, s, reps, "the weighting passes", [&] { return weight_plane(ctx, ref, g, ctx->d_wp[0], wp->w0, wp->round, wp->shift, wp->offset + info.bias, s); },
+                   ref_ms, [&] { return bias_blocks(ctx, cur, ctx->d_wp[1], info.bias, s); }, cur_ms);
   return pairs_end(ctx, &cur, &ref, 1, s, rc);
 }
 
@@ -2578,21 +2495,10 @@ int hmme_test_time_search_kernel(hmme_ctx* ctx, const hmme_plane* cur, const hmm
   // job table once (it is not part of the timed kernel), then `reps` launches of the search kernel(s) alone
   FramePlan plan;
   rc = prep_jobs(ctx, cur, fp, d_pred_q, first, count, 1, s, &plan);
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipError_t e = hipSuccess;
-  float ms = 0.f;
-  if (rc == HMME_OK && (e = hipEventCreate(&e0)) == hipSuccess && (e = hipEventCreate(&e1)) == hipSuccess) {
-    e = hipEventRecord(e0, s);
-    for (int i = 0; i < reps && rc == HMME_OK && e == hipSuccess; ++i)
-      rc = run_search(ctx, pl.cur_blocks, cur->ctus_x, pl.refs, ref->pitch, fp, plan, (int16_t*)d_out_mv, (uint32_t*)d_out_sad, s);
-    if (rc == HMME_OK && e == hipSuccess) e = hipEventRecord(e1, s);
-    if (rc == HMME_OK && e == hipSuccess) e = hipEventSynchronize(e1);
-    if (rc == HMME_OK && e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-  }
-  if (e0) hipEventDestroy(e0);
-  if (e1) hipEventDestroy(e1);
-  if (rc == HMME_OK && e != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "timing the search kernel: %s", hipGetErrorString(e));
-  if (rc == HMME_OK) *avg_ms = ms / reps;
+  if (rc == HMME_OK)
+    rc = time_reps(ctx, s, reps, "the search kernel", [&] {
+      return run_search(ctx, pl.cur_blocks, cur->ctus_x, pl.refs, ref->pitch, fp, plan, (int16_t*)d_out_mv, (uint32_t*)d_out_sad, s);
+    }, avg_ms);
   return pairs_end(ctx, &cur, &ref, 1, s, rc);
 }
 

@@ -1287,6 +1287,72 @@ def test_refinement_launch_modes_give_the_same_tables():
     assert json.loads(r.stdout.strip().splitlines()[-1])["tables_crc32"] == crcs[("0", "8")]
 
 
+def test_weighted_and_bi_refinement_launch_modes_give_the_same_tables(oracle_lib):
+    """The weighted and the bi-prediction refinement go through the launcher of the plain one (hmme.hip launch_refine), so the launch modes
+    of the test above hold for them too -- tools/refine_modes.py, one process per mode (the knobs are read once per process): three pairs
+    in one launch on 3 x 3 CTUs (168x136, search range 12, Hadamard, 8 and 10 bit); weights [A, A, B] with non-zero predictors (a run of
+    two pairs, then a run of one: each run's job table and counter in the same buffer); bi with a motion field per 8x8 block and window
+    centres.  HMME_FRAC_GRID=4 is fewer workgroups than the 9 jobs of the short run: every run walks.  The default mode's tables, computed
+    here, are the oracle's: every CTU and slot of every pair (hmo_frac_refine_w per slot; the oracle's frame refinement of the origin
+    2 * cur - prediction built in numpy)."""
+    import importlib.util
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    from frame_helpers import bind_hmo, ctu_origin, oracle_prediction, origin_picture
+    from hmme import synth
+    tool = os.path.join(ROOT, "tools", "refine_modes.py")
+    modes = {"default": {}, "grid 4": {"HMME_FRAC_GRID": "4"}, "grid -1": {"HMME_FRAC_GRID": "-1"}, "job table": {"HMME_FRAC_JOB_TABLE": "1"}}
+    base = {k: v for k, v in os.environ.items() if k not in ("HMME_FRAC_GRID", "HMME_FRAC_JOB_TABLE")}
+    crcs = {}
+    for name, env in modes.items():
+        r = subprocess.run([sys.executable, tool, "8", "10"], capture_output=True, text=True, timeout=600, env=dict(base, **env))
+        assert r.returncode == 0, (name, r.stderr[-1500:])
+        crcs[name] = json.loads(r.stdout.strip().splitlines()[-1])
+    for bd in ("8", "10"):
+        for kind in ("weighted_crc32", "bi_crc32"):
+            assert len({crcs[name][bd][kind] for name in modes}) == 1, (bd, kind, crcs)
+    assert crcs["default"]["8"] != crcs["default"]["10"]
+
+    # the default mode against the oracle (this process reads the knobs itself: it must be in the default mode too)
+    assert "HMME_FRAC_GRID" not in os.environ and "HMME_FRAC_JOB_TABLE" not in os.environ
+    spec = importlib.util.spec_from_file_location("refine_modes", tool)
+    rm = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rm)
+    hmo = bind_hmo(oracle_lib)
+    table = oracle_lib.slot_table()
+    m, w, h = synth.MARGIN, rm.W, rm.H
+    eng = rm.engine()
+    try:
+        for bd in (8, 10):
+            r = rm.weighted(eng, bd)
+            assert rm.crc(r) == crcs["default"][str(bd)]["weighted_crc32"]
+            assert len({r["wps"][0], r["wps"][1]}) == 1 and r["wps"][2] != r["wps"][0]
+            for i in range(3):
+                cur, ref = r["curs"][i], r["refs"][i]
+                for ctu in range(rm.N_CTU):
+                    cx, cy = ctu_origin(ctu, w)
+                    pq = (int(r["pred"][i, ctu, 0]), int(r["pred"][i, ctu, 1]))
+                    for s in range(593):
+                        x, y, bw, bh = (int(v) for v in table[s])
+                        imv = (int(r["mv"][i, ctu, s, 0]), int(r["mv"][i, ctu, s, 1]))
+                        hx, hy, qx, qy, c = oracle_lib.frac_refine_w(cur, (m + cx + x, m + cy + y), ref, (m + cx + x, m + cy + y), bw, bh, imv, pq,
+                                                                     eng.lambda_q16, 1, bd, r["wps"][i])
+                        got = (int(r["qmv"][i, ctu, s, 0]), int(r["qmv"][i, ctu, s, 1]), int(r["cost"][i, ctu, s]))
+                        assert got == (4 * imv[0] + 2 * hx + qx, 4 * imv[1] + 2 * hy + qy, c), (bd, i, ctu, s)
+            r = rm.bi(eng, bd)
+            assert rm.crc(r) == crcs["default"][str(bd)]["bi_crc32"]
+            for i in range(3):
+                org = origin_picture(r["curs"][i], oracle_prediction(hmo, r["others"][i], w, h, bd, r["field"][i]), w, h)
+                oq, oc = oracle_lib.refine_frame(np.ascontiguousarray(np.pad(org, m)), r["refs"][i], (m, m), w, h, r["mv"][i], r["pred"][i], eng.lambda_q16, 1,
+                                                 bd, n_threads=8)
+                assert np.array_equal(r["qmv"][i], oq), (bd, i, np.argwhere(r["qmv"][i] != oq)[:4])
+                assert np.array_equal(r["cost"][i], oc), (bd, i, np.argwhere(r["cost"][i] != oc)[:4])
+    finally:
+        eng.close()
+
+
 def test_sequence_driver_reads_a_yuv_file(tmp_path):
     """tools/me_sequence.py --yuv: the frame feeder (planar 8-bit 4:2:0 reader, hmme/yuv.py) in front of the sharded sequence
     search; the file holds a texture panning by (2, 1) per picture, which the 64x64 PUs must find"""
