@@ -1622,9 +1622,13 @@ int hmme_refine_frame(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* re
 // an 8-bit plane) and weights the clipped prediction per sample: me_frac_kernel<HAD, 2, 1>, one launch per run of equal weights.
 namespace {
 struct WpInfo { int bias = 0; bool identity = false; };
+// the nominal range of the block a weighted reference is compared with, in units of maxv = 2^bitDepth - 1
+struct BlockRange { int lo, hi; };
+constexpr BlockRange kPictureBlock{0, 1};   // samples of a picture: [0, maxv]
+constexpr BlockRange kBiOrigin{-1, 2};      // a bi-prediction origin 2 * org - pred: [-maxv, 2 * maxv]
 
-// what ctu_call decides from the samples it scans, decided from the nominal range [0, 2^bitDepth - 1] of both pictures
-int weight_eval(int bit_depth, const hmme_weight* wp, int refine, WpInfo* info, char* msg, size_t n) {
+// what ctu_call decides from the samples it scans, decided from the nominal ranges: the reference in [0, 2^bitDepth - 1], the block in `block`
+int weight_eval(int bit_depth, const hmme_weight* wp, int refine, BlockRange block, WpInfo* info, char* msg, size_t n) {
   msg[0] = 0;
   if (!wp) { snprintf(msg, n, "null weight"); return HMME_ERR_ARG; }
   if (wp->shift < 0 || wp->shift > 15) { snprintf(msg, n, "weighted prediction: shift %d outside 0..15", wp->shift); return HMME_ERR_ARG; }
@@ -1640,9 +1644,10 @@ int weight_eval(int bit_depth, const hmme_weight* wp, int refine, WpInfo* info, 
   const long a = (p0 >> wp->shift) + wp->offset, b = (p1 >> wp->shift) + wp->offset;
   const long wlo = std::min(a, b), whi = std::max(a, b);
   if (wlo < -32768 || whi > 32767) { snprintf(msg, n, "weighted prediction reaches %ld..%ld, beyond a Pel", wlo, whi); return HMME_ERR_UNSUPPORTED; }
-  const long bias = wlo < 0 ? -wlo : 0;   // the block's lowest nominal sample is 0
-  if (std::max(whi, maxv) + bias > 65535) { snprintf(msg, n, "weighted prediction: samples span more than 16 bits"); return HMME_ERR_UNSUPPORTED; }
-  const long span = std::max(maxv - wlo, whi);   // largest |block - weighted sample| the two ranges admit
+  const long blo = block.lo * maxv, bhi = block.hi * maxv;
+  const long bias = std::max(0L, -std::min(wlo, blo));   // what keeps block and weighted plane unsigned
+  if (std::max(whi, bhi) + bias > 65535) { snprintf(msg, n, "weighted prediction: samples span more than 16 bits"); return HMME_ERR_UNSUPPORTED; }
+  const long span = std::max(bhi - wlo, whi - blo);   // largest |block - weighted sample| the two ranges admit
   if (((4096 * span) >> (bit_depth - 8)) + 65535 >= (long)hmme::kInvCost16) {
     snprintf(msg, n, "weighted SADs of a %d-bit block could reach %ld: beyond the cost field", bit_depth, 4096 * span);
     return HMME_ERR_UNSUPPORTED;
@@ -1671,7 +1676,7 @@ int check_weights(hmme_ctx* ctx, const char* who, const hmme_frame_params* fp, c
   *all_identity = true;
   char msg[256];
   for (int r = 0; r < n_pairs; ++r) {
-    const int rc = weight_eval(fp->bit_depth, &wps[r], refine, &info[r], msg, sizeof msg);
+    const int rc = weight_eval(fp->bit_depth, &wps[r], refine, kPictureBlock, &info[r], msg, sizeof msg);
     if (rc) return fail(ctx, rc, "%s: pair %d: %s", who, r, msg);
     *all_identity = *all_identity && info[r].identity;
   }
@@ -1741,7 +1746,7 @@ int cached_copy(hmme_ctx* ctx, CopyCache& cc, const WpGeom& g, int r, const Copy
 
 int hmme_weight_check(int bit_depth, const hmme_weight* wp, int refine) {
   char msg[256];
-  return weight_eval(bit_depth, wp, refine, nullptr, msg, sizeof msg);
+  return weight_eval(bit_depth, wp, refine, kPictureBlock, nullptr, msg, sizeof msg);
 }
 
 int hmme_search_pairs_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, int n_pairs,
@@ -1908,13 +1913,85 @@ int bi_args(hmme_ctx* ctx, const char* who, const hmme_plane* const* curs, const
   return HMME_OK;
 }
 
+// A pair of the bi pass as the kernels take it: the searched list's bias and identity (WpInfo) and the other list's weight as addWeightUni
+// forms it.  Without explicit weights: bias maxv, both identities.
+struct BiWp {
+  WpInfo info;
+  bool other_identity = true;
+  hmme::MePredWp<1> pw{};
+};
+void bi_unweighted(int bit_depth, int n_pairs, BiWp* bw) {
+  for (int r = 0; r < n_pairs; ++r) { bw[r] = BiWp{}; bw[r].info.bias = (1 << bit_depth) - 1; bw[r].info.identity = true; }
+}
+
+// What is an argument error in every weight of the bi family, before any range is looked at: bit depth, null, shift.  (weight_eval, the
+// *_w family's check, answers HMME_ERR_UNSUPPORTED to a bit depth outside 8..12 and keeps doing so; the bi family follows hmme_bipred_check,
+// which answers HMME_ERR_ARG, so the depth is tested here first and weight_eval never sees a bad one.)
+int bi_weight_args(int bit_depth, const hmme_weight* wp, const char* which, char* msg, size_t n) {
+  msg[0] = 0;
+  if (bit_depth < 8 || bit_depth > 12) { snprintf(msg, n, "bit depth %d outside 8..12", bit_depth); return HMME_ERR_ARG; }
+  if (!wp) { snprintf(msg, n, "null weight of the %s list", which); return HMME_ERR_ARG; }
+  if (wp->shift < 0 || wp->shift > 15) { snprintf(msg, n, "weighted prediction of the %s list: shift %d outside 0..15", which, wp->shift); return HMME_ERR_ARG; }
+  return HMME_OK;
+}
+
+// the other list's weight (TComWeightPrediction.cpp:133-180): ClipBD(((w0 * (P + 8192) + round') >> shift') + offset) with
+// shift' = shift + headRoom and round' = 1 << (shift' - 1); wp->round is not used.  P is a Pel, so P + 8192 lies within [-24 576, 40 959].
+int other_weight_eval(int bit_depth, const hmme_weight* wp, bool* identity, hmme::MePredWp<1>* pw, char* msg, size_t n) {
+  const int rc = bi_weight_args(bit_depth, wp, "other", msg, n);
+  if (rc) return rc;
+  const int sh = wp->shift + std::max(2, 14 - bit_depth);
+  const long rnd = 1L << (sh - 1);
+  if (std::labs((long)wp->w0) * 40960 + rnd > INT32_MAX) {
+    snprintf(msg, n, "weighted prediction of the other list: |w0| * 40960 + round' reaches %ld, beyond 32 bits", std::labs((long)wp->w0) * 40960 + rnd);
+    return HMME_ERR_UNSUPPORTED;
+  }
+  if (identity) *identity = wp->w0 == (1 << wp->shift) && wp->offset == 0;
+  if (pw) *pw = hmme::MePredWp<1>{wp->w0, (int)rnd, sh, wp->offset};
+  return HMME_OK;
+}
+
+// both weights of a pair: the argument errors of both first, then the searched list's ranges against a bi-prediction origin, then the
+// other list's
+int bipred_weight_eval(int bit_depth, const hmme_weight* wp, const hmme_weight* other_wp, int refine, BiWp* bw, char* msg, size_t n) {
+  int rc = bi_weight_args(bit_depth, wp, "searched", msg, n);
+  if (rc == HMME_OK) rc = bi_weight_args(bit_depth, other_wp, "other", msg, n);
+  if (rc == HMME_OK) rc = weight_eval(bit_depth, wp, refine, kBiOrigin, bw ? &bw->info : nullptr, msg, n);
+  if (rc == HMME_OK) rc = other_weight_eval(bit_depth, other_wp, bw ? &bw->other_identity : nullptr, bw ? &bw->pw : nullptr, msg, n);
+  return rc;
+}
+
+// every pair's two weights before anything is launched; the message names the pair
+int check_bi_weights(hmme_ctx* ctx, const char* who, const hmme_frame_params* fp, const hmme_weight* wps, const hmme_weight* other_wps, int n_pairs, int refine,
+                     BiWp* bw, bool* all_identity) {
+  if (!fp) return fail(ctx, HMME_ERR_ARG, "%s: null params", who);
+  if (!wps || !other_wps) return fail(ctx, HMME_ERR_ARG, "%s: null weights", who);
+  if (n_pairs < 1 || n_pairs > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d picture pairs outside 1..%d", who, n_pairs, hmme::kMaxRefs);
+  *all_identity = true;
+  char msg[256];
+  for (int r = 0; r < n_pairs; ++r) {
+    const int rc = bipred_weight_eval(fp->bit_depth, &wps[r], &other_wps[r], refine, &bw[r], msg, sizeof msg);
+    if (rc) return fail(ctx, rc, "%s: pair %d: %s", who, r, msg);
+    *all_identity = *all_identity && bw[r].info.identity && bw[r].other_identity;
+  }
+  return HMME_OK;
+}
+
 // me_predict_kernel for CTUs [first, first + count) of `src` with its motion field (int16 [n_ctu][mv_per_ctu][2], device)
 int launch_predict(hmme_ctx* ctx, const hmme_plane* src, const int16_t* d_field, int mv_per_ctu, int first, int count, bool origin, const uint8_t* cur_blocks,
-                   int bias, uint8_t* dst, long dst_ctu_x, long dst_ctu_y, int dst_pitch, hipStream_t s) {
+                   int bias, uint8_t* dst, long dst_ctu_x, long dst_ctu_y, int dst_pitch, hipStream_t s, const hmme::MePredWp<1>* pw = nullptr) {
   const dim3 grid((unsigned)count), block(256);
+  // pw: the weight of a slice with explicit weighted prediction (null: none, and the identity -- WP = 0 computes the same samples)
 #define HMME_PREDICT(T, OUT)                                                                                                              \
-  hipLaunchKernelGGL((hmme::me_predict_kernel<T, OUT>), grid, block, 0, s, src->origin(), src->pitch, d_field, mv_per_ctu, first, src->width, \
-                     src->height, src->bit_depth, cur_blocks, bias, dst, dst_ctu_x, dst_ctu_y, dst_pitch)
+  do {                                                                                                                                    \
+    if (pw)                                                                                                                               \
+      hipLaunchKernelGGL((hmme::me_predict_kernel<T, OUT, 1>), grid, block, 0, s, src->origin(), src->pitch, d_field, mv_per_ctu, first,  \
+                         src->width, src->height, src->bit_depth, cur_blocks, bias, dst, dst_ctu_x, dst_ctu_y, dst_pitch, *pw);           \
+    else                                                                                                                                  \
+      hipLaunchKernelGGL((hmme::me_predict_kernel<T, OUT, 0>), grid, block, 0, s, src->origin(), src->pitch, d_field, mv_per_ctu, first,  \
+                         src->width, src->height, src->bit_depth, cur_blocks, bias, dst, dst_ctu_x, dst_ctu_y, dst_pitch,                 \
+                         hmme::MePredWp<0>{});                                                                                            \
+  } while (0)
   if (src->bps == 1) { if (origin) HMME_PREDICT(uint8_t, 1); else HMME_PREDICT(uint8_t, 0); }
   else { if (origin) HMME_PREDICT(uint16_t, 1); else HMME_PREDICT(uint16_t, 0); }
 #undef HMME_PREDICT
@@ -1928,16 +2005,26 @@ int hmme_bipred_check(int bit_depth, int refine) {
   return bipred_eval(bit_depth, refine, msg, sizeof msg);
 }
 
-int hmme_predict_pairs_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_pairs, const hmme_frame_params* fp, const void* d_mv_field,
-                              int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream) {
-  if (!ctx) return HMME_ERR_ARG;
-  int rc = bi_check(ctx, "hmme_predict_pairs_device", fp, 0);
+namespace {
+// hmme_predict_pairs_device (wps == null) and hmme_predict_pairs_w_device
+int predict_pairs(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs, int n_pairs, const hmme_frame_params* fp, const hmme_weight* wps,
+                  const void* d_mv_field, int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream) {
+  int rc = bi_check(ctx, who, fp, 0);
   if (rc) return rc;
-  if (!refs || !d_outs || n_pairs < 1 || n_pairs > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "hmme_predict_pairs_device: %d pictures outside 1..%d (or a null list)", n_pairs, hmme::kMaxRefs);
-  if (!d_mv_field || (mv_per_ctu != 1 && mv_per_ctu != 64)) return fail(ctx, HMME_ERR_ARG, "hmme_predict_pairs_device: null motion field, or %d MVs per CTU (1 or 64)", mv_per_ctu);
+  if (!refs || !d_outs || n_pairs < 1 || n_pairs > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d pictures outside 1..%d (or a null list)", who, n_pairs, hmme::kMaxRefs);
+  bool identity[hmme::kMaxRefs];
+  hmme::MePredWp<1> pw[hmme::kMaxRefs];
+  for (int r = 0; r < n_pairs; ++r) {
+    identity[r] = true;
+    if (!wps) continue;
+    char msg[256];
+    rc = other_weight_eval(fp->bit_depth, &wps[r], &identity[r], &pw[r], msg, sizeof msg);
+    if (rc) return fail(ctx, rc, "%s: picture %d: %s", who, r, msg);
+  }
+  if (!d_mv_field || (mv_per_ctu != 1 && mv_per_ctu != 64)) return fail(ctx, HMME_ERR_ARG, "%s: null motion field, or %d MVs per CTU (1 or 64)", who, mv_per_ctu);
   for (int r = 0; r < n_pairs; ++r)
-    if (!refs[r] || !d_outs[r]) return fail(ctx, HMME_ERR_ARG, "hmme_predict_pairs_device: null plane / output image");
-  if (out_pitch_bytes < refs[0]->width * refs[0]->bps) return fail(ctx, HMME_ERR_ARG, "hmme_predict_pairs_device: output pitch %d below a picture row", out_pitch_bytes);
+    if (!refs[r] || !d_outs[r]) return fail(ctx, HMME_ERR_ARG, "%s: null plane / output image", who);
+  if (out_pitch_bytes < refs[0]->width * refs[0]->bps) return fail(ctx, HMME_ERR_ARG, "%s: output pitch %d below a picture row", who, out_pitch_bytes);
   hmme_frame_params f = *fp;
   f.search_range = 1;   // not consulted: nothing is searched
   hipStream_t s = (hipStream_t)stream;
@@ -1947,18 +2034,23 @@ int hmme_predict_pairs_device(hmme_ctx* ctx, const hmme_plane* const* refs, int 
   const size_t field = (size_t)refs[0]->n_ctu * mv_per_ctu * 2;
   for (int r = 0; r < n_pairs && rc == HMME_OK; ++r)
     rc = launch_predict(ctx, refs[r], (const int16_t*)d_mv_field + field * r, mv_per_ctu, pl.first, pl.count, false, nullptr, 0, (uint8_t*)d_outs[r], 0, 0,
-                        out_pitch_bytes, s);
+                        out_pitch_bytes, s, identity[r] ? nullptr : &pw[r]);
   return pairs_end(ctx, refs, refs, n_pairs, s, rc);
 }
 
-int hmme_predict_frame(hmme_ctx* ctx, const hmme_plane* ref, const hmme_frame_params* fp, const int16_t* mv_field, int mv_per_ctu, void* out,
-                       int out_stride) {
-  if (!ctx) return HMME_ERR_ARG;
-  int rc = bi_check(ctx, "hmme_predict_frame", fp, 0);
+// hmme_predict_frame (wp == null) and hmme_predict_frame_w
+int predict_frame(hmme_ctx* ctx, const char* who, const hmme_plane* ref, const hmme_frame_params* fp, const hmme_weight* wp, bool weighted, const int16_t* mv_field,
+                  int mv_per_ctu, void* out, int out_stride) {
+  int rc = bi_check(ctx, who, fp, 0);
   if (rc) return rc;
-  if (!ref || !mv_field || !out || (mv_per_ctu != 1 && mv_per_ctu != 64)) return fail(ctx, HMME_ERR_ARG, "hmme_predict_frame: null argument, or %d MVs per CTU (1 or 64)", mv_per_ctu);
+  if (weighted) {   // before anything is staged
+    char msg[256];
+    rc = other_weight_eval(fp->bit_depth, wp, nullptr, nullptr, msg, sizeof msg);
+    if (rc) return fail(ctx, rc, "%s: %s", who, msg);
+  }
+  if (!ref || !mv_field || !out || (mv_per_ctu != 1 && mv_per_ctu != 64)) return fail(ctx, HMME_ERR_ARG, "%s: null argument, or %d MVs per CTU (1 or 64)", who, mv_per_ctu);
   if (ref->ctx != ctx) return fail(ctx, HMME_ERR_ARG, "plane belongs to another context (planes are used with the context that created them)");
-  if (out_stride < ref->width) return fail(ctx, HMME_ERR_ARG, "hmme_predict_frame: output stride %d below the picture width", out_stride);
+  if (out_stride < ref->width) return fail(ctx, HMME_ERR_ARG, "%s: output stride %d below the picture width", who, out_stride);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t field_bytes = sizeof(int16_t) * 2 * (size_t)ref->n_ctu * mv_per_ctu, row = (size_t)ref->width * ref->bps;
   rc = ensure(ctx, &ctx->d_bi[0], &ctx->bi_cap[0], field_bytes);
@@ -1969,39 +2061,66 @@ int hmme_predict_frame(hmme_ctx* ctx, const hmme_plane* ref, const hmme_frame_pa
   // the caller's image travels both ways: samples outside the CTU range come back as they were
   HIP_TRY(ctx, hipMemcpy2DAsync(ctx->d_bi[1], row, out, (size_t)out_stride * ref->bps, row, ref->height, hipMemcpyHostToDevice, s));
   void* img = ctx->d_bi[1];
-  rc = hmme_predict_pairs_device(ctx, &ref, 1, fp, ctx->d_bi[0], mv_per_ctu, &img, (int)row, s);
+  rc = predict_pairs(ctx, who, &ref, 1, fp, weighted ? wp : nullptr, ctx->d_bi[0], mv_per_ctu, &img, (int)row, s);
   if (rc) return rc;
   HIP_TRY(ctx, hipMemcpy2DAsync(out, (size_t)out_stride * ref->bps, ctx->d_bi[1], row, row, ref->height, hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipStreamSynchronize(s));
   return HMME_OK;
 }
+}  // namespace
 
-int hmme_search_pairs_bi_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others,
-                                int n_pairs, const hmme_frame_params* fp, const void* d_other_mv, int mv_per_ctu, const void* d_center_q,
-                                const void* d_pred_q, void* d_out_mv, void* d_out_sad, void* stream) {
+int hmme_predict_pairs_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_pairs, const hmme_frame_params* fp, const void* d_mv_field,
+                              int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream) {
   if (!ctx) return HMME_ERR_ARG;
-  int rc = bi_check(ctx, "hmme_search_pairs_bi_device", fp, 0);
-  if (rc == HMME_OK) rc = bi_args(ctx, "hmme_search_pairs_bi_device", curs, refs, others, n_pairs, fp, d_other_mv, mv_per_ctu);
-  if (rc) return rc;
+  return predict_pairs(ctx, "hmme_predict_pairs_device", refs, n_pairs, fp, nullptr, d_mv_field, mv_per_ctu, d_outs, out_pitch_bytes, stream);
+}
+
+int hmme_predict_pairs_w_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_pairs, const hmme_frame_params* fp, const hmme_weight* wps,
+                                const void* d_mv_field, int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  if (!wps) return fail(ctx, HMME_ERR_ARG, "hmme_predict_pairs_w_device: null weights");
+  return predict_pairs(ctx, "hmme_predict_pairs_w_device", refs, n_pairs, fp, wps, d_mv_field, mv_per_ctu, d_outs, out_pitch_bytes, stream);
+}
+
+int hmme_predict_frame(hmme_ctx* ctx, const hmme_plane* ref, const hmme_frame_params* fp, const int16_t* mv_field, int mv_per_ctu, void* out,
+                       int out_stride) {
+  if (!ctx) return HMME_ERR_ARG;
+  return predict_frame(ctx, "hmme_predict_frame", ref, fp, nullptr, false, mv_field, mv_per_ctu, out, out_stride);
+}
+
+int hmme_predict_frame_w(hmme_ctx* ctx, const hmme_plane* ref, const hmme_frame_params* fp, const hmme_weight* wp, const int16_t* mv_field,
+                         int mv_per_ctu, void* out, int out_stride) {
+  if (!ctx) return HMME_ERR_ARG;
+  return predict_frame(ctx, "hmme_predict_frame_w", ref, fp, wp, true, mv_field, mv_per_ctu, out, out_stride);
+}
+
+namespace {
+// the bi search after its checks.  wps == null: no explicit weights (bw from bi_unweighted); else the searched list's weights, bw from
+// check_bi_weights and fp->fen already 0
+int bi_search(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others, int n_pairs,
+              const hmme_frame_params* fp, const hmme_weight* wps, const BiWp* bw, const void* d_other_mv, int mv_per_ctu, const void* d_center_q,
+              const void* d_pred_q, void* d_out_mv, void* d_out_sad, void* stream) {
   if (!d_out_mv || !d_out_sad) return fail(ctx, HMME_ERR_ARG, "null output buffer");
   hipStream_t s = (hipStream_t)stream;
   PairLaunch pl;
-  rc = pairs_begin(ctx, curs, refs, n_pairs, fp, s, &pl);
+  int rc = pairs_begin(ctx, curs, refs, n_pairs, fp, s, &pl);
   if (rc || pl.count == 0) return rc;
   for (int r = 0; r < n_pairs && rc == HMME_OK; ++r) rc = plane_wait(ctx, others[r], s);
   const WpGeom g(refs[0]);
-  const int bias = (1 << fp->bit_depth) - 1, n_ctu = curs[0]->n_ctu, ctus_x = curs[0]->ctus_x;
+  const int n_ctu = curs[0]->n_ctu, ctus_x = curs[0]->ctus_x;
   if (rc == HMME_OK) rc = ensure(ctx, &ctx->d_wp[0], &ctx->wp_cap[0], g.plane_bytes * n_pairs);
   if (rc == HMME_OK) rc = ensure(ctx, &ctx->d_wp[1], &ctx->wp_cap[1], g.blk_bytes * n_pairs);
   RefSet wrefs = one_ref(nullptr), wcurs = one_ref(nullptr);
   const size_t field = (size_t)n_ctu * mv_per_ctu * 2;
   CopyCache wref(ctx->d_wp[0], g.plane_bytes, false);   // the references with the origin's bias
   for (int r = 0; r < n_pairs && rc == HMME_OK; ++r) {
-    rc = cached_copy(ctx, wref, g, r, CopyKey{refs[r], 1, 0, 0, bias}, s, &wrefs.base[r]);
+    const int bias = bw[r].info.bias;   // origin and weighted reference carry the pair's bias
+    rc = cached_copy(ctx, wref, g, r, wps ? CopyKey{refs[r], wps[r].w0, wps[r].round, wps[r].shift, wps[r].offset + bias} : CopyKey{refs[r], 1, 0, 0, bias}, s,
+                     &wrefs.base[r]);
     if (rc != HMME_OK) break;
     uint8_t* blocks = ctx->d_wp[1] + g.blk_bytes * r;   // the origin: one per pair (it depends on the pair's field)
     rc = launch_predict(ctx, others[r], (const int16_t*)d_other_mv + field * r, mv_per_ctu, pl.first, pl.count, true, curs[r]->d_blocks, bias, blocks,
-                        hmme::kBlkBytes16, (long)ctus_x * hmme::kBlkBytes16, 128, s);
+                        hmme::kBlkBytes16, (long)ctus_x * hmme::kBlkBytes16, 128, s, bw[r].other_identity ? nullptr : &bw[r].pw);
     wcurs.base[r] = blocks;
   }
   FramePlan plan;
@@ -2010,20 +2129,18 @@ int hmme_search_pairs_bi_device(hmme_ctx* ctx, const hmme_plane* const* curs, co
   return pairs_end(ctx, curs, refs, n_pairs, s, rc, others);
 }
 
-int hmme_refine_pairs_bi_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others,
-                                int n_pairs, const hmme_frame_params* fp, const void* d_other_mv, int mv_per_ctu, const void* d_center_q,
-                                const void* d_pred_q, const void* d_int_mv, int use_hadamard, void* d_out_qmv, void* d_out_cost, void* stream) {
-  if (!ctx) return HMME_ERR_ARG;
-  int rc = bi_check(ctx, "hmme_refine_pairs_bi_device", fp, 1);
-  if (rc == HMME_OK) rc = bi_args(ctx, "hmme_refine_pairs_bi_device", curs, refs, others, n_pairs, fp, d_other_mv, mv_per_ctu);
-  if (rc) return rc;
+// the bi refinement after its checks; wps / bw as in bi_search.  One launch per run of equal searched weights (the weight is one kernel
+// argument, FracWp), one launch in all without explicit weights
+int bi_refine(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others, int n_pairs,
+              const hmme_frame_params* fp, const hmme_weight* wps, const BiWp* bw, const void* d_other_mv, int mv_per_ctu, const void* d_center_q,
+              const void* d_pred_q, const void* d_int_mv, int use_hadamard, void* d_out_qmv, void* d_out_cost, void* stream) {
   if (!d_int_mv || !d_out_qmv || !d_out_cost) return fail(ctx, HMME_ERR_ARG, "null buffer");
   hipStream_t s = (hipStream_t)stream;
   PairLaunch pl;
-  rc = pairs_begin(ctx, curs, refs, n_pairs, fp, s, &pl);
+  int rc = pairs_begin(ctx, curs, refs, n_pairs, fp, s, &pl);
   if (rc || pl.count == 0) return rc;
   for (int r = 0; r < n_pairs && rc == HMME_OK; ++r) rc = plane_wait(ctx, others[r], s);
-  const int src_wide = curs[0]->bps == 2 ? 1 : 0, bias = (1 << fp->bit_depth) - 1, n_ctu = curs[0]->n_ctu;
+  const int src_wide = curs[0]->bps == 2 ? 1 : 0, n_ctu = curs[0]->n_ctu;
   const WpGeom g(refs[0]);
   if (rc == HMME_OK && !src_wide) rc = ensure(ctx, &ctx->d_wp[2], &ctx->wp_cap[2], g.plane_bytes * n_pairs);
   if (rc == HMME_OK) rc = ensure(ctx, &ctx->d_wp[3], &ctx->wp_cap[3], g.plane_bytes * n_pairs);
@@ -2038,20 +2155,101 @@ int hmme_refine_pairs_bi_device(hmme_ctx* ctx, const hmme_plane* const* curs, co
     // the origin in a padded plane's layout: only the CTU blocks are written and read (a partial CTU's block ends 63 samples into the
     // 128 / 80-sample margins at most)
     uint8_t* plane = ctx->d_wp[3] + g.plane_bytes * r + g.origin;
-    rc = launch_predict(ctx, others[r], (const int16_t*)d_other_mv + field * r, mv_per_ctu, pl.first, pl.count, true, curs[r]->d_blocks, bias, plane, 128,
-                        64L * g.pitch, g.pitch, s);
+    rc = launch_predict(ctx, others[r], (const int16_t*)d_other_mv + field * r, mv_per_ctu, pl.first, pl.count, true, curs[r]->d_blocks, bw[r].info.bias, plane,
+                        128, 64L * g.pitch, g.pitch, s, bw[r].other_identity ? nullptr : &bw[r].pw);
     c.base[r] = plane;
   }
-  if (rc == HMME_OK) {
+  for (int a = 0, b; a < n_pairs && rc == HMME_OK; a = b) {
+    for (b = wps ? a + 1 : n_pairs; b < n_pairs && same_weight(wps[b], wps[a]); ++b) {}
+    RefSet ca = one_ref(nullptr), ra = one_ref(nullptr);
+    for (int r = a; r < b; ++r) { ca.base[r - a] = c.base[r]; ra.base[r - a] = rf.base[r]; }
+    // the run's own table and counter in the same buffer as the run before (on one stream: behind its kernel)
+    const size_t res0 = (size_t)a * pl.count * HMME_NUM_CTU_PARTS;
     RefineLaunch L;
-    refine_common(L, pl, curs[0], fp, use_hadamard, d_int_mv, d_out_qmv, d_out_cost);
-    L.curs = c; L.refs = rf; L.cur_pitch = g.pitch; L.ref_pitch = g.pitch;
-    L.wide = 1; L.wp = 1; L.fw = hmme::FracWp{1.f, 0.f, (float)bias};   // the identity weight; org_sub takes the origin's bias off
-    L.d_pred = (const int16_t*)d_pred_q; L.d_center = (const int16_t*)d_center_q; L.pairs = n_pairs;
+    refine_common(L, pl, curs[0], fp, use_hadamard, (const int16_t*)d_int_mv + 2 * res0, (int16_t*)d_out_qmv + 2 * res0, (uint32_t*)d_out_cost + res0);
+    L.curs = ca; L.refs = ra; L.cur_pitch = g.pitch; L.ref_pitch = g.pitch;
+    L.wide = 1; L.wp = 1;
+    // org_sub takes the origin's bias off, with the weight's offset; without explicit weights (and for an identity weight) the weight is 1
+    if (wps && !bw[a].info.identity)
+      L.fw = hmme::FracWp{std::ldexp((float)wps[a].w0, -wps[a].shift), std::ldexp((float)wps[a].round, -wps[a].shift), (float)(bw[a].info.bias + wps[a].offset)};
+    else
+      L.fw = hmme::FracWp{1.f, 0.f, (float)bw[a].info.bias};
+    L.d_pred = d_pred_q ? (const int16_t*)d_pred_q + (size_t)a * n_ctu * 2 : nullptr;
+    L.d_center = d_center_q ? (const int16_t*)d_center_q + (size_t)a * n_ctu * 2 : nullptr;
+    L.pairs = b - a;
     L.table = FracTable::kAlways;   // the table carries the window centres (FracPrep derives windows from predictors only)
     rc = launch_refine(ctx, L, s);
   }
   return pairs_end(ctx, curs, refs, n_pairs, s, rc, others);
+}
+}  // namespace
+
+int hmme_search_pairs_bi_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others,
+                                int n_pairs, const hmme_frame_params* fp, const void* d_other_mv, int mv_per_ctu, const void* d_center_q,
+                                const void* d_pred_q, void* d_out_mv, void* d_out_sad, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  int rc = bi_check(ctx, "hmme_search_pairs_bi_device", fp, 0);
+  if (rc == HMME_OK) rc = bi_args(ctx, "hmme_search_pairs_bi_device", curs, refs, others, n_pairs, fp, d_other_mv, mv_per_ctu);
+  if (rc) return rc;
+  BiWp bw[hmme::kMaxRefs];
+  bi_unweighted(fp->bit_depth, n_pairs, bw);
+  return bi_search(ctx, curs, refs, others, n_pairs, fp, nullptr, bw, d_other_mv, mv_per_ctu, d_center_q, d_pred_q, d_out_mv, d_out_sad, stream);
+}
+
+int hmme_refine_pairs_bi_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others,
+                                int n_pairs, const hmme_frame_params* fp, const void* d_other_mv, int mv_per_ctu, const void* d_center_q,
+                                const void* d_pred_q, const void* d_int_mv, int use_hadamard, void* d_out_qmv, void* d_out_cost, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  int rc = bi_check(ctx, "hmme_refine_pairs_bi_device", fp, 1);
+  if (rc == HMME_OK) rc = bi_args(ctx, "hmme_refine_pairs_bi_device", curs, refs, others, n_pairs, fp, d_other_mv, mv_per_ctu);
+  if (rc) return rc;
+  BiWp bw[hmme::kMaxRefs];
+  bi_unweighted(fp->bit_depth, n_pairs, bw);
+  return bi_refine(ctx, curs, refs, others, n_pairs, fp, nullptr, bw, d_other_mv, mv_per_ctu, d_center_q, d_pred_q, d_int_mv, use_hadamard, d_out_qmv, d_out_cost,
+                   stream);
+}
+
+// ---- ... with explicit weighted prediction: the searched list's weight prices the candidates (xGetSADw / xGetHADsw), the other list's
+// shapes the prediction the origin is built from (addWeightUni).  A launch whose weights are all the identity IS the unweighted call with
+// FEN off.
+int hmme_bipred_weight_check(int bit_depth, const hmme_weight* wp, const hmme_weight* other_wp, int refine) {
+  char msg[256];
+  return bipred_weight_eval(bit_depth, wp, other_wp, refine, nullptr, msg, sizeof msg);
+}
+
+int hmme_search_pairs_bi_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others,
+                                  int n_pairs, const hmme_frame_params* fp, const hmme_weight* wps, const hmme_weight* other_wps, const void* d_other_mv,
+                                  int mv_per_ctu, const void* d_center_q, const void* d_pred_q, void* d_out_mv, void* d_out_sad, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  BiWp bw[hmme::kMaxRefs];
+  bool all_identity = false;
+  int rc = check_bi_weights(ctx, "hmme_search_pairs_bi_w_device", fp, wps, other_wps, n_pairs, 0, bw, &all_identity);
+  if (rc) return rc;
+  hmme_frame_params f = *fp;
+  f.fen = 0;   // xGetSADw reads every row (TComRdCost.cpp:467-469): FEN is not consulted
+  if (all_identity) return hmme_search_pairs_bi_device(ctx, curs, refs, others, n_pairs, &f, d_other_mv, mv_per_ctu, d_center_q, d_pred_q, d_out_mv, d_out_sad, stream);
+  rc = bi_args(ctx, "hmme_search_pairs_bi_w_device", curs, refs, others, n_pairs, &f, d_other_mv, mv_per_ctu);
+  if (rc) return rc;
+  return bi_search(ctx, curs, refs, others, n_pairs, &f, wps, bw, d_other_mv, mv_per_ctu, d_center_q, d_pred_q, d_out_mv, d_out_sad, stream);
+}
+
+int hmme_refine_pairs_bi_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others,
+                                  int n_pairs, const hmme_frame_params* fp, const hmme_weight* wps, const hmme_weight* other_wps, const void* d_other_mv,
+                                  int mv_per_ctu, const void* d_center_q, const void* d_pred_q, const void* d_int_mv, int use_hadamard, void* d_out_qmv,
+                                  void* d_out_cost, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  BiWp bw[hmme::kMaxRefs];
+  bool all_identity = false;
+  int rc = check_bi_weights(ctx, "hmme_refine_pairs_bi_w_device", fp, wps, other_wps, n_pairs, 1, bw, &all_identity);
+  if (rc) return rc;
+  hmme_frame_params f = *fp;
+  f.fen = 0;
+  if (all_identity)
+    return hmme_refine_pairs_bi_device(ctx, curs, refs, others, n_pairs, &f, d_other_mv, mv_per_ctu, d_center_q, d_pred_q, d_int_mv, use_hadamard, d_out_qmv,
+                                       d_out_cost, stream);
+  rc = bi_args(ctx, "hmme_refine_pairs_bi_w_device", curs, refs, others, n_pairs, &f, d_other_mv, mv_per_ctu);
+  if (rc) return rc;
+  return bi_refine(ctx, curs, refs, others, n_pairs, &f, wps, bw, d_other_mv, mv_per_ctu, d_center_q, d_pred_q, d_int_mv, use_hadamard, d_out_qmv, d_out_cost, stream);
 }
 
 namespace {
@@ -2069,36 +2267,66 @@ int bi_stage(hmme_ctx* ctx, const hmme_plane* cur, const int16_t* other_mv, int 
 }
 }  // namespace
 
-int hmme_search_frame_bi(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
-                         const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q, const int16_t* pred_q, int16_t* out_mv, uint32_t* out_sad) {
-  if (!ctx) return HMME_ERR_ARG;
-  int rc = bi_check(ctx, "hmme_search_frame_bi", fp, 0);
-  if (rc == HMME_OK) rc = bi_args(ctx, "hmme_search_frame_bi", &cur, &ref, &other, 1, fp, other_mv, mv_per_ctu);
+namespace {
+// the four synchronous one-pair bi calls: wp == null is the call without explicit weights; int_mv != null the refinement
+int bi_frame(hmme_ctx* ctx, const char* who, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
+             const hmme_weight* wp, const hmme_weight* other_wp, bool weighted, const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q,
+             const int16_t* pred_q, bool refine, const int16_t* int_mv, int use_hadamard, int16_t* out_mv, uint32_t* out_cost) {
+  int rc;
+  if (weighted) {   // before anything is staged: the device call checks again
+    BiWp bw;
+    bool identity = false;
+    rc = check_bi_weights(ctx, who, fp, wp, other_wp, 1, refine, &bw, &identity);
+  } else {
+    rc = bi_check(ctx, who, fp, refine);
+  }
+  if (rc == HMME_OK) rc = bi_args(ctx, who, &cur, &ref, &other, 1, fp, other_mv, mv_per_ctu);
   if (rc) return rc;
   int count;
   const void *d_pred, *d_field, *d_center;
-  rc = stage_in(ctx, cur, ref, fp, 1, pred_q, false, nullptr, out_mv, out_sad, &count, &d_pred);
+  rc = stage_in(ctx, cur, ref, fp, 1, pred_q, refine, int_mv, out_mv, out_cost, &count, &d_pred);
   if (rc || count == 0) return rc;
   rc = bi_stage(ctx, cur, other_mv, mv_per_ctu, center_q, &d_field, &d_center);
-  if (rc == HMME_OK) rc = hmme_search_pairs_bi_device(ctx, &cur, &ref, &other, 1, fp, d_field, mv_per_ctu, d_center, d_pred, ctx->d_mv, ctx->d_sad, ctx->stream);
-  return rc ? rc : stage_out(ctx, false, count, out_mv, out_sad);
+  if (rc) return rc;
+  if (!refine)
+    rc = weighted ? hmme_search_pairs_bi_w_device(ctx, &cur, &ref, &other, 1, fp, wp, other_wp, d_field, mv_per_ctu, d_center, d_pred, ctx->d_mv, ctx->d_sad, ctx->stream)
+                  : hmme_search_pairs_bi_device(ctx, &cur, &ref, &other, 1, fp, d_field, mv_per_ctu, d_center, d_pred, ctx->d_mv, ctx->d_sad, ctx->stream);
+  else
+    rc = weighted ? hmme_refine_pairs_bi_w_device(ctx, &cur, &ref, &other, 1, fp, wp, other_wp, d_field, mv_per_ctu, d_center, d_pred, ctx->d_imv, use_hadamard,
+                                                  ctx->d_qmv, ctx->d_fcost, ctx->stream)
+                  : hmme_refine_pairs_bi_device(ctx, &cur, &ref, &other, 1, fp, d_field, mv_per_ctu, d_center, d_pred, ctx->d_imv, use_hadamard, ctx->d_qmv,
+                                                ctx->d_fcost, ctx->stream);
+  return rc ? rc : stage_out(ctx, refine, count, out_mv, out_cost);
+}
+}  // namespace
+
+int hmme_search_frame_bi(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
+                         const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q, const int16_t* pred_q, int16_t* out_mv, uint32_t* out_sad) {
+  if (!ctx) return HMME_ERR_ARG;
+  return bi_frame(ctx, "hmme_search_frame_bi", cur, ref, other, fp, nullptr, nullptr, false, other_mv, mv_per_ctu, center_q, pred_q, false, nullptr, 0, out_mv, out_sad);
 }
 
 int hmme_refine_frame_bi(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
                          const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q, const int16_t* pred_q, const int16_t* int_mv,
                          int use_hadamard, int16_t* out_qmv, uint32_t* out_cost) {
   if (!ctx) return HMME_ERR_ARG;
-  int rc = bi_check(ctx, "hmme_refine_frame_bi", fp, 1);
-  if (rc == HMME_OK) rc = bi_args(ctx, "hmme_refine_frame_bi", &cur, &ref, &other, 1, fp, other_mv, mv_per_ctu);
-  if (rc) return rc;
-  int count;
-  const void *d_pred, *d_field, *d_center;
-  rc = stage_in(ctx, cur, ref, fp, 1, pred_q, true, int_mv, out_qmv, out_cost, &count, &d_pred);
-  if (rc || count == 0) return rc;
-  rc = bi_stage(ctx, cur, other_mv, mv_per_ctu, center_q, &d_field, &d_center);
-  if (rc == HMME_OK)
-    rc = hmme_refine_pairs_bi_device(ctx, &cur, &ref, &other, 1, fp, d_field, mv_per_ctu, d_center, d_pred, ctx->d_imv, use_hadamard, ctx->d_qmv, ctx->d_fcost, ctx->stream);
-  return rc ? rc : stage_out(ctx, true, count, out_qmv, out_cost);
+  return bi_frame(ctx, "hmme_refine_frame_bi", cur, ref, other, fp, nullptr, nullptr, false, other_mv, mv_per_ctu, center_q, pred_q, true, int_mv, use_hadamard, out_qmv,
+                  out_cost);
+}
+
+int hmme_search_frame_bi_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
+                           const hmme_weight* wp, const hmme_weight* other_wp, const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q,
+                           const int16_t* pred_q, int16_t* out_mv, uint32_t* out_sad) {
+  if (!ctx) return HMME_ERR_ARG;
+  return bi_frame(ctx, "hmme_search_frame_bi_w", cur, ref, other, fp, wp, other_wp, true, other_mv, mv_per_ctu, center_q, pred_q, false, nullptr, 0, out_mv, out_sad);
+}
+
+int hmme_refine_frame_bi_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
+                           const hmme_weight* wp, const hmme_weight* other_wp, const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q,
+                           const int16_t* pred_q, const int16_t* int_mv, int use_hadamard, int16_t* out_qmv, uint32_t* out_cost) {
+  if (!ctx) return HMME_ERR_ARG;
+  return bi_frame(ctx, "hmme_refine_frame_bi_w", cur, ref, other, fp, wp, other_wp, true, other_mv, mv_per_ctu, center_q, pred_q, true, int_mv, use_hadamard, out_qmv,
+                  out_cost);
 }
 
 // ---- partition decision and motion field from the 593-slot tables ---------------------------------------------------------------------
@@ -2466,7 +2694,7 @@ int hmme_test_time_weight_passes(hmme_ctx* ctx, const hmme_plane* cur, const hmm
   if (!cur || !ref || !wp || !ref_ms || !cur_ms || reps < 1) return fail(ctx, HMME_ERR_ARG, "hmme_test_time_weight_passes: bad argument");
   WpInfo info;
   char msg[256];
-  int rc = weight_eval(ref->bit_depth, wp, 0, &info, msg, sizeof msg);
+  int rc = weight_eval(ref->bit_depth, wp, 0, kPictureBlock, &info, msg, sizeof msg);
   if (rc) return fail(ctx, rc, "hmme_test_time_weight_passes: %s", msg);
   hmme_frame_params fp = {1, 0, ref->bit_depth, 0, -1};
   hipStream_t s = (hipStream_t)stream;

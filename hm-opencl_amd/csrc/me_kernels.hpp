@@ -2184,17 +2184,27 @@ __constant__ int kLumaTaps[4][8] = {{0, 0, 0, 64, 0, 0, 0, 0}, {-1, 4, -10, 58, 
 // (TComPrediction.cpp:590-594, :669) in integer arithmetic, int32 sums: bit-identical to hmo_pred_block_qpel at every phase.
 //   OUT = 0: the prediction, samples of the plane's type, into a pitched image at the block's picture position; samples beyond the
 //            picture are not written (blocks wholly outside it are skipped)
-//   OUT = 1: the bi-prediction origin 2 * cur - pred + bias as u16 (TEncSearch.cpp:3702-3712, TComYuv::removeHighFreq, unclipped), cur from
+//   OUT = 1: the bi-prediction origin 2 * cur - pred + bias as u16 (TEncSearch.cpp:3702-3712, TComYuv::removeHighFreq, unclipped; bias = the
+//            pair's: maxv, or more where the searched list's weighted samples go below -maxv), cur from
 //            the current picture's CTU-blocked copy -- partial edge CTUs are whole blocks there (edge replication), and so they are here.
 //            The block of CTU (cx, cy) starts at dst + cy * dst_ctu_y + cx * dst_ctu_x, its rows dst_pitch bytes apart: the CTU-blocked
 //            layout the search reads (8192, ctus_x * 8192, 128) or a padded plane's (128, 64 * pitch, pitch), which the refinement reads
 // All stores are 8 consecutive samples per block row.  Bandwidth is not tuned further: the pass moves tens of MB beside a search of
 // milliseconds.
-template <typename SrcT, int OUT>
+//   WP = 1:  the prediction of a slice with explicit weighted prediction (TComPrediction::motionCompensation, TComPrediction.cpp:527-541):
+//            xPredInterUni with bi = true leaves the 14-bit intermediate P = sum >> 6 of the vertical pass (shift 6, offset 0, no clip),
+//            addWeightUni (TComWeightPrediction.cpp:133-180) weights it: ClipBD(((w0 * (P + 8192) + round') >> shift') + offset) with
+//            shift' = wp.shift + headRoom and round' = 1 << (shift' - 1) -- both made by the host (MePredWp).  The numerator stays inside
+//            int32 (hmme_bipred_weight_check); the offset is added in 64 bits, so any int offset is exact before the clip.  With
+//            w0 == 1 << wp.shift and offset 0 this IS the WP = 0 result (nested floors), which is why identity weights run WP = 0.
+//            The weight travels in the kernel arguments; WP = 0 takes an empty struct and compiles to what it did without it.
+template <int WP> struct MePredWp {};
+template <> struct MePredWp<1> { int w0, round, shift, offset; };   // round / shift: addWeightUni's round' and shift'
+template <typename SrcT, int OUT, int WP = 0>
 __global__ void __launch_bounds__(256)
 me_predict_kernel(const uint8_t* __restrict__ ref_origin, int ref_pitch, const int16_t* __restrict__ mv_field, int mv_per_ctu, int ctu_first,
                   int pic_w, int pic_h, int bit_depth, const uint8_t* __restrict__ cur_blocks, int bias, uint8_t* __restrict__ dst,
-                  long dst_ctu_x, long dst_ctu_y, int dst_pitch) {
+                  long dst_ctu_x, long dst_ctu_y, int dst_pitch, MePredWp<WP> wp) {
   __shared__ int16_t patch[4][15 * 16];
   __shared__ int16_t mid[4][15 * 8];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -2240,8 +2250,15 @@ me_predict_kernel(const uint8_t* __restrict__ ref_origin, int ref_pitch, const i
       int sum = 0;
 #pragma unroll
       for (int t = 0; t < 8; ++t) sum += cv[t] * (int)mid[wave][(r + t) * 8 + c];
-      int v = (sum + off2) >> sh2;
-      v = v < 0 ? 0 : (v > maxv ? maxv : v);
+      int v;
+      if constexpr (WP) {
+        const int P = (int16_t)(sum >> 6);   // HM keeps the intermediate in a Pel: P + 8192 lies within [-24 576, 40 959] whatever the plane holds
+        const long long t = (long long)((wp.w0 * (P + 8192) + wp.round) >> wp.shift) + wp.offset;
+        v = t < 0 ? 0 : (t > maxv ? maxv : (int)t);
+      } else {
+        v = (sum + off2) >> sh2;
+        v = v < 0 ? 0 : (v > maxv ? maxv : v);
+      }
       if (OUT == 0) {
         const int x = cu_x + bx + c, y = cu_y + by + r;
         if (x < pic_w && y < pic_h) ((SrcT*)(dst + (long)y * dst_pitch))[x] = (SrcT)v;

@@ -26,6 +26,8 @@ SYMBOLS = ["hmme_create", "hmme_destroy", "hmme_last_error", "hmme_device_info",
            "hmme_weight_check", "hmme_search_pairs_w_device", "hmme_refine_pairs_w_device", "hmme_search_frame_w", "hmme_refine_frame_w",
            "hmme_bipred_check", "hmme_predict_pairs_device", "hmme_predict_frame", "hmme_search_pairs_bi_device", "hmme_refine_pairs_bi_device",
            "hmme_search_frame_bi", "hmme_refine_frame_bi",
+           "hmme_bipred_weight_check", "hmme_predict_pairs_w_device", "hmme_predict_frame_w", "hmme_search_pairs_bi_w_device",
+           "hmme_refine_pairs_bi_w_device", "hmme_search_frame_bi_w", "hmme_refine_frame_bi_w",
            "hmme_slot_key", "hmme_select_check", "hmme_select_pairs_device", "hmme_select_frame",
            "hmme_plane_stats", "hmme_wp_estimate"]
 # test / measurement entry points (include/hmme_test.h): not part of the boundary
@@ -156,6 +158,14 @@ def load():
     L.hmme_refine_pairs_bi_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, C.POINTER(FrameParams), vp, i, vp, vp, vp, i, vp, vp, vp]
     L.hmme_search_frame_bi.argtypes = [vp, vp, vp, vp, C.POINTER(FrameParams), vp, i, vp, vp, vp, vp]
     L.hmme_refine_frame_bi.argtypes = [vp, vp, vp, vp, C.POINTER(FrameParams), vp, i, vp, vp, vp, i, vp, vp]
+    pw = C.POINTER(Weight)
+    L.hmme_bipred_weight_check.argtypes = [i, pw, pw, i]
+    L.hmme_predict_pairs_w_device.argtypes = [vp, C.POINTER(vp), i, C.POINTER(FrameParams), pw, vp, i, C.POINTER(vp), i, vp]
+    L.hmme_predict_frame_w.argtypes = [vp, vp, C.POINTER(FrameParams), pw, vp, i, vp, i]
+    L.hmme_search_pairs_bi_w_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, C.POINTER(FrameParams), pw, pw, vp, i, vp, vp, vp, vp, vp]
+    L.hmme_refine_pairs_bi_w_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, C.POINTER(FrameParams), pw, pw, vp, i, vp, vp, vp, i, vp, vp, vp]
+    L.hmme_search_frame_bi_w.argtypes = [vp, vp, vp, vp, C.POINTER(FrameParams), pw, pw, vp, i, vp, vp, vp, vp]
+    L.hmme_refine_frame_bi_w.argtypes = [vp, vp, vp, vp, C.POINTER(FrameParams), pw, pw, vp, i, vp, vp, vp, i, vp, vp]
     L.hmme_test_time_bipred_origin.argtypes = [vp, vp, vp, vp, i, vp, i, C.POINTER(C.c_float)]
     L.hmme_slot_key.argtypes = [i] + [C.POINTER(i)] * 4
     L.hmme_select_check.argtypes = [C.POINTER(SelectParams)]
@@ -557,6 +567,84 @@ class Engine:
                                                 int(use_hadamard), qmv.ctypes.data, cost.ctypes.data))
         return qmv, cost
 
+    # ---- ... in a slice with explicit weighted prediction (include/hmme.h, "bi-prediction with explicit weighted prediction"): weights are
+    # (w0, offset, shift, round); `wp` / `weights` belong to the searched list, `other_wp` / `other_weights` to the list whose prediction is subtracted
+    @staticmethod
+    def _weights(weights):
+        return (Weight * len(weights))(*[Weight(*[int(v) for v in w]) for w in weights])
+
+    def predict_pairs_w_device(self, refs, fp, weights, d_mv_field, mv_per_ctu, d_outs, out_pitch_bytes, stream=0):
+        """hmme_predict_pairs_w_device: predict_pairs_device with one weight per picture (the prediction HM's motionCompensation writes in a WP slice)"""
+        assert len(refs) == len(d_outs) == len(weights)
+        ra = (C.c_void_p * len(refs))(*[r.h for r in refs])
+        oa = (C.c_void_p * len(d_outs))(*[int(o) for o in d_outs])
+        self._check(self.L.hmme_predict_pairs_w_device(self.h, ra, len(refs), C.byref(fp), self._weights(weights), d_mv_field, int(mv_per_ctu), oa,
+                                                       int(out_pitch_bytes), stream))
+
+    def predict_frame_w(self, ref, wp, mv_field, out=None, ctu_first=0, ctu_count=-1):
+        """hmme_predict_frame_w: predict_frame with the weight wp"""
+        n = self.L.hmme_num_ctus(ref.width, ref.height)
+        f, per = self._field(mv_field, n)
+        dt = np.uint8 if ref.bit_depth == 8 else np.uint16
+        if out is None:
+            out = np.zeros((ref.height, ref.width), dt)
+        assert out.dtype == dt and out.shape == (ref.height, ref.width) and out.flags.c_contiguous
+        fp = FrameParams(1, 0, ref.bit_depth, ctu_first, ctu_count)
+        w = Weight(*[int(v) for v in wp])
+        self._check(self.L.hmme_predict_frame_w(self.h, ref.h, C.byref(fp), C.byref(w), f.ctypes.data, per, out.ctypes.data, out.shape[1]))
+        return out
+
+    def search_pairs_bi_w_device(self, curs, refs, others, fp, weights, other_weights, d_other_mv, mv_per_ctu, d_center, d_pred, d_mv, d_sad, stream=0):
+        """hmme_search_pairs_bi_w_device: the bi-prediction pass of up to 16 pairs of a WP slice in one launch"""
+        assert len(curs) == len(refs) == len(others) == len(weights) == len(other_weights)
+        ca = (C.c_void_p * len(curs))(*[c.h for c in curs])
+        ra = (C.c_void_p * len(refs))(*[r.h for r in refs])
+        oa = (C.c_void_p * len(others))(*[o.h for o in others])
+        self._check(self.L.hmme_search_pairs_bi_w_device(self.h, ca, ra, oa, len(refs), C.byref(fp), self._weights(weights), self._weights(other_weights),
+                                                         d_other_mv, int(mv_per_ctu), d_center, d_pred, d_mv, d_sad, stream))
+
+    def refine_pairs_bi_w_device(self, curs, refs, others, fp, weights, other_weights, d_other_mv, mv_per_ctu, d_center, d_pred, d_int_mv, use_hadamard,
+                                 d_qmv, d_cost, stream=0):
+        assert len(curs) == len(refs) == len(others) == len(weights) == len(other_weights)
+        ca = (C.c_void_p * len(curs))(*[c.h for c in curs])
+        ra = (C.c_void_p * len(refs))(*[r.h for r in refs])
+        oa = (C.c_void_p * len(others))(*[o.h for o in others])
+        self._check(self.L.hmme_refine_pairs_bi_w_device(self.h, ca, ra, oa, len(refs), C.byref(fp), self._weights(weights), self._weights(other_weights),
+                                                         d_other_mv, int(mv_per_ctu), d_center, d_pred, d_int_mv, int(use_hadamard), d_qmv, d_cost, stream))
+
+    def search_frame_bi_w(self, cur, ref, other, sr, wp, other_wp, other_mv, center_q=None, pred_q=None, fen=0, ctu_first=0, ctu_count=-1):
+        """hmme_search_frame_bi_w: search_frame_bi in a WP slice (fen is passed through and not consulted by the engine)
+        -> (mv int16[count,593,2], sad uint32[count,593])"""
+        n = self.L.hmme_num_ctus(cur.width, cur.height)
+        count = n - ctu_first if ctu_count < 0 else ctu_count
+        fp = FrameParams(sr, int(fen), cur.bit_depth, ctu_first, count)
+        f, per = self._field(other_mv, n)
+        cq, cptr = self._pq(center_q, n)
+        pq, pptr = self._pq(pred_q, n)
+        mv = np.zeros((count, NUM_PARTS, 2), np.int16)
+        sad = np.zeros((count, NUM_PARTS), np.uint32)
+        w, ow = Weight(*[int(v) for v in wp]), Weight(*[int(v) for v in other_wp])
+        self._check(self.L.hmme_search_frame_bi_w(self.h, cur.h, ref.h, other.h, C.byref(fp), C.byref(w), C.byref(ow), f.ctypes.data, per, cptr, pptr,
+                                                  mv.ctypes.data, sad.ctypes.data))
+        return mv, sad
+
+    def refine_frame_bi_w(self, cur, ref, other, sr, wp, other_wp, other_mv, int_mv, center_q=None, pred_q=None, use_hadamard=True, ctu_first=0, ctu_count=-1):
+        """hmme_refine_frame_bi_w: refine_frame_bi in a WP slice -> (qmv int16[count,593,2], cost uint32[count,593])"""
+        n = self.L.hmme_num_ctus(cur.width, cur.height)
+        count = n - ctu_first if ctu_count < 0 else ctu_count
+        fp = FrameParams(sr, 0, cur.bit_depth, ctu_first, count)
+        f, per = self._field(other_mv, n)
+        cq, cptr = self._pq(center_q, n)
+        pq, pptr = self._pq(pred_q, n)
+        int_mv = np.ascontiguousarray(int_mv, dtype=np.int16)
+        assert int_mv.shape == (count, NUM_PARTS, 2)
+        qmv = np.zeros((count, NUM_PARTS, 2), np.int16)
+        cost = np.zeros((count, NUM_PARTS), np.uint32)
+        w, ow = Weight(*[int(v) for v in wp]), Weight(*[int(v) for v in other_wp])
+        self._check(self.L.hmme_refine_frame_bi_w(self.h, cur.h, ref.h, other.h, C.byref(fp), C.byref(w), C.byref(ow), f.ctypes.data, per, cptr, pptr,
+                                                  int_mv.ctypes.data, int(use_hadamard), qmv.ctypes.data, cost.ctypes.data))
+        return qmv, cost
+
     # ---- partition decision and motion field from the 593-slot tables (include/hmme.h, "partition decision and motion field") ----
     def select_pairs_device(self, width, height, n_pairs, fp, sel, d_mv, d_cost, d_pred, d_field, d_slot=None, d_ctu_cost=None, stream=0):
         """hmme_select_pairs_device: the tables of up to 16 pairs (device, as a search / refinement with the same fp wrote them) -> motion field
@@ -653,6 +741,14 @@ def bipred_check(bit_depth, refine=False):
     """hmme_bipred_check: 0, or the HMME_ERR_* code with which the whole-picture bi-prediction calls refuse this bit depth
     (pure host arithmetic: needs no GPU)"""
     return int(load().hmme_bipred_check(int(bit_depth), 1 if refine else 0))
+
+
+def bipred_weight_check(bit_depth, wp, other_wp, refine=False):
+    """hmme_bipred_weight_check: 0, or the HMME_ERR_* code with which the weighted whole-picture bi-prediction calls refuse the pair of weights
+    (wp: the searched list's, other_wp: the other list's; None passes a null pointer) at this bit depth (pure host arithmetic: needs no GPU)"""
+    w = None if wp is None else C.byref(Weight(*[int(v) for v in wp]))
+    ow = None if other_wp is None else C.byref(Weight(*[int(v) for v in other_wp]))
+    return int(load().hmme_bipred_weight_check(int(bit_depth), w, ow, 1 if refine else 0))
 
 
 def select_check(sel):

@@ -27,6 +27,9 @@
  *   hmme_predict_pairs_device,    <- motion compensation (TComPrediction::xPredInterBlk, TComPrediction.cpp:590-594, :669) and the bi-prediction
  *   hmme_search_pairs_bi_device,     pass of xMotionEstimation (origin 2*org - pred_other, TEncSearch.cpp:3702-3712; window around the list's
  *   hmme_refine_pairs_bi_device, ... MV, TEncSearch.cpp:3726-3737) on whole pictures and picture pairs
+ *   hmme_predict_pairs_w_device,  <- the same in a slice with explicit weighted prediction (TComPrediction::motionCompensation,
+ *   hmme_search_pairs_bi_w_device,   TComPrediction.cpp:527-541 + addWeightUni for the other list, bApplyWeight with the searched list's
+ *   hmme_refine_pairs_bi_w_device    weight)
  *   hmme_plane_*           <- the padded reference plane calcMotionVectors reads
  *                             (TComPicYuv, TLibCommon/TComPicYuv.cpp:91-92, 214-262); hmme_plane_upload_* take what
  *                             TVideoIOYuv::read delivers (TVideoIOYuv.cpp:247, :680: 8-bit or 16-bit little-endian samples)
@@ -356,7 +359,7 @@ int hmme_refine_frame_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* 
  * rectangle the field's MVs describe) is the caller's business.  Lambda is the context's.  Array shapes, ctu_first / ctu_count, the limit
  * of 16 pairs, plane ownership and stream ordering are those of hmme_search_pairs_device / hmme_refine_pairs_device; others[i] must have
  * the size and bit depth of its pair and is ordered like a reference.  Origins and u16 copies live in the scratch of the weighted calls.
- * Combining this with explicit weighted prediction is not offered.
+ * In a slice with explicit weighted prediction the *_bi_w_* calls further down take their place.
  *
  * Refusal.  hmme_bipred_check decides from the NOMINAL sample range: with maxv = 2^bitDepth - 1 the origin lies in [-maxv, 2 * maxv] and is
  * staged with the bias maxv, so block and reference copy span [0, 3 * maxv]; span = 2 * maxv is the largest |origin - reference sample|:
@@ -387,6 +390,73 @@ int hmme_search_frame_bi(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane*
 int hmme_refine_frame_bi(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
                          const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q, const int16_t* pred_q, const int16_t* int_mv,
                          int use_hadamard, int16_t* out_qmv, uint32_t* out_cost);
+
+/* ---- bi-prediction with explicit weighted prediction on whole pictures and picture pairs ------------------------
+ * The calls above in a slice with explicit weighted prediction (HM: WeightedPredB), where the *_w and the _bi_ calls meet.  New entry points,
+ * no struct and no existing entry point changed, so HMME_ABI_VERSION stays 6.  Every pair carries TWO weights, both arrays of n_pairs in HOST
+ * memory, read before the call returns: wps[i] for refs[i] (the searched list) and other_wps[i] for others[i].  THIS TEXT PLUS THE CITATIONS IS
+ * THE RULE (paths below source/Lib of the reference).
+ *
+ * 1. The other list's prediction is what TComPrediction::motionCompensation writes in a slice whose PPS has getUseWP()
+ *    (TLibCommon/TComPrediction.cpp:527-541): xPredInterUni with bi = true leaves the 14-bit intermediate P -- no rounding, no clip, the
+ *    vertical stage with shift 6 and offset 0, the copy case (src << (14 - bd)) - 8192 --, then xWeightedPredictionUni -> addWeightUni
+ *    (TLibCommon/TComWeightPrediction.cpp:52-55, :133-180) with w0, offset, shift of getWpScaling (:250-262), the fields of hmme_weight:
+ *        shift' = wp.shift + max(2, 14 - bd)
+ *        round' = 1 << (shift' - 1)              (recomputed there: wp.round is NOT used)
+ *        pred   = ClipBD(((w0 * (P + 8192) + round') >> shift') + offset)
+ *    With w0 == 1 << shift and offset == 0 (whatever wp.round holds) this equals the bi = false prediction of hmme_predict_pairs_device at
+ *    every phase and bit depth -- nested floors: ((P + 8192 + 2^(head-1)) >> head) is the rounding of its vertical pass -- and the engine
+ *    relies on that: such a weight runs the unweighted prediction.
+ *    Quirk of the reference, kept: TComPrediction.cpp:529 tests the P-slice flag getUseWP(), not getWPBiPred().  In a B slice with
+ *    WeightedPredB = 1 and WeightedPredP = 0 the other list's prediction is therefore unweighted while the distortion is weighted; the two
+ *    weights are independent arguments here, and such a caller passes the identity for the other list.
+ * 2. The origin is 2 * org - pred, unclipped (TEncSearch.cpp:3702-3712, TComYuv::removeHighFreq); pred is clipped, so the origin lies in
+ *    [-maxv, 2 * maxv] as without weights.
+ * 3. The search runs with bApplyWeight and the SEARCHED list's weight (setWpScalingDistParam, TEncSearch.cpp:3740, :5594-5635): the integer
+ *    search prices xGetSADw -- every row, fp->fen not consulted, the prediction unclipped, the block sum >> (bd - 8) --, the refinement
+ *    xGetHADsw / xGetSADw; the window is centred on the list's own MV, MV bits are priced against the predictor (:3726-3737).
+ *
+ * hmme_predict_pairs_w_device / hmme_predict_frame_w: hmme_predict_pairs_device / hmme_predict_frame with one weight per picture; they write
+ * step 1's pred.
+ * hmme_search_pairs_bi_w_device: for pair i and CTU c what hmme_search_ctu_w returns for the block 2 * B - pred(others[i], field, other_wps[i]),
+ * refs[i] at the CTU origin, the window around d_center_q (NULL: the predictor) and the weight wps[i].  hmme_refine_pairs_bi_w_device: what
+ * hmme_refine_ctu_w returns at the same inputs.  Shapes, the limit of 16 pairs, mv_per_ctu 1 | 64, CTU sub-ranges, plane ownership and stream
+ * ordering are those of hmme_search_pairs_bi_device.  A pair whose other weight is the identity uses the unweighted prediction; a launch in
+ * which every weight of both lists is the identity IS hmme_search_pairs_bi_device / hmme_refine_pairs_bi_device with fen = 0.
+ *
+ * Refusal.  hmme_bipred_weight_check decides from the NOMINAL ranges: the origin in [-maxv, 2 * maxv], the reference in [0, maxv].  With
+ * wlo / whi the extremes of the searched list's weighted sample ((w0 * v + round) >> shift) + offset over that range,
+ * bias = max(maxv, -wlo) (what keeps origin and weighted plane unsigned) and span = max(2 * maxv - wlo, whi + maxv):
+ *   bit depth outside 8..12, a NULL weight, a shift outside 0..15 (either weight)          -> HMME_ERR_ARG
+ *   searched weight: a weighted sample beyond int16, or w0 * sample + round beyond 32 bits  -> HMME_ERR_UNSUPPORTED
+ *   searched weight: max(whi, 2 * maxv) + bias > 65535                                      -> HMME_ERR_UNSUPPORTED
+ *   searched weight: ((4096 * span) >> (bitDepth-8)) + 65535 >= 8 000 000                    -> HMME_ERR_UNSUPPORTED
+ *   searched weight, refine != 0: 4096 * span >= 2^24, or -- identity weights excepted --
+ *   |w0 * sample + round| >= 2^24                                                           -> HMME_ERR_UNSUPPORTED
+ *   other weight: |w0| * 40 960 + round' beyond int32 (P is a Pel, so P + 8192 lies within
+ *   [-24 576, 40 959]); nothing else, because the result is clipped                         -> HMME_ERR_UNSUPPORTED
+ * With the identity for both lists this is hmme_bipred_check: the 12-bit refinement stays refused for every weight.  A pure host function:
+ * no context, no GPU.  Every call below runs it for every pair first (refine = 1 in the refinement calls; the prediction calls apply the
+ * other weight's lines to their one weight) and launches NOTHING if one pair fails: it returns that code, hmme_last_error names the pair. */
+int hmme_bipred_weight_check(int bit_depth, const hmme_weight* wp, const hmme_weight* other_wp, int refine);
+int hmme_predict_pairs_w_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_pairs, const hmme_frame_params* fp, const hmme_weight* wps,
+                                const void* d_mv_field, int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream);
+int hmme_predict_frame_w(hmme_ctx* ctx, const hmme_plane* ref, const hmme_frame_params* fp, const hmme_weight* wp, const int16_t* mv_field,
+                         int mv_per_ctu, void* out, int out_stride);
+int hmme_search_pairs_bi_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others,
+                                  int n_pairs, const hmme_frame_params* fp, const hmme_weight* wps, const hmme_weight* other_wps, const void* d_other_mv,
+                                  int mv_per_ctu, const void* d_center_q, const void* d_pred_q, void* d_out_mv, void* d_out_sad, void* stream);
+int hmme_refine_pairs_bi_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others,
+                                  int n_pairs, const hmme_frame_params* fp, const hmme_weight* wps, const hmme_weight* other_wps, const void* d_other_mv,
+                                  int mv_per_ctu, const void* d_center_q, const void* d_pred_q, const void* d_int_mv, int use_hadamard, void* d_out_qmv,
+                                  void* d_out_cost, void* stream);
+/* synchronous, host arrays, one pair: the weighted siblings of hmme_search_frame_bi / hmme_refine_frame_bi */
+int hmme_search_frame_bi_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
+                           const hmme_weight* wp, const hmme_weight* other_wp, const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q,
+                           const int16_t* pred_q, int16_t* out_mv, uint32_t* out_sad);
+int hmme_refine_frame_bi_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
+                           const hmme_weight* wp, const hmme_weight* other_wp, const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q,
+                           const int16_t* pred_q, const int16_t* int_mv, int use_hadamard, int16_t* out_qmv, uint32_t* out_cost);
 
 /* ---- partition decision and motion field from the 593-slot tables ---------------------------------------------
  * The step between the uni-directional searches and the calls that take a motion field (hmme_predict_pairs_device, hmme_search_pairs_bi_device,
