@@ -16,6 +16,8 @@ Every .npz holds inputs and the reference's outputs -- data only.
   border.npz           TComPicYuv::create + extendPicBorder: small pictures in, the whole padded luma buffer out
   frac_bipred.npz      xPatternSearchFracDIF(..., biPred = true) on bi-prediction origins 2*org - pred_other (samples outside the
                        sample range, TEncSearch.cpp:3702-3712): `python tests/golden/gen_golden.py frac_bipred` makes this file alone
+  frac_edges.npz       xPatternSearchFracDIF at window corners, at the clipMv extremes of the picture corners and with predictors 8191 pels
+                       away (cases and seeded pictures: tests/refine_tables.py): `python tests/golden/gen_golden.py frac_edges`
   oracle_vs_ref.npz    the reference's answers to the questions of tests/test_oracle_vs_ref.py, in the order the tests ask them, recorded
                        by those tests against the live library: `python tests/golden/gen_golden.py oracle_vs_ref` makes this file alone
 """
@@ -386,6 +388,23 @@ def gen_frac_bipred(table):
     print("frac_bipred:", len(rows))
 
 
+def gen_frac_edges():
+    """xPatternSearchFracDIF where the interior cases of frac.npz do not reach: the cases of tests/refine_tables.py frac_edge_cases (window
+    corners at SR 128, the clipMv extremes of the four picture corners, predictors 8191 pels away).  The pictures are seeded
+    (refine_tables.full_picture / edge_picture), so the file holds the case rows and the reference's answers only."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import refine_tables as rt
+    rows = rt.frac_edge_cases()
+    planes = rt.edge_case_planes()
+    table = O.slot_table()
+    outs = [rt.run_edge_case(O, row, planes, table, use_ref=True) for row in rows]
+    lq = [R.ref_lambda_q16(int(r[-1]) / 10.0) for r in rows]
+    np.savez_compressed(os.path.join(HERE, "frac_edges.npz"), rows=rows, out=np.array(outs, np.int64), lambda_q16=np.array(lq, np.int64),
+                        columns=np.array(rt.EDGE_COLUMNS), out_columns=np.array("half_x half_y qter_x qter_y cost".split()),
+                        sizes=np.array([rt.FULL["w"], rt.FULL["h"], rt.EDGE_W, rt.EDGE_H], np.int64))
+    print("frac_edges:", len(rows))
+
+
 def gen_wp(table):
     """explicit weighted prediction (TEncSearch::setWpScalingDistParam, TEncSearch.cpp:5594-5635 -> TComRdCostWeightPrediction::xGetSADw):
     weighted SAD known answers for every width function, and whole 593-slot searches with bApplyWeight from the reference's own
@@ -488,6 +507,9 @@ def main():
     if sys.argv[1:] == ["frac_wp"]:
         gen_frac_wp(np.load(os.path.join(HERE, "slots.npz"))["table"])
         return
+    if sys.argv[1:] == ["frac_edges"]:
+        gen_frac_edges()
+        return
     table = gen_slots()
     gen_cost()
     gen_sad()
@@ -522,6 +544,7 @@ def main():
     gen_frac_bipred(table)
     gen_wp(table)
     gen_frac_wp(table)
+    gen_frac_edges()
     gen_slots_amp_off()
     gen_border()
 

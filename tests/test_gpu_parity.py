@@ -752,10 +752,14 @@ def test_tiny_and_sliver_pictures(engine, oracle_lib, w, h, sr, bd):
     with engine.plane(w, h, bd) as pc, engine.plane(w, h, bd) as pr:
         pc.upload_pel(cur, (m, m)); pr.upload_pel(ref, (m, m))
         mv, sad = engine.search_frame(pc, pr, sr, pred)
-        qmv, _ = engine.refine_frame(pc, pr, sr, mv, pred)
+        qmv, cost = engine.refine_frame(pc, pr, sr, mv, pred)
         assert np.abs(qmv.astype(np.int32) - 4 * mv.astype(np.int32)).max() <= 3
     ox, oy, osad = oracle_lib.search_frame(cur, ref, (m, m), w, h, sr, pred, engine.lambda_q16, 1, bd, n_threads=4)
     assert np.array_equal(mv[:, :, 0], ox) and np.array_equal(mv[:, :, 1], oy) and np.array_equal(sad, osad)
+    # the refinement of the winners: every slot of every CTU equals the oracle's xPatternSearchFracDIF
+    oq, oc = oracle_lib.refine_frame(cur, ref, (m, m), w, h, mv, pred, engine.lambda_q16, 1, bd, n_threads=4)
+    assert np.array_equal(qmv, oq), np.argwhere(qmv != oq)[:5]
+    assert np.array_equal(cost, oc), np.argwhere(cost != oc)[:5]
 
 
 @pytest.mark.parametrize("sr,fen,use_pred", [(65, 1, True), (100, 1, False), (128, 0, True)])
