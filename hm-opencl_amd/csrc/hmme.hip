@@ -1986,11 +1986,12 @@ int launch_predict(hmme_ctx* ctx, const hmme_plane* src, const int16_t* d_field,
   do {                                                                                                                                    \
     if (pw)                                                                                                                               \
       hipLaunchKernelGGL((hmme::me_predict_kernel<T, OUT, 1>), grid, block, 0, s, src->origin(), src->pitch, d_field, mv_per_ctu, first,  \
-                         src->width, src->height, src->bit_depth, cur_blocks, bias, dst, dst_ctu_x, dst_ctu_y, dst_pitch, *pw);           \
+                         src->width, src->height, src->bit_depth, cur_blocks, bias, dst, dst_ctu_x, dst_ctu_y, dst_pitch, *pw,            \
+                         hmme::MePredRefs<0>{});                                                                                          \
     else                                                                                                                                  \
       hipLaunchKernelGGL((hmme::me_predict_kernel<T, OUT, 0>), grid, block, 0, s, src->origin(), src->pitch, d_field, mv_per_ctu, first,  \
                          src->width, src->height, src->bit_depth, cur_blocks, bias, dst, dst_ctu_x, dst_ctu_y, dst_pitch,                 \
-                         hmme::MePredWp<0>{});                                                                                            \
+                         hmme::MePredWp<0>{}, hmme::MePredRefs<0>{});                                                                     \
   } while (0)
   if (src->bps == 1) { if (origin) HMME_PREDICT(uint8_t, 1); else HMME_PREDICT(uint8_t, 0); }
   else { if (origin) HMME_PREDICT(uint16_t, 1); else HMME_PREDICT(uint16_t, 0); }
@@ -2408,6 +2409,159 @@ int hmme_select_frame(hmme_ctx* ctx, int width, int height, const hmme_frame_par
   HIP_TRY(ctx, hipMemcpyAsync(out_field + (size_t)first * per * 2, d + o_field + (size_t)first * per * 4, (size_t)count * per * 4, hipMemcpyDeviceToHost, s));
   if (out_slot) HIP_TRY(ctx, hipMemcpyAsync(out_slot + (size_t)first * per, d + o_slot + (size_t)first * per * 2, (size_t)count * per * 2, hipMemcpyDeviceToHost, s));
   if (out_cost) HIP_TRY(ctx, hipMemcpyAsync(out_cost + first, d + o_ccost + (size_t)first * 4, (size_t)count * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  return HMME_OK;
+}
+
+// ---- reference picture per PU: the decision over all references' tables, and the prediction that follows it ---------------------------------
+int hmme_ref_idx_bits(int n_refs, int ref_idx) {   // TEncSearch.cpp:3030-3037
+  if (n_refs < 1 || n_refs > hmme::kMaxRefs || ref_idx < 0 || ref_idx >= n_refs) return -1;
+  if (n_refs == 1) return 0;
+  return ref_idx + 1 - (ref_idx == n_refs - 1 ? 1 : 0);
+}
+
+namespace {
+int select_refs_eval(const hmme_select_params* sel, int n_pics, int n_refs, const uint32_t* ref_cost, char* msg, size_t cap) {
+  const int bad = select_eval(sel, msg, cap);
+  if (bad) return bad;
+  if (n_refs < 1 || n_refs > hmme::kMaxRefs) { snprintf(msg, cap, "%d reference pictures outside 1..%d", n_refs, hmme::kMaxRefs); return HMME_ERR_ARG; }
+  if (n_pics < 1 || (long long)n_pics * n_refs > hmme::kMaxRefs) {
+    snprintf(msg, cap, "%d pictures x %d references: outside 1..%d table sets", n_pics, n_refs, hmme::kMaxRefs);
+    return HMME_ERR_ARG;
+  }
+  for (int r = 0; ref_cost && r < n_refs; ++r)
+    if (ref_cost[r] > (1u << 20)) { snprintf(msg, cap, "ref_cost[%d] = %u above 2^20", r, ref_cost[r]); return HMME_ERR_ARG; }
+  return HMME_OK;
+}
+}  // namespace
+
+int hmme_select_refs_check(const hmme_select_params* sel, int n_pics, int n_refs, const uint32_t* ref_cost) {
+  char msg[256];
+  return select_refs_eval(sel, n_pics, n_refs, ref_cost, msg, sizeof msg);
+}
+
+int hmme_select_refs_device(hmme_ctx* ctx, int width, int height, int n_pics, int n_refs, const hmme_frame_params* fp, const hmme_select_params* sel,
+                            const uint32_t* ref_cost, const void* d_mv, const void* d_cost, const void* d_pred_q, void* d_out_field, void* d_out_ref,
+                            void* d_out_slot, void* d_out_cost, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  char msg[256];
+  const int bad = select_refs_eval(sel, n_pics, n_refs, ref_cost, msg, sizeof msg);
+  if (bad) return fail(ctx, bad, "hmme_select_refs_device: %s", msg);
+  if (!fp || width < 1 || height < 1) return fail(ctx, HMME_ERR_ARG, "hmme_select_refs_device: null frame parameters, or a %d x %d picture", width, height);
+  if (!d_mv || !d_cost || !d_out_field || !d_out_ref) return fail(ctx, HMME_ERR_ARG, "hmme_select_refs_device: null table / field / reference buffer");
+  // the kernel moves MVs as dwords and, with four MVs per 8x8 block, two entries per store
+  if (((uintptr_t)d_mv & 3) || ((uintptr_t)d_cost & 3) || ((uintptr_t)d_out_field & 7) || ((uintptr_t)d_out_ref & 1) || ((uintptr_t)d_out_slot & 3) ||
+      ((uintptr_t)d_out_cost & 3) || ((uintptr_t)d_pred_q & 1))
+    return fail(ctx, HMME_ERR_ARG, "hmme_select_refs_device: misaligned buffer (tables and costs 4 bytes, field 8, references 2, slots 4)");
+  const int n_ctu = hmme_num_ctus(width, height);
+  const int first = fp->ctu_first, count = fp->ctu_count < 0 ? n_ctu - fp->ctu_first : fp->ctu_count;
+  if (first < 0 || count < 0 || first + count > n_ctu) return fail(ctx, HMME_ERR_ARG, "CTU range [%d, +%d) outside 0..%d", first, count, n_ctu);
+  if (count == 0) return HMME_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const hmme::MeSelect a = {sel->mv_per_ctu, sel->mv_unit, sel->price_mv, sel->part_mask, sel->min_depth, sel->max_depth, sel->cu_cost, sel->pu_cost};
+  hmme::MeRefCost rc = {};
+  for (int r = 0; ref_cost && r < n_refs; ++r) rc.c[r] = ref_cost[r];
+  const dim3 grid((unsigned)((count + 3) / 4), (unsigned)n_pics), block(256);
+  hipLaunchKernelGGL(hmme::me_select_refs_kernel, grid, block, 0, (hipStream_t)stream, (const uint32_t*)d_mv, (const uint32_t*)d_cost, (const int16_t*)d_pred_q,
+                     (uint32_t*)d_out_field, (uint8_t*)d_out_ref, (uint16_t*)d_out_slot, (uint32_t*)d_out_cost, a, rc, n_refs, width, height, n_ctu, first, count,
+                     ctx->lambda_q16);
+  HIP_TRY(ctx, hipGetLastError());
+  return HMME_OK;
+}
+
+int hmme_select_refs_frame(hmme_ctx* ctx, int width, int height, int n_refs, const hmme_frame_params* fp, const hmme_select_params* sel,
+                           const uint32_t* ref_cost, const int16_t* mv, const uint32_t* cost, const int16_t* pred_q, int16_t* out_field, uint8_t* out_ref,
+                           uint16_t* out_slot, uint32_t* out_cost) {
+  if (!ctx) return HMME_ERR_ARG;
+  char msg[256];
+  const int bad = select_refs_eval(sel, 1, n_refs, ref_cost, msg, sizeof msg);
+  if (bad) return fail(ctx, bad, "hmme_select_refs_frame: %s", msg);
+  if (!fp || width < 1 || height < 1 || !mv || !cost || !out_field || !out_ref)
+    return fail(ctx, HMME_ERR_ARG, "hmme_select_refs_frame: null argument, or a %d x %d picture", width, height);
+  const int n_ctu = hmme_num_ctus(width, height);
+  const int first = fp->ctu_first, count = fp->ctu_count < 0 ? n_ctu - fp->ctu_first : fp->ctu_count;
+  if (first < 0 || count < 0 || first + count > n_ctu) return fail(ctx, HMME_ERR_ARG, "CTU range [%d, +%d) outside 0..%d", first, count, n_ctu);
+  if (count == 0) return HMME_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t per = (size_t)sel->mv_per_ctu, tab = (size_t)n_refs * count * HMME_NUM_CTU_PARTS, preds = (size_t)n_refs * n_ctu * 4;
+  const size_t o_mv = 0, o_cost = o_mv + pad16(tab * 4), o_pred = o_cost + pad16(tab * 4), o_field = o_pred + pad16(preds);
+  const size_t o_ref = o_field + pad16((size_t)n_ctu * per * 4), o_slot = o_ref + pad16((size_t)n_ctu * per), o_ccost = o_slot + pad16((size_t)n_ctu * per * 2);
+  const size_t total = o_ccost + pad16((size_t)n_ctu * 4);
+  int rc = ensure(ctx, &ctx->d_sel, &ctx->sel_cap, total);
+  if (rc) return rc;
+  hipStream_t s = ctx->stream;
+  uint8_t* d = ctx->d_sel;
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_mv, mv, tab * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_cost, cost, tab * 4, hipMemcpyHostToDevice, s));
+  if (pred_q) HIP_TRY(ctx, hipMemcpyAsync(d + o_pred, pred_q, preds, hipMemcpyHostToDevice, s));
+  rc = hmme_select_refs_device(ctx, width, height, 1, n_refs, fp, sel, ref_cost, d + o_mv, d + o_cost, pred_q ? d + o_pred : nullptr, d + o_field, d + o_ref,
+                               out_slot ? d + o_slot : nullptr, out_cost ? d + o_ccost : nullptr, s);
+  if (rc) return rc;
+  // only the CTUs of the range come back: the caller's entries outside it keep their values
+  HIP_TRY(ctx, hipMemcpyAsync(out_field + (size_t)first * per * 2, d + o_field + (size_t)first * per * 4, (size_t)count * per * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipMemcpyAsync(out_ref + (size_t)first * per, d + o_ref + (size_t)first * per, (size_t)count * per, hipMemcpyDeviceToHost, s));
+  if (out_slot) HIP_TRY(ctx, hipMemcpyAsync(out_slot + (size_t)first * per, d + o_slot + (size_t)first * per * 2, (size_t)count * per * 2, hipMemcpyDeviceToHost, s));
+  if (out_cost) HIP_TRY(ctx, hipMemcpyAsync(out_cost + first, d + o_ccost + (size_t)first * 4, (size_t)count * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  return HMME_OK;
+}
+
+// me_predict_kernel<SrcT, 0, 0, 1>: one launch, every block from the plane its reference index names
+int hmme_predict_refs_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp, const void* d_mv_field,
+                             const void* d_ref_field, int mv_per_ctu, void* d_out, int out_pitch_bytes, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  const char* who = "hmme_predict_refs_device";
+  int rc = bi_check(ctx, who, fp, 0);
+  if (rc) return rc;
+  if (!refs || n_refs < 1 || n_refs > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d reference pictures outside 1..%d (or a null list)", who, n_refs, hmme::kMaxRefs);
+  if (!d_mv_field || !d_ref_field || !d_out || (mv_per_ctu != 1 && mv_per_ctu != 64))
+    return fail(ctx, HMME_ERR_ARG, "%s: null motion field / reference field / output image, or %d MVs per CTU (1 or 64)", who, mv_per_ctu);
+  for (int r = 0; r < n_refs; ++r)
+    if (!refs[r]) return fail(ctx, HMME_ERR_ARG, "%s: null plane", who);
+  if (out_pitch_bytes < refs[0]->width * refs[0]->bps) return fail(ctx, HMME_ERR_ARG, "%s: output pitch %d below a picture row", who, out_pitch_bytes);
+  hmme_frame_params f = *fp;
+  f.search_range = 1;   // not consulted: nothing is searched
+  hipStream_t s = (hipStream_t)stream;
+  PairLaunch pl;   // checks every plane: of this context, of one size, of fp's bit depth; each is ordered like a reference
+  rc = pairs_begin(ctx, refs, refs, n_refs, &f, s, &pl);
+  if (rc || pl.count == 0) return rc;
+  const hmme_plane* p0 = refs[0];
+  const hmme::MePredRefs<1> pr = {pl.refs, (const uint8_t*)d_ref_field, n_refs};
+  const dim3 grid((unsigned)pl.count), block(256);
+  if (p0->bps == 1)
+    hipLaunchKernelGGL((hmme::me_predict_kernel<uint8_t, 0, 0, 1>), grid, block, 0, s, p0->origin(), p0->pitch, (const int16_t*)d_mv_field, mv_per_ctu, pl.first,
+                       p0->width, p0->height, p0->bit_depth, nullptr, 0, (uint8_t*)d_out, 0, 0, out_pitch_bytes, hmme::MePredWp<0>{}, pr);
+  else
+    hipLaunchKernelGGL((hmme::me_predict_kernel<uint16_t, 0, 0, 1>), grid, block, 0, s, p0->origin(), p0->pitch, (const int16_t*)d_mv_field, mv_per_ctu, pl.first,
+                       p0->width, p0->height, p0->bit_depth, nullptr, 0, (uint8_t*)d_out, 0, 0, out_pitch_bytes, hmme::MePredWp<0>{}, pr);
+  if (hipGetLastError() != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "%s: the launch failed", who);
+  return pairs_end(ctx, refs, refs, n_refs, s, rc);
+}
+
+int hmme_predict_refs_frame(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp, const int16_t* mv_field,
+                            const uint8_t* ref_field, int mv_per_ctu, void* out, int out_stride) {
+  if (!ctx) return HMME_ERR_ARG;
+  const char* who = "hmme_predict_refs_frame";
+  int rc = bi_check(ctx, who, fp, 0);
+  if (rc) return rc;
+  if (!refs || n_refs < 1 || n_refs > hmme::kMaxRefs || !refs[0]) return fail(ctx, HMME_ERR_ARG, "%s: %d reference pictures outside 1..%d (or a null plane)", who, n_refs, hmme::kMaxRefs);
+  if (!mv_field || !ref_field || !out || (mv_per_ctu != 1 && mv_per_ctu != 64)) return fail(ctx, HMME_ERR_ARG, "%s: null argument, or %d MVs per CTU (1 or 64)", who, mv_per_ctu);
+  const hmme_plane* ref = refs[0];
+  if (ref->ctx != ctx) return fail(ctx, HMME_ERR_ARG, "plane belongs to another context (planes are used with the context that created them)");
+  if (out_stride < ref->width) return fail(ctx, HMME_ERR_ARG, "%s: output stride %d below the picture width", who, out_stride);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t blocks = (size_t)ref->n_ctu * mv_per_ctu, field_bytes = pad16(sizeof(int16_t) * 2 * blocks), row = (size_t)ref->width * ref->bps;
+  rc = ensure(ctx, &ctx->d_bi[0], &ctx->bi_cap[0], field_bytes + blocks);   // the motion field, behind it the reference field
+  if (rc == HMME_OK) rc = ensure(ctx, &ctx->d_bi[1], &ctx->bi_cap[1], row * ref->height);
+  if (rc) return rc;
+  hipStream_t s = ctx->stream;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_bi[0], mv_field, sizeof(int16_t) * 2 * blocks, hipMemcpyHostToDevice, s));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_bi[0] + field_bytes, ref_field, blocks, hipMemcpyHostToDevice, s));
+  // the caller's image travels both ways: samples outside the CTU range, and of blocks without a reference, come back as they were
+  HIP_TRY(ctx, hipMemcpy2DAsync(ctx->d_bi[1], row, out, (size_t)out_stride * ref->bps, row, ref->height, hipMemcpyHostToDevice, s));
+  rc = hmme_predict_refs_device(ctx, refs, n_refs, fp, ctx->d_bi[0], ctx->d_bi[0] + field_bytes, mv_per_ctu, ctx->d_bi[1], (int)row, s);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemcpy2DAsync(out, (size_t)out_stride * ref->bps, ctx->d_bi[1], row, row, ref->height, hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipStreamSynchronize(s));
   return HMME_OK;
 }

@@ -2198,13 +2198,20 @@ __constant__ int kLumaTaps[4][8] = {{0, 0, 0, 64, 0, 0, 0, 0}, {-1, 4, -10, 58, 
 //            int32 (hmme_bipred_weight_check); the offset is added in 64 bits, so any int offset is exact before the clip.  With
 //            w0 == 1 << wp.shift and offset 0 this IS the WP = 0 result (nested floors), which is why identity weights run WP = 0.
 //            The weight travels in the kernel arguments; WP = 0 takes an empty struct and compiles to what it did without it.
+//   REFS = 1: a reference picture per block (hmme_predict_refs_device): ref_field uint8 [n_ctu][mv_per_ctu] names, beside every MV, the
+//            plane of `set` the block reads (all of one pitch; ref_origin is not used).  The index is the same for the whole wave -- a
+//            wave handles one 8x8 block at a time -- so the choice of the source base is a scalar one.  A block whose index is >= n_refs
+//            (0xFF: no CU covers it) is not live: it reads no plane and writes nothing, and still meets both barriers of its iteration.
+//            REFS = 0 takes an empty struct and compiles to what it did without it.
 template <int WP> struct MePredWp {};
 template <> struct MePredWp<1> { int w0, round, shift, offset; };   // round / shift: addWeightUni's round' and shift'
-template <typename SrcT, int OUT, int WP = 0>
+template <int REFS> struct MePredRefs {};
+template <> struct MePredRefs<1> { RefSet set; const uint8_t* ref_field; int n_refs; };
+template <typename SrcT, int OUT, int WP = 0, int REFS = 0>
 __global__ void __launch_bounds__(256)
 me_predict_kernel(const uint8_t* __restrict__ ref_origin, int ref_pitch, const int16_t* __restrict__ mv_field, int mv_per_ctu, int ctu_first,
                   int pic_w, int pic_h, int bit_depth, const uint8_t* __restrict__ cur_blocks, int bias, uint8_t* __restrict__ dst,
-                  long dst_ctu_x, long dst_ctu_y, int dst_pitch, MePredWp<WP> wp) {
+                  long dst_ctu_x, long dst_ctu_y, int dst_pitch, MePredWp<WP> wp, MePredRefs<REFS> refs) {
   __shared__ int16_t patch[4][15 * 16];
   __shared__ int16_t mid[4][15 * 8];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -2220,9 +2227,15 @@ me_predict_kernel(const uint8_t* __restrict__ ref_origin, int ref_pitch, const i
     const int16_t* mv = mv_field + ((long)ctu * mv_per_ctu + (mv_per_ctu == 1 ? 0 : b)) * 2;
     int mx = mv[0], my = mv[1];
     clip_mv_q(mx, my, cu_x, cu_y, pic_w, pic_h);
-    const bool live = OUT == 1 || (cu_x + bx < pic_w && cu_y + by < pic_h);   // wave-uniform
+    bool live = OUT == 1 || (cu_x + bx < pic_w && cu_y + by < pic_h);   // wave-uniform
+    const uint8_t* origin = ref_origin;
+    if constexpr (REFS) {
+      const int ri = __builtin_amdgcn_readfirstlane((int)refs.ref_field[(long)ctu * mv_per_ctu + (mv_per_ctu == 1 ? 0 : b)]);
+      live = live && ri < refs.n_refs;
+      origin = refs.set.base[ri < refs.n_refs ? ri : 0];
+    }
     if (live) {
-      const uint8_t* src = ref_origin + (long)(cu_y + by + (my >> 2) - 3) * ref_pitch + (long)(cu_x + bx + (mx >> 2) - 3) * (long)sizeof(SrcT);
+      const uint8_t* src = origin + (long)(cu_y + by + (my >> 2) - 3) * ref_pitch + (long)(cu_x + bx + (mx >> 2) - 3) * (long)sizeof(SrcT);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const int e = lane + 64 * k, r = e / 15, c = e - r * 15;
@@ -2328,8 +2341,9 @@ struct MeSelectState {
 // One level of the bottom-up decision, for the lane's ancestor CU at depth D.  Every lane of the CU computes the CU's own best redundantly
 // (LDS broadcast reads, no divergence), the sum of the four children is a quad reduction over the lanes that differ in bit (2 - D) of the
 // block's column and row.  Called for D = 3, 2, 1, 0: a shallower leaf overrides a deeper one, so no decision has to be pushed back down.
-template <int D>
-__device__ __forceinline__ void me_select_level(const MeSelect& a, const uint32_t* s_cost, const uint32_t* s_mv, uint32_t lambda_q16, int pred_x, int pred_y,
+// CostT: the element type of the slot costs -- uint32_t table costs (me_select_kernel) or the 64-bit merged costs of me_select_refs_kernel.
+template <int D, typename CostT>
+__device__ __forceinline__ void me_select_level(const MeSelect& a, const CostT* s_cost, const uint32_t* s_mv, uint32_t lambda_q16, int pred_x, int pred_y,
                                                 int bx, int by, int ctu_x, int ctu_y, int pic_w, int pic_h, MeSelectState& st) {
   if (D > a.max_depth) return;   // wave-uniform
   constexpr int s = 64 >> D;
@@ -2421,6 +2435,106 @@ me_select_kernel(const uint32_t* __restrict__ mv_tab, const uint32_t* __restrict
       }
       const long e = o * 256 + (2 * by + j) * 16 + 2 * bx;   // even: the pair of entries is 8-byte (MVs) / 4-byte (slots) aligned
       *(uint2*)(out_field + e) = make_uint2(mv[0], mv[1]);
+      if (out_slot) *(uint32_t*)(out_slot + e) = (uint32_t)slot[0] | (uint32_t)slot[1] << 16;
+    }
+  }
+}
+
+// ---- reference picture per PU (hmme_select_refs_device; the rule: include/hmme.h) --------------------------------------------------------
+// the caller's price of each reference index, as the kernel takes it
+struct MeRefCost { uint32_t c[kMaxRefs]; };
+
+// me_select_kernel with a reference dimension in front: one wave per CTU, four CTUs per workgroup; blockIdx.y = picture.  The tables are
+// those of one multi-reference launch -- mv_tab int16 [n_pics][n_refs][ctu_count][593][2] as dwords, cost_tab uint32 of the same shape,
+// pred_q int16 [n_pics][n_refs][n_ctu][2] or null.  A lane owns the slots lane, lane + 64, ... (ten, the last one in 17 lanes only) and
+// walks the references with coalesced loads straight from the tables, its slots' running best -- the priced cost in 64 bits, the MV
+// dword, the reference -- in registers: no LDS traffic, no atomic and no cross-lane step in the reference loop; the predictor and the
+// price of a reference are wave-uniform.  The comparison is strict in the order 0, 1, ...: the lowest index wins ties
+// (TEncSearch.cpp:3086).  Behind the last reference the merged slots go to LDS (7.6 KB per CTU with the costs in 64 bits: unsaturated)
+// and the level functions of me_select_kernel decide on them, the MV cost -- already inside the merged cost, against each reference's own
+// predictor -- switched off.  Stores as in me_select_kernel; out_ref: uint8 [n_pics][n_ctu][per], a wave's bytes one run of 64 with one
+// MV per 8x8 block, pairs of them as one 16-bit store with four; 0xFF where no CU covers the block.  Bandwidth-sized like its sibling:
+// n_refs x 7.1 KB in per CTU, under 2 KB out.
+__global__ void __launch_bounds__(256)
+me_select_refs_kernel(const uint32_t* __restrict__ mv_tab, const uint32_t* __restrict__ cost_tab, const int16_t* __restrict__ pred_q,
+                      uint32_t* __restrict__ out_field, uint8_t* __restrict__ out_ref, uint16_t* __restrict__ out_slot, uint32_t* __restrict__ out_cost,
+                      MeSelect a, MeRefCost ref_cost, int n_refs, int pic_w, int pic_h, int n_ctu, int ctu_first, int ctu_count, uint32_t lambda_q16) {
+  constexpr int kOwn = (kParts + 63) / 64;   // slots per lane
+  __shared__ uint64_t s_cost[4][kParts + 3];
+  __shared__ uint32_t s_mv[4][kParts + 3];
+  __shared__ uint8_t s_ref[4][kParts + 3];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int c = blockIdx.x * 4 + wave, pic = blockIdx.y;
+  const bool live = c < ctu_count;   // wave-uniform
+  const int ctu = ctu_first + c;
+  if (live) {
+    uint64_t best[kOwn];
+    uint32_t best_mv[kOwn];
+    int best_ref[kOwn];
+#pragma unroll 1
+    for (int r = 0; r < n_refs; ++r) {
+      const long set = (long)pic * n_refs + r, base = (set * ctu_count + c) * kParts, po = (set * n_ctu + ctu) * 2;
+      const int pred_x = pred_q ? pred_q[po] : 0, pred_y = pred_q ? pred_q[po + 1] : 0;
+      const uint32_t rc = ref_cost.c[r];
+#pragma unroll
+      for (int k = 0; k < kOwn; ++k) {
+        const int i = lane + 64 * k;
+        if (i >= kParts) continue;
+        const uint32_t m = mv_tab[base + i];
+        uint64_t p = (uint64_t)cost_tab[base + i] + rc;
+        if (a.price_mv) {
+          const int vx = (int16_t)(m & 0xffffu), vy = (int16_t)(m >> 16);
+          p += a.mv_unit ? me_mv_cost(lambda_q16, vx, vy, pred_x, pred_y) : me_mv_cost_q(lambda_q16, vx, vy, pred_x, pred_y);
+        }
+        if (r == 0 || p < best[k]) { best[k] = p; best_mv[k] = m; best_ref[k] = r; }   // strict: the lower index wins ties
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kOwn; ++k) {
+      const int i = lane + 64 * k;
+      if (i >= kParts) continue;
+      s_cost[wave][i] = best[k];
+      s_mv[wave][i] = best_mv[k];
+      s_ref[wave][i] = (uint8_t)best_ref[k];
+    }
+  }
+  __syncthreads();
+  if (!live) return;
+  const int ctus_x = (pic_w + 63) >> 6;
+  const int ctu_x = (ctu % ctus_x) * 64, ctu_y = (ctu / ctus_x) * 64;
+  const long o = (long)pic * n_ctu + ctu;
+  const int bx = lane & 7, by = lane >> 3;
+  MeSelect merged = a;
+  merged.price_mv = 0;   // priced above, per reference: not a second time
+  MeSelectState st = {0, -1, 0};
+  me_select_level<3>(merged, s_cost[wave], s_mv[wave], lambda_q16, 0, 0, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
+  me_select_level<2>(merged, s_cost[wave], s_mv[wave], lambda_q16, 0, 0, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
+  me_select_level<1>(merged, s_cost[wave], s_mv[wave], lambda_q16, 0, 0, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
+  me_select_level<0>(merged, s_cost[wave], s_mv[wave], lambda_q16, 0, 0, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
+  if (lane == 0 && out_cost) out_cost[o] = st.resolved > 0xffffffffull ? 0xffffffffu : (uint32_t)st.resolved;
+  auto field_mv = [&](int slot) -> uint32_t {   // as in me_select_kernel
+    const uint32_t m = s_mv[wave][slot];
+    return a.mv_unit ? (m << 2) & 0xfffcfffcu : m;
+  };
+  if (a.per == 64) {
+    const int slot = st.leaf_depth < 0 ? 0xffff : me_select_pu_slot_at(st.leaf_depth, st.leaf_ps, bx * 8, by * 8);
+    out_field[o * 64 + lane] = slot == 0xffff ? 0u : field_mv(slot);
+    out_ref[o * 64 + lane] = slot == 0xffff ? (uint8_t)0xff : s_ref[wave][slot];
+    if (out_slot) out_slot[o * 64 + lane] = (uint16_t)slot;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {   // the block's two rows of two 4x4 blocks
+      int slot[2];
+      uint32_t mv[2], ref[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        slot[i] = st.leaf_depth < 0 ? 0xffff : me_select_pu_slot_at(st.leaf_depth, st.leaf_ps, bx * 8 + 4 * i, by * 8 + 4 * j);
+        mv[i] = slot[i] == 0xffff ? 0u : field_mv(slot[i]);
+        ref[i] = slot[i] == 0xffff ? 0xffu : (uint32_t)s_ref[wave][slot[i]];
+      }
+      const long e = o * 256 + (2 * by + j) * 16 + 2 * bx;   // even: 8-byte (MVs) / 4-byte (slots) / 2-byte (references) aligned pairs
+      *(uint2*)(out_field + e) = make_uint2(mv[0], mv[1]);
+      *(uint16_t*)(out_ref + e) = (uint16_t)(ref[0] | ref[1] << 8);
       if (out_slot) *(uint32_t*)(out_slot + e) = (uint32_t)slot[0] | (uint32_t)slot[1] << 16;
     }
   }

@@ -29,6 +29,8 @@ SYMBOLS = ["hmme_create", "hmme_destroy", "hmme_last_error", "hmme_device_info",
            "hmme_bipred_weight_check", "hmme_predict_pairs_w_device", "hmme_predict_frame_w", "hmme_search_pairs_bi_w_device",
            "hmme_refine_pairs_bi_w_device", "hmme_search_frame_bi_w", "hmme_refine_frame_bi_w",
            "hmme_slot_key", "hmme_select_check", "hmme_select_pairs_device", "hmme_select_frame",
+           "hmme_ref_idx_bits", "hmme_select_refs_check", "hmme_select_refs_device", "hmme_select_refs_frame",
+           "hmme_predict_refs_device", "hmme_predict_refs_frame",
            "hmme_plane_stats", "hmme_wp_estimate"]
 # test / measurement entry points (include/hmme_test.h): not part of the boundary
 TEST_SYMBOLS = ["hmme_test_time_search_kernel", "hmme_test_device_address", "hmme_test_frac_deal", "hmme_test_tail_plan", "hmme_test_time_weight_passes", "hmme_test_time_bipred_origin",
@@ -171,6 +173,12 @@ def load():
     L.hmme_select_check.argtypes = [C.POINTER(SelectParams)]
     L.hmme_select_pairs_device.argtypes = [vp, i, i, i, C.POINTER(FrameParams), C.POINTER(SelectParams), vp, vp, vp, vp, vp, vp, vp]
     L.hmme_select_frame.argtypes = [vp, i, i, C.POINTER(FrameParams), C.POINTER(SelectParams), vp, vp, vp, vp, vp, vp]
+    L.hmme_ref_idx_bits.argtypes = [i, i]
+    L.hmme_select_refs_check.argtypes = [C.POINTER(SelectParams), i, i, vp]
+    L.hmme_select_refs_device.argtypes = [vp, i, i, i, i, C.POINTER(FrameParams), C.POINTER(SelectParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.hmme_select_refs_frame.argtypes = [vp, i, i, i, C.POINTER(FrameParams), C.POINTER(SelectParams), vp, vp, vp, vp, vp, vp, vp, vp]
+    L.hmme_predict_refs_device.argtypes = [vp, C.POINTER(vp), i, C.POINTER(FrameParams), vp, vp, i, vp, i, vp]
+    L.hmme_predict_refs_frame.argtypes = [vp, C.POINTER(vp), i, C.POINTER(FrameParams), vp, vp, i, vp, i]
     L.hmme_plane_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.hmme_wp_estimate.argtypes = [vp, vp, C.POINTER(vp), i, i, C.POINTER(Weight), C.POINTER(WpInfo)]
     L.hmme_test_time_wp_estimate_passes.argtypes = [vp, vp, C.POINTER(vp), i, C.POINTER(Weight), vp, i, C.POINTER(C.c_float), C.POINTER(C.c_float)]
@@ -674,6 +682,71 @@ class Engine:
                                              field.ctypes.data, slot.ctypes.data, ctu_cost.ctypes.data))
         return field, slot, ctu_cost
 
+    # ---- the reference picture per PU, and the prediction from it (include/hmme.h, "the reference picture per PU") ----
+    def select_refs_device(self, width, height, n_pics, n_refs, fp, sel, ref_cost, d_mv, d_cost, d_pred, d_field, d_ref, d_slot=None, d_ctu_cost=None,
+                           stream=0):
+        """hmme_select_refs_device: the tables of n_pics pictures x n_refs references (device, [n_pics, n_refs, count, 593, ...] as a multi-reference
+        search / refinement with the same fp wrote them) -> motion field int16[n_pics, n_ctu, mv_per_ctu, 2], reference indices uint8[n_pics, n_ctu,
+        mv_per_ctu], covering slots uint16 of that shape and CTU costs uint32[n_pics, n_ctu] (device addresses; d_slot / d_ctu_cost may be None).
+        ref_cost: n_refs host integers, or None for zeros"""
+        self._check(self.L.hmme_select_refs_device(self.h, int(width), int(height), int(n_pics), int(n_refs), C.byref(fp), C.byref(sel),
+                                                   _ref_cost(ref_cost, n_refs), d_mv, d_cost, d_pred, d_field, d_ref, d_slot, d_ctu_cost, stream))
+
+    def select_refs_frame(self, width, height, sel, mv, cost, ref_cost=None, pred_q=None, ctu_first=0, ctu_count=-1, field=None, ref=None, slot=None,
+                          ctu_cost=None):
+        """hmme_select_refs_frame: one picture, host arrays.  mv int16[n_refs, count, 593, 2], cost uint32[n_refs, count, 593], pred_q
+        int16[n_refs, n_ctu, 2] or None -> (field int16[n_ctu, mv_per_ctu, 2], ref uint8[n_ctu, mv_per_ctu], slot uint16[n_ctu, mv_per_ctu],
+        ctu_cost uint32[n_ctu]); entries outside the CTU range keep the values of the arrays passed in (zeros when none is)"""
+        n = self.L.hmme_num_ctus(width, height)
+        count = n - ctu_first if ctu_count < 0 else ctu_count
+        fp = FrameParams(1, 0, 8, ctu_first, count)
+        per = int(sel.mv_per_ctu)
+        mv = np.ascontiguousarray(mv, dtype=np.int16)
+        cost = np.ascontiguousarray(cost, dtype=np.uint32)
+        n_refs = mv.shape[0]
+        assert mv.shape == (n_refs, count, NUM_PARTS, 2) and cost.shape == (n_refs, count, NUM_PARTS)
+        pq = pptr = None
+        if pred_q is not None:
+            pq = np.ascontiguousarray(pred_q, dtype=np.int16)
+            assert pq.shape == (n_refs, n, 2)
+            pptr = pq.ctypes.data
+        field = np.zeros((n, per, 2), np.int16) if field is None else field
+        ref = np.zeros((n, per), np.uint8) if ref is None else ref
+        slot = np.zeros((n, per), np.uint16) if slot is None else slot
+        ctu_cost = np.zeros(n, np.uint32) if ctu_cost is None else ctu_cost
+        for a, dt, shape in ((field, np.int16, (n, per, 2)), (ref, np.uint8, (n, per)), (slot, np.uint16, (n, per)), (ctu_cost, np.uint32, (n,))):
+            assert a.dtype == dt and a.shape == shape and a.flags.c_contiguous
+        self._check(self.L.hmme_select_refs_frame(self.h, int(width), int(height), n_refs, C.byref(fp), C.byref(sel), _ref_cost(ref_cost, n_refs),
+                                                  mv.ctypes.data, cost.ctypes.data, pptr, field.ctypes.data, ref.ctypes.data, slot.ctypes.data,
+                                                  ctu_cost.ctypes.data))
+        return field, ref, slot, ctu_cost
+
+    def predict_refs_device(self, refs, fp, d_mv_field, d_ref_field, mv_per_ctu, d_out, out_pitch_bytes, stream=0):
+        """hmme_predict_refs_device: the luma prediction of one picture, every block from the plane of `refs` its reference index names
+        (d_ref_field uint8[n_ctu, mv_per_ctu]; blocks with an index >= len(refs) are not written); d_out = the device image"""
+        ra = (C.c_void_p * len(refs))(*[r.h for r in refs])
+        self._check(self.L.hmme_predict_refs_device(self.h, ra, len(refs), C.byref(fp), d_mv_field, d_ref_field, int(mv_per_ctu), d_out,
+                                                    int(out_pitch_bytes), stream))
+
+    def predict_refs_frame(self, refs, mv_field, ref_field, out=None, ctu_first=0, ctu_count=-1):
+        """hmme_predict_refs_frame: motion-compensated luma prediction of one picture from several references -> [height, width] array of the
+        planes' sample type (u8 / u16).  mv_field: int16[n_ctu, 2] or [n_ctu, 1 | 64, 2] quarter pels; ref_field: uint8[n_ctu] or [n_ctu, 1 | 64],
+        the plane of `refs` per block; `out` (same shape and type) keeps its samples outside the CTU range and in blocks whose index is
+        >= len(refs)"""
+        r0 = refs[0]
+        n = self.L.hmme_num_ctus(r0.width, r0.height)
+        f, per = self._field(mv_field, n)
+        rf = np.ascontiguousarray(ref_field, dtype=np.uint8).reshape(n, -1)
+        assert rf.shape == (n, per)
+        dt = np.uint8 if r0.bit_depth == 8 else np.uint16
+        if out is None:
+            out = np.zeros((r0.height, r0.width), dt)
+        assert out.dtype == dt and out.shape == (r0.height, r0.width) and out.flags.c_contiguous
+        fp = FrameParams(1, 0, r0.bit_depth, ctu_first, ctu_count)
+        ra = (C.c_void_p * len(refs))(*[r.h for r in refs])
+        self._check(self.L.hmme_predict_refs_frame(self.h, ra, len(refs), C.byref(fp), f.ctypes.data, rf.ctypes.data, per, out.ctypes.data, out.shape[1]))
+        return out
+
     # ---- estimating explicit weighted-prediction parameters (include/hmme.h, "estimating explicit weighted-prediction parameters") ----
     def plane_stats(self, plane):
         """hmme_plane_stats: xCalcACDCParamSlice of one picture -> (dc_sum, ac) = (sum of the samples, sum of |sample - normDC|) over the picture
@@ -754,6 +827,26 @@ def bipred_weight_check(bit_depth, wp, other_wp, refine=False):
 def select_check(sel):
     """hmme_select_check: 0, or HMME_ERR_ARG when a field of the SelectParams lies outside its range (pure host arithmetic: needs no GPU)"""
     return int(load().hmme_select_check(C.byref(sel)))
+
+
+def _ref_cost(ref_cost, n_refs):
+    """n_refs host uint32 for the ref_cost argument of the hmme_select_refs_* calls (None: a null pointer = zeros)"""
+    if ref_cost is None:
+        return None
+    assert len(ref_cost) == n_refs
+    return (C.c_uint32 * max(n_refs, 1))(*[int(v) for v in ref_cost])
+
+
+def ref_idx_bits(n_refs, ref_idx):
+    """hmme_ref_idx_bits: HM's bits of reference index ref_idx in a list of n_refs (TEncSearch.cpp:3030-3037); -1 outside 0 <= ref_idx < n_refs <= 16"""
+    return int(load().hmme_ref_idx_bits(int(n_refs), int(ref_idx)))
+
+
+def select_refs_check(sel, n_pics, n_refs, ref_cost=None):
+    """hmme_select_refs_check: 0, or HMME_ERR_ARG when the SelectParams, the number of pictures / references or a ref_cost lies outside its
+    range (pure host arithmetic: needs no GPU).  ref_cost: a sequence of integers (any length: n_refs of them are read) or None"""
+    rc = None if ref_cost is None else (C.c_uint32 * max(len(ref_cost), 16))(*[int(v) for v in ref_cost])   # at most 16 are ever read
+    return int(load().hmme_select_refs_check(C.byref(sel), int(n_pics), int(n_refs), rc))
 
 
 def ocl_compat_params(lt_x, lt_y, sr):

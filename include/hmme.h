@@ -518,6 +518,70 @@ int hmme_select_pairs_device(hmme_ctx* ctx, int width, int height, int n_pairs, 
 int hmme_select_frame(hmme_ctx* ctx, int width, int height, const hmme_frame_params* fp, const hmme_select_params* sel, const int16_t* mv,
                       const uint32_t* cost, const int16_t* pred_q, int16_t* out_field, uint16_t* out_slot, uint32_t* out_cost);
 
+/* ---- the reference picture per PU, and the prediction from it ----------------------------------------------------
+ * hmme_search_frame_multi_device / hmme_refine_frame_multi_device (and hmme_search_pairs_device in general) leave one 593-slot table per
+ * reference picture and CTU; an encoder needs, per PU, the best (refIdx, MV) of the list -- the loop over iRefIdxTemp in
+ * TEncSearch::predInterSearch (source/Lib/TLibEncoder/TEncSearch.cpp:3027-3094) -- and the partition decided on those winners.  The calls
+ * below do both on the device and predict from the result.  New entry points only; no struct and no existing entry point changed, so
+ * HMME_ABI_VERSION stays 6.  THIS TEXT PLUS THE CITATIONS IS THE RULE.
+ *
+ * Inputs of the decision.  d_mv: int16[n_pics][n_refs][count][593][2], d_cost: uint32[n_pics][n_refs][count][593] -- exactly what
+ * hmme_search_frame_multi_device / hmme_refine_frame_multi_device write for one picture (n_pics = 1), and what hmme_search_pairs_device /
+ * hmme_refine_pairs_device write when their pairs are ordered picture-major (pair = picture * n_refs + reference).  d_pred_q:
+ * int16[n_pics][n_refs][n_ctu][2], quarter pels, one predictor per reference and CTU as the multi-reference search takes them; NULL: (0,0).
+ * ref_cost: HOST array of n_refs prices, one per reference index, read before the call returns; NULL: all zero.
+ * Limits: n_refs in 1..16, n_pics >= 1, n_pics * n_refs <= 16, every ref_cost[r] <= 2^20; sel as hmme_select_check has it, unchanged.
+ * hmme_select_refs_check (a pure host function: no context, no GPU) returns HMME_ERR_ARG for anything outside these limits; the calls run
+ * it first and launch NOTHING when it fails.
+ *
+ * Rule.
+ *   1. The priced cost of slot s in reference r is cost[r][s], plus -- if sel->price_mv -- HM's MV cost of mv[r][s] against reference r's
+ *      OWN predictor (the two formulas of price_mv above, for mv_unit 1 / 0, the product wrapping in 32 bits), plus ref_cost[r]; the sum
+ *      is carried in 64 bits.
+ *   2. Slot s takes the reference with the smallest priced cost; comparison is strict '<' in the order r = 0, 1, ..., so the lowest index
+ *      wins ties, as a later reference wins in HM only on uiCostTemp < uiCost[iRefList] (:3086).  Every slot of a CTU chooses on its own:
+ *      the two PUs of one CU may use different references, as in HM.
+ *   3. The decision of hmme_select_pairs_device, its steps 1-5 word for word, runs on the merged slots with the merged priced cost (64
+ *      bits, not saturated) standing for "slot cost"; the MV cost is not applied a second time.
+ *   4. Outputs -- only the entries of the CTUs in [ctu_first, ctu_first + ctu_count) are written, as in the select call:
+ *        d_out_field  int16[n_pics][n_ctu][mv_per_ctu][2]   the winner's MV (<< 2 if mv_unit), (0,0) for blocks of CUs that do not exist
+ *        d_out_ref    uint8[n_pics][n_ctu][mv_per_ctu]      the winner's reference index, 0xFF for blocks of CUs that do not exist; not NULL
+ *        d_out_slot   uint16[n_pics][n_ctu][mv_per_ctu]     the covering slot, 0xFFFF likewise; may be NULL
+ *        d_out_cost   uint32[n_pics][n_ctu]                 the CTU's cost, saturated at UINT32_MAX; may be NULL
+ * With n_refs = 1 and ref_cost = {0} field, slots and costs are bit for bit those of hmme_select_pairs_device and every existing block has
+ * reference 0.
+ *
+ * Reference-index bits.  hmme_ref_idx_bits(n_refs, r) is HM's count (:3030-3037): 0 when n_refs == 1, otherwise r + 1, minus 1 when
+ * r == n_refs - 1 (the last index needs no terminating bin); -1 for arguments outside 0 <= r < n_refs <= 16.  A caller who wants HM's price
+ * passes ref_cost[r] = (lambda_q16 * bits) >> 16.  HM floors getCost ONCE over the summed bits -- MV bits and reference-index bits together
+ * (the closing lines of TEncSearch::xMotionEstimation) -- so an additive ref_cost can differ from HM's total by at most 1.  ref_cost is the
+ * caller's model, like cu_cost / pu_cost.
+ *
+ * hmme_select_refs_device: asynchronous on `stream`; like hmme_select_pairs_device it takes no planes, consults of fp only ctu_first /
+ * ctu_count, uses no scratch of the context and is ordered like any kernel of the caller on `stream`.  Buffers: tables, costs and slots
+ * 4-byte aligned, the field 8-byte, the reference indices 2-byte.  hmme_select_refs_frame: synchronous, host arrays of the same shapes with
+ * n_pics = 1, on the context's private stream; entries outside the CTU range keep their values.
+ *
+ * Prediction.  hmme_predict_refs_device is hmme_predict_pairs_device for ONE picture, except that the block of every MV reads the plane
+ * refs[d_ref_field[ctu][block]]: d_mv_field int16[n_ctu][mv_per_ctu][2], d_ref_field uint8[n_ctu][mv_per_ctu], mv_per_ctu 1 | 64 (what the
+ * decision writes with mv_per_ctu = 64), d_out one device image of out_pitch_bytes per row.  A block whose index is >= n_refs -- 0xFF
+ * included -- is not written and reads nothing.  All refs (1..16) must have one size and fp's bit depth and belong to the context; each is
+ * ordered across streams like any reference.  Unweighted only: a variant with one explicit weight per reference is out of scope.
+ * hmme_predict_refs_frame: synchronous, host motion field, reference field and image (out_stride in samples; samples outside the CTU
+ * range and of blocks without a reference keep their values). */
+int hmme_ref_idx_bits(int n_refs, int ref_idx);
+int hmme_select_refs_check(const hmme_select_params* sel, int n_pics, int n_refs, const uint32_t* ref_cost);
+int hmme_select_refs_device(hmme_ctx* ctx, int width, int height, int n_pics, int n_refs, const hmme_frame_params* fp, const hmme_select_params* sel,
+                            const uint32_t* ref_cost, const void* d_mv, const void* d_cost, const void* d_pred_q, void* d_out_field, void* d_out_ref,
+                            void* d_out_slot, void* d_out_cost, void* stream);
+int hmme_select_refs_frame(hmme_ctx* ctx, int width, int height, int n_refs, const hmme_frame_params* fp, const hmme_select_params* sel,
+                           const uint32_t* ref_cost, const int16_t* mv, const uint32_t* cost, const int16_t* pred_q, int16_t* out_field, uint8_t* out_ref,
+                           uint16_t* out_slot, uint32_t* out_cost);
+int hmme_predict_refs_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp, const void* d_mv_field,
+                             const void* d_ref_field, int mv_per_ctu, void* d_out, int out_pitch_bytes, void* stream);
+int hmme_predict_refs_frame(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp, const int16_t* mv_field,
+                            const uint8_t* ref_field, int mv_per_ctu, void* out, int out_stride);
+
 /* ---- estimating explicit weighted-prediction parameters --------------------------------------------------------
  * Where the weights of the *_w calls come from when the caller has none: the luma part of HM's estimator, WeightPredAnalysis::
  * xCalcACDCParamSlice, xEstimateWPParamSlice, xUpdatingWPParameters, xSelectWP and xCalcSADvalueWP (source/Lib/TLibEncoder/
