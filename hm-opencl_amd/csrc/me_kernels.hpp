@@ -102,6 +102,19 @@ __device__ __forceinline__ uint32_t me_min4(uint32_t a, uint32_t b, uint32_t c, 
   return r;
 }
 #define ME_MIN4(k) me_min4(k##_0, k##_1, k##_2, k##_3)
+// A difference K(a \\ b) is read by nothing but the minimum of its own slot (the right 4x8 half of an 8x8 CU, 12x16, 24x32, 48x64, ...;
+// a and b keys of ONE family, b inside a): the four keys and their minimum as one asm block of six instructions.  hipcc pads an asm block
+// that reads what the asm block right before it wrote (s_nop), never inside one; the four keys live in two scratch registers.
+#define ME_SUBMIN4(r, a, b)                                                                                     \
+  uint32_t r;                                                                                                   \
+  {                                                                                                             \
+    uint32_t r##_t, r##_u;                                                                                      \
+    asm volatile("v_sad_u32 %0, %3, %7, %11\n\tv_sad_u32 %1, %4, %8, %12\n\tv_sad_u32 %2, %5, %9, %13\n\t"            \
+                 "v_min3_u32 %0, %0, %1, %2\n\tv_sad_u32 %1, %6, %10, %14\n\tv_min_u32 %0, %0, %1"                    \
+                 : "=&v"(r), "=&v"(r##_t), "=&v"(r##_u)                                                        \
+                 : "v"(a##_0), "v"(a##_1), "v"(a##_2), "v"(a##_3), "v"(b##_0), "v"(b##_1), "v"(b##_2), "v"(b##_3), "v"(c0), "v"(c1),     \
+                   "v"(c2), "v"(c3));                                                                           \
+  }
 
 // butterfly transpose-reduce: merge two slot registers into one; lanes whose role bit is 0 keep
 // slot a (min over the lane pair), lanes whose role bit is 1 keep slot b.

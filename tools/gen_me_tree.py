@@ -7,10 +7,13 @@ One *lane-iteration* of the kernel evaluates FOUR horizontally adjacent candidat
   leaves   256 4x4 blocks x 4 rows of v_qsad_pk_u16_u8 (4 candidates per instruction, packed
            u16 accumulators); per block an "even rows" sum E (rows 0,2 -- what HM's FEN
            sub-sampled SAD reads) and an "all rows" sum A (E chained through rows 1,3)
-  tree     packed-u16 sums (v_pk_add_u16) up to 16x16, then 32-bit *keys*
+  tree     packed-u16 sums (v_pk_add_u16) wherever a sum fits u16 and is not yet a key, 32-bit *keys*
            K = sad * MULT + C_j,  C_j = (mvcost_j << 10) | candidate index   (one v_mad_u32_u16)
-           Keys are linear:  K(a U b) = K(a) + K(b) - C  (v_add3_u32),  K(a \\ b) = K(a) - K(b) + C,
-           so everything above 16x16 is one VALU op per candidate and slot.
+           Keys are linear:  K(a U b) = K(a) + K(b) - C  (v_add3_u32),  K(a \\ b) = |K(a) - K(b)| + C  (v_sad_u32:
+           b inside a, same family), one VALU op per candidate and slot.  Neither form owns a size range; each slot takes
+           the cheaper one: a packed add (1 op for 4 candidates) + a key (4) where no key of its parts exists, one key op (4)
+           where they do -- the right 4x8 half of an 8x8 CU (8x8 - left half), 12x16 (16x16 - 4x16) and everything
+           above 16x16 but the two tall-family 32x8 strips of a 32x32, which stay packed up to 32x8 (2 x 16x8, one key).
   arg-min  per slot: min over the lane's 4 candidates (v_min3_u32 + v_min_u32), then a
            64-register -> 1-register *butterfly transpose-reduce* across the wave
            (v_permlane32_swap, v_permlane16_swap, DPP row_ror:8 / row_half_mirror / quad_perm):
@@ -75,6 +78,8 @@ LOAD_OPS = ("LDS", "CURLD", "BASE", "LDS16Q", "ROWBASE", "CURLD16")
 class Tree:
     """builds the op list for one lane-iteration"""
 
+    KEY_SUB = True   # an 8x8 CU's right 4x8 half is formed from keys (8x8 - left half); the 16-bit tree keeps its packed sum
+
     def __init__(self, fen):
         self.fen = fen
         self.ops = []
@@ -89,6 +94,14 @@ class Tree:
     def new(self, prefix="v"):
         self.n += 1
         return f"{prefix}{self.n}"
+
+    def retire(self, count=1):
+        """give up the numbers of values that a CU / region no longer forms: every later name stays what it was, so a change to
+        one part of the tree renames nothing in the rest of the generated source"""
+        if not self.KEY_SUB:     # the 16-bit tree forms what it always formed
+            return None
+        self.n += count
+        return self.n
 
     # ---- leaves -------------------------------------------------------------------------
     def lds(self, row, k):
@@ -138,6 +151,13 @@ class Tree:
         v = self.new("p")
         self.ops.append(("PKADD", v, a, b))
         return v
+
+    def pkadd_as(self, number, a, b):
+        """pkadd under a retired number (None: the next one)"""
+        if number is None:
+            return self.pkadd(a, b)
+        self.ops.append(("PKADD", f"p{number}", a, b))
+        return f"p{number}"
 
     def pksub(self, a, b):
         v = self.new("p")
@@ -208,7 +228,7 @@ class Tree:
                                 self.ops[start:] = [("LOADS_FOR", len(self.cu_loads))] + \
                                     [o for o in new if o[0] not in LOAD_OPS]
                         regions.append(self.level1(qx * 2 + rx, qy * 2 + ry, rx, ry, cus, U))
-                quads.append(self.level2(qx, qy, regions))
+                quads.append(self.level2(qx, qy, regions, U))
         self.level3(quads)
         self.flush()
         self.ops = self._assemble()
@@ -237,13 +257,24 @@ class Tree:
         (e0, a0), (e1, a1) = self.block(2 * cx8, 2 * cy8), self.block(2 * cx8 + 1, 2 * cy8)
         (e2, a2), (e3, a3) = self.block(2 * cx8, 2 * cy8 + 1), self.block(2 * cx8 + 1, 2 * cy8 + 1)
         at, ab = self.pkadd(a0, a1), self.pkadd(a2, a3)
-        al, ar = self.pkadd(a0, a2), self.pkadd(a1, a3)
+        al = self.pkadd(a0, a2)
+        # the right 4x8 half as a packed sum only where something reads the packed sum: the tall family's 4x16 column without FEN
+        ar = self.pkadd(a1, a3) if not self.KEY_SUB or (not self.fen and cx == 1) else None
+        if ar is None:
+            self.retire()
         k_at, k_ab = self.keys(at, "A"), self.keys(ab, "A")
         self.emit(slot_2NxN(8, cx8, cy8, 0), k_at)
         self.emit(slot_2NxN(8, cx8, cy8, 1), k_ab)
-        self.emit(slot_Nx2N(8, cx8, cy8, 0), self.keys(al, "A"))
-        self.emit(slot_Nx2N(8, cx8, cy8, 1), self.keys(ar, "A"))
-        k_a8 = self.lin(k_at, k_ab)
+        if self.KEY_SUB:
+            # the 8x8 key exists anyway: right half = whole - left half, one key op per candidate and no packed add in front of it
+            k_al = self.keys(al, "A")
+            k_a8 = self.lin(k_at, k_ab)
+            self.emit(slot_Nx2N(8, cx8, cy8, 0), k_al)
+            self.emit(slot_Nx2N(8, cx8, cy8, 1), self.keys(ar, "A") if ar is not None else self.sub(k_a8, k_al))
+        else:
+            self.emit(slot_Nx2N(8, cx8, cy8, 0), self.keys(al, "A"))
+            self.emit(slot_Nx2N(8, cx8, cy8, 1), self.keys(ar, "A"))
+            k_a8 = self.lin(k_at, k_ab)
         self.emit(slot_2Nx2N(8, cx8, cy8), k_a8)
         out = {"k_a8": k_a8, "k_at": k_at, "k_ab": k_ab}
         if self.fen:
@@ -277,19 +308,23 @@ class Tree:
         self.emit(slot_2Nx2N(S, rx16, ry16), k_u16)
         self.emit(slot_AMP(S, rx16, ry16, 2), self.keys(self.pksub(u16, b4), U))   # 16x12 top
         self.emit(slot_AMP(S, rx16, ry16, 3), self.keys(self.pksub(u16, t4), U))   # 16x12 bottom
-        self.emit(slot_AMP(S, rx16, ry16, 4), self.keys(l4, U))                    # 4x16 left
-        self.emit(slot_AMP(S, rx16, ry16, 5), self.keys(r4, U))                    # 4x16 right
-        self.emit(slot_AMP(S, rx16, ry16, 6), self.keys(self.pksub(u16, r4), U))   # 12x16 left
-        self.emit(slot_AMP(S, rx16, ry16, 7), self.keys(self.pksub(u16, l4), U))   # 12x16 right
+        k_l4, k_r4 = self.keys(l4, U), self.keys(r4, U)
+        self.retire(2)                                                             # the packed 12x16 sums
+        self.emit(slot_AMP(S, rx16, ry16, 4), k_l4)                                # 4x16 left
+        self.emit(slot_AMP(S, rx16, ry16, 5), k_r4)                                # 4x16 right
+        self.emit(slot_AMP(S, rx16, ry16, 6), self.sub(k_u16, k_r4))               # 12x16 left: whole - 4x16, both keys exist
+        self.emit(slot_AMP(S, rx16, ry16, 7), self.sub(k_u16, k_l4))               # 12x16 right
         out = {"k_u16": k_u16,
                "k_ucol": k_left if rx == 0 else k_right,                          # 8x16 strip on the 32x32's edge
                "k_a16x8": k_top if ry == 0 else k_bot}                            # all-rows 16x8 strip on the edge
-        strip = self.pkadd(c[0]["u8"], c[1]["u8"]) if ry == 0 else self.pkadd(c[2]["u8"], c[3]["u8"])
-        out["k_u16x8"] = self.keys(strip, U)                                        # tall-family 16x8 strip
+        # tall-family 16x8 strip on the edge, still packed: two of them make a 32x8 strip that fits u16 (<= 32*4*255 even rows /
+        # 32*8*255 all rows), so level 2 adds first and forms ONE key
+        out["u16x8"] = self.pkadd(c[0]["u8"], c[1]["u8"]) if ry == 0 else self.pkadd(c[2]["u8"], c[3]["u8"])
+        out["spare"] = self.retire()                                               # the 16x8 key's number: level 2 names a 32x8 sum with it
         return out
 
-    def level2(self, qx, qy, r):
-        """32x32 CU; every value is a key from here on"""
+    def level2(self, qx, qy, r, U):
+        """32x32 CU; every value is a key from here on, but for the two 32x8 strips of the tall family (packed up to here)"""
         S = 32
         k_t, k_b = self.lin(r[0]["k_u16"], r[1]["k_u16"]), self.lin(r[2]["k_u16"], r[3]["k_u16"])
         k_l, k_r = self.lin(r[0]["k_u16"], r[2]["k_u16"]), self.lin(r[1]["k_u16"], r[3]["k_u16"])
@@ -301,8 +336,8 @@ class Tree:
         self.emit(slot_2Nx2N(S, qx, qy), k_u32)
         self.emit(slot_AMP(S, qx, qy, 0), self.lin(r[0]["k_a16x8"], r[1]["k_a16x8"]))   # 32x8 top   (all rows)
         self.emit(slot_AMP(S, qx, qy, 1), self.lin(r[2]["k_a16x8"], r[3]["k_a16x8"]))   # 32x8 bottom
-        k_u32x8t = self.lin(r[0]["k_u16x8"], r[1]["k_u16x8"])
-        k_u32x8b = self.lin(r[2]["k_u16x8"], r[3]["k_u16x8"])
+        k_u32x8t = self.keys(self.pkadd_as(r[0]["spare"], r[0]["u16x8"], r[1]["u16x8"]), U)
+        k_u32x8b = self.keys(self.pkadd_as(r[2]["spare"], r[2]["u16x8"], r[3]["u16x8"]), U)
         k_u8x32l = self.lin(r[0]["k_ucol"], r[2]["k_ucol"])
         k_u8x32r = self.lin(r[1]["k_ucol"], r[3]["k_ucol"])
         self.emit(slot_AMP(S, qx, qy, 2), self.sub(k_u32, k_u32x8b))   # 32x24 top
@@ -372,6 +407,7 @@ class Tree16(Tree):
     of the CU being consumed, so the prefetch distance is half a CU (_assemble)."""
 
     nc = 3
+    KEY_SUB = False   # its "keys" are exact sums: a subtraction saves nothing there, and its op list stays what it was
 
     def block16(self, cx8, cy8):
         """-> [(E, A)] for the 4 blocks TL, TR, BL, BR of the CU; E/A are NC-candidate sum tuples"""
@@ -520,7 +556,22 @@ MASKED_MERGE_LEVELS = (0, 1)   # the two levels done with hand-written bank-mask
 # pair's key constants are one v_lshl_add_u64 each (shift 0: the instruction only shifts by 0..4, which is why the key's shift rides on the
 # first add of two leaf sums), 6 instructions per slot where three separate candidates took 7, 2 per add where they took 3
 PAIR64 = True
-ORDERED_INSTRS = {"KEYS": 4, "LIN": 4, "SUB": 4, "MIN4": 2, "KEYMINN": 1 if PAIR64 else 7}
+ORDERED_INSTRS = {"KEYS": 4, "LIN": 4, "SUB": 4, "MIN4": 2, "SUBMIN4": 6, "KEYMINN": 1 if PAIR64 else 7}
+
+
+def fuse_sub_min(ops):
+    """A difference of two keys is read by nothing but the minimum of its own slot: SUB + MIN4 become ONE asm block (ME_SUBMIN4) in the
+    emitted source -- the compiler pads between two asm blocks of which the second reads what the first wrote, not inside one, and the
+    four keys of the difference need no names.  The op list itself (what `simulate` interprets) keeps the two ops."""
+    out = []
+    for op in ops:
+        if op[0] == "MIN4" and out and out[-1][0] == "SUB" and out[-1][1] == op[2]:
+            _, k, a, b = out.pop()
+            assert not any(k in o[2:] for o in ops if o is not op and o[0] in ("LIN", "SUB", "MIN4")), "a fused difference has one reader"
+            out.append(("SUBMIN4", op[1], a, b))
+        else:
+            out.append(op)
+    return out
 
 
 def space_merges(ops, enable):
@@ -571,7 +622,7 @@ def space_merges(ops, enable):
         count[0] += ORDERED_INSTRS.get(op[0], 0)
         if op[0] in ("KEYS", "LIN", "SUB"):
             key_at[op[1]] = count[0]
-        if op[0] in ("MIN4", "KEYMINN"):       # the ops whose result a level-0 merge reads
+        if op[0] in ("MIN4", "KEYMINN", "SUBMIN4"):       # the ops whose result a level-0 merge reads
             where[op[1]] = count[0]
         out.append((op, False))
 
@@ -600,7 +651,7 @@ def space_merges(ops, enable):
 def emit_cpp(tree, path, header=None):
     o = [(header or HEADER) % tree.fen]
     max_declared = False
-    for op, padded in space_merges(tree.ops, enable=True):
+    for op, padded in space_merges(fuse_sub_min(tree.ops), enable=True):
         t = op[0]
         if t == "BASE":
             _, b, row, k = op
@@ -632,6 +683,8 @@ def emit_cpp(tree, path, header=None):
             o.append(f"ME_SUB({op[1]}, {op[2]}, {op[3]});")
         elif t == "MIN4":
             o.append(f"const uint32_t {op[1]} = ME_MIN4({op[2]});")
+        elif t == "SUBMIN4":
+            o.append(f"ME_SUBMIN4({op[1]}, {op[2]}, {op[3]});")
         elif t == "MERGE":
             _, level, m, a, b = op
             a = a if a is not None else "ME_MAXKEY"
