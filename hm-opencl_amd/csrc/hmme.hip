@@ -398,6 +398,14 @@ int finalize_best(hmme_ctx* ctx, unsigned long long* d_best, const MeJob16* d_jo
   return HMME_OK;
 }
 
+// the CTUs a call handles: ctu_count < 0 = from ctu_first to the end of the picture
+int ctu_range(hmme_ctx* ctx, const hmme_frame_params* fp, int n_ctu, int* first, int* count) {
+  *first = fp->ctu_first;
+  *count = fp->ctu_count < 0 ? n_ctu - fp->ctu_first : fp->ctu_count;
+  if (*first < 0 || *count < 0 || *first + *count > n_ctu) return fail(ctx, HMME_ERR_ARG, "CTU range [%d, +%d) outside 0..%d", *first, *count, n_ctu);
+  return HMME_OK;
+}
+
 int check_frame_args(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_frame_params* fp, int* first,
                      int* count) {
   if (!ctx) return HMME_ERR_ARG;
@@ -411,11 +419,7 @@ int check_frame_args(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref
     return fail(ctx, HMME_ERR_ARG, "planes hold %d/%d-bit samples, search asks for %d", cur->bit_depth, ref->bit_depth, fp->bit_depth);
   if (fp->search_range < 1 || fp->search_range > ctx->sr_max)
     return fail(ctx, HMME_ERR_ARG, "search range %d outside [1, %d]", fp->search_range, ctx->sr_max);
-  const int n = hmme_num_ctus(cur->width, cur->height);
-  *first = fp->ctu_first;
-  *count = fp->ctu_count < 0 ? n - fp->ctu_first : fp->ctu_count;
-  if (*first < 0 || *count < 0 || *first + *count > n) return fail(ctx, HMME_ERR_ARG, "CTU range [%d, +%d) outside 0..%d", *first, *count, n);
-  return HMME_OK;
+  return ctu_range(ctx, fp, hmme_num_ctus(cur->width, cur->height), first, count);
 }
 
 // Range violations are latched on the device: flag 0 by the synchronous uploads (taken right behind the fill, on its stream), flag 1
@@ -1978,23 +1982,25 @@ int check_bi_weights(hmme_ctx* ctx, const char* who, const hmme_frame_params* fp
 }
 
 // me_predict_kernel for CTUs [first, first + count) of `src` with its motion field (int16 [n_ctu][mv_per_ctu][2], device)
+// pw: the weight of a slice with explicit weighted prediction (null: none, and the identity -- WP = 0 computes the same samples)
+// pr: a reference picture per block (hmme_predict_refs_device: an image without weights; `src` gives the geometry all planes share)
 int launch_predict(hmme_ctx* ctx, const hmme_plane* src, const int16_t* d_field, int mv_per_ctu, int first, int count, bool origin, const uint8_t* cur_blocks,
-                   int bias, uint8_t* dst, long dst_ctu_x, long dst_ctu_y, int dst_pitch, hipStream_t s, const hmme::MePredWp<1>* pw = nullptr) {
+                   int bias, uint8_t* dst, long dst_ctu_x, long dst_ctu_y, int dst_pitch, hipStream_t s, const hmme::MePredWp<1>* pw = nullptr,
+                   const hmme::MePredRefs<1>* pr = nullptr) {
   const dim3 grid((unsigned)count), block(256);
-  // pw: the weight of a slice with explicit weighted prediction (null: none, and the identity -- WP = 0 computes the same samples)
-#define HMME_PREDICT(T, OUT)                                                                                                              \
-  do {                                                                                                                                    \
-    if (pw)                                                                                                                               \
-      hipLaunchKernelGGL((hmme::me_predict_kernel<T, OUT, 1>), grid, block, 0, s, src->origin(), src->pitch, d_field, mv_per_ctu, first,  \
-                         src->width, src->height, src->bit_depth, cur_blocks, bias, dst, dst_ctu_x, dst_ctu_y, dst_pitch, *pw,            \
-                         hmme::MePredRefs<0>{});                                                                                          \
-    else                                                                                                                                  \
-      hipLaunchKernelGGL((hmme::me_predict_kernel<T, OUT, 0>), grid, block, 0, s, src->origin(), src->pitch, d_field, mv_per_ctu, first,  \
-                         src->width, src->height, src->bit_depth, cur_blocks, bias, dst, dst_ctu_x, dst_ctu_y, dst_pitch,                 \
-                         hmme::MePredWp<0>{}, hmme::MePredRefs<0>{});                                                                     \
+#define HMME_PREDICT(T, OUT, WP, REFS, wp, refs)                                                                                                \
+  hipLaunchKernelGGL((hmme::me_predict_kernel<T, OUT, WP, REFS>), grid, block, 0, s, src->origin(), src->pitch, d_field, mv_per_ctu, first,    \
+                     src->width, src->height, src->bit_depth, cur_blocks, bias, dst, dst_ctu_x, dst_ctu_y, dst_pitch, wp, refs)
+#define HMME_PREDICT_T(T)                                                                      \
+  do {                                                                                         \
+    if (pr) { HMME_PREDICT(T, 0, 0, 1, hmme::MePredWp<0>{}, *pr); }                            \
+    else if (origin && pw) { HMME_PREDICT(T, 1, 1, 0, *pw, hmme::MePredRefs<0>{}); }           \
+    else if (origin) { HMME_PREDICT(T, 1, 0, 0, hmme::MePredWp<0>{}, hmme::MePredRefs<0>{}); } \
+    else if (pw) { HMME_PREDICT(T, 0, 1, 0, *pw, hmme::MePredRefs<0>{}); }                     \
+    else { HMME_PREDICT(T, 0, 0, 0, hmme::MePredWp<0>{}, hmme::MePredRefs<0>{}); }             \
   } while (0)
-  if (src->bps == 1) { if (origin) HMME_PREDICT(uint8_t, 1); else HMME_PREDICT(uint8_t, 0); }
-  else { if (origin) HMME_PREDICT(uint16_t, 1); else HMME_PREDICT(uint16_t, 0); }
+  if (src->bps == 1) HMME_PREDICT_T(uint8_t); else HMME_PREDICT_T(uint16_t);
+#undef HMME_PREDICT_T
 #undef HMME_PREDICT
   HIP_TRY(ctx, hipGetLastError());
   return HMME_OK;
@@ -2007,36 +2013,76 @@ int hmme_bipred_check(int bit_depth, int refine) {
 }
 
 namespace {
-// hmme_predict_pairs_device (wps == null) and hmme_predict_pairs_w_device
-int predict_pairs(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs, int n_pairs, const hmme_frame_params* fp, const hmme_weight* wps,
-                  const void* d_mv_field, int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream) {
-  int rc = bi_check(ctx, who, fp, 0);
-  if (rc) return rc;
-  if (!refs || !d_outs || n_pairs < 1 || n_pairs > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d pictures outside 1..%d (or a null list)", who, n_pairs, hmme::kMaxRefs);
+size_t pad16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+
+// What hmme_predict_pairs_device, _w_device and hmme_predict_refs_device check alike, in the order that decides the code returned
+// null_arg: one of the caller's other pointers is null; wps: one weight per plane, or null for none
+struct PredictArgs {
+  hmme_frame_params f;   // fp for pairs_begin
   bool identity[hmme::kMaxRefs];
   hmme::MePredWp<1> pw[hmme::kMaxRefs];
-  for (int r = 0; r < n_pairs; ++r) {
-    identity[r] = true;
+};
+int predict_args(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs, int n, bool null_arg, const hmme_frame_params* fp, const hmme_weight* wps,
+                 const void* d_mv_field, int mv_per_ctu, int out_pitch_bytes, PredictArgs* a) {
+  int rc = bi_check(ctx, who, fp, 0);
+  if (rc) return rc;
+  if (!refs || null_arg || n < 1 || n > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d pictures outside 1..%d (or a null argument)", who, n, hmme::kMaxRefs);
+  for (int r = 0; r < n; ++r) {
+    a->identity[r] = true;
     if (!wps) continue;
     char msg[256];
-    rc = other_weight_eval(fp->bit_depth, &wps[r], &identity[r], &pw[r], msg, sizeof msg);
+    rc = other_weight_eval(fp->bit_depth, &wps[r], &a->identity[r], &a->pw[r], msg, sizeof msg);
     if (rc) return fail(ctx, rc, "%s: picture %d: %s", who, r, msg);
   }
   if (!d_mv_field || (mv_per_ctu != 1 && mv_per_ctu != 64)) return fail(ctx, HMME_ERR_ARG, "%s: null motion field, or %d MVs per CTU (1 or 64)", who, mv_per_ctu);
-  for (int r = 0; r < n_pairs; ++r)
-    if (!refs[r] || !d_outs[r]) return fail(ctx, HMME_ERR_ARG, "%s: null plane / output image", who);
+  for (int r = 0; r < n; ++r)
+    if (!refs[r]) return fail(ctx, HMME_ERR_ARG, "%s: null plane", who);
   if (out_pitch_bytes < refs[0]->width * refs[0]->bps) return fail(ctx, HMME_ERR_ARG, "%s: output pitch %d below a picture row", who, out_pitch_bytes);
-  hmme_frame_params f = *fp;
-  f.search_range = 1;   // not consulted: nothing is searched
+  a->f = *fp;
+  a->f.search_range = 1;   // not consulted: nothing is searched
+  return HMME_OK;
+}
+
+// hmme_predict_pairs_device (wps == null) and hmme_predict_pairs_w_device
+int predict_pairs(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs, int n_pairs, const hmme_frame_params* fp, const hmme_weight* wps,
+                  const void* d_mv_field, int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream) {
+  PredictArgs a;
+  int rc = predict_args(ctx, who, refs, n_pairs, !d_outs, fp, wps, d_mv_field, mv_per_ctu, out_pitch_bytes, &a);
+  if (rc) return rc;
+  for (int r = 0; r < n_pairs; ++r)
+    if (!d_outs[r]) return fail(ctx, HMME_ERR_ARG, "%s: null output image", who);
   hipStream_t s = (hipStream_t)stream;
   PairLaunch pl;
-  rc = pairs_begin(ctx, refs, refs, n_pairs, &f, s, &pl);
+  rc = pairs_begin(ctx, refs, refs, n_pairs, &a.f, s, &pl);
   if (rc || pl.count == 0) return rc;
   const size_t field = (size_t)refs[0]->n_ctu * mv_per_ctu * 2;
   for (int r = 0; r < n_pairs && rc == HMME_OK; ++r)
     rc = launch_predict(ctx, refs[r], (const int16_t*)d_mv_field + field * r, mv_per_ctu, pl.first, pl.count, false, nullptr, 0, (uint8_t*)d_outs[r], 0, 0,
-                        out_pitch_bytes, s, identity[r] ? nullptr : &pw[r]);
+                        out_pitch_bytes, s, a.identity[r] ? nullptr : &a.pw[r]);
   return pairs_end(ctx, refs, refs, n_pairs, s, rc);
+}
+
+// hmme_predict_frame, _w and hmme_predict_refs_frame: the motion field and, behind it, the reference field (null: none) into ctx->d_bi[0], the
+// caller's image through ctx->d_bi[1] both ways around `launch`: samples that are not written come back as they were
+int predict_staged(hmme_ctx* ctx, const char* who, const hmme_plane* ref, const int16_t* mv_field, const uint8_t* ref_field, int mv_per_ctu, void* out, int out_stride,
+                   const std::function<int(void* d_field, void* d_ref_field, void* d_img, int pitch, hipStream_t s)>& launch) {
+  if (ref->ctx != ctx) return fail(ctx, HMME_ERR_ARG, "plane belongs to another context (planes are used with the context that created them)");
+  if (out_stride < ref->width) return fail(ctx, HMME_ERR_ARG, "%s: output stride %d below the picture width", who, out_stride);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t blocks = (size_t)ref->n_ctu * mv_per_ctu, field_bytes = sizeof(int16_t) * 2 * blocks, row = (size_t)ref->width * ref->bps;
+  int rc = ensure(ctx, &ctx->d_bi[0], &ctx->bi_cap[0], pad16(field_bytes) + (ref_field ? blocks : 0));
+  if (rc == HMME_OK) rc = ensure(ctx, &ctx->d_bi[1], &ctx->bi_cap[1], row * ref->height);
+  if (rc) return rc;
+  hipStream_t s = ctx->stream;
+  uint8_t* d_ref_field = ctx->d_bi[0] + pad16(field_bytes);
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_bi[0], mv_field, field_bytes, hipMemcpyHostToDevice, s));
+  if (ref_field) HIP_TRY(ctx, hipMemcpyAsync(d_ref_field, ref_field, blocks, hipMemcpyHostToDevice, s));
+  HIP_TRY(ctx, hipMemcpy2DAsync(ctx->d_bi[1], row, out, (size_t)out_stride * ref->bps, row, ref->height, hipMemcpyHostToDevice, s));
+  rc = launch(ctx->d_bi[0], d_ref_field, ctx->d_bi[1], (int)row, s);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemcpy2DAsync(out, (size_t)out_stride * ref->bps, ctx->d_bi[1], row, row, ref->height, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  return HMME_OK;
 }
 
 // hmme_predict_frame (wp == null) and hmme_predict_frame_w
@@ -2050,23 +2096,9 @@ int predict_frame(hmme_ctx* ctx, const char* who, const hmme_plane* ref, const h
     if (rc) return fail(ctx, rc, "%s: %s", who, msg);
   }
   if (!ref || !mv_field || !out || (mv_per_ctu != 1 && mv_per_ctu != 64)) return fail(ctx, HMME_ERR_ARG, "%s: null argument, or %d MVs per CTU (1 or 64)", who, mv_per_ctu);
-  if (ref->ctx != ctx) return fail(ctx, HMME_ERR_ARG, "plane belongs to another context (planes are used with the context that created them)");
-  if (out_stride < ref->width) return fail(ctx, HMME_ERR_ARG, "%s: output stride %d below the picture width", who, out_stride);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t field_bytes = sizeof(int16_t) * 2 * (size_t)ref->n_ctu * mv_per_ctu, row = (size_t)ref->width * ref->bps;
-  rc = ensure(ctx, &ctx->d_bi[0], &ctx->bi_cap[0], field_bytes);
-  if (rc == HMME_OK) rc = ensure(ctx, &ctx->d_bi[1], &ctx->bi_cap[1], row * ref->height);
-  if (rc) return rc;
-  hipStream_t s = ctx->stream;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_bi[0], mv_field, field_bytes, hipMemcpyHostToDevice, s));
-  // the caller's image travels both ways: samples outside the CTU range come back as they were
-  HIP_TRY(ctx, hipMemcpy2DAsync(ctx->d_bi[1], row, out, (size_t)out_stride * ref->bps, row, ref->height, hipMemcpyHostToDevice, s));
-  void* img = ctx->d_bi[1];
-  rc = predict_pairs(ctx, who, &ref, 1, fp, weighted ? wp : nullptr, ctx->d_bi[0], mv_per_ctu, &img, (int)row, s);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpy2DAsync(out, (size_t)out_stride * ref->bps, ctx->d_bi[1], row, row, ref->height, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  return HMME_OK;
+  return predict_staged(ctx, who, ref, mv_field, nullptr, mv_per_ctu, out, out_stride, [&](void* d_field, void*, void* d_img, int pitch, hipStream_t s) {
+    return predict_pairs(ctx, who, &ref, 1, fp, weighted ? wp : nullptr, d_field, mv_per_ctu, &d_img, pitch, s);
+  });
 }
 }  // namespace
 
@@ -2345,82 +2377,7 @@ int select_eval(const hmme_select_params* p, char* msg, size_t cap) {
   if (p->cu_cost > (1u << 20) || p->pu_cost > (1u << 20)) { snprintf(msg, cap, "cu_cost %u / pu_cost %u above 2^20", p->cu_cost, p->pu_cost); return HMME_ERR_ARG; }
   return HMME_OK;
 }
-size_t pad16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
-}  // namespace
-
-int hmme_select_check(const hmme_select_params* sel) {
-  char msg[256];
-  return select_eval(sel, msg, sizeof msg);
-}
-
-int hmme_select_pairs_device(hmme_ctx* ctx, int width, int height, int n_pairs, const hmme_frame_params* fp, const hmme_select_params* sel,
-                             const void* d_mv, const void* d_cost, const void* d_pred_q, void* d_out_field, void* d_out_slot, void* d_out_cost,
-                             void* stream) {
-  if (!ctx) return HMME_ERR_ARG;
-  char msg[256];
-  const int bad = select_eval(sel, msg, sizeof msg);
-  if (bad) return fail(ctx, bad, "hmme_select_pairs_device: %s", msg);
-  if (!fp || width < 1 || height < 1) return fail(ctx, HMME_ERR_ARG, "hmme_select_pairs_device: null frame parameters, or a %d x %d picture", width, height);
-  if (n_pairs < 1 || n_pairs > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "hmme_select_pairs_device: %d picture pairs outside 1..%d", n_pairs, hmme::kMaxRefs);
-  if (!d_mv || !d_cost || !d_out_field) return fail(ctx, HMME_ERR_ARG, "hmme_select_pairs_device: null table / field buffer");
-  // the kernel moves MVs as dwords and, with four MVs per 8x8 block, two entries per store
-  if (((uintptr_t)d_mv & 3) || ((uintptr_t)d_cost & 3) || ((uintptr_t)d_out_field & 7) || ((uintptr_t)d_out_slot & 3) || ((uintptr_t)d_out_cost & 3) ||
-      ((uintptr_t)d_pred_q & 1))
-    return fail(ctx, HMME_ERR_ARG, "hmme_select_pairs_device: misaligned buffer (tables and costs 4 bytes, field 8, slots 4)");
-  const int n_ctu = hmme_num_ctus(width, height);
-  const int first = fp->ctu_first, count = fp->ctu_count < 0 ? n_ctu - fp->ctu_first : fp->ctu_count;
-  if (first < 0 || count < 0 || first + count > n_ctu) return fail(ctx, HMME_ERR_ARG, "CTU range [%d, +%d) outside 0..%d", first, count, n_ctu);
-  if (count == 0) return HMME_OK;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const hmme::MeSelect a = {sel->mv_per_ctu, sel->mv_unit, sel->price_mv, sel->part_mask, sel->min_depth, sel->max_depth, sel->cu_cost, sel->pu_cost};
-  const dim3 grid((unsigned)((count + 3) / 4), (unsigned)n_pairs), block(256);
-  hipLaunchKernelGGL(hmme::me_select_kernel, grid, block, 0, (hipStream_t)stream, (const uint32_t*)d_mv, (const uint32_t*)d_cost, (const int16_t*)d_pred_q,
-                     (uint32_t*)d_out_field, (uint16_t*)d_out_slot, (uint32_t*)d_out_cost, a, width, height, n_ctu, first, count, ctx->lambda_q16);
-  HIP_TRY(ctx, hipGetLastError());
-  return HMME_OK;
-}
-
-int hmme_select_frame(hmme_ctx* ctx, int width, int height, const hmme_frame_params* fp, const hmme_select_params* sel, const int16_t* mv,
-                      const uint32_t* cost, const int16_t* pred_q, int16_t* out_field, uint16_t* out_slot, uint32_t* out_cost) {
-  if (!ctx) return HMME_ERR_ARG;
-  char msg[256];
-  const int bad = select_eval(sel, msg, sizeof msg);
-  if (bad) return fail(ctx, bad, "hmme_select_frame: %s", msg);
-  if (!fp || width < 1 || height < 1 || !mv || !cost || !out_field) return fail(ctx, HMME_ERR_ARG, "hmme_select_frame: null argument, or a %d x %d picture", width, height);
-  const int n_ctu = hmme_num_ctus(width, height);
-  const int first = fp->ctu_first, count = fp->ctu_count < 0 ? n_ctu - fp->ctu_first : fp->ctu_count;
-  if (first < 0 || count < 0 || first + count > n_ctu) return fail(ctx, HMME_ERR_ARG, "CTU range [%d, +%d) outside 0..%d", first, count, n_ctu);
-  if (count == 0) return HMME_OK;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t per = (size_t)sel->mv_per_ctu, tab = (size_t)count * HMME_NUM_CTU_PARTS;
-  const size_t o_mv = 0, o_cost = o_mv + pad16(tab * 4), o_pred = o_cost + pad16(tab * 4), o_field = o_pred + pad16((size_t)n_ctu * 4);
-  const size_t o_slot = o_field + pad16((size_t)n_ctu * per * 4), o_ccost = o_slot + pad16((size_t)n_ctu * per * 2), total = o_ccost + pad16((size_t)n_ctu * 4);
-  int rc = ensure(ctx, &ctx->d_sel, &ctx->sel_cap, total);
-  if (rc) return rc;
-  hipStream_t s = ctx->stream;
-  uint8_t* d = ctx->d_sel;
-  HIP_TRY(ctx, hipMemcpyAsync(d + o_mv, mv, tab * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(ctx, hipMemcpyAsync(d + o_cost, cost, tab * 4, hipMemcpyHostToDevice, s));
-  if (pred_q) HIP_TRY(ctx, hipMemcpyAsync(d + o_pred, pred_q, (size_t)n_ctu * 4, hipMemcpyHostToDevice, s));
-  rc = hmme_select_pairs_device(ctx, width, height, 1, fp, sel, d + o_mv, d + o_cost, pred_q ? d + o_pred : nullptr, d + o_field, out_slot ? d + o_slot : nullptr,
-                                out_cost ? d + o_ccost : nullptr, s);
-  if (rc) return rc;
-  // only the CTUs of the range come back: the caller's entries outside it keep their values
-  HIP_TRY(ctx, hipMemcpyAsync(out_field + (size_t)first * per * 2, d + o_field + (size_t)first * per * 4, (size_t)count * per * 4, hipMemcpyDeviceToHost, s));
-  if (out_slot) HIP_TRY(ctx, hipMemcpyAsync(out_slot + (size_t)first * per, d + o_slot + (size_t)first * per * 2, (size_t)count * per * 2, hipMemcpyDeviceToHost, s));
-  if (out_cost) HIP_TRY(ctx, hipMemcpyAsync(out_cost + first, d + o_ccost + (size_t)first * 4, (size_t)count * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  return HMME_OK;
-}
-
-// ---- reference picture per PU: the decision over all references' tables, and the prediction that follows it ---------------------------------
-int hmme_ref_idx_bits(int n_refs, int ref_idx) {   // TEncSearch.cpp:3030-3037
-  if (n_refs < 1 || n_refs > hmme::kMaxRefs || ref_idx < 0 || ref_idx >= n_refs) return -1;
-  if (n_refs == 1) return 0;
-  return ref_idx + 1 - (ref_idx == n_refs - 1 ? 1 : 0);
-}
-
-namespace {
+// ... and of a decision over n_pics pictures x n_refs references (the decision of one table set per picture pair: n_refs = 1, no prices)
 int select_refs_eval(const hmme_select_params* sel, int n_pics, int n_refs, const uint32_t* ref_cost, char* msg, size_t cap) {
   const int bad = select_eval(sel, msg, cap);
   if (bad) return bad;
@@ -2435,6 +2392,110 @@ int select_refs_eval(const hmme_select_params* sel, int n_pics, int n_refs, cons
 }
 }  // namespace
 
+int hmme_select_check(const hmme_select_params* sel) {
+  char msg[256];
+  return select_eval(sel, msg, sizeof msg);
+}
+
+namespace {
+// What hmme_select_pairs_device (n_refs = 1, no prices) and hmme_select_refs_device share: the checks of the parameters, of the buffers both
+// take and of the CTU range, then hmme_select_params as the kernels take it and the grid
+struct SelectLaunch {
+  hmme::MeSelect a;
+  int n_ctu, first, count;   // count == 0: nothing to launch
+  dim3 grid;
+};
+int select_begin(hmme_ctx* ctx, const char* who, int width, int height, int n_pics, int n_refs, const uint32_t* ref_cost, const hmme_frame_params* fp,
+                 const hmme_select_params* sel, const void* d_mv, const void* d_cost, const void* d_pred_q, const void* d_out_field, const void* d_out_slot,
+                 const void* d_out_cost, SelectLaunch* L) {
+  char msg[256];
+  const int bad = select_refs_eval(sel, n_pics, n_refs, ref_cost, msg, sizeof msg);
+  if (bad) return fail(ctx, bad, "%s: %s", who, msg);
+  if (!fp || width < 1 || height < 1) return fail(ctx, HMME_ERR_ARG, "%s: null frame parameters, or a %d x %d picture", who, width, height);
+  if (!d_mv || !d_cost || !d_out_field) return fail(ctx, HMME_ERR_ARG, "%s: null table / field buffer", who);
+  // the kernel moves MVs as dwords and, with four MVs per 8x8 block, two entries per store
+  if (((uintptr_t)d_mv & 3) || ((uintptr_t)d_cost & 3) || ((uintptr_t)d_out_field & 7) || ((uintptr_t)d_out_slot & 3) || ((uintptr_t)d_out_cost & 3) ||
+      ((uintptr_t)d_pred_q & 1))
+    return fail(ctx, HMME_ERR_ARG, "%s: misaligned buffer (tables and costs 4 bytes, field 8, slots 4)", who);
+  L->n_ctu = hmme_num_ctus(width, height);
+  const int rc = ctu_range(ctx, fp, L->n_ctu, &L->first, &L->count);
+  if (rc || L->count == 0) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  L->a = {sel->mv_per_ctu, sel->mv_unit, sel->price_mv, sel->part_mask, sel->min_depth, sel->max_depth, sel->cu_cost, sel->pu_cost};
+  L->grid = dim3((unsigned)((L->count + 3) / 4), (unsigned)n_pics);
+  return HMME_OK;
+}
+
+// hmme_select_frame and hmme_select_refs_frame: n_refs table and predictor sets into ctx->d_sel, `launch` on the device addresses (null
+// where the caller's array is; out_ref exists in the refs call only), then the outputs back
+using SelectLaunchFn = std::function<int(void* d_mv, void* d_cost, void* d_pred_q, void* d_field, void* d_ref, void* d_slot, void* d_ccost, hipStream_t s)>;
+int select_staged(hmme_ctx* ctx, const char* who, int width, int height, const hmme_frame_params* fp, const hmme_select_params* sel, int n_refs,
+                  const uint32_t* ref_cost, const int16_t* mv, const uint32_t* cost, const int16_t* pred_q, int16_t* out_field, uint8_t* out_ref, uint16_t* out_slot,
+                  uint32_t* out_cost, const SelectLaunchFn& launch) {
+  char msg[256];
+  const int bad = select_refs_eval(sel, 1, n_refs, ref_cost, msg, sizeof msg);
+  if (bad) return fail(ctx, bad, "%s: %s", who, msg);
+  if (!fp || width < 1 || height < 1 || !mv || !cost || !out_field) return fail(ctx, HMME_ERR_ARG, "%s: null argument, or a %d x %d picture", who, width, height);
+  const size_t n_ctu = hmme_num_ctus(width, height), per = sel->mv_per_ctu;
+  int first, count;
+  int rc = ctu_range(ctx, fp, (int)n_ctu, &first, &count);
+  if (rc || count == 0) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t tab = (size_t)n_refs * count * HMME_NUM_CTU_PARTS * 4, preds = (size_t)n_refs * n_ctu * 4;
+  uint8_t* const host[4] = {(uint8_t*)out_field, out_ref, (uint8_t*)out_slot, (uint8_t*)out_cost};
+  const size_t ctu_bytes[4] = {per * 4, per, per * 2, 4};   // of the four outputs
+  size_t at[4], total = 2 * pad16(tab) + pad16(preds);
+  for (int k = 0; k < 4; ++k) {
+    at[k] = total;
+    if (host[k]) total += pad16(n_ctu * ctu_bytes[k]);
+  }
+  rc = ensure(ctx, &ctx->d_sel, &ctx->sel_cap, total);
+  if (rc) return rc;
+  hipStream_t s = ctx->stream;
+  uint8_t *d = ctx->d_sel, *d_out[4];
+  for (int k = 0; k < 4; ++k) d_out[k] = host[k] ? d + at[k] : nullptr;
+  HIP_TRY(ctx, hipMemcpyAsync(d, mv, tab, hipMemcpyHostToDevice, s));
+  HIP_TRY(ctx, hipMemcpyAsync(d + pad16(tab), cost, tab, hipMemcpyHostToDevice, s));
+  if (pred_q) HIP_TRY(ctx, hipMemcpyAsync(d + 2 * pad16(tab), pred_q, preds, hipMemcpyHostToDevice, s));
+  rc = launch(d, d + pad16(tab), pred_q ? d + 2 * pad16(tab) : nullptr, d_out[0], d_out[1], d_out[2], d_out[3], s);
+  if (rc) return rc;
+  // only the CTUs of the range come back: the caller's entries outside it keep their values
+  for (int k = 0; k < 4; ++k)
+    if (host[k]) HIP_TRY(ctx, hipMemcpyAsync(host[k] + first * ctu_bytes[k], d_out[k] + first * ctu_bytes[k], count * ctu_bytes[k], hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  return HMME_OK;
+}
+}  // namespace
+
+int hmme_select_pairs_device(hmme_ctx* ctx, int width, int height, int n_pairs, const hmme_frame_params* fp, const hmme_select_params* sel,
+                             const void* d_mv, const void* d_cost, const void* d_pred_q, void* d_out_field, void* d_out_slot, void* d_out_cost,
+                             void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  SelectLaunch L;
+  const int rc = select_begin(ctx, "hmme_select_pairs_device", width, height, n_pairs, 1, nullptr, fp, sel, d_mv, d_cost, d_pred_q, d_out_field, d_out_slot, d_out_cost, &L);
+  if (rc || L.count == 0) return rc;
+  hipLaunchKernelGGL(hmme::me_select_kernel, L.grid, dim3(256), 0, (hipStream_t)stream, (const uint32_t*)d_mv, (const uint32_t*)d_cost, (const int16_t*)d_pred_q,
+                     (uint32_t*)d_out_field, (uint16_t*)d_out_slot, (uint32_t*)d_out_cost, L.a, width, height, L.n_ctu, L.first, L.count, ctx->lambda_q16);
+  HIP_TRY(ctx, hipGetLastError());
+  return HMME_OK;
+}
+
+int hmme_select_frame(hmme_ctx* ctx, int width, int height, const hmme_frame_params* fp, const hmme_select_params* sel, const int16_t* mv,
+                      const uint32_t* cost, const int16_t* pred_q, int16_t* out_field, uint16_t* out_slot, uint32_t* out_cost) {
+  if (!ctx) return HMME_ERR_ARG;
+  return select_staged(ctx, "hmme_select_frame", width, height, fp, sel, 1, nullptr, mv, cost, pred_q, out_field, nullptr, out_slot, out_cost,
+                       [&](void* d_mv, void* d_cost, void* d_pred_q, void* d_field, void*, void* d_slot, void* d_ccost, hipStream_t s) {
+                         return hmme_select_pairs_device(ctx, width, height, 1, fp, sel, d_mv, d_cost, d_pred_q, d_field, d_slot, d_ccost, s);
+                       });
+}
+
+// ---- reference picture per PU: the decision over all references' tables, and the prediction that follows it ---------------------------------
+int hmme_ref_idx_bits(int n_refs, int ref_idx) {   // TEncSearch.cpp:3030-3037
+  if (n_refs < 1 || n_refs > hmme::kMaxRefs || ref_idx < 0 || ref_idx >= n_refs) return -1;
+  if (n_refs == 1) return 0;
+  return ref_idx + 1 - (ref_idx == n_refs - 1 ? 1 : 0);
+}
+
 int hmme_select_refs_check(const hmme_select_params* sel, int n_pics, int n_refs, const uint32_t* ref_cost) {
   char msg[256];
   return select_refs_eval(sel, n_pics, n_refs, ref_cost, msg, sizeof msg);
@@ -2444,27 +2505,16 @@ int hmme_select_refs_device(hmme_ctx* ctx, int width, int height, int n_pics, in
                             const uint32_t* ref_cost, const void* d_mv, const void* d_cost, const void* d_pred_q, void* d_out_field, void* d_out_ref,
                             void* d_out_slot, void* d_out_cost, void* stream) {
   if (!ctx) return HMME_ERR_ARG;
-  char msg[256];
-  const int bad = select_refs_eval(sel, n_pics, n_refs, ref_cost, msg, sizeof msg);
-  if (bad) return fail(ctx, bad, "hmme_select_refs_device: %s", msg);
-  if (!fp || width < 1 || height < 1) return fail(ctx, HMME_ERR_ARG, "hmme_select_refs_device: null frame parameters, or a %d x %d picture", width, height);
-  if (!d_mv || !d_cost || !d_out_field || !d_out_ref) return fail(ctx, HMME_ERR_ARG, "hmme_select_refs_device: null table / field / reference buffer");
-  // the kernel moves MVs as dwords and, with four MVs per 8x8 block, two entries per store
-  if (((uintptr_t)d_mv & 3) || ((uintptr_t)d_cost & 3) || ((uintptr_t)d_out_field & 7) || ((uintptr_t)d_out_ref & 1) || ((uintptr_t)d_out_slot & 3) ||
-      ((uintptr_t)d_out_cost & 3) || ((uintptr_t)d_pred_q & 1))
-    return fail(ctx, HMME_ERR_ARG, "hmme_select_refs_device: misaligned buffer (tables and costs 4 bytes, field 8, references 2, slots 4)");
-  const int n_ctu = hmme_num_ctus(width, height);
-  const int first = fp->ctu_first, count = fp->ctu_count < 0 ? n_ctu - fp->ctu_first : fp->ctu_count;
-  if (first < 0 || count < 0 || first + count > n_ctu) return fail(ctx, HMME_ERR_ARG, "CTU range [%d, +%d) outside 0..%d", first, count, n_ctu);
-  if (count == 0) return HMME_OK;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const hmme::MeSelect a = {sel->mv_per_ctu, sel->mv_unit, sel->price_mv, sel->part_mask, sel->min_depth, sel->max_depth, sel->cu_cost, sel->pu_cost};
-  hmme::MeRefCost rc = {};
-  for (int r = 0; ref_cost && r < n_refs; ++r) rc.c[r] = ref_cost[r];
-  const dim3 grid((unsigned)((count + 3) / 4), (unsigned)n_pics), block(256);
-  hipLaunchKernelGGL(hmme::me_select_refs_kernel, grid, block, 0, (hipStream_t)stream, (const uint32_t*)d_mv, (const uint32_t*)d_cost, (const int16_t*)d_pred_q,
-                     (uint32_t*)d_out_field, (uint8_t*)d_out_ref, (uint16_t*)d_out_slot, (uint32_t*)d_out_cost, a, rc, n_refs, width, height, n_ctu, first, count,
-                     ctx->lambda_q16);
+  // with four MVs per 8x8 block the kernel stores two reference indices at a time
+  if (!d_out_ref || ((uintptr_t)d_out_ref & 1)) return fail(ctx, HMME_ERR_ARG, "hmme_select_refs_device: null or misaligned reference buffer (2 bytes)");
+  SelectLaunch L;
+  const int rc = select_begin(ctx, "hmme_select_refs_device", width, height, n_pics, n_refs, ref_cost, fp, sel, d_mv, d_cost, d_pred_q, d_out_field, d_out_slot, d_out_cost, &L);
+  if (rc || L.count == 0) return rc;
+  hmme::MeRefCost price = {};
+  for (int r = 0; ref_cost && r < n_refs; ++r) price.c[r] = ref_cost[r];
+  hipLaunchKernelGGL(hmme::me_select_refs_kernel, L.grid, dim3(256), 0, (hipStream_t)stream, (const uint32_t*)d_mv, (const uint32_t*)d_cost, (const int16_t*)d_pred_q,
+                     (uint32_t*)d_out_field, (uint8_t*)d_out_ref, (uint16_t*)d_out_slot, (uint32_t*)d_out_cost, L.a, price, n_refs, width, height, L.n_ctu, L.first,
+                     L.count, ctx->lambda_q16);
   HIP_TRY(ctx, hipGetLastError());
   return HMME_OK;
 }
@@ -2473,69 +2523,27 @@ int hmme_select_refs_frame(hmme_ctx* ctx, int width, int height, int n_refs, con
                            const uint32_t* ref_cost, const int16_t* mv, const uint32_t* cost, const int16_t* pred_q, int16_t* out_field, uint8_t* out_ref,
                            uint16_t* out_slot, uint32_t* out_cost) {
   if (!ctx) return HMME_ERR_ARG;
-  char msg[256];
-  const int bad = select_refs_eval(sel, 1, n_refs, ref_cost, msg, sizeof msg);
-  if (bad) return fail(ctx, bad, "hmme_select_refs_frame: %s", msg);
-  if (!fp || width < 1 || height < 1 || !mv || !cost || !out_field || !out_ref)
-    return fail(ctx, HMME_ERR_ARG, "hmme_select_refs_frame: null argument, or a %d x %d picture", width, height);
-  const int n_ctu = hmme_num_ctus(width, height);
-  const int first = fp->ctu_first, count = fp->ctu_count < 0 ? n_ctu - fp->ctu_first : fp->ctu_count;
-  if (first < 0 || count < 0 || first + count > n_ctu) return fail(ctx, HMME_ERR_ARG, "CTU range [%d, +%d) outside 0..%d", first, count, n_ctu);
-  if (count == 0) return HMME_OK;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t per = (size_t)sel->mv_per_ctu, tab = (size_t)n_refs * count * HMME_NUM_CTU_PARTS, preds = (size_t)n_refs * n_ctu * 4;
-  const size_t o_mv = 0, o_cost = o_mv + pad16(tab * 4), o_pred = o_cost + pad16(tab * 4), o_field = o_pred + pad16(preds);
-  const size_t o_ref = o_field + pad16((size_t)n_ctu * per * 4), o_slot = o_ref + pad16((size_t)n_ctu * per), o_ccost = o_slot + pad16((size_t)n_ctu * per * 2);
-  const size_t total = o_ccost + pad16((size_t)n_ctu * 4);
-  int rc = ensure(ctx, &ctx->d_sel, &ctx->sel_cap, total);
-  if (rc) return rc;
-  hipStream_t s = ctx->stream;
-  uint8_t* d = ctx->d_sel;
-  HIP_TRY(ctx, hipMemcpyAsync(d + o_mv, mv, tab * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(ctx, hipMemcpyAsync(d + o_cost, cost, tab * 4, hipMemcpyHostToDevice, s));
-  if (pred_q) HIP_TRY(ctx, hipMemcpyAsync(d + o_pred, pred_q, preds, hipMemcpyHostToDevice, s));
-  rc = hmme_select_refs_device(ctx, width, height, 1, n_refs, fp, sel, ref_cost, d + o_mv, d + o_cost, pred_q ? d + o_pred : nullptr, d + o_field, d + o_ref,
-                               out_slot ? d + o_slot : nullptr, out_cost ? d + o_ccost : nullptr, s);
-  if (rc) return rc;
-  // only the CTUs of the range come back: the caller's entries outside it keep their values
-  HIP_TRY(ctx, hipMemcpyAsync(out_field + (size_t)first * per * 2, d + o_field + (size_t)first * per * 4, (size_t)count * per * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(out_ref + (size_t)first * per, d + o_ref + (size_t)first * per, (size_t)count * per, hipMemcpyDeviceToHost, s));
-  if (out_slot) HIP_TRY(ctx, hipMemcpyAsync(out_slot + (size_t)first * per, d + o_slot + (size_t)first * per * 2, (size_t)count * per * 2, hipMemcpyDeviceToHost, s));
-  if (out_cost) HIP_TRY(ctx, hipMemcpyAsync(out_cost + first, d + o_ccost + (size_t)first * 4, (size_t)count * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  return HMME_OK;
+  if (!out_ref) return fail(ctx, HMME_ERR_ARG, "hmme_select_refs_frame: null reference array");
+  return select_staged(ctx, "hmme_select_refs_frame", width, height, fp, sel, n_refs, ref_cost, mv, cost, pred_q, out_field, out_ref, out_slot, out_cost,
+                       [&](void* d_mv, void* d_cost, void* d_pred_q, void* d_field, void* d_ref, void* d_slot, void* d_ccost, hipStream_t s) {
+                         return hmme_select_refs_device(ctx, width, height, 1, n_refs, fp, sel, ref_cost, d_mv, d_cost, d_pred_q, d_field, d_ref, d_slot, d_ccost, s);
+                       });
 }
 
-// me_predict_kernel<SrcT, 0, 0, 1>: one launch, every block from the plane its reference index names
+// one launch of me_predict_kernel<SrcT, 0, 0, 1>: every block from the plane its reference index names
 int hmme_predict_refs_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp, const void* d_mv_field,
                              const void* d_ref_field, int mv_per_ctu, void* d_out, int out_pitch_bytes, void* stream) {
   if (!ctx) return HMME_ERR_ARG;
-  const char* who = "hmme_predict_refs_device";
-  int rc = bi_check(ctx, who, fp, 0);
+  PredictArgs a;
+  int rc = predict_args(ctx, "hmme_predict_refs_device", refs, n_refs, !d_ref_field || !d_out, fp, nullptr, d_mv_field, mv_per_ctu, out_pitch_bytes, &a);
   if (rc) return rc;
-  if (!refs || n_refs < 1 || n_refs > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d reference pictures outside 1..%d (or a null list)", who, n_refs, hmme::kMaxRefs);
-  if (!d_mv_field || !d_ref_field || !d_out || (mv_per_ctu != 1 && mv_per_ctu != 64))
-    return fail(ctx, HMME_ERR_ARG, "%s: null motion field / reference field / output image, or %d MVs per CTU (1 or 64)", who, mv_per_ctu);
-  for (int r = 0; r < n_refs; ++r)
-    if (!refs[r]) return fail(ctx, HMME_ERR_ARG, "%s: null plane", who);
-  if (out_pitch_bytes < refs[0]->width * refs[0]->bps) return fail(ctx, HMME_ERR_ARG, "%s: output pitch %d below a picture row", who, out_pitch_bytes);
-  hmme_frame_params f = *fp;
-  f.search_range = 1;   // not consulted: nothing is searched
   hipStream_t s = (hipStream_t)stream;
   PairLaunch pl;   // checks every plane: of this context, of one size, of fp's bit depth; each is ordered like a reference
-  rc = pairs_begin(ctx, refs, refs, n_refs, &f, s, &pl);
+  rc = pairs_begin(ctx, refs, refs, n_refs, &a.f, s, &pl);
   if (rc || pl.count == 0) return rc;
-  const hmme_plane* p0 = refs[0];
   const hmme::MePredRefs<1> pr = {pl.refs, (const uint8_t*)d_ref_field, n_refs};
-  const dim3 grid((unsigned)pl.count), block(256);
-  if (p0->bps == 1)
-    hipLaunchKernelGGL((hmme::me_predict_kernel<uint8_t, 0, 0, 1>), grid, block, 0, s, p0->origin(), p0->pitch, (const int16_t*)d_mv_field, mv_per_ctu, pl.first,
-                       p0->width, p0->height, p0->bit_depth, nullptr, 0, (uint8_t*)d_out, 0, 0, out_pitch_bytes, hmme::MePredWp<0>{}, pr);
-  else
-    hipLaunchKernelGGL((hmme::me_predict_kernel<uint16_t, 0, 0, 1>), grid, block, 0, s, p0->origin(), p0->pitch, (const int16_t*)d_mv_field, mv_per_ctu, pl.first,
-                       p0->width, p0->height, p0->bit_depth, nullptr, 0, (uint8_t*)d_out, 0, 0, out_pitch_bytes, hmme::MePredWp<0>{}, pr);
-  if (hipGetLastError() != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "%s: the launch failed", who);
-  return pairs_end(ctx, refs, refs, n_refs, s, rc);
+  rc = launch_predict(ctx, refs[0], (const int16_t*)d_mv_field, mv_per_ctu, pl.first, pl.count, false, nullptr, 0, (uint8_t*)d_out, 0, 0, out_pitch_bytes, s, nullptr, &pr);
+  return pairs_end(ctx, refs, refs, n_refs, s, rc);   // whatever the launch returned: the scratch is acquired
 }
 
 int hmme_predict_refs_frame(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp, const int16_t* mv_field,
@@ -2546,24 +2554,10 @@ int hmme_predict_refs_frame(hmme_ctx* ctx, const hmme_plane* const* refs, int n_
   if (rc) return rc;
   if (!refs || n_refs < 1 || n_refs > hmme::kMaxRefs || !refs[0]) return fail(ctx, HMME_ERR_ARG, "%s: %d reference pictures outside 1..%d (or a null plane)", who, n_refs, hmme::kMaxRefs);
   if (!mv_field || !ref_field || !out || (mv_per_ctu != 1 && mv_per_ctu != 64)) return fail(ctx, HMME_ERR_ARG, "%s: null argument, or %d MVs per CTU (1 or 64)", who, mv_per_ctu);
-  const hmme_plane* ref = refs[0];
-  if (ref->ctx != ctx) return fail(ctx, HMME_ERR_ARG, "plane belongs to another context (planes are used with the context that created them)");
-  if (out_stride < ref->width) return fail(ctx, HMME_ERR_ARG, "%s: output stride %d below the picture width", who, out_stride);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t blocks = (size_t)ref->n_ctu * mv_per_ctu, field_bytes = pad16(sizeof(int16_t) * 2 * blocks), row = (size_t)ref->width * ref->bps;
-  rc = ensure(ctx, &ctx->d_bi[0], &ctx->bi_cap[0], field_bytes + blocks);   // the motion field, behind it the reference field
-  if (rc == HMME_OK) rc = ensure(ctx, &ctx->d_bi[1], &ctx->bi_cap[1], row * ref->height);
-  if (rc) return rc;
-  hipStream_t s = ctx->stream;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_bi[0], mv_field, sizeof(int16_t) * 2 * blocks, hipMemcpyHostToDevice, s));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_bi[0] + field_bytes, ref_field, blocks, hipMemcpyHostToDevice, s));
-  // the caller's image travels both ways: samples outside the CTU range, and of blocks without a reference, come back as they were
-  HIP_TRY(ctx, hipMemcpy2DAsync(ctx->d_bi[1], row, out, (size_t)out_stride * ref->bps, row, ref->height, hipMemcpyHostToDevice, s));
-  rc = hmme_predict_refs_device(ctx, refs, n_refs, fp, ctx->d_bi[0], ctx->d_bi[0] + field_bytes, mv_per_ctu, ctx->d_bi[1], (int)row, s);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpy2DAsync(out, (size_t)out_stride * ref->bps, ctx->d_bi[1], row, row, ref->height, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  return HMME_OK;
+  // blocks without a reference, too, come back as they were
+  return predict_staged(ctx, who, refs[0], mv_field, ref_field, mv_per_ctu, out, out_stride, [&](void* d_field, void* d_ref_field, void* d_img, int pitch, hipStream_t s) {
+    return hmme_predict_refs_device(ctx, refs, n_refs, fp, d_field, d_ref_field, mv_per_ctu, d_img, pitch, s);
+  });
 }
 
 // ---- estimating explicit weighted-prediction parameters ----------------------------------------------------------------------------------------

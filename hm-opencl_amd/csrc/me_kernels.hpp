@@ -2392,6 +2392,49 @@ __device__ __forceinline__ void me_select_level(const MeSelect& a, const CostT* 
   else st.resolved = children;
 }
 
+// The decision over a CTU's slots in LDS and the stores that follow it: what both select kernels end in, one wave per CTU, lane = 8x8 block
+// in RASTER order inside the CTU.  o = the CTU's index in the outputs.  REFS: the slots carry a reference index (s_ref) that leaves
+// beside the field (out_ref) -- me_select_refs_kernel; without it both pointers are null and never looked at.
+template <bool REFS, typename CostT>
+__device__ __forceinline__ void me_select_decide_store(const MeSelect& a, const CostT* s_cost, const uint32_t* s_mv, const uint8_t* s_ref, uint32_t lambda_q16,
+                                                       int pred_x, int pred_y, int lane, int ctu_x, int ctu_y, long o, int pic_w, int pic_h,
+                                                       uint32_t* out_field, uint8_t* out_ref, uint16_t* out_slot, uint32_t* out_cost) {
+  const int bx = lane & 7, by = lane >> 3;
+  MeSelectState st = {0, -1, 0};
+  me_select_level<3>(a, s_cost, s_mv, lambda_q16, pred_x, pred_y, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
+  me_select_level<2>(a, s_cost, s_mv, lambda_q16, pred_x, pred_y, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
+  me_select_level<1>(a, s_cost, s_mv, lambda_q16, pred_x, pred_y, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
+  me_select_level<0>(a, s_cost, s_mv, lambda_q16, pred_x, pred_y, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
+  if (lane == 0 && out_cost) out_cost[o] = st.resolved > 0xffffffffull ? 0xffffffffu : (uint32_t)st.resolved;
+  // integer-pel MVs leave as quarter pels: both halves of the dword << 2, the two bits that cross into the upper half masked off
+  auto field_mv = [&](int slot) -> uint32_t {
+    const uint32_t m = s_mv[slot];
+    return a.mv_unit ? (m << 2) & 0xfffcfffcu : m;
+  };
+  if (a.per == 64) {
+    const int slot = st.leaf_depth < 0 ? 0xffff : me_select_pu_slot_at(st.leaf_depth, st.leaf_ps, bx * 8, by * 8);
+    out_field[o * 64 + lane] = slot == 0xffff ? 0u : field_mv(slot);
+    if constexpr (REFS) out_ref[o * 64 + lane] = slot == 0xffff ? (uint8_t)0xff : s_ref[slot];
+    if (out_slot) out_slot[o * 64 + lane] = (uint16_t)slot;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {   // the block's two rows of two 4x4 blocks
+      int slot[2];
+      uint32_t mv[2], ref[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        slot[i] = st.leaf_depth < 0 ? 0xffff : me_select_pu_slot_at(st.leaf_depth, st.leaf_ps, bx * 8 + 4 * i, by * 8 + 4 * j);
+        mv[i] = slot[i] == 0xffff ? 0u : field_mv(slot[i]);
+        if constexpr (REFS) ref[i] = slot[i] == 0xffff ? 0xffu : (uint32_t)s_ref[slot[i]];
+      }
+      const long e = o * 256 + (2 * by + j) * 16 + 2 * bx;   // even: 8-byte (MVs) / 4-byte (slots) / 2-byte (references) aligned pairs
+      *(uint2*)(out_field + e) = make_uint2(mv[0], mv[1]);
+      if constexpr (REFS) *(uint16_t*)(out_ref + e) = (uint16_t)(ref[0] | ref[1] << 8);
+      if (out_slot) *(uint32_t*)(out_slot + e) = (uint32_t)slot[0] | (uint32_t)slot[1] << 16;
+    }
+  }
+}
+
 // One wave per CTU, four CTUs per workgroup; blockIdx.y = picture pair.  The CTU's 593 costs and MVs are loaded coalesced into LDS (4.7 KB
 // per CTU), lane = 8x8 block in RASTER order inside the CTU -- the layout of the field, so that every store of the wave is one contiguous
 // run (256 B of MVs with one MV per 8x8 block; rows of 64 B with four).  mv_tab: int16 [n_pairs][ctu_count][593][2] read as dwords;
@@ -2420,37 +2463,8 @@ me_select_kernel(const uint32_t* __restrict__ mv_tab, const uint32_t* __restrict
   const int ctu_x = (ctu % ctus_x) * 64, ctu_y = (ctu / ctus_x) * 64;
   const long o = (long)pair * n_ctu + ctu;
   const int pred_x = pred_q ? pred_q[o * 2] : 0, pred_y = pred_q ? pred_q[o * 2 + 1] : 0;
-  const int bx = lane & 7, by = lane >> 3;
-  MeSelectState st = {0, -1, 0};
-  me_select_level<3>(a, s_cost[wave], s_mv[wave], lambda_q16, pred_x, pred_y, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
-  me_select_level<2>(a, s_cost[wave], s_mv[wave], lambda_q16, pred_x, pred_y, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
-  me_select_level<1>(a, s_cost[wave], s_mv[wave], lambda_q16, pred_x, pred_y, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
-  me_select_level<0>(a, s_cost[wave], s_mv[wave], lambda_q16, pred_x, pred_y, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
-  if (lane == 0 && out_cost) out_cost[o] = st.resolved > 0xffffffffull ? 0xffffffffu : (uint32_t)st.resolved;
-  // integer-pel MVs leave as quarter pels: both halves of the dword << 2, the two bits that cross into the upper half masked off
-  auto field_mv = [&](int slot) -> uint32_t {
-    const uint32_t m = s_mv[wave][slot];
-    return a.mv_unit ? (m << 2) & 0xfffcfffcu : m;
-  };
-  if (a.per == 64) {
-    const int slot = st.leaf_depth < 0 ? 0xffff : me_select_pu_slot_at(st.leaf_depth, st.leaf_ps, bx * 8, by * 8);
-    out_field[o * 64 + lane] = slot == 0xffff ? 0u : field_mv(slot);
-    if (out_slot) out_slot[o * 64 + lane] = (uint16_t)slot;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {   // the block's two rows of two 4x4 blocks
-      int slot[2];
-      uint32_t mv[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        slot[i] = st.leaf_depth < 0 ? 0xffff : me_select_pu_slot_at(st.leaf_depth, st.leaf_ps, bx * 8 + 4 * i, by * 8 + 4 * j);
-        mv[i] = slot[i] == 0xffff ? 0u : field_mv(slot[i]);
-      }
-      const long e = o * 256 + (2 * by + j) * 16 + 2 * bx;   // even: the pair of entries is 8-byte (MVs) / 4-byte (slots) aligned
-      *(uint2*)(out_field + e) = make_uint2(mv[0], mv[1]);
-      if (out_slot) *(uint32_t*)(out_slot + e) = (uint32_t)slot[0] | (uint32_t)slot[1] << 16;
-    }
-  }
+  me_select_decide_store<false>(a, s_cost[wave], s_mv[wave], nullptr, lambda_q16, pred_x, pred_y, lane, ctu_x, ctu_y, o, pic_w, pic_h, out_field, nullptr,
+                                out_slot, out_cost);
 }
 
 // ---- reference picture per PU (hmme_select_refs_device; the rule: include/hmme.h) --------------------------------------------------------
@@ -2464,9 +2478,9 @@ struct MeRefCost { uint32_t c[kMaxRefs]; };
 // dword, the reference -- in registers: no LDS traffic, no atomic and no cross-lane step in the reference loop; the predictor and the
 // price of a reference are wave-uniform.  The comparison is strict in the order 0, 1, ...: the lowest index wins ties
 // (TEncSearch.cpp:3086).  Behind the last reference the merged slots go to LDS (7.6 KB per CTU with the costs in 64 bits: unsaturated)
-// and the level functions of me_select_kernel decide on them, the MV cost -- already inside the merged cost, against each reference's own
-// predictor -- switched off.  Stores as in me_select_kernel; out_ref: uint8 [n_pics][n_ctu][per], a wave's bytes one run of 64 with one
-// MV per 8x8 block, pairs of them as one 16-bit store with four; 0xFF where no CU covers the block.  Bandwidth-sized like its sibling:
+// and me_select_decide_store decides on them as in me_select_kernel, the MV cost -- already inside the merged cost, against each
+// reference's own predictor -- switched off.  out_ref: uint8 [n_pics][n_ctu][per], a wave's bytes one run of 64 with one MV per 8x8
+// block, pairs of them as one 16-bit store with four; 0xFF where no CU covers the block.  Bandwidth-sized like its sibling:
 // n_refs x 7.1 KB in per CTU, under 2 KB out.
 __global__ void __launch_bounds__(256)
 me_select_refs_kernel(const uint32_t* __restrict__ mv_tab, const uint32_t* __restrict__ cost_tab, const int16_t* __restrict__ pred_q,
@@ -2515,42 +2529,10 @@ me_select_refs_kernel(const uint32_t* __restrict__ mv_tab, const uint32_t* __res
   if (!live) return;
   const int ctus_x = (pic_w + 63) >> 6;
   const int ctu_x = (ctu % ctus_x) * 64, ctu_y = (ctu / ctus_x) * 64;
-  const long o = (long)pic * n_ctu + ctu;
-  const int bx = lane & 7, by = lane >> 3;
   MeSelect merged = a;
   merged.price_mv = 0;   // priced above, per reference: not a second time
-  MeSelectState st = {0, -1, 0};
-  me_select_level<3>(merged, s_cost[wave], s_mv[wave], lambda_q16, 0, 0, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
-  me_select_level<2>(merged, s_cost[wave], s_mv[wave], lambda_q16, 0, 0, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
-  me_select_level<1>(merged, s_cost[wave], s_mv[wave], lambda_q16, 0, 0, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
-  me_select_level<0>(merged, s_cost[wave], s_mv[wave], lambda_q16, 0, 0, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
-  if (lane == 0 && out_cost) out_cost[o] = st.resolved > 0xffffffffull ? 0xffffffffu : (uint32_t)st.resolved;
-  auto field_mv = [&](int slot) -> uint32_t {   // as in me_select_kernel
-    const uint32_t m = s_mv[wave][slot];
-    return a.mv_unit ? (m << 2) & 0xfffcfffcu : m;
-  };
-  if (a.per == 64) {
-    const int slot = st.leaf_depth < 0 ? 0xffff : me_select_pu_slot_at(st.leaf_depth, st.leaf_ps, bx * 8, by * 8);
-    out_field[o * 64 + lane] = slot == 0xffff ? 0u : field_mv(slot);
-    out_ref[o * 64 + lane] = slot == 0xffff ? (uint8_t)0xff : s_ref[wave][slot];
-    if (out_slot) out_slot[o * 64 + lane] = (uint16_t)slot;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {   // the block's two rows of two 4x4 blocks
-      int slot[2];
-      uint32_t mv[2], ref[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        slot[i] = st.leaf_depth < 0 ? 0xffff : me_select_pu_slot_at(st.leaf_depth, st.leaf_ps, bx * 8 + 4 * i, by * 8 + 4 * j);
-        mv[i] = slot[i] == 0xffff ? 0u : field_mv(slot[i]);
-        ref[i] = slot[i] == 0xffff ? 0xffu : (uint32_t)s_ref[wave][slot[i]];
-      }
-      const long e = o * 256 + (2 * by + j) * 16 + 2 * bx;   // even: 8-byte (MVs) / 4-byte (slots) / 2-byte (references) aligned pairs
-      *(uint2*)(out_field + e) = make_uint2(mv[0], mv[1]);
-      *(uint16_t*)(out_ref + e) = (uint16_t)(ref[0] | ref[1] << 8);
-      if (out_slot) *(uint32_t*)(out_slot + e) = (uint32_t)slot[0] | (uint32_t)slot[1] << 16;
-    }
-  }
+  me_select_decide_store<true>(merged, s_cost[wave], s_mv[wave], s_ref[wave], lambda_q16, 0, 0, lane, ctu_x, ctu_y, (long)pic * n_ctu + ctu, pic_w, pic_h,
+                               out_field, out_ref, out_slot, out_cost);
 }
 
 // ---- estimating explicit weighted-prediction parameters (hmme_plane_stats / hmme_wp_estimate) ---------------------------------------------

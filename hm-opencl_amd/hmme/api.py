@@ -387,7 +387,7 @@ class Engine:
             pred_q = np.ascontiguousarray(pred_q, dtype=np.int16)
             assert pred_q.shape == (len(refs), n, 2)
             pq = pred_q.ctypes.data
-        arr = (C.c_void_p * len(refs))(*[r.h for r in refs])
+        arr = _handles(refs)
         self._check(self.L.hmme_search_frame_multi(self.h, cur.h, arr, len(refs), C.byref(fp), pq, mv.ctypes.data, sad.ctypes.data))
         return mv, sad
 
@@ -409,25 +409,25 @@ class Engine:
         return qmv, cost
 
     def refine_frame_multi_device(self, cur, refs, fp, d_pred, d_int_mv, use_hadamard, d_qmv, d_cost, stream=0):
-        arr = (C.c_void_p * len(refs))(*[r.h for r in refs])
+        arr = _handles(refs)
         self._check(self.L.hmme_refine_frame_multi_device(self.h, cur.h, arr, len(refs), C.byref(fp), d_pred, d_int_mv,
                                                           int(use_hadamard), d_qmv, d_cost, stream))
 
     def search_frame_multi_device(self, cur, refs, fp, d_pred, d_mv, d_sad, stream=0):
-        arr = (C.c_void_p * len(refs))(*[r.h for r in refs])
+        arr = _handles(refs)
         self._check(self.L.hmme_search_frame_multi_device(self.h, cur.h, arr, len(refs), C.byref(fp), d_pred, d_mv, d_sad, stream))
 
     def search_pairs_device(self, curs, refs, fp, d_pred, d_mv, d_sad, stream=0):
         """up to 16 (current, reference) picture pairs of one size in one launch (hmme_search_pairs_device)"""
         assert len(curs) == len(refs)
-        ca = (C.c_void_p * len(curs))(*[c.h for c in curs])
-        ra = (C.c_void_p * len(refs))(*[r.h for r in refs])
+        ca = _handles(curs)
+        ra = _handles(refs)
         self._check(self.L.hmme_search_pairs_device(self.h, ca, ra, len(refs), C.byref(fp), d_pred, d_mv, d_sad, stream))
 
     def refine_pairs_device(self, curs, refs, fp, d_pred, d_int_mv, use_hadamard, d_qmv, d_cost, stream=0):
         assert len(curs) == len(refs)
-        ca = (C.c_void_p * len(curs))(*[c.h for c in curs])
-        ra = (C.c_void_p * len(refs))(*[r.h for r in refs])
+        ca = _handles(curs)
+        ra = _handles(refs)
         self._check(self.L.hmme_refine_pairs_device(self.h, ca, ra, len(refs), C.byref(fp), d_pred, d_int_mv, int(use_hadamard),
                                                     d_qmv, d_cost, stream))
 
@@ -470,15 +470,15 @@ class Engine:
     def search_pairs_w_device(self, curs, refs, fp, weights, d_pred, d_mv, d_sad, stream=0):
         """hmme_search_pairs_w_device: up to 16 pairs in one launch, weights = one (w0, offset, shift, round) per pair"""
         assert len(curs) == len(refs) == len(weights)
-        ca = (C.c_void_p * len(curs))(*[c.h for c in curs])
-        ra = (C.c_void_p * len(refs))(*[r.h for r in refs])
+        ca = _handles(curs)
+        ra = _handles(refs)
         wa = (Weight * len(weights))(*[Weight(*[int(v) for v in w]) for w in weights])
         self._check(self.L.hmme_search_pairs_w_device(self.h, ca, ra, len(refs), C.byref(fp), wa, d_pred, d_mv, d_sad, stream))
 
     def refine_pairs_w_device(self, curs, refs, fp, weights, d_pred, d_int_mv, use_hadamard, d_qmv, d_cost, stream=0):
         assert len(curs) == len(refs) == len(weights)
-        ca = (C.c_void_p * len(curs))(*[c.h for c in curs])
-        ra = (C.c_void_p * len(refs))(*[r.h for r in refs])
+        ca = _handles(curs)
+        ra = _handles(refs)
         wa = (Weight * len(weights))(*[Weight(*[int(v) for v in w]) for w in weights])
         self._check(self.L.hmme_refine_pairs_w_device(self.h, ca, ra, len(refs), C.byref(fp), wa, d_pred, d_int_mv, int(use_hadamard),
                                                       d_qmv, d_cost, stream))
@@ -508,10 +508,19 @@ class Engine:
         assert a.shape == (n_ctu, 2)
         return a, a.ctypes.data
 
+    @staticmethod
+    def _image(ref, out):
+        """the image argument of the predict_* methods: `out`, or zeros when None, of the plane's size and sample type"""
+        dt = np.uint8 if ref.bit_depth == 8 else np.uint16
+        if out is None:
+            out = np.zeros((ref.height, ref.width), dt)
+        assert out.dtype == dt and out.shape == (ref.height, ref.width) and out.flags.c_contiguous
+        return out
+
     def predict_pairs_device(self, refs, fp, d_mv_field, mv_per_ctu, d_outs, out_pitch_bytes, stream=0):
         """hmme_predict_pairs_device: the luma prediction of up to 16 pictures from their motion fields; d_outs = one device image address per picture"""
         assert len(refs) == len(d_outs)
-        ra = (C.c_void_p * len(refs))(*[r.h for r in refs])
+        ra = _handles(refs)
         oa = (C.c_void_p * len(d_outs))(*[int(o) for o in d_outs])
         self._check(self.L.hmme_predict_pairs_device(self.h, ra, len(refs), C.byref(fp), d_mv_field, int(mv_per_ctu), oa, int(out_pitch_bytes), stream))
 
@@ -520,10 +529,7 @@ class Engine:
         mv_field: int16[n_ctu, 2] or [n_ctu, 1 | 64, 2] quarter pels; `out` (same shape and type) keeps its samples outside the CTU range"""
         n = self.L.hmme_num_ctus(ref.width, ref.height)
         f, per = self._field(mv_field, n)
-        dt = np.uint8 if ref.bit_depth == 8 else np.uint16
-        if out is None:
-            out = np.zeros((ref.height, ref.width), dt)
-        assert out.dtype == dt and out.shape == (ref.height, ref.width) and out.flags.c_contiguous
+        out = self._image(ref, out)
         fp = FrameParams(1, 0, ref.bit_depth, ctu_first, ctu_count)
         self._check(self.L.hmme_predict_frame(self.h, ref.h, C.byref(fp), f.ctypes.data, per, out.ctypes.data, out.shape[1]))
         return out
@@ -531,49 +537,46 @@ class Engine:
     def search_pairs_bi_device(self, curs, refs, others, fp, d_other_mv, mv_per_ctu, d_center, d_pred, d_mv, d_sad, stream=0):
         """hmme_search_pairs_bi_device: the bi-prediction pass of up to 16 pairs in one launch (origin 2 * cur - prediction of others[i])"""
         assert len(curs) == len(refs) == len(others)
-        ca = (C.c_void_p * len(curs))(*[c.h for c in curs])
-        ra = (C.c_void_p * len(refs))(*[r.h for r in refs])
-        oa = (C.c_void_p * len(others))(*[o.h for o in others])
+        ca = _handles(curs)
+        ra = _handles(refs)
+        oa = _handles(others)
         self._check(self.L.hmme_search_pairs_bi_device(self.h, ca, ra, oa, len(refs), C.byref(fp), d_other_mv, int(mv_per_ctu), d_center, d_pred,
                                                        d_mv, d_sad, stream))
 
     def refine_pairs_bi_device(self, curs, refs, others, fp, d_other_mv, mv_per_ctu, d_center, d_pred, d_int_mv, use_hadamard, d_qmv, d_cost, stream=0):
         assert len(curs) == len(refs) == len(others)
-        ca = (C.c_void_p * len(curs))(*[c.h for c in curs])
-        ra = (C.c_void_p * len(refs))(*[r.h for r in refs])
-        oa = (C.c_void_p * len(others))(*[o.h for o in others])
+        ca = _handles(curs)
+        ra = _handles(refs)
+        oa = _handles(others)
         self._check(self.L.hmme_refine_pairs_bi_device(self.h, ca, ra, oa, len(refs), C.byref(fp), d_other_mv, int(mv_per_ctu), d_center, d_pred,
                                                        d_int_mv, int(use_hadamard), d_qmv, d_cost, stream))
 
-    def search_frame_bi(self, cur, ref, other, sr, other_mv, center_q=None, pred_q=None, fen=1, ctu_first=0, ctu_count=-1):
-        """hmme_search_frame_bi: one pair, host arrays -> (mv int16[count,593,2], sad uint32[count,593]).  other_mv: the motion field of `other`
-        (int16[n_ctu, 2] or [n_ctu, 1 | 64, 2]); center_q: window centres int16[n_ctu, 2] (None: the predictors)"""
+    def _frame_bi(self, entry, cur, ref, other, sr, fen, weights, other_mv, int_mv, center_q, pred_q, use_hadamard, ctu_first, ctu_count):
+        """the four *_frame_bi* methods: weights = (wp, other_wp) for the *_w entries, else (); int_mv: None for a search -> the two result tables"""
         n = self.L.hmme_num_ctus(cur.width, cur.height)
         count = n - ctu_first if ctu_count < 0 else ctu_count
         fp = FrameParams(sr, int(fen), cur.bit_depth, ctu_first, count)
         f, per = self._field(other_mv, n)
         cq, cptr = self._pq(center_q, n)
         pq, pptr = self._pq(pred_q, n)
+        args = [C.byref(Weight(*[int(v) for v in w])) for w in weights] + [f.ctypes.data, per, cptr, pptr]
+        if int_mv is not None:
+            int_mv = np.ascontiguousarray(int_mv, dtype=np.int16)
+            assert int_mv.shape == (count, NUM_PARTS, 2)
+            args += [int_mv.ctypes.data, int(use_hadamard)]
         mv = np.zeros((count, NUM_PARTS, 2), np.int16)
-        sad = np.zeros((count, NUM_PARTS), np.uint32)
-        self._check(self.L.hmme_search_frame_bi(self.h, cur.h, ref.h, other.h, C.byref(fp), f.ctypes.data, per, cptr, pptr, mv.ctypes.data, sad.ctypes.data))
-        return mv, sad
+        cost = np.zeros((count, NUM_PARTS), np.uint32)
+        self._check(entry(self.h, cur.h, ref.h, other.h, C.byref(fp), *args, mv.ctypes.data, cost.ctypes.data))
+        return mv, cost
+
+    def search_frame_bi(self, cur, ref, other, sr, other_mv, center_q=None, pred_q=None, fen=1, ctu_first=0, ctu_count=-1):
+        """hmme_search_frame_bi: one pair, host arrays -> (mv int16[count,593,2], sad uint32[count,593]).  other_mv: the motion field of `other`
+        (int16[n_ctu, 2] or [n_ctu, 1 | 64, 2]); center_q: window centres int16[n_ctu, 2] (None: the predictors)"""
+        return self._frame_bi(self.L.hmme_search_frame_bi, cur, ref, other, sr, fen, (), other_mv, None, center_q, pred_q, True, ctu_first, ctu_count)
 
     def refine_frame_bi(self, cur, ref, other, sr, other_mv, int_mv, center_q=None, pred_q=None, use_hadamard=True, ctu_first=0, ctu_count=-1):
         """hmme_refine_frame_bi: xPatternSearchFracDIF of integer winners against the bi-prediction origin -> (qmv int16[count,593,2], cost uint32[count,593])"""
-        n = self.L.hmme_num_ctus(cur.width, cur.height)
-        count = n - ctu_first if ctu_count < 0 else ctu_count
-        fp = FrameParams(sr, 1, cur.bit_depth, ctu_first, count)
-        f, per = self._field(other_mv, n)
-        cq, cptr = self._pq(center_q, n)
-        pq, pptr = self._pq(pred_q, n)
-        int_mv = np.ascontiguousarray(int_mv, dtype=np.int16)
-        assert int_mv.shape == (count, NUM_PARTS, 2)
-        qmv = np.zeros((count, NUM_PARTS, 2), np.int16)
-        cost = np.zeros((count, NUM_PARTS), np.uint32)
-        self._check(self.L.hmme_refine_frame_bi(self.h, cur.h, ref.h, other.h, C.byref(fp), f.ctypes.data, per, cptr, pptr, int_mv.ctypes.data,
-                                                int(use_hadamard), qmv.ctypes.data, cost.ctypes.data))
-        return qmv, cost
+        return self._frame_bi(self.L.hmme_refine_frame_bi, cur, ref, other, sr, 1, (), other_mv, int_mv, center_q, pred_q, use_hadamard, ctu_first, ctu_count)
 
     # ---- ... in a slice with explicit weighted prediction (include/hmme.h, "bi-prediction with explicit weighted prediction"): weights are
     # (w0, offset, shift, round); `wp` / `weights` belong to the searched list, `other_wp` / `other_weights` to the list whose prediction is subtracted
@@ -584,7 +587,7 @@ class Engine:
     def predict_pairs_w_device(self, refs, fp, weights, d_mv_field, mv_per_ctu, d_outs, out_pitch_bytes, stream=0):
         """hmme_predict_pairs_w_device: predict_pairs_device with one weight per picture (the prediction HM's motionCompensation writes in a WP slice)"""
         assert len(refs) == len(d_outs) == len(weights)
-        ra = (C.c_void_p * len(refs))(*[r.h for r in refs])
+        ra = _handles(refs)
         oa = (C.c_void_p * len(d_outs))(*[int(o) for o in d_outs])
         self._check(self.L.hmme_predict_pairs_w_device(self.h, ra, len(refs), C.byref(fp), self._weights(weights), d_mv_field, int(mv_per_ctu), oa,
                                                        int(out_pitch_bytes), stream))
@@ -593,10 +596,7 @@ class Engine:
         """hmme_predict_frame_w: predict_frame with the weight wp"""
         n = self.L.hmme_num_ctus(ref.width, ref.height)
         f, per = self._field(mv_field, n)
-        dt = np.uint8 if ref.bit_depth == 8 else np.uint16
-        if out is None:
-            out = np.zeros((ref.height, ref.width), dt)
-        assert out.dtype == dt and out.shape == (ref.height, ref.width) and out.flags.c_contiguous
+        out = self._image(ref, out)
         fp = FrameParams(1, 0, ref.bit_depth, ctu_first, ctu_count)
         w = Weight(*[int(v) for v in wp])
         self._check(self.L.hmme_predict_frame_w(self.h, ref.h, C.byref(fp), C.byref(w), f.ctypes.data, per, out.ctypes.data, out.shape[1]))
@@ -605,53 +605,30 @@ class Engine:
     def search_pairs_bi_w_device(self, curs, refs, others, fp, weights, other_weights, d_other_mv, mv_per_ctu, d_center, d_pred, d_mv, d_sad, stream=0):
         """hmme_search_pairs_bi_w_device: the bi-prediction pass of up to 16 pairs of a WP slice in one launch"""
         assert len(curs) == len(refs) == len(others) == len(weights) == len(other_weights)
-        ca = (C.c_void_p * len(curs))(*[c.h for c in curs])
-        ra = (C.c_void_p * len(refs))(*[r.h for r in refs])
-        oa = (C.c_void_p * len(others))(*[o.h for o in others])
+        ca = _handles(curs)
+        ra = _handles(refs)
+        oa = _handles(others)
         self._check(self.L.hmme_search_pairs_bi_w_device(self.h, ca, ra, oa, len(refs), C.byref(fp), self._weights(weights), self._weights(other_weights),
                                                          d_other_mv, int(mv_per_ctu), d_center, d_pred, d_mv, d_sad, stream))
 
     def refine_pairs_bi_w_device(self, curs, refs, others, fp, weights, other_weights, d_other_mv, mv_per_ctu, d_center, d_pred, d_int_mv, use_hadamard,
                                  d_qmv, d_cost, stream=0):
         assert len(curs) == len(refs) == len(others) == len(weights) == len(other_weights)
-        ca = (C.c_void_p * len(curs))(*[c.h for c in curs])
-        ra = (C.c_void_p * len(refs))(*[r.h for r in refs])
-        oa = (C.c_void_p * len(others))(*[o.h for o in others])
+        ca = _handles(curs)
+        ra = _handles(refs)
+        oa = _handles(others)
         self._check(self.L.hmme_refine_pairs_bi_w_device(self.h, ca, ra, oa, len(refs), C.byref(fp), self._weights(weights), self._weights(other_weights),
                                                          d_other_mv, int(mv_per_ctu), d_center, d_pred, d_int_mv, int(use_hadamard), d_qmv, d_cost, stream))
 
     def search_frame_bi_w(self, cur, ref, other, sr, wp, other_wp, other_mv, center_q=None, pred_q=None, fen=0, ctu_first=0, ctu_count=-1):
         """hmme_search_frame_bi_w: search_frame_bi in a WP slice (fen is passed through and not consulted by the engine)
         -> (mv int16[count,593,2], sad uint32[count,593])"""
-        n = self.L.hmme_num_ctus(cur.width, cur.height)
-        count = n - ctu_first if ctu_count < 0 else ctu_count
-        fp = FrameParams(sr, int(fen), cur.bit_depth, ctu_first, count)
-        f, per = self._field(other_mv, n)
-        cq, cptr = self._pq(center_q, n)
-        pq, pptr = self._pq(pred_q, n)
-        mv = np.zeros((count, NUM_PARTS, 2), np.int16)
-        sad = np.zeros((count, NUM_PARTS), np.uint32)
-        w, ow = Weight(*[int(v) for v in wp]), Weight(*[int(v) for v in other_wp])
-        self._check(self.L.hmme_search_frame_bi_w(self.h, cur.h, ref.h, other.h, C.byref(fp), C.byref(w), C.byref(ow), f.ctypes.data, per, cptr, pptr,
-                                                  mv.ctypes.data, sad.ctypes.data))
-        return mv, sad
+        return self._frame_bi(self.L.hmme_search_frame_bi_w, cur, ref, other, sr, fen, (wp, other_wp), other_mv, None, center_q, pred_q, True, ctu_first, ctu_count)
 
     def refine_frame_bi_w(self, cur, ref, other, sr, wp, other_wp, other_mv, int_mv, center_q=None, pred_q=None, use_hadamard=True, ctu_first=0, ctu_count=-1):
         """hmme_refine_frame_bi_w: refine_frame_bi in a WP slice -> (qmv int16[count,593,2], cost uint32[count,593])"""
-        n = self.L.hmme_num_ctus(cur.width, cur.height)
-        count = n - ctu_first if ctu_count < 0 else ctu_count
-        fp = FrameParams(sr, 0, cur.bit_depth, ctu_first, count)
-        f, per = self._field(other_mv, n)
-        cq, cptr = self._pq(center_q, n)
-        pq, pptr = self._pq(pred_q, n)
-        int_mv = np.ascontiguousarray(int_mv, dtype=np.int16)
-        assert int_mv.shape == (count, NUM_PARTS, 2)
-        qmv = np.zeros((count, NUM_PARTS, 2), np.int16)
-        cost = np.zeros((count, NUM_PARTS), np.uint32)
-        w, ow = Weight(*[int(v) for v in wp]), Weight(*[int(v) for v in other_wp])
-        self._check(self.L.hmme_refine_frame_bi_w(self.h, cur.h, ref.h, other.h, C.byref(fp), C.byref(w), C.byref(ow), f.ctypes.data, per, cptr, pptr,
-                                                  int_mv.ctypes.data, int(use_hadamard), qmv.ctypes.data, cost.ctypes.data))
-        return qmv, cost
+        return self._frame_bi(self.L.hmme_refine_frame_bi_w, cur, ref, other, sr, 0, (wp, other_wp), other_mv, int_mv, center_q, pred_q, use_hadamard, ctu_first,
+                              ctu_count)
 
     # ---- partition decision and motion field from the 593-slot tables (include/hmme.h, "partition decision and motion field") ----
     def select_pairs_device(self, width, height, n_pairs, fp, sel, d_mv, d_cost, d_pred, d_field, d_slot=None, d_ctu_cost=None, stream=0):
@@ -661,26 +638,37 @@ class Engine:
         self._check(self.L.hmme_select_pairs_device(self.h, int(width), int(height), int(n_pairs), C.byref(fp), C.byref(sel), d_mv, d_cost, d_pred,
                                                     d_field, d_slot, d_ctu_cost, stream))
 
+    def _select_frame(self, call, lead, width, height, mv, cost, pred_q, ctu_first, ctu_count, outs):
+        """select_frame (lead = ()) and select_refs_frame (lead = (n_refs,): the dimension mv, cost and pred_q carry in front).  call(fp, *addresses)
+        -> the C entry's return code; outs: (array or None, dtype, shape behind n_ctu) per output of the entry, in its order -> the arrays, zeros
+        where None was passed"""
+        n = self.L.hmme_num_ctus(width, height)
+        count = n - ctu_first if ctu_count < 0 else ctu_count
+        fp = FrameParams(1, 0, 8, ctu_first, count)
+        mv = np.ascontiguousarray(mv, dtype=np.int16)
+        cost = np.ascontiguousarray(cost, dtype=np.uint32)
+        assert mv.shape == lead + (count, NUM_PARTS, 2) and cost.shape == lead + (count, NUM_PARTS)
+        pptr = None
+        if pred_q is not None:
+            pq = np.ascontiguousarray(pred_q, dtype=np.int16)
+            assert pq.shape == lead + (n, 2)
+            pptr = pq.ctypes.data
+        arrays = []
+        for a, dt, shape in outs:
+            a = np.zeros((n,) + shape, dt) if a is None else a
+            assert a.dtype == dt and a.shape == (n,) + shape and a.flags.c_contiguous
+            arrays.append(a)
+        self._check(call(fp, mv.ctypes.data, cost.ctypes.data, pptr, *[a.ctypes.data for a in arrays]))
+        return tuple(arrays)
+
     def select_frame(self, width, height, sel, mv, cost, pred_q=None, ctu_first=0, ctu_count=-1, field=None, slot=None, ctu_cost=None):
         """hmme_select_frame: one pair, host arrays.  mv int16[count, 593, 2], cost uint32[count, 593] -> (field int16[n_ctu, mv_per_ctu, 2],
         slot uint16[n_ctu, mv_per_ctu], ctu_cost uint32[n_ctu]); entries outside the CTU range keep the values of the arrays passed in (zeros
         when none is)"""
-        n = self.L.hmme_num_ctus(width, height)
-        count = n - ctu_first if ctu_count < 0 else ctu_count
-        fp = FrameParams(1, 0, 8, ctu_first, count)
         per = int(sel.mv_per_ctu)
-        mv = np.ascontiguousarray(mv, dtype=np.int16)
-        cost = np.ascontiguousarray(cost, dtype=np.uint32)
-        assert mv.shape == (count, NUM_PARTS, 2) and cost.shape == (count, NUM_PARTS)
-        pq, pptr = self._pq(pred_q, n)
-        field = np.zeros((n, per, 2), np.int16) if field is None else field
-        slot = np.zeros((n, per), np.uint16) if slot is None else slot
-        ctu_cost = np.zeros(n, np.uint32) if ctu_cost is None else ctu_cost
-        for a, dt, shape in ((field, np.int16, (n, per, 2)), (slot, np.uint16, (n, per)), (ctu_cost, np.uint32, (n,))):
-            assert a.dtype == dt and a.shape == shape and a.flags.c_contiguous
-        self._check(self.L.hmme_select_frame(self.h, int(width), int(height), C.byref(fp), C.byref(sel), mv.ctypes.data, cost.ctypes.data, pptr,
-                                             field.ctypes.data, slot.ctypes.data, ctu_cost.ctypes.data))
-        return field, slot, ctu_cost
+        call = lambda fp, *a: self.L.hmme_select_frame(self.h, int(width), int(height), C.byref(fp), C.byref(sel), *a)
+        return self._select_frame(call, (), width, height, mv, cost, pred_q, ctu_first, ctu_count,
+                                  ((field, np.int16, (per, 2)), (slot, np.uint16, (per,)), (ctu_cost, np.uint32, ())))
 
     # ---- the reference picture per PU, and the prediction from it (include/hmme.h, "the reference picture per PU") ----
     def select_refs_device(self, width, height, n_pics, n_refs, fp, sel, ref_cost, d_mv, d_cost, d_pred, d_field, d_ref, d_slot=None, d_ctu_cost=None,
@@ -697,34 +685,16 @@ class Engine:
         """hmme_select_refs_frame: one picture, host arrays.  mv int16[n_refs, count, 593, 2], cost uint32[n_refs, count, 593], pred_q
         int16[n_refs, n_ctu, 2] or None -> (field int16[n_ctu, mv_per_ctu, 2], ref uint8[n_ctu, mv_per_ctu], slot uint16[n_ctu, mv_per_ctu],
         ctu_cost uint32[n_ctu]); entries outside the CTU range keep the values of the arrays passed in (zeros when none is)"""
-        n = self.L.hmme_num_ctus(width, height)
-        count = n - ctu_first if ctu_count < 0 else ctu_count
-        fp = FrameParams(1, 0, 8, ctu_first, count)
         per = int(sel.mv_per_ctu)
-        mv = np.ascontiguousarray(mv, dtype=np.int16)
-        cost = np.ascontiguousarray(cost, dtype=np.uint32)
-        n_refs = mv.shape[0]
-        assert mv.shape == (n_refs, count, NUM_PARTS, 2) and cost.shape == (n_refs, count, NUM_PARTS)
-        pq = pptr = None
-        if pred_q is not None:
-            pq = np.ascontiguousarray(pred_q, dtype=np.int16)
-            assert pq.shape == (n_refs, n, 2)
-            pptr = pq.ctypes.data
-        field = np.zeros((n, per, 2), np.int16) if field is None else field
-        ref = np.zeros((n, per), np.uint8) if ref is None else ref
-        slot = np.zeros((n, per), np.uint16) if slot is None else slot
-        ctu_cost = np.zeros(n, np.uint32) if ctu_cost is None else ctu_cost
-        for a, dt, shape in ((field, np.int16, (n, per, 2)), (ref, np.uint8, (n, per)), (slot, np.uint16, (n, per)), (ctu_cost, np.uint32, (n,))):
-            assert a.dtype == dt and a.shape == shape and a.flags.c_contiguous
-        self._check(self.L.hmme_select_refs_frame(self.h, int(width), int(height), n_refs, C.byref(fp), C.byref(sel), _ref_cost(ref_cost, n_refs),
-                                                  mv.ctypes.data, cost.ctypes.data, pptr, field.ctypes.data, ref.ctypes.data, slot.ctypes.data,
-                                                  ctu_cost.ctypes.data))
-        return field, ref, slot, ctu_cost
+        n_refs = np.shape(mv)[0]
+        call = lambda fp, *a: self.L.hmme_select_refs_frame(self.h, int(width), int(height), n_refs, C.byref(fp), C.byref(sel), _ref_cost(ref_cost, n_refs), *a)
+        return self._select_frame(call, (n_refs,), width, height, mv, cost, pred_q, ctu_first, ctu_count,
+                                  ((field, np.int16, (per, 2)), (ref, np.uint8, (per,)), (slot, np.uint16, (per,)), (ctu_cost, np.uint32, ())))
 
     def predict_refs_device(self, refs, fp, d_mv_field, d_ref_field, mv_per_ctu, d_out, out_pitch_bytes, stream=0):
         """hmme_predict_refs_device: the luma prediction of one picture, every block from the plane of `refs` its reference index names
         (d_ref_field uint8[n_ctu, mv_per_ctu]; blocks with an index >= len(refs) are not written); d_out = the device image"""
-        ra = (C.c_void_p * len(refs))(*[r.h for r in refs])
+        ra = _handles(refs)
         self._check(self.L.hmme_predict_refs_device(self.h, ra, len(refs), C.byref(fp), d_mv_field, d_ref_field, int(mv_per_ctu), d_out,
                                                     int(out_pitch_bytes), stream))
 
@@ -738,12 +708,9 @@ class Engine:
         f, per = self._field(mv_field, n)
         rf = np.ascontiguousarray(ref_field, dtype=np.uint8).reshape(n, -1)
         assert rf.shape == (n, per)
-        dt = np.uint8 if r0.bit_depth == 8 else np.uint16
-        if out is None:
-            out = np.zeros((r0.height, r0.width), dt)
-        assert out.dtype == dt and out.shape == (r0.height, r0.width) and out.flags.c_contiguous
+        out = self._image(r0, out)
         fp = FrameParams(1, 0, r0.bit_depth, ctu_first, ctu_count)
-        ra = (C.c_void_p * len(refs))(*[r.h for r in refs])
+        ra = _handles(refs)
         self._check(self.L.hmme_predict_refs_frame(self.h, ra, len(refs), C.byref(fp), f.ctypes.data, rf.ctypes.data, per, out.ctypes.data, out.shape[1]))
         return out
 
@@ -760,7 +727,7 @@ class Engine:
         denominator at 6, at 7 with more than three references) -> (weights, infos): one (w0, offset, shift, round) per reference, as the *_w
         calls take it, and one WpInfo each"""
         n = len(refs)
-        ra = (C.c_void_p * n)(*[r.h for r in refs])
+        ra = _handles(refs)
         wa, ia = (Weight * max(n, 1))(), (WpInfo * max(n, 1))()
         self._check(self.L.hmme_wp_estimate(self.h, cur.h, ra, n, int(log2_denom_start), wa, ia))
         return [(w.w0, w.offset, w.shift, w.round) for w in wa[:n]], list(ia[:n])
@@ -768,7 +735,7 @@ class Engine:
     def time_wp_estimate_passes(self, cur, refs, wp, stream=0, reps=5):
         """device time in ms of the estimator's passes on their own -> (the two statistics launches over `cur`, the SAD pass against `refs`)"""
         a, b = C.c_float(), C.c_float()
-        ra = (C.c_void_p * len(refs))(*[r.h for r in refs])
+        ra = _handles(refs)
         w = Weight(*[int(v) for v in wp])
         self._check(self.L.hmme_test_time_wp_estimate_passes(self.h, cur.h, ra, len(refs), C.byref(w), stream, reps, C.byref(a), C.byref(b)))
         return float(a.value), float(b.value)
@@ -827,6 +794,11 @@ def bipred_weight_check(bit_depth, wp, other_wp, refine=False):
 def select_check(sel):
     """hmme_select_check: 0, or HMME_ERR_ARG when a field of the SelectParams lies outside its range (pure host arithmetic: needs no GPU)"""
     return int(load().hmme_select_check(C.byref(sel)))
+
+
+def _handles(planes):
+    """the handles of a list of planes as the array of pointers the C calls take"""
+    return (C.c_void_p * len(planes))(*[p.h for p in planes])
 
 
 def _ref_cost(ref_cost, n_refs):

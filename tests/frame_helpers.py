@@ -120,6 +120,27 @@ def oracle_bi_search(oracle_lib, org, ref, w, h, sr, center, pred, lq, fen, bd, 
     return mv, sad
 
 
+def check_strided_image(w, h, bd, wrapper, entry, spare=24):
+    """A host prediction call into an image whose stride exceeds the picture width (the Python wrappers always pass the width), once over the
+    whole picture and once over CTU 1 alone.  wrapper(out, ctu_first, ctu_count) -> the Python method's result into the contiguous `out`;
+    entry(fp, out_address, out_stride) -> the return code of the C entry.  The picture columns equal the contiguous result bit for bit; the
+    spare columns, and the picture outside the CTU range, keep the sentinel."""
+    from hmme import api
+    dt, sentinel = (np.uint8, 0xA5) if bd == 8 else (np.uint16, 0xA5A5)
+    for first, count in ((0, -1), (1, 1)):
+        want = wrapper(np.full((h, w), sentinel, dt), first, count)
+        img = np.full((h, w + spare), sentinel, dt)
+        assert entry(api.FrameParams(1, 0, bd, first, count), img.ctypes.data, w + spare) == 0
+        assert np.array_equal(img[:, :w], want) and (want != sentinel).any()
+        assert (img[:, w:] == sentinel).all()
+        if count > 0:
+            inside = np.zeros((h, w), bool)
+            for ctu in range(first, first + count):
+                x, y = ctu_origin(ctu, w)
+                inside[y:y + 64, x:x + 64] = True
+            assert (img[:, :w][~inside] == sentinel).all()
+
+
 def random_field(n_ctu, per, seed, max_pel=6):
     rng = np.random.default_rng(seed)
     return rng.integers(-4 * max_pel, 4 * max_pel + 1, size=(n_ctu, per, 2)).astype(np.int16)

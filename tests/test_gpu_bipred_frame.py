@@ -6,7 +6,7 @@ Pictures are sized so that no case needs more than about a minute of oracle time
 import numpy as np
 import pytest
 
-from frame_helpers import (bind_hmo, dims, mkplane, oracle_bi_search, oracle_prediction, origin_picture, random_field, run_bi_search,
+from frame_helpers import (bind_hmo, check_strided_image, dims, mkplane, oracle_bi_search, oracle_prediction, origin_picture, random_field, run_bi_search,
                            three_planes)
 
 pytestmark = pytest.mark.gpu
@@ -66,6 +66,17 @@ def test_prediction_equals_the_oracle_at_every_phase(engine, hmo, bd, per):
         assert np.all(img[~inside] == sentinel)
     finally:
         pr.close()
+    # ... and into an image whose stride exceeds the width, on 3 x 2 CTUs
+    import ctypes as C
+    sw, sh = 136, 72
+    _, sref, _ = synth.make_pair(sw, sh, seed=13 + bd, bit_depth=bd, max_mv=4, region=64)
+    sfield = random_field(6, per, 9 + bd + per)
+    ps = mkplane(engine, sref, sw, sh, bd)
+    try:
+        check_strided_image(sw, sh, bd, lambda out, first, count: engine.predict_frame(ps, sfield, out=out, ctu_first=first, ctu_count=count),
+                            lambda fp, out, stride: engine.L.hmme_predict_frame(engine.h, ps.h, C.byref(fp), sfield.ctypes.data, per, out, stride))
+    finally:
+        ps.close()
 
 
 # ---- 2: the bi search against the oracle, all 593 slots of every CTU -----------------------------------------------------------

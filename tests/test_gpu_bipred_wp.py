@@ -8,7 +8,7 @@ import pytest
 
 import bipred_wp_model as model
 import range_content as rc
-from frame_helpers import bind_hmo, device_tables, dims, mkplane, random_field, three_planes
+from frame_helpers import bind_hmo, check_strided_image, device_tables, dims, mkplane, random_field, three_planes
 
 pytestmark = pytest.mark.gpu
 
@@ -180,6 +180,11 @@ def test_weighted_prediction_equals_the_model(engine, hmo, bd, per):
             x, y = (ctu % cx_n) * 64, (ctu // cx_n) * 64
             inside[y:y + 64, x:x + 64] = True
         assert np.array_equal(img[inside].astype(np.int64), want[inside]) and np.all(img[~inside] == sentinel)
+        # ... and into an image whose stride exceeds the width
+        import ctypes as C
+        cw = api.Weight(*wp)
+        check_strided_image(W, H, bd, lambda out, first, count: engine.predict_frame_w(pr, wp, f, out=out, ctu_first=first, ctu_count=count),
+                            lambda fp, out, stride: engine.L.hmme_predict_frame_w(engine.h, pr.h, C.byref(fp), C.byref(cw), f.ctypes.data, per, out, stride))
         # two pictures with two weights in one launch == one at a time
         import torch
         dev = torch.device("cuda", 0)

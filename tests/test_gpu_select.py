@@ -302,6 +302,25 @@ def test_ctu_sub_range_and_null_outputs(engine, mv_cost, tables40):
         assert (slot == S_FILL).all() and (cc == C_FILL).all()                               # NULL outputs: nothing written anywhere
         field, slot, cc = device_select(engine, 512, 320, m, c, sel, None, first, cnt, want_slot=True, want_cost=False)
         assert np.array_equal(slot[:, first:first + cnt], ms) and (cc == C_FILL).all()
+    # the host-facing call with NULL for out_slot, out_cost and both (the Python method always passes every array), on a sub-range of 3 x 2 CTUs:
+    # the field is the full call's, an array that was not passed is not written
+    import ctypes as C
+    w, h, n, first, cnt = 136, 72, 6, 1, 4
+    fp = api.FrameParams(1, 0, 8, first, cnt)
+    t_mv, t_cost = np.ascontiguousarray(mv[first:first + cnt]), np.ascontiguousarray(cost[first:first + cnt])
+    for per in (64, 256):
+        sel = api.SelectParams(per)
+        f0 = np.full((n, per, 2), 0x1111, np.int16); s0 = np.full((n, per), 0x2222, np.uint16); c0 = np.full(n, 0x33333333, np.uint32)
+        engine.select_frame(w, h, sel, t_mv, t_cost, None, ctu_first=first, ctu_count=cnt, field=f0, slot=s0, ctu_cost=c0)
+        mf, ms, mc, _ = sm.select_picture(t_mv, t_cost, sel, w, h, first, None, engine.lambda_q16, mv_cost)
+        assert np.array_equal(f0[first:first + cnt], mf) and np.array_equal(s0[first:first + cnt], ms) and np.array_equal(c0[first:first + cnt], mc)
+        for want_slot, want_cost in ((False, True), (True, False), (False, False)):
+            f1 = np.full((n, per, 2), 0x1111, np.int16); s1 = np.full((n, per), 0x2222, np.uint16); c1 = np.full(n, 0x33333333, np.uint32)
+            assert engine.L.hmme_select_frame(engine.h, w, h, C.byref(fp), C.byref(sel), t_mv.ctypes.data, t_cost.ctypes.data, None, f1.ctypes.data,
+                                              s1.ctypes.data if want_slot else None, c1.ctypes.data if want_cost else None) == 0
+            assert np.array_equal(f1, f0)
+            assert np.array_equal(s1, s0) if want_slot else (s1 == 0x2222).all()
+            assert np.array_equal(c1, c0) if want_cost else (c1 == 0x33333333).all()
 
 
 def test_select_frame_host_call(engine, mv_cost, tables40):

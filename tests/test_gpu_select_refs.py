@@ -213,6 +213,24 @@ def test_ctu_sub_range_and_null_outputs(engine, mv_cost):
     assert np.array_equal(f0[rng_], mf[0]) and np.array_equal(r0[rng_], mr[0]) and np.array_equal(s0[rng_], ms[0]) and np.array_equal(c0[rng_], mc[0])
     out = np.ones(n, bool); out[rng_] = False
     assert (f0[out] == 0x1111).all() and (r0[out] == 0x22).all() and (s0[out] == 0x3333).all() and (c0[out] == 0x44444444).all()
+    # ... with NULL for out_slot, out_cost and both (the Python method always passes every array), in both layouts: the field and the references
+    # are the full call's, an array that was not passed is not written
+    fp, rcost = api.FrameParams(1, 0, 8, first, cnt), (C.c_uint32 * 2)(0, 2)
+    t_mv, t_cost = np.ascontiguousarray(mv[1], dtype=np.int16), np.ascontiguousarray(cost[1], dtype=np.uint32)
+    for per in (64, 256):
+        sel = api.SelectParams(per)
+        fill = lambda: (np.full((n, per, 2), 0x1111, np.int16), np.full((n, per), 0x22, np.uint8), np.full((n, per), 0x3333, np.uint16), np.full(n, 0x44444444, np.uint32))
+        f0, r0, s0, c0 = fill()
+        engine.select_refs_frame(w, h, sel, mv[1], cost[1], [0, 2], None, ctu_first=first, ctu_count=cnt, field=f0, ref=r0, slot=s0, ctu_cost=c0)
+        mf, mr, ms, mc = model_select_refs(mv_cost, w, h, mv[1:], cost[1:], sel, [0, 2], None, first)
+        assert np.array_equal(f0[rng_], mf[0]) and np.array_equal(r0[rng_], mr[0]) and np.array_equal(s0[rng_], ms[0]) and np.array_equal(c0[rng_], mc[0])
+        for want_slot, want_cost in ((False, True), (True, False), (False, False)):
+            f1, r1, s1, c1 = fill()
+            assert engine.L.hmme_select_refs_frame(engine.h, w, h, 2, C.byref(fp), C.byref(sel), rcost, t_mv.ctypes.data, t_cost.ctypes.data, None, f1.ctypes.data,
+                                                   r1.ctypes.data, s1.ctypes.data if want_slot else None, c1.ctypes.data if want_cost else None) == 0
+            assert np.array_equal(f1, f0) and np.array_equal(r1, r0)
+            assert np.array_equal(s1, s0) if want_slot else (s1 == 0x3333).all()
+            assert np.array_equal(c1, c0) if want_cost else (c1 == 0x44444444).all()
 
 
 # ---- 7: 64-bit merged costs -------------------------------------------------------------------------------------------------------------
@@ -333,6 +351,11 @@ def test_predict_refs_frame_is_predict_frame_block_by_block(engine, bit_depth, p
         assert np.array_equal(part[:64, 64:128], want[:64, 64:128])
         part[:64, 64:128] = fill
         assert (part == fill).all()
+        # ... and into an image whose stride exceeds the width
+        from frame_helpers import check_strided_image
+        ra = (C.c_void_p * 3)(*[p.h for p in planes])
+        check_strided_image(w, h, bit_depth, lambda out, first, count: engine.predict_refs_frame(planes, field, ref_field, out=out, ctu_first=first, ctu_count=count),
+                            lambda fp, out, stride: engine.L.hmme_predict_refs_frame(engine.h, ra, 3, C.byref(fp), field.ctypes.data, ref_field.ctypes.data, per, out, stride))
     finally:
         for p in planes:
             p.close()
