@@ -2062,14 +2062,15 @@ int predict_pairs(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs,
   return pairs_end(ctx, refs, refs, n_pairs, s, rc);
 }
 
-// hmme_predict_frame, _w and hmme_predict_refs_frame: the motion field and, behind it, the reference field (null: none) into ctx->d_bi[0], the
-// caller's image through ctx->d_bi[1] both ways around `launch`: samples that are not written come back as they were
+// hmme_predict_frame, _w, hmme_predict_refs_frame and hmme_predict_bi_frame: the motion field (`lists` of them, one behind the other) and,
+// behind it, the reference / direction field (null: none) into ctx->d_bi[0], the caller's image through ctx->d_bi[1] both ways around `launch`:
+// samples that are not written come back as they were
 int predict_staged(hmme_ctx* ctx, const char* who, const hmme_plane* ref, const int16_t* mv_field, const uint8_t* ref_field, int mv_per_ctu, void* out, int out_stride,
-                   const std::function<int(void* d_field, void* d_ref_field, void* d_img, int pitch, hipStream_t s)>& launch) {
+                   const std::function<int(void* d_field, void* d_ref_field, void* d_img, int pitch, hipStream_t s)>& launch, int lists = 1) {
   if (ref->ctx != ctx) return fail(ctx, HMME_ERR_ARG, "plane belongs to another context (planes are used with the context that created them)");
   if (out_stride < ref->width) return fail(ctx, HMME_ERR_ARG, "%s: output stride %d below the picture width", who, out_stride);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t blocks = (size_t)ref->n_ctu * mv_per_ctu, field_bytes = sizeof(int16_t) * 2 * blocks, row = (size_t)ref->width * ref->bps;
+  const size_t blocks = (size_t)ref->n_ctu * mv_per_ctu, field_bytes = sizeof(int16_t) * 2 * blocks * lists, row = (size_t)ref->width * ref->bps;
   int rc = ensure(ctx, &ctx->d_bi[0], &ctx->bi_cap[0], pad16(field_bytes) + (ref_field ? blocks : 0));
   if (rc == HMME_OK) rc = ensure(ctx, &ctx->d_bi[1], &ctx->bi_cap[1], row * ref->height);
   if (rc) return rc;
@@ -2428,10 +2429,13 @@ int select_begin(hmme_ctx* ctx, const char* who, int width, int height, int n_pi
 
 // hmme_select_frame and hmme_select_refs_frame: n_refs table and predictor sets into ctx->d_sel, `launch` on the device addresses (null
 // where the caller's array is; out_ref exists in the refs call only), then the outputs back
-using SelectLaunchFn = std::function<int(void* d_mv, void* d_cost, void* d_pred_q, void* d_field, void* d_ref, void* d_slot, void* d_ccost, hipStream_t s)>;
+// bi (hmme_select_dirs_frame; else null): the n_refs sets are the two lists.  A second run of n_refs table sets is staged behind the first
+// (d_mv / d_cost + n_refs sets), the lists' input field goes in as d_in_field, and the field that comes back has one part per list
+struct SelectStagedBi { const int16_t* mv; const uint32_t* cost; const int16_t* in_field; };
+using SelectLaunchFn = std::function<int(void* d_mv, void* d_cost, void* d_pred_q, void* d_in_field, void* d_field, void* d_ref, void* d_slot, void* d_ccost, hipStream_t s)>;
 int select_staged(hmme_ctx* ctx, const char* who, int width, int height, const hmme_frame_params* fp, const hmme_select_params* sel, int n_refs,
                   const uint32_t* ref_cost, const int16_t* mv, const uint32_t* cost, const int16_t* pred_q, int16_t* out_field, uint8_t* out_ref, uint16_t* out_slot,
-                  uint32_t* out_cost, const SelectLaunchFn& launch) {
+                  uint32_t* out_cost, const SelectLaunchFn& launch, const SelectStagedBi* bi = nullptr) {
   char msg[256];
   const int bad = select_refs_eval(sel, 1, n_refs, ref_cost, msg, sizeof msg);
   if (bad) return fail(ctx, bad, "%s: %s", who, msg);
@@ -2442,12 +2446,15 @@ int select_staged(hmme_ctx* ctx, const char* who, int width, int height, const h
   if (rc || count == 0) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t tab = (size_t)n_refs * count * HMME_NUM_CTU_PARTS * 4, preds = (size_t)n_refs * n_ctu * 4;
+  const size_t tabs = bi ? 2 * tab : tab, lists = bi ? n_refs : 1, list_bytes = n_ctu * per * 4;   // tab and list_bytes are multiples of 4
   uint8_t* const host[4] = {(uint8_t*)out_field, out_ref, (uint8_t*)out_slot, (uint8_t*)out_cost};
   const size_t ctu_bytes[4] = {per * 4, per, per * 2, 4};   // of the four outputs
-  size_t at[4], total = 2 * pad16(tab) + pad16(preds);
+  size_t at[4], total = 2 * pad16(tabs) + pad16(preds);
+  const size_t in_at = total;
+  if (bi) total += pad16(lists * list_bytes);
   for (int k = 0; k < 4; ++k) {
     at[k] = total;
-    if (host[k]) total += pad16(n_ctu * ctu_bytes[k]);
+    if (host[k]) total += pad16((k == 0 ? lists : 1) * n_ctu * ctu_bytes[k]);
   }
   rc = ensure(ctx, &ctx->d_sel, &ctx->sel_cap, total);
   if (rc) return rc;
@@ -2455,13 +2462,21 @@ int select_staged(hmme_ctx* ctx, const char* who, int width, int height, const h
   uint8_t *d = ctx->d_sel, *d_out[4];
   for (int k = 0; k < 4; ++k) d_out[k] = host[k] ? d + at[k] : nullptr;
   HIP_TRY(ctx, hipMemcpyAsync(d, mv, tab, hipMemcpyHostToDevice, s));
-  HIP_TRY(ctx, hipMemcpyAsync(d + pad16(tab), cost, tab, hipMemcpyHostToDevice, s));
-  if (pred_q) HIP_TRY(ctx, hipMemcpyAsync(d + 2 * pad16(tab), pred_q, preds, hipMemcpyHostToDevice, s));
-  rc = launch(d, d + pad16(tab), pred_q ? d + 2 * pad16(tab) : nullptr, d_out[0], d_out[1], d_out[2], d_out[3], s);
+  HIP_TRY(ctx, hipMemcpyAsync(d + pad16(tabs), cost, tab, hipMemcpyHostToDevice, s));
+  if (bi) {
+    HIP_TRY(ctx, hipMemcpyAsync(d + tab, bi->mv, tab, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d + pad16(tabs) + tab, bi->cost, tab, hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d + in_at, bi->in_field, lists * list_bytes, hipMemcpyHostToDevice, s));
+  }
+  if (pred_q) HIP_TRY(ctx, hipMemcpyAsync(d + 2 * pad16(tabs), pred_q, preds, hipMemcpyHostToDevice, s));
+  rc = launch(d, d + pad16(tabs), pred_q ? d + 2 * pad16(tabs) : nullptr, bi ? d + in_at : nullptr, d_out[0], d_out[1], d_out[2], d_out[3], s);
   if (rc) return rc;
   // only the CTUs of the range come back: the caller's entries outside it keep their values
   for (int k = 0; k < 4; ++k)
-    if (host[k]) HIP_TRY(ctx, hipMemcpyAsync(host[k] + first * ctu_bytes[k], d_out[k] + first * ctu_bytes[k], count * ctu_bytes[k], hipMemcpyDeviceToHost, s));
+    for (size_t l = 0; host[k] && l < (k == 0 ? lists : 1); ++l) {
+      const size_t o = l * list_bytes + first * ctu_bytes[k];
+      HIP_TRY(ctx, hipMemcpyAsync(host[k] + o, d_out[k] + o, count * ctu_bytes[k], hipMemcpyDeviceToHost, s));
+    }
   HIP_TRY(ctx, hipStreamSynchronize(s));
   return HMME_OK;
 }
@@ -2484,7 +2499,7 @@ int hmme_select_frame(hmme_ctx* ctx, int width, int height, const hmme_frame_par
                       const uint32_t* cost, const int16_t* pred_q, int16_t* out_field, uint16_t* out_slot, uint32_t* out_cost) {
   if (!ctx) return HMME_ERR_ARG;
   return select_staged(ctx, "hmme_select_frame", width, height, fp, sel, 1, nullptr, mv, cost, pred_q, out_field, nullptr, out_slot, out_cost,
-                       [&](void* d_mv, void* d_cost, void* d_pred_q, void* d_field, void*, void* d_slot, void* d_ccost, hipStream_t s) {
+                       [&](void* d_mv, void* d_cost, void* d_pred_q, void*, void* d_field, void*, void* d_slot, void* d_ccost, hipStream_t s) {
                          return hmme_select_pairs_device(ctx, width, height, 1, fp, sel, d_mv, d_cost, d_pred_q, d_field, d_slot, d_ccost, s);
                        });
 }
@@ -2525,7 +2540,7 @@ int hmme_select_refs_frame(hmme_ctx* ctx, int width, int height, int n_refs, con
   if (!ctx) return HMME_ERR_ARG;
   if (!out_ref) return fail(ctx, HMME_ERR_ARG, "hmme_select_refs_frame: null reference array");
   return select_staged(ctx, "hmme_select_refs_frame", width, height, fp, sel, n_refs, ref_cost, mv, cost, pred_q, out_field, out_ref, out_slot, out_cost,
-                       [&](void* d_mv, void* d_cost, void* d_pred_q, void* d_field, void* d_ref, void* d_slot, void* d_ccost, hipStream_t s) {
+                       [&](void* d_mv, void* d_cost, void* d_pred_q, void*, void* d_field, void* d_ref, void* d_slot, void* d_ccost, hipStream_t s) {
                          return hmme_select_refs_device(ctx, width, height, 1, n_refs, fp, sel, ref_cost, d_mv, d_cost, d_pred_q, d_field, d_ref, d_slot, d_ccost, s);
                        });
 }
@@ -2558,6 +2573,123 @@ int hmme_predict_refs_frame(hmme_ctx* ctx, const hmme_plane* const* refs, int n_
   return predict_staged(ctx, who, refs[0], mv_field, ref_field, mv_per_ctu, out, out_stride, [&](void* d_field, void* d_ref_field, void* d_img, int pitch, hipStream_t s) {
     return hmme_predict_refs_device(ctx, refs, n_refs, fp, d_field, d_ref_field, mv_per_ctu, d_img, pitch, s);
   });
+}
+
+// ---- L0, L1 or bi per PU: the decision over the four table sets of a B picture, and the prediction that follows it ---------------------------
+namespace {
+constexpr int kMaxDirPics = 4;
+int select_dirs_eval(const hmme_select_params* sel, int n_pics, const hmme_dir_params* dirs, char* msg, size_t cap) {
+  const int bad = select_eval(sel, msg, cap);
+  if (bad) return bad;
+  if (sel->mv_per_ctu != 64 || sel->mv_unit != 0 || sel->price_mv != 0) {
+    snprintf(msg, cap, "mv_per_ctu %d, mv_unit %d, price_mv %d: the direction is decided on quarter-pel refinement tables, one MV per 8x8 block (64, 0, 0)",
+             sel->mv_per_ctu, sel->mv_unit, sel->price_mv);
+    return HMME_ERR_ARG;
+  }
+  if (n_pics < 1 || n_pics > kMaxDirPics) { snprintf(msg, cap, "%d pictures outside 1..%d", n_pics, kMaxDirPics); return HMME_ERR_ARG; }
+  if (!dirs) { snprintf(msg, cap, "null direction parameters"); return HMME_ERR_ARG; }
+  for (int p = 0; p < n_pics; ++p) {
+    const uint32_t v[5] = {dirs[p].dir_bits[0], dirs[p].dir_bits[1], dirs[p].dir_bits[2], dirs[p].list_bits[0], dirs[p].list_bits[1]};
+    for (int k = 0; k < 5; ++k)
+      if (v[k] > 4096) { snprintf(msg, cap, "picture %d: %s[%d] = %u above 4096", p, k < 3 ? "dir_bits" : "list_bits", k < 3 ? k : k - 3, v[k]); return HMME_ERR_ARG; }
+  }
+  return HMME_OK;
+}
+}  // namespace
+
+int hmme_select_dirs_check(const hmme_select_params* sel, int n_pics, const hmme_dir_params* dirs) {
+  char msg[256];
+  return select_dirs_eval(sel, n_pics, dirs, msg, sizeof msg);
+}
+
+int hmme_select_dirs_device(hmme_ctx* ctx, int width, int height, int n_pics, const hmme_frame_params* fp, const hmme_select_params* sel,
+                            const hmme_dir_params* dirs, const void* d_mv_uni, const void* d_cost_uni, const void* d_mv_bi, const void* d_cost_bi,
+                            const void* d_uni_field, const void* d_pred_q, void* d_out_field, void* d_out_dir, void* d_out_slot, void* d_out_cost,
+                            void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  const char* who = "hmme_select_dirs_device";
+  char msg[256];
+  const int bad = select_dirs_eval(sel, n_pics, dirs, msg, sizeof msg);
+  if (bad) return fail(ctx, bad, "%s: %s", who, msg);
+  if (!d_mv_bi || !d_cost_bi || !d_uni_field || !d_out_dir) return fail(ctx, HMME_ERR_ARG, "%s: null bi table, input field or direction buffer", who);
+  if (((uintptr_t)d_mv_bi & 3) || ((uintptr_t)d_cost_bi & 3) || ((uintptr_t)d_uni_field & 3) || ((uintptr_t)d_out_dir & 1))
+    return fail(ctx, HMME_ERR_ARG, "%s: misaligned buffer (tables, costs and the input field 4 bytes, directions 2)", who);
+  SelectLaunch L;   // the two lists of a picture are its two table sets
+  const int rc = select_begin(ctx, who, width, height, n_pics, 2, nullptr, fp, sel, d_mv_uni, d_cost_uni, d_pred_q, d_out_field, d_out_slot, d_out_cost, &L);
+  if (rc || L.count == 0) return rc;
+  hmme::MeDirParams bits = {};
+  for (int p = 0; p < n_pics; ++p) bits.p[p] = {{dirs[p].dir_bits[0], dirs[p].dir_bits[1], dirs[p].dir_bits[2]}, {dirs[p].list_bits[0], dirs[p].list_bits[1]}};
+  hipLaunchKernelGGL(hmme::me_select_dirs_kernel, L.grid, dim3(256), 0, (hipStream_t)stream, (const uint32_t*)d_mv_uni, (const uint32_t*)d_cost_uni,
+                     (const uint32_t*)d_mv_bi, (const uint32_t*)d_cost_bi, (const uint32_t*)d_uni_field, (const int16_t*)d_pred_q, (uint32_t*)d_out_field,
+                     (uint8_t*)d_out_dir, (uint16_t*)d_out_slot, (uint32_t*)d_out_cost, L.a, bits, width, height, L.n_ctu, L.first, L.count, ctx->lambda_q16);
+  HIP_TRY(ctx, hipGetLastError());
+  return HMME_OK;
+}
+
+int hmme_select_dirs_frame(hmme_ctx* ctx, int width, int height, const hmme_frame_params* fp, const hmme_select_params* sel,
+                           const hmme_dir_params* dir, const int16_t* mv_uni, const uint32_t* cost_uni, const int16_t* mv_bi, const uint32_t* cost_bi,
+                           const int16_t* uni_field, const int16_t* pred_q, int16_t* out_field, uint8_t* out_dir, uint16_t* out_slot,
+                           uint32_t* out_cost) {
+  if (!ctx) return HMME_ERR_ARG;
+  const char* who = "hmme_select_dirs_frame";
+  char msg[256];
+  const int bad = select_dirs_eval(sel, 1, dir, msg, sizeof msg);   // before anything is staged
+  if (bad) return fail(ctx, bad, "%s: %s", who, msg);
+  if (!mv_bi || !cost_bi || !uni_field || !out_dir) return fail(ctx, HMME_ERR_ARG, "%s: null bi table, input field or direction array", who);
+  const SelectStagedBi bi = {mv_bi, cost_bi, uni_field};
+  return select_staged(ctx, who, width, height, fp, sel, 2, nullptr, mv_uni, cost_uni, pred_q, out_field, out_dir, out_slot, out_cost,
+                       [&](void* d_mv, void* d_cost, void* d_pred_q, void* d_in_field, void* d_field, void* d_dir, void* d_slot, void* d_ccost, hipStream_t s) {
+                         const size_t tab = (size_t)2 * (fp->ctu_count < 0 ? hmme_num_ctus(width, height) - fp->ctu_first : fp->ctu_count) * HMME_NUM_CTU_PARTS * 4;
+                         return hmme_select_dirs_device(ctx, width, height, 1, fp, sel, dir, d_mv, d_cost, (uint8_t*)d_mv + tab, (uint8_t*)d_cost + tab, d_in_field,
+                                                        d_pred_q, d_field, d_dir, d_slot, d_ccost, s);
+                       }, &bi);
+}
+
+// one launch of me_predict_bi_kernel per picture: every block from the planes its direction names
+int hmme_predict_bi_device(hmme_ctx* ctx, const hmme_plane* const* refs0, const hmme_plane* const* refs1, int n_pics, const hmme_frame_params* fp,
+                           const void* d_mv_field, const void* d_dir_field, int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  const char* who = "hmme_predict_bi_device";
+  if (!refs0 || !refs1 || n_pics < 1 || 2 * n_pics > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d pictures outside 1..%d (or a null plane list)", who, n_pics, hmme::kMaxRefs / 2);
+  const hmme_plane* planes[hmme::kMaxRefs];   // picture i: planes[2 i] (list 0), planes[2 i + 1] (list 1)
+  for (int i = 0; i < n_pics; ++i) { planes[2 * i] = refs0[i]; planes[2 * i + 1] = refs1[i]; }
+  PredictArgs a;
+  int rc = predict_args(ctx, who, planes, 2 * n_pics, !d_dir_field || !d_outs, fp, nullptr, d_mv_field, mv_per_ctu, out_pitch_bytes, &a);
+  if (rc) return rc;
+  for (int i = 0; i < n_pics; ++i)
+    if (!d_outs[i]) return fail(ctx, HMME_ERR_ARG, "%s: null output image", who);
+  hipStream_t s = (hipStream_t)stream;
+  PairLaunch pl;   // checks every plane: of this context, of one size, of fp's bit depth; each is ordered like a reference
+  rc = pairs_begin(ctx, planes, planes, 2 * n_pics, &a.f, s, &pl);
+  if (rc || pl.count == 0) return rc;
+  const hmme_plane* p0 = planes[0];
+  const size_t blocks = (size_t)p0->n_ctu * mv_per_ctu;
+  for (int i = 0; i < n_pics; ++i) {
+    const int16_t* field = (const int16_t*)d_mv_field + blocks * 4 * i;
+    const uint8_t* dirs = (const uint8_t*)d_dir_field + blocks * i;
+    if (p0->bps == 1)
+      hipLaunchKernelGGL(hmme::me_predict_bi_kernel<uint8_t>, dim3((unsigned)pl.count), dim3(256), 0, s, planes[2 * i]->origin(), planes[2 * i + 1]->origin(), p0->pitch,
+                         field, dirs, mv_per_ctu, p0->n_ctu, pl.first, p0->width, p0->height, p0->bit_depth, (uint8_t*)d_outs[i], out_pitch_bytes);
+    else
+      hipLaunchKernelGGL(hmme::me_predict_bi_kernel<uint16_t>, dim3((unsigned)pl.count), dim3(256), 0, s, planes[2 * i]->origin(), planes[2 * i + 1]->origin(), p0->pitch,
+                         field, dirs, mv_per_ctu, p0->n_ctu, pl.first, p0->width, p0->height, p0->bit_depth, (uint8_t*)d_outs[i], out_pitch_bytes);
+  }
+  rc = hipGetLastError() == hipSuccess ? HMME_OK : fail(ctx, HMME_ERR_DEVICE, "%s: launch failed", who);
+  return pairs_end(ctx, planes, planes, 2 * n_pics, s, rc);   // whatever the launches returned: the scratch is acquired
+}
+
+int hmme_predict_bi_frame(hmme_ctx* ctx, const hmme_plane* ref0, const hmme_plane* ref1, const hmme_frame_params* fp, const int16_t* mv_field,
+                          const uint8_t* dir_field, int mv_per_ctu, void* out, int out_stride) {
+  if (!ctx) return HMME_ERR_ARG;
+  const char* who = "hmme_predict_bi_frame";
+  int rc = bi_check(ctx, who, fp, 0);
+  if (rc) return rc;
+  if (!ref0 || !ref1 || !mv_field || !dir_field || !out || (mv_per_ctu != 1 && mv_per_ctu != 64))
+    return fail(ctx, HMME_ERR_ARG, "%s: null argument, or %d MVs per CTU (1 or 64)", who, mv_per_ctu);
+  // blocks without a direction, too, come back as they were
+  return predict_staged(ctx, who, ref0, mv_field, dir_field, mv_per_ctu, out, out_stride, [&](void* d_field, void* d_dir_field, void* d_img, int pitch, hipStream_t s) {
+    return hmme_predict_bi_device(ctx, &ref0, &ref1, 1, fp, d_field, d_dir_field, mv_per_ctu, &d_img, pitch, s);
+  }, 2);
 }
 
 // ---- estimating explicit weighted-prediction parameters ----------------------------------------------------------------------------------------

@@ -2395,10 +2395,14 @@ __device__ __forceinline__ void me_select_level(const MeSelect& a, const CostT* 
 // The decision over a CTU's slots in LDS and the stores that follow it: what both select kernels end in, one wave per CTU, lane = 8x8 block
 // in RASTER order inside the CTU.  o = the CTU's index in the outputs.  REFS: the slots carry a reference index (s_ref) that leaves
 // beside the field (out_ref) -- me_select_refs_kernel; without it both pointers are null and never looked at.
-template <bool REFS, typename CostT>
+// DIRS (me_select_dirs_kernel; one MV per 8x8 block only): s_ref holds direction | searched list << 2 per slot, out_ref takes the direction,
+// and the field has two lists list_stride dwords apart: the winner's MV in its list; in the other list (0,0) under a direction-1 / -2
+// slot and, under a direction-3 slot, the block's own entry of uni_field (laid out like out_field).  Without DIRS neither is looked at.
+template <bool REFS, typename CostT, bool DIRS = false>
 __device__ __forceinline__ void me_select_decide_store(const MeSelect& a, const CostT* s_cost, const uint32_t* s_mv, const uint8_t* s_ref, uint32_t lambda_q16,
                                                        int pred_x, int pred_y, int lane, int ctu_x, int ctu_y, long o, int pic_w, int pic_h,
-                                                       uint32_t* out_field, uint8_t* out_ref, uint16_t* out_slot, uint32_t* out_cost) {
+                                                       uint32_t* out_field, uint8_t* out_ref, uint16_t* out_slot, uint32_t* out_cost,
+                                                       const uint32_t* uni_field = nullptr, long list_stride = 0) {
   const int bx = lane & 7, by = lane >> 3;
   MeSelectState st = {0, -1, 0};
   me_select_level<3>(a, s_cost, s_mv, lambda_q16, pred_x, pred_y, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
@@ -2413,8 +2417,19 @@ __device__ __forceinline__ void me_select_decide_store(const MeSelect& a, const 
   };
   if (a.per == 64) {
     const int slot = st.leaf_depth < 0 ? 0xffff : me_select_pu_slot_at(st.leaf_depth, st.leaf_ps, bx * 8, by * 8);
-    out_field[o * 64 + lane] = slot == 0xffff ? 0u : field_mv(slot);
-    if constexpr (REFS) out_ref[o * 64 + lane] = slot == 0xffff ? (uint8_t)0xff : s_ref[slot];
+    if constexpr (DIRS) {
+      const int d = slot == 0xffff ? 0 : (int)s_ref[slot];   // direction | searched list << 2
+      const int dir = d & 3, bl = d >> 2;
+      uint32_t f[2] = {0u, 0u};
+      if (dir == 3) { f[bl] = s_mv[slot]; f[1 - bl] = uni_field[o * 64 + lane + (1 - bl) * list_stride]; }
+      else if (dir) f[dir - 1] = s_mv[slot];
+      out_field[o * 64 + lane] = f[0];
+      out_field[o * 64 + lane + list_stride] = f[1];
+      out_ref[o * 64 + lane] = dir ? (uint8_t)dir : (uint8_t)0xff;
+    } else {
+      out_field[o * 64 + lane] = slot == 0xffff ? 0u : field_mv(slot);
+      if constexpr (REFS) out_ref[o * 64 + lane] = slot == 0xffff ? (uint8_t)0xff : s_ref[slot];
+    }
     if (out_slot) out_slot[o * 64 + lane] = (uint16_t)slot;
   } else {
 #pragma unroll
@@ -2533,6 +2548,181 @@ me_select_refs_kernel(const uint32_t* __restrict__ mv_tab, const uint32_t* __res
   merged.price_mv = 0;   // priced above, per reference: not a second time
   me_select_decide_store<true>(merged, s_cost[wave], s_mv[wave], s_ref[wave], lambda_q16, 0, 0, lane, ctu_x, ctu_y, (long)pic * n_ctu + ctu, pic_w, pic_h,
                                out_field, out_ref, out_slot, out_cost);
+}
+
+// ---- L0, L1 or bi per PU (hmme_select_dirs_device; the rule: include/hmme.h) ---------------------------------------------------------------
+// hmme_dir_params of every picture of the launch, as the kernel takes them
+struct MeDirBits { uint32_t dir_bits[3], list_bits[2]; };
+struct MeDirParams { MeDirBits p[4]; };
+
+// me_select_refs_kernel's geometry -- one wave per CTU, four CTUs per workgroup, blockIdx.y = picture -- over FOUR table sets per picture:
+// uni / bi, each int16 [n_pics][2][ctu_count][593][2] as dwords with costs uint32 of that shape; pred_q int16 [n_pics][2][n_ctu][2] or null.
+// A lane owns the slots lane, lane + 64, ... and takes each through the four sets in registers: the MV bits of the four MVs against
+// their lists' predictors, the distortions with the MV cost taken out again (clamped at 0; the bi pass's halved: fWeight 0.5,
+// TEncSearch.cpp:3808), HM's bits put back in ONE getCost per candidate (32-bit wrap), every sum in 64 bits.  The bi candidate is list 0's
+// unless list 1's is strictly cheaper (:3183-3186, :3226); bi wins on <= against both lists, list 0 on <= against list 1 (:3291, :3314).
+// The winner's cost, its MV dword and direction | searched list << 2 go to LDS and me_select_decide_store<.., DIRS> decides on them
+// with the MV cost switched off.  uni_field / out_field: int16 [n_pics][2][n_ctu][64][2] as dwords; out_dir uint8 [n_pics][n_ctu][64].
+__global__ void __launch_bounds__(256)
+me_select_dirs_kernel(const uint32_t* __restrict__ mv_uni, const uint32_t* __restrict__ cost_uni, const uint32_t* __restrict__ mv_bi,
+                      const uint32_t* __restrict__ cost_bi, const uint32_t* __restrict__ uni_field, const int16_t* __restrict__ pred_q,
+                      uint32_t* __restrict__ out_field, uint8_t* __restrict__ out_dir, uint16_t* __restrict__ out_slot, uint32_t* __restrict__ out_cost,
+                      MeSelect a, MeDirParams dirs, int pic_w, int pic_h, int n_ctu, int ctu_first, int ctu_count, uint32_t lambda_q16) {
+  constexpr int kOwn = (kParts + 63) / 64;   // slots per lane
+  __shared__ uint64_t s_cost[4][kParts + 3];
+  __shared__ uint32_t s_mv[4][kParts + 3];
+  __shared__ uint8_t s_dir[4][kParts + 3];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int c = blockIdx.x * 4 + wave, pic = blockIdx.y;
+  const bool live = c < ctu_count;   // wave-uniform
+  const int ctu = ctu_first + c;
+  if (live) {
+    const MeDirBits b = dirs.p[pic];
+    int px[2] = {0, 0}, py[2] = {0, 0};
+    if (pred_q) {   // wave-uniform: the two lists' predictors of the CTU
+      const int16_t* pq = pred_q + ((long)pic * 2 * n_ctu + ctu) * 2;
+      px[0] = pq[0]; py[0] = pq[1];
+      px[1] = pq[2 * (long)n_ctu]; py[1] = pq[2 * (long)n_ctu + 1];
+    }
+    const long base[2] = {((long)pic * 2 * ctu_count + c) * kParts, (((long)pic * 2 + 1) * ctu_count + c) * kParts};
+    auto mvb = [](uint32_t m, int pred_x, int pred_y) -> uint32_t {   // HM's getBits at cost scale 0
+      return me_component_bits((int16_t)(m & 0xffffu) - pred_x) + me_component_bits((int16_t)(m >> 16) - pred_y);
+    };
+    auto gc = [&](uint32_t n) -> uint64_t { return (lambda_q16 * n) >> 16; };   // TComRdCost::getCost: the product wraps in 32 bits
+    auto dist = [&](uint32_t cost, uint32_t bits) -> uint64_t {
+      const uint64_t g = gc(bits);
+      return cost > g ? cost - g : 0;
+    };
+#pragma unroll 1
+    for (int k = 0; k < kOwn; ++k) {
+      const int i = lane + 64 * k;
+      if (i >= kParts) continue;
+      uint32_t mu[2], mb[2], bu[2], bb[2];
+      uint64_t cu[2], cb[2];
+#pragma unroll
+      for (int l = 0; l < 2; ++l) {
+        mu[l] = mv_uni[base[l] + i];
+        mb[l] = mv_bi[base[l] + i];
+        bu[l] = mvb(mu[l], px[l], py[l]);
+        bb[l] = mvb(mb[l], px[l], py[l]);
+      }
+#pragma unroll
+      for (int l = 0; l < 2; ++l) {
+        cu[l] = dist(cost_uni[base[l] + i], bu[l]) + gc(b.dir_bits[l] + b.list_bits[l] + bu[l]);
+        cb[l] = (dist(cost_bi[base[l] + i], bb[l]) >> 1) + gc(b.dir_bits[2] + b.list_bits[0] + b.list_bits[1] + bb[l] + bu[1 - l]);
+      }
+      const int bl = cb[1] < cb[0] ? 1 : 0;   // strict: list 0 is tried first
+      const uint64_t cbi = cb[bl];
+      uint64_t best;
+      uint32_t m;
+      int d;
+      if (cbi <= cu[0] && cbi <= cu[1]) { best = cbi; m = mb[bl]; d = 3 | bl << 2; }
+      else if (cu[0] <= cu[1]) { best = cu[0]; m = mu[0]; d = 1; }
+      else { best = cu[1]; m = mu[1]; d = 2; }
+      s_cost[wave][i] = best;
+      s_mv[wave][i] = m;
+      s_dir[wave][i] = (uint8_t)d;
+    }
+  }
+  __syncthreads();
+  if (!live) return;
+  const int ctus_x = (pic_w + 63) >> 6;
+  const int ctu_x = (ctu % ctus_x) * 64, ctu_y = (ctu / ctus_x) * 64;
+  MeSelect merged = a;
+  merged.price_mv = 0;   // inside the merged cost already
+  const long lists = (long)n_ctu * 64, at = (long)pic * lists;   // the picture's two lists start at dword 2 * at; its CTU index is at / 64 + ctu
+  me_select_decide_store<true, uint64_t, true>(merged, s_cost[wave], s_mv[wave], s_dir[wave], lambda_q16, 0, 0, lane, ctu_x, ctu_y, (long)pic * n_ctu + ctu,
+                                               pic_w, pic_h, out_field + at, out_dir, out_slot, out_cost, uni_field + at, lists);
+}
+
+// ---- the prediction of a picture whose blocks are L0, L1 or bi (hmme_predict_bi_device) ----------------------------------------------------
+// One list's two passes of me_predict_kernel for the wave's 8x8 block at picture position (x0, y0): the 15 x 15 patch at the clamped MV
+// through LDS, the horizontal pass into the 14-bit intermediate, the vertical sum of lane (r, c) = (lane >> 3, lane & 7) -- returned
+// before any shift, so that the caller ends it as bi = false (rounded) or bi = true (>> 6).  live is wave-uniform; a wave that is not
+// live reads nothing and still meets both barriers.
+template <typename SrcT>
+__device__ __forceinline__ int me_predict_block_sum(bool live, const uint8_t* origin, int ref_pitch, int x0, int y0, int mx, int my, int16_t* patch,
+                                                    int16_t* mid, int lane, int sh1, int off1) {
+  if (live) {
+    const uint8_t* src = origin + (long)(y0 + (my >> 2) - 3) * ref_pitch + (long)(x0 + (mx >> 2) - 3) * (long)sizeof(SrcT);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int e = lane + 64 * k, r = e / 15, c = e - r * 15;
+      if (e < 225) patch[r * 16 + c] = (int16_t)((const SrcT*)(src + (long)r * ref_pitch))[c];
+    }
+  }
+  __syncthreads();
+  if (live) {
+    const int* ch = kLumaTaps[mx & 3];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int o = lane + 64 * k, r = o >> 3, c = o & 7;
+      if (o < 120) {
+        int sum = 0;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) sum += ch[t] * (int)patch[r * 16 + c + t];
+        mid[o] = (int16_t)((sum + off1) >> sh1);
+      }
+    }
+  }
+  __syncthreads();
+  int sum = 0;
+  if (live) {
+    const int* cv = kLumaTaps[my & 3];
+    const int r = lane >> 3, c = lane & 7;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) sum += cv[t] * (int)mid[(r + t) * 8 + c];
+  }
+  return sum;
+}
+
+// me_predict_kernel<SrcT, 0> with a direction per block: one CTU per workgroup, a wave one 8x8 block at a time.  mv_field: int16
+// [2][n_ctu][mv_per_ctu][2] (list-major), dir_field: uint8 [n_ctu][mv_per_ctu] -- HM's interDir: 1 = list 0 (ref0), 2 = list 1 (ref1),
+// 3 = both.  The direction is the same for the whole wave, so it is read as a scalar; a list the direction does not name is not live in its
+// pass.  Direction 1 / 2: the sample me_predict_kernel writes from that plane and MV.  Direction 3 (TComPrediction.cpp:527-541 without WP):
+// both lists leave the 14-bit intermediate P = sum >> 6 (xPredInterUni with bi = true), then TComYuv::addAvg (TComYuv.cpp:352-390):
+// ClipBD((P0 + P1 + offset) >> shift), shift = headRoom + 1, offset = (1 << (shift - 1)) + 2 * 8192 -- |P| < 2^15, so int32 holds it at every
+// depth.  Any other direction (0xFF: no CU) reads no plane and writes nothing, and still meets all four barriers of its iteration.
+template <typename SrcT>
+__global__ void __launch_bounds__(256)
+me_predict_bi_kernel(const uint8_t* __restrict__ ref0, const uint8_t* __restrict__ ref1, int ref_pitch, const int16_t* __restrict__ mv_field,
+                     const uint8_t* __restrict__ dir_field, int mv_per_ctu, int n_ctu, int ctu_first, int pic_w, int pic_h, int bit_depth,
+                     uint8_t* __restrict__ dst, int dst_pitch) {
+  __shared__ int16_t patch[4][15 * 16];
+  __shared__ int16_t mid[4][15 * 8];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int ctus_x = (pic_w + 63) >> 6;
+  const int ctu = ctu_first + blockIdx.x;
+  const int cx = ctu % ctus_x, cy = ctu / ctus_x, cu_x = cx * 64, cu_y = cy * 64;
+  const int head = 14 - bit_depth > 2 ? 14 - bit_depth : 2;   // headRoom (IF_INTERNAL_PREC - bitDepth, at least 2)
+  const int sh1 = 6 - head, off1 = -(8192 << sh1), sh2 = 6 + head, off2 = (1 << (sh2 - 1)) + (8192 << 6);
+  const int shb = head + 1, offb = (1 << (shb - 1)) + 2 * 8192;   // addAvg
+  const int maxv = (1 << bit_depth) - 1;
+#pragma unroll 1
+  for (int it = 0; it < 16; ++it) {
+    const int b = it * 4 + wave, bx = (b & 7) * 8, by = (b >> 3) * 8;   // the four waves: four blocks side by side
+    const long e = (long)ctu * mv_per_ctu + (mv_per_ctu == 1 ? 0 : b);
+    const int dir = __builtin_amdgcn_readfirstlane((int)dir_field[e]);
+    const bool in_pic = cu_x + bx < pic_w && cu_y + by < pic_h && dir >= 1 && dir <= 3;   // wave-uniform
+    const bool use0 = in_pic && (dir & 1), use1 = in_pic && (dir & 2);
+    int mx0 = 0, my0 = 0, mx1 = 0, my1 = 0;
+    if (use0) { mx0 = mv_field[e * 2]; my0 = mv_field[e * 2 + 1]; clip_mv_q(mx0, my0, cu_x, cu_y, pic_w, pic_h); }
+    if (use1) {
+      const int16_t* mv = mv_field + ((long)n_ctu * mv_per_ctu + e) * 2;
+      mx1 = mv[0]; my1 = mv[1];
+      clip_mv_q(mx1, my1, cu_x, cu_y, pic_w, pic_h);
+    }
+    const int sum0 = me_predict_block_sum<SrcT>(use0, ref0, ref_pitch, cu_x + bx, cu_y + by, mx0, my0, patch[wave], mid[wave], lane, sh1, off1);
+    const int sum1 = me_predict_block_sum<SrcT>(use1, ref1, ref_pitch, cu_x + bx, cu_y + by, mx1, my1, patch[wave], mid[wave], lane, sh1, off1);
+    if (in_pic) {
+      int v;
+      if (use0 && use1) v = ((int)(int16_t)(sum0 >> 6) + (int)(int16_t)(sum1 >> 6) + offb) >> shb;   // HM keeps the intermediates in Pels
+      else v = ((use0 ? sum0 : sum1) + off2) >> sh2;
+      v = v < 0 ? 0 : (v > maxv ? maxv : v);
+      const int x = cu_x + bx + (lane & 7), y = cu_y + by + (lane >> 3);
+      if (x < pic_w && y < pic_h) ((SrcT*)(dst + (long)y * dst_pitch))[x] = (SrcT)v;
+    }
+  }
 }
 
 // ---- estimating explicit weighted-prediction parameters (hmme_plane_stats / hmme_wp_estimate) ---------------------------------------------

@@ -31,6 +31,7 @@ SYMBOLS = ["hmme_create", "hmme_destroy", "hmme_last_error", "hmme_device_info",
            "hmme_slot_key", "hmme_select_check", "hmme_select_pairs_device", "hmme_select_frame",
            "hmme_ref_idx_bits", "hmme_select_refs_check", "hmme_select_refs_device", "hmme_select_refs_frame",
            "hmme_predict_refs_device", "hmme_predict_refs_frame",
+           "hmme_select_dirs_check", "hmme_select_dirs_device", "hmme_select_dirs_frame", "hmme_predict_bi_device", "hmme_predict_bi_frame",
            "hmme_plane_stats", "hmme_wp_estimate"]
 # test / measurement entry points (include/hmme_test.h): not part of the boundary
 TEST_SYMBOLS = ["hmme_test_time_search_kernel", "hmme_test_device_address", "hmme_test_frac_deal", "hmme_test_tail_plan", "hmme_test_time_weight_passes", "hmme_test_time_bipred_origin",
@@ -71,6 +72,15 @@ class SelectParams(C.Structure):
 
     def __init__(self, mv_per_ctu=64, mv_unit=0, price_mv=0, part_mask=0xF7, min_depth=0, max_depth=3, cu_cost=0, pu_cost=0):
         super().__init__(int(mv_per_ctu), int(mv_unit), int(price_mv), int(part_mask), int(min_depth), int(max_depth), int(cu_cost), int(pu_cost))
+
+
+class DirParams(C.Structure):
+    """hmme_dir_params: the caller's bit counts of the L0 / L1 / bi decision (the rule: include/hmme.h): dir_bits = HM's uiMbBits[3],
+    list_bits = reference-index + MVP-index bits of list 0 and list 1"""
+    _fields_ = [("dir_bits", C.c_uint32 * 3), ("list_bits", C.c_uint32 * 2)]
+
+    def __init__(self, dir_bits=(0, 0, 0), list_bits=(0, 0)):
+        super().__init__((C.c_uint32 * 3)(*[int(v) for v in dir_bits]), (C.c_uint32 * 2)(*[int(v) for v in list_bits]))
 
 
 class FrameParams(C.Structure):
@@ -179,6 +189,11 @@ def load():
     L.hmme_select_refs_frame.argtypes = [vp, i, i, i, C.POINTER(FrameParams), C.POINTER(SelectParams), vp, vp, vp, vp, vp, vp, vp, vp]
     L.hmme_predict_refs_device.argtypes = [vp, C.POINTER(vp), i, C.POINTER(FrameParams), vp, vp, i, vp, i, vp]
     L.hmme_predict_refs_frame.argtypes = [vp, C.POINTER(vp), i, C.POINTER(FrameParams), vp, vp, i, vp, i]
+    L.hmme_select_dirs_check.argtypes = [C.POINTER(SelectParams), i, C.POINTER(DirParams)]
+    L.hmme_select_dirs_device.argtypes = [vp, i, i, i, C.POINTER(FrameParams), C.POINTER(SelectParams), C.POINTER(DirParams)] + [vp] * 11
+    L.hmme_select_dirs_frame.argtypes = [vp, i, i, C.POINTER(FrameParams), C.POINTER(SelectParams), C.POINTER(DirParams)] + [vp] * 10
+    L.hmme_predict_bi_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, C.POINTER(FrameParams), vp, vp, i, C.POINTER(vp), i, vp]
+    L.hmme_predict_bi_frame.argtypes = [vp, vp, vp, C.POINTER(FrameParams), vp, vp, i, vp, i]
     L.hmme_plane_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.hmme_wp_estimate.argtypes = [vp, vp, C.POINTER(vp), i, i, C.POINTER(Weight), C.POINTER(WpInfo)]
     L.hmme_test_time_wp_estimate_passes.argtypes = [vp, vp, C.POINTER(vp), i, C.POINTER(Weight), vp, i, C.POINTER(C.c_float), C.POINTER(C.c_float)]
@@ -714,6 +729,72 @@ class Engine:
         self._check(self.L.hmme_predict_refs_frame(self.h, ra, len(refs), C.byref(fp), f.ctypes.data, rf.ctypes.data, per, out.ctypes.data, out.shape[1]))
         return out
 
+    # ---- L0, L1 or bi per PU, and the prediction from it (include/hmme.h, "L0, L1 or bi per PU") ----
+    def select_dirs_device(self, width, height, n_pics, fp, sel, dirs, d_mv_uni, d_cost_uni, d_mv_bi, d_cost_bi, d_uni_field, d_pred, d_field, d_dir,
+                           d_slot=None, d_ctu_cost=None, stream=0):
+        """hmme_select_dirs_device: the four refinement table sets of n_pics B pictures (device: uni and bi, each [n_pics, 2, count, 593, ...]) and
+        the lists' uni fields int16[n_pics, 2, n_ctu, 64, 2] -> motion field of that shape, directions uint8[n_pics, n_ctu, 64] (1, 2, 3; 0xFF: no
+        CU), covering slots uint16 of that shape and CTU costs uint32[n_pics, n_ctu] (device addresses; d_slot / d_ctu_cost may be None).
+        dirs: one DirParams per picture"""
+        self._check(self.L.hmme_select_dirs_device(self.h, int(width), int(height), int(n_pics), C.byref(fp), C.byref(sel), _dir_params(dirs, n_pics),
+                                                   d_mv_uni, d_cost_uni, d_mv_bi, d_cost_bi, d_uni_field, d_pred, d_field, d_dir, d_slot, d_ctu_cost, stream))
+
+    def select_dirs_frame(self, width, height, sel, dir_params, mv_uni, cost_uni, mv_bi, cost_bi, uni_field, pred_q=None, ctu_first=0, ctu_count=-1,
+                          field=None, dirs=None, slot=None, ctu_cost=None):
+        """hmme_select_dirs_frame: one picture, host arrays.  mv_uni / mv_bi int16[2, count, 593, 2], cost_uni / cost_bi uint32[2, count, 593],
+        uni_field int16[2, n_ctu, 64, 2], pred_q int16[2, n_ctu, 2] or None -> (field int16[2, n_ctu, 64, 2], dirs uint8[n_ctu, 64], slot
+        uint16[n_ctu, 64], ctu_cost uint32[n_ctu]); entries outside the CTU range keep the values of the arrays passed in (zeros when none is)"""
+        n = self.L.hmme_num_ctus(width, height)
+        count = n - ctu_first if ctu_count < 0 else ctu_count
+        fp = FrameParams(1, 0, 8, ctu_first, count)
+        tabs = []
+        for a, dt, tail in ((mv_uni, np.int16, (NUM_PARTS, 2)), (cost_uni, np.uint32, (NUM_PARTS,)), (mv_bi, np.int16, (NUM_PARTS, 2)),
+                            (cost_bi, np.uint32, (NUM_PARTS,))):
+            a = np.ascontiguousarray(a, dtype=dt)
+            assert a.shape == (2, count) + tail
+            tabs.append(a)
+        uf = np.ascontiguousarray(uni_field, dtype=np.int16)
+        assert uf.shape == (2, n, 64, 2)
+        pptr = None
+        if pred_q is not None:
+            pq = np.ascontiguousarray(pred_q, dtype=np.int16)
+            assert pq.shape == (2, n, 2)
+            pptr = pq.ctypes.data
+        outs = []
+        for a, dt, shape in ((field, np.int16, (2, n, 64, 2)), (dirs, np.uint8, (n, 64)), (slot, np.uint16, (n, 64)), (ctu_cost, np.uint32, (n,))):
+            a = np.zeros(shape, dt) if a is None else a
+            assert a.dtype == dt and a.shape == shape and a.flags.c_contiguous
+            outs.append(a)
+        self._check(self.L.hmme_select_dirs_frame(self.h, int(width), int(height), C.byref(fp), C.byref(sel), C.byref(dir_params), tabs[0].ctypes.data,
+                                                  tabs[1].ctypes.data, tabs[2].ctypes.data, tabs[3].ctypes.data, uf.ctypes.data, pptr,
+                                                  *[a.ctypes.data for a in outs]))
+        return tuple(outs)
+
+    def predict_bi_device(self, refs0, refs1, fp, d_mv_field, d_dir_field, mv_per_ctu, d_outs, out_pitch_bytes, stream=0):
+        """hmme_predict_bi_device: the luma prediction of up to 8 pictures whose blocks are L0 (refs0[i]), L1 (refs1[i]) or bi (both, averaged
+        like TComYuv::addAvg): d_mv_field int16[n_pics, 2, n_ctu, mv_per_ctu, 2], d_dir_field uint8[n_pics, n_ctu, mv_per_ctu]; d_outs = one device
+        image address per picture"""
+        assert len(refs0) == len(refs1) == len(d_outs)
+        oa = (C.c_void_p * len(d_outs))(*[int(o) for o in d_outs])
+        self._check(self.L.hmme_predict_bi_device(self.h, _handles(refs0), _handles(refs1), len(refs0), C.byref(fp), d_mv_field, d_dir_field, int(mv_per_ctu),
+                                                  oa, int(out_pitch_bytes), stream))
+
+    def predict_bi_frame(self, ref0, ref1, mv_field, dir_field, out=None, ctu_first=0, ctu_count=-1):
+        """hmme_predict_bi_frame: the prediction of one picture from list 0 (ref0) and list 1 (ref1) -> [height, width] array of the planes'
+        sample type.  mv_field: int16[2, n_ctu, 2] or [2, n_ctu, 1 | 64, 2] quarter pels; dir_field: uint8[n_ctu] or [n_ctu, 1 | 64] (1, 2, 3;
+        anything else: not written); `out` keeps its samples outside the CTU range and in blocks without a direction"""
+        n = self.L.hmme_num_ctus(ref0.width, ref0.height)
+        f0, per = self._field(mv_field[0], n)
+        f1, per1 = self._field(mv_field[1], n)
+        assert per == per1
+        f = np.ascontiguousarray(np.stack([f0, f1]))
+        df = np.ascontiguousarray(dir_field, dtype=np.uint8).reshape(n, -1)
+        assert df.shape == (n, per)
+        out = self._image(ref0, out)
+        fp = FrameParams(1, 0, ref0.bit_depth, ctu_first, ctu_count)
+        self._check(self.L.hmme_predict_bi_frame(self.h, ref0.h, ref1.h, C.byref(fp), f.ctypes.data, df.ctypes.data, per, out.ctypes.data, out.shape[1]))
+        return out
+
     # ---- estimating explicit weighted-prediction parameters (include/hmme.h, "estimating explicit weighted-prediction parameters") ----
     def plane_stats(self, plane):
         """hmme_plane_stats: xCalcACDCParamSlice of one picture -> (dc_sum, ac) = (sum of the samples, sum of |sample - normDC|) over the picture
@@ -819,6 +900,27 @@ def select_refs_check(sel, n_pics, n_refs, ref_cost=None):
     range (pure host arithmetic: needs no GPU).  ref_cost: a sequence of integers (any length: n_refs of them are read) or None"""
     rc = None if ref_cost is None else (C.c_uint32 * max(len(ref_cost), 16))(*[int(v) for v in ref_cost])   # at most 16 are ever read
     return int(load().hmme_select_refs_check(C.byref(sel), int(n_pics), int(n_refs), rc))
+
+
+def _dir_params(dirs, n_pics):
+    """n_pics DirParams as the array the hmme_select_dirs_* calls take"""
+    assert len(dirs) == n_pics
+    a = (DirParams * max(n_pics, 1))()
+    for k, d in enumerate(dirs):
+        a[k] = d
+    return a
+
+
+def select_dirs_check(sel, n_pics, dirs):
+    """hmme_select_dirs_check: 0, or HMME_ERR_ARG when the SelectParams (mv_per_ctu 64, mv_unit 0, price_mv 0 only), the number of pictures
+    (1..4) or a bit count (<= 4096) lies outside its range (pure host arithmetic: needs no GPU).  dirs: a sequence of DirParams (any length:
+    n_pics of them are read) or None"""
+    a = None
+    if dirs is not None:
+        a = (DirParams * max(len(dirs), 4))()
+        for k, d in enumerate(dirs):
+            a[k] = d
+    return int(load().hmme_select_dirs_check(C.byref(sel), int(n_pics), a))
 
 
 def ocl_compat_params(lt_x, lt_y, sr):

@@ -582,6 +582,94 @@ int hmme_predict_refs_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n
 int hmme_predict_refs_frame(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp, const int16_t* mv_field,
                             const uint8_t* ref_field, int mv_per_ctu, void* out, int out_stride);
 
+/* ---- L0, L1 or bi per PU, and the prediction of a picture whose blocks are L0, L1 or bi -------------------------------------
+ * What TEncSearch::predInterSearch ends in for a B picture (paths below source/Lib/TLibEncoder of the reference): every PU takes the
+ * cheapest of list 0, list 1 and bi (TEncSearch.cpp:3291, :3314), the costs being those of xMotionEstimation's closing line (:3808),
+ * floor(fWeight * (cost - mvcost)) + getCost(bits) with fWeight 0.5 in the bi pass; and the prediction of a bi PU, TComYuv::addAvg
+ * (TLibCommon/TComYuv.cpp:352-390) over the two 14-bit intermediates.  New entry points and one new struct; no struct and no existing entry
+ * point changed, so HMME_ABI_VERSION stays 6.  THIS TEXT PLUS THE CITATIONS IS THE RULE.
+ *
+ * Inputs of the decision, for n_pics B pictures (1..4), four table sets each, all quarter-pel refinement tables written for the same
+ * ctu_first / ctu_count:
+ *   d_mv_uni  int16[n_pics][2][count][593][2], d_cost_uni uint32[n_pics][2][count][593]: the uni-directional refinement of list 0 and list 1
+ *             -- what hmme_refine_pairs_device writes with its pairs ordered (picture, list).
+ *   d_mv_bi, d_cost_bi: the same shapes; set [p][l] is what hmme_refine_pairs_bi_device wrote when list l was searched against the origin
+ *             built from list 1-l's field.
+ *   d_uni_field  int16[n_pics][2][n_ctu][64][2]: list l's uni-directional field, indexed by list and NOT swapped -- the field the bi pass of
+ *             list 1-l consumed as d_other_mv.
+ *   d_pred_q  int16[n_pics][2][n_ctu][2], quarter pels, or NULL for (0,0): the predictors the searches took.
+ *   dirs      HOST array of n_pics hmme_dir_params, read before the call returns: the caller's model of uiMbBits[3] (:2969, :3534-3557;
+ *             dir_bits[0], [1], [2] for list 0, list 1 and bi) and of each list's reference-index plus MVP-index bits (list_bits).  Every
+ *             value <= 4096.
+ *   sel       an hmme_select_params with mv_per_ctu == 64, mv_unit == 0 and price_mv == 0 (the tables are refinement tables, whose costs
+ *             contain the MV cost).  8x4 and 4x8 PUs never take part at this granularity, so HM's isBipredRestriction does not arise.
+ * hmme_select_dirs_check (a pure host function: no context, no GPU) returns HMME_ERR_ARG for a sel hmme_select_check refuses or with
+ * another mv_per_ctu / mv_unit / price_mv, n_pics outside 1..4, a NULL dirs, or a bit count above 4096; the calls run it first and launch
+ * NOTHING when it fails.
+ *
+ * Definitions.  mvb(v, p) = bits(vx - px) + bits(vy - py): HM's getBits at cost scale 0, the count behind price_mv's quarter-pel formula.
+ * gc(n) = (lambda_q16 * n) >> 16 with the context's lambda, the product wrapping in 32 bits as in TComRdCost::getCost.  Everything else is
+ * carried in 64 bits.
+ *
+ * Rule, per slot s (pred[l] = list l's predictor of the CTU):
+ *   1. D_U[l] = max(0, cost_uni[l][s] - gc(mvb(mv_uni[l][s], pred[l])))
+ *      C[l]   = D_U[l] + gc(dir_bits[l] + list_bits[l] + mvb(mv_uni[l][s], pred[l]))
+ *      On tables of the engine cost >= gc(mvb) always holds (the cost contains that term): the clamp is a formality.
+ *   2. D_B[l] = max(0, cost_bi[l][s] - gc(mvb(mv_bi[l][s], pred[l]))) >> 1
+ *      C_B[l] = D_B[l] + gc(dir_bits[2] + list_bits[0] + list_bits[1] + mvb(mv_bi[l][s], pred[l]) + mvb(mv_uni[1-l][s], pred[1-l]))
+ *      The other list's motion bits are those of its uni slot s.  That is exact for the slot whose rectangle the consumed field describes
+ *      (slot 592 with one MV per CTU); for every other slot it is the caller's model, like dir_bits and list_bits.
+ *   3. The bi candidate is C_B[0] unless C_B[1] < C_B[0]: strict, list 0 is tried first (:3183-3186, :3226).
+ *   4. C_bi <= C[0] && C_bi <= C[1]: direction 3; otherwise C[0] <= C[1]: direction 1; otherwise direction 2 -- HM's interDir values and HM's
+ *      comparisons (:3291, :3314).
+ *   5. The decision of hmme_select_pairs_device, its steps 1-5 word for word, runs on the merged slots with the winner's cost (64 bits, not
+ *      saturated) standing for "slot cost"; no MV cost is applied again.
+ * Outputs -- only the entries of the CTUs in [ctu_first, ctu_first + ctu_count) are written:
+ *   d_out_field  int16[n_pics][2][n_ctu][64][2], list-major, so that each half feeds the predict and _bi_ calls.  A block under a
+ *                direction-1 or -2 slot holds the winner's MV in its list and (0,0) in the other.  Under a direction-3 slot whose bi
+ *                candidate searched list l it holds mv_bi[l][s] in list l and, in list 1-l, THE BLOCK'S OWN ENTRY OF d_uni_field[1-l]:
+ *                the motion the bi cost was measured with.  (0,0) in both lists for blocks of CUs that do not exist.
+ *   d_out_dir    uint8[n_pics][n_ctu][64]: 1, 2 or 3; 0xFF for blocks of CUs that do not exist; not NULL
+ *   d_out_slot   uint16[n_pics][n_ctu][64], the covering slot, 0xFFFF likewise; may be NULL
+ *   d_out_cost   uint32[n_pics][n_ctu], the CTU's cost, saturated at UINT32_MAX; may be NULL
+ * hmme_select_dirs_device: asynchronous on `stream`; like its siblings it takes no planes, consults of fp only ctu_first / ctu_count, uses
+ * no scratch of the context and is ordered like any kernel of the caller on `stream`.  Buffers: tables, costs, the input field and slots
+ * 4-byte aligned, the output field 8-byte, the directions 2-byte.  hmme_select_dirs_frame: synchronous, host arrays of the same shapes with
+ * n_pics = 1 (dir: the one hmme_dir_params), on the context's private stream; entries outside the CTU range keep their values.
+ *
+ * Prediction.  hmme_predict_bi_device: for picture i (n_pics >= 1, 2 * n_pics <= 16 planes) the luma prediction from refs0[i] (list 0) and
+ * refs1[i] (list 1) with d_mv_field int16[n_pics][2][n_ctu][mv_per_ctu][2] and d_dir_field uint8[n_pics][n_ctu][mv_per_ctu], mv_per_ctu 1 |
+ * 64 -- with 64 what the decision above writes.  Every MV is clamped like TComDataCU::clipMv, as in hmme_predict_pairs_device.
+ *   direction 1 / 2   bit for bit what hmme_predict_pairs_device writes from that list's plane and MV
+ *   direction 3       TComPrediction::motionCompensation without WP (TLibCommon/TComPrediction.cpp:527-541): xPredInterUni with bi = true on
+ *                     both lists -- the 14-bit intermediates P0, P1: vertical stage with shift 6 and offset 0, the copy case
+ *                     (src << (14 - bd)) - 8192 --, then addAvg: ClipBD((P0 + P1 + offset) >> shift) with shift = max(2, 14 - bd) + 1 and
+ *                     offset = (1 << (shift - 1)) + 2 * 8192
+ *   anything else     (0xFF included) the block is not written and reads no plane
+ * d_outs: HOST array of n_pics device images of out_pitch_bytes per row; the writes are those of hmme_predict_pairs_device: inside the
+ * picture and inside the CTU range only.  All planes must have one size and fp's bit depth and belong to the context; each is ordered
+ * across streams like any reference.  A bit depth outside 8..12 is HMME_ERR_ARG; every depth in 8..12 is served (the sum stays in int32).
+ * Unweighted only: TComWeightPrediction::addWeightBi is out of scope.  hmme_predict_bi_frame: synchronous, one picture, host motion field
+ * int16[2][n_ctu][mv_per_ctu][2], direction field and image (out_stride in samples; samples outside the CTU range and of blocks without a
+ * direction keep their values). */
+typedef struct hmme_dir_params {
+  uint32_t dir_bits[3];    /* uiMbBits: list 0, list 1, bi */
+  uint32_t list_bits[2];   /* reference-index + MVP-index bits of list 0, list 1 */
+} hmme_dir_params;
+int hmme_select_dirs_check(const hmme_select_params* sel, int n_pics, const hmme_dir_params* dirs);
+int hmme_select_dirs_device(hmme_ctx* ctx, int width, int height, int n_pics, const hmme_frame_params* fp, const hmme_select_params* sel,
+                            const hmme_dir_params* dirs, const void* d_mv_uni, const void* d_cost_uni, const void* d_mv_bi, const void* d_cost_bi,
+                            const void* d_uni_field, const void* d_pred_q, void* d_out_field, void* d_out_dir, void* d_out_slot, void* d_out_cost,
+                            void* stream);
+int hmme_select_dirs_frame(hmme_ctx* ctx, int width, int height, const hmme_frame_params* fp, const hmme_select_params* sel,
+                           const hmme_dir_params* dir, const int16_t* mv_uni, const uint32_t* cost_uni, const int16_t* mv_bi, const uint32_t* cost_bi,
+                           const int16_t* uni_field, const int16_t* pred_q, int16_t* out_field, uint8_t* out_dir, uint16_t* out_slot,
+                           uint32_t* out_cost);
+int hmme_predict_bi_device(hmme_ctx* ctx, const hmme_plane* const* refs0, const hmme_plane* const* refs1, int n_pics, const hmme_frame_params* fp,
+                           const void* d_mv_field, const void* d_dir_field, int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream);
+int hmme_predict_bi_frame(hmme_ctx* ctx, const hmme_plane* ref0, const hmme_plane* ref1, const hmme_frame_params* fp, const int16_t* mv_field,
+                          const uint8_t* dir_field, int mv_per_ctu, void* out, int out_stride);
+
 /* ---- estimating explicit weighted-prediction parameters --------------------------------------------------------
  * Where the weights of the *_w calls come from when the caller has none: the luma part of HM's estimator, WeightPredAnalysis::
  * xCalcACDCParamSlice, xEstimateWPParamSlice, xUpdatingWPParameters, xSelectWP and xCalcSADvalueWP (source/Lib/TLibEncoder/
