@@ -1941,13 +1941,13 @@ int bi_weight_args(int bit_depth, const hmme_weight* wp, const char* which, char
 
 // the other list's weight (TComWeightPrediction.cpp:133-180): ClipBD(((w0 * (P + 8192) + round') >> shift') + offset) with
 // shift' = shift + headRoom and round' = 1 << (shift' - 1); wp->round is not used.  P is a Pel, so P + 8192 lies within [-24 576, 40 959].
-int other_weight_eval(int bit_depth, const hmme_weight* wp, bool* identity, hmme::MePredWp<1>* pw, char* msg, size_t n) {
-  const int rc = bi_weight_args(bit_depth, wp, "other", msg, n);
+int other_weight_eval(int bit_depth, const hmme_weight* wp, bool* identity, hmme::MePredWp<1>* pw, char* msg, size_t n, const char* which = "other") {
+  const int rc = bi_weight_args(bit_depth, wp, which, msg, n);
   if (rc) return rc;
   const int sh = wp->shift + std::max(2, 14 - bit_depth);
   const long rnd = 1L << (sh - 1);
   if (std::labs((long)wp->w0) * 40960 + rnd > INT32_MAX) {
-    snprintf(msg, n, "weighted prediction of the other list: |w0| * 40960 + round' reaches %ld, beyond 32 bits", std::labs((long)wp->w0) * 40960 + rnd);
+    snprintf(msg, n, "weighted prediction of the %s list: |w0| * 40960 + round' reaches %ld, beyond 32 bits", which, std::labs((long)wp->w0) * 40960 + rnd);
     return HMME_ERR_UNSUPPORTED;
   }
   if (identity) *identity = wp->w0 == (1 << wp->shift) && wp->offset == 0;
@@ -1963,6 +1963,41 @@ int bipred_weight_eval(int bit_depth, const hmme_weight* wp, const hmme_weight* 
   if (rc == HMME_OK) rc = weight_eval(bit_depth, wp, refine, kBiOrigin, bw ? &bw->info : nullptr, msg, n);
   if (rc == HMME_OK) rc = other_weight_eval(bit_depth, other_wp, bw ? &bw->other_identity : nullptr, bw ? &bw->pw : nullptr, msg, n);
   return rc;
+}
+
+// The two weights of a picture whose blocks are L0, L1 or bi (hmme_predict_bi_w_device; the rule: include/hmme.h): the argument errors of
+// both first, then each weight alone -- uni-directional blocks go through addWeightUni with it --, then the pair in addWeightBi
+// (TComWeightPrediction.cpp:46-49, :67-129, getWpScaling :230-247): shift' = shift + 1 + headRoom, round' = 1 << (shift' - 1), the two
+// offsets summed and multiplied by 2^(shift' - 1).  P + 8192 lies within [-24 576, 40 959] for each list.
+struct PredBiWp {
+  bool identity = true;   // both weights: the picture is hmme_predict_bi_device's
+  hmme::MePredBiWp<1> k{};
+};
+int predict_bi_weight_eval(int bit_depth, const hmme_weight* wp0, const hmme_weight* wp1, PredBiWp* out, char* msg, size_t n) {
+  int rc = bi_weight_args(bit_depth, wp0, "L0", msg, n);
+  if (rc == HMME_OK) rc = bi_weight_args(bit_depth, wp1, "L1", msg, n);
+  if (rc) return rc;
+  if (wp0->shift != wp1->shift) {
+    snprintf(msg, n, "weighted bi-prediction: shifts %d and %d differ (luma has one log2WeightDenom per slice)", wp0->shift, wp1->shift);
+    return HMME_ERR_ARG;
+  }
+  bool id[2];
+  hmme::MePredWp<1> uni[2];
+  rc = other_weight_eval(bit_depth, wp0, &id[0], &uni[0], msg, n, "L0");
+  if (rc == HMME_OK) rc = other_weight_eval(bit_depth, wp1, &id[1], &uni[1], msg, n, "L1");
+  if (rc) return rc;
+  const int sh = wp0->shift + 1 + std::max(2, 14 - bit_depth);
+  const int64_t rnd = (int64_t)1 << (sh - 1), off = (int64_t)wp0->offset + wp1->offset;
+  const int64_t reach = (std::llabs((long long)wp0->w0) + std::llabs((long long)wp1->w0)) * 40960 + rnd + std::llabs((long long)off) * rnd;
+  if (reach > INT32_MAX) {
+    snprintf(msg, n, "weighted bi-prediction: (|w0| + |w1|) * 40960 + round' + |offset0 + offset1| * 2^(shift' - 1) reaches %lld, beyond 32 bits", (long long)reach);
+    return HMME_ERR_UNSUPPORTED;
+  }
+  if (out) {
+    out->identity = id[0] && id[1];
+    out->k = hmme::MePredBiWp<1>{wp0->w0, wp1->w0, (int)(rnd + off * rnd), sh, {uni[0], uni[1]}};
+  }
+  return HMME_OK;
 }
 
 // every pair's two weights before anything is launched; the message names the pair
@@ -1983,17 +2018,19 @@ int check_bi_weights(hmme_ctx* ctx, const char* who, const hmme_frame_params* fp
 
 // me_predict_kernel for CTUs [first, first + count) of `src` with its motion field (int16 [n_ctu][mv_per_ctu][2], device)
 // pw: the weight of a slice with explicit weighted prediction (null: none, and the identity -- WP = 0 computes the same samples)
-// pr: a reference picture per block (hmme_predict_refs_device: an image without weights; `src` gives the geometry all planes share)
+// pr: a reference picture per block (hmme_predict_refs_device; `src` gives the geometry all planes share), prw: with one weight per
+// reference (hmme_predict_refs_w_device; null: none)
 int launch_predict(hmme_ctx* ctx, const hmme_plane* src, const int16_t* d_field, int mv_per_ctu, int first, int count, bool origin, const uint8_t* cur_blocks,
                    int bias, uint8_t* dst, long dst_ctu_x, long dst_ctu_y, int dst_pitch, hipStream_t s, const hmme::MePredWp<1>* pw = nullptr,
-                   const hmme::MePredRefs<1>* pr = nullptr) {
+                   const hmme::MePredRefs<1>* pr = nullptr, const hmme::MePredWp<2>* prw = nullptr) {
   const dim3 grid((unsigned)count), block(256);
 #define HMME_PREDICT(T, OUT, WP, REFS, wp, refs)                                                                                                \
   hipLaunchKernelGGL((hmme::me_predict_kernel<T, OUT, WP, REFS>), grid, block, 0, s, src->origin(), src->pitch, d_field, mv_per_ctu, first,    \
                      src->width, src->height, src->bit_depth, cur_blocks, bias, dst, dst_ctu_x, dst_ctu_y, dst_pitch, wp, refs)
 #define HMME_PREDICT_T(T)                                                                      \
   do {                                                                                         \
-    if (pr) { HMME_PREDICT(T, 0, 0, 1, hmme::MePredWp<0>{}, *pr); }                            \
+    if (pr && prw) { HMME_PREDICT(T, 0, 2, 1, *prw, *pr); }                                    \
+    else if (pr) { HMME_PREDICT(T, 0, 0, 1, hmme::MePredWp<0>{}, *pr); }                       \
     else if (origin && pw) { HMME_PREDICT(T, 1, 1, 0, *pw, hmme::MePredRefs<0>{}); }           \
     else if (origin) { HMME_PREDICT(T, 1, 0, 0, hmme::MePredWp<0>{}, hmme::MePredRefs<0>{}); } \
     else if (pw) { HMME_PREDICT(T, 0, 1, 0, *pw, hmme::MePredRefs<0>{}); }                     \
@@ -2015,15 +2052,15 @@ int hmme_bipred_check(int bit_depth, int refine) {
 namespace {
 size_t pad16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
 
-// What hmme_predict_pairs_device, _w_device and hmme_predict_refs_device check alike, in the order that decides the code returned
-// null_arg: one of the caller's other pointers is null; wps: one weight per plane, or null for none
+// What hmme_predict_pairs_device, _w_device, hmme_predict_refs_device and _w_device check alike, in the order that decides the code returned
+// null_arg: one of the caller's other pointers is null; wps: one weight per plane, or null for none; unit: what a refusal calls plane r
 struct PredictArgs {
   hmme_frame_params f;   // fp for pairs_begin
   bool identity[hmme::kMaxRefs];
   hmme::MePredWp<1> pw[hmme::kMaxRefs];
 };
 int predict_args(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs, int n, bool null_arg, const hmme_frame_params* fp, const hmme_weight* wps,
-                 const void* d_mv_field, int mv_per_ctu, int out_pitch_bytes, PredictArgs* a) {
+                 const void* d_mv_field, int mv_per_ctu, int out_pitch_bytes, PredictArgs* a, const char* unit = "picture") {
   int rc = bi_check(ctx, who, fp, 0);
   if (rc) return rc;
   if (!refs || null_arg || n < 1 || n > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d pictures outside 1..%d (or a null argument)", who, n, hmme::kMaxRefs);
@@ -2032,7 +2069,7 @@ int predict_args(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs, 
     if (!wps) continue;
     char msg[256];
     rc = other_weight_eval(fp->bit_depth, &wps[r], &a->identity[r], &a->pw[r], msg, sizeof msg);
-    if (rc) return fail(ctx, rc, "%s: picture %d: %s", who, r, msg);
+    if (rc) return fail(ctx, rc, "%s: %s %d: %s", who, unit, r, msg);
   }
   if (!d_mv_field || (mv_per_ctu != 1 && mv_per_ctu != 64)) return fail(ctx, HMME_ERR_ARG, "%s: null motion field, or %d MVs per CTU (1 or 64)", who, mv_per_ctu);
   for (int r = 0; r < n; ++r)
@@ -2545,34 +2582,74 @@ int hmme_select_refs_frame(hmme_ctx* ctx, int width, int height, int n_refs, con
                        });
 }
 
-// one launch of me_predict_kernel<SrcT, 0, 0, 1>: every block from the plane its reference index names
-int hmme_predict_refs_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp, const void* d_mv_field,
-                             const void* d_ref_field, int mv_per_ctu, void* d_out, int out_pitch_bytes, void* stream) {
-  if (!ctx) return HMME_ERR_ARG;
+namespace {
+// hmme_predict_refs_device (wps == null) and hmme_predict_refs_w_device: one launch of me_predict_kernel<SrcT, 0, WP, 1>, every block from
+// the plane its reference index names.  WP = 0 without weights and where every weight is the identity, else 2: every block through
+// addWeightUni with its plane's weight (for an identity weight that is the unweighted sample: nested floors)
+int predict_refs(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp, const hmme_weight* wps,
+                 const void* d_mv_field, const void* d_ref_field, int mv_per_ctu, void* d_out, int out_pitch_bytes, void* stream) {
   PredictArgs a;
-  int rc = predict_args(ctx, "hmme_predict_refs_device", refs, n_refs, !d_ref_field || !d_out, fp, nullptr, d_mv_field, mv_per_ctu, out_pitch_bytes, &a);
+  int rc = predict_args(ctx, who, refs, n_refs, !d_ref_field || !d_out, fp, wps, d_mv_field, mv_per_ctu, out_pitch_bytes, &a, "reference");
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   PairLaunch pl;   // checks every plane: of this context, of one size, of fp's bit depth; each is ordered like a reference
   rc = pairs_begin(ctx, refs, refs, n_refs, &a.f, s, &pl);
   if (rc || pl.count == 0) return rc;
   const hmme::MePredRefs<1> pr = {pl.refs, (const uint8_t*)d_ref_field, n_refs};
-  rc = launch_predict(ctx, refs[0], (const int16_t*)d_mv_field, mv_per_ctu, pl.first, pl.count, false, nullptr, 0, (uint8_t*)d_out, 0, 0, out_pitch_bytes, s, nullptr, &pr);
+  hmme::MePredWp<2> prw = {};
+  bool weighted = false;
+  for (int r = 0; r < n_refs; ++r) {
+    weighted = weighted || !a.identity[r];
+    if (wps) prw.ref[r] = a.pw[r];
+  }
+  rc = launch_predict(ctx, refs[0], (const int16_t*)d_mv_field, mv_per_ctu, pl.first, pl.count, false, nullptr, 0, (uint8_t*)d_out, 0, 0, out_pitch_bytes, s, nullptr, &pr,
+                      weighted ? &prw : nullptr);
   return pairs_end(ctx, refs, refs, n_refs, s, rc);   // whatever the launch returned: the scratch is acquired
+}
+
+// hmme_predict_refs_frame (wps == null) and hmme_predict_refs_w_frame
+int predict_refs_frame(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp, const hmme_weight* wps,
+                       const int16_t* mv_field, const uint8_t* ref_field, int mv_per_ctu, void* out, int out_stride) {
+  int rc = bi_check(ctx, who, fp, 0);
+  if (rc) return rc;
+  if (!refs || n_refs < 1 || n_refs > hmme::kMaxRefs || !refs[0]) return fail(ctx, HMME_ERR_ARG, "%s: %d reference pictures outside 1..%d (or a null plane)", who, n_refs, hmme::kMaxRefs);
+  for (int r = 0; wps && r < n_refs; ++r) {   // before anything is staged
+    char msg[256];
+    rc = other_weight_eval(fp->bit_depth, &wps[r], nullptr, nullptr, msg, sizeof msg);
+    if (rc) return fail(ctx, rc, "%s: reference %d: %s", who, r, msg);
+  }
+  if (!mv_field || !ref_field || !out || (mv_per_ctu != 1 && mv_per_ctu != 64)) return fail(ctx, HMME_ERR_ARG, "%s: null argument, or %d MVs per CTU (1 or 64)", who, mv_per_ctu);
+  // blocks without a reference, too, come back as they were
+  return predict_staged(ctx, who, refs[0], mv_field, ref_field, mv_per_ctu, out, out_stride, [&](void* d_field, void* d_ref_field, void* d_img, int pitch, hipStream_t s) {
+    return predict_refs(ctx, who, refs, n_refs, fp, wps, d_field, d_ref_field, mv_per_ctu, d_img, pitch, s);
+  });
+}
+}  // namespace
+
+int hmme_predict_refs_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp, const void* d_mv_field,
+                             const void* d_ref_field, int mv_per_ctu, void* d_out, int out_pitch_bytes, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  return predict_refs(ctx, "hmme_predict_refs_device", refs, n_refs, fp, nullptr, d_mv_field, d_ref_field, mv_per_ctu, d_out, out_pitch_bytes, stream);
+}
+
+int hmme_predict_refs_w_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp, const hmme_weight* wps,
+                               const void* d_mv_field, const void* d_ref_field, int mv_per_ctu, void* d_out, int out_pitch_bytes, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  if (!wps) return fail(ctx, HMME_ERR_ARG, "hmme_predict_refs_w_device: null weights");
+  return predict_refs(ctx, "hmme_predict_refs_w_device", refs, n_refs, fp, wps, d_mv_field, d_ref_field, mv_per_ctu, d_out, out_pitch_bytes, stream);
 }
 
 int hmme_predict_refs_frame(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp, const int16_t* mv_field,
                             const uint8_t* ref_field, int mv_per_ctu, void* out, int out_stride) {
   if (!ctx) return HMME_ERR_ARG;
-  const char* who = "hmme_predict_refs_frame";
-  int rc = bi_check(ctx, who, fp, 0);
-  if (rc) return rc;
-  if (!refs || n_refs < 1 || n_refs > hmme::kMaxRefs || !refs[0]) return fail(ctx, HMME_ERR_ARG, "%s: %d reference pictures outside 1..%d (or a null plane)", who, n_refs, hmme::kMaxRefs);
-  if (!mv_field || !ref_field || !out || (mv_per_ctu != 1 && mv_per_ctu != 64)) return fail(ctx, HMME_ERR_ARG, "%s: null argument, or %d MVs per CTU (1 or 64)", who, mv_per_ctu);
-  // blocks without a reference, too, come back as they were
-  return predict_staged(ctx, who, refs[0], mv_field, ref_field, mv_per_ctu, out, out_stride, [&](void* d_field, void* d_ref_field, void* d_img, int pitch, hipStream_t s) {
-    return hmme_predict_refs_device(ctx, refs, n_refs, fp, d_field, d_ref_field, mv_per_ctu, d_img, pitch, s);
-  });
+  return predict_refs_frame(ctx, "hmme_predict_refs_frame", refs, n_refs, fp, nullptr, mv_field, ref_field, mv_per_ctu, out, out_stride);
+}
+
+int hmme_predict_refs_w_frame(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp, const hmme_weight* wps,
+                              const int16_t* mv_field, const uint8_t* ref_field, int mv_per_ctu, void* out, int out_stride) {
+  if (!ctx) return HMME_ERR_ARG;
+  if (!wps) return fail(ctx, HMME_ERR_ARG, "hmme_predict_refs_w_frame: null weights");
+  return predict_refs_frame(ctx, "hmme_predict_refs_w_frame", refs, n_refs, fp, wps, mv_field, ref_field, mv_per_ctu, out, out_stride);
 }
 
 // ---- L0, L1 or bi per PU: the decision over the four table sets of a B picture, and the prediction that follows it ---------------------------
@@ -2645,16 +2722,32 @@ int hmme_select_dirs_frame(hmme_ctx* ctx, int width, int height, const hmme_fram
                        }, &bi);
 }
 
-// one launch of me_predict_bi_kernel per picture: every block from the planes its direction names
-int hmme_predict_bi_device(hmme_ctx* ctx, const hmme_plane* const* refs0, const hmme_plane* const* refs1, int n_pics, const hmme_frame_params* fp,
-                           const void* d_mv_field, const void* d_dir_field, int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream) {
-  if (!ctx) return HMME_ERR_ARG;
-  const char* who = "hmme_predict_bi_device";
+namespace {
+// every picture's two weights before anything is launched; the message names the picture
+int check_predict_bi_weights(hmme_ctx* ctx, const char* who, const hmme_frame_params* fp, const hmme_weight* wps0, const hmme_weight* wps1, int n_pics, PredBiWp* bw) {
+  if (!fp) return fail(ctx, HMME_ERR_ARG, "%s: null params", who);
+  if (!wps0 || !wps1) return fail(ctx, HMME_ERR_ARG, "%s: null weights", who);
+  char msg[256];
+  for (int i = 0; i < n_pics; ++i) {
+    const int rc = predict_bi_weight_eval(fp->bit_depth, &wps0[i], &wps1[i], bw ? &bw[i] : nullptr, msg, sizeof msg);
+    if (rc) return fail(ctx, rc, "%s: picture %d: %s", who, i, msg);
+  }
+  return HMME_OK;
+}
+
+// hmme_predict_bi_device (weighted == false) and hmme_predict_bi_w_device: one launch of me_predict_bi_kernel per picture, every block from
+// the planes its direction names; WP = 0 for a picture without weights or with two identities, else 1
+int predict_bi(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs0, const hmme_plane* const* refs1, int n_pics, const hmme_frame_params* fp,
+               const hmme_weight* wps0, const hmme_weight* wps1, bool weighted, const void* d_mv_field, const void* d_dir_field, int mv_per_ctu, void* const* d_outs,
+               int out_pitch_bytes, void* stream) {
   if (!refs0 || !refs1 || n_pics < 1 || 2 * n_pics > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d pictures outside 1..%d (or a null plane list)", who, n_pics, hmme::kMaxRefs / 2);
+  PredBiWp bw[hmme::kMaxRefs / 2];
+  int rc = weighted ? check_predict_bi_weights(ctx, who, fp, wps0, wps1, n_pics, bw) : HMME_OK;
+  if (rc) return rc;
   const hmme_plane* planes[hmme::kMaxRefs];   // picture i: planes[2 i] (list 0), planes[2 i + 1] (list 1)
   for (int i = 0; i < n_pics; ++i) { planes[2 * i] = refs0[i]; planes[2 * i + 1] = refs1[i]; }
   PredictArgs a;
-  int rc = predict_args(ctx, who, planes, 2 * n_pics, !d_dir_field || !d_outs, fp, nullptr, d_mv_field, mv_per_ctu, out_pitch_bytes, &a);
+  rc = predict_args(ctx, who, planes, 2 * n_pics, !d_dir_field || !d_outs, fp, nullptr, d_mv_field, mv_per_ctu, out_pitch_bytes, &a);
   if (rc) return rc;
   for (int i = 0; i < n_pics; ++i)
     if (!d_outs[i]) return fail(ctx, HMME_ERR_ARG, "%s: null output image", who);
@@ -2667,29 +2760,63 @@ int hmme_predict_bi_device(hmme_ctx* ctx, const hmme_plane* const* refs0, const 
   for (int i = 0; i < n_pics; ++i) {
     const int16_t* field = (const int16_t*)d_mv_field + blocks * 4 * i;
     const uint8_t* dirs = (const uint8_t*)d_dir_field + blocks * i;
-    if (p0->bps == 1)
-      hipLaunchKernelGGL(hmme::me_predict_bi_kernel<uint8_t>, dim3((unsigned)pl.count), dim3(256), 0, s, planes[2 * i]->origin(), planes[2 * i + 1]->origin(), p0->pitch,
-                         field, dirs, mv_per_ctu, p0->n_ctu, pl.first, p0->width, p0->height, p0->bit_depth, (uint8_t*)d_outs[i], out_pitch_bytes);
-    else
-      hipLaunchKernelGGL(hmme::me_predict_bi_kernel<uint16_t>, dim3((unsigned)pl.count), dim3(256), 0, s, planes[2 * i]->origin(), planes[2 * i + 1]->origin(), p0->pitch,
-                         field, dirs, mv_per_ctu, p0->n_ctu, pl.first, p0->width, p0->height, p0->bit_depth, (uint8_t*)d_outs[i], out_pitch_bytes);
+#define HMME_PREDICT_BI(T, WP, wp)                                                                                                                       \
+  hipLaunchKernelGGL((hmme::me_predict_bi_kernel<T, WP>), dim3((unsigned)pl.count), dim3(256), 0, s, planes[2 * i]->origin(), planes[2 * i + 1]->origin(), \
+                     p0->pitch, field, dirs, mv_per_ctu, p0->n_ctu, pl.first, p0->width, p0->height, p0->bit_depth, (uint8_t*)d_outs[i], out_pitch_bytes, wp)
+    if (bw[i].identity) {
+      if (p0->bps == 1) HMME_PREDICT_BI(uint8_t, 0, hmme::MePredBiWp<0>{}); else HMME_PREDICT_BI(uint16_t, 0, hmme::MePredBiWp<0>{});
+    } else {
+      if (p0->bps == 1) HMME_PREDICT_BI(uint8_t, 1, bw[i].k); else HMME_PREDICT_BI(uint16_t, 1, bw[i].k);
+    }
+#undef HMME_PREDICT_BI
   }
   rc = hipGetLastError() == hipSuccess ? HMME_OK : fail(ctx, HMME_ERR_DEVICE, "%s: launch failed", who);
   return pairs_end(ctx, planes, planes, 2 * n_pics, s, rc);   // whatever the launches returned: the scratch is acquired
 }
 
-int hmme_predict_bi_frame(hmme_ctx* ctx, const hmme_plane* ref0, const hmme_plane* ref1, const hmme_frame_params* fp, const int16_t* mv_field,
-                          const uint8_t* dir_field, int mv_per_ctu, void* out, int out_stride) {
-  if (!ctx) return HMME_ERR_ARG;
-  const char* who = "hmme_predict_bi_frame";
-  int rc = bi_check(ctx, who, fp, 0);
+// hmme_predict_bi_frame (weighted == false) and hmme_predict_bi_w_frame
+int predict_bi_frame(hmme_ctx* ctx, const char* who, const hmme_plane* ref0, const hmme_plane* ref1, const hmme_frame_params* fp, const hmme_weight* wp0,
+                     const hmme_weight* wp1, bool weighted, const int16_t* mv_field, const uint8_t* dir_field, int mv_per_ctu, void* out, int out_stride) {
+  int rc = weighted ? check_predict_bi_weights(ctx, who, fp, wp0, wp1, 1, nullptr) : HMME_OK;   // before anything is staged
+  if (rc == HMME_OK) rc = bi_check(ctx, who, fp, 0);
   if (rc) return rc;
   if (!ref0 || !ref1 || !mv_field || !dir_field || !out || (mv_per_ctu != 1 && mv_per_ctu != 64))
     return fail(ctx, HMME_ERR_ARG, "%s: null argument, or %d MVs per CTU (1 or 64)", who, mv_per_ctu);
   // blocks without a direction, too, come back as they were
   return predict_staged(ctx, who, ref0, mv_field, dir_field, mv_per_ctu, out, out_stride, [&](void* d_field, void* d_dir_field, void* d_img, int pitch, hipStream_t s) {
-    return hmme_predict_bi_device(ctx, &ref0, &ref1, 1, fp, d_field, d_dir_field, mv_per_ctu, &d_img, pitch, s);
+    return predict_bi(ctx, who, &ref0, &ref1, 1, fp, wp0, wp1, weighted, d_field, d_dir_field, mv_per_ctu, &d_img, pitch, s);
   }, 2);
+}
+}  // namespace
+
+int hmme_predict_bi_weight_check(int bit_depth, const hmme_weight* wp0, const hmme_weight* wp1) {
+  char msg[256];
+  return predict_bi_weight_eval(bit_depth, wp0, wp1, nullptr, msg, sizeof msg);
+}
+
+int hmme_predict_bi_device(hmme_ctx* ctx, const hmme_plane* const* refs0, const hmme_plane* const* refs1, int n_pics, const hmme_frame_params* fp,
+                           const void* d_mv_field, const void* d_dir_field, int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  return predict_bi(ctx, "hmme_predict_bi_device", refs0, refs1, n_pics, fp, nullptr, nullptr, false, d_mv_field, d_dir_field, mv_per_ctu, d_outs, out_pitch_bytes, stream);
+}
+
+int hmme_predict_bi_w_device(hmme_ctx* ctx, const hmme_plane* const* refs0, const hmme_plane* const* refs1, int n_pics, const hmme_frame_params* fp,
+                             const hmme_weight* wps0, const hmme_weight* wps1, const void* d_mv_field, const void* d_dir_field, int mv_per_ctu,
+                             void* const* d_outs, int out_pitch_bytes, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  return predict_bi(ctx, "hmme_predict_bi_w_device", refs0, refs1, n_pics, fp, wps0, wps1, true, d_mv_field, d_dir_field, mv_per_ctu, d_outs, out_pitch_bytes, stream);
+}
+
+int hmme_predict_bi_frame(hmme_ctx* ctx, const hmme_plane* ref0, const hmme_plane* ref1, const hmme_frame_params* fp, const int16_t* mv_field,
+                          const uint8_t* dir_field, int mv_per_ctu, void* out, int out_stride) {
+  if (!ctx) return HMME_ERR_ARG;
+  return predict_bi_frame(ctx, "hmme_predict_bi_frame", ref0, ref1, fp, nullptr, nullptr, false, mv_field, dir_field, mv_per_ctu, out, out_stride);
+}
+
+int hmme_predict_bi_w_frame(hmme_ctx* ctx, const hmme_plane* ref0, const hmme_plane* ref1, const hmme_frame_params* fp, const hmme_weight* wp0,
+                            const hmme_weight* wp1, const int16_t* mv_field, const uint8_t* dir_field, int mv_per_ctu, void* out, int out_stride) {
+  if (!ctx) return HMME_ERR_ARG;
+  return predict_bi_frame(ctx, "hmme_predict_bi_w_frame", ref0, ref1, fp, wp0, wp1, true, mv_field, dir_field, mv_per_ctu, out, out_stride);
 }
 
 // ---- estimating explicit weighted-prediction parameters ----------------------------------------------------------------------------------------

@@ -2216,8 +2216,12 @@ __constant__ int kLumaTaps[4][8] = {{0, 0, 0, 64, 0, 0, 0, 0}, {-1, 4, -10, 58, 
 //            wave handles one 8x8 block at a time -- so the choice of the source base is a scalar one.  A block whose index is >= n_refs
 //            (0xFF: no CU covers it) is not live: it reads no plane and writes nothing, and still meets both barriers of its iteration.
 //            REFS = 0 takes an empty struct and compiles to what it did without it.
+//   WP = 2:  WP = 1 with one weight per reference picture (hmme_predict_refs_w_device; REFS = 1 only): the block's reference index --
+//            already a scalar -- picks its {w0, round', shift', offset} among the sixteen in the kernel arguments.  A value of its own
+//            and not more fields of MePredWp<1>, because that struct is an argument of the existing WP = 1 kernels.
 template <int WP> struct MePredWp {};
 template <> struct MePredWp<1> { int w0, round, shift, offset; };   // round / shift: addWeightUni's round' and shift'
+template <> struct MePredWp<2> { MePredWp<1> ref[kMaxRefs]; };
 template <int REFS> struct MePredRefs {};
 template <> struct MePredRefs<1> { RefSet set; const uint8_t* ref_field; int n_refs; };
 template <typename SrcT, int OUT, int WP = 0, int REFS = 0>
@@ -2242,8 +2246,9 @@ me_predict_kernel(const uint8_t* __restrict__ ref_origin, int ref_pitch, const i
     clip_mv_q(mx, my, cu_x, cu_y, pic_w, pic_h);
     bool live = OUT == 1 || (cu_x + bx < pic_w && cu_y + by < pic_h);   // wave-uniform
     const uint8_t* origin = ref_origin;
+    int ri = 0;
     if constexpr (REFS) {
-      const int ri = __builtin_amdgcn_readfirstlane((int)refs.ref_field[(long)ctu * mv_per_ctu + (mv_per_ctu == 1 ? 0 : b)]);
+      ri = __builtin_amdgcn_readfirstlane((int)refs.ref_field[(long)ctu * mv_per_ctu + (mv_per_ctu == 1 ? 0 : b)]);
       live = live && ri < refs.n_refs;
       origin = refs.set.base[ri < refs.n_refs ? ri : 0];
     }
@@ -2278,8 +2283,10 @@ me_predict_kernel(const uint8_t* __restrict__ ref_origin, int ref_pitch, const i
       for (int t = 0; t < 8; ++t) sum += cv[t] * (int)mid[wave][(r + t) * 8 + c];
       int v;
       if constexpr (WP) {
+        MePredWp<1> w;
+        if constexpr (WP == 2) w = wp.ref[ri]; else w = wp;   // live: ri < n_refs
         const int P = (int16_t)(sum >> 6);   // HM keeps the intermediate in a Pel: P + 8192 lies within [-24 576, 40 959] whatever the plane holds
-        const long long t = (long long)((wp.w0 * (P + 8192) + wp.round) >> wp.shift) + wp.offset;
+        const long long t = (long long)((w.w0 * (P + 8192) + w.round) >> w.shift) + w.offset;
         v = t < 0 ? 0 : (t > maxv ? maxv : (int)t);
       } else {
         v = (sum + off2) >> sh2;
@@ -2683,11 +2690,20 @@ __device__ __forceinline__ int me_predict_block_sum(bool live, const uint8_t* or
 // both lists leave the 14-bit intermediate P = sum >> 6 (xPredInterUni with bi = true), then TComYuv::addAvg (TComYuv.cpp:352-390):
 // ClipBD((P0 + P1 + offset) >> shift), shift = headRoom + 1, offset = (1 << (shift - 1)) + 2 * 8192 -- |P| < 2^15, so int32 holds it at every
 // depth.  Any other direction (0xFF: no CU) reads no plane and writes nothing, and still meets all four barriers of its iteration.
-template <typename SrcT>
+//   WP = 1:  the same picture in a B slice with getWPBiPred() (hmme_predict_bi_w_device; TComPrediction.cpp:603-651 xPredInterBi,
+//            TComWeightPrediction.cpp:268-301 xWeightedPredictionBi).  Direction 1 / 2: me_predict_kernel<.., WP = 1> with that list's weight
+//            (addWeightUni, the offset added in 64 bits).  Direction 3: addWeightBi (:46-49, :67-129) with the bi-directional getWpScaling
+//            (:230-247): ClipBD((w0 * (P0 + 8192) + w1 * (P1 + 8192) + add) >> shift), shift = the slice's log2WeightDenom + 1 + headRoom and
+//            add = (1 << (shift - 1)) + (offset0 + offset1) * 2^(shift - 1) -- both made by the host, which also refuses a pair whose numerator
+//            could leave int32 (hmme_predict_bi_weight_check), so int32 holds it.  The shift is arithmetic.  WP = 0 takes an empty struct and
+//            compiles to what it did without it.
+template <int WP> struct MePredBiWp {};
+template <> struct MePredBiWp<1> { int w0, w1, add, shift; MePredWp<1> uni[2]; };
+template <typename SrcT, int WP = 0>
 __global__ void __launch_bounds__(256)
 me_predict_bi_kernel(const uint8_t* __restrict__ ref0, const uint8_t* __restrict__ ref1, int ref_pitch, const int16_t* __restrict__ mv_field,
                      const uint8_t* __restrict__ dir_field, int mv_per_ctu, int n_ctu, int ctu_first, int pic_w, int pic_h, int bit_depth,
-                     uint8_t* __restrict__ dst, int dst_pitch) {
+                     uint8_t* __restrict__ dst, int dst_pitch, MePredBiWp<WP> wp) {
   __shared__ int16_t patch[4][15 * 16];
   __shared__ int16_t mid[4][15 * 8];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -2716,9 +2732,21 @@ me_predict_bi_kernel(const uint8_t* __restrict__ ref0, const uint8_t* __restrict
     const int sum1 = me_predict_block_sum<SrcT>(use1, ref1, ref_pitch, cu_x + bx, cu_y + by, mx1, my1, patch[wave], mid[wave], lane, sh1, off1);
     if (in_pic) {
       int v;
-      if (use0 && use1) v = ((int)(int16_t)(sum0 >> 6) + (int)(int16_t)(sum1 >> 6) + offb) >> shb;   // HM keeps the intermediates in Pels
-      else v = ((use0 ? sum0 : sum1) + off2) >> sh2;
-      v = v < 0 ? 0 : (v > maxv ? maxv : v);
+      if constexpr (WP) {
+        if (use0 && use1) {
+          v = (wp.w0 * ((int)(int16_t)(sum0 >> 6) + 8192) + wp.w1 * ((int)(int16_t)(sum1 >> 6) + 8192) + wp.add) >> wp.shift;
+          v = v < 0 ? 0 : (v > maxv ? maxv : v);
+        } else {
+          const MePredWp<1> w = use0 ? wp.uni[0] : wp.uni[1];   // wave-uniform
+          const int P = (int16_t)((use0 ? sum0 : sum1) >> 6);
+          const long long t = (long long)((w.w0 * (P + 8192) + w.round) >> w.shift) + w.offset;
+          v = t < 0 ? 0 : (t > maxv ? maxv : (int)t);
+        }
+      } else {
+        if (use0 && use1) v = ((int)(int16_t)(sum0 >> 6) + (int)(int16_t)(sum1 >> 6) + offb) >> shb;   // HM keeps the intermediates in Pels
+        else v = ((use0 ? sum0 : sum1) + off2) >> sh2;
+        v = v < 0 ? 0 : (v > maxv ? maxv : v);
+      }
       const int x = cu_x + bx + (lane & 7), y = cu_y + by + (lane >> 3);
       if (x < pic_w && y < pic_h) ((SrcT*)(dst + (long)y * dst_pitch))[x] = (SrcT)v;
     }

@@ -32,6 +32,7 @@ SYMBOLS = ["hmme_create", "hmme_destroy", "hmme_last_error", "hmme_device_info",
            "hmme_ref_idx_bits", "hmme_select_refs_check", "hmme_select_refs_device", "hmme_select_refs_frame",
            "hmme_predict_refs_device", "hmme_predict_refs_frame",
            "hmme_select_dirs_check", "hmme_select_dirs_device", "hmme_select_dirs_frame", "hmme_predict_bi_device", "hmme_predict_bi_frame",
+           "hmme_predict_bi_weight_check", "hmme_predict_bi_w_device", "hmme_predict_bi_w_frame", "hmme_predict_refs_w_device", "hmme_predict_refs_w_frame",
            "hmme_plane_stats", "hmme_wp_estimate"]
 # test / measurement entry points (include/hmme_test.h): not part of the boundary
 TEST_SYMBOLS = ["hmme_test_time_search_kernel", "hmme_test_device_address", "hmme_test_frac_deal", "hmme_test_tail_plan", "hmme_test_time_weight_passes", "hmme_test_time_bipred_origin",
@@ -194,6 +195,11 @@ def load():
     L.hmme_select_dirs_frame.argtypes = [vp, i, i, C.POINTER(FrameParams), C.POINTER(SelectParams), C.POINTER(DirParams)] + [vp] * 10
     L.hmme_predict_bi_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, C.POINTER(FrameParams), vp, vp, i, C.POINTER(vp), i, vp]
     L.hmme_predict_bi_frame.argtypes = [vp, vp, vp, C.POINTER(FrameParams), vp, vp, i, vp, i]
+    L.hmme_predict_bi_weight_check.argtypes = [i, pw, pw]
+    L.hmme_predict_bi_w_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, C.POINTER(FrameParams), pw, pw, vp, vp, i, C.POINTER(vp), i, vp]
+    L.hmme_predict_bi_w_frame.argtypes = [vp, vp, vp, C.POINTER(FrameParams), pw, pw, vp, vp, i, vp, i]
+    L.hmme_predict_refs_w_device.argtypes = [vp, C.POINTER(vp), i, C.POINTER(FrameParams), pw, vp, vp, i, vp, i, vp]
+    L.hmme_predict_refs_w_frame.argtypes = [vp, C.POINTER(vp), i, C.POINTER(FrameParams), pw, vp, vp, i, vp, i]
     L.hmme_plane_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.hmme_wp_estimate.argtypes = [vp, vp, C.POINTER(vp), i, i, C.POINTER(Weight), C.POINTER(WpInfo)]
     L.hmme_test_time_wp_estimate_passes.argtypes = [vp, vp, C.POINTER(vp), i, C.POINTER(Weight), vp, i, C.POINTER(C.c_float), C.POINTER(C.c_float)]
@@ -795,6 +801,52 @@ class Engine:
         self._check(self.L.hmme_predict_bi_frame(self.h, ref0.h, ref1.h, C.byref(fp), f.ctypes.data, df.ctypes.data, per, out.ctypes.data, out.shape[1]))
         return out
 
+    # ---- the final prediction in a WP slice (include/hmme.h, "the final prediction in a slice with explicit weighted prediction"): weights
+    # are (w0, offset, shift, round)
+    def predict_bi_w_device(self, refs0, refs1, fp, weights0, weights1, d_mv_field, d_dir_field, mv_per_ctu, d_outs, out_pitch_bytes, stream=0):
+        """hmme_predict_bi_w_device: predict_bi_device with two weights per picture (weights0[i] for refs0[i], weights1[i] for refs1[i]): uni
+        blocks like predict_pairs_w_device, bi blocks like TComWeightPrediction::addWeightBi"""
+        assert len(refs0) == len(refs1) == len(d_outs) == len(weights0) == len(weights1)
+        oa = (C.c_void_p * len(d_outs))(*[int(o) for o in d_outs])
+        self._check(self.L.hmme_predict_bi_w_device(self.h, _handles(refs0), _handles(refs1), len(refs0), C.byref(fp), self._weights(weights0),
+                                                    self._weights(weights1), d_mv_field, d_dir_field, int(mv_per_ctu), oa, int(out_pitch_bytes), stream))
+
+    def predict_bi_w_frame(self, ref0, ref1, wp0, wp1, mv_field, dir_field, out=None, ctu_first=0, ctu_count=-1):
+        """hmme_predict_bi_w_frame: predict_bi_frame with the weights wp0 (ref0) and wp1 (ref1)"""
+        n = self.L.hmme_num_ctus(ref0.width, ref0.height)
+        f0, per = self._field(mv_field[0], n)
+        f1, per1 = self._field(mv_field[1], n)
+        assert per == per1
+        f = np.ascontiguousarray(np.stack([f0, f1]))
+        df = np.ascontiguousarray(dir_field, dtype=np.uint8).reshape(n, -1)
+        assert df.shape == (n, per)
+        out = self._image(ref0, out)
+        fp = FrameParams(1, 0, ref0.bit_depth, ctu_first, ctu_count)
+        w0, w1 = (Weight(*[int(v) for v in w]) for w in (wp0, wp1))
+        self._check(self.L.hmme_predict_bi_w_frame(self.h, ref0.h, ref1.h, C.byref(fp), C.byref(w0), C.byref(w1), f.ctypes.data, df.ctypes.data, per,
+                                                   out.ctypes.data, out.shape[1]))
+        return out
+
+    def predict_refs_w_device(self, refs, fp, weights, d_mv_field, d_ref_field, mv_per_ctu, d_out, out_pitch_bytes, stream=0):
+        """hmme_predict_refs_w_device: predict_refs_device with one weight per reference"""
+        assert len(refs) == len(weights)
+        self._check(self.L.hmme_predict_refs_w_device(self.h, _handles(refs), len(refs), C.byref(fp), self._weights(weights), d_mv_field, d_ref_field,
+                                                      int(mv_per_ctu), d_out, int(out_pitch_bytes), stream))
+
+    def predict_refs_w_frame(self, refs, weights, mv_field, ref_field, out=None, ctu_first=0, ctu_count=-1):
+        """hmme_predict_refs_w_frame: predict_refs_frame with one weight per reference"""
+        assert len(refs) == len(weights)
+        r0 = refs[0]
+        n = self.L.hmme_num_ctus(r0.width, r0.height)
+        f, per = self._field(mv_field, n)
+        rf = np.ascontiguousarray(ref_field, dtype=np.uint8).reshape(n, -1)
+        assert rf.shape == (n, per)
+        out = self._image(r0, out)
+        fp = FrameParams(1, 0, r0.bit_depth, ctu_first, ctu_count)
+        self._check(self.L.hmme_predict_refs_w_frame(self.h, _handles(refs), len(refs), C.byref(fp), self._weights(weights), f.ctypes.data, rf.ctypes.data, per,
+                                                     out.ctypes.data, out.shape[1]))
+        return out
+
     # ---- estimating explicit weighted-prediction parameters (include/hmme.h, "estimating explicit weighted-prediction parameters") ----
     def plane_stats(self, plane):
         """hmme_plane_stats: xCalcACDCParamSlice of one picture -> (dc_sum, ac) = (sum of the samples, sum of |sample - normDC|) over the picture
@@ -870,6 +922,14 @@ def bipred_weight_check(bit_depth, wp, other_wp, refine=False):
     w = None if wp is None else C.byref(Weight(*[int(v) for v in wp]))
     ow = None if other_wp is None else C.byref(Weight(*[int(v) for v in other_wp]))
     return int(load().hmme_bipred_weight_check(int(bit_depth), w, ow, 1 if refine else 0))
+
+
+def predict_bi_weight_check(bit_depth, wp0, wp1):
+    """hmme_predict_bi_weight_check: 0, or the HMME_ERR_* code with which hmme_predict_bi_w_device refuses a picture's two weights (wp0: list
+    0's, wp1: list 1's; None passes a null pointer) at this bit depth (pure host arithmetic: needs no GPU)"""
+    w0 = None if wp0 is None else C.byref(Weight(*[int(v) for v in wp0]))
+    w1 = None if wp1 is None else C.byref(Weight(*[int(v) for v in wp1]))
+    return int(load().hmme_predict_bi_weight_check(int(bit_depth), w0, w1))
 
 
 def select_check(sel):

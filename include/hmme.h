@@ -566,7 +566,7 @@ int hmme_select_frame(hmme_ctx* ctx, int width, int height, const hmme_frame_par
  * refs[d_ref_field[ctu][block]]: d_mv_field int16[n_ctu][mv_per_ctu][2], d_ref_field uint8[n_ctu][mv_per_ctu], mv_per_ctu 1 | 64 (what the
  * decision writes with mv_per_ctu = 64), d_out one device image of out_pitch_bytes per row.  A block whose index is >= n_refs -- 0xFF
  * included -- is not written and reads nothing.  All refs (1..16) must have one size and fp's bit depth and belong to the context; each is
- * ordered across streams like any reference.  Unweighted only: a variant with one explicit weight per reference is out of scope.
+ * ordered across streams like any reference.  With one explicit weight per reference: hmme_predict_refs_w_device, further down.
  * hmme_predict_refs_frame: synchronous, host motion field, reference field and image (out_stride in samples; samples outside the CTU
  * range and of blocks without a reference keep their values). */
 int hmme_ref_idx_bits(int n_refs, int ref_idx);
@@ -649,7 +649,7 @@ int hmme_predict_refs_frame(hmme_ctx* ctx, const hmme_plane* const* refs, int n_
  * d_outs: HOST array of n_pics device images of out_pitch_bytes per row; the writes are those of hmme_predict_pairs_device: inside the
  * picture and inside the CTU range only.  All planes must have one size and fp's bit depth and belong to the context; each is ordered
  * across streams like any reference.  A bit depth outside 8..12 is HMME_ERR_ARG; every depth in 8..12 is served (the sum stays in int32).
- * Unweighted only: TComWeightPrediction::addWeightBi is out of scope.  hmme_predict_bi_frame: synchronous, one picture, host motion field
+ * In a slice with explicit weighted prediction (addWeightBi): hmme_predict_bi_w_device, further down.  hmme_predict_bi_frame: synchronous, one picture, host motion field
  * int16[2][n_ctu][mv_per_ctu][2], direction field and image (out_stride in samples; samples outside the CTU range and of blocks without a
  * direction keep their values). */
 typedef struct hmme_dir_params {
@@ -669,6 +669,65 @@ int hmme_predict_bi_device(hmme_ctx* ctx, const hmme_plane* const* refs0, const 
                            const void* d_mv_field, const void* d_dir_field, int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream);
 int hmme_predict_bi_frame(hmme_ctx* ctx, const hmme_plane* ref0, const hmme_plane* ref1, const hmme_frame_params* fp, const int16_t* mv_field,
                           const uint8_t* dir_field, int mv_per_ctu, void* out, int out_stride);
+
+/* ---- the final prediction in a slice with explicit weighted prediction ---------------------------------------------------------
+ * hmme_predict_bi_device and hmme_predict_refs_device with explicit weights: the prediction that belongs to the decisions of
+ * hmme_select_dirs_device / hmme_select_refs_device when the searches before them were the *_w and *_bi_w_* calls.  New entry points only; no
+ * struct and no existing entry point changed, so HMME_ABI_VERSION stays 6.  THIS TEXT PLUS THE CITATIONS IS THE RULE (paths below source/Lib
+ * of the reference).
+ *
+ * hmme_predict_bi_w_device / hmme_predict_bi_w_frame: hmme_predict_bi_device / hmme_predict_bi_frame with two weights per picture, wps0[i]
+ * for refs0[i] and wps1[i] for refs1[i], both HOST arrays of n_pics hmme_weight, read before the call returns.  Fields, directions, mv_per_ctu
+ * 1 | 64, the clamp of every MV, CTU sub-ranges, the limit 2 * n_pics <= 16, plane ownership and stream ordering are unchanged.  The rule is
+ * TComPrediction::xPredInterBi in a B slice with getWPBiPred() (TLibCommon/TComPrediction.cpp:603-651) -> xWeightedPredictionBi
+ * (TLibCommon/TComWeightPrediction.cpp:268-301) with getWpScaling (:189-264):
+ *   direction 1 / 2   bit for bit what hmme_predict_pairs_w_device writes from that list's plane, MV and weight: xPredInterUni with bi = true,
+ *                     then addWeightUni (:133-180) with the uni-directional getWpScaling (:250-262) -- rule 1 of the section "bi-prediction with
+ *                     explicit weighted prediction" above; wp.round is not used
+ *   direction 3       addWeightBi (:46-49, :67-129) with the bi-directional getWpScaling (:230-247).  With head = max(2, 14 - bd) and P0, P1 the
+ *                     Pel-truncated 14-bit intermediates of hmme_predict_bi_device:
+ *                         shift' = wp0.shift + 1 + head
+ *                         round' = 1 << (shift' - 1)
+ *                         off    = wp0.offset + wp1.offset
+ *                         pred   = ClipBD((w0 * (P0 + 8192) + w1 * (P1 + 8192) + round' + off * 2^(shift' - 1)) >> shift')
+ *                     The shift is arithmetic.  HM writes offset << (shift - 1); it is the product here, so that a negative offset is defined.
+ *   anything else     (0xFF included) the block is not written and reads no plane
+ * Luma has ONE log2WeightDenom per slice and getWpScaling uses list 0's shift for both lists (:242-245), so wps0[i].shift != wps1[i].shift is
+ * HMME_ERR_ARG.  hmme_wp_estimate called ONCE with the references of both lists shares the denominator among all of them (its step 2) and so
+ * delivers weights this call accepts; two calls, one per list, may not.  TComPrediction::xCheckIdenticalMotion does not apply: it is off
+ * under getWPBiPred() (TLibCommon/TComPrediction.cpp:501-503).
+ * A picture whose two weights are both the identity (w0 == 1 << shift, offset 0, whatever round holds) runs hmme_predict_bi_device's kernel.
+ * That is exact: uni blocks by the nested floors of rule 1 above, bi blocks because with d = shift
+ *     (2^d * (P0 + P1 + 16384) + 2^(d + head)) >> (d + 1 + head)  =  (P0 + P1 + 16384 + 2^head) >> (head + 1)  =  addAvg
+ * (the numerator is a multiple of 2^d).  One identity beside another weight is served by the weighted kernel.
+ *
+ * hmme_predict_refs_w_device / hmme_predict_refs_w_frame: hmme_predict_refs_device / hmme_predict_refs_frame with one weight per reference
+ * (wps: n_refs HOST weights, read before the call returns): every block gets the addWeightUni result (direction 1 / 2 above) of the plane
+ * its index names with that plane's weight; a block whose index is >= n_refs is untouched.  If every weight is the identity the unweighted
+ * kernel runs; otherwise every block goes through the weighted formula, which for an identity weight equals the unweighted sample (nested
+ * floors again).
+ *
+ * Refusal.  hmme_predict_bi_weight_check(bit_depth, wp0, wp1), a pure host function (no context, no GPU):
+ *   bit depth outside 8..12, a NULL weight, a shift outside 0..15, unequal shifts                    -> HMME_ERR_ARG
+ *   either weight alone: |w0| * 40 960 + round'_uni beyond int32 (the "other weight" line of
+ *   hmme_bipred_weight_check, round'_uni = 1 << (shift + head - 1): uni blocks use it)                -> HMME_ERR_UNSUPPORTED
+ *   the pair: (|w0| + |w1|) * 40 960 + round' + |off| * 2^(shift' - 1) beyond int32, evaluated in 64 bits  -> HMME_ERR_UNSUPPORTED
+ * The pair's bound is derived, not measured: P is a Pel, so P + 8192 lies within [-24 576, 40 959] for each list whatever the planes hold,
+ * and below the bound the int32 numerator cannot wrap.  HM wraps there; the engine refuses.  HM's own range -- |w| <= 255, shift <= 7,
+ * |offset| <= 128 << (bd - 8) per list -- is served entirely at every depth 8..12: its largest numerator is 510 * 40 960 + 2^9 + 4096 * 2^9
+ * < 2^25 at 12 bits and 510 * 40 960 + 2^13 + 256 * 2^13 < 2^25 at 8.  The bi_w calls run the check for every picture first, the refs_w calls
+ * its single-weight line for every reference, and launch NOTHING if one fails: they return that code, hmme_last_error names the picture /
+ * the reference. */
+int hmme_predict_bi_weight_check(int bit_depth, const hmme_weight* wp0, const hmme_weight* wp1);
+int hmme_predict_bi_w_device(hmme_ctx* ctx, const hmme_plane* const* refs0, const hmme_plane* const* refs1, int n_pics, const hmme_frame_params* fp,
+                             const hmme_weight* wps0, const hmme_weight* wps1, const void* d_mv_field, const void* d_dir_field, int mv_per_ctu,
+                             void* const* d_outs, int out_pitch_bytes, void* stream);
+int hmme_predict_bi_w_frame(hmme_ctx* ctx, const hmme_plane* ref0, const hmme_plane* ref1, const hmme_frame_params* fp, const hmme_weight* wp0,
+                            const hmme_weight* wp1, const int16_t* mv_field, const uint8_t* dir_field, int mv_per_ctu, void* out, int out_stride);
+int hmme_predict_refs_w_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp, const hmme_weight* wps,
+                               const void* d_mv_field, const void* d_ref_field, int mv_per_ctu, void* d_out, int out_pitch_bytes, void* stream);
+int hmme_predict_refs_w_frame(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp, const hmme_weight* wps,
+                              const int16_t* mv_field, const uint8_t* ref_field, int mv_per_ctu, void* out, int out_stride);
 
 /* ---- estimating explicit weighted-prediction parameters --------------------------------------------------------
  * Where the weights of the *_w calls come from when the caller has none: the luma part of HM's estimator, WeightPredAnalysis::
