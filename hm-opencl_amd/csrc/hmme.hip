@@ -2102,23 +2102,30 @@ int predict_pairs(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs,
 // hmme_predict_frame, _w, hmme_predict_refs_frame and hmme_predict_bi_frame: the motion field (`lists` of them, one behind the other) and,
 // behind it, the reference / direction field (null: none) into ctx->d_bi[0], the caller's image through ctx->d_bi[1] both ways around `launch`:
 // samples that are not written come back as they were
+// chroma (hmme_predict_chroma_*_frame): `ref` is the Cb plane, the fields are those of the n_ctu LUMA CTUs, and a second image of the same
+// size and stride (Cr) travels right behind the first in ctx->d_bi[1]
+struct StagedChroma { int n_ctu; void* out2; };
 int predict_staged(hmme_ctx* ctx, const char* who, const hmme_plane* ref, const int16_t* mv_field, const uint8_t* ref_field, int mv_per_ctu, void* out, int out_stride,
-                   const std::function<int(void* d_field, void* d_ref_field, void* d_img, int pitch, hipStream_t s)>& launch, int lists = 1) {
+                   const std::function<int(void* d_field, void* d_ref_field, void* d_img, int pitch, hipStream_t s)>& launch, int lists = 1,
+                   const StagedChroma* chroma = nullptr) {
   if (ref->ctx != ctx) return fail(ctx, HMME_ERR_ARG, "plane belongs to another context (planes are used with the context that created them)");
   if (out_stride < ref->width) return fail(ctx, HMME_ERR_ARG, "%s: output stride %d below the picture width", who, out_stride);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t blocks = (size_t)ref->n_ctu * mv_per_ctu, field_bytes = sizeof(int16_t) * 2 * blocks * lists, row = (size_t)ref->width * ref->bps;
+  const size_t blocks = (size_t)(chroma ? chroma->n_ctu : ref->n_ctu) * mv_per_ctu, field_bytes = sizeof(int16_t) * 2 * blocks * lists, row = (size_t)ref->width * ref->bps;
+  const size_t img = row * ref->height;
   int rc = ensure(ctx, &ctx->d_bi[0], &ctx->bi_cap[0], pad16(field_bytes) + (ref_field ? blocks : 0));
-  if (rc == HMME_OK) rc = ensure(ctx, &ctx->d_bi[1], &ctx->bi_cap[1], row * ref->height);
+  if (rc == HMME_OK) rc = ensure(ctx, &ctx->d_bi[1], &ctx->bi_cap[1], img * (chroma ? 2 : 1));
   if (rc) return rc;
   hipStream_t s = ctx->stream;
   uint8_t* d_ref_field = ctx->d_bi[0] + pad16(field_bytes);
   HIP_TRY(ctx, hipMemcpyAsync(ctx->d_bi[0], mv_field, field_bytes, hipMemcpyHostToDevice, s));
   if (ref_field) HIP_TRY(ctx, hipMemcpyAsync(d_ref_field, ref_field, blocks, hipMemcpyHostToDevice, s));
   HIP_TRY(ctx, hipMemcpy2DAsync(ctx->d_bi[1], row, out, (size_t)out_stride * ref->bps, row, ref->height, hipMemcpyHostToDevice, s));
+  if (chroma) HIP_TRY(ctx, hipMemcpy2DAsync(ctx->d_bi[1] + img, row, chroma->out2, (size_t)out_stride * ref->bps, row, ref->height, hipMemcpyHostToDevice, s));
   rc = launch(ctx->d_bi[0], d_ref_field, ctx->d_bi[1], (int)row, s);
   if (rc) return rc;
   HIP_TRY(ctx, hipMemcpy2DAsync(out, (size_t)out_stride * ref->bps, ctx->d_bi[1], row, row, ref->height, hipMemcpyDeviceToHost, s));
+  if (chroma) HIP_TRY(ctx, hipMemcpy2DAsync(chroma->out2, (size_t)out_stride * ref->bps, ctx->d_bi[1] + img, row, row, ref->height, hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipStreamSynchronize(s));
   return HMME_OK;
 }
@@ -2817,6 +2824,231 @@ int hmme_predict_bi_w_frame(hmme_ctx* ctx, const hmme_plane* ref0, const hmme_pl
                             const hmme_weight* wp1, const int16_t* mv_field, const uint8_t* dir_field, int mv_per_ctu, void* out, int out_stride) {
   if (!ctx) return HMME_ERR_ARG;
   return predict_bi_frame(ctx, "hmme_predict_bi_w_frame", ref0, ref1, fp, wp0, wp1, true, mv_field, dir_field, mv_per_ctu, out, out_stride);
+}
+
+// ---- 4:2:0 chroma motion compensation from the luma motion fields ------------------------------------------------------------------------------
+// The three prediction forms for Cb and Cr (me_predict_chroma_kernel; the rule: include/hmme.h).  Planes, images and weights come in component
+// pairs; the fields and the CTU range are those of the LUMA picture of width x height, so the planes go through pairs_begin with the whole
+// range (a chroma plane counts its own CTUs) and the luma range is taken from ctu_range.
+namespace {
+struct ChromaLaunch {
+  PairLaunch pl;
+  int w = 0, h = 0, n_ctu = 0, first = 0, count = 0;   // luma
+};
+// a refusal of the shared checks names the entry, too
+int chroma_named(hmme_ctx* ctx, const char* who, int rc) {
+  if (rc && ctx->err.compare(0, strlen(who), who) != 0) ctx->err = std::string(who) + ": " + ctx->err;
+  return rc;
+}
+// 4:2:0: an even luma size, every plane (none is null) half of it each way
+int chroma_size(hmme_ctx* ctx, const char* who, const hmme_plane* const* planes, int n, int width, int height) {
+  if (width < 16 || height < 16 || (width & 1) || (height & 1)) return fail(ctx, HMME_ERR_ARG, "%s: luma size %d x %d: 4:2:0 needs an even size of at least 16 x 16", who, width, height);
+  for (int r = 0; r < n; ++r)
+    if (planes[r]->width != width / 2 || planes[r]->height != height / 2)
+      return fail(ctx, HMME_ERR_ARG, "%s: plane %d is %d x %d, the chroma of a %d x %d picture is %d x %d", who, r, planes[r]->width, planes[r]->height, width, height, width / 2, height / 2);
+  return HMME_OK;
+}
+// after predict_args (no plane is null): the luma size, the planes' size, the luma CTU range; then pairs_begin
+int chroma_begin(hmme_ctx* ctx, const char* who, const hmme_plane* const* planes, int n, int width, int height, const hmme_frame_params* fp, const PredictArgs& a,
+                 hipStream_t s, ChromaLaunch* cl) {
+  int rc = chroma_size(ctx, who, planes, n, width, height);
+  if (rc) return rc;
+  cl->w = width; cl->h = height; cl->n_ctu = hmme_num_ctus(width, height);
+  rc = chroma_named(ctx, who, ctu_range(ctx, fp, cl->n_ctu, &cl->first, &cl->count));
+  if (rc) return rc;
+  hmme_frame_params f = a.f;
+  f.ctu_first = 0; f.ctu_count = -1;
+  return chroma_named(ctx, who, pairs_begin(ctx, planes, planes, n, &f, s, &cl->pl));   // every plane: of this context, of one size, of fp's bit depth
+}
+
+extern "C++" {
+template <int FORM, int WP>
+int launch_chroma(hmme_ctx* ctx, const hmme_plane* p0, const hmme::MeChromaSrc& src, const int16_t* d_field, int mv_per_ctu, const ChromaLaunch& cl, void* d_cb, void* d_cr,
+                  int out_pitch_bytes, hipStream_t s, const hmme::MeChromaWp<FORM, WP>& wp) {
+#define HMME_CHROMA(T, PER)                                                                                                                            \
+  hipLaunchKernelGGL((hmme::me_predict_chroma_kernel<T, FORM, WP, PER>), dim3((unsigned)cl.count), dim3(256), 0, s, src, p0->pitch, d_field, cl.first, \
+                     cl.w, cl.h, p0->bit_depth, (uint8_t*)d_cb, (uint8_t*)d_cr, out_pitch_bytes, wp)
+  if (p0->bps == 1) { if (mv_per_ctu == 1) HMME_CHROMA(uint8_t, 1); else HMME_CHROMA(uint8_t, 64); }
+  else { if (mv_per_ctu == 1) HMME_CHROMA(uint16_t, 1); else HMME_CHROMA(uint16_t, 64); }
+#undef HMME_CHROMA
+  HIP_TRY(ctx, hipGetLastError());
+  return HMME_OK;
+}
+}  // extern "C++"
+
+// hmme_predict_chroma_pairs_device: one launch per picture, WP = 0 without weights and where both components' are the identity
+int predict_chroma_pairs(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs, int n_pairs, int width, int height, const hmme_frame_params* fp,
+                         const hmme_weight* wps, const void* d_mv_field, int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream) {
+  if (n_pairs < 1 || 2 * n_pairs > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d pictures outside 1..%d", who, n_pairs, hmme::kMaxRefs / 2);
+  PredictArgs a;
+  int rc = predict_args(ctx, who, refs, 2 * n_pairs, !d_outs, fp, wps, d_mv_field, mv_per_ctu, out_pitch_bytes, &a, "plane");
+  if (rc) return rc;
+  for (int r = 0; r < 2 * n_pairs; ++r)
+    if (!d_outs[r]) return fail(ctx, HMME_ERR_ARG, "%s: null output image", who);
+  hipStream_t s = (hipStream_t)stream;
+  ChromaLaunch cl;
+  rc = chroma_begin(ctx, who, refs, 2 * n_pairs, width, height, fp, a, s, &cl);
+  if (rc) return rc;
+  const size_t field = (size_t)cl.n_ctu * mv_per_ctu * 2;
+  for (int i = 0; i < n_pairs && rc == HMME_OK && cl.count; ++i) {
+    hmme::MeChromaSrc src = {};
+    src.set.base[0] = refs[2 * i]->origin(); src.set.base[1] = refs[2 * i + 1]->origin();
+    const int16_t* f = (const int16_t*)d_mv_field + field * i;
+    if (a.identity[2 * i] && a.identity[2 * i + 1])
+      rc = launch_chroma<0, 0>(ctx, refs[0], src, f, mv_per_ctu, cl, d_outs[2 * i], d_outs[2 * i + 1], out_pitch_bytes, s, hmme::MeChromaWp<0, 0>{});
+    else
+      rc = launch_chroma<0, 1>(ctx, refs[0], src, f, mv_per_ctu, cl, d_outs[2 * i], d_outs[2 * i + 1], out_pitch_bytes, s, hmme::MeChromaWp<0, 1>{{a.pw[2 * i], a.pw[2 * i + 1]}});
+  }
+  return pairs_end(ctx, refs, refs, 2 * n_pairs, s, rc);   // whatever the launches returned: the scratch is acquired
+}
+
+// hmme_predict_chroma_refs_device: one launch, WP = 0 without weights and where every weight is the identity, else 2
+int predict_chroma_refs(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs, int n_refs, int width, int height, const hmme_frame_params* fp,
+                        const hmme_weight* wps, const void* d_mv_field, const void* d_ref_field, int mv_per_ctu, void* d_out_cb, void* d_out_cr, int out_pitch_bytes,
+                        void* stream) {
+  if (n_refs < 1 || 2 * n_refs > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d reference pictures outside 1..%d", who, n_refs, hmme::kMaxRefs / 2);
+  PredictArgs a;
+  int rc = predict_args(ctx, who, refs, 2 * n_refs, !d_ref_field || !d_out_cb || !d_out_cr, fp, wps, d_mv_field, mv_per_ctu, out_pitch_bytes, &a, "plane");
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  ChromaLaunch cl;
+  rc = chroma_begin(ctx, who, refs, 2 * n_refs, width, height, fp, a, s, &cl);
+  if (rc) return rc;
+  if (cl.count) {
+    hmme::MeChromaSrc src = {cl.pl.refs, (const uint8_t*)d_ref_field, n_refs, cl.n_ctu};
+    hmme::MeChromaWp<1, 2> prw = {};
+    bool weighted = false;
+    for (int r = 0; r < 2 * n_refs; ++r) {
+      weighted = weighted || !a.identity[r];
+      if (wps) prw.ref[r] = a.pw[r];
+    }
+    if (weighted) rc = launch_chroma<1, 2>(ctx, refs[0], src, (const int16_t*)d_mv_field, mv_per_ctu, cl, d_out_cb, d_out_cr, out_pitch_bytes, s, prw);
+    else rc = launch_chroma<1, 0>(ctx, refs[0], src, (const int16_t*)d_mv_field, mv_per_ctu, cl, d_out_cb, d_out_cr, out_pitch_bytes, s, hmme::MeChromaWp<1, 0>{});
+  }
+  return pairs_end(ctx, refs, refs, 2 * n_refs, s, rc);
+}
+
+// hmme_predict_chroma_bi_device: one launch per picture; a component's two weights go through predict_bi_weight_eval like a luma picture's.
+// WP = 0 for a picture without weights or with four identities, else 1
+int predict_chroma_bi(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs0, const hmme_plane* const* refs1, int n_pics, int width, int height,
+                      const hmme_frame_params* fp, const hmme_weight* wps0, const hmme_weight* wps1, const void* d_mv_field, const void* d_dir_field, int mv_per_ctu,
+                      void* const* d_outs, int out_pitch_bytes, void* stream) {
+  if (!refs0 || !refs1 || n_pics < 1 || 4 * n_pics > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d pictures outside 1..%d (or a null plane list)", who, n_pics, hmme::kMaxRefs / 4);
+  PredBiWp bw[hmme::kMaxRefs / 2];   // entry 2 i + c: component c of picture i
+  int rc = (wps0 || wps1) ? check_predict_bi_weights(ctx, who, fp, wps0, wps1, 2 * n_pics, bw) : HMME_OK;
+  if (rc) return rc;
+  const hmme_plane* planes[hmme::kMaxRefs];   // picture i: planes[4 i], [4 i + 1] (list 0: Cb, Cr), planes[4 i + 2], [4 i + 3] (list 1)
+  for (int i = 0; i < n_pics; ++i)
+    for (int c = 0; c < 2; ++c) { planes[4 * i + c] = refs0[2 * i + c]; planes[4 * i + 2 + c] = refs1[2 * i + c]; }
+  PredictArgs a;
+  rc = predict_args(ctx, who, planes, 4 * n_pics, !d_dir_field || !d_outs, fp, nullptr, d_mv_field, mv_per_ctu, out_pitch_bytes, &a, "plane");
+  if (rc) return rc;
+  for (int r = 0; r < 2 * n_pics; ++r)
+    if (!d_outs[r]) return fail(ctx, HMME_ERR_ARG, "%s: null output image", who);
+  hipStream_t s = (hipStream_t)stream;
+  ChromaLaunch cl;
+  rc = chroma_begin(ctx, who, planes, 4 * n_pics, width, height, fp, a, s, &cl);
+  if (rc) return rc;
+  const size_t blocks = (size_t)cl.n_ctu * mv_per_ctu;
+  for (int i = 0; i < n_pics && rc == HMME_OK && cl.count; ++i) {
+    hmme::MeChromaSrc src = {};
+    for (int k = 0; k < 4; ++k) src.set.base[k] = planes[4 * i + k]->origin();
+    src.field = (const uint8_t*)d_dir_field + blocks * i;
+    src.n_ctu = cl.n_ctu;
+    const int16_t* f = (const int16_t*)d_mv_field + blocks * 4 * i;
+    if (bw[2 * i].identity && bw[2 * i + 1].identity)
+      rc = launch_chroma<2, 0>(ctx, planes[0], src, f, mv_per_ctu, cl, d_outs[2 * i], d_outs[2 * i + 1], out_pitch_bytes, s, hmme::MeChromaWp<2, 0>{});
+    else
+      rc = launch_chroma<2, 1>(ctx, planes[0], src, f, mv_per_ctu, cl, d_outs[2 * i], d_outs[2 * i + 1], out_pitch_bytes, s, hmme::MeChromaWp<2, 1>{{bw[2 * i].k, bw[2 * i + 1].k}});
+  }
+  return pairs_end(ctx, planes, planes, 4 * n_pics, s, rc);
+}
+
+// what the three _frame forms check before anything is staged
+int chroma_frame_args(hmme_ctx* ctx, const char* who, const hmme_frame_params* fp, const hmme_plane* const* planes, int n, bool null_arg, int mv_per_ctu, int width, int height) {
+  int rc = bi_check(ctx, who, fp, 0);
+  if (rc) return rc;
+  if (!planes || null_arg || (mv_per_ctu != 1 && mv_per_ctu != 64)) return fail(ctx, HMME_ERR_ARG, "%s: null argument, or %d MVs per CTU (1 or 64)", who, mv_per_ctu);
+  for (int r = 0; r < n; ++r)
+    if (!planes[r]) return fail(ctx, HMME_ERR_ARG, "%s: null plane", who);
+  // the images are staged at the first plane's size and sample type (every plane's depth is compared with fp's before a launch)
+  if (planes[0]->bit_depth != fp->bit_depth) return fail(ctx, HMME_ERR_ARG, "%s: planes hold %d-bit samples, the call asks for %d", who, planes[0]->bit_depth, fp->bit_depth);
+  return chroma_size(ctx, who, planes, n, width, height);
+}
+}  // namespace
+
+int hmme_predict_chroma_pairs_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_pairs, int width, int height, const hmme_frame_params* fp,
+                                     const hmme_weight* wps, const void* d_mv_field, int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  return predict_chroma_pairs(ctx, "hmme_predict_chroma_pairs_device", refs, n_pairs, width, height, fp, wps, d_mv_field, mv_per_ctu, d_outs, out_pitch_bytes, stream);
+}
+
+int hmme_predict_chroma_frame(hmme_ctx* ctx, const hmme_plane* const* ref, int width, int height, const hmme_frame_params* fp, const hmme_weight* wp,
+                              const int16_t* mv_field, int mv_per_ctu, void* const* outs, int out_stride) {
+  if (!ctx) return HMME_ERR_ARG;
+  const char* who = "hmme_predict_chroma_frame";
+  int rc = chroma_frame_args(ctx, who, fp, ref, 2, !mv_field || !outs || !outs[0] || !outs[1], mv_per_ctu, width, height);
+  for (int c = 0; rc == HMME_OK && wp && c < 2; ++c) {   // before anything is staged
+    char msg[256];
+    rc = other_weight_eval(fp->bit_depth, &wp[c], nullptr, nullptr, msg, sizeof msg);
+    if (rc) return fail(ctx, rc, "%s: plane %d: %s", who, c, msg);
+  }
+  if (rc) return rc;
+  const StagedChroma ch = {hmme_num_ctus(width, height), outs[1]};
+  return chroma_named(ctx, who, predict_staged(ctx, who, ref[0], mv_field, nullptr, mv_per_ctu, outs[0], out_stride, [&](void* d_field, void*, void* d_img, int pitch, hipStream_t s) {
+    void* d_outs[2] = {d_img, (uint8_t*)d_img + (size_t)pitch * ref[0]->height};
+    return predict_chroma_pairs(ctx, who, ref, 1, width, height, fp, wp, d_field, mv_per_ctu, d_outs, pitch, s);
+  }, 1, &ch));
+}
+
+int hmme_predict_chroma_refs_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, int width, int height, const hmme_frame_params* fp,
+                                    const hmme_weight* wps, const void* d_mv_field, const void* d_ref_field, int mv_per_ctu, void* d_out_cb, void* d_out_cr,
+                                    int out_pitch_bytes, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  return predict_chroma_refs(ctx, "hmme_predict_chroma_refs_device", refs, n_refs, width, height, fp, wps, d_mv_field, d_ref_field, mv_per_ctu, d_out_cb, d_out_cr,
+                             out_pitch_bytes, stream);
+}
+
+int hmme_predict_chroma_refs_frame(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, int width, int height, const hmme_frame_params* fp,
+                                   const hmme_weight* wps, const int16_t* mv_field, const uint8_t* ref_field, int mv_per_ctu, void* const* outs, int out_stride) {
+  if (!ctx) return HMME_ERR_ARG;
+  const char* who = "hmme_predict_chroma_refs_frame";
+  if (n_refs < 1 || 2 * n_refs > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d reference pictures outside 1..%d", who, n_refs, hmme::kMaxRefs / 2);
+  int rc = chroma_frame_args(ctx, who, fp, refs, 2 * n_refs, !mv_field || !ref_field || !outs || !outs[0] || !outs[1], mv_per_ctu, width, height);
+  for (int r = 0; rc == HMME_OK && wps && r < 2 * n_refs; ++r) {   // before anything is staged
+    char msg[256];
+    rc = other_weight_eval(fp->bit_depth, &wps[r], nullptr, nullptr, msg, sizeof msg);
+    if (rc) return fail(ctx, rc, "%s: plane %d: %s", who, r, msg);
+  }
+  if (rc) return rc;
+  const StagedChroma ch = {hmme_num_ctus(width, height), outs[1]};
+  return chroma_named(ctx, who, predict_staged(ctx, who, refs[0], mv_field, ref_field, mv_per_ctu, outs[0], out_stride, [&](void* d_field, void* d_ref_field, void* d_img, int pitch, hipStream_t s) {
+    return predict_chroma_refs(ctx, who, refs, n_refs, width, height, fp, wps, d_field, d_ref_field, mv_per_ctu, d_img, (uint8_t*)d_img + (size_t)pitch * refs[0]->height, pitch, s);
+  }, 1, &ch));
+}
+
+int hmme_predict_chroma_bi_device(hmme_ctx* ctx, const hmme_plane* const* refs0, const hmme_plane* const* refs1, int n_pics, int width, int height,
+                                  const hmme_frame_params* fp, const hmme_weight* wps0, const hmme_weight* wps1, const void* d_mv_field, const void* d_dir_field,
+                                  int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  return predict_chroma_bi(ctx, "hmme_predict_chroma_bi_device", refs0, refs1, n_pics, width, height, fp, wps0, wps1, d_mv_field, d_dir_field, mv_per_ctu, d_outs,
+                           out_pitch_bytes, stream);
+}
+
+int hmme_predict_chroma_bi_frame(hmme_ctx* ctx, const hmme_plane* const* ref0, const hmme_plane* const* ref1, int width, int height, const hmme_frame_params* fp,
+                                 const hmme_weight* wp0, const hmme_weight* wp1, const int16_t* mv_field, const uint8_t* dir_field, int mv_per_ctu, void* const* outs,
+                                 int out_stride) {
+  if (!ctx) return HMME_ERR_ARG;
+  const char* who = "hmme_predict_chroma_bi_frame";
+  int rc = (wp0 || wp1) ? check_predict_bi_weights(ctx, who, fp, wp0, wp1, 2, nullptr) : HMME_OK;   // before anything is staged
+  if (rc == HMME_OK) rc = chroma_frame_args(ctx, who, fp, ref0, 2, !ref1 || !mv_field || !dir_field || !outs || !outs[0] || !outs[1], mv_per_ctu, width, height);
+  if (rc) return rc;
+  if (!ref1[0] || !ref1[1]) return fail(ctx, HMME_ERR_ARG, "%s: null plane", who);
+  const StagedChroma ch = {hmme_num_ctus(width, height), outs[1]};
+  return chroma_named(ctx, who, predict_staged(ctx, who, ref0[0], mv_field, dir_field, mv_per_ctu, outs[0], out_stride, [&](void* d_field, void* d_dir_field, void* d_img, int pitch, hipStream_t s) {
+    void* d_outs[2] = {d_img, (uint8_t*)d_img + (size_t)pitch * ref0[0]->height};
+    return predict_chroma_bi(ctx, who, ref0, ref1, 1, width, height, fp, wp0, wp1, d_field, d_dir_field, mv_per_ctu, d_outs, pitch, s);
+  }, 2, &ch));
 }
 
 // ---- estimating explicit weighted-prediction parameters ----------------------------------------------------------------------------------------

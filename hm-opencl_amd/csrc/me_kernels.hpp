@@ -2753,6 +2753,152 @@ me_predict_bi_kernel(const uint8_t* __restrict__ ref0, const uint8_t* __restrict
   }
 }
 
+// ---- 4:2:0 chroma motion compensation from the luma motion fields (hmme_predict_chroma_*_device) -------------------------------------------
+// TComPrediction::xPredInterBlk for a chroma component of a 4:2:0 picture (TComPrediction.cpp:669-707): the quarter-pel LUMA MV, clamped like
+// clip_mv_q with the luma picture size and the CTU's luma position, is an eighth-pel chroma MV: integer offset mv >> 3 (arithmetic), phase
+// mv & 7, four taps (m_chromaFilter, TComInterpolationFilter.cpp:65-75).  HM's three branches (horizontal only, vertical only, both through
+// the 14-bit intermediate) are the ONE two-stage formula of me_predict_kernel with phase 0 as the filter {0, 64, 0, 0}.
+// Taps by eighth-pel phase, one dword per phase (tap j = signed byte j): a lane fetches a block's four taps with one LDS read.
+__constant__ uint32_t kChromaTaps[8] = {0x00004000u, 0xFE0A3AFEu, 0xFE1036FCu, 0xFC1C2EFAu, 0xFC2424FCu, 0xFA2E1CFCu, 0xFC3610FEu, 0xFE3A0AFEu};
+
+// One list's two passes for a 16-lane GROUP: the 4x4 block of one component (one 8x8 luma block) at chroma position (x0, y0).  The 7 x 7
+// patch -- rows / columns -1 .. +5 around the displaced block -- goes through LDS (patch: 7 rows of 8), the horizontal pass writes the 14-bit
+// intermediate (mid: 7 rows of 4), and lane l16 = 4 r + c returns the vertical sum of sample (r, c) before any shift, so that the caller ends
+// it as bi = false (rounded) or bi = true (>> 6).  origin, mx, my and live are the same for the 16 lanes of a group (and for the 32 of a
+// luma block's two components, apart from origin); a group that is not live reads nothing and still meets both barriers.
+template <typename SrcT>
+__device__ __forceinline__ int me_predict_chroma_sum(bool live, const uint8_t* origin, int ref_pitch, int x0, int y0, int mx, int my, int16_t* patch,
+                                                     int16_t* mid, int l16, const uint32_t* taps, int sh1, int off1) {
+  if (live) {
+    const uint8_t* src = origin + (long)(y0 + (my >> 3) - 1) * ref_pitch + (long)(x0 + (mx >> 3) - 1) * (long)sizeof(SrcT);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int e = l16 + 16 * k, r = e / 7, c = e - r * 7;
+      if (e < 49) patch[r * 8 + c] = (int16_t)((const SrcT*)(src + (long)r * ref_pitch))[c];
+    }
+  }
+  __syncthreads();
+  if (live) {
+    const uint32_t th = taps[mx & 7];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int o = l16 + 16 * k, r = o >> 2, c = o & 3;
+      if (o < 28) {
+        int sum = 0;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) sum += (int)(int8_t)(th >> (8 * t)) * (int)patch[r * 8 + c + t];
+        mid[o] = (int16_t)((sum + off1) >> sh1);
+      }
+    }
+  }
+  __syncthreads();
+  int sum = 0;
+  if (live) {
+    const uint32_t tv = taps[my & 7];
+    const int r = l16 >> 2, c = l16 & 3;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) sum += (int)(int8_t)(tv >> (8 * t)) * (int)mid[(r + t) * 4 + c];
+  }
+  return sum;
+}
+
+// The three forms of the luma prediction for Cb and Cr in ONE launch: one LUMA CTU (a 32 x 32 chroma area per component) per workgroup.
+// A wave carries two 8x8 luma blocks x two components, a lane one output sample: lane = 32 * (block of the pair) + 16 * component +
+// 4 * row + column, the four waves take the eight blocks of one block row, eight iterations per CTU.  MV, phase, direction and
+// reference index are uniform per 32 lanes, the plane per 16.  PER = mv_per_ctu (1 | 64): with 1 they are the same for the whole workgroup
+// and stay in scalar registers.  Planes and weights come in component pairs (entry 2 i: Cb, 2 i + 1: Cr of picture / reference i), all
+// planes of one pitch; pic_w / pic_h are the LUMA size (even), the fields are indexed by luma CTUs.
+//   FORM 0: me_predict_kernel<SrcT, 0, WP>: one plane pair (hmme_predict_chroma_pairs_device); WP = 1: one MePredWp<1> per component
+//   FORM 1: me_predict_kernel<SrcT, 0, WP, 1>: ref_field uint8 [n_ctu][PER] names the plane pair of `set` (hmme_predict_chroma_refs_device);
+//           WP = 2: the MePredWp<1> of plane 2 * index + component.  An index >= n_refs is not live.
+//   FORM 2: me_predict_bi_kernel<SrcT, WP>: mv_field int16 [2][n_ctu][PER][2], dir_field uint8 [n_ctu][PER], set.base[0..1] list 0, [2..3]
+//           list 1 (hmme_predict_chroma_bi_device); WP = 1: one MePredBiWp<1> per component.  A direction outside 1..3 is not live.
+// The tails are the luma kernels', with the component's own weight.  A block that is not live -- or whose luma block lies wholly outside
+// the picture -- reads no plane and writes nothing, and still meets every barrier.  Stores are samples of the planes' type, only inside the
+// chroma picture.
+struct MeChromaSrc { RefSet set; const uint8_t* field; int n_refs, n_ctu; };   // field: ref_field (FORM 1) / dir_field (FORM 2)
+template <int FORM, int WP> struct MeChromaWp {};
+template <> struct MeChromaWp<0, 1> { MePredWp<1> c[2]; };
+template <> struct MeChromaWp<1, 2> { MePredWp<1> ref[kMaxRefs]; };
+template <> struct MeChromaWp<2, 1> { MePredBiWp<1> c[2]; };
+template <typename SrcT, int FORM, int WP, int PER>
+__global__ void __launch_bounds__(256)
+me_predict_chroma_kernel(MeChromaSrc src, int ref_pitch, const int16_t* __restrict__ mv_field, int ctu_first, int pic_w, int pic_h, int bit_depth,
+                         uint8_t* __restrict__ dst_cb, uint8_t* __restrict__ dst_cr, int dst_pitch, MeChromaWp<FORM, WP> wp) {
+  __shared__ int16_t patch[16][7 * 8];
+  __shared__ int16_t mid[16][7 * 4];
+  __shared__ uint32_t taps[8];
+  const int group = threadIdx.x >> 4, l16 = threadIdx.x & 15, comp = group & 1;
+  if (threadIdx.x < 8) taps[threadIdx.x] = kChromaTaps[threadIdx.x];   // read behind the first barrier of the first pass
+  const int ctus_x = (pic_w + 63) >> 6;
+  const int ctu = ctu_first + blockIdx.x;
+  const int cx = ctu % ctus_x, cy = ctu / ctus_x, cu_x = cx * 64, cu_y = cy * 64;
+  const int head = 14 - bit_depth > 2 ? 14 - bit_depth : 2;   // headRoom (IF_INTERNAL_PREC - bitDepth, at least 2)
+  const int sh1 = 6 - head, off1 = -(8192 << sh1), sh2 = 6 + head, off2 = (1 << (sh2 - 1)) + (8192 << 6);
+  const int shb = head + 1, offb = (1 << (shb - 1)) + 2 * 8192;   // addAvg
+  const int maxv = (1 << bit_depth) - 1;
+  uint8_t* const dst = comp ? dst_cr : dst_cb;
+#pragma unroll 1
+  for (int it = 0; it < 8; ++it) {
+    const int b = it * 8 + (group >> 1), bx = (b & 7) * 8, by = it * 8;   // luma block of the CTU: a block row per iteration
+    const long e = (long)ctu * PER + (PER == 1 ? 0 : b);
+    const bool in_pic = cu_x + bx < pic_w && cu_y + by < pic_h;
+    const int x0 = (cu_x + bx) >> 1, y0 = (cu_y + by) >> 1;
+    bool use0 = in_pic, use1 = false;
+    int sel = 0;   // FORM 1: the reference index
+    if constexpr (FORM == 1) {
+      sel = src.field[e];
+      use0 = use0 && sel < src.n_refs;
+      if (!use0) sel = 0;
+    }
+    if constexpr (FORM == 2) {
+      const int dir = src.field[e];
+      const bool ok = in_pic && dir >= 1 && dir <= 3;
+      use0 = ok && (dir & 1); use1 = ok && (dir & 2);
+    }
+    int mx0 = 0, my0 = 0, mx1 = 0, my1 = 0;
+    if (use0) { mx0 = mv_field[e * 2]; my0 = mv_field[e * 2 + 1]; clip_mv_q(mx0, my0, cu_x, cu_y, pic_w, pic_h); }
+    const int sum0 = me_predict_chroma_sum<SrcT>(use0, src.set.base[2 * sel + comp], ref_pitch, x0, y0, mx0, my0, patch[group], mid[group], l16, taps, sh1, off1);
+    int sum1 = 0;
+    if constexpr (FORM == 2) {
+      if (use1) {
+        const int16_t* mv = mv_field + ((long)src.n_ctu * PER + e) * 2;
+        mx1 = mv[0]; my1 = mv[1];
+        clip_mv_q(mx1, my1, cu_x, cu_y, pic_w, pic_h);
+      }
+      sum1 = me_predict_chroma_sum<SrcT>(use1, src.set.base[2 + comp], ref_pitch, x0, y0, mx1, my1, patch[group], mid[group], l16, taps, sh1, off1);
+    }
+    if (use0 || use1) {
+      int v;
+      if (FORM == 2 && use0 && use1) {
+        if constexpr (FORM == 2 && WP == 1) {
+          const MePredBiWp<1>& w = wp.c[comp];
+          v = (w.w0 * ((int)(int16_t)(sum0 >> 6) + 8192) + w.w1 * ((int)(int16_t)(sum1 >> 6) + 8192) + w.add) >> w.shift;
+        } else {
+          v = ((int)(int16_t)(sum0 >> 6) + (int)(int16_t)(sum1 >> 6) + offb) >> shb;   // HM keeps the intermediates in Pels
+        }
+        v = v < 0 ? 0 : (v > maxv ? maxv : v);
+      } else {
+        const int sum = use0 ? sum0 : sum1;
+        if constexpr (WP != 0) {
+          MePredWp<1> w;
+          if constexpr (FORM == 0) w = wp.c[comp];
+          else if constexpr (FORM == 1) w = wp.ref[2 * sel + comp];
+          else w = wp.c[comp].uni[use0 ? 0 : 1];
+          const int P = (int16_t)(sum >> 6);   // P + 8192 lies within [-24 576, 40 959] whatever the plane holds
+          const long long t = (long long)((w.w0 * (P + 8192) + w.round) >> w.shift) + w.offset;
+          v = t < 0 ? 0 : (t > maxv ? maxv : (int)t);
+        } else {
+          v = (sum + off2) >> sh2;
+          v = v < 0 ? 0 : (v > maxv ? maxv : v);
+        }
+      }
+      const int x = x0 + (l16 & 3), y = y0 + (l16 >> 2);
+      if (x < (pic_w >> 1) && y < (pic_h >> 1)) ((SrcT*)(dst + (long)y * dst_pitch))[x] = (SrcT)v;
+    }
+  }
+}
+
 // ---- estimating explicit weighted-prediction parameters (hmme_plane_stats / hmme_wp_estimate) ---------------------------------------------
 // The whole-picture reductions of HM's WeightPredAnalysis (WeightPredAnalysis.cpp:67-120 xCalcACDCParamSlice, :324-351 xCalcSADvalueWP) over
 // the PICTURE AREA of padded planes -- no margin, no replicated edge.  Geometry shared by both kernels: a workgroup of 256 lanes is

@@ -33,7 +33,9 @@ SYMBOLS = ["hmme_create", "hmme_destroy", "hmme_last_error", "hmme_device_info",
            "hmme_predict_refs_device", "hmme_predict_refs_frame",
            "hmme_select_dirs_check", "hmme_select_dirs_device", "hmme_select_dirs_frame", "hmme_predict_bi_device", "hmme_predict_bi_frame",
            "hmme_predict_bi_weight_check", "hmme_predict_bi_w_device", "hmme_predict_bi_w_frame", "hmme_predict_refs_w_device", "hmme_predict_refs_w_frame",
-           "hmme_plane_stats", "hmme_wp_estimate"]
+           "hmme_plane_stats", "hmme_wp_estimate",
+           "hmme_predict_chroma_pairs_device", "hmme_predict_chroma_frame", "hmme_predict_chroma_refs_device", "hmme_predict_chroma_refs_frame",
+           "hmme_predict_chroma_bi_device", "hmme_predict_chroma_bi_frame"]
 # test / measurement entry points (include/hmme_test.h): not part of the boundary
 TEST_SYMBOLS = ["hmme_test_time_search_kernel", "hmme_test_device_address", "hmme_test_frac_deal", "hmme_test_tail_plan", "hmme_test_time_weight_passes", "hmme_test_time_bipred_origin",
                 "hmme_test_time_wp_estimate_passes"]
@@ -200,6 +202,12 @@ def load():
     L.hmme_predict_bi_w_frame.argtypes = [vp, vp, vp, C.POINTER(FrameParams), pw, pw, vp, vp, i, vp, i]
     L.hmme_predict_refs_w_device.argtypes = [vp, C.POINTER(vp), i, C.POINTER(FrameParams), pw, vp, vp, i, vp, i, vp]
     L.hmme_predict_refs_w_frame.argtypes = [vp, C.POINTER(vp), i, C.POINTER(FrameParams), pw, vp, vp, i, vp, i]
+    L.hmme_predict_chroma_pairs_device.argtypes = [vp, C.POINTER(vp), i, i, i, C.POINTER(FrameParams), pw, vp, i, C.POINTER(vp), i, vp]
+    L.hmme_predict_chroma_frame.argtypes = [vp, C.POINTER(vp), i, i, C.POINTER(FrameParams), pw, vp, i, C.POINTER(vp), i]
+    L.hmme_predict_chroma_refs_device.argtypes = [vp, C.POINTER(vp), i, i, i, C.POINTER(FrameParams), pw, vp, vp, i, vp, vp, i, vp]
+    L.hmme_predict_chroma_refs_frame.argtypes = [vp, C.POINTER(vp), i, i, i, C.POINTER(FrameParams), pw, vp, vp, i, C.POINTER(vp), i]
+    L.hmme_predict_chroma_bi_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, i, i, C.POINTER(FrameParams), pw, pw, vp, vp, i, C.POINTER(vp), i, vp]
+    L.hmme_predict_chroma_bi_frame.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, i, C.POINTER(FrameParams), pw, pw, vp, vp, i, C.POINTER(vp), i]
     L.hmme_plane_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.hmme_wp_estimate.argtypes = [vp, vp, C.POINTER(vp), i, i, C.POINTER(Weight), C.POINTER(WpInfo)]
     L.hmme_test_time_wp_estimate_passes.argtypes = [vp, vp, C.POINTER(vp), i, C.POINTER(Weight), vp, i, C.POINTER(C.c_float), C.POINTER(C.c_float)]
@@ -846,6 +854,90 @@ class Engine:
         self._check(self.L.hmme_predict_refs_w_frame(self.h, _handles(refs), len(refs), C.byref(fp), self._weights(weights), f.ctypes.data, rf.ctypes.data, per,
                                                      out.ctypes.data, out.shape[1]))
         return out
+
+    # ---- 4:2:0 chroma motion compensation from the luma motion fields (include/hmme.h, "4:2:0 chroma motion compensation"): planes, images and
+    # weights come in component pairs (entry 2 i: Cb, 2 i + 1: Cr of picture / reference i); width, height: the LUMA size; weights None: none
+    def _weights_or_none(self, weights, n):
+        if weights is None:
+            return None
+        assert len(weights) == n
+        return self._weights(weights)
+
+    @staticmethod
+    def _ptrs(addresses):
+        return (C.c_void_p * len(addresses))(*[int(a) for a in addresses])
+
+    def _chroma_images(self, plane, outs):
+        """the (Cb, Cr) image pair of the predict_chroma_*_frame methods: `outs`, or zeros when None, each of the CHROMA plane's shape"""
+        outs = (None, None) if outs is None else outs
+        assert len(outs) == 2
+        cb, cr = (self._image(plane, o) for o in outs)
+        return cb, cr, self._ptrs([cb.ctypes.data, cr.ctypes.data])
+
+    def predict_chroma_pairs_device(self, refs, width, height, fp, d_mv_field, mv_per_ctu, d_outs, out_pitch_bytes, weights=None, stream=0):
+        """hmme_predict_chroma_pairs_device: the Cb and Cr prediction of up to 8 pictures from their LUMA motion fields; refs = [cb0, cr0, cb1, ...],
+        d_outs = one device image address per plane, weights = one (w0, offset, shift, round) per plane or None"""
+        assert len(refs) == len(d_outs) and len(refs) % 2 == 0
+        self._check(self.L.hmme_predict_chroma_pairs_device(self.h, _handles(refs), len(refs) // 2, int(width), int(height), C.byref(fp),
+                                                            self._weights_or_none(weights, len(refs)), d_mv_field, int(mv_per_ctu), self._ptrs(d_outs),
+                                                            int(out_pitch_bytes), stream))
+
+    def predict_chroma_frame(self, ref, width, height, mv_field, outs=None, weights=None, ctu_first=0, ctu_count=-1):
+        """hmme_predict_chroma_frame: ref = (cb, cr) planes of (width / 2) x (height / 2) -> (cb, cr) arrays [height / 2, width / 2] of the planes'
+        sample type.  mv_field: the LUMA field, int16[n_ctu, 2] or [n_ctu, 1 | 64, 2] quarter pels; weights: None or one per component"""
+        n = self.L.hmme_num_ctus(int(width), int(height))
+        f, per = self._field(mv_field, n)
+        cb, cr, oa = self._chroma_images(ref[0], outs)
+        fp = FrameParams(1, 0, ref[0].bit_depth, ctu_first, ctu_count)
+        self._check(self.L.hmme_predict_chroma_frame(self.h, _handles(ref), int(width), int(height), C.byref(fp), self._weights_or_none(weights, 2), f.ctypes.data,
+                                                     per, oa, cb.shape[1]))
+        return cb, cr
+
+    def predict_chroma_refs_device(self, refs, width, height, fp, d_mv_field, d_ref_field, mv_per_ctu, d_out_cb, d_out_cr, out_pitch_bytes, weights=None, stream=0):
+        """hmme_predict_chroma_refs_device: the Cb and Cr prediction of one picture, every block from the plane pair of refs = [cb0, cr0, cb1, ...]
+        its reference index names (up to 8 references)"""
+        assert len(refs) % 2 == 0
+        self._check(self.L.hmme_predict_chroma_refs_device(self.h, _handles(refs), len(refs) // 2, int(width), int(height), C.byref(fp),
+                                                           self._weights_or_none(weights, len(refs)), d_mv_field, d_ref_field, int(mv_per_ctu), d_out_cb, d_out_cr,
+                                                           int(out_pitch_bytes), stream))
+
+    def predict_chroma_refs_frame(self, refs, width, height, mv_field, ref_field, outs=None, weights=None, ctu_first=0, ctu_count=-1):
+        """hmme_predict_chroma_refs_frame: predict_refs_frame for Cb and Cr; refs = [cb0, cr0, cb1, cr1, ...] -> (cb, cr)"""
+        assert len(refs) % 2 == 0
+        n = self.L.hmme_num_ctus(int(width), int(height))
+        f, per = self._field(mv_field, n)
+        rf = np.ascontiguousarray(ref_field, dtype=np.uint8).reshape(n, -1)
+        assert rf.shape == (n, per)
+        cb, cr, oa = self._chroma_images(refs[0], outs)
+        fp = FrameParams(1, 0, refs[0].bit_depth, ctu_first, ctu_count)
+        self._check(self.L.hmme_predict_chroma_refs_frame(self.h, _handles(refs), len(refs) // 2, int(width), int(height), C.byref(fp),
+                                                          self._weights_or_none(weights, len(refs)), f.ctypes.data, rf.ctypes.data, per, oa, cb.shape[1]))
+        return cb, cr
+
+    def predict_chroma_bi_device(self, refs0, refs1, width, height, fp, d_mv_field, d_dir_field, mv_per_ctu, d_outs, out_pitch_bytes, weights0=None, weights1=None,
+                                 stream=0):
+        """hmme_predict_chroma_bi_device: the Cb and Cr prediction of up to 4 pictures whose blocks are L0, L1 or bi; refs0 / refs1 = [cb0, cr0, ...] of
+        list 0 / list 1, fields as predict_bi_device takes them, d_outs = one device image address per plane of a list"""
+        assert len(refs0) == len(refs1) == len(d_outs) and len(refs0) % 2 == 0
+        self._check(self.L.hmme_predict_chroma_bi_device(self.h, _handles(refs0), _handles(refs1), len(refs0) // 2, int(width), int(height), C.byref(fp),
+                                                         self._weights_or_none(weights0, len(refs0)), self._weights_or_none(weights1, len(refs1)), d_mv_field,
+                                                         d_dir_field, int(mv_per_ctu), self._ptrs(d_outs), int(out_pitch_bytes), stream))
+
+    def predict_chroma_bi_frame(self, ref0, ref1, width, height, mv_field, dir_field, outs=None, weights0=None, weights1=None, ctu_first=0, ctu_count=-1):
+        """hmme_predict_chroma_bi_frame: predict_bi_frame for Cb and Cr; ref0 / ref1 = (cb, cr) of list 0 / list 1 -> (cb, cr)"""
+        n = self.L.hmme_num_ctus(int(width), int(height))
+        f0, per = self._field(mv_field[0], n)
+        f1, per1 = self._field(mv_field[1], n)
+        assert per == per1
+        f = np.ascontiguousarray(np.stack([f0, f1]))
+        df = np.ascontiguousarray(dir_field, dtype=np.uint8).reshape(n, -1)
+        assert df.shape == (n, per)
+        cb, cr, oa = self._chroma_images(ref0[0], outs)
+        fp = FrameParams(1, 0, ref0[0].bit_depth, ctu_first, ctu_count)
+        self._check(self.L.hmme_predict_chroma_bi_frame(self.h, _handles(ref0), _handles(ref1), int(width), int(height), C.byref(fp),
+                                                        self._weights_or_none(weights0, 2), self._weights_or_none(weights1, 2), f.ctypes.data, df.ctypes.data, per,
+                                                        oa, cb.shape[1]))
+        return cb, cr
 
     # ---- estimating explicit weighted-prediction parameters (include/hmme.h, "estimating explicit weighted-prediction parameters") ----
     def plane_stats(self, plane):

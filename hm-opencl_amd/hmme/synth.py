@@ -5,7 +5,8 @@ full sample range; frame t+1 ("cur") is the same texture translated by a known p
 motion vector plus small seeded noise, so arg-mins are non-trivial and checkable.  Both are
 returned as HM-style padded planes: int16 `Pel` samples, `margin` (=80) edge-replicated
 samples on every side exactly like TComPicYuv (reference TLibCommon/TComPicYuv.cpp:91-92,
-214-262).  Luma only: integer ME never reads chroma.
+214-262).  make_pair is luma only: integer ME never reads chroma; make_chroma_pair derives the 4:2:0 Cb / Cr of
+such a pair for the chroma motion compensation.
 """
 import numpy as np
 
@@ -51,6 +52,36 @@ def make_pair(width, height, seed=1234, bit_depth=8, max_mv=12, region=128, nois
             cur[y0:y1, x0:x1] = base[g + y0 + dy:g + y1 + dy, g + x0 + dx:g + x1 + dx]
     cur = np.clip(np.rint(cur + rng.normal(0.0, noise_sigma * (1 << (bit_depth - 8)), size=cur.shape)), 0, maxv)
     return pad_plane(cur, margin), pad_plane(ref, margin), mv
+
+
+def make_chroma_pair(width, height, true_mv, seed=1234, bit_depth=8, region=128, noise_sigma=1.0, margin=MARGIN, shift=(0, 0)):
+    """The 4:2:0 chroma of a make_pair picture pair -> ((cur_cb, cur_cr), (ref_cb, ref_cr)), padded int16 planes of (height / 2, width / 2)
+    with sample (0, 0) at [margin, margin].  true_mv, region and shift are make_pair's: each component is a texture of its own at LUMA
+    resolution, displaced region by region exactly like the luma picture and then averaged 2 x 2, so the chroma of a region moves by HALF its
+    luma MV -- an eighth-pel chroma MV of 4 * (dx, dy), which is the quarter-pel luma MV read in eighth chroma pels.  Cb and Cr differ."""
+    assert width % 2 == 0 and height % 2 == 0
+    true_mv = np.asarray(true_mv)
+    maxv = (1 << bit_depth) - 1
+    g = int(np.abs(true_mv).max(initial=0)) + 2 + max(abs(shift[0]), abs(shift[1]))
+    down = lambda a: (a[0::2, 0::2] + a[0::2, 1::2] + a[1::2, 0::2] + a[1::2, 1::2]) / 4.0
+    curs, refs = [], []
+    for comp in range(2):
+        rng = np.random.default_rng([seed, 420 + comp])
+        base = _box5(_box5(rng.integers(0, 256, size=(height + 2 * g, width + 2 * g)).astype(np.float64)))
+        lo, hi = base.min(), base.max()
+        base = (base - lo) * (maxv / (hi - lo))
+        moved = np.empty((height, width))
+        for j in range(true_mv.shape[0]):
+            for i in range(true_mv.shape[1]):
+                y0, y1 = j * region, min((j + 1) * region, height)
+                x0, x1 = i * region, min((i + 1) * region, width)
+                dx, dy = int(true_mv[j, i, 0]) + shift[0], int(true_mv[j, i, 1]) + shift[1]
+                moved[y0:y1, x0:x1] = base[g + y0 + dy:g + y1 + dy, g + x0 + dx:g + x1 + dx]
+        cur = down(moved)
+        cur = np.clip(np.rint(cur + rng.normal(0.0, noise_sigma * (1 << (bit_depth - 8)), size=cur.shape)), 0, maxv)
+        curs.append(pad_plane(cur, margin))
+        refs.append(pad_plane(np.clip(np.rint(down(base[g:g + height, g:g + width])), 0, maxv), margin))
+    return tuple(curs), tuple(refs)
 
 
 class Sequence:

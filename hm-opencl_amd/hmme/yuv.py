@@ -1,7 +1,8 @@
 """Frame feeder: planar YUV reader for the luma plane (the step before the ME path; reference
 TLibVideoIO/TVideoIOYuv.cpp:680 `read`, :247 `readPlane`: 8-bit files hold one byte per sample,
 higher bit depths two bytes little-endian; 4:2:0 chroma follows luma and is skipped here because
-integer ME never reads it).  Padding to HM's 80-sample margin is done on the device by
+integer ME never reads it -- read_chroma / LumaFile.chroma fetch it for the chroma motion compensation,
+Engine.predict_chroma_*).  Padding to HM's 80-sample margin is done on the device by
 hmme_plane_upload_* (TComPicYuv::extendPicBorder, TComPicYuv.cpp:214-262)."""
 import numpy as np
 
@@ -22,6 +23,19 @@ def read_luma(path, width, height, frame, file_bit_depth=8, chroma="420"):
     if a.size != width * height:
         raise ValueError(f"{path}: picture {frame} is beyond the end of the file")
     return a.reshape(height, width)
+
+
+def read_chroma(path, width, height, frame, file_bit_depth=8):
+    """-> (cb, cr), each (height / 2, width / 2) uint8 / uint16, of picture `frame` of a planar 4:2:0 file (width, height: the luma size)"""
+    if width % 2 or height % 2:
+        raise ValueError(f"4:2:0 needs an even picture size, not {width} x {height}")
+    bps = 1 if file_bit_depth <= 8 else 2
+    n = (width // 2) * (height // 2)
+    off = frame * frame_bytes(width, height, file_bit_depth, "420") + width * height * bps
+    a = np.fromfile(path, dtype=np.uint8 if bps == 1 else np.dtype("<u2"), count=2 * n, offset=off)
+    if a.size != 2 * n:
+        raise ValueError(f"{path}: picture {frame} is beyond the end of the file")
+    return a[:n].reshape(height // 2, width // 2), a[n:].reshape(height // 2, width // 2)
 
 
 class LumaFile:
@@ -57,6 +71,10 @@ class LumaFile:
         self.read_into(frame, out)
         return out
 
+    def chroma(self, frame):
+        """-> (cb, cr) of picture `frame` of a 4:2:0 file, each (height / 2, width / 2)"""
+        return read_chroma(self.path, self.width, self.height, frame, self.bit_depth)
+
     def close(self):
         import os
         if self.fd is not None:
@@ -71,3 +89,12 @@ def write_luma_420(path, frames):
             y = np.ascontiguousarray(y, dtype=np.uint8)
             f.write(y.tobytes())
             f.write(np.full(y.size // 2, 128, np.uint8).tobytes())
+
+
+def write_420(path, frames, file_bit_depth=8):
+    """write planar 4:2:0 pictures, frames = [(y, cb, cr), ...], one or two (little-endian) bytes per sample: test helper"""
+    dt = np.uint8 if file_bit_depth <= 8 else np.dtype("<u2")
+    with open(path, "wb") as f:
+        for planes in frames:
+            for a in planes:
+                f.write(np.ascontiguousarray(a, dtype=dt).tobytes())

@@ -729,6 +729,69 @@ int hmme_predict_refs_w_device(hmme_ctx* ctx, const hmme_plane* const* refs, int
 int hmme_predict_refs_w_frame(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp, const hmme_weight* wps,
                               const int16_t* mv_field, const uint8_t* ref_field, int mv_per_ctu, void* out, int out_stride);
 
+/* ---- 4:2:0 chroma motion compensation from the luma motion fields ------------------------------------------------
+ * What TComPrediction::motionCompensation (TComPrediction.cpp:527-541) does for Cb and Cr right after the luma block, with the SAME motion
+ * field, reference field and direction field the luma call of the same form takes: the caller of a 4:2:0 picture downloads nothing.  New
+ * entry points only; no struct and no existing entry point changed, so HMME_ABI_VERSION stays 6.  THIS TEXT PLUS THE CITATIONS IS THE RULE
+ * (paths below source/Lib/TLibCommon/).
+ *
+ * Planes.  A chroma component is an ordinary hmme_plane of (width / 2) x (height / 2) samples, width x height being the LUMA size, which
+ * the calls take explicitly (even, at least 16 x 16).  The planes' 128 / 80-sample margins hold every displacement: a clamped MV moves a
+ * chroma block at most 36 samples beyond the picture, the filter adds 2.  Planes, images and weights come in COMPONENT PAIRS: entry 2 i
+ * is Cb of picture / reference i, entry 2 i + 1 is Cr.  Both components are written by one launch.  All planes of a call share one bit
+ * depth (fp->bit_depth) and one context; a launch takes at most 16 planes: 8 pictures (pairs), 8 references (refs), 4 pictures (bi).
+ *
+ * Block rule (TComPrediction.cpp:669-707 xPredInterBlk for a chroma component, ChromaFormat 4:2:0).  One 8x8 luma block is one 4x4 block
+ * per component at half the luma position.  Its quarter-pel luma MV is first clamped like TComDataCU::clipMv with the LUMA picture size and
+ * the CTU's LUMA position -- exactly the clamp of hmme_predict_pairs_device.  The clamped MV, read in eighth chroma pels, gives the integer
+ * offset mv >> 3 (arithmetic: negative MVs floor) and the phases mv & 7.  Taps: m_chromaFilter (TComInterpolationFilter.cpp:65-75), four per
+ * phase.  HM's three branches -- horizontal only when yFrac == 0, vertical only when xFrac == 0, else horizontal over rows -1 .. h + 1 into
+ * the 14-bit intermediate and then vertical -- are ONE two-stage formula with phase 0 as the filter {0, 64, 0, 0}, head = max(2, 14 -
+ * bitDepth):
+ *   first stage           (sum - (8192 << sh1)) >> sh1, sh1 = 6 - head, kept in an int16
+ *   second stage, uni     ClipBD((sum + (1 << (sh2 - 1)) + (8192 << 6)) >> sh2), sh2 = 6 + head
+ *   second stage, bi / WP P = sum >> 6 in an int16
+ * The tails are the luma tails per sample, with the COMPONENT'S OWN {w0, offset, shift}: TComYuv::addAvg for direction 3, addWeightUni in a
+ * slice with weights (hmme_predict_pairs_w_device), addWeightBi for direction 3 with weights (hmme_predict_bi_w_device).
+ *
+ * Fields.  d_mv_field, d_ref_field, d_dir_field, mv_per_ctu (1 | 64) and fp->ctu_first / ctu_count are what the luma call of the same
+ * form takes, indexed by LUMA CTUs: a CTU is a 32 x 32 area of each component.  A block is live if its luma block starts inside the luma
+ * picture and -- refs -- its index is < n_refs, -- bi -- its direction is 1, 2 or 3.  A block that is not live reads no plane and writes
+ * nothing (0xFF and every other sentinel keep the image's samples).  Stores are samples of the planes' type (u8 at 8 bits, else u16), only
+ * inside the chroma picture and inside the CTU range.  d_outs: HOST array of device images, one per plane pair entry, out_pitch_bytes per
+ * row (>= a chroma row).
+ *
+ * Weights are optional: NULL runs the unweighted kernel, and so do identity weights (w0 == 1 << shift, offset 0, whatever round holds).
+ *   pairs   wps: 2 * n_pairs HOST weights (Cb, Cr per picture); each passes the "other weight" line of hmme_bipred_weight_check
+ *   refs    wps: 2 * n_refs HOST weights (Cb, Cr per reference); the same check
+ *   bi      wps0 / wps1: 2 * n_pics HOST weights each (list 0 / list 1; both or neither); each component's pair passes
+ *           hmme_predict_bi_weight_check, so the two lists' shifts are equal WITHIN a component; Cb and Cr may differ from each other
+ *
+ * Refusal.  Nothing is launched and hmme_last_error names the entry:
+ *   an odd luma width or height, or one below 16; a plane whose size is not (width / 2, height / 2)  -> HMME_ERR_ARG
+ *   planes whose bit depth is not fp->bit_depth (so: Cb / Cr or lists of different depth)            -> HMME_ERR_ARG
+ *   planes of another context; more planes than a launch takes; a null argument; mv_per_ctu          -> HMME_ERR_ARG
+ *   a CTU range outside the LUMA picture's CTUs                                                      -> HMME_ERR_ARG
+ *   weights: the codes of hmme_bipred_weight_check / hmme_predict_bi_weight_check, per component
+ *
+ * The _frame forms are synchronous, one picture: host fields, `ref` / `ref0` / `ref1` / `outs` arrays of two entries (Cb, Cr), host images
+ * of the chroma size with out_stride in samples; samples that are not written come back as they were. */
+int hmme_predict_chroma_pairs_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_pairs, int width, int height, const hmme_frame_params* fp,
+                                     const hmme_weight* wps, const void* d_mv_field, int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream);
+int hmme_predict_chroma_frame(hmme_ctx* ctx, const hmme_plane* const* ref, int width, int height, const hmme_frame_params* fp, const hmme_weight* wp,
+                              const int16_t* mv_field, int mv_per_ctu, void* const* outs, int out_stride);
+int hmme_predict_chroma_refs_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, int width, int height, const hmme_frame_params* fp,
+                                    const hmme_weight* wps, const void* d_mv_field, const void* d_ref_field, int mv_per_ctu, void* d_out_cb, void* d_out_cr,
+                                    int out_pitch_bytes, void* stream);
+int hmme_predict_chroma_refs_frame(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, int width, int height, const hmme_frame_params* fp,
+                                   const hmme_weight* wps, const int16_t* mv_field, const uint8_t* ref_field, int mv_per_ctu, void* const* outs, int out_stride);
+int hmme_predict_chroma_bi_device(hmme_ctx* ctx, const hmme_plane* const* refs0, const hmme_plane* const* refs1, int n_pics, int width, int height,
+                                  const hmme_frame_params* fp, const hmme_weight* wps0, const hmme_weight* wps1, const void* d_mv_field, const void* d_dir_field,
+                                  int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream);
+int hmme_predict_chroma_bi_frame(hmme_ctx* ctx, const hmme_plane* const* ref0, const hmme_plane* const* ref1, int width, int height, const hmme_frame_params* fp,
+                                 const hmme_weight* wp0, const hmme_weight* wp1, const int16_t* mv_field, const uint8_t* dir_field, int mv_per_ctu, void* const* outs,
+                                 int out_stride);
+
 /* ---- estimating explicit weighted-prediction parameters --------------------------------------------------------
  * Where the weights of the *_w calls come from when the caller has none: the luma part of HM's estimator, WeightPredAnalysis::
  * xCalcACDCParamSlice, xEstimateWPParamSlice, xUpdatingWPParameters, xSelectWP and xCalcSADvalueWP (source/Lib/TLibEncoder/
