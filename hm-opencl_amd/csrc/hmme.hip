@@ -2016,6 +2016,15 @@ int check_bi_weights(hmme_ctx* ctx, const char* who, const hmme_frame_params* fp
   return HMME_OK;
 }
 
+// The one way a predict launch picks its instantiation: f is called with a value of the planes' sample type (bps 1: uint8_t, 2: uint16_t),
+// and names its kernel with decltype of it.
+extern "C++" {
+template <class F>
+void with_sample_type(int bps, F&& f) {
+  if (bps == 1) f(uint8_t{}); else f(uint16_t{});
+}
+}  // extern "C++"
+
 // me_predict_kernel for CTUs [first, first + count) of `src` with its motion field (int16 [n_ctu][mv_per_ctu][2], device)
 // pw: the weight of a slice with explicit weighted prediction (null: none, and the identity -- WP = 0 computes the same samples)
 // pr: a reference picture per block (hmme_predict_refs_device; `src` gives the geometry all planes share), prw: with one weight per
@@ -2023,22 +2032,21 @@ int check_bi_weights(hmme_ctx* ctx, const char* who, const hmme_frame_params* fp
 int launch_predict(hmme_ctx* ctx, const hmme_plane* src, const int16_t* d_field, int mv_per_ctu, int first, int count, bool origin, const uint8_t* cur_blocks,
                    int bias, uint8_t* dst, long dst_ctu_x, long dst_ctu_y, int dst_pitch, hipStream_t s, const hmme::MePredWp<1>* pw = nullptr,
                    const hmme::MePredRefs<1>* pr = nullptr, const hmme::MePredWp<2>* prw = nullptr) {
-  const dim3 grid((unsigned)count), block(256);
-#define HMME_PREDICT(T, OUT, WP, REFS, wp, refs)                                                                                                \
-  hipLaunchKernelGGL((hmme::me_predict_kernel<T, OUT, WP, REFS>), grid, block, 0, s, src->origin(), src->pitch, d_field, mv_per_ctu, first,    \
-                     src->width, src->height, src->bit_depth, cur_blocks, bias, dst, dst_ctu_x, dst_ctu_y, dst_pitch, wp, refs)
-#define HMME_PREDICT_T(T)                                                                      \
-  do {                                                                                         \
-    if (pr && prw) { HMME_PREDICT(T, 0, 2, 1, *prw, *pr); }                                    \
-    else if (pr) { HMME_PREDICT(T, 0, 0, 1, hmme::MePredWp<0>{}, *pr); }                       \
-    else if (origin && pw) { HMME_PREDICT(T, 1, 1, 0, *pw, hmme::MePredRefs<0>{}); }           \
-    else if (origin) { HMME_PREDICT(T, 1, 0, 0, hmme::MePredWp<0>{}, hmme::MePredRefs<0>{}); } \
-    else if (pw) { HMME_PREDICT(T, 0, 1, 0, *pw, hmme::MePredRefs<0>{}); }                     \
-    else { HMME_PREDICT(T, 0, 0, 0, hmme::MePredWp<0>{}, hmme::MePredRefs<0>{}); }             \
-  } while (0)
-  if (src->bps == 1) HMME_PREDICT_T(uint8_t); else HMME_PREDICT_T(uint16_t);
-#undef HMME_PREDICT_T
-#undef HMME_PREDICT
+  with_sample_type(src->bps, [&](auto sample) {
+    using T = decltype(sample);
+    const auto go = [&](auto kernel, auto wp, auto refs) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)count), dim3(256), 0, s, src->origin(), src->pitch, d_field, mv_per_ctu, first, src->width, src->height,
+                         src->bit_depth, cur_blocks, bias, dst, dst_ctu_x, dst_ctu_y, dst_pitch, wp, refs);
+    };
+    const hmme::MePredWp<0> no_wp;
+    const hmme::MePredRefs<0> no_refs;
+    if (pr && prw) go(hmme::me_predict_kernel<T, 0, 2, 1>, *prw, *pr);
+    else if (pr) go(hmme::me_predict_kernel<T, 0, 0, 1>, no_wp, *pr);
+    else if (origin && pw) go(hmme::me_predict_kernel<T, 1, 1, 0>, *pw, no_refs);
+    else if (origin) go(hmme::me_predict_kernel<T, 1, 0, 0>, no_wp, no_refs);
+    else if (pw) go(hmme::me_predict_kernel<T, 0, 1, 0>, *pw, no_refs);
+    else go(hmme::me_predict_kernel<T, 0, 0, 0>, no_wp, no_refs);
+  });
   HIP_TRY(ctx, hipGetLastError());
   return HMME_OK;
 }
@@ -2080,23 +2088,92 @@ int predict_args(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs, 
   return HMME_OK;
 }
 
-// hmme_predict_pairs_device (wps == null) and hmme_predict_pairs_w_device
-int predict_pairs(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs, int n_pairs, const hmme_frame_params* fp, const hmme_weight* wps,
-                  const void* d_mv_field, int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream) {
-  PredictArgs a;
-  int rc = predict_args(ctx, who, refs, n_pairs, !d_outs, fp, wps, d_mv_field, mv_per_ctu, out_pitch_bytes, &a);
+// ---- one body per prediction form, for luma (comps == 1) and for the Cb / Cr of a 4:2:0 picture (comps == 2, with the LUMA width and height) --
+// With two components planes, weights and images come in (Cb, Cr) pairs; the fields and the CTU range are those of the luma picture, so the
+// planes go through pairs_begin with the whole range (a chroma plane counts its own CTUs) and the luma range is taken from ctu_range.
+struct PredictLaunch {
+  PairLaunch pl;
+  int w = 0, h = 0, n_ctu = 0, first = 0, count = 0;   // luma
+  bool acquired = false;                               // the scratch is: pairs_end is due
+};
+// a refusal of the shared checks names the entry, too
+int named(hmme_ctx* ctx, const char* who, int rc) {
+  if (rc && ctx->err.compare(0, strlen(who), who) != 0) ctx->err = std::string(who) + ": " + ctx->err;
+  return rc;
+}
+// 4:2:0: an even luma size, every plane (none is null) half of it each way
+int chroma_size(hmme_ctx* ctx, const char* who, const hmme_plane* const* planes, int n, int width, int height) {
+  if (width < 16 || height < 16 || (width & 1) || (height & 1)) return fail(ctx, HMME_ERR_ARG, "%s: luma size %d x %d: 4:2:0 needs an even size of at least 16 x 16", who, width, height);
+  for (int r = 0; r < n; ++r)
+    if (planes[r]->width != width / 2 || planes[r]->height != height / 2)
+      return fail(ctx, HMME_ERR_ARG, "%s: plane %d is %d x %d, the chroma of a %d x %d picture is %d x %d", who, r, planes[r]->width, planes[r]->height, width, height, width / 2, height / 2);
+  return HMME_OK;
+}
+// after predict_args (no plane is null): pairs_begin -- every plane of this context, of one size, of fp's bit depth, each ordered like a
+// reference -- and the luma geometry; for two components behind the planes' size against the luma size and the luma CTU range
+int predict_begin(hmme_ctx* ctx, const char* who, const hmme_plane* const* planes, int n, int comps, int width, int height, const hmme_frame_params* fp,
+                  const PredictArgs& a, hipStream_t s, PredictLaunch* L) {
+  hmme_frame_params f = a.f;
+  if (comps == 2) {
+    int rc = chroma_size(ctx, who, planes, n, width, height);
+    if (rc == HMME_OK) rc = named(ctx, who, ctu_range(ctx, fp, hmme_num_ctus(width, height), &L->first, &L->count));
+    if (rc) return rc;
+    f.ctu_first = 0; f.ctu_count = -1;
+  }
+  const int rc = named(ctx, who, pairs_begin(ctx, planes, planes, n, &f, s, &L->pl));
   if (rc) return rc;
-  for (int r = 0; r < n_pairs; ++r)
+  L->acquired = L->pl.count != 0;
+  if (comps == 1) { width = planes[0]->width; height = planes[0]->height; L->first = L->pl.first; L->count = L->pl.count; }
+  L->w = width; L->h = height; L->n_ctu = hmme_num_ctus(width, height);
+  return HMME_OK;
+}
+
+extern "C++" {
+template <int FORM, int WP>
+int launch_chroma(hmme_ctx* ctx, const hmme_plane* p0, const hmme::MeChromaSrc& src, const int16_t* d_field, int mv_per_ctu, const PredictLaunch& cl, void* d_cb, void* d_cr,
+                  int out_pitch_bytes, hipStream_t s, const hmme::MeChromaWp<FORM, WP>& wp) {
+  with_sample_type(p0->bps, [&](auto sample) {
+    using T = decltype(sample);
+    const auto go = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)cl.count), dim3(256), 0, s, src, p0->pitch, d_field, cl.first, cl.w, cl.h, p0->bit_depth, (uint8_t*)d_cb, (uint8_t*)d_cr,
+                         out_pitch_bytes, wp);
+    };
+    if (mv_per_ctu == 1) go(hmme::me_predict_chroma_kernel<T, FORM, WP, 1>); else go(hmme::me_predict_chroma_kernel<T, FORM, WP, 64>);
+  });
+  HIP_TRY(ctx, hipGetLastError());
+  return HMME_OK;
+}
+}  // extern "C++"
+
+// hmme_predict_pairs_device (wps == null), _w_device and hmme_predict_chroma_pairs_device: one launch per picture; WP = 0 without weights and
+// where the picture's are the identity
+int predict_pairs(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs, int n_pairs, int comps, int width, int height, const hmme_frame_params* fp,
+                  const hmme_weight* wps, const void* d_mv_field, int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream) {
+  const int np = comps * n_pairs;
+  PredictArgs a;
+  int rc = predict_args(ctx, who, refs, np, !d_outs, fp, wps, d_mv_field, mv_per_ctu, out_pitch_bytes, &a, comps == 2 ? "plane" : "picture");
+  if (rc) return rc;
+  for (int r = 0; r < np; ++r)
     if (!d_outs[r]) return fail(ctx, HMME_ERR_ARG, "%s: null output image", who);
   hipStream_t s = (hipStream_t)stream;
-  PairLaunch pl;
-  rc = pairs_begin(ctx, refs, refs, n_pairs, &a.f, s, &pl);
-  if (rc || pl.count == 0) return rc;
-  const size_t field = (size_t)refs[0]->n_ctu * mv_per_ctu * 2;
-  for (int r = 0; r < n_pairs && rc == HMME_OK; ++r)
-    rc = launch_predict(ctx, refs[r], (const int16_t*)d_mv_field + field * r, mv_per_ctu, pl.first, pl.count, false, nullptr, 0, (uint8_t*)d_outs[r], 0, 0,
-                        out_pitch_bytes, s, a.identity[r] ? nullptr : &a.pw[r]);
-  return pairs_end(ctx, refs, refs, n_pairs, s, rc);
+  PredictLaunch L;
+  rc = predict_begin(ctx, who, refs, np, comps, width, height, fp, a, s, &L);
+  if (rc || !L.acquired) return rc;
+  const size_t field = (size_t)L.n_ctu * mv_per_ctu * 2;
+  for (int i = 0; i < n_pairs && rc == HMME_OK && L.count; ++i) {
+    const int16_t* f = (const int16_t*)d_mv_field + field * i;
+    if (comps == 1) {
+      rc = launch_predict(ctx, refs[i], f, mv_per_ctu, L.first, L.count, false, nullptr, 0, (uint8_t*)d_outs[i], 0, 0, out_pitch_bytes, s, a.identity[i] ? nullptr : &a.pw[i]);
+      continue;
+    }
+    hmme::MeChromaSrc src = {};
+    src.set.base[0] = refs[2 * i]->origin(); src.set.base[1] = refs[2 * i + 1]->origin();
+    if (a.identity[2 * i] && a.identity[2 * i + 1])
+      rc = launch_chroma<0, 0>(ctx, refs[0], src, f, mv_per_ctu, L, d_outs[2 * i], d_outs[2 * i + 1], out_pitch_bytes, s, hmme::MeChromaWp<0, 0>{});
+    else
+      rc = launch_chroma<0, 1>(ctx, refs[0], src, f, mv_per_ctu, L, d_outs[2 * i], d_outs[2 * i + 1], out_pitch_bytes, s, hmme::MeChromaWp<0, 1>{{a.pw[2 * i], a.pw[2 * i + 1]}});
+  }
+  return pairs_end(ctx, refs, refs, np, s, rc);   // whatever the launches returned: the scratch is acquired
 }
 
 // hmme_predict_frame, _w, hmme_predict_refs_frame and hmme_predict_bi_frame: the motion field (`lists` of them, one behind the other) and,
@@ -2130,19 +2207,50 @@ int predict_staged(hmme_ctx* ctx, const char* who, const hmme_plane* ref, const 
   return HMME_OK;
 }
 
-// hmme_predict_frame (wp == null) and hmme_predict_frame_w
-int predict_frame(hmme_ctx* ctx, const char* who, const hmme_plane* ref, const hmme_frame_params* fp, const hmme_weight* wp, bool weighted, const int16_t* mv_field,
-                  int mv_per_ctu, void* out, int out_stride) {
-  int rc = bi_check(ctx, who, fp, 0);
-  if (rc) return rc;
-  if (weighted) {   // before anything is staged
+// What the _frame forms check before anything is staged.  planes: the n of the call, `comps` per picture; null_arg: one of the caller's other
+// pointers is null.  Chroma also answers here for what a luma call leaves to the launch: the images are staged at the first plane's size and
+// sample type, so its depth and every plane's size against the luma size are looked at first.
+bool frame_null_outs(void* const* outs, int comps) { return !outs || !outs[0] || (comps == 2 && !outs[1]); }
+int frame_args(hmme_ctx* ctx, const char* who, const hmme_frame_params* fp, const hmme_plane* const* planes, int n, int comps, bool null_arg, int mv_per_ctu, int width,
+               int height) {
+  if (!planes || null_arg || (mv_per_ctu != 1 && mv_per_ctu != 64)) return fail(ctx, HMME_ERR_ARG, "%s: null argument, or %d MVs per CTU (1 or 64)", who, mv_per_ctu);
+  for (int r = 0; r < n; ++r)
+    if (!planes[r]) return fail(ctx, HMME_ERR_ARG, "%s: null plane", who);
+  if (comps == 1) return HMME_OK;
+  if (planes[0]->bit_depth != fp->bit_depth) return fail(ctx, HMME_ERR_ARG, "%s: planes hold %d-bit samples, the call asks for %d", who, planes[0]->bit_depth, fp->bit_depth);
+  return chroma_size(ctx, who, planes, n, width, height);
+}
+// frame_args and the n weights (null: none) of the uni-directional forms.  A luma call answers for a weight before its arguments, a chroma
+// call behind them: what each did when it was written, and what tests/test_gpu_predict_refusal_order.py pins.
+int frame_checks(hmme_ctx* ctx, const char* who, const hmme_frame_params* fp, const hmme_plane* const* planes, int n, int comps, bool null_arg, int mv_per_ctu, int width,
+                 int height, const hmme_weight* wps, const char* unit) {
+  int rc = comps == 2 ? frame_args(ctx, who, fp, planes, n, comps, null_arg, mv_per_ctu, width, height) : HMME_OK;
+  for (int r = 0; rc == HMME_OK && wps && r < n; ++r) {
     char msg[256];
-    rc = other_weight_eval(fp->bit_depth, wp, nullptr, nullptr, msg, sizeof msg);
-    if (rc) return fail(ctx, rc, "%s: %s", who, msg);
+    rc = other_weight_eval(fp->bit_depth, &wps[r], nullptr, nullptr, msg, sizeof msg);
+    if (rc) return fail(ctx, rc, "%s: %s %d: %s", who, unit, r, msg);
   }
-  if (!ref || !mv_field || !out || (mv_per_ctu != 1 && mv_per_ctu != 64)) return fail(ctx, HMME_ERR_ARG, "%s: null argument, or %d MVs per CTU (1 or 64)", who, mv_per_ctu);
-  return predict_staged(ctx, who, ref, mv_field, nullptr, mv_per_ctu, out, out_stride, [&](void* d_field, void*, void* d_img, int pitch, hipStream_t s) {
-    return predict_pairs(ctx, who, &ref, 1, fp, weighted ? wp : nullptr, d_field, mv_per_ctu, &d_img, pitch, s);
+  if (rc == HMME_OK && comps == 1) rc = frame_args(ctx, who, fp, planes, n, comps, null_arg, mv_per_ctu, width, height);
+  return rc;
+}
+// predict_staged for the `comps` images of a call: launch gets their device addresses
+int frame_staged(hmme_ctx* ctx, const char* who, const hmme_plane* p0, int comps, int width, int height, const int16_t* mv_field, const uint8_t* block_field, int mv_per_ctu,
+                 void* const* outs, int out_stride, int lists, const std::function<int(void*, void*, void* const*, int, hipStream_t)>& launch) {
+  const StagedChroma ch = {comps == 2 ? hmme_num_ctus(width, height) : 0, comps == 2 ? outs[1] : nullptr};
+  return named(ctx, who, predict_staged(ctx, who, p0, mv_field, block_field, mv_per_ctu, outs[0], out_stride, [&](void* d_field, void* d_block_field, void* d_img, int pitch, hipStream_t s) {
+    void* d_outs[2] = {d_img, (uint8_t*)d_img + (size_t)pitch * p0->height};
+    return launch(d_field, d_block_field, d_outs, pitch, s);
+  }, lists, comps == 2 ? &ch : nullptr));
+}
+
+// hmme_predict_frame (wps == null), hmme_predict_frame_w and hmme_predict_chroma_frame; refs / wps / outs: `comps` entries
+int predict_frame(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs, int comps, int width, int height, const hmme_frame_params* fp, const hmme_weight* wps,
+                  const int16_t* mv_field, int mv_per_ctu, void* const* outs, int out_stride) {
+  int rc = bi_check(ctx, who, fp, 0);
+  if (rc == HMME_OK) rc = frame_checks(ctx, who, fp, refs, comps, comps, !mv_field || frame_null_outs(outs, comps), mv_per_ctu, width, height, wps, comps == 2 ? "plane" : "picture");
+  if (rc) return rc;
+  return frame_staged(ctx, who, refs[0], comps, width, height, mv_field, nullptr, mv_per_ctu, outs, out_stride, 1, [&](void* d_field, void*, void* const* d_outs, int pitch, hipStream_t s) {
+    return predict_pairs(ctx, who, refs, 1, comps, width, height, fp, wps, d_field, mv_per_ctu, d_outs, pitch, s);
   });
 }
 }  // namespace
@@ -2150,26 +2258,27 @@ int predict_frame(hmme_ctx* ctx, const char* who, const hmme_plane* ref, const h
 int hmme_predict_pairs_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_pairs, const hmme_frame_params* fp, const void* d_mv_field,
                               int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream) {
   if (!ctx) return HMME_ERR_ARG;
-  return predict_pairs(ctx, "hmme_predict_pairs_device", refs, n_pairs, fp, nullptr, d_mv_field, mv_per_ctu, d_outs, out_pitch_bytes, stream);
+  return predict_pairs(ctx, "hmme_predict_pairs_device", refs, n_pairs, 1, 0, 0, fp, nullptr, d_mv_field, mv_per_ctu, d_outs, out_pitch_bytes, stream);
 }
 
 int hmme_predict_pairs_w_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_pairs, const hmme_frame_params* fp, const hmme_weight* wps,
                                 const void* d_mv_field, int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream) {
   if (!ctx) return HMME_ERR_ARG;
   if (!wps) return fail(ctx, HMME_ERR_ARG, "hmme_predict_pairs_w_device: null weights");
-  return predict_pairs(ctx, "hmme_predict_pairs_w_device", refs, n_pairs, fp, wps, d_mv_field, mv_per_ctu, d_outs, out_pitch_bytes, stream);
+  return predict_pairs(ctx, "hmme_predict_pairs_w_device", refs, n_pairs, 1, 0, 0, fp, wps, d_mv_field, mv_per_ctu, d_outs, out_pitch_bytes, stream);
 }
 
 int hmme_predict_frame(hmme_ctx* ctx, const hmme_plane* ref, const hmme_frame_params* fp, const int16_t* mv_field, int mv_per_ctu, void* out,
                        int out_stride) {
   if (!ctx) return HMME_ERR_ARG;
-  return predict_frame(ctx, "hmme_predict_frame", ref, fp, nullptr, false, mv_field, mv_per_ctu, out, out_stride);
+  return predict_frame(ctx, "hmme_predict_frame", &ref, 1, 0, 0, fp, nullptr, mv_field, mv_per_ctu, &out, out_stride);
 }
 
 int hmme_predict_frame_w(hmme_ctx* ctx, const hmme_plane* ref, const hmme_frame_params* fp, const hmme_weight* wp, const int16_t* mv_field,
                          int mv_per_ctu, void* out, int out_stride) {
   if (!ctx) return HMME_ERR_ARG;
-  return predict_frame(ctx, "hmme_predict_frame_w", ref, fp, wp, true, mv_field, mv_per_ctu, out, out_stride);
+  if (!wp) return fail(ctx, HMME_ERR_ARG, "hmme_predict_frame_w: null weight");
+  return predict_frame(ctx, "hmme_predict_frame_w", &ref, 1, 0, 0, fp, wp, mv_field, mv_per_ctu, &out, out_stride);
 }
 
 namespace {
@@ -2590,45 +2699,54 @@ int hmme_select_refs_frame(hmme_ctx* ctx, int width, int height, int n_refs, con
 }
 
 namespace {
-// hmme_predict_refs_device (wps == null) and hmme_predict_refs_w_device: one launch of me_predict_kernel<SrcT, 0, WP, 1>, every block from
-// the plane its reference index names.  WP = 0 without weights and where every weight is the identity, else 2: every block through
-// addWeightUni with its plane's weight (for an identity weight that is the unweighted sample: nested floors)
-int predict_refs(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp, const hmme_weight* wps,
-                 const void* d_mv_field, const void* d_ref_field, int mv_per_ctu, void* d_out, int out_pitch_bytes, void* stream) {
+// hmme_predict_refs_device (wps == null), _w_device and hmme_predict_chroma_refs_device: ONE launch, every block from the plane (pair) its
+// reference index names.  WP = 0 without weights and where every weight is the identity, else 2: every block through addWeightUni with its
+// plane's weight (for an identity weight that is the unweighted sample: nested floors).  d_out_cr: the second image of comps == 2
+int predict_refs(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs, int n_refs, int comps, int width, int height, const hmme_frame_params* fp,
+                 const hmme_weight* wps, const void* d_mv_field, const void* d_ref_field, int mv_per_ctu, void* d_out, void* d_out_cr, int out_pitch_bytes, void* stream) {
+  const int np = comps * n_refs;
   PredictArgs a;
-  int rc = predict_args(ctx, who, refs, n_refs, !d_ref_field || !d_out, fp, wps, d_mv_field, mv_per_ctu, out_pitch_bytes, &a, "reference");
+  int rc = predict_args(ctx, who, refs, np, !d_ref_field || !d_out || (comps == 2 && !d_out_cr), fp, wps, d_mv_field, mv_per_ctu, out_pitch_bytes, &a,
+                        comps == 2 ? "plane" : "reference");
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
-  PairLaunch pl;   // checks every plane: of this context, of one size, of fp's bit depth; each is ordered like a reference
-  rc = pairs_begin(ctx, refs, refs, n_refs, &a.f, s, &pl);
-  if (rc || pl.count == 0) return rc;
-  const hmme::MePredRefs<1> pr = {pl.refs, (const uint8_t*)d_ref_field, n_refs};
-  hmme::MePredWp<2> prw = {};
-  bool weighted = false;
-  for (int r = 0; r < n_refs; ++r) {
-    weighted = weighted || !a.identity[r];
-    if (wps) prw.ref[r] = a.pw[r];
+  PredictLaunch L;
+  rc = predict_begin(ctx, who, refs, np, comps, width, height, fp, a, s, &L);
+  if (rc || !L.acquired) return rc;
+  if (L.count) {
+    hmme::MePredWp<2> prw = {};
+    hmme::MeChromaWp<1, 2> cprw = {};
+    bool weighted = false;
+    for (int r = 0; r < np; ++r) {
+      weighted = weighted || !a.identity[r];
+      if (wps) prw.ref[r] = cprw.ref[r] = a.pw[r];
+    }
+    if (comps == 1) {
+      const hmme::MePredRefs<1> pr = {L.pl.refs, (const uint8_t*)d_ref_field, n_refs};
+      rc = launch_predict(ctx, refs[0], (const int16_t*)d_mv_field, mv_per_ctu, L.first, L.count, false, nullptr, 0, (uint8_t*)d_out, 0, 0, out_pitch_bytes, s, nullptr, &pr,
+                          weighted ? &prw : nullptr);
+    } else {
+      const hmme::MeChromaSrc src = {L.pl.refs, (const uint8_t*)d_ref_field, n_refs, L.n_ctu};
+      if (weighted) rc = launch_chroma<1, 2>(ctx, refs[0], src, (const int16_t*)d_mv_field, mv_per_ctu, L, d_out, d_out_cr, out_pitch_bytes, s, cprw);
+      else rc = launch_chroma<1, 0>(ctx, refs[0], src, (const int16_t*)d_mv_field, mv_per_ctu, L, d_out, d_out_cr, out_pitch_bytes, s, hmme::MeChromaWp<1, 0>{});
+    }
   }
-  rc = launch_predict(ctx, refs[0], (const int16_t*)d_mv_field, mv_per_ctu, pl.first, pl.count, false, nullptr, 0, (uint8_t*)d_out, 0, 0, out_pitch_bytes, s, nullptr, &pr,
-                      weighted ? &prw : nullptr);
-  return pairs_end(ctx, refs, refs, n_refs, s, rc);   // whatever the launch returned: the scratch is acquired
+  return pairs_end(ctx, refs, refs, np, s, rc);   // whatever the launch returned: the scratch is acquired
 }
 
-// hmme_predict_refs_frame (wps == null) and hmme_predict_refs_w_frame
-int predict_refs_frame(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp, const hmme_weight* wps,
-                       const int16_t* mv_field, const uint8_t* ref_field, int mv_per_ctu, void* out, int out_stride) {
+// hmme_predict_refs_frame (wps == null), _w_frame and hmme_predict_chroma_refs_frame
+int predict_refs_frame(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs, int n_refs, int comps, int width, int height, const hmme_frame_params* fp,
+                       const hmme_weight* wps, const int16_t* mv_field, const uint8_t* ref_field, int mv_per_ctu, void* const* outs, int out_stride) {
   int rc = bi_check(ctx, who, fp, 0);
   if (rc) return rc;
-  if (!refs || n_refs < 1 || n_refs > hmme::kMaxRefs || !refs[0]) return fail(ctx, HMME_ERR_ARG, "%s: %d reference pictures outside 1..%d (or a null plane)", who, n_refs, hmme::kMaxRefs);
-  for (int r = 0; wps && r < n_refs; ++r) {   // before anything is staged
-    char msg[256];
-    rc = other_weight_eval(fp->bit_depth, &wps[r], nullptr, nullptr, msg, sizeof msg);
-    if (rc) return fail(ctx, rc, "%s: reference %d: %s", who, r, msg);
-  }
-  if (!mv_field || !ref_field || !out || (mv_per_ctu != 1 && mv_per_ctu != 64)) return fail(ctx, HMME_ERR_ARG, "%s: null argument, or %d MVs per CTU (1 or 64)", who, mv_per_ctu);
+  if (!refs || n_refs < 1 || comps * n_refs > hmme::kMaxRefs || !refs[0])
+    return fail(ctx, HMME_ERR_ARG, "%s: %d reference pictures outside 1..%d (or a null plane)", who, n_refs, hmme::kMaxRefs / comps);
+  rc = frame_checks(ctx, who, fp, refs, comps * n_refs, comps, !mv_field || !ref_field || frame_null_outs(outs, comps), mv_per_ctu, width, height, wps,
+                    comps == 2 ? "plane" : "reference");
+  if (rc) return rc;
   // blocks without a reference, too, come back as they were
-  return predict_staged(ctx, who, refs[0], mv_field, ref_field, mv_per_ctu, out, out_stride, [&](void* d_field, void* d_ref_field, void* d_img, int pitch, hipStream_t s) {
-    return predict_refs(ctx, who, refs, n_refs, fp, wps, d_field, d_ref_field, mv_per_ctu, d_img, pitch, s);
+  return frame_staged(ctx, who, refs[0], comps, width, height, mv_field, ref_field, mv_per_ctu, outs, out_stride, 1, [&](void* d_field, void* d_ref_field, void* const* d_outs, int pitch, hipStream_t s) {
+    return predict_refs(ctx, who, refs, n_refs, comps, width, height, fp, wps, d_field, d_ref_field, mv_per_ctu, d_outs[0], comps == 2 ? d_outs[1] : nullptr, pitch, s);
   });
 }
 }  // namespace
@@ -2636,27 +2754,27 @@ int predict_refs_frame(hmme_ctx* ctx, const char* who, const hmme_plane* const* 
 int hmme_predict_refs_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp, const void* d_mv_field,
                              const void* d_ref_field, int mv_per_ctu, void* d_out, int out_pitch_bytes, void* stream) {
   if (!ctx) return HMME_ERR_ARG;
-  return predict_refs(ctx, "hmme_predict_refs_device", refs, n_refs, fp, nullptr, d_mv_field, d_ref_field, mv_per_ctu, d_out, out_pitch_bytes, stream);
+  return predict_refs(ctx, "hmme_predict_refs_device", refs, n_refs, 1, 0, 0, fp, nullptr, d_mv_field, d_ref_field, mv_per_ctu, d_out, nullptr, out_pitch_bytes, stream);
 }
 
 int hmme_predict_refs_w_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp, const hmme_weight* wps,
                                const void* d_mv_field, const void* d_ref_field, int mv_per_ctu, void* d_out, int out_pitch_bytes, void* stream) {
   if (!ctx) return HMME_ERR_ARG;
   if (!wps) return fail(ctx, HMME_ERR_ARG, "hmme_predict_refs_w_device: null weights");
-  return predict_refs(ctx, "hmme_predict_refs_w_device", refs, n_refs, fp, wps, d_mv_field, d_ref_field, mv_per_ctu, d_out, out_pitch_bytes, stream);
+  return predict_refs(ctx, "hmme_predict_refs_w_device", refs, n_refs, 1, 0, 0, fp, wps, d_mv_field, d_ref_field, mv_per_ctu, d_out, nullptr, out_pitch_bytes, stream);
 }
 
 int hmme_predict_refs_frame(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp, const int16_t* mv_field,
                             const uint8_t* ref_field, int mv_per_ctu, void* out, int out_stride) {
   if (!ctx) return HMME_ERR_ARG;
-  return predict_refs_frame(ctx, "hmme_predict_refs_frame", refs, n_refs, fp, nullptr, mv_field, ref_field, mv_per_ctu, out, out_stride);
+  return predict_refs_frame(ctx, "hmme_predict_refs_frame", refs, n_refs, 1, 0, 0, fp, nullptr, mv_field, ref_field, mv_per_ctu, &out, out_stride);
 }
 
 int hmme_predict_refs_w_frame(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp, const hmme_weight* wps,
                               const int16_t* mv_field, const uint8_t* ref_field, int mv_per_ctu, void* out, int out_stride) {
   if (!ctx) return HMME_ERR_ARG;
   if (!wps) return fail(ctx, HMME_ERR_ARG, "hmme_predict_refs_w_frame: null weights");
-  return predict_refs_frame(ctx, "hmme_predict_refs_w_frame", refs, n_refs, fp, wps, mv_field, ref_field, mv_per_ctu, out, out_stride);
+  return predict_refs_frame(ctx, "hmme_predict_refs_w_frame", refs, n_refs, 1, 0, 0, fp, wps, mv_field, ref_field, mv_per_ctu, &out, out_stride);
 }
 
 // ---- L0, L1 or bi per PU: the decision over the four table sets of a B picture, and the prediction that follows it ---------------------------
@@ -2742,57 +2860,72 @@ int check_predict_bi_weights(hmme_ctx* ctx, const char* who, const hmme_frame_pa
   return HMME_OK;
 }
 
-// hmme_predict_bi_device (weighted == false) and hmme_predict_bi_w_device: one launch of me_predict_bi_kernel per picture, every block from
-// the planes its direction names; WP = 0 for a picture without weights or with two identities, else 1
-int predict_bi(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs0, const hmme_plane* const* refs1, int n_pics, const hmme_frame_params* fp,
-               const hmme_weight* wps0, const hmme_weight* wps1, bool weighted, const void* d_mv_field, const void* d_dir_field, int mv_per_ctu, void* const* d_outs,
-               int out_pitch_bytes, void* stream) {
-  if (!refs0 || !refs1 || n_pics < 1 || 2 * n_pics > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d pictures outside 1..%d (or a null plane list)", who, n_pics, hmme::kMaxRefs / 2);
-  PredBiWp bw[hmme::kMaxRefs / 2];
-  int rc = weighted ? check_predict_bi_weights(ctx, who, fp, wps0, wps1, n_pics, bw) : HMME_OK;
+// hmme_predict_bi_device, _w_device and hmme_predict_chroma_bi_device: one launch per picture, every block from the planes its direction names.
+// weighted: two weights per picture and component, each pair through predict_bi_weight_eval; WP = 0 for a picture without weights or with
+// identities only, else 1.  Plane lists, weights and images hold `comps` entries per picture.
+int predict_bi(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs0, const hmme_plane* const* refs1, int n_pics, int comps, int width, int height,
+               const hmme_frame_params* fp, const hmme_weight* wps0, const hmme_weight* wps1, bool weighted, const void* d_mv_field, const void* d_dir_field,
+               int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream) {
+  const int per_pic = 2 * comps, max_pics = hmme::kMaxRefs / per_pic;
+  if (!refs0 || !refs1 || n_pics < 1 || n_pics > max_pics) return fail(ctx, HMME_ERR_ARG, "%s: %d pictures outside 1..%d (or a null plane list)", who, n_pics, max_pics);
+  PredBiWp bw[hmme::kMaxRefs / 2];   // entry comps * i + c: component c of picture i
+  int rc = weighted ? check_predict_bi_weights(ctx, who, fp, wps0, wps1, comps * n_pics, bw) : HMME_OK;
   if (rc) return rc;
-  const hmme_plane* planes[hmme::kMaxRefs];   // picture i: planes[2 i] (list 0), planes[2 i + 1] (list 1)
-  for (int i = 0; i < n_pics; ++i) { planes[2 * i] = refs0[i]; planes[2 * i + 1] = refs1[i]; }
-  PredictArgs a;
-  rc = predict_args(ctx, who, planes, 2 * n_pics, !d_dir_field || !d_outs, fp, nullptr, d_mv_field, mv_per_ctu, out_pitch_bytes, &a);
-  if (rc) return rc;
+  const hmme_plane* planes[hmme::kMaxRefs];   // picture i: its list 0 planes, then its list 1 planes
   for (int i = 0; i < n_pics; ++i)
-    if (!d_outs[i]) return fail(ctx, HMME_ERR_ARG, "%s: null output image", who);
+    for (int c = 0; c < comps; ++c) { planes[per_pic * i + c] = refs0[comps * i + c]; planes[per_pic * i + comps + c] = refs1[comps * i + c]; }
+  PredictArgs a;
+  rc = predict_args(ctx, who, planes, per_pic * n_pics, !d_dir_field || !d_outs, fp, nullptr, d_mv_field, mv_per_ctu, out_pitch_bytes, &a, comps == 2 ? "plane" : "picture");
+  if (rc) return rc;
+  for (int r = 0; r < comps * n_pics; ++r)
+    if (!d_outs[r]) return fail(ctx, HMME_ERR_ARG, "%s: null output image", who);
   hipStream_t s = (hipStream_t)stream;
-  PairLaunch pl;   // checks every plane: of this context, of one size, of fp's bit depth; each is ordered like a reference
-  rc = pairs_begin(ctx, planes, planes, 2 * n_pics, &a.f, s, &pl);
-  if (rc || pl.count == 0) return rc;
+  PredictLaunch L;
+  rc = predict_begin(ctx, who, planes, per_pic * n_pics, comps, width, height, fp, a, s, &L);
+  if (rc || !L.acquired) return rc;
   const hmme_plane* p0 = planes[0];
-  const size_t blocks = (size_t)p0->n_ctu * mv_per_ctu;
-  for (int i = 0; i < n_pics; ++i) {
+  const size_t blocks = (size_t)L.n_ctu * mv_per_ctu;
+  for (int i = 0; i < n_pics && rc == HMME_OK && L.count; ++i) {
     const int16_t* field = (const int16_t*)d_mv_field + blocks * 4 * i;
     const uint8_t* dirs = (const uint8_t*)d_dir_field + blocks * i;
-#define HMME_PREDICT_BI(T, WP, wp)                                                                                                                       \
-  hipLaunchKernelGGL((hmme::me_predict_bi_kernel<T, WP>), dim3((unsigned)pl.count), dim3(256), 0, s, planes[2 * i]->origin(), planes[2 * i + 1]->origin(), \
-                     p0->pitch, field, dirs, mv_per_ctu, p0->n_ctu, pl.first, p0->width, p0->height, p0->bit_depth, (uint8_t*)d_outs[i], out_pitch_bytes, wp)
-    if (bw[i].identity) {
-      if (p0->bps == 1) HMME_PREDICT_BI(uint8_t, 0, hmme::MePredBiWp<0>{}); else HMME_PREDICT_BI(uint16_t, 0, hmme::MePredBiWp<0>{});
-    } else {
-      if (p0->bps == 1) HMME_PREDICT_BI(uint8_t, 1, bw[i].k); else HMME_PREDICT_BI(uint16_t, 1, bw[i].k);
+    if (comps == 2) {
+      hmme::MeChromaSrc src = {};
+      for (int k = 0; k < 4; ++k) src.set.base[k] = planes[4 * i + k]->origin();
+      src.field = dirs;
+      src.n_ctu = L.n_ctu;
+      if (bw[2 * i].identity && bw[2 * i + 1].identity)
+        rc = launch_chroma<2, 0>(ctx, p0, src, field, mv_per_ctu, L, d_outs[2 * i], d_outs[2 * i + 1], out_pitch_bytes, s, hmme::MeChromaWp<2, 0>{});
+      else
+        rc = launch_chroma<2, 1>(ctx, p0, src, field, mv_per_ctu, L, d_outs[2 * i], d_outs[2 * i + 1], out_pitch_bytes, s, hmme::MeChromaWp<2, 1>{{bw[2 * i].k, bw[2 * i + 1].k}});
+      continue;
     }
-#undef HMME_PREDICT_BI
+    with_sample_type(p0->bps, [&](auto sample) {
+      using T = decltype(sample);
+      const auto go = [&](auto kernel, auto wp) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)L.count), dim3(256), 0, s, planes[2 * i]->origin(), planes[2 * i + 1]->origin(), p0->pitch, field, dirs, mv_per_ctu,
+                           L.n_ctu, L.first, L.w, L.h, p0->bit_depth, (uint8_t*)d_outs[i], out_pitch_bytes, wp);
+      };
+      if (bw[i].identity) go(hmme::me_predict_bi_kernel<T, 0>, hmme::MePredBiWp<0>{}); else go(hmme::me_predict_bi_kernel<T, 1>, bw[i].k);
+    });
+    if (hipGetLastError() != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "%s: launch failed", who);
   }
-  rc = hipGetLastError() == hipSuccess ? HMME_OK : fail(ctx, HMME_ERR_DEVICE, "%s: launch failed", who);
-  return pairs_end(ctx, planes, planes, 2 * n_pics, s, rc);   // whatever the launches returned: the scratch is acquired
+  return pairs_end(ctx, planes, planes, per_pic * n_pics, s, rc);   // whatever the launches returned: the scratch is acquired
 }
 
-// hmme_predict_bi_frame (weighted == false) and hmme_predict_bi_w_frame
-int predict_bi_frame(hmme_ctx* ctx, const char* who, const hmme_plane* ref0, const hmme_plane* ref1, const hmme_frame_params* fp, const hmme_weight* wp0,
-                     const hmme_weight* wp1, bool weighted, const int16_t* mv_field, const uint8_t* dir_field, int mv_per_ctu, void* out, int out_stride) {
-  int rc = weighted ? check_predict_bi_weights(ctx, who, fp, wp0, wp1, 1, nullptr) : HMME_OK;   // before anything is staged
+// hmme_predict_bi_frame, _w_frame and hmme_predict_chroma_bi_frame; ref0 / ref1 / outs: `comps` entries each.  The weights answer first.
+int predict_bi_frame(hmme_ctx* ctx, const char* who, const hmme_plane* const* ref0, const hmme_plane* const* ref1, int comps, int width, int height,
+                     const hmme_frame_params* fp, const hmme_weight* wp0, const hmme_weight* wp1, bool weighted, const int16_t* mv_field, const uint8_t* dir_field,
+                     int mv_per_ctu, void* const* outs, int out_stride) {
+  int rc = weighted ? check_predict_bi_weights(ctx, who, fp, wp0, wp1, comps, nullptr) : HMME_OK;   // before anything is staged
   if (rc == HMME_OK) rc = bi_check(ctx, who, fp, 0);
+  if (rc == HMME_OK) rc = frame_args(ctx, who, fp, ref0, comps, comps, !ref1 || !mv_field || !dir_field || frame_null_outs(outs, comps), mv_per_ctu, width, height);
+  for (int c = 0; rc == HMME_OK && c < comps; ++c)
+    if (!ref1[c]) rc = fail(ctx, HMME_ERR_ARG, "%s: null plane", who);
   if (rc) return rc;
-  if (!ref0 || !ref1 || !mv_field || !dir_field || !out || (mv_per_ctu != 1 && mv_per_ctu != 64))
-    return fail(ctx, HMME_ERR_ARG, "%s: null argument, or %d MVs per CTU (1 or 64)", who, mv_per_ctu);
   // blocks without a direction, too, come back as they were
-  return predict_staged(ctx, who, ref0, mv_field, dir_field, mv_per_ctu, out, out_stride, [&](void* d_field, void* d_dir_field, void* d_img, int pitch, hipStream_t s) {
-    return predict_bi(ctx, who, &ref0, &ref1, 1, fp, wp0, wp1, weighted, d_field, d_dir_field, mv_per_ctu, &d_img, pitch, s);
-  }, 2);
+  return frame_staged(ctx, who, ref0[0], comps, width, height, mv_field, dir_field, mv_per_ctu, outs, out_stride, 2, [&](void* d_field, void* d_dir_field, void* const* d_outs, int pitch, hipStream_t s) {
+    return predict_bi(ctx, who, ref0, ref1, 1, comps, width, height, fp, wp0, wp1, weighted, d_field, d_dir_field, mv_per_ctu, d_outs, pitch, s);
+  });
 }
 }  // namespace
 
@@ -2804,251 +2937,72 @@ int hmme_predict_bi_weight_check(int bit_depth, const hmme_weight* wp0, const hm
 int hmme_predict_bi_device(hmme_ctx* ctx, const hmme_plane* const* refs0, const hmme_plane* const* refs1, int n_pics, const hmme_frame_params* fp,
                            const void* d_mv_field, const void* d_dir_field, int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream) {
   if (!ctx) return HMME_ERR_ARG;
-  return predict_bi(ctx, "hmme_predict_bi_device", refs0, refs1, n_pics, fp, nullptr, nullptr, false, d_mv_field, d_dir_field, mv_per_ctu, d_outs, out_pitch_bytes, stream);
+  return predict_bi(ctx, "hmme_predict_bi_device", refs0, refs1, n_pics, 1, 0, 0, fp, nullptr, nullptr, false, d_mv_field, d_dir_field, mv_per_ctu, d_outs,
+                    out_pitch_bytes, stream);
 }
 
 int hmme_predict_bi_w_device(hmme_ctx* ctx, const hmme_plane* const* refs0, const hmme_plane* const* refs1, int n_pics, const hmme_frame_params* fp,
                              const hmme_weight* wps0, const hmme_weight* wps1, const void* d_mv_field, const void* d_dir_field, int mv_per_ctu,
                              void* const* d_outs, int out_pitch_bytes, void* stream) {
   if (!ctx) return HMME_ERR_ARG;
-  return predict_bi(ctx, "hmme_predict_bi_w_device", refs0, refs1, n_pics, fp, wps0, wps1, true, d_mv_field, d_dir_field, mv_per_ctu, d_outs, out_pitch_bytes, stream);
+  return predict_bi(ctx, "hmme_predict_bi_w_device", refs0, refs1, n_pics, 1, 0, 0, fp, wps0, wps1, true, d_mv_field, d_dir_field, mv_per_ctu, d_outs, out_pitch_bytes,
+                    stream);
 }
 
 int hmme_predict_bi_frame(hmme_ctx* ctx, const hmme_plane* ref0, const hmme_plane* ref1, const hmme_frame_params* fp, const int16_t* mv_field,
                           const uint8_t* dir_field, int mv_per_ctu, void* out, int out_stride) {
   if (!ctx) return HMME_ERR_ARG;
-  return predict_bi_frame(ctx, "hmme_predict_bi_frame", ref0, ref1, fp, nullptr, nullptr, false, mv_field, dir_field, mv_per_ctu, out, out_stride);
+  return predict_bi_frame(ctx, "hmme_predict_bi_frame", &ref0, &ref1, 1, 0, 0, fp, nullptr, nullptr, false, mv_field, dir_field, mv_per_ctu, &out, out_stride);
 }
 
 int hmme_predict_bi_w_frame(hmme_ctx* ctx, const hmme_plane* ref0, const hmme_plane* ref1, const hmme_frame_params* fp, const hmme_weight* wp0,
                             const hmme_weight* wp1, const int16_t* mv_field, const uint8_t* dir_field, int mv_per_ctu, void* out, int out_stride) {
   if (!ctx) return HMME_ERR_ARG;
-  return predict_bi_frame(ctx, "hmme_predict_bi_w_frame", ref0, ref1, fp, wp0, wp1, true, mv_field, dir_field, mv_per_ctu, out, out_stride);
+  return predict_bi_frame(ctx, "hmme_predict_bi_w_frame", &ref0, &ref1, 1, 0, 0, fp, wp0, wp1, true, mv_field, dir_field, mv_per_ctu, &out, out_stride);
 }
 
 // ---- 4:2:0 chroma motion compensation from the luma motion fields ------------------------------------------------------------------------------
-// The three prediction forms for Cb and Cr (me_predict_chroma_kernel; the rule: include/hmme.h).  Planes, images and weights come in component
-// pairs; the fields and the CTU range are those of the LUMA picture of width x height, so the planes go through pairs_begin with the whole
-// range (a chroma plane counts its own CTUs) and the luma range is taken from ctu_range.
-namespace {
-struct ChromaLaunch {
-  PairLaunch pl;
-  int w = 0, h = 0, n_ctu = 0, first = 0, count = 0;   // luma
-};
-// a refusal of the shared checks names the entry, too
-int chroma_named(hmme_ctx* ctx, const char* who, int rc) {
-  if (rc && ctx->err.compare(0, strlen(who), who) != 0) ctx->err = std::string(who) + ": " + ctx->err;
-  return rc;
-}
-// 4:2:0: an even luma size, every plane (none is null) half of it each way
-int chroma_size(hmme_ctx* ctx, const char* who, const hmme_plane* const* planes, int n, int width, int height) {
-  if (width < 16 || height < 16 || (width & 1) || (height & 1)) return fail(ctx, HMME_ERR_ARG, "%s: luma size %d x %d: 4:2:0 needs an even size of at least 16 x 16", who, width, height);
-  for (int r = 0; r < n; ++r)
-    if (planes[r]->width != width / 2 || planes[r]->height != height / 2)
-      return fail(ctx, HMME_ERR_ARG, "%s: plane %d is %d x %d, the chroma of a %d x %d picture is %d x %d", who, r, planes[r]->width, planes[r]->height, width, height, width / 2, height / 2);
-  return HMME_OK;
-}
-// after predict_args (no plane is null): the luma size, the planes' size, the luma CTU range; then pairs_begin
-int chroma_begin(hmme_ctx* ctx, const char* who, const hmme_plane* const* planes, int n, int width, int height, const hmme_frame_params* fp, const PredictArgs& a,
-                 hipStream_t s, ChromaLaunch* cl) {
-  int rc = chroma_size(ctx, who, planes, n, width, height);
-  if (rc) return rc;
-  cl->w = width; cl->h = height; cl->n_ctu = hmme_num_ctus(width, height);
-  rc = chroma_named(ctx, who, ctu_range(ctx, fp, cl->n_ctu, &cl->first, &cl->count));
-  if (rc) return rc;
-  hmme_frame_params f = a.f;
-  f.ctu_first = 0; f.ctu_count = -1;
-  return chroma_named(ctx, who, pairs_begin(ctx, planes, planes, n, &f, s, &cl->pl));   // every plane: of this context, of one size, of fp's bit depth
-}
-
-extern "C++" {
-template <int FORM, int WP>
-int launch_chroma(hmme_ctx* ctx, const hmme_plane* p0, const hmme::MeChromaSrc& src, const int16_t* d_field, int mv_per_ctu, const ChromaLaunch& cl, void* d_cb, void* d_cr,
-                  int out_pitch_bytes, hipStream_t s, const hmme::MeChromaWp<FORM, WP>& wp) {
-#define HMME_CHROMA(T, PER)                                                                                                                            \
-  hipLaunchKernelGGL((hmme::me_predict_chroma_kernel<T, FORM, WP, PER>), dim3((unsigned)cl.count), dim3(256), 0, s, src, p0->pitch, d_field, cl.first, \
-                     cl.w, cl.h, p0->bit_depth, (uint8_t*)d_cb, (uint8_t*)d_cr, out_pitch_bytes, wp)
-  if (p0->bps == 1) { if (mv_per_ctu == 1) HMME_CHROMA(uint8_t, 1); else HMME_CHROMA(uint8_t, 64); }
-  else { if (mv_per_ctu == 1) HMME_CHROMA(uint16_t, 1); else HMME_CHROMA(uint16_t, 64); }
-#undef HMME_CHROMA
-  HIP_TRY(ctx, hipGetLastError());
-  return HMME_OK;
-}
-}  // extern "C++"
-
-// hmme_predict_chroma_pairs_device: one launch per picture, WP = 0 without weights and where both components' are the identity
-int predict_chroma_pairs(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs, int n_pairs, int width, int height, const hmme_frame_params* fp,
-                         const hmme_weight* wps, const void* d_mv_field, int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream) {
-  if (n_pairs < 1 || 2 * n_pairs > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d pictures outside 1..%d", who, n_pairs, hmme::kMaxRefs / 2);
-  PredictArgs a;
-  int rc = predict_args(ctx, who, refs, 2 * n_pairs, !d_outs, fp, wps, d_mv_field, mv_per_ctu, out_pitch_bytes, &a, "plane");
-  if (rc) return rc;
-  for (int r = 0; r < 2 * n_pairs; ++r)
-    if (!d_outs[r]) return fail(ctx, HMME_ERR_ARG, "%s: null output image", who);
-  hipStream_t s = (hipStream_t)stream;
-  ChromaLaunch cl;
-  rc = chroma_begin(ctx, who, refs, 2 * n_pairs, width, height, fp, a, s, &cl);
-  if (rc) return rc;
-  const size_t field = (size_t)cl.n_ctu * mv_per_ctu * 2;
-  for (int i = 0; i < n_pairs && rc == HMME_OK && cl.count; ++i) {
-    hmme::MeChromaSrc src = {};
-    src.set.base[0] = refs[2 * i]->origin(); src.set.base[1] = refs[2 * i + 1]->origin();
-    const int16_t* f = (const int16_t*)d_mv_field + field * i;
-    if (a.identity[2 * i] && a.identity[2 * i + 1])
-      rc = launch_chroma<0, 0>(ctx, refs[0], src, f, mv_per_ctu, cl, d_outs[2 * i], d_outs[2 * i + 1], out_pitch_bytes, s, hmme::MeChromaWp<0, 0>{});
-    else
-      rc = launch_chroma<0, 1>(ctx, refs[0], src, f, mv_per_ctu, cl, d_outs[2 * i], d_outs[2 * i + 1], out_pitch_bytes, s, hmme::MeChromaWp<0, 1>{{a.pw[2 * i], a.pw[2 * i + 1]}});
-  }
-  return pairs_end(ctx, refs, refs, 2 * n_pairs, s, rc);   // whatever the launches returned: the scratch is acquired
-}
-
-// hmme_predict_chroma_refs_device: one launch, WP = 0 without weights and where every weight is the identity, else 2
-int predict_chroma_refs(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs, int n_refs, int width, int height, const hmme_frame_params* fp,
-                        const hmme_weight* wps, const void* d_mv_field, const void* d_ref_field, int mv_per_ctu, void* d_out_cb, void* d_out_cr, int out_pitch_bytes,
-                        void* stream) {
-  if (n_refs < 1 || 2 * n_refs > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d reference pictures outside 1..%d", who, n_refs, hmme::kMaxRefs / 2);
-  PredictArgs a;
-  int rc = predict_args(ctx, who, refs, 2 * n_refs, !d_ref_field || !d_out_cb || !d_out_cr, fp, wps, d_mv_field, mv_per_ctu, out_pitch_bytes, &a, "plane");
-  if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  ChromaLaunch cl;
-  rc = chroma_begin(ctx, who, refs, 2 * n_refs, width, height, fp, a, s, &cl);
-  if (rc) return rc;
-  if (cl.count) {
-    hmme::MeChromaSrc src = {cl.pl.refs, (const uint8_t*)d_ref_field, n_refs, cl.n_ctu};
-    hmme::MeChromaWp<1, 2> prw = {};
-    bool weighted = false;
-    for (int r = 0; r < 2 * n_refs; ++r) {
-      weighted = weighted || !a.identity[r];
-      if (wps) prw.ref[r] = a.pw[r];
-    }
-    if (weighted) rc = launch_chroma<1, 2>(ctx, refs[0], src, (const int16_t*)d_mv_field, mv_per_ctu, cl, d_out_cb, d_out_cr, out_pitch_bytes, s, prw);
-    else rc = launch_chroma<1, 0>(ctx, refs[0], src, (const int16_t*)d_mv_field, mv_per_ctu, cl, d_out_cb, d_out_cr, out_pitch_bytes, s, hmme::MeChromaWp<1, 0>{});
-  }
-  return pairs_end(ctx, refs, refs, 2 * n_refs, s, rc);
-}
-
-// hmme_predict_chroma_bi_device: one launch per picture; a component's two weights go through predict_bi_weight_eval like a luma picture's.
-// WP = 0 for a picture without weights or with four identities, else 1
-int predict_chroma_bi(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs0, const hmme_plane* const* refs1, int n_pics, int width, int height,
-                      const hmme_frame_params* fp, const hmme_weight* wps0, const hmme_weight* wps1, const void* d_mv_field, const void* d_dir_field, int mv_per_ctu,
-                      void* const* d_outs, int out_pitch_bytes, void* stream) {
-  if (!refs0 || !refs1 || n_pics < 1 || 4 * n_pics > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d pictures outside 1..%d (or a null plane list)", who, n_pics, hmme::kMaxRefs / 4);
-  PredBiWp bw[hmme::kMaxRefs / 2];   // entry 2 i + c: component c of picture i
-  int rc = (wps0 || wps1) ? check_predict_bi_weights(ctx, who, fp, wps0, wps1, 2 * n_pics, bw) : HMME_OK;
-  if (rc) return rc;
-  const hmme_plane* planes[hmme::kMaxRefs];   // picture i: planes[4 i], [4 i + 1] (list 0: Cb, Cr), planes[4 i + 2], [4 i + 3] (list 1)
-  for (int i = 0; i < n_pics; ++i)
-    for (int c = 0; c < 2; ++c) { planes[4 * i + c] = refs0[2 * i + c]; planes[4 * i + 2 + c] = refs1[2 * i + c]; }
-  PredictArgs a;
-  rc = predict_args(ctx, who, planes, 4 * n_pics, !d_dir_field || !d_outs, fp, nullptr, d_mv_field, mv_per_ctu, out_pitch_bytes, &a, "plane");
-  if (rc) return rc;
-  for (int r = 0; r < 2 * n_pics; ++r)
-    if (!d_outs[r]) return fail(ctx, HMME_ERR_ARG, "%s: null output image", who);
-  hipStream_t s = (hipStream_t)stream;
-  ChromaLaunch cl;
-  rc = chroma_begin(ctx, who, planes, 4 * n_pics, width, height, fp, a, s, &cl);
-  if (rc) return rc;
-  const size_t blocks = (size_t)cl.n_ctu * mv_per_ctu;
-  for (int i = 0; i < n_pics && rc == HMME_OK && cl.count; ++i) {
-    hmme::MeChromaSrc src = {};
-    for (int k = 0; k < 4; ++k) src.set.base[k] = planes[4 * i + k]->origin();
-    src.field = (const uint8_t*)d_dir_field + blocks * i;
-    src.n_ctu = cl.n_ctu;
-    const int16_t* f = (const int16_t*)d_mv_field + blocks * 4 * i;
-    if (bw[2 * i].identity && bw[2 * i + 1].identity)
-      rc = launch_chroma<2, 0>(ctx, planes[0], src, f, mv_per_ctu, cl, d_outs[2 * i], d_outs[2 * i + 1], out_pitch_bytes, s, hmme::MeChromaWp<2, 0>{});
-    else
-      rc = launch_chroma<2, 1>(ctx, planes[0], src, f, mv_per_ctu, cl, d_outs[2 * i], d_outs[2 * i + 1], out_pitch_bytes, s, hmme::MeChromaWp<2, 1>{{bw[2 * i].k, bw[2 * i + 1].k}});
-  }
-  return pairs_end(ctx, planes, planes, 4 * n_pics, s, rc);
-}
-
-// what the three _frame forms check before anything is staged
-int chroma_frame_args(hmme_ctx* ctx, const char* who, const hmme_frame_params* fp, const hmme_plane* const* planes, int n, bool null_arg, int mv_per_ctu, int width, int height) {
-  int rc = bi_check(ctx, who, fp, 0);
-  if (rc) return rc;
-  if (!planes || null_arg || (mv_per_ctu != 1 && mv_per_ctu != 64)) return fail(ctx, HMME_ERR_ARG, "%s: null argument, or %d MVs per CTU (1 or 64)", who, mv_per_ctu);
-  for (int r = 0; r < n; ++r)
-    if (!planes[r]) return fail(ctx, HMME_ERR_ARG, "%s: null plane", who);
-  // the images are staged at the first plane's size and sample type (every plane's depth is compared with fp's before a launch)
-  if (planes[0]->bit_depth != fp->bit_depth) return fail(ctx, HMME_ERR_ARG, "%s: planes hold %d-bit samples, the call asks for %d", who, planes[0]->bit_depth, fp->bit_depth);
-  return chroma_size(ctx, who, planes, n, width, height);
-}
-}  // namespace
-
+// The three prediction forms for Cb and Cr (me_predict_chroma_kernel; the rule: include/hmme.h): the bodies of the luma forms with two
+// components (predict_begin).
 int hmme_predict_chroma_pairs_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_pairs, int width, int height, const hmme_frame_params* fp,
                                      const hmme_weight* wps, const void* d_mv_field, int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream) {
   if (!ctx) return HMME_ERR_ARG;
-  return predict_chroma_pairs(ctx, "hmme_predict_chroma_pairs_device", refs, n_pairs, width, height, fp, wps, d_mv_field, mv_per_ctu, d_outs, out_pitch_bytes, stream);
+  return predict_pairs(ctx, "hmme_predict_chroma_pairs_device", refs, n_pairs, 2, width, height, fp, wps, d_mv_field, mv_per_ctu, d_outs, out_pitch_bytes, stream);
 }
 
 int hmme_predict_chroma_frame(hmme_ctx* ctx, const hmme_plane* const* ref, int width, int height, const hmme_frame_params* fp, const hmme_weight* wp,
                               const int16_t* mv_field, int mv_per_ctu, void* const* outs, int out_stride) {
   if (!ctx) return HMME_ERR_ARG;
-  const char* who = "hmme_predict_chroma_frame";
-  int rc = chroma_frame_args(ctx, who, fp, ref, 2, !mv_field || !outs || !outs[0] || !outs[1], mv_per_ctu, width, height);
-  for (int c = 0; rc == HMME_OK && wp && c < 2; ++c) {   // before anything is staged
-    char msg[256];
-    rc = other_weight_eval(fp->bit_depth, &wp[c], nullptr, nullptr, msg, sizeof msg);
-    if (rc) return fail(ctx, rc, "%s: plane %d: %s", who, c, msg);
-  }
-  if (rc) return rc;
-  const StagedChroma ch = {hmme_num_ctus(width, height), outs[1]};
-  return chroma_named(ctx, who, predict_staged(ctx, who, ref[0], mv_field, nullptr, mv_per_ctu, outs[0], out_stride, [&](void* d_field, void*, void* d_img, int pitch, hipStream_t s) {
-    void* d_outs[2] = {d_img, (uint8_t*)d_img + (size_t)pitch * ref[0]->height};
-    return predict_chroma_pairs(ctx, who, ref, 1, width, height, fp, wp, d_field, mv_per_ctu, d_outs, pitch, s);
-  }, 1, &ch));
+  return predict_frame(ctx, "hmme_predict_chroma_frame", ref, 2, width, height, fp, wp, mv_field, mv_per_ctu, outs, out_stride);
 }
 
 int hmme_predict_chroma_refs_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, int width, int height, const hmme_frame_params* fp,
                                     const hmme_weight* wps, const void* d_mv_field, const void* d_ref_field, int mv_per_ctu, void* d_out_cb, void* d_out_cr,
                                     int out_pitch_bytes, void* stream) {
   if (!ctx) return HMME_ERR_ARG;
-  return predict_chroma_refs(ctx, "hmme_predict_chroma_refs_device", refs, n_refs, width, height, fp, wps, d_mv_field, d_ref_field, mv_per_ctu, d_out_cb, d_out_cr,
-                             out_pitch_bytes, stream);
+  return predict_refs(ctx, "hmme_predict_chroma_refs_device", refs, n_refs, 2, width, height, fp, wps, d_mv_field, d_ref_field, mv_per_ctu, d_out_cb, d_out_cr,
+                      out_pitch_bytes, stream);
 }
 
 int hmme_predict_chroma_refs_frame(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, int width, int height, const hmme_frame_params* fp,
                                    const hmme_weight* wps, const int16_t* mv_field, const uint8_t* ref_field, int mv_per_ctu, void* const* outs, int out_stride) {
   if (!ctx) return HMME_ERR_ARG;
-  const char* who = "hmme_predict_chroma_refs_frame";
-  if (n_refs < 1 || 2 * n_refs > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d reference pictures outside 1..%d", who, n_refs, hmme::kMaxRefs / 2);
-  int rc = chroma_frame_args(ctx, who, fp, refs, 2 * n_refs, !mv_field || !ref_field || !outs || !outs[0] || !outs[1], mv_per_ctu, width, height);
-  for (int r = 0; rc == HMME_OK && wps && r < 2 * n_refs; ++r) {   // before anything is staged
-    char msg[256];
-    rc = other_weight_eval(fp->bit_depth, &wps[r], nullptr, nullptr, msg, sizeof msg);
-    if (rc) return fail(ctx, rc, "%s: plane %d: %s", who, r, msg);
-  }
-  if (rc) return rc;
-  const StagedChroma ch = {hmme_num_ctus(width, height), outs[1]};
-  return chroma_named(ctx, who, predict_staged(ctx, who, refs[0], mv_field, ref_field, mv_per_ctu, outs[0], out_stride, [&](void* d_field, void* d_ref_field, void* d_img, int pitch, hipStream_t s) {
-    return predict_chroma_refs(ctx, who, refs, n_refs, width, height, fp, wps, d_field, d_ref_field, mv_per_ctu, d_img, (uint8_t*)d_img + (size_t)pitch * refs[0]->height, pitch, s);
-  }, 1, &ch));
+  return predict_refs_frame(ctx, "hmme_predict_chroma_refs_frame", refs, n_refs, 2, width, height, fp, wps, mv_field, ref_field, mv_per_ctu, outs, out_stride);
 }
 
 int hmme_predict_chroma_bi_device(hmme_ctx* ctx, const hmme_plane* const* refs0, const hmme_plane* const* refs1, int n_pics, int width, int height,
                                   const hmme_frame_params* fp, const hmme_weight* wps0, const hmme_weight* wps1, const void* d_mv_field, const void* d_dir_field,
                                   int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream) {
   if (!ctx) return HMME_ERR_ARG;
-  return predict_chroma_bi(ctx, "hmme_predict_chroma_bi_device", refs0, refs1, n_pics, width, height, fp, wps0, wps1, d_mv_field, d_dir_field, mv_per_ctu, d_outs,
-                           out_pitch_bytes, stream);
+  return predict_bi(ctx, "hmme_predict_chroma_bi_device", refs0, refs1, n_pics, 2, width, height, fp, wps0, wps1, wps0 || wps1, d_mv_field, d_dir_field, mv_per_ctu,
+                    d_outs, out_pitch_bytes, stream);
 }
 
 int hmme_predict_chroma_bi_frame(hmme_ctx* ctx, const hmme_plane* const* ref0, const hmme_plane* const* ref1, int width, int height, const hmme_frame_params* fp,
                                  const hmme_weight* wp0, const hmme_weight* wp1, const int16_t* mv_field, const uint8_t* dir_field, int mv_per_ctu, void* const* outs,
                                  int out_stride) {
   if (!ctx) return HMME_ERR_ARG;
-  const char* who = "hmme_predict_chroma_bi_frame";
-  int rc = (wp0 || wp1) ? check_predict_bi_weights(ctx, who, fp, wp0, wp1, 2, nullptr) : HMME_OK;   // before anything is staged
-  if (rc == HMME_OK) rc = chroma_frame_args(ctx, who, fp, ref0, 2, !ref1 || !mv_field || !dir_field || !outs || !outs[0] || !outs[1], mv_per_ctu, width, height);
-  if (rc) return rc;
-  if (!ref1[0] || !ref1[1]) return fail(ctx, HMME_ERR_ARG, "%s: null plane", who);
-  const StagedChroma ch = {hmme_num_ctus(width, height), outs[1]};
-  return chroma_named(ctx, who, predict_staged(ctx, who, ref0[0], mv_field, dir_field, mv_per_ctu, outs[0], out_stride, [&](void* d_field, void* d_dir_field, void* d_img, int pitch, hipStream_t s) {
-    void* d_outs[2] = {d_img, (uint8_t*)d_img + (size_t)pitch * ref0[0]->height};
-    return predict_chroma_bi(ctx, who, ref0, ref1, 1, width, height, fp, wp0, wp1, d_field, d_dir_field, mv_per_ctu, d_outs, pitch, s);
-  }, 2, &ch));
+  return predict_bi_frame(ctx, "hmme_predict_chroma_bi_frame", ref0, ref1, 2, width, height, fp, wp0, wp1, wp0 || wp1, mv_field, dir_field, mv_per_ctu, outs, out_stride);
 }
 
 // ---- estimating explicit weighted-prediction parameters ----------------------------------------------------------------------------------------

@@ -2188,13 +2188,108 @@ me_weight_plane_kernel(const uint8_t* __restrict__ src, int src_pitch, uint8_t* 
 // below then yields the sample itself, which is what HM's filterCopy / single-stage paths produce
 __constant__ int kLumaTaps[4][8] = {{0, 0, 0, 64, 0, 0, 0, 0}, {-1, 4, -10, 58, 17, -5, 1, 0}, {-1, 4, -11, 40, 40, -11, 4, -1}, {0, 1, -5, 17, 58, -10, 4, -1}};
 
+// ---- what the three predict kernels share: the constants of a bit depth, the four ends of a sample (HM's "tails"), a block's field
+// entry, and the luma sum -----------------------------------------------------------------------------------------------------------------
+// the weight of addWeightUni as the kernels take it: round / shift are its round' and shift', made by the host (other_weight_eval)
+template <int WP> struct MePredWp {};
+template <> struct MePredWp<1> { int w0, round, shift, offset; };
+template <> struct MePredWp<2> { MePredWp<1> ref[kMaxRefs]; };
+
+// TComPrediction::xPredInterBlk's shifts and offsets (TComPrediction.cpp:669-707, TComInterpolationFilter.cpp) at one bit depth
+struct MePredConst {
+  int sh1, off1;   // horizontal pass into the 14-bit intermediate: (sum + off1) >> sh1
+  int sh2, off2;   // vertical pass, bi = false: rounds the intermediate back to a sample
+  int shb, offb;   // TComYuv::addAvg of two intermediates
+  int maxv;        // ClipBD
+  __device__ __forceinline__ explicit MePredConst(int bit_depth) {
+    const int head = 14 - bit_depth > 2 ? 14 - bit_depth : 2;   // headRoom (IF_INTERNAL_PREC - bitDepth, at least 2)
+    sh1 = 6 - head; off1 = -(8192 << sh1);
+    sh2 = 6 + head; off2 = (1 << (sh2 - 1)) + (8192 << 6);
+    shb = head + 1; offb = (1 << (shb - 1)) + 2 * 8192;
+    maxv = (1 << bit_depth) - 1;
+  }
+};
+
+__device__ __forceinline__ int me_clip_bd(int v, int maxv) { return v < 0 ? 0 : (v > maxv ? maxv : v); }
+// xPredInterUni with bi = true leaves the 14-bit intermediate P = sum >> 6 of the vertical pass (shift 6, offset 0, no clip).  HM keeps it in
+// a Pel: P + 8192 lies within [-24 576, 40 959] whatever the plane holds, |P| < 2^15.
+__device__ __forceinline__ int me_pel14(int sum) { return (int16_t)(sum >> 6); }
+
+// The four tails take the vertical sum(s) of a sample before any shift and return the sample.
+// rounded uni: xPredInterBlk with bi = false (TComPrediction.cpp:590-594, :669): ClipBD((sum + off2) >> sh2), int32 sums -- bit-identical to
+// hmo_pred_block_qpel at every phase
+__device__ __forceinline__ int me_tail_uni(int sum, const MePredConst& k) { return me_clip_bd((sum + k.off2) >> k.sh2, k.maxv); }
+// addWeightUni (TComWeightPrediction.cpp:133-180) in a slice with explicit weighted prediction (TComPrediction::motionCompensation,
+// TComPrediction.cpp:527-541): ClipBD(((w0 * (P + 8192) + round') >> shift') + offset), shift' = wp.shift + headRoom, round' = 1 << (shift' - 1).
+// The numerator stays inside int32 (hmme_bipred_weight_check); the offset is added in 64 bits, so any int offset is exact before the clip.
+// With w0 == 1 << wp.shift and offset 0 this IS me_tail_uni's result (nested floors), which is why identity weights run the unweighted kernels.
+__device__ __forceinline__ int me_tail_weight_uni(int sum, const MePredWp<1>& w, int maxv) {
+  const long long t = (long long)((w.w0 * (me_pel14(sum) + 8192) + w.round) >> w.shift) + w.offset;
+  return t < 0 ? 0 : (t > maxv ? maxv : (int)t);
+}
+// TComYuv::addAvg (TComYuv.cpp:352-390; TComPrediction.cpp:527-541 without WP): ClipBD((P0 + P1 + offset) >> shift), shift = headRoom + 1,
+// offset = (1 << (shift - 1)) + 2 * 8192 -- |P| < 2^15, so int32 holds it at every depth
+__device__ __forceinline__ int me_tail_avg(int sum0, int sum1, const MePredConst& k) {
+  return me_clip_bd((me_pel14(sum0) + me_pel14(sum1) + k.offb) >> k.shb, k.maxv);
+}
+// addWeightBi (TComWeightPrediction.cpp:46-49, :67-129; TComPrediction.cpp:603-651 xPredInterBi, :268-301 xWeightedPredictionBi) with the
+// bi-directional getWpScaling (:230-247): ClipBD((w0 * (P0 + 8192) + w1 * (P1 + 8192) + add) >> shift), shift = the slice's log2WeightDenom + 1 +
+// headRoom, add = (1 << (shift - 1)) + (offset0 + offset1) * 2^(shift - 1) -- the four fields of MePredBiWp<1>, made by the host, which also
+// refuses a pair whose numerator could leave int32 (hmme_predict_bi_weight_check), so int32 holds it.  The shift is arithmetic.
+__device__ __forceinline__ int me_tail_weight_bi(int sum0, int sum1, int w0, int w1, int add, int shift, int maxv) {
+  return me_clip_bd((w0 * (me_pel14(sum0) + 8192) + w1 * (me_pel14(sum1) + 8192) + add) >> shift, maxv);
+}
+
+// entry e of a motion field (int16 pairs, quarter-pel luma MVs), clamped like TComDataCU::clipMv for the CTU at luma position (cu_x, cu_y) of a
+// pic_w x pic_h luma picture: the patch a block reads then stays within 75 samples of the picture, inside the planes' 128 / 80-sample margins
+__device__ __forceinline__ void me_field_mv(const int16_t* __restrict__ mv_field, long e, int cu_x, int cu_y, int pic_w, int pic_h, int& mx, int& my) {
+  mx = mv_field[e * 2]; my = mv_field[e * 2 + 1];
+  clip_mv_q(mx, my, cu_x, cu_y, pic_w, pic_h);
+}
+
+// One plane's two passes for the wave's 8x8 luma block at picture position (x0, y0): the 15 x 15 patch at the clamped MV -- rows / columns
+// -3 .. +11 around the displaced block -- through LDS (rows of 15 consecutive samples per load), the horizontal pass into the 14-bit
+// intermediate (15 rows x 8), the vertical sum of lane (r, c) = (lane >> 3, lane & 7) -- returned before any shift, so that the caller ends it
+// with one of the tails.  live is wave-uniform; a wave that is not live reads nothing and still meets both barriers.
+template <typename SrcT>
+__device__ __forceinline__ int me_predict_block_sum(bool live, const uint8_t* origin, int ref_pitch, int x0, int y0, int mx, int my, int16_t* patch,
+                                                    int16_t* mid, int lane, const MePredConst& k) {
+  if (live) {
+    const uint8_t* src = origin + (long)(y0 + (my >> 2) - 3) * ref_pitch + (long)(x0 + (mx >> 2) - 3) * (long)sizeof(SrcT);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int e = lane + 64 * j, r = e / 15, c = e - r * 15;
+      if (e < 225) patch[r * 16 + c] = (int16_t)((const SrcT*)(src + (long)r * ref_pitch))[c];
+    }
+  }
+  __syncthreads();
+  if (live) {
+    const int* ch = kLumaTaps[mx & 3];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int o = lane + 64 * j, r = o >> 3, c = o & 7;
+      if (o < 120) {
+        int sum = 0;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) sum += ch[t] * (int)patch[r * 16 + c + t];
+        mid[o] = (int16_t)((sum + k.off1) >> k.sh1);
+      }
+    }
+  }
+  __syncthreads();
+  int sum = 0;
+  if (live) {
+    const int* cv = kLumaTaps[my & 3];
+    const int r = lane >> 3, c = lane & 7;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) sum += cv[t] * (int)mid[(r + t) * 8 + c];
+  }
+  return sum;
+}
+
 // The luma prediction of one CTU per workgroup from a MOTION FIELD: quarter-pel MVs int16 [n_ctu][mv_per_ctu][2], mv_per_ctu = 1 (one MV
-// for the CTU: HM's 64x64 2Nx2N) or 64 (one per 8x8 block, raster order inside the CTU).  Every MV is first clamped like
-// TComDataCU::clipMv for the CTU's position (clip_mv_q), so the 15 x 15 patch of an 8x8 block -- rows / columns -3 .. +11 around the
-// displaced block -- stays within 75 samples of the picture: inside the plane's 128 / 80-sample margins.  A wave takes one 8x8 block at a
-// time (16 of the CTU's 64): the patch goes through LDS (rows of 15 consecutive samples per load), the horizontal pass writes the 14-bit
-// intermediate (15 rows x 8), the vertical pass rounds and clips -- TComPrediction::xPredInterBlk with bi = false
-// (TComPrediction.cpp:590-594, :669) in integer arithmetic, int32 sums: bit-identical to hmo_pred_block_qpel at every phase.
+// for the CTU: HM's 64x64 2Nx2N) or 64 (one per 8x8 block, raster order inside the CTU), each read through me_field_mv.  A wave takes one
+// 8x8 block at a time (16 of the CTU's 64) through me_predict_block_sum.
 //   OUT = 0: the prediction, samples of the plane's type, into a pitched image at the block's picture position; samples beyond the
 //            picture are not written (blocks wholly outside it are skipped)
 //   OUT = 1: the bi-prediction origin 2 * cur - pred + bias as u16 (TEncSearch.cpp:3702-3712, TComYuv::removeHighFreq, unclipped; bias = the
@@ -2204,24 +2299,15 @@ __constant__ int kLumaTaps[4][8] = {{0, 0, 0, 64, 0, 0, 0, 0}, {-1, 4, -10, 58, 
 //            layout the search reads (8192, ctus_x * 8192, 128) or a padded plane's (128, 64 * pitch, pitch), which the refinement reads
 // All stores are 8 consecutive samples per block row.  Bandwidth is not tuned further: the pass moves tens of MB beside a search of
 // milliseconds.
-//   WP = 1:  the prediction of a slice with explicit weighted prediction (TComPrediction::motionCompensation, TComPrediction.cpp:527-541):
-//            xPredInterUni with bi = true leaves the 14-bit intermediate P = sum >> 6 of the vertical pass (shift 6, offset 0, no clip),
-//            addWeightUni (TComWeightPrediction.cpp:133-180) weights it: ClipBD(((w0 * (P + 8192) + round') >> shift') + offset) with
-//            shift' = wp.shift + headRoom and round' = 1 << (shift' - 1) -- both made by the host (MePredWp).  The numerator stays inside
-//            int32 (hmme_bipred_weight_check); the offset is added in 64 bits, so any int offset is exact before the clip.  With
-//            w0 == 1 << wp.shift and offset 0 this IS the WP = 0 result (nested floors), which is why identity weights run WP = 0.
-//            The weight travels in the kernel arguments; WP = 0 takes an empty struct and compiles to what it did without it.
+//   WP = 0:  me_tail_uni.  Takes an empty struct and compiles to what it did without the argument.
+//   WP = 1:  me_tail_weight_uni with the one weight in the kernel arguments (a slice with explicit weighted prediction)
 //   REFS = 1: a reference picture per block (hmme_predict_refs_device): ref_field uint8 [n_ctu][mv_per_ctu] names, beside every MV, the
 //            plane of `set` the block reads (all of one pitch; ref_origin is not used).  The index is the same for the whole wave -- a
 //            wave handles one 8x8 block at a time -- so the choice of the source base is a scalar one.  A block whose index is >= n_refs
 //            (0xFF: no CU covers it) is not live: it reads no plane and writes nothing, and still meets both barriers of its iteration.
 //            REFS = 0 takes an empty struct and compiles to what it did without it.
 //   WP = 2:  WP = 1 with one weight per reference picture (hmme_predict_refs_w_device; REFS = 1 only): the block's reference index --
-//            already a scalar -- picks its {w0, round', shift', offset} among the sixteen in the kernel arguments.  A value of its own
-//            and not more fields of MePredWp<1>, because that struct is an argument of the existing WP = 1 kernels.
-template <int WP> struct MePredWp {};
-template <> struct MePredWp<1> { int w0, round, shift, offset; };   // round / shift: addWeightUni's round' and shift'
-template <> struct MePredWp<2> { MePredWp<1> ref[kMaxRefs]; };
+//            already a scalar -- picks its MePredWp<1> among the sixteen in the kernel arguments.
 template <int REFS> struct MePredRefs {};
 template <> struct MePredRefs<1> { RefSet set; const uint8_t* ref_field; int n_refs; };
 template <typename SrcT, int OUT, int WP = 0, int REFS = 0>
@@ -2235,63 +2321,28 @@ me_predict_kernel(const uint8_t* __restrict__ ref_origin, int ref_pitch, const i
   const int ctus_x = (pic_w + 63) >> 6;
   const int ctu = ctu_first + blockIdx.x;
   const int cx = ctu % ctus_x, cy = ctu / ctus_x, cu_x = cx * 64, cu_y = cy * 64;
-  const int head = 14 - bit_depth > 2 ? 14 - bit_depth : 2;   // headRoom (IF_INTERNAL_PREC - bitDepth, at least 2)
-  const int sh1 = 6 - head, off1 = -(8192 << sh1), sh2 = 6 + head, off2 = (1 << (sh2 - 1)) + (8192 << 6);
-  const int maxv = (1 << bit_depth) - 1;
+  const MePredConst k(bit_depth);
 #pragma unroll 1
   for (int it = 0; it < 16; ++it) {
     const int b = it * 4 + wave, bx = (b & 7) * 8, by = (b >> 3) * 8;   // the four waves: four blocks side by side
-    const int16_t* mv = mv_field + ((long)ctu * mv_per_ctu + (mv_per_ctu == 1 ? 0 : b)) * 2;
-    int mx = mv[0], my = mv[1];
-    clip_mv_q(mx, my, cu_x, cu_y, pic_w, pic_h);
+    const long e = (long)ctu * mv_per_ctu + (mv_per_ctu == 1 ? 0 : b);
+    int mx, my;
+    me_field_mv(mv_field, e, cu_x, cu_y, pic_w, pic_h, mx, my);
     bool live = OUT == 1 || (cu_x + bx < pic_w && cu_y + by < pic_h);   // wave-uniform
     const uint8_t* origin = ref_origin;
     int ri = 0;
     if constexpr (REFS) {
-      ri = __builtin_amdgcn_readfirstlane((int)refs.ref_field[(long)ctu * mv_per_ctu + (mv_per_ctu == 1 ? 0 : b)]);
+      ri = __builtin_amdgcn_readfirstlane((int)refs.ref_field[e]);
       live = live && ri < refs.n_refs;
       origin = refs.set.base[ri < refs.n_refs ? ri : 0];
     }
+    const int sum = me_predict_block_sum<SrcT>(live, origin, ref_pitch, cu_x + bx, cu_y + by, mx, my, patch[wave], mid[wave], lane, k);
     if (live) {
-      const uint8_t* src = origin + (long)(cu_y + by + (my >> 2) - 3) * ref_pitch + (long)(cu_x + bx + (mx >> 2) - 3) * (long)sizeof(SrcT);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int e = lane + 64 * k, r = e / 15, c = e - r * 15;
-        if (e < 225) patch[wave][r * 16 + c] = (int16_t)((const SrcT*)(src + (long)r * ref_pitch))[c];
-      }
-    }
-    __syncthreads();
-    if (live) {
-      const int* ch = kLumaTaps[mx & 3];
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        const int o = lane + 64 * k, r = o >> 3, c = o & 7;
-        if (o < 120) {
-          int sum = 0;
-#pragma unroll
-          for (int t = 0; t < 8; ++t) sum += ch[t] * (int)patch[wave][r * 16 + c + t];
-          mid[wave][o] = (int16_t)((sum + off1) >> sh1);
-        }
-      }
-    }
-    __syncthreads();
-    if (live) {
-      const int* cv = kLumaTaps[my & 3];
       const int r = lane >> 3, c = lane & 7;
-      int sum = 0;
-#pragma unroll
-      for (int t = 0; t < 8; ++t) sum += cv[t] * (int)mid[wave][(r + t) * 8 + c];
       int v;
-      if constexpr (WP) {
-        MePredWp<1> w;
-        if constexpr (WP == 2) w = wp.ref[ri]; else w = wp;   // live: ri < n_refs
-        const int P = (int16_t)(sum >> 6);   // HM keeps the intermediate in a Pel: P + 8192 lies within [-24 576, 40 959] whatever the plane holds
-        const long long t = (long long)((w.w0 * (P + 8192) + w.round) >> w.shift) + w.offset;
-        v = t < 0 ? 0 : (t > maxv ? maxv : (int)t);
-      } else {
-        v = (sum + off2) >> sh2;
-        v = v < 0 ? 0 : (v > maxv ? maxv : v);
-      }
+      if constexpr (WP == 2) v = me_tail_weight_uni(sum, wp.ref[ri], k.maxv);   // live: ri < n_refs
+      else if constexpr (WP == 1) v = me_tail_weight_uni(sum, wp, k.maxv);
+      else v = me_tail_uni(sum, k);
       if (OUT == 0) {
         const int x = cu_x + bx + c, y = cu_y + by + r;
         if (x < pic_w && y < pic_h) ((SrcT*)(dst + (long)y * dst_pitch))[x] = (SrcT)v;
@@ -2643,60 +2694,15 @@ me_select_dirs_kernel(const uint32_t* __restrict__ mv_uni, const uint32_t* __res
 }
 
 // ---- the prediction of a picture whose blocks are L0, L1 or bi (hmme_predict_bi_device) ----------------------------------------------------
-// One list's two passes of me_predict_kernel for the wave's 8x8 block at picture position (x0, y0): the 15 x 15 patch at the clamped MV
-// through LDS, the horizontal pass into the 14-bit intermediate, the vertical sum of lane (r, c) = (lane >> 3, lane & 7) -- returned
-// before any shift, so that the caller ends it as bi = false (rounded) or bi = true (>> 6).  live is wave-uniform; a wave that is not
-// live reads nothing and still meets both barriers.
-template <typename SrcT>
-__device__ __forceinline__ int me_predict_block_sum(bool live, const uint8_t* origin, int ref_pitch, int x0, int y0, int mx, int my, int16_t* patch,
-                                                    int16_t* mid, int lane, int sh1, int off1) {
-  if (live) {
-    const uint8_t* src = origin + (long)(y0 + (my >> 2) - 3) * ref_pitch + (long)(x0 + (mx >> 2) - 3) * (long)sizeof(SrcT);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int e = lane + 64 * k, r = e / 15, c = e - r * 15;
-      if (e < 225) patch[r * 16 + c] = (int16_t)((const SrcT*)(src + (long)r * ref_pitch))[c];
-    }
-  }
-  __syncthreads();
-  if (live) {
-    const int* ch = kLumaTaps[mx & 3];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int o = lane + 64 * k, r = o >> 3, c = o & 7;
-      if (o < 120) {
-        int sum = 0;
-#pragma unroll
-        for (int t = 0; t < 8; ++t) sum += ch[t] * (int)patch[r * 16 + c + t];
-        mid[o] = (int16_t)((sum + off1) >> sh1);
-      }
-    }
-  }
-  __syncthreads();
-  int sum = 0;
-  if (live) {
-    const int* cv = kLumaTaps[my & 3];
-    const int r = lane >> 3, c = lane & 7;
-#pragma unroll
-    for (int t = 0; t < 8; ++t) sum += cv[t] * (int)mid[(r + t) * 8 + c];
-  }
-  return sum;
-}
-
 // me_predict_kernel<SrcT, 0> with a direction per block: one CTU per workgroup, a wave one 8x8 block at a time.  mv_field: int16
 // [2][n_ctu][mv_per_ctu][2] (list-major), dir_field: uint8 [n_ctu][mv_per_ctu] -- HM's interDir: 1 = list 0 (ref0), 2 = list 1 (ref1),
 // 3 = both.  The direction is the same for the whole wave, so it is read as a scalar; a list the direction does not name is not live in its
-// pass.  Direction 1 / 2: the sample me_predict_kernel writes from that plane and MV.  Direction 3 (TComPrediction.cpp:527-541 without WP):
-// both lists leave the 14-bit intermediate P = sum >> 6 (xPredInterUni with bi = true), then TComYuv::addAvg (TComYuv.cpp:352-390):
-// ClipBD((P0 + P1 + offset) >> shift), shift = headRoom + 1, offset = (1 << (shift - 1)) + 2 * 8192 -- |P| < 2^15, so int32 holds it at every
-// depth.  Any other direction (0xFF: no CU) reads no plane and writes nothing, and still meets all four barriers of its iteration.
-//   WP = 1:  the same picture in a B slice with getWPBiPred() (hmme_predict_bi_w_device; TComPrediction.cpp:603-651 xPredInterBi,
-//            TComWeightPrediction.cpp:268-301 xWeightedPredictionBi).  Direction 1 / 2: me_predict_kernel<.., WP = 1> with that list's weight
-//            (addWeightUni, the offset added in 64 bits).  Direction 3: addWeightBi (:46-49, :67-129) with the bi-directional getWpScaling
-//            (:230-247): ClipBD((w0 * (P0 + 8192) + w1 * (P1 + 8192) + add) >> shift), shift = the slice's log2WeightDenom + 1 + headRoom and
-//            add = (1 << (shift - 1)) + (offset0 + offset1) * 2^(shift - 1) -- both made by the host, which also refuses a pair whose numerator
-//            could leave int32 (hmme_predict_bi_weight_check), so int32 holds it.  The shift is arithmetic.  WP = 0 takes an empty struct and
-//            compiles to what it did without it.
+// pass of me_predict_block_sum.  Any direction outside 1..3 (0xFF: no CU) reads no plane and writes nothing, and still meets all four
+// barriers of its iteration.
+//   WP = 0:  direction 1 / 2: me_tail_uni, the sample me_predict_kernel writes from that plane and MV; direction 3: me_tail_avg.  Takes an
+//            empty struct and compiles to what it did without the argument.
+//   WP = 1:  the same picture in a B slice with getWPBiPred() (hmme_predict_bi_w_device).  Direction 1 / 2: me_tail_weight_uni with that
+//            list's weight (uni[]); direction 3: me_tail_weight_bi.
 template <int WP> struct MePredBiWp {};
 template <> struct MePredBiWp<1> { int w0, w1, add, shift; MePredWp<1> uni[2]; };
 template <typename SrcT, int WP = 0>
@@ -2710,10 +2716,7 @@ me_predict_bi_kernel(const uint8_t* __restrict__ ref0, const uint8_t* __restrict
   const int ctus_x = (pic_w + 63) >> 6;
   const int ctu = ctu_first + blockIdx.x;
   const int cx = ctu % ctus_x, cy = ctu / ctus_x, cu_x = cx * 64, cu_y = cy * 64;
-  const int head = 14 - bit_depth > 2 ? 14 - bit_depth : 2;   // headRoom (IF_INTERNAL_PREC - bitDepth, at least 2)
-  const int sh1 = 6 - head, off1 = -(8192 << sh1), sh2 = 6 + head, off2 = (1 << (sh2 - 1)) + (8192 << 6);
-  const int shb = head + 1, offb = (1 << (shb - 1)) + 2 * 8192;   // addAvg
-  const int maxv = (1 << bit_depth) - 1;
+  const MePredConst k(bit_depth);
 #pragma unroll 1
   for (int it = 0; it < 16; ++it) {
     const int b = it * 4 + wave, bx = (b & 7) * 8, by = (b >> 3) * 8;   // the four waves: four blocks side by side
@@ -2722,30 +2725,18 @@ me_predict_bi_kernel(const uint8_t* __restrict__ ref0, const uint8_t* __restrict
     const bool in_pic = cu_x + bx < pic_w && cu_y + by < pic_h && dir >= 1 && dir <= 3;   // wave-uniform
     const bool use0 = in_pic && (dir & 1), use1 = in_pic && (dir & 2);
     int mx0 = 0, my0 = 0, mx1 = 0, my1 = 0;
-    if (use0) { mx0 = mv_field[e * 2]; my0 = mv_field[e * 2 + 1]; clip_mv_q(mx0, my0, cu_x, cu_y, pic_w, pic_h); }
-    if (use1) {
-      const int16_t* mv = mv_field + ((long)n_ctu * mv_per_ctu + e) * 2;
-      mx1 = mv[0]; my1 = mv[1];
-      clip_mv_q(mx1, my1, cu_x, cu_y, pic_w, pic_h);
-    }
-    const int sum0 = me_predict_block_sum<SrcT>(use0, ref0, ref_pitch, cu_x + bx, cu_y + by, mx0, my0, patch[wave], mid[wave], lane, sh1, off1);
-    const int sum1 = me_predict_block_sum<SrcT>(use1, ref1, ref_pitch, cu_x + bx, cu_y + by, mx1, my1, patch[wave], mid[wave], lane, sh1, off1);
+    if (use0) me_field_mv(mv_field, e, cu_x, cu_y, pic_w, pic_h, mx0, my0);
+    if (use1) me_field_mv(mv_field, (long)n_ctu * mv_per_ctu + e, cu_x, cu_y, pic_w, pic_h, mx1, my1);
+    const int sum0 = me_predict_block_sum<SrcT>(use0, ref0, ref_pitch, cu_x + bx, cu_y + by, mx0, my0, patch[wave], mid[wave], lane, k);
+    const int sum1 = me_predict_block_sum<SrcT>(use1, ref1, ref_pitch, cu_x + bx, cu_y + by, mx1, my1, patch[wave], mid[wave], lane, k);
     if (in_pic) {
       int v;
       if constexpr (WP) {
-        if (use0 && use1) {
-          v = (wp.w0 * ((int)(int16_t)(sum0 >> 6) + 8192) + wp.w1 * ((int)(int16_t)(sum1 >> 6) + 8192) + wp.add) >> wp.shift;
-          v = v < 0 ? 0 : (v > maxv ? maxv : v);
-        } else {
-          const MePredWp<1> w = use0 ? wp.uni[0] : wp.uni[1];   // wave-uniform
-          const int P = (int16_t)((use0 ? sum0 : sum1) >> 6);
-          const long long t = (long long)((w.w0 * (P + 8192) + w.round) >> w.shift) + w.offset;
-          v = t < 0 ? 0 : (t > maxv ? maxv : (int)t);
-        }
+        if (use0 && use1) v = me_tail_weight_bi(sum0, sum1, wp.w0, wp.w1, wp.add, wp.shift, k.maxv);
+        else v = me_tail_weight_uni(use0 ? sum0 : sum1, use0 ? wp.uni[0] : wp.uni[1], k.maxv);   // wave-uniform
       } else {
-        if (use0 && use1) v = ((int)(int16_t)(sum0 >> 6) + (int)(int16_t)(sum1 >> 6) + offb) >> shb;   // HM keeps the intermediates in Pels
-        else v = ((use0 ? sum0 : sum1) + off2) >> sh2;
-        v = v < 0 ? 0 : (v > maxv ? maxv : v);
+        if (use0 && use1) v = me_tail_avg(sum0, sum1, k);
+        else v = me_tail_uni(use0 ? sum0 : sum1, k);
       }
       const int x = cu_x + bx + (lane & 7), y = cu_y + by + (lane >> 3);
       if (x < pic_w && y < pic_h) ((SrcT*)(dst + (long)y * dst_pitch))[x] = (SrcT)v;
@@ -2764,16 +2755,16 @@ __constant__ uint32_t kChromaTaps[8] = {0x00004000u, 0xFE0A3AFEu, 0xFE1036FCu, 0
 // One list's two passes for a 16-lane GROUP: the 4x4 block of one component (one 8x8 luma block) at chroma position (x0, y0).  The 7 x 7
 // patch -- rows / columns -1 .. +5 around the displaced block -- goes through LDS (patch: 7 rows of 8), the horizontal pass writes the 14-bit
 // intermediate (mid: 7 rows of 4), and lane l16 = 4 r + c returns the vertical sum of sample (r, c) before any shift, so that the caller ends
-// it as bi = false (rounded) or bi = true (>> 6).  origin, mx, my and live are the same for the 16 lanes of a group (and for the 32 of a
+// it with one of the tails.  origin, mx, my and live are the same for the 16 lanes of a group (and for the 32 of a
 // luma block's two components, apart from origin); a group that is not live reads nothing and still meets both barriers.
 template <typename SrcT>
 __device__ __forceinline__ int me_predict_chroma_sum(bool live, const uint8_t* origin, int ref_pitch, int x0, int y0, int mx, int my, int16_t* patch,
-                                                     int16_t* mid, int l16, const uint32_t* taps, int sh1, int off1) {
+                                                     int16_t* mid, int l16, const uint32_t* taps, const MePredConst& k) {
   if (live) {
     const uint8_t* src = origin + (long)(y0 + (my >> 3) - 1) * ref_pitch + (long)(x0 + (mx >> 3) - 1) * (long)sizeof(SrcT);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int e = l16 + 16 * k, r = e / 7, c = e - r * 7;
+    for (int j = 0; j < 4; ++j) {
+      const int e = l16 + 16 * j, r = e / 7, c = e - r * 7;
       if (e < 49) patch[r * 8 + c] = (int16_t)((const SrcT*)(src + (long)r * ref_pitch))[c];
     }
   }
@@ -2781,13 +2772,13 @@ __device__ __forceinline__ int me_predict_chroma_sum(bool live, const uint8_t* o
   if (live) {
     const uint32_t th = taps[mx & 7];
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int o = l16 + 16 * k, r = o >> 2, c = o & 3;
+    for (int j = 0; j < 2; ++j) {
+      const int o = l16 + 16 * j, r = o >> 2, c = o & 3;
       if (o < 28) {
         int sum = 0;
 #pragma unroll
         for (int t = 0; t < 4; ++t) sum += (int)(int8_t)(th >> (8 * t)) * (int)patch[r * 8 + c + t];
-        mid[o] = (int16_t)((sum + off1) >> sh1);
+        mid[o] = (int16_t)((sum + k.off1) >> k.sh1);
       }
     }
   }
@@ -2813,7 +2804,8 @@ __device__ __forceinline__ int me_predict_chroma_sum(bool live, const uint8_t* o
 //           WP = 2: the MePredWp<1> of plane 2 * index + component.  An index >= n_refs is not live.
 //   FORM 2: me_predict_bi_kernel<SrcT, WP>: mv_field int16 [2][n_ctu][PER][2], dir_field uint8 [n_ctu][PER], set.base[0..1] list 0, [2..3]
 //           list 1 (hmme_predict_chroma_bi_device); WP = 1: one MePredBiWp<1> per component.  A direction outside 1..3 is not live.
-// The tails are the luma kernels', with the component's own weight.  A block that is not live -- or whose luma block lies wholly outside
+// The tails are the luma kernels' (WP = 0: me_tail_uni / me_tail_avg; else me_tail_weight_uni / me_tail_weight_bi), with the component's own
+// weight.  A block that is not live -- or whose luma block lies wholly outside
 // the picture -- reads no plane and writes nothing, and still meets every barrier.  Stores are samples of the planes' type, only inside the
 // chroma picture.
 struct MeChromaSrc { RefSet set; const uint8_t* field; int n_refs, n_ctu; };   // field: ref_field (FORM 1) / dir_field (FORM 2)
@@ -2833,10 +2825,7 @@ me_predict_chroma_kernel(MeChromaSrc src, int ref_pitch, const int16_t* __restri
   const int ctus_x = (pic_w + 63) >> 6;
   const int ctu = ctu_first + blockIdx.x;
   const int cx = ctu % ctus_x, cy = ctu / ctus_x, cu_x = cx * 64, cu_y = cy * 64;
-  const int head = 14 - bit_depth > 2 ? 14 - bit_depth : 2;   // headRoom (IF_INTERNAL_PREC - bitDepth, at least 2)
-  const int sh1 = 6 - head, off1 = -(8192 << sh1), sh2 = 6 + head, off2 = (1 << (sh2 - 1)) + (8192 << 6);
-  const int shb = head + 1, offb = (1 << (shb - 1)) + 2 * 8192;   // addAvg
-  const int maxv = (1 << bit_depth) - 1;
+  const MePredConst k(bit_depth);
   uint8_t* const dst = comp ? dst_cr : dst_cb;
 #pragma unroll 1
   for (int it = 0; it < 8; ++it) {
@@ -2857,27 +2846,18 @@ me_predict_chroma_kernel(MeChromaSrc src, int ref_pitch, const int16_t* __restri
       use0 = ok && (dir & 1); use1 = ok && (dir & 2);
     }
     int mx0 = 0, my0 = 0, mx1 = 0, my1 = 0;
-    if (use0) { mx0 = mv_field[e * 2]; my0 = mv_field[e * 2 + 1]; clip_mv_q(mx0, my0, cu_x, cu_y, pic_w, pic_h); }
-    const int sum0 = me_predict_chroma_sum<SrcT>(use0, src.set.base[2 * sel + comp], ref_pitch, x0, y0, mx0, my0, patch[group], mid[group], l16, taps, sh1, off1);
+    if (use0) me_field_mv(mv_field, e, cu_x, cu_y, pic_w, pic_h, mx0, my0);
+    const int sum0 = me_predict_chroma_sum<SrcT>(use0, src.set.base[2 * sel + comp], ref_pitch, x0, y0, mx0, my0, patch[group], mid[group], l16, taps, k);
     int sum1 = 0;
     if constexpr (FORM == 2) {
-      if (use1) {
-        const int16_t* mv = mv_field + ((long)src.n_ctu * PER + e) * 2;
-        mx1 = mv[0]; my1 = mv[1];
-        clip_mv_q(mx1, my1, cu_x, cu_y, pic_w, pic_h);
-      }
-      sum1 = me_predict_chroma_sum<SrcT>(use1, src.set.base[2 + comp], ref_pitch, x0, y0, mx1, my1, patch[group], mid[group], l16, taps, sh1, off1);
+      if (use1) me_field_mv(mv_field, (long)src.n_ctu * PER + e, cu_x, cu_y, pic_w, pic_h, mx1, my1);
+      sum1 = me_predict_chroma_sum<SrcT>(use1, src.set.base[2 + comp], ref_pitch, x0, y0, mx1, my1, patch[group], mid[group], l16, taps, k);
     }
     if (use0 || use1) {
       int v;
       if (FORM == 2 && use0 && use1) {
-        if constexpr (FORM == 2 && WP == 1) {
-          const MePredBiWp<1>& w = wp.c[comp];
-          v = (w.w0 * ((int)(int16_t)(sum0 >> 6) + 8192) + w.w1 * ((int)(int16_t)(sum1 >> 6) + 8192) + w.add) >> w.shift;
-        } else {
-          v = ((int)(int16_t)(sum0 >> 6) + (int)(int16_t)(sum1 >> 6) + offb) >> shb;   // HM keeps the intermediates in Pels
-        }
-        v = v < 0 ? 0 : (v > maxv ? maxv : v);
+        if constexpr (FORM == 2 && WP == 1) v = me_tail_weight_bi(sum0, sum1, wp.c[comp].w0, wp.c[comp].w1, wp.c[comp].add, wp.c[comp].shift, k.maxv);
+        else v = me_tail_avg(sum0, sum1, k);
       } else {
         const int sum = use0 ? sum0 : sum1;
         if constexpr (WP != 0) {
@@ -2885,12 +2865,9 @@ me_predict_chroma_kernel(MeChromaSrc src, int ref_pitch, const int16_t* __restri
           if constexpr (FORM == 0) w = wp.c[comp];
           else if constexpr (FORM == 1) w = wp.ref[2 * sel + comp];
           else w = wp.c[comp].uni[use0 ? 0 : 1];
-          const int P = (int16_t)(sum >> 6);   // P + 8192 lies within [-24 576, 40 959] whatever the plane holds
-          const long long t = (long long)((w.w0 * (P + 8192) + w.round) >> w.shift) + w.offset;
-          v = t < 0 ? 0 : (t > maxv ? maxv : (int)t);
+          v = me_tail_weight_uni(sum, w, k.maxv);
         } else {
-          v = (sum + off2) >> sh2;
-          v = v < 0 ? 0 : (v > maxv ? maxv : v);
+          v = me_tail_uni(sum, k);
         }
       }
       const int x = x0 + (l16 & 3), y = y0 + (l16 >> 2);

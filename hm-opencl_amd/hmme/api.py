@@ -546,6 +546,24 @@ class Engine:
         assert out.dtype == dt and out.shape == (ref.height, ref.width) and out.flags.c_contiguous
         return out
 
+    def _predict_fields(self, plane, width, height, mv_field, block_field, lists, ctu_first, ctu_count):
+        """what the predict_*_frame methods prepare alike, for a picture of width x height LUMA samples whose planes are like `plane`: the
+        motion field (lists == 2: the two lists' fields, stacked), the reference / direction field beside it (None: the form has none) and the
+        call's parameters -> (field, mv_per_ctu, block field or None, FrameParams)"""
+        n = self.L.hmme_num_ctus(int(width), int(height))
+        if lists == 1:
+            f, per = self._field(mv_field, n)
+        else:
+            f0, per = self._field(mv_field[0], n)
+            f1, per1 = self._field(mv_field[1], n)
+            assert per == per1
+            f = np.ascontiguousarray(np.stack([f0, f1]))
+        bf = None
+        if block_field is not None:
+            bf = np.ascontiguousarray(block_field, dtype=np.uint8).reshape(n, -1)
+            assert bf.shape == (n, per)
+        return f, per, bf, FrameParams(1, 0, plane.bit_depth, ctu_first, ctu_count)
+
     def predict_pairs_device(self, refs, fp, d_mv_field, mv_per_ctu, d_outs, out_pitch_bytes, stream=0):
         """hmme_predict_pairs_device: the luma prediction of up to 16 pictures from their motion fields; d_outs = one device image address per picture"""
         assert len(refs) == len(d_outs)
@@ -556,10 +574,8 @@ class Engine:
     def predict_frame(self, ref, mv_field, out=None, ctu_first=0, ctu_count=-1):
         """hmme_predict_frame: motion-compensated luma prediction of one picture -> [height, width] array of the plane's sample type (u8 / u16).
         mv_field: int16[n_ctu, 2] or [n_ctu, 1 | 64, 2] quarter pels; `out` (same shape and type) keeps its samples outside the CTU range"""
-        n = self.L.hmme_num_ctus(ref.width, ref.height)
-        f, per = self._field(mv_field, n)
+        f, per, _, fp = self._predict_fields(ref, ref.width, ref.height, mv_field, None, 1, ctu_first, ctu_count)
         out = self._image(ref, out)
-        fp = FrameParams(1, 0, ref.bit_depth, ctu_first, ctu_count)
         self._check(self.L.hmme_predict_frame(self.h, ref.h, C.byref(fp), f.ctypes.data, per, out.ctypes.data, out.shape[1]))
         return out
 
@@ -623,10 +639,8 @@ class Engine:
 
     def predict_frame_w(self, ref, wp, mv_field, out=None, ctu_first=0, ctu_count=-1):
         """hmme_predict_frame_w: predict_frame with the weight wp"""
-        n = self.L.hmme_num_ctus(ref.width, ref.height)
-        f, per = self._field(mv_field, n)
+        f, per, _, fp = self._predict_fields(ref, ref.width, ref.height, mv_field, None, 1, ctu_first, ctu_count)
         out = self._image(ref, out)
-        fp = FrameParams(1, 0, ref.bit_depth, ctu_first, ctu_count)
         w = Weight(*[int(v) for v in wp])
         self._check(self.L.hmme_predict_frame_w(self.h, ref.h, C.byref(fp), C.byref(w), f.ctypes.data, per, out.ctypes.data, out.shape[1]))
         return out
@@ -733,12 +747,8 @@ class Engine:
         the plane of `refs` per block; `out` (same shape and type) keeps its samples outside the CTU range and in blocks whose index is
         >= len(refs)"""
         r0 = refs[0]
-        n = self.L.hmme_num_ctus(r0.width, r0.height)
-        f, per = self._field(mv_field, n)
-        rf = np.ascontiguousarray(ref_field, dtype=np.uint8).reshape(n, -1)
-        assert rf.shape == (n, per)
+        f, per, rf, fp = self._predict_fields(r0, r0.width, r0.height, mv_field, ref_field, 1, ctu_first, ctu_count)
         out = self._image(r0, out)
-        fp = FrameParams(1, 0, r0.bit_depth, ctu_first, ctu_count)
         ra = _handles(refs)
         self._check(self.L.hmme_predict_refs_frame(self.h, ra, len(refs), C.byref(fp), f.ctypes.data, rf.ctypes.data, per, out.ctypes.data, out.shape[1]))
         return out
@@ -797,15 +807,8 @@ class Engine:
         """hmme_predict_bi_frame: the prediction of one picture from list 0 (ref0) and list 1 (ref1) -> [height, width] array of the planes'
         sample type.  mv_field: int16[2, n_ctu, 2] or [2, n_ctu, 1 | 64, 2] quarter pels; dir_field: uint8[n_ctu] or [n_ctu, 1 | 64] (1, 2, 3;
         anything else: not written); `out` keeps its samples outside the CTU range and in blocks without a direction"""
-        n = self.L.hmme_num_ctus(ref0.width, ref0.height)
-        f0, per = self._field(mv_field[0], n)
-        f1, per1 = self._field(mv_field[1], n)
-        assert per == per1
-        f = np.ascontiguousarray(np.stack([f0, f1]))
-        df = np.ascontiguousarray(dir_field, dtype=np.uint8).reshape(n, -1)
-        assert df.shape == (n, per)
+        f, per, df, fp = self._predict_fields(ref0, ref0.width, ref0.height, mv_field, dir_field, 2, ctu_first, ctu_count)
         out = self._image(ref0, out)
-        fp = FrameParams(1, 0, ref0.bit_depth, ctu_first, ctu_count)
         self._check(self.L.hmme_predict_bi_frame(self.h, ref0.h, ref1.h, C.byref(fp), f.ctypes.data, df.ctypes.data, per, out.ctypes.data, out.shape[1]))
         return out
 
@@ -821,15 +824,8 @@ class Engine:
 
     def predict_bi_w_frame(self, ref0, ref1, wp0, wp1, mv_field, dir_field, out=None, ctu_first=0, ctu_count=-1):
         """hmme_predict_bi_w_frame: predict_bi_frame with the weights wp0 (ref0) and wp1 (ref1)"""
-        n = self.L.hmme_num_ctus(ref0.width, ref0.height)
-        f0, per = self._field(mv_field[0], n)
-        f1, per1 = self._field(mv_field[1], n)
-        assert per == per1
-        f = np.ascontiguousarray(np.stack([f0, f1]))
-        df = np.ascontiguousarray(dir_field, dtype=np.uint8).reshape(n, -1)
-        assert df.shape == (n, per)
+        f, per, df, fp = self._predict_fields(ref0, ref0.width, ref0.height, mv_field, dir_field, 2, ctu_first, ctu_count)
         out = self._image(ref0, out)
-        fp = FrameParams(1, 0, ref0.bit_depth, ctu_first, ctu_count)
         w0, w1 = (Weight(*[int(v) for v in w]) for w in (wp0, wp1))
         self._check(self.L.hmme_predict_bi_w_frame(self.h, ref0.h, ref1.h, C.byref(fp), C.byref(w0), C.byref(w1), f.ctypes.data, df.ctypes.data, per,
                                                    out.ctypes.data, out.shape[1]))
@@ -845,12 +841,8 @@ class Engine:
         """hmme_predict_refs_w_frame: predict_refs_frame with one weight per reference"""
         assert len(refs) == len(weights)
         r0 = refs[0]
-        n = self.L.hmme_num_ctus(r0.width, r0.height)
-        f, per = self._field(mv_field, n)
-        rf = np.ascontiguousarray(ref_field, dtype=np.uint8).reshape(n, -1)
-        assert rf.shape == (n, per)
+        f, per, rf, fp = self._predict_fields(r0, r0.width, r0.height, mv_field, ref_field, 1, ctu_first, ctu_count)
         out = self._image(r0, out)
-        fp = FrameParams(1, 0, r0.bit_depth, ctu_first, ctu_count)
         self._check(self.L.hmme_predict_refs_w_frame(self.h, _handles(refs), len(refs), C.byref(fp), self._weights(weights), f.ctypes.data, rf.ctypes.data, per,
                                                      out.ctypes.data, out.shape[1]))
         return out
@@ -885,10 +877,8 @@ class Engine:
     def predict_chroma_frame(self, ref, width, height, mv_field, outs=None, weights=None, ctu_first=0, ctu_count=-1):
         """hmme_predict_chroma_frame: ref = (cb, cr) planes of (width / 2) x (height / 2) -> (cb, cr) arrays [height / 2, width / 2] of the planes'
         sample type.  mv_field: the LUMA field, int16[n_ctu, 2] or [n_ctu, 1 | 64, 2] quarter pels; weights: None or one per component"""
-        n = self.L.hmme_num_ctus(int(width), int(height))
-        f, per = self._field(mv_field, n)
+        f, per, _, fp = self._predict_fields(ref[0], width, height, mv_field, None, 1, ctu_first, ctu_count)
         cb, cr, oa = self._chroma_images(ref[0], outs)
-        fp = FrameParams(1, 0, ref[0].bit_depth, ctu_first, ctu_count)
         self._check(self.L.hmme_predict_chroma_frame(self.h, _handles(ref), int(width), int(height), C.byref(fp), self._weights_or_none(weights, 2), f.ctypes.data,
                                                      per, oa, cb.shape[1]))
         return cb, cr
@@ -904,12 +894,8 @@ class Engine:
     def predict_chroma_refs_frame(self, refs, width, height, mv_field, ref_field, outs=None, weights=None, ctu_first=0, ctu_count=-1):
         """hmme_predict_chroma_refs_frame: predict_refs_frame for Cb and Cr; refs = [cb0, cr0, cb1, cr1, ...] -> (cb, cr)"""
         assert len(refs) % 2 == 0
-        n = self.L.hmme_num_ctus(int(width), int(height))
-        f, per = self._field(mv_field, n)
-        rf = np.ascontiguousarray(ref_field, dtype=np.uint8).reshape(n, -1)
-        assert rf.shape == (n, per)
+        f, per, rf, fp = self._predict_fields(refs[0], width, height, mv_field, ref_field, 1, ctu_first, ctu_count)
         cb, cr, oa = self._chroma_images(refs[0], outs)
-        fp = FrameParams(1, 0, refs[0].bit_depth, ctu_first, ctu_count)
         self._check(self.L.hmme_predict_chroma_refs_frame(self.h, _handles(refs), len(refs) // 2, int(width), int(height), C.byref(fp),
                                                           self._weights_or_none(weights, len(refs)), f.ctypes.data, rf.ctypes.data, per, oa, cb.shape[1]))
         return cb, cr
@@ -925,15 +911,8 @@ class Engine:
 
     def predict_chroma_bi_frame(self, ref0, ref1, width, height, mv_field, dir_field, outs=None, weights0=None, weights1=None, ctu_first=0, ctu_count=-1):
         """hmme_predict_chroma_bi_frame: predict_bi_frame for Cb and Cr; ref0 / ref1 = (cb, cr) of list 0 / list 1 -> (cb, cr)"""
-        n = self.L.hmme_num_ctus(int(width), int(height))
-        f0, per = self._field(mv_field[0], n)
-        f1, per1 = self._field(mv_field[1], n)
-        assert per == per1
-        f = np.ascontiguousarray(np.stack([f0, f1]))
-        df = np.ascontiguousarray(dir_field, dtype=np.uint8).reshape(n, -1)
-        assert df.shape == (n, per)
+        f, per, df, fp = self._predict_fields(ref0[0], width, height, mv_field, dir_field, 2, ctu_first, ctu_count)
         cb, cr, oa = self._chroma_images(ref0[0], outs)
-        fp = FrameParams(1, 0, ref0[0].bit_depth, ctu_first, ctu_count)
         self._check(self.L.hmme_predict_chroma_bi_frame(self.h, _handles(ref0), _handles(ref1), int(width), int(height), C.byref(fp),
                                                         self._weights_or_none(weights0, 2), self._weights_or_none(weights1, 2), f.ctypes.data, df.ctypes.data, per,
                                                         oa, cb.shape[1]))

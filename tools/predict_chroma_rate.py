@@ -7,9 +7,11 @@
   refs_*                                 hmme_predict_refs(_w)_device / hmme_predict_chroma_refs_device, four references drawn per block
   bi_*                                   hmme_predict_bi(_w)_device / hmme_predict_chroma_bi_device, blocks L0, L1 and bi in equal parts
   *_ratio                                chroma median over luma median
+  crc32 (per form)                       CRC-32 of the image(s) the form wrote, downloaded after its timed repeats: two libraries that
+                                         report the same value computed the same samples at the size timed
 
 Both bit depths 8 and 10.  REPS (default 7) repeats of each from a warm clock; median, min and max.  usage: tools/predict_chroma_rate.py [out.json]"""
-import json, os, statistics, sys
+import json, os, statistics, sys, zlib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "hm-opencl_amd"))
 import numpy as np
@@ -28,13 +30,18 @@ def stats(t, nd=4):
     return {"median": round(statistics.median(t), nd), "min": round(min(t), nd), "max": round(max(t), nd)}
 
 
-def timed(fn):
-    """REPS single launches, each between its own pair of events -> ms"""
+def timed(fn, images):
+    """REPS single launches, each between its own pair of events -> ms, and the CRC-32 of what the last one left in `images`"""
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(REPS)]
     for a, b in ev:
         a.record(); fn(); b.record()
     torch.cuda.synchronize()
-    return stats([a.elapsed_time(b) for a, b in ev])
+    res = stats([a.elapsed_time(b) for a, b in ev])
+    crc = 0
+    for t in images:
+        crc = zlib.crc32(t.cpu().numpy().tobytes(), crc)
+    res["crc32"] = f"{crc:08x}"
+    return res
 
 
 def plane(pw, ph, bd, rng):
@@ -84,7 +91,7 @@ for bd in (8, 10):
         for fn in runs.values():
             fn()
     torch.cuda.synchronize()
-    case = {k: timed(fn) for k, fn in runs.items()}
+    case = {k: timed(fn, d_c if "chroma" in k else [d_img]) for k, fn in runs.items()}
     for form in ("pairs", "pairs_w", "refs", "refs_w", "bi", "bi_w"):
         case[f"{form}_ratio"] = round(case[f"{form}_chroma_ms"]["median"] / case[f"{form}_luma_ms"]["median"], 3)
     case["blocks_per_direction"] = np.bincount(d_dir.cpu().numpy().reshape(-1), minlength=4)[1:4].tolist()
