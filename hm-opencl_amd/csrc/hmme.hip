@@ -13,6 +13,7 @@
 #include <cstring>
 #include <functional>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "me_kernels.hpp"
@@ -129,8 +130,8 @@ struct hmme_ctx {
   int* d_flag = nullptr;
   bool lds_optin[8] = {false, false, false, false, false, false, false, false};
   int num_cus = 0;
-  bool frac_lds_optin[3][2] = {{false, false}, {false, false}, {false, false}};   // [8-bit | u16 | u16 weighted][hadamard]
-  int frac_wg_per_cu[3][2] = {{0, 0}, {0, 0}, {0, 0}};   // same index: workgroups of that me_frac_kernel a CU holds (runtime occupancy query, first use)
+  bool frac_lds_optin[6] = {false, false, false, false, false, false};   // per build of me_frac_kernel (FracBuild::index)
+  int frac_wg_per_cu[6] = {0, 0, 0, 0, 0, 0};   // same index: workgroups of that me_frac_kernel a CU holds (runtime occupancy query, first use)
   uint8_t* d_wwin = nullptr;          // per-CTU calls with weighted prediction: the weighted copy of the staged window (the search's)
   uint16_t* d_frac_cover = nullptr;   // fractional refinement: slots covering each 8x8 / 4x4 position, same for every CTU
   int16_t* d_imv = nullptr;           // host-facing refine call: integer MVs / quarter-pel MVs / costs on the device
@@ -249,6 +250,16 @@ int plane_write_wait(hmme_ctx* ctx, const hmme_plane* pl, hipStream_t s) {
   return HMME_OK;
 }
 
+// the A/B knobs of the environment (include/hmme.h, "Environment"), read once per process
+struct Knobs { int tail_parts = 0, tail_launches = 0, frac_grid = 0; bool frac_job_table = false, trace = false; };
+const Knobs& knobs() {
+  static const Knobs k = [] {
+    const auto num = [](const char* name) { const char* v = std::getenv(name); return v ? std::atoi(v) : 0; };
+    return Knobs{num("HMME_TAIL_PARTS"), num("HMME_TAIL_LAUNCHES"), num("HMME_FRAC_GRID"), std::getenv("HMME_FRAC_JOB_TABLE") != nullptr, std::getenv("HMME_TRACE") != nullptr};
+  }();
+  return k;
+}
+
 // ---- 8-bit path --------------------------------------------------------------------------------------
 RefSet one_ref(const uint8_t* base) {
   RefSet r;
@@ -265,24 +276,28 @@ int fair_prio(const hmme_ctx* ctx, int workgroups, bool whole_jobs) {
   return (whole_jobs || workgroups <= 4 * ctx->wg_slots) ? 1 : 0;
 }
 
-int launch_search8(hmme_ctx* ctx, const RefSet& cur, int cur_ctus_x, const RefSet& ref, int ref_pitch, const MeJob* d_jobs,
-                   int n_jobs, int fen, int16_t* d_mv, uint32_t* d_sad, hipStream_t stream) {
-  if (n_jobs <= 0) return HMME_OK;
-  const int fair = fair_prio(ctx, n_jobs, true);
-  if (fen)
-    hipLaunchKernelGGL((hmme::me_search_kernel<1, 0>), dim3(n_jobs), dim3(hmme::kThreads), 0, stream, cur, cur_ctus_x, ref,
-                       ref_pitch, (const void*)d_jobs, ctx->lambda_q16, d_mv, d_sad, (unsigned long long*)nullptr, fair, 0);
-  else
-    hipLaunchKernelGGL((hmme::me_search_kernel<0, 0>), dim3(n_jobs), dim3(hmme::kThreads), 0, stream, cur, cur_ctus_x, ref,
-                       ref_pitch, (const void*)d_jobs, ctx->lambda_q16, d_mv, d_sad, (unsigned long long*)nullptr, fair, 0);
-  HIP_TRY(ctx, hipGetLastError());
-  return HMME_OK;
+// The one way a search launch picks its cost function: f is called with std::integral_constant<int, FEN> and names its kernel with it.
+template <class F>
+auto with_fen(int fen, F&& f) {
+  return fen ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 0>{});
+}
+
+// me_search_kernel<FEN, SPLIT> over n_wg workgroups.  SPLIT = 0: whole jobs (MeJob), results straight into d_mv / d_sad; 1 and 2 (below) merge into `best`
+template <int SPLIT>
+int launch_search8(hmme_ctx* ctx, const RefSet& cur, int cur_ctus_x, const RefSet& ref, int ref_pitch, const void* d_jobs, int n_wg, int fen,
+                   int16_t* d_mv, uint32_t* d_sad, unsigned long long* best, int n_seg_jobs, hipStream_t stream) {
+  if (n_wg <= 0) return HMME_OK;
+  return with_fen(fen, [&](auto f) -> int {
+    hipLaunchKernelGGL((hmme::me_search_kernel<decltype(f)::value, SPLIT>), dim3(n_wg), dim3(hmme::kThreads), 0, stream, cur, cur_ctus_x, ref,
+                       ref_pitch, d_jobs, ctx->lambda_q16, d_mv, d_sad, best, fair_prio(ctx, n_wg, SPLIT == 0), n_seg_jobs);
+    HIP_TRY(ctx, hipGetLastError());
+    return HMME_OK;
+  });
 }
 
 int finalize_best(hmme_ctx* ctx, unsigned long long* d_best, const MeJob16* d_jobs, const int* d_first_strip, int n_jobs, int16_t* d_mv,
                   uint32_t* d_sad, hipStream_t stream);
 
-// 8-bit split mode: n_jobs * n_split workgroups, each runs a slice of its CTU's tasks and merges through ctx->d_best
 // the 64-bit merge table of a split / strip / tile launch: the caller's (already all ones), or ctx->d_best grown and preset here
 int merge_table(hmme_ctx* ctx, int n_jobs, unsigned long long* preset, hipStream_t stream, unsigned long long** table) {
   if (preset) { *table = preset; return HMME_OK; }
@@ -298,6 +313,7 @@ int merge_table(hmme_ctx* ctx, int n_jobs, unsigned long long* preset, hipStream
   return HMME_OK;
 }
 
+// 8-bit split mode: n_jobs * n_split workgroups, each runs a slice of its CTU's tasks and merges through ctx->d_best
 int launch_search8_split(hmme_ctx* ctx, const RefSet& cur, int cur_ctus_x, const RefSet& ref, int ref_pitch, const MeJob16* d_jobs,
                          const int* d_first_strip, int n_jobs, int n_split, int fen, int16_t* d_mv, uint32_t* d_sad,
                          hipStream_t stream, unsigned long long* preset_best = nullptr, bool finalize = true) {
@@ -305,14 +321,8 @@ int launch_search8_split(hmme_ctx* ctx, const RefSet& cur, int cur_ctus_x, const
   unsigned long long* best = nullptr;
   int rc = merge_table(ctx, n_jobs, preset_best, stream, &best);
   if (rc) return rc;
-  const int fair = fair_prio(ctx, n_jobs * n_split, false);
-  if (fen)
-    hipLaunchKernelGGL((hmme::me_search_kernel<1, 1>), dim3(n_jobs * n_split), dim3(hmme::kThreads), 0, stream, cur, cur_ctus_x,
-                       ref, ref_pitch, (const void*)d_jobs, ctx->lambda_q16, (int16_t*)nullptr, (uint32_t*)nullptr, best, fair, 0);
-  else
-    hipLaunchKernelGGL((hmme::me_search_kernel<0, 1>), dim3(n_jobs * n_split), dim3(hmme::kThreads), 0, stream, cur, cur_ctus_x,
-                       ref, ref_pitch, (const void*)d_jobs, ctx->lambda_q16, (int16_t*)nullptr, (uint32_t*)nullptr, best, fair, 0);
-  HIP_TRY(ctx, hipGetLastError());
+  rc = launch_search8<1>(ctx, cur, cur_ctus_x, ref, ref_pitch, d_jobs, n_jobs * n_split, fen, nullptr, nullptr, best, 0, stream);
+  if (rc) return rc;
   return finalize ? finalize_best(ctx, best, d_jobs, d_first_strip, n_jobs, d_mv, d_sad, stream) : HMME_OK;
 }
 
@@ -321,14 +331,8 @@ int launch_search8_segments(hmme_ctx* ctx, const RefSet& cur, int cur_ctus_x, co
                             const int* d_first_strip, int n_jobs, int n_wg, int fen, int16_t* d_mv, uint32_t* d_sad, hipStream_t stream,
                             unsigned long long* best) {
   if (n_jobs <= 0 || n_wg <= 0) return HMME_OK;
-  const int fair = fair_prio(ctx, n_wg, false);
-  if (fen)
-    hipLaunchKernelGGL((hmme::me_search_kernel<1, 2>), dim3(n_wg), dim3(hmme::kThreads), 0, stream, cur, cur_ctus_x, ref, ref_pitch, d_table,
-                       ctx->lambda_q16, (int16_t*)nullptr, (uint32_t*)nullptr, best, fair, n_jobs);
-  else
-    hipLaunchKernelGGL((hmme::me_search_kernel<0, 2>), dim3(n_wg), dim3(hmme::kThreads), 0, stream, cur, cur_ctus_x, ref, ref_pitch, d_table,
-                       ctx->lambda_q16, (int16_t*)nullptr, (uint32_t*)nullptr, best, fair, n_jobs);
-  HIP_TRY(ctx, hipGetLastError());
+  const int rc = launch_search8<2>(ctx, cur, cur_ctus_x, ref, ref_pitch, d_table, n_wg, fen, nullptr, nullptr, best, n_jobs, stream);
+  if (rc) return rc;
   return finalize_best(ctx, best, hmme::me_seg_table_jobs(d_table, n_wg), d_first_strip, n_jobs, d_mv, d_sad, stream);
 }
 
@@ -348,6 +352,17 @@ int strips_for(int pdw, int wy_max) {
   int n = 1;
   while (n < wy_max && lds_bytes16(pdw, (wy_max + n - 1) / n) > kLdsBudget16) ++n;   // bounded: one-row strips always fit
   return n;
+}
+
+// f is called with std::integral_constant<int, PDW> of the compiled pitch `pdw` (pick_pdw16)
+template <class F>
+auto with_pdw16(int pdw, F&& f) {
+  switch (pdw16_index(pdw)) {
+    case 0: return f(std::integral_constant<int, kPdw16[0]>{});
+    case 1: return f(std::integral_constant<int, kPdw16[1]>{});
+    case 2: return f(std::integral_constant<int, kPdw16[2]>{});
+    default: return f(std::integral_constant<int, kPdw16[3]>{});
+  }
 }
 
 template <int FEN, int PDW>
@@ -374,16 +389,9 @@ int launch_search16(hmme_ctx* ctx, const RefSet& cur, int cur_ctus_x, const RefS
   if (rc) return rc;
   const size_t lds = lds_bytes16(pdw, strip_rows_max);
   const int sh = bit_depth - 8;
-#define LAUNCH16(I)                                                                                                       \
-  rc = fen ? launch16_t<1, kPdw16[I]>(ctx, cur, cur_ctus_x, ref, ref_pitch, d_jobs, n_wg, lds, sh, best, stream)            \
-           : launch16_t<0, kPdw16[I]>(ctx, cur, cur_ctus_x, ref, ref_pitch, d_jobs, n_wg, lds, sh, best, stream)
-  switch (pdw16_index(pdw)) {
-    case 0: LAUNCH16(0); break;
-    case 1: LAUNCH16(1); break;
-    case 2: LAUNCH16(2); break;
-    default: LAUNCH16(3); break;
-  }
-#undef LAUNCH16
+  rc = with_fen(fen, [&](auto f) {
+    return with_pdw16(pdw, [&](auto p) { return launch16_t<decltype(f)::value, decltype(p)::value>(ctx, cur, cur_ctus_x, ref, ref_pitch, d_jobs, n_wg, lds, sh, best, stream); });
+  });
   if (rc) return rc;
   return finalize ? finalize_best(ctx, best, d_jobs, d_first_strip, n_jobs, d_mv, d_sad, stream) : HMME_OK;
 }
@@ -722,19 +730,23 @@ using frac_fn = void (*)(const RefSet, int, const RefSet, int, const MeJob*, con
 // One build per (sample width, distortion, weighting) at two waves per SIMD: the 8-bit kernels spill nothing (231 / 237 VGPRs), two
 // workgroups per CU.  Round 4's three-wave build of the 8-bit kernel (168 VGPRs + 50 spilled dwords per lane: 104 MB of scratch writes
 // per 2160p launch) is gone.
-inline frac_fn frac_kernel(int wide, int had, int wp = 0) {
-  static const frac_fn fns[2][2] = {{hmme::me_frac_kernel<0, 1, 0, 2>, hmme::me_frac_kernel<1, 1, 0, 2>}, {hmme::me_frac_kernel<0, 2, 0>, hmme::me_frac_kernel<1, 2, 0>}};
-  static const frac_fn fns_wp[2] = {hmme::me_frac_kernel<0, 2, 1>, hmme::me_frac_kernel<1, 2, 1>};   // weighted calls always stage u16 samples
-  if (wp) return fns_wp[had ? 1 : 0];
-  return fns[wide ? 1 : 0][had ? 1 : 0];
+struct FracBuild {
+  int wide = 0, had = 0, wp = 0;   // u16 samples (else 8-bit), Hadamard (else SAD), weighted (always on u16 samples)
+  int bps() const { return wide ? 2 : 1; }
+  int index() const { return (wp ? 2 : wide ? 1 : 0) * 2 + (had ? 1 : 0); }
+};
+inline frac_fn frac_kernel(FracBuild b) {
+  static const frac_fn fns[6] = {hmme::me_frac_kernel<0, 1, 0, 2>, hmme::me_frac_kernel<1, 1, 0, 2>, hmme::me_frac_kernel<0, 2, 0>, hmme::me_frac_kernel<1, 2, 0>,
+                                 hmme::me_frac_kernel<0, 2, 1>, hmme::me_frac_kernel<1, 2, 1>};
+  return fns[b.index()];
 }
 // more than 64 KiB of dynamic LDS: opt in once per kernel and context
-int frac_lds_optin(hmme_ctx* ctx, int wide, int had, int wp) {
-  bool& done = ctx->frac_lds_optin[wp ? 2 : (wide ? 1 : 0)][had ? 1 : 0];
+int frac_lds_optin(hmme_ctx* ctx, FracBuild b) {
+  bool& done = ctx->frac_lds_optin[b.index()];
   if (done) return HMME_OK;
-  const size_t bytes = hmme::frac_lds_bytes(wide ? 2 : 1);
+  const size_t bytes = hmme::frac_lds_bytes(b.bps());
   if (bytes > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute((const void*)frac_kernel(wide, had, wp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    const hipError_t e = hipFuncSetAttribute((const void*)frac_kernel(b), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e != hipSuccess) return fail(ctx, HMME_ERR_DEVICE, "hipFuncSetAttribute(me_frac_kernel, %zu bytes of LDS) -> %s", bytes, hipGetErrorString(e));
   }
   done = true;
@@ -746,21 +758,20 @@ const hmme::FracPrep kNoPrep = {nullptr, 1u << 16, 0, 0};
 // workgroups that take job after job from a counter instead, HMME_FRAC_GRID=-1 as many of those as the chip holds at a time (the
 // runtime's occupancy figure for this kernel with its LDS block x the CUs): round 4's intermediate launch, kept for A/B runs -- once
 // both orders ran last-first it was the slower one on every content (profiles/r04g_frac_grid_both_last_first.txt)
-int frac_grid(hmme_ctx* ctx, int wide, int had, int wp, int jobs) {
-  static const int forced = std::getenv("HMME_FRAC_GRID") ? std::atoi(std::getenv("HMME_FRAC_GRID")) : 0;
+int frac_grid(hmme_ctx* ctx, FracBuild b, int jobs) {
+  const int forced = knobs().frac_grid;
   if (forced == 0) return jobs;
   int grid = forced;
   if (forced < 0) {
-    int& per_cu = ctx->frac_wg_per_cu[wp ? 2 : (wide ? 1 : 0)][had ? 1 : 0];
+    int& per_cu = ctx->frac_wg_per_cu[b.index()];
     if (per_cu == 0) {
       int n = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)frac_kernel(wide, had, wp), hmme::frac_threads(wide ? 2 : 1),
-                                                       hmme::frac_lds_bytes(wide ? 2 : 1)) != hipSuccess || n < 1) {
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)frac_kernel(b), hmme::frac_threads(b.bps()), hmme::frac_lds_bytes(b.bps())) != hipSuccess || n < 1) {
         (void)hipGetLastError();
         n = 2;
       }
       per_cu = n;
-      if (std::getenv("HMME_TRACE")) fprintf(stderr, "hmme: me_frac_kernel<%d, %d, %d>: %d workgroups per CU, %d CUs\n", had ? 1 : 0, wide ? 2 : 1, wp ? 1 : 0, n, ctx->num_cus);
+      if (knobs().trace) fprintf(stderr, "hmme: me_frac_kernel<%d, %d, %d>: %d workgroups per CU, %d CUs\n", b.had ? 1 : 0, b.bps(), b.wp ? 1 : 0, n, ctx->num_cus);
     }
     grid = per_cu * ctx->num_cus;
   }
@@ -890,10 +901,7 @@ int ctu_call(hmme_ctx* ctx, const int16_t* ctu, int ctu_stride, const int16_t* r
     const int per_tile = kCallMaxJobs / (tiles_x * tiles_y);
     for (int ty = 0; ty < tiles_y; ++ty)
       for (int tx = 0; tx < tiles_x; ++tx) {
-        MeJob sub = job;
-        sub.lt_x = (int16_t)(job.lt_x + tx * hmme::kTileStep); sub.lt_y = (int16_t)(job.lt_y + ty * hmme::kTileStep);
-        sub.rb_x = (int16_t)std::min<int>(job.rb_x, sub.lt_x + hmme::kTileStep - 1);
-        sub.rb_y = (int16_t)std::min<int>(job.rb_y, sub.lt_y + hmme::kTileStep - 1);
+        const MeJob sub = hmme::me_tile_job(job, tx, ty);
         const int nt = hmme::me_num_tasks(sub.rb_x - sub.lt_x + 1, sub.rb_y - sub.lt_y + 1);
         const int parts = std::max(1, std::min(per_tile, (nt + 3) / 4));   // 4 tasks = one per wave
         for (int i = 0; i < parts; ++i, ++n_wg) {
@@ -955,9 +963,10 @@ int ctu_call(hmme_ctx* ctx, const int16_t* ctu, int ctu_stride, const int16_t* r
     const int16_t* d_imv = do_search ? d_mv1 : (const int16_t*)(ctx->d_call + kCallImv);
     // weighted: the interpolated prediction is weighted sample by sample (me_frac_eval0 / me_frac_eval1, FracWp); the current samples carry `bias`, the raw window none
     const hmme::FracWp fw = wp ? hmme::FracWp{std::ldexp((float)wp->w0, -wp->shift), std::ldexp((float)wp->round, -wp->shift), (float)(bias + wp->offset)} : kNoWp;
-    rc = frac_lds_optin(ctx, wide ? 1 : 0, refine_had ? 1 : 0, wp ? 1 : 0);
+    const FracBuild build = {wide ? 1 : 0, refine_had ? 1 : 0, wp ? 1 : 0};
+    rc = frac_lds_optin(ctx, build);
     if (rc) return rc;
-    hipLaunchKernelGGL(frac_kernel(wide ? 1 : 0, refine_had ? 1 : 0, wp ? 1 : 0), dim3(1), dim3(hmme::frac_threads(bps)), hmme::frac_lds_bytes(bps), s, one_ref(ctx->d_call + kCallCtu),
+    hipLaunchKernelGGL(frac_kernel(build), dim3(1), dim3(hmme::frac_threads(bps)), hmme::frac_lds_bytes(bps), s, one_ref(ctx->d_call + kCallCtu),
                        64 * bps, one_ref(ref_base), kWinPitch, (const MeJob*)(ctx->d_call + kCallFracJob), kNoPrep, 1, (uint32_t*)nullptr, ctx->d_frac_cover, d_imv, ctx->lambda_q16,
                        p->bit_depth | ((bipred_origin && !wp) ? 0x100 : 0), fw, (int16_t*)(ctx->d_res + kResQmv), (uint32_t*)(ctx->d_res + kResCost));
     HIP_TRY(ctx, hipGetLastError());
@@ -1084,23 +1093,20 @@ int hmme_test_timeline16(void* out, size_t bytes) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(hmme::g_timeline16), bytes < sizeof(hmme::g_timeline16) ? bytes : sizeof(hmme::g_timeline16)) == hipSuccess ? HMME_OK : HMME_ERR_DEVICE;
 }
 #endif
-static int plan_tail8(int tail, int slots, int w, int tail_knob);
-static bool tail_one_launch(int head, int n_tail, int launches_knob);
-int hmme_test_tail_plan(int width, int height, int search_range, int n_pairs, int slots, int* out) {
-  if (!out || width < 8 || height < 8 || width > 16384 || height > 16384 || search_range < 1 || search_range > 64 || n_pairs < 1 || slots < 1) return HMME_ERR_ARG;
-  const int jobs = hmme_num_ctus(width, height) * n_pairs, tail = jobs % slots, w = 2 * search_range + 1;
-  const int wgs = plan_tail8(tail, slots, w, 0);
-  const int head = wgs > 0 ? jobs - tail : jobs;
-  out[0] = jobs; out[1] = head; out[2] = wgs; out[3] = (wgs > 0 && tail_one_launch(head, jobs - head, 0)) ? 1 : 0;
-  return HMME_OK;
-}
-
 int hmme_test_frac_deal(int k, int n_pairs, int width, int height) {
   if (n_pairs < 1 || width < 8 || height < 8 || width > 16384 || height > 16384) return -1;
   const int n_ctu = hmme_num_ctus(width, height);
   if (n_ctu > 0xffff || k < 0 || k >= n_pairs * n_ctu) return -1;
   const hmme::FracPrep prep = {nullptr, (uint32_t)n_ctu << 16, (uint32_t)width | (uint32_t)height << 16, 0};
   return hmme::me_frac_deal(k, n_pairs * n_ctu, prep);
+}
+
+int hmme_test_picture_job(int job, int ctu_first, int ctu_count, int pic_w, int pic_h, int sr, const int16_t* pred_q, const int16_t* center_q, int16_t* out) {
+  if (!out || job < 0 || pic_w < 8 || pic_h < 8 || pic_w > 16384 || pic_h > 16384 || sr < 1 || sr > 128) return HMME_ERR_ARG;
+  if (ctu_first < 0 || ctu_count < 1 || ctu_first + ctu_count > hmme_num_ctus(pic_w, pic_h)) return HMME_ERR_ARG;
+  const MeJob j = hmme::me_picture_job(job, pred_q, center_q, ctu_first, ctu_count, pic_w, pic_h, sr);
+  std::memcpy(out, &j, sizeof j);
+  return HMME_OK;
 }
 
 int hmme_abi_version(void) { return HMME_ABI_VERSION; }
@@ -1147,18 +1153,24 @@ int hmme_plane_set_device_u8(hmme_plane* pl, const void* d_src, int src_pitch, v
 //   16-bit: one launch; jobs [0, tail_first) are cut into n_strips strips, tail jobs into tail_parts (>= n_strips).
 // A launch of fewer jobs than slots is all tail (the small-picture split mode of round 1).  8-bit windows beyond 129 x 129 (four tiles
 // per job through the split kernel) are not re-planned.
+enum class SearchMode {
+  kWhole8,             // me_search_kernel<FEN, 0>: a workgroup per job, no tail plan
+  kTiles8,             // 8-bit windows beyond 129 x 129: four tile searches per job through me_search_kernel<FEN, 1>
+  kSegments8,          // head jobs whole and the tail's segments in ONE launch of me_search_kernel<FEN, 2>
+  kHeadThenSegments8,  // the head's whole jobs (<FEN, 0>), then the tail's segments (<FEN, 2>): HMME_TAIL_LAUNCHES=2, short tails
+  kStrips16            // me_search16_kernel: planes of more than 8 bits, or the u16 copies of a weighted search
+};
 struct FramePlan {
+  SearchMode mode = SearchMode::kWhole8;
   int jobs = 0;
-  int n_strips = 1;        // 16-bit: strips of a head job; 8-bit: 4 when tiled, else 1
-  int pdw = 0, strip_rows = 0;
+  int n_strips = 1, pdw = 0, strip_rows = 0;   // 16-bit: strips of a head job, the LDS window pitch, most candidate rows of a strip
   int tail_first = 0;      // == jobs: no tail
   int tail_parts = 1;      // 16-bit: strips of a tail job
   int tail_wgs = 0;        // 8-bit: workgroups (= segments) of the tail
-  bool one_launch = true;  // 8-bit with a tail: head and tail in one segment launch (else the head whole, then the tail's segments: HMME_TAIL_LAUNCHES=2)
-  bool tile8 = false;
-  bool wide = false;       // the 16-bit kernel runs the launch: planes of more than 8 bits, or the u16 copies of a weighted search
   int n_wg16 = 0;          // 16-bit: workgroups of the launch
-  size_t tail_jobs_off = 0;   // (8-bit segment launches: the table, me_seg_table_*, starts at ctx->d_jobs)
+  size_t table_bytes = 0, table_grow = 0;   // the job table in ctx->d_jobs, and what a table that has to grow grows to (kMaxRefs references of this picture size)
+  size_t tail_jobs_off = 0;   // kHeadThenSegments8: where the tail's segment table (me_seg_table_*) starts in it; the other tables start at ctx->d_jobs
+  bool first_strip = false;   // the launch decodes through ctx->d_first_strip (me_finalize16_kernel): every mode but kWhole8
 };
 
 // pieces per tail job that finish `tail` jobs soonest: rounds of `slots` workgroups, each as long as its piece of a whole job
@@ -1201,30 +1213,24 @@ static int plan_tail8(int tail, int slots, int w, int tail_knob) {
   if (tail_knob > 1) best_wgs = (int)std::max<long>(1, std::min<long>((long)tail * tail_knob, total));   // A/B: tail_knob workgroups per tail job
   return best_wgs;
 }
-// head and tail of an 8-bit launch as one segment launch?  (see prep_jobs)
+// head and tail of an 8-bit launch as one segment launch?  One launch lets the tail's segments start on the slots the head's short jobs (clipped
+// windows at the picture's edge) leave first, but sends the head's jobs through the merge table and its decode as well: worth it where the tail
+// is a good part of the launch (1440p, 408 tail jobs behind 512: +0.4 %; 2560 x 1088, 168: +0.5 %), not for a few jobs behind a full round
+// (1200p, 58: -3 %).  profiles/r06n_tail_one_or_two_launches.txt
 static bool tail_one_launch(int head, int n_tail, int launches_knob) { return launches_knob == 1 || (launches_knob != 2 && 3 * n_tail >= head); }
 
-// builds the device job table of a picture search against n_refs reference pictures on `s`; job index =
-// ref * count + ctu.  8-bit: MeJob[head jobs] (+ MeJob16[tail jobs * parts]); 8-bit tiled / 16-bit: MeJob16[workgroups]
-// d_center_q (16-bit tables only; null = the predictor): the windows' centres of a bi-prediction pass, laid out like d_pred_q
-static int prep_jobs(hmme_ctx* ctx, const hmme_plane* cur, const hmme_frame_params* fp, const void* d_pred_q, int first, int count,
-                     int n_refs, hipStream_t s, FramePlan* pl, bool force16 = false, const void* d_center_q = nullptr) {
-  const bool wide = fp->bit_depth > 8 || force16;   // force16: a weighted search of 8-bit planes (its u16 copies)
-  pl->wide = wide;
-  const int jobs = count * n_refs, slots = ctx->wg_slots, w = 2 * fp->search_range + 1;
-  pl->jobs = jobs;
-  pl->pdw = pick_pdw16(w);
-  pl->n_strips = 1;
-  pl->strip_rows = w;
-  pl->tile8 = !wide && fp->search_range > 64;   // window beyond 129 x 129: four tile searches per CTU, merged like split tasks
-  pl->tail_first = jobs; pl->tail_parts = 1;
-  static const int tail_knob = std::getenv("HMME_TAIL_PARTS") ? std::atoi(std::getenv("HMME_TAIL_PARTS")) : 0;   // A/B knob: 1 = no tail plan
-  const int tail = jobs % slots;
+// How `jobs` = CTUs x n_refs searches at `search_range` are launched on a chip of `slots` workgroup slots, and the size of their job
+// table.  wide: the 16-bit kernel runs them.  Pure arithmetic: no context, no device (hmme_test_tail_plan shows it to the CPU tests).
+static FramePlan plan_search(int jobs, int n_refs, int slots, int search_range, bool wide, const Knobs& knobs) {
+  FramePlan pl;
+  const int w = 2 * search_range + 1, tail = jobs % slots;
+  pl.jobs = pl.tail_first = jobs;
   if (wide) {   // strips of equal height for the full window (me_strip_rows16); clipped windows choose their own within n_strips
-    const int rmax = rows_max16(pl->pdw), n_min = strips_for(pl->pdw, w);
-    pl->strip_rows = rmax;
+    pl.mode = SearchMode::kStrips16;
+    pl.pdw = pick_pdw16(w);
+    const int rmax = pl.strip_rows = rows_max16(pl.pdw), n_min = strips_for(pl.pdw, w);
     const int h = hmme::me_strip_rows16(w, w, rmax, n_min + 4);   // up to four strips more than LDS alone needs
-    pl->n_strips = (w + h - 1) / h;
+    pl.n_strips = (w + h - 1) / h;
     // the workgroups beyond the last full round: head jobs give (jobs - tail) * n_strips of them, which need not fill whole rounds
     // either -- the tail is planned on what is left of the last head round
     const int lanes = (((w + 1) >> 1) + 2) / 3;
@@ -1232,40 +1238,62 @@ static int prep_jobs(hmme_ctx* ctx, const hmme_plane* cur, const hmme_frame_para
       const int hk = (w + k - 1) / k;
       return 2.0 * ((((hk * lanes + 63) >> 6) + 3) >> 2) + 1.0;
     };
-    if (tail && tail_knob != 1) {
+    if (tail && knobs.tail_parts != 1) {
       const int k_max = std::min(w / 4, 64);
-      int k = tail_knob > 1 ? std::min(tail_knob, k_max) : plan_tail(tail, slots, pl->n_strips, k_max, strip_cost);
-      if (k < pl->n_strips) k = pl->n_strips;
-      if (k > pl->n_strips) { pl->tail_first = jobs - tail; pl->tail_parts = k; }
+      int k = knobs.tail_parts > 1 ? std::min(knobs.tail_parts, k_max) : plan_tail(tail, slots, pl.n_strips, k_max, strip_cost);
+      if (k < pl.n_strips) k = pl.n_strips;
+      if (k > pl.n_strips) { pl.tail_first = jobs - tail; pl.tail_parts = k; }
     }
-    pl->n_wg16 = pl->tail_first * pl->n_strips + (jobs - pl->tail_first) * pl->tail_parts;
-  } else if (pl->tile8) {
-    pl->n_strips = 4;
-  } else if (tail && tail_knob != 1) {
-    const int wgs = plan_tail8(tail, slots, w, tail_knob);
-    if (wgs > 0) { pl->tail_first = jobs - tail; pl->tail_wgs = wgs; }
+    pl.n_wg16 = pl.tail_first * pl.n_strips + (jobs - pl.tail_first) * pl.tail_parts;
+    pl.table_bytes = sizeof(MeJob16) * (size_t)pl.n_wg16;
+  } else if (search_range > 64) {   // window beyond 129 x 129: four tile searches per CTU, merged like split tasks
+    pl.mode = SearchMode::kTiles8;
+    pl.table_bytes = sizeof(MeJob16) * (size_t)jobs * 4;
+  } else {
+    const int wgs = tail && knobs.tail_parts != 1 ? plan_tail8(tail, slots, w, knobs.tail_parts) : 0;
+    if (wgs > 0) { pl.tail_first = jobs - tail; pl.tail_wgs = wgs; }
+    const int head = pl.tail_first, n_tail = jobs - head;
+    if (!n_tail) {
+      pl.table_bytes = sizeof(MeJob) * (size_t)head;
+    } else if (tail_one_launch(head, n_tail, knobs.tail_launches)) {
+      pl.mode = SearchMode::kSegments8;
+      pl.table_bytes = hmme::me_seg_table_bytes(head + wgs, jobs);
+    } else {
+      pl.mode = SearchMode::kHeadThenSegments8;
+      pl.tail_jobs_off = (sizeof(MeJob) * (size_t)head + 255) & ~(size_t)255;
+      pl.table_bytes = pl.tail_jobs_off + hmme::me_seg_table_bytes(wgs, n_tail);
+    }
   }
-  const int head = pl->tail_first, n_tail = jobs - head;
-  size_t need;
-  if (wide) need = sizeof(MeJob16) * (size_t)pl->n_wg16;
-  else if (pl->tile8) need = sizeof(MeJob16) * (size_t)jobs * 4;
-  else {
-    // One launch lets the tail's segments start on the slots the head's short jobs (clipped windows at the picture's edge) leave first, but sends
-    // the head's jobs through the merge table and its decode as well: worth it where the tail is a good part of the launch (1440p, 408 tail
-    // jobs behind 512: +0.4 %; 2560 x 1088, 168: +0.5 %), not for a few jobs behind a full round (1200p, 58: -3 %).  profiles/r06n_tail_one_or_two_launches.txt
-    static const int launches_knob = std::getenv("HMME_TAIL_LAUNCHES") ? std::atoi(std::getenv("HMME_TAIL_LAUNCHES")) : 0;   // A/B knob: 1 | 2
-    pl->one_launch = tail_one_launch(head, n_tail, launches_knob);
-    pl->tail_jobs_off = pl->one_launch ? 0 : (sizeof(MeJob) * (size_t)head + 255) & ~(size_t)255;
-    need = !n_tail ? sizeof(MeJob) * (size_t)head
-         : pl->one_launch ? hmme::me_seg_table_bytes(head + pl->tail_wgs, jobs) : pl->tail_jobs_off + hmme::me_seg_table_bytes(pl->tail_wgs, n_tail);
-  }
+  pl.first_strip = pl.mode != SearchMode::kWhole8;
+  const size_t per_ref = n_refs > 0 ? (pl.table_bytes + n_refs - 1) / n_refs : pl.table_bytes;
+  pl.table_grow = per_ref * hmme::kMaxRefs + 4096;
+  return pl;
+}
+// the plan of a launch of the context: force16 = a weighted search of 8-bit planes (its u16 copies)
+static FramePlan plan_launch(const hmme_ctx* ctx, const hmme_frame_params* fp, int count, int n_refs, bool force16 = false) {
+  return plan_search(count * n_refs, n_refs, ctx->wg_slots, fp->search_range, fp->bit_depth > 8 || force16, knobs());
+}
+
+int hmme_test_tail_plan(int width, int height, int search_range, int n_pairs, int slots, int* out) {
+  if (!out || width < 8 || height < 8 || width > 16384 || height > 16384 || search_range < 1 || search_range > 64 || n_pairs < 1 || slots < 1) return HMME_ERR_ARG;
+  const FramePlan pl = plan_search(hmme_num_ctus(width, height) * n_pairs, n_pairs, slots, search_range, false, Knobs{});
+  out[0] = pl.jobs; out[1] = pl.tail_first; out[2] = pl.tail_wgs; out[3] = pl.mode == SearchMode::kSegments8 ? 1 : 0;
+  return HMME_OK;
+}
+
+// writes the device job table of plan `pl` -- a picture search over CTUs [first, first + count) against n_refs reference pictures -- on `s`;
+// job index = ref * count + ctu.  kWhole8: MeJob[jobs]; kHeadThenSegments8: MeJob[head], then the tail's segment table; kSegments8: one
+// segment table; kTiles8 / kStrips16: MeJob16[workgroups].  A table without predictors or centres that the launch before left is kept.
+// d_center_q (16-bit tables only; null = the predictor): the windows' centres of a bi-prediction pass, laid out like d_pred_q
+static int prep_jobs(hmme_ctx* ctx, const hmme_plane* cur, const hmme_frame_params* fp, const void* d_pred_q, int first, int count,
+                     int n_refs, hipStream_t s, const FramePlan& pl, const void* d_center_q = nullptr) {
+  const int jobs = pl.jobs, head = pl.tail_first, n_tail = jobs - head, w = cur->width, h = cur->height, sr = fp->search_range;
   size_t cap = ctx->jobs_bytes;
-  const size_t per_ref = n_refs > 0 ? (need + n_refs - 1) / n_refs : need;   // what kMaxRefs pairs of this picture size would ask for
-  int rc = ensure(ctx, (uint8_t**)&ctx->d_jobs, &cap, need, per_ref * hmme::kMaxRefs + 4096);
+  int rc = ensure(ctx, (uint8_t**)&ctx->d_jobs, &cap, pl.table_bytes, pl.table_grow);
   if (cap != ctx->jobs_bytes) ctx->jobs_tag.valid = false;   // reallocated: whatever the table was, it is gone
   ctx->jobs_bytes = cap;
   if (rc) return rc;
-  if (wide || pl->tile8 || n_tail) {
+  if (pl.first_strip) {
     size_t fcap = (size_t)ctx->first_strip_cap * sizeof(int);
     const size_t fcap0 = fcap;
     rc = ensure(ctx, &ctx->d_first_strip, &fcap, sizeof(int) * (size_t)jobs, sizeof(int) * (size_t)(jobs / (n_refs > 0 ? n_refs : 1) + 1) * hmme::kMaxRefs);
@@ -1275,33 +1303,37 @@ static int prep_jobs(hmme_ctx* ctx, const hmme_plane* cur, const hmme_frame_para
   }
   hmme_ctx::TableTag tag;
   tag.valid = !d_pred_q && !d_center_q;
-  tag.w = cur->width; tag.h = cur->height; tag.bit_depth = fp->bit_depth | (wide && fp->bit_depth == 8 ? 0x100 : 0); tag.sr = fp->search_range; tag.first = first; tag.count = count; tag.pairs = n_refs;
-  tag.buf = ctx->d_jobs; tag.buf2 = (wide || pl->tile8 || n_tail) ? ctx->d_first_strip : nullptr; tag.stream = (void*)s;
+  tag.w = w; tag.h = h; tag.sr = sr; tag.first = first; tag.count = count; tag.pairs = n_refs;
+  tag.bit_depth = fp->bit_depth | (pl.mode == SearchMode::kStrips16 && fp->bit_depth == 8 ? 0x100 : 0);   // 0x100: the 16-bit table of 8-bit planes (weighted search)
+  tag.buf = ctx->d_jobs; tag.buf2 = pl.first_strip ? ctx->d_first_strip : nullptr; tag.stream = (void*)s;
   if (tag.same(ctx->jobs_tag)) return HMME_OK;   // the table of the launch before is this launch's table
   ctx->jobs_tag.valid = false;
   const dim3 block(256);
-  auto grid = [](int n) { return dim3((n + 255) / 256); };
-  if (pl->tile8)
-    hipLaunchKernelGGL(hmme::me_prep_jobs_tile_kernel, grid(jobs), block, 0, s, (MeJob16*)ctx->d_jobs, ctx->d_first_strip,
-                       (const int16_t*)d_pred_q, first, count, n_refs, cur->width, cur->height, fp->search_range);
-  else if (wide)
-    hipLaunchKernelGGL(hmme::me_prep_jobs16_kernel, grid(jobs), block, 0, s, (MeJob16*)ctx->d_jobs, ctx->d_first_strip,
-                       (const int16_t*)d_pred_q, first, count, n_refs, cur->width, cur->height, fp->search_range, pl->n_strips, pl->strip_rows,
-                       pl->tail_first, pl->tail_parts, (const int16_t*)d_center_q);
-  else {
-    if (!n_tail || !pl->one_launch) {
-      if (head)
-        hipLaunchKernelGGL(hmme::me_prep_jobs_kernel, grid(head), block, 0, s, (MeJob*)ctx->d_jobs, (const int16_t*)d_pred_q, first, count,
-                           n_refs, cur->width, cur->height, fp->search_range, 0, head, 1, (uint32_t*)nullptr, (const int16_t*)nullptr);
+  const auto grid = [](int n) { return dim3((n + 255) / 256); };
+  const int16_t* pred = (const int16_t*)d_pred_q;
+  switch (pl.mode) {
+    case SearchMode::kTiles8:
+      hipLaunchKernelGGL(hmme::me_prep_jobs_tile_kernel, grid(jobs), block, 0, s, (MeJob16*)ctx->d_jobs, ctx->d_first_strip, pred, first, count, n_refs, w, h, sr);
+      break;
+    case SearchMode::kStrips16:
+      hipLaunchKernelGGL(hmme::me_prep_jobs16_kernel, grid(jobs), block, 0, s, (MeJob16*)ctx->d_jobs, ctx->d_first_strip, pred, first, count, n_refs, w, h, sr,
+                         pl.n_strips, pl.strip_rows, pl.tail_first, pl.tail_parts, (const int16_t*)d_center_q);
+      break;
+    case SearchMode::kWhole8:
+    case SearchMode::kSegments8:
+    case SearchMode::kHeadThenSegments8: {
+      // kSegments8: one segment table for the whole launch, the head's jobs its entries / workgroups 0 .. head - 1; else the head's MeJobs, then a table of the tail alone
+      const int idx0 = pl.mode == SearchMode::kSegments8 ? head : 0;
+      if (head && idx0)
+        hipLaunchKernelGGL(hmme::me_prep_whole_segments_kernel, grid(head), block, 0, s, ctx->d_jobs, ctx->d_first_strip, pred, first, count, n_refs, w, h, sr,
+                           head + pl.tail_wgs, head);
+      else if (head)
+        hipLaunchKernelGGL(hmme::me_prep_jobs_kernel, grid(head), block, 0, s, (MeJob*)ctx->d_jobs, pred, first, count, n_refs, w, h, sr, 0, head, 1,
+                           (uint32_t*)nullptr, (const int16_t*)nullptr);
       if (n_tail)
-        hipLaunchKernelGGL(hmme::me_prep_segments_kernel, dim3(1), dim3(hmme::kSegPrepThreads), 0, s, (void*)((uint8_t*)ctx->d_jobs + pl->tail_jobs_off), ctx->d_first_strip,
-                           (const int16_t*)d_pred_q, first, count, n_refs, cur->width, cur->height, fp->search_range, pl->tail_wgs, head, n_tail, 0);
-    } else {   // one segment table for the whole launch: the head's jobs whole, then the tail's segments
-      if (head)
-        hipLaunchKernelGGL(hmme::me_prep_whole_segments_kernel, grid(head), block, 0, s, ctx->d_jobs, ctx->d_first_strip, (const int16_t*)d_pred_q, first, count,
-                           n_refs, cur->width, cur->height, fp->search_range, head + pl->tail_wgs, head);
-      hipLaunchKernelGGL(hmme::me_prep_segments_kernel, dim3(1), dim3(hmme::kSegPrepThreads), 0, s, ctx->d_jobs, ctx->d_first_strip,
-                         (const int16_t*)d_pred_q, first, count, n_refs, cur->width, cur->height, fp->search_range, head + pl->tail_wgs, head, n_tail, head);
+        hipLaunchKernelGGL(hmme::me_prep_segments_kernel, dim3(1), dim3(hmme::kSegPrepThreads), 0, s, (void*)((uint8_t*)ctx->d_jobs + pl.tail_jobs_off), ctx->d_first_strip,
+                           pred, first, count, n_refs, w, h, sr, idx0 + pl.tail_wgs, head, n_tail, idx0);
+      break;
     }
   }
   HIP_TRY(ctx, hipGetLastError());
@@ -1312,20 +1344,26 @@ static int prep_jobs(hmme_ctx* ctx, const hmme_plane* cur, const hmme_frame_para
 // curs: the CTU-blocked copies of the current pictures (hmme_plane::d_blocks), cur_ctus_x their blocks per block row
 static int run_search(hmme_ctx* ctx, const RefSet& curs, int cur_ctus_x, const RefSet& refs, int ref_pitch, const hmme_frame_params* fp, const FramePlan& pl,
                       int16_t* d_mv, uint32_t* d_sad, hipStream_t s) {
-  if (pl.wide)
-    return launch_search16(ctx, curs, cur_ctus_x, refs, ref_pitch, (const MeJob16*)ctx->d_jobs, ctx->d_first_strip, pl.jobs, pl.n_wg16,
-                           pl.pdw, pl.strip_rows, fp->fen, fp->bit_depth, d_mv, d_sad, s);
-  if (pl.tile8)
-    return launch_search8_split(ctx, curs, cur_ctus_x, refs, ref_pitch, (const MeJob16*)ctx->d_jobs, ctx->d_first_strip, pl.jobs, 4,
-                                fp->fen, d_mv, d_sad, s);
   const int head = pl.tail_first, n_tail = pl.jobs - head;
-  if (!n_tail) return launch_search8(ctx, curs, cur_ctus_x, refs, ref_pitch, (const MeJob*)ctx->d_jobs, head, fp->fen, d_mv, d_sad, s);
+  const bool one_launch = pl.mode == SearchMode::kSegments8;
+  switch (pl.mode) {
+    case SearchMode::kStrips16:
+      return launch_search16(ctx, curs, cur_ctus_x, refs, ref_pitch, (const MeJob16*)ctx->d_jobs, ctx->d_first_strip, pl.jobs, pl.n_wg16,
+                             pl.pdw, pl.strip_rows, fp->fen, fp->bit_depth, d_mv, d_sad, s);
+    case SearchMode::kTiles8:
+      return launch_search8_split(ctx, curs, cur_ctus_x, refs, ref_pitch, (const MeJob16*)ctx->d_jobs, ctx->d_first_strip, pl.jobs, 4,
+                                  fp->fen, d_mv, d_sad, s);
+    case SearchMode::kWhole8:
+      return launch_search8<0>(ctx, curs, cur_ctus_x, refs, ref_pitch, ctx->d_jobs, head, fp->fen, d_mv, d_sad, nullptr, 0, s);
+    case SearchMode::kSegments8:
+    case SearchMode::kHeadThenSegments8: break;
+  }
   unsigned long long* best = nullptr;
-  int rc = merge_table(ctx, pl.one_launch ? pl.jobs : n_tail, nullptr, s, &best);   // (preset, if it has to be, before the head runs, not between the two)
+  int rc = merge_table(ctx, one_launch ? pl.jobs : n_tail, nullptr, s, &best);   // (preset, if it has to be, before the head runs, not between the two)
   if (rc) return rc;
-  if (pl.one_launch)
+  if (one_launch)
     return launch_search8_segments(ctx, curs, cur_ctus_x, refs, ref_pitch, ctx->d_jobs, ctx->d_first_strip, pl.jobs, head + pl.tail_wgs, fp->fen, d_mv, d_sad, s, best);
-  rc = launch_search8(ctx, curs, cur_ctus_x, refs, ref_pitch, (const MeJob*)ctx->d_jobs, head, fp->fen, d_mv, d_sad, s);
+  rc = launch_search8<0>(ctx, curs, cur_ctus_x, refs, ref_pitch, ctx->d_jobs, head, fp->fen, d_mv, d_sad, nullptr, 0, s);
   if (rc) return rc;
   return launch_search8_segments(ctx, curs, cur_ctus_x, refs, ref_pitch, (const uint8_t*)ctx->d_jobs + pl.tail_jobs_off, ctx->d_first_strip, n_tail, pl.tail_wgs,
                                  fp->fen, d_mv + (size_t)head * 2 * HMME_NUM_CTU_PARTS, d_sad + (size_t)head * HMME_NUM_CTU_PARTS, s, best);
@@ -1389,8 +1427,8 @@ int hmme_search_pairs_device(hmme_ctx* ctx, const hmme_plane* const* curs, const
   PairLaunch pl;
   int rc = pairs_begin(ctx, curs, refs, n_pairs, fp, s, &pl);
   if (rc || pl.count == 0) return rc;
-  FramePlan plan;
-  rc = prep_jobs(ctx, curs[0], fp, d_pred_q, pl.first, pl.count, n_pairs, s, &plan);
+  const FramePlan plan = plan_launch(ctx, fp, pl.count, n_pairs);
+  rc = prep_jobs(ctx, curs[0], fp, d_pred_q, pl.first, pl.count, n_pairs, s, plan);
   if (rc == HMME_OK) rc = run_search(ctx, pl.cur_blocks, curs[0]->ctus_x, pl.refs, refs[0]->pitch, fp, plan, (int16_t*)d_out_mv, (uint32_t*)d_out_sad, s);
   return pairs_end(ctx, curs, refs, n_pairs, s, rc);
 }
@@ -1513,7 +1551,7 @@ enum class FracTable { kReuse, kAsNeeded, kAlways };
 struct RefineLaunch {
   RefSet curs, refs;   // one entry per pair of THIS launch
   int cur_pitch = 0, ref_pitch = 0;
-  int wide = 0, had = 0, wp = 0;   // the build: frac_kernel(wide, had, wp)
+  FracBuild build;
   hmme::FracWp fw = kNoWp;
   const int16_t* d_pred = nullptr;     // [pairs][CTUs of the picture][2], null = zero predictors
   const int16_t* d_center = nullptr;   // window centres, same layout; null = the predictors
@@ -1526,7 +1564,7 @@ struct RefineLaunch {
 // what every picture-level refinement takes from its arguments; the caller adds the planes, the build and the predictors
 void refine_common(RefineLaunch& L, const PairLaunch& pl, const hmme_plane* cur, const hmme_frame_params* fp, int use_hadamard, const void* d_int_mv,
                    void* d_out_qmv, void* d_out_cost) {
-  L.had = use_hadamard ? 1 : 0;
+  L.build.had = use_hadamard ? 1 : 0;
   L.first = pl.first; L.count = pl.count; L.width = cur->width; L.height = cur->height; L.search_range = fp->search_range; L.bit_depth = fp->bit_depth;
   L.d_int_mv = (const int16_t*)d_int_mv; L.d_qmv = (int16_t*)d_out_qmv; L.d_cost = (uint32_t*)d_out_cost;
 }
@@ -1543,15 +1581,14 @@ int launch_refine(hmme_ctx* ctx, const RefineLaunch& L, hipStream_t s) {
   ctx->frac_jobs_bytes = cap;
   if (rc) return rc;
   uint32_t* counter = (uint32_t*)((uint8_t*)ctx->d_frac_jobs + ((sizeof(MeJob) * (size_t)jobs + 15) & ~(size_t)15));
-  const int grid = frac_grid(ctx, L.wide, L.had, L.wp, jobs);
+  const int grid = frac_grid(ctx, L.build, jobs);
   // one workgroup per job (the default) on the two-wave builds: every workgroup derives its job itself (FracPrep) -- no job table, no
   // launch in front of this one (1080p: 0.095 -> 0.090 ms).  A table is read by the job-walking launch of HMME_FRAC_GRID (its prep
   // kernel is also what resets the job counter: every launch), under the A/B knob HMME_FRAC_JOB_TABLE (the job table and its kernel as
   // before), by CTU ranges FracPrep cannot pack and by launches with window centres (FracPrep derives windows from predictors only)
-  static const bool table_forced = std::getenv("HMME_FRAC_JOB_TABLE") != nullptr;
   const bool walk = grid < jobs;
   const bool packable = L.count <= 0xffff && L.first <= 0xffff;   // FracPrep packs the CTU range into 16 + 16 bits (a 16384 x 16384 picture has 65 536 CTUs)
-  const bool need_table = L.table == FracTable::kAlways || walk || table_forced || !packable || L.d_center;
+  const bool need_table = L.table == FracTable::kAlways || walk || knobs().frac_job_table || !packable || L.d_center;
   if (need_table) {
     hmme_ctx::TableTag tag;
     tag.valid = L.table == FracTable::kReuse && !L.d_pred && !L.d_center && !walk;
@@ -1563,7 +1600,7 @@ int launch_refine(hmme_ctx* ctx, const RefineLaunch& L, hipStream_t s) {
                          L.width, L.height, L.search_range, 0, jobs, 0, counter, L.d_center);
     }
   }
-  rc = frac_lds_optin(ctx, L.wide, L.had, L.wp);
+  rc = frac_lds_optin(ctx, L.build);
   if (rc) return rc;
   // prep: the job of a workgroup without a table (a table carries the predictors itself) and the order the jobs are dealt in
   // (me_frac_deal).  A CTU range beyond 16 + 16 bits gets kNoPrep and with it the plain last-first order.  That is the order such a
@@ -1572,7 +1609,7 @@ int launch_refine(hmme_ctx* ctx, const RefineLaunch& L, hipStream_t s) {
   const hmme::FracPrep prep = packable ? hmme::FracPrep{need_table ? nullptr : L.d_pred, (uint32_t)L.first | (uint32_t)L.count << 16,
                                                         (uint32_t)L.width | (uint32_t)L.height << 16, L.search_range}
                                        : kNoPrep;
-  hipLaunchKernelGGL(frac_kernel(L.wide, L.had, L.wp), dim3(grid), dim3(hmme::frac_threads(L.wide ? 2 : 1)), hmme::frac_lds_bytes(L.wide ? 2 : 1), s, L.curs,
+  hipLaunchKernelGGL(frac_kernel(L.build), dim3(grid), dim3(hmme::frac_threads(L.build.bps())), hmme::frac_lds_bytes(L.build.bps()), s, L.curs,
                      L.cur_pitch, L.refs, L.ref_pitch, need_table ? (const MeJob*)ctx->d_frac_jobs : (const MeJob*)nullptr, prep, jobs,
                      walk ? counter : (uint32_t*)nullptr, ctx->d_frac_cover, L.d_int_mv, ctx->lambda_q16, L.bit_depth, L.fw, L.d_qmv, L.d_cost);
   const hipError_t e = hipGetLastError();
@@ -1592,7 +1629,7 @@ int hmme_refine_pairs_device(hmme_ctx* ctx, const hmme_plane* const* curs, const
   RefineLaunch L;
   refine_common(L, pl, curs[0], fp, use_hadamard, d_int_mv, d_out_qmv, d_out_cost);
   L.curs = pl.curs; L.refs = pl.refs; L.cur_pitch = curs[0]->pitch; L.ref_pitch = refs[0]->pitch;
-  L.wide = curs[0]->bps == 2 ? 1 : 0;
+  L.build.wide = curs[0]->bps == 2 ? 1 : 0;
   L.d_pred = (const int16_t*)d_pred_q; L.pairs = n_pairs;
   L.table = FracTable::kReuse;
   return pairs_end(ctx, curs, refs, n_pairs, s, launch_refine(ctx, L, s));
@@ -1781,8 +1818,8 @@ int hmme_search_pairs_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, con
     if (curs[r]->bps == 2 && info[r].bias == 0) wcurs.base[r] = curs[r]->d_blocks;   // the plane's own blocks serve
     else rc = cached_copy(ctx, wcur, g, r, CopyKey{curs[r], 1, 0, 0, info[r].bias}, s, &wcurs.base[r]);
   }
-  FramePlan plan;
-  if (rc == HMME_OK) rc = prep_jobs(ctx, curs[0], &f, d_pred_q, pl.first, pl.count, n_pairs, s, &plan, true);
+  const FramePlan plan = plan_launch(ctx, &f, pl.count, n_pairs, true);
+  if (rc == HMME_OK) rc = prep_jobs(ctx, curs[0], &f, d_pred_q, pl.first, pl.count, n_pairs, s, plan);
   if (rc == HMME_OK) rc = run_search(ctx, wcurs, curs[0]->ctus_x, wrefs, g.pitch, &f, plan, (int16_t*)d_out_mv, (uint32_t*)d_out_sad, s);
   return pairs_end(ctx, curs, refs, n_pairs, s, rc);
 }
@@ -1846,7 +1883,7 @@ int hmme_refine_pairs_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, con
     refine_common(L, pl, curs[0], fp, use_hadamard, (const int16_t*)d_int_mv + 2 * res0, (int16_t*)d_out_qmv + 2 * res0, (uint32_t*)d_out_cost + res0);
     L.curs = c; L.refs = rf;
     L.cur_pitch = ident ? curs[0]->pitch : g.pitch; L.ref_pitch = ident ? refs[0]->pitch : g.pitch;   // (a u16 plane's own pitch is g.pitch)
-    L.wide = wide; L.wp = ident ? 0 : 1;
+    L.build.wide = wide; L.build.wp = ident ? 0 : 1;
     if (!ident) L.fw = hmme::FracWp{std::ldexp((float)w.w0, -w.shift), std::ldexp((float)w.round, -w.shift), (float)(info[a].bias + w.offset)};
     L.d_pred = d_pred_q ? (const int16_t*)d_pred_q + (size_t)a * n_ctu * 2 : nullptr; L.pairs = b - a;
     rc = launch_refine(ctx, L, s);
@@ -2310,8 +2347,8 @@ int bi_search(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* co
                         hmme::kBlkBytes16, (long)ctus_x * hmme::kBlkBytes16, 128, s, bw[r].other_identity ? nullptr : &bw[r].pw);
     wcurs.base[r] = blocks;
   }
-  FramePlan plan;
-  if (rc == HMME_OK) rc = prep_jobs(ctx, curs[0], fp, d_pred_q, pl.first, pl.count, n_pairs, s, &plan, true, d_center_q);
+  const FramePlan plan = plan_launch(ctx, fp, pl.count, n_pairs, true);
+  if (rc == HMME_OK) rc = prep_jobs(ctx, curs[0], fp, d_pred_q, pl.first, pl.count, n_pairs, s, plan, d_center_q);
   if (rc == HMME_OK) rc = run_search(ctx, wcurs, ctus_x, wrefs, g.pitch, fp, plan, (int16_t*)d_out_mv, (uint32_t*)d_out_sad, s);
   return pairs_end(ctx, curs, refs, n_pairs, s, rc, others);
 }
@@ -2355,7 +2392,7 @@ int bi_refine(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* co
     RefineLaunch L;
     refine_common(L, pl, curs[0], fp, use_hadamard, (const int16_t*)d_int_mv + 2 * res0, (int16_t*)d_out_qmv + 2 * res0, (uint32_t*)d_out_cost + res0);
     L.curs = ca; L.refs = ra; L.cur_pitch = g.pitch; L.ref_pitch = g.pitch;
-    L.wide = 1; L.wp = 1;
+    L.build.wide = 1; L.build.wp = 1;
     // org_sub takes the origin's bias off, with the weight's offset; without explicit weights (and for an identity weight) the weight is 1
     if (wps && !bw[a].info.identity)
       L.fw = hmme::FracWp{std::ldexp((float)wps[a].w0, -wps[a].shift), std::ldexp((float)wps[a].round, -wps[a].shift), (float)(bw[a].info.bias + wps[a].offset)};
@@ -3314,8 +3351,8 @@ int hmme_test_time_search_kernel(hmme_ctx* ctx, const hmme_plane* cur, const hmm
   rc = pairs_begin(ctx, &cur, &ref, 1, fp, s, &pl);
   if (rc || pl.count == 0) return rc;
   // job table once (it is not part of the timed kernel), then `reps` launches of the search kernel(s) alone
-  FramePlan plan;
-  rc = prep_jobs(ctx, cur, fp, d_pred_q, first, count, 1, s, &plan);
+  const FramePlan plan = plan_launch(ctx, fp, count, 1);
+  rc = prep_jobs(ctx, cur, fp, d_pred_q, first, count, 1, s, plan);
   if (rc == HMME_OK)
     rc = time_reps(ctx, s, reps, "the search kernel", [&] {
       return run_search(ctx, pl.cur_blocks, cur->ctus_x, pl.refs, ref->pitch, fp, plan, (int16_t*)d_out_mv, (uint32_t*)d_out_sad, s);

@@ -637,9 +637,37 @@ __host__ __device__ inline void set_search_range(int pred_x, int pred_y, int sr,
   lt_x = ltx >> 2; lt_y = lty >> 2; rb_x = rbx >> 2; rb_y = rby >> 2;
 }
 
-// one job per CTU of the picture from the per-CTU predictors
-// job i = reference (i / ctu_count), CTU ctu_first + (i % ctu_count); pred_q is [n_refs][n_ctu][2]
-// jobs [job0, job0 + n_jobs) of the ctu_count * n_refs (CTU, reference) searches of a launch; jobs[] is indexed from job0
+// The MeJob of job i of a launch over CTUs [ctu_first, ctu_first + ctu_count) of a picture and its references: reference r = i / ctu_count
+// (packed into the low six bits of ctu_x, whose CTU origins are multiples of 64), CTU ctu_first + i % ctu_count.  pred_q and center_q are
+// [n_refs][CTUs of the picture][2], quarter pels.  Null pred_q: zero predictors.  center_q: the window's centre where it is not the
+// predictor -- HM's bi-prediction pass searches around the list's current MV and prices MV bits against the AMVP predictor
+// (TEncSearch.cpp:3726-3737); null: the predictor.  Every job table and the table-less refinement launch take their jobs from here.
+__host__ __device__ __forceinline__ MeJob me_picture_job(int i, const int16_t* __restrict__ pred_q, const int16_t* __restrict__ center_q,
+                                                         int ctu_first, int ctu_count, int pic_w, int pic_h, int sr) {
+  const int r = i / ctu_count;
+  const int ctus_x = (pic_w + 63) >> 6, n_ctu = ctus_x * ((pic_h + 63) >> 6);
+  const int ctu = ctu_first + (i - r * ctu_count);
+  const int cu_x = (ctu % ctus_x) * 64, cu_y = (ctu / ctus_x) * 64;
+  const long pq = 2 * ((long)r * n_ctu + ctu);
+  const int px = pred_q ? pred_q[pq] : 0, py = pred_q ? pred_q[pq + 1] : 0;
+  const int wx_q = center_q ? center_q[pq] : px, wy_q = center_q ? center_q[pq + 1] : py;
+  int ltx, lty, rbx, rby;
+  set_search_range(wx_q, wy_q, sr, cu_x, cu_y, pic_w, pic_h, ltx, lty, rbx, rby);
+  MeJob j;
+  j.ctu_x = (int16_t)(cu_x | r); j.ctu_y = (int16_t)cu_y;
+  j.lt_x = (int16_t)ltx; j.lt_y = (int16_t)lty; j.rb_x = (int16_t)rbx; j.rb_y = (int16_t)rby;
+  j.pred_x = (int16_t)px; j.pred_y = (int16_t)py;
+  return j;
+}
+// tile (tx, ty) of a window beyond 129 x 129 candidates: the sub-window of step kTileStep, clipped to the job's right-bottom
+__host__ __device__ inline MeJob me_tile_job(MeJob job, int tx, int ty) {
+  const int x1 = job.lt_x + (tx + 1) * kTileStep - 1, y1 = job.lt_y + (ty + 1) * kTileStep - 1;
+  job.lt_x = (int16_t)(job.lt_x + tx * kTileStep); job.lt_y = (int16_t)(job.lt_y + ty * kTileStep);
+  job.rb_x = (int16_t)(x1 < job.rb_x ? x1 : job.rb_x); job.rb_y = (int16_t)(y1 < job.rb_y ? y1 : job.rb_y);
+  return job;
+}
+
+// one MeJob per (CTU, reference) search: jobs [job0, job0 + n_jobs) of the launch (me_picture_job); jobs[] is indexed from job0
 // xcd_order: jobs[] is written in the XCD-aware order of me_search_kernel<FEN, 0> (position li holds job job0 + me_xcd_unit(li, n_jobs));
 // 0 for the refinement kernel, which takes job blockIdx.x
 // job_counter (may be null): the refinement kernel's work counter, reset here for the launch that follows on the same stream
@@ -650,21 +678,7 @@ __global__ void me_prep_jobs_kernel(MeJob* jobs, const int16_t* __restrict__ pre
   if (li == 0 && job_counter) *job_counter = 0;
   if (li >= n_jobs) return;
   const int i = job0 + (xcd_order ? me_xcd_unit(li, n_jobs) : li);
-  const int r = i / ctu_count;
-  const int ctus_x = (pic_w + 63) >> 6, n_ctu = ctus_x * ((pic_h + 63) >> 6);
-  const int ctu = ctu_first + (i - r * ctu_count);
-  const int cu_x = (ctu % ctus_x) * 64, cu_y = (ctu / ctus_x) * 64;
-  const long pq = 2 * ((long)r * n_ctu + ctu);
-  const int px = pred_q ? pred_q[pq] : 0, py = pred_q ? pred_q[pq + 1] : 0;
-  // center_q (null = the predictor): the window's centre of a bi-prediction pass, as in me_prep_jobs16_kernel (the refinement's job table)
-  const int wx_q = center_q ? center_q[pq] : px, wy_q = center_q ? center_q[pq + 1] : py;
-  int ltx, lty, rbx, rby;
-  set_search_range(wx_q, wy_q, sr, cu_x, cu_y, pic_w, pic_h, ltx, lty, rbx, rby);
-  MeJob j;
-  j.ctu_x = (int16_t)(cu_x | r); j.ctu_y = (int16_t)cu_y;
-  j.lt_x = (int16_t)ltx; j.lt_y = (int16_t)lty; j.rb_x = (int16_t)rbx; j.rb_y = (int16_t)rby;
-  j.pred_x = (int16_t)px; j.pred_y = (int16_t)py;
-  jobs[li] = j;
+  jobs[li] = me_picture_job(i, pred_q, center_q, ctu_first, ctu_count, pic_w, pic_h, sr);
 }
 
 // picture area (int16 Pel, u16 or u8; pitch in elements) -> padded u8 / u16 plane, borders edge-replicated like
@@ -993,22 +1007,8 @@ __global__ void me_prep_jobs16_kernel(MeJob16* jobs, int* first_strip_of_job, co
                                       int tail_first, int tail_strips, const int16_t* __restrict__ center_q) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= ctu_count * n_refs) return;
-  const int r = i / ctu_count;
-  const int ctus_x = (pic_w + 63) >> 6, n_ctu = ctus_x * ((pic_h + 63) >> 6);
-  const int ctu = ctu_first + (i - r * ctu_count);
-  const int cu_x = (ctu % ctus_x) * 64, cu_y = (ctu / ctus_x) * 64;
-  const long pq = 2 * ((long)r * n_ctu + ctu);
-  const int px = pred_q ? pred_q[pq] : 0, py = pred_q ? pred_q[pq + 1] : 0;
-  // center_q (same layout as pred_q; null = the predictor): the window's centre where it is not the predictor -- HM's bi-prediction pass
-  // searches around the list's current MV and prices MV bits against the AMVP predictor (TEncSearch.cpp:3726-3737)
-  const int wx_q = center_q ? center_q[pq] : px, wy_q = center_q ? center_q[pq + 1] : py;
-  int ltx, lty, rbx, rby;
-  set_search_range(wx_q, wy_q, sr, cu_x, cu_y, pic_w, pic_h, ltx, lty, rbx, rby);
-  MeJob j;
-  j.ctu_x = (int16_t)(cu_x | r); j.ctu_y = (int16_t)cu_y;
-  j.lt_x = (int16_t)ltx; j.lt_y = (int16_t)lty; j.rb_x = (int16_t)rbx; j.rb_y = (int16_t)rby;
-  j.pred_x = (int16_t)px; j.pred_y = (int16_t)py;
-  const int wy = rby - lty + 1;
+  const MeJob j = me_picture_job(i, pred_q, center_q, ctu_first, ctu_count, pic_w, pic_h, sr);
+  const int wx = j.rb_x - j.lt_x + 1, wy = j.rb_y - j.lt_y + 1;
   const int n_strips = i < tail_first ? n_strips_head : tail_strips;
   const int base = i < tail_first ? i * n_strips_head : tail_first * n_strips_head + (i - tail_first) * tail_strips;
   const int n_units = tail_first * n_strips_head + (ctu_count * n_refs - tail_first) * tail_strips;   // workgroups of the launch
@@ -1017,7 +1017,7 @@ __global__ void me_prep_jobs16_kernel(MeJob16* jobs, int* first_strip_of_job, co
   // windows need fewer) are empty: y0 == y1
   // head jobs: the planner's choice within n_strips; tail jobs: exactly tail_strips equal pieces (the host chose that number for
   // the sake of the launch's last round, not for this window)
-  const int h = i < tail_first ? me_strip_rows16(rbx - ltx + 1, wy, rows_max, n_strips) : max(1, (wy + n_strips - 1) / n_strips);
+  const int h = i < tail_first ? me_strip_rows16(wx, wy, rows_max, n_strips) : max(1, (wy + n_strips - 1) / n_strips);
   for (int s = 0; s < n_strips; ++s) {
     MeJob16 js;
     js.j = j;
@@ -1041,18 +1041,8 @@ __global__ void me_prep_whole_segments_kernel(void* table, int* first_strip_of_j
                                               int n_refs, int pic_w, int pic_h, int sr, int n_wg, int n_head) {
   const int li = blockIdx.x * blockDim.x + threadIdx.x;
   if (li >= n_head) return;
-  const int r = li / ctu_count;
-  const int ctus_x = (pic_w + 63) >> 6, n_ctu = ctus_x * ((pic_h + 63) >> 6);
-  const int ctu = ctu_first + (li - r * ctu_count);
-  const int cu_x = (ctu % ctus_x) * 64, cu_y = (ctu / ctus_x) * 64;
-  const long pq = 2 * ((long)r * n_ctu + ctu);
-  const int px = pred_q ? pred_q[pq] : 0, py = pred_q ? pred_q[pq + 1] : 0;
-  int ltx, lty, rbx, rby;
-  set_search_range(px, py, sr, cu_x, cu_y, pic_w, pic_h, ltx, lty, rbx, rby);
   MeJob16 js;
-  js.j.ctu_x = (int16_t)(cu_x | r); js.j.ctu_y = (int16_t)cu_y;
-  js.j.lt_x = (int16_t)ltx; js.j.lt_y = (int16_t)lty; js.j.rb_x = (int16_t)rbx; js.j.rb_y = (int16_t)rby;
-  js.j.pred_x = (int16_t)px; js.j.pred_y = (int16_t)py;
+  js.j = me_picture_job(li, pred_q, nullptr, ctu_first, ctu_count, pic_w, pic_h, sr);
   js.y0 = 0; js.y1 = 0x7fff; js.job = li;
   ((MeJob16*)me_seg_table_jobs(table, n_wg))[li] = js;
   first_strip_of_job[li] = li;
@@ -1068,19 +1058,9 @@ me_prep_segments_kernel(void* table, int* first_strip_of_job, const int16_t* __r
   int nt = 0;
   if (li < n_jobs) {
     const int i = job0 + li;              // which (CTU, reference): the launch's job i
-    const int r = i / ctu_count;
-    const int ctus_x = (pic_w + 63) >> 6, n_ctu = ctus_x * ((pic_h + 63) >> 6);
-    const int ctu = ctu_first + (i - r * ctu_count);
-    const int cu_x = (ctu % ctus_x) * 64, cu_y = (ctu / ctus_x) * 64;
-    const long pq = 2 * ((long)r * n_ctu + ctu);
-    const int px = pred_q ? pred_q[pq] : 0, py = pred_q ? pred_q[pq + 1] : 0;
-    int ltx, lty, rbx, rby;
-    set_search_range(px, py, sr, cu_x, cu_y, pic_w, pic_h, ltx, lty, rbx, rby);
     MeJob16 js;
-    js.j.ctu_x = (int16_t)(cu_x | r); js.j.ctu_y = (int16_t)cu_y;
-    js.j.lt_x = (int16_t)ltx; js.j.lt_y = (int16_t)lty; js.j.rb_x = (int16_t)rbx; js.j.rb_y = (int16_t)rby;
-    js.j.pred_x = (int16_t)px; js.j.pred_y = (int16_t)py;
-    nt = me_num_tasks(rbx - ltx + 1, rby - lty + 1);
+    js.j = me_picture_job(i, pred_q, nullptr, ctu_first, ctu_count, pic_w, pic_h, sr);
+    nt = me_num_tasks(js.j.rb_x - js.j.lt_x + 1, js.j.rb_y - js.j.lt_y + 1);
     js.y0 = 0; js.y1 = (int16_t)nt; js.job = idx0 + li;
     nt = (nt + kSegUnit - 1) / kSegUnit;   // from here on: units
     ((MeJob16*)me_seg_table_jobs(table, n_wg))[idx0 + li] = js;
@@ -1117,24 +1097,13 @@ __global__ void me_prep_jobs_tile_kernel(MeJob16* jobs, int* first_strip_of_job,
                                          int ctu_first, int ctu_count, int n_refs, int pic_w, int pic_h, int sr) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= ctu_count * n_refs) return;
-  const int r = i / ctu_count;
-  const int ctus_x = (pic_w + 63) >> 6, n_ctu = ctus_x * ((pic_h + 63) >> 6);
-  const int ctu = ctu_first + (i - r * ctu_count);
-  const int cu_x = (ctu % ctus_x) * 64, cu_y = (ctu / ctus_x) * 64;
-  const long pq = 2 * ((long)r * n_ctu + ctu);
-  const int px = pred_q ? pred_q[pq] : 0, py = pred_q ? pred_q[pq + 1] : 0;
-  int ltx, lty, rbx, rby;
-  set_search_range(px, py, sr, cu_x, cu_y, pic_w, pic_h, ltx, lty, rbx, rby);
+  const MeJob j = me_picture_job(i, pred_q, nullptr, ctu_first, ctu_count, pic_w, pic_h, sr);
   first_strip_of_job[i] = i * 4;
   for (int t = 0; t < 4; ++t) {
     const int tx = t & 1, ty = t >> 1;
-    const int x0 = ltx + tx * kTileStep, y0 = lty + ty * kTileStep;
-    const bool empty = x0 > rbx || y0 > rby;
+    const bool empty = j.lt_x + tx * kTileStep > j.rb_x || j.lt_y + ty * kTileStep > j.rb_y;
     MeJob16 js;
-    js.j.ctu_x = (int16_t)(cu_x | r); js.j.ctu_y = (int16_t)cu_y;
-    js.j.lt_x = (int16_t)(empty ? ltx : x0); js.j.lt_y = (int16_t)(empty ? lty : y0);
-    js.j.rb_x = (int16_t)min(rbx, js.j.lt_x + kTileStep - 1); js.j.rb_y = (int16_t)min(rby, js.j.lt_y + kTileStep - 1);
-    js.j.pred_x = (int16_t)px; js.j.pred_y = (int16_t)py;
+    js.j = empty ? me_tile_job(j, 0, 0) : me_tile_job(j, tx, ty);   // a tile the clipped window does not reach keeps the window's own top-left
     js.y0 = 0; js.y1 = empty ? 0 : 0x7fff;   // task range: everything, or nothing for a tile the clipped window does not reach
     js.job = i | tx << 30 | ty << 29;
     jobs[i * 4 + t] = js;
@@ -1389,8 +1358,8 @@ struct FracOrgRegs {
   const float (&m)[16];
   __device__ __forceinline__ float4 row(int r) const { return make_float4(m[4 * r], m[4 * r + 1], m[4 * r + 2], m[4 * r + 3]); }
 };
-// a whole-picture launch derives each job's window itself (what me_prep_jobs_kernel writes into a job table: pair, CTU, predictor,
-// xSetSearchRange + clipMv) -- one kernel launch less per refinement; the per-CTU call hands over the job the host prepared
+// a whole-picture launch derives each job itself (me_picture_job: what me_prep_jobs_kernel writes into a job table) -- one kernel
+// launch less per refinement; the per-CTU call hands over the job the host prepared
 struct FracPrep { const int16_t* pred_q; uint32_t ctus, dims; int sr; };   // ctus: ctu_first | ctu_count << 16; dims: width | height << 16 (few scalar registers: they stay live across the kernel)
 constexpr float kRoundMagic = 12582912.0f;   // 1.5 * 2^23: x + magic rounds x to the nearest integer (ties to even)
 // First pass on 8-bit planes without v_cvt_f32_i32: the dot-product chain of a filtered sample starts from the BIT PATTERN of
@@ -2017,19 +1986,8 @@ me_frac_kernel(const RefSet curs, int cur_pitch, const RefSet refs, int ref_pitc
   MeJob job;
   if (jobs) {   // a table (job-walking launches, HMME_FRAC_JOB_TABLE, CTU ranges beyond 16 bits), else the job derived here
     job = jobs[jb];
-  } else {   // job jb = pair jb / ctu_count, CTU ctu_first + jb % ctu_count
-    const int ctu_first = (int)(prep.ctus & 0xffff), ctu_count = (int)(prep.ctus >> 16), pic_w = (int)(prep.dims & 0xffff), pic_h = (int)(prep.dims >> 16);
-    const int r = jb / ctu_count;
-    const int ctus_x = (pic_w + 63) >> 6, n_ctu = ctus_x * ((pic_h + 63) >> 6);
-    const int ctu = ctu_first + (jb - r * ctu_count);
-    const int cu_x = (ctu % ctus_x) * 64, cu_y = (ctu / ctus_x) * 64;
-    const long pq = 2 * ((long)r * n_ctu + ctu);
-    const int px = prep.pred_q ? prep.pred_q[pq] : 0, py = prep.pred_q ? prep.pred_q[pq + 1] : 0;
-    int ltx, lty, rbx, rby;
-    set_search_range(px, py, prep.sr, cu_x, cu_y, pic_w, pic_h, ltx, lty, rbx, rby);
-    job.ctu_x = (int16_t)(cu_x | r); job.ctu_y = (int16_t)cu_y;
-    job.lt_x = (int16_t)ltx; job.lt_y = (int16_t)lty; job.rb_x = (int16_t)rbx; job.rb_y = (int16_t)rby;
-    job.pred_x = (int16_t)px; job.pred_y = (int16_t)py;
+  } else {
+    job = me_picture_job(jb, prep.pred_q, nullptr, (int)(prep.ctus & 0xffff), (int)(prep.ctus >> 16), (int)(prep.dims & 0xffff), (int)(prep.dims >> 16), prep.sr);
   }
   const uint8_t* __restrict__ ref_base = refs.base[job.ctu_x & 63];
   const uint8_t* __restrict__ cur_base = curs.base[job.ctu_x & 63];

@@ -19,13 +19,21 @@ int hmme_test_time_search_kernel(hmme_ctx* ctx, const hmme_plane* cur, const hmm
                                  float* avg_ms);
 
 /* how an 8-bit whole-picture search of n_pairs pictures of width x height at `search_range` (<= 64) is dealt to a chip of `slots` workgroup slots
- * (hmme.hip prep_jobs; host arithmetic, needs no device): out[0] = jobs, out[1] = jobs searched whole (the head; == jobs: no tail plan),
+ * (hmme.hip plan_search; host arithmetic, needs no device): out[0] = jobs, out[1] = jobs searched whole (the head; == jobs: no tail plan),
  * out[2] = workgroups (segments) of the tail, out[3] = 1 if head and tail are one launch */
 int hmme_test_tail_plan(int width, int height, int search_range, int n_pairs, int slots, int* out);
 
 /* which job the k-th workgroup of a refinement launch over `n_pairs` whole pictures of width x height takes (me_frac_deal, me_kernels.hpp:
  * edge CTUs of every pair first, then the interiors); host code, needs no device.  -1 for k outside the launch */
 int hmme_test_frac_deal(int k, int n_pairs, int width, int height);
+
+/* the MeJob of job `job` of a launch over CTUs [ctu_first, ctu_first + ctu_count) of a pic_w x pic_h picture at search range `sr`
+ * (me_picture_job, me_kernels.hpp: what every job table and the table-less refinement launch derive on the device; host code, needs no
+ * device): reference job / ctu_count, CTU ctu_first + job % ctu_count.  pred_q / center_q: [references][CTUs of the picture][2] quarter
+ * pels, covering every reference `job` reaches; null = zero predictors / windows centred on the predictors.
+ * out[8] = ctu_x | reference, ctu_y, lt_x, lt_y, rb_x, rb_y, pred_x, pred_y */
+int hmme_test_picture_job(int job, int ctu_first, int ctu_count, int pic_w, int pic_h, int sr, const int16_t* pred_q, const int16_t* center_q,
+                          int16_t* out);
 
 /* average device time in ms of the two plane passes of a weighted whole-picture search on their own, `reps` back-to-back launches each on
  * `stream`: *ref_ms = weighting the padded reference plane (me_weight_plane_kernel), *cur_ms = the u16 CTU-blocked copy of the current picture */

@@ -304,7 +304,7 @@ def test_bench_counts_the_candidates_actually_searched():
 
 
 def test_tail_plan_of_whole_picture_searches():
-    """hmme.hip prep_jobs, 8-bit: which jobs of a launch run whole and how the rest -- the jobs beyond the last full round of the chip's 512 workgroup
+    """hmme.hip plan_search, 8-bit: which jobs of a launch run whole and how the rest -- the jobs beyond the last full round of the chip's 512 workgroup
     slots -- are cut into equal segments (hmme_test_tail_plan: host arithmetic).  2160p's 504 and 1080p's 510 left-over jobs stay whole (measured
     slower as segments); 720p is all tail on exactly one round of segments; 1440p's 408 tail jobs share one launch with the 512 head jobs, 1200p's
     58 get a launch of their own; tiny windows never get more workgroups than they have units of four tasks"""
@@ -331,3 +331,45 @@ def test_tail_plan_of_whole_picture_searches():
         jobs, head, wgs, one = plan(w, h, sr, pairs)
         assert head in (jobs, jobs - jobs % 512) and (wgs > 0) == (head < jobs) and (not one or wgs > 0)
     assert L.hmme_test_tail_plan(1280, 720, 65, 1, 512, (C.c_int * 4)()) != 0      # windows beyond 129 x 129 are tiled, not planned here
+
+
+def test_picture_job_matches_the_oracle_window_for_every_job_of_a_launch():
+    """me_picture_job (host + device function: what the five job-table kernels and the table-less refinement launch derive a job from), through
+    hmme_test_picture_job: job i of a launch over CTUs [first, first + count) and two references is reference i // count (in ctu_x & 63),
+    CTU first + i % count at its origin, carries that (reference, CTU)'s predictor unchanged, and its window is the oracle's xSetSearchRange +
+    clipMv for the window centre where one is given, else for the predictor.  136 x 72 = 3 x 2 CTUs with a partial right column and bottom
+    row; predictors null, within 16 pels, and 8191 pels away in each diagonal direction (the window collapses against every clipMv limit)"""
+    import itertools
+    import oracle_py as O
+    import refine_tables as RT
+    from hmme import api, synth
+    L = api.load()
+    i16p = C.POINTER(C.c_int16)
+    L.hmme_test_picture_job.restype = C.c_int
+    L.hmme_test_picture_job.argtypes = [C.c_int] * 6 + [i16p, i16p, i16p]
+    ptr = lambda a: a.ctypes.data_as(i16p) if a is not None else None
+    n_refs, out, win = 2, np.zeros(8, np.int16), [C.c_int() for _ in range(4)]
+    checked = 0
+    for (w, h, ranges) in ((RT.EDGE_W, RT.EDGE_H, ((0, 6), (1, 4))), (64, 64, ((0, 1),))):
+        X, n = (w + 63) // 64, ((w + 63) // 64) * ((h + 63) // 64)
+        seeded = lambda seed: np.ascontiguousarray(np.stack([synth.random_predictors(n, seed=seed + r, max_pel=16) for r in range(n_refs)]))
+        far = lambda d, fy=RT.FAR: np.ascontiguousarray(np.stack([np.tile(np.array([s * d[0] * RT.FAR, s * d[1] * fy], np.int16), (n, 1)) for s in (1, -1)]))
+        preds = [None, seeded(11)] + [far(d) for d in RT.DIAGONALS]
+        centres = [None, seeded(23), far((1, -1), RT.FAR // 2), far((-1, 1), RT.FAR // 2)]      # as far off as the predictors, and no predictor's value
+        for sr, (first, count), pred, centre in itertools.product((8, 64), ranges, preds, centres):
+            assert centre is None or pred is None or not np.array_equal(centre, pred)
+            for job in range(n_refs * count):
+                assert L.hmme_test_picture_job(job, first, count, w, h, sr, ptr(pred), ptr(centre), ptr(out)) == 0
+                r, ctu = job // count, first + job % count
+                cx, cy = (ctu % X) * 64, (ctu // X) * 64
+                px, py = (int(v) for v in pred[r, ctu]) if pred is not None else (0, 0)
+                wx, wy = (int(v) for v in centre[r, ctu]) if centre is not None else (px, py)
+                O.oracle().hmo_set_search_range(wx, wy, sr, cx, cy, w, h, 64, *[C.byref(v) for v in win])
+                assert int(out[0]) & 63 == r and int(out[0]) & ~63 == cx and out[1] == cy, (w, h, sr, first, count, job)
+                assert tuple(int(v) for v in out[2:6]) == tuple(v.value for v in win), (w, h, sr, first, count, job, (px, py), (wx, wy))
+                assert (int(out[6]), int(out[7])) == (px, py), (w, h, sr, first, count, job)
+                checked += 1
+    assert checked == 2 * 24 * (12 + 8 + 2)
+    for bad in ((-1, 0, 6), (0, -1, 6), (0, 0, 0), (0, 1, 6)):      # a job, a first CTU or a count outside the picture
+        assert L.hmme_test_picture_job(bad[0], bad[1], bad[2], RT.EDGE_W, RT.EDGE_H, 8, None, None, ptr(out)) != 0
+    assert L.hmme_test_picture_job(0, 0, 6, RT.EDGE_W, RT.EDGE_H, 8, None, None, None) != 0
