@@ -927,8 +927,11 @@ int ctu_call(hmme_ctx* ctx, const int16_t* ctu, int ctu_stride, const int16_t* r
     hipLaunchKernelGGL(hmme::me_stage_call_kernel, dim3((n16 + 255) / 256), dim3(256), 0, s, (const uint4*)ctx->h_call_dev, (uint4*)ctx->d_call, n16);
     HIP_TRY(ctx, hipGetLastError());
     if (wp && do_search) {   // the weighted window the integer search runs on; the raw one stays where it is for the refinement's interpolation
-      if (!ctx->d_wwin) HIP_TRY(ctx, hipMalloc(&ctx->d_wwin, (size_t)kWinRows * kWinPitch + 64));
-      hipLaunchKernelGGL(hmme::me_weight_window_kernel, dim3((rows * cols + 255) / 256), dim3(256), 0, s, (const uint8_t*)(ctx->d_call + kCallWin), ctx->d_wwin,
+      if (!ctx->d_wwin) {   // cleared once: rows below a call's window hold zeros or an earlier call's samples, never what the allocator left
+        HIP_TRY(ctx, hipMalloc(&ctx->d_wwin, (size_t)kWinRows * kWinPitch + 64));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_wwin, 0, (size_t)kWinRows * kWinPitch + 64, s));
+      }
+      hipLaunchKernelGGL(hmme::me_weight_window_kernel, dim3((rows * (cols + 8) + 255) / 256), dim3(256), 0, s, (const uint8_t*)(ctx->d_call + kCallWin), ctx->d_wwin,
                          (int)kWinPitch, rows, cols, wp->w0, wp->round, wp->shift, wp->offset + bias);
       HIP_TRY(ctx, hipGetLastError());
     }
@@ -1198,7 +1201,10 @@ static int plan_tail(int tail, int slots, int k_min, int k_max, const std::funct
 // segment launch is taken only where the model says it wins by 8 % plus half a lane-iteration (1080p's 510 jobs and the 504 left over
 // at 2160p stay whole: measured 10 % and 4 % slower as segments, profiles/r06d_tail_segments.txt).
 static int plan_tail8(int tail, int slots, int w, int tail_knob) {
-  if (tail <= 0 || tail > hmme::kSegPrepThreads) return 0;
+  // me_prep_segments_kernel writes prefix[li] for li <= n_jobs from kSegPrepThreads threads: a tail of exactly that many jobs would leave
+  // prefix[n_jobs] unwritten.  A 256-CU part (512 slots) has tails of at most 511; a chip with more slots keeps such a tail whole.  (The
+  // kernel is left as it is: no chip at hand can run it on a tail of 512.)
+  if (tail <= 0 || tail >= hmme::kSegPrepThreads) return 0;
   const int nt = hmme::me_num_tasks(w, w), units = (nt + hmme::kSegUnit - 1) / hmme::kSegUnit;
   const long total = (long)tail * units;
   int best_wgs = 0;

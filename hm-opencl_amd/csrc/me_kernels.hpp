@@ -963,9 +963,12 @@ __global__ void me_stage_call_kernel(const uint4* __restrict__ host_block, uint4
 // kernel runs on it unchanged.
 __global__ void me_weight_window_kernel(const uint8_t* __restrict__ win, uint8_t* __restrict__ out, int pitch, int rows, int cols, int w0, int round,
                                         int shift, int offset_bias) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= rows * cols) return;
-  const int y = i / cols, x = i - y * cols;
+  // eight samples past the last one of each row are written too, as zeros: the search kernel stages whole 16-byte pieces past the last sample,
+  // and what it finds there must be defined like the raw window's padding (hmme.hip ctu_call) -- `out` is never cleared otherwise
+  const int i = blockIdx.x * blockDim.x + threadIdx.x, cw = cols + 8;
+  if (i >= rows * cw) return;
+  const int y = i / cw, x = i - y * cw;
+  if (x >= cols) { ((uint16_t*)(out + (long)y * pitch))[x] = 0; return; }
   const uint16_t v = ((const uint16_t*)(win + (long)y * pitch))[x];
   ((uint16_t*)(out + (long)y * pitch))[x] = (uint16_t)(((w0 * (int)v + round) >> shift) + offset_bias);   // the raw window stays: the refinement interpolates IT
 }

@@ -1,6 +1,7 @@
 """Oracle legs and plane plumbing shared by the whole-picture GPU tests (test_gpu_wp_frame.py, test_gpu_bipred_frame.py,
 test_gpu_range_edges.py): hmo_search_ctu_w per CTU for the weighted search, hmo_pred_block_qpel for the prediction, hmo_search_ctu on the
-origin 2 * cur - prediction built here in numpy for the bi search."""
+origin 2 * cur - prediction built here in numpy for the bi search; hmo_search_ctu_w / hmo_frac_refine_w on an origin for the weighted bi
+calls (test_gpu_bipred_wp.py, test_gpu_context_state.py)."""
 import ctypes as C
 
 import numpy as np
@@ -118,6 +119,45 @@ def oracle_bi_search(oracle_lib, org, ref, w, h, sr, center, pred, lq, fen, bd, 
         ox, oy, osad = oracle_lib.search_ctu(org, (x, y), ref, (m + x, m + y), p)
         mv[k, :, 0], mv[k, :, 1], sad[k] = ox, oy, osad
     return mv, sad
+
+
+def oracle_origin_search_w(oracle_lib, org, ref, w, h, sr, center, pred, lq, bd, wp, ctus):
+    """hmo_search_ctu_w per CTU on an origin `org` (sample (0, 0) at [0, 0]: a bi-prediction origin, or a picture's CTU blocks), window
+    around the centre (None: the predictor), FEN on: xGetSADw must not consult it"""
+    from hmme import api, synth
+    m = synth.MARGIN
+    cx_n, _ = dims(w, h)
+    mv = np.zeros((len(ctus), 593, 2), np.int16)
+    sad = np.zeros((len(ctus), 593), np.uint32)
+    for k, ctu in enumerate(ctus):
+        x, y = (ctu % cx_n) * 64, (ctu // cx_n) * 64
+        px, py = (int(pred[ctu, 0]), int(pred[ctu, 1])) if pred is not None else (0, 0)
+        qx, qy = (int(center[ctu, 0]), int(center[ctu, 1])) if center is not None else (px, py)
+        lt_x, lt_y, rb_x, rb_y = api.set_search_range(qx, qy, sr, x, y, w, h)
+        p = oracle_lib.make_params((lt_x, lt_y), (rb_x, rb_y), (px, py), lq, 1, bd)
+        ox, oy, osad = oracle_lib.search_ctu_w(org, (x, y), ref, (m + x, m + y), p, wp)
+        mv[k, :, 0], mv[k, :, 1], sad[k] = ox, oy, osad
+    return mv, sad
+
+
+def oracle_origin_refine_w(oracle_lib, org, ref, w, h, int_mv, pred, lq, had, bd, wp, ctus):
+    """hmo_frac_refine_w per slot on the origin -> (qmv [len(ctus), 593, 2], cost [len(ctus), 593])"""
+    from hmme import synth
+    m = synth.MARGIN
+    cx_n, _ = dims(w, h)
+    table = oracle_lib.slot_table()
+    qmv = np.zeros((len(ctus), 593, 2), np.int16)
+    cost = np.zeros((len(ctus), 593), np.uint32)
+    for k, ctu in enumerate(ctus):
+        cx, cy = (ctu % cx_n) * 64, (ctu // cx_n) * 64
+        pq = (int(pred[ctu, 0]), int(pred[ctu, 1])) if pred is not None else (0, 0)
+        for s in range(593):
+            x, y, bw, bh = (int(v) for v in table[s])
+            imv = (int(int_mv[k, s, 0]), int(int_mv[k, s, 1]))
+            hx, hy, qx, qy, c = oracle_lib.frac_refine_w(org, (cx + x, cy + y), ref, (m + cx + x, m + cy + y), bw, bh, imv, pq, lq, had, bd, wp)
+            qmv[k, s] = (4 * imv[0] + 2 * hx + qx, 4 * imv[1] + 2 * hy + qy)
+            cost[k, s] = c
+    return qmv, cost
 
 
 def check_strided_image(w, h, bd, wrapper, entry, spare=24):

@@ -330,6 +330,12 @@ def test_tail_plan_of_whole_picture_searches():
     for w, h, sr, pairs in ((1280, 720, 64, 3), (3840, 2160, 32, 1), (640, 360, 64, 16), (4096, 2304, 64, 1)):
         jobs, head, wgs, one = plan(w, h, sr, pairs)
         assert head in (jobs, jobs - jobs % 512) and (wgs > 0) == (head < jobs) and (not one or wgs > 0)
+    # a chip with more than 512 slots: the kernel that writes the tail's segment table (me_prep_segments_kernel, 512 threads) holds a tail of
+    # 511 jobs at most, so a tail of exactly 512 -- 2240 x 2048 = 35 x 32 = 1 120 jobs on 608 slots -- runs whole; 511 are planned as ever
+    assert plan(2240, 2048, slots=608) == (1120, 1120, 0, 0)
+    for w, h in ((4672, 448), (10048, 704)):                          # 73 x 7 = 511 jobs: all tail; 157 x 11 = 1 727 = two rounds + 511
+        jobs, head, wgs, one = plan(w, h, slots=608)
+        assert jobs % 608 == 511 and head in (jobs, jobs - 511) and (wgs > 0) == (head < jobs) and (not one or wgs > 0)
     assert L.hmme_test_tail_plan(1280, 720, 65, 1, 512, (C.c_int * 4)()) != 0      # windows beyond 129 x 129 are tiled, not planned here
 
 

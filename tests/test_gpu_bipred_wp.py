@@ -9,6 +9,7 @@ import pytest
 import bipred_wp_model as model
 import range_content as rc
 from frame_helpers import bind_hmo, check_strided_image, device_tables, dims, mkplane, random_field, three_planes
+from frame_helpers import oracle_origin_refine_w as oracle_refine, oracle_origin_search_w as oracle_search
 
 pytestmark = pytest.mark.gpu
 
@@ -45,44 +46,6 @@ def hmo(oracle_lib):
 def accepted(bd, wp, owp, refine):
     from hmme import api
     assert api.bipred_weight_check(bd, wp, owp, refine) == 0, (bd, wp, owp, refine)
-
-
-def oracle_search(oracle_lib, org, ref, w, h, sr, center, pred, lq, bd, wp, ctus):
-    """hmo_search_ctu_w per CTU on the origin, window around the centre (None: the predictor), FEN on: xGetSADw must not consult it"""
-    from hmme import api, synth
-    m = synth.MARGIN
-    cx_n, _ = dims(w, h)
-    mv = np.zeros((len(ctus), 593, 2), np.int16)
-    sad = np.zeros((len(ctus), 593), np.uint32)
-    for k, ctu in enumerate(ctus):
-        x, y = (ctu % cx_n) * 64, (ctu // cx_n) * 64
-        px, py = (int(pred[ctu, 0]), int(pred[ctu, 1])) if pred is not None else (0, 0)
-        qx, qy = (int(center[ctu, 0]), int(center[ctu, 1])) if center is not None else (px, py)
-        lt_x, lt_y, rb_x, rb_y = api.set_search_range(qx, qy, sr, x, y, w, h)
-        p = oracle_lib.make_params((lt_x, lt_y), (rb_x, rb_y), (px, py), lq, 1, bd)
-        ox, oy, osad = oracle_lib.search_ctu_w(org, (x, y), ref, (m + x, m + y), p, wp)
-        mv[k, :, 0], mv[k, :, 1], sad[k] = ox, oy, osad
-    return mv, sad
-
-
-def oracle_refine(oracle_lib, org, ref, w, h, int_mv, pred, lq, had, bd, wp, ctus):
-    """hmo_frac_refine_w per slot on the origin -> (qmv [len(ctus), 593, 2], cost [len(ctus), 593])"""
-    from hmme import synth
-    m = synth.MARGIN
-    cx_n, _ = dims(w, h)
-    table = oracle_lib.slot_table()
-    qmv = np.zeros((len(ctus), 593, 2), np.int16)
-    cost = np.zeros((len(ctus), 593), np.uint32)
-    for k, ctu in enumerate(ctus):
-        cx, cy = (ctu % cx_n) * 64, (ctu // cx_n) * 64
-        pq = (int(pred[ctu, 0]), int(pred[ctu, 1])) if pred is not None else (0, 0)
-        for s in range(593):
-            x, y, bw, bh = (int(v) for v in table[s])
-            imv = (int(int_mv[k, s, 0]), int(int_mv[k, s, 1]))
-            hx, hy, qx, qy, c = oracle_lib.frac_refine_w(org, (cx + x, cy + y), ref, (m + cx + x, m + cy + y), bw, bh, imv, pq, lq, had, bd, wp)
-            qmv[k, s] = (4 * imv[0] + 2 * hx + qx, 4 * imv[1] + 2 * hy + qy)
-            cost[k, s] = c
-    return qmv, cost
 
 
 def run_case(engine, oracle_lib, hmo, w, h, bd, sr, wp, owp, per, seed, with_center=True, fen=0, planes3=None, had=None, field=None):
