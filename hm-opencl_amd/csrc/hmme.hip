@@ -579,7 +579,9 @@ int hmme_device_index(const hmme_ctx* ctx) { return ctx ? ctx->device : -1; }
 int hmme_set_lambda(hmme_ctx* ctx, double lambda) {
   if (!ctx) return HMME_ERR_ARG;
   if (!(lambda >= 0.0)) return fail(ctx, HMME_ERR_ARG, "lambda %g", lambda);
-  ctx->lambda_q16 = (uint32_t)std::floor(65536.0 * std::sqrt(lambda));   // TEncOpenCL.h:121 == TComRdCost.cpp:209
+  const double q = std::floor(65536.0 * std::sqrt(lambda));   // TEncOpenCL.h:121 == TComRdCost.cpp:209
+  if (!(q < 4294967296.0)) return fail(ctx, HMME_ERR_ARG, "lambda %g: 65536 * sqrt(lambda) does not fit 32 bits", lambda);
+  ctx->lambda_q16 = (uint32_t)q;
   return HMME_OK;
 }
 int hmme_set_lambda_q16(hmme_ctx* ctx, uint32_t q) {

@@ -294,6 +294,9 @@ class Engine:
         self._check(self.L.hmme_set_lambda(self.h, float(lam)))
 
     def set_lambda_q16(self, q):
+        """any uint32 (the MV cost's product wraps in 32 bits, as HM's); ValueError outside 0..2^32-1, which ctypes would truncate silently"""
+        if not 0 <= int(q) <= 0xFFFFFFFF:
+            raise ValueError(f"lambda_q16 {q} is outside 0..2^32-1")
         self._check(self.L.hmme_set_lambda_q16(self.h, int(q)))
 
     @property

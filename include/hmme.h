@@ -132,8 +132,11 @@ const char* hmme_last_error(const hmme_ctx* ctx); /* ctx may be NULL: error of t
 int hmme_set_error_printing(hmme_ctx* ctx, int on);
 const char* hmme_device_info(const hmme_ctx* ctx);
 int hmme_device_index(const hmme_ctx* ctx);   /* the HIP device the context lives on (host code that makes its own HIP calls beside the library's) */
-int hmme_set_lambda(hmme_ctx* ctx, double lambda);         /* m_lambda = floor(65536*sqrt(lambda)) */
-int hmme_set_lambda_q16(hmme_ctx* ctx, uint32_t lambda_q16);
+/* m_lambda = floor(65536*sqrt(lambda)).  HMME_ERR_ARG, the context's value unchanged, for a lambda that is negative, not a number, or
+ * so large that 65536*sqrt(lambda) is not below 2^32 (lambda >= 2^32, infinity included): the conversion to uint32 is undefined there.
+ * The largest accepted lambda gives 0xFFFFFFFF; every uint32 can be set through hmme_set_lambda_q16. */
+int hmme_set_lambda(hmme_ctx* ctx, double lambda);
+int hmme_set_lambda_q16(hmme_ctx* ctx, uint32_t lambda_q16);   /* any value: the MV cost is (lambda_q16 * bits) >> 16 with the product wrapping in 32 bits, as HM's */
 uint32_t hmme_get_lambda_q16(const hmme_ctx* ctx);
 
 /* the parameter set that reproduces the reference GPU path's choices */

@@ -132,10 +132,11 @@ static void pu_rect(int part_size, int part_idx, int s, hmo_rect* r) {
 }
 
 static hmo_rect g_slot_rect[HMO_NUM_CTU_PARTS];
-static int g_slot_init = 0;
+static pthread_once_t g_slot_once = PTHREAD_ONCE_INIT;
 
-static void init_slots(void) {
-  if (g_slot_init) return;
+/* once per process, whichever thread comes first: the workers of hmo_search_frame / hmo_tz_frame all start here, and a second thread that
+ * ran the fill beside the first (or read the table while it was being zeroed) saw empty rectangles for the slots filled last, the largest */
+static void fill_slots(void) {
   static const int part_sizes[7] = {P_2Nx2N, P_2NxN, P_Nx2N, P_2NxnU, P_2NxnD, P_nLx2N, P_nRx2N};
   for (int i = 0; i < HMO_NUM_CTU_PARTS; ++i) g_slot_rect[i].w = 0;
   for (int lvl = 0; lvl < 4; ++lvl) {
@@ -153,8 +154,9 @@ static void init_slots(void) {
             g_slot_rect[slot] = r;
           }
   }
-  g_slot_init = 1;
 }
+
+static void init_slots(void) { pthread_once(&g_slot_once, fill_slots); }
 
 int hmo_slot_rect(int slot, hmo_rect* r) {
   init_slots();

@@ -238,6 +238,7 @@ def test_cpp_sequence_driver_is_clean_under_asan_and_ubsan(tmp_path):
     -fsanitize=address,undefined together with tests/cpp/test_sequence_plan.cpp"""
     import shutil
     import subprocess
+    import pytest
     import torch
     from hmme import api
     if not shutil.which("hipcc"):

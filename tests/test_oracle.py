@@ -237,3 +237,34 @@ def test_fractional_refinement_of_biprediction_origins(oracle_lib):
         slot, x, y, w, h, ix, iy, px, py, had, bd, lq, o, which = (int(v) for v in row)
         got = oracle_lib.frac_refine(planes[(bd, which)], (o + x, o + y), refs[bd], (o + x, o + y), w, h, (ix, iy), (px, py), lq, had, bd)
         assert got == tuple(int(v) for v in want), row
+
+
+_FIRST_CALL = """
+import sys, zlib
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[2])
+import numpy as np
+import oracle_py
+from hmme import synth
+cur, ref, _ = synth.make_pair(512, 128, seed=31, max_mv=5, region=64)
+ox, oy, osad = oracle_py.search_frame(cur, ref, (synth.MARGIN, synth.MARGIN), 512, 128, 4, None, 3794275, 1, 8, n_threads=16)
+print(zlib.crc32(ox.tobytes() + oy.tobytes() + osad.tobytes()))
+"""
+
+
+def test_a_threaded_search_may_be_a_process_first_oracle_call(oracle_lib):
+    """the slot table is filled once per process by whichever worker comes first: fresh processes whose FIRST oracle call is a threaded
+    whole-frame search give the single-threaded answer (filled unguarded, a second worker could zero the table under the first and see empty
+    rectangles for the largest slots -- all candidates tie there and the window's first one wins)"""
+    import subprocess
+    import sys
+    import zlib
+    from conftest import ROOT
+    from hmme import synth
+    cur, ref, _ = synth.make_pair(512, 128, seed=31, max_mv=5, region=64)
+    ox, oy, osad = oracle_lib.search_frame(cur, ref, (synth.MARGIN, synth.MARGIN), 512, 128, 4, None, 3794275, 1, 8, n_threads=1)
+    want = zlib.crc32(ox.tobytes() + oy.tobytes() + osad.tobytes())
+    for _ in range(4):
+        r = subprocess.run([sys.executable, "-c", _FIRST_CALL, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "hm-opencl_amd")], capture_output=True, text=True,
+                           timeout=120)
+        assert r.returncode == 0, r.stderr[-1500:]
+        assert int(r.stdout.strip().splitlines()[-1]) == want

@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import lambda_cases as lc
 import oracle_py
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "oracle_vs_ref.npz")
@@ -187,4 +188,128 @@ def test_full_search_over_whole_ctus_matches_reference(oracle_lib, reference):
         want = reference.ask(live)   # (x, y, cost) tables, flat
         ox, oy, os_ = oracle_lib.search_frame(cur, ref, (m, m), w, h, sr, None, lq, 1, bd, first, 2, 2)
         assert ox.shape == (2, 593) and np.array_equal(want, np.concatenate([np.ravel(a) for a in (ox, oy, os_)]))
+    reference.done()
+
+
+# ---- where the MV cost wraps or peaks (tests/lambda_cases.py): getCost's product wraps in 32 bits in the reference, and so must the oracle's ----
+def _edge_predictor(rng):
+    """quarter pels: each component near (+-60) or far (out to +-2000, where one component alone takes 21 or 23 bits)"""
+    return tuple(int(rng.integers(-s, s + 1)) for s in rng.choice([60, 2000], size=2))
+
+
+def _edge_lambda(reference, R, lq):
+    """the double the reference is asked with; its own conversion must give lambda_q16 back"""
+    lam = lc.as_double(lq)
+    assert int(reference.ask(lambda: R.ref_lambda_q16(lam))[0]) == lq
+    return lam
+
+
+def _moved_block(rng, bd, sr, noise=2):
+    """a 64x64 block that lies in `ref` displaced by a motion inside the window, under a little noise: the large PUs find it whatever its
+    bits cost, the small ones follow the MV cost"""
+    side = 64 + 2 * sr + 8
+    o = sr + 4
+    ref = rng.integers(0, 1 << bd, size=(side, side)).astype(np.int16)
+    tx, ty = (int(v) for v in rng.integers(-sr + 1, sr, size=2))
+    cur = np.clip(ref[o + ty:o + ty + 64, o + tx:o + tx + 64].astype(np.int32) + rng.integers(-noise, noise + 1, size=(64, 64)), 0, (1 << bd) - 1)
+    return np.ascontiguousarray(cur.astype(np.int16)), ref, o
+
+
+def _check_winner_conditions(bits):
+    """bits: lambda_q16 -> MV bit counts of the winners.  178956971: wrapped and unwrapped winners both occur.  0x80000000: an MV's bit count
+    is the sum of two odd exp-Golomb lengths, hence even, so getCost of it is 0 for every candidate -- winners of odd parity cannot occur in
+    a search or a refinement (they do in the direction decision, which adds the caller's bits: tests/test_select_dirs_cpu.py)"""
+    assert any(lc.wraps(lc.WRAP24, b) for b in bits[lc.WRAP24]) and any(not lc.wraps(lc.WRAP24, b) for b in bits[lc.WRAP24])
+    assert bits[lc.HALF] and all(b % 2 == 0 and lc.get_cost(lc.HALF, b) == 0 for b in bits[lc.HALF])
+    assert all(lc.get_cost(lc.ALL_ONES, b) == lc.MAX_MV_COST for b in bits[lc.ALL_ONES])
+    assert max(max(v) for v in bits.values()) >= 30
+
+
+def test_pu_searches_at_wrapping_lambdas_match_reference(oracle_lib, reference):
+    """per-PU integer search, 8 and 10 bit, FEN 0 and 1, at the six lambda_q16 of tests/lambda_cases.py, predictors out to +-2000 quarter pels"""
+    R = oracle_lib.ref() if reference.live else None
+    rng = np.random.default_rng(3101)
+    table = oracle_lib.slot_table()
+    bits = {lq: [] for lq in lc.LAMBDA_Q16}
+    for lq in lc.LAMBDA_Q16:
+        lam = _edge_lambda(reference, R, lq)
+        for bd in (8, 10):
+            for fen in (0, 1):
+                sr = 8
+                cur, ref, o = _moved_block(rng, bd, sr)
+                pred = _edge_predictor(rng) if fen else tuple(int(v) for v in rng.integers(-30, 31, size=2))
+                p = oracle_lib.make_params((-sr, -sr), (sr, sr), pred, lq, fen, bd)
+                ox, oy, osad = oracle_lib.search_ctu(cur, (0, 0), ref, (o, o), p)
+                for s in [592, 0] + [int(v) for v in rng.choice(np.arange(1, 592), size=8, replace=False)]:
+                    x, y, w, h = (int(v) for v in table[s])
+                    want = tuple(int(v) for v in reference.ask(lambda: oracle_lib.pattern_search(cur, (x, y), ref, (o + x, o + y), w, h, p, use_ref=True, lam=lam)))
+                    assert (int(ox[s]), int(oy[s]), int(osad[s])) == want, (lq, bd, fen, s, pred)
+                    assert tuple(oracle_lib.pattern_search(cur, (x, y), ref, (o + x, o + y), w, h, p)) == want
+                    bits[lq].append(lc.mv_bits(4 * want[0], 4 * want[1], *pred))
+    _check_winner_conditions(bits)
+    reference.done()
+
+
+def test_weighted_pu_searches_at_wrapping_lambdas_match_reference(oracle_lib, reference):
+    R = oracle_lib.ref() if reference.live else None
+    rng = np.random.default_rng(3102)
+    table = oracle_lib.slot_table()
+    bits = {lq: [] for lq in lc.LAMBDA_Q16}
+    for lq in lc.LAMBDA_Q16:
+        lam = _edge_lambda(reference, R, lq)
+        for bd in (8, 10):
+            sr = 8
+            cur, ref, o = _moved_block(rng, bd, sr)
+            shift = int(rng.integers(4, 8))
+            wp = ((1 << shift) + int(rng.integers(-3, 4)), int(rng.integers(-6, 7)) << (bd - 8), shift, 1 << (shift - 1))   # near the identity: the motion stays findable
+            pred = _edge_predictor(rng) if bd == 10 else tuple(int(v) for v in rng.integers(-30, 31, size=2))
+            p = oracle_lib.make_params((-sr, -sr), (sr, sr), pred, lq, int(rng.integers(0, 2)), bd)
+            ox, oy, osad = oracle_lib.search_ctu_w(cur, (0, 0), ref, (o, o), p, wp)
+            for s in [592, 0] + [int(v) for v in rng.choice(np.arange(1, 592), size=6, replace=False)]:
+                x, y, w, h = (int(v) for v in table[s])
+                want = tuple(int(v) for v in reference.ask(lambda: oracle_lib.pattern_search_w(cur, (x, y), ref, (o + x, o + y), w, h, p, wp, use_ref=True, lam=lam)))
+                assert (int(ox[s]), int(oy[s]), int(osad[s])) == want, (lq, bd, s, wp, pred)
+                assert tuple(oracle_lib.pattern_search_w(cur, (x, y), ref, (o + x, o + y), w, h, p, wp)) == want
+                bits[lq].append(lc.mv_bits(4 * want[0], 4 * want[1], *pred))
+    _check_winner_conditions(bits)
+    reference.done()
+
+
+def test_fractional_refinement_at_wrapping_lambdas_matches_reference(oracle_lib, reference):
+    """SAD and Hadamard, plain and the bi origin, 8 and 10 bit.  Every second case puts the predictor 16 and 3 pels from the integer MV
+    (4 * mv - pred = (+-64, +-12): 13 or 15 bits in x, 9 in y), so that the nine half-pel points lie on both sides of 24 bits, the first
+    wrap of lambda_q16 = 178956971; the others draw it out to +-2000 quarter pels"""
+    from hmme import synth
+    R = oracle_lib.ref() if reference.live else None
+    rng = np.random.default_rng(3103)
+    table = oracle_lib.slot_table()
+    straddles, top = {lq: 0 for lq in lc.LAMBDA_Q16}, 0
+    it = 0
+    for lq in lc.LAMBDA_Q16:
+        lam = _edge_lambda(reference, R, lq)
+        for bd in (8, 10):
+            for had in (0, 1):
+                for near in (True, False):
+                    it += 1
+                    cur, ref, _ = synth.make_pair(160, 160, seed=700 + it, bit_depth=bd, max_mv=3, region=64, margin=16, noise_sigma=3.0)
+                    x, y, w, h = (int(v) for v in table[int(rng.integers(0, 593))])
+                    mv = (int(rng.integers(-5, 6)), int(rng.integers(-5, 6)))
+                    sx, sy = (int(v) for v in rng.choice([-1, 1], size=2))
+                    pred = (4 * mv[0] - 64 * sx, 4 * mv[1] - 12 * sy) if near else _edge_predictor(rng)
+                    nine = [lc.mv_bits(4 * mv[0] + dx, 4 * mv[1] + dy, *pred) for dy in (-2, 0, 2) for dx in (-2, 0, 2)]
+                    straddles[lq] += min(nine) < 24 <= max(nine)
+                    top = max(top, max(nine))
+                    o = 16 + 48
+                    a = oracle_lib.frac_refine(cur, (o + x, o + y), ref, (o + x, o + y), w, h, mv, pred, lq, had, bd)
+                    b = tuple(int(v) for v in reference.ask(lambda: oracle_lib.frac_refine(cur, (o + x, o + y), ref, (o + x, o + y), w, h, mv, pred, lam, had, bd,
+                                                                                         use_ref=True)))
+                    assert tuple(a) == b, (lq, w, h, mv, pred, had, bd)
+                    other = np.roll(cur, (int(rng.integers(-3, 4)), int(rng.integers(-3, 4))), axis=(0, 1)).astype(np.int32) + rng.integers(-30, 31, size=cur.shape)
+                    org = (2 * cur.astype(np.int32) - np.clip(other, 0, (1 << bd) - 1)).astype(np.int16)
+                    a = oracle_lib.frac_refine(org, (o + x, o + y), ref, (o + x, o + y), w, h, mv, pred, lq, had, bd)
+                    b = tuple(int(v) for v in reference.ask(lambda: oracle_lib.frac_refine(org, (o + x, o + y), ref, (o + x, o + y), w, h, mv, pred, lam, had, bd,
+                                                                                         use_ref=True, bi=True)))
+                    assert tuple(a) == b, ("bi", lq, w, h, mv, pred, had, bd)
+    assert all(n >= 4 for n in straddles.values()) and top >= 30, (straddles, top)
+    assert not lc.wraps(lc.WRAP24, 22) and lc.wraps(lc.WRAP24, 24)
     reference.done()

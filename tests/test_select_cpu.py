@@ -6,8 +6,11 @@ import inspect
 import os
 import re
 
+import numpy as np
 import pytest
 
+import lambda_cases as lc
+import select_model as sm
 from conftest import ROOT
 
 OK, ERR_ARG = 0, -1
@@ -120,3 +123,45 @@ def test_run_rank_select_defaults_to_none_and_is_checked_before_any_device(api):
         sequence.run_rank(None, None, [(1, 0)], 64, 64, 8, 8, refine=True, select=api.SelectParams(64, mv_unit=1, price_mv=0))
     with pytest.raises(ValueError):   # outside hmme_select_check's ranges
         sequence.run_rank(None, None, [(1, 0)], 64, 64, 8, 8, refine=True, select=api.SelectParams(128))
+
+
+# ---- the MV cost where its product wraps (tests/lambda_cases.py) -----------------------------------------------------------------------
+def _wide(lq, x, y, px, py, scale):
+    """the MV cost from a 64-bit product: what the rule does NOT say"""
+    return lc.get_cost_64(lq, lc.mv_bits(x << scale, y << scale, px, py))
+
+
+def _wrapped(lq, x, y, px, py, scale):
+    return lc.get_cost(lq, lc.mv_bits(x << scale, y << scale, px, py))
+
+
+@pytest.mark.parametrize("unit", [0, 1])
+@pytest.mark.parametrize("lq", lc.LAMBDA_Q16)
+def test_the_model_prices_mvs_with_the_wrapping_product(api, oracle_lib, lq, unit):
+    """select_model with the oracle's hmo_mv_cost == with tests/lambda_cases.py's Python restatement, at every lambda of the set, far predictors"""
+    L = oracle_lib.oracle()
+    mv, cost = sm.random_tables(2, seed=91, noise=64)
+    pred = np.array([[-1900, 1733], [37, -1012]], np.int16)
+    sel = api.SelectParams(64, mv_unit=unit, price_mv=1, cu_cost=40, pu_cost=12)
+    a = sm.select_picture(mv, cost, sel, 128, 64, 0, pred, lq, lambda *v: L.hmo_mv_cost(*v))
+    b = sm.select_picture(mv, cost, sel, 128, 64, 0, pred, lq, _wrapped)
+    assert all(np.array_equal(x, y) for x, y in zip(a[:3], b[:3])) and a[3] == b[3]
+    bits = [lc.mv_bits(int(v[0]) << (2 * unit), int(v[1]) << (2 * unit), *pred[k]) for k in range(2) for v in mv[k]]
+    if lq in lc.WRAPPING:
+        assert any(lc.wraps(lq, n) for n in bits)
+        assert not np.array_equal(sm.select_picture(mv, cost, sel, 128, 64, 0, pred, lq, _wide)[2], a[2])
+
+
+def test_the_wrap_changes_the_partition_by_hand(api):
+    """one 64x64 CU, 2Nx2N or 2NxN, lambda_q16 = 178956971 = ceil(2^32 / 24).  2Nx2N: cost 1000 at MV (1024, 0) quarter pels -- 23 + 1 = 24 bits,
+    24 * 178956971 = 2^32 + 8, wrapped >> 16 = 0: 1000 in all.  2NxN: 400 per PU at MV (0, 0) -- 2 bits, 357913942 >> 16 = 5461: 2 * (400 + 5461)
+    = 11722.  HM's wrapping product codes 2Nx2N; a 64-bit product would price the 24 bits at 65536 and code 2NxN"""
+    assert lc.mv_bits(1024, 0, 0, 0) == 24 and lc.get_cost(lc.WRAP24, 24) == 0 and lc.get_cost_64(lc.WRAP24, 24) == 65536 and lc.get_cost(lc.WRAP24, 2) == 5461
+    whole, (top, bottom) = api.slot_index(0, 0, 0, 0), (api.slot_index(1, 0, i, 0) for i in range(2))
+    mv, cost = np.zeros((593, 2), np.int16), np.full(593, 1 << 20, np.uint32)
+    mv[whole], cost[whole], cost[top], cost[bottom] = (1024, 0), 1000, 400, 400
+    sel = api.SelectParams(64, price_mv=1, part_mask=0x03, max_depth=0)
+    _, slot, total, leaves = sm.select_ctu(mv, cost, sel, 0, 0, 64, 64, (0, 0), lc.WRAP24, _wrapped)
+    assert (total, leaves) == (1000, [(0, 0)]) and set(slot.tolist()) == {whole}
+    _, slot, total, leaves = sm.select_ctu(mv, cost, sel, 0, 0, 64, 64, (0, 0), lc.WRAP24, _wide)
+    assert (total, leaves) == (11722, [(0, 1)]) and set(slot.tolist()) == {top, bottom}

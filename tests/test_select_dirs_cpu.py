@@ -9,6 +9,7 @@ import re
 import numpy as np
 import pytest
 
+import lambda_cases as lc
 import select_dirs_model as sdm
 import select_model as sm
 import select_refs_model as srm
@@ -140,3 +141,49 @@ def test_the_recipes_of_the_gpu_cases_exercise_every_direction_and_every_tie(api
     # the rule at the ties themselves
     assert sdm.decide([10, 10], [10, 10]) == (3, 0, 10) and sdm.decide([10, 10], [11, 11]) == (1, 0, 10) and sdm.decide([10, 9], [10, 10]) == (2, 0, 9)
     assert sdm.decide([10, 10], [10, 9]) == (3, 1, 9) and sdm.decide([9, 10], [10, 9]) == (3, 1, 9) and sdm.decide([9, 10], [10, 10]) == (1, 0, 9)
+
+
+# ---- getCost where its product wraps (tests/lambda_cases.py) -----------------------------------------------------------------------------
+@pytest.mark.parametrize("lq", lc.LAMBDA_Q16)
+def test_the_models_get_cost_is_the_wrapping_product(oracle_lib, lq):
+    L = oracle_lib.oracle()
+    for n in list(range(0, 80)) + [4096, 3 * 4096 + 77, 20000]:
+        assert sdm.gc(lq, n) == lc.get_cost(lq, n) == ((lq * n) % (1 << 32)) >> 16
+    for x, y, px, py in ((5, -3, 0, 0), (-200, 117, 1900, -7), (300, -300, -2000, 2000), (1024, 0, 0, 0)):
+        assert sdm.gc(lq, sdm.mvb((x, y), (px, py))) == L.hmo_mv_cost(lq, x, y, px, py, 0)
+    assert all(sdm.mvb((x, y), (px, py)) % 2 == 0 for x in range(-9, 10) for y in (-300, 0, 7) for px in (-2000, 3) for py in (0, 11))   # two odd lengths
+
+
+@pytest.mark.parametrize("lq", lc.WRAPPING)
+def test_the_direction_model_at_the_wrapping_lambdas_differs_from_a_64_bit_product(api, monkeypatch, lq):
+    """both uses of gc wrap, and the floor of rule 1 is hit: distortion-only tables (written at lambda_q16 = 1) priced at lq"""
+    w, h = 136, 72
+    n = sdm.n_ctus(w, h)
+    rng = np.random.default_rng(93)
+    pred = rng.integers(-2000, 2001, size=(2, n, 2)).astype(np.int16)
+    tabs = sdm.random_dir_tables(n, n, seed=94, pred=pred, lambda_q16=lc.TINY)
+    floor = sum(int(tabs[1][l, k, s]) < sdm.gc(lq, sdm.mvb(tabs[0][l, k, s], pred[l][k])) for l in range(2) for k in range(n) for s in range(0, 593, 5))
+    assert floor > 0 or lq == lc.HALF      # an MV's bit count is even: at 0x80000000 gc(mv bits) is 0, only the bits put back cost
+    sel = api.SelectParams(64, cu_cost=40, pu_cost=12)
+    bits = ((3, 3, 5), (2, 1))
+    want = sdm.select_dirs_picture(*tabs, sel, w, h, bits, 0, pred, lq)
+    monkeypatch.setattr(sdm, "gc", lc.get_cost_64)
+    wide = sdm.select_dirs_picture(*tabs, sel, w, h, bits, 0, pred, lq)
+    assert not np.array_equal(want[3], wide[3])
+
+
+def test_the_wrap_changes_the_direction_by_hand(monkeypatch):
+    """one slot at lambda_q16 = 178956971, no direction or list bits, no bi candidate (cost 2^32 - 1).  List 0: cost 1000 at an MV of 24 bits --
+    gc(24) = 0 wrapped: C[0] = 1000 - 0 + 0 = 1000; with a 64-bit product gc(24) = 65536: max(0, 1000 - 65536) + 65536 = 65536.  List 1: cost 7000
+    at an MV of 2 bits, gc(2) = 5461: C[1] = 1539 + 5461 = 7000 either way.  HM's wrapping product codes L0, a 64-bit one L1.  And the floor:
+    a cost of 3000 under gc(2) = 5461 leaves a distortion of 0"""
+    zero = ((0, 0, 0), (0, 0))
+    mu, cu = np.array([[1024, 0], [0, 0]], np.int16), [1000, 7000]
+    mb, cb = np.zeros((2, 2), np.int16), [0xFFFFFFFF, 0xFFFFFFFF]
+    pred = [(0, 0), (0, 0)]
+    c, c_b = sdm.slot_candidates(mu, cu, mb, cb, pred, zero, lc.WRAP24)
+    assert c == [1000, 7000] and sdm.decide(c, c_b)[0] == 1
+    assert sdm.slot_candidates(mu, [1000, 3000], mb, cb, pred, zero, lc.WRAP24)[0] == [1000, 0 + 5461]
+    monkeypatch.setattr(sdm, "gc", lc.get_cost_64)
+    c, c_b = sdm.slot_candidates(mu, cu, mb, cb, pred, zero, lc.WRAP24)
+    assert c == [65536, 7000] and sdm.decide(c, c_b)[0] == 2

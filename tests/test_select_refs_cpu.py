@@ -9,6 +9,7 @@ import re
 import numpy as np
 import pytest
 
+import lambda_cases as lc
 import select_model as sm
 import select_refs_model as srm
 from conftest import ROOT
@@ -125,3 +126,39 @@ def test_the_recipes_of_the_gpu_cases_exercise_the_choice(api, mv_cost, n_refs, 
     assert (ref[slot == sm.NO_SLOT] == srm.NO_REF).all() and (slot == sm.NO_SLOT).any()      # partial CTUs: blocks no CU covers
     assert any((pred[a] != pred[b]).any() for a in range(n_refs) for b in range(a))           # distinct predictors
     assert len(set(ref_cost)) > 1 or n_refs == 2                                               # HM's prices differ by index
+
+
+# ---- the MV cost where its product wraps (tests/lambda_cases.py) -----------------------------------------------------------------------
+def _wide(lq, x, y, px, py, scale):
+    return lc.get_cost_64(lq, lc.mv_bits(x << scale, y << scale, px, py))
+
+
+def _wrapped(lq, x, y, px, py, scale):
+    return lc.get_cost(lq, lc.mv_bits(x << scale, y << scale, px, py))
+
+
+@pytest.mark.parametrize("unit", [0, 1])
+@pytest.mark.parametrize("lq", lc.LAMBDA_Q16)
+def test_the_model_prices_mvs_with_the_wrapping_product(api, mv_cost, lq, unit):
+    """three references, each with its own far predictor: the oracle's hmo_mv_cost == the Python restatement, at every lambda of the set"""
+    mv, cost = srm.random_ref_tables(3, 2, seed=92, noise=64)
+    pred = np.array([[[-1900, 1733], [37, -1012]], [[1999, -8], [-640, 1500]], [[12, 1024], [-2000, -2000]]], np.int16)
+    sel = api.SelectParams(64, mv_unit=unit, price_mv=1, cu_cost=40, pu_cost=12)
+    a = srm.select_refs_picture(mv, cost, sel, 128, 64, srm.hm_ref_cost(3), 0, pred, lq, mv_cost)
+    b = srm.select_refs_picture(mv, cost, sel, 128, 64, srm.hm_ref_cost(3), 0, pred, lq, _wrapped)
+    assert all(np.array_equal(x, y) for x, y in zip(a[:4], b[:4])) and a[4] == b[4]
+    if lq in lc.WRAPPING:
+        assert not np.array_equal(srm.select_refs_picture(mv, cost, sel, 128, 64, srm.hm_ref_cost(3), 0, pred, lq, _wide)[3], a[3])
+
+
+def test_the_wrap_changes_the_reference_by_hand(api):
+    """one 64x64 2Nx2N CU, two references at lambda_q16 = 178956971: reference 0 costs 1000 at an MV of 24 bits (wrapped price 0, 64-bit
+    price 65536), reference 1 costs 900 at an MV of 2 bits (price 5461: 6361).  HM's wrapping product takes reference 0, a 64-bit one reference 1"""
+    whole = api.slot_index(0, 0, 0, 0)
+    mv, cost = np.zeros((2, 1, 593, 2), np.int16), np.full((2, 1, 593), 1 << 20, np.uint32)
+    mv[0, 0, whole], cost[0, 0, whole], cost[1, 0, whole] = (1024, 0), 1000, 900
+    sel = api.SelectParams(64, price_mv=1, part_mask=0x01, max_depth=0)
+    _, ref, _, total, _ = srm.select_refs_picture(mv, cost, sel, 64, 64, None, 0, None, lc.WRAP24, _wrapped)
+    assert set(ref.reshape(-1).tolist()) == {0} and total.tolist() == [1000]
+    _, ref, _, total, _ = srm.select_refs_picture(mv, cost, sel, 64, 64, None, 0, None, lc.WRAP24, _wide)
+    assert set(ref.reshape(-1).tolist()) == {1} and total.tolist() == [6361]
