@@ -313,3 +313,97 @@ def test_fractional_refinement_at_wrapping_lambdas_matches_reference(oracle_lib,
     assert all(n >= 4 for n in straddles.values()) and top >= 30, (straddles, top)
     assert not lc.wraps(lc.WRAP24, 22) and lc.wraps(lc.WRAP24, 24)
     reference.done()
+
+
+# ---- partial ties (tests/tie_content.py): where candidates cost the same the reference's answer is its loop order's alone, and so must the oracle's be ----
+def test_pu_searches_on_partial_ties_match_reference(oracle_lib, reference):
+    """per-PU integer search on the four skewed lattices (every slot has SAD 0 on a lattice of candidates; the MV cost leaves several of them
+    tied), search range 8, lambda_q16 0, 1 << 13, 1 << 16 and that of 57.9, 8 and 10 bit, FEN 0 and 1; and on two pictures that hold the
+    CTU's block twice, at search ranges 64 and 128"""
+    import tie_content as tc
+    from hmme import synth
+    from refine_tables import oracle_windows
+    R = oracle_lib.ref() if reference.live else None
+    rng = np.random.default_rng(3201)
+    table = oracle_lib.slot_table()
+    m, w, sr = synth.MARGIN, 192, 8
+    o = m + 64                                        # CTU 4 of the 192 x 192 picture
+    tied = 0
+    for lattice in tc.LATTICES:
+        for lq in tc.SEARCH_LAMBDA_Q16:
+            lam = _edge_lambda(reference, R, lq)
+            for bd in (8, 10):
+                cur, ref = tc.skewed_lattice(w, w, *lattice, bd, seed=11)
+                for fen in (0, 1):
+                    pred = rng.integers(-32, 33, size=(9, 2)).astype(np.int16)
+                    win = oracle_windows(w, w, sr, pred)[4]
+                    pq = (int(pred[4, 0]), int(pred[4, 1]))
+                    p = oracle_lib.make_params((int(win[0]), int(win[1])), (int(win[2]), int(win[3])), pq, lq, fen, bd)
+                    ox, oy, osad = oracle_lib.search_ctu(cur, (o, o), ref, (o, o), p)
+                    ts = tc.tie_set(win, pq, lq, lattice, tc.LATTICE_SHIFT, (w, w, 64, 64))
+                    tied += len(ts["members"]) >= 2
+                    for s in [592, 0] + [int(v) for v in rng.choice(np.arange(1, 592), size=23, replace=False)]:
+                        x, y, bw, bh = (int(v) for v in table[s])
+                        want = tuple(int(v) for v in reference.ask(lambda: oracle_lib.pattern_search(cur, (o + x, o + y), ref, (o + x, o + y), bw, bh, p, use_ref=True, lam=lam)))
+                        assert (int(ox[s]), int(oy[s]), int(osad[s])) == want, (lattice, lq, bd, fen, s, pq)
+                        assert tuple(oracle_lib.pattern_search(cur, (o + x, o + y), ref, (o + x, o + y), bw, bh, p)) == want
+                    assert (int(ox[592]), int(oy[592]), int(osad[592])) == ts["raster_first"] + (0,), (lattice, lq, bd, fen, ts)
+    assert tied >= 32, tied                           # in at least half of the 64 cases the 64x64 slot had several candidates tied for the win
+    for (name, sr, a, b), bd, lq in ((tc.TWO_MATCH_8[0], 8, tc.Q16_57_9), (tc.TWO_MATCH_8[2], 10, 0)):
+        lam = _edge_lambda(reference, R, lq)
+        size = tc.two_match_size(sr)
+        _, cu_x, cu_y = tc.centre_ctu(size)
+        cur, ref = tc.two_match(bd, 31, a, b, size)
+        pq = tc.tie_predictor(a, b) if lq else (0, 0)
+        p = oracle_lib.make_params((-sr, -sr), (sr, sr), pq, lq, 1, bd)
+        ox, oy, osad = oracle_lib.search_ctu(cur, (m + cu_x, m + cu_y), ref, (m + cu_x, m + cu_y), p)
+        for s in [592, 0] + [int(v) for v in rng.choice(np.arange(1, 592), size=10, replace=False)]:
+            x, y, bw, bh = (int(v) for v in table[s])
+            want = tuple(int(v) for v in reference.ask(lambda: oracle_lib.pattern_search(cur, (m + cu_x + x, m + cu_y + y), ref, (m + cu_x + x, m + cu_y + y), bw, bh,
+                                                                                       p, use_ref=True, lam=lam)))
+            assert want == a + (0,) and (int(ox[s]), int(oy[s]), int(osad[s])) == want, (name, s, want)
+    reference.done()
+
+
+def test_fractional_refinement_on_partial_ties_matches_reference(oracle_lib, reference):
+    """plain and weighted xPatternSearchFracDIF on flat content (the MV cost alone decides), on content constant along x and on content constant
+    along y (the distortion ties along one axis), over the grid of predictor offsets -9..9 quarter pels in both components, lambda 0, 1.0 and
+    57.9, Hadamard and SAD, 8 and 10 bit.  Block sizes 8x4, 16x16, 12x16 and 64x64: each combination runs the whole grid at one of them, in
+    turn, and a seeded dozen of offsets at the three others"""
+    import tie_content as tc
+    from hmme import synth
+    if reference.live and not hasattr(oracle_lib.ref(), "ref_frac_refine_w"):
+        pytest.skip("libhmref.so predates the weighted-prediction harness")
+    rng = np.random.default_rng(3202)
+    sizes = ((8, 4), (16, 16), (12, 16), (64, 64))
+    grid = [(dx, dy) for dy in range(-9, 10) for dx in range(-9, 10)]
+    o = synth.MARGIN + 64
+    combo = 0
+    moved = {k: 0 for k in tc.REFINE_KINDS}
+    for kind in tc.REFINE_KINDS:
+        for bd in (8, 10):
+            cur, ref = tc.refine_content(kind, 192, 192, bd, seed=3)
+            for had in (0, 1):
+                for lam in tc.REFINE_LAMBDAS:
+                    lq = oracle_lib.oracle().hmo_lambda_q16(lam)
+                    assert lq == tc.lambda_q16_of(lam)
+                    for weighted in (False, True):
+                        whole = sizes[combo % 4]
+                        combo += 1
+                        for bw, bh in sizes:
+                            offs = grid if (bw, bh) == whole else [grid[i] for i in rng.choice(len(grid), size=12, replace=False)]
+                            for dx, dy in offs:
+                                mv = (int(rng.integers(-2, 3)), int(rng.integers(-2, 3)))
+                                pred = (4 * mv[0] - dx, 4 * mv[1] - dy)
+                                if weighted:
+                                    a = oracle_lib.frac_refine_w(cur, (o, o), ref, (o, o), bw, bh, mv, pred, lq, had, bd, tc.WP)
+                                    b = reference.ask(lambda: oracle_lib.frac_refine_w(cur, (o, o), ref, (o, o), bw, bh, mv, pred, lam, had, bd, tc.WP, use_ref=True))
+                                else:
+                                    a = oracle_lib.frac_refine(cur, (o, o), ref, (o, o), bw, bh, mv, pred, lq, had, bd)
+                                    b = reference.ask(lambda: oracle_lib.frac_refine(cur, (o, o), ref, (o, o), bw, bh, mv, pred, lam, had, bd, use_ref=True))
+                                assert tuple(a) == tuple(int(v) for v in b), (kind, bd, had, lam, weighted, (bw, bh), mv, pred)
+                                moved[kind] += a[:4] != (0, 0, 0, 0)
+                                if kind == "flat" and not weighted:
+                                    assert (4 * mv[0] + 2 * a[0] + a[2], 4 * mv[1] + 2 * a[1] + a[3]) == tc.flat_refine_model(mv, pred, lq)[:2]
+    assert all(n > 1000 for n in moved.values()), moved
+    reference.done()
