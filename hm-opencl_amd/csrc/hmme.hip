@@ -68,6 +68,36 @@ constexpr size_t lds_bytes16_c(int pdw, int strip_rows) { return (size_t)(2 * 59
 static_assert(lds_bytes16_c(kPdw16Large, 1) <= kLdsBudget16, "a one-row strip fits the LDS budget (strips_for terminates)");
 }  // namespace
 
+// One growable device allocation: every device buffer a context or a plane owns.  The capacity is in bytes; a use site takes a typed
+// view (as<T>).  grow: free and allocate anew -- hipFree synchronises the whole device
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  template <typename T> T* as() const { return (T*)p; }
+  hipError_t grow(size_t bytes) {
+    if (p) hipFree(p);
+    p = nullptr; cap = 0;
+    const hipError_t e = hipMalloc(&p, bytes);
+    if (e == hipSuccess) cap = bytes;
+    return e;
+  }
+};
+// the device buffers of a context: hmme_ctx::buf, freed by one loop in hmme_destroy
+enum Buf {
+  kCall,        // per-CTU path: the call block (kCall* offsets above), allocated by hmme_create
+  kFlag,        // int[4]: [0] synchronous uploads, [1] asynchronous uploads, [2] take_flag's result; hmme_create
+  kJobs,        // frame path scratch: MeJob[] or MeJob16[] of the searches (jobs_tag)
+  kFirstStrip,  // int[]: the jobs' first strips
+  kFracJobs,    // MeJob[] of the refinement launches that read a table (+ the job counter of the job-walking mode; frac_jobs_tag)
+  kBest,        // [jobs][593] 64-bit merge table of the split / strip / segment launches (best_clean)
+  kWp0, kWp1, kWp2, kWp3,   // weighted whole-picture calls: u16 copies of the planes of one launch (below)
+  kWwin,        // per-CTU calls with weighted prediction: the weighted copy of the staged window (the search's); first use
+  kFracCover,   // uint16[]: fractional refinement, the slots covering each 8x8 / 4x4 position, same for every CTU; first use
+  kWpEst,       // hmme_plane_stats / hmme_wp_estimate: the 64-bit sums of one call (kWpStat* below); first use
+  kStage,       // the staging arena of the synchronous, host-array forms (Stage)
+  kNumBufs
+};
+
 struct hmme_ctx {
   int device = 0;
   int sr_max = 64;
@@ -90,15 +120,12 @@ struct hmme_ctx {
   bool scratch_used = false;
   // per-CTU path: one device block and its pinned host mirror -- jobs, first-strip index, merge table preset, current
   // block, window -- so that a call is one upload, the kernels, one download (layout: kCall* offsets below)
-  uint8_t* d_call = nullptr;
+  DevBuf buf[kNumBufs];
   uint8_t* h_call = nullptr;
   uint8_t* h_call_dev = nullptr;  // device-side address of h_call (mapped pinned memory)
   uint8_t* h_res = nullptr;       // 593 MVs (int16 x, y), 593 SADs, then the completion word: pinned host memory the finalize kernel writes
   uint8_t* d_res = nullptr;       // ... and its device-side address
   uint32_t call_seq = 0;
-  // frame path scratch (grown on demand)
-  void* d_jobs = nullptr;         // MeJob[] or MeJob16[]
-  size_t jobs_bytes = 0;
   // A job table is a function of the picture size, the search range, the CTU range, the number of pairs and the predictors.  Launches
   // WITHOUT predictors (d_pred_q == null: the zero predictor of the reference's own call) of the same geometry on the same stream find
   // the table of the launch before still in place and skip the kernels that write it -- one kernel launch less per search step.
@@ -112,46 +139,20 @@ struct hmme_ctx {
              buf == o.buf && buf2 == o.buf2 && stream == o.stream;
     }
   };
-  TableTag jobs_tag;              // what d_jobs / d_first_strip hold (searches)
-  void* d_frac_jobs = nullptr;    // MeJob[] of the refinement launches that read a table (+ the job counter of the job-walking mode)
-  size_t frac_jobs_bytes = 0;
-  TableTag frac_jobs_tag;
+  TableTag jobs_tag;              // what kJobs / kFirstStrip hold (searches)
+  TableTag frac_jobs_tag;         // ... and kFracJobs
   int wg_slots = 512;     // search workgroups resident at once: 2 per CU (VGPRs of the search kernels, LDS of the 16-bit one)
-  int* d_first_strip = nullptr;
-  int first_strip_cap = 0;
-  unsigned long long* d_best = nullptr;   // [jobs][593] merge table of the split / strip / segment launches
-  size_t best_cap = 0;
-  bool best_clean = false;   // every entry of d_best is all ones: me_finalize16_kernel resets what it decodes, so only a table that is new, has
+  bool best_clean = false;   // every entry of kBest is all ones: me_finalize16_kernel resets what it decodes, so only a table that is new, has
                              // grown or was left behind by a failed launch needs the preset (merge_table)
-  int16_t* d_pred = nullptr;
-  int16_t* d_mv = nullptr;
-  uint32_t* d_sad = nullptr;
-  int out_cap = 0;
-  int* d_flag = nullptr;
   bool lds_optin[8] = {false, false, false, false, false, false, false, false};
   int num_cus = 0;
   bool frac_lds_optin[6] = {false, false, false, false, false, false};   // per build of me_frac_kernel (FracBuild::index)
   int frac_wg_per_cu[6] = {0, 0, 0, 0, 0, 0};   // same index: workgroups of that me_frac_kernel a CU holds (runtime occupancy query, first use)
-  uint8_t* d_wwin = nullptr;          // per-CTU calls with weighted prediction: the weighted copy of the staged window (the search's)
-  uint16_t* d_frac_cover = nullptr;   // fractional refinement: slots covering each 8x8 / 4x4 position, same for every CTU
-  int16_t* d_imv = nullptr;           // host-facing refine call: integer MVs / quarter-pel MVs / costs on the device
-  int16_t* d_qmv = nullptr;
-  uint32_t* d_fcost = nullptr;
-  size_t refine_cap = 0;
-  // weighted whole-picture calls (hmme_search_pairs_w_device / hmme_refine_pairs_w_device): u16 copies of the planes of one launch, one
-  // per pair, grown on demand -- [0] weighted reference planes and [1] biased CTU-blocked current pictures (search); [2] raw reference
-  // planes widened from 8 bit and [3] biased padded current pictures (refinement).  Scratch like the job tables: scratch_acquire / launch_end
-  uint8_t* d_wp[4] = {nullptr, nullptr, nullptr, nullptr};
-  size_t wp_cap[4] = {0, 0, 0, 0};
-  // host-facing bi-prediction / prediction calls (hmme_search_frame_bi, hmme_refine_frame_bi, hmme_predict_frame): device staging for the
-  // motion field and the window centres [0] and for the predicted picture [1]
-  uint8_t* d_bi[2] = {nullptr, nullptr};
-  size_t bi_cap[2] = {0, 0};
-  // hmme_select_frame: device staging for the tables, the predictors and the three results of one picture
-  uint8_t* d_sel = nullptr;
-  size_t sel_cap = 0;
-  // hmme_plane_stats / hmme_wp_estimate: the 64-bit sums of one call (kWpStat* below), allocated at first use
-  unsigned long long* d_wpest = nullptr;
+  // kWp0..kWp3, weighted whole-picture calls (hmme_search_pairs_w_device / hmme_refine_pairs_w_device): one copy per pair, grown on
+  // demand -- kWp0 weighted reference planes and kWp1 biased CTU-blocked current pictures (search); kWp2 raw reference planes widened
+  // from 8 bit and kWp3 biased padded current pictures (refinement).  Scratch like the job tables: scratch_acquire / launch_end
+  uint8_t* wp(int i) const { return buf[kWp0 + i].as<uint8_t>(); }
+  uint8_t* d_call() const { return buf[kCall].as<uint8_t>(); }
 };
 
 struct hmme_plane {
@@ -167,8 +168,7 @@ struct hmme_plane {
   // the picture's size: me_kernels.hpp me_prefetch_cur).  Written by every fill right behind the padded plane (plane_fill).
   uint8_t* d_blocks = nullptr;
   int ctus_x = 0, n_ctu = 0;
-  void* d_stage = nullptr;  // device staging for uploads
-  size_t stage_bytes = 0;
+  DevBuf stage;   // device staging for uploads
   hipEvent_t filled = nullptr;      // recorded after the last fill; readers on another stream wait for it
   hipStream_t fill_stream = nullptr;
   bool fill_pending = false;
@@ -202,19 +202,94 @@ int fail(hmme_ctx* ctx, int code, const char* fmt, ...) {
     if (e_ != hipSuccess) return fail(ctx, HMME_ERR_DEVICE, "%s -> %s", #call, hipGetErrorString(e_));   \
   } while (0)
 
-template <typename T>
-int ensure(hmme_ctx* ctx, T** p, size_t* cap_bytes, size_t bytes, size_t grow_to = 0) {
-  if (bytes <= *cap_bytes) return HMME_OK;
+// `b` holds at least `bytes`.  *moved: the allocation was replaced (or lost, where this fails) -- what it held is gone
+int ensure(hmme_ctx* ctx, DevBuf& b, size_t bytes, size_t grow_to = 0, bool* moved = nullptr) {
+  if (moved) *moved = false;
+  if (bytes <= b.cap) return HMME_OK;
   // hipFree synchronises the whole device -- in the middle of a streaming pipeline that stalls the copy and download streams.  A
   // scratch that has to grow therefore grows to `grow_to` at once (the callers pass what kMaxRefs pairs of this picture size need:
   // KBs to a few MB), so a steady stream meets this path on its first launch of a picture size and never again.
   if (grow_to > bytes) bytes = grow_to;
-  if (*p) hipFree(*p);
-  *p = nullptr; *cap_bytes = 0;
-  HIP_TRY(ctx, hipMalloc((void**)p, bytes));
-  *cap_bytes = bytes;
+  if (moved) *moved = true;
+  HIP_TRY(ctx, b.grow(bytes));
   return HMME_OK;
 }
+
+// ---- the staging arena of the synchronous, host-array forms -----------------------------------------------------------
+// Every hmme_*_frame* entry point has the same shape: lay its host arrays out in one device buffer (kStage), grow it, copy up, run the
+// *_device form on ctx->stream, copy down, wait.  A call describes its arrays as items (in / out / image), begin() places and uploads
+// them, at() hands the device addresses to the launch, end() downloads and makes the call's one hipStreamSynchronize.  The arena grows to
+// exactly what a call needs and never shrinks; an error returns without a wait.
+constexpr size_t kStageAlign = 256;   // every item starts like an allocation of its own would (the select kernels need 8 bytes)
+// the pure layout: item i of bytes[i] at offsets[i], a multiple of kStageAlign; an empty item takes no room.  Returns the arena's size
+size_t stage_layout(const size_t* bytes, int n, size_t* offsets) {
+  size_t total = 0;
+  for (int i = 0; i < n; ++i) {
+    offsets[i] = total;
+    total += (bytes[i] + kStageAlign - 1) & ~(kStageAlign - 1);
+  }
+  return total;
+}
+struct Stage {
+  struct Item {
+    size_t bytes = 0;                       // on the device; 0: the caller has no such array, at() is null
+    const void* up[2] = {nullptr, nullptr}; // linear in: one host array, or two of up_bytes each that travel one behind the other
+    size_t up_bytes = 0;
+    void* down = nullptr;                   // linear out and image: the host array
+    size_t parts = 0, part_bytes = 0, off = 0, len = 0;   // linear out: of each of `parts` equal parts the bytes [off, off + len) come back
+    size_t row = 0, rows = 0, stride = 0;   // image: rows of `row` bytes, `stride` bytes apart at the host, packed on the device
+  };
+  hmme_ctx* ctx;
+  std::vector<Item> items;
+  std::vector<size_t> at_;
+  explicit Stage(hmme_ctx* c) : ctx(c) {}
+  int add(const Item& it) { items.push_back(it); return (int)items.size() - 1; }
+  // each returns the item's index for at().  A null host pointer reserves nothing
+  int in(const void* host, size_t bytes, const void* host2 = nullptr) {
+    Item it;
+    if (host && bytes) { it.bytes = host2 ? 2 * bytes : bytes; it.up[0] = host; it.up[1] = host2; it.up_bytes = bytes; }
+    return add(it);
+  }
+  int out(void* host, size_t part_bytes, size_t off, size_t len, size_t parts = 1) {
+    Item it;
+    if (host && len) { it.bytes = parts * part_bytes; it.down = host; it.parts = parts; it.part_bytes = part_bytes; it.off = off; it.len = len; }
+    return add(it);
+  }
+  // in and out: uploaded before the launch, so samples the kernel does not write come back as they were
+  int image(void* host, size_t row, size_t rows, size_t stride) {
+    Item it;
+    if (host && row * rows) { it.bytes = row * rows; it.down = host; it.row = row; it.rows = rows; it.stride = stride; }
+    return add(it);
+  }
+  uint8_t* at(int i) const { return items[i].bytes ? ctx->buf[kStage].as<uint8_t>() + at_[i] : nullptr; }
+  int begin() {
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<size_t> bytes;
+    for (const Item& it : items) bytes.push_back(it.bytes);
+    at_.resize(items.size());
+    const int rc = ensure(ctx, ctx->buf[kStage], stage_layout(bytes.data(), (int)bytes.size(), at_.data()));
+    if (rc) return rc;
+    for (size_t i = 0; i < items.size(); ++i) {
+      const Item& it = items[i];
+      if (it.row) HIP_TRY(ctx, hipMemcpy2DAsync(at((int)i), it.row, it.down, it.stride, it.row, it.rows, hipMemcpyHostToDevice, ctx->stream));
+      for (int k = 0; k < 2; ++k)
+        if (it.up[k]) HIP_TRY(ctx, hipMemcpyAsync(at((int)i) + k * it.up_bytes, it.up[k], it.up_bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return HMME_OK;
+  }
+  int end() {
+    for (size_t i = 0; i < items.size(); ++i) {
+      const Item& it = items[i];
+      if (it.row) HIP_TRY(ctx, hipMemcpy2DAsync(it.down, it.stride, at((int)i), it.row, it.row, it.rows, hipMemcpyDeviceToHost, ctx->stream));
+      for (size_t p = 0; p < it.parts; ++p) {
+        const size_t o = p * it.part_bytes + it.off;
+        HIP_TRY(ctx, hipMemcpyAsync((uint8_t*)it.down + o, at((int)i) + o, it.len, hipMemcpyDeviceToHost, ctx->stream));
+      }
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return HMME_OK;
+  }
+};
 
 // cross-stream ordering (see hmme.h "Streams"): scratch of the context, contents of a plane
 int scratch_acquire(hmme_ctx* ctx, hipStream_t s) {
@@ -298,22 +373,22 @@ int launch_search8(hmme_ctx* ctx, const RefSet& cur, int cur_ctus_x, const RefSe
 int finalize_best(hmme_ctx* ctx, unsigned long long* d_best, const MeJob16* d_jobs, const int* d_first_strip, int n_jobs, int16_t* d_mv,
                   uint32_t* d_sad, hipStream_t stream);
 
-// the 64-bit merge table of a split / strip / tile launch: the caller's (already all ones), or ctx->d_best grown and preset here
+// the 64-bit merge table of a split / strip / tile launch: the caller's (already all ones), or the context's (kBest) grown and preset here
 int merge_table(hmme_ctx* ctx, int n_jobs, unsigned long long* preset, hipStream_t stream, unsigned long long** table) {
   if (preset) { *table = preset; return HMME_OK; }
-  size_t cap = ctx->best_cap;
-  int rc = ensure(ctx, &ctx->d_best, &cap, sizeof(unsigned long long) * HMME_NUM_CTU_PARTS * (size_t)n_jobs,
-                  n_jobs > 64 ? sizeof(unsigned long long) * HMME_NUM_CTU_PARTS * (size_t)n_jobs * 2 : 0);
-  if (cap != ctx->best_cap) ctx->best_clean = false;
-  ctx->best_cap = cap;
+  DevBuf& best = ctx->buf[kBest];
+  bool moved;
+  const int rc = ensure(ctx, best, sizeof(unsigned long long) * HMME_NUM_CTU_PARTS * (size_t)n_jobs,
+                        n_jobs > 64 ? sizeof(unsigned long long) * HMME_NUM_CTU_PARTS * (size_t)n_jobs * 2 : 0, &moved);
+  if (moved) ctx->best_clean = false;
   if (rc) return rc;
-  if (!ctx->best_clean) HIP_TRY(ctx, hipMemsetAsync(ctx->d_best, 0xFF, ctx->best_cap, stream));
+  if (!ctx->best_clean) HIP_TRY(ctx, hipMemsetAsync(best.p, 0xFF, best.cap, stream));
   ctx->best_clean = false;   // until the launch's finalize_best has been enqueued (it sets every entry it decodes back to all ones)
-  *table = ctx->d_best;
+  *table = best.as<unsigned long long>();
   return HMME_OK;
 }
 
-// 8-bit split mode: n_jobs * n_split workgroups, each runs a slice of its CTU's tasks and merges through ctx->d_best
+// 8-bit split mode: n_jobs * n_split workgroups, each runs a slice of its CTU's tasks and merges through the merge table
 int launch_search8_split(hmme_ctx* ctx, const RefSet& cur, int cur_ctus_x, const RefSet& ref, int ref_pitch, const MeJob16* d_jobs,
                          const int* d_first_strip, int n_jobs, int n_split, int fen, int16_t* d_mv, uint32_t* d_sad,
                          hipStream_t stream, unsigned long long* preset_best = nullptr, bool finalize = true) {
@@ -379,7 +454,7 @@ int launch16_t(hmme_ctx* ctx, const RefSet& cur, int cur_ctus_x, const RefSet& r
   return HMME_OK;
 }
 
-// d_jobs: n_jobs * n_strips MeJob16; results merged in ctx->d_best then decoded into d_mv / d_sad
+// d_jobs: n_jobs * n_strips MeJob16; results merged in the merge table then decoded into d_mv / d_sad
 int launch_search16(hmme_ctx* ctx, const RefSet& cur, int cur_ctus_x, const RefSet& ref, int ref_pitch, const MeJob16* d_jobs,
                     const int* d_first_strip, int n_jobs, int n_wg, int pdw, int strip_rows_max, int fen, int bit_depth,
                     int16_t* d_mv, uint32_t* d_sad, hipStream_t stream, unsigned long long* preset_best = nullptr, bool finalize = true) {
@@ -402,7 +477,7 @@ int finalize_best(hmme_ctx* ctx, unsigned long long* d_best, const MeJob16* d_jo
   hipLaunchKernelGGL(hmme::me_finalize16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, d_best, d_jobs,
                      d_first_strip, n_jobs, ctx->lambda_q16, d_mv, d_sad);
   HIP_TRY(ctx, hipGetLastError());
-  if (d_best == ctx->d_best) ctx->best_clean = true;   // the launches of a context are one chain (scratch_acquire): the next one finds the table reset
+  if (d_best == ctx->buf[kBest].p) ctx->best_clean = true;   // the launches of a context are one chain (scratch_acquire): the next one finds the table reset
   return HMME_OK;
 }
 
@@ -434,9 +509,9 @@ int check_frame_args(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref
 // by the asynchronous ones (taken by hmme_upload_status) -- a bad sample of an asynchronous upload can no longer fail the next
 // synchronous upload of another, valid plane.  Read and clear are one atomic exchange on the stream (me_take_flag_kernel).
 int take_flag(hmme_ctx* ctx, int which, hipStream_t s, int* out) {
-  hipLaunchKernelGGL(hmme::me_take_flag_kernel, dim3(1), dim3(1), 0, s, ctx->d_flag + which, ctx->d_flag + 2);
+  hipLaunchKernelGGL(hmme::me_take_flag_kernel, dim3(1), dim3(1), 0, s, ctx->buf[kFlag].as<int>() + which, ctx->buf[kFlag].as<int>() + 2);
   HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_flag + 2, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->buf[kFlag].as<int>() + 2, sizeof(int), hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipStreamSynchronize(s));
   return HMME_OK;
 }
@@ -449,7 +524,7 @@ int plane_fill(hmme_plane* pl, const SrcT* d_src, int src_pitch_elems, hipStream
   if (wrc) return wrc;
   dim3 grid((pl->pitch / 4 + 255) / 256, pl->rows);
   hipLaunchKernelGGL((hmme::me_fill_plane_kernel<SrcT, DstT>), grid, dim3(256), 0, s, pl->d_data, pl->pitch, kMarginX, kMarginY,
-                     pl->width, pl->height, d_src, src_pitch_elems, (1 << pl->bit_depth) - 1, ctx->d_flag + (check ? 0 : 1));
+                     pl->width, pl->height, d_src, src_pitch_elems, (1 << pl->bit_depth) - 1, ctx->buf[kFlag].as<int>() + (check ? 0 : 1));
   HIP_TRY(ctx, hipGetLastError());
   // ... and the CTU-blocked copy the searches read the current picture from (one more pass over the staged picture: 8 MB at 2160p)
   const long blk_threads = (long)pl->n_ctu * (hmme::kBlkBytes8 * pl->bps / 4);
@@ -478,18 +553,15 @@ int plane_upload(hmme_plane* pl, const T* origin, int stride, hipStream_t s, boo
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (sync) s = ctx->stream;
   const size_t bytes = sizeof(T) * (size_t)pl->width * pl->height;
-  if (pl->stage_bytes < bytes) {
-    if (pl->fill_pending) HIP_TRY(ctx, hipEventSynchronize(pl->filled));   // a fill may still be reading the old staging buffer
-    hipFree(pl->d_stage); pl->d_stage = nullptr; pl->stage_bytes = 0;
-    HIP_TRY(ctx, hipMalloc(&pl->d_stage, bytes));
-    pl->stage_bytes = bytes;
-  }
-  int rc = plane_write_wait(ctx, pl, s);   // the staging buffer is read by the previous fill
+  if (pl->stage.cap < bytes && pl->fill_pending) HIP_TRY(ctx, hipEventSynchronize(pl->filled));   // a fill may still be reading the old staging buffer
+  int rc = ensure(ctx, pl->stage, bytes);
   if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpy2DAsync(pl->d_stage, sizeof(T) * pl->width, origin, sizeof(T) * (size_t)stride, sizeof(T) * pl->width,
+  rc = plane_write_wait(ctx, pl, s);   // the staging buffer is read by the previous fill
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemcpy2DAsync(pl->stage.p, sizeof(T) * pl->width, origin, sizeof(T) * (size_t)stride, sizeof(T) * pl->width,
                                 pl->height, hipMemcpyHostToDevice, s));
-  if (pl->bps == 1) return plane_fill<T, uint8_t>(pl, (const T*)pl->d_stage, pl->width, s, sync);
-  return plane_fill<T, uint16_t>(pl, (const T*)pl->d_stage, pl->width, s, sync);
+  if (pl->bps == 1) return plane_fill<T, uint8_t>(pl, pl->stage.as<const T>(), pl->width, s, sync);
+  return plane_fill<T, uint16_t>(pl, pl->stage.as<const T>(), pl->width, s, sync);
 }
 
 }  // namespace
@@ -532,7 +604,7 @@ int hmme_create(int device, int sr_max, unsigned flags, hmme_ctx** out) {
   } while (0)
   CREATE_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
   for (int i = 0; i < hmme_ctx::kLaunchEvents; ++i) CREATE_TRY(hipEventCreateWithFlags(&ctx->launch_ev[i], hipEventDisableTiming));
-  CREATE_TRY(hipMalloc(&ctx->d_call, kCallWin + win_bytes));
+  CREATE_TRY(ctx->buf[kCall].grow(kCallWin + win_bytes));
   CREATE_TRY(hipHostMalloc(&ctx->h_call, kCallWin + win_bytes, hipHostMallocMapped));
   CREATE_TRY(hipHostGetDevicePointer((void**)&ctx->h_call_dev, ctx->h_call, 0));
   std::memset(ctx->h_call, 0, kCallWin);
@@ -540,8 +612,8 @@ int hmme_create(int device, int sr_max, unsigned flags, hmme_ctx** out) {
   CREATE_TRY(hipHostMalloc(&ctx->h_res, kResBytes, hipHostMallocMapped));
   std::memset(ctx->h_res, 0, kResBytes);
   CREATE_TRY(hipHostGetDevicePointer((void**)&ctx->d_res, ctx->h_res, 0));
-  CREATE_TRY(hipMalloc(&ctx->d_flag, 4 * sizeof(int)));   // [0] synchronous uploads, [1] asynchronous uploads, [2] take_flag's result
-  CREATE_TRY(hipMemset(ctx->d_flag, 0, 4 * sizeof(int)));
+  CREATE_TRY(ctx->buf[kFlag].grow(4 * sizeof(int)));
+  CREATE_TRY(hipMemset(ctx->buf[kFlag].p, 0, 4 * sizeof(int)));
 #undef CREATE_TRY
   *out = ctx;
   return HMME_OK;
@@ -553,14 +625,7 @@ void hmme_destroy(hmme_ctx* ctx) {
   if (ctx->stream) { hipStreamSynchronize(ctx->stream); hipStreamDestroy(ctx->stream); }
   for (int i = 0; i < hmme_ctx::kLaunchEvents; ++i)
     if (ctx->launch_ev[i]) hipEventDestroy(ctx->launch_ev[i]);
-  hipFree(ctx->d_call);
-  hipFree(ctx->d_jobs); hipFree(ctx->d_frac_jobs); hipFree(ctx->d_first_strip); hipFree(ctx->d_best);
-  hipFree(ctx->d_pred); hipFree(ctx->d_mv); hipFree(ctx->d_sad); hipFree(ctx->d_flag);
-  hipFree(ctx->d_wwin); hipFree(ctx->d_frac_cover); hipFree(ctx->d_imv); hipFree(ctx->d_qmv); hipFree(ctx->d_fcost);
-  for (int i = 0; i < 4; ++i) hipFree(ctx->d_wp[i]);
-  for (int i = 0; i < 2; ++i) hipFree(ctx->d_bi[i]);
-  hipFree(ctx->d_sel);
-  hipFree(ctx->d_wpest);
+  for (DevBuf& b : ctx->buf) hipFree(b.p);
   if (ctx->h_call) hipHostFree(ctx->h_call);
   if (ctx->h_res) hipHostFree(ctx->h_res);
   delete ctx;
@@ -926,24 +991,24 @@ int ctu_call(hmme_ctx* ctx, const int16_t* ctu, int ctu_stride, const int16_t* r
   std::memcpy(ctx->h_call + kCallFracJob, &job, sizeof job);
   {
     const int n16 = (int)((kCallWin + (size_t)rows * kWinPitch + 64 + 15) / 16);
-    hipLaunchKernelGGL(hmme::me_stage_call_kernel, dim3((n16 + 255) / 256), dim3(256), 0, s, (const uint4*)ctx->h_call_dev, (uint4*)ctx->d_call, n16);
+    hipLaunchKernelGGL(hmme::me_stage_call_kernel, dim3((n16 + 255) / 256), dim3(256), 0, s, (const uint4*)ctx->h_call_dev, (uint4*)ctx->d_call(), n16);
     HIP_TRY(ctx, hipGetLastError());
     if (wp && do_search) {   // the weighted window the integer search runs on; the raw one stays where it is for the refinement's interpolation
-      if (!ctx->d_wwin) {   // cleared once: rows below a call's window hold zeros or an earlier call's samples, never what the allocator left
-        HIP_TRY(ctx, hipMalloc(&ctx->d_wwin, (size_t)kWinRows * kWinPitch + 64));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_wwin, 0, (size_t)kWinRows * kWinPitch + 64, s));
-      }
-      hipLaunchKernelGGL(hmme::me_weight_window_kernel, dim3((rows * (cols + 8) + 255) / 256), dim3(256), 0, s, (const uint8_t*)(ctx->d_call + kCallWin), ctx->d_wwin,
+      bool fresh;   // cleared once: rows below a call's window hold zeros or an earlier call's samples, never what the allocator left
+      const int erc = ensure(ctx, ctx->buf[kWwin], (size_t)kWinRows * kWinPitch + 64, 0, &fresh);
+      if (erc) return erc;
+      if (fresh) HIP_TRY(ctx, hipMemsetAsync(ctx->buf[kWwin].p, 0, (size_t)kWinRows * kWinPitch + 64, s));
+      hipLaunchKernelGGL(hmme::me_weight_window_kernel, dim3((rows * (cols + 8) + 255) / 256), dim3(256), 0, s, (const uint8_t*)(ctx->d_call() + kCallWin), ctx->buf[kWwin].as<uint8_t>(),
                          (int)kWinPitch, rows, cols, wp->w0, wp->round, wp->shift, wp->offset + bias);
       HIP_TRY(ctx, hipGetLastError());
     }
   }
   // the kernel addresses ref(ctu + lt): bias the base so that (lt_x, lt_y) lands on the window copy's first sample
-  const uint8_t* ref_base = ctx->d_call + kCallWin - (long)(p->lt_y - halo) * kWinPitch - (long)(p->lt_x - halo) * bps;
-  const uint8_t* ref_base_search = wp ? ctx->d_wwin - (long)(p->lt_y - halo) * kWinPitch - (long)(p->lt_x - halo) * bps : ref_base;
-  const MeJob16* d_js = (const MeJob16*)(ctx->d_call + kCallJobs);
-  const int* d_first = (const int*)(ctx->d_call + kCallFirst);
-  unsigned long long* d_best1 = (unsigned long long*)(ctx->d_call + kCallBest);
+  const uint8_t* ref_base = ctx->d_call() + kCallWin - (long)(p->lt_y - halo) * kWinPitch - (long)(p->lt_x - halo) * bps;
+  const uint8_t* ref_base_search = wp ? ctx->buf[kWwin].as<uint8_t>() - (long)(p->lt_y - halo) * kWinPitch - (long)(p->lt_x - halo) * bps : ref_base;
+  const MeJob16* d_js = (const MeJob16*)(ctx->d_call() + kCallJobs);
+  const int* d_first = (const int*)(ctx->d_call() + kCallFirst);
+  unsigned long long* d_best1 = (unsigned long long*)(ctx->d_call() + kCallBest);
   // the 4.7 KB of results go straight into pinned host memory (mapped into the device's address space): no download step
   int16_t* d_mv1 = (int16_t*)(ctx->d_res + kResMv);
   uint32_t* d_sad1 = (uint32_t*)(ctx->d_res + kResSad);
@@ -951,9 +1016,9 @@ int ctu_call(hmme_ctx* ctx, const int16_t* ctu, int ctu_stride, const int16_t* r
   const uint32_t seq = ++ctx->call_seq ? ctx->call_seq : ++ctx->call_seq;   // never 0, the words' initial value
   if (do_search) {
   if (!wide)
-    rc = launch_search8_split(ctx, one_ref(ctx->d_call + kCallCtu), 1, one_ref(ref_base), kWinPitch, d_js, d_first, 1, n_wg, p->fen, d_mv1, d_sad1, s, d_best1, false);
+    rc = launch_search8_split(ctx, one_ref(ctx->d_call() + kCallCtu), 1, one_ref(ref_base), kWinPitch, d_js, d_first, 1, n_wg, p->fen, d_mv1, d_sad1, s, d_best1, false);
   else
-    rc = launch_search16(ctx, one_ref(ctx->d_call + kCallCtu), 1, one_ref(ref_base_search), kWinPitch, d_js, d_first, 1, n_wg, pdw, smax, wp ? 0 : p->fen, shift_bd,   // xGetSADw reads every row
+    rc = launch_search16(ctx, one_ref(ctx->d_call() + kCallCtu), 1, one_ref(ref_base_search), kWinPitch, d_js, d_first, 1, n_wg, pdw, smax, wp ? 0 : p->fen, shift_bd,   // xGetSADw reads every row
                          d_mv1, d_sad1, s, d_best1, false);
   if (rc) return rc;
   hipLaunchKernelGGL(hmme::me_finalize1_kernel, dim3(1), dim3(640), 0, s, d_best1, d_js, ctx->lambda_q16, d_mv1, d_sad1,
@@ -965,14 +1030,14 @@ int ctu_call(hmme_ctx* ctx, const int16_t* ctu, int ctu_stride, const int16_t* r
     // its input the integer tables the finalize kernel just wrote (or the caller's), its output in the same pinned block
     rc = build_frac_cover(ctx);
     if (rc) return rc;
-    const int16_t* d_imv = do_search ? d_mv1 : (const int16_t*)(ctx->d_call + kCallImv);
+    const int16_t* d_imv = do_search ? d_mv1 : (const int16_t*)(ctx->d_call() + kCallImv);
     // weighted: the interpolated prediction is weighted sample by sample (me_frac_eval0 / me_frac_eval1, FracWp); the current samples carry `bias`, the raw window none
     const hmme::FracWp fw = wp ? hmme::FracWp{std::ldexp((float)wp->w0, -wp->shift), std::ldexp((float)wp->round, -wp->shift), (float)(bias + wp->offset)} : kNoWp;
     const FracBuild build = {wide ? 1 : 0, refine_had ? 1 : 0, wp ? 1 : 0};
     rc = frac_lds_optin(ctx, build);
     if (rc) return rc;
-    hipLaunchKernelGGL(frac_kernel(build), dim3(1), dim3(hmme::frac_threads(bps)), hmme::frac_lds_bytes(bps), s, one_ref(ctx->d_call + kCallCtu),
-                       64 * bps, one_ref(ref_base), kWinPitch, (const MeJob*)(ctx->d_call + kCallFracJob), kNoPrep, 1, (uint32_t*)nullptr, ctx->d_frac_cover, d_imv, ctx->lambda_q16,
+    hipLaunchKernelGGL(frac_kernel(build), dim3(1), dim3(hmme::frac_threads(bps)), hmme::frac_lds_bytes(bps), s, one_ref(ctx->d_call() + kCallCtu),
+                       64 * bps, one_ref(ref_base), kWinPitch, (const MeJob*)(ctx->d_call() + kCallFracJob), kNoPrep, 1, (uint32_t*)nullptr, ctx->buf[kFracCover].as<uint16_t>(), d_imv, ctx->lambda_q16,
                        p->bit_depth | ((bipred_origin && !wp) ? 0x100 : 0), fw, (int16_t*)(ctx->d_res + kResQmv), (uint32_t*)(ctx->d_res + kResCost));
     HIP_TRY(ctx, hipGetLastError());
     hipLaunchKernelGGL(hmme::me_publish_kernel, dim3(1), dim3(1), 0, s, (volatile uint32_t*)(ctx->d_res + kResDone2), seq);
@@ -1059,7 +1124,7 @@ void hmme_plane_destroy(hmme_plane* pl) {
   if (pl->filled) hipEventDestroy(pl->filled);
   hipFree(pl->d_data);
   hipFree(pl->d_blocks);
-  hipFree(pl->d_stage);
+  hipFree(pl->stage.p);
   delete pl;
 }
 
@@ -1090,7 +1155,7 @@ int hmme_upload_status(hmme_ctx* ctx, void* stream) {
 
 uint64_t hmme_test_device_address(const hmme_ctx* ctx, const hmme_plane* pl) {
   if (pl) return (uint64_t)(uintptr_t)pl->origin();
-  return ctx ? (uint64_t)(uintptr_t)(ctx->d_call + kCallCtu) : 0;
+  return ctx ? (uint64_t)(uintptr_t)(ctx->d_call() + kCallCtu) : 0;
 }
 
 #ifdef ME_SEARCH_T_TIMELINE   // timing-only builds (tools/search16_timeline.py): the per-workgroup stamps me_search16_kernel left
@@ -1112,6 +1177,12 @@ int hmme_test_picture_job(int job, int ctu_first, int ctu_count, int pic_w, int 
   const MeJob j = hmme::me_picture_job(job, pred_q, center_q, ctu_first, ctu_count, pic_w, pic_h, sr);
   std::memcpy(out, &j, sizeof j);
   return HMME_OK;
+}
+
+int hmme_test_stage_layout(const size_t* bytes, int n, size_t* offsets, size_t* total) {
+  if (!bytes || !offsets || !total || n < 0) return -1;
+  *total = stage_layout(bytes, n, offsets);
+  return (int)kStageAlign;
 }
 
 int hmme_abi_version(void) { return HMME_ABI_VERSION; }
@@ -1173,9 +1244,9 @@ struct FramePlan {
   int tail_parts = 1;      // 16-bit: strips of a tail job
   int tail_wgs = 0;        // 8-bit: workgroups (= segments) of the tail
   int n_wg16 = 0;          // 16-bit: workgroups of the launch
-  size_t table_bytes = 0, table_grow = 0;   // the job table in ctx->d_jobs, and what a table that has to grow grows to (kMaxRefs references of this picture size)
-  size_t tail_jobs_off = 0;   // kHeadThenSegments8: where the tail's segment table (me_seg_table_*) starts in it; the other tables start at ctx->d_jobs
-  bool first_strip = false;   // the launch decodes through ctx->d_first_strip (me_finalize16_kernel): every mode but kWhole8
+  size_t table_bytes = 0, table_grow = 0;   // the job table in the context's kJobs, and what a table that has to grow grows to (kMaxRefs references of this picture size)
+  size_t tail_jobs_off = 0;   // kHeadThenSegments8: where the tail's segment table (me_seg_table_*) starts in it; the other tables start at its first byte
+  bool first_strip = false;   // the launch decodes through kFirstStrip (me_finalize16_kernel): every mode but kWhole8
 };
 
 // pieces per tail job that finish `tail` jobs soonest: rounds of `slots` workgroups, each as long as its piece of a whole job
@@ -1296,24 +1367,22 @@ int hmme_test_tail_plan(int width, int height, int search_range, int n_pairs, in
 static int prep_jobs(hmme_ctx* ctx, const hmme_plane* cur, const hmme_frame_params* fp, const void* d_pred_q, int first, int count,
                      int n_refs, hipStream_t s, const FramePlan& pl, const void* d_center_q = nullptr) {
   const int jobs = pl.jobs, head = pl.tail_first, n_tail = jobs - head, w = cur->width, h = cur->height, sr = fp->search_range;
-  size_t cap = ctx->jobs_bytes;
-  int rc = ensure(ctx, (uint8_t**)&ctx->d_jobs, &cap, pl.table_bytes, pl.table_grow);
-  if (cap != ctx->jobs_bytes) ctx->jobs_tag.valid = false;   // reallocated: whatever the table was, it is gone
-  ctx->jobs_bytes = cap;
+  bool moved;
+  int rc = ensure(ctx, ctx->buf[kJobs], pl.table_bytes, pl.table_grow, &moved);
+  if (moved) ctx->jobs_tag.valid = false;   // reallocated: whatever the table was, it is gone
   if (rc) return rc;
   if (pl.first_strip) {
-    size_t fcap = (size_t)ctx->first_strip_cap * sizeof(int);
-    const size_t fcap0 = fcap;
-    rc = ensure(ctx, &ctx->d_first_strip, &fcap, sizeof(int) * (size_t)jobs, sizeof(int) * (size_t)(jobs / (n_refs > 0 ? n_refs : 1) + 1) * hmme::kMaxRefs);
-    if (fcap != fcap0) ctx->jobs_tag.valid = false;
-    ctx->first_strip_cap = (int)(fcap / sizeof(int));
+    rc = ensure(ctx, ctx->buf[kFirstStrip], sizeof(int) * (size_t)jobs, sizeof(int) * (size_t)(jobs / (n_refs > 0 ? n_refs : 1) + 1) * hmme::kMaxRefs, &moved);
+    if (moved) ctx->jobs_tag.valid = false;
     if (rc) return rc;
   }
+  void* const d_jobs = ctx->buf[kJobs].p;
+  int* const d_first_strip = ctx->buf[kFirstStrip].as<int>();
   hmme_ctx::TableTag tag;
   tag.valid = !d_pred_q && !d_center_q;
   tag.w = w; tag.h = h; tag.sr = sr; tag.first = first; tag.count = count; tag.pairs = n_refs;
   tag.bit_depth = fp->bit_depth | (pl.mode == SearchMode::kStrips16 && fp->bit_depth == 8 ? 0x100 : 0);   // 0x100: the 16-bit table of 8-bit planes (weighted search)
-  tag.buf = ctx->d_jobs; tag.buf2 = pl.first_strip ? ctx->d_first_strip : nullptr; tag.stream = (void*)s;
+  tag.buf = d_jobs; tag.buf2 = pl.first_strip ? d_first_strip : nullptr; tag.stream = (void*)s;
   if (tag.same(ctx->jobs_tag)) return HMME_OK;   // the table of the launch before is this launch's table
   ctx->jobs_tag.valid = false;
   const dim3 block(256);
@@ -1321,10 +1390,10 @@ static int prep_jobs(hmme_ctx* ctx, const hmme_plane* cur, const hmme_frame_para
   const int16_t* pred = (const int16_t*)d_pred_q;
   switch (pl.mode) {
     case SearchMode::kTiles8:
-      hipLaunchKernelGGL(hmme::me_prep_jobs_tile_kernel, grid(jobs), block, 0, s, (MeJob16*)ctx->d_jobs, ctx->d_first_strip, pred, first, count, n_refs, w, h, sr);
+      hipLaunchKernelGGL(hmme::me_prep_jobs_tile_kernel, grid(jobs), block, 0, s, (MeJob16*)d_jobs, d_first_strip, pred, first, count, n_refs, w, h, sr);
       break;
     case SearchMode::kStrips16:
-      hipLaunchKernelGGL(hmme::me_prep_jobs16_kernel, grid(jobs), block, 0, s, (MeJob16*)ctx->d_jobs, ctx->d_first_strip, pred, first, count, n_refs, w, h, sr,
+      hipLaunchKernelGGL(hmme::me_prep_jobs16_kernel, grid(jobs), block, 0, s, (MeJob16*)d_jobs, d_first_strip, pred, first, count, n_refs, w, h, sr,
                          pl.n_strips, pl.strip_rows, pl.tail_first, pl.tail_parts, (const int16_t*)d_center_q);
       break;
     case SearchMode::kWhole8:
@@ -1333,13 +1402,13 @@ static int prep_jobs(hmme_ctx* ctx, const hmme_plane* cur, const hmme_frame_para
       // kSegments8: one segment table for the whole launch, the head's jobs its entries / workgroups 0 .. head - 1; else the head's MeJobs, then a table of the tail alone
       const int idx0 = pl.mode == SearchMode::kSegments8 ? head : 0;
       if (head && idx0)
-        hipLaunchKernelGGL(hmme::me_prep_whole_segments_kernel, grid(head), block, 0, s, ctx->d_jobs, ctx->d_first_strip, pred, first, count, n_refs, w, h, sr,
+        hipLaunchKernelGGL(hmme::me_prep_whole_segments_kernel, grid(head), block, 0, s, d_jobs, d_first_strip, pred, first, count, n_refs, w, h, sr,
                            head + pl.tail_wgs, head);
       else if (head)
-        hipLaunchKernelGGL(hmme::me_prep_jobs_kernel, grid(head), block, 0, s, (MeJob*)ctx->d_jobs, pred, first, count, n_refs, w, h, sr, 0, head, 1,
+        hipLaunchKernelGGL(hmme::me_prep_jobs_kernel, grid(head), block, 0, s, (MeJob*)d_jobs, pred, first, count, n_refs, w, h, sr, 0, head, 1,
                            (uint32_t*)nullptr, (const int16_t*)nullptr);
       if (n_tail)
-        hipLaunchKernelGGL(hmme::me_prep_segments_kernel, dim3(1), dim3(hmme::kSegPrepThreads), 0, s, (void*)((uint8_t*)ctx->d_jobs + pl.tail_jobs_off), ctx->d_first_strip,
+        hipLaunchKernelGGL(hmme::me_prep_segments_kernel, dim3(1), dim3(hmme::kSegPrepThreads), 0, s, (void*)((uint8_t*)d_jobs + pl.tail_jobs_off), d_first_strip,
                            pred, first, count, n_refs, w, h, sr, idx0 + pl.tail_wgs, head, n_tail, idx0);
       break;
     }
@@ -1354,15 +1423,17 @@ static int run_search(hmme_ctx* ctx, const RefSet& curs, int cur_ctus_x, const R
                       int16_t* d_mv, uint32_t* d_sad, hipStream_t s) {
   const int head = pl.tail_first, n_tail = pl.jobs - head;
   const bool one_launch = pl.mode == SearchMode::kSegments8;
+  const void* const d_jobs = ctx->buf[kJobs].p;
+  const int* const d_first_strip = ctx->buf[kFirstStrip].as<int>();
   switch (pl.mode) {
     case SearchMode::kStrips16:
-      return launch_search16(ctx, curs, cur_ctus_x, refs, ref_pitch, (const MeJob16*)ctx->d_jobs, ctx->d_first_strip, pl.jobs, pl.n_wg16,
+      return launch_search16(ctx, curs, cur_ctus_x, refs, ref_pitch, (const MeJob16*)d_jobs, d_first_strip, pl.jobs, pl.n_wg16,
                              pl.pdw, pl.strip_rows, fp->fen, fp->bit_depth, d_mv, d_sad, s);
     case SearchMode::kTiles8:
-      return launch_search8_split(ctx, curs, cur_ctus_x, refs, ref_pitch, (const MeJob16*)ctx->d_jobs, ctx->d_first_strip, pl.jobs, 4,
+      return launch_search8_split(ctx, curs, cur_ctus_x, refs, ref_pitch, (const MeJob16*)d_jobs, d_first_strip, pl.jobs, 4,
                                   fp->fen, d_mv, d_sad, s);
     case SearchMode::kWhole8:
-      return launch_search8<0>(ctx, curs, cur_ctus_x, refs, ref_pitch, ctx->d_jobs, head, fp->fen, d_mv, d_sad, nullptr, 0, s);
+      return launch_search8<0>(ctx, curs, cur_ctus_x, refs, ref_pitch, d_jobs, head, fp->fen, d_mv, d_sad, nullptr, 0, s);
     case SearchMode::kSegments8:
     case SearchMode::kHeadThenSegments8: break;
   }
@@ -1370,10 +1441,10 @@ static int run_search(hmme_ctx* ctx, const RefSet& curs, int cur_ctus_x, const R
   int rc = merge_table(ctx, one_launch ? pl.jobs : n_tail, nullptr, s, &best);   // (preset, if it has to be, before the head runs, not between the two)
   if (rc) return rc;
   if (one_launch)
-    return launch_search8_segments(ctx, curs, cur_ctus_x, refs, ref_pitch, ctx->d_jobs, ctx->d_first_strip, pl.jobs, head + pl.tail_wgs, fp->fen, d_mv, d_sad, s, best);
-  rc = launch_search8<0>(ctx, curs, cur_ctus_x, refs, ref_pitch, ctx->d_jobs, head, fp->fen, d_mv, d_sad, nullptr, 0, s);
+    return launch_search8_segments(ctx, curs, cur_ctus_x, refs, ref_pitch, d_jobs, d_first_strip, pl.jobs, head + pl.tail_wgs, fp->fen, d_mv, d_sad, s, best);
+  rc = launch_search8<0>(ctx, curs, cur_ctus_x, refs, ref_pitch, d_jobs, head, fp->fen, d_mv, d_sad, nullptr, 0, s);
   if (rc) return rc;
-  return launch_search8_segments(ctx, curs, cur_ctus_x, refs, ref_pitch, (const uint8_t*)ctx->d_jobs + pl.tail_jobs_off, ctx->d_first_strip, n_tail, pl.tail_wgs,
+  return launch_search8_segments(ctx, curs, cur_ctus_x, refs, ref_pitch, (const uint8_t*)d_jobs + pl.tail_jobs_off, d_first_strip, n_tail, pl.tail_wgs,
                                  fp->fen, d_mv + (size_t)head * 2 * HMME_NUM_CTU_PARTS, d_sad + (size_t)head * HMME_NUM_CTU_PARTS, s, best);
 }
 
@@ -1455,56 +1526,24 @@ int hmme_search_frame_device(hmme_ctx* ctx, const hmme_plane* cur, const hmme_pl
   return hmme_search_frame_multi_device(ctx, cur, &ref, 1, fp, d_pred_q, d_out_mv, d_out_sad, stream);
 }
 
-// host-facing frame calls: device staging for `need` (CTU, reference) result tables and their predictors
-static int ensure_frame_buffers(hmme_ctx* ctx, size_t need) {
-  if ((size_t)ctx->out_cap >= need) return HMME_OK;
-  hipFree(ctx->d_mv); hipFree(ctx->d_sad); hipFree(ctx->d_pred);
-  ctx->d_mv = nullptr; ctx->d_sad = nullptr; ctx->d_pred = nullptr; ctx->out_cap = 0;
-  HIP_TRY(ctx, hipMalloc(&ctx->d_mv, sizeof(int16_t) * 2 * HMME_NUM_CTU_PARTS * need));
-  HIP_TRY(ctx, hipMalloc(&ctx->d_sad, sizeof(uint32_t) * HMME_NUM_CTU_PARTS * need));
-  HIP_TRY(ctx, hipMalloc(&ctx->d_pred, sizeof(int16_t) * 2 * need));
-  ctx->out_cap = (int)need;
-  return HMME_OK;
-}
-
-// host-facing refinement calls: device staging for the integer MVs, quarter-pel MVs and costs of `slots` (CTU, slot) entries
-static int ensure_refine_buffers(hmme_ctx* ctx, size_t slots) {
-  if (ctx->refine_cap >= slots) return HMME_OK;
-  hipFree(ctx->d_imv); hipFree(ctx->d_qmv); hipFree(ctx->d_fcost);
-  ctx->d_imv = nullptr; ctx->d_qmv = nullptr; ctx->d_fcost = nullptr; ctx->refine_cap = 0;
-  HIP_TRY(ctx, hipMalloc(&ctx->d_imv, sizeof(int16_t) * 2 * slots));
-  HIP_TRY(ctx, hipMalloc(&ctx->d_qmv, sizeof(int16_t) * 2 * slots));
-  HIP_TRY(ctx, hipMalloc(&ctx->d_fcost, sizeof(uint32_t) * slots));
-  ctx->refine_cap = slots;
-  return HMME_OK;
-}
-
-// The synchronous calls' way in, behind the checks of their own: the CTU range, the output pointers (a refinement's integer MVs too), then
-// -- unless the range is empty: *count == 0, nothing to do -- the device, the staging buffers, the predictors of `n_refs` references up
-// into d_pred (*d_pred: where the device call finds them, null without) and a refinement's integer MVs into d_imv.  On ctx->stream.
+// The synchronous searches' and refinements' way in, behind the checks of their own: the CTU range, the output pointers (a refinement's
+// integer MVs too), then -- unless the range is empty: *count == 0, nothing to do -- their items into `st` behind whatever the caller has
+// put there, and st.begin().  Up go the predictors of the whole picture and `n_refs` references (null: none) and a refinement's integer
+// MVs; st.end() brings back the *count x n_refs result tables.
+struct FrameItems { int pred, imv, mv, cost; };
 static int stage_in(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_frame_params* fp, int n_refs, const int16_t* pred_q,
-                    bool refine, const int16_t* int_mv, const void* out_mv, const void* out_cost, int* count, const void** d_pred) {
+                    bool refine, const int16_t* int_mv, int16_t* out_mv, uint32_t* out_cost, int* count, Stage& st, FrameItems* it) {
   int first;
   int rc = check_frame_args(ctx, cur, ref, fp, &first, count);
   if (rc) return rc;
   if (refine ? (!int_mv || !out_mv || !out_cost) : (!out_mv || !out_cost)) return fail(ctx, HMME_ERR_ARG, refine ? "null buffer" : "null output buffer");
   if (*count == 0) return HMME_OK;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t need = (size_t)hmme_num_ctus(cur->width, cur->height) * n_refs;
-  if (refine) rc = ensure_refine_buffers(ctx, HMME_NUM_CTU_PARTS * need);
-  if (rc == HMME_OK) rc = ensure_frame_buffers(ctx, need);   // (a refinement's predictors travel in the search path's staging buffer)
-  if (rc) return rc;
-  if (pred_q) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_pred, pred_q, sizeof(int16_t) * 2 * need, hipMemcpyHostToDevice, ctx->stream));
-  if (refine) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_imv, int_mv, sizeof(int16_t) * 2 * HMME_NUM_CTU_PARTS * (size_t)*count * n_refs, hipMemcpyHostToDevice, ctx->stream));
-  *d_pred = pred_q ? ctx->d_pred : nullptr;
-  return HMME_OK;
-}
-// ... and out: the `tables` (CTU, reference) result tables of the search (d_mv, d_sad) or the refinement (d_qmv, d_fcost) down, and the wait
-static int stage_out(hmme_ctx* ctx, bool refine, size_t tables, int16_t* out_mv, uint32_t* out_cost) {
-  HIP_TRY(ctx, hipMemcpyAsync(out_mv, refine ? ctx->d_qmv : ctx->d_mv, sizeof(int16_t) * 2 * HMME_NUM_CTU_PARTS * tables, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(out_cost, refine ? ctx->d_fcost : ctx->d_sad, sizeof(uint32_t) * HMME_NUM_CTU_PARTS * tables, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return HMME_OK;
+  const size_t slots = HMME_NUM_CTU_PARTS * (size_t)*count * n_refs;
+  it->pred = st.in(pred_q, sizeof(int16_t) * 2 * hmme_num_ctus(cur->width, cur->height) * n_refs);
+  it->imv = st.in(int_mv, sizeof(int16_t) * 2 * slots);
+  it->mv = st.out(out_mv, sizeof(int16_t) * 2 * slots, 0, sizeof(int16_t) * 2 * slots);
+  it->cost = st.out(out_cost, sizeof(uint32_t) * slots, 0, sizeof(uint32_t) * slots);
+  return st.begin();
 }
 
 int hmme_search_frame_multi(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs,
@@ -1512,11 +1551,12 @@ int hmme_search_frame_multi(hmme_ctx* ctx, const hmme_plane* cur, const hmme_pla
   if (!ctx) return HMME_ERR_ARG;
   if (!refs || n_refs < 1 || n_refs > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "n_refs %d outside 1..%d", n_refs, hmme::kMaxRefs);
   int count;
-  const void* d_pred;
-  int rc = stage_in(ctx, cur, refs[0], fp, n_refs, pred_q, false, nullptr, out_mv, out_sad, &count, &d_pred);
+  Stage st(ctx);
+  FrameItems it;
+  int rc = stage_in(ctx, cur, refs[0], fp, n_refs, pred_q, false, nullptr, out_mv, out_sad, &count, st, &it);
   if (rc || count == 0) return rc;
-  rc = hmme_search_frame_multi_device(ctx, cur, refs, n_refs, fp, d_pred, ctx->d_mv, ctx->d_sad, ctx->stream);
-  return rc ? rc : stage_out(ctx, false, (size_t)count * n_refs, out_mv, out_sad);
+  rc = hmme_search_frame_multi_device(ctx, cur, refs, n_refs, fp, st.at(it.pred), st.at(it.mv), st.at(it.cost), ctx->stream);
+  return rc ? rc : st.end();
 }
 
 int hmme_search_frame(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_frame_params* fp,
@@ -1530,7 +1570,7 @@ namespace {
 // multiples of 8: 8x8 Hadamard blocks, xGetHADs) that contain it, then for each of the 256 4x4 positions the 6 other
 // slots that contain it; ascending slot ids
 int build_frac_cover(hmme_ctx* ctx) {
-  if (ctx->d_frac_cover) return HMME_OK;
+  if (ctx->buf[kFracCover].p) return HMME_OK;
   std::vector<uint16_t> cover;
   for (int kind8 = 1; kind8 >= 0; --kind8) {
     const int step = kind8 ? 8 : 4, per = kind8 ? hmme::kFracCover8 : hmme::kFracCover4;
@@ -1546,12 +1586,13 @@ int build_frac_cover(hmme_ctx* ctx) {
         if (n != per) return fail(ctx, HMME_ERR_DEVICE, "internal: %d slots cover a %dx%d position, expected %d", n, step, step, per);
       }
   }
-  HIP_TRY(ctx, hipMalloc(&ctx->d_frac_cover, sizeof(uint16_t) * cover.size()));
-  HIP_TRY(ctx, hipMemcpy(ctx->d_frac_cover, cover.data(), sizeof(uint16_t) * cover.size(), hipMemcpyHostToDevice));
+  const int rc = ensure(ctx, ctx->buf[kFracCover], sizeof(uint16_t) * cover.size());
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemcpy(ctx->buf[kFracCover].p, cover.data(), sizeof(uint16_t) * cover.size(), hipMemcpyHostToDevice));
   return HMME_OK;
 }
 
-// One refinement launch, whoever asks for it (plain, weighted, bi-prediction): cover table, job table and counter in d_frac_jobs, the
+// One refinement launch, whoever asks for it (plain, weighted, bi-prediction): cover table, job table and counter in kFracJobs, the
 // table's kernel where the launch reads one, LDS opt-in, me_frac_kernel.
 // kReuse: a table without predictors may be the one the launch before left (frac_jobs_tag); kAsNeeded: written where the launch reads
 // one; kAlways: written in any case -- the bi-prediction calls, whose table carries the window centres
@@ -1582,13 +1623,13 @@ int launch_refine(hmme_ctx* ctx, const RefineLaunch& L, hipStream_t s) {
   int rc = build_frac_cover(ctx);
   if (rc) return rc;
   // (a scratch that grows, grows to what kMaxRefs pairs of this CTU range need: the shorter and longer runs of one weighted call fit alike)
-  size_t cap = ctx->frac_jobs_bytes;
-  rc = ensure(ctx, (uint8_t**)&ctx->d_frac_jobs, &cap, sizeof(MeJob) * (size_t)jobs + 64,   // + the launch's job counter behind the table
-              sizeof(MeJob) * (size_t)L.count * hmme::kMaxRefs + 4096);
-  if (cap != ctx->frac_jobs_bytes || L.table != FracTable::kReuse) ctx->frac_jobs_tag.valid = false;
-  ctx->frac_jobs_bytes = cap;
+  bool moved;
+  rc = ensure(ctx, ctx->buf[kFracJobs], sizeof(MeJob) * (size_t)jobs + 64,   // + the launch's job counter behind the table
+              sizeof(MeJob) * (size_t)L.count * hmme::kMaxRefs + 4096, &moved);
+  if (moved || L.table != FracTable::kReuse) ctx->frac_jobs_tag.valid = false;
   if (rc) return rc;
-  uint32_t* counter = (uint32_t*)((uint8_t*)ctx->d_frac_jobs + ((sizeof(MeJob) * (size_t)jobs + 15) & ~(size_t)15));
+  MeJob* const d_frac_jobs = ctx->buf[kFracJobs].as<MeJob>();
+  uint32_t* counter = (uint32_t*)((uint8_t*)d_frac_jobs + ((sizeof(MeJob) * (size_t)jobs + 15) & ~(size_t)15));
   const int grid = frac_grid(ctx, L.build, jobs);
   // one workgroup per job (the default) on the two-wave builds: every workgroup derives its job itself (FracPrep) -- no job table, no
   // launch in front of this one (1080p: 0.095 -> 0.090 ms).  A table is read by the job-walking launch of HMME_FRAC_GRID (its prep
@@ -1601,10 +1642,10 @@ int launch_refine(hmme_ctx* ctx, const RefineLaunch& L, hipStream_t s) {
     hmme_ctx::TableTag tag;
     tag.valid = L.table == FracTable::kReuse && !L.d_pred && !L.d_center && !walk;
     tag.w = L.width; tag.h = L.height; tag.bit_depth = L.bit_depth; tag.sr = L.search_range; tag.first = L.first; tag.count = L.count;
-    tag.pairs = L.pairs; tag.buf = ctx->d_frac_jobs; tag.stream = (void*)s;
+    tag.pairs = L.pairs; tag.buf = d_frac_jobs; tag.stream = (void*)s;
     if (!tag.same(ctx->frac_jobs_tag)) {
       ctx->frac_jobs_tag = tag;
-      hipLaunchKernelGGL(hmme::me_prep_jobs_kernel, dim3((jobs + 255) / 256), dim3(256), 0, s, (MeJob*)ctx->d_frac_jobs, L.d_pred, L.first, L.count, L.pairs,
+      hipLaunchKernelGGL(hmme::me_prep_jobs_kernel, dim3((jobs + 255) / 256), dim3(256), 0, s, d_frac_jobs, L.d_pred, L.first, L.count, L.pairs,
                          L.width, L.height, L.search_range, 0, jobs, 0, counter, L.d_center);
     }
   }
@@ -1618,8 +1659,8 @@ int launch_refine(hmme_ctx* ctx, const RefineLaunch& L, hipStream_t s) {
                                                         (uint32_t)L.width | (uint32_t)L.height << 16, L.search_range}
                                        : kNoPrep;
   hipLaunchKernelGGL(frac_kernel(L.build), dim3(grid), dim3(hmme::frac_threads(L.build.bps())), hmme::frac_lds_bytes(L.build.bps()), s, L.curs,
-                     L.cur_pitch, L.refs, L.ref_pitch, need_table ? (const MeJob*)ctx->d_frac_jobs : (const MeJob*)nullptr, prep, jobs,
-                     walk ? counter : (uint32_t*)nullptr, ctx->d_frac_cover, L.d_int_mv, ctx->lambda_q16, L.bit_depth, L.fw, L.d_qmv, L.d_cost);
+                     L.cur_pitch, L.refs, L.ref_pitch, need_table ? d_frac_jobs : (const MeJob*)nullptr, prep, jobs,
+                     walk ? counter : (uint32_t*)nullptr, ctx->buf[kFracCover].as<uint16_t>(), L.d_int_mv, ctx->lambda_q16, L.bit_depth, L.fw, L.d_qmv, L.d_cost);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? HMME_OK : fail(ctx, HMME_ERR_DEVICE, "refinement launch -> %s", hipGetErrorString(e));
 }
@@ -1656,11 +1697,12 @@ int hmme_refine_frame_multi_device(hmme_ctx* ctx, const hmme_plane* cur, const h
 int hmme_refine_frame(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_frame_params* fp, const int16_t* pred_q,
                       const int16_t* int_mv, int use_hadamard, int16_t* out_qmv, uint32_t* out_cost) {
   int count;
-  const void* d_pred;
-  int rc = stage_in(ctx, cur, ref, fp, 1, pred_q, true, int_mv, out_qmv, out_cost, &count, &d_pred);
+  Stage st(ctx);
+  FrameItems it;
+  int rc = stage_in(ctx, cur, ref, fp, 1, pred_q, true, int_mv, out_qmv, out_cost, &count, st, &it);
   if (rc || count == 0) return rc;
-  rc = hmme_refine_frame_multi_device(ctx, cur, &ref, 1, fp, d_pred, ctx->d_imv, use_hadamard, ctx->d_qmv, ctx->d_fcost, ctx->stream);
-  return rc ? rc : stage_out(ctx, true, count, out_qmv, out_cost);
+  rc = hmme_refine_frame_multi_device(ctx, cur, &ref, 1, fp, st.at(it.pred), st.at(it.imv), use_hadamard, st.at(it.mv), st.at(it.cost), ctx->stream);
+  return rc ? rc : st.end();
 }
 
 // ---- explicit weighted prediction on whole pictures -----------------------------------------------------------
@@ -1815,10 +1857,10 @@ int hmme_search_pairs_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, con
   rc = pairs_begin(ctx, curs, refs, n_pairs, &f, s, &pl);
   if (rc || pl.count == 0) return rc;
   const WpGeom g(refs[0]);
-  rc = ensure(ctx, &ctx->d_wp[0], &ctx->wp_cap[0], g.plane_bytes * n_pairs);
-  if (rc == HMME_OK) rc = ensure(ctx, &ctx->d_wp[1], &ctx->wp_cap[1], g.blk_bytes * n_pairs);
+  rc = ensure(ctx, ctx->buf[kWp0], g.plane_bytes * n_pairs);
+  if (rc == HMME_OK) rc = ensure(ctx, ctx->buf[kWp1], g.blk_bytes * n_pairs);
   RefSet wrefs = one_ref(nullptr), wcurs = one_ref(nullptr);
-  CopyCache wref(ctx->d_wp[0], g.plane_bytes, false), wcur(ctx->d_wp[1], g.blk_bytes, true);
+  CopyCache wref(ctx->wp(0), g.plane_bytes, false), wcur(ctx->wp(1), g.blk_bytes, true);
   for (int r = 0; r < n_pairs && rc == HMME_OK; ++r) {
     const hmme_weight& w = wps[r];
     rc = cached_copy(ctx, wref, g, r, CopyKey{refs[r], w.w0, w.round, w.shift, w.offset + info[r].bias}, s, &wrefs.base[r]);
@@ -1840,11 +1882,12 @@ int hmme_search_frame_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* 
   int rc = check_weights(ctx, "hmme_search_frame_w", fp, wp, 1, 0, &info, &identity);
   if (rc) return rc;
   int count;
-  const void* d_pred;
-  rc = stage_in(ctx, cur, ref, fp, 1, pred_q, false, nullptr, out_mv, out_sad, &count, &d_pred);
+  Stage st(ctx);
+  FrameItems it;
+  rc = stage_in(ctx, cur, ref, fp, 1, pred_q, false, nullptr, out_mv, out_sad, &count, st, &it);
   if (rc || count == 0) return rc;
-  rc = hmme_search_pairs_w_device(ctx, &cur, &ref, 1, fp, wp, d_pred, ctx->d_mv, ctx->d_sad, ctx->stream);
-  return rc ? rc : stage_out(ctx, false, count, out_mv, out_sad);
+  rc = hmme_search_pairs_w_device(ctx, &cur, &ref, 1, fp, wp, st.at(it.pred), st.at(it.mv), st.at(it.cost), ctx->stream);
+  return rc ? rc : st.end();
 }
 
 int hmme_refine_pairs_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, int n_pairs,
@@ -1865,9 +1908,9 @@ int hmme_refine_pairs_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, con
   const WpGeom g(refs[0]);
   bool need_cur = false;
   for (int r = 0; r < n_pairs; ++r) need_cur = need_cur || (!info[r].identity && (!src_wide || info[r].bias));
-  if (!src_wide) rc = ensure(ctx, &ctx->d_wp[2], &ctx->wp_cap[2], g.plane_bytes * n_pairs);
-  if (rc == HMME_OK && need_cur) rc = ensure(ctx, &ctx->d_wp[3], &ctx->wp_cap[3], g.plane_bytes * n_pairs);
-  CopyCache raw(ctx->d_wp[2], g.plane_bytes, false), wcur(ctx->d_wp[3], g.plane_bytes, false);   // references widened to u16 / current pictures widened and biased
+  if (!src_wide) rc = ensure(ctx, ctx->buf[kWp2], g.plane_bytes * n_pairs);
+  if (rc == HMME_OK && need_cur) rc = ensure(ctx, ctx->buf[kWp3], g.plane_bytes * n_pairs);
+  CopyCache raw(ctx->wp(2), g.plane_bytes, false), wcur(ctx->wp(3), g.plane_bytes, false);   // references widened to u16 / current pictures widened and biased
   // one launch per run of pairs with equal weights: the weight is one kernel argument (FracWp)
   for (int a = 0, b; a < n_pairs && rc == HMME_OK; a = b) {
     for (b = a + 1; b < n_pairs && same_weight(wps[b], wps[a]); ++b) {}
@@ -1907,11 +1950,12 @@ int hmme_refine_frame_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* 
   int rc = check_weights(ctx, "hmme_refine_frame_w", fp, wp, 1, 1, &info, &identity);
   if (rc) return rc;
   int count;
-  const void* d_pred;
-  rc = stage_in(ctx, cur, ref, fp, 1, pred_q, true, int_mv, out_qmv, out_cost, &count, &d_pred);
+  Stage st(ctx);
+  FrameItems it;
+  rc = stage_in(ctx, cur, ref, fp, 1, pred_q, true, int_mv, out_qmv, out_cost, &count, st, &it);
   if (rc || count == 0) return rc;
-  rc = hmme_refine_pairs_w_device(ctx, &cur, &ref, 1, fp, wp, d_pred, ctx->d_imv, use_hadamard, ctx->d_qmv, ctx->d_fcost, ctx->stream);
-  return rc ? rc : stage_out(ctx, true, count, out_qmv, out_cost);
+  rc = hmme_refine_pairs_w_device(ctx, &cur, &ref, 1, fp, wp, st.at(it.pred), st.at(it.imv), use_hadamard, st.at(it.mv), st.at(it.cost), ctx->stream);
+  return rc ? rc : st.end();
 }
 
 // ---- bi-prediction on whole pictures and picture pairs ----------------------------------------------------------
@@ -2103,8 +2147,6 @@ int hmme_bipred_check(int bit_depth, int refine) {
 }
 
 namespace {
-size_t pad16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
-
 // What hmme_predict_pairs_device, _w_device, hmme_predict_refs_device and _w_device check alike, in the order that decides the code returned
 // null_arg: one of the caller's other pointers is null; wps: one weight per plane, or null for none; unit: what a refusal calls plane r
 struct PredictArgs {
@@ -2221,37 +2263,6 @@ int predict_pairs(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs,
   return pairs_end(ctx, refs, refs, np, s, rc);   // whatever the launches returned: the scratch is acquired
 }
 
-// hmme_predict_frame, _w, hmme_predict_refs_frame and hmme_predict_bi_frame: the motion field (`lists` of them, one behind the other) and,
-// behind it, the reference / direction field (null: none) into ctx->d_bi[0], the caller's image through ctx->d_bi[1] both ways around `launch`:
-// samples that are not written come back as they were
-// chroma (hmme_predict_chroma_*_frame): `ref` is the Cb plane, the fields are those of the n_ctu LUMA CTUs, and a second image of the same
-// size and stride (Cr) travels right behind the first in ctx->d_bi[1]
-struct StagedChroma { int n_ctu; void* out2; };
-int predict_staged(hmme_ctx* ctx, const char* who, const hmme_plane* ref, const int16_t* mv_field, const uint8_t* ref_field, int mv_per_ctu, void* out, int out_stride,
-                   const std::function<int(void* d_field, void* d_ref_field, void* d_img, int pitch, hipStream_t s)>& launch, int lists = 1,
-                   const StagedChroma* chroma = nullptr) {
-  if (ref->ctx != ctx) return fail(ctx, HMME_ERR_ARG, "plane belongs to another context (planes are used with the context that created them)");
-  if (out_stride < ref->width) return fail(ctx, HMME_ERR_ARG, "%s: output stride %d below the picture width", who, out_stride);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t blocks = (size_t)(chroma ? chroma->n_ctu : ref->n_ctu) * mv_per_ctu, field_bytes = sizeof(int16_t) * 2 * blocks * lists, row = (size_t)ref->width * ref->bps;
-  const size_t img = row * ref->height;
-  int rc = ensure(ctx, &ctx->d_bi[0], &ctx->bi_cap[0], pad16(field_bytes) + (ref_field ? blocks : 0));
-  if (rc == HMME_OK) rc = ensure(ctx, &ctx->d_bi[1], &ctx->bi_cap[1], img * (chroma ? 2 : 1));
-  if (rc) return rc;
-  hipStream_t s = ctx->stream;
-  uint8_t* d_ref_field = ctx->d_bi[0] + pad16(field_bytes);
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_bi[0], mv_field, field_bytes, hipMemcpyHostToDevice, s));
-  if (ref_field) HIP_TRY(ctx, hipMemcpyAsync(d_ref_field, ref_field, blocks, hipMemcpyHostToDevice, s));
-  HIP_TRY(ctx, hipMemcpy2DAsync(ctx->d_bi[1], row, out, (size_t)out_stride * ref->bps, row, ref->height, hipMemcpyHostToDevice, s));
-  if (chroma) HIP_TRY(ctx, hipMemcpy2DAsync(ctx->d_bi[1] + img, row, chroma->out2, (size_t)out_stride * ref->bps, row, ref->height, hipMemcpyHostToDevice, s));
-  rc = launch(ctx->d_bi[0], d_ref_field, ctx->d_bi[1], (int)row, s);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpy2DAsync(out, (size_t)out_stride * ref->bps, ctx->d_bi[1], row, row, ref->height, hipMemcpyDeviceToHost, s));
-  if (chroma) HIP_TRY(ctx, hipMemcpy2DAsync(chroma->out2, (size_t)out_stride * ref->bps, ctx->d_bi[1] + img, row, row, ref->height, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  return HMME_OK;
-}
-
 // What the _frame forms check before anything is staged.  planes: the n of the call, `comps` per picture; null_arg: one of the caller's other
 // pointers is null.  Chroma also answers here for what a luma call leaves to the launch: the images are staged at the first plane's size and
 // sample type, so its depth and every plane's size against the luma size are looked at first.
@@ -2278,14 +2289,24 @@ int frame_checks(hmme_ctx* ctx, const char* who, const hmme_frame_params* fp, co
   if (rc == HMME_OK && comps == 1) rc = frame_args(ctx, who, fp, planes, n, comps, null_arg, mv_per_ctu, width, height);
   return rc;
 }
-// predict_staged for the `comps` images of a call: launch gets their device addresses
+// hmme_predict_frame, _w, hmme_predict_refs_frame, hmme_predict_bi_frame and their chroma forms through the staging arena: up go the motion
+// field (`lists` of them, one behind the other), the block field (a reference or direction per block; null: none) and the call's `comps`
+// images, `launch` gets their device addresses, the images come back: samples that are not written come back as they were.
+// comps == 2: p0 is the Cb plane, the fields are those of the LUMA CTUs, and the Cr image has the Cb image's size and stride
 int frame_staged(hmme_ctx* ctx, const char* who, const hmme_plane* p0, int comps, int width, int height, const int16_t* mv_field, const uint8_t* block_field, int mv_per_ctu,
                  void* const* outs, int out_stride, int lists, const std::function<int(void*, void*, void* const*, int, hipStream_t)>& launch) {
-  const StagedChroma ch = {comps == 2 ? hmme_num_ctus(width, height) : 0, comps == 2 ? outs[1] : nullptr};
-  return named(ctx, who, predict_staged(ctx, who, p0, mv_field, block_field, mv_per_ctu, outs[0], out_stride, [&](void* d_field, void* d_block_field, void* d_img, int pitch, hipStream_t s) {
-    void* d_outs[2] = {d_img, (uint8_t*)d_img + (size_t)pitch * p0->height};
-    return launch(d_field, d_block_field, d_outs, pitch, s);
-  }, lists, comps == 2 ? &ch : nullptr));
+  if (p0->ctx != ctx) return named(ctx, who, fail(ctx, HMME_ERR_ARG, "plane belongs to another context (planes are used with the context that created them)"));
+  if (out_stride < p0->width) return fail(ctx, HMME_ERR_ARG, "%s: output stride %d below the picture width", who, out_stride);
+  const size_t blocks = (size_t)(comps == 2 ? hmme_num_ctus(width, height) : p0->n_ctu) * mv_per_ctu, row = (size_t)p0->width * p0->bps;
+  Stage st(ctx);
+  const int field = st.in(mv_field, sizeof(int16_t) * 2 * blocks * lists), bfield = st.in(block_field, blocks);
+  const int img0 = st.image(outs[0], row, p0->height, (size_t)out_stride * p0->bps), img1 = st.image(comps == 2 ? outs[1] : nullptr, row, p0->height, (size_t)out_stride * p0->bps);
+  int rc = st.begin();
+  if (rc == HMME_OK) {
+    void* d_outs[2] = {st.at(img0), st.at(img1)};
+    rc = launch(st.at(field), st.at(bfield), d_outs, (int)row, ctx->stream);
+  }
+  return named(ctx, who, rc ? rc : st.end());
 }
 
 // hmme_predict_frame (wps == null), hmme_predict_frame_w and hmme_predict_chroma_frame; refs / wps / outs: `comps` entries
@@ -2340,17 +2361,17 @@ int bi_search(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* co
   for (int r = 0; r < n_pairs && rc == HMME_OK; ++r) rc = plane_wait(ctx, others[r], s);
   const WpGeom g(refs[0]);
   const int n_ctu = curs[0]->n_ctu, ctus_x = curs[0]->ctus_x;
-  if (rc == HMME_OK) rc = ensure(ctx, &ctx->d_wp[0], &ctx->wp_cap[0], g.plane_bytes * n_pairs);
-  if (rc == HMME_OK) rc = ensure(ctx, &ctx->d_wp[1], &ctx->wp_cap[1], g.blk_bytes * n_pairs);
+  if (rc == HMME_OK) rc = ensure(ctx, ctx->buf[kWp0], g.plane_bytes * n_pairs);
+  if (rc == HMME_OK) rc = ensure(ctx, ctx->buf[kWp1], g.blk_bytes * n_pairs);
   RefSet wrefs = one_ref(nullptr), wcurs = one_ref(nullptr);
   const size_t field = (size_t)n_ctu * mv_per_ctu * 2;
-  CopyCache wref(ctx->d_wp[0], g.plane_bytes, false);   // the references with the origin's bias
+  CopyCache wref(ctx->wp(0), g.plane_bytes, false);   // the references with the origin's bias
   for (int r = 0; r < n_pairs && rc == HMME_OK; ++r) {
     const int bias = bw[r].info.bias;   // origin and weighted reference carry the pair's bias
     rc = cached_copy(ctx, wref, g, r, wps ? CopyKey{refs[r], wps[r].w0, wps[r].round, wps[r].shift, wps[r].offset + bias} : CopyKey{refs[r], 1, 0, 0, bias}, s,
                      &wrefs.base[r]);
     if (rc != HMME_OK) break;
-    uint8_t* blocks = ctx->d_wp[1] + g.blk_bytes * r;   // the origin: one per pair (it depends on the pair's field)
+    uint8_t* blocks = ctx->wp(1) + g.blk_bytes * r;   // the origin: one per pair (it depends on the pair's field)
     rc = launch_predict(ctx, others[r], (const int16_t*)d_other_mv + field * r, mv_per_ctu, pl.first, pl.count, true, curs[r]->d_blocks, bias, blocks,
                         hmme::kBlkBytes16, (long)ctus_x * hmme::kBlkBytes16, 128, s, bw[r].other_identity ? nullptr : &bw[r].pw);
     wcurs.base[r] = blocks;
@@ -2374,11 +2395,11 @@ int bi_refine(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* co
   for (int r = 0; r < n_pairs && rc == HMME_OK; ++r) rc = plane_wait(ctx, others[r], s);
   const int src_wide = curs[0]->bps == 2 ? 1 : 0, n_ctu = curs[0]->n_ctu;
   const WpGeom g(refs[0]);
-  if (rc == HMME_OK && !src_wide) rc = ensure(ctx, &ctx->d_wp[2], &ctx->wp_cap[2], g.plane_bytes * n_pairs);
-  if (rc == HMME_OK) rc = ensure(ctx, &ctx->d_wp[3], &ctx->wp_cap[3], g.plane_bytes * n_pairs);
+  if (rc == HMME_OK && !src_wide) rc = ensure(ctx, ctx->buf[kWp2], g.plane_bytes * n_pairs);
+  if (rc == HMME_OK) rc = ensure(ctx, ctx->buf[kWp3], g.plane_bytes * n_pairs);
   RefSet c = one_ref(nullptr), rf = one_ref(nullptr);
   const size_t field = (size_t)n_ctu * mv_per_ctu * 2;
-  CopyCache raw(ctx->d_wp[2], g.plane_bytes, false);
+  CopyCache raw(ctx->wp(2), g.plane_bytes, false);
   for (int r = 0; r < n_pairs && rc == HMME_OK; ++r) {
     // the RAW reference is interpolated: a u16 plane serves as it is, an 8-bit one is widened
     if (src_wide) rf.base[r] = pl.refs.base[r];
@@ -2386,7 +2407,7 @@ int bi_refine(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* co
     if (rc != HMME_OK) break;
     // the origin in a padded plane's layout: only the CTU blocks are written and read (a partial CTU's block ends 63 samples into the
     // 128 / 80-sample margins at most)
-    uint8_t* plane = ctx->d_wp[3] + g.plane_bytes * r + g.origin;
+    uint8_t* plane = ctx->wp(3) + g.plane_bytes * r + g.origin;
     rc = launch_predict(ctx, others[r], (const int16_t*)d_other_mv + field * r, mv_per_ctu, pl.first, pl.count, true, curs[r]->d_blocks, bw[r].info.bias, plane,
                         128, 64L * g.pitch, g.pitch, s, bw[r].other_identity ? nullptr : &bw[r].pw);
     c.base[r] = plane;
@@ -2485,21 +2506,6 @@ int hmme_refine_pairs_bi_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, 
 }
 
 namespace {
-// host-facing bi calls: the motion field and the centres go up into d_bi[0] (the predictors into d_pred: stage_in)
-int bi_stage(hmme_ctx* ctx, const hmme_plane* cur, const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q, const void** d_field,
-             const void** d_center) {
-  const size_t n_ctu = (size_t)cur->n_ctu, field_bytes = sizeof(int16_t) * 2 * n_ctu * mv_per_ctu, pq_bytes = sizeof(int16_t) * 2 * n_ctu;
-  int rc = ensure(ctx, &ctx->d_bi[0], &ctx->bi_cap[0], field_bytes + pq_bytes);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_bi[0], other_mv, field_bytes, hipMemcpyHostToDevice, ctx->stream));
-  if (center_q) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_bi[0] + field_bytes, center_q, pq_bytes, hipMemcpyHostToDevice, ctx->stream));
-  *d_field = ctx->d_bi[0];
-  *d_center = center_q ? ctx->d_bi[0] + field_bytes : nullptr;
-  return HMME_OK;
-}
-}  // namespace
-
-namespace {
 // the four synchronous one-pair bi calls: wp == null is the call without explicit weights; int_mv != null the refinement
 int bi_frame(hmme_ctx* ctx, const char* who, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
              const hmme_weight* wp, const hmme_weight* other_wp, bool weighted, const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q,
@@ -2515,20 +2521,21 @@ int bi_frame(hmme_ctx* ctx, const char* who, const hmme_plane* cur, const hmme_p
   if (rc == HMME_OK) rc = bi_args(ctx, who, &cur, &ref, &other, 1, fp, other_mv, mv_per_ctu);
   if (rc) return rc;
   int count;
-  const void *d_pred, *d_field, *d_center;
-  rc = stage_in(ctx, cur, ref, fp, 1, pred_q, refine, int_mv, out_mv, out_cost, &count, &d_pred);
+  Stage st(ctx);
+  FrameItems it;
+  const int field = st.in(other_mv, sizeof(int16_t) * 2 * (size_t)cur->n_ctu * mv_per_ctu), center = st.in(center_q, sizeof(int16_t) * 2 * (size_t)cur->n_ctu);
+  rc = stage_in(ctx, cur, ref, fp, 1, pred_q, refine, int_mv, out_mv, out_cost, &count, st, &it);
   if (rc || count == 0) return rc;
-  rc = bi_stage(ctx, cur, other_mv, mv_per_ctu, center_q, &d_field, &d_center);
-  if (rc) return rc;
+  void *d_pred = st.at(it.pred), *d_field = st.at(field), *d_center = st.at(center), *d_mv = st.at(it.mv), *d_cost = st.at(it.cost);
   if (!refine)
-    rc = weighted ? hmme_search_pairs_bi_w_device(ctx, &cur, &ref, &other, 1, fp, wp, other_wp, d_field, mv_per_ctu, d_center, d_pred, ctx->d_mv, ctx->d_sad, ctx->stream)
-                  : hmme_search_pairs_bi_device(ctx, &cur, &ref, &other, 1, fp, d_field, mv_per_ctu, d_center, d_pred, ctx->d_mv, ctx->d_sad, ctx->stream);
+    rc = weighted ? hmme_search_pairs_bi_w_device(ctx, &cur, &ref, &other, 1, fp, wp, other_wp, d_field, mv_per_ctu, d_center, d_pred, d_mv, d_cost, ctx->stream)
+                  : hmme_search_pairs_bi_device(ctx, &cur, &ref, &other, 1, fp, d_field, mv_per_ctu, d_center, d_pred, d_mv, d_cost, ctx->stream);
   else
-    rc = weighted ? hmme_refine_pairs_bi_w_device(ctx, &cur, &ref, &other, 1, fp, wp, other_wp, d_field, mv_per_ctu, d_center, d_pred, ctx->d_imv, use_hadamard,
-                                                  ctx->d_qmv, ctx->d_fcost, ctx->stream)
-                  : hmme_refine_pairs_bi_device(ctx, &cur, &ref, &other, 1, fp, d_field, mv_per_ctu, d_center, d_pred, ctx->d_imv, use_hadamard, ctx->d_qmv,
-                                                ctx->d_fcost, ctx->stream);
-  return rc ? rc : stage_out(ctx, refine, count, out_mv, out_cost);
+    rc = weighted ? hmme_refine_pairs_bi_w_device(ctx, &cur, &ref, &other, 1, fp, wp, other_wp, d_field, mv_per_ctu, d_center, d_pred, st.at(it.imv), use_hadamard,
+                                                  d_mv, d_cost, ctx->stream)
+                  : hmme_refine_pairs_bi_device(ctx, &cur, &ref, &other, 1, fp, d_field, mv_per_ctu, d_center, d_pred, st.at(it.imv), use_hadamard, d_mv, d_cost,
+                                                ctx->stream);
+  return rc ? rc : st.end();
 }
 }  // namespace
 
@@ -2625,7 +2632,7 @@ int select_begin(hmme_ctx* ctx, const char* who, int width, int height, int n_pi
   return HMME_OK;
 }
 
-// hmme_select_frame and hmme_select_refs_frame: n_refs table and predictor sets into ctx->d_sel, `launch` on the device addresses (null
+// hmme_select_frame and hmme_select_refs_frame: n_refs table and predictor sets into the staging arena, `launch` on the device addresses (null
 // where the caller's array is; out_ref exists in the refs call only), then the outputs back
 // bi (hmme_select_dirs_frame; else null): the n_refs sets are the two lists.  A second run of n_refs table sets is staged behind the first
 // (d_mv / d_cost + n_refs sets), the lists' input field goes in as d_in_field, and the field that comes back has one part per list
@@ -2642,41 +2649,16 @@ int select_staged(hmme_ctx* ctx, const char* who, int width, int height, const h
   int first, count;
   int rc = ctu_range(ctx, fp, (int)n_ctu, &first, &count);
   if (rc || count == 0) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t tab = (size_t)n_refs * count * HMME_NUM_CTU_PARTS * 4, preds = (size_t)n_refs * n_ctu * 4;
-  const size_t tabs = bi ? 2 * tab : tab, lists = bi ? n_refs : 1, list_bytes = n_ctu * per * 4;   // tab and list_bytes are multiples of 4
-  uint8_t* const host[4] = {(uint8_t*)out_field, out_ref, (uint8_t*)out_slot, (uint8_t*)out_cost};
-  const size_t ctu_bytes[4] = {per * 4, per, per * 2, 4};   // of the four outputs
-  size_t at[4], total = 2 * pad16(tabs) + pad16(preds);
-  const size_t in_at = total;
-  if (bi) total += pad16(lists * list_bytes);
-  for (int k = 0; k < 4; ++k) {
-    at[k] = total;
-    if (host[k]) total += pad16((k == 0 ? lists : 1) * n_ctu * ctu_bytes[k]);
-  }
-  rc = ensure(ctx, &ctx->d_sel, &ctx->sel_cap, total);
-  if (rc) return rc;
-  hipStream_t s = ctx->stream;
-  uint8_t *d = ctx->d_sel, *d_out[4];
-  for (int k = 0; k < 4; ++k) d_out[k] = host[k] ? d + at[k] : nullptr;
-  HIP_TRY(ctx, hipMemcpyAsync(d, mv, tab, hipMemcpyHostToDevice, s));
-  HIP_TRY(ctx, hipMemcpyAsync(d + pad16(tabs), cost, tab, hipMemcpyHostToDevice, s));
-  if (bi) {
-    HIP_TRY(ctx, hipMemcpyAsync(d + tab, bi->mv, tab, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(d + pad16(tabs) + tab, bi->cost, tab, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(d + in_at, bi->in_field, lists * list_bytes, hipMemcpyHostToDevice, s));
-  }
-  if (pred_q) HIP_TRY(ctx, hipMemcpyAsync(d + 2 * pad16(tabs), pred_q, preds, hipMemcpyHostToDevice, s));
-  rc = launch(d, d + pad16(tabs), pred_q ? d + 2 * pad16(tabs) : nullptr, bi ? d + in_at : nullptr, d_out[0], d_out[1], d_out[2], d_out[3], s);
-  if (rc) return rc;
+  const size_t tab = (size_t)n_refs * count * HMME_NUM_CTU_PARTS * 4, lists = bi ? n_refs : 1;
+  Stage st(ctx);
+  const int i_mv = st.in(mv, tab, bi ? bi->mv : nullptr), i_cost = st.in(cost, tab, bi ? bi->cost : nullptr), i_pred = st.in(pred_q, (size_t)n_refs * n_ctu * 4);
+  const int i_in = st.in(bi ? bi->in_field : nullptr, lists * n_ctu * per * 4);
   // only the CTUs of the range come back: the caller's entries outside it keep their values
-  for (int k = 0; k < 4; ++k)
-    for (size_t l = 0; host[k] && l < (k == 0 ? lists : 1); ++l) {
-      const size_t o = l * list_bytes + first * ctu_bytes[k];
-      HIP_TRY(ctx, hipMemcpyAsync(host[k] + o, d_out[k] + o, count * ctu_bytes[k], hipMemcpyDeviceToHost, s));
-    }
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  return HMME_OK;
+  const auto out = [&](void* host, size_t ctu_bytes, size_t parts) { return st.out(host, n_ctu * ctu_bytes, first * ctu_bytes, count * ctu_bytes, parts); };
+  const int o_field = out(out_field, per * 4, lists), o_ref = out(out_ref, per, 1), o_slot = out(out_slot, per * 2, 1), o_cost = out(out_cost, 4, 1);
+  rc = st.begin();
+  if (rc == HMME_OK) rc = launch(st.at(i_mv), st.at(i_cost), st.at(i_pred), st.at(i_in), st.at(o_field), st.at(o_ref), st.at(o_slot), st.at(o_cost), ctx->stream);
+  return rc ? rc : st.end();
 }
 }  // namespace
 
@@ -3055,7 +3037,7 @@ int hmme_predict_chroma_bi_frame(hmme_ctx* ctx, const hmme_plane* const* ref0, c
 // (WeightPredAnalysis.cpp:67-120, :172-351) for luma: the whole-picture sums are kernels (me_plane_stats_kernel, me_wp_sad_kernel), the scalar
 // derivation between and behind them runs here in HM's own double / Int64 arithmetic.  Synchronous, on the context's private stream.
 namespace {
-// ctx->d_wpest: [2 i] / [2 i + 1] = sample sum and AC of plane i of the call, then two sums per reference of the SAD pass
+// kWpEst: [2 i] / [2 i + 1] = sample sum and AC of plane i of the call, then two sums per reference of the SAD pass
 constexpr int kWpStatPlanes = hmme::kMaxRefs + 1;
 constexpr int kWpStatSad = 2 * kWpStatPlanes;
 constexpr int kWpStatWords = kWpStatSad + 2 * hmme::kMaxRefs;
@@ -3100,12 +3082,12 @@ int launch_wp_sad(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const*
   return HMME_OK;
 }
 
-// kernels on `s` read planes[0 .. n): what pairs_begin / pairs_end do for the planes of picture pairs -- the scratch (d_wpest) and the last fill of
+// kernels on `s` read planes[0 .. n): what pairs_begin / pairs_end do for the planes of picture pairs -- the scratch (kWpEst) and the last fill of
 // every plane before, one event of the context's ring behind, so that a refill of any of them on another stream waits
 int planes_read_begin(hmme_ctx* ctx, const hmme_plane* const* planes, int n, hipStream_t s) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (!ctx->d_wpest) HIP_TRY(ctx, hipMalloc((void**)&ctx->d_wpest, sizeof(unsigned long long) * kWpStatWords));
-  int rc = scratch_acquire(ctx, s);
+  int rc = ensure(ctx, ctx->buf[kWpEst], sizeof(unsigned long long) * kWpStatWords);
+  if (rc == HMME_OK) rc = scratch_acquire(ctx, s);
   for (int i = 0; i < n && rc == HMME_OK; ++i) rc = plane_wait(ctx, planes[i], s);
   return rc;
 }
@@ -3134,10 +3116,10 @@ int collect_stats(hmme_ctx* ctx, const hmme_plane* const* planes, int n, hipStre
   int rc = planes_read_begin(ctx, todo, n_todo, s);
   if (rc) return rc;
   unsigned long long h[2 * kWpStatPlanes];
-  hipError_t e = hipMemsetAsync(ctx->d_wpest, 0, sizeof(unsigned long long) * 2 * n_todo, s);
+  hipError_t e = hipMemsetAsync(ctx->buf[kWpEst].as<unsigned long long>(), 0, sizeof(unsigned long long) * 2 * n_todo, s);
   if (e != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "plane statistics: %s", hipGetErrorString(e));
-  for (int j = 0; j < n_todo && rc == HMME_OK; ++j) rc = launch_stats(ctx, todo[j], ctx->d_wpest + 2 * j, s);
-  if (rc == HMME_OK && (e = hipMemcpyAsync(h, ctx->d_wpest, sizeof(unsigned long long) * 2 * n_todo, hipMemcpyDeviceToHost, s)) != hipSuccess)
+  for (int j = 0; j < n_todo && rc == HMME_OK; ++j) rc = launch_stats(ctx, todo[j], ctx->buf[kWpEst].as<unsigned long long>() + 2 * j, s);
+  if (rc == HMME_OK && (e = hipMemcpyAsync(h, ctx->buf[kWpEst].as<unsigned long long>(), sizeof(unsigned long long) * 2 * n_todo, hipMemcpyDeviceToHost, s)) != hipSuccess)
     rc = fail(ctx, HMME_ERR_DEVICE, "plane statistics: %s", hipGetErrorString(e));
   rc = planes_read_end(ctx, todo, n_todo, s, rc);
   if (rc) return rc;
@@ -3222,7 +3204,7 @@ int hmme_wp_estimate(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* con
   rc = planes_read_begin(ctx, planes, 1 + n_refs, s);
   if (rc) return rc;
   unsigned long long h[2 * hmme::kMaxRefs];
-  unsigned long long* d_sums = ctx->d_wpest + kWpStatSad;
+  unsigned long long* d_sums = ctx->buf[kWpEst].as<unsigned long long>() + kWpStatSad;
   hipError_t e = hipMemsetAsync(d_sums, 0, sizeof(unsigned long long) * 2 * n_refs, s);
   if (e != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "hmme_wp_estimate: %s", hipGetErrorString(e));
   if (rc == HMME_OK) rc = launch_wp_sad(ctx, cur, refs, n_refs, a, d_sums, s);
@@ -3297,11 +3279,11 @@ int hmme_test_time_wp_estimate_passes(hmme_ctx* ctx, const hmme_plane* cur, cons
   if (rc) return rc;
   hmme::MeWpSad a = {};
   for (int r = 0; r < n_refs; ++r) { a.weight[r] = wp->w0; a.offset[r] = wp->offset * (1 << wp->shift); a.log2_denom[r] = wp->shift; }
-  const hipError_t e = hipMemsetAsync(ctx->d_wpest, 0, sizeof(unsigned long long) * kWpStatWords, s);
+  const hipError_t e = hipMemsetAsync(ctx->buf[kWpEst].as<unsigned long long>(), 0, sizeof(unsigned long long) * kWpStatWords, s);
   if (e != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "hmme_test_time_wp_estimate_passes: %s", hipGetErrorString(e));
   if (rc == HMME_OK)
-    rc = time_reps(ctx, s, reps, "the estimator's passes", [&] { return launch_stats(ctx, cur, ctx->d_wpest, s); }, stats_ms,
-                   [&] { return launch_wp_sad(ctx, cur, refs, n_refs, a, ctx->d_wpest + kWpStatSad, s); }, sad_ms);
+    rc = time_reps(ctx, s, reps, "the estimator's passes", [&] { return launch_stats(ctx, cur, ctx->buf[kWpEst].as<unsigned long long>(), s); }, stats_ms,
+                   [&] { return launch_wp_sad(ctx, cur, refs, n_refs, a, ctx->buf[kWpEst].as<unsigned long long>() + kWpStatSad, s); }, sad_ms);
   return planes_read_end(ctx, planes, 1 + n_refs, s, rc);
 }
 
@@ -3317,10 +3299,10 @@ int hmme_test_time_bipred_origin(hmme_ctx* ctx, const hmme_plane* cur, const hmm
   rc = pairs_begin(ctx, &cur, &other, 1, &fp, s, &pl);
   if (rc) return rc;
   const WpGeom g(cur);
-  rc = ensure(ctx, &ctx->d_wp[1], &ctx->wp_cap[1], g.blk_bytes);
+  rc = ensure(ctx, ctx->buf[kWp1], g.blk_bytes);
   if (rc == HMME_OK)
     rc = time_reps(ctx, s, reps, "the origin pass", [&] {
-      return launch_predict(ctx, other, (const int16_t*)d_other_mv, mv_per_ctu, 0, cur->n_ctu, true, cur->d_blocks, (1 << cur->bit_depth) - 1, ctx->d_wp[1],
+      return launch_predict(ctx, other, (const int16_t*)d_other_mv, mv_per_ctu, 0, cur->n_ctu, true, cur->d_blocks, (1 << cur->bit_depth) - 1, ctx->wp(1),
                             hmme::kBlkBytes16, (long)cur->ctus_x * hmme::kBlkBytes16, 128, s);
     }, avg_ms);
   return pairs_end(ctx, &cur, &other, 1, s, rc);
@@ -3340,11 +3322,11 @@ int hmme_test_time_weight_passes(hmme_ctx* ctx, const hmme_plane* cur, const hmm
   rc = pairs_begin(ctx, &cur, &ref, 1, &fp, s, &pl);
   if (rc) return rc;
   const WpGeom g(ref);
-  rc = ensure(ctx, &ctx->d_wp[0], &ctx->wp_cap[0], g.plane_bytes);
-  if (rc == HMME_OK) rc = ensure(ctx, &ctx->d_wp[1], &ctx->wp_cap[1], g.blk_bytes);
+  rc = ensure(ctx, ctx->buf[kWp0], g.plane_bytes);
+  if (rc == HMME_OK) rc = ensure(ctx, ctx->buf[kWp1], g.blk_bytes);
   if (rc == HMME_OK)
-    rc = time_reps(ctx, s, reps, "the weighting passes", [&] { return weight_plane(ctx, ref, g, ctx->d_wp[0], wp->w0, wp->round, wp->shift, wp->offset + info.bias, s); },
-                   ref_ms, [&] { return bias_blocks(ctx, cur, ctx->d_wp[1], info.bias, s); }, cur_ms);
+    rc = time_reps(ctx, s, reps, "the weighting passes", [&] { return weight_plane(ctx, ref, g, ctx->wp(0), wp->w0, wp->round, wp->shift, wp->offset + info.bias, s); },
+                   ref_ms, [&] { return bias_blocks(ctx, cur, ctx->wp(1), info.bias, s); }, cur_ms);
   return pairs_end(ctx, &cur, &ref, 1, s, rc);
 }
 

@@ -125,15 +125,17 @@ class _Reader(threading.Thread):
 class RankResources:
     """What a pass of run_rank(stream_mode=True) allocates besides its tables -- the ring of plane slots, the page-locked host buffers, the
     streams -- kept between passes by a caller that runs several (a long-running job allocates once; hipMalloc / hipFree / hipHostMalloc
-    of a pass cost ~10 ms, nothing beside a 0.3 s pass, a fifth of one rank's share of the same job on eight GPUs).  close() frees them."""
+    of a pass cost ~10 ms, nothing beside a 0.3 s pass, a fifth of one rank's share of the same job on eight GPUs).  close() frees them.
+    The kept planes belong to the context whose handle is in the key, and `engine` keeps that Engine object alive; planes are destroyed
+    before their context (include/hmme.h), so close() runs before that engine's Engine.close()."""
 
     def __init__(self):
-        self.key, self.planes, self.bufs_t, self.streams = None, [], [], {}
+        self.key, self.engine, self.planes, self.bufs_t, self.streams = None, None, [], [], {}
 
     def close(self):
         for pl in self.planes:
             pl.close()
-        self.key, self.planes, self.bufs_t = None, [], []
+        self.key, self.engine, self.planes, self.bufs_t = None, None, [], []
 
     def __enter__(self):
         return self
@@ -298,7 +300,7 @@ def run_rank(eng, source, pairs, width, height, bit_depth, search_range, *, stre
             n_slots = n_slots or max(8, 2 * k + 2)
             loads, where = plan_plane_loads(pairs, batches, n_slots)
             n_planes = min(n_slots, max(1, len(pocs)))
-            key = (id(eng), width, height, bit_depth, n_planes, host_buffers)
+            key = (eng.h.value, width, height, bit_depth, n_planes, host_buffers)
             if keep is not None and keep.key == key:
                 planes, bufs_t = keep.planes, keep.bufs_t
             else:
@@ -307,7 +309,7 @@ def run_rank(eng, source, pairs, width, height, bit_depth, search_range, *, stre
                 planes = [eng.plane(width, height, bit_depth) for _ in range(n_planes)]
                 bufs_t = [torch.empty((height, width), dtype=t_dt, pin_memory=True) for _ in range(host_buffers)]
                 if keep is not None:
-                    keep.key, keep.planes, keep.bufs_t = key, planes, bufs_t
+                    keep.key, keep.engine, keep.planes, keep.bufs_t = key, eng, planes, bufs_t
             bufs = [t.numpy().view(np_dt) for t in bufs_t]
             order = [p for l in loads for (p, _) in l]
             torch.cuda.synchronize(dev)

@@ -23,6 +23,11 @@ int hmme_test_time_search_kernel(hmme_ctx* ctx, const hmme_plane* cur, const hmm
  * out[2] = workgroups (segments) of the tail, out[3] = 1 if head and tail are one launch */
 int hmme_test_tail_plan(int width, int height, int search_range, int n_pairs, int slots, int* out);
 
+/* where the staging arena of a synchronous, host-array call puts n items of bytes[i] bytes (hmme.hip stage_layout: what every hmme_*_frame*
+ * entry point lays its arrays out with; host arithmetic, needs no device): offsets[i] and *total, the arena's size.  Returns the alignment of
+ * every item, or a negative value for a null argument */
+int hmme_test_stage_layout(const size_t* bytes, int n, size_t* offsets, size_t* total);
+
 /* which job the k-th workgroup of a refinement launch over `n_pairs` whole pictures of width x height takes (me_frac_deal, me_kernels.hpp:
  * edge CTUs of every pair first, then the interiors); host code, needs no device.  -1 for k outside the launch */
 int hmme_test_frac_deal(int k, int n_pairs, int width, int height);

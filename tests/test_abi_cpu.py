@@ -340,6 +340,55 @@ def test_tail_plan_of_whole_picture_searches():
     assert L.hmme_test_tail_plan(1280, 720, 65, 1, 512, (C.c_int * 4)()) != 0      # windows beyond 129 x 129 are tiled, not planned here
 
 
+def test_stage_layout_of_every_synchronous_family():
+    """hmme.hip stage_layout, through hmme_test_stage_layout: where the staging arena of a synchronous, host-array call puts the call's items
+    (host arithmetic).  The item sizes of every staging family for a picture of 8 CTUs and of one, whole range, and zero-sized items (an
+    array the caller left out) in front, in the middle and at the end: every offset is a multiple of the alignment the hook returns (>= 16:
+    the select kernels move 8-byte entries), items keep their order and do not overlap, an empty item takes no room, and the arena ends
+    where the last item does, rounded up."""
+    from hmme import api
+    L = api.load()
+    szp = C.POINTER(C.c_size_t)
+    L.hmme_test_stage_layout.restype = C.c_int
+    L.hmme_test_stage_layout.argtypes = [szp, C.c_int, szp, szp]
+
+    def layout(sizes):
+        n = len(sizes)
+        off, total = (C.c_size_t * max(n, 1))(), C.c_size_t(~0)
+        align = L.hmme_test_stage_layout((C.c_size_t * max(n, 1))(*sizes), n, off, C.byref(total))
+        assert align >= 16 and align & (align - 1) == 0
+        return align, list(off)[:n], total.value
+
+    def families(n_ctu, refs=2):
+        tab, pred, per = 593 * 4 * n_ctu, 4 * n_ctu, 64          # one (CTU, reference) table of MVs or costs; predictors; MVs per CTU
+        w, h = 64 * n_ctu - 3, 61                                   # odd image sizes
+        yield "search", [pred * refs, tab * refs, tab * refs]
+        yield "refine", [pred, tab, tab, tab]
+        yield "bi", [4 * n_ctu * per, pred, pred, tab, tab, tab]
+        yield "bi, no centres, no predictors", [4 * n_ctu * per, 0, 0, tab, tab, tab]
+        yield "predict", [4 * n_ctu * per * 2, n_ctu * 64, w * h, (w // 2) * (h // 2)]
+        yield "select", [2 * tab * refs, 2 * tab * refs, pred * refs, 4 * n_ctu * per * refs, 4 * n_ctu * per * refs, n_ctu * per, 2 * n_ctu * per, 4 * n_ctu]
+        yield "select, fields only", [tab, tab, 0, 0, 4 * n_ctu, 0, 0, 0]
+        yield "empty items only", [0, 0, 0]
+        yield "no items", []
+        yield "bytes", [0, 1, 0, 15, 16, 17, 0]
+
+    checked = 0
+    for n_ctu in (8, 1):
+        for name, sizes in families(n_ctu):
+            align, off, total = layout(sizes)
+            up = lambda v: -(-v // align) * align
+            end = 0
+            for i, (o, b) in enumerate(zip(off, sizes)):
+                assert o % align == 0 and o >= end, (name, n_ctu, i)          # aligned, behind every item before it
+                assert o == up(end), (name, n_ctu, i)                         # ... and no further: an empty item has taken no room
+                end = o + b
+            assert total == up(end), (name, n_ctu)
+            checked += 1
+    assert checked == 20
+    assert L.hmme_test_stage_layout(None, 1, None, None) < 0
+
+
 def test_picture_job_matches_the_oracle_window_for_every_job_of_a_launch():
     """me_picture_job (host + device function: what the five job-table kernels and the table-less refinement launch derive a job from), through
     hmme_test_picture_job: job i of a launch over CTUs [first, first + count) and two references is reference i // count (in ctu_x & 63),

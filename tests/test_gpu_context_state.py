@@ -241,7 +241,7 @@ def refused(g, bd, what):
 
 def refine(g, bd, sr, form, had=True, pred=None, center=None, per=1):
     """a search and the refinement of its winners with the same arguments -> (mv, sad, qmv, cost).  form: "plain", "w2" (two pairs with
-    different weights in one refine_pairs_w_device call: two runs), "bi", "bi_w" """
+    different weights in one refine_pairs_w_device call: two runs), "w" (search_frame_w and refine_frame_w with the weight FADE), "bi", "bi_w" """
     names = [pl(g, bd, "cur", 0), pl(g, bd, "ref", 1), pl(g, bd, "other", 2)]
 
     def run(eng, P):
@@ -252,6 +252,9 @@ def refine(g, bd, sr, form, had=True, pred=None, center=None, per=1):
         if form == "plain":
             mv, sad = eng.search_frame(P[0], P[1], sr, pq)
             return (mv, sad) + eng.refine_frame(P[0], P[1], sr, mv, pq, use_hadamard=had)
+        if form == "w":
+            mv, sad = eng.search_frame_w(P[0], P[1], sr, at(FADE, bd), pq)
+            return (mv, sad) + eng.refine_frame_w(P[0], P[1], sr, at(FADE, bd), mv, pq, use_hadamard=had)
         if form == "bi":
             f = field_of(g, per)
             mv, sad = eng.search_frame_bi(P[0], P[1], P[2], sr, f, center_q=cq, pred_q=pq)
@@ -360,6 +363,10 @@ def spot_refine(oracle_lib, hmo, step, got, seed=2):
         for c in ctus:
             oq, oc = oracle_lib.refine_frame(org, ref, (m, m), w, h, mv[c:c + 1], pq, lq, had, bd, ctu_first=c, ctu_count=1)
             assert np.array_equal(qmv[c], oq[0]) and np.array_equal(cost[c], oc[0]), f"[{step.label}] CTU {c} on the used context differs from the oracle"
+    elif i["kind"] == "refine_w":
+        blocks = np.ascontiguousarray(cur[m:m + h, m:m + w])   # (the picture's CTU blocks at origin (0, 0): GEOM sizes are whole CTUs)
+        oq, oc = fh.oracle_origin_refine_w(oracle_lib, blocks, ref, w, h, mv[ctus], pq, lq, had, bd, at(FADE, bd), ctus)
+        assert np.array_equal(qmv[ctus], oq) and np.array_equal(cost[ctus], oc), f"[{step.label}] on the used context differs from the oracle"
     elif i["kind"] == "refine_bi_w":
         i = dict(i, wps=(at(BI_W, bd), at(BI_OW, bd)))
         oq, oc = fh.oracle_origin_refine_w(oracle_lib, origin_of(hmo, i), ref, w, h, mv[ctus], pq, lq, had, bd, i["wps"][0], ctus)
@@ -462,7 +469,7 @@ def tail_plan(g, n_pairs, sr=64):
 def test_search_tables_at_the_four_launch_shapes(used, oracle_lib, hmo):
     """transition 9 of the list above: the 8-bit launch shapes at search range 64 on a 256-CU part (512 workgroup slots), from pairs of small
     pictures -- 342 jobs all tail, then 456, 570 (head, then the tail in a launch of its own: its table at tail_jobs_off), 912 (head and tail
-    in one launch), 510 (whole), 570 again -- so d_jobs, d_first_strip and the merge table grow between uses and every layout follows every
+    in one launch), 510 (whole), 570 again -- so kJobs, kFirstStrip and the merge table grow between uses and every layout follows every
     other.  (The cost model of plan_tail8 runs 456 jobs whole, like 510: 456 x 17 units on 512 segments are 16 lane-iterations against 17
     of whole jobs, not the 8 % it asks for.  The count stays in the sequence as a second whole-jobs table of another size; the all-tail shape
     comes from 342.)"""
@@ -501,7 +508,7 @@ def test_search_tables_at_the_four_launch_shapes(used, oracle_lib, hmo):
 
 # ---- b: merge table ------------------------------------------------------------------------------------------------------------------------
 def test_merge_table_grows_between_two_launches_that_merge_through_it(used, oracle_lib, hmo):
-    """d_best and best_clean (merge_table, finalize_best).  Each sequence makes the table grow between two launches that merge through it
+    """kBest and best_clean (merge_table, finalize_best).  Each sequence makes the table grow between two launches that merge through it
     and ends with a launch smaller than the one before: stale keys of the larger launch would lie beyond what the last finalize reset."""
     S = [
         # all-tail 8 bit (15 jobs), 10-bit strips of a larger picture (60), all-tail 8 bit again
@@ -533,7 +540,7 @@ def test_merge_table_in_a_context_of_its_own_first_small_then_large():
 
 # ---- c: refinement -------------------------------------------------------------------------------------------------------------------------
 def test_refinement_forms_in_alternation(used, oracle_lib, hmo):
-    """frac_jobs_tag, the d_wp copies, d_bi, the LDS opt-in and occupancy query of each me_frac_kernel build (launch_refine): plain, weighted
+    """frac_jobs_tag, the kWp0..kWp3 copies, the staging arena, the LDS opt-in and occupancy query of each me_frac_kernel build (launch_refine): plain, weighted
     (two pairs with different weights: two runs in one call), bi and bi-weighted refinement in alternation on one size, Hadamard and SAD,
     8 and 10 bit, with and without predictors and centres.  The six builds are (Hadamard | SAD) x (8-bit planes, 16-bit planes, weighted):
     each is first used after another one has taken its opt-in."""
@@ -693,22 +700,199 @@ def spot_staging(oracle_lib, hmo, step, got):
         assert tuple(int(v) for v in got[0]) == tuple(int(v) for v in wem.plane_stats(luma[2][m:m + h, m:m + w].astype(np.int64))), f"[{step.label}] differs from the model"
 
 
+def search_calls(g, bd=8, sr=8):
+    """the synchronous search and refinement forms on one picture size (the steps of sections a and c): search_frame, search_frame_multi with
+    two references, refine_frame, search_frame_w / refine_frame_w, search_frame_bi / refine_frame_bi and their _w forms, with and without
+    predictors and centres, one and 64 MVs per CTU in the other list's field -- items of the arena that are there in one call and not in the next"""
+    return [plain(g, bd, sr, pred=91), pairs(g, bd, sr, 2, pred=92, form="multi"), refine(g, bd, sr, "plain", pred=93), weighted(g, bd, sr),
+            refine(g, bd, sr, "w", pred=94), bi(g, bd, sr, center=95, pred=96, per=64), bi(g, bd, sr, wps=(BI_W, BI_OW)),
+            refine(g, bd, sr, "bi", center=97), refine(g, bd, sr, "bi_w", pred=98, per=64)]
+
+
+def spot_multi(oracle_lib, step, got):
+    """search_frame_multi of the used context (one current picture against pictures 1 and 2) against the oracle, per reference"""
+    from hmme import synth
+    i, m = step.info, synth.MARGIN
+    g, bd = i["g"], i["bd"]
+    w, h = GEOM[g]
+    pq = preds(g, i["pred"], (i["n_pairs"],))
+    for r in range(i["n_pairs"]):
+        cur, ref = content(cid(g, bd, 0)), content(cid(g, bd, 1 + r % 2))
+        for c in spot_ctus(n_ctu(g), 11 + r):
+            ox, oy, os_ = oracle_lib.search_frame(cur, ref, (m, m), w, h, i["sr"], None if pq is None else pq[r], lambda_q16(step.lam), i["fen"], bd, ctu_first=c, ctu_count=1)
+            assert np.array_equal(got[0][r, c, :, 0], ox[0]) and np.array_equal(got[0][r, c, :, 1], oy[0]) and np.array_equal(got[1][r, c], os_[0]), \
+                f"[{step.label}] reference {r} CTU {c} on the used context differs from the oracle"
+
+
 @pytest.mark.parametrize("seed", [20261, 77003])
 def test_host_staging_calls_in_shuffled_order(used, oracle_lib, hmo, seed):
-    """d_bi, d_sel, the prediction staging and d_wpest behind the fourteen host-facing calls: all of them on a small picture, then on a
-    larger one (every staging buffer grows in the middle of the sequence), then on the small one again, each pass in a seeded order"""
+    """The staging arena (kStage) behind every synchronous, host-array form, and kWpEst: the fourteen prediction, selection and estimation
+    calls and the nine search and refinement forms, all of them on a small picture, then on a larger one (the arena grows in the middle of
+    the sequence), then on the small one again, each pass in a seeded order.  One arena serves them all, so a search's tables land where a
+    selection's outputs were and a short field where a long one was."""
     rng = np.random.default_rng(seed)
     S = []
     for g in ("T", "S", "T"):
-        calls = list(staging_calls(g).values())
+        calls = list(staging_calls(g).values()) + search_calls(g)
         S += [calls[k] for k in rng.permutation(len(calls))]
     outs = run_sequence(used, S, f"d (shuffle seed {seed})")
     seen = set()
     for st, got in reversed(list(zip(S, outs))):   # each family once, where it has the most history behind it: the last pass
-        if st.info["kind"] not in seen:
-            seen.add(st.info["kind"])
+        kind = st.info["kind"]
+        if kind in seen:
+            continue
+        seen.add(kind)
+        if kind in ("plain", "weighted", "bi", "bi_w"):
+            spot_search(oracle_lib, hmo, st, got)
+        elif kind == "pairs":
+            spot_multi(oracle_lib, st, got)
+        elif kind.startswith("refine_"):
+            spot_refine(oracle_lib, hmo, st, got)
+        else:
             spot_staging(oracle_lib, hmo, st, got)
-    assert len(seen) == 14
+    assert len(seen) == 14 + 9
+
+
+ODD_W, ODD_H, ODD_FIRST, ODD_COUNT, ODD_SPARE = 200, 72, 1, 3, 3      # 4 x 2 CTUs, partial on both edges; 100 x 36 chroma
+
+
+@pytest.mark.parametrize("bd", [8, 10])
+def test_host_staging_at_a_size_where_no_item_is_a_multiple_of_the_alignment(bd):
+    """The arena's items at sizes that are no multiple of its alignment: a 200 x 72 picture (8 CTUs, 100 x 36 chroma), the CTU range
+    [1, 4), images whose stride is the width + 3 samples.  predict_frame, predict_chroma_frame, predict_bi_frame, select_frame and
+    select_dirs_frame run through the C entries on one context, in an order in which every call follows one of another family, the
+    selections with all optional outputs and with each one left out; every output array and image is pre-filled with a sentinel.  Each
+    call's outputs equal a fresh context's, every sentinel outside the CTU range and in the stride padding is untouched, and something
+    inside the range is written."""
+    from hmme import api
+    w, h, first, cnt, spare = ODD_W, ODD_H, ODD_FIRST, ODD_COUNT, ODD_SPARE
+    n, ctus_x = sdm.n_ctus(w, h), (w + 63) // 64
+    assert n == 8
+    rng = np.random.default_rng(9100 + bd)
+    dt, sentinel = (np.uint8, 0xA5) if bd == 8 else (np.uint16, 0xA5A5)
+    pics = [rng.integers(0, 1 << bd, size=(h, w)).astype(np.int16) for _ in range(2)] + [rng.integers(0, 1 << bd, size=(h // 2, w // 2)).astype(np.int16) for _ in range(2)]
+    field64, field1 = fh.random_field(n, 64, 9101), fh.random_field(n, 1, 9102)
+    field2 = np.ascontiguousarray(np.stack([fh.random_field(n, 64, 9103), fh.random_field(n, 64, 9104)]))
+    dirs64 = rng.choice(np.array([1, 2, 3, 3, 0xFF], np.uint8), size=(n, 64))
+    t_mv, t_cost = (np.ascontiguousarray(a) for a in sm.random_tables(cnt, seed=9105))
+    pred = np.ascontiguousarray(sdm.predictors(n, 9106))
+    dir_tabs = [np.ascontiguousarray(a) for a in sdm.random_dir_tables(n, cnt, 9107, pred, first, lambda_q16())]
+    fp, sel, dp = api.FrameParams(1, 0, bd, first, cnt), api.SelectParams(64), api.DirParams(*sdm.HM_BITS)
+    fp_sel = api.FrameParams(1, 0, 8, first, cnt)
+    ptr = lambda a: None if a is None else a.ctypes.data
+
+    def inside(half):
+        """the samples of the CTU range in an image of the picture (half: of a chroma plane)"""
+        s = 32 if half else 64
+        m = np.zeros((h // 2, w // 2) if half else (h, w), bool)
+        for c in range(first, first + cnt):
+            m[(c // ctus_x) * s:(c // ctus_x + 1) * s, (c % ctus_x) * s:(c % ctus_x + 1) * s] = True
+        return m
+
+    def image(half=False):
+        return np.full((h // 2, w // 2 + spare) if half else (h, w + spare), sentinel, dt)
+
+    def check_image(img, half=False):
+        wi, m = img.shape[1] - spare, inside(half)
+        assert (img[:, wi:] == sentinel).all() and (img[:, :wi][~m] == sentinel).all() and (img[:, :wi][m] != sentinel).any()
+
+    def check_rows(a, fill, axis=0):
+        """a select output: the entries of the CTUs outside the range keep the sentinel, those inside do not all"""
+        a = np.moveaxis(a, axis, 0)
+        out = np.ones(n, bool)
+        out[first:first + cnt] = False
+        assert (a[out] == fill).all() and (a[~out] != fill).any()
+
+    def predict(e, P):
+        img = image()
+        assert e.L.hmme_predict_frame(e.h, P[0].h, C.byref(fp), ptr(field64), 64, ptr(img), w + spare) == 0
+        check_image(img)
+        return (img,)
+
+    def predict1(e, P):
+        img = image()
+        assert e.L.hmme_predict_frame(e.h, P[1].h, C.byref(fp), ptr(field1), 1, ptr(img), w + spare) == 0
+        check_image(img)
+        return (img,)
+
+    def predict_chroma(e, P):
+        cb, cr = image(True), image(True)
+        planes, outs = (C.c_void_p * 2)(P[2].h, P[3].h), (C.c_void_p * 2)(ptr(cb), ptr(cr))
+        assert e.L.hmme_predict_chroma_frame(e.h, planes, w, h, C.byref(fp), None, ptr(field64), 64, outs, w // 2 + spare) == 0
+        check_image(cb, True)
+        check_image(cr, True)
+        return cb, cr
+
+    def predict_bi(e, P):
+        img = image()
+        assert e.L.hmme_predict_bi_frame(e.h, P[0].h, P[1].h, C.byref(fp), ptr(field2), ptr(dirs64), 64, ptr(img), w + spare) == 0
+        check_image(img)
+        return (img,)
+
+    def select(slot, cost, with_pred):
+        def run(e, P):
+            f = np.full((n, 64, 2), 0x1111, np.int16)
+            s = np.full((n, 64), 0x3333, np.uint16) if slot else None
+            c = np.full(n, 0x44444444, np.uint32) if cost else None
+            assert e.L.hmme_select_frame(e.h, w, h, C.byref(fp_sel), C.byref(sel), ptr(t_mv), ptr(t_cost), ptr(pred[0]) if with_pred else None, ptr(f), ptr(s), ptr(c)) == 0
+            for a, fill in ((f, 0x1111), (s, 0x3333), (c, 0x44444444)):
+                if a is not None:
+                    check_rows(a, fill)
+            return tuple(a for a in (f, s, c) if a is not None)
+        return run
+
+    def select_dirs(slot, cost, with_pred):
+        def run(e, P):
+            f, d = np.full((2, n, 64, 2), 0x1111, np.int16), np.full((n, 64), 0x22, np.uint8)
+            s = np.full((n, 64), 0x3333, np.uint16) if slot else None
+            c = np.full(n, 0x44444444, np.uint32) if cost else None
+            assert e.L.hmme_select_dirs_frame(e.h, w, h, C.byref(fp_sel), C.byref(sel), C.byref(dp), *[ptr(a) for a in dir_tabs], ptr(pred) if with_pred else None,
+                                              ptr(f), ptr(d), ptr(s), ptr(c)) == 0
+            check_rows(f, 0x1111, axis=1)
+            for a, fill in ((d, 0x22), (s, 0x3333), (c, 0x44444444)):
+                if a is not None:
+                    check_rows(a, fill)
+            return tuple(a for a in (f, d, s, c) if a is not None)
+        return run
+
+    calls = [("predict_frame", predict), ("select all", select(True, True, True)), ("predict_chroma_frame", predict_chroma), ("select no slot", select(False, True, True)),
+             ("predict_bi_frame", predict_bi), ("select_dirs all", select_dirs(True, True, True)), ("select no cost", select(True, False, False)),
+             ("predict_frame per 1", predict1), ("select_dirs no slot", select_dirs(False, True, False)), ("predict_chroma_frame", predict_chroma),
+             ("select_dirs no cost", select_dirs(True, False, True)), ("select fields only", select(False, False, True)), ("predict_bi_frame", predict_bi),
+             ("select_dirs fields only", select_dirs(False, False, True)), ("predict_frame", predict), ("select all", select(True, True, True))]
+
+    def context():
+        ctx = Ctx()
+        ctx.eng.set_lambda(LAMBDA)
+        planes = []
+        for a in pics:
+            p = ctx.eng.plane(a.shape[1], a.shape[0], bd)
+            p.upload_u8(a.astype(np.uint8)) if bd == 8 else p.upload_pel(a, (0, 0))
+            planes.append(p)
+        return ctx, planes
+
+    def close(ctx, planes):
+        for p in planes:
+            p.close()
+        ctx.close()
+
+    fresh = {}
+    for name, run in calls:
+        if name not in fresh:
+            ctx, planes = context()
+            try:
+                fresh[name] = run(ctx.eng, planes)
+            finally:
+                close(ctx, planes)
+    ctx, planes = context()
+    try:
+        for k, (name, run) in enumerate(calls):
+            got = run(ctx.eng, planes)
+            assert len(got) == len(fresh[name])
+            for j, (a, b) in enumerate(zip(got, fresh[name])):
+                assert np.array_equal(a, b), f"call {k} [{name}] output {j} differs from the fresh context's (the call before: [{calls[k - 1][0] if k else '-'}])"
+    finally:
+        close(ctx, planes)
 
 
 # ---- e: streams ----------------------------------------------------------------------------------------------------------------------------
