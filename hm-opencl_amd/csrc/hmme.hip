@@ -237,7 +237,9 @@ struct Stage {
     size_t up_bytes = 0;
     void* down = nullptr;                   // linear out and image: the host array
     size_t parts = 0, part_bytes = 0, off = 0, len = 0;   // linear out: of each of `parts` equal parts the bytes [off, off + len) come back
-    size_t row = 0, rows = 0, stride = 0;   // image: rows of `row` bytes, `stride` bytes apart at the host, packed on the device
+    size_t row = 0, rows = 0, stride = 0;   // image: rows of `row` bytes, `stride` bytes apart at the host, `pitch` (packed: `row`) on the device
+    size_t pitch = 0;
+    const void* up_image = nullptr;         // image that only goes up (the caller's is const): `down` is null
   };
   hmme_ctx* ctx;
   std::vector<Item> items;
@@ -256,9 +258,15 @@ struct Stage {
     return add(it);
   }
   // in and out: uploaded before the launch, so samples the kernel does not write come back as they were
-  int image(void* host, size_t row, size_t rows, size_t stride) {
+  int image(void* host, size_t row, size_t rows, size_t stride, size_t pitch = 0) {
     Item it;
-    if (host && row * rows) { it.bytes = row * rows; it.down = host; it.row = row; it.rows = rows; it.stride = stride; }
+    if (host && row * rows) { it.pitch = pitch ? pitch : row; it.bytes = it.pitch * rows; it.down = host; it.row = row; it.rows = rows; it.stride = stride; }
+    return add(it);
+  }
+  // in only: an image the launch reads
+  int image_in(const void* host, size_t row, size_t rows, size_t stride) {
+    Item it;
+    if (host && row * rows) { it.pitch = row; it.bytes = row * rows; it.up_image = host; it.row = row; it.rows = rows; it.stride = stride; }
     return add(it);
   }
   uint8_t* at(int i) const { return items[i].bytes ? ctx->buf[kStage].as<uint8_t>() + at_[i] : nullptr; }
@@ -271,7 +279,7 @@ struct Stage {
     if (rc) return rc;
     for (size_t i = 0; i < items.size(); ++i) {
       const Item& it = items[i];
-      if (it.row) HIP_TRY(ctx, hipMemcpy2DAsync(at((int)i), it.row, it.down, it.stride, it.row, it.rows, hipMemcpyHostToDevice, ctx->stream));
+      if (it.row) HIP_TRY(ctx, hipMemcpy2DAsync(at((int)i), it.pitch, it.down ? it.down : it.up_image, it.stride, it.row, it.rows, hipMemcpyHostToDevice, ctx->stream));
       for (int k = 0; k < 2; ++k)
         if (it.up[k]) HIP_TRY(ctx, hipMemcpyAsync(at((int)i) + k * it.up_bytes, it.up[k], it.up_bytes, hipMemcpyHostToDevice, ctx->stream));
     }
@@ -280,7 +288,7 @@ struct Stage {
   int end() {
     for (size_t i = 0; i < items.size(); ++i) {
       const Item& it = items[i];
-      if (it.row) HIP_TRY(ctx, hipMemcpy2DAsync(it.down, it.stride, at((int)i), it.row, it.row, it.rows, hipMemcpyDeviceToHost, ctx->stream));
+      if (it.row && it.down) HIP_TRY(ctx, hipMemcpy2DAsync(it.down, it.stride, at((int)i), it.pitch, it.row, it.rows, hipMemcpyDeviceToHost, ctx->stream));
       for (size_t p = 0; p < it.parts; ++p) {
         const size_t o = p * it.part_bytes + it.off;
         HIP_TRY(ctx, hipMemcpyAsync((uint8_t*)it.down + o, at((int)i) + o, it.len, hipMemcpyDeviceToHost, ctx->stream));
@@ -2682,6 +2690,102 @@ int hmme_select_frame(hmme_ctx* ctx, int width, int height, const hmme_frame_par
                        [&](void* d_mv, void* d_cost, void* d_pred_q, void*, void* d_field, void*, void* d_slot, void* d_ccost, hipStream_t s) {
                          return hmme_select_pairs_device(ctx, width, height, 1, fp, sel, d_mv, d_cost, d_pred_q, d_field, d_slot, d_ccost, s);
                        });
+}
+
+// ---- residual and per-PU / per-CU distortion of a prediction (the rule: include/hmme.h) -------------------------------------------------------
+namespace {
+extern "C++" {
+template <typename T>
+void launch_residual(dim3 grid, hipStream_t s, int per, bool had, bool map, const hmme::RefSet& blocks, const hmme::RefSet& preds, int pred_pitch, const uint16_t* d_slot,
+                     const hmme::MeResidualSet& resid, int resid_pitch, uint32_t* d_pu, uint32_t* d_cu, uint32_t* d_ctu, const hmme_plane* p0, int first) {
+  const auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, blocks, preds, pred_pitch, d_slot, resid, resid_pitch, d_pu, d_cu, d_ctu, p0->width, p0->height, p0->bit_depth,
+                       p0->n_ctu, first);
+  };
+  const auto with_map = [&](auto per_c, auto had_c) {
+    if (map) go(hmme::me_residual_kernel<T, decltype(per_c)::value, decltype(had_c)::value, true>);
+    else go(hmme::me_residual_kernel<T, decltype(per_c)::value, decltype(had_c)::value, false>);
+  };
+  const auto with_had = [&](auto per_c) {
+    if (had) with_map(per_c, std::true_type{}); else with_map(per_c, std::false_type{});
+  };
+  if (per == 64) with_had(std::integral_constant<int, 64>{}); else with_had(std::integral_constant<int, 256>{});
+}
+}  // extern "C++"
+}  // namespace
+
+int hmme_residual_pairs_device(hmme_ctx* ctx, const hmme_plane* const* curs, const void* const* d_preds, int pred_pitch_bytes, int n_pairs,
+                               const hmme_frame_params* fp, const void* d_slot, int mv_per_ctu, int use_hadamard, void* const* d_out_resid,
+                               int resid_pitch_bytes, void* d_out_pu, void* d_out_cu, void* d_out_ctu, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  const char* who = "hmme_residual_pairs_device";
+  if (!curs || !d_preds || !fp || n_pairs < 1 || n_pairs > hmme::kMaxRefs)
+    return fail(ctx, HMME_ERR_ARG, "%s: %d picture pairs outside 1..%d (or a null argument)", who, n_pairs, hmme::kMaxRefs);
+  if ((mv_per_ctu != 64 && mv_per_ctu != 256) || (use_hadamard != 0 && use_hadamard != 1))
+    return fail(ctx, HMME_ERR_ARG, "%s: %d blocks per CTU (64 or 256), use_hadamard %d (0 or 1)", who, mv_per_ctu, use_hadamard);
+  if (!d_out_resid && !d_out_pu && !d_out_cu && !d_out_ctu) return fail(ctx, HMME_ERR_ARG, "%s: no output", who);
+  hmme::RefSet preds = {};
+  hmme::MeResidualSet resid = {};
+  for (int r = 0; r < n_pairs; ++r) {
+    if (!curs[r] || !d_preds[r]) return fail(ctx, HMME_ERR_ARG, "%s: null plane or predicted image", who);
+    if (curs[r]->ctx != ctx) return fail(ctx, HMME_ERR_ARG, "%s: plane belongs to another context (planes are used with the context that created them)", who);
+    if (curs[r]->bit_depth != fp->bit_depth) return fail(ctx, HMME_ERR_ARG, "%s: planes hold %d-bit samples, the call asks for %d", who, curs[r]->bit_depth, fp->bit_depth);
+    preds.base[r] = (const uint8_t*)d_preds[r];
+    resid.base[r] = d_out_resid ? (uint8_t*)d_out_resid[r] : nullptr;
+    if (((uintptr_t)preds.base[r] & 3) || ((uintptr_t)resid.base[r] & 7)) return fail(ctx, HMME_ERR_ARG, "%s: misaligned image (predicted 4 bytes, residual 8)", who);
+  }
+  const hmme_plane* p0 = curs[0];
+  if (pred_pitch_bytes < p0->width * p0->bps) return fail(ctx, HMME_ERR_ARG, "%s: predicted pitch %d below a picture row", who, pred_pitch_bytes);
+  if (d_out_resid && (resid_pitch_bytes < p0->width * 2 || (resid_pitch_bytes & 7)))
+    return fail(ctx, HMME_ERR_ARG, "%s: residual pitch %d below a picture row of int16, or no multiple of 8", who, resid_pitch_bytes);
+  if (((uintptr_t)d_slot & 3) || ((uintptr_t)d_out_pu & 3) || ((uintptr_t)d_out_cu & 3) || ((uintptr_t)d_out_ctu & 3))
+    return fail(ctx, HMME_ERR_ARG, "%s: misaligned buffer (slots and the uint32 outputs 4 bytes)", who);
+  hmme_frame_params f = *fp;
+  f.search_range = 1;   // not consulted: nothing is searched
+  hipStream_t s = (hipStream_t)stream;
+  PairLaunch pl;
+  int rc = named(ctx, who, pairs_begin(ctx, curs, curs, n_pairs, &f, s, &pl));   // one size, the CTU range; ordered behind the planes' fills
+  if (rc || pl.count == 0) return rc;
+  const dim3 grid((unsigned)pl.count, (unsigned)n_pairs);
+  with_sample_type(p0->bps, [&](auto sample) {
+    launch_residual<decltype(sample)>(grid, s, mv_per_ctu, use_hadamard != 0, d_slot != nullptr, pl.cur_blocks, preds, pred_pitch_bytes, (const uint16_t*)d_slot, resid,
+                                      resid_pitch_bytes, (uint32_t*)d_out_pu, (uint32_t*)d_out_cu, (uint32_t*)d_out_ctu, p0, pl.first);
+  });
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "%s: launch -> %s", who, hipGetErrorString(e));
+  return pairs_end(ctx, curs, curs, n_pairs, s, rc);
+}
+
+int hmme_residual_frame(hmme_ctx* ctx, const hmme_plane* cur, const hmme_frame_params* fp, const void* pred, int pred_stride, const uint16_t* slot,
+                        int mv_per_ctu, int use_hadamard, int16_t* out_resid, int resid_stride, uint32_t* out_pu, uint32_t* out_cu, uint32_t* out_ctu) {
+  if (!ctx) return HMME_ERR_ARG;
+  const char* who = "hmme_residual_frame";
+  if (!cur || !fp || !pred) return fail(ctx, HMME_ERR_ARG, "%s: null argument", who);
+  if ((mv_per_ctu != 64 && mv_per_ctu != 256) || (use_hadamard != 0 && use_hadamard != 1))
+    return fail(ctx, HMME_ERR_ARG, "%s: %d blocks per CTU (64 or 256), use_hadamard %d (0 or 1)", who, mv_per_ctu, use_hadamard);
+  if (cur->ctx != ctx) return fail(ctx, HMME_ERR_ARG, "%s: plane belongs to another context (planes are used with the context that created them)", who);
+  if (pred_stride < cur->width || (out_resid && resid_stride < cur->width))
+    return fail(ctx, HMME_ERR_ARG, "%s: stride %d / %d below the picture width", who, pred_stride, resid_stride);
+  int first, count;
+  int rc = named(ctx, who, ctu_range(ctx, fp, cur->n_ctu, &first, &count));
+  if (rc || count == 0) return rc;
+  const size_t n_ctu = cur->n_ctu, per = mv_per_ctu, row = (size_t)cur->width * cur->bps, rrow = (size_t)cur->width * 2, rpitch = (rrow + 7) & ~(size_t)7;
+  Stage st(ctx);
+  const int i_pred = st.image_in(pred, row, cur->height, (size_t)pred_stride * cur->bps), i_slot = st.in(slot, n_ctu * per * 2);
+  const int i_res = st.image(out_resid, rrow, cur->height, (size_t)resid_stride * 2, rpitch);
+  // only the CTUs of the range come back: the caller's entries outside it keep their values
+  const int o_pu = st.out(out_pu, n_ctu * per * 4, first * per * 4, count * per * 4), o_cu = st.out(out_cu, n_ctu * per * 4, first * per * 4, count * per * 4);
+  const int o_ctu = st.out(out_ctu, n_ctu * 8, (size_t)first * 8, (size_t)count * 8);
+  rc = st.begin();
+  if (rc == HMME_OK) {
+    const void* d_pred = st.at(i_pred);
+    void* d_res = st.at(i_res);
+    rc = hmme_residual_pairs_device(ctx, &cur, &d_pred, (int)row, 1, fp, st.at(i_slot), mv_per_ctu, use_hadamard, out_resid ? &d_res : nullptr, (int)rpitch, st.at(o_pu),
+                                    st.at(o_cu), st.at(o_ctu), ctx->stream);
+    if (rc && ctx->err.compare(0, strlen("hmme_residual_pairs_device"), "hmme_residual_pairs_device") == 0)
+      ctx->err.replace(0, strlen("hmme_residual_pairs_device"), who);   // the refusal names the entry the caller made
+  }
+  return rc ? rc : st.end();
 }
 
 // ---- reference picture per PU: the decision over all references' tables, and the prediction that follows it ---------------------------------

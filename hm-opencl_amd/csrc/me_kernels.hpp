@@ -2654,6 +2654,198 @@ me_select_dirs_kernel(const uint32_t* __restrict__ mv_uni, const uint32_t* __res
                                                pic_w, pic_h, out_field + at, out_dir, out_slot, out_cost, uni_field + at, lists);
 }
 
+// ---- residual and per-PU / per-CU distortion of a prediction (hmme_residual_pairs_device; the rule: include/hmme.h) -----------------------
+// The slot layout read backwards: what me_slot_of<D> encodes, by the bases of its families.  Depth of the CU a slot belongs to:
+//   [0, 256) 2NxN / Nx2N of 8x8 CUs, [256, 384) AMP of 16x16, [384, 448) 2Nx2N 8x8, [448, 512) 2NxN / Nx2N 16x16, [512, 544) AMP 32x32,
+//   [544, 560) 2Nx2N 16x16, [560, 576) 2NxN / Nx2N 32x32, [576, 584) AMP 64x64, [584, 588) 2Nx2N 32x32, [588, 593) the 64x64 CU's other shapes
+__host__ __device__ constexpr int me_slot_depth(int s) {
+  return s < 256 ? 3 : s < 384 ? 2 : s < 448 ? 3 : s < 512 ? 2 : s < 544 ? 1 : s < 560 ? 2 : s < 576 ? 1 : s < 584 ? 0 : s < 588 ? 1 : 0;
+}
+// xGetHADs takes 8x8 Hadamards when both sides of the PU are multiples of 8: everything but 8x4 / 4x8 (slots 0..255) and the AMP shapes of a
+// 16x16 CU (16x4, 16x12, 4x16, 12x16: slots 256..383).  Such a PU is 8-aligned in position as well, so it covers whole lane quads.
+__host__ __device__ constexpr bool me_slot_had8(int s) { return s >= 384; }
+// index of the depth-d CU that holds the 4x4 block (bx4, by4) among the CTU's 85 CUs: 1 + 4 + 16 + 64, raster order inside a depth
+__host__ __device__ constexpr int me_cu_index(int depth, int bx4, int by4) {
+  return ((1 << (2 * depth)) - 1) / 3 + ((by4 >> (4 - depth)) << depth) + (bx4 >> (4 - depth));
+}
+constexpr int kResidualCus = 85;
+static_assert(me_cu_index(3, 15, 15) == kResidualCus - 1 && me_cu_index(0, 15, 15) == 0 && me_cu_index(1, 8, 0) == 2 && me_cu_index(2, 0, 4) == 9, "85 CUs per CTU");
+static_assert(me_slot_depth(0) == 3 && me_slot_depth(255) == 3 && me_slot_depth(256) == 2 && me_slot_depth(383) == 2 && me_slot_depth(384) == 3 &&
+              me_slot_depth(447) == 3 && me_slot_depth(448) == 2 && me_slot_depth(511) == 2 && me_slot_depth(512) == 1 && me_slot_depth(543) == 1 &&
+              me_slot_depth(544) == 2 && me_slot_depth(559) == 2 && me_slot_depth(560) == 1 && me_slot_depth(575) == 1 && me_slot_depth(576) == 0 &&
+              me_slot_depth(583) == 0 && me_slot_depth(584) == 1 && me_slot_depth(587) == 1 && me_slot_depth(588) == 0 && me_slot_depth(592) == 0,
+              "the family bases of me_slot_of");
+
+// the int16 residual images of a launch, one per pair (null: the pair has none)
+struct MeResidualSet { uint8_t* base[kMaxRefs]; };
+
+__device__ __forceinline__ int me_quad_xor1(int v) { return __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false); }   // quad_perm [1,0,3,2]
+__device__ __forceinline__ int me_quad_xor2(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false); }   // quad_perm [2,3,0,1]
+__device__ __forceinline__ uint32_t me_quad_sum(uint32_t v) {
+  v += (uint32_t)me_quad_xor1((int)v);
+  return v + (uint32_t)me_quad_xor2((int)v);
+}
+__device__ __forceinline__ uint32_t me_wave_sum(uint32_t v) {
+#pragma unroll
+  for (int m = 32; m; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m);
+  return v;
+}
+// one row of four samples, widened; the address is 4-byte aligned
+template <typename SrcT>
+__device__ __forceinline__ void me_load_row4(const uint8_t* p, int* v) {
+  if (sizeof(SrcT) == 1) {
+    const uint32_t a = *(const uint32_t*)p;
+    v[0] = a & 0xff; v[1] = (a >> 8) & 0xff; v[2] = (a >> 16) & 0xff; v[3] = a >> 24;
+  } else {
+    const uint32_t a = ((const uint32_t*)p)[0], b = ((const uint32_t*)p)[1];
+    v[0] = a & 0xffff; v[1] = a >> 16; v[2] = b & 0xffff; v[3] = b >> 16;
+  }
+}
+// the unnormalised 4-point Walsh-Hadamard butterfly on v[0], v[s], v[2s], v[3s]
+__device__ __forceinline__ void me_wht4(int* v, int s) {
+  const int s0 = v[0] + v[s], s1 = v[0] - v[s], s2 = v[2 * s] + v[3 * s], s3 = v[2 * s] - v[3 * s];
+  v[0] = s0 + s2; v[s] = s1 + s3; v[2 * s] = s0 - s2; v[3 * s] = s1 - s3;
+}
+
+// One workgroup of 256 lanes per CTU, blockIdx.y = pair; a lane holds one 4x4 block.  Lanes 4q .. 4q + 3 hold the four 4x4 blocks of 8x8
+// block q (raster order inside the CTU), so an 8x8 block is one DPP quad: its Hadamard is the 2x2 butterfly over the quad's four 4x4
+// transforms (H8 = H2 (x) H4: the |coefficients| are a permutation of xCalcHADs8x8's, the sum is the same), two quad_perm moves per
+// coefficient and no LDS, as me_frac_kernel assembles its own.  The 16 current samples come from the plane's CTU-blocked copy (whole for
+// partial CTUs), the 16 predicted ones from the pair's image: whole rows of four where the block lies inside the picture and the pitch is a
+// multiple of 4, sample by sample otherwise; a sample outside the picture has difference 0 and is never read from the image.  SAD, SSE and
+// the 4x4 transform are exact 32-bit integers in the lane.
+//   MAP:  slot_map (uint16 [n_pairs][n_ctu][PER]) names the PU of every block.  Per-PU and per-CU sums are ds_add_u32 into two LDS tables
+//         (593 slots, 85 CUs); one lane of a quad adds the 8x8 value of a slot made of 8x8 Hadamards.  After a barrier every lane reads its
+//         slot's and its CU's total.  A slot >= 593 (0xFFFF: no CU covers the block) carries 0 and adds nothing.
+//   !MAP: every block (8x8 with PER 64, 4x4 with 256) is its own PU and CU: no tables.
+// out_pu / out_cu: uint32 [n_pairs][n_ctu][PER]; out_ctu: uint32 [n_pairs][n_ctu][2] = (sum of the PU errors, sum of the CU SSEs); each may
+// be null.  With PER 64 lane 0 of a quad stores its block; a wave's stores are one run of 64 B (PER 64) or 256 B.  The residual leaves as
+// 8-byte rows, only inside the picture.  No scratch.  Bandwidth-sized: nothing tuned beyond that.
+template <typename SrcT, int PER, bool HAD, bool MAP>
+__global__ void __launch_bounds__(256)
+me_residual_kernel(RefSet cur_blocks, RefSet preds, int pred_pitch, const uint16_t* __restrict__ slot_map, MeResidualSet resid, int resid_pitch,
+                   uint32_t* __restrict__ out_pu, uint32_t* __restrict__ out_cu, uint32_t* __restrict__ out_ctu, int pic_w, int pic_h, int bit_depth,
+                   int n_ctu, int ctu_first) {
+  __shared__ uint32_t s_pu[MAP ? kParts + 3 : 1];
+  __shared__ uint32_t s_cu[MAP ? kResidualCus + 3 : 1];
+  __shared__ uint32_t s_tot[2];
+  const int tid = threadIdx.x, q = tid >> 2, sub = tid & 3;
+  const int bx4 = 2 * (q & 7) + (sub & 1), by4 = 2 * (q >> 3) + (sub >> 1);
+  const int pair = blockIdx.y, ctu = ctu_first + blockIdx.x, ctus_x = (pic_w + 63) >> 6;
+  const int x0 = (ctu % ctus_x) * 64 + bx4 * 4, y0 = (ctu / ctus_x) * 64 + by4 * 4;
+  const long o = (long)pair * n_ctu + ctu;
+  if constexpr (MAP) {
+    for (int i = tid; i < kParts; i += 256) s_pu[i] = 0;
+    if (tid < kResidualCus) s_cu[tid] = 0;
+  }
+  if (tid < 2) s_tot[tid] = 0;
+
+  // the lane's 16 differences
+  int d[16];
+  const uint8_t* cb = cur_blocks.base[pair] + ((long)ctu * 4096 + by4 * 256 + bx4 * 4) * (long)sizeof(SrcT);
+  const uint8_t* pb = preds.base[pair] + (long)y0 * pred_pitch + (long)x0 * (long)sizeof(SrcT);
+  const bool whole = x0 + 4 <= pic_w && y0 + 4 <= pic_h;
+  const bool rows4 = whole && !(pred_pitch & 3);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    int c[4], p[4];
+    me_load_row4<SrcT>(cb + r * 64 * (int)sizeof(SrcT), c);
+    if (rows4) {
+      me_load_row4<SrcT>(pb + (long)r * pred_pitch, p);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        p[i] = (x0 + i < pic_w && y0 + r < pic_h) ? (int)((const SrcT*)(pb + (long)r * pred_pitch))[i] : c[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) d[4 * r + i] = c[i] - p[i];
+  }
+  uint8_t* rb = resid.base[pair];   // workgroup-uniform
+  if (rb) {
+    rb += (long)y0 * resid_pitch + (long)x0 * 2;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      if (whole) {
+        *(uint2*)(rb + (long)r * resid_pitch) = make_uint2((uint32_t)(d[4 * r] & 0xffff) | (uint32_t)d[4 * r + 1] << 16,
+                                                           (uint32_t)(d[4 * r + 2] & 0xffff) | (uint32_t)d[4 * r + 3] << 16);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (x0 + i < pic_w && y0 + r < pic_h) ((int16_t*)(rb + (long)r * resid_pitch))[i] = (int16_t)d[4 * r + i];
+      }
+    }
+  }
+
+  // SAD, SSE (xGetSSE: every square shifted before it is added) and, with HAD, the 4x4 and the quad's 8x8 Hadamard sums
+  const int sh = bit_depth - 8;
+  uint32_t sad = 0, sse = 0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    sad += (uint32_t)(d[i] < 0 ? -d[i] : d[i]);
+    sse += (uint32_t)(d[i] * d[i]) >> (sh << 1);
+  }
+  uint32_t e4 = sad, e8 = 0;   // the block's PU error before the PU's shift: alone, and (lanes of a quad alike) as a quarter of its 8x8 block
+  if constexpr (HAD) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) me_wht4(d + 4 * r, 1);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) me_wht4(d + c, 4);
+    uint32_t a4 = 0, a8 = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      a4 += (uint32_t)(d[i] < 0 ? -d[i] : d[i]);
+      const int n1 = me_quad_xor1(d[i]);
+      const int t = (sub & 1) ? n1 - d[i] : d[i] + n1;
+      const int n2 = me_quad_xor2(t);
+      const int u = (sub & 2) ? n2 - t : t + n2;
+      a8 += (uint32_t)(u < 0 ? -u : u);
+    }
+    e4 = (a4 + 1) >> 1;                 // xCalcHADs4x4
+    e8 = (me_quad_sum(a8) + 2) >> 2;    // xCalcHADs8x8
+  } else {
+    e8 = me_quad_sum(sad);
+  }
+
+  uint32_t pu, cu, t_pu, t_cu;   // what the lane's block carries; what the lane adds to the CTU's two sums
+  bool store;
+  long at;
+  if (PER == 64) { store = sub == 0; at = o * 64 + q; } else { store = true; at = o * 256 + by4 * 16 + bx4; }
+  if constexpr (MAP) {
+    const int s = slot_map[at];          // with PER 64 the quad's four lanes read the same entry
+    const bool valid = s < kParts;
+    const int ci = me_cu_index(me_slot_depth(s), bx4, by4);
+    __syncthreads();                     // the tables are zero
+    if (valid) {
+      const uint32_t add = !HAD ? sad : me_slot_had8(s) ? (sub == 0 ? e8 : 0u) : e4;
+      if (add) atomicAdd(&s_pu[s], add);
+      if (sse) atomicAdd(&s_cu[ci], sse);
+    }
+    __syncthreads();
+    pu = valid ? s_pu[s] >> sh : 0u;
+    cu = valid ? s_cu[ci] : 0u;
+    t_pu = 0;
+    for (int i = tid; i < kParts; i += 256) t_pu += s_pu[i] >> sh;
+    t_cu = tid < kResidualCus ? s_cu[tid] : 0u;
+  } else {
+    pu = (PER == 64 ? e8 : e4) >> sh;
+    cu = PER == 64 ? me_quad_sum(sse) : sse;
+    t_pu = store ? pu : 0u;
+    t_cu = store ? cu : 0u;
+    __syncthreads();                     // s_tot is zero
+  }
+  if (store) {
+    if (out_pu) out_pu[at] = pu;
+    if (out_cu) out_cu[at] = cu;
+  }
+  if (out_ctu) {   // workgroup-uniform
+    t_pu = me_wave_sum(t_pu);
+    t_cu = me_wave_sum(t_cu);
+    if ((tid & 63) == 0) { atomicAdd(&s_tot[0], t_pu); atomicAdd(&s_tot[1], t_cu); }
+    __syncthreads();
+    if (tid < 2) out_ctu[o * 2 + tid] = s_tot[tid];
+  }
+}
+
 // ---- the prediction of a picture whose blocks are L0, L1 or bi (hmme_predict_bi_device) ----------------------------------------------------
 // me_predict_kernel<SrcT, 0> with a direction per block: one CTU per workgroup, a wave one 8x8 block at a time.  mv_field: int16
 // [2][n_ctu][mv_per_ctu][2] (list-major), dir_field: uint8 [n_ctu][mv_per_ctu] -- HM's interDir: 1 = list 0 (ref0), 2 = list 1 (ref1),

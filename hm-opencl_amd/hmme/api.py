@@ -35,7 +35,8 @@ SYMBOLS = ["hmme_create", "hmme_destroy", "hmme_last_error", "hmme_device_info",
            "hmme_predict_bi_weight_check", "hmme_predict_bi_w_device", "hmme_predict_bi_w_frame", "hmme_predict_refs_w_device", "hmme_predict_refs_w_frame",
            "hmme_plane_stats", "hmme_wp_estimate",
            "hmme_predict_chroma_pairs_device", "hmme_predict_chroma_frame", "hmme_predict_chroma_refs_device", "hmme_predict_chroma_refs_frame",
-           "hmme_predict_chroma_bi_device", "hmme_predict_chroma_bi_frame"]
+           "hmme_predict_chroma_bi_device", "hmme_predict_chroma_bi_frame",
+           "hmme_residual_pairs_device", "hmme_residual_frame"]
 # test / measurement entry points (include/hmme_test.h): not part of the boundary
 TEST_SYMBOLS = ["hmme_test_time_search_kernel", "hmme_test_device_address", "hmme_test_frac_deal", "hmme_test_tail_plan", "hmme_test_stage_layout", "hmme_test_picture_job", "hmme_test_time_weight_passes", "hmme_test_time_bipred_origin",
                 "hmme_test_time_wp_estimate_passes"]
@@ -208,6 +209,8 @@ def load():
     L.hmme_predict_chroma_refs_frame.argtypes = [vp, C.POINTER(vp), i, i, i, C.POINTER(FrameParams), pw, vp, vp, i, C.POINTER(vp), i]
     L.hmme_predict_chroma_bi_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, i, i, C.POINTER(FrameParams), pw, pw, vp, vp, i, C.POINTER(vp), i, vp]
     L.hmme_predict_chroma_bi_frame.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, i, C.POINTER(FrameParams), pw, pw, vp, vp, i, C.POINTER(vp), i]
+    L.hmme_residual_pairs_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, i, C.POINTER(FrameParams), vp, i, i, C.POINTER(vp), i, vp, vp, vp, vp]
+    L.hmme_residual_frame.argtypes = [vp, vp, C.POINTER(FrameParams), vp, i, vp, i, i, vp, i, vp, vp, vp]
     L.hmme_plane_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.hmme_wp_estimate.argtypes = [vp, vp, C.POINTER(vp), i, i, C.POINTER(Weight), C.POINTER(WpInfo)]
     L.hmme_test_time_wp_estimate_passes.argtypes = [vp, vp, C.POINTER(vp), i, C.POINTER(Weight), vp, i, C.POINTER(C.c_float), C.POINTER(C.c_float)]
@@ -755,6 +758,42 @@ class Engine:
         ra = _handles(refs)
         self._check(self.L.hmme_predict_refs_frame(self.h, ra, len(refs), C.byref(fp), f.ctypes.data, rf.ctypes.data, per, out.ctypes.data, out.shape[1]))
         return out
+
+    # ---- residual and distortion of a prediction (include/hmme.h, "residual and distortion of a prediction") ----
+    def residual_pairs_device(self, curs, d_preds, pred_pitch_bytes, fp, d_slot, mv_per_ctu, use_hadamard, d_resids, resid_pitch_bytes, d_pu, d_cu,
+                              d_ctu, stream=0):
+        """hmme_residual_pairs_device: for up to 16 (current plane, predicted device image) pairs the residual images (d_resids: one int16 device
+        image per pair, entries or the whole list None), the PU error and the CU SSE per block (uint32[n_pairs, n_ctu, mv_per_ctu]) and the CTU
+        sums (uint32[n_pairs, n_ctu, 2]); d_slot: the covering slots uint16[n_pairs, n_ctu, mv_per_ctu] of a select call, or None (every
+        block its own PU and CU).  Device addresses; d_pu / d_cu / d_ctu may be None"""
+        assert len(curs) == len(d_preds) and (d_resids is None or len(d_resids) == len(curs))
+        ca = _handles(curs)
+        pa = (C.c_void_p * len(d_preds))(*[int(p) for p in d_preds])
+        ra = None if d_resids is None else (C.c_void_p * len(d_resids))(*[None if r is None else int(r) for r in d_resids])
+        self._check(self.L.hmme_residual_pairs_device(self.h, ca, pa, int(pred_pitch_bytes), len(curs), C.byref(fp), d_slot, int(mv_per_ctu),
+                                                      int(use_hadamard), ra, int(resid_pitch_bytes), d_pu, d_cu, d_ctu, stream))
+
+    def residual_frame(self, cur, pred, slot=None, mv_per_ctu=64, use_hadamard=True, ctu_first=0, ctu_count=-1, resid=None, pu=None, cu=None, ctu=None):
+        """hmme_residual_frame: one picture, host arrays.  pred: [height, width] of the plane's sample type (u8 / u16); slot: uint16[n_ctu,
+        mv_per_ctu] or None -> (resid int16[height, width], pu uint32[n_ctu, mv_per_ctu], cu of that shape, ctu uint32[n_ctu, 2]); samples and
+        entries outside the CTU range keep the values of the arrays passed in (zeros when none is)"""
+        n, per = self.L.hmme_num_ctus(cur.width, cur.height), int(mv_per_ctu)
+        fp = FrameParams(1, 0, cur.bit_depth, ctu_first, ctu_count)
+        pred = np.ascontiguousarray(pred, dtype=np.uint8 if cur.bit_depth == 8 else np.uint16)
+        assert pred.shape == (cur.height, cur.width)
+        sptr = None
+        if slot is not None:
+            slot = np.ascontiguousarray(slot, dtype=np.uint16)
+            assert slot.shape == (n, per)
+            sptr = slot.ctypes.data
+        outs = []
+        for a, dt, shape in ((resid, np.int16, (cur.height, cur.width)), (pu, np.uint32, (n, per)), (cu, np.uint32, (n, per)), (ctu, np.uint32, (n, 2))):
+            a = np.zeros(shape, dt) if a is None else a
+            assert a.dtype == dt and a.shape == shape and a.flags.c_contiguous
+            outs.append(a)
+        self._check(self.L.hmme_residual_frame(self.h, cur.h, C.byref(fp), pred.ctypes.data, cur.width, sptr, per, 1 if use_hadamard else 0,
+                                               outs[0].ctypes.data, cur.width, outs[1].ctypes.data, outs[2].ctypes.data, outs[3].ctypes.data))
+        return tuple(outs)
 
     # ---- L0, L1 or bi per PU, and the prediction from it (include/hmme.h, "L0, L1 or bi per PU") ----
     def select_dirs_device(self, width, height, n_pics, fp, sel, dirs, d_mv_uni, d_cost_uni, d_mv_bi, d_cost_bi, d_uni_field, d_pred, d_field, d_dir,

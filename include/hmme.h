@@ -795,6 +795,60 @@ int hmme_predict_chroma_bi_frame(hmme_ctx* ctx, const hmme_plane* const* ref0, c
                                  const hmme_weight* wp0, const hmme_weight* wp1, const int16_t* mv_field, const uint8_t* dir_field, int mv_per_ctu, void* const* outs,
                                  int out_stride);
 
+/* ---- residual and distortion of a prediction ------------------------------------------------------------------------
+ * The first things HM does with a prediction, on the device: the residual, what the prediction costs per PU, and what coding no residual
+ * would cost per CU -- one pass over the current picture, the predicted image as any hmme_predict_*_device call wrote it, and the covering-slot
+ * map (d_out_slot) of the hmme_select_*_device calls.  New entry points only; nothing existing changed, so HMME_ABI_VERSION stays 6.
+ *
+ * Inputs.  curs[i]: planes of this context, of one size, bit depth 8..12; fp->bit_depth must be theirs, and of fp only ctu_first, ctu_count and
+ * bit_depth are consulted.  d_preds: a HOST array of n_pairs device images, samples of the planes' type (u8 for 8-bit planes, u16 otherwise),
+ * pred_pitch_bytes per row.  mv_per_ctu: 64 (blocks of 8x8) or 256 (blocks of 4x4), raster order inside the CTU.  d_slot:
+ * uint16[n_pairs][n_ctu][mv_per_ctu] as a select call wrote it -- n_ctu = ALL CTUs of the picture -- or NULL: every block is then its own PU and
+ * its own CU, which gives a per-block cost map.  The NULL form is also how a chroma plane is served; a chroma form driven by the luma slot map is
+ * out of scope.  A block whose entry is 0xFFFF (no CU covers it; any value above 592 is read that way) carries 0 in both outputs and
+ * contributes nothing.  The blocks that carry a slot are taken to be the slot's rectangle (hmme_slot_rect), as the select calls write them.
+ *
+ * Difference.  D = cur - pred at samples inside the picture, D = 0 at samples outside it.  HM never evaluates outside a picture, so this
+ * sentence is the rule for partial edge CTUs, and for CUs that straddle the edge when max_depth < 3.
+ *
+ * d_out_resid (may be NULL, as may any entry of it): a HOST array of n_pairs device images of int16, resid_pitch_bytes per row, holding D --
+ * TComYuv::subtract (TComYuv.cpp:320).  Written only inside the picture and inside the CTUs [ctu_first, ctu_first + ctu_count).
+ *
+ * d_out_pu (may be NULL): uint32[n_pairs][n_ctu][mv_per_ctu].  Every block carries the prediction error of the PU whose slot covers it:
+ * TEncSearch::xGetInterPredictionError (TEncSearch.cpp:2816-2836), what xMergeEstimation (:2876) and the AMP merge check (:3368, :3374)
+ * compare -- the distortion of original against prediction over the PU's rectangle with bApplyWeight = false:
+ *   use_hadamard 1: xGetHADs (TComRdCost.cpp:1537-1604).  A PU whose width and height are both multiples of 8 is the sum of xCalcHADs8x8 over
+ *                   its 8x8 blocks, each (sum |coefficient| + 2) >> 2; any other PU the sum of xCalcHADs4x4 over its 4x4 blocks, each
+ *                   (sum |coefficient| + 1) >> 1.  The PU's total is then >> (bitDepth - 8).
+ *   use_hadamard 0: xGetSAD over all rows; the PU's total >> (bitDepth - 8).
+ *
+ * d_out_cu (may be NULL): the same shape.  Every block carries the SSE of the CU that holds it -- the CU named by the depth and abs_z_idx of
+ * the slot's key (hmme_slot_key): TComRdCost::getDistPart with DF_SSE (TComRdCost.cpp:433), the zero-residual distortion of the skip check of
+ * encodeResAndCalcRdInterCU.  As xGetSSE (TComRdCost.cpp:970-1000) computes it: the sum of (D * D) >> ((bitDepth - 8) << 1), every sample
+ * shifted before it is added (FULL_NBIT is 0, TypeDef.h:276, so DISTORTION_PRECISION_ADJUSTMENT is its argument, :280-284).
+ *
+ * d_out_ctu (may be NULL): uint32[n_pairs][n_ctu][2].  Entry 0: the sum of the PU errors over the distinct PUs of the CTU; entry 1: the sum of
+ * the CU SSEs over its distinct CUs.  At least one of the four outputs must be given.
+ *
+ * Overflow.  Nothing saturates and nothing can wrap: at 12 bits the Hadamard total of a 64x64 PU stays below 2^32 before the shift
+ * (<= 64 * ((64 * 64 * 4095 + 2) >> 2) = 268 369 920), a SAD is at most 4096 * 4095, a CU's or a CTU's SSE at most
+ * 4096 * ((4095 * 4095) >> 8) = 268 304 384 (8 bits: 4096 * 255 * 255), and a CTU's PU errors sum to no more than the 64x64 bound.
+ *
+ * hmme_residual_pairs_device: asynchronous on `stream`, up to 16 pairs.  Limits, plane ownership and stream ordering are those of
+ * hmme_predict_pairs_device; the call uses no scratch of the context.  HMME_ERR_ARG, with nothing launched, for: a null context, plane list,
+ * plane, image list, image or fp; no output at all; n_pairs outside 1..16; mv_per_ctu other than 64 or 256; use_hadamard other than 0 or 1;
+ * planes whose bit depth is not fp->bit_depth; a plane of another context; planes of different sizes; a CTU range outside the picture;
+ * pred_pitch_bytes below a picture row, resid_pitch_bytes below 2 bytes per sample of one; a misaligned buffer -- predicted images and d_slot
+ * 4 bytes, residual images AND their pitch 8 bytes, the uint32 outputs 4 bytes.  A predicted image whose pitch is not a multiple of 4 is
+ * served, sample by sample.
+ * hmme_residual_frame: synchronous, one picture, host arrays of the same shapes with n_pairs = 1 (pred_stride and resid_stride in samples, at
+ * least the picture width), on the context's private stream; entries and samples outside the CTU range keep their values. */
+int hmme_residual_pairs_device(hmme_ctx* ctx, const hmme_plane* const* curs, const void* const* d_preds, int pred_pitch_bytes, int n_pairs,
+                               const hmme_frame_params* fp, const void* d_slot, int mv_per_ctu, int use_hadamard, void* const* d_out_resid,
+                               int resid_pitch_bytes, void* d_out_pu, void* d_out_cu, void* d_out_ctu, void* stream);
+int hmme_residual_frame(hmme_ctx* ctx, const hmme_plane* cur, const hmme_frame_params* fp, const void* pred, int pred_stride, const uint16_t* slot,
+                        int mv_per_ctu, int use_hadamard, int16_t* out_resid, int resid_stride, uint32_t* out_pu, uint32_t* out_cu, uint32_t* out_ctu);
+
 /* ---- estimating explicit weighted-prediction parameters --------------------------------------------------------
  * Where the weights of the *_w calls come from when the caller has none: the luma part of HM's estimator, WeightPredAnalysis::
  * xCalcACDCParamSlice, xEstimateWPParamSlice, xUpdatingWPParameters, xSelectWP and xCalcSADvalueWP (source/Lib/TLibEncoder/
