@@ -215,6 +215,8 @@ int hmme_refine_ctu(hmme_ctx* ctx, const int16_t* ctu, int ctu_stride, const int
 /* device-resident luma plane with edge-replicated margins; 8-bit planes store bytes, 9..12-bit planes u16.  Every plane also holds its picture
  * area once more CTU by CTU (64 x 64 blocks, contiguous: what a search reads the CURRENT picture from), so a plane costs about
  * (W + 256) x (H + 160) + W x H samples of device memory -- 17.9 MB for an 8-bit 2160p picture.
+ * Any width and any height from 8 to 16384 is served by every call (odd ones too: no size has to be a multiple of anything; only the 4:2:0
+ * chroma calls ask for an even luma size); outside that range hmme_plane_create* returns HMME_ERR_ARG.
  * A plane belongs to the context that created it: every frame call refuses planes of another context (HMME_ERR_ARG), and a
  * context's planes are destroyed BEFORE the context (hmme_plane_destroy reads its context). */
 int hmme_plane_create(hmme_ctx* ctx, int width, int height, hmme_plane** out);   /* 8-bit */
