@@ -3145,6 +3145,10 @@ namespace {
 constexpr int kWpStatPlanes = hmme::kMaxRefs + 1;
 constexpr int kWpStatSad = 2 * kWpStatPlanes;
 constexpr int kWpStatWords = kWpStatSad + 2 * hmme::kMaxRefs;
+// hmme_wp_estimate_420 lays the same scratch out for its plane set: two sums per plane, then two per (reference, component)
+constexpr int kWpSetSad = 2 * hmme::kMaxSetPlanes;
+constexpr int kWpSetWords = kWpSetSad + 2 * hmme::kMaxSetPairs;
+static_assert(kWpSetWords >= kWpStatWords, "one allocation serves both layouts");
 constexpr int kWpStatBlocks = 1024;   // workgroups of one launch at most: each ends in one atomic add per sum
 
 // lanes per row (log2) and workgroups of a reduction over the picture area of `pl`, n_y of them side by side (me_kernels.hpp: the geometry
@@ -3186,11 +3190,46 @@ int launch_wp_sad(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const*
   return HMME_OK;
 }
 
+// the plane-set forms (me_kernels.hpp): one table entry per plane, the grid's x extent that of the plane that needs most workgroups
+hmme::MePlaneDesc plane_desc(const hmme_plane* pl, int n_y, unsigned* blocks) {
+  const StatGrid g = stat_grid(pl, n_y);
+  *blocks = std::max(*blocks, g.blocks);
+  return {pl->origin(), pl->pitch, pl->width, pl->height, g.lpr_log2};
+}
+// the two passes of xCalcACDCParamSlice over n (1..kMaxSetPlanes) planes of one sample type in two launches: sums[2 i], sums[2 i + 1] (zero on entry)
+int launch_stats_set(hmme_ctx* ctx, const hmme_plane* const* pl, int n, unsigned long long* sums, hipStream_t s) {
+  hmme::MePlaneSet set = {};
+  unsigned blocks = 1;
+  for (int i = 0; i < n; ++i) set.p[i] = plane_desc(pl[i], n, &blocks);
+  const dim3 grid(blocks, (unsigned)n);
+  if (pl[0]->bps == 1) {
+    hipLaunchKernelGGL((hmme::me_plane_set_stats_kernel<uint8_t, 0>), grid, dim3(256), 0, s, set, sums);
+    hipLaunchKernelGGL((hmme::me_plane_set_stats_kernel<uint8_t, 1>), grid, dim3(256), 0, s, set, sums);
+  } else {
+    hipLaunchKernelGGL((hmme::me_plane_set_stats_kernel<uint16_t, 0>), grid, dim3(256), 0, s, set, sums);
+    hipLaunchKernelGGL((hmme::me_plane_set_stats_kernel<uint16_t, 1>), grid, dim3(256), 0, s, set, sums);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  return HMME_OK;
+}
+// xCalcSADvalueWP of the three components of `cur` against those of n_refs references in one launch: pair 3 r + c = refs[3 r + c] against
+// cur[c], a.weight / offset / log2_denom filled in by the caller; two sums per pair (zero on entry)
+int launch_wp_sad_set(hmme_ctx* ctx, const hmme_plane* const* cur, const hmme_plane* const* refs, int n_refs, hmme::MeWpSadSet& a, unsigned long long* sums, hipStream_t s) {
+  unsigned blocks = 1;
+  for (int c = 0; c < 3; ++c) a.cur[c] = plane_desc(cur[c], 3 * n_refs, &blocks);
+  for (int i = 0; i < 3 * n_refs; ++i) a.ref[i] = refs[i]->origin();
+  const dim3 grid(blocks, (unsigned)(3 * n_refs));
+  if (cur[0]->bps == 1) hipLaunchKernelGGL(hmme::me_wp_sad_set_kernel<uint8_t>, grid, dim3(256), 0, s, a, sums);
+  else hipLaunchKernelGGL(hmme::me_wp_sad_set_kernel<uint16_t>, grid, dim3(256), 0, s, a, sums);
+  HIP_TRY(ctx, hipGetLastError());
+  return HMME_OK;
+}
+
 // kernels on `s` read planes[0 .. n): what pairs_begin / pairs_end do for the planes of picture pairs -- the scratch (kWpEst) and the last fill of
 // every plane before, one event of the context's ring behind, so that a refill of any of them on another stream waits
 int planes_read_begin(hmme_ctx* ctx, const hmme_plane* const* planes, int n, hipStream_t s) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int rc = ensure(ctx, ctx->buf[kWpEst], sizeof(unsigned long long) * kWpStatWords);
+  int rc = ensure(ctx, ctx->buf[kWpEst], sizeof(unsigned long long) * kWpSetWords);
   if (rc == HMME_OK) rc = scratch_acquire(ctx, s);
   for (int i = 0; i < n && rc == HMME_OK; ++i) rc = plane_wait(ctx, planes[i], s);
   return rc;
@@ -3206,9 +3245,10 @@ int planes_read_end(hmme_ctx* ctx, const hmme_plane* const* planes, int n, hipSt
   return rc ? rc : r3;
 }
 
-// the sums of every plane of the list that has none cached: all their passes enqueued, one download, one wait
-int collect_stats(hmme_ctx* ctx, const hmme_plane* const* planes, int n, hipStream_t s) {
-  const hmme_plane* todo[kWpStatPlanes];
+// the sums of every plane of the list that has none cached: all their passes enqueued, one download, one wait.  as_set: the planes (of one
+// sample type, up to kMaxSetPlanes) go through the plane-set kernels, two launches for all of them; otherwise two launches per plane
+int collect_stats(hmme_ctx* ctx, const hmme_plane* const* planes, int n, hipStream_t s, bool as_set = false) {
+  const hmme_plane* todo[hmme::kMaxSetPlanes];
   int n_todo = 0;
   for (int i = 0; i < n; ++i) {
     if (planes[i]->stats_valid) continue;
@@ -3219,10 +3259,14 @@ int collect_stats(hmme_ctx* ctx, const hmme_plane* const* planes, int n, hipStre
   if (n_todo == 0) return HMME_OK;
   int rc = planes_read_begin(ctx, todo, n_todo, s);
   if (rc) return rc;
-  unsigned long long h[2 * kWpStatPlanes];
+  unsigned long long h[2 * hmme::kMaxSetPlanes];
   hipError_t e = hipMemsetAsync(ctx->buf[kWpEst].as<unsigned long long>(), 0, sizeof(unsigned long long) * 2 * n_todo, s);
   if (e != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "plane statistics: %s", hipGetErrorString(e));
-  for (int j = 0; j < n_todo && rc == HMME_OK; ++j) rc = launch_stats(ctx, todo[j], ctx->buf[kWpEst].as<unsigned long long>() + 2 * j, s);
+  if (as_set) {
+    if (rc == HMME_OK) rc = launch_stats_set(ctx, todo, n_todo, ctx->buf[kWpEst].as<unsigned long long>(), s);
+  } else {
+    for (int j = 0; j < n_todo && rc == HMME_OK; ++j) rc = launch_stats(ctx, todo[j], ctx->buf[kWpEst].as<unsigned long long>() + 2 * j, s);
+  }
   if (rc == HMME_OK && (e = hipMemcpyAsync(h, ctx->buf[kWpEst].as<unsigned long long>(), sizeof(unsigned long long) * 2 * n_todo, hipMemcpyDeviceToHost, s)) != hipSuccess)
     rc = fail(ctx, HMME_ERR_DEVICE, "plane statistics: %s", hipGetErrorString(e));
   rc = planes_read_end(ctx, todo, n_todo, s, rc);
@@ -3338,6 +3382,114 @@ int hmme_wp_estimate(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* con
       o.present = present;
       o.served_search = hmme_weight_check(bd, &wp, 0) == HMME_OK ? 1 : 0;
       o.served_refine = hmme_weight_check(bd, &wp, 1) == HMME_OK ? 1 : 0;
+    }
+  }
+  return HMME_OK;
+}
+
+// xEstimateWPParamSlice for a 4:2:0 slice: the same steps joint over Y, Cb, Cr (the rule: include/hmme.h).  planes[c] = cur[c],
+// planes[3 (1 + r) + c] = refs[3 r + c]; the sums of all of them through the plane-set kernels.
+int hmme_wp_estimate_420(hmme_ctx* ctx, const hmme_plane* const* cur, const hmme_plane* const* refs, int n_refs, int log2_denom_start,
+                         hmme_weight* out_wp_luma, hmme_weight* out_wp_chroma, hmme_wp_info* out_info) {
+  static const char* const who = "hmme_wp_estimate_420";
+  if (!ctx) return HMME_ERR_ARG;
+  if (!cur || !refs || !out_wp_luma || !out_wp_chroma) return fail(ctx, HMME_ERR_ARG, "%s: null argument", who);
+  if (n_refs < 1 || n_refs > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d references outside 1..%d", who, n_refs, hmme::kMaxRefs);
+  if (log2_denom_start < 3 || log2_denom_start > 7) return fail(ctx, HMME_ERR_ARG, "%s: log2_denom_start %d outside 3..7", who, log2_denom_start);
+  const int n_planes = 3 * (1 + n_refs);
+  const hmme_plane* planes[hmme::kMaxSetPlanes];
+  for (int i = 0; i < n_planes; ++i) {
+    planes[i] = i < 3 ? cur[i] : refs[i - 3];
+    if (!planes[i]) return fail(ctx, HMME_ERR_ARG, "%s: null plane", who);
+    if (planes[i]->ctx != ctx) return fail(ctx, HMME_ERR_ARG, "%s: plane belongs to another context", who);
+  }
+  const int w = cur[0]->width, h = cur[0]->height, bd = cur[0]->bit_depth;
+  for (int i = 0; i < n_planes; i += 3) {   // Y, Cb, Cr of one picture: chroma_size is what the hmme_predict_chroma_* calls ask of their planes
+    if (planes[i]->width != w || planes[i]->height != h)
+      return fail(ctx, HMME_ERR_ARG, "%s: reference %d is %d x %d, the current picture %d x %d", who, i / 3 - 1, planes[i]->width, planes[i]->height, w, h);
+    const int rc = chroma_size(ctx, who, planes + i + 1, 2, w, h);
+    if (rc) return rc;
+  }
+  for (int i = 0; i < n_planes; ++i)
+    if (planes[i]->bit_depth != bd) return fail(ctx, HMME_ERR_ARG, "%s: planes of %d and %d bits in one call", who, bd, planes[i]->bit_depth);
+  hipStream_t s = ctx->stream;
+  int rc = collect_stats(ctx, planes, n_planes, s, true);   // xCalcACDCParamSlice of every plane that has not been through it since its last fill
+  if (rc) return rc;
+
+  // xUpdatingWPParameters (:200-268) from log2_denom_start downwards: reference outer, component inner, the first weight out of range ends a pass
+  const int64_t n_samples[3] = {(int64_t)w * h, (int64_t)(w / 2) * (h / 2), (int64_t)(w / 2) * (h / 2)};
+  auto norm_dc = [&](const hmme_plane* p, int c) { return (p->stats_dc + (n_samples[c] >> 1)) / n_samples[c]; };   // :115 without the RExt precision shift
+  int d = log2_denom_start, weight[hmme::kMaxSetPairs], offset[hmme::kMaxSetPairs];
+  for (;; --d) {   // ends at d = 3 at the latest, as in hmme_wp_estimate
+    const int real_d = d + (bd - 8);
+    bool in_range = true;
+    for (int i = 0; i < 3 * n_refs && in_range; ++i) {
+      const int c = i % 3;
+      const int64_t cur_dc = norm_dc(cur[c], c), cur_ac = cur[c]->stats_ac, ref_dc = norm_dc(refs[i], c), ref_ac = refs[i]->stats_ac;
+      const double dw = ref_ac == 0 ? 1.0 : std::min(std::max(-16.0, (double)cur_ac / (double)ref_ac), 15.0);        // :234
+      const int wgt = (int)(0.5 + dw * (double)(1 << d));                                                             // :235
+      const int off = (int)(((cur_dc << d) - (int64_t)wgt * ref_dc + ((int64_t)1 << (real_d - 1))) >> real_d);        // :236
+      weight[i] = wgt;
+      if (c) {                                                                                                         // :239-245, range = 128
+        const int pred = 128 - ((128 * wgt) >> d);
+        const int delta_off = std::min(std::max(-512, off - pred), 511);
+        offset[i] = std::min(std::max(-128, delta_off + pred), 127);
+      } else {
+        offset[i] = std::min(std::max(-128, off), 127);                                                                // :248
+      }
+      const int delta = (1 << d) - wgt;                                                                                // :252-258
+      in_range = !(delta >= 128 || delta < -128);
+    }
+    if (in_range) break;
+  }
+
+  // xSelectWP (:272-320): both of xCalcSADvalueWP's sums of every (reference, component) in one launch
+  hmme::MeWpSadSet a = {};
+  for (int i = 0; i < 3 * n_refs; ++i) {
+    a.weight[i] = weight[i];
+    a.offset[i] = offset[i] * (1 << (d + bd - 8));   // iOffset << iRealLog2Denom (:344)
+    a.log2_denom[i] = d;
+  }
+  rc = planes_read_begin(ctx, planes, n_planes, s);
+  if (rc) return rc;
+  unsigned long long hs[2 * hmme::kMaxSetPairs];
+  unsigned long long* d_sums = ctx->buf[kWpEst].as<unsigned long long>() + kWpSetSad;
+  hipError_t e = hipMemsetAsync(d_sums, 0, sizeof(unsigned long long) * 6 * n_refs, s);
+  if (e != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
+  if (rc == HMME_OK) rc = launch_wp_sad_set(ctx, cur, refs, n_refs, a, d_sums, s);
+  if (rc == HMME_OK && (e = hipMemcpyAsync(hs, d_sums, sizeof(unsigned long long) * 6 * n_refs, hipMemcpyDeviceToHost, s)) != hipSuccess)
+    rc = fail(ctx, HMME_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
+  rc = planes_read_end(ctx, planes, n_planes, s, rc);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+
+  for (int r = 0; r < n_refs; ++r) {
+    int64_t sad_wp[3], sad_nowp[3], sum_wp = 0, sum_nowp = 0;   // every component divided by its own size (:350) before they are added (:301-302)
+    for (int c = 0; c < 3; ++c) {
+      sad_wp[c] = (int64_t)hs[2 * (3 * r + c)] / n_samples[c];
+      sad_nowp[c] = (int64_t)(hs[2 * (3 * r + c) + 1] << d) / n_samples[c];
+      sum_wp += sad_wp[c]; sum_nowp += sad_nowp[c];
+    }
+    const double ratio = (double)sum_wp / (double)sum_nowp;   // :305 -- NaN keeps the weights present, +inf disables them, as in hmme_wp_estimate
+    const int present = ratio >= 0.99 ? 0 : 1;               // DTHRESH (:46); :306-314: all three components together
+    for (int c = 0; c < 3; ++c) {
+      const int i = 3 * r + c;
+      if (!present) { weight[i] = 1 << d; offset[i] = 0; }
+      const hmme_weight wp = {weight[i], offset[i] * (1 << (bd - 8)), d, d ? 1 << (d - 1) : 0};   // TComSlice::initWpScaling (TComSlice.cpp:1487-1512)
+      if (c == 0) out_wp_luma[r] = wp; else out_wp_chroma[2 * r + c - 1] = wp;
+      if (!out_info) continue;
+      hmme_wp_info& o = out_info[i];
+      o.cur_dc_sum = cur[c]->stats_dc; o.cur_ac = cur[c]->stats_ac; o.ref_dc_sum = refs[i]->stats_dc; o.ref_ac = refs[i]->stats_ac;
+      o.sad_wp = sad_wp[c]; o.sad_nowp = sad_nowp[c];
+      o.log2_denom = d; o.weight = weight[i]; o.offset = offset[i];
+      o.present = present;
+      if (c == 0) {
+        o.served_search = hmme_weight_check(bd, &wp, 0) == HMME_OK ? 1 : 0;
+        o.served_refine = hmme_weight_check(bd, &wp, 1) == HMME_OK ? 1 : 0;
+      } else {   // what predict_args / frame_checks ask of a component's weight in the hmme_predict_chroma_* calls
+        char msg[256];
+        o.served_search = o.served_refine = other_weight_eval(bd, &wp, nullptr, nullptr, msg, sizeof msg) == HMME_OK ? 1 : 0;
+      }
     }
   }
   return HMME_OK;

@@ -3164,4 +3164,124 @@ me_wp_sad_kernel(const uint8_t* __restrict__ cur, RefSet refs, int pitch, int w,
   me_block_sum_u64<2>(acc, sums + 2 * r);
 }
 
+// ---- the plane-set forms (hmme_wp_estimate_420) ---------------------------------------------------------------------------------------------
+// The two reductions above over SEVERAL planes of different sizes in one launch: blockIdx.y names a plane (statistics) or a pair of planes
+// (SAD) of a table passed by value, like RefSet.  A 4:2:0 call with 16 references has 51 planes and 48 pairs; one launch each replaces 51 and
+// 3.  Geometry and arithmetic are those of the single-plane kernels -- 16-byte vector loads from the aligned picture edge, the last vector of
+// a row masked to the row's bytes, packed SADs, a 32-bit partial per vector into 64-bit lane sums, me_block_sum_u64 -- but every plane brings
+// its own lpr_log2, so rows per workgroup differ between the planes of a launch.  gridDim.x is sized for the plane that needs most
+// workgroups; a workgroup whose first row lies beyond its (smaller) plane has nothing to add and LEAVES AS A WHOLE, before any barrier:
+// the test is on blockIdx and the plane's table entry only, the same for all 256 lanes.  The sums are zero on entry, so a sum nobody adds to
+// is the right one.
+constexpr int kMaxSetPlanes = 3 * (kMaxRefs + 1);   // Y, Cb, Cr of the current picture and of kMaxRefs references
+constexpr int kMaxSetPairs = 3 * kMaxRefs;
+struct MePlaneDesc { const uint8_t* origin; int pitch, w, h, lpr_log2; };
+struct MePlaneSet { MePlaneDesc p[kMaxSetPlanes]; };
+
+// sums[2 p] / sums[2 p + 1] = sample sum / AC of plane p, as me_plane_stats_kernel leaves them for one plane: PASS 1 reads its own plane's
+// PASS 0 sum.  All planes of a launch hold samples of type T (one bit depth per call).  A vector's partial is at most 16 * 255 / 8 * 4095.
+template <typename T, int PASS>
+__global__ void __launch_bounds__(256)
+me_plane_set_stats_kernel(MePlaneSet set, unsigned long long* sums) {
+  __shared__ uint32_t s_mean;
+  const MePlaneDesc pd = set.p[blockIdx.y];
+  const int lpr = 1 << pd.lpr_log2, lx = threadIdx.x & (lpr - 1), ry = threadIdx.x >> pd.lpr_log2, rpb = 256 >> pd.lpr_log2;
+  if ((int)blockIdx.x * rpb >= pd.h) return;   // the whole workgroup: no lane has a row
+  sums += 2 * blockIdx.y;
+  uint32_t mean = 0;   // the mean in every sample of a dword
+  if (PASS == 1) {
+    if (threadIdx.x == 0) {
+      const unsigned long long n = (unsigned long long)pd.w * (unsigned long long)pd.h;
+      s_mean = (uint32_t)((sums[0] + (n >> 1)) / n);
+    }
+    __syncthreads();
+    mean = s_mean * (sizeof(T) == 1 ? 0x01010101u : 0x00010001u);
+  }
+  const int row_bytes = pd.w * (int)sizeof(T), nvec = (row_bytes + 15) >> 4;
+  uint64_t acc[1] = {0};
+  for (int y = blockIdx.x * rpb + ry; y < pd.h; y += gridDim.x * rpb) {
+    const uint8_t* row = pd.origin + (long)y * pd.pitch;
+    for (int v = lx; v < nvec; v += lpr) {
+      const uint4 in = *(const uint4*)(row + 16 * v);
+      const uint32_t d[4] = {in.x, in.y, in.z, in.w};
+      const int nb = row_bytes - 16 * v;
+      uint32_t part = 0;
+      if (nb >= 16) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) part = me_sad_packed<T>(d[k], mean, part);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const uint32_t m = me_tail_mask(nb, k);
+          part = me_sad_packed<T>(d[k] & m, mean & m, part);
+        }
+      }
+      acc[0] += part;
+    }
+  }
+  me_block_sum_u64<1>(acc, sums + PASS);
+}
+
+// xCalcSADvalueWP for up to kMaxSetPairs pairs (current plane, reference plane) in one launch: pair y = 3 * reference + component reads
+// component y % 3 of the current picture (its size, pitch and lpr_log2 are the pair's: a reference plane has its component's size and so
+// its pitch) with the pair's own (weight, offset term, log2Denom).  sums[2 y] / sums[2 y + 1] as me_wp_sad_kernel's.  Its bounds hold for
+// chroma unchanged: hmme_wp_estimate_420 hands over weight in [0, 1920] (dWeight clipped to 15, d <= 7) and a chroma offset that ends in
+// Clip3(-128, 127) like luma's (WeightPredAnalysis.cpp:244), so |offset term| <= 128 << 11 = 2^18, a sample's term is below 2^23 and a
+// vector's partial below 2^26.
+struct MeWpSadSet {
+  MePlaneDesc cur[3];
+  const uint8_t* ref[kMaxSetPairs];
+  int weight[kMaxSetPairs], offset[kMaxSetPairs], log2_denom[kMaxSetPairs];
+};
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+me_wp_sad_set_kernel(MeWpSadSet a, unsigned long long* sums) {
+  constexpr int PER = 4 / (int)sizeof(T);   // samples per dword
+  const int pair = blockIdx.y;
+  const MePlaneDesc pd = a.cur[pair % 3];
+  const int lpr = 1 << pd.lpr_log2, lx = threadIdx.x & (lpr - 1), ry = threadIdx.x >> pd.lpr_log2, rpb = 256 >> pd.lpr_log2;
+  if ((int)blockIdx.x * rpb >= pd.h) return;   // the whole workgroup: no lane has a row
+  const uint8_t* __restrict__ cur = pd.origin;
+  const uint8_t* __restrict__ ref = a.ref[pair];
+  const int wt = a.weight[pair], off = a.offset[pair], d = a.log2_denom[pair];
+  const int row_bytes = pd.w * (int)sizeof(T), nvec = (row_bytes + 15) >> 4;
+  uint64_t acc[2] = {0, 0};
+  auto sample = [](uint32_t dw, int j) -> int { return sizeof(T) == 1 ? (int)((dw >> (8 * j)) & 0xffu) : (int)((dw >> (16 * j)) & 0xffffu); };
+  for (int y = blockIdx.x * rpb + ry; y < pd.h; y += gridDim.x * rpb) {
+    const long row = (long)y * pd.pitch;
+    for (int v = lx; v < nvec; v += lpr) {
+      const uint4 o4 = *(const uint4*)(cur + row + 16 * v), r4 = *(const uint4*)(ref + row + 16 * v);
+      const uint32_t o[4] = {o4.x, o4.y, o4.z, o4.w}, q[4] = {r4.x, r4.y, r4.z, r4.w};
+      const int nb = row_bytes - 16 * v;
+      uint32_t pw = 0, pn = 0;
+      if (nb >= 16) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          pn = me_sad_packed<T>(o[k], q[k], pn);
+#pragma unroll
+          for (int j = 0; j < PER; ++j) {
+            const int t = (sample(o[k], j) << d) - (sample(q[k], j) * wt + off);
+            pw += (uint32_t)(t < 0 ? -t : t);
+          }
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const uint32_t m = me_tail_mask(nb, k);
+          pn = me_sad_packed<T>(o[k] & m, q[k] & m, pn);
+#pragma unroll
+          for (int j = 0; j < PER; ++j) {
+            const int t = (sample(o[k], j) << d) - (sample(q[k], j) * wt + off);
+            if ((4 * k + j * (int)sizeof(T)) < nb) pw += (uint32_t)(t < 0 ? -t : t);
+          }
+        }
+      }
+      acc[0] += pw;
+      acc[1] += pn;
+    }
+  }
+  me_block_sum_u64<2>(acc, sums + 2 * pair);
+}
+
 }  // namespace hmme

@@ -33,7 +33,7 @@ SYMBOLS = ["hmme_create", "hmme_destroy", "hmme_last_error", "hmme_device_info",
            "hmme_predict_refs_device", "hmme_predict_refs_frame",
            "hmme_select_dirs_check", "hmme_select_dirs_device", "hmme_select_dirs_frame", "hmme_predict_bi_device", "hmme_predict_bi_frame",
            "hmme_predict_bi_weight_check", "hmme_predict_bi_w_device", "hmme_predict_bi_w_frame", "hmme_predict_refs_w_device", "hmme_predict_refs_w_frame",
-           "hmme_plane_stats", "hmme_wp_estimate",
+           "hmme_plane_stats", "hmme_wp_estimate", "hmme_wp_estimate_420",
            "hmme_predict_chroma_pairs_device", "hmme_predict_chroma_frame", "hmme_predict_chroma_refs_device", "hmme_predict_chroma_refs_frame",
            "hmme_predict_chroma_bi_device", "hmme_predict_chroma_bi_frame",
            "hmme_residual_pairs_device", "hmme_residual_frame"]
@@ -213,6 +213,7 @@ def load():
     L.hmme_residual_frame.argtypes = [vp, vp, C.POINTER(FrameParams), vp, i, vp, i, i, vp, i, vp, vp, vp]
     L.hmme_plane_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.hmme_wp_estimate.argtypes = [vp, vp, C.POINTER(vp), i, i, C.POINTER(Weight), C.POINTER(WpInfo)]
+    L.hmme_wp_estimate_420.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, i, C.POINTER(Weight), C.POINTER(Weight), C.POINTER(WpInfo)]
     L.hmme_test_time_wp_estimate_passes.argtypes = [vp, vp, C.POINTER(vp), i, C.POINTER(Weight), vp, i, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.hmme_upload_status.argtypes = [vp, vp]
     L.hmme_test_device_address.argtypes = [vp, vp]
@@ -977,6 +978,17 @@ class Engine:
         wa, ia = (Weight * max(n, 1))(), (WpInfo * max(n, 1))()
         self._check(self.L.hmme_wp_estimate(self.h, cur.h, ra, n, int(log2_denom_start), wa, ia))
         return [(w.w0, w.offset, w.shift, w.round) for w in wa[:n]], list(ia[:n])
+
+    def wp_estimate_420(self, cur3, refs3, log2_denom_start=6):
+        """hmme_wp_estimate_420: HM's weighted-prediction estimate for a 4:2:0 slice, joint over the components; cur3 = (y, cb, cr) planes of the
+        current picture, refs3 = one such triple per reference -> (luma_weights, chroma_weights, infos): one (w0, offset, shift, round) per
+        reference, one (cb, cr) pair of them per reference -- flattened, what predict_chroma_* take as `weights` --, and 3 WpInfo per reference"""
+        n = len(refs3)
+        ca, ra = _handles(cur3), _handles([p for ref in refs3 for p in ref])
+        wl, wc, ia = (Weight * max(n, 1))(), (Weight * max(2 * n, 1))(), (WpInfo * max(3 * n, 1))()
+        self._check(self.L.hmme_wp_estimate_420(self.h, ca, ra, n, int(log2_denom_start), wl, wc, ia))
+        unpack = lambda ws: [(w.w0, w.offset, w.shift, w.round) for w in ws]
+        return unpack(wl[:n]), unpack(wc[:2 * n]), list(ia[:3 * n])
 
     def time_wp_estimate_passes(self, cur, refs, wp, stream=0, reps=5):
         """device time in ms of the estimator's passes on their own -> (the two statistics launches over `cur`, the SAD pass against `refs`)"""

@@ -854,7 +854,8 @@ int hmme_residual_frame(hmme_ctx* ctx, const hmme_plane* cur, const hmme_frame_p
 /* ---- estimating explicit weighted-prediction parameters --------------------------------------------------------
  * Where the weights of the *_w calls come from when the caller has none: the luma part of HM's estimator, WeightPredAnalysis::
  * xCalcACDCParamSlice, xEstimateWPParamSlice, xUpdatingWPParameters, xSelectWP and xCalcSADvalueWP (source/Lib/TLibEncoder/
- * WeightPredAnalysis.cpp:67-120, :172-351), bit-identical to what HM computes for a 4:0:0 slice without high-precision weighting.  The
+ * WeightPredAnalysis.cpp:67-120, :172-351), bit-identical to what HM computes for a 4:0:0 slice without high-precision weighting (for a
+ * 4:2:0 slice, where HM decides jointly over Y, Cb and Cr and the luma weights differ too: hmme_wp_estimate_420 below).  The
  * whole-picture sums run on the device over the picture area of the planes (margins are never counted); the scalar steps run on the host in
  * HM's own double / Int64 arithmetic.  New entry points and one new struct; nothing existing changed, so HMME_ABI_VERSION stays 6.
  *
@@ -896,6 +897,44 @@ typedef struct hmme_wp_info {
 } hmme_wp_info;
 int hmme_wp_estimate(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, int log2_denom_start, hmme_weight* out_wp,
                      hmme_wp_info* out_info);
+
+/* hmme_wp_estimate_420: xEstimateWPParamSlice for a 4:2:0 slice, bit-identical to HM without high-precision weighting and with one bit depth
+ * bd for all planes.  HM's estimator is joint over the three components, so neither the chroma NOR THE LUMA weights of a 4:2:0 slice are
+ * what hmme_wp_estimate gives for the luma planes alone: one chroma weight out of range lowers the denominator luma uses, and the
+ * present / not present decision is taken on the three components' SADs together.  cur = Y, Cb, Cr of the current picture; refs = Y, Cb, Cr
+ * of reference r at 3 r .. 3 r + 2; Cb and Cr are (W / 2) x (H / 2) for a W x H luma.  One new entry point, no new or changed struct:
+ * HMME_ABI_VERSION stays 6.
+ *   Statistics per component: those of hmme_plane_stats (:67-120) with N_c the component's own sample count; DC = (dc_sum + (N_c >> 1)) / N_c.
+ *   1. d = log2_denom_start (3..7), as above.
+ *   2. (:218-264) For every reference and, inside, every component (HM's order): dWeight, weight and the raw offset as in step 2 of
+ *      hmme_wp_estimate from that component's AC / DC.  Luma: offset clipped to [-128, 127] (:248).  Chroma (:241-244):
+ *        pred    = 128 - ((128 * weight) >> d)
+ *        delta   = Clip3(-512, 511, offset - pred)
+ *        clipped = Clip3(-128, 127, delta + pred)
+ *      If (1 << d) - weight lies outside [-128, 128) for ANY component of ANY reference (:255), d is decremented and step 2 starts again:
+ *      all 3 * n_refs entries share d.
+ *   3. (xSelectWP, :287-315) Per reference, with N_c and (weight_c, offset_c) the component's:
+ *        sad_wp   = sum over c of ((sum of |(org << d) - (ref * weight_c + (offset_c << (d + bd - 8)))|) / N_c)
+ *        sad_nowp = sum over c of ((sum of |(org << d) - (ref << d)|) / N_c)
+ *      -- every component is divided by its own N_c before the three are added, as xCalcSADvalueWP returns them (:350, :301-302).
+ *      ratio = (double)sad_wp / (double)sad_nowp >= 0.99: ALL THREE components of the reference get weight 1 << d, offset 0, not present
+ *      (:306-314); otherwise all three stay.  NaN (0 / 0) keeps them present and +inf disables them, as above, now on the summed values.
+ *   4. Every component goes through TComSlice::initWpScaling (TComSlice.cpp:1487-1512): w0 = weight, offset << (bd - 8), shift = d,
+ *      round = d ? 1 << (d - 1) : 0.  out_wp_luma[r] is what the *_w search / refinement / prediction calls take; out_wp_chroma[2 r],
+ *      [2 r + 1] = Cb, Cr of reference r, the layout hmme_predict_chroma_pairs_device, _refs_device and _bi_device take.
+ * out_info (may be NULL; 3 * n_refs entries): entry 3 r + c carries component c's own sums and parameters: sad_wp / sad_nowp are that
+ * component's quotient (the ratio is formed on their sums over c), present is the joint decision.  served_search / served_refine of a luma
+ * entry are those of hmme_wp_estimate; of a chroma entry both are 1 exactly when the hmme_predict_chroma_* calls accept that weight for a
+ * component.
+ * HMME_ERR_ARG (nothing launched, nothing written to the outputs): a null argument other than out_info, n_refs outside 1..16,
+ * log2_denom_start outside 3..7, a plane of another context, a luma size that is odd or below 16 x 16, a chroma plane that is not
+ * (W / 2) x (H / 2), any plane whose bit depth differs from cur[0]'s, a reference luma plane of another size.
+ * Ordering and caching as hmme_wp_estimate: the context's private stream, planes read after their fills and recorded for refills; the
+ * per-plane sums are the ones hmme_plane_stats keeps in the planes (every fill drops them), so a picture that was a reference of the previous
+ * call costs nothing the second time.  On the device the planes without cached sums go through two launches together and all
+ * (reference, component) pairs through one (me_kernels.hpp, "the plane-set forms"). */
+int hmme_wp_estimate_420(hmme_ctx* ctx, const hmme_plane* const* cur, const hmme_plane* const* refs, int n_refs, int log2_denom_start,
+                         hmme_weight* out_wp_luma, hmme_weight* out_wp_chroma, hmme_wp_info* out_info);
 
 /* ---- environment (diagnostics and A/B measurements; none of these changes a result) ---------
  *   HMME_TRACE=1          one stderr line per context about launch geometry the library derives at run time (with HMME_FRAC_GRID=-1:
