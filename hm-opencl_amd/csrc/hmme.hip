@@ -1504,6 +1504,19 @@ int pairs_end(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* co
     }
   return rc ? rc : r3;
 }
+// pairs_end for a launch whose planes do not come in pairs (the *_bi_refs calls: two plane lists of their own lengths): every plane read
+// like a reference, one event for all
+int lists_end(hmme_ctx* ctx, const hmme_plane* const* a, int na, const hmme_plane* const* b, int nb, hipStream_t s, int rc) {
+  const auto at = [&](int r) { return r < na ? a[r] : b[r - na]; };
+  for (int r = 0; r < na + nb; ++r) {
+    const int r2 = plane_read_chain(ctx, at(r), s);
+    if (rc == HMME_OK) rc = r2;
+  }
+  const int r3 = launch_end(ctx, s);
+  if (r3 == HMME_OK)
+    for (int r = 0; r < na + nb; ++r) plane_read_mark(ctx, at(r), s);
+  return rc ? rc : r3;
+}
 }  // namespace
 
 int hmme_search_pairs_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, int n_pairs,
@@ -2125,7 +2138,7 @@ void with_sample_type(int bps, F&& f) {
 // me_predict_kernel for CTUs [first, first + count) of `src` with its motion field (int16 [n_ctu][mv_per_ctu][2], device)
 // pw: the weight of a slice with explicit weighted prediction (null: none, and the identity -- WP = 0 computes the same samples)
 // pr: a reference picture per block (hmme_predict_refs_device; `src` gives the geometry all planes share), prw: with one weight per
-// reference (hmme_predict_refs_w_device; null: none)
+// reference (hmme_predict_refs_w_device; null: none); origin with pr: the origin of the *_bi_refs calls
 int launch_predict(hmme_ctx* ctx, const hmme_plane* src, const int16_t* d_field, int mv_per_ctu, int first, int count, bool origin, const uint8_t* cur_blocks,
                    int bias, uint8_t* dst, long dst_ctu_x, long dst_ctu_y, int dst_pitch, hipStream_t s, const hmme::MePredWp<1>* pw = nullptr,
                    const hmme::MePredRefs<1>* pr = nullptr, const hmme::MePredWp<2>* prw = nullptr) {
@@ -2138,6 +2151,7 @@ int launch_predict(hmme_ctx* ctx, const hmme_plane* src, const int16_t* d_field,
     const hmme::MePredWp<0> no_wp;
     const hmme::MePredRefs<0> no_refs;
     if (pr && prw) go(hmme::me_predict_kernel<T, 0, 2, 1>, *prw, *pr);
+    else if (origin && pr) go(hmme::me_predict_kernel<T, 1, 0, 1>, no_wp, *pr);
     else if (pr) go(hmme::me_predict_kernel<T, 0, 0, 1>, no_wp, *pr);
     else if (origin && pw) go(hmme::me_predict_kernel<T, 1, 1, 0>, *pw, no_refs);
     else if (origin) go(hmme::me_predict_kernel<T, 1, 0, 0>, no_wp, no_refs);
@@ -2576,6 +2590,179 @@ int hmme_refine_frame_bi_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plan
                   out_cost);
 }
 
+// ---- the bi pass of one list over all its references, against a reference per block in the other list (the rule: include/hmme.h) ----------
+// bi_search / bi_refine with ONE origin for all n_refs pairs, as the multi-reference uni launch hands one current picture to its pairs: the
+// other list's prediction comes from others[d_other_ref[block]] (me_predict_kernel<T, 1, 0, 1>, one launch per call), the biased / raw
+// reference copies stay per reference.  No explicit weights: the bias is maxv.
+namespace {
+int bi_refs_args(hmme_ctx* ctx, const char* who, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
+                 const hmme_frame_params* fp, const void* d_other_mv, const void* d_other_ref, int mv_per_ctu) {
+  if (!cur || !refs || !others || n_refs < 1 || n_refs > hmme::kMaxRefs || n_others < 1 || n_others > hmme::kMaxRefs)
+    return fail(ctx, HMME_ERR_ARG, "%s: %d / %d reference pictures outside 1..%d (or a null plane or plane list)", who, n_refs, n_others, hmme::kMaxRefs);
+  if (!d_other_mv || !d_other_ref || (mv_per_ctu != 1 && mv_per_ctu != 64))
+    return fail(ctx, HMME_ERR_ARG, "%s: null motion or reference field, or %d MVs per CTU (1 or 64)", who, mv_per_ctu);
+  for (int r = 0; r < n_refs; ++r)
+    if (!refs[r]) return fail(ctx, HMME_ERR_ARG, "%s: null plane", who);
+  for (int r = 0; r < n_others; ++r) {
+    if (!others[r]) return fail(ctx, HMME_ERR_ARG, "%s: null plane", who);
+    if (others[r]->ctx != ctx) return fail(ctx, HMME_ERR_ARG, "plane belongs to another context (planes are used with the context that created them)");
+    if (others[r]->width != cur->width || others[r]->height != cur->height) return fail(ctx, HMME_ERR_ARG, "%s: the other list's plane %d differs in size", who, r);
+    if (others[r]->bit_depth != fp->bit_depth) return fail(ctx, HMME_ERR_ARG, "%s: the other list's plane %d holds %d-bit samples, the call asks for %d", who, r, others[r]->bit_depth, fp->bit_depth);
+  }
+  return HMME_OK;
+}
+
+// the launch's planes as lists_end takes them: the current picture and the searched list
+struct BiRefsPlanes {
+  const hmme_plane* curs[hmme::kMaxRefs];
+  const hmme_plane* read[hmme::kMaxRefs + 1];
+  BiRefsPlanes(const hmme_plane* cur, const hmme_plane* const* refs, int n_refs) {
+    read[0] = cur;
+    for (int r = 0; r < n_refs; ++r) { curs[r] = cur; read[r + 1] = refs[r]; }
+  }
+};
+hmme::MePredRefs<1> other_set(const hmme_plane* const* others, int n_others, const void* d_other_ref) {
+  hmme::MePredRefs<1> pr = {one_ref(nullptr), (const uint8_t*)d_other_ref, n_others};
+  for (int r = 0; r < n_others; ++r) pr.set.base[r] = others[r]->origin();
+  return pr;
+}
+
+int bi_refs_search(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
+                   const hmme_frame_params* fp, const void* d_other_mv, const void* d_other_ref, int mv_per_ctu, const void* d_center_q, const void* d_pred_q,
+                   void* d_out_mv, void* d_out_sad, void* stream) {
+  if (!d_out_mv || !d_out_sad) return fail(ctx, HMME_ERR_ARG, "null output buffer");
+  hipStream_t s = (hipStream_t)stream;
+  const BiRefsPlanes p(cur, refs, n_refs);
+  PairLaunch pl;
+  int rc = pairs_begin(ctx, p.curs, refs, n_refs, fp, s, &pl);
+  if (rc || pl.count == 0) return rc;
+  for (int r = 0; r < n_others && rc == HMME_OK; ++r) rc = plane_wait(ctx, others[r], s);
+  const WpGeom g(refs[0]);
+  const int ctus_x = cur->ctus_x, bias = (1 << fp->bit_depth) - 1;
+  if (rc == HMME_OK) rc = ensure(ctx, ctx->buf[kWp0], g.plane_bytes * n_refs);
+  if (rc == HMME_OK) rc = ensure(ctx, ctx->buf[kWp1], g.blk_bytes);
+  RefSet wrefs = one_ref(nullptr), wcurs = one_ref(nullptr);
+  CopyCache wref(ctx->wp(0), g.plane_bytes, false);   // the references with the origin's bias
+  for (int r = 0; r < n_refs && rc == HMME_OK; ++r) {
+    rc = cached_copy(ctx, wref, g, r, CopyKey{refs[r], 1, 0, 0, bias}, s, &wrefs.base[r]);
+    wcurs.base[r] = ctx->wp(1);   // the ONE origin
+  }
+  if (rc == HMME_OK) {
+    const hmme::MePredRefs<1> pr = other_set(others, n_others, d_other_ref);
+    rc = launch_predict(ctx, others[0], (const int16_t*)d_other_mv, mv_per_ctu, pl.first, pl.count, true, cur->d_blocks, bias, ctx->wp(1), hmme::kBlkBytes16,
+                        (long)ctus_x * hmme::kBlkBytes16, 128, s, nullptr, &pr);
+  }
+  const FramePlan plan = plan_launch(ctx, fp, pl.count, n_refs, true);
+  if (rc == HMME_OK) rc = prep_jobs(ctx, cur, fp, d_pred_q, pl.first, pl.count, n_refs, s, plan, d_center_q);
+  if (rc == HMME_OK) rc = run_search(ctx, wcurs, ctus_x, wrefs, g.pitch, fp, plan, (int16_t*)d_out_mv, (uint32_t*)d_out_sad, s);
+  return lists_end(ctx, p.read, n_refs + 1, others, n_others, s, rc);
+}
+
+int bi_refs_refine(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
+                   const hmme_frame_params* fp, const void* d_other_mv, const void* d_other_ref, int mv_per_ctu, const void* d_center_q, const void* d_pred_q,
+                   const void* d_int_mv, int use_hadamard, void* d_out_qmv, void* d_out_cost, void* stream) {
+  if (!d_int_mv || !d_out_qmv || !d_out_cost) return fail(ctx, HMME_ERR_ARG, "null buffer");
+  hipStream_t s = (hipStream_t)stream;
+  const BiRefsPlanes p(cur, refs, n_refs);
+  PairLaunch pl;
+  int rc = pairs_begin(ctx, p.curs, refs, n_refs, fp, s, &pl);
+  if (rc || pl.count == 0) return rc;
+  for (int r = 0; r < n_others && rc == HMME_OK; ++r) rc = plane_wait(ctx, others[r], s);
+  const int src_wide = cur->bps == 2 ? 1 : 0, bias = (1 << fp->bit_depth) - 1;
+  const WpGeom g(refs[0]);
+  if (rc == HMME_OK && !src_wide) rc = ensure(ctx, ctx->buf[kWp2], g.plane_bytes * n_refs);
+  if (rc == HMME_OK) rc = ensure(ctx, ctx->buf[kWp3], g.plane_bytes);
+  RefSet c = one_ref(nullptr), rf = one_ref(nullptr);
+  CopyCache raw(ctx->wp(2), g.plane_bytes, false);
+  for (int r = 0; r < n_refs && rc == HMME_OK; ++r) {
+    // the RAW reference is interpolated: a u16 plane serves as it is, an 8-bit one is widened
+    if (src_wide) rf.base[r] = pl.refs.base[r];
+    else rc = cached_copy(ctx, raw, g, r, CopyKey{refs[r], 1, 0, 0, 0}, s, &rf.base[r]);
+    c.base[r] = ctx->wp(3) + g.origin;   // the ONE origin, in a padded plane's layout
+  }
+  if (rc == HMME_OK) {
+    const hmme::MePredRefs<1> pr = other_set(others, n_others, d_other_ref);
+    rc = launch_predict(ctx, others[0], (const int16_t*)d_other_mv, mv_per_ctu, pl.first, pl.count, true, cur->d_blocks, bias, ctx->wp(3) + g.origin, 128,
+                        64L * g.pitch, g.pitch, s, nullptr, &pr);
+  }
+  if (rc == HMME_OK) {
+    RefineLaunch L;
+    refine_common(L, pl, cur, fp, use_hadamard, (const int16_t*)d_int_mv, (int16_t*)d_out_qmv, (uint32_t*)d_out_cost);
+    L.curs = c; L.refs = rf; L.cur_pitch = g.pitch; L.ref_pitch = g.pitch;
+    L.build.wide = 1; L.build.wp = 1;
+    L.fw = hmme::FracWp{1.f, 0.f, (float)bias};   // org_sub takes the origin's bias off
+    L.d_pred = (const int16_t*)d_pred_q;
+    L.d_center = (const int16_t*)d_center_q;
+    L.pairs = n_refs;
+    L.table = FracTable::kAlways;   // the table carries the window centres
+    rc = launch_refine(ctx, L, s);
+  }
+  return lists_end(ctx, p.read, n_refs + 1, others, n_others, s, rc);
+}
+
+// the two synchronous forms; int_mv != null: the refinement
+int bi_refs_frame(hmme_ctx* ctx, const char* who, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
+                  const hmme_frame_params* fp, const int16_t* other_mv, const uint8_t* other_ref, int mv_per_ctu, const int16_t* center_q, const int16_t* pred_q,
+                  bool refine, const int16_t* int_mv, int use_hadamard, int16_t* out_mv, uint32_t* out_cost) {
+  int rc = bi_check(ctx, who, fp, refine);
+  if (rc == HMME_OK) rc = bi_refs_args(ctx, who, cur, refs, n_refs, others, n_others, fp, other_mv, other_ref, mv_per_ctu);
+  if (rc) return rc;
+  int count;
+  Stage st(ctx);
+  FrameItems it;
+  const size_t blocks = (size_t)cur->n_ctu * mv_per_ctu;
+  const int field = st.in(other_mv, sizeof(int16_t) * 2 * blocks), rfield = st.in(other_ref, blocks);
+  const int center = st.in(center_q, sizeof(int16_t) * 2 * (size_t)cur->n_ctu * n_refs);
+  rc = stage_in(ctx, cur, refs[0], fp, n_refs, pred_q, refine, int_mv, out_mv, out_cost, &count, st, &it);
+  if (rc || count == 0) return rc;
+  if (!refine)
+    rc = hmme_search_frame_bi_refs_device(ctx, cur, refs, n_refs, others, n_others, fp, st.at(field), st.at(rfield), mv_per_ctu, st.at(center), st.at(it.pred),
+                                          st.at(it.mv), st.at(it.cost), ctx->stream);
+  else
+    rc = hmme_refine_frame_bi_refs_device(ctx, cur, refs, n_refs, others, n_others, fp, st.at(field), st.at(rfield), mv_per_ctu, st.at(center), st.at(it.pred),
+                                          st.at(it.imv), use_hadamard, st.at(it.mv), st.at(it.cost), ctx->stream);
+  return rc ? rc : st.end();
+}
+}  // namespace
+
+int hmme_search_frame_bi_refs_device(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others,
+                                     int n_others, const hmme_frame_params* fp, const void* d_other_mv, const void* d_other_ref, int mv_per_ctu,
+                                     const void* d_center_q, const void* d_pred_q, void* d_out_mv, void* d_out_sad, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  int rc = bi_check(ctx, "hmme_search_frame_bi_refs_device", fp, 0);
+  if (rc == HMME_OK) rc = bi_refs_args(ctx, "hmme_search_frame_bi_refs_device", cur, refs, n_refs, others, n_others, fp, d_other_mv, d_other_ref, mv_per_ctu);
+  if (rc) return rc;
+  return bi_refs_search(ctx, cur, refs, n_refs, others, n_others, fp, d_other_mv, d_other_ref, mv_per_ctu, d_center_q, d_pred_q, d_out_mv, d_out_sad, stream);
+}
+
+int hmme_refine_frame_bi_refs_device(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others,
+                                     int n_others, const hmme_frame_params* fp, const void* d_other_mv, const void* d_other_ref, int mv_per_ctu,
+                                     const void* d_center_q, const void* d_pred_q, const void* d_int_mv, int use_hadamard, void* d_out_qmv, void* d_out_cost,
+                                     void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  int rc = bi_check(ctx, "hmme_refine_frame_bi_refs_device", fp, 1);
+  if (rc == HMME_OK) rc = bi_refs_args(ctx, "hmme_refine_frame_bi_refs_device", cur, refs, n_refs, others, n_others, fp, d_other_mv, d_other_ref, mv_per_ctu);
+  if (rc) return rc;
+  return bi_refs_refine(ctx, cur, refs, n_refs, others, n_others, fp, d_other_mv, d_other_ref, mv_per_ctu, d_center_q, d_pred_q, d_int_mv, use_hadamard, d_out_qmv,
+                        d_out_cost, stream);
+}
+
+int hmme_search_frame_bi_refs(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
+                              const hmme_frame_params* fp, const int16_t* other_mv, const uint8_t* other_ref, int mv_per_ctu, const int16_t* center_q,
+                              const int16_t* pred_q, int16_t* out_mv, uint32_t* out_sad) {
+  if (!ctx) return HMME_ERR_ARG;
+  return bi_refs_frame(ctx, "hmme_search_frame_bi_refs", cur, refs, n_refs, others, n_others, fp, other_mv, other_ref, mv_per_ctu, center_q, pred_q, false, nullptr, 0,
+                       out_mv, out_sad);
+}
+
+int hmme_refine_frame_bi_refs(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
+                              const hmme_frame_params* fp, const int16_t* other_mv, const uint8_t* other_ref, int mv_per_ctu, const int16_t* center_q,
+                              const int16_t* pred_q, const int16_t* int_mv, int use_hadamard, int16_t* out_qmv, uint32_t* out_cost) {
+  if (!ctx) return HMME_ERR_ARG;
+  return bi_refs_frame(ctx, "hmme_refine_frame_bi_refs", cur, refs, n_refs, others, n_others, fp, other_mv, other_ref, mv_per_ctu, center_q, pred_q, true, int_mv,
+                       use_hadamard, out_qmv, out_cost);
+}
+
 // ---- partition decision and motion field from the 593-slot tables ---------------------------------------------------------------------
 namespace {
 int select_eval(const hmme_select_params* p, char* msg, size_t cap) {
@@ -2978,6 +3165,99 @@ int hmme_select_dirs_frame(hmme_ctx* ctx, int width, int height, const hmme_fram
                        }, &bi);
 }
 
+// ---- L0, L1 or bi and the reference index per list, per PU: the decision over the table sets of a B picture with several references -----------
+namespace {
+int select_dirs_refs_eval(const hmme_select_params* sel, int n_pics, int n_refs_max, const hmme_dir_refs_params* dirs, char* msg, size_t cap) {
+  const hmme_dir_params none[kMaxDirPics] = {};   // what hmme_select_dirs_check refuses of sel, n_pics and a null dirs
+  const int bad = select_dirs_eval(sel, n_pics, dirs ? none : nullptr, msg, cap);
+  if (bad) return bad;
+  if (n_refs_max < 1 || n_refs_max > hmme::kMaxDirRefs) { snprintf(msg, cap, "%d table sets per list outside 1..%d", n_refs_max, hmme::kMaxDirRefs); return HMME_ERR_ARG; }
+  for (int p = 0; p < n_pics; ++p) {
+    const hmme_dir_refs_params& d = dirs[p];
+    for (int k = 0; k < 3; ++k)
+      if (d.dir_bits[k] > 4096) { snprintf(msg, cap, "picture %d: dir_bits[%d] = %u above 4096", p, k, d.dir_bits[k]); return HMME_ERR_ARG; }
+    for (int l = 0; l < 2; ++l) {
+      if (d.n_refs[l] < 1 || d.n_refs[l] > n_refs_max) { snprintf(msg, cap, "picture %d: %d references in list %d outside 1..%d", p, d.n_refs[l], l, n_refs_max); return HMME_ERR_ARG; }
+      for (int r = 0; r < hmme::kMaxDirRefs; ++r)
+        if (d.ref_bits[l][r] > 4096) { snprintf(msg, cap, "picture %d: ref_bits[%d][%d] = %u above 4096", p, l, r, d.ref_bits[l][r]); return HMME_ERR_ARG; }
+    }
+    if (d.l1_valid_mask >> d.n_refs[1]) { snprintf(msg, cap, "picture %d: l1_valid_mask 0x%x names references at or above %d", p, d.l1_valid_mask, d.n_refs[1]); return HMME_ERR_ARG; }
+  }
+  return HMME_OK;
+}
+}  // namespace
+
+int hmme_select_dirs_refs_check(const hmme_select_params* sel, int n_pics, int n_refs_max, const hmme_dir_refs_params* dirs) {
+  char msg[256];
+  return select_dirs_refs_eval(sel, n_pics, n_refs_max, dirs, msg, sizeof msg);
+}
+
+int hmme_select_dirs_refs_device(hmme_ctx* ctx, int width, int height, int n_pics, int n_refs_max, const hmme_frame_params* fp, const hmme_select_params* sel,
+                                 const hmme_dir_refs_params* dirs, const void* d_mv_uni, const void* d_cost_uni, const void* d_mv_bi, const void* d_cost_bi,
+                                 const void* d_uni_field, const void* d_uni_ref, const void* d_pred_q, void* d_out_field, void* d_out_ref, void* d_out_dir,
+                                 void* d_out_slot, void* d_out_cost, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  const char* who = "hmme_select_dirs_refs_device";
+  char msg[256];
+  const int bad = select_dirs_refs_eval(sel, n_pics, n_refs_max, dirs, msg, sizeof msg);
+  if (bad) return fail(ctx, bad, "%s: %s", who, msg);
+  if (!d_mv_bi || !d_cost_bi || !d_uni_field || !d_uni_ref || !d_out_ref || !d_out_dir)
+    return fail(ctx, HMME_ERR_ARG, "%s: null bi table, input field, or reference / direction buffer", who);
+  if (((uintptr_t)d_mv_bi & 3) || ((uintptr_t)d_cost_bi & 3) || ((uintptr_t)d_uni_field & 3))
+    return fail(ctx, HMME_ERR_ARG, "%s: misaligned buffer (tables, costs and the input field 4 bytes)", who);
+  SelectLaunch L;   // (the shared checks count table sets: a picture's two lists)
+  const int rc = select_begin(ctx, who, width, height, n_pics, 2, nullptr, fp, sel, d_mv_uni, d_cost_uni, d_pred_q, d_out_field, d_out_slot, d_out_cost, &L);
+  if (rc || L.count == 0) return rc;
+  hmme::MeDirRefsParams bits = {};
+  for (int p = 0; p < n_pics; ++p) {
+    hmme::MeDirRefsBits& b = bits.p[p];
+    for (int k = 0; k < 3; ++k) b.dir_bits[k] = dirs[p].dir_bits[k];
+    for (int l = 0; l < 2; ++l) {
+      b.n_refs[l] = dirs[p].n_refs[l];
+      for (int r = 0; r < hmme::kMaxDirRefs; ++r) b.ref_bits[l][r] = dirs[p].ref_bits[l][r];
+    }
+    b.l1_valid_mask = dirs[p].l1_valid_mask;
+  }
+  hipLaunchKernelGGL(hmme::me_select_dirs_refs_kernel, L.grid, dim3(256), 0, (hipStream_t)stream, (const uint32_t*)d_mv_uni, (const uint32_t*)d_cost_uni,
+                     (const uint32_t*)d_mv_bi, (const uint32_t*)d_cost_bi, (const uint32_t*)d_uni_field, (const uint8_t*)d_uni_ref, (const int16_t*)d_pred_q,
+                     (uint32_t*)d_out_field, (uint8_t*)d_out_ref, (uint8_t*)d_out_dir, (uint16_t*)d_out_slot, (uint32_t*)d_out_cost, L.a, bits, n_refs_max, width, height,
+                     L.n_ctu, L.first, L.count, ctx->lambda_q16);
+  HIP_TRY(ctx, hipGetLastError());
+  return HMME_OK;
+}
+
+int hmme_select_dirs_refs_frame(hmme_ctx* ctx, int width, int height, int n_refs_max, const hmme_frame_params* fp, const hmme_select_params* sel,
+                                const hmme_dir_refs_params* dir, const int16_t* mv_uni, const uint32_t* cost_uni, const int16_t* mv_bi, const uint32_t* cost_bi,
+                                const int16_t* uni_field, const uint8_t* uni_ref, const int16_t* pred_q, int16_t* out_field, uint8_t* out_ref, uint8_t* out_dir,
+                                uint16_t* out_slot, uint32_t* out_cost) {
+  if (!ctx) return HMME_ERR_ARG;
+  const char* who = "hmme_select_dirs_refs_frame";
+  char msg[256];
+  const int bad = select_dirs_refs_eval(sel, 1, n_refs_max, dir, msg, sizeof msg);   // before anything is staged
+  if (bad) return fail(ctx, bad, "%s: %s", who, msg);
+  if (!fp || width < 1 || height < 1 || !mv_uni || !cost_uni || !mv_bi || !cost_bi || !uni_field || !uni_ref || !out_field || !out_ref || !out_dir)
+    return fail(ctx, HMME_ERR_ARG, "%s: null argument, or a %d x %d picture", who, width, height);
+  const size_t n_ctu = hmme_num_ctus(width, height);
+  int first, count;
+  int rc = ctu_range(ctx, fp, (int)n_ctu, &first, &count);
+  if (rc || count == 0) return rc;
+  const size_t sets = (size_t)2 * n_refs_max, tab = sets * count * HMME_NUM_CTU_PARTS * 4;
+  Stage st(ctx);
+  const int i_mu = st.in(mv_uni, tab), i_cu = st.in(cost_uni, tab), i_mb = st.in(mv_bi, tab), i_cb = st.in(cost_bi, tab);
+  const int i_pred = st.in(pred_q, sets * n_ctu * 4), i_field = st.in(uni_field, 2 * n_ctu * 64 * 4), i_ref = st.in(uni_ref, 2 * n_ctu * 64);
+  // only the CTUs of the range come back: the caller's entries outside it keep their values
+  const auto out = [&](void* host, size_t ctu_bytes, size_t parts) { return st.out(host, n_ctu * ctu_bytes, first * ctu_bytes, count * ctu_bytes, parts); };
+  const int o_field = out(out_field, 64 * 4, 2), o_ref = out(out_ref, 64, 2), o_dir = out(out_dir, 64, 1), o_slot = out(out_slot, 64 * 2, 1), o_cost = out(out_cost, 4, 1);
+  rc = st.begin();
+  if (rc == HMME_OK) {
+    rc = hmme_select_dirs_refs_device(ctx, width, height, 1, n_refs_max, fp, sel, dir, st.at(i_mu), st.at(i_cu), st.at(i_mb), st.at(i_cb), st.at(i_field), st.at(i_ref),
+                                      st.at(i_pred), st.at(o_field), st.at(o_ref), st.at(o_dir), st.at(o_slot), st.at(o_cost), ctx->stream);
+    if (rc && ctx->err.compare(0, strlen("hmme_select_dirs_refs_device"), "hmme_select_dirs_refs_device") == 0)
+      ctx->err.replace(0, strlen("hmme_select_dirs_refs_device"), who);   // the refusal names the entry the caller made
+  }
+  return rc ? rc : st.end();
+}
+
 namespace {
 // every picture's two weights before anything is launched; the message names the picture
 int check_predict_bi_weights(hmme_ctx* ctx, const char* who, const hmme_frame_params* fp, const hmme_weight* wps0, const hmme_weight* wps1, int n_pics, PredBiWp* bw) {
@@ -3034,7 +3314,7 @@ int predict_bi(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs0, c
       using T = decltype(sample);
       const auto go = [&](auto kernel, auto wp) {
         hipLaunchKernelGGL(kernel, dim3((unsigned)L.count), dim3(256), 0, s, planes[2 * i]->origin(), planes[2 * i + 1]->origin(), p0->pitch, field, dirs, mv_per_ctu,
-                           L.n_ctu, L.first, L.w, L.h, p0->bit_depth, (uint8_t*)d_outs[i], out_pitch_bytes, wp);
+                           L.n_ctu, L.first, L.w, L.h, p0->bit_depth, (uint8_t*)d_outs[i], out_pitch_bytes, wp, hmme::MePredBiRefs<0>{});
       };
       if (bw[i].identity) go(hmme::me_predict_bi_kernel<T, 0>, hmme::MePredBiWp<0>{}); else go(hmme::me_predict_bi_kernel<T, 1>, bw[i].k);
     });
@@ -3090,6 +3370,73 @@ int hmme_predict_bi_w_frame(hmme_ctx* ctx, const hmme_plane* ref0, const hmme_pl
                             const hmme_weight* wp1, const int16_t* mv_field, const uint8_t* dir_field, int mv_per_ctu, void* out, int out_stride) {
   if (!ctx) return HMME_ERR_ARG;
   return predict_bi_frame(ctx, "hmme_predict_bi_w_frame", &ref0, &ref1, 1, 0, 0, fp, wp0, wp1, true, mv_field, dir_field, mv_per_ctu, &out, out_stride);
+}
+
+// ---- the prediction of a B picture with several references per list (the rule: include/hmme.h) --------------------------------------------------
+// hmme_predict_bi_refs_device: ONE picture, ONE launch of me_predict_bi_kernel<T, 0, 1>: every block from the planes its direction and its two
+// reference indices name.  The two lists go through the checks of predict_refs one after the other (each up to 16 planes), list 1 against
+// list 0's first plane for the size.
+int hmme_predict_bi_refs_device(hmme_ctx* ctx, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, const hmme_frame_params* fp,
+                                const void* d_mv_field, const void* d_dir_field, const void* d_ref_field, int mv_per_ctu, void* d_out, int out_pitch_bytes,
+                                void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  const char* who = "hmme_predict_bi_refs_device";
+  int rc = bi_check(ctx, who, fp, 0);
+  if (rc) return rc;
+  if (!refs0 || !refs1 || n0 < 1 || n0 > hmme::kMaxRefs || n1 < 1 || n1 > hmme::kMaxRefs)
+    return fail(ctx, HMME_ERR_ARG, "%s: %d / %d reference pictures outside 1..%d (or a null plane list)", who, n0, n1, hmme::kMaxRefs);
+  PredictArgs a;
+  rc = predict_args(ctx, who, refs0, n0, !d_dir_field || !d_ref_field || !d_out, fp, nullptr, d_mv_field, mv_per_ctu, out_pitch_bytes, &a, "reference");
+  if (rc) return rc;
+  const hmme_plane* first0[hmme::kMaxRefs];
+  for (int r = 0; r < n1; ++r) {
+    if (!refs1[r]) return fail(ctx, HMME_ERR_ARG, "%s: null plane", who);
+    first0[r] = refs0[0];
+  }
+  hipStream_t s = (hipStream_t)stream;
+  PredictLaunch L;
+  rc = predict_begin(ctx, who, refs0, n0, 1, 0, 0, fp, a, s, &L);
+  PairLaunch l1;   // list 1: this context, fp's bit depth, list 0's size; ordered like references
+  if (rc == HMME_OK) rc = named(ctx, who, pairs_begin(ctx, first0, refs1, n1, &a.f, s, &l1));
+  if (rc || !L.acquired) return rc;
+  const hmme_plane* p0 = refs0[0];
+  const hmme::MePredBiRefs<1> br = {{L.pl.refs, l1.refs}, (const uint8_t*)d_ref_field, {n0, n1}};
+  with_sample_type(p0->bps, [&](auto sample) {
+    using T = decltype(sample);
+    hipLaunchKernelGGL((hmme::me_predict_bi_kernel<T, 0, 1>), dim3((unsigned)L.count), dim3(256), 0, s, (const uint8_t*)nullptr, (const uint8_t*)nullptr, p0->pitch,
+                       (const int16_t*)d_mv_field, (const uint8_t*)d_dir_field, mv_per_ctu, L.n_ctu, L.first, L.w, L.h, p0->bit_depth, (uint8_t*)d_out, out_pitch_bytes,
+                       hmme::MePredBiWp<0>{}, br);
+  });
+  if (hipGetLastError() != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "%s: launch failed", who);
+  return lists_end(ctx, refs0, n0, refs1, n1, s, rc);   // whatever the launch returned: the scratch is acquired
+}
+
+int hmme_predict_bi_refs_frame(hmme_ctx* ctx, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, const hmme_frame_params* fp,
+                               const int16_t* mv_field, const uint8_t* dir_field, const uint8_t* ref_field, int mv_per_ctu, void* out, int out_stride) {
+  if (!ctx) return HMME_ERR_ARG;
+  const char* who = "hmme_predict_bi_refs_frame";
+  int rc = bi_check(ctx, who, fp, 0);   // before anything is staged
+  if (rc) return rc;
+  if (!refs0 || !refs1 || n0 < 1 || n0 > hmme::kMaxRefs || n1 < 1 || n1 > hmme::kMaxRefs || !refs0[0])
+    return fail(ctx, HMME_ERR_ARG, "%s: %d / %d reference pictures outside 1..%d (or a null plane)", who, n0, n1, hmme::kMaxRefs);
+  rc = frame_args(ctx, who, fp, refs0, n0, 1, !mv_field || !dir_field || !ref_field || !out, mv_per_ctu, 0, 0);
+  if (rc == HMME_OK) rc = frame_args(ctx, who, fp, refs1, n1, 1, false, mv_per_ctu, 0, 0);
+  if (rc) return rc;
+  const hmme_plane* p0 = refs0[0];
+  if (p0->ctx != ctx) return fail(ctx, HMME_ERR_ARG, "%s: plane belongs to another context (planes are used with the context that created them)", who);
+  if (out_stride < p0->width) return fail(ctx, HMME_ERR_ARG, "%s: output stride %d below the picture width", who, out_stride);
+  // blocks without a direction or a reference, too, come back as they were
+  const size_t blocks = (size_t)p0->n_ctu * mv_per_ctu, row = (size_t)p0->width * p0->bps;
+  Stage st(ctx);
+  const int field = st.in(mv_field, sizeof(int16_t) * 2 * blocks * 2), dirs = st.in(dir_field, blocks), rfield = st.in(ref_field, 2 * blocks);
+  const int img = st.image(out, row, p0->height, (size_t)out_stride * p0->bps);
+  rc = st.begin();
+  if (rc == HMME_OK) {
+    rc = hmme_predict_bi_refs_device(ctx, refs0, n0, refs1, n1, fp, st.at(field), st.at(dirs), st.at(rfield), mv_per_ctu, st.at(img), (int)row, ctx->stream);
+    if (rc && ctx->err.compare(0, strlen("hmme_predict_bi_refs_device"), "hmme_predict_bi_refs_device") == 0)
+      ctx->err.replace(0, strlen("hmme_predict_bi_refs_device"), who);   // the refusal names the entry the caller made
+  }
+  return rc ? rc : st.end();
 }
 
 // ---- 4:2:0 chroma motion compensation from the luma motion fields ------------------------------------------------------------------------------

@@ -2267,6 +2267,8 @@ __device__ __forceinline__ int me_predict_block_sum(bool live, const uint8_t* or
 //            wave handles one 8x8 block at a time -- so the choice of the source base is a scalar one.  A block whose index is >= n_refs
 //            (0xFF: no CU covers it) is not live: it reads no plane and writes nothing, and still meets both barriers of its iteration.
 //            REFS = 0 takes an empty struct and compiles to what it did without it.
+//            With OUT = 1 (hmme_search_frame_bi_refs_device: the origin against a reference per block of the other list) every block is
+//            written, and an index >= n_refs reads reference 0 -- the blocks outside the picture, whose index is 0xFF and whose MV (0,0).
 //   WP = 2:  WP = 1 with one weight per reference picture (hmme_predict_refs_w_device; REFS = 1 only): the block's reference index --
 //            already a scalar -- picks its MePredWp<1> among the sixteen in the kernel arguments.
 template <int REFS> struct MePredRefs {};
@@ -2294,7 +2296,7 @@ me_predict_kernel(const uint8_t* __restrict__ ref_origin, int ref_pitch, const i
     int ri = 0;
     if constexpr (REFS) {
       ri = __builtin_amdgcn_readfirstlane((int)refs.ref_field[e]);
-      live = live && ri < refs.n_refs;
+      if (OUT == 0) live = live && ri < refs.n_refs;   // OUT = 1: every block of the origin is written; such an index reads reference 0
       origin = refs.set.base[ri < refs.n_refs ? ri : 0];
     }
     const int sum = me_predict_block_sum<SrcT>(live, origin, ref_pitch, cu_x + bx, cu_y + by, mx, my, patch[wave], mid[wave], lane, k);
@@ -2417,11 +2419,16 @@ __device__ __forceinline__ void me_select_level(const MeSelect& a, const CostT* 
 // DIRS (me_select_dirs_kernel; one MV per 8x8 block only): s_ref holds direction | searched list << 2 per slot, out_ref takes the direction,
 // and the field has two lists list_stride dwords apart: the winner's MV in its list; in the other list (0,0) under a direction-1 / -2
 // slot and, under a direction-3 slot, the block's own entry of uni_field (laid out like out_field).  Without DIRS neither is looked at.
-template <bool REFS, typename CostT, bool DIRS = false>
+// LREFS (me_select_dirs_refs_kernel; with DIRS): a reference index per list leaves beside the direction, laid out like the field with bytes
+// for dwords (out_lref, two lists list_stride bytes apart).  s_lref holds per slot the winner's index in list 0 and, kParts + 3 bytes on, in
+// list 1: the index travels with the MV -- the winner's in its list, 0xFF in the other under a direction-1 / -2 slot, the block's own entry
+// of uni_ref (laid out like out_lref) under a direction-3 slot.  Without LREFS none of the three is looked at.
+template <bool REFS, typename CostT, bool DIRS = false, bool LREFS = false>
 __device__ __forceinline__ void me_select_decide_store(const MeSelect& a, const CostT* s_cost, const uint32_t* s_mv, const uint8_t* s_ref, uint32_t lambda_q16,
                                                        int pred_x, int pred_y, int lane, int ctu_x, int ctu_y, long o, int pic_w, int pic_h,
                                                        uint32_t* out_field, uint8_t* out_ref, uint16_t* out_slot, uint32_t* out_cost,
-                                                       const uint32_t* uni_field = nullptr, long list_stride = 0) {
+                                                       const uint32_t* uni_field = nullptr, long list_stride = 0, const uint8_t* s_lref = nullptr,
+                                                       const uint8_t* uni_ref = nullptr, uint8_t* out_lref = nullptr) {
   const int bx = lane & 7, by = lane >> 3;
   MeSelectState st = {0, -1, 0};
   me_select_level<3>(a, s_cost, s_mv, lambda_q16, pred_x, pred_y, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
@@ -2445,6 +2452,13 @@ __device__ __forceinline__ void me_select_decide_store(const MeSelect& a, const 
       out_field[o * 64 + lane] = f[0];
       out_field[o * 64 + lane + list_stride] = f[1];
       out_ref[o * 64 + lane] = dir ? (uint8_t)dir : (uint8_t)0xff;
+      if constexpr (LREFS) {
+        uint8_t rl[2] = {0xff, 0xff};
+        if (dir == 3) { rl[bl] = s_lref[bl * (kParts + 3) + slot]; rl[1 - bl] = uni_ref[o * 64 + lane + (1 - bl) * list_stride]; }
+        else if (dir) rl[dir - 1] = s_lref[(dir - 1) * (kParts + 3) + slot];
+        out_lref[o * 64 + lane] = rl[0];
+        out_lref[o * 64 + lane + list_stride] = rl[1];
+      }
     } else {
       out_field[o * 64 + lane] = slot == 0xffff ? 0u : field_mv(slot);
       if constexpr (REFS) out_ref[o * 64 + lane] = slot == 0xffff ? (uint8_t)0xff : s_ref[slot];
@@ -2654,6 +2668,115 @@ me_select_dirs_kernel(const uint32_t* __restrict__ mv_uni, const uint32_t* __res
                                                pic_w, pic_h, out_field + at, out_dir, out_slot, out_cost, uni_field + at, lists);
 }
 
+// ---- L0, L1 or bi and the reference index per list, per PU (hmme_select_dirs_refs_device; the rule: include/hmme.h) -----------------------
+// hmme_dir_refs_params of every picture of the launch, as the kernel takes them
+constexpr int kMaxDirRefs = 8;
+struct MeDirRefsBits { uint32_t dir_bits[3]; int n_refs[2]; uint32_t ref_bits[2][kMaxDirRefs]; uint32_t l1_valid_mask; };
+struct MeDirRefsParams { MeDirRefsBits p[4]; };
+
+// me_select_dirs_kernel with a reference dimension behind the list: uni / bi tables int16 [n_pics][2][R][ctu_count][593][2] as dwords with
+// costs uint32 of that shape, pred_q int16 [n_pics][2][R][n_ctu][2] or null; list l uses its first n_refs[l] sets.  A lane owns the slots
+// lane, lane + 64, ... and walks each through the references of both lists in registers, twice: the uni pass keeps per list the first
+// strict minimum (:3086) with its MV, index and motion bits (ref_bits + MV bits, :3154-3155), list 1 also the minimum over the references
+// of l1_valid_mask -- its direction-2 candidate (:3096-3104, :3282-3285), absent with an empty mask; the bi pass prices every reference
+// against the OTHER list's motion bits (:3210-3219) and keeps the first strict minimum (:3226).  Predictors and bit counts are wave-uniform;
+// no LDS traffic, no atomic and no cross-lane step in the reference loops.  The winner's cost (64 bits), MV dword, direction | searched
+// list << 2 and the two reference indices go to LDS (35.8 KB per workgroup) and me_select_decide_store<.., DIRS, LREFS> decides on them
+// with the MV cost switched off.  uni_field / out_field: int16 [n_pics][2][n_ctu][64][2] as dwords; uni_ref / out_ref: uint8
+// [n_pics][2][n_ctu][64]; out_dir uint8 [n_pics][n_ctu][64].
+__global__ void __launch_bounds__(256)
+me_select_dirs_refs_kernel(const uint32_t* __restrict__ mv_uni, const uint32_t* __restrict__ cost_uni, const uint32_t* __restrict__ mv_bi,
+                           const uint32_t* __restrict__ cost_bi, const uint32_t* __restrict__ uni_field, const uint8_t* __restrict__ uni_ref,
+                           const int16_t* __restrict__ pred_q, uint32_t* __restrict__ out_field, uint8_t* __restrict__ out_ref, uint8_t* __restrict__ out_dir,
+                           uint16_t* __restrict__ out_slot, uint32_t* __restrict__ out_cost, MeSelect a, MeDirRefsParams dirs, int n_refs_max, int pic_w,
+                           int pic_h, int n_ctu, int ctu_first, int ctu_count, uint32_t lambda_q16) {
+  constexpr int kOwn = (kParts + 63) / 64;   // slots per lane
+  __shared__ uint64_t s_cost[4][kParts + 3];
+  __shared__ uint32_t s_mv[4][kParts + 3];
+  __shared__ uint8_t s_dir[4][kParts + 3];
+  __shared__ uint8_t s_lref[4][2 * (kParts + 3)];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int c = blockIdx.x * 4 + wave, pic = blockIdx.y;
+  const bool live = c < ctu_count;   // wave-uniform
+  const int ctu = ctu_first + c;
+  if (live) {
+    const MeDirRefsBits& b = dirs.p[pic];
+    auto mvb = [](uint32_t m, int pred_x, int pred_y) -> uint32_t {   // HM's getBits at cost scale 0
+      return me_component_bits((int16_t)(m & 0xffffu) - pred_x) + me_component_bits((int16_t)(m >> 16) - pred_y);
+    };
+    auto gc = [&](uint32_t n) -> uint64_t { return (lambda_q16 * n) >> 16; };   // TComRdCost::getCost: the product wraps in 32 bits
+    auto dist = [&](uint32_t cost, uint32_t bits) -> uint64_t {
+      const uint64_t g = gc(bits);
+      return cost > g ? cost - g : 0;
+    };
+    // set (l, r) of the picture: its table row of this CTU, its predictor of this CTU (wave-uniform)
+    auto row = [&](int l, int r) -> long { return ((((long)pic * 2 + l) * n_refs_max + r) * ctu_count + c) * kParts; };
+    auto pred = [&](int l, int r, int& px, int& py) {
+      px = 0; py = 0;
+      if (pred_q) {
+        const int16_t* pq = pred_q + ((((long)pic * 2 + l) * n_refs_max + r) * n_ctu + ctu) * 2;
+        px = pq[0]; py = pq[1];
+      }
+    };
+#pragma unroll 1
+    for (int k = 0; k < kOwn; ++k) {
+      const int i = lane + 64 * k;
+      if (i >= kParts) continue;
+      uint64_t cu[2] = {0, 0}, cb[2] = {0, 0}, cv = 0;   // cv: list 1's direction-2 candidate
+      uint32_t mu[2] = {0, 0}, mb[2] = {0, 0}, mot[2] = {0, 0}, mvv = 0;
+      int ru[2] = {0, 0}, rb[2] = {0, 0}, rv = -1;   // rv < 0: no reference of the mask yet
+#pragma unroll
+      for (int l = 0; l < 2; ++l) {
+#pragma unroll 1
+        for (int r = 0; r < b.n_refs[l]; ++r) {
+          int px, py;
+          pred(l, r, px, py);
+          const long at = row(l, r) + i;
+          const uint32_t m = mv_uni[at], bits = mvb(m, px, py);
+          const uint64_t p = dist(cost_uni[at], bits) + gc(b.dir_bits[l] + b.ref_bits[l][r] + bits);
+          if (r == 0 || p < cu[l]) { cu[l] = p; mu[l] = m; ru[l] = r; mot[l] = b.ref_bits[l][r] + bits; }   // strict: the lower index wins ties
+          if (l == 1 && ((b.l1_valid_mask >> r) & 1u) && (rv < 0 || p < cv)) { cv = p; mvv = m; rv = r; }
+        }
+      }
+#pragma unroll
+      for (int l = 0; l < 2; ++l) {
+#pragma unroll 1
+        for (int r = 0; r < b.n_refs[l]; ++r) {
+          int px, py;
+          pred(l, r, px, py);
+          const long at = row(l, r) + i;
+          const uint32_t m = mv_bi[at], bits = mvb(m, px, py);
+          const uint64_t p = (dist(cost_bi[at], bits) >> 1) + gc(b.dir_bits[2] + b.ref_bits[l][r] + bits + mot[1 - l]);
+          if (r == 0 || p < cb[l]) { cb[l] = p; mb[l] = m; rb[l] = r; }
+        }
+      }
+      const int bl = cb[1] < cb[0] ? 1 : 0;   // strict: list 0 is tried first
+      const uint64_t cbi = cb[bl];
+      uint64_t best;
+      uint32_t m;
+      int d, r0 = 0xff, r1 = 0xff;
+      if (cbi <= cu[0] && (rv < 0 || cbi <= cv)) { best = cbi; m = mb[bl]; d = 3 | bl << 2; r0 = rb[0]; r1 = rb[1]; }
+      else if (rv < 0 || cu[0] <= cv) { best = cu[0]; m = mu[0]; d = 1; r0 = ru[0]; }
+      else { best = cv; m = mvv; d = 2; r1 = rv; }
+      s_cost[wave][i] = best;
+      s_mv[wave][i] = m;
+      s_dir[wave][i] = (uint8_t)d;
+      s_lref[wave][i] = (uint8_t)r0;
+      s_lref[wave][kParts + 3 + i] = (uint8_t)r1;
+    }
+  }
+  __syncthreads();
+  if (!live) return;
+  const int ctus_x = (pic_w + 63) >> 6;
+  const int ctu_x = (ctu % ctus_x) * 64, ctu_y = (ctu / ctus_x) * 64;
+  MeSelect merged = a;
+  merged.price_mv = 0;   // inside the merged cost already
+  const long lists = (long)n_ctu * 64, at = (long)pic * lists;   // the picture's two lists start at entry 2 * at; its CTU index is at / 64 + ctu
+  me_select_decide_store<true, uint64_t, true, true>(merged, s_cost[wave], s_mv[wave], s_dir[wave], lambda_q16, 0, 0, lane, ctu_x, ctu_y, (long)pic * n_ctu + ctu,
+                                                     pic_w, pic_h, out_field + at, out_dir, out_slot, out_cost, uni_field + at, lists, s_lref[wave],
+                                                     uni_ref + at, out_ref + at);
+}
+
 // ---- residual and per-PU / per-CU distortion of a prediction (hmme_residual_pairs_device; the rule: include/hmme.h) -----------------------
 // The slot layout read backwards: what me_slot_of<D> encodes, by the bases of its families.  Depth of the CU a slot belongs to:
 //   [0, 256) 2NxN / Nx2N of 8x8 CUs, [256, 384) AMP of 16x16, [384, 448) 2Nx2N 8x8, [448, 512) 2NxN / Nx2N 16x16, [512, 544) AMP 32x32,
@@ -2856,13 +2979,21 @@ me_residual_kernel(RefSet cur_blocks, RefSet preds, int pred_pitch, const uint16
 //            empty struct and compiles to what it did without the argument.
 //   WP = 1:  the same picture in a B slice with getWPBiPred() (hmme_predict_bi_w_device).  Direction 1 / 2: me_tail_weight_uni with that
 //            list's weight (uni[]); direction 3: me_tail_weight_bi.
+//   REFS = 1: a reference picture per block and list (hmme_predict_bi_refs_device; WP = 0 only): ref_field uint8 [2][n_ctu][mv_per_ctu]
+//            (list-major, like the MVs) names the plane of set[l] a block reads in list l (all of one pitch; ref0 / ref1 are not used).
+//            Both indices are wave-uniform like the direction, so the source bases are scalar choices, each clamped before the lookup.  A
+//            block that uses a list whose index is >= n[l] (0xFF: no CU) is like a block without a direction: it reads no plane and
+//            writes nothing.  The index of a list the direction does not name is not looked at.  REFS = 0 takes an empty struct and
+//            compiles to what it did without it.
 template <int WP> struct MePredBiWp {};
 template <> struct MePredBiWp<1> { int w0, w1, add, shift; MePredWp<1> uni[2]; };
-template <typename SrcT, int WP = 0>
+template <int REFS> struct MePredBiRefs {};
+template <> struct MePredBiRefs<1> { RefSet set[2]; const uint8_t* ref_field; int n[2]; };
+template <typename SrcT, int WP = 0, int REFS = 0>
 __global__ void __launch_bounds__(256)
 me_predict_bi_kernel(const uint8_t* __restrict__ ref0, const uint8_t* __restrict__ ref1, int ref_pitch, const int16_t* __restrict__ mv_field,
                      const uint8_t* __restrict__ dir_field, int mv_per_ctu, int n_ctu, int ctu_first, int pic_w, int pic_h, int bit_depth,
-                     uint8_t* __restrict__ dst, int dst_pitch, MePredBiWp<WP> wp) {
+                     uint8_t* __restrict__ dst, int dst_pitch, MePredBiWp<WP> wp, MePredBiRefs<REFS> refs) {
   __shared__ int16_t patch[4][15 * 16];
   __shared__ int16_t mid[4][15 * 8];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -2875,13 +3006,22 @@ me_predict_bi_kernel(const uint8_t* __restrict__ ref0, const uint8_t* __restrict
     const int b = it * 4 + wave, bx = (b & 7) * 8, by = (b >> 3) * 8;   // the four waves: four blocks side by side
     const long e = (long)ctu * mv_per_ctu + (mv_per_ctu == 1 ? 0 : b);
     const int dir = __builtin_amdgcn_readfirstlane((int)dir_field[e]);
-    const bool in_pic = cu_x + bx < pic_w && cu_y + by < pic_h && dir >= 1 && dir <= 3;   // wave-uniform
+    bool in_pic = cu_x + bx < pic_w && cu_y + by < pic_h && dir >= 1 && dir <= 3;   // wave-uniform
+    const uint8_t* origin0 = ref0;
+    const uint8_t* origin1 = ref1;
+    if constexpr (REFS) {
+      const int r0 = __builtin_amdgcn_readfirstlane((int)refs.ref_field[e]);
+      const int r1 = __builtin_amdgcn_readfirstlane((int)refs.ref_field[(long)n_ctu * mv_per_ctu + e]);
+      in_pic = in_pic && (!(dir & 1) || r0 < refs.n[0]) && (!(dir & 2) || r1 < refs.n[1]);
+      origin0 = refs.set[0].base[r0 < refs.n[0] ? r0 : 0];
+      origin1 = refs.set[1].base[r1 < refs.n[1] ? r1 : 0];
+    }
     const bool use0 = in_pic && (dir & 1), use1 = in_pic && (dir & 2);
     int mx0 = 0, my0 = 0, mx1 = 0, my1 = 0;
     if (use0) me_field_mv(mv_field, e, cu_x, cu_y, pic_w, pic_h, mx0, my0);
     if (use1) me_field_mv(mv_field, (long)n_ctu * mv_per_ctu + e, cu_x, cu_y, pic_w, pic_h, mx1, my1);
-    const int sum0 = me_predict_block_sum<SrcT>(use0, ref0, ref_pitch, cu_x + bx, cu_y + by, mx0, my0, patch[wave], mid[wave], lane, k);
-    const int sum1 = me_predict_block_sum<SrcT>(use1, ref1, ref_pitch, cu_x + bx, cu_y + by, mx1, my1, patch[wave], mid[wave], lane, k);
+    const int sum0 = me_predict_block_sum<SrcT>(use0, origin0, ref_pitch, cu_x + bx, cu_y + by, mx0, my0, patch[wave], mid[wave], lane, k);
+    const int sum1 = me_predict_block_sum<SrcT>(use1, origin1, ref_pitch, cu_x + bx, cu_y + by, mx1, my1, patch[wave], mid[wave], lane, k);
     if (in_pic) {
       int v;
       if constexpr (WP) {

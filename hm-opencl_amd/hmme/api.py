@@ -36,7 +36,10 @@ SYMBOLS = ["hmme_create", "hmme_destroy", "hmme_last_error", "hmme_device_info",
            "hmme_plane_stats", "hmme_wp_estimate", "hmme_wp_estimate_420",
            "hmme_predict_chroma_pairs_device", "hmme_predict_chroma_frame", "hmme_predict_chroma_refs_device", "hmme_predict_chroma_refs_frame",
            "hmme_predict_chroma_bi_device", "hmme_predict_chroma_bi_frame",
-           "hmme_residual_pairs_device", "hmme_residual_frame"]
+           "hmme_residual_pairs_device", "hmme_residual_frame",
+           "hmme_search_frame_bi_refs_device", "hmme_refine_frame_bi_refs_device", "hmme_search_frame_bi_refs", "hmme_refine_frame_bi_refs",
+           "hmme_select_dirs_refs_check", "hmme_select_dirs_refs_device", "hmme_select_dirs_refs_frame",
+           "hmme_predict_bi_refs_device", "hmme_predict_bi_refs_frame"]
 # test / measurement entry points (include/hmme_test.h): not part of the boundary
 TEST_SYMBOLS = ["hmme_test_time_search_kernel", "hmme_test_device_address", "hmme_test_frac_deal", "hmme_test_tail_plan", "hmme_test_stage_layout", "hmme_test_picture_job", "hmme_test_time_weight_passes", "hmme_test_time_bipred_origin",
                 "hmme_test_time_wp_estimate_passes"]
@@ -85,6 +88,21 @@ class DirParams(C.Structure):
 
     def __init__(self, dir_bits=(0, 0, 0), list_bits=(0, 0)):
         super().__init__((C.c_uint32 * 3)(*[int(v) for v in dir_bits]), (C.c_uint32 * 2)(*[int(v) for v in list_bits]))
+
+
+class DirRefsParams(C.Structure):
+    """hmme_dir_refs_params: the caller's bit counts of the L0 / L1 / bi decision of a B picture with several references per list (the rule:
+    include/hmme.h): dir_bits = HM's uiMbBits[3], n_refs = references of list 0 and list 1, ref_bits[l][r] = reference-index + MVP-index bits
+    of list l's reference r (up to 8 per list), l1_valid_mask: bit r set = list 1's reference r may win direction 2"""
+    _fields_ = [("dir_bits", C.c_uint32 * 3), ("n_refs", C.c_int * 2), ("ref_bits", (C.c_uint32 * 8) * 2), ("l1_valid_mask", C.c_uint32)]
+
+    def __init__(self, dir_bits=(0, 0, 0), n_refs=(1, 1), ref_bits=((), ()), l1_valid_mask=None):
+        rb = ((C.c_uint32 * 8) * 2)()
+        for l in range(2):
+            for r, v in enumerate(ref_bits[l]):
+                rb[l][r] = int(v)
+        mask = (1 << int(n_refs[1])) - 1 if l1_valid_mask is None else int(l1_valid_mask)
+        super().__init__((C.c_uint32 * 3)(*[int(v) for v in dir_bits]), (C.c_int * 2)(*[int(v) for v in n_refs]), rb, mask)
 
 
 class FrameParams(C.Structure):
@@ -211,7 +229,17 @@ def load():
     L.hmme_predict_chroma_bi_frame.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, i, C.POINTER(FrameParams), pw, pw, vp, vp, i, C.POINTER(vp), i]
     L.hmme_residual_pairs_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, i, C.POINTER(FrameParams), vp, i, i, C.POINTER(vp), i, vp, vp, vp, vp]
     L.hmme_residual_frame.argtypes = [vp, vp, C.POINTER(FrameParams), vp, i, vp, i, i, vp, i, vp, vp, vp]
-    L.hmme_plane_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    pvp, pfp = C.POINTER(vp), C.POINTER(FrameParams)
+    L.hmme_search_frame_bi_refs_device.argtypes = [vp, vp, pvp, i, pvp, i, pfp, vp, vp, i, vp, vp, vp, vp, vp]
+    L.hmme_refine_frame_bi_refs_device.argtypes = [vp, vp, pvp, i, pvp, i, pfp, vp, vp, i, vp, vp, vp, i, vp, vp, vp]
+    L.hmme_search_frame_bi_refs.argtypes = [vp, vp, pvp, i, pvp, i, pfp, vp, vp, i, vp, vp, vp, vp]
+    L.hmme_refine_frame_bi_refs.argtypes = [vp, vp, pvp, i, pvp, i, pfp, vp, vp, i, vp, vp, vp, i, vp, vp]
+    L.hmme_select_dirs_refs_check.argtypes = [C.POINTER(SelectParams), i, i, C.POINTER(DirRefsParams)]
+    L.hmme_select_dirs_refs_device.argtypes = [vp, i, i, i, i, pfp, C.POINTER(SelectParams), C.POINTER(DirRefsParams)] + [vp] * 13
+    L.hmme_select_dirs_refs_frame.argtypes = [vp, i, i, i, pfp, C.POINTER(SelectParams), C.POINTER(DirRefsParams)] + [vp] * 12
+    L.hmme_predict_bi_refs_device.argtypes = [vp, pvp, i, pvp, i, pfp, vp, vp, vp, i, vp, i, vp]
+    L.hmme_predict_bi_refs_frame.argtypes = [vp, pvp, i, pvp, i, pfp, vp, vp, vp, i, vp, i]
+    L.hmme_plane_stats.argtypes =[vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.hmme_wp_estimate.argtypes = [vp, vp, C.POINTER(vp), i, i, C.POINTER(Weight), C.POINTER(WpInfo)]
     L.hmme_wp_estimate_420.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, i, C.POINTER(Weight), C.POINTER(Weight), C.POINTER(WpInfo)]
     L.hmme_test_time_wp_estimate_passes.argtypes = [vp, vp, C.POINTER(vp), i, C.POINTER(Weight), vp, i, C.POINTER(C.c_float), C.POINTER(C.c_float)]
@@ -855,6 +883,125 @@ class Engine:
         self._check(self.L.hmme_predict_bi_frame(self.h, ref0.h, ref1.h, C.byref(fp), f.ctypes.data, df.ctypes.data, per, out.ctypes.data, out.shape[1]))
         return out
 
+    # ---- B pictures with several references per list (include/hmme.h, "B pictures with several references per list") ----
+    def search_frame_bi_refs_device(self, cur, refs, others, fp, d_other_mv, d_other_ref, mv_per_ctu, d_center, d_pred, d_mv, d_sad, stream=0):
+        """hmme_search_frame_bi_refs_device: the bi pass of one list over all its references `refs` against ONE origin, 2 * cur - the prediction
+        of `others` with a motion field and a reference index per block (d_other_ref uint8[n_ctu, mv_per_ctu]; an index >= len(others) reads
+        others[0]); tables [len(refs), count, 593, ...]"""
+        self._check(self.L.hmme_search_frame_bi_refs_device(self.h, cur.h, _handles(refs), len(refs), _handles(others), len(others), C.byref(fp), d_other_mv,
+                                                            d_other_ref, int(mv_per_ctu), d_center, d_pred, d_mv, d_sad, stream))
+
+    def refine_frame_bi_refs_device(self, cur, refs, others, fp, d_other_mv, d_other_ref, mv_per_ctu, d_center, d_pred, d_int_mv, use_hadamard, d_qmv, d_cost,
+                                    stream=0):
+        self._check(self.L.hmme_refine_frame_bi_refs_device(self.h, cur.h, _handles(refs), len(refs), _handles(others), len(others), C.byref(fp), d_other_mv,
+                                                            d_other_ref, int(mv_per_ctu), d_center, d_pred, d_int_mv, int(use_hadamard), d_qmv, d_cost, stream))
+
+    def _frame_bi_refs(self, entry, cur, refs, others, sr, fen, other_mv, other_ref, int_mv, center_q, pred_q, use_hadamard, ctu_first, ctu_count):
+        """the two *_frame_bi_refs methods; int_mv: None for a search -> the two result tables [len(refs), count, 593, ...]"""
+        n = self.L.hmme_num_ctus(cur.width, cur.height)
+        count = n - ctu_first if ctu_count < 0 else ctu_count
+        fp = FrameParams(sr, int(fen), cur.bit_depth, ctu_first, count)
+        f, per = self._field(other_mv, n)
+        rf = np.ascontiguousarray(other_ref, dtype=np.uint8).reshape(n, -1)
+        assert rf.shape == (n, per)
+        ptrs = []
+        keep = []
+        for a in (center_q, pred_q):
+            if a is None:
+                ptrs.append(None)
+                continue
+            a = np.ascontiguousarray(a, dtype=np.int16)
+            assert a.shape == (len(refs), n, 2)
+            keep.append(a)
+            ptrs.append(a.ctypes.data)
+        args = [f.ctypes.data, rf.ctypes.data, per] + ptrs
+        if int_mv is not None:
+            int_mv = np.ascontiguousarray(int_mv, dtype=np.int16)
+            assert int_mv.shape == (len(refs), count, NUM_PARTS, 2)
+            args += [int_mv.ctypes.data, int(use_hadamard)]
+        mv = np.zeros((len(refs), count, NUM_PARTS, 2), np.int16)
+        cost = np.zeros((len(refs), count, NUM_PARTS), np.uint32)
+        self._check(entry(self.h, cur.h, _handles(refs), len(refs), _handles(others), len(others), C.byref(fp), *args, mv.ctypes.data, cost.ctypes.data))
+        return mv, cost
+
+    def search_frame_bi_refs(self, cur, refs, others, sr, other_mv, other_ref, center_q=None, pred_q=None, fen=1, ctu_first=0, ctu_count=-1):
+        """hmme_search_frame_bi_refs: host arrays -> (mv int16[n_refs,count,593,2], sad uint32[n_refs,count,593]).  other_mv: the other list's
+        motion field (int16[n_ctu, 2] or [n_ctu, 1 | 64, 2]), other_ref: uint8[n_ctu] or [n_ctu, 1 | 64], the plane of `others` per block;
+        center_q / pred_q: int16[n_refs, n_ctu, 2] or None"""
+        return self._frame_bi_refs(self.L.hmme_search_frame_bi_refs, cur, refs, others, sr, fen, other_mv, other_ref, None, center_q, pred_q, True, ctu_first,
+                                   ctu_count)
+
+    def refine_frame_bi_refs(self, cur, refs, others, sr, other_mv, other_ref, int_mv, center_q=None, pred_q=None, use_hadamard=True, ctu_first=0, ctu_count=-1):
+        """hmme_refine_frame_bi_refs: the refinement of integer winners int16[n_refs,count,593,2] against that origin -> (qmv, cost)"""
+        return self._frame_bi_refs(self.L.hmme_refine_frame_bi_refs, cur, refs, others, sr, 1, other_mv, other_ref, int_mv, center_q, pred_q, use_hadamard,
+                                   ctu_first, ctu_count)
+
+    def select_dirs_refs_device(self, width, height, n_pics, n_refs_max, fp, sel, dirs, d_mv_uni, d_cost_uni, d_mv_bi, d_cost_bi, d_uni_field, d_uni_ref, d_pred,
+                                d_field, d_ref, d_dir, d_slot=None, d_ctu_cost=None, stream=0):
+        """hmme_select_dirs_refs_device: the refinement table sets of n_pics B pictures (device: uni and bi, each [n_pics, 2, n_refs_max, count, 593,
+        ...]), the lists' uni fields int16[n_pics, 2, n_ctu, 64, 2] and reference indices uint8[n_pics, 2, n_ctu, 64] -> motion field and reference
+        indices of those shapes, directions uint8[n_pics, n_ctu, 64], covering slots and CTU costs (d_slot / d_ctu_cost may be None).  dirs: one
+        DirRefsParams per picture"""
+        self._check(self.L.hmme_select_dirs_refs_device(self.h, int(width), int(height), int(n_pics), int(n_refs_max), C.byref(fp), C.byref(sel),
+                                                        _dir_refs_params(dirs, n_pics), d_mv_uni, d_cost_uni, d_mv_bi, d_cost_bi, d_uni_field, d_uni_ref, d_pred,
+                                                        d_field, d_ref, d_dir, d_slot, d_ctu_cost, stream))
+
+    def select_dirs_refs_frame(self, width, height, sel, dir_params, mv_uni, cost_uni, mv_bi, cost_bi, uni_field, uni_ref, pred_q=None, ctu_first=0, ctu_count=-1,
+                               field=None, ref=None, dirs=None, slot=None, ctu_cost=None):
+        """hmme_select_dirs_refs_frame: one picture, host arrays.  mv_uni / mv_bi int16[2, R, count, 593, 2], cost_uni / cost_bi uint32[2, R, count,
+        593], uni_field int16[2, n_ctu, 64, 2], uni_ref uint8[2, n_ctu, 64], pred_q int16[2, R, n_ctu, 2] or None -> (field int16[2, n_ctu, 64, 2],
+        ref uint8[2, n_ctu, 64], dirs uint8[n_ctu, 64], slot uint16[n_ctu, 64], ctu_cost uint32[n_ctu]); entries outside the CTU range keep the
+        values of the arrays passed in (zeros when none is)"""
+        n = self.L.hmme_num_ctus(width, height)
+        count = n - ctu_first if ctu_count < 0 else ctu_count
+        fp = FrameParams(1, 0, 8, ctu_first, count)
+        R = int(np.shape(mv_uni)[1])
+        tabs = []
+        for a, dt, tail in ((mv_uni, np.int16, (NUM_PARTS, 2)), (cost_uni, np.uint32, (NUM_PARTS,)), (mv_bi, np.int16, (NUM_PARTS, 2)),
+                            (cost_bi, np.uint32, (NUM_PARTS,))):
+            a = np.ascontiguousarray(a, dtype=dt)
+            assert a.shape == (2, R, count) + tail
+            tabs.append(a)
+        uf = np.ascontiguousarray(uni_field, dtype=np.int16)
+        ur = np.ascontiguousarray(uni_ref, dtype=np.uint8)
+        assert uf.shape == (2, n, 64, 2) and ur.shape == (2, n, 64)
+        pptr = None
+        if pred_q is not None:
+            pq = np.ascontiguousarray(pred_q, dtype=np.int16)
+            assert pq.shape == (2, R, n, 2)
+            pptr = pq.ctypes.data
+        outs = []
+        for a, dt, shape in ((field, np.int16, (2, n, 64, 2)), (ref, np.uint8, (2, n, 64)), (dirs, np.uint8, (n, 64)), (slot, np.uint16, (n, 64)),
+                             (ctu_cost, np.uint32, (n,))):
+            a = np.zeros(shape, dt) if a is None else a
+            assert a.dtype == dt and a.shape == shape and a.flags.c_contiguous
+            outs.append(a)
+        self._check(self.L.hmme_select_dirs_refs_frame(self.h, int(width), int(height), R, C.byref(fp), C.byref(sel), C.byref(dir_params), tabs[0].ctypes.data,
+                                                       tabs[1].ctypes.data, tabs[2].ctypes.data, tabs[3].ctypes.data, uf.ctypes.data, ur.ctypes.data, pptr,
+                                                       *[a.ctypes.data for a in outs]))
+        return tuple(outs)
+
+    def predict_bi_refs_device(self, refs0, refs1, fp, d_mv_field, d_dir_field, d_ref_field, mv_per_ctu, d_out, out_pitch_bytes, stream=0):
+        """hmme_predict_bi_refs_device: the luma prediction of one B picture, every block from refs0[ref0] (L0), refs1[ref1] (L1) or both (averaged
+        like TComYuv::addAvg): d_mv_field int16[2, n_ctu, mv_per_ctu, 2], d_dir_field uint8[n_ctu, mv_per_ctu], d_ref_field uint8[2, n_ctu,
+        mv_per_ctu]; d_out = the device image"""
+        self._check(self.L.hmme_predict_bi_refs_device(self.h, _handles(refs0), len(refs0), _handles(refs1), len(refs1), C.byref(fp), d_mv_field, d_dir_field,
+                                                       d_ref_field, int(mv_per_ctu), d_out, int(out_pitch_bytes), stream))
+
+    def predict_bi_refs_frame(self, refs0, refs1, mv_field, dir_field, ref_field, out=None, ctu_first=0, ctu_count=-1):
+        """hmme_predict_bi_refs_frame: the prediction of one B picture from list 0 (refs0) and list 1 (refs1) -> [height, width] array of the
+        planes' sample type.  mv_field: int16[2, n_ctu, 2] or [2, n_ctu, 1 | 64, 2] quarter pels; dir_field: uint8[n_ctu] or [n_ctu, 1 | 64];
+        ref_field: uint8[2, n_ctu] or [2, n_ctu, 1 | 64]; `out` keeps its samples outside the CTU range and in blocks without a direction or
+        with an index >= the list's length"""
+        r0 = refs0[0]
+        f, per, df, fp = self._predict_fields(r0, r0.width, r0.height, mv_field, dir_field, 2, ctu_first, ctu_count)
+        rf = np.ascontiguousarray(ref_field, dtype=np.uint8).reshape(2, df.shape[0], -1)
+        assert rf.shape == (2,) + df.shape
+        out = self._image(r0, out)
+        self._check(self.L.hmme_predict_bi_refs_frame(self.h, _handles(refs0), len(refs0), _handles(refs1), len(refs1), C.byref(fp), f.ctypes.data, df.ctypes.data,
+                                                      rf.ctypes.data, per, out.ctypes.data, out.shape[1]))
+        return out
+
     # ---- the final prediction in a WP slice (include/hmme.h, "the final prediction in a slice with explicit weighted prediction"): weights
     # are (w0, offset, shift, round)
     def predict_bi_w_device(self, refs0, refs1, fp, weights0, weights1, d_mv_field, d_dir_field, mv_per_ctu, d_outs, out_pitch_bytes, stream=0):
@@ -1106,6 +1253,27 @@ def select_dirs_check(sel, n_pics, dirs):
         for k, d in enumerate(dirs):
             a[k] = d
     return int(load().hmme_select_dirs_check(C.byref(sel), int(n_pics), a))
+
+
+def _dir_refs_params(dirs, n_pics):
+    """n_pics DirRefsParams as the array the hmme_select_dirs_refs_* calls take"""
+    assert len(dirs) == n_pics
+    a = (DirRefsParams * max(n_pics, 1))()
+    for k, d in enumerate(dirs):
+        a[k] = d
+    return a
+
+
+def select_dirs_refs_check(sel, n_pics, n_refs_max, dirs):
+    """hmme_select_dirs_refs_check: 0, or HMME_ERR_ARG for what select_dirs_check refuses, n_refs_max outside 1..8, an n_refs outside
+    1..n_refs_max, a bit count above 4096 or l1_valid_mask bits at or above n_refs[1] (pure host arithmetic: needs no GPU).  dirs: a sequence
+    of DirRefsParams (any length: n_pics of them are read) or None"""
+    a = None
+    if dirs is not None:
+        a = (DirRefsParams * max(len(dirs), 4))()
+        for k, d in enumerate(dirs):
+            a[k] = d
+    return int(load().hmme_select_dirs_refs_check(C.byref(sel), int(n_pics), int(n_refs_max), a))
 
 
 def ocl_compat_params(lt_x, lt_y, sr):

@@ -675,6 +675,113 @@ int hmme_predict_bi_device(hmme_ctx* ctx, const hmme_plane* const* refs0, const 
 int hmme_predict_bi_frame(hmme_ctx* ctx, const hmme_plane* ref0, const hmme_plane* ref1, const hmme_frame_params* fp, const int16_t* mv_field,
                           const uint8_t* dir_field, int mv_per_ctu, void* out, int out_stride);
 
+/* ---- B pictures with several references per list ---------------------------------------------------------------------------------
+ * The two sections above joined: a B picture with n0 / n1 references in list 0 / list 1, as HM's loop walks iRefIdxTemp in the uni pass
+ * (TEncSearch.cpp:3027-3094) and again inside the bi pass (:3208-3247), against the other list's best (MV, refIdx).  The pipeline:
+ *   1. hmme_search_frame_multi_device / hmme_refine_frame_multi_device, once per list;
+ *   2. hmme_select_refs_device with the two lists as its two "pictures": uni_field[2] and uni_ref[2];
+ *   3. hmme_search_frame_bi_refs_device / hmme_refine_frame_bi_refs_device, once per list: the bi pass of list l over all its references
+ *      against ONE origin, built from list 1-l's field and per-block reference indices;
+ *   4. hmme_select_dirs_refs_device: L0 / L1 / bi and the reference index per list, per PU, then the partition decision;
+ *   5. hmme_predict_bi_refs_device: the prediction from the two-list field, the direction field and the two reference-index fields;
+ *   6. hmme_residual_pairs_device.
+ * New entry points and one new struct; no struct and no existing entry point changed, so HMME_ABI_VERSION stays 6.
+ * THIS TEXT PLUS THE CITATIONS IS THE RULE.  Out of scope: the _w (explicit weighted prediction) forms of the three parts; the chroma form of the prediction;
+ * GPB_SIMPLE_UNI's copy of list-0 results into list 1; MvdL1ZeroFlag; HM's further bi iterations (hmme_select_dirs_device, too, takes each
+ * list's first iteration only).
+ *
+ * The bi pass.  hmme_search_frame_bi_refs_device is the bi-pass sibling of hmme_search_frame_multi_device: one current plane, refs[n_refs]
+ * the searched list (1..16 planes), others[n_others] the other list (1..16 planes), d_other_mv int16[n_ctu][mv_per_ctu][2] and d_other_ref
+ * uint8[n_ctu][mv_per_ctu] the other list's field and reference index per block (mv_per_ctu 1 | 64), d_center_q / d_pred_q
+ * int16[n_refs][n_ctu][2] or NULL as in hmme_search_pairs_bi_device, tables [n_refs][count][593].  For every reference r the result is what
+ * hmme_search_pairs_bi_device / hmme_refine_pairs_bi_device define for pair r = (cur, refs[r]) with ONE difference: the 8x8 block of the
+ * other list's prediction P is read from others[d_other_ref[block]] -- hmme_predict_refs_device's prediction; an index >= n_others is read
+ * as reference 0.  That covers the 0xFF hmme_select_refs_device writes for CUs that do not exist, whose blocks lie outside the picture and
+ * carry MV (0,0): with n_others == 1 the call equals the existing one on every field the select calls write.  The origin is built once
+ * per call and serves all n_refs references.  hmme_bipred_check runs first (refine = 1 in the refinement); every plane of refs and others
+ * must have cur's size and fp's bit depth and belong to the context, and is ordered like a reference; a NULL d_other_ref is HMME_ERR_ARG.
+ * NOTHING is launched or written on refusal.  hmme_search_frame_bi_refs / hmme_refine_frame_bi_refs: synchronous, host arrays of the same
+ * shapes.
+ *
+ * The decision.  Inputs for n_pics B pictures (1..4), R = n_refs_max in 1..8, all quarter-pel refinement tables of one ctu_first / ctu_count:
+ *   d_mv_uni, d_mv_bi    int16[n_pics][2][R][count][593][2]; d_cost_uni, d_cost_bi uint32[n_pics][2][R][count][593].  List l uses its first
+ *                        n_refs[l] sets; set [p][l][r] of the bi tables is what the bi pass above wrote for list l's reference r.
+ *   d_uni_field  int16[n_pics][2][n_ctu][64][2], d_uni_ref uint8[n_pics][2][n_ctu][64]: what hmme_select_refs_device wrote for the two lists
+ *                and what the bi pass of the opposite list consumed.
+ *   d_pred_q     int16[n_pics][2][R][n_ctu][2], or NULL for (0,0)
+ *   dirs         HOST array of n_pics hmme_dir_refs_params: dir_bits as in hmme_dir_params; n_refs[l] in 1..R; ref_bits[l][r] the caller's
+ *                model of the reference-index plus MVP-index bits of list l's reference r (hmme_ref_idx_bits gives HM's index part);
+ *                l1_valid_mask: bit r set = list 1's reference r may win direction 2 -- HM sets this where getList1IdxToList0Idx(r) < 0
+ *                (:3096-3104, :3282-3285).
+ *   sel          as hmme_select_dirs_check requires it: mv_per_ctu 64, mv_unit 0, price_mv 0.
+ * hmme_select_dirs_refs_check (a pure host function, run first; on failure the call launches NOTHING) returns HMME_ERR_ARG for anything
+ * hmme_select_dirs_check refuses, R outside 1..8, n_refs[l] outside 1..R, any bit count above 4096, or l1_valid_mask bits at or above
+ * n_refs[1].
+ * Rule, per slot s; mvb, gc, the clamp at 0 and the 64-bit sums as in the hmme_select_dirs_device text; pred[l][r] = the predictor of list
+ * l's reference r for the CTU:
+ *   1. For r < n_refs[l]:  bu[l][r] = mvb(mv_uni[l][r][s], pred[l][r])
+ *                          C[l][r]  = max(0, cost_uni[l][r][s] - gc(bu[l][r])) + gc(dir_bits[l] + ref_bits[l][r] + bu[l][r])
+ *      ru[l] = the first r with the smallest C[l][r]: strict < in the order 0, 1, ... (:3086).  C[l] = C[l][ru[l]].
+ *      mot[l] = ref_bits[l][ru[l]] + bu[l][ru[l]] (:3154-3155).
+ *   2. List 1's direction-2 candidate C_V is the same minimum taken only over the r of l1_valid_mask (rv its index).  With an empty mask
+ *      the candidate does not exist and direction 2 cannot win (HM's costValidList1 stays MAX_UINT).  mot[1] and the bi pass still use the
+ *      unrestricted ru[1], as HM's cMv[1] / iRefIdx[1] do until :3282.
+ *   3. For r < n_refs[l]:  bb[l][r]  = mvb(mv_bi[l][r][s], pred[l][r])
+ *                          C_B[l][r] = (max(0, cost_bi[l][r][s] - gc(bb[l][r])) >> 1) + gc(dir_bits[2] + ref_bits[l][r] + bb[l][r] + mot[1-l])
+ *      (:3210-3219, :3808).  rb[l] = the first strict minimum (:3226).  The bi candidate is list 0's unless list 1's is strictly cheaper.
+ *      As in hmme_select_dirs_device's rule 2 the other list's motion bits are those of its uni slot s.
+ *   4. C_bi <= C[0] and (C_V absent or C_bi <= C_V): direction 3; otherwise C_V absent or C[0] <= C_V: direction 1; otherwise direction 2
+ *      (:3291, :3314).  Then the decision of hmme_select_pairs_device, steps 1-5, runs on the winners with the MV cost switched off.
+ * Outputs -- only the entries of the CTUs in [ctu_first, ctu_first + ctu_count) are written:
+ *   d_out_field  int16[n_pics][2][n_ctu][64][2] and d_out_ref uint8[n_pics][2][n_ctu][64] (not NULL).  Under direction 1 or 2 the winner's
+ *                MV and reference (ru[0]; rv) in its list, (0,0) and 0xFF in the other.  Under direction 3 with the bi candidate having
+ *                searched list l: list l holds mv_bi[l][rb[l]][s] and rb[l], list 1-l THE BLOCK'S OWN ENTRIES of d_uni_field[1-l] and
+ *                d_uni_ref[1-l]: the motion the bi cost was measured with.  Blocks of CUs that do not exist: (0,0), 0xFF and 0xFF.
+ *   d_out_dir    uint8[n_pics][n_ctu][64]: 1, 2 or 3; 0xFF for blocks of CUs that do not exist; not NULL
+ *   d_out_slot   uint16[n_pics][n_ctu][64], may be NULL;  d_out_cost uint32[n_pics][n_ctu], saturated, may be NULL
+ * Buffers: tables, costs, the input field and slots 4-byte aligned, the output field 8-byte.  hmme_select_dirs_refs_frame: synchronous,
+ * host arrays of the same shapes with n_pics = 1; entries outside the CTU range keep their values.
+ *
+ * The prediction.  hmme_predict_bi_refs_device: ONE picture, like hmme_predict_refs_device: refs0[n0], refs1[n1] (each 1..16 planes),
+ * d_mv_field int16[2][n_ctu][mv_per_ctu][2], d_dir_field uint8[n_ctu][mv_per_ctu], d_ref_field uint8[2][n_ctu][mv_per_ctu], mv_per_ctu 1 | 64,
+ * one device image.  A block of direction 1 / 2 / 3 reads refs0[ref0] and / or refs1[ref1]; the result is what hmme_predict_bi_device
+ * defines for those planes: the uni tail, or addAvg.  A block whose direction is anything else, or which uses a list whose index is >= that
+ * list's count, is not written and reads no plane.  Plane checks and stream ordering are those of hmme_predict_refs_device, for both lists.
+ * hmme_predict_bi_refs_frame: synchronous, host fields and image (out_stride in samples). */
+typedef struct hmme_dir_refs_params {
+  uint32_t dir_bits[3];      /* uiMbBits: list 0, list 1, bi */
+  int n_refs[2];             /* references of list 0, list 1 */
+  uint32_t ref_bits[2][8];   /* reference-index + MVP-index bits of list l's reference r */
+  uint32_t l1_valid_mask;    /* bit r: list 1's reference r may win direction 2 */
+} hmme_dir_refs_params;
+int hmme_search_frame_bi_refs_device(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others,
+                                     int n_others, const hmme_frame_params* fp, const void* d_other_mv, const void* d_other_ref, int mv_per_ctu,
+                                     const void* d_center_q, const void* d_pred_q, void* d_out_mv, void* d_out_sad, void* stream);
+int hmme_refine_frame_bi_refs_device(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others,
+                                     int n_others, const hmme_frame_params* fp, const void* d_other_mv, const void* d_other_ref, int mv_per_ctu,
+                                     const void* d_center_q, const void* d_pred_q, const void* d_int_mv, int use_hadamard, void* d_out_qmv, void* d_out_cost,
+                                     void* stream);
+int hmme_search_frame_bi_refs(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
+                              const hmme_frame_params* fp, const int16_t* other_mv, const uint8_t* other_ref, int mv_per_ctu, const int16_t* center_q,
+                              const int16_t* pred_q, int16_t* out_mv, uint32_t* out_sad);
+int hmme_refine_frame_bi_refs(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
+                              const hmme_frame_params* fp, const int16_t* other_mv, const uint8_t* other_ref, int mv_per_ctu, const int16_t* center_q,
+                              const int16_t* pred_q, const int16_t* int_mv, int use_hadamard, int16_t* out_qmv, uint32_t* out_cost);
+int hmme_select_dirs_refs_check(const hmme_select_params* sel, int n_pics, int n_refs_max, const hmme_dir_refs_params* dirs);
+int hmme_select_dirs_refs_device(hmme_ctx* ctx, int width, int height, int n_pics, int n_refs_max, const hmme_frame_params* fp, const hmme_select_params* sel,
+                                 const hmme_dir_refs_params* dirs, const void* d_mv_uni, const void* d_cost_uni, const void* d_mv_bi, const void* d_cost_bi,
+                                 const void* d_uni_field, const void* d_uni_ref, const void* d_pred_q, void* d_out_field, void* d_out_ref, void* d_out_dir,
+                                 void* d_out_slot, void* d_out_cost, void* stream);
+int hmme_select_dirs_refs_frame(hmme_ctx* ctx, int width, int height, int n_refs_max, const hmme_frame_params* fp, const hmme_select_params* sel,
+                                const hmme_dir_refs_params* dir, const int16_t* mv_uni, const uint32_t* cost_uni, const int16_t* mv_bi, const uint32_t* cost_bi,
+                                const int16_t* uni_field, const uint8_t* uni_ref, const int16_t* pred_q, int16_t* out_field, uint8_t* out_ref, uint8_t* out_dir,
+                                uint16_t* out_slot, uint32_t* out_cost);
+int hmme_predict_bi_refs_device(hmme_ctx* ctx, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, const hmme_frame_params* fp,
+                                const void* d_mv_field, const void* d_dir_field, const void* d_ref_field, int mv_per_ctu, void* d_out, int out_pitch_bytes,
+                                void* stream);
+int hmme_predict_bi_refs_frame(hmme_ctx* ctx, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, const hmme_frame_params* fp,
+                               const int16_t* mv_field, const uint8_t* dir_field, const uint8_t* ref_field, int mv_per_ctu, void* out, int out_stride);
+
 /* ---- the final prediction in a slice with explicit weighted prediction ---------------------------------------------------------
  * hmme_predict_bi_device and hmme_predict_refs_device with explicit weights: the prediction that belongs to the decisions of
  * hmme_select_dirs_device / hmme_select_refs_device when the searches before them were the *_w and *_bi_w_* calls.  New entry points only; no
