@@ -11,6 +11,10 @@ stores go only to samples inside -- and none of it assumes a multiple of anythin
     9 x 9         the minimum plus one: a single CTU whose blocks at x = 8 and y = 8 hold one sample
     16384 x 8,    the largest a plane accepts: 256 CTUs in a row / in a column
     8 x 16384
+    (128 + 2k)    for k = 1..15, 4:2:0: chroma planes of (64 + k) x 9 -- every partial vector and dword of the plane-set kernels -- next to a
+      x 18        luma plane that ends 2k samples past a vector boundary in the same launch
+    2048 x 50     4:2:0 with 16 references at 8 bit: 51 planes side by side cap a launch at 20 row blocks per plane, luma has 25 (two rounds:
+                  the strided row loop iterates twice) and chroma 7 (its workgroups beyond block 6 leave at once); stat_grid below shows it
 
 Host arithmetic only; the window rule is restated here from TEncSearch::xSetSearchRange and TComDataCU::clipMv in Python integers."""
 import numpy as np
@@ -24,6 +28,9 @@ LAST_CTU = {ODD: (37, 7), NARROW: (1, 3), EVEN: (2, 2), MIN1: (9, 9)}    # width
 PLANE_MIN, PLANE_MAX = 8, 16384
 REFUSED_PLANES = ((7, 8), (8, 7), (16385, 8), (8, 16385))
 STATS_SIZES = tuple((64 + k, 9) for k in range(1, 16))                    # rows that end 1..15 samples into a 16-sample vector
+STATS_SIZES_420 = tuple((128 + 2 * k, 18) for k in range(1, 16))           # luma; chroma (64 + k) x 9: STATS_SIZES, luma 2k samples past a vector boundary
+STAT_BLOCKS = 1024                                                        # kWpStatBlocks of hmme.hip
+ROUNDS_420 = (2048, 50, 16)                                               # luma width, height, references of the 8-bit case whose luma rows take two rounds
 FAR = 4 * 400                                                             # quarter pels: beyond clipMv's range at every size but the slivers' long side
 DIRECTIONS = ((-1, -1), (0, -1), (1, -1), (-1, 0), (1, 0), (-1, 1), (0, 1), (1, 1))
 FUZZ_SEEDS = tuple(range(3000, 3010))
@@ -67,6 +74,29 @@ def window(pred_x, pred_y, sr, cu_x, cu_y, w, h):
 def is_clipped(win, sr):
     """a window narrower or lower than the 2 * sr + 1 candidates of an unclipped one"""
     return win[2] - win[0] < 2 * sr or win[3] - win[1] < 2 * sr
+
+
+def stat_grid(width, height, sample_bytes, n_y, stat_blocks=STAT_BLOCKS):
+    """stat_grid of hmme.hip restated: the launch geometry of a reduction over a width x height plane, n_y planes (or pairs) side by side in
+    one launch whose workgroups are capped at stat_blocks -> dict(lpr_log2, rows_per_block, row_blocks, cap, rounds, blocks): 16-byte vectors
+    per row -> lanes per row (a power of two, 256 at most) -> rows per workgroup; the row blocks dealt evenly over the rounds the cap needs"""
+    nvec = (width * sample_bytes + 15) // 16
+    l = 0
+    while (1 << l) < nvec and l < 8:
+        l += 1
+    rpb = 256 >> l
+    row_blocks = (height + rpb - 1) // rpb
+    cap = max(1, stat_blocks // n_y)
+    rounds = (row_blocks + cap - 1) // cap
+    return dict(lpr_log2=l, rows_per_block=rpb, row_blocks=row_blocks, cap=cap, rounds=rounds, blocks=(row_blocks + rounds - 1) // rounds)
+
+
+def stat_grids_420(w, h, sample_bytes, n_refs, stat_blocks=STAT_BLOCKS):
+    """the two set launches of hmme_wp_estimate_420 on a w x h luma picture with n_refs references, every plane distinct: the statistics of
+    3 * (n_refs + 1) planes, the SADs of 3 * n_refs pairs -> {"stats" | "sad": (luma's grid, chroma's grid)}; a launch's x extent is the larger
+    `blocks` of the two, and a workgroup whose first row block * rows_per_block lies beyond its plane's height leaves at once"""
+    return {name: (stat_grid(w, h, sample_bytes, n_y, stat_blocks), stat_grid(w // 2, h // 2, sample_bytes, n_y, stat_blocks))
+            for name, n_y in (("stats", 3 * (n_refs + 1)), ("sad", 3 * n_refs))}
 
 
 def predictors(w, h, seed, max_pel=5):

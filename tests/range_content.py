@@ -4,6 +4,7 @@ tests/test_gpu_range_edges.py.  Plain numpy, no GPU.
   boundary_weights(bd, refine)   the accepted weight nearest to each refusal, found by walking one parameter of a weight family until
                                  api.weight_check flips (a pure host function of libhmme.so); nothing here is a hard-coded bound
   extreme_pair / extreme_triple  pictures of samples in {0, maxv} that make a block reach the sample differences the rule admits
+  extreme_lists                  the same for the bi pass over several references: every plane of the other list flat where the origin peaks
   ramp_pair                      a reference that holds every sample value
   sad_w, pred_qpel               int64 restatements of the weighted SAD and of the two-stage luma interpolation
 """
@@ -226,6 +227,30 @@ def extreme_triple(w, h, bd, seed):
         noise = _binary(rng, y1 - y0, x1 - x0, maxv)
         cur[y0:y1, x0:x1] = np.where(rng.integers(0, 16, size=moved.shape) == 0, noise, moved)
     return synth.pad_plane(cur), synth.pad_plane(ref), synth.pad_plane(other)
+
+
+def extreme_lists(w, h, bd, seed, n_refs=2, n_others=2, band=32):
+    """-> (cur, [refs], [others]) padded int16 planes for the bi pass over several references.  refs: binary patterns of the same scene, each
+    displaced as a whole.  others: independent binary patterns, ALL flat maxv over the first `band` columns and FLAT_REACH beyond, all flat 0
+    over the last `band` columns and FLAT_REACH before them, over the whole height: whichever plane a block's index names and whatever its
+    MV of up to 6 pels, the prediction there is flat.  cur: 0 over the first band and maxv over the last -- origins of -maxv and 2 * maxv --,
+    elsewhere refs[0]'s scene with one sample in 16 replaced by binary noise"""
+    from hmme import synth
+    maxv = (1 << bd) - 1
+    assert w >= 2 * (band + FLAT_REACH) + 16
+    rng = np.random.default_rng(seed)
+    scene = np.pad(_binary(rng, h, w, maxv), 8, mode="edge")
+    refs = [scene[8 + dy:8 + dy + h, 8 + dx:8 + dx + w] for dx, dy in [(0, 0), (2, -1), (-1, 2), (-2, -2)][:n_refs]]
+    others = []
+    for _ in range(n_others):
+        o = _binary(rng, h, w, maxv)
+        o[:, :band + FLAT_REACH] = maxv
+        o[:, w - band - FLAT_REACH:] = 0
+        others.append(o)
+    cur = np.where(rng.integers(0, 16, size=(h, w)) == 0, _binary(rng, h, w, maxv), refs[0])
+    cur[:, :band] = 0
+    cur[:, w - band:] = maxv
+    return synth.pad_plane(cur), [synth.pad_plane(r) for r in refs], [synth.pad_plane(o) for o in others]
 
 
 def ramp_pair(w, h, bd, seed):

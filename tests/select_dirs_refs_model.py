@@ -106,6 +106,130 @@ def select_dirs_refs_picture(mv_uni, cost_uni, mv_bi, cost_bi, uni_field, uni_re
     return field, ref, dirs, np.stack(slots), np.array(costs, np.uint32)
 
 
+# ---- hand-made tables: one slot, and the ties of rules 1-4 (tests/test_select_dirs_refs_cpu.py on the model, tests/test_gpu_select_dirs_refs.py on the device) ----
+NO_BI = 0xFFFFFFFF
+Z = (0, 0)                                                 # mvb((0,0), (0,0)) = 2 bits: gc 2 at lambda 1 per bit
+TIE_MVS = ((4, 0), (0, 4), (-4, 0), (0, -4))               # MVs of equal bit count (8 against the zero predictor), told apart in the field
+TIE_MASK = 0b110                                           # list 1's reference 0 -- its cheapest in every scenario -- is not allowed for direction 2
+TIE_LAMBDA_Q16 = 1 << 16                                   # 1 per bit: gc(a + b) = gc(a) + gc(b)
+FAR = 1 << 22                                              # the priced cost of everything that must not win
+
+
+def slot_of_lists(mu, cu, mb, cb, bits, lq=1 << 16, pred=None):
+    """slot_decide on lists of per-reference (mv, cost) with the zero predictor"""
+    R = max(len(mu[0]), len(mu[1]))
+    pad = lambda a, fill: [list(a[l]) + [fill] * (R - len(a[l])) for l in range(2)]
+    p = [[(0, 0)] * R, [(0, 0)] * R] if pred is None else pred
+    return slot_decide(pad(mu, (0, 0)), pad(cu, 0), pad(mb, (0, 0)), pad(cb, 0), p, bits, lq)
+
+
+def tie_bits(mask):
+    """the bit counts the tie scenarios are run with, on the model and on the device: HM-like and all zero"""
+    return [hm_bits(3, 3, mask), Bits((0, 0, 0), (3, 3), ([0] * 3, [0] * 3), mask)]
+
+
+def tie_scenarios():
+    """name -> (mask, C[0], C[1], C_B[0], C_B[1], (direction, searched list of the bi candidate, reference of the winner in its list)): the
+    PRICED costs of three references per list -- what rules 1 and 3 compare, whatever the bit counts -- and what the rule in include/hmme.h
+    makes of them (for directions 1 and 2 the searched list is not part of the statement).  tie_mv gives every candidate its MV"""
+    M, far = TIE_MASK, [FAR] * 3
+    l1 = [4000, FAR, FAR]                                  # list 1's cheapest is reference 0: outside the mask, it never wins direction 2
+    return {
+        # rule 1: the first of equal uni costs, a strictly cheaper later one
+        "uni tie, the first wins":                  (M, [5000, 5000, 5000], l1, far, far, (1, 0, 0)),
+        "a later uni reference strictly cheaper":   (M, [5000, 4999, 4999], l1, far, far, (1, 0, 1)),
+        # rule 2: the same among the references of the mask
+        "masked uni tie, the first wins":           (M, far, [4000, 5000, 5000], far, far, (2, 0, 1)),
+        "a later masked reference strictly cheaper": (M, far, [4000, 5000, 4999], far, far, (2, 0, 2)),
+        # rule 4, second part: list 0 wins a tie against the masked list-1 candidate
+        "masked list 1 equals list 0":              (M, [5000, 6000, 6000], [4000, 5000, 6000], far, far, (1, 0, 0)),
+        "masked list 1 strictly cheaper":           (M, [5000, 6000, 6000], [4000, 6000, 4999], far, far, (2, 0, 2)),
+        # rule 3: the first of equal bi costs per list; list 0's unless list 1's is strictly cheaper
+        "bi tie in list 0, the first wins":         (M, far, l1, [5000, 5000, 5000], [6000, 6000, 6000], (3, 0, 0)),
+        "a later bi reference of list 0 strictly cheaper": (M, far, l1, [5000, 4999, 4999], [6000, 6000, 6000], (3, 0, 1)),
+        "bi tie in list 1, the first wins":         (M, far, l1, [6000, 6000, 6000], [5000, 5000, 5000], (3, 1, 0)),
+        "a later bi reference of list 1 strictly cheaper": (M, far, l1, [6000, 6000, 6000], [5000, 5000, 4999], (3, 1, 2)),
+        "list 1's bi equals list 0's":              (M, far, l1, [5000, 5500, 5500], [5500, 5000, 5500], (3, 0, 0)),
+        "list 1's bi strictly cheaper":             (M, far, l1, [5000, 5500, 5500], [5500, 4999, 5500], (3, 1, 1)),
+        # rule 4, first part: bi wins ties against both lists
+        "bi equals both uni":                       (M, [5000, 6000, 6000], [4000, 5000, 6000], [5500, 5000, 5500], far, (3, 0, 1)),
+        "bi equals list 0, list 1 one below":       (M, [5000, 6000, 6000], [4000, 6000, 4999], [5000, 5500, 5500], far, (2, 0, 2)),
+        "bi equals list 1, list 0 one below":       (M, [6000, 4999, 6000], [4000, 5000, 6000], [5000, 5500, 5500], far, (1, 0, 1)),
+        "bi equals list 0, whose winner is its last reference": (M, [6000, 6000, 5000], l1, [5000, 5500, 5500], far, (3, 0, 0)),   # priced with mot[1], not mot[0]
+        "bi one above both uni":                   (M, [5000, 6000, 6000], [4000, 5000, 6000], far, [5500, 5500, 5001], (1, 0, 0)),
+        # an empty mask: direction 2 never wins, and bi is compared with list 0 alone
+        "empty mask, list 1 far cheaper":           (0, [5000, 5000, 6000], [100, 200, 300], far, far, (1, 0, 0)),
+        "empty mask, bi equals list 0":             (0, [6000, 5000, 6000], [100, 200, 300], far, [5500, 5000, 5000], (3, 1, 1)),
+        "empty mask, bi one above list 0":          (0, [6000, 5000, 5000], [100, 200, 300], [5001, 5001, 5500], far, (1, 0, 1)),
+    }
+
+
+def tie_mv(bi, l, r):
+    """the MV of reference r of list l in the uni (bi = 0) or bi set: the three references of a set carry three different MVs of one bit
+    count, and a list's bi set another rotation of them than its uni set"""
+    return TIE_MVS[(r + 2 * bi + l) % 4]
+
+
+def tie_slot_tables(c, c1, cb0, cb1, bits, lambda_q16=TIE_LAMBDA_Q16):
+    """the table entries (mu, cu, mb, cb as slot_decide takes them, zero predictor) whose priced costs under `bits` are the given ones: the
+    bit prices rule 1 and rule 3 add are taken off again, the bi distortion doubled -- mot[] of the unrestricted uni winners included"""
+    gc, mvb = dm.gc, dm.mvb
+    cs, cbs = (c, c1), (cb0, cb1)
+    mu = [[tie_mv(0, l, r) for r in range(3)] for l in range(2)]
+    mb = [[tie_mv(1, l, r) for r in range(3)] for l in range(2)]
+    cu, cb, mot = [[0] * 3, [0] * 3], [[0] * 3, [0] * 3], [0, 0]
+    for l in range(2):
+        for r in range(3):
+            bu = mvb(mu[l][r], Z)
+            cu[l][r] = cs[l][r] - gc(lambda_q16, bits.dir_bits[l] + bits.ref_bits[l][r] + bu) + gc(lambda_q16, bu)
+        ru = cs[l].index(min(cs[l]))                       # the first strict minimum
+        mot[l] = bits.ref_bits[l][ru] + mvb(mu[l][ru], Z)
+    for l in range(2):
+        for r in range(3):
+            bb = mvb(mb[l][r], Z)
+            cb[l][r] = 2 * (cbs[l][r] - gc(lambda_q16, bits.dir_bits[2] + bits.ref_bits[l][r] + bb + mot[1 - l])) + gc(lambda_q16, bb)
+    assert all(gc(lambda_q16, 16) <= v <= NO_BI for l in range(2) for v in cu[l] + cb[l])
+    return mu, cu, mb, cb
+
+
+def tie_want(bits_mask, scenario):
+    """(direction, searched list, the winner's MV, (ref index list 0, list 1) as slot_decide states them) of a scenario"""
+    mask, _, _, _, _, (d, bl, r) = scenario
+    assert mask == bits_mask
+    refs = [NO_REF, NO_REF]
+    l = bl if d == 3 else d - 1
+    refs[l] = r
+    return d, bl, tie_mv(int(d == 3), l, r), tuple(refs)
+
+
+def tie_sites():
+    """[(slot, depth)]: the 2Nx2N slots of CUs that tile a 64x64 CTU at three depths -- one 32x32 CU, eight 16x16 CUs (two quadrants) and
+    sixteen 8x8 CUs (one quadrant) -- for a scenario each; every other slot of the CTU is priced at FAR, so that the partition decision
+    codes exactly these CUs and every scenario stays visible in the field"""
+    from hmme import api
+    cus = [(1, 0, 0)] + [(2, 32 + 16 * i, 16 * j) for j in range(2) for i in range(2)] + [(2, 32 + 16 * i, 32 + 16 * j) for j in range(2) for i in range(2)]
+    cus += [(3, 8 * i, 32 + 8 * j) for j in range(4) for i in range(4)]
+    return [(api.slot_index(0, d, 0, sm.z_index(x, y)), d) for d, x, y in cus]
+
+
+def tie_tables(bits, seed=0, lambda_q16=TIE_LAMBDA_Q16):
+    """one CTU whose sites (tie_sites) hold the scenarios of bits.l1_valid_mask in turn: the first nine in the 32x32 and the 16x16 CUs, the
+    others and -- the sites being more than the scenarios -- the first ones again in 8x8 CUs -> ((mv_uni, cost_uni, mv_bi, cost_bi [2, 3, 1, 593, ...], uni_field [2, 1, 64, 2], uni_ref [2, 1, 64]), {slot: scenario name})"""
+    names = [k for k, v in tie_scenarios().items() if v[0] == bits.l1_valid_mask]
+    sites = tie_sites()
+    mv_uni, mv_bi = np.zeros((2, 3, 1, 593, 2), np.int16), np.zeros((2, 3, 1, 593, 2), np.int16)
+    cost_uni, cost_bi = np.zeros((2, 3, 1, 593), np.uint32), np.zeros((2, 3, 1, 593), np.uint32)
+    filler = tie_slot_tables([FAR] * 3, [FAR] * 3, [FAR] * 3, [FAR] * 3, bits, lambda_q16)
+    placed = {s: names[k % len(names)] for k, (s, d) in enumerate(sites)}   # more sites than scenarios: the first ones come again in 8x8 CUs
+    for s in range(593):
+        mu, cu, mb, cb = tie_slot_tables(*tie_scenarios()[placed[s]][1:5], bits, lambda_q16) if s in placed else filler
+        mv_uni[:, :, 0, s], cost_uni[:, :, 0, s], mv_bi[:, :, 0, s], cost_bi[:, :, 0, s] = mu, cu, mb, cb
+    rng = np.random.default_rng(seed + 9)
+    uni_field = rng.integers(-300, 301, size=(2, 1, 64, 2)).astype(np.int16)
+    uni_ref = rng.integers(0, 3, size=(2, 1, 64)).astype(np.uint8)
+    return (mv_uni, cost_uni, mv_bi, cost_bi, uni_field, uni_ref), placed
+
+
 # ---- table recipes -------------------------------------------------------------------------------------------------------------------------
 def predictors(R, n_ctu, seed):
     """int16[2, R, n_ctu, 2], drawn independently per list, reference and CTU, no component zero"""

@@ -33,6 +33,33 @@ def test_the_table_says_what_the_sizes_are():
     assert sum(1 for w, h in sizes if w % 2 or h % 2) >= 5 and sum(1 for w, h in sizes if w % 8 or h % 8) >= 8
 
 
+def test_the_plane_set_launches_take_the_rounds_the_cases_claim():
+    """geometry_cases.stat_grid restates stat_grid of hmme.hip: the 2048 x 50 case with 16 references needs two rounds for luma in both set
+    launches while chroma's workgroups beyond its seventh row block leave; every size of tests/test_gpu_wp_estimate_420.py and the row-tail
+    sizes need one"""
+    import os
+    import re
+    from conftest import ROOT
+    src = open(os.path.join(ROOT, "hm-opencl_amd", "csrc", "hmme.hip")).read()
+    assert int(re.search(r"constexpr int kWpStatBlocks = (\d+);", src).group(1)) == gc.STAT_BLOCKS
+    assert "cap = std::max(1, kWpStatBlocks / n_y)" in src and "rounds = (row_blocks + cap - 1) / cap" in src
+    w, h, n_refs = gc.ROUNDS_420
+    for name, grids in gc.stat_grids_420(w, h, 1, n_refs).items():
+        luma, chroma = grids
+        assert (luma["lpr_log2"], luma["rows_per_block"], luma["row_blocks"], luma["rounds"], luma["blocks"]) == (7, 2, 25, 2, 13), name
+        assert luma["cap"] == (20 if name == "stats" else 21) and luma["row_blocks"] > luma["cap"]
+        assert luma["blocks"] * luma["rows_per_block"] < h                       # a second iteration of the row loop has rows to read
+        assert (chroma["lpr_log2"], chroma["rows_per_block"], chroma["row_blocks"], chroma["rounds"], chroma["blocks"]) == (6, 4, 7, 1, 7), name
+        assert chroma["blocks"] < luma["blocks"] and chroma["blocks"] * chroma["rows_per_block"] >= h // 2   # workgroups 7..12 of a chroma plane: no row
+    # one round everywhere else: the family's own sizes with the most references each is run with, and the row tails
+    from_family = [(16, 16, 2), (32, 16, 16), (48, 18, 4), (130, 66, 3), (8200, 16, 2), (512, 128, 1), (128, 128, 1)]
+    for w, h, n_refs in from_family + [s + (1,) for s in gc.STATS_SIZES_420]:
+        for bytes_ in (1, 2):
+            assert all(g["rounds"] == 1 for grids in gc.stat_grids_420(w, h, bytes_, n_refs).values() for g in grids), (w, h, n_refs)
+    assert sorted({(w // 2) % 16 for w, _ in gc.STATS_SIZES_420}) == list(range(1, 16)) and all(h == 18 and w % 16 == 2 * k % 16
+                                                                                                  for k, (w, h) in enumerate(gc.STATS_SIZES_420, 1))
+
+
 def test_windows_are_clipped_as_the_table_states(api, oracle_lib):
     hmo = oracle_lib.oracle()
     win = [C.c_int() for _ in range(4)]

@@ -87,15 +87,15 @@ def select_refs_field(engine, cur_plane, other_planes, w, h):
     return field, ref
 
 
-def check_against_the_per_ctu_calls(engine, hmo, w, h, bd, pics, refs_i, others_i, field, ref_field, seed, fen=1, had=True, ctus=None):
+def check_against_the_per_ctu_calls(engine, hmo, w, h, bd, pics, refs_i, others_i, field, ref_field, seed, fen=1, had=True, ctus=None, sr=SR_BI):
     """both calls over the references pics[refs_i] against pics[others_i] with the given field -> the four tables, checked on `ctus`"""
     n_ctu = dims(w, h)[0] * dims(w, h)[1]
     planes = [mkplane(engine, p, w, h, bd) for p in pics]
     try:
         refs, others = [planes[i] for i in refs_i], [planes[i] for i in others_i]
         pred, center = predictors(len(refs), n_ctu, seed), predictors(len(refs), n_ctu, seed + 50)
-        mv, sad = engine.search_frame_bi_refs(planes[0], refs, others, SR_BI, field, ref_field, center_q=center, pred_q=pred, fen=fen)
-        qmv, cost = engine.refine_frame_bi_refs(planes[0], refs, others, SR_BI, field, ref_field, mv, center_q=center, pred_q=pred, use_hadamard=had)
+        mv, sad = engine.search_frame_bi_refs(planes[0], refs, others, sr, field, ref_field, center_q=center, pred_q=pred, fen=fen)
+        qmv, cost = engine.refine_frame_bi_refs(planes[0], refs, others, sr, field, ref_field, mv, center_q=center, pred_q=pred, use_hadamard=had)
         f3 = field.reshape(n_ctu, -1, 2)
         rf = np.asarray(ref_field).reshape(n_ctu, -1)
         p_full = refs_prediction(hmo, [pics[i] for i in others_i], w, h, bd, f3, rf)
@@ -110,9 +110,9 @@ def check_against_the_per_ctu_calls(engine, hmo, w, h, bd, pics, refs_i, others_
         org = origin_picture(pics[0], p_full, w, h)
         for r, i in enumerate(refs_i):
             todo = range(n_ctu) if ctus is None else ctus
-            smv, ssad = per_ctu(engine, org, pics[i], w, h, bd, SR_BI, center[r], pred[r], fen, todo)
+            smv, ssad = per_ctu(engine, org, pics[i], w, h, bd, sr, center[r], pred[r], fen, todo)
             assert np.array_equal(mv[r][list(todo)], smv) and np.array_equal(sad[r][list(todo)], ssad), ("search", r)
-            sq, sc = per_ctu(engine, org, pics[i], w, h, bd, SR_BI, center[r], pred[r], fen, todo, mv[r][list(todo)], had)
+            sq, sc = per_ctu(engine, org, pics[i], w, h, bd, sr, center[r], pred[r], fen, todo, mv[r][list(todo)], had)
             assert np.array_equal(qmv[r][list(todo)], sq) and np.array_equal(cost[r][list(todo)], sc), ("refine", r)
         return mv, sad, qmv, cost
     finally:

@@ -895,6 +895,180 @@ def test_host_staging_at_a_size_where_no_item_is_a_multiple_of_the_alignment(bd)
         close(ctx, planes)
 
 
+# ---- d': B pictures with several references per list, and the 4:2:0 estimate --------------------------------------------------------------
+def more(g, bd, name, k):
+    """a plane slot with a picture of a second scene of the geometry: the other list of the bi-refs calls"""
+    w, h = GEOM[g]
+    return (f"{g}{bd}.{name}", (w, h, bd, SEED[g] + bd + 500, k))
+
+
+def ref_field_of(g, per):
+    """reference indices 0 / 1 that change from block to block (one MV per CTU: from CTU to CTU)"""
+    b, c = np.arange(per), np.arange(n_ctu(g))[:, None]
+    return (((b % 8) + (b // 8) + c) % 2).astype(np.uint8)
+
+
+def bi_refs(g, bd, sr, had=True, center=None, pred=None, per=64, refk=1, swap=False):
+    """search_frame_bi_refs and refine_frame_bi_refs of its winners: the references are the slots "ref" and "other" of the older calls (refk:
+    the picture the first one holds), the other list two slots of its own (swap: their pictures exchanged) -> (mv, sad, qmv, cost)"""
+    names = [pl(g, bd, "cur", 0), pl(g, bd, "ref", refk), pl(g, bd, "other", 2), more(g, bd, "o0", int(swap)), more(g, bd, "o1", 1 - int(swap))]
+
+    def run(eng, P):
+        f, rf = field_of(g, per, 13), ref_field_of(g, per)
+        pq, cq = preds(g, pred, (2,)), preds(g, center, (2,))
+        mv, sad = eng.search_frame_bi_refs(P[0], P[1:3], P[3:], sr, f, rf, center_q=cq, pred_q=pq, fen=1)
+        return (mv, sad) + eng.refine_frame_bi_refs(P[0], P[1:3], P[3:], sr, f, rf, mv, center_q=cq, pred_q=pq, use_hadamard=had)
+    return Step(f"bi_refs {g} {bd}b sr{sr} had{had} centre{center} pred{pred} per{per} ref{refk} swap{swap}", names, run,
+                kind="bi_refs", g=g, bd=bd, sr=sr, had=int(had), center=center, pred=pred, per=per, refk=refk, swap=swap)
+
+
+def spot_bi_refs(oracle_lib, hmo, step, got, seed=3):
+    """the four tables of a bi_refs step against the oracle on the origin built here (tests/bipred_refs_bands.refs_prediction)"""
+    from bipred_refs_bands import refs_prediction
+    from hmme import synth
+    i, m = step.info, synth.MARGIN
+    g, bd, sr = i["g"], i["bd"], i["sr"]
+    w, h = GEOM[g]
+    ctus = spot_ctus(n_ctu(g), seed)
+    lq = lambda_q16(step.lam)
+    cur, refs = content(cid(g, bd, 0)), [content(cid(g, bd, i["refk"])), content(cid(g, bd, 2))]
+    others = [content(more(g, bd, "o", k)[1]) for k in ((1, 0) if i["swap"] else (0, 1))]
+    org = fh.origin_picture(cur, refs_prediction(hmo, others, w, h, bd, field_of(g, i["per"], 13), ref_field_of(g, i["per"])), w, h)
+    pq, cq = preds(g, i["pred"], (2,)), preds(g, i["center"], (2,))
+    mv, sad, qmv, cost = got
+    for r in range(2):
+        omv, osad = fh.oracle_bi_search(oracle_lib, org, refs[r], w, h, sr, None if cq is None else cq[r], None if pq is None else pq[r], lq, 1, bd, ctus)
+        assert np.array_equal(mv[r][ctus], omv) and np.array_equal(sad[r][ctus], osad), f"[{step.label}] reference {r} on the used context differs from the oracle"
+        for c in ctus:
+            oq, oc = oracle_lib.refine_frame(np.ascontiguousarray(np.pad(org, m)), refs[r], (m, m), w, h, mv[r][c:c + 1], None if pq is None else pq[r], lq, i["had"], bd,
+                                             ctu_first=c, ctu_count=1)
+            assert np.array_equal(qmv[r][c], oq[0]) and np.array_equal(cost[r][c], oc[0]), f"[{step.label}] reference {r} CTU {c} on the used context differs from the oracle"
+
+
+def planes_420(g, bd, cb=2):
+    """the nine planes of a 4:2:0 estimate with two references: the luma slots of the older calls and chroma slots c<picture><component>;
+    cb: the picture reference 0's Cb slot holds (another one = the plane is re-uploaded)"""
+    chroma = lambda k, c, j: pl(g, bd, f"c{k}{c}", j, half=True)
+    return [pl(g, bd, "cur", 0), chroma(0, 0, 0), chroma(0, 1, 1), pl(g, bd, "ref", 1), chroma(1, 0, cb), chroma(1, 1, 3), pl(g, bd, "other", 2), chroma(2, 0, 4), chroma(2, 1, 5)]
+
+
+def wp420(g, bd, cb=2):
+    def run(eng, P):
+        wl, wc, infos = eng.wp_estimate_420(P[:3], [P[3:6], P[6:9]])
+        return np.array(wl, np.int64), np.array(wc, np.int64), np.array([[i.as_dict()[k] for k in wem.INFO_FIELDS] for i in infos], np.int64)
+    return Step(f"wp_estimate_420 {g} {bd}b cb{cb}", planes_420(g, bd, cb), run, kind="wp420", g=g, bd=bd, cb=cb)
+
+
+def spot_wp420(step, got):
+    import wp_estimate_420_model as model
+    from hmme import synth
+    m = synth.MARGIN
+    area = lambda c: content(c)[m:m + c[1], m:m + c[0]].astype(np.int64)
+    pics = [area(c) for _, c in step.planes]
+    want = model.estimate(tuple(pics[:3]), [tuple(pics[3:6]), tuple(pics[6:9])], step.info["bd"])
+    flat = [e for r in want for e in r]
+    assert [tuple(int(v) for v in r) for r in got[0]] == [tuple(r[0]["wp"]) for r in want], f"[{step.label}] luma weights differ from wp_estimate_420_model"
+    assert [tuple(int(v) for v in r) for r in got[1]] == [tuple(e["wp"]) for r in want for e in r[1:]], f"[{step.label}] chroma weights differ from wp_estimate_420_model"
+    assert [[int(v) for v in r] for r in got[2]] == [[int(e[k]) for k in wem.INFO_FIELDS] for e in flat], f"[{step.label}] statistics differ from wp_estimate_420_model"
+
+
+@functools.lru_cache(maxsize=None)
+def refs_inputs(g, count=-1):
+    """what select_dirs_refs and predict_bi_refs of one picture size are fed (drawn once, read-only): two references per list; count: the
+    tables of the first `count` CTUs only"""
+    import select_dirs_refs_model as drm
+    n = n_ctu(g)
+    rng = np.random.default_rng(SEED[g] + 30)
+    pred = drm.predictors(2, n, SEED[g] + 31)
+    d = dict(pred=pred, tables=drm.random_tables(2, n, n if count < 0 else count, SEED[g] + 32, pred, 0, lambda_q16()),
+             field2=np.ascontiguousarray(np.stack([fh.random_field(n, 64, SEED[g] + 33), fh.random_field(n, 64, SEED[g] + 34)])),
+             dirs64=rng.choice(np.array([1, 2, 3, 3, 0xFF], np.uint8), size=(n, 64)),
+             refs64=rng.integers(0, 3, size=(2, n, 64)).astype(np.uint8))       # index 2 of two references: blocks that are not written
+    for v in d.values():
+        for a in (v if isinstance(v, tuple) else (v,)):
+            a.setflags(write=False)
+    return d
+
+
+def dirs_refs(g):
+    import select_dirs_refs_model as drm
+
+    def run(eng, P):
+        from hmme import api
+        d, b = refs_inputs(g), drm.hm_bits(2, 2, 0b10)
+        return eng.select_dirs_refs_frame(*GEOM[g], api.SelectParams(64), api.DirRefsParams(b.dir_bits, b.n_refs, b.ref_bits, b.l1_valid_mask), *d["tables"], d["pred"])
+    return Step(f"select_dirs_refs_frame {g}", [], run, kind="dirs_refs", g=g)
+
+
+def spot_dirs_refs(step, got):
+    import select_dirs_refs_model as drm
+    from hmme import api
+    g = step.info["g"]
+    d, t = refs_inputs(g), refs_inputs(g)["tables"]
+    for c in spot_ctus(n_ctu(g), 7)[:4]:                                       # (the model takes 593 slots x references per CTU in Python)
+        f, r, dr, s, cc = drm.select_dirs_refs_picture(*[a[:, :, c:c + 1] for a in t[:4]], t[4], t[5], api.SelectParams(64), *GEOM[g], drm.hm_bits(2, 2, 0b10), c, d["pred"],
+                                                       lambda_q16())
+        assert np.array_equal(got[0][:, c], f[:, 0]) and np.array_equal(got[1][:, c], r[:, 0]) and np.array_equal(got[2][c], dr[0]) and np.array_equal(got[3][c], s[0]) \
+            and got[4][c] == cc[0], f"[{step.label}] CTU {c} on the used context differs from select_dirs_refs_model"
+
+
+def predict_bi_refs(g, bd, refk=1):
+    names = [pl(g, bd, "ref", refk), pl(g, bd, "other", 2), more(g, bd, "o0", 0), more(g, bd, "o1", 1)]
+
+    def run(eng, P):
+        d = refs_inputs(g)
+        return (eng.predict_bi_refs_frame(P[:2], P[2:], d["field2"], d["dirs64"], d["refs64"]),)
+    return Step(f"predict_bi_refs_frame {g} {bd}b ref{refk}", names, run, kind="predict_bi_refs", g=g, bd=bd, refk=refk)
+
+
+def spot_predict_bi_refs(hmo, step, got):
+    import predict_bi_refs_model as pbrm
+    g, bd = step.info["g"], step.info["bd"]
+    w, h = GEOM[g]
+    d, ctus = refs_inputs(g), spot_ctus(n_ctu(g), 7)
+    pics = [content(c) for _, c in step.planes]
+    want = pbrm.pred_picture(hmo, pics[:2], pics[2:], w, h, bd, d["field2"], d["dirs64"], d["refs64"], np.zeros((h, w), np.int64), ctus)   # the wrapper hands the engine zeros
+    for c in ctus:
+        x, y = fh.ctu_origin(c, w)
+        assert np.array_equal(got[0][y:y + 64, x:x + 64], want[y:y + 64, x:x + 64]), f"[{step.label}] CTU {c} on the used context differs from predict_bi_refs_model"
+
+
+def test_b_pictures_with_several_references_between_the_older_calls(used, oracle_lib, hmo):
+    """hmme_search / refine_frame_bi_refs share the scratch kWp0..kWp3 (through ensure), the CopyCache entries keyed by plane and bias and the
+    job tables (FracTable::kAlways) with the weighted and bi calls; hmme_wp_estimate_420 shares kWpEst and the per-plane sums with
+    hmme_wp_estimate and hmme_plane_stats; hmme_select_dirs_refs_frame and hmme_predict_bi_refs_frame the staging arena with every host form"""
+    st = staging_calls("S")
+    S = [
+        # 1. two references after a weighted search of a larger geometry, then after one of a smaller: scratch sized by another call
+        weighted("M", 8, 16), bi_refs("S", 8, 8), bi_refs("S", 8, 8), weighted("T", 8, 8), bi_refs("S", 8, 8), refine("M", 8, 16, "w2"), bi_refs("S", 8, 8, pred=101),
+        # 2. the same call with one reference plane re-uploaded in between, then one plane of the other list: the copies keyed by plane and bias
+        bi_refs("S", 8, 8), bi_refs("S", 8, 8, refk=2), bi_refs("S", 8, 8, refk=2), bi_refs("S", 8, 8), bi_refs("S", 8, 8, swap=True), bi_refs("S", 8, 8),
+        refine("S", 8, 8, "bi"), bi_refs("S", 8, 8), refine("S", 8, 8, "bi_w"), bi_refs("S", 8, 8, center=102, pred=103, per=1),
+        # 3. after a plain refinement without predictors, and before one: the job-table tags
+        refine("S", 8, 8, "plain"), bi_refs("S", 8, 8), refine("S", 8, 8, "plain"), bi_refs("S", 8, 8, had=False), refine("S", 8, 8, "plain", had=False),
+        # 4. 8 bit, then 10 bit of the same size (kWp2 serves 8 bit only), and back
+        bi_refs("S", 8, 8), bi_refs("S", 10, 8), bi_refs("S", 10, 8), bi_refs("S", 8, 8), bi_refs("S", 10, 8, center=104, pred=105),
+        # 5. the 4:2:0 estimate after the luma estimate, the plane statistics and a weighted search, and again after a chroma plane was re-uploaded
+        st["wp_estimate"], st["plane_stats"], weighted("S", 8, 16), wp420("S", 8), wp420("S", 8), wp420("S", 8, cb=6), wp420("S", 8), st["wp_estimate"], st["plane_stats"],
+        wp420("S", 10), bi_refs("S", 8, 8), wp420("S", 8, cb=6),
+        # 6. the decision and the prediction between launches of other families
+        dirs_refs("S"), st["select_dirs_frame"], dirs_refs("S"), bi_refs("S", 8, 8), predict_bi_refs("S", 8), st["predict_bi_frame"], predict_bi_refs("S", 8),
+        predict_bi_refs("S", 8, refk=2), predict_bi_refs("S", 10), dirs_refs("T"), predict_bi_refs("T", 8), weighted("S", 8, 16), dirs_refs("S"), predict_bi_refs("S", 8),
+    ]
+    outs = run_sequence(used, S, "d'")
+    by = {s.label: o for s, o in zip(S, outs)}
+    # the results do follow the re-uploaded planes (the transitions are real ones)
+    assert not np.array_equal(by[bi_refs("S", 8, 8).label][1][0], by[bi_refs("S", 8, 8, refk=2).label][1][0])
+    assert not np.array_equal(by[bi_refs("S", 8, 8).label][1], by[bi_refs("S", 8, 8, swap=True).label][1])
+    assert not np.array_equal(by[wp420("S", 8).label][2], by[wp420("S", 8, cb=6).label][2])
+    assert not np.array_equal(by[predict_bi_refs("S", 8).label][0], by[predict_bi_refs("S", 8, refk=2).label][0])
+    for want in (dict(bd=8, had=1, pred=None, center=None, refk=1, swap=False), dict(bd=10, center=104)):
+        spot_bi_refs(oracle_lib, hmo, *last_of(S, outs, "bi_refs", **want))
+    spot_wp420(*last_of(S, outs, "wp420", cb=6))
+    spot_dirs_refs(*last_of(S, outs, "dirs_refs", g="S"))
+    spot_predict_bi_refs(hmo, *last_of(S, outs, "predict_bi_refs", g="S", bd=8, refk=1))
+
+
 # ---- e: streams ----------------------------------------------------------------------------------------------------------------------------
 def test_streams_share_tables_scratch_and_the_event_ring(used, oracle_lib, hmo):
     """scratch_acquire / launch_end, the table tags that carry the stream, and the planes' fill and read events (plane_wait,
@@ -938,6 +1112,35 @@ def test_streams_share_tables_scratch_and_the_event_ring(used, oracle_lib, hmo):
         want[refk, "long"] = fresh_result(st)
         spot_search(oracle_lib, hmo, st, want[refk, "long"], seed=9, stride=4)   # (an oracle CTU at range 64 costs 0.13 s: three or four of them)
     assert not np.array_equal(want[1, 0][1], want[2, 0][1]) and not np.array_equal(want[1, "long"][1], want[2, "long"][1])   # the refills do change the results
+    # beside four of the launches, on the stream the launch does NOT use: the decision of a B picture with two references per list over the
+    # first six CTUs and its prediction from the current and the reference plane (hmme_select_dirs_refs_device, hmme_predict_bi_refs_device);
+    # they are no launches of the count above and take entries of the event ring of their own
+    import select_dirs_refs_model as drm
+    bd_in, bits = refs_inputs(g, 6), drm.hm_bits(2, 2, 0b10)
+    b_fp, b_sel, b_dirs = api.FrameParams(1, 0, 8, 0, 6), api.SelectParams(64), [api.DirRefsParams(bits.dir_bits, bits.n_refs, bits.ref_bits, bits.l1_valid_mask)]
+    to_dev = lambda a: torch.from_numpy(np.array(a).view(np.int32) if a.dtype == np.uint32 else np.array(a)).to(dev)   # (copies: the inputs are read-only)
+
+    def b_inputs():
+        return [to_dev(a) for a in bd_in["tables"]] + [to_dev(bd_in[k]) for k in ("pred", "field2", "dirs64", "refs64")]
+
+    def b_outputs():
+        return [torch.zeros((2, n, 64, 2), dtype=torch.int16, device=dev), torch.zeros((2, n, 64), dtype=torch.uint8, device=dev), torch.zeros((n, 64), dtype=torch.uint8, device=dev),
+                torch.zeros((n, 64), dtype=torch.int16, device=dev), torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros((h, w), dtype=torch.uint8, device=dev)]
+
+    def b_launch(e, cur, ref, d_in, d_out, s):
+        t, (d_pred, d_f2, d_dirs, d_refs) = d_in[:6], d_in[6:]
+        e.select_dirs_refs_device(w, h, 1, 2, b_fp, b_sel, b_dirs, *[x.data_ptr() for x in t], d_pred.data_ptr(), *[x.data_ptr() for x in d_out[:5]], s)
+        e.predict_bi_refs_device([cur, ref], [ref, cur], api.FrameParams(1, 0, bd, 0, n), d_f2.data_ptr(), d_dirs.data_ptr(), d_refs.data_ptr(), 64, d_out[5].data_ptr(), w, s)
+
+    def b_fresh(e, P):
+        d_in, d_out = b_inputs(), b_outputs()
+        torch.cuda.synchronize()
+        b_launch(e, P[0], P[1], d_in, d_out, 0)
+        torch.cuda.synchronize()
+        return [x.cpu().numpy() for x in d_out]
+    b_want = {refk: fresh_result(Step(f"streams {g} {bd}b b-picture ref{refk}", [pl(g, bd, "cur", 0), pl(g, bd, "ref", refk)], b_fresh, kind="b_picture")) for refk in (1, 2)}
+    assert b_want[1][2][:6].any() and not b_want[1][2][6:].any() and b_want[1][5].any() and not np.array_equal(b_want[1][5], b_want[2][5])
+    b_at = {10: None, 40: None, 72: None, 78: None}                            # launch -> (the picture the reference plane held, the outputs)
     eng = used.eng
     eng.set_lambda(LAMBDA)
     pc, pr, pi = used.plane(*pl(g, bd, "cur", 0)), used.plane(*pl(g, bd, "ref", 1)), used.plane(*pl(g, bd, "idle", 1))
@@ -953,6 +1156,9 @@ def test_streams_share_tables_scratch_and_the_event_ring(used, oracle_lib, hmo):
     long_readers, idle_reads = (36, 74), (0, 71)
     holds, plane_of = {"ref": 1, "idle": 1}, {"ref": pr, "idle": pi}
     outs = [fh.device_tables(1, n, dev) for _ in range(n_launches)]
+    b_in = b_inputs()
+    for k in b_at:
+        b_at[k] = [None, b_outputs()]
     torch.cuda.synchronize()
     launched, j = [], 0
     try:
@@ -981,6 +1187,9 @@ def test_streams_share_tables_scratch_and_the_event_ring(used, oracle_lib, hmo):
                 else:
                     eng.refine_pairs_device([pc], [pr], fp, None, d_imv[refk, wk].data_ptr(), 1, a.data_ptr(), b.data_ptr(), s)
             launched.append((form, wk, refk, k % 2))
+            if k in b_at:
+                b_at[k][0] = holds["ref"]
+                b_launch(eng, pc, pr, b_in, b_at[k][1], streams[(k + 1) % 2].cuda_stream)
         torch.cuda.synchronize()
         eng.upload_status(third.cuda_stream)
     finally:
@@ -996,3 +1205,7 @@ def test_streams_share_tables_scratch_and_the_event_ring(used, oracle_lib, hmo):
         ref_out = want[refk, wk][2:] if form == "refine" else want[refk, wk][:2]
         assert np.array_equal(mv, ref_out[0]) and np.array_equal(cost, ref_out[1]), \
             f"launch {k} ({form}, weighted {wk}, stream {st_}, reference picture {refk}) differs from the fresh context's"
+    assert [b_at[k][0] for k in sorted(b_at)] == [1, 2, 2, 1]
+    for k, (refk, d_out) in b_at.items():
+        for j, (a, b) in enumerate(zip(d_out, b_want[refk])):
+            assert np.array_equal(a.cpu().numpy(), b), f"the B picture beside launch {k} (reference picture {refk}): output {j} differs from the fresh context's"

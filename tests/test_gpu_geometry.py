@@ -267,6 +267,46 @@ def test_weighted_bi_search_and_refinement(engine, oracle_lib, hmo, size, bd):
     assert not np.array_equal(r["org"], bwm.origin(r["cur"], unweighted, w, h))     # the other list's weight acts on the origin
 
 
+@pytest.mark.parametrize("size,bd,per", [(gc.ODD, 8, 64), (gc.ODD, 10, 64), (gc.NARROW, 8, 64), (gc.NARROW, 10, 64), (gc.ODD, 8, 1), (gc.MIN1, 8, 64)],
+                         ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_bi_search_and_refinement_over_several_references(engine, hmo, size, bd, per):
+    """hmme_search / refine_frame_bi_refs: two references in the searched list against two planes of DIFFERENT content in the other list, whose
+    index changes from 8x8 block to 8x8 block -- the blocks that straddle the picture edge read different planes -- every CTU against the
+    per-CTU calls on the origin; 9 x 9 with one reference"""
+    from test_gpu_bipred_refs import check_against_the_per_ctu_calls, checkerboard, unrelated
+    w, h = size
+    n = gc.n_ctus(w, h)
+    n_refs = 1 if size == gc.MIN1 else 2
+    engine.set_lambda(57.9)
+    pics = pictures(w, h, bd, seed=4550 + w + bd + per, n=n_refs) + unrelated(w, h, bd, 4560 + w + bd, 2)
+    field = fh.random_field(n, per, 4570 + w + bd)
+    ref_field = checkerboard(n, per, 2, w)
+    assert set(ref_field.reshape(-1).tolist()) == ({0, 1} if per == 64 or n > 1 else {0})
+    if per == 64:                                                                   # the blocks that begin inside the picture and end beyond it name both planes
+        straddle = set()
+        for c in range(n):
+            x0, y0 = gc.ctu_origin(c, w)
+            straddle |= {int(ref_field[c, b]) for b in range(64) if x0 + (b % 8) * 8 < w and y0 + (b // 8) * 8 < h
+                         and (x0 + (b % 8) * 8 + 8 > w or y0 + (b // 8) * 8 + 8 > h)}
+        assert straddle == {0, 1}
+    refs_i, others_i = list(range(1, 1 + n_refs)), [1 + n_refs, 2 + n_refs]
+    for had in ((True, False) if size == gc.NARROW else (True,)):
+        mv, sad, qmv, cost = check_against_the_per_ctu_calls(engine, hmo, w, h, bd, pics, refs_i, others_i, field, ref_field, 4580 + w, fen=int(bd == 8), had=had,
+                                                             sr=gc.SEARCH_RANGE[size])
+    assert mv.shape == (n_refs, n, 593, 2) and (n_refs == 1 or not np.array_equal(mv[0], mv[1]))
+    # the index matters at the edge: the last CTU read from plane 0 alone gives another table
+    planes = [fh.mkplane(engine, p, w, h, bd) for p in pics]
+    try:
+        flat, _ = engine.search_frame_bi_refs(planes[0], [planes[i] for i in refs_i], [planes[i] for i in others_i], gc.SEARCH_RANGE[size], field, np.zeros_like(ref_field),
+                                              fen=int(bd == 8), ctu_first=n - 1, ctu_count=1)
+        again, _ = engine.search_frame_bi_refs(planes[0], [planes[i] for i in refs_i], [planes[i] for i in others_i], gc.SEARCH_RANGE[size], field, ref_field,
+                                               fen=int(bd == 8), ctu_first=n - 1, ctu_count=1)
+        assert not np.array_equal(flat, again)
+    finally:
+        for p in planes:
+            p.close()
+
+
 # ---- 4: decisions --------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("size", [gc.ODD, gc.NARROW, gc.MIN1])
 def test_decisions(engine, mv_cost, size):
@@ -325,6 +365,35 @@ def test_decisions(engine, mv_cost, size):
         assert (want[2] == sm.NO_SLOT).any() and ((want[1] == sdm.NO_DIR) == (want[2] == sm.NO_SLOT)).all()
         assert n == 1 or len(set(want[1][want[2] != sm.NO_SLOT].tolist())) >= 2
         assert max_depth != 1 or gc.straddling_leaves(want[2], w, h, 64) >= 1
+
+
+@pytest.mark.parametrize("size", [gc.ODD, gc.NARROW, gc.MIN1])
+def test_direction_and_reference_decision(engine, size):
+    """hmme_select_dirs_refs_device, two references per list and list 1's reference 0 masked out, against select_dirs_refs_model: blocks of
+    CUs whose origin lies outside the picture carry no direction and no reference; a CU at the picture edge is decided bi"""
+    import select_dirs_refs_model as drm
+    from hmme import api
+    from test_gpu_select_dirs_refs import compare, one_picture
+    w, h = size
+    n = gc.n_ctus(w, h)
+    engine.set_lambda_q16(drm.LAMBDA_Q16)
+    pred = drm.predictors(2, n, seed=4650 + w)
+    tabs = one_picture(2, w, h, 4651 + w, pred)
+    edge_bi = 0
+    for max_depth in (3, 1):
+        sel = api.SelectParams(64, max_depth=max_depth, cu_cost=40, pu_cost=12)
+        mf, mr, md, ms, _ = compare(engine, w, h, tabs, sel, [drm.hm_bits(2, 2, 0b10)], pred[None])
+        gone = ms[0] == sm.NO_SLOT
+        assert gone.any() and (md[0][gone] == drm.NO_DIR).all() and (mr[0][:, gone] == drm.NO_REF).all() and (mf[0][:, gone] == 0).all()
+        assert (md[0][~gone] != drm.NO_DIR).all() and 0 not in set(mr[0, 1][md[0] == 2].tolist())
+        for c in range(n):
+            x0, y0 = gc.ctu_origin(c, w)
+            for v in np.unique(ms[0, c][~gone[c]]):
+                _, (qx, qy, qs) = rm.slot_geometry(int(v))
+                at_edge = x0 + qx < w <= x0 + qx + qs or y0 + qy < h <= y0 + qy + qs
+                edge_bi += int(at_edge and (md[0, c][ms[0, c] == v] == 3).all())
+        assert max_depth != 1 or gc.straddling_leaves(ms[0], w, h, 64) >= 1
+    assert edge_bi >= 1
 
 
 # ---- 5: luma prediction --------------------------------------------------------------------------------------------------------------------------
@@ -437,6 +506,54 @@ def test_luma_prediction(engine, hmo, size, bd, per):
             want = np.where(inside, models[name], fill)
             assert np.array_equal(got[:, :w], want), ("device", name, per, np.argwhere(got[:, :w] != want)[:4])
             assert (got[:, w:] == fill).all()
+    finally:
+        for p in planes:
+            p.close()
+
+
+@pytest.mark.parametrize("bd", BDS)
+@pytest.mark.parametrize("size", [gc.ODD, gc.NARROW, gc.EVEN])
+def test_luma_prediction_of_a_b_picture_with_several_references(engine, hmo, size, bd):
+    """hmme_predict_bi_refs_frame with two planes per list against predict_bi_refs_model, into images whose stride exceeds the width: one MV
+    per block with all three directions and every plane named; one far MV per CTU in each of the eight directions, every CTU bi from another
+    pair of planes, so that a block averages the replicated borders of two different planes"""
+    import predict_bi_refs_model as pbrm
+    from hmme import api
+    from test_gpu_predict_bi_refs import inputs, textures
+    w, h = size
+    n, L = gc.n_ctus(w, h), engine.L
+    dt, fill = sentinel(bd)
+    pics = textures(w, h, bd, 4750 + w + bd, 4)
+    planes = [fh.mkplane(engine, a, w, h, bd) for a in pics]
+    try:
+        h0, h1 = api._handles(planes[:2]), api._handles(planes[2:])
+        new = lambda: np.full((h, w), fill, np.int64)
+
+        def run(field, dirs, refs, per, what):
+            f, d, r = (np.ascontiguousarray(a) for a in (field, dirs, refs))
+            model = pbrm.pred_picture(hmo, pics[:2], pics[2:], w, h, bd, f, d, r, new())
+            check_image_forms(w, h, bd, lambda fp, out, s: L.hmme_predict_bi_refs_frame(engine.h, h0, 2, h1, 2, C.byref(fp), f.ctypes.data, d.ctypes.data, r.ctypes.data,
+                                                                                         per, out, s), model, what)
+            return model
+
+        field, dirs, refs = inputs(w, h, 64, 4751 + w + bd, 2, 2)
+        model = run(field, dirs, refs, 64, "blocks")
+        live = [(c, b) for c in range(n) for b in range(64) if dirs[c, b] in (1, 2, 3) and gc.ctu_origin(c, w)[0] + (b % 8) * 8 < w and gc.ctu_origin(c, w)[1] + (b // 8) * 8 < h
+                and all(not (dirs[c, b] >> l) & 1 or refs[l, c, b] < 2 for l in range(2))]
+        assert {int(dirs[c, b]) for c, b in live} == {1, 2, 3} and (model == fill).any()
+        assert all({int(refs[l, c, b]) for c, b in live if (dirs[c, b] >> l) & 1} == {0, 1} for l in range(2))
+        # the border: list 0 and list 1 far away in the same direction, the pair of planes changing from CTU to CTU
+        c = np.arange(n)
+        far_refs = np.stack([c % 2, (c // 2 + 1) % 2]).astype(np.uint8).reshape(2, n, 1)
+        far_dirs = np.full((n, 1), 3, np.uint8)
+        seen = set()
+        for k, f in enumerate(gc.far_fields(w, h)):
+            both = np.stack([f, f + np.array([3, 2], np.int16)])                  # another phase in list 1
+            model = run(both, far_dirs, far_refs, 1, ("far", k))
+            alone = [pbrm.pred_picture(hmo, pics[:2], pics[2:], w, h, bd, both, np.full((n, 1), l + 1, np.uint8), far_refs, new()) for l in range(2)]
+            assert not np.array_equal(alone[0], alone[1]) and not np.array_equal(model, alone[0]) and not np.array_equal(model, alone[1])
+            seen.add(model.tobytes())
+        assert len(seen) == 8 and (n == 1 or len(set(map(tuple, far_refs[:, :, 0].T.tolist()))) >= 2)
     finally:
         for p in planes:
             p.close()
@@ -604,6 +721,45 @@ def test_wp_estimate_on_a_fade(engine, w, h, bd):
     cur = fade(ref, 0.75, 20, bd)
     want = check_estimate(engine, cur, [ref, other], bd)                            # every sum, intermediate and weight against the model
     assert want[0]["present"] == 1 and want[0]["weight"] != 1 << want[0]["log2_denom"] and want[0]["sad_wp"] < want[0]["sad_nowp"]
+
+
+@pytest.mark.parametrize("bd", [8, 10, 12])
+def test_wp_estimate_420_at_every_row_tail(engine, bd):
+    """the plane-set kernels' own masked last vector: luma (128 + 2k) x 18 for k = 1..15 puts chroma at (64 + k) x 9 -- every partial vector,
+    every partial dword -- while luma ends 2k samples past a vector boundary in the same launch; the last column of every plane at the
+    nominal maximum, as in test_plane_stats_at_every_row_tail.  Every sum, intermediate and weight against the model"""
+    from test_gpu_wp_estimate import fade
+    from test_gpu_wp_estimate_420 import check, picture
+    top = (1 << bd) - 1
+    for w, h in gc.STATS_SIZES_420:
+        ref = picture(w, h, bd, seed=5150 + w + bd)
+        cur = tuple(fade(p, 0.75, 12, bd) for p in ref)
+        for p in cur + ref:
+            p[:, -1] = top
+        (e,) = check(engine, cur, [ref], bd)
+        assert all(x["cur_ac"] > 0 and x["ref_ac"] > 0 and x["sad_nowp"] > 0 for x in e), (w, h)
+        assert (cur[0].shape[1] - 128, cur[1].shape[1] - 64) == (w - 128, (w - 128) // 2) and all((p[:, -1] == top).all() for p in cur + ref)
+
+
+def test_wp_estimate_420_over_two_rounds_of_workgroups(engine):
+    """16 references of 2048 x 50 at 8 bit: 51 planes / 48 pairs side by side cap a launch at 20 / 21 row blocks per plane; luma has 25 -- its
+    row loop iterates twice -- and chroma (1024 x 25) 7, so that the workgroups beyond its block 6 leave at once in the same launch
+    (tests/test_geometry_cpu.py asserts this arithmetic against geometry_cases.stat_grid)"""
+    from test_gpu_wp_estimate import fade
+    from test_gpu_wp_estimate_420 import check, picture
+    w, h, n_refs = gc.ROUNDS_420
+    grids = gc.stat_grids_420(w, h, 1, n_refs)
+    assert all(g[0]["rounds"] == 2 and g[1]["rounds"] == 1 and g[1]["blocks"] < g[0]["blocks"] for g in grids.values())
+    cur = picture(w, h, 8, seed=5160)
+    rows = np.arange(h)[:, None]
+    refs = []
+    for i in range(n_refs):                                                      # the fade of reference i acts on the rows of the second round alone, or of the first
+        ref = tuple(fade(p, 0.6 + 0.05 * i, 2 * i - 10, 8) for p in cur)
+        second = rows >= grids["stats"][0]["blocks"] * grids["stats"][0]["rows_per_block"]
+        ref[0][:] = np.where(second if i % 2 else ~second, ref[0], cur[0])
+        refs.append(ref)
+    es = check(engine, cur, refs, 8, 7)
+    assert len({(r[0]["ref_ac"], r[0]["sad_nowp"]) for r in es}) == n_refs and all(x["sad_nowp"] > 0 for r in es for x in r)
 
 
 # ---- 9: the largest sizes ------------------------------------------------------------------------------------------------------------------------

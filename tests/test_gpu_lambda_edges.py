@@ -321,6 +321,25 @@ def test_bi_search_on_extreme_origins(engine, oracle_lib, hmo, bd, fen, lq):
     assert_the_wrap_is_met(lq, r["mv"], oracle_windows(RW, RH, R_SR_BI, r["pred"], r["center"]), r["pred"], every_window=False)
 
 
+@pytest.mark.parametrize("lq", [lc.ALL_ONES, lc.WRAP24])
+@pytest.mark.parametrize("bd", [8, 10])
+def test_bi_search_and_refinement_over_several_references(engine, hmo, bd, lq):
+    """hmme_search / refine_frame_bi_refs, two references against two planes named block by block, window centres that differ from the
+    predictors: every CTU and slot against the per-CTU calls on the origin at the same lambda"""
+    from test_gpu_bipred_refs import SR_BI, check_against_the_per_ctu_calls, checkerboard, pictures, predictors, unrelated
+    w, h, n = RW, RH, R_CTUS
+    pics = pictures(w, h, bd, 2400 + bd, 3) + unrelated(w, h, bd, 2450 + bd, 2)
+    field, ref_field = random_field(n, 64, 2410 + bd), checkerboard(n, 64, 2, w)
+    seed = 2420 + bd
+    pred, center = predictors(2, n, seed), predictors(2, n, seed + 50)          # what check_against_the_per_ctu_calls draws
+    assert all(np.any(center[r] != pred[r], axis=1).all() for r in range(2))
+    with at(engine, lq):
+        for had in (True, False):
+            mv, sad, qmv, cost = check_against_the_per_ctu_calls(engine, hmo, w, h, bd, pics, [1, 2], [3, 4], field, ref_field, seed, fen=int(bd == 8), had=had)
+    for r in range(2):
+        assert_the_wrap_is_met(lq, mv[r], oracle_windows(w, h, SR_BI, pred[r], center[r]), pred[r], every_window=False)
+
+
 # ---- d: the refinement ----------------------------------------------------------------------------------------------------------------
 FW, FH, F_CTUS, F_SR = 192, 128, 6, 32
 REFINE_CASES = [(bd, had, lq) for bd in (8, 10) for had in (0, 1) for lq in lc.WRAPPING]
@@ -604,6 +623,44 @@ def test_select_dirs_frame_wraps_both_costs_and_hits_the_floor(engine, w, h, bit
     with at(engine, lq):
         f, d, s, cc = engine.select_dirs_frame(w, h, sel, api.DirParams(*bits), *tabs, pred)
     assert np.array_equal(f, mf) and np.array_equal(d, md) and np.array_equal(s, ms) and np.array_equal(cc, mc), (diff(d, md), diff(s, ms), diff(cc, mc))
+
+
+@pytest.mark.parametrize("lq", [lc.HALF, lc.WRAP24])
+@pytest.mark.parametrize("R", [2, 4])
+def test_select_dirs_refs_frame_at_odd_and_even_bit_totals(engine, R, lq):
+    """hmme_select_dirs_refs_device with far predictors and reference-index bits that make the totals dir_bits + ref_bits (+ an MV's even bit
+    count) odd for one reference and even for the next in either list: at 0x80000000 a candidate is priced at 32768 or at 0 by that parity
+    alone; at the first wrap some totals wrap and some do not"""
+    import select_dirs_refs_model as drm
+    from hmme import api
+    from test_gpu_select_dirs_refs import compare
+    w, h = 100, 70
+    n = sdm.n_ctus(w, h)
+    pred = far_predictors((2, R, n), seed=900 + R)
+    tabs = tuple(a[None] for a in drm.random_tables(R, n, n, 901 + R, pred, 0, lc.TINY, bi_gain=0))   # costs = distortions alone; uni and bi alike
+    bits = drm.Bits((3, 3, 5), (R, R), ([1, 2, 3, 6][:R], [2, 1, 4, 3][:R]), 0b10 if R == 2 else 0b0101)
+    totals = [{bits.dir_bits[l] + bits.ref_bits[l][r] for r in range(R)} for l in range(2)]
+    assert all({t & 1 for t in totals[l]} == {0, 1} for l in range(2))
+    priced, wrapped = [set(), set()], set()
+    for l in range(2):
+        for r in range(R):
+            for k in range(n):
+                for s in range(0, 593, 7):
+                    bu = sdm.mvb(tabs[0][0, l, r, k, s], pred[l, r, k])
+                    assert bu % 2 == 0
+                    priced[l].add(sdm.gc(lq, bits.dir_bits[l] + bits.ref_bits[l][r] + bu))
+                    wrapped.add(lc.wraps(lq, bits.dir_bits[l] + bits.ref_bits[l][r] + bu))
+    if lq == lc.HALF:
+        assert priced == [{0, 32768}, {0, 32768}] and wrapped == {True}
+    else:
+        assert wrapped == {False, True}
+    sel = api.SelectParams(64, cu_cost=40, pu_cost=12)
+    with at(engine, lq):
+        _, mr, md, ms, _ = compare(engine, w, h, tabs, sel, [bits], pred[None], lambda_q16=lq)
+    coded = ms != sm.NO_SLOT
+    assert len(set(md[coded].tolist())) >= 2 and (md[0] == 1).any()
+    if lq == lc.HALF:                                                           # 32768 is more than any distortion here: the parity alone rules a reference out
+        assert all((bits.dir_bits[l] + bits.ref_bits[l][r]) % 2 == 0 for l in range(2) for r in set(mr[0, l][md[0] == l + 1].tolist()))
 
 
 # ---- f: one chain end to end ------------------------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 """The refusal rules of hmme_weight_check / hmme_bipred_check as tested contracts: at every bit depth 8..12 the accepted inputs nearest to each
 refusal (tests/range_content.py finds them through hmme_weight_check) run on pictures of samples in {0, maxv} that reach the sample differences
 the rule admits, and the engine must be bit-exact against the CPU oracle there -- weighted search and refinement, the prediction at the filter
-shifts of 9, 11 and 12 bit, the bi-prediction search and refinement.  tests/test_range_edges_cpu.py holds the oracle to int64 numpy on the
+shifts of 9, 11 and 12 bit, the bi-prediction search and refinement, single-reference and over several references per list (128 x 64).  tests/test_range_edges_cpu.py holds the oracle to int64 numpy on the
 same inputs.  Pictures are 136 x 72 (3 x 2 CTUs, partial on the right, at the bottom and in the corner) unless a test says why not."""
 import ctypes as C
 import functools
@@ -258,6 +258,139 @@ def test_bi_refinement_at_every_served_bit_depth(engine, oracle_lib, bi_search, 
             engine.refine_frame_bi(pc, pr, po, SR_BI, r["field"], r["mv"], use_hadamard=bool(had))
     finally:
         pc.close(); pr.close(); po.close()
+
+
+# ---- 6b: the bi pass over several references: the origin built from a field and a reference-index field -------------------------------
+W_REFS, H_REFS, SR_REFS = 128, 64, 8
+
+
+@functools.lru_cache(maxsize=None)
+def lists(bd):
+    cur, refs, others = rc.extreme_lists(W_REFS, H_REFS, bd, seed=2200 + bd)
+    for a in [cur] + refs + others:
+        a.setflags(write=False)
+    return cur, refs, others
+
+
+@pytest.fixture(scope="module")
+def bi_refs_search(engine, hmo):
+    """search_frame_bi_refs on rc.extreme_lists -- two references, two planes in the other list named block by block -- against the per-CTU
+    search on the origin built here, all CTUs and slots, once per bit depth for the search and the refinement test; one MV per 8x8 block at
+    odd depths, one per CTU at even -> a function bd -> what was used and found"""
+    from bipred_refs_bands import refs_prediction
+    from frame_helpers import origin_picture, random_field
+    from test_gpu_bipred_refs import checkerboard, per_ctu, predictors as ref_predictors
+    done = {}
+
+    def get(bd):
+        if bd not in done:
+            from hmme import api, synth
+            assert api.bipred_check(bd, False) == 0                             # the search is served at every depth 8..12
+            maxv = (1 << bd) - 1
+            cur, refs, others = lists(bd)
+            per, n = 64 if bd & 1 else 1, 2
+            field, ref_field = random_field(n, per, 2210 + bd), checkerboard(n, per, 2, W_REFS)
+            pred, center = ref_predictors(2, n, 2220 + bd), ref_predictors(2, n, 2230 + bd)
+            p_full = refs_prediction(hmo, others, W_REFS, H_REFS, bd, field, ref_field)
+            org = origin_picture(cur, p_full, W_REFS, H_REFS)
+            assert org.min() == -maxv and org.max() == 2 * maxv and set(ref_field.reshape(-1).tolist()) == {0, 1}
+            m = synth.MARGIN                                                    # the current picture 0 where the other list's prediction is maxv, and the reverse
+            assert (cur[m:m + H_REFS, m:m + 32] == 0).all() and (p_full[:, :32] == maxv).all()
+            assert (cur[m:m + H_REFS, m + W_REFS - 32:m + W_REFS] == maxv).all() and (p_full[:, -32:] == 0).all()
+            planes = [mkplane(engine, a, W_REFS, H_REFS, bd) for a in [cur] + refs + others]
+            try:
+                fen = (bd >> 1) & 1
+                mv, sad = engine.search_frame_bi_refs(planes[0], planes[1:3], planes[3:], SR_REFS, field, ref_field, center_q=center, pred_q=pred, fen=fen)
+            finally:
+                for p in planes:
+                    p.close()
+            for r in range(2):
+                smv, ssad = per_ctu(engine, org, refs[r], W_REFS, H_REFS, bd, SR_REFS, center[r], pred[r], fen, range(n))
+                assert np.array_equal(mv[r], smv), (bd, r, np.argwhere(mv[r] != smv)[:4])
+                assert np.array_equal(sad[r], ssad), (bd, r, np.argwhere(sad[r] != ssad)[:4])
+            assert not np.array_equal(mv[0], mv[1])
+            done[bd] = dict(org=org, field=field, ref_field=ref_field, pred=pred, center=center, mv=mv, fen=fen)
+        return done[bd]
+    return get
+
+
+@pytest.mark.parametrize("bd", BDS)
+def test_bi_refs_search_at_every_bit_depth(bi_refs_search, bd):
+    maxv = (1 << bd) - 1
+    r = bi_refs_search(bd)
+    assert r["org"].min() == -maxv and r["org"].max() == 2 * maxv
+
+
+@pytest.mark.parametrize("had", [1, 0])
+@pytest.mark.parametrize("bd", BDS)
+def test_bi_refs_refinement_at_every_served_bit_depth(engine, bi_refs_search, bd, had):
+    import torch
+    from hmme import api
+    from test_gpu_bipred_refs import per_ctu
+    r = bi_refs_search(bd)
+    cur, refs, others = lists(bd)
+    n = 2
+    planes = [mkplane(engine, a, W_REFS, H_REFS, bd) for a in [cur] + refs + others]
+    try:
+        if api.bipred_check(bd, True) == 0:
+            assert bd < 12
+            qmv, cost = engine.refine_frame_bi_refs(planes[0], planes[1:3], planes[3:], SR_REFS, r["field"], r["ref_field"], r["mv"], center_q=r["center"],
+                                                    pred_q=r["pred"], use_hadamard=bool(had))
+            for k in range(2):
+                sq, sc = per_ctu(engine, r["org"], refs[k], W_REFS, H_REFS, bd, SR_REFS, r["center"][k], r["pred"][k], r["fen"], range(n), r["mv"][k], bool(had))
+                assert np.array_equal(qmv[k], sq), (bd, had, k, np.argwhere(qmv[k] != sq)[:4])
+                assert np.array_equal(cost[k], sc), (bd, had, k, np.argwhere(cost[k] != sc)[:4])
+            return
+        # what hmme_bipred_check refuses the _refs call refuses: HMME_ERR_UNSUPPORTED, nothing launched
+        assert bd == 12 and api.bipred_check(12, True) == ERR_UNSUPPORTED
+        dev = torch.device("cuda", 0)
+        d_f = torch.from_numpy(np.ascontiguousarray(r["field"])).to(dev)
+        d_r = torch.from_numpy(np.ascontiguousarray(r["ref_field"])).to(dev)
+        d_imv = torch.from_numpy(np.ascontiguousarray(r["mv"])).to(dev)
+        t_q = torch.full((2, n, 593, 2), 0x5A5A, dtype=torch.int16, device=dev)
+        t_c = torch.full((2, n, 593), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+        fp = api.FrameParams(SR_REFS, 1, 12, 0, n)
+        L = engine.L
+        was = L.hmme_set_error_printing(engine.h, 0)
+        try:
+            torch.cuda.synchronize()
+            rc_ = L.hmme_refine_frame_bi_refs_device(engine.h, planes[0].h, api._handles(planes[1:3]), 2, api._handles(planes[3:]), 2, C.byref(fp), d_f.data_ptr(),
+                                                     d_r.data_ptr(), int(r["field"].shape[1]), None, None, d_imv.data_ptr(), had, t_q.data_ptr(), t_c.data_ptr(), None)
+        finally:
+            L.hmme_set_error_printing(engine.h, was)
+        torch.cuda.synchronize()
+        assert rc_ == ERR_UNSUPPORTED
+        assert bool((t_q == 0x5A5A).all()) and bool((t_c == 0x5A5A5A5A).all())
+        with pytest.raises(api.HmmeError):
+            engine.refine_frame_bi_refs(planes[0], planes[1:3], planes[3:], SR_REFS, r["field"], r["ref_field"], r["mv"], use_hadamard=bool(had))
+    finally:
+        for p in planes:
+            p.close()
+
+
+@pytest.mark.parametrize("bd", [9, 11, 12])
+@pytest.mark.parametrize("per", [1, 64])
+def test_prediction_of_a_b_picture_with_several_references_at_9_11_12_bit(engine, hmo, bd, per):
+    """hmme_predict_bi_refs_frame on planes of samples in {0, maxv}, two per list, against predict_bi_refs_model: the average of two clipped
+    predictions at the filter shifts of 9, 11 and 12 bit reaches both ends of the range"""
+    import predict_bi_refs_model as pbrm
+    from hmme import synth
+    from test_gpu_predict_bi_refs import inputs
+    maxv = (1 << bd) - 1
+    rng = np.random.default_rng(2300 + bd)
+    pics = [synth.pad_plane(rc._binary(rng, H, W, maxv)) for _ in range(4)]
+    field, dirs, refs = inputs(W, H, per, 2310 + bd + per, 2, 2)
+    fill = 0xA5A5
+    want = pbrm.pred_picture(hmo, pics[:2], pics[2:], W, H, bd, field, dirs, refs, np.full((H, W), fill, np.int64))
+    assert (want == 0).any() and (want == maxv).any() and (want == fill).any() == (per == 64)
+    assert {int(d) for d in dirs.reshape(-1)} >= {1, 2, 3} and ((want != 0) & (want != maxv) & (want != fill)).any()
+    planes = [mkplane(engine, a, W, H, bd) for a in pics]
+    try:
+        got = engine.predict_bi_refs_frame(planes[:2], planes[2:], field, dirs, refs, out=np.full((H, W), fill, np.uint16))
+        assert got.dtype == np.uint16 and np.array_equal(got, want), (bd, per, np.argwhere(got != want)[:4])
+    finally:
+        for p in planes:
+            p.close()
 
 
 # ---- 7: bias and offset are per pair ---------------------------------------------------------------------------------------------

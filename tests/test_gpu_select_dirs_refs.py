@@ -2,7 +2,7 @@
 tests/select_dirs_refs_model.py -- the rule of include/hmme.h restated in Python integers -- bit for bit.  The decision reads tables, not
 pictures: the cases feed the recipes of select_dirs_refs_model, of which tests/test_select_dirs_refs_cpu.py shows on the model alone that
 every direction, every reference and the mask occur; the other cases assert on the MODEL's result that the input exercises what the case is
-about.  Tables of the engine go through the decision in tests/test_gpu_bipred_refs.py (the end-to-end case)."""
+about.  Random tables hold no exact tie: the ties of rules 1-4 come from the hand-made scenarios of select_dirs_refs_model.  Tables of the engine go through the decision in tests/test_gpu_bipred_refs.py (the end-to-end case)."""
 import ctypes as C
 
 import numpy as np
@@ -166,6 +166,36 @@ def test_an_empty_mask_and_a_masked_out_cheapest_reference(engine):
         assert set(md[coded].tolist()) == dirs and set(mr[0, 1][coded[0]].tolist()) == refs1, mask
 
 
+def test_every_tie_of_the_reference_and_direction_rules(engine):
+    """the hand-made scenarios of select_dirs_refs_model.tie_scenarios (tests/test_select_dirs_refs_cpu.py shows what the model makes of each)
+    through the device: three references per list, list 1's cheapest outside the mask, every scenario in 2Nx2N slots of CUs of different
+    depths with every other slot priced out of reach -- four pictures in one launch: the mask and the empty mask, each with HM-like and with
+    all-zero bit counts.  Beyond the comparison with the model, every site of the field carries the winner the scenario states"""
+    from hmme import api
+    bits = drm.tie_bits(drm.TIE_MASK) + drm.tie_bits(0)
+    made = [drm.tie_tables(b, seed=i) for i, b in enumerate(bits)]
+    tabs = tuple(np.stack([m[0][k] for m in made]) for k in range(6))
+    engine.set_lambda_q16(drm.TIE_LAMBDA_Q16)
+    try:
+        mf, mr, md, ms, _ = compare(engine, 64, 64, tabs, api.SelectParams(64), bits, None, lambda_q16=drm.TIE_LAMBDA_Q16)
+    finally:
+        engine.set_lambda_q16(drm.LAMBDA_Q16)
+    scenarios, seen = drm.tie_scenarios(), set()
+    for i, (b, (t, placed)) in enumerate(zip(bits, made)):
+        assert set(ms[i, 0].tolist()) == set(placed)                            # every site is coded, nothing else
+        for s, name in placed.items():
+            d, bl, mv, refs = drm.tie_want(b.l1_valid_mask, scenarios[name])
+            blocks = np.flatnonzero(ms[i, 0] == s)
+            l = bl if d == 3 else d - 1
+            assert (md[i, 0, blocks] == d).all() and (mf[i, l, 0, blocks] == mv).all() and (mr[i, l, 0, blocks] == refs[l]).all(), (i, name, s)
+            if d == 3:                                                          # the other list: the block's own entries of the input fields
+                assert np.array_equal(mf[i, 1 - l, 0, blocks], t[4][1 - l, 0, blocks]) and np.array_equal(mr[i, 1 - l, 0, blocks], t[5][1 - l, 0, blocks])
+            else:
+                assert (mf[i, 1 - l, 0, blocks] == 0).all() and (mr[i, 1 - l, 0, blocks] == drm.NO_REF).all()
+            seen.add((name, len(blocks)))
+    assert {n for n, _ in seen} == set(scenarios) and {c for _, c in seen} == {1, 4, 16}   # 8x8, 16x16 and 32x32 CUs
+
+
 # ---- 2: with one reference per list it is hmme_select_dirs_frame -----------------------------------------------------------------------------
 @pytest.mark.parametrize("w,h", sdm.SIZES)
 def test_with_one_reference_per_list_it_is_select_dirs_frame(engine, w, h):
@@ -224,6 +254,58 @@ def test_a_lambda_at_which_get_cost_wraps(engine, lq):
         compare(engine, w, h, tabs, api.SelectParams(64, cu_cost=40, pu_cost=12), [drm.hm_bits(3, 2, 0b01)], pred[None], lambda_q16=lq)
     finally:
         engine.set_lambda_q16(drm.LAMBDA_Q16)
+
+
+def test_eight_table_sets_per_list_the_limit(engine):
+    """n_refs_max = 8 (kMaxDirRefs): n_refs = (8, 8) with a mask of bits 1, 4 and 7, and n_refs = (8, 5), where bit 7 lies beyond list 1's
+    count and is refused, with bits 1 and 4; reference 7 of list 0 is the strict winner in some slots; nine sets are refused with the
+    outputs untouched"""
+    import torch
+    from hmme import api
+    w, h, R, n = 64, 64, 8, 1
+    pred = drm.predictors(R, n, seed=800)
+    mv_uni, cost_uni, mv_bi, cost_bi, uni_field, uni_ref = drm.random_tables(R, n, n, 801, pred)
+    cost_uni = cost_uni.copy()
+    rng = np.random.default_rng(802)
+    cheap = rng.random(593) < 0.3                                               # list 0's last reference far below every other candidate there
+    cost_uni[0, 7, 0, cheap] = cost_uni[:, :, 0][:, :, cheap].min(axis=(0, 1)) // 4
+    tabs = tuple(a[None] for a in (mv_uni, cost_uni, mv_bi, cost_bi, uni_field, uni_ref))
+    sel = api.SelectParams(64, min_depth=2, cu_cost=40, pu_cost=12)
+    p = [[pred[l][r][0] for r in range(R)] for l in range(2)]
+    # bit 7 needs eight references in list 1 (include/hmme.h: mask bits below n_refs[1] only); with five, bits 1 and 4 are the mask
+    for n_refs, mask in (((8, 8), 0b10010010), ((8, 5), 0b00010010)):
+        bits = drm.hm_bits(*n_refs, mask)
+        mf, mr, md, ms, _ = compare(engine, w, h, tabs, sel, [bits], pred[None])
+        strict = 0
+        for s in (int(v) for v in np.unique(ms[0, 0]) if v != sm.NO_SLOT):      # on the model: reference 7 wins direction 1 strictly, not by a tie
+            slot_tabs = (mv_uni[:, :, 0, s], cost_uni[:, :, 0, s], mv_bi[:, :, 0, s], cost_bi[:, :, 0, s])
+            d, _, c, _, refs = drm.slot_decide(*slot_tabs, p, bits, drm.LAMBDA_Q16)
+            if (d, refs[0]) == (1, 7):
+                without = drm.Bits(bits.dir_bits, (7, n_refs[1]), bits.ref_bits, mask)
+                strict += drm.slot_decide(*slot_tabs, p, without, drm.LAMBDA_Q16)[2] > c
+        assert strict >= 3 and 7 in mr[0, 0][md[0] == 1], n_refs
+        allowed = {r for r in range(n_refs[1]) if (mask >> r) & 1}
+        assert set(mr[0, 1][md[0] == 2].tolist()) <= allowed and len(allowed) == (3 if n_refs[1] == 8 else 2) and (md[0] == 2).any()
+    assert api.select_dirs_refs_check(sel, 1, 8, [dir_params(drm.Bits(bits.dir_bits, (8, 5), bits.ref_bits, 0b10010010))]) == -1   # bit 7: list 1 has five
+    # nine table sets per list: refused, nothing written (the tables need not be that large: they are not read)
+    d = [to_device(a) for a in tabs]
+    out = Outputs(1, n)
+    torch.cuda.synchronize()
+    L = api.load()
+    fp = api.FrameParams(1, 0, 8, 0, n)
+    dp = (api.DirRefsParams * 1)(dir_params(bits))
+    prev = L.hmme_set_error_printing(engine.h, 0)
+    try:
+        call = lambda r: L.hmme_select_dirs_refs_device(engine.h, w, h, 1, r, C.byref(fp), C.byref(sel), dp, *[t.data_ptr() for t in d], None, out.field.data_ptr(),
+                                                        out.ref.data_ptr(), out.dir.data_ptr(), out.slot.data_ptr(), out.cc.data_ptr(), None)
+        assert call(9) == -1 and api.select_dirs_refs_check(sel, 1, 9, [dir_params(bits)]) == -1
+        torch.cuda.synchronize()
+        assert out.untouched()
+        assert call(8) == 0                                                     # the accepted neighbour does run
+        torch.cuda.synchronize()
+        assert not out.untouched()
+    finally:
+        L.hmme_set_error_printing(engine.h, prev)
 
 
 # ---- 4: several pictures, the partition limits, CTU sub-ranges, NULL outputs ---------------------------------------------------------------

@@ -161,6 +161,28 @@ def test_the_bi_prediction_origin_reaches_both_extremes(oracle_lib, bd):
     assert set(np.unique(ref)) == {0, maxv} and set(np.unique(other)) == {0, maxv}
 
 
+@pytest.mark.parametrize("bd", BDS)
+def test_the_origin_of_several_references_reaches_both_extremes(oracle_lib, bd):
+    """rc.extreme_lists at the size of the GPU case (128 x 64): whichever plane of the other list a block's index names, the origin is -maxv
+    over the first 32 columns and 2 * maxv over the last 32; between them the two planes differ, so the index matters"""
+    from bipred_refs_bands import refs_prediction
+    hmo = bind_hmo(oracle_lib)
+    maxv = (1 << bd) - 1
+    w, h = 128, 64
+    cur, refs, others = rc.extreme_lists(w, h, bd, seed=60 + bd)
+    assert len(refs) == 2 and len(others) == 2 and all(set(np.unique(a)) == {0, maxv} for a in refs + others)
+    assert not np.array_equal(refs[0], refs[1]) and not np.array_equal(others[0], others[1])
+    for per in (1, 64):
+        field = random_field(2, per, 61 + bd + per)
+        b = np.arange(per)
+        by_index = []
+        for ref_field in (np.zeros((2, per), np.uint8), np.ones((2, per), np.uint8), (((b % 8) + (b // 8)) % 2).astype(np.uint8)[None].repeat(2, axis=0)):
+            org = origin_picture(cur, refs_prediction(hmo, others, w, h, bd, field, ref_field), w, h)
+            assert np.all(org[:, :32] == -maxv) and np.all(org[:, -32:] == 2 * maxv) and org.min() == -maxv and org.max() == 2 * maxv
+            by_index.append(org)
+        assert len({o.tobytes() for o in by_index}) == (3 if per == 64 else 2)
+
+
 @pytest.mark.parametrize("bd", [9, 11, 12])
 def test_oracle_prediction_equals_the_int64_interpolation(oracle_lib, bd):
     """hmo_pred_block_qpel at the filter shifts only 9, 11 and 12 bit take (headroom 5, 3, 2), all 16 phases, on the binary pattern: the

@@ -163,16 +163,7 @@ def test_with_list_1_and_bi_priced_out_the_model_is_the_reference_choice_on_list
     assert set(rr.reshape(-1).tolist()) >= set(range(n_refs))                  # every reference wins somewhere
 
 
-def slot(mu, cu, mb, cb, bits, lq=1 << 16, pred=None):
-    """slot_decide on lists of per-reference (mv, cost) with the zero predictor"""
-    R = max(len(mu[0]), len(mu[1]))
-    pad = lambda a, fill: [list(a[l]) + [fill] * (R - len(a[l])) for l in range(2)]
-    p = [[(0, 0)] * R, [(0, 0)] * R] if pred is None else pred
-    return drm.slot_decide(pad(mu, (0, 0)), pad(cu, 0), pad(mb, (0, 0)), pad(cb, 0), p, bits, lq)
-
-
-NO_BI = 0xFFFFFFFF
-Z = (0, 0)                                                                     # mvb((0,0), (0,0)) = 2 bits: gc 2 at lambda 1 per bit
+slot, NO_BI, Z = drm.slot_of_lists, drm.NO_BI, drm.Z                           # the hand-made tables' builders: shared with tests/test_gpu_select_dirs_refs.py
 dcr = lambda res: (res[0], res[2], res[4])                                     # direction, cost, the two reference indices
 
 
@@ -234,6 +225,38 @@ def test_every_strict_comparison():
     one = lambda c0, c1, mask=None: slot([[Z], [Z]], [[c0], [c1]], [[a], [a]], bi([500], [600]), flat(1, 1, mask))
     assert one(t, t)[0] == 3 and one(t - 1, t)[0] == 1 and one(t, t - 1)[0] == 2 and one(t - 1, t - 1)[0] == 1 and one(t - 1, t - 2)[0] == 2
     assert one(t, t - 1, 0)[0] == 3 and one(t - 1, 0, 0)[0] == 1               # ... and against list 0 alone with an empty mask
+
+
+tie_bits = drm.tie_bits
+
+
+def test_the_tie_scenarios_price_as_stated_and_decide_as_stated(api):
+    """select_dirs_refs_model.tie_scenarios: under either set of bit counts the tables of tie_slot_tables price at exactly the stated costs,
+    slot_decide makes of them what the scenario states, and the picture of tie_tables codes every site, so every scenario shows in the field"""
+    scenarios = drm.tie_scenarios()
+    assert len(scenarios) >= 16 and {v[0] for v in scenarios.values()} == {drm.TIE_MASK, 0}
+    assert len({sdm.mvb(m, Z) for m in drm.TIE_MVS}) == 1 and len(set(drm.TIE_MVS)) == 4
+    gc, mvb = sdm.gc, sdm.mvb
+    for name, sc in scenarios.items():
+        for bits in tie_bits(sc[0]):
+            mu, cu, mb, cb = drm.tie_slot_tables(*sc[1:5], bits)
+            lq = drm.TIE_LAMBDA_Q16
+            priced = [[int(cu[l][r]) - gc(lq, mvb(mu[l][r], Z)) + gc(lq, bits.dir_bits[l] + bits.ref_bits[l][r] + mvb(mu[l][r], Z)) for r in range(3)] for l in range(2)]
+            assert priced == [list(sc[1]), list(sc[2])], name
+            d, bl, c, m, refs = drm.slot_decide(mu, cu, mb, cb, [[Z] * 3] * 2, bits, lq)
+            wd, wbl, wm, wrefs = drm.tie_want(bits.l1_valid_mask, sc)
+            assert (d, tuple(m), refs) == (wd, wm, wrefs) and (d != 3 or bl == wbl), (name, d, bl, m, refs)
+            assert c == min(v for v in sc[1] + (sc[2][1:] if sc[0] else []) + sc[3] + sc[4]), name      # the winner's priced cost: the least of those allowed
+    # in every masked scenario list 1's cheapest reference is the one outside the mask
+    assert all(sc[2].index(min(sc[2])) == 0 and not drm.TIE_MASK & 1 for sc in scenarios.values() if sc[0])
+    sel = api.SelectParams(64)
+    for mask in (drm.TIE_MASK, 0):
+        for bits in tie_bits(mask):
+            tabs, placed = drm.tie_tables(bits)
+            field, ref, dirs, slot_, cost = drm.select_dirs_refs_picture(*tabs, sel, 64, 64, bits, 0, None, drm.TIE_LAMBDA_Q16)
+            assert set(slot_.reshape(-1).tolist()) == set(placed) and len(placed) == 25
+            assert {placed[s] for s in placed} == {k for k, v in scenarios.items() if v[0] == mask}
+            assert len({d for _, d in drm.tie_sites()}) == 3
 
 
 def test_the_model_carries_its_sums_unwrapped_and_its_products_wrapped():
