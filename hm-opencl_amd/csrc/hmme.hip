@@ -2138,7 +2138,7 @@ void with_sample_type(int bps, F&& f) {
 // me_predict_kernel for CTUs [first, first + count) of `src` with its motion field (int16 [n_ctu][mv_per_ctu][2], device)
 // pw: the weight of a slice with explicit weighted prediction (null: none, and the identity -- WP = 0 computes the same samples)
 // pr: a reference picture per block (hmme_predict_refs_device; `src` gives the geometry all planes share), prw: with one weight per
-// reference (hmme_predict_refs_w_device; null: none); origin with pr: the origin of the *_bi_refs calls
+// reference (hmme_predict_refs_w_device; null: none); origin with pr: the origin of the *_bi_refs calls, with prw too: of the *_bi_refs_w calls
 int launch_predict(hmme_ctx* ctx, const hmme_plane* src, const int16_t* d_field, int mv_per_ctu, int first, int count, bool origin, const uint8_t* cur_blocks,
                    int bias, uint8_t* dst, long dst_ctu_x, long dst_ctu_y, int dst_pitch, hipStream_t s, const hmme::MePredWp<1>* pw = nullptr,
                    const hmme::MePredRefs<1>* pr = nullptr, const hmme::MePredWp<2>* prw = nullptr) {
@@ -2150,7 +2150,8 @@ int launch_predict(hmme_ctx* ctx, const hmme_plane* src, const int16_t* d_field,
     };
     const hmme::MePredWp<0> no_wp;
     const hmme::MePredRefs<0> no_refs;
-    if (pr && prw) go(hmme::me_predict_kernel<T, 0, 2, 1>, *prw, *pr);
+    if (origin && pr && prw) go(hmme::me_predict_kernel<T, 1, 2, 1>, *prw, *pr);
+    else if (pr && prw) go(hmme::me_predict_kernel<T, 0, 2, 1>, *prw, *pr);
     else if (origin && pr) go(hmme::me_predict_kernel<T, 1, 0, 1>, no_wp, *pr);
     else if (pr) go(hmme::me_predict_kernel<T, 0, 0, 1>, no_wp, *pr);
     else if (origin && pw) go(hmme::me_predict_kernel<T, 1, 1, 0>, *pw, no_refs);
@@ -2594,7 +2595,67 @@ int hmme_refine_frame_bi_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plan
 // bi_search / bi_refine with ONE origin for all n_refs pairs, as the multi-reference uni launch hands one current picture to its pairs: the
 // other list's prediction comes from others[d_other_ref[block]] (me_predict_kernel<T, 1, 0, 1>, one launch per call), the biased / raw
 // reference copies stay per reference.  No explicit weights: the bias is maxv.
+// With explicit weights (the *_bi_refs_w calls; the rule: include/hmme.h, "multi-reference B pictures: explicit weights and 4:2:0 chroma"):
+// the ONE origin carries ONE bias for all references, the largest of the searched weights' own (weight_eval); every weighted copy carries
+// offset_r + bias, the refinement runs one launch per run of equal searched weights as bi_refine does, and the origin comes from
+// me_predict_kernel<T, 1, 2, 1> unless every other weight is the identity.
 namespace {
+struct BiRefsWp {
+  int bias = 0;
+  bool identity[hmme::kMaxRefs] = {};   // the searched weights, as weight_eval reads the word (round included)
+  bool all_identity = true;             // every weight of both lists: the call IS the unweighted one with fen = 0
+  bool others_identity = true;          // every other weight (the prediction family's meaning): the unweighted origin
+  hmme::MePredWp<2> pw = {};            // the other list's weights as addWeightUni takes them
+};
+BiRefsWp bi_refs_unweighted(int bit_depth) {
+  BiRefsWp bw;
+  bw.bias = (1 << bit_depth) - 1;
+  for (bool& id : bw.identity) id = true;
+  return bw;
+}
+// In the header's order: 1. the argument errors of all searched weights, then of all other weights; 2. the searched lines per reference, with
+// `refine`; 3. the "other weight" line per other reference.
+int bipred_refs_weight_eval(int bit_depth, const hmme_weight* wps, int n_refs, const hmme_weight* other_wps, int n_others, int refine, BiRefsWp* out, char* msg, size_t n) {
+  const hmme_weight* const lists[2] = {wps, other_wps};
+  const int cnt[2] = {n_refs, n_others};
+  static const char* const name[2] = {"searched", "other"};
+  char why[192];
+  msg[0] = 0;
+  for (int l = 0; l < 2; ++l) {
+    if (bit_depth < 8 || bit_depth > 12) { snprintf(msg, n, "bit depth %d outside 8..12", bit_depth); return HMME_ERR_ARG; }
+    if (!lists[l]) { snprintf(msg, n, "null weights of the %s list", name[l]); return HMME_ERR_ARG; }
+    if (cnt[l] < 1 || cnt[l] > hmme::kMaxRefs) { snprintf(msg, n, "%s list: %d references outside 1..%d", name[l], cnt[l], hmme::kMaxRefs); return HMME_ERR_ARG; }
+    for (int r = 0; r < cnt[l]; ++r) {
+      const int rc = bi_weight_args(bit_depth, &lists[l][r], name[l], why, sizeof why);
+      if (rc) { snprintf(msg, n, "%s reference %d: %s", name[l], r, why); return rc; }
+    }
+  }
+  BiRefsWp bw;
+  for (int r = 0; r < n_refs; ++r) {
+    WpInfo info;
+    const int rc = weight_eval(bit_depth, &wps[r], refine, kBiOrigin, &info, why, sizeof why);
+    if (rc) { snprintf(msg, n, "searched reference %d: %s", r, why); return rc; }
+    bw.bias = std::max(bw.bias, info.bias);
+    bw.identity[r] = info.identity;
+    bw.all_identity = bw.all_identity && info.identity;
+  }
+  for (int r = 0; r < n_others; ++r) {
+    bool id = true;
+    const int rc = other_weight_eval(bit_depth, &other_wps[r], &id, &bw.pw.ref[r], why, sizeof why);
+    if (rc) { snprintf(msg, n, "other reference %d: %s", r, why); return rc; }
+    bw.others_identity = bw.others_identity && id;
+  }
+  bw.all_identity = bw.all_identity && bw.others_identity;
+  if (out) *out = bw;
+  return HMME_OK;
+}
+int check_bi_refs_weights(hmme_ctx* ctx, const char* who, const hmme_frame_params* fp, const hmme_weight* wps, int n_refs, const hmme_weight* other_wps, int n_others,
+                          int refine, BiRefsWp* bw) {
+  if (!fp) return fail(ctx, HMME_ERR_ARG, "%s: null params", who);
+  char msg[256];
+  const int rc = bipred_refs_weight_eval(fp->bit_depth, wps, n_refs, other_wps, n_others, refine, bw, msg, sizeof msg);
+  return rc ? fail(ctx, rc, "%s: %s", who, msg) : HMME_OK;
+}
 int bi_refs_args(hmme_ctx* ctx, const char* who, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
                  const hmme_frame_params* fp, const void* d_other_mv, const void* d_other_ref, int mv_per_ctu) {
   if (!cur || !refs || !others || n_refs < 1 || n_refs > hmme::kMaxRefs || n_others < 1 || n_others > hmme::kMaxRefs)
@@ -2628,8 +2689,8 @@ hmme::MePredRefs<1> other_set(const hmme_plane* const* others, int n_others, con
 }
 
 int bi_refs_search(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
-                   const hmme_frame_params* fp, const void* d_other_mv, const void* d_other_ref, int mv_per_ctu, const void* d_center_q, const void* d_pred_q,
-                   void* d_out_mv, void* d_out_sad, void* stream) {
+                   const hmme_frame_params* fp, const hmme_weight* wps, const BiRefsWp& bw, const void* d_other_mv, const void* d_other_ref, int mv_per_ctu,
+                   const void* d_center_q, const void* d_pred_q, void* d_out_mv, void* d_out_sad, void* stream) {
   if (!d_out_mv || !d_out_sad) return fail(ctx, HMME_ERR_ARG, "null output buffer");
   hipStream_t s = (hipStream_t)stream;
   const BiRefsPlanes p(cur, refs, n_refs);
@@ -2638,19 +2699,20 @@ int bi_refs_search(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const
   if (rc || pl.count == 0) return rc;
   for (int r = 0; r < n_others && rc == HMME_OK; ++r) rc = plane_wait(ctx, others[r], s);
   const WpGeom g(refs[0]);
-  const int ctus_x = cur->ctus_x, bias = (1 << fp->bit_depth) - 1;
+  const int ctus_x = cur->ctus_x, bias = bw.bias;
   if (rc == HMME_OK) rc = ensure(ctx, ctx->buf[kWp0], g.plane_bytes * n_refs);
   if (rc == HMME_OK) rc = ensure(ctx, ctx->buf[kWp1], g.blk_bytes);
   RefSet wrefs = one_ref(nullptr), wcurs = one_ref(nullptr);
   CopyCache wref(ctx->wp(0), g.plane_bytes, false);   // the references with the origin's bias
   for (int r = 0; r < n_refs && rc == HMME_OK; ++r) {
-    rc = cached_copy(ctx, wref, g, r, CopyKey{refs[r], 1, 0, 0, bias}, s, &wrefs.base[r]);
+    rc = cached_copy(ctx, wref, g, r, wps ? CopyKey{refs[r], wps[r].w0, wps[r].round, wps[r].shift, wps[r].offset + bias} : CopyKey{refs[r], 1, 0, 0, bias}, s,
+                     &wrefs.base[r]);
     wcurs.base[r] = ctx->wp(1);   // the ONE origin
   }
   if (rc == HMME_OK) {
     const hmme::MePredRefs<1> pr = other_set(others, n_others, d_other_ref);
     rc = launch_predict(ctx, others[0], (const int16_t*)d_other_mv, mv_per_ctu, pl.first, pl.count, true, cur->d_blocks, bias, ctx->wp(1), hmme::kBlkBytes16,
-                        (long)ctus_x * hmme::kBlkBytes16, 128, s, nullptr, &pr);
+                        (long)ctus_x * hmme::kBlkBytes16, 128, s, nullptr, &pr, bw.others_identity ? nullptr : &bw.pw);
   }
   const FramePlan plan = plan_launch(ctx, fp, pl.count, n_refs, true);
   if (rc == HMME_OK) rc = prep_jobs(ctx, cur, fp, d_pred_q, pl.first, pl.count, n_refs, s, plan, d_center_q);
@@ -2659,8 +2721,8 @@ int bi_refs_search(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const
 }
 
 int bi_refs_refine(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
-                   const hmme_frame_params* fp, const void* d_other_mv, const void* d_other_ref, int mv_per_ctu, const void* d_center_q, const void* d_pred_q,
-                   const void* d_int_mv, int use_hadamard, void* d_out_qmv, void* d_out_cost, void* stream) {
+                   const hmme_frame_params* fp, const hmme_weight* wps, const BiRefsWp& bw, const void* d_other_mv, const void* d_other_ref, int mv_per_ctu,
+                   const void* d_center_q, const void* d_pred_q, const void* d_int_mv, int use_hadamard, void* d_out_qmv, void* d_out_cost, void* stream) {
   if (!d_int_mv || !d_out_qmv || !d_out_cost) return fail(ctx, HMME_ERR_ARG, "null buffer");
   hipStream_t s = (hipStream_t)stream;
   const BiRefsPlanes p(cur, refs, n_refs);
@@ -2668,7 +2730,7 @@ int bi_refs_refine(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const
   int rc = pairs_begin(ctx, p.curs, refs, n_refs, fp, s, &pl);
   if (rc || pl.count == 0) return rc;
   for (int r = 0; r < n_others && rc == HMME_OK; ++r) rc = plane_wait(ctx, others[r], s);
-  const int src_wide = cur->bps == 2 ? 1 : 0, bias = (1 << fp->bit_depth) - 1;
+  const int src_wide = cur->bps == 2 ? 1 : 0, bias = bw.bias, n_ctu = cur->n_ctu;
   const WpGeom g(refs[0]);
   if (rc == HMME_OK && !src_wide) rc = ensure(ctx, ctx->buf[kWp2], g.plane_bytes * n_refs);
   if (rc == HMME_OK) rc = ensure(ctx, ctx->buf[kWp3], g.plane_bytes);
@@ -2683,17 +2745,27 @@ int bi_refs_refine(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const
   if (rc == HMME_OK) {
     const hmme::MePredRefs<1> pr = other_set(others, n_others, d_other_ref);
     rc = launch_predict(ctx, others[0], (const int16_t*)d_other_mv, mv_per_ctu, pl.first, pl.count, true, cur->d_blocks, bias, ctx->wp(3) + g.origin, 128,
-                        64L * g.pitch, g.pitch, s, nullptr, &pr);
+                        64L * g.pitch, g.pitch, s, nullptr, &pr, bw.others_identity ? nullptr : &bw.pw);
   }
-  if (rc == HMME_OK) {
+  // one launch per run of equal searched weights (the weight is one kernel argument, FracWp), one launch in all without explicit weights
+  for (int a = 0, b; a < n_refs && rc == HMME_OK; a = b) {
+    for (b = wps ? a + 1 : n_refs; b < n_refs && same_weight(wps[b], wps[a]); ++b) {}
+    RefSet ra = one_ref(nullptr);
+    for (int r = a; r < b; ++r) ra.base[r - a] = rf.base[r];
+    // the run's own table and counter in the same buffer as the run before (on one stream: behind its kernel)
+    const size_t res0 = (size_t)a * pl.count * HMME_NUM_CTU_PARTS;
     RefineLaunch L;
-    refine_common(L, pl, cur, fp, use_hadamard, (const int16_t*)d_int_mv, (int16_t*)d_out_qmv, (uint32_t*)d_out_cost);
-    L.curs = c; L.refs = rf; L.cur_pitch = g.pitch; L.ref_pitch = g.pitch;
+    refine_common(L, pl, cur, fp, use_hadamard, (const int16_t*)d_int_mv + 2 * res0, (int16_t*)d_out_qmv + 2 * res0, (uint32_t*)d_out_cost + res0);
+    L.curs = c; L.refs = ra; L.cur_pitch = g.pitch; L.ref_pitch = g.pitch;   // c: the ONE origin in every entry
     L.build.wide = 1; L.build.wp = 1;
-    L.fw = hmme::FracWp{1.f, 0.f, (float)bias};   // org_sub takes the origin's bias off
-    L.d_pred = (const int16_t*)d_pred_q;
-    L.d_center = (const int16_t*)d_center_q;
-    L.pairs = n_refs;
+    // org_sub takes the origin's bias off, with the weight's offset; without explicit weights (and for an identity weight) the weight is 1
+    if (wps && !bw.identity[a])
+      L.fw = hmme::FracWp{std::ldexp((float)wps[a].w0, -wps[a].shift), std::ldexp((float)wps[a].round, -wps[a].shift), (float)(bias + wps[a].offset)};
+    else
+      L.fw = hmme::FracWp{1.f, 0.f, (float)bias};
+    L.d_pred = d_pred_q ? (const int16_t*)d_pred_q + (size_t)a * n_ctu * 2 : nullptr;
+    L.d_center = d_center_q ? (const int16_t*)d_center_q + (size_t)a * n_ctu * 2 : nullptr;
+    L.pairs = b - a;
     L.table = FracTable::kAlways;   // the table carries the window centres
     rc = launch_refine(ctx, L, s);
   }
@@ -2702,9 +2774,10 @@ int bi_refs_refine(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const
 
 // the two synchronous forms; int_mv != null: the refinement
 int bi_refs_frame(hmme_ctx* ctx, const char* who, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
-                  const hmme_frame_params* fp, const int16_t* other_mv, const uint8_t* other_ref, int mv_per_ctu, const int16_t* center_q, const int16_t* pred_q,
-                  bool refine, const int16_t* int_mv, int use_hadamard, int16_t* out_mv, uint32_t* out_cost) {
-  int rc = bi_check(ctx, who, fp, refine);
+                  const hmme_frame_params* fp, const hmme_weight* wps, const hmme_weight* other_wps, bool weighted, const int16_t* other_mv, const uint8_t* other_ref,
+                  int mv_per_ctu, const int16_t* center_q, const int16_t* pred_q, bool refine, const int16_t* int_mv, int use_hadamard, int16_t* out_mv, uint32_t* out_cost) {
+  // weighted: before anything is staged; the device call checks again
+  int rc = weighted ? check_bi_refs_weights(ctx, who, fp, wps, n_refs, other_wps, n_others, refine, nullptr) : bi_check(ctx, who, fp, refine);
   if (rc == HMME_OK) rc = bi_refs_args(ctx, who, cur, refs, n_refs, others, n_others, fp, other_mv, other_ref, mv_per_ctu);
   if (rc) return rc;
   int count;
@@ -2715,12 +2788,18 @@ int bi_refs_frame(hmme_ctx* ctx, const char* who, const hmme_plane* cur, const h
   const int center = st.in(center_q, sizeof(int16_t) * 2 * (size_t)cur->n_ctu * n_refs);
   rc = stage_in(ctx, cur, refs[0], fp, n_refs, pred_q, refine, int_mv, out_mv, out_cost, &count, st, &it);
   if (rc || count == 0) return rc;
-  if (!refine)
+  if (!refine && !weighted)
     rc = hmme_search_frame_bi_refs_device(ctx, cur, refs, n_refs, others, n_others, fp, st.at(field), st.at(rfield), mv_per_ctu, st.at(center), st.at(it.pred),
                                           st.at(it.mv), st.at(it.cost), ctx->stream);
-  else
+  else if (!refine)
+    rc = hmme_search_frame_bi_refs_w_device(ctx, cur, refs, n_refs, others, n_others, fp, wps, other_wps, st.at(field), st.at(rfield), mv_per_ctu, st.at(center),
+                                            st.at(it.pred), st.at(it.mv), st.at(it.cost), ctx->stream);
+  else if (!weighted)
     rc = hmme_refine_frame_bi_refs_device(ctx, cur, refs, n_refs, others, n_others, fp, st.at(field), st.at(rfield), mv_per_ctu, st.at(center), st.at(it.pred),
                                           st.at(it.imv), use_hadamard, st.at(it.mv), st.at(it.cost), ctx->stream);
+  else
+    rc = hmme_refine_frame_bi_refs_w_device(ctx, cur, refs, n_refs, others, n_others, fp, wps, other_wps, st.at(field), st.at(rfield), mv_per_ctu, st.at(center),
+                                            st.at(it.pred), st.at(it.imv), use_hadamard, st.at(it.mv), st.at(it.cost), ctx->stream);
   return rc ? rc : st.end();
 }
 }  // namespace
@@ -2732,7 +2811,8 @@ int hmme_search_frame_bi_refs_device(hmme_ctx* ctx, const hmme_plane* cur, const
   int rc = bi_check(ctx, "hmme_search_frame_bi_refs_device", fp, 0);
   if (rc == HMME_OK) rc = bi_refs_args(ctx, "hmme_search_frame_bi_refs_device", cur, refs, n_refs, others, n_others, fp, d_other_mv, d_other_ref, mv_per_ctu);
   if (rc) return rc;
-  return bi_refs_search(ctx, cur, refs, n_refs, others, n_others, fp, d_other_mv, d_other_ref, mv_per_ctu, d_center_q, d_pred_q, d_out_mv, d_out_sad, stream);
+  return bi_refs_search(ctx, cur, refs, n_refs, others, n_others, fp, nullptr, bi_refs_unweighted(fp->bit_depth), d_other_mv, d_other_ref, mv_per_ctu, d_center_q, d_pred_q,
+                        d_out_mv, d_out_sad, stream);
 }
 
 int hmme_refine_frame_bi_refs_device(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others,
@@ -2743,15 +2823,15 @@ int hmme_refine_frame_bi_refs_device(hmme_ctx* ctx, const hmme_plane* cur, const
   int rc = bi_check(ctx, "hmme_refine_frame_bi_refs_device", fp, 1);
   if (rc == HMME_OK) rc = bi_refs_args(ctx, "hmme_refine_frame_bi_refs_device", cur, refs, n_refs, others, n_others, fp, d_other_mv, d_other_ref, mv_per_ctu);
   if (rc) return rc;
-  return bi_refs_refine(ctx, cur, refs, n_refs, others, n_others, fp, d_other_mv, d_other_ref, mv_per_ctu, d_center_q, d_pred_q, d_int_mv, use_hadamard, d_out_qmv,
-                        d_out_cost, stream);
+  return bi_refs_refine(ctx, cur, refs, n_refs, others, n_others, fp, nullptr, bi_refs_unweighted(fp->bit_depth), d_other_mv, d_other_ref, mv_per_ctu, d_center_q,
+                        d_pred_q, d_int_mv, use_hadamard, d_out_qmv, d_out_cost, stream);
 }
 
 int hmme_search_frame_bi_refs(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
                               const hmme_frame_params* fp, const int16_t* other_mv, const uint8_t* other_ref, int mv_per_ctu, const int16_t* center_q,
                               const int16_t* pred_q, int16_t* out_mv, uint32_t* out_sad) {
   if (!ctx) return HMME_ERR_ARG;
-  return bi_refs_frame(ctx, "hmme_search_frame_bi_refs", cur, refs, n_refs, others, n_others, fp, other_mv, other_ref, mv_per_ctu, center_q, pred_q, false, nullptr, 0,
+  return bi_refs_frame(ctx, "hmme_search_frame_bi_refs", cur, refs, n_refs, others, n_others, fp, nullptr, nullptr, false, other_mv, other_ref, mv_per_ctu, center_q, pred_q, false, nullptr, 0,
                        out_mv, out_sad);
 }
 
@@ -2759,8 +2839,71 @@ int hmme_refine_frame_bi_refs(hmme_ctx* ctx, const hmme_plane* cur, const hmme_p
                               const hmme_frame_params* fp, const int16_t* other_mv, const uint8_t* other_ref, int mv_per_ctu, const int16_t* center_q,
                               const int16_t* pred_q, const int16_t* int_mv, int use_hadamard, int16_t* out_qmv, uint32_t* out_cost) {
   if (!ctx) return HMME_ERR_ARG;
-  return bi_refs_frame(ctx, "hmme_refine_frame_bi_refs", cur, refs, n_refs, others, n_others, fp, other_mv, other_ref, mv_per_ctu, center_q, pred_q, true, int_mv,
+  return bi_refs_frame(ctx, "hmme_refine_frame_bi_refs", cur, refs, n_refs, others, n_others, fp, nullptr, nullptr, false, other_mv, other_ref, mv_per_ctu, center_q, pred_q, true, int_mv,
                        use_hadamard, out_qmv, out_cost);
+}
+
+// ---- ... with a weight per reference of both lists.  A launch in which every weight of both lists is the identity IS the unweighted call
+// with FEN off.
+int hmme_bipred_refs_weight_check(int bit_depth, const hmme_weight* wps, int n_refs, const hmme_weight* other_wps, int n_others, int refine) {
+  char msg[256];
+  return bipred_refs_weight_eval(bit_depth, wps, n_refs, other_wps, n_others, refine, nullptr, msg, sizeof msg);
+}
+
+int hmme_search_frame_bi_refs_w_device(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others,
+                                       int n_others, const hmme_frame_params* fp, const hmme_weight* wps, const hmme_weight* other_wps, const void* d_other_mv,
+                                       const void* d_other_ref, int mv_per_ctu, const void* d_center_q, const void* d_pred_q, void* d_out_mv, void* d_out_sad,
+                                       void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  const char* who = "hmme_search_frame_bi_refs_w_device";
+  BiRefsWp bw;
+  int rc = check_bi_refs_weights(ctx, who, fp, wps, n_refs, other_wps, n_others, 0, &bw);
+  if (rc) return rc;
+  hmme_frame_params f = *fp;
+  f.fen = 0;   // xGetSADw reads every row (TComRdCost.cpp:467-469): FEN is not consulted
+  if (bw.all_identity)
+    return hmme_search_frame_bi_refs_device(ctx, cur, refs, n_refs, others, n_others, &f, d_other_mv, d_other_ref, mv_per_ctu, d_center_q, d_pred_q, d_out_mv, d_out_sad,
+                                            stream);
+  rc = bi_refs_args(ctx, who, cur, refs, n_refs, others, n_others, &f, d_other_mv, d_other_ref, mv_per_ctu);
+  if (rc) return rc;
+  return bi_refs_search(ctx, cur, refs, n_refs, others, n_others, &f, wps, bw, d_other_mv, d_other_ref, mv_per_ctu, d_center_q, d_pred_q, d_out_mv, d_out_sad, stream);
+}
+
+int hmme_refine_frame_bi_refs_w_device(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others,
+                                       int n_others, const hmme_frame_params* fp, const hmme_weight* wps, const hmme_weight* other_wps, const void* d_other_mv,
+                                       const void* d_other_ref, int mv_per_ctu, const void* d_center_q, const void* d_pred_q, const void* d_int_mv, int use_hadamard,
+                                       void* d_out_qmv, void* d_out_cost, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  const char* who = "hmme_refine_frame_bi_refs_w_device";
+  BiRefsWp bw;
+  int rc = check_bi_refs_weights(ctx, who, fp, wps, n_refs, other_wps, n_others, 1, &bw);
+  if (rc) return rc;
+  hmme_frame_params f = *fp;
+  f.fen = 0;
+  if (bw.all_identity)
+    return hmme_refine_frame_bi_refs_device(ctx, cur, refs, n_refs, others, n_others, &f, d_other_mv, d_other_ref, mv_per_ctu, d_center_q, d_pred_q, d_int_mv,
+                                            use_hadamard, d_out_qmv, d_out_cost, stream);
+  rc = bi_refs_args(ctx, who, cur, refs, n_refs, others, n_others, &f, d_other_mv, d_other_ref, mv_per_ctu);
+  if (rc) return rc;
+  return bi_refs_refine(ctx, cur, refs, n_refs, others, n_others, &f, wps, bw, d_other_mv, d_other_ref, mv_per_ctu, d_center_q, d_pred_q, d_int_mv, use_hadamard,
+                        d_out_qmv, d_out_cost, stream);
+}
+
+int hmme_search_frame_bi_refs_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
+                                const hmme_frame_params* fp, const hmme_weight* wps, const hmme_weight* other_wps, const int16_t* other_mv, const uint8_t* other_ref,
+                                int mv_per_ctu, const int16_t* center_q, const int16_t* pred_q, int16_t* out_mv, uint32_t* out_sad) {
+  if (!ctx) return HMME_ERR_ARG;
+  return bi_refs_frame(ctx, "hmme_search_frame_bi_refs_w", cur, refs, n_refs, others, n_others, fp, wps, other_wps, true, other_mv, other_ref, mv_per_ctu, center_q,
+                       pred_q, false, nullptr, 0, out_mv, out_sad);
+}
+
+int hmme_refine_frame_bi_refs_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
+                                const hmme_frame_params* fp, const hmme_weight* wps, const hmme_weight* other_wps, const int16_t* other_mv, const uint8_t* other_ref,
+                                int mv_per_ctu, const int16_t* center_q, const int16_t* pred_q, const int16_t* int_mv, int use_hadamard, int16_t* out_qmv,
+                                uint32_t* out_cost) {
+  if (!ctx) return HMME_ERR_ARG;
+  return bi_refs_frame(ctx, "hmme_refine_frame_bi_refs_w", cur, refs, n_refs, others, n_others, fp, wps, other_wps, true, other_mv, other_ref, mv_per_ctu, center_q,
+                       pred_q, true, int_mv, use_hadamard, out_qmv, out_cost);
 }
 
 // ---- partition decision and motion field from the 593-slot tables ---------------------------------------------------------------------
@@ -3373,28 +3516,132 @@ int hmme_predict_bi_w_frame(hmme_ctx* ctx, const hmme_plane* ref0, const hmme_pl
 }
 
 // ---- the prediction of a B picture with several references per list (the rule: include/hmme.h) --------------------------------------------------
-// hmme_predict_bi_refs_device: ONE picture, ONE launch of me_predict_bi_kernel<T, 0, 1>: every block from the planes its direction and its two
-// reference indices name.  The two lists go through the checks of predict_refs one after the other (each up to 16 planes), list 1 against
-// list 0's first plane for the size.
-int hmme_predict_bi_refs_device(hmme_ctx* ctx, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, const hmme_frame_params* fp,
-                                const void* d_mv_field, const void* d_dir_field, const void* d_ref_field, int mv_per_ctu, void* d_out, int out_pitch_bytes,
-                                void* stream) {
-  if (!ctx) return HMME_ERR_ARG;
-  const char* who = "hmme_predict_bi_refs_device";
-  int rc = bi_check(ctx, who, fp, 0);
-  if (rc) return rc;
+namespace {
+// The weights of one component of such a picture as the kernels take them (hmme_predict_bi_refs_weight_check; the rule: include/hmme.h,
+// "multi-reference B pictures: explicit weights and 4:2:0 chroma"): uni[l][r] is addWeightUni's form of list l's reference r, shift the
+// slice's common shift' of addWeightBi.  The weight of list l's reference r is wps_l[stride * r] (stride 2: one component of (Cb, Cr) pairs).
+struct PredBiRefsWp {
+  bool identity = true;   // every weight of both lists: the picture is hmme_predict_bi_refs_device's
+  hmme::MePredWp<1> uni[2][hmme::kMaxRefs] = {};
+  int shift = 0;
+};
+// In the header's order: 1. the argument errors of every weight of list 0, then of list 1; 2. two unequal shifts; 3. each weight alone, list 0
+// then list 1; 4. every pair (r0, r1), r0-major.  The message names the list and the reference(s).
+int predict_bi_refs_weight_eval(int bit_depth, const hmme_weight* wps0, int n0, const hmme_weight* wps1, int n1, int stride, PredBiRefsWp* out, char* msg, size_t n) {
+  const hmme_weight* const lists[2] = {wps0, wps1};
+  const int cnt[2] = {n0, n1};
+  static const char* const name[2] = {"L0", "L1"};
+  char why[192];
+  msg[0] = 0;
+  for (int l = 0; l < 2; ++l) {
+    if (bit_depth < 8 || bit_depth > 12) { snprintf(msg, n, "bit depth %d outside 8..12", bit_depth); return HMME_ERR_ARG; }
+    if (!lists[l]) { snprintf(msg, n, "null weights of list %d", l); return HMME_ERR_ARG; }
+    if (cnt[l] < 1 || cnt[l] > hmme::kMaxRefs) { snprintf(msg, n, "list %d: %d references outside 1..%d", l, cnt[l], hmme::kMaxRefs); return HMME_ERR_ARG; }
+    for (int r = 0; r < cnt[l]; ++r) {
+      const int rc = bi_weight_args(bit_depth, &lists[l][stride * r], name[l], why, sizeof why);
+      if (rc) { snprintf(msg, n, "list %d reference %d: %s", l, r, why); return rc; }
+    }
+  }
+  for (int l = 0; l < 2; ++l)
+    for (int r = 0; r < cnt[l]; ++r)
+      if (lists[l][stride * r].shift != wps0[0].shift) {
+        snprintf(msg, n, "list %d reference %d: shift %d differs from list 0 reference 0's %d (one log2WeightDenom per slice and component)", l, r,
+                 lists[l][stride * r].shift, wps0[0].shift);
+        return HMME_ERR_ARG;
+      }
+  bool all = true;
+  for (int l = 0; l < 2; ++l)
+    for (int r = 0; r < cnt[l]; ++r) {
+      bool id = true;
+      hmme::MePredWp<1> pw;
+      const int rc = other_weight_eval(bit_depth, &lists[l][stride * r], &id, &pw, why, sizeof why, name[l]);
+      if (rc) { snprintf(msg, n, "list %d reference %d: %s", l, r, why); return rc; }
+      all = all && id;
+      if (out) out->uni[l][r] = pw;
+    }
+  for (int r0 = 0; r0 < n0; ++r0)
+    for (int r1 = 0; r1 < n1; ++r1) {   // arguments and single lines have passed: only the pair's line can answer
+      const int rc = predict_bi_weight_eval(bit_depth, &wps0[stride * r0], &wps1[stride * r1], nullptr, why, sizeof why);
+      if (rc) { snprintf(msg, n, "list 0 reference %d with list 1 reference %d: %s", r0, r1, why); return rc; }
+    }
+  if (out) {
+    out->identity = all;
+    out->shift = wps0[0].shift + 1 + std::max(2, 14 - bit_depth);
+  }
+  return HMME_OK;
+}
+
+// the weights of a bi_refs prediction before anything else is looked at: comps == 2: (Cb, Cr) per reference, each component on its own
+int check_predict_bi_refs_weights(hmme_ctx* ctx, const char* who, const hmme_frame_params* fp, const hmme_weight* wps0, int n0, const hmme_weight* wps1, int n1,
+                                  int comps, PredBiRefsWp* bw) {
+  if (!fp) return fail(ctx, HMME_ERR_ARG, "%s: null params", who);
+  char msg[256];
+  for (int c = 0; c < comps; ++c) {
+    const int rc = predict_bi_refs_weight_eval(fp->bit_depth, wps0 ? wps0 + c : nullptr, n0, wps1 ? wps1 + c : nullptr, n1, comps, bw ? &bw[c] : nullptr, msg, sizeof msg);
+    if (rc) return comps == 2 ? fail(ctx, rc, "%s: %s: %s", who, c ? "Cr" : "Cb", msg) : fail(ctx, rc, "%s: %s", who, msg);
+  }
+  return HMME_OK;
+}
+// what a list count may be: luma 1..16 planes per list (two plane sets), 4:2:0 2 * (n0 + n1) <= 16 planes in the ONE set of the chroma kernel
+int bi_refs_counts(hmme_ctx* ctx, const char* who, const void* refs0, int n0, const void* refs1, int n1, int comps) {
   if (!refs0 || !refs1 || n0 < 1 || n0 > hmme::kMaxRefs || n1 < 1 || n1 > hmme::kMaxRefs)
     return fail(ctx, HMME_ERR_ARG, "%s: %d / %d reference pictures outside 1..%d (or a null plane list)", who, n0, n1, hmme::kMaxRefs);
+  if (comps == 2 && 2 * (n0 + n1) > hmme::kMaxRefs)
+    return fail(ctx, HMME_ERR_ARG, "%s: %d + %d reference pictures: a launch takes %d planes, %d references of both lists together", who, n0, n1, hmme::kMaxRefs, hmme::kMaxRefs / 2);
+  return HMME_OK;
+}
+
+// hmme_predict_bi_refs_device, _w_device and hmme_predict_chroma_bi_refs_device: ONE picture, ONE launch, every block from the planes its
+// direction and its two reference indices name.  Luma: me_predict_bi_kernel<T, 0 | 2, 1>, the two lists through the checks of predict_refs one
+// after the other (each up to 16 planes), list 1 against list 0's first plane for the size.  4:2:0 (comps == 2; refs_l: (Cb, Cr) per reference):
+// me_predict_chroma_kernel<T, 3, 0 | 2, PER> with list 0's planes, then list 1's, in one set.  weighted: the weights answer first; WP = 0
+// without weights and where every weight is the identity, else every block goes through the weighted tails.
+int predict_bi_refs(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, int comps, int width, int height,
+                    const hmme_frame_params* fp, const hmme_weight* wps0, const hmme_weight* wps1, bool weighted, const void* d_mv_field, const void* d_dir_field,
+                    const void* d_ref_field, int mv_per_ctu, void* d_out, void* d_out_cr, int out_pitch_bytes, void* stream) {
+  PredBiRefsWp bw[2];
+  int rc = weighted ? check_predict_bi_refs_weights(ctx, who, fp, wps0, n0, wps1, n1, comps, bw) : HMME_OK;
+  if (rc == HMME_OK) rc = bi_check(ctx, who, fp, 0);
+  if (rc == HMME_OK) rc = bi_refs_counts(ctx, who, refs0, n0, refs1, n1, comps);
+  if (rc) return rc;
+  const bool null_arg = !d_dir_field || !d_ref_field || !d_out || (comps == 2 && !d_out_cr);
+  hipStream_t s = (hipStream_t)stream;
   PredictArgs a;
-  rc = predict_args(ctx, who, refs0, n0, !d_dir_field || !d_ref_field || !d_out, fp, nullptr, d_mv_field, mv_per_ctu, out_pitch_bytes, &a, "reference");
+  PredictLaunch L;
+  if (comps == 2) {
+    const int np = 2 * (n0 + n1);
+    const hmme_plane* planes[hmme::kMaxRefs];   // list 0's (Cb, Cr) pairs, then list 1's: the kernel's set
+    for (int r = 0; r < 2 * n0; ++r) planes[r] = refs0[r];
+    for (int r = 0; r < 2 * n1; ++r) planes[2 * n0 + r] = refs1[r];
+    rc = predict_args(ctx, who, planes, np, null_arg, fp, nullptr, d_mv_field, mv_per_ctu, out_pitch_bytes, &a, "plane");
+    if (rc) return rc;
+    rc = predict_begin(ctx, who, planes, np, 2, width, height, fp, a, s, &L);
+    if (rc || !L.acquired) return rc;
+    if (L.count) {
+      const hmme::MeChromaSrc src = {L.pl.refs, (const uint8_t*)d_dir_field, n0, L.n_ctu};
+      if (weighted && !(bw[0].identity && bw[1].identity)) {
+        hmme::MeChromaWp<3, 2> cw = {};
+        cw.ref_field = (const uint8_t*)d_ref_field; cw.n_refs1 = n1;
+        for (int c = 0; c < 2; ++c) {
+          cw.shift[c] = bw[c].shift;
+          for (int r = 0; r < n0; ++r) cw.ref[2 * r + c] = bw[c].uni[0][r];
+          for (int r = 0; r < n1; ++r) cw.ref[2 * (n0 + r) + c] = bw[c].uni[1][r];
+        }
+        rc = launch_chroma<3, 2>(ctx, planes[0], src, (const int16_t*)d_mv_field, mv_per_ctu, L, d_out, d_out_cr, out_pitch_bytes, s, cw);
+      } else {
+        rc = launch_chroma<3, 0>(ctx, planes[0], src, (const int16_t*)d_mv_field, mv_per_ctu, L, d_out, d_out_cr, out_pitch_bytes, s,
+                                 hmme::MeChromaWp<3, 0>{(const uint8_t*)d_ref_field, n1});
+      }
+    }
+    return pairs_end(ctx, planes, planes, np, s, rc);   // whatever the launch returned: the scratch is acquired
+  }
+  rc = predict_args(ctx, who, refs0, n0, null_arg, fp, nullptr, d_mv_field, mv_per_ctu, out_pitch_bytes, &a, "reference");
   if (rc) return rc;
   const hmme_plane* first0[hmme::kMaxRefs];
   for (int r = 0; r < n1; ++r) {
     if (!refs1[r]) return fail(ctx, HMME_ERR_ARG, "%s: null plane", who);
     first0[r] = refs0[0];
   }
-  hipStream_t s = (hipStream_t)stream;
-  PredictLaunch L;
   rc = predict_begin(ctx, who, refs0, n0, 1, 0, 0, fp, a, s, &L);
   PairLaunch l1;   // list 1: this context, fp's bit depth, list 0's size; ordered like references
   if (rc == HMME_OK) rc = named(ctx, who, pairs_begin(ctx, first0, refs1, n1, &a.f, s, &l1));
@@ -3403,40 +3650,107 @@ int hmme_predict_bi_refs_device(hmme_ctx* ctx, const hmme_plane* const* refs0, i
   const hmme::MePredBiRefs<1> br = {{L.pl.refs, l1.refs}, (const uint8_t*)d_ref_field, {n0, n1}};
   with_sample_type(p0->bps, [&](auto sample) {
     using T = decltype(sample);
-    hipLaunchKernelGGL((hmme::me_predict_bi_kernel<T, 0, 1>), dim3((unsigned)L.count), dim3(256), 0, s, (const uint8_t*)nullptr, (const uint8_t*)nullptr, p0->pitch,
-                       (const int16_t*)d_mv_field, (const uint8_t*)d_dir_field, mv_per_ctu, L.n_ctu, L.first, L.w, L.h, p0->bit_depth, (uint8_t*)d_out, out_pitch_bytes,
-                       hmme::MePredBiWp<0>{}, br);
+    const auto go = [&](auto kernel, auto wp) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)L.count), dim3(256), 0, s, (const uint8_t*)nullptr, (const uint8_t*)nullptr, p0->pitch, (const int16_t*)d_mv_field,
+                         (const uint8_t*)d_dir_field, mv_per_ctu, L.n_ctu, L.first, L.w, L.h, p0->bit_depth, (uint8_t*)d_out, out_pitch_bytes, wp, br);
+    };
+    if (weighted && !bw[0].identity) {
+      hmme::MePredBiWp<2> kw = {};
+      for (int l = 0; l < 2; ++l)
+        for (int r = 0; r < (l ? n1 : n0); ++r) kw.ref[l][r] = bw[0].uni[l][r];
+      kw.shift = bw[0].shift;
+      go(hmme::me_predict_bi_kernel<T, 2, 1>, kw);
+    } else {
+      go(hmme::me_predict_bi_kernel<T, 0, 1>, hmme::MePredBiWp<0>{});
+    }
   });
   if (hipGetLastError() != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "%s: launch failed", who);
   return lists_end(ctx, refs0, n0, refs1, n1, s, rc);   // whatever the launch returned: the scratch is acquired
 }
 
-int hmme_predict_bi_refs_frame(hmme_ctx* ctx, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, const hmme_frame_params* fp,
-                               const int16_t* mv_field, const uint8_t* dir_field, const uint8_t* ref_field, int mv_per_ctu, void* out, int out_stride) {
-  if (!ctx) return HMME_ERR_ARG;
-  const char* who = "hmme_predict_bi_refs_frame";
-  int rc = bi_check(ctx, who, fp, 0);   // before anything is staged
+// the _frame forms of the three; refs_l: `comps` planes per reference, outs: `comps` images.  The weights answer first.
+int predict_bi_refs_frame(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, int comps, int width, int height,
+                          const hmme_frame_params* fp, const hmme_weight* wps0, const hmme_weight* wps1, bool weighted, const int16_t* mv_field, const uint8_t* dir_field,
+                          const uint8_t* ref_field, int mv_per_ctu, void* const* outs, int out_stride) {
+  int rc = weighted ? check_predict_bi_refs_weights(ctx, who, fp, wps0, n0, wps1, n1, comps, nullptr) : HMME_OK;   // before anything is staged
+  if (rc == HMME_OK) rc = bi_check(ctx, who, fp, 0);
   if (rc) return rc;
-  if (!refs0 || !refs1 || n0 < 1 || n0 > hmme::kMaxRefs || n1 < 1 || n1 > hmme::kMaxRefs || !refs0[0])
-    return fail(ctx, HMME_ERR_ARG, "%s: %d / %d reference pictures outside 1..%d (or a null plane)", who, n0, n1, hmme::kMaxRefs);
-  rc = frame_args(ctx, who, fp, refs0, n0, 1, !mv_field || !dir_field || !ref_field || !out, mv_per_ctu, 0, 0);
-  if (rc == HMME_OK) rc = frame_args(ctx, who, fp, refs1, n1, 1, false, mv_per_ctu, 0, 0);
+  if (comps == 2) rc = bi_refs_counts(ctx, who, refs0, n0, refs1, n1, comps);
+  else if (!refs0 || !refs1 || n0 < 1 || n0 > hmme::kMaxRefs || n1 < 1 || n1 > hmme::kMaxRefs || !refs0[0])
+    rc = fail(ctx, HMME_ERR_ARG, "%s: %d / %d reference pictures outside 1..%d (or a null plane)", who, n0, n1, hmme::kMaxRefs);
+  if (rc) return rc;
+  if (comps == 2 && !refs0[0]) return fail(ctx, HMME_ERR_ARG, "%s: null plane", who);
+  rc = frame_args(ctx, who, fp, refs0, comps * n0, comps, !mv_field || !dir_field || !ref_field || frame_null_outs(outs, comps), mv_per_ctu, width, height);
+  if (rc == HMME_OK) rc = frame_args(ctx, who, fp, refs1, comps * n1, comps, false, mv_per_ctu, width, height);
   if (rc) return rc;
   const hmme_plane* p0 = refs0[0];
   if (p0->ctx != ctx) return fail(ctx, HMME_ERR_ARG, "%s: plane belongs to another context (planes are used with the context that created them)", who);
   if (out_stride < p0->width) return fail(ctx, HMME_ERR_ARG, "%s: output stride %d below the picture width", who, out_stride);
   // blocks without a direction or a reference, too, come back as they were
-  const size_t blocks = (size_t)p0->n_ctu * mv_per_ctu, row = (size_t)p0->width * p0->bps;
+  const size_t blocks = (size_t)(comps == 2 ? hmme_num_ctus(width, height) : p0->n_ctu) * mv_per_ctu, row = (size_t)p0->width * p0->bps;
   Stage st(ctx);
   const int field = st.in(mv_field, sizeof(int16_t) * 2 * blocks * 2), dirs = st.in(dir_field, blocks), rfield = st.in(ref_field, 2 * blocks);
-  const int img = st.image(out, row, p0->height, (size_t)out_stride * p0->bps);
+  const int img = st.image(outs[0], row, p0->height, (size_t)out_stride * p0->bps);
+  const int img1 = st.image(comps == 2 ? outs[1] : nullptr, row, p0->height, (size_t)out_stride * p0->bps);
   rc = st.begin();
-  if (rc == HMME_OK) {
-    rc = hmme_predict_bi_refs_device(ctx, refs0, n0, refs1, n1, fp, st.at(field), st.at(dirs), st.at(rfield), mv_per_ctu, st.at(img), (int)row, ctx->stream);
-    if (rc && ctx->err.compare(0, strlen("hmme_predict_bi_refs_device"), "hmme_predict_bi_refs_device") == 0)
-      ctx->err.replace(0, strlen("hmme_predict_bi_refs_device"), who);   // the refusal names the entry the caller made
-  }
+  if (rc == HMME_OK)
+    rc = predict_bi_refs(ctx, who, refs0, n0, refs1, n1, comps, width, height, fp, wps0, wps1, weighted, st.at(field), st.at(dirs), st.at(rfield), mv_per_ctu, st.at(img),
+                         st.at(img1), (int)row, ctx->stream);
   return rc ? rc : st.end();
+}
+}  // namespace
+
+int hmme_predict_bi_refs_device(hmme_ctx* ctx, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, const hmme_frame_params* fp,
+                                const void* d_mv_field, const void* d_dir_field, const void* d_ref_field, int mv_per_ctu, void* d_out, int out_pitch_bytes,
+                                void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  return predict_bi_refs(ctx, "hmme_predict_bi_refs_device", refs0, n0, refs1, n1, 1, 0, 0, fp, nullptr, nullptr, false, d_mv_field, d_dir_field, d_ref_field, mv_per_ctu,
+                         d_out, nullptr, out_pitch_bytes, stream);
+}
+
+int hmme_predict_bi_refs_frame(hmme_ctx* ctx, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, const hmme_frame_params* fp,
+                               const int16_t* mv_field, const uint8_t* dir_field, const uint8_t* ref_field, int mv_per_ctu, void* out, int out_stride) {
+  if (!ctx) return HMME_ERR_ARG;
+  return predict_bi_refs_frame(ctx, "hmme_predict_bi_refs_frame", refs0, n0, refs1, n1, 1, 0, 0, fp, nullptr, nullptr, false, mv_field, dir_field, ref_field, mv_per_ctu,
+                               &out, out_stride);
+}
+
+// ---- ... with a weight per reference, and for Cb / Cr (the rule: include/hmme.h, "multi-reference B pictures: explicit weights and 4:2:0 chroma")
+int hmme_predict_bi_refs_weight_check(int bit_depth, const hmme_weight* wps0, int n0, const hmme_weight* wps1, int n1) {
+  char msg[256];
+  return predict_bi_refs_weight_eval(bit_depth, wps0, n0, wps1, n1, 1, nullptr, msg, sizeof msg);
+}
+
+int hmme_predict_bi_refs_w_device(hmme_ctx* ctx, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, const hmme_frame_params* fp,
+                                  const hmme_weight* wps0, const hmme_weight* wps1, const void* d_mv_field, const void* d_dir_field, const void* d_ref_field,
+                                  int mv_per_ctu, void* d_out, int out_pitch_bytes, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  return predict_bi_refs(ctx, "hmme_predict_bi_refs_w_device", refs0, n0, refs1, n1, 1, 0, 0, fp, wps0, wps1, true, d_mv_field, d_dir_field, d_ref_field, mv_per_ctu, d_out,
+                         nullptr, out_pitch_bytes, stream);
+}
+
+int hmme_predict_bi_refs_w_frame(hmme_ctx* ctx, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, const hmme_frame_params* fp,
+                                 const hmme_weight* wps0, const hmme_weight* wps1, const int16_t* mv_field, const uint8_t* dir_field, const uint8_t* ref_field,
+                                 int mv_per_ctu, void* out, int out_stride) {
+  if (!ctx) return HMME_ERR_ARG;
+  return predict_bi_refs_frame(ctx, "hmme_predict_bi_refs_w_frame", refs0, n0, refs1, n1, 1, 0, 0, fp, wps0, wps1, true, mv_field, dir_field, ref_field, mv_per_ctu, &out,
+                               out_stride);
+}
+
+int hmme_predict_chroma_bi_refs_device(hmme_ctx* ctx, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, int width, int height,
+                                       const hmme_frame_params* fp, const hmme_weight* wps0, const hmme_weight* wps1, const void* d_mv_field, const void* d_dir_field,
+                                       const void* d_ref_field, int mv_per_ctu, void* d_out_cb, void* d_out_cr, int out_pitch_bytes, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  return predict_bi_refs(ctx, "hmme_predict_chroma_bi_refs_device", refs0, n0, refs1, n1, 2, width, height, fp, wps0, wps1, wps0 || wps1, d_mv_field, d_dir_field, d_ref_field,
+                         mv_per_ctu, d_out_cb, d_out_cr, out_pitch_bytes, stream);
+}
+
+int hmme_predict_chroma_bi_refs_frame(hmme_ctx* ctx, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, int width, int height,
+                                      const hmme_frame_params* fp, const hmme_weight* wps0, const hmme_weight* wps1, const int16_t* mv_field, const uint8_t* dir_field,
+                                      const uint8_t* ref_field, int mv_per_ctu, void* const* outs, int out_stride) {
+  if (!ctx) return HMME_ERR_ARG;
+  return predict_bi_refs_frame(ctx, "hmme_predict_chroma_bi_refs_frame", refs0, n0, refs1, n1, 2, width, height, fp, wps0, wps1, wps0 || wps1, mv_field, dir_field, ref_field,
+                               mv_per_ctu, outs, out_stride);
 }
 
 // ---- 4:2:0 chroma motion compensation from the luma motion fields ------------------------------------------------------------------------------

@@ -2270,7 +2270,8 @@ __device__ __forceinline__ int me_predict_block_sum(bool live, const uint8_t* or
 //            With OUT = 1 (hmme_search_frame_bi_refs_device: the origin against a reference per block of the other list) every block is
 //            written, and an index >= n_refs reads reference 0 -- the blocks outside the picture, whose index is 0xFF and whose MV (0,0).
 //   WP = 2:  WP = 1 with one weight per reference picture (hmme_predict_refs_w_device; REFS = 1 only): the block's reference index --
-//            already a scalar -- picks its MePredWp<1> among the sixteen in the kernel arguments.
+//            already a scalar -- picks its MePredWp<1> among the sixteen in the kernel arguments.  With OUT = 1
+//            (hmme_search_frame_bi_refs_w_device) the index is clamped before this lookup, too: an index >= n_refs takes reference 0's weight.
 template <int REFS> struct MePredRefs {};
 template <> struct MePredRefs<1> { RefSet set; const uint8_t* ref_field; int n_refs; };
 template <typename SrcT, int OUT, int WP = 0, int REFS = 0>
@@ -2303,7 +2304,8 @@ me_predict_kernel(const uint8_t* __restrict__ ref_origin, int ref_pitch, const i
     if (live) {
       const int r = lane >> 3, c = lane & 7;
       int v;
-      if constexpr (WP == 2) v = me_tail_weight_uni(sum, wp.ref[ri], k.maxv);   // live: ri < n_refs
+      if constexpr (WP == 2 && OUT == 1) v = me_tail_weight_uni(sum, wp.ref[ri < refs.n_refs ? ri : 0], k.maxv);   // reference 0's plane, and its weight
+      else if constexpr (WP == 2) v = me_tail_weight_uni(sum, wp.ref[ri], k.maxv);   // live: ri < n_refs
       else if constexpr (WP == 1) v = me_tail_weight_uni(sum, wp, k.maxv);
       else v = me_tail_uni(sum, k);
       if (OUT == 0) {
@@ -2985,8 +2987,14 @@ me_residual_kernel(RefSet cur_blocks, RefSet preds, int pred_pitch, const uint16
 //            block that uses a list whose index is >= n[l] (0xFF: no CU) is like a block without a direction: it reads no plane and
 //            writes nothing.  The index of a list the direction does not name is not looked at.  REFS = 0 takes an empty struct and
 //            compiles to what it did without it.
+//   WP = 2:  WP = 1 with one weight per reference picture and list (hmme_predict_bi_refs_w_device; REFS = 1 only).  Both indices are already
+//            scalars, so ref[l][index] is a scalar load of kernel arguments, clamped like the plane base: a block that is not live never
+//            indexes beyond its list.  Direction 1 / 2: me_tail_weight_uni with ref[l][r].  Direction 3: me_tail_weight_bi with the two
+//            entries' w0, the slice's common shift' = log2WeightDenom + 1 + headRoom and add = (1 + offset0 + offset1) * 2^(shift' - 1),
+//            formed here -- the host has checked every (r0, r1) pair's numerator against int32.
 template <int WP> struct MePredBiWp {};
 template <> struct MePredBiWp<1> { int w0, w1, add, shift; MePredWp<1> uni[2]; };
+template <> struct MePredBiWp<2> { MePredWp<1> ref[2][kMaxRefs]; int shift; };
 template <int REFS> struct MePredBiRefs {};
 template <> struct MePredBiRefs<1> { RefSet set[2]; const uint8_t* ref_field; int n[2]; };
 template <typename SrcT, int WP = 0, int REFS = 0>
@@ -3009,12 +3017,14 @@ me_predict_bi_kernel(const uint8_t* __restrict__ ref0, const uint8_t* __restrict
     bool in_pic = cu_x + bx < pic_w && cu_y + by < pic_h && dir >= 1 && dir <= 3;   // wave-uniform
     const uint8_t* origin0 = ref0;
     const uint8_t* origin1 = ref1;
+    int i0 = 0, i1 = 0;   // WP = 2: the clamped indices
     if constexpr (REFS) {
       const int r0 = __builtin_amdgcn_readfirstlane((int)refs.ref_field[e]);
       const int r1 = __builtin_amdgcn_readfirstlane((int)refs.ref_field[(long)n_ctu * mv_per_ctu + e]);
       in_pic = in_pic && (!(dir & 1) || r0 < refs.n[0]) && (!(dir & 2) || r1 < refs.n[1]);
       origin0 = refs.set[0].base[r0 < refs.n[0] ? r0 : 0];
       origin1 = refs.set[1].base[r1 < refs.n[1] ? r1 : 0];
+      if constexpr (WP == 2) { i0 = r0 < refs.n[0] ? r0 : 0; i1 = r1 < refs.n[1] ? r1 : 0; }
     }
     const bool use0 = in_pic && (dir & 1), use1 = in_pic && (dir & 2);
     int mx0 = 0, my0 = 0, mx1 = 0, my1 = 0;
@@ -3024,7 +3034,11 @@ me_predict_bi_kernel(const uint8_t* __restrict__ ref0, const uint8_t* __restrict
     const int sum1 = me_predict_block_sum<SrcT>(use1, origin1, ref_pitch, cu_x + bx, cu_y + by, mx1, my1, patch[wave], mid[wave], lane, k);
     if (in_pic) {
       int v;
-      if constexpr (WP) {
+      if constexpr (WP == 2) {
+        const MePredWp<1> a0 = wp.ref[0][i0], a1 = wp.ref[1][i1];
+        if (use0 && use1) v = me_tail_weight_bi(sum0, sum1, a0.w0, a1.w0, (1 + a0.offset + a1.offset) * (1 << (wp.shift - 1)), wp.shift, k.maxv);
+        else v = me_tail_weight_uni(use0 ? sum0 : sum1, use0 ? a0 : a1, k.maxv);   // wave-uniform
+      } else if constexpr (WP == 1) {
         if (use0 && use1) v = me_tail_weight_bi(sum0, sum1, wp.w0, wp.w1, wp.add, wp.shift, k.maxv);
         else v = me_tail_weight_uni(use0 ? sum0 : sum1, use0 ? wp.uni[0] : wp.uni[1], k.maxv);   // wave-uniform
       } else {
@@ -3097,15 +3111,24 @@ __device__ __forceinline__ int me_predict_chroma_sum(bool live, const uint8_t* o
 //           WP = 2: the MePredWp<1> of plane 2 * index + component.  An index >= n_refs is not live.
 //   FORM 2: me_predict_bi_kernel<SrcT, WP>: mv_field int16 [2][n_ctu][PER][2], dir_field uint8 [n_ctu][PER], set.base[0..1] list 0, [2..3]
 //           list 1 (hmme_predict_chroma_bi_device); WP = 1: one MePredBiWp<1> per component.  A direction outside 1..3 is not live.
+//   FORM 3: me_predict_bi_kernel<SrcT, WP, 1>: FORM 2 with a reference per block and list (hmme_predict_chroma_bi_refs_device): wp.ref_field
+//           uint8 [2][n_ctu][PER] is read beside the direction; set.base[2 * r + comp] is list 0's reference r (r < n_refs), set.base[2 *
+//           (n_refs + r) + comp] list 1's (r < n_refs1).  A block that uses a list whose index is beyond it is not live.  WP = 2: the
+//           MePredWp<1> of every plane, indexed like set.base -- the indices are uniform per 32 lanes, not per wave, so this is a per-lane
+//           index; the weights are therefore staged into LDS beside the taps, which keeps the kernel arguments out of scratch.  An index
+//           that is not used is clamped to 0 before any lookup.
 // The tails are the luma kernels' (WP = 0: me_tail_uni / me_tail_avg; else me_tail_weight_uni / me_tail_weight_bi), with the component's own
 // weight.  A block that is not live -- or whose luma block lies wholly outside
 // the picture -- reads no plane and writes nothing, and still meets every barrier.  Stores are samples of the planes' type, only inside the
 // chroma picture.
-struct MeChromaSrc { RefSet set; const uint8_t* field; int n_refs, n_ctu; };   // field: ref_field (FORM 1) / dir_field (FORM 2)
+struct MeChromaSrc { RefSet set; const uint8_t* field; int n_refs, n_ctu; };   // field: ref_field (FORM 1) / dir_field (FORM 2, 3)
 template <int FORM, int WP> struct MeChromaWp {};
 template <> struct MeChromaWp<0, 1> { MePredWp<1> c[2]; };
 template <> struct MeChromaWp<1, 2> { MePredWp<1> ref[kMaxRefs]; };
 template <> struct MeChromaWp<2, 1> { MePredBiWp<1> c[2]; };
+// FORM 3 carries its second field and list 1's count here, so that MeChromaSrc stays what the other forms take
+template <> struct MeChromaWp<3, 0> { const uint8_t* ref_field; int n_refs1; };
+template <> struct MeChromaWp<3, 2> { const uint8_t* ref_field; int n_refs1; int shift[2]; MePredWp<1> ref[kMaxRefs]; };   // ref[plane], indexed like set.base; shift[comp]: the bi shift'
 template <typename SrcT, int FORM, int WP, int PER>
 __global__ void __launch_bounds__(256)
 me_predict_chroma_kernel(MeChromaSrc src, int ref_pitch, const int16_t* __restrict__ mv_field, int ctu_first, int pic_w, int pic_h, int bit_depth,
@@ -3115,6 +3138,12 @@ me_predict_chroma_kernel(MeChromaSrc src, int ref_pitch, const int16_t* __restri
   __shared__ uint32_t taps[8];
   const int group = threadIdx.x >> 4, l16 = threadIdx.x & 15, comp = group & 1;
   if (threadIdx.x < 8) taps[threadIdx.x] = kChromaTaps[threadIdx.x];   // read behind the first barrier of the first pass
+  const int* s_wp = nullptr;   // FORM 3, WP 2: the planes' weights in LDS, read behind the barriers, too
+  if constexpr (FORM == 3 && WP == 2) {
+    __shared__ int s_weights[kMaxRefs * 4];
+    if (threadIdx.x < kMaxRefs * 4) s_weights[threadIdx.x] = ((const int*)wp.ref)[threadIdx.x];
+    s_wp = s_weights;
+  }
   const int ctus_x = (pic_w + 63) >> 6;
   const int ctu = ctu_first + blockIdx.x;
   const int cx = ctu % ctus_x, cy = ctu / ctus_x, cu_x = cx * 64, cu_y = cy * 64;
@@ -3138,25 +3167,39 @@ me_predict_chroma_kernel(MeChromaSrc src, int ref_pitch, const int16_t* __restri
       const bool ok = in_pic && dir >= 1 && dir <= 3;
       use0 = ok && (dir & 1); use1 = ok && (dir & 2);
     }
+    int sel1 = 1;   // the plane pair of list 1: FORM 2's second pair, FORM 3: n_refs + the index
+    if constexpr (FORM == 3) {
+      const int dir = src.field[e], r0 = wp.ref_field[e], r1 = wp.ref_field[(long)src.n_ctu * PER + e];
+      const bool ok = in_pic && dir >= 1 && dir <= 3 && (!(dir & 1) || r0 < src.n_refs) && (!(dir & 2) || r1 < wp.n_refs1);
+      use0 = ok && (dir & 1); use1 = ok && (dir & 2);
+      sel = use0 ? r0 : 0;
+      sel1 = src.n_refs + (use1 ? r1 : 0);
+    }
     int mx0 = 0, my0 = 0, mx1 = 0, my1 = 0;
     if (use0) me_field_mv(mv_field, e, cu_x, cu_y, pic_w, pic_h, mx0, my0);
     const int sum0 = me_predict_chroma_sum<SrcT>(use0, src.set.base[2 * sel + comp], ref_pitch, x0, y0, mx0, my0, patch[group], mid[group], l16, taps, k);
     int sum1 = 0;
-    if constexpr (FORM == 2) {
+    if constexpr (FORM >= 2) {
       if (use1) me_field_mv(mv_field, (long)src.n_ctu * PER + e, cu_x, cu_y, pic_w, pic_h, mx1, my1);
-      sum1 = me_predict_chroma_sum<SrcT>(use1, src.set.base[2 + comp], ref_pitch, x0, y0, mx1, my1, patch[group], mid[group], l16, taps, k);
+      sum1 = me_predict_chroma_sum<SrcT>(use1, src.set.base[2 * sel1 + comp], ref_pitch, x0, y0, mx1, my1, patch[group], mid[group], l16, taps, k);
     }
     if (use0 || use1) {
       int v;
-      if (FORM == 2 && use0 && use1) {
+      if (FORM >= 2 && use0 && use1) {
         if constexpr (FORM == 2 && WP == 1) v = me_tail_weight_bi(sum0, sum1, wp.c[comp].w0, wp.c[comp].w1, wp.c[comp].add, wp.c[comp].shift, k.maxv);
-        else v = me_tail_avg(sum0, sum1, k);
+        else if constexpr (FORM == 3 && WP == 2) {
+          const int* a0 = s_wp + 4 * (2 * sel + comp);    // {w0, round, shift, offset} of MePredWp<1>
+          const int* a1 = s_wp + 4 * (2 * sel1 + comp);
+          const int sh = wp.shift[comp];
+          v = me_tail_weight_bi(sum0, sum1, a0[0], a1[0], (1 + a0[3] + a1[3]) * (1 << (sh - 1)), sh, k.maxv);
+        } else v = me_tail_avg(sum0, sum1, k);
       } else {
         const int sum = use0 ? sum0 : sum1;
         if constexpr (WP != 0) {
           MePredWp<1> w;
           if constexpr (FORM == 0) w = wp.c[comp];
           else if constexpr (FORM == 1) w = wp.ref[2 * sel + comp];
+          else if constexpr (FORM == 3) { const int* a = s_wp + 4 * (2 * (use0 ? sel : sel1) + comp); w = MePredWp<1>{a[0], a[1], a[2], a[3]}; }
           else w = wp.c[comp].uni[use0 ? 0 : 1];
           v = me_tail_weight_uni(sum, w, k.maxv);
         } else {

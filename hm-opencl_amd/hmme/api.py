@@ -39,7 +39,11 @@ SYMBOLS = ["hmme_create", "hmme_destroy", "hmme_last_error", "hmme_device_info",
            "hmme_residual_pairs_device", "hmme_residual_frame",
            "hmme_search_frame_bi_refs_device", "hmme_refine_frame_bi_refs_device", "hmme_search_frame_bi_refs", "hmme_refine_frame_bi_refs",
            "hmme_select_dirs_refs_check", "hmme_select_dirs_refs_device", "hmme_select_dirs_refs_frame",
-           "hmme_predict_bi_refs_device", "hmme_predict_bi_refs_frame"]
+           "hmme_predict_bi_refs_device", "hmme_predict_bi_refs_frame",
+           "hmme_bipred_refs_weight_check", "hmme_search_frame_bi_refs_w_device", "hmme_refine_frame_bi_refs_w_device", "hmme_search_frame_bi_refs_w",
+           "hmme_refine_frame_bi_refs_w",
+           "hmme_predict_bi_refs_weight_check", "hmme_predict_bi_refs_w_device", "hmme_predict_bi_refs_w_frame",
+           "hmme_predict_chroma_bi_refs_device", "hmme_predict_chroma_bi_refs_frame"]
 # test / measurement entry points (include/hmme_test.h): not part of the boundary
 TEST_SYMBOLS = ["hmme_test_time_search_kernel", "hmme_test_device_address", "hmme_test_frac_deal", "hmme_test_tail_plan", "hmme_test_stage_layout", "hmme_test_picture_job", "hmme_test_time_weight_passes", "hmme_test_time_bipred_origin",
                 "hmme_test_time_wp_estimate_passes"]
@@ -239,6 +243,16 @@ def load():
     L.hmme_select_dirs_refs_frame.argtypes = [vp, i, i, i, pfp, C.POINTER(SelectParams), C.POINTER(DirRefsParams)] + [vp] * 12
     L.hmme_predict_bi_refs_device.argtypes = [vp, pvp, i, pvp, i, pfp, vp, vp, vp, i, vp, i, vp]
     L.hmme_predict_bi_refs_frame.argtypes = [vp, pvp, i, pvp, i, pfp, vp, vp, vp, i, vp, i]
+    L.hmme_bipred_refs_weight_check.argtypes = [i, pw, i, pw, i, i]
+    L.hmme_search_frame_bi_refs_w_device.argtypes = [vp, vp, pvp, i, pvp, i, pfp, pw, pw, vp, vp, i, vp, vp, vp, vp, vp]
+    L.hmme_refine_frame_bi_refs_w_device.argtypes = [vp, vp, pvp, i, pvp, i, pfp, pw, pw, vp, vp, i, vp, vp, vp, i, vp, vp, vp]
+    L.hmme_search_frame_bi_refs_w.argtypes = [vp, vp, pvp, i, pvp, i, pfp, pw, pw, vp, vp, i, vp, vp, vp, vp]
+    L.hmme_refine_frame_bi_refs_w.argtypes = [vp, vp, pvp, i, pvp, i, pfp, pw, pw, vp, vp, i, vp, vp, vp, i, vp, vp]
+    L.hmme_predict_bi_refs_weight_check.argtypes = [i, pw, i, pw, i]
+    L.hmme_predict_bi_refs_w_device.argtypes = [vp, pvp, i, pvp, i, pfp, pw, pw, vp, vp, vp, i, vp, i, vp]
+    L.hmme_predict_bi_refs_w_frame.argtypes = [vp, pvp, i, pvp, i, pfp, pw, pw, vp, vp, vp, i, vp, i]
+    L.hmme_predict_chroma_bi_refs_device.argtypes = [vp, pvp, i, pvp, i, i, i, pfp, pw, pw, vp, vp, vp, i, vp, vp, i, vp]
+    L.hmme_predict_chroma_bi_refs_frame.argtypes = [vp, pvp, i, pvp, i, i, i, pfp, pw, pw, vp, vp, vp, i, pvp, i]
     L.hmme_plane_stats.argtypes =[vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.hmme_wp_estimate.argtypes = [vp, vp, C.POINTER(vp), i, i, C.POINTER(Weight), C.POINTER(WpInfo)]
     L.hmme_wp_estimate_420.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, i, C.POINTER(Weight), C.POINTER(Weight), C.POINTER(WpInfo)]
@@ -896,8 +910,9 @@ class Engine:
         self._check(self.L.hmme_refine_frame_bi_refs_device(self.h, cur.h, _handles(refs), len(refs), _handles(others), len(others), C.byref(fp), d_other_mv,
                                                             d_other_ref, int(mv_per_ctu), d_center, d_pred, d_int_mv, int(use_hadamard), d_qmv, d_cost, stream))
 
-    def _frame_bi_refs(self, entry, cur, refs, others, sr, fen, other_mv, other_ref, int_mv, center_q, pred_q, use_hadamard, ctu_first, ctu_count):
-        """the two *_frame_bi_refs methods; int_mv: None for a search -> the two result tables [len(refs), count, 593, ...]"""
+    def _frame_bi_refs(self, entry, cur, refs, others, sr, fen, other_mv, other_ref, int_mv, center_q, pred_q, use_hadamard, ctu_first, ctu_count, weights=None):
+        """the *_frame_bi_refs and *_frame_bi_refs_w methods; int_mv: None for a search; weights: None or (searched list's, other list's) -> the
+        two result tables [len(refs), count, 593, ...]"""
         n = self.L.hmme_num_ctus(cur.width, cur.height)
         count = n - ctu_first if ctu_count < 0 else ctu_count
         fp = FrameParams(sr, int(fen), cur.bit_depth, ctu_first, count)
@@ -915,6 +930,9 @@ class Engine:
             keep.append(a)
             ptrs.append(a.ctypes.data)
         args = [f.ctypes.data, rf.ctypes.data, per] + ptrs
+        if weights is not None:
+            assert len(weights[0]) == len(refs) and len(weights[1]) == len(others)
+            args = [self._weights(weights[0]), self._weights(weights[1])] + args
         if int_mv is not None:
             int_mv = np.ascontiguousarray(int_mv, dtype=np.int16)
             assert int_mv.shape == (len(refs), count, NUM_PARTS, 2)
@@ -1108,6 +1126,77 @@ class Engine:
                                                         oa, cb.shape[1]))
         return cb, cr
 
+    # ---- multi-reference B pictures with explicit weights and in 4:2:0 (include/hmme.h, "multi-reference B pictures: explicit weights and
+    # 4:2:0 chroma"): one (w0, offset, shift, round) per reference of each list; chroma: per plane, (Cb, Cr) per reference, or None
+    def search_frame_bi_refs_w_device(self, cur, refs, others, fp, weights, other_weights, d_other_mv, d_other_ref, mv_per_ctu, d_center, d_pred, d_mv, d_sad, stream=0):
+        """hmme_search_frame_bi_refs_w_device: search_frame_bi_refs_device in a WP slice: weights[r] prices the candidates of refs[r], other_weights[o]
+        shapes the prediction of others[o] the ONE origin is built from"""
+        assert len(refs) == len(weights) and len(others) == len(other_weights)
+        self._check(self.L.hmme_search_frame_bi_refs_w_device(self.h, cur.h, _handles(refs), len(refs), _handles(others), len(others), C.byref(fp),
+                                                              self._weights(weights), self._weights(other_weights), d_other_mv, d_other_ref, int(mv_per_ctu), d_center,
+                                                              d_pred, d_mv, d_sad, stream))
+
+    def refine_frame_bi_refs_w_device(self, cur, refs, others, fp, weights, other_weights, d_other_mv, d_other_ref, mv_per_ctu, d_center, d_pred, d_int_mv,
+                                      use_hadamard, d_qmv, d_cost, stream=0):
+        """hmme_refine_frame_bi_refs_w_device: refine_frame_bi_refs_device in a WP slice"""
+        assert len(refs) == len(weights) and len(others) == len(other_weights)
+        self._check(self.L.hmme_refine_frame_bi_refs_w_device(self.h, cur.h, _handles(refs), len(refs), _handles(others), len(others), C.byref(fp),
+                                                              self._weights(weights), self._weights(other_weights), d_other_mv, d_other_ref, int(mv_per_ctu), d_center,
+                                                              d_pred, d_int_mv, int(use_hadamard), d_qmv, d_cost, stream))
+
+    def search_frame_bi_refs_w(self, cur, refs, others, sr, weights, other_weights, other_mv, other_ref, center_q=None, pred_q=None, ctu_first=0, ctu_count=-1):
+        """hmme_search_frame_bi_refs_w: search_frame_bi_refs with one weight per reference of both lists (FEN is not consulted)"""
+        return self._frame_bi_refs(self.L.hmme_search_frame_bi_refs_w, cur, refs, others, sr, 1, other_mv, other_ref, None, center_q, pred_q, True, ctu_first,
+                                   ctu_count, weights=(weights, other_weights))
+
+    def refine_frame_bi_refs_w(self, cur, refs, others, sr, weights, other_weights, other_mv, other_ref, int_mv, center_q=None, pred_q=None, use_hadamard=True,
+                               ctu_first=0, ctu_count=-1):
+        """hmme_refine_frame_bi_refs_w: refine_frame_bi_refs with one weight per reference of both lists"""
+        return self._frame_bi_refs(self.L.hmme_refine_frame_bi_refs_w, cur, refs, others, sr, 1, other_mv, other_ref, int_mv, center_q, pred_q, use_hadamard,
+                                   ctu_first, ctu_count, weights=(weights, other_weights))
+
+    def predict_bi_refs_w_device(self, refs0, refs1, fp, weights0, weights1, d_mv_field, d_dir_field, d_ref_field, mv_per_ctu, d_out, out_pitch_bytes, stream=0):
+        """hmme_predict_bi_refs_w_device: predict_bi_refs_device with weights0[r] for refs0[r] and weights1[r] for refs1[r]: uni blocks through
+        addWeightUni with their reference's weight, bi blocks through addWeightBi with the two weights their indices name"""
+        assert len(refs0) == len(weights0) and len(refs1) == len(weights1)
+        self._check(self.L.hmme_predict_bi_refs_w_device(self.h, _handles(refs0), len(refs0), _handles(refs1), len(refs1), C.byref(fp), self._weights(weights0),
+                                                         self._weights(weights1), d_mv_field, d_dir_field, d_ref_field, int(mv_per_ctu), d_out, int(out_pitch_bytes),
+                                                         stream))
+
+    def predict_bi_refs_w_frame(self, refs0, refs1, weights0, weights1, mv_field, dir_field, ref_field, out=None, ctu_first=0, ctu_count=-1):
+        """hmme_predict_bi_refs_w_frame: predict_bi_refs_frame with one weight per reference of each list"""
+        assert len(refs0) == len(weights0) and len(refs1) == len(weights1)
+        r0 = refs0[0]
+        f, per, df, fp = self._predict_fields(r0, r0.width, r0.height, mv_field, dir_field, 2, ctu_first, ctu_count)
+        rf = np.ascontiguousarray(ref_field, dtype=np.uint8).reshape(2, df.shape[0], -1)
+        assert rf.shape == (2,) + df.shape
+        out = self._image(r0, out)
+        self._check(self.L.hmme_predict_bi_refs_w_frame(self.h, _handles(refs0), len(refs0), _handles(refs1), len(refs1), C.byref(fp), self._weights(weights0),
+                                                        self._weights(weights1), f.ctypes.data, df.ctypes.data, rf.ctypes.data, per, out.ctypes.data, out.shape[1]))
+        return out
+
+    def predict_chroma_bi_refs_device(self, refs0, refs1, width, height, fp, d_mv_field, d_dir_field, d_ref_field, mv_per_ctu, d_out_cb, d_out_cr, out_pitch_bytes,
+                                      weights0=None, weights1=None, stream=0):
+        """hmme_predict_chroma_bi_refs_device: the Cb and Cr prediction of one B picture, every block from the plane pairs of refs0 / refs1 = [cb0,
+        cr0, cb1, ...] its two reference indices name (up to 8 references in both lists together); fields as predict_bi_refs_device takes them"""
+        assert len(refs0) % 2 == 0 and len(refs1) % 2 == 0
+        self._check(self.L.hmme_predict_chroma_bi_refs_device(self.h, _handles(refs0), len(refs0) // 2, _handles(refs1), len(refs1) // 2, int(width), int(height),
+                                                              C.byref(fp), self._weights_or_none(weights0, len(refs0)), self._weights_or_none(weights1, len(refs1)),
+                                                              d_mv_field, d_dir_field, d_ref_field, int(mv_per_ctu), d_out_cb, d_out_cr, int(out_pitch_bytes), stream))
+
+    def predict_chroma_bi_refs_frame(self, refs0, refs1, width, height, mv_field, dir_field, ref_field, outs=None, weights0=None, weights1=None, ctu_first=0,
+                                     ctu_count=-1):
+        """hmme_predict_chroma_bi_refs_frame: predict_bi_refs_frame for Cb and Cr; refs0 / refs1 = [cb0, cr0, cb1, cr1, ...] -> (cb, cr)"""
+        assert len(refs0) % 2 == 0 and len(refs1) % 2 == 0
+        f, per, df, fp = self._predict_fields(refs0[0], width, height, mv_field, dir_field, 2, ctu_first, ctu_count)
+        rf = np.ascontiguousarray(ref_field, dtype=np.uint8).reshape(2, df.shape[0], -1)
+        assert rf.shape == (2,) + df.shape
+        cb, cr, oa = self._chroma_images(refs0[0], outs)
+        self._check(self.L.hmme_predict_chroma_bi_refs_frame(self.h, _handles(refs0), len(refs0) // 2, _handles(refs1), len(refs1) // 2, int(width), int(height),
+                                                             C.byref(fp), self._weights_or_none(weights0, len(refs0)), self._weights_or_none(weights1, len(refs1)),
+                                                             f.ctypes.data, df.ctypes.data, rf.ctypes.data, per, oa, cb.shape[1]))
+        return cb, cr
+
     # ---- estimating explicit weighted-prediction parameters (include/hmme.h, "estimating explicit weighted-prediction parameters") ----
     def plane_stats(self, plane):
         """hmme_plane_stats: xCalcACDCParamSlice of one picture -> (dc_sum, ac) = (sum of the samples, sum of |sample - normDC|) over the picture
@@ -1202,6 +1291,28 @@ def predict_bi_weight_check(bit_depth, wp0, wp1):
     w0 = None if wp0 is None else C.byref(Weight(*[int(v) for v in wp0]))
     w1 = None if wp1 is None else C.byref(Weight(*[int(v) for v in wp1]))
     return int(load().hmme_predict_bi_weight_check(int(bit_depth), w0, w1))
+
+
+def predict_bi_refs_weight_check(bit_depth, wps0, wps1, n0=None, n1=None):
+    """hmme_predict_bi_refs_weight_check: 0, or the HMME_ERR_* code with which hmme_predict_bi_refs_w_device refuses the weights of a picture's two
+    lists (wps0 / wps1: one (w0, offset, shift, round) per reference; None passes a null pointer; n0 / n1: the counts passed, default the
+    lengths) at this bit depth (pure host arithmetic: needs no GPU)"""
+    a0 = None if wps0 is None else Engine._weights(wps0)
+    a1 = None if wps1 is None else Engine._weights(wps1)
+    n0 = (0 if wps0 is None else len(wps0)) if n0 is None else n0
+    n1 = (0 if wps1 is None else len(wps1)) if n1 is None else n1
+    return int(load().hmme_predict_bi_refs_weight_check(int(bit_depth), a0, int(n0), a1, int(n1)))
+
+
+def bipred_refs_weight_check(bit_depth, wps, other_wps, refine=False, n_refs=None, n_others=None):
+    """hmme_bipred_refs_weight_check: 0, or the HMME_ERR_* code with which the *_frame_bi_refs_w calls refuse the weights of the searched list
+    (wps) and of the other list (other_wps); None passes a null pointer; n_refs / n_others: the counts passed, default the lengths (pure host
+    arithmetic: needs no GPU)"""
+    a = None if wps is None else Engine._weights(wps)
+    b = None if other_wps is None else Engine._weights(other_wps)
+    n_refs = (0 if wps is None else len(wps)) if n_refs is None else n_refs
+    n_others = (0 if other_wps is None else len(other_wps)) if n_others is None else n_others
+    return int(load().hmme_bipred_refs_weight_check(int(bit_depth), a, int(n_refs), b, int(n_others), 1 if refine else 0))
 
 
 def select_check(sel):

@@ -686,7 +686,8 @@ int hmme_predict_bi_frame(hmme_ctx* ctx, const hmme_plane* ref0, const hmme_plan
  *   5. hmme_predict_bi_refs_device: the prediction from the two-list field, the direction field and the two reference-index fields;
  *   6. hmme_residual_pairs_device.
  * New entry points and one new struct; no struct and no existing entry point changed, so HMME_ABI_VERSION stays 6.
- * THIS TEXT PLUS THE CITATIONS IS THE RULE.  Out of scope: the _w (explicit weighted prediction) forms of the three parts; the chroma form of the prediction;
+ * THIS TEXT PLUS THE CITATIONS IS THE RULE.  The _w (explicit weighted prediction) forms of the bi pass and of the prediction, and the chroma
+ * form of the prediction: "multi-reference B pictures: explicit weights and 4:2:0 chroma" below.  Out of scope:
  * GPB_SIMPLE_UNI's copy of list-0 results into list 1; MvdL1ZeroFlag; HM's further bi iterations (hmme_select_dirs_device, too, takes each
  * list's first iteration only).
  *
@@ -903,6 +904,116 @@ int hmme_predict_chroma_bi_device(hmme_ctx* ctx, const hmme_plane* const* refs0,
 int hmme_predict_chroma_bi_frame(hmme_ctx* ctx, const hmme_plane* const* ref0, const hmme_plane* const* ref1, int width, int height, const hmme_frame_params* fp,
                                  const hmme_weight* wp0, const hmme_weight* wp1, const int16_t* mv_field, const uint8_t* dir_field, int mv_per_ctu, void* const* outs,
                                  int out_stride);
+
+/* ---- multi-reference B pictures: explicit weights and 4:2:0 chroma -------------------------------------------------------
+ * Steps 3 and 5 of the pipeline of "B pictures with several references per list" for a slice with explicit weighted prediction, and step 5
+ * for the Cb / Cr of a 4:2:0 picture: the bi pass with a weight per reference of both lists, hmme_predict_bi_refs_device with a weight per
+ * reference of each list, and its chroma form with optional weights.  The weights are what hmme_wp_estimate / hmme_wp_estimate_420 deliver
+ * for the references of both lists in ONE call.  New entry points only; no struct and no existing entry point changed, so HMME_ABI_VERSION
+ * stays 6.  THIS TEXT PLUS THE CITATIONS IS THE RULE (paths below source/Lib/TLibCommon/ unless they name another directory).  Every weight
+ * array is HOST memory, read before the call returns.  "Identity" means w0 == 1 << shift and offset == 0, whatever round holds -- the
+ * prediction family's meaning; the SEARCHED list of the bi pass is the exception: there the *_w family's meaning applies, which also asks
+ * for round == (shift ? 1 << (shift - 1) : 0).
+ * The decision between the two (hmme_select_dirs_refs_device) needs no weighted form: it reads cost tables only, as hmme_select_dirs_device
+ * does in the single-reference WP pipeline.
+ *
+ * Luma.  hmme_predict_bi_refs_w_device / _frame: hmme_predict_bi_refs_device / _frame with wps0[n0] and wps1[n1].  Fields, liveness, the
+ * clamp of every MV, CTU sub-ranges, the limit of 16 planes per list, plane checks and stream ordering are unchanged.  A live block of
+ * direction d with indices (r0, r1) is bit for bit what hmme_predict_bi_w_frame(refs0[r0], refs1[r1], wps0[r0], wps1[r1], ...) writes for that
+ * block -- TComWeightPrediction::getWpScaling(pcCU, iRefIdx0, iRefIdx1, ...) (TComWeightPrediction.cpp:189-264), called with the PU's own
+ * indices (:268-301 xWeightedPredictionBi, :312-329 xWeightedPredictionUni):
+ *   direction 1 / 2   addWeightUni with that reference's weight (the index of the list the direction does not name is not looked at)
+ *   direction 3       addWeightBi with w0 = wps0[r0].w0, w1 = wps1[r1].w0, off = wps0[r0].offset + wps1[r1].offset,
+ *                     shift' = shift + 1 + head, round' = 1 << (shift' - 1)   -- the formula of hmme_predict_bi_w_device
+ * If every weight of both lists is the identity the kernel of hmme_predict_bi_refs_device runs.  Otherwise every block goes through the
+ * weighted tails, which for identity weights equal the unweighted sample: the nested floors (uni) and the addAvg identity (bi) proved in
+ * "the final prediction in a slice with explicit weighted prediction".
+ *
+ * hmme_predict_bi_refs_weight_check(bit_depth, wps0, n0, wps1, n1), a pure host function (no context, no GPU).  The _w calls run it first
+ * and launch and write NOTHING if it fails; they return its code, hmme_last_error names the list and the reference(s).  In this order, the
+ * first failure deciding:
+ *   1. argument errors of list 0, then of list 1: bit depth outside 8..12, a NULL array, n outside 1..16,
+ *      a shift outside 0..15 (in the order of the references)                                            -> HMME_ERR_ARG
+ *   2. two unequal shifts anywhere among the n0 + n1 weights (luma has ONE log2WeightDenom per slice)     -> HMME_ERR_ARG
+ *   3. each weight alone, list 0 in order, then list 1: the single-weight line of
+ *      hmme_predict_bi_weight_check (|w0| * 40 960 + round'_uni beyond int32)                             -> HMME_ERR_UNSUPPORTED
+ *   4. every pair (r0, r1), r0-major: the pair line of hmme_predict_bi_weight_check                       -> HMME_ERR_UNSUPPORTED
+ * So an argument error of list 1 is reported before a range of list 0, and n0 = n1 = 1 is hmme_predict_bi_weight_check.  Every pair is
+ * checked, whether or not a block names it: the launch is safe for any field.
+ *
+ * 4:2:0.  hmme_predict_chroma_bi_refs_device / _frame: the Cb and Cr of the same picture from the luma call's three fields, in the
+ * conventions of "4:2:0 chroma motion compensation": refs0 holds 2 * n0 planes, (Cb, Cr) per reference, refs1 2 * n1; width x height is the
+ * LUMA size; wps0 / wps1 hold 2 * n0 / 2 * n1 weights in the planes' order, or both are NULL (one NULL beside an array: HMME_ERR_ARG).  A
+ * launch takes at most 16 planes, so n0 + n1 <= 8 -- 4 + 4 is HM's low-delay B exactly; more is HMME_ERR_ARG.  A block is live if its luma
+ * block starts inside the luma picture, its direction is 1..3 and every list the direction names has an index < that list's count; a block
+ * that is not live reads nothing and writes nothing.  The two 4x4 blocks of a live luma block are what hmme_predict_chroma_bi_frame writes with
+ * the planes -- and the component's weights -- the indices name.  Each component's weights go through the four steps above on their own:
+ * shifts are equal WITHIN a component over all references of both lists, Cb and Cr may differ from each other; Cb answers before Cr.  NULL
+ * weights, or identities throughout, run the unweighted form.  Every other refusal is that of hmme_predict_chroma_bi_device.  The _frame form
+ * is synchronous: host fields, outs = (Cb, Cr) host images of the chroma size, out_stride in samples.
+ *
+ * The bi pass.  hmme_search_frame_bi_refs_w_device / hmme_refine_frame_bi_refs_w_device: hmme_search_frame_bi_refs_device /
+ * hmme_refine_frame_bi_refs_device with wps[n_refs] for the searched list and other_wps[n_others] for the other list.  For reference r and
+ * CTU c the result is what hmme_search_ctu_w / hmme_refine_ctu_w return with the weight wps[r] on the origin 2 * B - P, each 8x8 block of P
+ * being the addWeightUni prediction -- rule 1 of "bi-prediction with explicit weighted prediction", with its getUseWP() quirk -- from
+ * others[o] with other_wps[o], o = d_other_ref[block].  An index >= n_others reads reference 0 AND reference 0's weight.  fp->fen is not
+ * consulted (xGetSADw reads every row).  A launch in which every weight of both lists is the identity IS the unweighted call with fen = 0;
+ * if only the other weights are all identities the origin is the unweighted one; otherwise every block of P goes through addWeightUni
+ * (nested floors: an identity weight gives the unweighted sample).  Shapes, limits, plane checks and stream ordering are those of the
+ * unweighted calls.  hmme_search_frame_bi_refs_w / hmme_refine_frame_bi_refs_w: synchronous, host arrays of the same shapes.
+ * One origin, one bias.  The origin is built once per call and serves all n_refs references, so it carries ONE bias B for all of them:
+ * B = max(maxv, max_r(-wlo_r)), wlo_r the smallest weighted sample of wps[r] over [0, maxv] (hmme_bipred_weight_check's wlo).  Reference r's
+ * weighted u16 copy carries offset_r + B, the refinement takes B + offset_r off again; the results do not depend on B.  The 16-bit span
+ * line of hmme_bipred_weight_check, max(whi, 2 * maxv) + bias <= 65 535, cannot fail for the common bias once every weight passes its
+ * own lines: each weighted sample fits a Pel, so whi_r <= 32 767 and -wlo_r <= 32 768 for every r, hence B <= 32 768 (maxv <= 4095) and
+ * whi_r + B <= 65 535, while 2 * maxv + B <= 8 190 + 32 768.  That is derived, not measured.  So a set of weights is served exactly when
+ * every weight passes its lines of hmme_bipred_weight_check:
+ * hmme_bipred_refs_weight_check(bit_depth, wps, n_refs, other_wps, n_others, refine), a pure host function, run first by the four calls
+ * (refine = 1 in the refinement), which launch and write NOTHING if it fails.  In this order, the first failure deciding:
+ *   1. argument errors of the searched weights, then of the other weights: bit depth outside 8..12, a NULL array, a count outside
+ *      1..16, a shift outside 0..15 (in the order of the references)                                       -> HMME_ERR_ARG
+ *   2. the searched-weight lines of hmme_bipred_weight_check per reference, in order, with `refine`         -> HMME_ERR_UNSUPPORTED
+ *   3. the "other weight" line of hmme_bipred_weight_check per other reference, in order                     -> HMME_ERR_UNSUPPORTED
+ * The 12-bit refinement stays refused for every weight.  With one reference per list this is hmme_bipred_weight_check.
+ *
+ * The pipeline of a 4:2:0 B picture of a WP slice with n0 / n1 references, all on the device: hmme_wp_estimate_420 once for both lists;
+ *   1. hmme_search_pairs_w_device / hmme_refine_pairs_w_device per list (its references as pairs with the one current picture);
+ *   2. hmme_select_refs_device;
+ *   3. hmme_search_frame_bi_refs_w_device / hmme_refine_frame_bi_refs_w_device, once per list;
+ *   4. hmme_select_dirs_refs_device, unchanged (cost tables only);
+ *   5. hmme_predict_bi_refs_w_device and hmme_predict_chroma_bi_refs_device with the component weights;
+ *   6. hmme_residual_pairs_device per component.
+ * Without WP: steps 1-6 as they were, plus hmme_predict_chroma_bi_refs_device with NULL weights in step 5.
+ * Out of scope: GPB_SIMPLE_UNI; MvdL1ZeroFlag; HM's further bi iterations; the sequence layer (sequence.run_rank, tools/me_sequence.py). */
+int hmme_bipred_refs_weight_check(int bit_depth, const hmme_weight* wps, int n_refs, const hmme_weight* other_wps, int n_others, int refine);
+int hmme_search_frame_bi_refs_w_device(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others,
+                                       int n_others, const hmme_frame_params* fp, const hmme_weight* wps, const hmme_weight* other_wps, const void* d_other_mv,
+                                       const void* d_other_ref, int mv_per_ctu, const void* d_center_q, const void* d_pred_q, void* d_out_mv, void* d_out_sad,
+                                       void* stream);
+int hmme_refine_frame_bi_refs_w_device(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others,
+                                       int n_others, const hmme_frame_params* fp, const hmme_weight* wps, const hmme_weight* other_wps, const void* d_other_mv,
+                                       const void* d_other_ref, int mv_per_ctu, const void* d_center_q, const void* d_pred_q, const void* d_int_mv, int use_hadamard,
+                                       void* d_out_qmv, void* d_out_cost, void* stream);
+int hmme_search_frame_bi_refs_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
+                                const hmme_frame_params* fp, const hmme_weight* wps, const hmme_weight* other_wps, const int16_t* other_mv, const uint8_t* other_ref,
+                                int mv_per_ctu, const int16_t* center_q, const int16_t* pred_q, int16_t* out_mv, uint32_t* out_sad);
+int hmme_refine_frame_bi_refs_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
+                                const hmme_frame_params* fp, const hmme_weight* wps, const hmme_weight* other_wps, const int16_t* other_mv, const uint8_t* other_ref,
+                                int mv_per_ctu, const int16_t* center_q, const int16_t* pred_q, const int16_t* int_mv, int use_hadamard, int16_t* out_qmv,
+                                uint32_t* out_cost);
+int hmme_predict_bi_refs_weight_check(int bit_depth, const hmme_weight* wps0, int n0, const hmme_weight* wps1, int n1);
+int hmme_predict_bi_refs_w_device(hmme_ctx* ctx, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, const hmme_frame_params* fp,
+                                  const hmme_weight* wps0, const hmme_weight* wps1, const void* d_mv_field, const void* d_dir_field, const void* d_ref_field,
+                                  int mv_per_ctu, void* d_out, int out_pitch_bytes, void* stream);
+int hmme_predict_bi_refs_w_frame(hmme_ctx* ctx, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, const hmme_frame_params* fp,
+                                 const hmme_weight* wps0, const hmme_weight* wps1, const int16_t* mv_field, const uint8_t* dir_field, const uint8_t* ref_field,
+                                 int mv_per_ctu, void* out, int out_stride);
+int hmme_predict_chroma_bi_refs_device(hmme_ctx* ctx, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, int width, int height,
+                                       const hmme_frame_params* fp, const hmme_weight* wps0, const hmme_weight* wps1, const void* d_mv_field, const void* d_dir_field,
+                                       const void* d_ref_field, int mv_per_ctu, void* d_out_cb, void* d_out_cr, int out_pitch_bytes, void* stream);
+int hmme_predict_chroma_bi_refs_frame(hmme_ctx* ctx, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, int width, int height,
+                                      const hmme_frame_params* fp, const hmme_weight* wps0, const hmme_weight* wps1, const int16_t* mv_field, const uint8_t* dir_field,
+                                      const uint8_t* ref_field, int mv_per_ctu, void* const* outs, int out_stride);
 
 /* ---- residual and distortion of a prediction ------------------------------------------------------------------------
  * The first things HM does with a prediction, on the device: the residual, what the prediction costs per PU, and what coding no residual
