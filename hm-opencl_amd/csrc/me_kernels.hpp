@@ -116,6 +116,35 @@ __device__ __forceinline__ uint32_t me_min4(uint32_t a, uint32_t b, uint32_t c, 
                    "v"(c2), "v"(c3));                                                                           \
   }
 
+// Packed minimum (the PK twin of the search kernel, me_tree_pk_fen*.inc): a slot of an 8x8 CU -- 8x4, 4x8, 8x8: all-row sums of at most
+// kPkSlotMax -- whose packed sums p feed nothing as keys takes the minimum over the lane's four candidates on packed u16 COSTS:
+//   q = p + pkm        one 64-bit add (the compiler's v_lshl_add_u64); pkm = the four MV costs, kPkMarker where a candidate is invalid
+//   m = min of q's four fields    two v_pk_min_u16 (the second one reads the first one's two halves through op_sel)
+//   key = m * 1024 + ctag         one v_mad_u32_u16; ctag = iteration | lane << 2, j = 0
+// 4 instructions where ME_KEYS + ME_MIN4 are 6.  The key says which QUAD won, not which of its four candidates: me_pk_recover finds that
+// once per slot and job.  Exact while every valid cost + sum stays below the marker and the marker + any sum below 2^16: me_pk_gate decides
+// per launch (hmme.hip launch_search8).  An invalid candidate loses by value; a lane whose four candidates are all invalid carries
+// kInvCost << 10 in ctag, so ME_FLUSH drops it like any other invalid key.  The three instructions are one asm block (nothing padded
+// inside it; the first reads what the compiler's add wrote, which the compiler pads if it must).
+constexpr uint32_t kPkSlotMax = 64 * 255;                 // 16 320: the 8x8 CU, every sample difference 255
+constexpr uint32_t kPkMarker = 0xFFFFu - kPkSlotMax;      // 49 215: marker + any sum fits u16
+// The MV cost of a launch is at most (lambda_q16 * bits) >> 16 with bits <= 2 * 37: window and predictor components are int16 (integer
+// and quarter pels), so a component's difference is below 2^18 in quarter pels and me_component_bits at most 2 * 18 + 1.  The packed
+// path runs only where that bound + kPkSlotMax stays below the marker (and the product does not wrap uint32, or `cost` would be no bound).
+constexpr uint32_t kPkMaxBits = 2 * 37;
+__host__ __device__ inline bool me_pk_gate(uint32_t lambda_q16) {
+  const uint64_t prod = (uint64_t)lambda_q16 * kPkMaxBits;
+  return prod <= 0xFFFFFFFFull && (prod >> 16) + kPkSlotMax < kPkMarker;
+}
+#define ME_PKMIN(r, p)                                                                                          \
+  uint32_t r;                                                                                                   \
+  {                                                                                                             \
+    const uint64_t r##_q = (p) + pkm;                                                                           \
+    asm volatile("v_pk_min_u16 %0, %1, %2\n\tv_pk_min_u16 %0, %0, %0 op_sel:[0,1] op_sel_hi:[1,0]\n\t"                \
+                 "v_mad_u32_u16 %0, %0, %3, %4"                                                                 \
+                 : "=&v"(r) : "v"((uint32_t)r##_q), "v"((uint32_t)(r##_q >> 32)), "s"(mult_a), "v"(ctag));      \
+  }
+
 // butterfly transpose-reduce: merge two slot registers into one; lanes whose role bit is 0 keep
 // slot a (min over the lane pair), lanes whose role bit is 1 keep slot b.
 // Levels 0/1 (447 of the 588 merges): two DPP mins, the second one bank-masked so that it only
@@ -160,6 +189,61 @@ __device__ __forceinline__ uint32_t me_component_bits(int v) {
 // TComRdCost::getCost(x, y) with cost scale 2 (reference TComRdCost.h:172-189): uint32 wrap, >> 16
 __device__ __forceinline__ uint32_t me_mv_cost(uint32_t lambda_q16, int x, int y, int pred_x, int pred_y) {
   return (lambda_q16 * (me_component_bits((x << 2) - pred_x) + me_component_bits((y << 2) - pred_y))) >> 16;
+}
+
+// The slots that take the packed minimum in the PK twin (ME_PKMIN) and their rectangles in the CTU: 8x4 halves 0..127, 4x8 halves
+// 128..255, 8x8 CUs 384..447 (tools/gen_me_tree.py slot_2NxN / slot_Nx2N / slot_2Nx2N at size 8)
+__device__ __forceinline__ bool me_pk_slot(int s, int& x, int& y, int& w, int& h) {
+  if (s < 128) { x = (s & 7) * 8; y = (s >> 4) * 8 + ((s >> 3) & 1) * 4; w = 8; h = 4; return true; }
+  if (s < 256) { x = ((s >> 1) & 7) * 8 + (s & 1) * 4; y = ((s - 128) >> 4) * 8; w = 4; h = 8; return true; }
+  if (s >= 384 && s < 448) { x = (s & 7) * 8; y = ((s - 384) >> 3) * 8; w = 8; h = 8; return true; }
+  return false;
+}
+// PK twin: a packed slot's entry v = (cost, y, x of the winning quad's first candidate) of the workgroup's table -> the same entry with
+// the x of the winning candidate.  The slot's SAD is computed again for the quad's (up to four) valid candidates from the window still
+// in LDS and the job's current block; the FIRST j whose SAD + MV cost equals the minimum wins, as xPatternSearch's strict '<' has it
+// inside a row.  Between quads the order was settled by (cost, y, x of the quad), which is the raster order: quads do not overlap.
+// About 0.1 % of a job's absolute differences.  A quad starts on a window dword and a slot on a current-block dword (both x are multiples
+// of 4), so a row is RW / 4 + 1 window dwords and RW / 4 current-block dwords, candidate j four bytes at a time through v_alignbyte_b32 and
+// v_sad_u8; every load of the slot is issued before the first is used (one round trip: a workgroup of a segment launch runs a few
+// lane-iterations per job, and a byte-wise loop with a load per row cost it 3 %).
+template <int RW, int RH>
+__device__ __forceinline__ void me_pk_sads(const uint32_t* wrow, int pdw, const uint8_t* __restrict__ crow, uint32_t sad[4]) {
+  constexpr int ND = RW / 4;
+  uint32_t c[RH][ND], d[RH][ND + 1];
+#pragma unroll
+  for (int r = 0; r < RH; ++r) {
+#pragma unroll
+    for (int k = 0; k < ND; ++k) c[r][k] = *(const uint32_t*)(crow + r * 64 + 4 * k);
+#pragma unroll
+    for (int k = 0; k <= ND; ++k) d[r][k] = wrow[r * pdw + k];
+  }
+#pragma unroll
+  for (int r = 0; r < RH; ++r)
+#pragma unroll
+    for (int k = 0; k < ND; ++k) {
+      sad[0] = __builtin_amdgcn_sad_u8(d[r][k], c[r][k], sad[0]);
+#pragma unroll
+      for (int j = 1; j < 4; ++j) sad[j] = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(d[r][k + 1], d[r][k], (uint32_t)j), c[r][k], sad[j]);
+    }
+}
+__device__ __forceinline__ unsigned long long me_pk_recover(unsigned long long v, int s, const uint32_t* win, int pdw, const uint8_t* __restrict__ cur_blk,
+                                                            const MeJob& job, int wx, uint32_t lambda_q16) {
+  int rx, ry, rw, rh;
+  if (v == ~0ull || !me_pk_slot(s, rx, ry, rw, rh)) return v;
+  const int xq = (int)(v & 0xffff), y = (int)((v >> 16) & 0xffff);
+  const uint32_t cost = (uint32_t)(v >> 32);
+  const uint32_t* wrow = win + (y + ry) * pdw + ((xq + rx) >> 2);   // dwords (xq + rx) / 4 .. + rw / 4 <= 48 of a 49-dword row
+  const uint8_t* crow = cur_blk + ry * 64 + rx;
+  uint32_t sad[4] = {0u, 0u, 0u, 0u};
+  if (rh == 4) me_pk_sads<8, 4>(wrow, pdw, crow, sad);
+  else if (rw == 4) me_pk_sads<4, 8>(wrow, pdw, crow, sad);
+  else me_pk_sads<8, 8>(wrow, pdw, crow, sad);
+  const uint32_t by = me_component_bits(((job.lt_y + y) << 2) - job.pred_y);
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (xq + j < wx && sad[j] + ((lambda_q16 * (me_component_bits(((job.lt_x + xq + j) << 2) - job.pred_x) + by)) >> 16) == cost) return v + (unsigned long long)j;
+  return v;
 }
 
 // 16-bit kernel (three candidates per lane, one lane-iteration per task): key = cost << 8 | lane(6) | j(2).  The 24-bit cost field
@@ -332,7 +416,9 @@ constexpr int kTileStep = 129, kTileJobMask = 0x1fffffff;
 //            of jobs and however the picture's edge clips their windows.  jobs_v: MeSegTable layout (below).
 // n_seg_jobs: SPLIT = 2 only, the number of jobs the segment table covers
 // curs: the CTU-blocked copies of the current pictures (above me_prefetch_cur), cur_ctus_x: CTUs per picture row (blocks per block row).
-template <int FEN, int SPLIT>
+// PK = 1: the packed-minimum twin (ME_PKMIN above; every <FEN, SPLIT> has one).  Same results, fewer instructions per lane-iteration;
+// only for launches that pass me_pk_gate.
+template <int FEN, int SPLIT, int PK>
 __global__ void __launch_bounds__(kThreads, 2)
 me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_pitch,
                  const void* __restrict__ jobs_v, uint32_t lambda_q16, int16_t* __restrict__ out_mv,
@@ -526,6 +612,15 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
       }
       const uint32_t c0 = cc[0], c1 = cc[1], c2 = cc[2], c3 = cc[3];
       const uint32_t nc0 = 0u - c0, nc1 = 0u - c1, nc2 = 0u - c2, nc3 = 0u - c3;
+      // PK: the same four MV costs as packed u16 (the gate keeps them below kPkMarker - kPkSlotMax), and the lane's key constant
+      uint64_t pkm = 0;
+      uint32_t ctag = 0;
+      if constexpr (PK) {
+        const uint32_t m0 = cc[0] < (kInvCost << kIdxBits) ? cc[0] >> kIdxBits : kPkMarker, m1 = cc[1] < (kInvCost << kIdxBits) ? cc[1] >> kIdxBits : kPkMarker;
+        const uint32_t m2 = cc[2] < (kInvCost << kIdxBits) ? cc[2] >> kIdxBits : kPkMarker, m3 = cc[3] < (kInvCost << kIdxBits) ? cc[3] >> kIdxBits : kPkMarker;
+        pkm = (uint64_t)(m0 | m1 << 16) | (uint64_t)(m2 | m3 << 16) << 32;
+        ctag = ((vy && cx < wx) ? 0u : kInvCost << kIdxBits) | tag;   // candidate 0 is valid wherever one of the four is
+      }
       // lanes outside the window still run (wave-uniform code) on clamped, in-bounds addresses
       const lds_char_t* lpc = (const lds_char_t*)(win + min(cy, wy - 1) * kPDW + (min(cx, wx - 1) >> 2));
       // scalar loads complete out of order: ME8_CUR_WAIT (placed by the generator one CU after the loads, before the next CU's are
@@ -540,7 +635,13 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
   asm volatile("" : : "v"(d0), "v"(d1), "v"(d2), "v"(d3), "v"(d4), "v"(d5), "v"(d6), "v"(d7), "v"(d8), "v"(d9), "v"(d10), "v"(d11),  \
                "v"(d12), "v"(d13), "v"(d14), "v"(d15));                                                                             \
   asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(w0), "+s"(w1), "+s"(w2), "+s"(w3), "+s"(w4), "+s"(w5), "+s"(w6), "+s"(w7))
-      if constexpr (FEN) {
+      if constexpr (PK) {
+        if constexpr (FEN) {
+#include "me_tree_pk_fen1.inc"
+        } else {
+#include "me_tree_pk_fen0.inc"
+        }
+      } else if constexpr (FEN) {
 #include "me_tree_fen1.inc"
       } else {
 #include "me_tree_fen0.inc"
@@ -578,7 +679,8 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
   //       TEncSearch.cpp:3895: best - getCost(best))
   if constexpr (SPLIT) {
     for (int s = tid; s < kParts; s += kThreads) {
-      const unsigned long long v = best64[s];
+      unsigned long long v = best64[s];
+      if constexpr (PK) v = me_pk_recover(v, s, win, kPDW, (const uint8_t*)cur_addr, job, wx, lambda_q16);   // before the entry leaves the workgroup
       if (v != ~0ull) atomicMin(&g_best[(long)out_job * kParts + s], v + tile_off);
     }
     if constexpr (SPLIT == 2) {
@@ -587,7 +689,8 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
     return;
   }
   for (int s = tid; s < kParts; s += kThreads) {
-    const unsigned long long v = best64[s];
+    unsigned long long v = best64[s];
+    if constexpr (PK) v = me_pk_recover(v, s, win, kPDW, (const uint8_t*)cur_addr, job, wx, lambda_q16);
     const int mvx = job.lt_x + (int)(v & 0xffff), mvy = job.lt_y + (int)((v >> 16) & 0xffff);
     const uint32_t cost = (uint32_t)(v >> 32);
     const long o = (long)out_job * kParts + s;

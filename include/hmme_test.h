@@ -23,6 +23,11 @@ int hmme_test_time_search_kernel(hmme_ctx* ctx, const hmme_plane* cur, const hmm
  * out[2] = workgroups (segments) of the tail, out[3] = 1 if head and tail are one launch */
 int hmme_test_tail_plan(int width, int height, int search_range, int n_pairs, int slots, int* out);
 
+/* whether an 8-bit search launch at this lambda runs the packed-minimum twin of the search kernel (me_pk_gate, me_kernels.hpp; host
+ * arithmetic, needs no device): 1 while the largest MV cost the launch can meet + the largest sum of an 8x8 CU stays below the packed
+ * marker of an invalid candidate, 0 where the 32-bit tree runs */
+int hmme_test_pk_gate(uint32_t lambda_q16);
+
 /* where the staging arena of a synchronous, host-array call puts n items of bytes[i] bytes (hmme.hip stage_layout: what every hmme_*_frame*
  * entry point lays its arrays out with; host arithmetic, needs no device): offsets[i] and *total, the arena's size.  Returns the alignment of
  * every item, or a negative value for a null argument */

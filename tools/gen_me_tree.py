@@ -19,6 +19,11 @@ One *lane-iteration* of the kernel evaluates FOUR horizontally adjacent candidat
            (v_permlane32_swap, v_permlane16_swap, DPP row_ror:8 / row_half_mirror / quad_perm):
            afterwards lane l of group register g holds the wave-wide minimum of slot
            SLOT_OF[g][l]; ten running-minimum registers persist across iterations.
+  packed-minimum twin (Tree(fen, pk=True) -> csrc/me_tree_pk_fen{0,1}.inc, written at every build and kept out of git; the kernel's PK = 1): the five slots of every 8x8 CU (8x4, 4x8,
+           8x8: all-row sums <= 16 320) form no keys.  Their minimum over the lane's 4 candidates is taken on packed u16 COSTS (packed sum +
+           packed MV costs, one 64-bit add; two v_pk_min_u16) and ONE key per lane is formed from it (v_mad_u32_u16) with j = 0: 4 ops
+           where keys + minimum are 6.  The kernel recovers j once per slot and job (me_pk_recover); the host runs the twin only where every
+           cost fits (me_pk_gate).  What the 16x16 region needs of an 8x8 CU as keys (16x8, 16x4) it forms from the packed sums of two CUs.
 
 The slot numbering is the reference's (TComDataCU::getIndexBlock, TComDataCU.cpp:3379-3391 and
 :4676-6461; same offsets in cl/sad.cl:200-365); FEN semantics are TEncSearch.cpp:3853-3859 +
@@ -80,8 +85,9 @@ class Tree:
 
     KEY_SUB = True   # an 8x8 CU's right 4x8 half is formed from keys (8x8 - left half); the 16-bit tree keeps its packed sum
 
-    def __init__(self, fen):
+    def __init__(self, fen, pk=False):
         self.fen = fen
+        self.pk = pk               # the five slots of every 8x8 CU take the packed 16-bit minimum (PKMIN) instead of four 32-bit keys
         self.ops = []
         self.n = 0
         self.emitted = []          # slot ids in emission order (None = padding)
@@ -185,6 +191,15 @@ class Tree:
         self.ops.append(("MIN4", r, k))
         self._push(slot, r)
 
+    def emit_pk(self, slot, p):
+        """a slot whose packed sums exist and feed nothing as keys: the minimum over the lane's four candidates is taken on the packed
+        u16 costs (sum + packed MV cost), ONE key per lane formed from it -- 4 instructions where KEYS + MIN4 are 6.  The key carries
+        the candidate's iteration and lane but not which of the four it was (j = 0): the kernel recovers j from the window once per
+        slot and job (me_pk_recover)"""
+        r = self.new("r")
+        self.ops.append(("PKMIN", r, p))
+        self._push(slot, r)
+
     def _push(self, slot, r):
         self.emitted.append(slot)
         level = 0
@@ -256,6 +271,8 @@ class Tree:
         self.cu_k0 = 2 * cx8
         (e0, a0), (e1, a1) = self.block(2 * cx8, 2 * cy8), self.block(2 * cx8 + 1, 2 * cy8)
         (e2, a2), (e3, a3) = self.block(2 * cx8, 2 * cy8 + 1), self.block(2 * cx8 + 1, 2 * cy8 + 1)
+        if self.pk:
+            return self.level0_pk(cx, cy, cx8, cy8, (e0, a0), (e1, a1), (e2, a2), (e3, a3))
         at, ab = self.pkadd(a0, a1), self.pkadd(a2, a3)
         al = self.pkadd(a0, a2)
         # the right 4x8 half as a packed sum only where something reads the packed sum: the tall family's 4x16 column without FEN
@@ -287,16 +304,46 @@ class Tree:
         out["urow"] = ut if cy == 0 else ub
         return out
 
+    def level0_pk(self, cx, cy, cx8, cy8, b0, b1, b2, b3):
+        """the 8x8 CU of the packed-minimum tree: five packed sums (all rows, <= 64 * 255 = 16 320), five PKMIN, no key.  What the
+        16x16 region above needs of them as keys (16x8, 16x4) it forms from the packed sums of two CUs (level1)"""
+        (e0, a0), (e1, a1), (e2, a2), (e3, a3) = b0, b1, b2, b3
+        at, ab = self.pkadd(a0, a1), self.pkadd(a2, a3)
+        al, ar = self.pkadd(a0, a2), self.pkadd(a1, a3)
+        a8 = self.pkadd(at, ab)
+        self.emit_pk(slot_2NxN(8, cx8, cy8, 0), at)
+        self.emit_pk(slot_2NxN(8, cx8, cy8, 1), ab)
+        self.emit_pk(slot_Nx2N(8, cx8, cy8, 0), al)
+        self.emit_pk(slot_Nx2N(8, cx8, cy8, 1), ar)
+        self.emit_pk(slot_2Nx2N(8, cx8, cy8), a8)
+        out = {"a8": a8, "at": at, "ab": ab}
+        if self.fen:
+            ut, ub = self.pkadd(e0, e1), self.pkadd(e2, e3)
+            out["ucol"] = self.pkadd(e0, e2) if cx == 0 else self.pkadd(e1, e3)
+            out["u8"] = self.pkadd(ut, ub)
+        else:
+            ut, ub = at, ab
+            out["ucol"] = al if cx == 0 else ar
+            out["u8"] = a8
+        out["urow"] = ut if cy == 0 else ub
+        return out
+
     def level1(self, rx16, ry16, rx, ry, c, U):
         """16x16 region at region coords (rx16, ry16); (rx, ry) = position inside its 32x32"""
         S = 16
         # all-rows family (h <= 8)
-        k_top = self.lin(c[0]["k_a8"], c[1]["k_a8"])
-        k_bot = self.lin(c[2]["k_a8"], c[3]["k_a8"])
+        if self.pk:    # no keys below: one packed add of two CUs' sums (<= 32 640) and one KEYS, 5 ops where a LIN of two keys is 4
+            k_top = self.keys(self.pkadd(c[0]["a8"], c[1]["a8"]), "A")
+            k_bot = self.keys(self.pkadd(c[2]["a8"], c[3]["a8"]), "A")
+            k_t4 = self.keys(self.pkadd(c[0]["at"], c[1]["at"]), "A")
+            k_b4 = self.keys(self.pkadd(c[2]["ab"], c[3]["ab"]), "A")
+        else:
+            k_top = self.lin(c[0]["k_a8"], c[1]["k_a8"])
+            k_bot = self.lin(c[2]["k_a8"], c[3]["k_a8"])
         self.emit(slot_2NxN(S, rx16, ry16, 0), k_top)
         self.emit(slot_2NxN(S, rx16, ry16, 1), k_bot)
-        self.emit(slot_AMP(S, rx16, ry16, 0), self.lin(c[0]["k_at"], c[1]["k_at"]))   # 16x4 top
-        self.emit(slot_AMP(S, rx16, ry16, 1), self.lin(c[2]["k_ab"], c[3]["k_ab"]))   # 16x4 bottom
+        self.emit(slot_AMP(S, rx16, ry16, 0), k_t4 if self.pk else self.lin(c[0]["k_at"], c[1]["k_at"]))   # 16x4 top
+        self.emit(slot_AMP(S, rx16, ry16, 1), k_b4 if self.pk else self.lin(c[2]["k_ab"], c[3]["k_ab"]))   # 16x4 bottom
         # tall family (h > 8): packed sums still fit u16 (<= 16*8*255 even rows / 16*16*255 all rows)
         left, right = self.pkadd(c[0]["u8"], c[2]["u8"]), self.pkadd(c[1]["u8"], c[3]["u8"])
         u16 = self.pkadd(left, right)
@@ -541,6 +588,13 @@ HEADER = """// GENERATED by tools/gen_me_tree.py -- do not edit.  One lane-itera
 """
 
 
+HEADER_PK = """// GENERATED by tools/gen_me_tree.py -- do not edit.  One lane-iteration of the full-search
+// reduction tree (fen=%d), packed-minimum twin: the five slots of every 8x8 CU take their minimum on packed u16 costs (ME_PKMIN).
+// Expects in scope what me_tree_fen*.inc expects, and pkm (the lane's four packed u16 MV costs, the marker where a candidate is
+// invalid) and ctag (the lane's key constant with j = 0).
+"""
+
+
 HEADER16 = """// GENERATED by tools/gen_me_tree.py -- do not edit.  One lane-iteration of the 16-bit-sample reduction tree
 // (fen=%d): three candidates (x, x+2, x+4) per lane, exact 32-bit sums, v_sad_u16 leaves.
 // Expects in scope: lpd (per-lane LDS byte pointer at the first candidate, window row 0; 4-byte aligned), ME16_PDW (window pitch in
@@ -556,7 +610,7 @@ MASKED_MERGE_LEVELS = (0, 1)   # the two levels done with hand-written bank-mask
 # pair's key constants are one v_lshl_add_u64 each (shift 0: the instruction only shifts by 0..4, which is why the key's shift rides on the
 # first add of two leaf sums), 6 instructions per slot where three separate candidates took 7, 2 per add where they took 3
 PAIR64 = True
-ORDERED_INSTRS = {"KEYS": 4, "LIN": 4, "SUB": 4, "MIN4": 2, "SUBMIN4": 6, "KEYMINN": 1 if PAIR64 else 7}
+ORDERED_INSTRS = {"KEYS": 4, "LIN": 4, "SUB": 4, "MIN4": 2, "SUBMIN4": 6, "PKMIN": 3, "KEYMINN": 1 if PAIR64 else 7}
 
 
 def fuse_sub_min(ops):
@@ -622,7 +676,7 @@ def space_merges(ops, enable):
         count[0] += ORDERED_INSTRS.get(op[0], 0)
         if op[0] in ("KEYS", "LIN", "SUB"):
             key_at[op[1]] = count[0]
-        if op[0] in ("MIN4", "KEYMINN", "SUBMIN4"):       # the ops whose result a level-0 merge reads
+        if op[0] in ("MIN4", "KEYMINN", "SUBMIN4", "PKMIN"):       # the ops whose result a level-0 merge reads
             where[op[1]] = count[0]
         out.append((op, False))
 
@@ -685,6 +739,8 @@ def emit_cpp(tree, path, header=None):
             o.append(f"const uint32_t {op[1]} = ME_MIN4({op[2]});")
         elif t == "SUBMIN4":
             o.append(f"ME_SUBMIN4({op[1]}, {op[2]}, {op[3]});")
+        elif t == "PKMIN":
+            o.append(f"ME_PKMIN({op[1]}, {op[2]});")
         elif t == "MERGE":
             _, level, m, a, b = op
             a = a if a is not None else "ME_MAXKEY"
@@ -830,11 +886,18 @@ def simulate16(tree, window, cur, lane_off, c, best, sh):
     return best
 
 
-def simulate(tree, window, cur, lane_off, c, best):
+PK_SLOT_MAX = 64 * 255                 # the largest sum a PKMIN slot holds (the 8x8 CU, all rows)
+PK_MARKER = 0xFFFF - PK_SLOT_MAX       # packed MV cost of an invalid candidate: marker + any sum still fits u16 ...
+PK_COST_MAX = PK_MARKER - PK_SLOT_MAX - 1   # ... and every valid cost + sum stays below it (the host's gate: me_pk_gate, me_kernels.hpp)
+
+
+def simulate(tree, window, cur, lane_off, c, best, pk=None):
     """interpret one lane-iteration.
     window: (rows, PDW*4) uint8 LDS image; cur: (64,64) uint8; lane_off[l] = byte offset of lane l's
     (row 0, dword 0) in the flattened window; c: (4, 64) uint32 per-candidate constants;
-    best: (N_GROUPS, 64) uint32, updated in place."""
+    best: (N_GROUPS, 64) uint32, updated in place.
+    pk (a tree with PKMIN ops): (m, ctag) -- m (4, 64) the candidates' packed u16 MV costs (PK_MARKER where invalid), ctag (64,) uint32
+    the lane's key constant with j = 0 (and the invalid marker of the 32-bit keys where all four candidates are invalid)."""
     mult = {"A": np.uint32(MULT_A), "E": np.uint32(2 * MULT_A)}
     flat = window.reshape(-1)
     pad = np.zeros(8, np.uint8)
@@ -874,6 +937,10 @@ def simulate(tree, window, cur, lane_off, c, best):
             val[op[1]] = (val[op[2]] - val[op[3]] + c.T).astype(np.uint32)
         elif t == "MIN4":
             val[op[1]] = val[op[2]].min(axis=1).astype(np.uint32)
+        elif t == "PKMIN":
+            q = val[op[2]].astype(np.int64) + pk[0].T.astype(np.int64)      # one 64-bit add: a field that overflowed would carry into the next
+            assert (q <= 0xFFFF).all(), "a packed cost left its 16 bits"
+            val[op[1]] = (q.min(axis=1) * MULT_A + pk[1].astype(np.int64)).astype(np.uint32)
         elif t == "MERGE":
             _, level, m, a, b = op
             A = val[a] if a is not None else MAXK
@@ -888,19 +955,22 @@ def simulate(tree, window, cur, lane_off, c, best):
 
 
 def main():
-    for fen in (0, 1):
-        tree = Tree(fen).build()
-        emit_cpp(tree, os.path.join(OUT_DIR, f"me_tree_fen{fen}.inc"))
+    for fen, pk in ((0, False), (1, False), (0, True), (1, True)):
+        tree = Tree(fen, pk).build()
+        emit_cpp(tree, os.path.join(OUT_DIR, f"me_tree_pk_fen{fen}.inc" if pk else f"me_tree_fen{fen}.inc"), HEADER_PK if pk else None)
         counts = {}
         for op in tree.ops:
             counts[op[0]] = counts.get(op[0], 0) + 1
-        valu = (counts.get("PKADD", 0) + counts.get("PKSUB", 0)) * 2 + (counts.get("KEYS", 0) + counts.get("LIN", 0)) * 4 \
-            + counts.get("SUB", 0) * 4 + counts.get("MIN4", 0) * 2 + counts.get("ACC", 0)
+        # a packed add is ONE v_lshl_add_u64, a packed subtract two v_sub_u32; PKMIN = packed add of the MV costs + 3
+        valu = counts.get("PKADD", 0) + counts.get("PKSUB", 0) * 2 + (counts.get("KEYS", 0) + counts.get("LIN", 0)) * 4 \
+            + counts.get("SUB", 0) * 4 + counts.get("MIN4", 0) * 2 + counts.get("PKMIN", 0) * 4 + counts.get("ACC", 0)
         merges = [sum(1 for op in tree.ops if op[0] == "MERGE" and op[1] == lv) for lv in range(6)]
         valu += 2 * (merges[0] + merges[1]) + 4 * sum(merges[2:])
-        print(f"fen={fen}: {len(tree.ops)} IR ops {counts}; merges/level {merges}; ~{valu} full-rate VALU + "
+        print(f"fen={fen}{' packed minima' if pk else ''}: {len(tree.ops)} IR ops {counts}; merges/level {merges}; ~{valu} full-rate VALU + "
               f"{counts['QSAD']} qsad per lane-iteration (4 candidates)")
-        if fen == 1:
+        if pk:
+            assert np.array_equal(ref_map, tree.slot_of_lane()), "the packed-minimum tree must use the same slot map"
+        elif fen == 1:
             emit_slotmap(tree, os.path.join(OUT_DIR, "me_slotmap.inc"))
         else:
             ref_map = tree.slot_of_lane()
