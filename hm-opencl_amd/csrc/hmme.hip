@@ -366,13 +366,19 @@ auto with_fen(int fen, F&& f) {
 }
 
 // me_search_kernel<FEN, SPLIT, PK> over n_wg workgroups.  SPLIT = 0: whole jobs (MeJob), results straight into d_mv / d_sad; 1 and 2 (below) merge into `best`.
-// PK: the packed-minimum twin wherever the context's lambda passes me_pk_gate (HM's lambdas over QP 22..37 lie far inside), the 32-bit tree otherwise
+// PK (me_pk_body): with FEN 1 the kernel that holds the packed-minimum twin and its marker-free body wherever the context's lambda passes me_pk2_gate
+// (lambda <= 224: HM's lambdas over QP 22..37 lie far inside), the twin alone up to me_pk_gate and with FEN 0, the 32-bit tree beyond
 template <int SPLIT>
 int launch_search8(hmme_ctx* ctx, const RefSet& cur, int cur_ctus_x, const RefSet& ref, int ref_pitch, const void* d_jobs, int n_wg, int fen,
                    int16_t* d_mv, uint32_t* d_sad, unsigned long long* best, int n_seg_jobs, hipStream_t stream) {
   if (n_wg <= 0) return HMME_OK;
   return with_fen(fen, [&](auto f) -> int {
-    const auto kernel = hmme::me_pk_gate(ctx->lambda_q16) ? hmme::me_search_kernel<decltype(f)::value, SPLIT, 1> : hmme::me_search_kernel<decltype(f)::value, SPLIT, 0>;
+    constexpr int FEN = decltype(f)::value;
+    const int body = hmme::me_pk_body(ctx->lambda_q16, FEN);
+    auto kernel = body ? hmme::me_search_kernel<FEN, SPLIT, 1> : hmme::me_search_kernel<FEN, SPLIT, 0>;
+    if constexpr (FEN == 1) {
+      if (body == 2) kernel = hmme::me_search_kernel<1, SPLIT, 2>;
+    }
     hipLaunchKernelGGL(kernel, dim3(n_wg), dim3(hmme::kThreads), 0, stream, cur, cur_ctus_x, ref,
                        ref_pitch, d_jobs, ctx->lambda_q16, d_mv, d_sad, best, fair_prio(ctx, n_wg, SPLIT == 0), n_seg_jobs);
     HIP_TRY(ctx, hipGetLastError());
@@ -1371,6 +1377,8 @@ int hmme_test_tail_plan(int width, int height, int search_range, int n_pairs, in
 }
 
 int hmme_test_pk_gate(uint32_t lambda_q16) { return hmme::me_pk_gate(lambda_q16) ? 1 : 0; }
+int hmme_test_pk_body(uint32_t lambda_q16, int fen) { return hmme::me_pk_body(lambda_q16, fen ? 1 : 0); }
+int hmme_test_pk_task_marker_free(int wx, int wy, int k, int it0, int n_it) { return hmme::me_task_marker_free(wx, wy, k, it0, n_it) ? 1 : 0; }
 
 // writes the device job table of plan `pl` -- a picture search over CTUs [first, first + count) against n_refs reference pictures -- on `s`;
 // job index = ref * count + ctu.  kWhole8: MeJob[jobs]; kHeadThenSegments8: MeJob[head], then the tail's segment table; kSegments8: one

@@ -136,10 +136,42 @@ __host__ __device__ inline bool me_pk_gate(uint32_t lambda_q16) {
   const uint64_t prod = (uint64_t)lambda_q16 * kPkMaxBits;
   return prod <= 0xFFFFFFFFull && (prod >> 16) + kPkSlotMax < kPkMarker;
 }
-#define ME_PKMIN(r, p)                                                                                          \
+// Marker-free twin (PK = 2, me_tree_pk2_fen1.inc; FEN 1 only): the marker exists for the invalid candidates of a PARTLY valid lane, and
+// such lanes exist only where a window row's last quad is cut (wx % 4 != 0): in the part that holds that quad, and in the folded
+// iteration of the 32-quad part (me_task_marker_free).  Every other task has only lanes that are wholly valid -- pkm holds four real MV
+// costs -- or wholly invalid -- kInvCost << 10 in ctag drops the lane whatever its packed fields hold, carries between them included.
+// Without a marker a packed cost only has to stay below 2^16, and twelve of the thirteen slots of a 16x16 CU do: 16x4, 4x16 <= 16 320,
+// 16x8, 8x16 <= 32 640, 16x12, 12x16 <= kPk2SlotMax, + an MV cost of at most 0xFFFF - kPk2SlotMax (me_pk2_gate).  They take ME_PKMIN
+// there, ME_PKMINE where FEN halves the rows (h > 8): the 64-bit add that adds the packed MV costs doubles the even-row sums on the way
+// (v_lshl_add_u64; an even-row sum is at most 24 480, the shift stays inside its u16 field).  min * 1024 + ctag stays inside the key:
+// 65 535 * 1024 + (kInvCost << 10 | 1023) < 2^32.  Tasks with a partly valid lane run the PK = 1 body in the same kernel.
+constexpr uint32_t kPk2SlotMax = 16 * 12 * 255;           // 48 960: 16x12 / 12x16, every sample difference 255
+__host__ __device__ inline bool me_pk2_gate(uint32_t lambda_q16) {
+  const uint64_t prod = (uint64_t)lambda_q16 * kPkMaxBits;
+  return prod <= 0xFFFFFFFFull && (prod >> 16) + kPk2SlotMax <= 0xFFFFu;
+}
+// which body an 8-bit search launch runs: 0 the 32-bit tree, 1 the packed-minimum twin, 2 the kernel that holds the twin and its marker-free
+// body.  FEN 0 stays on 1: its tall-family sums are all-row sums of twice the rows, its recovery would read 16 rows per slot, and no
+// benchmark or encoder configuration runs it
+__host__ __device__ inline int me_pk_body(uint32_t lambda_q16, int fen) {
+  return (fen && me_pk2_gate(lambda_q16)) ? 2 : me_pk_gate(lambda_q16) ? 1 : 0;
+}
+// whether the task (part k, lane-iterations it0 .. it0 + n_it - 1) of a wx x wy window has no partly valid lane.  The last quad of a
+// row lies in the part of the lowest set bit of `quads`; with the fold, the leftover quads of the last window row are also met in the
+// second lane row of the 32-quad part's last iteration (rows wy - 1 and wy: wy is odd)
+__host__ __device__ inline bool me_task_marker_free(int wx, int wy, int k, int it0, int n_it) {
+  if (!(wx & 3)) return true;
+  const int quads = (wx + 3) >> 2;
+  if ((quads & -quads) == (1 << k)) return false;
+  const bool fold = (quads & 32) && (quads & 31) && (wy & 1);   // me_fold (below)
+  return !(fold && k == 5 && 2 * (it0 + n_it) > wy);
+}
+#define ME_PKMIN(r, p) ME_PKMIN_Q(r, (p) + pkm)
+#define ME_PKMINE(r, p) ME_PKMIN_Q(r, ((p) << 1) + pkm)
+#define ME_PKMIN_Q(r, q)                                                                                        \
   uint32_t r;                                                                                                   \
   {                                                                                                             \
-    const uint64_t r##_q = (p) + pkm;                                                                           \
+    const uint64_t r##_q = (q);                                                                                 \
     asm volatile("v_pk_min_u16 %0, %1, %2\n\tv_pk_min_u16 %0, %0, %0 op_sel:[0,1] op_sel_hi:[1,0]\n\t"                \
                  "v_mad_u32_u16 %0, %0, %3, %4"                                                                 \
                  : "=&v"(r) : "v"((uint32_t)r##_q), "v"((uint32_t)(r##_q >> 32)), "s"(mult_a), "v"(ctag));      \
@@ -192,11 +224,22 @@ __device__ __forceinline__ uint32_t me_mv_cost(uint32_t lambda_q16, int x, int y
 }
 
 // The slots that take the packed minimum in the PK twin (ME_PKMIN) and their rectangles in the CTU: 8x4 halves 0..127, 4x8 halves
-// 128..255, 8x8 CUs 384..447 (tools/gen_me_tree.py slot_2NxN / slot_Nx2N / slot_2Nx2N at size 8)
-__device__ __forceinline__ bool me_pk_slot(int s, int& x, int& y, int& w, int& h) {
+// 128..255, 8x8 CUs 384..447 (tools/gen_me_tree.py slot_2NxN / slot_Nx2N / slot_2Nx2N at size 8).  WIDE (PK = 2): also the twelve slots
+// of every 16x16 CU that the marker-free body packs -- the AMP slots 256..383 (16x4, 16x12, 4x16, 12x16), 16x8 448..479, 8x16 480..511
+__device__ __forceinline__ bool me_pk_slot(int s, bool wide, int& x, int& y, int& w, int& h) {
   if (s < 128) { x = (s & 7) * 8; y = (s >> 4) * 8 + ((s >> 3) & 1) * 4; w = 8; h = 4; return true; }
   if (s < 256) { x = ((s >> 1) & 7) * 8 + (s & 1) * 4; y = ((s - 128) >> 4) * 8; w = 4; h = 8; return true; }
   if (s >= 384 && s < 448) { x = (s & 7) * 8; y = ((s - 384) >> 3) * 8; w = 8; h = 8; return true; }
+  if (!wide) return false;
+  if (s < 384) {
+    const int kk = (s - 256) >> 4;                       // 0, 1: 16x4 top / bottom; 2, 3: 16x12; 4, 5: 4x16 left / right; 6, 7: 12x16
+    x = (s & 3) * 16; y = ((s >> 2) & 3) * 16; w = 16; h = 16;
+    if (kk < 4) { h = kk < 2 ? 4 : 12; if (kk & 1) y += 16 - h; }
+    else { w = kk < 6 ? 4 : 12; if (kk & 1) x += 16 - w; }
+    return true;
+  }
+  if (s < 480) { x = (s & 3) * 16; y = ((s - 448) >> 3) * 16 + ((s >> 2) & 1) * 8; w = 16; h = 8; return true; }
+  if (s < 512) { x = ((s >> 1) & 3) * 16 + (s & 1) * 8; y = ((s - 480) >> 3) * 16; w = 8; h = 16; return true; }
   return false;
 }
 // PK twin: a packed slot's entry v = (cost, y, x of the winning quad's first candidate) of the workgroup's table -> the same entry with
@@ -204,45 +247,67 @@ __device__ __forceinline__ bool me_pk_slot(int s, int& x, int& y, int& w, int& h
 // in LDS and the job's current block; the FIRST j whose SAD + MV cost equals the minimum wins, as xPatternSearch's strict '<' has it
 // inside a row.  Between quads the order was settled by (cost, y, x of the quad), which is the raster order: quads do not overlap.
 // About 0.1 % of a job's absolute differences.  A quad starts on a window dword and a slot on a current-block dword (both x are multiples
-// of 4), so a row is RW / 4 + 1 window dwords and RW / 4 current-block dwords, candidate j four bytes at a time through v_alignbyte_b32 and
-// v_sad_u8; every load of the slot is issued before the first is used (one round trip: a workgroup of a segment launch runs a few
+// of 4), so a row is RW / 4 + 1 window dwords and RW / 4 current-block dwords; four current-block bytes against the four candidates at once
+// through the leaves' own v_qsad_pk_u16_u8 on window dword pairs (k, k + 1), each pair read on its own as the body reads them (one
+// instruction per dword where v_alignbyte_b32 + v_sad_u8 per candidate were seven; a slot's sum is at most 32 640 here: packed u16);
+// every load of the slot is issued before the first is used (one round trip: a workgroup of a segment launch runs a few
 // lane-iterations per job, and a byte-wise loop with a load per row cost it 3 %).
-template <int RW, int RH>
+// NR rows, STEP apart: STEP = 2 reads the even rows of a slot taller than 8 under FEN (its cost is twice their sum).
+// PK = 2: a slot of the 16x16 level arrives with j = 0 from a marker-free task and with the winner's j from a task of the PK = 1 body
+// (32-bit keys there).  The quad starts at x & ~3 either way (every quad starts on a multiple of 4), and the key minimum took the
+// smallest j of the lane's equal costs, which is the first j that is found here: one path serves both.
+template <int RW, int NR, int STEP>
 __device__ __forceinline__ void me_pk_sads(const uint32_t* wrow, int pdw, const uint8_t* __restrict__ crow, uint32_t sad[4]) {
   constexpr int ND = RW / 4;
-  uint32_t c[RH][ND], d[RH][ND + 1];
+  static_assert(RW * NR * 255 <= 0xFFFF, "the four sums are packed u16");
+  typedef uint64_t __attribute__((aligned(4))) u64a4_t;
+  uint32_t c[NR][ND];
+  uint64_t d[NR][ND];
 #pragma unroll
-  for (int r = 0; r < RH; ++r) {
+  for (int r = 0; r < NR; ++r) {
 #pragma unroll
-    for (int k = 0; k < ND; ++k) c[r][k] = *(const uint32_t*)(crow + r * 64 + 4 * k);
+    for (int k = 0; k < ND; ++k) c[r][k] = *(const uint32_t*)(crow + r * STEP * 64 + 4 * k);
 #pragma unroll
-    for (int k = 0; k <= ND; ++k) d[r][k] = wrow[r * pdw + k];
+    for (int k = 0; k < ND; ++k) d[r][k] = *(const u64a4_t*)(wrow + r * STEP * pdw + k);   // dwords k, k + 1: a register pair of its own
   }
+  uint64_t acc = 0;
 #pragma unroll
-  for (int r = 0; r < RH; ++r)
+  for (int r = 0; r < NR; ++r)
 #pragma unroll
-    for (int k = 0; k < ND; ++k) {
-      sad[0] = __builtin_amdgcn_sad_u8(d[r][k], c[r][k], sad[0]);
+    for (int k = 0; k < ND; ++k) acc = ME_QSAD(d[r][k], c[r][k], acc);
 #pragma unroll
-      for (int j = 1; j < 4; ++j) sad[j] = __builtin_amdgcn_sad_u8(__builtin_amdgcn_alignbyte(d[r][k + 1], d[r][k], (uint32_t)j), c[r][k], sad[j]);
-    }
+  for (int j = 0; j < 4; ++j) sad[j] = (uint32_t)(acc >> (16 * j)) & 0xFFFFu;
 }
+template <bool WIDE>
 __device__ __forceinline__ unsigned long long me_pk_recover(unsigned long long v, int s, const uint32_t* win, int pdw, const uint8_t* __restrict__ cur_blk,
                                                             const MeJob& job, int wx, uint32_t lambda_q16) {
   int rx, ry, rw, rh;
-  if (v == ~0ull || !me_pk_slot(s, rx, ry, rw, rh)) return v;
-  const int xq = (int)(v & 0xffff), y = (int)((v >> 16) & 0xffff);
+  if (v == ~0ull || !me_pk_slot(s, WIDE, rx, ry, rw, rh)) return v;
+  const int xq = (int)(v & 0xfffc), y = (int)((v >> 16) & 0xffff);
   const uint32_t cost = (uint32_t)(v >> 32);
   const uint32_t* wrow = win + (y + ry) * pdw + ((xq + rx) >> 2);   // dwords (xq + rx) / 4 .. + rw / 4 <= 48 of a 49-dword row
   const uint8_t* crow = cur_blk + ry * 64 + rx;
   uint32_t sad[4] = {0u, 0u, 0u, 0u};
-  if (rh == 4) me_pk_sads<8, 4>(wrow, pdw, crow, sad);
-  else if (rw == 4) me_pk_sads<4, 8>(wrow, pdw, crow, sad);
-  else me_pk_sads<8, 8>(wrow, pdw, crow, sad);
+  int sh = 0;
+  if (!WIDE || max(rw, rh) <= 8) {
+    if (rh == 4) me_pk_sads<8, 4, 1>(wrow, pdw, crow, sad);
+    else if (rw == 4) me_pk_sads<4, 8, 1>(wrow, pdw, crow, sad);
+    else me_pk_sads<8, 8, 1>(wrow, pdw, crow, sad);
+  } else if (rh <= 8) {                                   // 16x4, 16x8: all rows
+    if (rh == 4) me_pk_sads<16, 4, 1>(wrow, pdw, crow, sad);
+    else me_pk_sads<16, 8, 1>(wrow, pdw, crow, sad);
+  } else {                                                // taller than 8 (WIDE is FEN 1): even rows, twice their sum
+    sh = 1;
+    if (rh == 12) me_pk_sads<16, 6, 2>(wrow, pdw, crow, sad);
+    else if (rw == 4) me_pk_sads<4, 8, 2>(wrow, pdw, crow, sad);
+    else if (rw == 8) me_pk_sads<8, 8, 2>(wrow, pdw, crow, sad);
+    else me_pk_sads<12, 8, 2>(wrow, pdw, crow, sad);
+  }
   const uint32_t by = me_component_bits(((job.lt_y + y) << 2) - job.pred_y);
+  v &= ~3ull;
 #pragma unroll
   for (int j = 0; j < 4; ++j)
-    if (xq + j < wx && sad[j] + ((lambda_q16 * (me_component_bits(((job.lt_x + xq + j) << 2) - job.pred_x) + by)) >> 16) == cost) return v + (unsigned long long)j;
+    if (xq + j < wx && (sad[j] << sh) + ((lambda_q16 * (me_component_bits(((job.lt_x + xq + j) << 2) - job.pred_x) + by)) >> 16) == cost) return v + (unsigned long long)j;
   return v;
 }
 
@@ -418,6 +483,8 @@ constexpr int kTileStep = 129, kTileJobMask = 0x1fffffff;
 // curs: the CTU-blocked copies of the current pictures (above me_prefetch_cur), cur_ctus_x: CTUs per picture row (blocks per block row).
 // PK = 1: the packed-minimum twin (ME_PKMIN above; every <FEN, SPLIT> has one).  Same results, fewer instructions per lane-iteration;
 // only for launches that pass me_pk_gate.
+// PK = 2 (FEN 1 only): the twin and its marker-free body in one kernel, one wave-uniform branch per task (me_task_marker_free); only for
+// launches that pass me_pk2_gate.
 template <int FEN, int SPLIT, int PK>
 __global__ void __launch_bounds__(kThreads, 2)
 me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_pitch,
@@ -448,6 +515,9 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
     job = ((const MeJob*)jobs_v)[blockIdx.x];
     out_job = me_xcd_unit(blockIdx.x, gridDim.x);   // the job table of a whole-job launch is in XCD order (me_prep_jobs_kernel)
   }
+  // every kernel argument and table entry loaded so far has arrived before the job loop: none of the compiler's own scalar loads stays
+  // in flight into the loop's blocks, where tools/check_dpp_hazard.py (a linear scan) could not tell its wait from a missing one
+  if constexpr (PK == 2) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll 1
   for (bool first_job = true;; first_job = false) {   // one pass, except SPLIT = 2: one pass per job the segment reaches into
   if constexpr (SPLIT == 2) {
@@ -588,6 +658,7 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
     const int ty = 64 >> k;
     const int lx = lane & ((1 << k) - 1), ly = lane >> k;
     const bool fold_part = fold && k == 5;
+    const bool marker_free = PK == 2 && me_task_marker_free(wx, wy, k, it0, n_it);   // wave-uniform: wx, wy of the job, k, it0, n_it of the task
 
     // running minima of the task: register g, lane l <-> slot ME_SLOT_OF[g][l]
     uint32_t b0 = ME_MAXKEY, b1 = ME_MAXKEY, b2 = ME_MAXKEY, b3 = ME_MAXKEY, b4 = ME_MAXKEY, b5 = ME_MAXKEY,
@@ -635,7 +706,14 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
   asm volatile("" : : "v"(d0), "v"(d1), "v"(d2), "v"(d3), "v"(d4), "v"(d5), "v"(d6), "v"(d7), "v"(d8), "v"(d9), "v"(d10), "v"(d11),  \
                "v"(d12), "v"(d13), "v"(d14), "v"(d15));                                                                             \
   asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(w0), "+s"(w1), "+s"(w2), "+s"(w3), "+s"(w4), "+s"(w5), "+s"(w6), "+s"(w7))
-      if constexpr (PK) {
+      if constexpr (PK == 2) {
+        static_assert(PK != 2 || FEN == 1, "the marker-free body exists for FEN 1");
+        if (marker_free) {
+#include "me_tree_pk2_fen1.inc"
+        } else {
+#include "me_tree_pk_fen1.inc"
+        }
+      } else if constexpr (PK) {
         if constexpr (FEN) {
 #include "me_tree_pk_fen1.inc"
         } else {
@@ -680,7 +758,7 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
   if constexpr (SPLIT) {
     for (int s = tid; s < kParts; s += kThreads) {
       unsigned long long v = best64[s];
-      if constexpr (PK) v = me_pk_recover(v, s, win, kPDW, (const uint8_t*)cur_addr, job, wx, lambda_q16);   // before the entry leaves the workgroup
+      if constexpr (PK) v = me_pk_recover<PK == 2>(v, s, win, kPDW, (const uint8_t*)cur_addr, job, wx, lambda_q16);   // before the entry leaves the workgroup
       if (v != ~0ull) atomicMin(&g_best[(long)out_job * kParts + s], v + tile_off);
     }
     if constexpr (SPLIT == 2) {
@@ -690,7 +768,7 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
   }
   for (int s = tid; s < kParts; s += kThreads) {
     unsigned long long v = best64[s];
-    if constexpr (PK) v = me_pk_recover(v, s, win, kPDW, (const uint8_t*)cur_addr, job, wx, lambda_q16);
+    if constexpr (PK) v = me_pk_recover<PK == 2>(v, s, win, kPDW, (const uint8_t*)cur_addr, job, wx, lambda_q16);
     const int mvx = job.lt_x + (int)(v & 0xffff), mvy = job.lt_y + (int)((v >> 16) & 0xffff);
     const uint32_t cost = (uint32_t)(v >> 32);
     const long o = (long)out_job * kParts + s;

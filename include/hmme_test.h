@@ -28,6 +28,14 @@ int hmme_test_tail_plan(int width, int height, int search_range, int n_pairs, in
  * marker of an invalid candidate, 0 where the 32-bit tree runs */
 int hmme_test_pk_gate(uint32_t lambda_q16);
 
+/* which body an 8-bit search launch at this lambda and FEN runs (me_pk_body; host arithmetic): 0 the 32-bit tree, 1 the packed-minimum
+ * twin, 2 the kernel that also holds the twin's marker-free body (FEN 1, the largest MV cost + the largest 16x12 sum within 16 bits) */
+int hmme_test_pk_body(uint32_t lambda_q16, int fen);
+
+/* whether a task of that kernel -- part k (2^k quads per lane row), lane-iterations it0 .. it0 + n_it - 1 of a wx x wy window -- runs the
+ * marker-free body: 1 where every lane of every one of its lane-iterations is wholly valid or wholly invalid (me_task_marker_free) */
+int hmme_test_pk_task_marker_free(int wx, int wy, int k, int it0, int n_it);
+
 /* where the staging arena of a synchronous, host-array call puts n items of bytes[i] bytes (hmme.hip stage_layout: what every hmme_*_frame*
  * entry point lays its arrays out with; host arithmetic, needs no device): offsets[i] and *total, the arena's size.  Returns the alignment of
  * every item, or a negative value for a null argument */

@@ -24,6 +24,12 @@ One *lane-iteration* of the kernel evaluates FOUR horizontally adjacent candidat
            packed MV costs, one 64-bit add; two v_pk_min_u16) and ONE key per lane is formed from it (v_mad_u32_u16) with j = 0: 4 ops
            where keys + minimum are 6.  The kernel recovers j once per slot and job (me_pk_recover); the host runs the twin only where every
            cost fits (me_pk_gate).  What the 16x16 region needs of an 8x8 CU as keys (16x8, 16x4) it forms from the packed sums of two CUs.
+  marker-free twin (Tree(1, pk=2) -> csrc/me_tree_pk2_fen1.inc, written at every build and kept out of git; the body that the kernel's PK = 2 runs in
+           tasks whose lanes are all wholly valid or wholly invalid): without the marker of an invalid candidate a packed cost only has to
+           stay below 2^16, and twelve of the thirteen slots of a 16x16 CU do (16x4, 4x16 <= 16 320; 16x8, 8x16 <= 32 640; 16x12, 12x16
+           <= 48 960; + the MV cost, me_pk2_gate).  They take PKMIN too (PKMINE where FEN halves the rows: the same 64-bit add doubles the
+           even-row sums).  16x16 (65 280) keeps its keys; 32x8 and 8x32 form theirs from the packed sum of two strips (5 ops where a union
+           of two keys is 4).  PK2_CLASSES holds the count that decides, class by class.
 
 The slot numbering is the reference's (TComDataCU::getIndexBlock, TComDataCU.cpp:3379-3391 and
 :4676-6461; same offsets in cl/sad.cl:200-365); FEN semantics are TEncSearch.cpp:3853-3859 +
@@ -88,6 +94,8 @@ class Tree:
     def __init__(self, fen, pk=False):
         self.fen = fen
         self.pk = pk               # the five slots of every 8x8 CU take the packed 16-bit minimum (PKMIN) instead of four 32-bit keys
+        assert pk != 2 or fen == 1, "the marker-free twin exists for FEN 1 only (FEN 0 stays on pk = 1)"
+        self.pk2 = pk2_choice() if pk == 2 else {}   # pk = 2: class of 16x16-level slots -> packed or not (marker-free tasks only)
         self.ops = []
         self.n = 0
         self.emitted = []          # slot ids in emission order (None = padding)
@@ -198,6 +206,13 @@ class Tree:
         slot and job (me_pk_recover)"""
         r = self.new("r")
         self.ops.append(("PKMIN", r, p))
+        self._push(slot, r)
+
+    def emit_pke(self, slot, p):
+        """emit_pk for a packed EVEN-ROW sum of the tall family under FEN: the cost is 2 * sum + MV cost, and the 64-bit add that adds
+        the packed MV costs shifts the sums by one on the way (every sum <= 32 640: the shift stays inside each u16 field)"""
+        r = self.new("r")
+        self.ops.append(("PKMINE", r, p))
         self._push(slot, r)
 
     def _push(self, slot, r):
@@ -331,6 +346,8 @@ class Tree:
     def level1(self, rx16, ry16, rx, ry, c, U):
         """16x16 region at region coords (rx16, ry16); (rx, ry) = position inside its 32x32"""
         S = 16
+        if self.pk == 2:
+            return self.level1_pk2(rx16, ry16, rx, ry, c, U)
         # all-rows family (h <= 8)
         if self.pk:    # no keys below: one packed add of two CUs' sums (<= 32 640) and one KEYS, 5 ops where a LIN of two keys is 4
             k_top = self.keys(self.pkadd(c[0]["a8"], c[1]["a8"]), "A")
@@ -370,6 +387,37 @@ class Tree:
         out["spare"] = self.retire()                                               # the 16x8 key's number: level 2 names a 32x8 sum with it
         return out
 
+    def level1_pk2(self, rx16, ry16, rx, ry, c, U):
+        """the 16x16 region of the marker-free twin: twelve PKMIN / PKMINE on packed sums, keys for 16x16 alone.  Emission order is
+        level1's (one slot map for every tree)"""
+        S = 16
+        assert all(self.pk2.values()), "PK2_CLASSES: a class that does not pay would keep level1's form here"
+        a_top, a_bot = self.pkadd(c[0]["a8"], c[1]["a8"]), self.pkadd(c[2]["a8"], c[3]["a8"])
+        a_t4, a_b4 = self.pkadd(c[0]["at"], c[1]["at"]), self.pkadd(c[2]["ab"], c[3]["ab"])
+        self.emit_pk(slot_2NxN(S, rx16, ry16, 0), a_top)
+        self.emit_pk(slot_2NxN(S, rx16, ry16, 1), a_bot)
+        self.emit_pk(slot_AMP(S, rx16, ry16, 0), a_t4)                             # 16x4 top
+        self.emit_pk(slot_AMP(S, rx16, ry16, 1), a_b4)                             # 16x4 bottom
+        left, right = self.pkadd(c[0]["u8"], c[2]["u8"]), self.pkadd(c[1]["u8"], c[3]["u8"])
+        u16 = self.pkadd(left, right)
+        t4, b4 = self.pkadd(c[0]["urow"], c[1]["urow"]), self.pkadd(c[2]["urow"], c[3]["urow"])
+        l4, r4 = self.pkadd(c[0]["ucol"], c[2]["ucol"]), self.pkadd(c[1]["ucol"], c[3]["ucol"])
+        self.emit_pke(slot_Nx2N(S, rx16, ry16, 0), left)
+        self.emit_pke(slot_Nx2N(S, rx16, ry16, 1), right)
+        k_u16 = self.keys(u16, U)
+        self.emit(slot_2Nx2N(S, rx16, ry16), k_u16)
+        self.emit_pke(slot_AMP(S, rx16, ry16, 2), self.pksub(u16, b4))             # 16x12 top
+        self.emit_pke(slot_AMP(S, rx16, ry16, 3), self.pksub(u16, t4))             # 16x12 bottom
+        self.emit_pke(slot_AMP(S, rx16, ry16, 4), l4)                              # 4x16 left
+        self.emit_pke(slot_AMP(S, rx16, ry16, 5), r4)                              # 4x16 right
+        self.emit_pke(slot_AMP(S, rx16, ry16, 6), self.pksub(u16, r4))             # 12x16 left: no keys of 4x16 to take from a key
+        self.emit_pke(slot_AMP(S, rx16, ry16, 7), self.pksub(u16, l4))             # 12x16 right
+        return {"k_u16": k_u16,
+                "p_ucol": left if rx == 0 else right,                             # packed: level 2 adds two and forms the 8x32 keys
+                "p_a16x8": a_top if ry == 0 else a_bot,                           # packed: likewise 32x8 (all rows, <= 65 280)
+                "u16x8": self.pkadd(c[0]["u8"], c[1]["u8"]) if ry == 0 else self.pkadd(c[2]["u8"], c[3]["u8"]),
+                "spare": None}
+
     def level2(self, qx, qy, r, U):
         """32x32 CU; every value is a key from here on, but for the two 32x8 strips of the tall family (packed up to here)"""
         S = 32
@@ -381,12 +429,20 @@ class Tree:
         self.emit(slot_Nx2N(S, qx, qy, 0), k_l)
         self.emit(slot_Nx2N(S, qx, qy, 1), k_r)
         self.emit(slot_2Nx2N(S, qx, qy), k_u32)
-        self.emit(slot_AMP(S, qx, qy, 0), self.lin(r[0]["k_a16x8"], r[1]["k_a16x8"]))   # 32x8 top   (all rows)
-        self.emit(slot_AMP(S, qx, qy, 1), self.lin(r[2]["k_a16x8"], r[3]["k_a16x8"]))   # 32x8 bottom
+        if self.pk == 2:   # the strips below are packed sums: one packed add (<= 65 280) and one KEYS
+            self.emit(slot_AMP(S, qx, qy, 0), self.keys(self.pkadd(r[0]["p_a16x8"], r[1]["p_a16x8"]), "A"))
+            self.emit(slot_AMP(S, qx, qy, 1), self.keys(self.pkadd(r[2]["p_a16x8"], r[3]["p_a16x8"]), "A"))
+        else:
+            self.emit(slot_AMP(S, qx, qy, 0), self.lin(r[0]["k_a16x8"], r[1]["k_a16x8"]))   # 32x8 top   (all rows)
+            self.emit(slot_AMP(S, qx, qy, 1), self.lin(r[2]["k_a16x8"], r[3]["k_a16x8"]))   # 32x8 bottom
         k_u32x8t = self.keys(self.pkadd_as(r[0]["spare"], r[0]["u16x8"], r[1]["u16x8"]), U)
         k_u32x8b = self.keys(self.pkadd_as(r[2]["spare"], r[2]["u16x8"], r[3]["u16x8"]), U)
-        k_u8x32l = self.lin(r[0]["k_ucol"], r[2]["k_ucol"])
-        k_u8x32r = self.lin(r[1]["k_ucol"], r[3]["k_ucol"])
+        if self.pk == 2:
+            k_u8x32l = self.keys(self.pkadd(r[0]["p_ucol"], r[2]["p_ucol"]), U)
+            k_u8x32r = self.keys(self.pkadd(r[1]["p_ucol"], r[3]["p_ucol"]), U)
+        else:
+            k_u8x32l = self.lin(r[0]["k_ucol"], r[2]["k_ucol"])
+            k_u8x32r = self.lin(r[1]["k_ucol"], r[3]["k_ucol"])
         self.emit(slot_AMP(S, qx, qy, 2), self.sub(k_u32, k_u32x8b))   # 32x24 top
         self.emit(slot_AMP(S, qx, qy, 3), self.sub(k_u32, k_u32x8t))   # 32x24 bottom
         self.emit(slot_AMP(S, qx, qy, 4), k_u8x32l)                    # 8x32 left
@@ -595,6 +651,13 @@ HEADER_PK = """// GENERATED by tools/gen_me_tree.py -- do not edit.  One lane-it
 """
 
 
+HEADER_PK2 = """// GENERATED by tools/gen_me_tree.py -- do not edit.  One lane-iteration of the full-search
+// reduction tree (fen=%d), marker-free packed-minimum twin: for tasks whose lanes are all wholly valid or wholly invalid.  Beside the five
+// slots of every 8x8 CU, twelve of the thirteen slots of every 16x16 CU take their minimum on packed u16 costs (ME_PKMIN, ME_PKMINE).
+// Expects in scope what me_tree_pk_fen*.inc expects; pkm needs no marker here.
+"""
+
+
 HEADER16 = """// GENERATED by tools/gen_me_tree.py -- do not edit.  One lane-iteration of the 16-bit-sample reduction tree
 // (fen=%d): three candidates (x, x+2, x+4) per lane, exact 32-bit sums, v_sad_u16 leaves.
 // Expects in scope: lpd (per-lane LDS byte pointer at the first candidate, window row 0; 4-byte aligned), ME16_PDW (window pitch in
@@ -610,7 +673,7 @@ MASKED_MERGE_LEVELS = (0, 1)   # the two levels done with hand-written bank-mask
 # pair's key constants are one v_lshl_add_u64 each (shift 0: the instruction only shifts by 0..4, which is why the key's shift rides on the
 # first add of two leaf sums), 6 instructions per slot where three separate candidates took 7, 2 per add where they took 3
 PAIR64 = True
-ORDERED_INSTRS = {"KEYS": 4, "LIN": 4, "SUB": 4, "MIN4": 2, "SUBMIN4": 6, "PKMIN": 3, "KEYMINN": 1 if PAIR64 else 7}
+ORDERED_INSTRS = {"KEYS": 4, "LIN": 4, "SUB": 4, "MIN4": 2, "SUBMIN4": 6, "PKMIN": 3, "PKMINE": 3, "KEYMINN": 1 if PAIR64 else 7}
 
 
 def fuse_sub_min(ops):
@@ -676,7 +739,7 @@ def space_merges(ops, enable):
         count[0] += ORDERED_INSTRS.get(op[0], 0)
         if op[0] in ("KEYS", "LIN", "SUB"):
             key_at[op[1]] = count[0]
-        if op[0] in ("MIN4", "KEYMINN", "SUBMIN4", "PKMIN"):       # the ops whose result a level-0 merge reads
+        if op[0] in ("MIN4", "KEYMINN", "SUBMIN4", "PKMIN", "PKMINE"):       # the ops whose result a level-0 merge reads
             where[op[1]] = count[0]
         out.append((op, False))
 
@@ -741,6 +804,8 @@ def emit_cpp(tree, path, header=None):
             o.append(f"ME_SUBMIN4({op[1]}, {op[2]}, {op[3]});")
         elif t == "PKMIN":
             o.append(f"ME_PKMIN({op[1]}, {op[2]});")
+        elif t == "PKMINE":
+            o.append(f"ME_PKMINE({op[1]}, {op[2]});")
         elif t == "MERGE":
             _, level, m, a, b = op
             a = a if a is not None else "ME_MAXKEY"
@@ -886,9 +951,45 @@ def simulate16(tree, window, cur, lane_off, c, best, sh):
     return best
 
 
+INV_COST = 3146751                     # kInvCost (me_kernels.hpp): the cost field of an invalid candidate's key constant
 PK_SLOT_MAX = 64 * 255                 # the largest sum a PKMIN slot holds (the 8x8 CU, all rows)
 PK_MARKER = 0xFFFF - PK_SLOT_MAX       # packed MV cost of an invalid candidate: marker + any sum still fits u16 ...
 PK_COST_MAX = PK_MARKER - PK_SLOT_MAX - 1   # ... and every valid cost + sum stays below it (the host's gate: me_pk_gate, me_kernels.hpp)
+
+
+# ---- marker-free twin (pk = 2): which classes of 16x16-level slots take the packed minimum ----------------------------------------
+PK2_SLOT_MAX = 16 * 12 * 255            # 48 960: 16x12 / 12x16, the largest sum a PKMIN slot of the marker-free body holds (FEN: even rows x 2)
+PK2_COST_MAX = 0xFFFF - PK2_SLOT_MAX    # 16 575: the largest MV cost with which every packed cost stays below 2^16 (me_pk2_gate)
+OPS = {"PKADD": 1, "PKSUB": 2, "KEYS": 4, "LIN": 4, "SUB": 4, "MIN4": 2, "PKMIN": 4, "PKMINE": 4}   # VALU instructions per IR op
+# class -> (slots per 16x16 CU, largest cost, ops per 16x16 CU in the pk tree, ops in packed form, ops it adds above per 16x16 CU).
+# Slots whose forms depend on each other are one class: 12x16 is a key difference (whole - 4x16) only while 4x16 forms keys.
+# Above: a 32x32 forms 32x8 (all rows) and 8x32 from the strips of two regions on its edge -- a union of two keys (LIN) today, a packed
+# add and a KEYS where the strips are packed: + 1 op per slot, 2 slots per kind and 32x32 CU = half an op per 16x16 CU and kind.
+PK2_CLASSES = {
+    "16x8":       (2, 16 * 8 * 255,  2 * (OPS["PKADD"] + OPS["KEYS"] + OPS["MIN4"]), 2 * (OPS["PKADD"] + OPS["PKMIN"]), 0.5),
+    "16x4":       (2, 16 * 4 * 255,  2 * (OPS["PKADD"] + OPS["KEYS"] + OPS["MIN4"]), 2 * (OPS["PKADD"] + OPS["PKMIN"]), 0),
+    "8x16":       (2, 8 * 16 * 255,  2 * (OPS["PKADD"] + OPS["KEYS"] + OPS["MIN4"]), 2 * (OPS["PKADD"] + OPS["PKMINE"]), 0.5),
+    "16x12":      (2, 16 * 12 * 255, 2 * (OPS["PKSUB"] + OPS["KEYS"] + OPS["MIN4"]), 2 * (OPS["PKSUB"] + OPS["PKMINE"]), 0),
+    "4x16+12x16": (4, 16 * 12 * 255, 2 * (OPS["PKADD"] + OPS["KEYS"] + OPS["MIN4"]) + 2 * (OPS["SUB"] + OPS["MIN4"]),
+                   2 * (OPS["PKADD"] + OPS["PKMINE"]) + 2 * (OPS["PKSUB"] + OPS["PKMINE"]), 0),
+    "16x16":      (1, 16 * 16 * 255, OPS["PKADD"] + OPS["KEYS"] + OPS["MIN4"], OPS["PKADD"] + OPS["PKMIN"], 0),   # 65 280: no room for any MV cost
+}
+# the two 32x8 strips of a 32x32 CU (all rows) hold up to 65 280 as well: not eligible, like 16x16
+
+
+def pk2_choice():
+    """class -> True where the packed form fits 16 bits beside an MV cost and is cheaper, what it costs the slots above included"""
+    return {name: mx <= PK2_SLOT_MAX and new + above < old for name, (n, mx, old, new, above) in PK2_CLASSES.items() if name != "16x16"}
+
+
+def valu_count(tree):
+    """full-rate VALU instructions of one lane-iteration of a Tree (the leaves' v_qsad_pk_u16_u8 not counted)"""
+    counts = {}
+    for op in tree.ops:
+        counts[op[0]] = counts.get(op[0], 0) + 1
+    valu = sum(OPS[t] * counts.get(t, 0) for t in OPS) + counts.get("ACC", 0)
+    merges = [sum(1 for op in tree.ops if op[0] == "MERGE" and op[1] == lv) for lv in range(6)]
+    return valu + 2 * (merges[0] + merges[1]) + 4 * sum(merges[2:]), counts, merges
 
 
 def simulate(tree, window, cur, lane_off, c, best, pk=None):
@@ -937,9 +1038,15 @@ def simulate(tree, window, cur, lane_off, c, best, pk=None):
             val[op[1]] = (val[op[2]] - val[op[3]] + c.T).astype(np.uint32)
         elif t == "MIN4":
             val[op[1]] = val[op[2]].min(axis=1).astype(np.uint32)
-        elif t == "PKMIN":
-            q = val[op[2]].astype(np.int64) + pk[0].T.astype(np.int64)      # one 64-bit add: a field that overflowed would carry into the next
-            assert (q <= 0xFFFF).all(), "a packed cost left its 16 bits"
+        elif t in ("PKMIN", "PKMINE"):
+            # one 64-bit add (PKMINE: of the sums shifted by one): a field that overflowed would carry into the next.  Only a lane whose
+            # four candidates are all invalid may do that (its key constant carries the invalid cost, so the key is dropped whatever its
+            # minimum is); its fields are modelled with the carries
+            q = (val[op[2]].astype(np.int64) << (1 if t == "PKMINE" else 0)) + pk[0].T.astype(np.int64)
+            live = (pk[1].astype(np.int64) >> IDX_BITS) < INV_COST
+            assert (q[live] <= 0xFFFF).all(), "a packed cost left its 16 bits"
+            word = sum(int(1 << (16 * j)) * q[:, j].astype(object) for j in range(4))
+            q = np.stack([np.array([(int(w) >> (16 * j)) & 0xFFFF for w in word], np.int64) for j in range(4)], axis=1)
             val[op[1]] = (q.min(axis=1) * MULT_A + pk[1].astype(np.int64)).astype(np.uint32)
         elif t == "MERGE":
             _, level, m, a, b = op
@@ -955,19 +1062,19 @@ def simulate(tree, window, cur, lane_off, c, best, pk=None):
 
 
 def main():
-    for fen, pk in ((0, False), (1, False), (0, True), (1, True)):
+    names = {False: "me_tree_fen%d.inc", True: "me_tree_pk_fen%d.inc", 2: "me_tree_pk2_fen%d.inc"}
+    headers = {False: None, True: HEADER_PK, 2: HEADER_PK2}
+    label = {False: "", True: " packed minima", 2: " packed minima, marker-free"}
+    for fen, pk in ((0, False), (1, False), (0, True), (1, True), (1, 2)):
         tree = Tree(fen, pk).build()
-        emit_cpp(tree, os.path.join(OUT_DIR, f"me_tree_pk_fen{fen}.inc" if pk else f"me_tree_fen{fen}.inc"), HEADER_PK if pk else None)
-        counts = {}
-        for op in tree.ops:
-            counts[op[0]] = counts.get(op[0], 0) + 1
+        emit_cpp(tree, os.path.join(OUT_DIR, names[pk] % fen), headers[pk])
         # a packed add is ONE v_lshl_add_u64, a packed subtract two v_sub_u32; PKMIN = packed add of the MV costs + 3
-        valu = counts.get("PKADD", 0) + counts.get("PKSUB", 0) * 2 + (counts.get("KEYS", 0) + counts.get("LIN", 0)) * 4 \
-            + counts.get("SUB", 0) * 4 + counts.get("MIN4", 0) * 2 + counts.get("PKMIN", 0) * 4 + counts.get("ACC", 0)
-        merges = [sum(1 for op in tree.ops if op[0] == "MERGE" and op[1] == lv) for lv in range(6)]
-        valu += 2 * (merges[0] + merges[1]) + 4 * sum(merges[2:])
-        print(f"fen={fen}{' packed minima' if pk else ''}: {len(tree.ops)} IR ops {counts}; merges/level {merges}; ~{valu} full-rate VALU + "
+        valu, counts, merges = valu_count(tree)
+        print(f"fen={fen}{label[pk]}: {len(tree.ops)} IR ops {counts}; merges/level {merges}; ~{valu} full-rate VALU + "
               f"{counts['QSAD']} qsad per lane-iteration (4 candidates)")
+        if pk == 2:
+            print(f"fen={fen}{label[pk]}: {valu_count(Tree(fen, True).build())[0] - valu} VALU instructions below the packed-minimum tree "
+                  f"(classes packed: {', '.join(k for k, v in tree.pk2.items() if v)})")
         if pk:
             assert np.array_equal(ref_map, tree.slot_of_lane()), "the packed-minimum tree must use the same slot map"
         elif fen == 1:
