@@ -1310,6 +1310,8 @@ __global__ void me_prep_jobs_tile_kernel(MeJob16* jobs, int* first_strip_of_job,
 // with ds_add_u64 -- a third of the LDS atomics, which on content whose slots share their motion were 40 % of an item's time (up to sixteen
 // lanes of a wave add to the same large slot: profiles/r05k_frac_phases_before_after.txt).  A field never carries into the next: the largest sum is the
 // 64x64 slot's, 64 8x8 Hadamard blocks of at most 8 * 64 * 255 / 4 = 32 640 each (Parseval) = 2 088 960 < 2^21; SAD 64 * 64 * 255.
+// The bound is reached: a difference of +-255 in the sign pattern of the Sylvester matrix H8 (a bent function: all 64 coefficients 8 * 255)
+// gives exactly 32 640 per 8x8 block, and tests/test_gpu_refine_spectral.py pins it (tests/spectral_content.py has the pictures).
 // Wider samples (and the biased ones of bi-prediction origins) keep nine 32-bit sums.
 constexpr bool frac_pack3(int bps) { return bps == 1; }
 constexpr int frac_acc_row(int bps) { return frac_pack3(bps) ? 6 : 9; }   // dwords per slot
