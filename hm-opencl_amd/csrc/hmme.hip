@@ -1807,6 +1807,18 @@ int check_weights(hmme_ctx* ctx, const char* who, const hmme_frame_params* fp, c
   return HMME_OK;
 }
 inline bool same_weight(const hmme_weight& a, const hmme_weight& b) { return a.w0 == b.w0 && a.offset == b.offset && a.shift == b.shift && a.round == b.round; }
+// A weighted refinement runs one launch per run of pairs with equal weights: the weight is one kernel argument (FracWp).
+// run_end: the end of the run that begins at pair a (wps == null: no explicit weights, all n pairs are one run)
+inline int run_end(const hmme_weight* wps, int a, int n) {
+  int b = wps ? a + 1 : n;
+  while (b < n && same_weight(wps[b], wps[a])) ++b;
+  return b;
+}
+// frac_wp: weight w on current samples staged with `bias` -- org_sub takes the bias off again, with the weight's offset; null: the weight is 1
+inline hmme::FracWp frac_wp(const hmme_weight* w, int bias) {
+  if (!w) return hmme::FracWp{1.f, 0.f, (float)bias};
+  return hmme::FracWp{std::ldexp((float)w->w0, -w->shift), std::ldexp((float)w->round, -w->shift), (float)(bias + w->offset)};
+}
 
 // geometry of the u16 copies of a launch's planes
 struct WpGeom {
@@ -1946,8 +1958,7 @@ int hmme_refine_pairs_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, con
   CopyCache raw(ctx->wp(2), g.plane_bytes, false), wcur(ctx->wp(3), g.plane_bytes, false);   // references widened to u16 / current pictures widened and biased
   // one launch per run of pairs with equal weights: the weight is one kernel argument (FracWp)
   for (int a = 0, b; a < n_pairs && rc == HMME_OK; a = b) {
-    for (b = a + 1; b < n_pairs && same_weight(wps[b], wps[a]); ++b) {}
-    const hmme_weight& w = wps[a];
+    b = run_end(wps, a, n_pairs);
     const bool ident = info[a].identity;   // the prediction is the reference: the unweighted kernel on the planes themselves
     const int wide = ident ? src_wide : 1;
     RefSet c = one_ref(nullptr), rf = one_ref(nullptr);
@@ -1968,7 +1979,7 @@ int hmme_refine_pairs_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, con
     L.curs = c; L.refs = rf;
     L.cur_pitch = ident ? curs[0]->pitch : g.pitch; L.ref_pitch = ident ? refs[0]->pitch : g.pitch;   // (a u16 plane's own pitch is g.pitch)
     L.build.wide = wide; L.build.wp = ident ? 0 : 1;
-    if (!ident) L.fw = hmme::FracWp{std::ldexp((float)w.w0, -w.shift), std::ldexp((float)w.round, -w.shift), (float)(info[a].bias + w.offset)};
+    if (!ident) L.fw = frac_wp(&wps[a], info[a].bias);
     L.d_pred = d_pred_q ? (const int16_t*)d_pred_q + (size_t)a * n_ctu * 2 : nullptr; L.pairs = b - a;
     rc = launch_refine(ctx, L, s);
   }
@@ -1999,6 +2010,19 @@ int hmme_refine_frame_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* 
 // the window centred on d_center_q where the caller gives one (me_prep_jobs16_kernel).  The refinement writes the origin into a padded u16
 // plane instead (the refinement kernel reads its current block by pitch) and runs me_frac_kernel<HAD, 2, 1> with the identity weight and
 // org_sub = bias on the RAW reference: the plane itself above 8 bits, a widened copy at 8 (DESIGN.md 7 gives the reason for this choice).
+// With explicit weights (the *_w calls) the searched list's weight prices the candidates (xGetSADw / xGetHADsw: the copy of the reference is
+// weighted, the refinement runs one launch per run of equal searched weights) and the other list's shapes the prediction the origin is built
+// from (addWeightUni).  A launch whose weights are all the identity IS the unweighted call with FEN off.
+// Two forms share the bodies below (BiLaunch, bi_search, bi_refine).  The PAIRS form (hmme_*_pairs_bi*, hmme_*_frame_bi, _bi_w) searches n
+// picture pairs, each against the prediction from its own plane and motion field of the other list; the LISTS form (hmme_*_frame_bi_refs*; the
+// rule: include/hmme.h) searches one picture against all references of a list, the other list's prediction coming from a reference per block,
+// others[d_other_ref[block]].  They differ in four things:
+//   origins  one per pair, from others[r] with the field at field * r -- or ONE for the launch, as the multi-reference uni launch hands one
+//            current picture to its pairs (me_predict_kernel<T, 1, 0 | 2, 1>, one launch per call); the biased / raw copies stay per reference
+//   bias     the pair's own -- or ONE for all references, the largest of the searched weights' own (weight_eval); every weighted copy then
+//            carries offset_r + bias
+//   weights  of the other list: one MePredWp<1> per origin launch (pw) -- or all of them in the one launch (pr with prw)
+//   tail     the planes come in pairs (pairs_end) -- or in two lists of their own lengths (lists_end)
 namespace {
 // what the kernels hold, from the nominal sample range: origin in [-maxv, 2 maxv], reference in [0, maxv]
 int bipred_eval(int bit_depth, int refine, char* msg, size_t n) {
@@ -2039,16 +2063,23 @@ int bi_args(hmme_ctx* ctx, const char* who, const hmme_plane* const* curs, const
   return HMME_OK;
 }
 
-// A pair of the bi pass as the kernels take it: the searched list's bias and identity (WpInfo) and the other list's weight as addWeightUni
-// forms it.  Without explicit weights: bias maxv, both identities.
+// The weights of a bi launch as the kernels take them.  Per searched pair r: the bias its origin and weighted reference carry and whether
+// its weight is the identity, as weight_eval reads the word (round included); in the lists form every bias is the common maximum.  Per pair
+// or plane k of the other list: its weight as addWeightUni forms it, and whether it is the identity (the prediction family's meaning).
+// Without explicit weights: bias maxv, all identities.
 struct BiWp {
-  WpInfo info;
-  bool other_identity = true;
-  hmme::MePredWp<1> pw{};
+  int bias[hmme::kMaxRefs] = {};
+  bool identity[hmme::kMaxRefs] = {};
+  hmme::MePredWp<2> other = {};
+  bool other_identity[hmme::kMaxRefs] = {};
+  bool others_identity = true;   // every other weight: the lists form's origin is the unweighted one
+  bool all_identity = true;      // every weight of both lists: the call IS the unweighted one with fen = 0
+  static BiWp unweighted(int bit_depth) {
+    BiWp bw;
+    for (int r = 0; r < hmme::kMaxRefs; ++r) { bw.bias[r] = (1 << bit_depth) - 1; bw.identity[r] = bw.other_identity[r] = true; }
+    return bw;
+  }
 };
-void bi_unweighted(int bit_depth, int n_pairs, BiWp* bw) {
-  for (int r = 0; r < n_pairs; ++r) { bw[r] = BiWp{}; bw[r].info.bias = (1 << bit_depth) - 1; bw[r].info.identity = true; }
-}
 
 // What is an argument error in every weight of the bi family, before any range is looked at: bit depth, null, shift.  (weight_eval, the
 // *_w family's check, answers HMME_ERR_UNSUPPORTED to a bit depth outside 8..12 and keeps doing so; the bi family follows hmme_bipred_check,
@@ -2077,13 +2108,32 @@ int other_weight_eval(int bit_depth, const hmme_weight* wp, bool* identity, hmme
   return HMME_OK;
 }
 
-// both weights of a pair: the argument errors of both first, then the searched list's ranges against a bi-prediction origin, then the
+// the range checks of one weight of a bi launch, and what the kernels take from it into the summary (bw null: the check alone): searched
+// weight r against a bi-prediction origin, other weight k
+int bi_searched_eval(int bit_depth, const hmme_weight* wp, int refine, BiWp* bw, int r, char* msg, size_t n) {
+  WpInfo info;
+  const int rc = weight_eval(bit_depth, wp, refine, kBiOrigin, &info, msg, n);
+  if (rc == HMME_OK && bw) { bw->bias[r] = info.bias; bw->identity[r] = info.identity; bw->all_identity = bw->all_identity && info.identity; }
+  return rc;
+}
+int bi_other_eval(int bit_depth, const hmme_weight* wp, BiWp* bw, int k, char* msg, size_t n) {
+  bool id = true;
+  hmme::MePredWp<1> pw;
+  const int rc = other_weight_eval(bit_depth, wp, &id, &pw, msg, n);
+  if (rc == HMME_OK && bw) {
+    bw->other.ref[k] = pw; bw->other_identity[k] = id;
+    bw->others_identity = bw->others_identity && id; bw->all_identity = bw->all_identity && id;
+  }
+  return rc;
+}
+
+// both weights of pair r: the argument errors of both first, then the searched list's ranges against a bi-prediction origin, then the
 // other list's
-int bipred_weight_eval(int bit_depth, const hmme_weight* wp, const hmme_weight* other_wp, int refine, BiWp* bw, char* msg, size_t n) {
+int bipred_weight_eval(int bit_depth, const hmme_weight* wp, const hmme_weight* other_wp, int refine, BiWp* bw, int r, char* msg, size_t n) {
   int rc = bi_weight_args(bit_depth, wp, "searched", msg, n);
   if (rc == HMME_OK) rc = bi_weight_args(bit_depth, other_wp, "other", msg, n);
-  if (rc == HMME_OK) rc = weight_eval(bit_depth, wp, refine, kBiOrigin, bw ? &bw->info : nullptr, msg, n);
-  if (rc == HMME_OK) rc = other_weight_eval(bit_depth, other_wp, bw ? &bw->other_identity : nullptr, bw ? &bw->pw : nullptr, msg, n);
+  if (rc == HMME_OK) rc = bi_searched_eval(bit_depth, wp, refine, bw, r, msg, n);
+  if (rc == HMME_OK) rc = bi_other_eval(bit_depth, other_wp, bw, r, msg, n);
   return rc;
 }
 
@@ -2124,16 +2174,15 @@ int predict_bi_weight_eval(int bit_depth, const hmme_weight* wp0, const hmme_wei
 
 // every pair's two weights before anything is launched; the message names the pair
 int check_bi_weights(hmme_ctx* ctx, const char* who, const hmme_frame_params* fp, const hmme_weight* wps, const hmme_weight* other_wps, int n_pairs, int refine,
-                     BiWp* bw, bool* all_identity) {
+                     BiWp* bw) {
   if (!fp) return fail(ctx, HMME_ERR_ARG, "%s: null params", who);
   if (!wps || !other_wps) return fail(ctx, HMME_ERR_ARG, "%s: null weights", who);
   if (n_pairs < 1 || n_pairs > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d picture pairs outside 1..%d", who, n_pairs, hmme::kMaxRefs);
-  *all_identity = true;
+  *bw = BiWp{};
   char msg[256];
   for (int r = 0; r < n_pairs; ++r) {
-    const int rc = bipred_weight_eval(fp->bit_depth, &wps[r], &other_wps[r], refine, &bw[r], msg, sizeof msg);
+    const int rc = bipred_weight_eval(fp->bit_depth, &wps[r], &other_wps[r], refine, bw, r, msg, sizeof msg);
     if (rc) return fail(ctx, rc, "%s: pair %d: %s", who, r, msg);
-    *all_identity = *all_identity && bw[r].info.identity && bw[r].other_identity;
   }
   return HMME_OK;
 }
@@ -2383,251 +2432,9 @@ int hmme_predict_frame_w(hmme_ctx* ctx, const hmme_plane* ref, const hmme_frame_
 }
 
 namespace {
-// the bi search after its checks.  wps == null: no explicit weights (bw from bi_unweighted); else the searched list's weights, bw from
-// check_bi_weights and fp->fen already 0
-int bi_search(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others, int n_pairs,
-              const hmme_frame_params* fp, const hmme_weight* wps, const BiWp* bw, const void* d_other_mv, int mv_per_ctu, const void* d_center_q,
-              const void* d_pred_q, void* d_out_mv, void* d_out_sad, void* stream) {
-  if (!d_out_mv || !d_out_sad) return fail(ctx, HMME_ERR_ARG, "null output buffer");
-  hipStream_t s = (hipStream_t)stream;
-  PairLaunch pl;
-  int rc = pairs_begin(ctx, curs, refs, n_pairs, fp, s, &pl);
-  if (rc || pl.count == 0) return rc;
-  for (int r = 0; r < n_pairs && rc == HMME_OK; ++r) rc = plane_wait(ctx, others[r], s);
-  const WpGeom g(refs[0]);
-  const int n_ctu = curs[0]->n_ctu, ctus_x = curs[0]->ctus_x;
-  if (rc == HMME_OK) rc = ensure(ctx, ctx->buf[kWp0], g.plane_bytes * n_pairs);
-  if (rc == HMME_OK) rc = ensure(ctx, ctx->buf[kWp1], g.blk_bytes * n_pairs);
-  RefSet wrefs = one_ref(nullptr), wcurs = one_ref(nullptr);
-  const size_t field = (size_t)n_ctu * mv_per_ctu * 2;
-  CopyCache wref(ctx->wp(0), g.plane_bytes, false);   // the references with the origin's bias
-  for (int r = 0; r < n_pairs && rc == HMME_OK; ++r) {
-    const int bias = bw[r].info.bias;   // origin and weighted reference carry the pair's bias
-    rc = cached_copy(ctx, wref, g, r, wps ? CopyKey{refs[r], wps[r].w0, wps[r].round, wps[r].shift, wps[r].offset + bias} : CopyKey{refs[r], 1, 0, 0, bias}, s,
-                     &wrefs.base[r]);
-    if (rc != HMME_OK) break;
-    uint8_t* blocks = ctx->wp(1) + g.blk_bytes * r;   // the origin: one per pair (it depends on the pair's field)
-    rc = launch_predict(ctx, others[r], (const int16_t*)d_other_mv + field * r, mv_per_ctu, pl.first, pl.count, true, curs[r]->d_blocks, bias, blocks,
-                        hmme::kBlkBytes16, (long)ctus_x * hmme::kBlkBytes16, 128, s, bw[r].other_identity ? nullptr : &bw[r].pw);
-    wcurs.base[r] = blocks;
-  }
-  const FramePlan plan = plan_launch(ctx, fp, pl.count, n_pairs, true);
-  if (rc == HMME_OK) rc = prep_jobs(ctx, curs[0], fp, d_pred_q, pl.first, pl.count, n_pairs, s, plan, d_center_q);
-  if (rc == HMME_OK) rc = run_search(ctx, wcurs, ctus_x, wrefs, g.pitch, fp, plan, (int16_t*)d_out_mv, (uint32_t*)d_out_sad, s);
-  return pairs_end(ctx, curs, refs, n_pairs, s, rc, others);
-}
-
-// the bi refinement after its checks; wps / bw as in bi_search.  One launch per run of equal searched weights (the weight is one kernel
-// argument, FracWp), one launch in all without explicit weights
-int bi_refine(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others, int n_pairs,
-              const hmme_frame_params* fp, const hmme_weight* wps, const BiWp* bw, const void* d_other_mv, int mv_per_ctu, const void* d_center_q,
-              const void* d_pred_q, const void* d_int_mv, int use_hadamard, void* d_out_qmv, void* d_out_cost, void* stream) {
-  if (!d_int_mv || !d_out_qmv || !d_out_cost) return fail(ctx, HMME_ERR_ARG, "null buffer");
-  hipStream_t s = (hipStream_t)stream;
-  PairLaunch pl;
-  int rc = pairs_begin(ctx, curs, refs, n_pairs, fp, s, &pl);
-  if (rc || pl.count == 0) return rc;
-  for (int r = 0; r < n_pairs && rc == HMME_OK; ++r) rc = plane_wait(ctx, others[r], s);
-  const int src_wide = curs[0]->bps == 2 ? 1 : 0, n_ctu = curs[0]->n_ctu;
-  const WpGeom g(refs[0]);
-  if (rc == HMME_OK && !src_wide) rc = ensure(ctx, ctx->buf[kWp2], g.plane_bytes * n_pairs);
-  if (rc == HMME_OK) rc = ensure(ctx, ctx->buf[kWp3], g.plane_bytes * n_pairs);
-  RefSet c = one_ref(nullptr), rf = one_ref(nullptr);
-  const size_t field = (size_t)n_ctu * mv_per_ctu * 2;
-  CopyCache raw(ctx->wp(2), g.plane_bytes, false);
-  for (int r = 0; r < n_pairs && rc == HMME_OK; ++r) {
-    // the RAW reference is interpolated: a u16 plane serves as it is, an 8-bit one is widened
-    if (src_wide) rf.base[r] = pl.refs.base[r];
-    else rc = cached_copy(ctx, raw, g, r, CopyKey{refs[r], 1, 0, 0, 0}, s, &rf.base[r]);
-    if (rc != HMME_OK) break;
-    // the origin in a padded plane's layout: only the CTU blocks are written and read (a partial CTU's block ends 63 samples into the
-    // 128 / 80-sample margins at most)
-    uint8_t* plane = ctx->wp(3) + g.plane_bytes * r + g.origin;
-    rc = launch_predict(ctx, others[r], (const int16_t*)d_other_mv + field * r, mv_per_ctu, pl.first, pl.count, true, curs[r]->d_blocks, bw[r].info.bias, plane,
-                        128, 64L * g.pitch, g.pitch, s, bw[r].other_identity ? nullptr : &bw[r].pw);
-    c.base[r] = plane;
-  }
-  for (int a = 0, b; a < n_pairs && rc == HMME_OK; a = b) {
-    for (b = wps ? a + 1 : n_pairs; b < n_pairs && same_weight(wps[b], wps[a]); ++b) {}
-    RefSet ca = one_ref(nullptr), ra = one_ref(nullptr);
-    for (int r = a; r < b; ++r) { ca.base[r - a] = c.base[r]; ra.base[r - a] = rf.base[r]; }
-    // the run's own table and counter in the same buffer as the run before (on one stream: behind its kernel)
-    const size_t res0 = (size_t)a * pl.count * HMME_NUM_CTU_PARTS;
-    RefineLaunch L;
-    refine_common(L, pl, curs[0], fp, use_hadamard, (const int16_t*)d_int_mv + 2 * res0, (int16_t*)d_out_qmv + 2 * res0, (uint32_t*)d_out_cost + res0);
-    L.curs = ca; L.refs = ra; L.cur_pitch = g.pitch; L.ref_pitch = g.pitch;
-    L.build.wide = 1; L.build.wp = 1;
-    // org_sub takes the origin's bias off, with the weight's offset; without explicit weights (and for an identity weight) the weight is 1
-    if (wps && !bw[a].info.identity)
-      L.fw = hmme::FracWp{std::ldexp((float)wps[a].w0, -wps[a].shift), std::ldexp((float)wps[a].round, -wps[a].shift), (float)(bw[a].info.bias + wps[a].offset)};
-    else
-      L.fw = hmme::FracWp{1.f, 0.f, (float)bw[a].info.bias};
-    L.d_pred = d_pred_q ? (const int16_t*)d_pred_q + (size_t)a * n_ctu * 2 : nullptr;
-    L.d_center = d_center_q ? (const int16_t*)d_center_q + (size_t)a * n_ctu * 2 : nullptr;
-    L.pairs = b - a;
-    L.table = FracTable::kAlways;   // the table carries the window centres (FracPrep derives windows from predictors only)
-    rc = launch_refine(ctx, L, s);
-  }
-  return pairs_end(ctx, curs, refs, n_pairs, s, rc, others);
-}
-}  // namespace
-
-int hmme_search_pairs_bi_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others,
-                                int n_pairs, const hmme_frame_params* fp, const void* d_other_mv, int mv_per_ctu, const void* d_center_q,
-                                const void* d_pred_q, void* d_out_mv, void* d_out_sad, void* stream) {
-  if (!ctx) return HMME_ERR_ARG;
-  int rc = bi_check(ctx, "hmme_search_pairs_bi_device", fp, 0);
-  if (rc == HMME_OK) rc = bi_args(ctx, "hmme_search_pairs_bi_device", curs, refs, others, n_pairs, fp, d_other_mv, mv_per_ctu);
-  if (rc) return rc;
-  BiWp bw[hmme::kMaxRefs];
-  bi_unweighted(fp->bit_depth, n_pairs, bw);
-  return bi_search(ctx, curs, refs, others, n_pairs, fp, nullptr, bw, d_other_mv, mv_per_ctu, d_center_q, d_pred_q, d_out_mv, d_out_sad, stream);
-}
-
-int hmme_refine_pairs_bi_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others,
-                                int n_pairs, const hmme_frame_params* fp, const void* d_other_mv, int mv_per_ctu, const void* d_center_q,
-                                const void* d_pred_q, const void* d_int_mv, int use_hadamard, void* d_out_qmv, void* d_out_cost, void* stream) {
-  if (!ctx) return HMME_ERR_ARG;
-  int rc = bi_check(ctx, "hmme_refine_pairs_bi_device", fp, 1);
-  if (rc == HMME_OK) rc = bi_args(ctx, "hmme_refine_pairs_bi_device", curs, refs, others, n_pairs, fp, d_other_mv, mv_per_ctu);
-  if (rc) return rc;
-  BiWp bw[hmme::kMaxRefs];
-  bi_unweighted(fp->bit_depth, n_pairs, bw);
-  return bi_refine(ctx, curs, refs, others, n_pairs, fp, nullptr, bw, d_other_mv, mv_per_ctu, d_center_q, d_pred_q, d_int_mv, use_hadamard, d_out_qmv, d_out_cost,
-                   stream);
-}
-
-// ---- ... with explicit weighted prediction: the searched list's weight prices the candidates (xGetSADw / xGetHADsw), the other list's
-// shapes the prediction the origin is built from (addWeightUni).  A launch whose weights are all the identity IS the unweighted call with
-// FEN off.
-int hmme_bipred_weight_check(int bit_depth, const hmme_weight* wp, const hmme_weight* other_wp, int refine) {
-  char msg[256];
-  return bipred_weight_eval(bit_depth, wp, other_wp, refine, nullptr, msg, sizeof msg);
-}
-
-int hmme_search_pairs_bi_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others,
-                                  int n_pairs, const hmme_frame_params* fp, const hmme_weight* wps, const hmme_weight* other_wps, const void* d_other_mv,
-                                  int mv_per_ctu, const void* d_center_q, const void* d_pred_q, void* d_out_mv, void* d_out_sad, void* stream) {
-  if (!ctx) return HMME_ERR_ARG;
-  BiWp bw[hmme::kMaxRefs];
-  bool all_identity = false;
-  int rc = check_bi_weights(ctx, "hmme_search_pairs_bi_w_device", fp, wps, other_wps, n_pairs, 0, bw, &all_identity);
-  if (rc) return rc;
-  hmme_frame_params f = *fp;
-  f.fen = 0;   // xGetSADw reads every row (TComRdCost.cpp:467-469): FEN is not consulted
-  if (all_identity) return hmme_search_pairs_bi_device(ctx, curs, refs, others, n_pairs, &f, d_other_mv, mv_per_ctu, d_center_q, d_pred_q, d_out_mv, d_out_sad, stream);
-  rc = bi_args(ctx, "hmme_search_pairs_bi_w_device", curs, refs, others, n_pairs, &f, d_other_mv, mv_per_ctu);
-  if (rc) return rc;
-  return bi_search(ctx, curs, refs, others, n_pairs, &f, wps, bw, d_other_mv, mv_per_ctu, d_center_q, d_pred_q, d_out_mv, d_out_sad, stream);
-}
-
-int hmme_refine_pairs_bi_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others,
-                                  int n_pairs, const hmme_frame_params* fp, const hmme_weight* wps, const hmme_weight* other_wps, const void* d_other_mv,
-                                  int mv_per_ctu, const void* d_center_q, const void* d_pred_q, const void* d_int_mv, int use_hadamard, void* d_out_qmv,
-                                  void* d_out_cost, void* stream) {
-  if (!ctx) return HMME_ERR_ARG;
-  BiWp bw[hmme::kMaxRefs];
-  bool all_identity = false;
-  int rc = check_bi_weights(ctx, "hmme_refine_pairs_bi_w_device", fp, wps, other_wps, n_pairs, 1, bw, &all_identity);
-  if (rc) return rc;
-  hmme_frame_params f = *fp;
-  f.fen = 0;
-  if (all_identity)
-    return hmme_refine_pairs_bi_device(ctx, curs, refs, others, n_pairs, &f, d_other_mv, mv_per_ctu, d_center_q, d_pred_q, d_int_mv, use_hadamard, d_out_qmv,
-                                       d_out_cost, stream);
-  rc = bi_args(ctx, "hmme_refine_pairs_bi_w_device", curs, refs, others, n_pairs, &f, d_other_mv, mv_per_ctu);
-  if (rc) return rc;
-  return bi_refine(ctx, curs, refs, others, n_pairs, &f, wps, bw, d_other_mv, mv_per_ctu, d_center_q, d_pred_q, d_int_mv, use_hadamard, d_out_qmv, d_out_cost, stream);
-}
-
-namespace {
-// the four synchronous one-pair bi calls: wp == null is the call without explicit weights; int_mv != null the refinement
-int bi_frame(hmme_ctx* ctx, const char* who, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
-             const hmme_weight* wp, const hmme_weight* other_wp, bool weighted, const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q,
-             const int16_t* pred_q, bool refine, const int16_t* int_mv, int use_hadamard, int16_t* out_mv, uint32_t* out_cost) {
-  int rc;
-  if (weighted) {   // before anything is staged: the device call checks again
-    BiWp bw;
-    bool identity = false;
-    rc = check_bi_weights(ctx, who, fp, wp, other_wp, 1, refine, &bw, &identity);
-  } else {
-    rc = bi_check(ctx, who, fp, refine);
-  }
-  if (rc == HMME_OK) rc = bi_args(ctx, who, &cur, &ref, &other, 1, fp, other_mv, mv_per_ctu);
-  if (rc) return rc;
-  int count;
-  Stage st(ctx);
-  FrameItems it;
-  const int field = st.in(other_mv, sizeof(int16_t) * 2 * (size_t)cur->n_ctu * mv_per_ctu), center = st.in(center_q, sizeof(int16_t) * 2 * (size_t)cur->n_ctu);
-  rc = stage_in(ctx, cur, ref, fp, 1, pred_q, refine, int_mv, out_mv, out_cost, &count, st, &it);
-  if (rc || count == 0) return rc;
-  void *d_pred = st.at(it.pred), *d_field = st.at(field), *d_center = st.at(center), *d_mv = st.at(it.mv), *d_cost = st.at(it.cost);
-  if (!refine)
-    rc = weighted ? hmme_search_pairs_bi_w_device(ctx, &cur, &ref, &other, 1, fp, wp, other_wp, d_field, mv_per_ctu, d_center, d_pred, d_mv, d_cost, ctx->stream)
-                  : hmme_search_pairs_bi_device(ctx, &cur, &ref, &other, 1, fp, d_field, mv_per_ctu, d_center, d_pred, d_mv, d_cost, ctx->stream);
-  else
-    rc = weighted ? hmme_refine_pairs_bi_w_device(ctx, &cur, &ref, &other, 1, fp, wp, other_wp, d_field, mv_per_ctu, d_center, d_pred, st.at(it.imv), use_hadamard,
-                                                  d_mv, d_cost, ctx->stream)
-                  : hmme_refine_pairs_bi_device(ctx, &cur, &ref, &other, 1, fp, d_field, mv_per_ctu, d_center, d_pred, st.at(it.imv), use_hadamard, d_mv, d_cost,
-                                                ctx->stream);
-  return rc ? rc : st.end();
-}
-}  // namespace
-
-int hmme_search_frame_bi(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
-                         const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q, const int16_t* pred_q, int16_t* out_mv, uint32_t* out_sad) {
-  if (!ctx) return HMME_ERR_ARG;
-  return bi_frame(ctx, "hmme_search_frame_bi", cur, ref, other, fp, nullptr, nullptr, false, other_mv, mv_per_ctu, center_q, pred_q, false, nullptr, 0, out_mv, out_sad);
-}
-
-int hmme_refine_frame_bi(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
-                         const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q, const int16_t* pred_q, const int16_t* int_mv,
-                         int use_hadamard, int16_t* out_qmv, uint32_t* out_cost) {
-  if (!ctx) return HMME_ERR_ARG;
-  return bi_frame(ctx, "hmme_refine_frame_bi", cur, ref, other, fp, nullptr, nullptr, false, other_mv, mv_per_ctu, center_q, pred_q, true, int_mv, use_hadamard, out_qmv,
-                  out_cost);
-}
-
-int hmme_search_frame_bi_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
-                           const hmme_weight* wp, const hmme_weight* other_wp, const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q,
-                           const int16_t* pred_q, int16_t* out_mv, uint32_t* out_sad) {
-  if (!ctx) return HMME_ERR_ARG;
-  return bi_frame(ctx, "hmme_search_frame_bi_w", cur, ref, other, fp, wp, other_wp, true, other_mv, mv_per_ctu, center_q, pred_q, false, nullptr, 0, out_mv, out_sad);
-}
-
-int hmme_refine_frame_bi_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
-                           const hmme_weight* wp, const hmme_weight* other_wp, const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q,
-                           const int16_t* pred_q, const int16_t* int_mv, int use_hadamard, int16_t* out_qmv, uint32_t* out_cost) {
-  if (!ctx) return HMME_ERR_ARG;
-  return bi_frame(ctx, "hmme_refine_frame_bi_w", cur, ref, other, fp, wp, other_wp, true, other_mv, mv_per_ctu, center_q, pred_q, true, int_mv, use_hadamard, out_qmv,
-                  out_cost);
-}
-
-// ---- the bi pass of one list over all its references, against a reference per block in the other list (the rule: include/hmme.h) ----------
-// bi_search / bi_refine with ONE origin for all n_refs pairs, as the multi-reference uni launch hands one current picture to its pairs: the
-// other list's prediction comes from others[d_other_ref[block]] (me_predict_kernel<T, 1, 0, 1>, one launch per call), the biased / raw
-// reference copies stay per reference.  No explicit weights: the bias is maxv.
-// With explicit weights (the *_bi_refs_w calls; the rule: include/hmme.h, "multi-reference B pictures: explicit weights and 4:2:0 chroma"):
-// the ONE origin carries ONE bias for all references, the largest of the searched weights' own (weight_eval); every weighted copy carries
-// offset_r + bias, the refinement runs one launch per run of equal searched weights as bi_refine does, and the origin comes from
-// me_predict_kernel<T, 1, 2, 1> unless every other weight is the identity.
-namespace {
-struct BiRefsWp {
-  int bias = 0;
-  bool identity[hmme::kMaxRefs] = {};   // the searched weights, as weight_eval reads the word (round included)
-  bool all_identity = true;             // every weight of both lists: the call IS the unweighted one with fen = 0
-  bool others_identity = true;          // every other weight (the prediction family's meaning): the unweighted origin
-  hmme::MePredWp<2> pw = {};            // the other list's weights as addWeightUni takes them
-};
-BiRefsWp bi_refs_unweighted(int bit_depth) {
-  BiRefsWp bw;
-  bw.bias = (1 << bit_depth) - 1;
-  for (bool& id : bw.identity) id = true;
-  return bw;
-}
-// In the header's order: 1. the argument errors of all searched weights, then of all other weights; 2. the searched lines per reference, with
-// `refine`; 3. the "other weight" line per other reference.
-int bipred_refs_weight_eval(int bit_depth, const hmme_weight* wps, int n_refs, const hmme_weight* other_wps, int n_others, int refine, BiRefsWp* out, char* msg, size_t n) {
+// The weights of the lists form, in the header's order: 1. the argument errors of all searched weights, then of all other weights; 2. the
+// searched lines per reference, with `refine`; 3. the "other weight" line per other reference.  (check_bi_weights goes pair by pair instead.)
+int bipred_refs_weight_eval(int bit_depth, const hmme_weight* wps, int n_refs, const hmme_weight* other_wps, int n_others, int refine, BiWp* out, char* msg, size_t n) {
   const hmme_weight* const lists[2] = {wps, other_wps};
   const int cnt[2] = {n_refs, n_others};
   static const char* const name[2] = {"searched", "other"};
@@ -2642,32 +2449,27 @@ int bipred_refs_weight_eval(int bit_depth, const hmme_weight* wps, int n_refs, c
       if (rc) { snprintf(msg, n, "%s reference %d: %s", name[l], r, why); return rc; }
     }
   }
-  BiRefsWp bw;
+  BiWp bw;
   for (int r = 0; r < n_refs; ++r) {
-    WpInfo info;
-    const int rc = weight_eval(bit_depth, &wps[r], refine, kBiOrigin, &info, why, sizeof why);
+    const int rc = bi_searched_eval(bit_depth, &wps[r], refine, &bw, r, why, sizeof why);
     if (rc) { snprintf(msg, n, "searched reference %d: %s", r, why); return rc; }
-    bw.bias = std::max(bw.bias, info.bias);
-    bw.identity[r] = info.identity;
-    bw.all_identity = bw.all_identity && info.identity;
   }
+  std::fill_n(bw.bias, n_refs, *std::max_element(bw.bias, bw.bias + n_refs));   // ONE origin, hence ONE bias
   for (int r = 0; r < n_others; ++r) {
-    bool id = true;
-    const int rc = other_weight_eval(bit_depth, &other_wps[r], &id, &bw.pw.ref[r], why, sizeof why);
+    const int rc = bi_other_eval(bit_depth, &other_wps[r], &bw, r, why, sizeof why);
     if (rc) { snprintf(msg, n, "other reference %d: %s", r, why); return rc; }
-    bw.others_identity = bw.others_identity && id;
   }
-  bw.all_identity = bw.all_identity && bw.others_identity;
   if (out) *out = bw;
   return HMME_OK;
 }
 int check_bi_refs_weights(hmme_ctx* ctx, const char* who, const hmme_frame_params* fp, const hmme_weight* wps, int n_refs, const hmme_weight* other_wps, int n_others,
-                          int refine, BiRefsWp* bw) {
+                          int refine, BiWp* bw) {
   if (!fp) return fail(ctx, HMME_ERR_ARG, "%s: null params", who);
   char msg[256];
   const int rc = bipred_refs_weight_eval(fp->bit_depth, wps, n_refs, other_wps, n_others, refine, bw, msg, sizeof msg);
   return rc ? fail(ctx, rc, "%s: %s", who, msg) : HMME_OK;
 }
+// bi_args for the lists form
 int bi_refs_args(hmme_ctx* ctx, const char* who, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
                  const hmme_frame_params* fp, const void* d_other_mv, const void* d_other_ref, int mv_per_ctu) {
   if (!cur || !refs || !others || n_refs < 1 || n_refs > hmme::kMaxRefs || n_others < 1 || n_others > hmme::kMaxRefs)
@@ -2685,237 +2487,310 @@ int bi_refs_args(hmme_ctx* ctx, const char* who, const hmme_plane* cur, const hm
   return HMME_OK;
 }
 
-// the launch's planes as lists_end takes them: the current picture and the searched list
-struct BiRefsPlanes {
-  const hmme_plane* curs[hmme::kMaxRefs];
-  const hmme_plane* read[hmme::kMaxRefs + 1];
-  BiRefsPlanes(const hmme_plane* cur, const hmme_plane* const* refs, int n_refs) {
-    read[0] = cur;
-    for (int r = 0; r < n_refs; ++r) { curs[r] = cur; read[r + 1] = refs[r]; }
-  }
+// A bi launch of either form, as the bodies take it after its checks
+struct BiLaunch {
+  const hmme_plane* const* curs;   // the n searched (current, reference) pairs; the lists form gives its one current picture as `cur`,
+  const hmme_plane* cur;           //   which bi_call puts into every entry of curs
+  const hmme_plane* const* refs;
+  int n;
+  const hmme_plane* const* others;   // the other list: a plane per pair (n_others == n), or the planes d_other_ref chooses among
+  int n_others;
+  const void* d_other_mv;            // its motion field(s): int16 [n | 1][n_ctu][mv_per_ctu][2]
+  const void* d_other_ref;           // null: the pairs form, one origin per pair; else the lists form, ONE origin for the launch
+  int mv_per_ctu;
+  const hmme_weight* wps;            // the searched weights; null: no explicit weights
+  BiWp bw;
+  int origins() const { return d_other_ref ? 1 : n; }
 };
-hmme::MePredRefs<1> other_set(const hmme_plane* const* others, int n_others, const void* d_other_ref) {
-  hmme::MePredRefs<1> pr = {one_ref(nullptr), (const uint8_t*)d_other_ref, n_others};
-  for (int r = 0; r < n_others; ++r) pr.set.base[r] = others[r]->origin();
-  return pr;
+
+// Where the origins 2 * cur - pred + bias go, origin k at dst + slot * k: the CTU blocks a search reads, or the padded plane a refinement
+// reads by pitch -- only the CTU blocks are written and read (a partial CTU's block ends 63 samples into the 128 / 80-sample margins at most)
+struct BiOrigin {
+  uint8_t* dst; size_t slot; long ctu_x, ctu_y; int pitch;
+  static BiOrigin blocks(hmme_ctx* ctx, const WpGeom& g, int ctus_x) { return {ctx->wp(1), g.blk_bytes, hmme::kBlkBytes16, (long)ctus_x * hmme::kBlkBytes16, 128}; }
+  static BiOrigin plane(hmme_ctx* ctx, const WpGeom& g) { return {ctx->wp(3) + g.origin, g.plane_bytes, 128, 64L * g.pitch, g.pitch}; }
+};
+// *at: the origin pair r is searched against; it is formed behind the copy of the last pair that reads it -- per pair in the pairs form (it
+// depends on the pair's field), once behind the last pair's in the lists form: others[0] gives the geometry all planes share, the weights go
+// along unless every other weight is the identity
+int bi_origin(hmme_ctx* ctx, const BiLaunch& B, int r, const PairLaunch& pl, const BiOrigin& o, hipStream_t s, const uint8_t** at) {
+  const bool lists = B.d_other_ref != nullptr;
+  const int k = lists ? 0 : r;
+  uint8_t* dst = o.dst + o.slot * k;
+  *at = dst;
+  if (lists && r != B.n - 1) return HMME_OK;
+  hmme::MePredRefs<1> pr = {one_ref(nullptr), (const uint8_t*)B.d_other_ref, B.n_others};
+  for (int q = 0; lists && q < B.n_others; ++q) pr.set.base[q] = B.others[q]->origin();
+  const size_t field = (size_t)B.curs[0]->n_ctu * B.mv_per_ctu * 2;
+  return launch_predict(ctx, B.others[k], (const int16_t*)B.d_other_mv + field * k, B.mv_per_ctu, pl.first, pl.count, true, B.curs[k]->d_blocks, B.bw.bias[k], dst,
+                        o.ctu_x, o.ctu_y, o.pitch, s, lists || B.bw.other_identity[k] ? nullptr : &B.bw.other.ref[k], lists ? &pr : nullptr,
+                        lists && !B.bw.others_identity ? &B.bw.other : nullptr);
+}
+// after the kernels are enqueued: all planes of the launch have a reader on `s`
+int bi_end(hmme_ctx* ctx, const BiLaunch& B, hipStream_t s, int rc) {
+  if (!B.d_other_ref) return pairs_end(ctx, B.curs, B.refs, B.n, s, rc, B.others);
+  const hmme_plane* read[hmme::kMaxRefs + 1] = {B.cur};   // the planes do not come in pairs: the current picture and the searched list, the other list
+  std::copy(B.refs, B.refs + B.n, read + 1);
+  return lists_end(ctx, read, B.n + 1, B.others, B.n_others, s, rc);
 }
 
-int bi_refs_search(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
-                   const hmme_frame_params* fp, const hmme_weight* wps, const BiRefsWp& bw, const void* d_other_mv, const void* d_other_ref, int mv_per_ctu,
-                   const void* d_center_q, const void* d_pred_q, void* d_out_mv, void* d_out_sad, void* stream) {
+// the bi search after its checks (fp->fen is 0 with explicit weights)
+int bi_search(hmme_ctx* ctx, const BiLaunch& B, const hmme_frame_params* fp, const void* d_center_q, const void* d_pred_q, void* d_out_mv, void* d_out_sad,
+              void* stream) {
   if (!d_out_mv || !d_out_sad) return fail(ctx, HMME_ERR_ARG, "null output buffer");
   hipStream_t s = (hipStream_t)stream;
-  const BiRefsPlanes p(cur, refs, n_refs);
   PairLaunch pl;
-  int rc = pairs_begin(ctx, p.curs, refs, n_refs, fp, s, &pl);
+  int rc = pairs_begin(ctx, B.curs, B.refs, B.n, fp, s, &pl);
   if (rc || pl.count == 0) return rc;
-  for (int r = 0; r < n_others && rc == HMME_OK; ++r) rc = plane_wait(ctx, others[r], s);
-  const WpGeom g(refs[0]);
-  const int ctus_x = cur->ctus_x, bias = bw.bias;
-  if (rc == HMME_OK) rc = ensure(ctx, ctx->buf[kWp0], g.plane_bytes * n_refs);
-  if (rc == HMME_OK) rc = ensure(ctx, ctx->buf[kWp1], g.blk_bytes);
+  for (int r = 0; r < B.n_others && rc == HMME_OK; ++r) rc = plane_wait(ctx, B.others[r], s);
+  const WpGeom g(B.refs[0]);
+  const int ctus_x = B.curs[0]->ctus_x;
+  if (rc == HMME_OK) rc = ensure(ctx, ctx->buf[kWp0], g.plane_bytes * B.n);
+  if (rc == HMME_OK) rc = ensure(ctx, ctx->buf[kWp1], g.blk_bytes * B.origins());
+  const BiOrigin o = BiOrigin::blocks(ctx, g, ctus_x);
   RefSet wrefs = one_ref(nullptr), wcurs = one_ref(nullptr);
   CopyCache wref(ctx->wp(0), g.plane_bytes, false);   // the references with the origin's bias
-  for (int r = 0; r < n_refs && rc == HMME_OK; ++r) {
-    rc = cached_copy(ctx, wref, g, r, wps ? CopyKey{refs[r], wps[r].w0, wps[r].round, wps[r].shift, wps[r].offset + bias} : CopyKey{refs[r], 1, 0, 0, bias}, s,
-                     &wrefs.base[r]);
-    wcurs.base[r] = ctx->wp(1);   // the ONE origin
+  for (int r = 0; r < B.n && rc == HMME_OK; ++r) {
+    const int bias = B.bw.bias[r];   // origin and weighted reference carry the same bias
+    rc = cached_copy(ctx, wref, g, r, B.wps ? CopyKey{B.refs[r], B.wps[r].w0, B.wps[r].round, B.wps[r].shift, B.wps[r].offset + bias} : CopyKey{B.refs[r], 1, 0, 0, bias},
+                     s, &wrefs.base[r]);
+    if (rc == HMME_OK) rc = bi_origin(ctx, B, r, pl, o, s, &wcurs.base[r]);
   }
-  if (rc == HMME_OK) {
-    const hmme::MePredRefs<1> pr = other_set(others, n_others, d_other_ref);
-    rc = launch_predict(ctx, others[0], (const int16_t*)d_other_mv, mv_per_ctu, pl.first, pl.count, true, cur->d_blocks, bias, ctx->wp(1), hmme::kBlkBytes16,
-                        (long)ctus_x * hmme::kBlkBytes16, 128, s, nullptr, &pr, bw.others_identity ? nullptr : &bw.pw);
-  }
-  const FramePlan plan = plan_launch(ctx, fp, pl.count, n_refs, true);
-  if (rc == HMME_OK) rc = prep_jobs(ctx, cur, fp, d_pred_q, pl.first, pl.count, n_refs, s, plan, d_center_q);
+  const FramePlan plan = plan_launch(ctx, fp, pl.count, B.n, true);
+  if (rc == HMME_OK) rc = prep_jobs(ctx, B.curs[0], fp, d_pred_q, pl.first, pl.count, B.n, s, plan, d_center_q);
   if (rc == HMME_OK) rc = run_search(ctx, wcurs, ctus_x, wrefs, g.pitch, fp, plan, (int16_t*)d_out_mv, (uint32_t*)d_out_sad, s);
-  return lists_end(ctx, p.read, n_refs + 1, others, n_others, s, rc);
+  return bi_end(ctx, B, s, rc);
 }
 
-int bi_refs_refine(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
-                   const hmme_frame_params* fp, const hmme_weight* wps, const BiRefsWp& bw, const void* d_other_mv, const void* d_other_ref, int mv_per_ctu,
-                   const void* d_center_q, const void* d_pred_q, const void* d_int_mv, int use_hadamard, void* d_out_qmv, void* d_out_cost, void* stream) {
+// the bi refinement after its checks: one launch per run of equal searched weights, one launch in all without explicit weights
+int bi_refine(hmme_ctx* ctx, const BiLaunch& B, const hmme_frame_params* fp, const void* d_center_q, const void* d_pred_q, const void* d_int_mv, int use_hadamard,
+              void* d_out_qmv, void* d_out_cost, void* stream) {
   if (!d_int_mv || !d_out_qmv || !d_out_cost) return fail(ctx, HMME_ERR_ARG, "null buffer");
   hipStream_t s = (hipStream_t)stream;
-  const BiRefsPlanes p(cur, refs, n_refs);
   PairLaunch pl;
-  int rc = pairs_begin(ctx, p.curs, refs, n_refs, fp, s, &pl);
+  int rc = pairs_begin(ctx, B.curs, B.refs, B.n, fp, s, &pl);
   if (rc || pl.count == 0) return rc;
-  for (int r = 0; r < n_others && rc == HMME_OK; ++r) rc = plane_wait(ctx, others[r], s);
-  const int src_wide = cur->bps == 2 ? 1 : 0, bias = bw.bias, n_ctu = cur->n_ctu;
-  const WpGeom g(refs[0]);
-  if (rc == HMME_OK && !src_wide) rc = ensure(ctx, ctx->buf[kWp2], g.plane_bytes * n_refs);
-  if (rc == HMME_OK) rc = ensure(ctx, ctx->buf[kWp3], g.plane_bytes);
+  for (int r = 0; r < B.n_others && rc == HMME_OK; ++r) rc = plane_wait(ctx, B.others[r], s);
+  const int src_wide = B.curs[0]->bps == 2 ? 1 : 0, n_ctu = B.curs[0]->n_ctu;
+  const WpGeom g(B.refs[0]);
+  if (rc == HMME_OK && !src_wide) rc = ensure(ctx, ctx->buf[kWp2], g.plane_bytes * B.n);
+  if (rc == HMME_OK) rc = ensure(ctx, ctx->buf[kWp3], g.plane_bytes * B.origins());
+  const BiOrigin o = BiOrigin::plane(ctx, g);
   RefSet c = one_ref(nullptr), rf = one_ref(nullptr);
   CopyCache raw(ctx->wp(2), g.plane_bytes, false);
-  for (int r = 0; r < n_refs && rc == HMME_OK; ++r) {
+  for (int r = 0; r < B.n && rc == HMME_OK; ++r) {
     // the RAW reference is interpolated: a u16 plane serves as it is, an 8-bit one is widened
     if (src_wide) rf.base[r] = pl.refs.base[r];
-    else rc = cached_copy(ctx, raw, g, r, CopyKey{refs[r], 1, 0, 0, 0}, s, &rf.base[r]);
-    c.base[r] = ctx->wp(3) + g.origin;   // the ONE origin, in a padded plane's layout
+    else rc = cached_copy(ctx, raw, g, r, CopyKey{B.refs[r], 1, 0, 0, 0}, s, &rf.base[r]);
+    if (rc == HMME_OK) rc = bi_origin(ctx, B, r, pl, o, s, &c.base[r]);
   }
-  if (rc == HMME_OK) {
-    const hmme::MePredRefs<1> pr = other_set(others, n_others, d_other_ref);
-    rc = launch_predict(ctx, others[0], (const int16_t*)d_other_mv, mv_per_ctu, pl.first, pl.count, true, cur->d_blocks, bias, ctx->wp(3) + g.origin, 128,
-                        64L * g.pitch, g.pitch, s, nullptr, &pr, bw.others_identity ? nullptr : &bw.pw);
-  }
-  // one launch per run of equal searched weights (the weight is one kernel argument, FracWp), one launch in all without explicit weights
-  for (int a = 0, b; a < n_refs && rc == HMME_OK; a = b) {
-    for (b = wps ? a + 1 : n_refs; b < n_refs && same_weight(wps[b], wps[a]); ++b) {}
-    RefSet ra = one_ref(nullptr);
-    for (int r = a; r < b; ++r) ra.base[r - a] = rf.base[r];
+  for (int a = 0, b; a < B.n && rc == HMME_OK; a = b) {
+    b = run_end(B.wps, a, B.n);
+    RefSet ca = one_ref(nullptr), ra = one_ref(nullptr);
+    for (int r = a; r < b; ++r) { ca.base[r - a] = c.base[r]; ra.base[r - a] = rf.base[r]; }
     // the run's own table and counter in the same buffer as the run before (on one stream: behind its kernel)
     const size_t res0 = (size_t)a * pl.count * HMME_NUM_CTU_PARTS;
     RefineLaunch L;
-    refine_common(L, pl, cur, fp, use_hadamard, (const int16_t*)d_int_mv + 2 * res0, (int16_t*)d_out_qmv + 2 * res0, (uint32_t*)d_out_cost + res0);
-    L.curs = c; L.refs = ra; L.cur_pitch = g.pitch; L.ref_pitch = g.pitch;   // c: the ONE origin in every entry
+    refine_common(L, pl, B.curs[0], fp, use_hadamard, (const int16_t*)d_int_mv + 2 * res0, (int16_t*)d_out_qmv + 2 * res0, (uint32_t*)d_out_cost + res0);
+    L.curs = ca; L.refs = ra; L.cur_pitch = g.pitch; L.ref_pitch = g.pitch;
     L.build.wide = 1; L.build.wp = 1;
-    // org_sub takes the origin's bias off, with the weight's offset; without explicit weights (and for an identity weight) the weight is 1
-    if (wps && !bw.identity[a])
-      L.fw = hmme::FracWp{std::ldexp((float)wps[a].w0, -wps[a].shift), std::ldexp((float)wps[a].round, -wps[a].shift), (float)(bias + wps[a].offset)};
-    else
-      L.fw = hmme::FracWp{1.f, 0.f, (float)bias};
+    L.fw = frac_wp(B.wps && !B.bw.identity[a] ? &B.wps[a] : nullptr, B.bw.bias[a]);   // (an identity weight: the weight is 1)
     L.d_pred = d_pred_q ? (const int16_t*)d_pred_q + (size_t)a * n_ctu * 2 : nullptr;
     L.d_center = d_center_q ? (const int16_t*)d_center_q + (size_t)a * n_ctu * 2 : nullptr;
     L.pairs = b - a;
-    L.table = FracTable::kAlways;   // the table carries the window centres
+    L.table = FracTable::kAlways;   // the table carries the window centres (FracPrep derives windows from predictors only)
     rc = launch_refine(ctx, L, s);
   }
-  return lists_end(ctx, p.read, n_refs + 1, others, n_others, s, rc);
+  return bi_end(ctx, B, s, rc);
 }
 
-// the two synchronous forms; int_mv != null: the refinement
-int bi_refs_frame(hmme_ctx* ctx, const char* who, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
-                  const hmme_frame_params* fp, const hmme_weight* wps, const hmme_weight* other_wps, bool weighted, const int16_t* other_mv, const uint8_t* other_ref,
-                  int mv_per_ctu, const int16_t* center_q, const int16_t* pred_q, bool refine, const int16_t* int_mv, int use_hadamard, int16_t* out_mv, uint32_t* out_cost) {
-  // weighted: before anything is staged; the device call checks again
-  int rc = weighted ? check_bi_refs_weights(ctx, who, fp, wps, n_refs, other_wps, n_others, refine, nullptr) : bi_check(ctx, who, fp, refine);
-  if (rc == HMME_OK) rc = bi_refs_args(ctx, who, cur, refs, n_refs, others, n_others, fp, other_mv, other_ref, mv_per_ctu);
+// What distinguishes the sixteen entries: the name for messages, the form, explicit weights or not, search or refinement, and whether the
+// arrays are the host's (the synchronous forms).  plain: the unweighted device entry, which an all-identity call IS and answers as
+enum : unsigned { kBiLists = 1, kBiWeighted = 2, kBiRefine = 4, kBiHost = 8 };
+struct BiCall {
+  const char* who; const char* plain; bool lists, weighted, refine, host;
+  BiCall(const char* who_, unsigned what, const char* plain_ = nullptr)
+      : who(who_), plain(plain_), lists(what & kBiLists), weighted(what & kBiWeighted), refine(what & kBiRefine), host(what & kBiHost) {}
+};
+
+// The refusals of a bi call in the order that decides the code returned: null params, then the weights (without them: the depth), then the
+// arguments pairs_begin does not look at.  Leaves in B the summary of the weights and in *f the parameters the bodies run with
+int bi_checks(hmme_ctx* ctx, const BiCall& c, BiLaunch* B, const hmme_frame_params* fp, const hmme_weight* other_wps, hmme_frame_params* f) {
+  const char* who = c.who;
+  int rc;
+  if (!c.weighted) rc = bi_check(ctx, who, fp, c.refine);
+  else if (c.lists) rc = check_bi_refs_weights(ctx, who, fp, B->wps, B->n, other_wps, B->n_others, c.refine, &B->bw);
+  else rc = check_bi_weights(ctx, who, fp, B->wps, other_wps, B->n, c.refine, &B->bw);
   if (rc) return rc;
+  *f = *fp;
+  if (c.weighted) f->fen = 0;   // xGetSADw reads every row (TComRdCost.cpp:467-469): FEN is not consulted
+  if (c.weighted && B->bw.all_identity) { B->wps = nullptr; if (!c.host) who = c.plain; }
+  if (!B->wps) B->bw = BiWp::unweighted(f->bit_depth);
+  return c.lists ? bi_refs_args(ctx, who, B->cur, B->refs, B->n, B->others, B->n_others, f, B->d_other_mv, B->d_other_ref, B->mv_per_ctu)
+                 : bi_args(ctx, who, B->curs, B->refs, B->others, B->n, f, B->d_other_mv, B->mv_per_ctu);
+}
+
+// Every entry: the checks, then the body on the caller's stream -- or, for the host arrays of a synchronous form, through the staging arena
+// on ctx->stream: up go the field, the reference field (lists), the centres and stage_in's items, the tables come back
+int bi_call(hmme_ctx* ctx, const BiCall& c, BiLaunch B, const hmme_frame_params* fp, const hmme_weight* other_wps, const void* center_q, const void* pred_q,
+            const void* int_mv, int use_hadamard, void* out_mv, void* out_cost, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  const hmme_plane* same[hmme::kMaxRefs];
+  if (c.lists) { std::fill_n(same, hmme::kMaxRefs, B.cur); B.curs = same; }
+  hmme_frame_params f;
+  int rc = bi_checks(ctx, c, &B, fp, other_wps, &f);   // (a synchronous form: before anything is staged)
+  if (rc) return rc;
+  const auto body = [&](const void* d_center, const void* d_pred, const void* d_imv, void* d_mv, void* d_cost, void* on) {
+    return c.refine ? bi_refine(ctx, B, &f, d_center, d_pred, d_imv, use_hadamard, d_mv, d_cost, on) : bi_search(ctx, B, &f, d_center, d_pred, d_mv, d_cost, on);
+  };
+  if (!c.host) return body(center_q, pred_q, int_mv, out_mv, out_cost, stream);
   int count;
   Stage st(ctx);
   FrameItems it;
-  const size_t blocks = (size_t)cur->n_ctu * mv_per_ctu;
-  const int field = st.in(other_mv, sizeof(int16_t) * 2 * blocks), rfield = st.in(other_ref, blocks);
-  const int center = st.in(center_q, sizeof(int16_t) * 2 * (size_t)cur->n_ctu * n_refs);
-  rc = stage_in(ctx, cur, refs[0], fp, n_refs, pred_q, refine, int_mv, out_mv, out_cost, &count, st, &it);
+  const size_t n_ctu = (size_t)B.curs[0]->n_ctu, blocks = n_ctu * B.mv_per_ctu;
+  const int field = st.in(B.d_other_mv, sizeof(int16_t) * 2 * blocks), rfield = st.in(B.d_other_ref, blocks);
+  const int center = st.in(center_q, sizeof(int16_t) * 2 * n_ctu * B.n);
+  rc = stage_in(ctx, B.curs[0], B.refs[0], fp, B.n, (const int16_t*)pred_q, c.refine, (const int16_t*)int_mv, (int16_t*)out_mv, (uint32_t*)out_cost, &count, st, &it);
   if (rc || count == 0) return rc;
-  if (!refine && !weighted)
-    rc = hmme_search_frame_bi_refs_device(ctx, cur, refs, n_refs, others, n_others, fp, st.at(field), st.at(rfield), mv_per_ctu, st.at(center), st.at(it.pred),
-                                          st.at(it.mv), st.at(it.cost), ctx->stream);
-  else if (!refine)
-    rc = hmme_search_frame_bi_refs_w_device(ctx, cur, refs, n_refs, others, n_others, fp, wps, other_wps, st.at(field), st.at(rfield), mv_per_ctu, st.at(center),
-                                            st.at(it.pred), st.at(it.mv), st.at(it.cost), ctx->stream);
-  else if (!weighted)
-    rc = hmme_refine_frame_bi_refs_device(ctx, cur, refs, n_refs, others, n_others, fp, st.at(field), st.at(rfield), mv_per_ctu, st.at(center), st.at(it.pred),
-                                          st.at(it.imv), use_hadamard, st.at(it.mv), st.at(it.cost), ctx->stream);
-  else
-    rc = hmme_refine_frame_bi_refs_w_device(ctx, cur, refs, n_refs, others, n_others, fp, wps, other_wps, st.at(field), st.at(rfield), mv_per_ctu, st.at(center),
-                                            st.at(it.pred), st.at(it.imv), use_hadamard, st.at(it.mv), st.at(it.cost), ctx->stream);
+  B.d_other_mv = st.at(field); B.d_other_ref = st.at(rfield);
+  rc = body(st.at(center), st.at(it.pred), st.at(it.imv), st.at(it.mv), st.at(it.cost), ctx->stream);
   return rc ? rc : st.end();
 }
 }  // namespace
 
+int hmme_bipred_weight_check(int bit_depth, const hmme_weight* wp, const hmme_weight* other_wp, int refine) {
+  char msg[256];
+  return bipred_weight_eval(bit_depth, wp, other_wp, refine, nullptr, 0, msg, sizeof msg);
+}
+
+int hmme_bipred_refs_weight_check(int bit_depth, const hmme_weight* wps, int n_refs, const hmme_weight* other_wps, int n_others, int refine) {
+  char msg[256];
+  return bipred_refs_weight_eval(bit_depth, wps, n_refs, other_wps, n_others, refine, nullptr, msg, sizeof msg);
+}
+
+// the pairs form on device arrays ...
+int hmme_search_pairs_bi_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others,
+                                int n_pairs, const hmme_frame_params* fp, const void* d_other_mv, int mv_per_ctu, const void* d_center_q,
+                                const void* d_pred_q, void* d_out_mv, void* d_out_sad, void* stream) {
+  return bi_call(ctx, BiCall("hmme_search_pairs_bi_device", 0), {curs, nullptr, refs, n_pairs, others, n_pairs, d_other_mv, nullptr, mv_per_ctu},
+                 fp, nullptr, d_center_q, d_pred_q, nullptr, 0, d_out_mv, d_out_sad, stream);
+}
+
+int hmme_refine_pairs_bi_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others,
+                                int n_pairs, const hmme_frame_params* fp, const void* d_other_mv, int mv_per_ctu, const void* d_center_q,
+                                const void* d_pred_q, const void* d_int_mv, int use_hadamard, void* d_out_qmv, void* d_out_cost, void* stream) {
+  return bi_call(ctx, BiCall("hmme_refine_pairs_bi_device", kBiRefine), {curs, nullptr, refs, n_pairs, others, n_pairs, d_other_mv, nullptr, mv_per_ctu},
+                 fp, nullptr, d_center_q, d_pred_q, d_int_mv, use_hadamard, d_out_qmv, d_out_cost, stream);
+}
+
+int hmme_search_pairs_bi_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others,
+                                  int n_pairs, const hmme_frame_params* fp, const hmme_weight* wps, const hmme_weight* other_wps, const void* d_other_mv,
+                                  int mv_per_ctu, const void* d_center_q, const void* d_pred_q, void* d_out_mv, void* d_out_sad, void* stream) {
+  return bi_call(ctx, BiCall("hmme_search_pairs_bi_w_device", kBiWeighted, "hmme_search_pairs_bi_device"),
+                 {curs, nullptr, refs, n_pairs, others, n_pairs, d_other_mv, nullptr, mv_per_ctu, wps}, fp, other_wps, d_center_q, d_pred_q, nullptr, 0, d_out_mv, d_out_sad,
+                 stream);
+}
+
+int hmme_refine_pairs_bi_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others,
+                                  int n_pairs, const hmme_frame_params* fp, const hmme_weight* wps, const hmme_weight* other_wps, const void* d_other_mv,
+                                  int mv_per_ctu, const void* d_center_q, const void* d_pred_q, const void* d_int_mv, int use_hadamard, void* d_out_qmv,
+                                  void* d_out_cost, void* stream) {
+  return bi_call(ctx, BiCall("hmme_refine_pairs_bi_w_device", kBiWeighted | kBiRefine, "hmme_refine_pairs_bi_device"),
+                 {curs, nullptr, refs, n_pairs, others, n_pairs, d_other_mv, nullptr, mv_per_ctu, wps}, fp, other_wps, d_center_q, d_pred_q, d_int_mv, use_hadamard, d_out_qmv,
+                 d_out_cost, stream);
+}
+
+// ... and one pair of it on host arrays
+int hmme_search_frame_bi(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
+                         const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q, const int16_t* pred_q, int16_t* out_mv, uint32_t* out_sad) {
+  return bi_call(ctx, BiCall("hmme_search_frame_bi", kBiHost), {&cur, nullptr, &ref, 1, &other, 1, other_mv, nullptr, mv_per_ctu}, fp, nullptr, center_q,
+                 pred_q, nullptr, 0, out_mv, out_sad, nullptr);
+}
+
+int hmme_refine_frame_bi(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
+                         const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q, const int16_t* pred_q, const int16_t* int_mv,
+                         int use_hadamard, int16_t* out_qmv, uint32_t* out_cost) {
+  return bi_call(ctx, BiCall("hmme_refine_frame_bi", kBiRefine | kBiHost), {&cur, nullptr, &ref, 1, &other, 1, other_mv, nullptr, mv_per_ctu}, fp, nullptr, center_q,
+                 pred_q, int_mv, use_hadamard, out_qmv, out_cost, nullptr);
+}
+
+int hmme_search_frame_bi_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
+                           const hmme_weight* wp, const hmme_weight* other_wp, const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q,
+                           const int16_t* pred_q, int16_t* out_mv, uint32_t* out_sad) {
+  return bi_call(ctx, BiCall("hmme_search_frame_bi_w", kBiWeighted | kBiHost), {&cur, nullptr, &ref, 1, &other, 1, other_mv, nullptr, mv_per_ctu, wp}, fp, other_wp,
+                 center_q, pred_q, nullptr, 0, out_mv, out_sad, nullptr);
+}
+
+int hmme_refine_frame_bi_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
+                           const hmme_weight* wp, const hmme_weight* other_wp, const int16_t* other_mv, int mv_per_ctu, const int16_t* center_q,
+                           const int16_t* pred_q, const int16_t* int_mv, int use_hadamard, int16_t* out_qmv, uint32_t* out_cost) {
+  return bi_call(ctx, BiCall("hmme_refine_frame_bi_w", kBiWeighted | kBiRefine | kBiHost), {&cur, nullptr, &ref, 1, &other, 1, other_mv, nullptr, mv_per_ctu, wp}, fp, other_wp,
+                 center_q, pred_q, int_mv, use_hadamard, out_qmv, out_cost, nullptr);
+}
+
+// the lists form on device arrays ...
 int hmme_search_frame_bi_refs_device(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others,
                                      int n_others, const hmme_frame_params* fp, const void* d_other_mv, const void* d_other_ref, int mv_per_ctu,
                                      const void* d_center_q, const void* d_pred_q, void* d_out_mv, void* d_out_sad, void* stream) {
-  if (!ctx) return HMME_ERR_ARG;
-  int rc = bi_check(ctx, "hmme_search_frame_bi_refs_device", fp, 0);
-  if (rc == HMME_OK) rc = bi_refs_args(ctx, "hmme_search_frame_bi_refs_device", cur, refs, n_refs, others, n_others, fp, d_other_mv, d_other_ref, mv_per_ctu);
-  if (rc) return rc;
-  return bi_refs_search(ctx, cur, refs, n_refs, others, n_others, fp, nullptr, bi_refs_unweighted(fp->bit_depth), d_other_mv, d_other_ref, mv_per_ctu, d_center_q, d_pred_q,
-                        d_out_mv, d_out_sad, stream);
+  return bi_call(ctx, BiCall("hmme_search_frame_bi_refs_device", kBiLists), {nullptr, cur, refs, n_refs, others, n_others, d_other_mv, d_other_ref, mv_per_ctu},
+                 fp, nullptr, d_center_q, d_pred_q, nullptr, 0, d_out_mv, d_out_sad, stream);
 }
 
 int hmme_refine_frame_bi_refs_device(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others,
                                      int n_others, const hmme_frame_params* fp, const void* d_other_mv, const void* d_other_ref, int mv_per_ctu,
                                      const void* d_center_q, const void* d_pred_q, const void* d_int_mv, int use_hadamard, void* d_out_qmv, void* d_out_cost,
                                      void* stream) {
-  if (!ctx) return HMME_ERR_ARG;
-  int rc = bi_check(ctx, "hmme_refine_frame_bi_refs_device", fp, 1);
-  if (rc == HMME_OK) rc = bi_refs_args(ctx, "hmme_refine_frame_bi_refs_device", cur, refs, n_refs, others, n_others, fp, d_other_mv, d_other_ref, mv_per_ctu);
-  if (rc) return rc;
-  return bi_refs_refine(ctx, cur, refs, n_refs, others, n_others, fp, nullptr, bi_refs_unweighted(fp->bit_depth), d_other_mv, d_other_ref, mv_per_ctu, d_center_q,
-                        d_pred_q, d_int_mv, use_hadamard, d_out_qmv, d_out_cost, stream);
-}
-
-int hmme_search_frame_bi_refs(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
-                              const hmme_frame_params* fp, const int16_t* other_mv, const uint8_t* other_ref, int mv_per_ctu, const int16_t* center_q,
-                              const int16_t* pred_q, int16_t* out_mv, uint32_t* out_sad) {
-  if (!ctx) return HMME_ERR_ARG;
-  return bi_refs_frame(ctx, "hmme_search_frame_bi_refs", cur, refs, n_refs, others, n_others, fp, nullptr, nullptr, false, other_mv, other_ref, mv_per_ctu, center_q, pred_q, false, nullptr, 0,
-                       out_mv, out_sad);
-}
-
-int hmme_refine_frame_bi_refs(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
-                              const hmme_frame_params* fp, const int16_t* other_mv, const uint8_t* other_ref, int mv_per_ctu, const int16_t* center_q,
-                              const int16_t* pred_q, const int16_t* int_mv, int use_hadamard, int16_t* out_qmv, uint32_t* out_cost) {
-  if (!ctx) return HMME_ERR_ARG;
-  return bi_refs_frame(ctx, "hmme_refine_frame_bi_refs", cur, refs, n_refs, others, n_others, fp, nullptr, nullptr, false, other_mv, other_ref, mv_per_ctu, center_q, pred_q, true, int_mv,
-                       use_hadamard, out_qmv, out_cost);
-}
-
-// ---- ... with a weight per reference of both lists.  A launch in which every weight of both lists is the identity IS the unweighted call
-// with FEN off.
-int hmme_bipred_refs_weight_check(int bit_depth, const hmme_weight* wps, int n_refs, const hmme_weight* other_wps, int n_others, int refine) {
-  char msg[256];
-  return bipred_refs_weight_eval(bit_depth, wps, n_refs, other_wps, n_others, refine, nullptr, msg, sizeof msg);
+  return bi_call(ctx, BiCall("hmme_refine_frame_bi_refs_device", kBiLists | kBiRefine), {nullptr, cur, refs, n_refs, others, n_others, d_other_mv, d_other_ref, mv_per_ctu},
+                 fp, nullptr, d_center_q, d_pred_q, d_int_mv, use_hadamard, d_out_qmv, d_out_cost, stream);
 }
 
 int hmme_search_frame_bi_refs_w_device(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others,
                                        int n_others, const hmme_frame_params* fp, const hmme_weight* wps, const hmme_weight* other_wps, const void* d_other_mv,
                                        const void* d_other_ref, int mv_per_ctu, const void* d_center_q, const void* d_pred_q, void* d_out_mv, void* d_out_sad,
                                        void* stream) {
-  if (!ctx) return HMME_ERR_ARG;
-  const char* who = "hmme_search_frame_bi_refs_w_device";
-  BiRefsWp bw;
-  int rc = check_bi_refs_weights(ctx, who, fp, wps, n_refs, other_wps, n_others, 0, &bw);
-  if (rc) return rc;
-  hmme_frame_params f = *fp;
-  f.fen = 0;   // xGetSADw reads every row (TComRdCost.cpp:467-469): FEN is not consulted
-  if (bw.all_identity)
-    return hmme_search_frame_bi_refs_device(ctx, cur, refs, n_refs, others, n_others, &f, d_other_mv, d_other_ref, mv_per_ctu, d_center_q, d_pred_q, d_out_mv, d_out_sad,
-                                            stream);
-  rc = bi_refs_args(ctx, who, cur, refs, n_refs, others, n_others, &f, d_other_mv, d_other_ref, mv_per_ctu);
-  if (rc) return rc;
-  return bi_refs_search(ctx, cur, refs, n_refs, others, n_others, &f, wps, bw, d_other_mv, d_other_ref, mv_per_ctu, d_center_q, d_pred_q, d_out_mv, d_out_sad, stream);
+  return bi_call(ctx, BiCall("hmme_search_frame_bi_refs_w_device", kBiLists | kBiWeighted, "hmme_search_frame_bi_refs_device"),
+                 {nullptr, cur, refs, n_refs, others, n_others, d_other_mv, d_other_ref, mv_per_ctu, wps}, fp, other_wps, d_center_q, d_pred_q, nullptr, 0, d_out_mv, d_out_sad,
+                 stream);
 }
 
 int hmme_refine_frame_bi_refs_w_device(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others,
                                        int n_others, const hmme_frame_params* fp, const hmme_weight* wps, const hmme_weight* other_wps, const void* d_other_mv,
                                        const void* d_other_ref, int mv_per_ctu, const void* d_center_q, const void* d_pred_q, const void* d_int_mv, int use_hadamard,
                                        void* d_out_qmv, void* d_out_cost, void* stream) {
-  if (!ctx) return HMME_ERR_ARG;
-  const char* who = "hmme_refine_frame_bi_refs_w_device";
-  BiRefsWp bw;
-  int rc = check_bi_refs_weights(ctx, who, fp, wps, n_refs, other_wps, n_others, 1, &bw);
-  if (rc) return rc;
-  hmme_frame_params f = *fp;
-  f.fen = 0;
-  if (bw.all_identity)
-    return hmme_refine_frame_bi_refs_device(ctx, cur, refs, n_refs, others, n_others, &f, d_other_mv, d_other_ref, mv_per_ctu, d_center_q, d_pred_q, d_int_mv,
-                                            use_hadamard, d_out_qmv, d_out_cost, stream);
-  rc = bi_refs_args(ctx, who, cur, refs, n_refs, others, n_others, &f, d_other_mv, d_other_ref, mv_per_ctu);
-  if (rc) return rc;
-  return bi_refs_refine(ctx, cur, refs, n_refs, others, n_others, &f, wps, bw, d_other_mv, d_other_ref, mv_per_ctu, d_center_q, d_pred_q, d_int_mv, use_hadamard,
-                        d_out_qmv, d_out_cost, stream);
+  return bi_call(ctx, BiCall("hmme_refine_frame_bi_refs_w_device", kBiLists | kBiWeighted | kBiRefine, "hmme_refine_frame_bi_refs_device"),
+                 {nullptr, cur, refs, n_refs, others, n_others, d_other_mv, d_other_ref, mv_per_ctu, wps}, fp, other_wps, d_center_q, d_pred_q, d_int_mv, use_hadamard, d_out_qmv,
+                 d_out_cost, stream);
+}
+
+// ... and on host arrays
+int hmme_search_frame_bi_refs(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
+                              const hmme_frame_params* fp, const int16_t* other_mv, const uint8_t* other_ref, int mv_per_ctu, const int16_t* center_q,
+                              const int16_t* pred_q, int16_t* out_mv, uint32_t* out_sad) {
+  return bi_call(ctx, BiCall("hmme_search_frame_bi_refs", kBiLists | kBiHost), {nullptr, cur, refs, n_refs, others, n_others, other_mv, other_ref, mv_per_ctu}, fp,
+                 nullptr, center_q, pred_q, nullptr, 0, out_mv, out_sad, nullptr);
+}
+
+int hmme_refine_frame_bi_refs(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
+                              const hmme_frame_params* fp, const int16_t* other_mv, const uint8_t* other_ref, int mv_per_ctu, const int16_t* center_q,
+                              const int16_t* pred_q, const int16_t* int_mv, int use_hadamard, int16_t* out_qmv, uint32_t* out_cost) {
+  return bi_call(ctx, BiCall("hmme_refine_frame_bi_refs", kBiLists | kBiRefine | kBiHost), {nullptr, cur, refs, n_refs, others, n_others, other_mv, other_ref, mv_per_ctu}, fp,
+                 nullptr, center_q, pred_q, int_mv, use_hadamard, out_qmv, out_cost, nullptr);
 }
 
 int hmme_search_frame_bi_refs_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
                                 const hmme_frame_params* fp, const hmme_weight* wps, const hmme_weight* other_wps, const int16_t* other_mv, const uint8_t* other_ref,
                                 int mv_per_ctu, const int16_t* center_q, const int16_t* pred_q, int16_t* out_mv, uint32_t* out_sad) {
-  if (!ctx) return HMME_ERR_ARG;
-  return bi_refs_frame(ctx, "hmme_search_frame_bi_refs_w", cur, refs, n_refs, others, n_others, fp, wps, other_wps, true, other_mv, other_ref, mv_per_ctu, center_q,
-                       pred_q, false, nullptr, 0, out_mv, out_sad);
+  return bi_call(ctx, BiCall("hmme_search_frame_bi_refs_w", kBiLists | kBiWeighted | kBiHost),
+                 {nullptr, cur, refs, n_refs, others, n_others, other_mv, other_ref, mv_per_ctu, wps}, fp, other_wps, center_q, pred_q, nullptr, 0, out_mv, out_sad, nullptr);
 }
 
 int hmme_refine_frame_bi_refs_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
                                 const hmme_frame_params* fp, const hmme_weight* wps, const hmme_weight* other_wps, const int16_t* other_mv, const uint8_t* other_ref,
                                 int mv_per_ctu, const int16_t* center_q, const int16_t* pred_q, const int16_t* int_mv, int use_hadamard, int16_t* out_qmv,
                                 uint32_t* out_cost) {
-  if (!ctx) return HMME_ERR_ARG;
-  return bi_refs_frame(ctx, "hmme_refine_frame_bi_refs_w", cur, refs, n_refs, others, n_others, fp, wps, other_wps, true, other_mv, other_ref, mv_per_ctu, center_q,
-                       pred_q, true, int_mv, use_hadamard, out_qmv, out_cost);
+  return bi_call(ctx, BiCall("hmme_refine_frame_bi_refs_w", kBiLists | kBiWeighted | kBiRefine | kBiHost),
+                 {nullptr, cur, refs, n_refs, others, n_others, other_mv, other_ref, mv_per_ctu, wps}, fp, other_wps, center_q, pred_q, int_mv, use_hadamard, out_qmv, out_cost,
+                 nullptr);
 }
 
 // ---- partition decision and motion field from the 593-slot tables ---------------------------------------------------------------------
@@ -4229,11 +4104,10 @@ int hmme_test_time_bipred_origin(hmme_ctx* ctx, const hmme_plane* cur, const hmm
   if (rc) return rc;
   const WpGeom g(cur);
   rc = ensure(ctx, ctx->buf[kWp1], g.blk_bytes);
+  const BiLaunch B = {&cur, nullptr, &other, 1, &other, 1, d_other_mv, nullptr, mv_per_ctu, nullptr, BiWp::unweighted(cur->bit_depth)};   // one pair, bias maxv
+  const uint8_t* at;
   if (rc == HMME_OK)
-    rc = time_reps(ctx, s, reps, "the origin pass", [&] {
-      return launch_predict(ctx, other, (const int16_t*)d_other_mv, mv_per_ctu, 0, cur->n_ctu, true, cur->d_blocks, (1 << cur->bit_depth) - 1, ctx->wp(1),
-                            hmme::kBlkBytes16, (long)cur->ctus_x * hmme::kBlkBytes16, 128, s);
-    }, avg_ms);
+    rc = time_reps(ctx, s, reps, "the origin pass", [&] { return bi_origin(ctx, B, 0, pl, BiOrigin::blocks(ctx, g, cur->ctus_x), s, &at); }, avg_ms);
   return pairs_end(ctx, &cur, &other, 1, s, rc);
 }
 
