@@ -233,8 +233,7 @@ size_t stage_layout(const size_t* bytes, int n, size_t* offsets) {
 struct Stage {
   struct Item {
     size_t bytes = 0;                       // on the device; 0: the caller has no such array, at() is null
-    const void* up[2] = {nullptr, nullptr}; // linear in: one host array, or two of up_bytes each that travel one behind the other
-    size_t up_bytes = 0;
+    const void* up = nullptr;               // linear in: the host array
     void* down = nullptr;                   // linear out and image: the host array
     size_t parts = 0, part_bytes = 0, off = 0, len = 0;   // linear out: of each of `parts` equal parts the bytes [off, off + len) come back
     size_t row = 0, rows = 0, stride = 0;   // image: rows of `row` bytes, `stride` bytes apart at the host, `pitch` (packed: `row`) on the device
@@ -247,9 +246,9 @@ struct Stage {
   explicit Stage(hmme_ctx* c) : ctx(c) {}
   int add(const Item& it) { items.push_back(it); return (int)items.size() - 1; }
   // each returns the item's index for at().  A null host pointer reserves nothing
-  int in(const void* host, size_t bytes, const void* host2 = nullptr) {
+  int in(const void* host, size_t bytes) {
     Item it;
-    if (host && bytes) { it.bytes = host2 ? 2 * bytes : bytes; it.up[0] = host; it.up[1] = host2; it.up_bytes = bytes; }
+    if (host && bytes) { it.bytes = bytes; it.up = host; }
     return add(it);
   }
   int out(void* host, size_t part_bytes, size_t off, size_t len, size_t parts = 1) {
@@ -280,8 +279,7 @@ struct Stage {
     for (size_t i = 0; i < items.size(); ++i) {
       const Item& it = items[i];
       if (it.row) HIP_TRY(ctx, hipMemcpy2DAsync(at((int)i), it.pitch, it.down ? it.down : it.up_image, it.stride, it.row, it.rows, hipMemcpyHostToDevice, ctx->stream));
-      for (int k = 0; k < 2; ++k)
-        if (it.up[k]) HIP_TRY(ctx, hipMemcpyAsync(at((int)i) + k * it.up_bytes, it.up[k], it.up_bytes, hipMemcpyHostToDevice, ctx->stream));
+      if (it.up) HIP_TRY(ctx, hipMemcpyAsync(at((int)i), it.up, it.bytes, hipMemcpyHostToDevice, ctx->stream));
     }
     return HMME_OK;
   }
@@ -2793,8 +2791,13 @@ int hmme_refine_frame_bi_refs_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme
                  nullptr);
 }
 
-// ---- partition decision and motion field from the 593-slot tables ---------------------------------------------------------------------
+// ---- the selection calls: partition decision and motion field from the 593-slot tables, over one table set per picture pair
+// (hmme_select_pairs_device / _frame), the references of a picture (hmme_select_refs_*), the two lists of a B picture (hmme_select_dirs_*)
+// and the references of its two lists (hmme_select_dirs_refs_*).  Every entry fills in a SelectCall; select_device checks and launches it,
+// select_host stages its arrays around select_device.  The entries of the last three families stand further down, by their predictions -------
 namespace {
+constexpr int kMaxDirPics = 4;
+// the evaluation of each family's parameters: what its hmme_select_*check entry returns and what its launches refuse with
 int select_eval(const hmme_select_params* p, char* msg, size_t cap) {
   msg[0] = 0;
   if (!p) { snprintf(msg, cap, "null parameters"); return HMME_ERR_ARG; }
@@ -2808,7 +2811,7 @@ int select_eval(const hmme_select_params* p, char* msg, size_t cap) {
   if (p->cu_cost > (1u << 20) || p->pu_cost > (1u << 20)) { snprintf(msg, cap, "cu_cost %u / pu_cost %u above 2^20", p->cu_cost, p->pu_cost); return HMME_ERR_ARG; }
   return HMME_OK;
 }
-// ... and of a decision over n_pics pictures x n_refs references (the decision of one table set per picture pair: n_refs = 1, no prices)
+// ... of a decision over n_pics pictures x n_refs references (the decision of one table set per picture pair: n_refs = 1, no prices)
 int select_refs_eval(const hmme_select_params* sel, int n_pics, int n_refs, const uint32_t* ref_cost, char* msg, size_t cap) {
   const int bad = select_eval(sel, msg, cap);
   if (bad) return bad;
@@ -2821,6 +2824,184 @@ int select_refs_eval(const hmme_select_params* sel, int n_pics, int n_refs, cons
     if (ref_cost[r] > (1u << 20)) { snprintf(msg, cap, "ref_cost[%d] = %u above 2^20", r, ref_cost[r]); return HMME_ERR_ARG; }
   return HMME_OK;
 }
+// ... of both B-picture decisions, up to the bit counts: dirs = the caller's hmme_dir_params or hmme_dir_refs_params, for null only
+int select_bi_eval(const hmme_select_params* sel, int n_pics, const void* dirs, char* msg, size_t cap) {
+  const int bad = select_eval(sel, msg, cap);
+  if (bad) return bad;
+  if (sel->mv_per_ctu != 64 || sel->mv_unit != 0 || sel->price_mv != 0) {
+    snprintf(msg, cap, "mv_per_ctu %d, mv_unit %d, price_mv %d: the direction is decided on quarter-pel refinement tables, one MV per 8x8 block (64, 0, 0)",
+             sel->mv_per_ctu, sel->mv_unit, sel->price_mv);
+    return HMME_ERR_ARG;
+  }
+  if (n_pics < 1 || n_pics > kMaxDirPics) { snprintf(msg, cap, "%d pictures outside 1..%d", n_pics, kMaxDirPics); return HMME_ERR_ARG; }
+  if (!dirs) { snprintf(msg, cap, "null direction parameters"); return HMME_ERR_ARG; }
+  return HMME_OK;
+}
+int select_dirs_eval(const hmme_select_params* sel, int n_pics, const hmme_dir_params* dirs, char* msg, size_t cap) {
+  const int bad = select_bi_eval(sel, n_pics, dirs, msg, cap);
+  if (bad) return bad;
+  for (int p = 0; p < n_pics; ++p) {
+    const uint32_t v[5] = {dirs[p].dir_bits[0], dirs[p].dir_bits[1], dirs[p].dir_bits[2], dirs[p].list_bits[0], dirs[p].list_bits[1]};
+    for (int k = 0; k < 5; ++k)
+      if (v[k] > 4096) { snprintf(msg, cap, "picture %d: %s[%d] = %u above 4096", p, k < 3 ? "dir_bits" : "list_bits", k < 3 ? k : k - 3, v[k]); return HMME_ERR_ARG; }
+  }
+  return HMME_OK;
+}
+int select_dirs_refs_eval(const hmme_select_params* sel, int n_pics, int n_refs_max, const hmme_dir_refs_params* dirs, char* msg, size_t cap) {
+  const int bad = select_bi_eval(sel, n_pics, dirs, msg, cap);
+  if (bad) return bad;
+  if (n_refs_max < 1 || n_refs_max > hmme::kMaxDirRefs) { snprintf(msg, cap, "%d table sets per list outside 1..%d", n_refs_max, hmme::kMaxDirRefs); return HMME_ERR_ARG; }
+  for (int p = 0; p < n_pics; ++p) {
+    const hmme_dir_refs_params& d = dirs[p];
+    for (int k = 0; k < 3; ++k)
+      if (d.dir_bits[k] > 4096) { snprintf(msg, cap, "picture %d: dir_bits[%d] = %u above 4096", p, k, d.dir_bits[k]); return HMME_ERR_ARG; }
+    for (int l = 0; l < 2; ++l) {
+      if (d.n_refs[l] < 1 || d.n_refs[l] > n_refs_max) { snprintf(msg, cap, "picture %d: %d references in list %d outside 1..%d", p, d.n_refs[l], l, n_refs_max); return HMME_ERR_ARG; }
+      for (int r = 0; r < hmme::kMaxDirRefs; ++r)
+        if (d.ref_bits[l][r] > 4096) { snprintf(msg, cap, "picture %d: ref_bits[%d][%d] = %u above 4096", p, l, r, d.ref_bits[l][r]); return HMME_ERR_ARG; }
+    }
+    if (d.l1_valid_mask >> d.n_refs[1]) { snprintf(msg, cap, "picture %d: l1_valid_mask 0x%x names references at or above %d", p, d.l1_valid_mask, d.n_refs[1]); return HMME_ERR_ARG; }
+  }
+  return HMME_OK;
+}
+
+// One selection call, device or host form.  The buffers in the order they are checked: the family's own, then the ones every family has
+enum SelectFamily { kSelectTable, kSelectRefs, kSelectDirs, kSelectDirsRefs };
+enum SelectBufName { kMvBi, kCostBi, kUniField, kUniRef, kOutRef, kOutDir, kMv, kCost, kPredQ, kOutField, kOutSlot, kOutCost, kSelectBufs };
+enum SelectRole { kInTable, kInPicture, kOut };   // an input over the CTUs of the range / of the picture; an output (of the picture: the range is written)
+struct SelectBuf {
+  const char* name;
+  SelectRole role;
+  size_t ctu_bytes;   // per CTU of one part
+  size_t parts;       // table sets or lists, one behind the other; 0: the family has no such buffer
+  unsigned align;     // of a device address: what the kernel's widest access to it needs
+  bool required;      // may not be null
+  const void* p;      // device address or host array
+};
+struct SelectCall {
+  const char* who;    // the entry the caller made: every refusal but ctu_range's names it
+  SelectFamily family;
+  int width, height, n_pics;
+  int n_refs;         // kSelectRefs: references per picture; kSelectDirsRefs: table sets per list (n_refs_max)
+  const hmme_frame_params* fp;
+  const hmme_select_params* sel;
+  const uint32_t* ref_cost = nullptr;                // kSelectRefs (null: zeros)
+  const hmme_dir_params* dirs = nullptr;             // kSelectDirs
+  const hmme_dir_refs_params* dir_refs = nullptr;    // kSelectDirsRefs
+  SelectBuf buf[kSelectBufs];
+  SelectCall(const char* who, SelectFamily family, int width, int height, int n_pics, int n_refs, const hmme_frame_params* fp, const hmme_select_params* sel)
+      : who(who), family(family), width(width), height(height), n_pics(n_pics), n_refs(n_refs), fp(fp), sel(sel) {
+    const bool refs = family == kSelectRefs, bi = family >= kSelectDirs, multi = family == kSelectDirsRefs;
+    // (sizes matter to select_host alone, behind the evaluation of sel and n_refs)
+    const size_t per = sel ? (size_t)sel->mv_per_ctu : 0, row = HMME_NUM_CTU_PARTS * 4, none = 0, one = 1, lists = bi ? 2 : 1;
+    const size_t sets = refs ? (size_t)n_refs : multi ? 2 * (size_t)n_refs : lists;
+    const SelectBuf all[kSelectBufs] = {
+        {"bi MV table", kInTable, row, bi ? sets : none, 4, true, nullptr},
+        {"bi cost table", kInTable, row, bi ? sets : none, 4, true, nullptr},
+        {"input field", kInPicture, 64 * 4, bi ? lists : none, 4, true, nullptr},
+        {"input reference", kInPicture, 64, multi ? lists : none, 1, true, nullptr},
+        {"reference", kOut, refs ? per : 64, refs ? one : multi ? lists : none, refs ? 2u : 1u, true, nullptr},   // with four MVs per 8x8 block the kernel stores two indices at a time
+        {"direction", kOut, 64, bi ? one : none, multi ? 1u : 2u, true, nullptr},
+        {"MV table", kInTable, row, sets, 4, true, nullptr},   // the kernels move MVs as dwords
+        {"cost table", kInTable, row, sets, 4, true, nullptr},
+        {"predictor", kInPicture, 4, sets, 2, false, nullptr},
+        {"field", kOut, per * 4, lists, 8, true, nullptr},     // with four MVs per 8x8 block, two entries per store
+        {"slot", kOut, per * 2, one, 4, false, nullptr},
+        {"CTU cost", kOut, 4, one, 4, false, nullptr}};
+    for (int b = 0; b < kSelectBufs; ++b) buf[b] = all[b];
+  }
+  SelectCall& with(SelectBufName b, const void* p) { buf[b].p = p; return *this; }
+  SelectCall& with(const uint32_t* prices) { ref_cost = prices; return *this; }
+  SelectCall& with(const hmme_dir_params* d) { dirs = d; return *this; }
+  SelectCall& with(const hmme_dir_refs_params* d) { dir_refs = d; return *this; }
+};
+
+// parameters, then null and (device) misaligned buffers, then the CTU range
+int select_check(hmme_ctx* ctx, const SelectCall& c, bool device, int* n_ctu, int* first, int* count) {
+  if (!ctx) return HMME_ERR_ARG;
+  const auto buffers = [&](int lo, int hi) {   // of the buffers [lo, hi): a null one, then a misaligned one
+    for (int b = lo; b < hi; ++b)
+      if (c.buf[b].parts && c.buf[b].required && !c.buf[b].p) return fail(ctx, HMME_ERR_ARG, "%s: null %s %s", c.who, c.buf[b].name, device ? "buffer" : "array");
+    for (int b = lo; device && b < hi; ++b)
+      if ((uintptr_t)c.buf[b].p & (c.buf[b].align - 1)) return fail(ctx, HMME_ERR_ARG, "%s: misaligned %s buffer (%u bytes)", c.who, c.buf[b].name, c.buf[b].align);
+    return (int)HMME_OK;
+  };
+  char msg[256];
+  int bad;
+  if (c.family == kSelectRefs && (bad = buffers(kOutRef, kOutRef + 1))) return bad;   // hmme_select_refs_* look at the reference buffer before the parameters
+  if (c.family == kSelectDirs) bad = select_dirs_eval(c.sel, c.n_pics, c.dirs, msg, sizeof msg);
+  else if (c.family == kSelectDirsRefs) bad = select_dirs_refs_eval(c.sel, c.n_pics, c.n_refs, c.dir_refs, msg, sizeof msg);
+  else bad = select_refs_eval(c.sel, c.n_pics, c.n_refs, c.ref_cost, msg, sizeof msg);
+  if (bad) return fail(ctx, bad, "%s: %s", c.who, msg);
+  if ((bad = buffers(0, kMv))) return bad;   // the family's own buffers, then the frame and the buffers every family has
+  if (!c.fp || c.width < 1 || c.height < 1) return fail(ctx, HMME_ERR_ARG, "%s: null frame parameters, or a %d x %d picture", c.who, c.width, c.height);
+  if ((bad = buffers(kMv, kSelectBufs))) return bad;
+  *n_ctu = hmme_num_ctus(c.width, c.height);
+  return ctu_range(ctx, c.fp, *n_ctu, first, count);
+}
+
+// the *_device entries: the checks, then the family's kernel over the CTUs of the range of every picture
+int select_device(hmme_ctx* ctx, const SelectCall& c, hipStream_t stream) {
+  int n_ctu, first, count;
+  const int rc = select_check(ctx, c, true, &n_ctu, &first, &count);
+  if (rc || count == 0) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const hmme_select_params& s = *c.sel;
+  const hmme::MeSelect a = {s.mv_per_ctu, s.mv_unit, s.price_mv, s.part_mask, s.min_depth, s.max_depth, s.cu_cost, s.pu_cost};
+  const dim3 grid((unsigned)((count + 3) / 4), (unsigned)c.n_pics), block(256);
+  const auto tab = [&](SelectBufName b) { return (const uint32_t*)c.buf[b].p; };
+  const auto bytes = [&](SelectBufName b) { return (uint8_t*)c.buf[b].p; };
+  const int16_t* pred_q = (const int16_t*)c.buf[kPredQ].p;
+  uint32_t *out_field = (uint32_t*)c.buf[kOutField].p, *out_cost = (uint32_t*)c.buf[kOutCost].p;
+  uint16_t* out_slot = (uint16_t*)c.buf[kOutSlot].p;
+  // the kernels take hmme_dir_params and hmme_dir_refs_params member for member: copied below as they are
+  using KB = hmme::MeDirBits; using KR = hmme::MeDirRefsBits;
+  static_assert(sizeof(KB) == sizeof(hmme_dir_params) && offsetof(KB, list_bits) == offsetof(hmme_dir_params, list_bits), "MeDirBits");
+  static_assert(sizeof(KR) == sizeof(hmme_dir_refs_params) && offsetof(KR, n_refs) == offsetof(hmme_dir_refs_params, n_refs) &&
+                offsetof(KR, ref_bits) == offsetof(hmme_dir_refs_params, ref_bits) && offsetof(KR, l1_valid_mask) == offsetof(hmme_dir_refs_params, l1_valid_mask) &&
+                sizeof(KR::ref_bits) == sizeof(hmme_dir_refs_params::ref_bits), "MeDirRefsBits");
+  if (c.family == kSelectTable) {
+    hipLaunchKernelGGL(hmme::me_select_kernel, grid, block, 0, stream, tab(kMv), tab(kCost), pred_q, out_field, out_slot, out_cost, a, c.width, c.height, n_ctu, first, count, ctx->lambda_q16);
+  } else if (c.family == kSelectRefs) {
+    hmme::MeRefCost price = {};
+    for (int r = 0; c.ref_cost && r < c.n_refs; ++r) price.c[r] = c.ref_cost[r];
+    hipLaunchKernelGGL(hmme::me_select_refs_kernel, grid, block, 0, stream, tab(kMv), tab(kCost), pred_q, out_field, bytes(kOutRef), out_slot, out_cost, a, price, c.n_refs, c.width, c.height,
+                       n_ctu, first, count, ctx->lambda_q16);
+  } else if (c.family == kSelectDirs) {
+    hmme::MeDirParams bits = {};
+    memcpy(bits.p, c.dirs, c.n_pics * sizeof *c.dirs);
+    hipLaunchKernelGGL(hmme::me_select_dirs_kernel, grid, block, 0, stream, tab(kMv), tab(kCost), tab(kMvBi), tab(kCostBi), tab(kUniField), pred_q, out_field, bytes(kOutDir),
+                       out_slot, out_cost, a, bits, c.width, c.height, n_ctu, first, count, ctx->lambda_q16);
+  } else {
+    hmme::MeDirRefsParams bits = {};
+    memcpy(bits.p, c.dir_refs, c.n_pics * sizeof *c.dir_refs);
+    hipLaunchKernelGGL(hmme::me_select_dirs_refs_kernel, grid, block, 0, stream, tab(kMv), tab(kCost), tab(kMvBi), tab(kCostBi), tab(kUniField),
+                       (const uint8_t*)bytes(kUniRef), pred_q, out_field, bytes(kOutRef), bytes(kOutDir), out_slot, out_cost, a, bits, c.n_refs, c.width, c.height, n_ctu, first, count,
+                       ctx->lambda_q16);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  return HMME_OK;
+}
+
+// the *_frame entries (one picture): every array the caller passed into the staging arena, select_device on the staged addresses (null where
+// the caller's array is), then of the outputs the CTUs of the range back: the caller's entries outside it keep their values
+int select_host(hmme_ctx* ctx, const SelectCall& c) {
+  int n_ctu, first, count;
+  int rc = select_check(ctx, c, false, &n_ctu, &first, &count);   // before anything is staged
+  if (rc || count == 0) return rc;
+  Stage st(ctx);
+  for (const SelectBuf& s : c.buf) {   // item b of the arena is buffer b
+    if (s.role == kOut) st.out((void*)s.p, n_ctu * s.ctu_bytes, first * s.ctu_bytes, count * s.ctu_bytes, s.parts);
+    else st.in(s.p, s.parts * (s.role == kInTable ? count : n_ctu) * s.ctu_bytes);
+  }
+  rc = st.begin();
+  if (rc == HMME_OK) {
+    SelectCall staged = c;
+    for (int b = 0; b < kSelectBufs; ++b) staged.buf[b].p = st.at(b);
+    rc = select_device(ctx, staged, ctx->stream);
+  }
+  return rc ? rc : st.end();
+}
 }  // namespace
 
 int hmme_select_check(const hmme_select_params* sel) {
@@ -2828,85 +3009,17 @@ int hmme_select_check(const hmme_select_params* sel) {
   return select_eval(sel, msg, sizeof msg);
 }
 
-namespace {
-// What hmme_select_pairs_device (n_refs = 1, no prices) and hmme_select_refs_device share: the checks of the parameters, of the buffers both
-// take and of the CTU range, then hmme_select_params as the kernels take it and the grid
-struct SelectLaunch {
-  hmme::MeSelect a;
-  int n_ctu, first, count;   // count == 0: nothing to launch
-  dim3 grid;
-};
-int select_begin(hmme_ctx* ctx, const char* who, int width, int height, int n_pics, int n_refs, const uint32_t* ref_cost, const hmme_frame_params* fp,
-                 const hmme_select_params* sel, const void* d_mv, const void* d_cost, const void* d_pred_q, const void* d_out_field, const void* d_out_slot,
-                 const void* d_out_cost, SelectLaunch* L) {
-  char msg[256];
-  const int bad = select_refs_eval(sel, n_pics, n_refs, ref_cost, msg, sizeof msg);
-  if (bad) return fail(ctx, bad, "%s: %s", who, msg);
-  if (!fp || width < 1 || height < 1) return fail(ctx, HMME_ERR_ARG, "%s: null frame parameters, or a %d x %d picture", who, width, height);
-  if (!d_mv || !d_cost || !d_out_field) return fail(ctx, HMME_ERR_ARG, "%s: null table / field buffer", who);
-  // the kernel moves MVs as dwords and, with four MVs per 8x8 block, two entries per store
-  if (((uintptr_t)d_mv & 3) || ((uintptr_t)d_cost & 3) || ((uintptr_t)d_out_field & 7) || ((uintptr_t)d_out_slot & 3) || ((uintptr_t)d_out_cost & 3) ||
-      ((uintptr_t)d_pred_q & 1))
-    return fail(ctx, HMME_ERR_ARG, "%s: misaligned buffer (tables and costs 4 bytes, field 8, slots 4)", who);
-  L->n_ctu = hmme_num_ctus(width, height);
-  const int rc = ctu_range(ctx, fp, L->n_ctu, &L->first, &L->count);
-  if (rc || L->count == 0) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  L->a = {sel->mv_per_ctu, sel->mv_unit, sel->price_mv, sel->part_mask, sel->min_depth, sel->max_depth, sel->cu_cost, sel->pu_cost};
-  L->grid = dim3((unsigned)((L->count + 3) / 4), (unsigned)n_pics);
-  return HMME_OK;
-}
-
-// hmme_select_frame and hmme_select_refs_frame: n_refs table and predictor sets into the staging arena, `launch` on the device addresses (null
-// where the caller's array is; out_ref exists in the refs call only), then the outputs back
-// bi (hmme_select_dirs_frame; else null): the n_refs sets are the two lists.  A second run of n_refs table sets is staged behind the first
-// (d_mv / d_cost + n_refs sets), the lists' input field goes in as d_in_field, and the field that comes back has one part per list
-struct SelectStagedBi { const int16_t* mv; const uint32_t* cost; const int16_t* in_field; };
-using SelectLaunchFn = std::function<int(void* d_mv, void* d_cost, void* d_pred_q, void* d_in_field, void* d_field, void* d_ref, void* d_slot, void* d_ccost, hipStream_t s)>;
-int select_staged(hmme_ctx* ctx, const char* who, int width, int height, const hmme_frame_params* fp, const hmme_select_params* sel, int n_refs,
-                  const uint32_t* ref_cost, const int16_t* mv, const uint32_t* cost, const int16_t* pred_q, int16_t* out_field, uint8_t* out_ref, uint16_t* out_slot,
-                  uint32_t* out_cost, const SelectLaunchFn& launch, const SelectStagedBi* bi = nullptr) {
-  char msg[256];
-  const int bad = select_refs_eval(sel, 1, n_refs, ref_cost, msg, sizeof msg);
-  if (bad) return fail(ctx, bad, "%s: %s", who, msg);
-  if (!fp || width < 1 || height < 1 || !mv || !cost || !out_field) return fail(ctx, HMME_ERR_ARG, "%s: null argument, or a %d x %d picture", who, width, height);
-  const size_t n_ctu = hmme_num_ctus(width, height), per = sel->mv_per_ctu;
-  int first, count;
-  int rc = ctu_range(ctx, fp, (int)n_ctu, &first, &count);
-  if (rc || count == 0) return rc;
-  const size_t tab = (size_t)n_refs * count * HMME_NUM_CTU_PARTS * 4, lists = bi ? n_refs : 1;
-  Stage st(ctx);
-  const int i_mv = st.in(mv, tab, bi ? bi->mv : nullptr), i_cost = st.in(cost, tab, bi ? bi->cost : nullptr), i_pred = st.in(pred_q, (size_t)n_refs * n_ctu * 4);
-  const int i_in = st.in(bi ? bi->in_field : nullptr, lists * n_ctu * per * 4);
-  // only the CTUs of the range come back: the caller's entries outside it keep their values
-  const auto out = [&](void* host, size_t ctu_bytes, size_t parts) { return st.out(host, n_ctu * ctu_bytes, first * ctu_bytes, count * ctu_bytes, parts); };
-  const int o_field = out(out_field, per * 4, lists), o_ref = out(out_ref, per, 1), o_slot = out(out_slot, per * 2, 1), o_cost = out(out_cost, 4, 1);
-  rc = st.begin();
-  if (rc == HMME_OK) rc = launch(st.at(i_mv), st.at(i_cost), st.at(i_pred), st.at(i_in), st.at(o_field), st.at(o_ref), st.at(o_slot), st.at(o_cost), ctx->stream);
-  return rc ? rc : st.end();
-}
-}  // namespace
-
 int hmme_select_pairs_device(hmme_ctx* ctx, int width, int height, int n_pairs, const hmme_frame_params* fp, const hmme_select_params* sel,
                              const void* d_mv, const void* d_cost, const void* d_pred_q, void* d_out_field, void* d_out_slot, void* d_out_cost,
                              void* stream) {
-  if (!ctx) return HMME_ERR_ARG;
-  SelectLaunch L;
-  const int rc = select_begin(ctx, "hmme_select_pairs_device", width, height, n_pairs, 1, nullptr, fp, sel, d_mv, d_cost, d_pred_q, d_out_field, d_out_slot, d_out_cost, &L);
-  if (rc || L.count == 0) return rc;
-  hipLaunchKernelGGL(hmme::me_select_kernel, L.grid, dim3(256), 0, (hipStream_t)stream, (const uint32_t*)d_mv, (const uint32_t*)d_cost, (const int16_t*)d_pred_q,
-                     (uint32_t*)d_out_field, (uint16_t*)d_out_slot, (uint32_t*)d_out_cost, L.a, width, height, L.n_ctu, L.first, L.count, ctx->lambda_q16);
-  HIP_TRY(ctx, hipGetLastError());
-  return HMME_OK;
+  return select_device(ctx, SelectCall("hmme_select_pairs_device", kSelectTable, width, height, n_pairs, 1, fp, sel).with(kMv, d_mv).with(kCost, d_cost)
+                           .with(kPredQ, d_pred_q).with(kOutField, d_out_field).with(kOutSlot, d_out_slot).with(kOutCost, d_out_cost), (hipStream_t)stream);
 }
 
 int hmme_select_frame(hmme_ctx* ctx, int width, int height, const hmme_frame_params* fp, const hmme_select_params* sel, const int16_t* mv,
                       const uint32_t* cost, const int16_t* pred_q, int16_t* out_field, uint16_t* out_slot, uint32_t* out_cost) {
-  if (!ctx) return HMME_ERR_ARG;
-  return select_staged(ctx, "hmme_select_frame", width, height, fp, sel, 1, nullptr, mv, cost, pred_q, out_field, nullptr, out_slot, out_cost,
-                       [&](void* d_mv, void* d_cost, void* d_pred_q, void*, void* d_field, void*, void* d_slot, void* d_ccost, hipStream_t s) {
-                         return hmme_select_pairs_device(ctx, width, height, 1, fp, sel, d_mv, d_cost, d_pred_q, d_field, d_slot, d_ccost, s);
-                       });
+  return select_host(ctx, SelectCall("hmme_select_frame", kSelectTable, width, height, 1, 1, fp, sel).with(kMv, mv).with(kCost, cost).with(kPredQ, pred_q)
+                         .with(kOutField, out_field).with(kOutSlot, out_slot).with(kOutCost, out_cost));
 }
 
 // ---- residual and per-PU / per-CU distortion of a prediction (the rule: include/hmme.h) -------------------------------------------------------
@@ -3020,30 +3133,16 @@ int hmme_select_refs_check(const hmme_select_params* sel, int n_pics, int n_refs
 int hmme_select_refs_device(hmme_ctx* ctx, int width, int height, int n_pics, int n_refs, const hmme_frame_params* fp, const hmme_select_params* sel,
                             const uint32_t* ref_cost, const void* d_mv, const void* d_cost, const void* d_pred_q, void* d_out_field, void* d_out_ref,
                             void* d_out_slot, void* d_out_cost, void* stream) {
-  if (!ctx) return HMME_ERR_ARG;
-  // with four MVs per 8x8 block the kernel stores two reference indices at a time
-  if (!d_out_ref || ((uintptr_t)d_out_ref & 1)) return fail(ctx, HMME_ERR_ARG, "hmme_select_refs_device: null or misaligned reference buffer (2 bytes)");
-  SelectLaunch L;
-  const int rc = select_begin(ctx, "hmme_select_refs_device", width, height, n_pics, n_refs, ref_cost, fp, sel, d_mv, d_cost, d_pred_q, d_out_field, d_out_slot, d_out_cost, &L);
-  if (rc || L.count == 0) return rc;
-  hmme::MeRefCost price = {};
-  for (int r = 0; ref_cost && r < n_refs; ++r) price.c[r] = ref_cost[r];
-  hipLaunchKernelGGL(hmme::me_select_refs_kernel, L.grid, dim3(256), 0, (hipStream_t)stream, (const uint32_t*)d_mv, (const uint32_t*)d_cost, (const int16_t*)d_pred_q,
-                     (uint32_t*)d_out_field, (uint8_t*)d_out_ref, (uint16_t*)d_out_slot, (uint32_t*)d_out_cost, L.a, price, n_refs, width, height, L.n_ctu, L.first,
-                     L.count, ctx->lambda_q16);
-  HIP_TRY(ctx, hipGetLastError());
-  return HMME_OK;
+  return select_device(ctx, SelectCall("hmme_select_refs_device", kSelectRefs, width, height, n_pics, n_refs, fp, sel).with(ref_cost).with(kMv, d_mv).with(kCost, d_cost)
+                           .with(kPredQ, d_pred_q).with(kOutField, d_out_field).with(kOutRef, d_out_ref).with(kOutSlot, d_out_slot).with(kOutCost, d_out_cost),
+                       (hipStream_t)stream);
 }
 
 int hmme_select_refs_frame(hmme_ctx* ctx, int width, int height, int n_refs, const hmme_frame_params* fp, const hmme_select_params* sel,
                            const uint32_t* ref_cost, const int16_t* mv, const uint32_t* cost, const int16_t* pred_q, int16_t* out_field, uint8_t* out_ref,
                            uint16_t* out_slot, uint32_t* out_cost) {
-  if (!ctx) return HMME_ERR_ARG;
-  if (!out_ref) return fail(ctx, HMME_ERR_ARG, "hmme_select_refs_frame: null reference array");
-  return select_staged(ctx, "hmme_select_refs_frame", width, height, fp, sel, n_refs, ref_cost, mv, cost, pred_q, out_field, out_ref, out_slot, out_cost,
-                       [&](void* d_mv, void* d_cost, void* d_pred_q, void*, void* d_field, void* d_ref, void* d_slot, void* d_ccost, hipStream_t s) {
-                         return hmme_select_refs_device(ctx, width, height, 1, n_refs, fp, sel, ref_cost, d_mv, d_cost, d_pred_q, d_field, d_ref, d_slot, d_ccost, s);
-                       });
+  return select_host(ctx, SelectCall("hmme_select_refs_frame", kSelectRefs, width, height, 1, n_refs, fp, sel).with(ref_cost).with(kMv, mv).with(kCost, cost)
+                         .with(kPredQ, pred_q).with(kOutField, out_field).with(kOutRef, out_ref).with(kOutSlot, out_slot).with(kOutCost, out_cost));
 }
 
 namespace {
@@ -3126,27 +3225,6 @@ int hmme_predict_refs_w_frame(hmme_ctx* ctx, const hmme_plane* const* refs, int 
 }
 
 // ---- L0, L1 or bi per PU: the decision over the four table sets of a B picture, and the prediction that follows it ---------------------------
-namespace {
-constexpr int kMaxDirPics = 4;
-int select_dirs_eval(const hmme_select_params* sel, int n_pics, const hmme_dir_params* dirs, char* msg, size_t cap) {
-  const int bad = select_eval(sel, msg, cap);
-  if (bad) return bad;
-  if (sel->mv_per_ctu != 64 || sel->mv_unit != 0 || sel->price_mv != 0) {
-    snprintf(msg, cap, "mv_per_ctu %d, mv_unit %d, price_mv %d: the direction is decided on quarter-pel refinement tables, one MV per 8x8 block (64, 0, 0)",
-             sel->mv_per_ctu, sel->mv_unit, sel->price_mv);
-    return HMME_ERR_ARG;
-  }
-  if (n_pics < 1 || n_pics > kMaxDirPics) { snprintf(msg, cap, "%d pictures outside 1..%d", n_pics, kMaxDirPics); return HMME_ERR_ARG; }
-  if (!dirs) { snprintf(msg, cap, "null direction parameters"); return HMME_ERR_ARG; }
-  for (int p = 0; p < n_pics; ++p) {
-    const uint32_t v[5] = {dirs[p].dir_bits[0], dirs[p].dir_bits[1], dirs[p].dir_bits[2], dirs[p].list_bits[0], dirs[p].list_bits[1]};
-    for (int k = 0; k < 5; ++k)
-      if (v[k] > 4096) { snprintf(msg, cap, "picture %d: %s[%d] = %u above 4096", p, k < 3 ? "dir_bits" : "list_bits", k < 3 ? k : k - 3, v[k]); return HMME_ERR_ARG; }
-  }
-  return HMME_OK;
-}
-}  // namespace
-
 int hmme_select_dirs_check(const hmme_select_params* sel, int n_pics, const hmme_dir_params* dirs) {
   char msg[256];
   return select_dirs_eval(sel, n_pics, dirs, msg, sizeof msg);
@@ -3156,67 +3234,21 @@ int hmme_select_dirs_device(hmme_ctx* ctx, int width, int height, int n_pics, co
                             const hmme_dir_params* dirs, const void* d_mv_uni, const void* d_cost_uni, const void* d_mv_bi, const void* d_cost_bi,
                             const void* d_uni_field, const void* d_pred_q, void* d_out_field, void* d_out_dir, void* d_out_slot, void* d_out_cost,
                             void* stream) {
-  if (!ctx) return HMME_ERR_ARG;
-  const char* who = "hmme_select_dirs_device";
-  char msg[256];
-  const int bad = select_dirs_eval(sel, n_pics, dirs, msg, sizeof msg);
-  if (bad) return fail(ctx, bad, "%s: %s", who, msg);
-  if (!d_mv_bi || !d_cost_bi || !d_uni_field || !d_out_dir) return fail(ctx, HMME_ERR_ARG, "%s: null bi table, input field or direction buffer", who);
-  if (((uintptr_t)d_mv_bi & 3) || ((uintptr_t)d_cost_bi & 3) || ((uintptr_t)d_uni_field & 3) || ((uintptr_t)d_out_dir & 1))
-    return fail(ctx, HMME_ERR_ARG, "%s: misaligned buffer (tables, costs and the input field 4 bytes, directions 2)", who);
-  SelectLaunch L;   // the two lists of a picture are its two table sets
-  const int rc = select_begin(ctx, who, width, height, n_pics, 2, nullptr, fp, sel, d_mv_uni, d_cost_uni, d_pred_q, d_out_field, d_out_slot, d_out_cost, &L);
-  if (rc || L.count == 0) return rc;
-  hmme::MeDirParams bits = {};
-  for (int p = 0; p < n_pics; ++p) bits.p[p] = {{dirs[p].dir_bits[0], dirs[p].dir_bits[1], dirs[p].dir_bits[2]}, {dirs[p].list_bits[0], dirs[p].list_bits[1]}};
-  hipLaunchKernelGGL(hmme::me_select_dirs_kernel, L.grid, dim3(256), 0, (hipStream_t)stream, (const uint32_t*)d_mv_uni, (const uint32_t*)d_cost_uni,
-                     (const uint32_t*)d_mv_bi, (const uint32_t*)d_cost_bi, (const uint32_t*)d_uni_field, (const int16_t*)d_pred_q, (uint32_t*)d_out_field,
-                     (uint8_t*)d_out_dir, (uint16_t*)d_out_slot, (uint32_t*)d_out_cost, L.a, bits, width, height, L.n_ctu, L.first, L.count, ctx->lambda_q16);
-  HIP_TRY(ctx, hipGetLastError());
-  return HMME_OK;
+  return select_device(ctx, SelectCall("hmme_select_dirs_device", kSelectDirs, width, height, n_pics, 1, fp, sel).with(dirs).with(kMv, d_mv_uni).with(kCost, d_cost_uni)
+                           .with(kMvBi, d_mv_bi).with(kCostBi, d_cost_bi).with(kUniField, d_uni_field).with(kPredQ, d_pred_q).with(kOutField, d_out_field)
+                           .with(kOutDir, d_out_dir).with(kOutSlot, d_out_slot).with(kOutCost, d_out_cost), (hipStream_t)stream);
 }
 
 int hmme_select_dirs_frame(hmme_ctx* ctx, int width, int height, const hmme_frame_params* fp, const hmme_select_params* sel,
                            const hmme_dir_params* dir, const int16_t* mv_uni, const uint32_t* cost_uni, const int16_t* mv_bi, const uint32_t* cost_bi,
                            const int16_t* uni_field, const int16_t* pred_q, int16_t* out_field, uint8_t* out_dir, uint16_t* out_slot,
                            uint32_t* out_cost) {
-  if (!ctx) return HMME_ERR_ARG;
-  const char* who = "hmme_select_dirs_frame";
-  char msg[256];
-  const int bad = select_dirs_eval(sel, 1, dir, msg, sizeof msg);   // before anything is staged
-  if (bad) return fail(ctx, bad, "%s: %s", who, msg);
-  if (!mv_bi || !cost_bi || !uni_field || !out_dir) return fail(ctx, HMME_ERR_ARG, "%s: null bi table, input field or direction array", who);
-  const SelectStagedBi bi = {mv_bi, cost_bi, uni_field};
-  return select_staged(ctx, who, width, height, fp, sel, 2, nullptr, mv_uni, cost_uni, pred_q, out_field, out_dir, out_slot, out_cost,
-                       [&](void* d_mv, void* d_cost, void* d_pred_q, void* d_in_field, void* d_field, void* d_dir, void* d_slot, void* d_ccost, hipStream_t s) {
-                         const size_t tab = (size_t)2 * (fp->ctu_count < 0 ? hmme_num_ctus(width, height) - fp->ctu_first : fp->ctu_count) * HMME_NUM_CTU_PARTS * 4;
-                         return hmme_select_dirs_device(ctx, width, height, 1, fp, sel, dir, d_mv, d_cost, (uint8_t*)d_mv + tab, (uint8_t*)d_cost + tab, d_in_field,
-                                                        d_pred_q, d_field, d_dir, d_slot, d_ccost, s);
-                       }, &bi);
+  return select_host(ctx, SelectCall("hmme_select_dirs_frame", kSelectDirs, width, height, 1, 1, fp, sel).with(dir).with(kMv, mv_uni).with(kCost, cost_uni)
+                         .with(kMvBi, mv_bi).with(kCostBi, cost_bi).with(kUniField, uni_field).with(kPredQ, pred_q).with(kOutField, out_field)
+                         .with(kOutDir, out_dir).with(kOutSlot, out_slot).with(kOutCost, out_cost));
 }
 
 // ---- L0, L1 or bi and the reference index per list, per PU: the decision over the table sets of a B picture with several references -----------
-namespace {
-int select_dirs_refs_eval(const hmme_select_params* sel, int n_pics, int n_refs_max, const hmme_dir_refs_params* dirs, char* msg, size_t cap) {
-  const hmme_dir_params none[kMaxDirPics] = {};   // what hmme_select_dirs_check refuses of sel, n_pics and a null dirs
-  const int bad = select_dirs_eval(sel, n_pics, dirs ? none : nullptr, msg, cap);
-  if (bad) return bad;
-  if (n_refs_max < 1 || n_refs_max > hmme::kMaxDirRefs) { snprintf(msg, cap, "%d table sets per list outside 1..%d", n_refs_max, hmme::kMaxDirRefs); return HMME_ERR_ARG; }
-  for (int p = 0; p < n_pics; ++p) {
-    const hmme_dir_refs_params& d = dirs[p];
-    for (int k = 0; k < 3; ++k)
-      if (d.dir_bits[k] > 4096) { snprintf(msg, cap, "picture %d: dir_bits[%d] = %u above 4096", p, k, d.dir_bits[k]); return HMME_ERR_ARG; }
-    for (int l = 0; l < 2; ++l) {
-      if (d.n_refs[l] < 1 || d.n_refs[l] > n_refs_max) { snprintf(msg, cap, "picture %d: %d references in list %d outside 1..%d", p, d.n_refs[l], l, n_refs_max); return HMME_ERR_ARG; }
-      for (int r = 0; r < hmme::kMaxDirRefs; ++r)
-        if (d.ref_bits[l][r] > 4096) { snprintf(msg, cap, "picture %d: ref_bits[%d][%d] = %u above 4096", p, l, r, d.ref_bits[l][r]); return HMME_ERR_ARG; }
-    }
-    if (d.l1_valid_mask >> d.n_refs[1]) { snprintf(msg, cap, "picture %d: l1_valid_mask 0x%x names references at or above %d", p, d.l1_valid_mask, d.n_refs[1]); return HMME_ERR_ARG; }
-  }
-  return HMME_OK;
-}
-}  // namespace
-
 int hmme_select_dirs_refs_check(const hmme_select_params* sel, int n_pics, int n_refs_max, const hmme_dir_refs_params* dirs) {
   char msg[256];
   return select_dirs_refs_eval(sel, n_pics, n_refs_max, dirs, msg, sizeof msg);
@@ -3226,66 +3258,19 @@ int hmme_select_dirs_refs_device(hmme_ctx* ctx, int width, int height, int n_pic
                                  const hmme_dir_refs_params* dirs, const void* d_mv_uni, const void* d_cost_uni, const void* d_mv_bi, const void* d_cost_bi,
                                  const void* d_uni_field, const void* d_uni_ref, const void* d_pred_q, void* d_out_field, void* d_out_ref, void* d_out_dir,
                                  void* d_out_slot, void* d_out_cost, void* stream) {
-  if (!ctx) return HMME_ERR_ARG;
-  const char* who = "hmme_select_dirs_refs_device";
-  char msg[256];
-  const int bad = select_dirs_refs_eval(sel, n_pics, n_refs_max, dirs, msg, sizeof msg);
-  if (bad) return fail(ctx, bad, "%s: %s", who, msg);
-  if (!d_mv_bi || !d_cost_bi || !d_uni_field || !d_uni_ref || !d_out_ref || !d_out_dir)
-    return fail(ctx, HMME_ERR_ARG, "%s: null bi table, input field, or reference / direction buffer", who);
-  if (((uintptr_t)d_mv_bi & 3) || ((uintptr_t)d_cost_bi & 3) || ((uintptr_t)d_uni_field & 3))
-    return fail(ctx, HMME_ERR_ARG, "%s: misaligned buffer (tables, costs and the input field 4 bytes)", who);
-  SelectLaunch L;   // (the shared checks count table sets: a picture's two lists)
-  const int rc = select_begin(ctx, who, width, height, n_pics, 2, nullptr, fp, sel, d_mv_uni, d_cost_uni, d_pred_q, d_out_field, d_out_slot, d_out_cost, &L);
-  if (rc || L.count == 0) return rc;
-  hmme::MeDirRefsParams bits = {};
-  for (int p = 0; p < n_pics; ++p) {
-    hmme::MeDirRefsBits& b = bits.p[p];
-    for (int k = 0; k < 3; ++k) b.dir_bits[k] = dirs[p].dir_bits[k];
-    for (int l = 0; l < 2; ++l) {
-      b.n_refs[l] = dirs[p].n_refs[l];
-      for (int r = 0; r < hmme::kMaxDirRefs; ++r) b.ref_bits[l][r] = dirs[p].ref_bits[l][r];
-    }
-    b.l1_valid_mask = dirs[p].l1_valid_mask;
-  }
-  hipLaunchKernelGGL(hmme::me_select_dirs_refs_kernel, L.grid, dim3(256), 0, (hipStream_t)stream, (const uint32_t*)d_mv_uni, (const uint32_t*)d_cost_uni,
-                     (const uint32_t*)d_mv_bi, (const uint32_t*)d_cost_bi, (const uint32_t*)d_uni_field, (const uint8_t*)d_uni_ref, (const int16_t*)d_pred_q,
-                     (uint32_t*)d_out_field, (uint8_t*)d_out_ref, (uint8_t*)d_out_dir, (uint16_t*)d_out_slot, (uint32_t*)d_out_cost, L.a, bits, n_refs_max, width, height,
-                     L.n_ctu, L.first, L.count, ctx->lambda_q16);
-  HIP_TRY(ctx, hipGetLastError());
-  return HMME_OK;
+  return select_device(ctx, SelectCall("hmme_select_dirs_refs_device", kSelectDirsRefs, width, height, n_pics, n_refs_max, fp, sel).with(dirs).with(kMv, d_mv_uni)
+                           .with(kCost, d_cost_uni).with(kMvBi, d_mv_bi).with(kCostBi, d_cost_bi).with(kUniField, d_uni_field).with(kUniRef, d_uni_ref)
+                           .with(kPredQ, d_pred_q).with(kOutField, d_out_field).with(kOutRef, d_out_ref).with(kOutDir, d_out_dir).with(kOutSlot, d_out_slot)
+                           .with(kOutCost, d_out_cost), (hipStream_t)stream);
 }
 
 int hmme_select_dirs_refs_frame(hmme_ctx* ctx, int width, int height, int n_refs_max, const hmme_frame_params* fp, const hmme_select_params* sel,
                                 const hmme_dir_refs_params* dir, const int16_t* mv_uni, const uint32_t* cost_uni, const int16_t* mv_bi, const uint32_t* cost_bi,
                                 const int16_t* uni_field, const uint8_t* uni_ref, const int16_t* pred_q, int16_t* out_field, uint8_t* out_ref, uint8_t* out_dir,
                                 uint16_t* out_slot, uint32_t* out_cost) {
-  if (!ctx) return HMME_ERR_ARG;
-  const char* who = "hmme_select_dirs_refs_frame";
-  char msg[256];
-  const int bad = select_dirs_refs_eval(sel, 1, n_refs_max, dir, msg, sizeof msg);   // before anything is staged
-  if (bad) return fail(ctx, bad, "%s: %s", who, msg);
-  if (!fp || width < 1 || height < 1 || !mv_uni || !cost_uni || !mv_bi || !cost_bi || !uni_field || !uni_ref || !out_field || !out_ref || !out_dir)
-    return fail(ctx, HMME_ERR_ARG, "%s: null argument, or a %d x %d picture", who, width, height);
-  const size_t n_ctu = hmme_num_ctus(width, height);
-  int first, count;
-  int rc = ctu_range(ctx, fp, (int)n_ctu, &first, &count);
-  if (rc || count == 0) return rc;
-  const size_t sets = (size_t)2 * n_refs_max, tab = sets * count * HMME_NUM_CTU_PARTS * 4;
-  Stage st(ctx);
-  const int i_mu = st.in(mv_uni, tab), i_cu = st.in(cost_uni, tab), i_mb = st.in(mv_bi, tab), i_cb = st.in(cost_bi, tab);
-  const int i_pred = st.in(pred_q, sets * n_ctu * 4), i_field = st.in(uni_field, 2 * n_ctu * 64 * 4), i_ref = st.in(uni_ref, 2 * n_ctu * 64);
-  // only the CTUs of the range come back: the caller's entries outside it keep their values
-  const auto out = [&](void* host, size_t ctu_bytes, size_t parts) { return st.out(host, n_ctu * ctu_bytes, first * ctu_bytes, count * ctu_bytes, parts); };
-  const int o_field = out(out_field, 64 * 4, 2), o_ref = out(out_ref, 64, 2), o_dir = out(out_dir, 64, 1), o_slot = out(out_slot, 64 * 2, 1), o_cost = out(out_cost, 4, 1);
-  rc = st.begin();
-  if (rc == HMME_OK) {
-    rc = hmme_select_dirs_refs_device(ctx, width, height, 1, n_refs_max, fp, sel, dir, st.at(i_mu), st.at(i_cu), st.at(i_mb), st.at(i_cb), st.at(i_field), st.at(i_ref),
-                                      st.at(i_pred), st.at(o_field), st.at(o_ref), st.at(o_dir), st.at(o_slot), st.at(o_cost), ctx->stream);
-    if (rc && ctx->err.compare(0, strlen("hmme_select_dirs_refs_device"), "hmme_select_dirs_refs_device") == 0)
-      ctx->err.replace(0, strlen("hmme_select_dirs_refs_device"), who);   // the refusal names the entry the caller made
-  }
-  return rc ? rc : st.end();
+  return select_host(ctx, SelectCall("hmme_select_dirs_refs_frame", kSelectDirsRefs, width, height, 1, n_refs_max, fp, sel).with(dir).with(kMv, mv_uni)
+                         .with(kCost, cost_uni).with(kMvBi, mv_bi).with(kCostBi, cost_bi).with(kUniField, uni_field).with(kUniRef, uni_ref).with(kPredQ, pred_q)
+                         .with(kOutField, out_field).with(kOutRef, out_ref).with(kOutDir, out_dir).with(kOutSlot, out_slot).with(kOutCost, out_cost));
 }
 
 namespace {

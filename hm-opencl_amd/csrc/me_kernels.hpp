@@ -2549,6 +2549,23 @@ __device__ __forceinline__ uint64_t me_shfl_xor_u64(uint64_t v, int mask) {
   const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, mask), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), mask);
   return (uint64_t)hi << 32 | lo;
 }
+// The prices the select kernels put on an MV dword (x in the low half), each defined here once.
+// HM's MV cost of a table entry, for the callers that set price_mv (mv_unit: the table holds integer pels)
+__device__ __forceinline__ uint32_t me_select_mv_price(const MeSelect& a, uint32_t lambda_q16, uint32_t m, int pred_x, int pred_y) {
+  const int vx = (int16_t)(m & 0xffffu), vy = (int16_t)(m >> 16);
+  return a.mv_unit ? me_mv_cost(lambda_q16, vx, vy, pred_x, pred_y) : me_mv_cost_q(lambda_q16, vx, vy, pred_x, pred_y);
+}
+// HM's getBits at cost scale 0 of a quarter-pel MV against its predictor
+__device__ __forceinline__ uint32_t me_select_mv_bits(uint32_t m, int pred_x, int pred_y) {
+  return me_component_bits((int16_t)(m & 0xffffu) - pred_x) + me_component_bits((int16_t)(m >> 16) - pred_y);
+}
+// TComRdCost::getCost: the product wraps in 32 bits
+__device__ __forceinline__ uint64_t me_select_get_cost(uint32_t lambda_q16, uint32_t bits) { return (lambda_q16 * bits) >> 16; }
+// a refinement table's cost with the MV cost of `bits` taken out again, clamped at 0: the distortion
+__device__ __forceinline__ uint64_t me_select_dist(uint32_t lambda_q16, uint32_t cost, uint32_t bits) {
+  const uint64_t g = me_select_get_cost(lambda_q16, bits);
+  return cost > g ? cost - g : 0;
+}
 
 // what the decision carries for one lane (= one 8x8 block): the resolved cost of the lane's ancestor CU at the depth handled last (the same
 // value in every lane of that CU) and the shallowest ancestor that stayed a leaf so far
@@ -2569,11 +2586,7 @@ __device__ __forceinline__ void me_select_level(const MeSelect& a, const CostT* 
   const int cx = bx >> (3 - D), cy = by >> (3 - D), x0 = ctu_x + cx * s, y0 = ctu_y + cy * s;
   auto pu = [&](int slot) -> uint64_t {   // slot cost (+ HM's MV cost) + pu_cost
     uint64_t c = (uint64_t)s_cost[slot] + a.pu_cost;
-    if (a.price_mv) {
-      const uint32_t m = s_mv[slot];
-      const int vx = (int16_t)(m & 0xffffu), vy = (int16_t)(m >> 16);
-      c += a.mv_unit ? me_mv_cost(lambda_q16, vx, vy, pred_x, pred_y) : me_mv_cost_q(lambda_q16, vx, vy, pred_x, pred_y);
-    }
+    if (a.price_mv) c += me_select_mv_price(a, lambda_q16, s_mv[slot], pred_x, pred_y);
     return c;
   };
   uint64_t own = a.cu_cost + pu(me_slot_of<D>(0, 0, cx, cy));   // bit 0 of part_mask is always set
@@ -2598,57 +2611,94 @@ __device__ __forceinline__ void me_select_level(const MeSelect& a, const CostT* 
   else st.resolved = children;
 }
 
-// The decision over a CTU's slots in LDS and the stores that follow it: what both select kernels end in, one wave per CTU, lane = 8x8 block
-// in RASTER order inside the CTU.  o = the CTU's index in the outputs.  REFS: the slots carry a reference index (s_ref) that leaves
-// beside the field (out_ref) -- me_select_refs_kernel; without it both pointers are null and never looked at.
-// DIRS (me_select_dirs_kernel; one MV per 8x8 block only): s_ref holds direction | searched list << 2 per slot, out_ref takes the direction,
-// and the field has two lists list_stride dwords apart: the winner's MV in its list; in the other list (0,0) under a direction-1 / -2
-// slot and, under a direction-3 slot, the block's own entry of uni_field (laid out like out_field).  Without DIRS neither is looked at.
-// LREFS (me_select_dirs_refs_kernel; with DIRS): a reference index per list leaves beside the direction, laid out like the field with bytes
-// for dwords (out_lref, two lists list_stride bytes apart).  s_lref holds per slot the winner's index in list 0 and, kParts + 3 bytes on, in
-// list 1: the index travels with the MV -- the winner's in its list, 0xFF in the other under a direction-1 / -2 slot, the block's own entry
-// of uni_ref (laid out like out_lref) under a direction-3 slot.  Without LREFS none of the three is looked at.
-template <bool REFS, typename CostT, bool DIRS = false, bool LREFS = false>
-__device__ __forceinline__ void me_select_decide_store(const MeSelect& a, const CostT* s_cost, const uint32_t* s_mv, const uint8_t* s_ref, uint32_t lambda_q16,
-                                                       int pred_x, int pred_y, int lane, int ctu_x, int ctu_y, long o, int pic_w, int pic_h,
-                                                       uint32_t* out_field, uint8_t* out_ref, uint16_t* out_slot, uint32_t* out_cost,
-                                                       const uint32_t* uni_field = nullptr, long list_stride = 0, const uint8_t* s_lref = nullptr,
-                                                       const uint8_t* uni_ref = nullptr, uint8_t* out_lref = nullptr) {
-  const int bx = lane & 7, by = lane >> 3;
+// What the four select kernels share.  Their geometry: one wave per CTU, four CTUs per workgroup, blockIdx.y = picture (pair); lane = 8x8
+// block in RASTER order inside the CTU -- the layout of the field, so that every store of the wave is one contiguous run.  Each kernel is
+// me_select_wave, its own merge of the tables into the CTU's slots in LDS, a barrier, and me_select_decide_store.
+struct MeSelectWave {
+  int wave, lane;    // of the workgroup
+  int c, ctu, pic;   // the CTU's index in the tables (which begin at ctu_first) and in the picture; the picture (pair) of the launch
+  bool live;         // wave-uniform: the CTU lies inside the range
+};
+__device__ __forceinline__ MeSelectWave me_select_wave(int ctu_first, int ctu_count) {
+  MeSelectWave w;
+  w.wave = threadIdx.x >> 6; w.lane = threadIdx.x & 63;
+  w.c = blockIdx.x * 4 + w.wave; w.ctu = ctu_first + w.c; w.pic = blockIdx.y;
+  w.live = w.c < ctu_count;
+  return w;
+}
+
+// what is decided: one table set per picture pair (me_select_kernel), the reference per PU (me_select_refs_kernel), L0 / L1 / bi per PU
+// (me_select_dirs_kernel) and that with a reference index per list (me_select_dirs_refs_kernel)
+enum MeSelectMode { kSelTable, kSelRefs, kSelDirs, kSelDirsRefs };
+
+// what a kernel's merge leaves in LDS per slot of the wave's CTU.  A member no mode of the kernel uses is null and never looked at
+template <typename CostT>
+struct MeSelectSlots {
+  CostT* cost;     // kSelTable: the table's cost (uint32_t).  Every other mode: the winner's cost in 64 bits, priced -- the MV cost is inside
+  uint32_t* mv;    // the table's / the winner's MV dword
+  uint8_t* ref;    // kSelRefs: the winner's reference index
+  uint8_t* dir;    // kSelDirs, kSelDirsRefs: the winner's direction (1, 2, 3) | the list the bi pass searched << 2
+  uint8_t* lref;   // kSelDirsRefs: the winner's reference index in list 0 and, kParts + 3 bytes on, in list 1; 0xFF in a list the winner does not use
+};
+// where the outputs go, and the inputs that are copied into them.  Per picture of the launch a field is [n_ctu][per] dwords, or with two
+// lists [2][n_ctu][64]; references are laid out like the field with bytes for dwords; null where the mode (or the caller: slot, cost) has none
+struct MeSelectOut {
+  uint32_t* field;             // the motion field; kSelDirs, kSelDirsRefs: two lists -- the winner's MV in its list, in the other list (0,0)
+                               // under a direction-1 / -2 slot and the block's own entry of uni_field under a direction-3 slot
+  uint16_t* slot;              // the covering slot per block, 0xFFFF where no CU covers it
+  uint32_t* cost;              // the CTU's cost, saturated
+  uint8_t* ref;                // kSelRefs: the reference index per block; kSelDirsRefs: per list, travelling with the MV (else 0xFF / uni_ref's)
+  uint8_t* dir;                // kSelDirs, kSelDirsRefs: the direction per block, 0xFF where no CU covers it
+  const uint32_t* uni_field;   // kSelDirs, kSelDirsRefs: the lists' fields of the uni-directional decisions, laid out like field
+  const uint8_t* uni_ref;      // kSelDirsRefs: their reference indices, laid out like ref
+};
+
+// The decision over the CTU's slots in LDS and the stores that follow it: what every select kernel ends in.  Outside kSelTable the MV cost
+// is inside the merged cost already -- against each reference's own predictor -- and is not priced a second time.
+template <MeSelectMode MODE, typename CostT>
+__device__ __forceinline__ void me_select_decide_store(const MeSelect& params, const MeSelectSlots<CostT>& s, const MeSelectOut& out, const MeSelectWave& w,
+                                                       uint32_t lambda_q16, int pred_x, int pred_y, int pic_w, int pic_h, int n_ctu) {
+  constexpr bool REFS = MODE == kSelRefs, DIRS = MODE == kSelDirs || MODE == kSelDirsRefs, LREFS = MODE == kSelDirsRefs;
+  MeSelect a = params;
+  if (MODE != kSelTable) a.price_mv = 0;
+  const int lane = w.lane, bx = lane & 7, by = lane >> 3, ctus_x = (pic_w + 63) >> 6;
+  const int ctu_x = (w.ctu % ctus_x) * 64, ctu_y = (w.ctu / ctus_x) * 64;
+  const long o = (long)w.pic * n_ctu + w.ctu;   // the CTU's index in the outputs
   MeSelectState st = {0, -1, 0};
-  me_select_level<3>(a, s_cost, s_mv, lambda_q16, pred_x, pred_y, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
-  me_select_level<2>(a, s_cost, s_mv, lambda_q16, pred_x, pred_y, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
-  me_select_level<1>(a, s_cost, s_mv, lambda_q16, pred_x, pred_y, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
-  me_select_level<0>(a, s_cost, s_mv, lambda_q16, pred_x, pred_y, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
-  if (lane == 0 && out_cost) out_cost[o] = st.resolved > 0xffffffffull ? 0xffffffffu : (uint32_t)st.resolved;
+  me_select_level<3>(a, s.cost, s.mv, lambda_q16, pred_x, pred_y, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
+  me_select_level<2>(a, s.cost, s.mv, lambda_q16, pred_x, pred_y, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
+  me_select_level<1>(a, s.cost, s.mv, lambda_q16, pred_x, pred_y, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
+  me_select_level<0>(a, s.cost, s.mv, lambda_q16, pred_x, pred_y, bx, by, ctu_x, ctu_y, pic_w, pic_h, st);
+  if (lane == 0 && out.cost) out.cost[o] = st.resolved > 0xffffffffull ? 0xffffffffu : (uint32_t)st.resolved;
   // integer-pel MVs leave as quarter pels: both halves of the dword << 2, the two bits that cross into the upper half masked off
   auto field_mv = [&](int slot) -> uint32_t {
-    const uint32_t m = s_mv[slot];
+    const uint32_t m = s.mv[slot];
     return a.mv_unit ? (m << 2) & 0xfffcfffcu : m;
   };
   if (a.per == 64) {
     const int slot = st.leaf_depth < 0 ? 0xffff : me_select_pu_slot_at(st.leaf_depth, st.leaf_ps, bx * 8, by * 8);
-    if constexpr (DIRS) {
-      const int d = slot == 0xffff ? 0 : (int)s_ref[slot];   // direction | searched list << 2
+    if constexpr (DIRS) {   // (one MV per 8x8 block only)
+      const long lists = (long)n_ctu * 64, e = 2 * w.pic * lists + w.ctu * 64 + lane;   // the block in list 0 of its picture; list 1: `lists` further
+      const int d = slot == 0xffff ? 0 : (int)s.dir[slot];
       const int dir = d & 3, bl = d >> 2;
       uint32_t f[2] = {0u, 0u};
-      if (dir == 3) { f[bl] = s_mv[slot]; f[1 - bl] = uni_field[o * 64 + lane + (1 - bl) * list_stride]; }
-      else if (dir) f[dir - 1] = s_mv[slot];
-      out_field[o * 64 + lane] = f[0];
-      out_field[o * 64 + lane + list_stride] = f[1];
-      out_ref[o * 64 + lane] = dir ? (uint8_t)dir : (uint8_t)0xff;
+      if (dir == 3) { f[bl] = s.mv[slot]; f[1 - bl] = out.uni_field[e + (1 - bl) * lists]; }
+      else if (dir) f[dir - 1] = s.mv[slot];
+      out.field[e] = f[0];
+      out.field[e + lists] = f[1];
+      out.dir[o * 64 + lane] = dir ? (uint8_t)dir : (uint8_t)0xff;
       if constexpr (LREFS) {
         uint8_t rl[2] = {0xff, 0xff};
-        if (dir == 3) { rl[bl] = s_lref[bl * (kParts + 3) + slot]; rl[1 - bl] = uni_ref[o * 64 + lane + (1 - bl) * list_stride]; }
-        else if (dir) rl[dir - 1] = s_lref[(dir - 1) * (kParts + 3) + slot];
-        out_lref[o * 64 + lane] = rl[0];
-        out_lref[o * 64 + lane + list_stride] = rl[1];
+        if (dir == 3) { rl[bl] = s.lref[bl * (kParts + 3) + slot]; rl[1 - bl] = out.uni_ref[e + (1 - bl) * lists]; }
+        else if (dir) rl[dir - 1] = s.lref[(dir - 1) * (kParts + 3) + slot];
+        out.ref[e] = rl[0];
+        out.ref[e + lists] = rl[1];
       }
     } else {
-      out_field[o * 64 + lane] = slot == 0xffff ? 0u : field_mv(slot);
-      if constexpr (REFS) out_ref[o * 64 + lane] = slot == 0xffff ? (uint8_t)0xff : s_ref[slot];
+      out.field[o * 64 + lane] = slot == 0xffff ? 0u : field_mv(slot);
+      if constexpr (REFS) out.ref[o * 64 + lane] = slot == 0xffff ? (uint8_t)0xff : s.ref[slot];
     }
-    if (out_slot) out_slot[o * 64 + lane] = (uint16_t)slot;
+    if (out.slot) out.slot[o * 64 + lane] = (uint16_t)slot;
   } else {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {   // the block's two rows of two 4x4 blocks
@@ -2658,63 +2708,55 @@ __device__ __forceinline__ void me_select_decide_store(const MeSelect& a, const 
       for (int i = 0; i < 2; ++i) {
         slot[i] = st.leaf_depth < 0 ? 0xffff : me_select_pu_slot_at(st.leaf_depth, st.leaf_ps, bx * 8 + 4 * i, by * 8 + 4 * j);
         mv[i] = slot[i] == 0xffff ? 0u : field_mv(slot[i]);
-        if constexpr (REFS) ref[i] = slot[i] == 0xffff ? 0xffu : (uint32_t)s_ref[slot[i]];
+        if constexpr (REFS) ref[i] = slot[i] == 0xffff ? 0xffu : (uint32_t)s.ref[slot[i]];
       }
       const long e = o * 256 + (2 * by + j) * 16 + 2 * bx;   // even: 8-byte (MVs) / 4-byte (slots) / 2-byte (references) aligned pairs
-      *(uint2*)(out_field + e) = make_uint2(mv[0], mv[1]);
-      if constexpr (REFS) *(uint16_t*)(out_ref + e) = (uint16_t)(ref[0] | ref[1] << 8);
-      if (out_slot) *(uint32_t*)(out_slot + e) = (uint32_t)slot[0] | (uint32_t)slot[1] << 16;
+      *(uint2*)(out.field + e) = make_uint2(mv[0], mv[1]);
+      if constexpr (REFS) *(uint16_t*)(out.ref + e) = (uint16_t)(ref[0] | ref[1] << 8);
+      if (out.slot) *(uint32_t*)(out.slot + e) = (uint32_t)slot[0] | (uint32_t)slot[1] << 16;
     }
   }
 }
 
-// One wave per CTU, four CTUs per workgroup; blockIdx.y = picture pair.  The CTU's 593 costs and MVs are loaded coalesced into LDS (4.7 KB
-// per CTU), lane = 8x8 block in RASTER order inside the CTU -- the layout of the field, so that every store of the wave is one contiguous
-// run (256 B of MVs with one MV per 8x8 block; rows of 64 B with four).  mv_tab: int16 [n_pairs][ctu_count][593][2] read as dwords;
-// cost_tab: uint32 [n_pairs][ctu_count][593]; pred_q: int16 [n_pairs][n_ctu][2] or null; out_field: int16 [n_pairs][n_ctu][per][2] written
-// as dwords; out_slot: uint16 [n_pairs][n_ctu][per] or null; out_cost: uint32 [n_pairs][n_ctu] or null.  Bandwidth-sized: nothing tuned
-// beyond coalesced accesses.
+// The merge: the CTU's 593 costs and MVs loaded coalesced into LDS (4.7 KB per CTU).  mv_tab: int16 [n_pairs][ctu_count][593][2] read as
+// dwords; cost_tab: uint32 [n_pairs][ctu_count][593]; pred_q: int16 [n_pairs][n_ctu][2] or null; out_field: int16 [n_pairs][n_ctu][per][2]
+// written as dwords (256 B of MVs per wave with one MV per 8x8 block; rows of 64 B with four); out_slot: uint16 [n_pairs][n_ctu][per] or
+// null; out_cost: uint32 [n_pairs][n_ctu] or null.  Bandwidth-sized: nothing tuned beyond coalesced accesses.
 __global__ void __launch_bounds__(256)
 me_select_kernel(const uint32_t* __restrict__ mv_tab, const uint32_t* __restrict__ cost_tab, const int16_t* __restrict__ pred_q,
                  uint32_t* __restrict__ out_field, uint16_t* __restrict__ out_slot, uint32_t* __restrict__ out_cost, MeSelect a, int pic_w, int pic_h,
                  int n_ctu, int ctu_first, int ctu_count, uint32_t lambda_q16) {
   __shared__ uint32_t s_cost[4][kParts + 3];
   __shared__ uint32_t s_mv[4][kParts + 3];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int c = blockIdx.x * 4 + wave, pair = blockIdx.y;
-  const bool live = c < ctu_count;   // wave-uniform
-  if (live) {
-    const long base = ((long)pair * ctu_count + c) * kParts;
-    for (int i = lane; i < kParts; i += 64) {
-      s_cost[wave][i] = cost_tab[base + i];
-      s_mv[wave][i] = mv_tab[base + i];
+  const MeSelectWave w = me_select_wave(ctu_first, ctu_count);
+  if (w.live) {
+    const long base = ((long)w.pic * ctu_count + w.c) * kParts;
+    for (int i = w.lane; i < kParts; i += 64) {
+      s_cost[w.wave][i] = cost_tab[base + i];
+      s_mv[w.wave][i] = mv_tab[base + i];
     }
   }
   __syncthreads();
-  if (!live) return;
-  const int ctu = ctu_first + c, ctus_x = (pic_w + 63) >> 6;
-  const int ctu_x = (ctu % ctus_x) * 64, ctu_y = (ctu / ctus_x) * 64;
-  const long o = (long)pair * n_ctu + ctu;
+  if (!w.live) return;
+  const long o = (long)w.pic * n_ctu + w.ctu;
   const int pred_x = pred_q ? pred_q[o * 2] : 0, pred_y = pred_q ? pred_q[o * 2 + 1] : 0;
-  me_select_decide_store<false>(a, s_cost[wave], s_mv[wave], nullptr, lambda_q16, pred_x, pred_y, lane, ctu_x, ctu_y, o, pic_w, pic_h, out_field, nullptr,
-                                out_slot, out_cost);
+  me_select_decide_store<kSelTable, uint32_t>(a, {s_cost[w.wave], s_mv[w.wave]}, {out_field, out_slot, out_cost}, w, lambda_q16, pred_x, pred_y, pic_w, pic_h,
+                                              n_ctu);
 }
 
 // ---- reference picture per PU (hmme_select_refs_device; the rule: include/hmme.h) --------------------------------------------------------
 // the caller's price of each reference index, as the kernel takes it
 struct MeRefCost { uint32_t c[kMaxRefs]; };
 
-// me_select_kernel with a reference dimension in front: one wave per CTU, four CTUs per workgroup; blockIdx.y = picture.  The tables are
-// those of one multi-reference launch -- mv_tab int16 [n_pics][n_refs][ctu_count][593][2] as dwords, cost_tab uint32 of the same shape,
-// pred_q int16 [n_pics][n_refs][n_ctu][2] or null.  A lane owns the slots lane, lane + 64, ... (ten, the last one in 17 lanes only) and
-// walks the references with coalesced loads straight from the tables, its slots' running best -- the priced cost in 64 bits, the MV
-// dword, the reference -- in registers: no LDS traffic, no atomic and no cross-lane step in the reference loop; the predictor and the
-// price of a reference are wave-uniform.  The comparison is strict in the order 0, 1, ...: the lowest index wins ties
-// (TEncSearch.cpp:3086).  Behind the last reference the merged slots go to LDS (7.6 KB per CTU with the costs in 64 bits: unsaturated)
-// and me_select_decide_store decides on them as in me_select_kernel, the MV cost -- already inside the merged cost, against each
-// reference's own predictor -- switched off.  out_ref: uint8 [n_pics][n_ctu][per], a wave's bytes one run of 64 with one MV per 8x8
-// block, pairs of them as one 16-bit store with four; 0xFF where no CU covers the block.  Bandwidth-sized like its sibling:
-// n_refs x 7.1 KB in per CTU, under 2 KB out.
+// me_select_kernel with a reference dimension in front.  The tables are those of one multi-reference launch -- mv_tab int16
+// [n_pics][n_refs][ctu_count][593][2] as dwords, cost_tab uint32 of the same shape, pred_q int16 [n_pics][n_refs][n_ctu][2] or null.  The
+// merge: a lane owns the slots lane, lane + 64, ... (ten, the last one in 17 lanes only) and walks the references with coalesced loads
+// straight from the tables, its slots' running best -- the priced cost in 64 bits, the MV dword, the reference -- in registers: no LDS
+// traffic, no atomic and no cross-lane step in the reference loop; the predictor and the price of a reference are wave-uniform.  The
+// comparison is strict in the order 0, 1, ...: the lowest index wins ties (TEncSearch.cpp:3086).  Behind the last reference the merged slots
+// go to LDS (7.6 KB per CTU with the costs in 64 bits: unsaturated).  out_ref: uint8 [n_pics][n_ctu][per], a wave's bytes one run of 64
+// with one MV per 8x8 block, pairs of them as one 16-bit store with four.  Bandwidth-sized like its sibling: n_refs x 7.1 KB in per CTU,
+// under 2 KB out.
 __global__ void __launch_bounds__(256)
 me_select_refs_kernel(const uint32_t* __restrict__ mv_tab, const uint32_t* __restrict__ cost_tab, const int16_t* __restrict__ pred_q,
                       uint32_t* __restrict__ out_field, uint8_t* __restrict__ out_ref, uint16_t* __restrict__ out_slot, uint32_t* __restrict__ out_cost,
@@ -2723,64 +2765,57 @@ me_select_refs_kernel(const uint32_t* __restrict__ mv_tab, const uint32_t* __res
   __shared__ uint64_t s_cost[4][kParts + 3];
   __shared__ uint32_t s_mv[4][kParts + 3];
   __shared__ uint8_t s_ref[4][kParts + 3];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int c = blockIdx.x * 4 + wave, pic = blockIdx.y;
-  const bool live = c < ctu_count;   // wave-uniform
-  const int ctu = ctu_first + c;
-  if (live) {
+  const MeSelectWave w = me_select_wave(ctu_first, ctu_count);
+  if (w.live) {
     uint64_t best[kOwn];
     uint32_t best_mv[kOwn];
     int best_ref[kOwn];
 #pragma unroll 1
     for (int r = 0; r < n_refs; ++r) {
-      const long set = (long)pic * n_refs + r, base = (set * ctu_count + c) * kParts, po = (set * n_ctu + ctu) * 2;
+      const long set = (long)w.pic * n_refs + r, base = (set * ctu_count + w.c) * kParts, po = (set * n_ctu + w.ctu) * 2;
       const int pred_x = pred_q ? pred_q[po] : 0, pred_y = pred_q ? pred_q[po + 1] : 0;
       const uint32_t rc = ref_cost.c[r];
 #pragma unroll
       for (int k = 0; k < kOwn; ++k) {
-        const int i = lane + 64 * k;
+        const int i = w.lane + 64 * k;
         if (i >= kParts) continue;
         const uint32_t m = mv_tab[base + i];
         uint64_t p = (uint64_t)cost_tab[base + i] + rc;
-        if (a.price_mv) {
-          const int vx = (int16_t)(m & 0xffffu), vy = (int16_t)(m >> 16);
-          p += a.mv_unit ? me_mv_cost(lambda_q16, vx, vy, pred_x, pred_y) : me_mv_cost_q(lambda_q16, vx, vy, pred_x, pred_y);
-        }
+        if (a.price_mv) p += me_select_mv_price(a, lambda_q16, m, pred_x, pred_y);
         if (r == 0 || p < best[k]) { best[k] = p; best_mv[k] = m; best_ref[k] = r; }   // strict: the lower index wins ties
       }
     }
 #pragma unroll
     for (int k = 0; k < kOwn; ++k) {
-      const int i = lane + 64 * k;
+      const int i = w.lane + 64 * k;
       if (i >= kParts) continue;
-      s_cost[wave][i] = best[k];
-      s_mv[wave][i] = best_mv[k];
-      s_ref[wave][i] = (uint8_t)best_ref[k];
+      s_cost[w.wave][i] = best[k];
+      s_mv[w.wave][i] = best_mv[k];
+      s_ref[w.wave][i] = (uint8_t)best_ref[k];
     }
   }
   __syncthreads();
-  if (!live) return;
-  const int ctus_x = (pic_w + 63) >> 6;
-  const int ctu_x = (ctu % ctus_x) * 64, ctu_y = (ctu / ctus_x) * 64;
-  MeSelect merged = a;
-  merged.price_mv = 0;   // priced above, per reference: not a second time
-  me_select_decide_store<true>(merged, s_cost[wave], s_mv[wave], s_ref[wave], lambda_q16, 0, 0, lane, ctu_x, ctu_y, (long)pic * n_ctu + ctu, pic_w, pic_h,
-                               out_field, out_ref, out_slot, out_cost);
+  if (!w.live) return;
+  me_select_decide_store<kSelRefs, uint64_t>(a, {s_cost[w.wave], s_mv[w.wave], s_ref[w.wave]}, {out_field, out_slot, out_cost, out_ref}, w, lambda_q16, 0, 0, pic_w,
+                                             pic_h, n_ctu);
 }
 
-// ---- L0, L1 or bi per PU (hmme_select_dirs_device; the rule: include/hmme.h) ---------------------------------------------------------------
-// hmme_dir_params of every picture of the launch, as the kernel takes them
+// ---- L0, L1 or bi per PU, with one reference per list (hmme_select_dirs_device) or several (hmme_select_dirs_refs_device; the rule of
+// each: include/hmme.h) ----------------------------------------------------------------------------------------------------------------------
+// hmme_dir_params / hmme_dir_refs_params of every picture of the launch, as the kernels take them
+constexpr int kMaxDirRefs = 8;
 struct MeDirBits { uint32_t dir_bits[3], list_bits[2]; };
 struct MeDirParams { MeDirBits p[4]; };
+struct MeDirRefsBits { uint32_t dir_bits[3]; int n_refs[2]; uint32_t ref_bits[2][kMaxDirRefs]; uint32_t l1_valid_mask; };
+struct MeDirRefsParams { MeDirRefsBits p[4]; };
 
-// me_select_refs_kernel's geometry -- one wave per CTU, four CTUs per workgroup, blockIdx.y = picture -- over FOUR table sets per picture:
-// uni / bi, each int16 [n_pics][2][ctu_count][593][2] as dwords with costs uint32 of that shape; pred_q int16 [n_pics][2][n_ctu][2] or null.
-// A lane owns the slots lane, lane + 64, ... and takes each through the four sets in registers: the MV bits of the four MVs against
-// their lists' predictors, the distortions with the MV cost taken out again (clamped at 0; the bi pass's halved: fWeight 0.5,
-// TEncSearch.cpp:3808), HM's bits put back in ONE getCost per candidate (32-bit wrap), every sum in 64 bits.  The bi candidate is list 0's
-// unless list 1's is strictly cheaper (:3183-3186, :3226); bi wins on <= against both lists, list 0 on <= against list 1 (:3291, :3314).
-// The winner's cost, its MV dword and direction | searched list << 2 go to LDS and me_select_decide_store<.., DIRS> decides on them
-// with the MV cost switched off.  uni_field / out_field: int16 [n_pics][2][n_ctu][64][2] as dwords; out_dir uint8 [n_pics][n_ctu][64].
+// One reference per list: FOUR table sets per picture -- uni / bi, each int16 [n_pics][2][ctu_count][593][2] as dwords with costs uint32 of
+// that shape; pred_q int16 [n_pics][2][n_ctu][2] or null.  The merge: a lane takes each of its slots (lane, lane + 64, ...) through the four
+// sets in registers, all eight loads up front: the distortions with the MV cost taken out again (the bi pass's halved: fWeight 0.5,
+// TEncSearch.cpp:3808), HM's bits put back in ONE getCost per candidate, every sum in 64 bits.  The bi candidate is list 0's unless list 1's
+// is strictly cheaper (:3183-3186, :3226); bi wins on <= against both lists, list 0 on <= against list 1 (:3291, :3314).  This is the
+// sibling's merge at one reference per list, written out: as one body with it, it measured 15 % slower.
+// uni_field / out_field: int16 [n_pics][2][n_ctu][64][2] as dwords; out_dir uint8 [n_pics][n_ctu][64].
 __global__ void __launch_bounds__(256)
 me_select_dirs_kernel(const uint32_t* __restrict__ mv_uni, const uint32_t* __restrict__ cost_uni, const uint32_t* __restrict__ mv_bi,
                       const uint32_t* __restrict__ cost_bi, const uint32_t* __restrict__ uni_field, const int16_t* __restrict__ pred_q,
@@ -2790,30 +2825,19 @@ me_select_dirs_kernel(const uint32_t* __restrict__ mv_uni, const uint32_t* __res
   __shared__ uint64_t s_cost[4][kParts + 3];
   __shared__ uint32_t s_mv[4][kParts + 3];
   __shared__ uint8_t s_dir[4][kParts + 3];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int c = blockIdx.x * 4 + wave, pic = blockIdx.y;
-  const bool live = c < ctu_count;   // wave-uniform
-  const int ctu = ctu_first + c;
-  if (live) {
-    const MeDirBits b = dirs.p[pic];
+  const MeSelectWave w = me_select_wave(ctu_first, ctu_count);
+  if (w.live) {
+    const MeDirBits b = dirs.p[w.pic];
     int px[2] = {0, 0}, py[2] = {0, 0};
     if (pred_q) {   // wave-uniform: the two lists' predictors of the CTU
-      const int16_t* pq = pred_q + ((long)pic * 2 * n_ctu + ctu) * 2;
+      const int16_t* pq = pred_q + ((long)w.pic * 2 * n_ctu + w.ctu) * 2;
       px[0] = pq[0]; py[0] = pq[1];
       px[1] = pq[2 * (long)n_ctu]; py[1] = pq[2 * (long)n_ctu + 1];
     }
-    const long base[2] = {((long)pic * 2 * ctu_count + c) * kParts, (((long)pic * 2 + 1) * ctu_count + c) * kParts};
-    auto mvb = [](uint32_t m, int pred_x, int pred_y) -> uint32_t {   // HM's getBits at cost scale 0
-      return me_component_bits((int16_t)(m & 0xffffu) - pred_x) + me_component_bits((int16_t)(m >> 16) - pred_y);
-    };
-    auto gc = [&](uint32_t n) -> uint64_t { return (lambda_q16 * n) >> 16; };   // TComRdCost::getCost: the product wraps in 32 bits
-    auto dist = [&](uint32_t cost, uint32_t bits) -> uint64_t {
-      const uint64_t g = gc(bits);
-      return cost > g ? cost - g : 0;
-    };
+    const long base[2] = {((long)w.pic * 2 * ctu_count + w.c) * kParts, (((long)w.pic * 2 + 1) * ctu_count + w.c) * kParts};
 #pragma unroll 1
     for (int k = 0; k < kOwn; ++k) {
-      const int i = lane + 64 * k;
+      const int i = w.lane + 64 * k;
       if (i >= kParts) continue;
       uint32_t mu[2], mb[2], bu[2], bb[2];
       uint64_t cu[2], cb[2];
@@ -2821,13 +2845,14 @@ me_select_dirs_kernel(const uint32_t* __restrict__ mv_uni, const uint32_t* __res
       for (int l = 0; l < 2; ++l) {
         mu[l] = mv_uni[base[l] + i];
         mb[l] = mv_bi[base[l] + i];
-        bu[l] = mvb(mu[l], px[l], py[l]);
-        bb[l] = mvb(mb[l], px[l], py[l]);
+        bu[l] = me_select_mv_bits(mu[l], px[l], py[l]);
+        bb[l] = me_select_mv_bits(mb[l], px[l], py[l]);
       }
 #pragma unroll
       for (int l = 0; l < 2; ++l) {
-        cu[l] = dist(cost_uni[base[l] + i], bu[l]) + gc(b.dir_bits[l] + b.list_bits[l] + bu[l]);
-        cb[l] = (dist(cost_bi[base[l] + i], bb[l]) >> 1) + gc(b.dir_bits[2] + b.list_bits[0] + b.list_bits[1] + bb[l] + bu[1 - l]);
+        cu[l] = me_select_dist(lambda_q16, cost_uni[base[l] + i], bu[l]) + me_select_get_cost(lambda_q16, b.dir_bits[l] + b.list_bits[l] + bu[l]);
+        cb[l] = (me_select_dist(lambda_q16, cost_bi[base[l] + i], bb[l]) >> 1) +
+                me_select_get_cost(lambda_q16, b.dir_bits[2] + b.list_bits[0] + b.list_bits[1] + bb[l] + bu[1 - l]);
       }
       const int bl = cb[1] < cb[0] ? 1 : 0;   // strict: list 0 is tried first
       const uint64_t cbi = cb[bl];
@@ -2837,38 +2862,26 @@ me_select_dirs_kernel(const uint32_t* __restrict__ mv_uni, const uint32_t* __res
       if (cbi <= cu[0] && cbi <= cu[1]) { best = cbi; m = mb[bl]; d = 3 | bl << 2; }
       else if (cu[0] <= cu[1]) { best = cu[0]; m = mu[0]; d = 1; }
       else { best = cu[1]; m = mu[1]; d = 2; }
-      s_cost[wave][i] = best;
-      s_mv[wave][i] = m;
-      s_dir[wave][i] = (uint8_t)d;
+      s_cost[w.wave][i] = best;
+      s_mv[w.wave][i] = m;
+      s_dir[w.wave][i] = (uint8_t)d;
     }
   }
   __syncthreads();
-  if (!live) return;
-  const int ctus_x = (pic_w + 63) >> 6;
-  const int ctu_x = (ctu % ctus_x) * 64, ctu_y = (ctu / ctus_x) * 64;
-  MeSelect merged = a;
-  merged.price_mv = 0;   // inside the merged cost already
-  const long lists = (long)n_ctu * 64, at = (long)pic * lists;   // the picture's two lists start at dword 2 * at; its CTU index is at / 64 + ctu
-  me_select_decide_store<true, uint64_t, true>(merged, s_cost[wave], s_mv[wave], s_dir[wave], lambda_q16, 0, 0, lane, ctu_x, ctu_y, (long)pic * n_ctu + ctu,
-                                               pic_w, pic_h, out_field + at, out_dir, out_slot, out_cost, uni_field + at, lists);
+  if (!w.live) return;
+  me_select_decide_store<kSelDirs, uint64_t>(a, {s_cost[w.wave], s_mv[w.wave], nullptr, s_dir[w.wave]}, {out_field, out_slot, out_cost, nullptr, out_dir, uni_field}, w,
+                                             lambda_q16, 0, 0, pic_w, pic_h, n_ctu);
 }
 
-// ---- L0, L1 or bi and the reference index per list, per PU (hmme_select_dirs_refs_device; the rule: include/hmme.h) -----------------------
-// hmme_dir_refs_params of every picture of the launch, as the kernel takes them
-constexpr int kMaxDirRefs = 8;
-struct MeDirRefsBits { uint32_t dir_bits[3]; int n_refs[2]; uint32_t ref_bits[2][kMaxDirRefs]; uint32_t l1_valid_mask; };
-struct MeDirRefsParams { MeDirRefsBits p[4]; };
-
-// me_select_dirs_kernel with a reference dimension behind the list: uni / bi tables int16 [n_pics][2][R][ctu_count][593][2] as dwords with
-// costs uint32 of that shape, pred_q int16 [n_pics][2][R][n_ctu][2] or null; list l uses its first n_refs[l] sets.  A lane owns the slots
-// lane, lane + 64, ... and walks each through the references of both lists in registers, twice: the uni pass keeps per list the first
-// strict minimum (:3086) with its MV, index and motion bits (ref_bits + MV bits, :3154-3155), list 1 also the minimum over the references
-// of l1_valid_mask -- its direction-2 candidate (:3096-3104, :3282-3285), absent with an empty mask; the bi pass prices every reference
-// against the OTHER list's motion bits (:3210-3219) and keeps the first strict minimum (:3226).  Predictors and bit counts are wave-uniform;
-// no LDS traffic, no atomic and no cross-lane step in the reference loops.  The winner's cost (64 bits), MV dword, direction | searched
-// list << 2 and the two reference indices go to LDS (35.8 KB per workgroup) and me_select_decide_store<.., DIRS, LREFS> decides on them
-// with the MV cost switched off.  uni_field / out_field: int16 [n_pics][2][n_ctu][64][2] as dwords; uni_ref / out_ref: uint8
-// [n_pics][2][n_ctu][64]; out_dir uint8 [n_pics][n_ctu][64].
+// Up to eight references per list: me_select_dirs_kernel with a reference dimension behind the list -- uni / bi tables int16
+// [n_pics][2][R][ctu_count][593][2] as dwords with costs uint32 of that shape, pred_q int16 [n_pics][2][R][n_ctu][2] or null (R =
+// n_refs_max); list l uses its first n_refs[l] sets.  The merge walks each of a lane's slots through the references of both lists in
+// registers, twice: the uni pass keeps per list the first strict minimum (:3086) with its MV, index and motion bits (ref_bits + MV bits,
+// :3154-3155), list 1 also the minimum over the references of l1_valid_mask -- its direction-2 candidate (:3096-3104, :3282-3285), absent
+// with an empty mask; the bi pass prices every reference against the OTHER list's motion bits (:3210-3219) and keeps the first strict
+// minimum (:3226).  Predictors and bit counts are wave-uniform; no LDS traffic, no atomic and no cross-lane step in the reference loops.
+// The two reference indices per slot go to LDS on top of the sibling's (35.8 KB per workgroup).  uni_ref / out_ref: uint8
+// [n_pics][2][n_ctu][64] beside the fields.
 __global__ void __launch_bounds__(256)
 me_select_dirs_refs_kernel(const uint32_t* __restrict__ mv_uni, const uint32_t* __restrict__ cost_uni, const uint32_t* __restrict__ mv_bi,
                            const uint32_t* __restrict__ cost_bi, const uint32_t* __restrict__ uni_field, const uint8_t* __restrict__ uni_ref,
@@ -2880,32 +2893,21 @@ me_select_dirs_refs_kernel(const uint32_t* __restrict__ mv_uni, const uint32_t* 
   __shared__ uint32_t s_mv[4][kParts + 3];
   __shared__ uint8_t s_dir[4][kParts + 3];
   __shared__ uint8_t s_lref[4][2 * (kParts + 3)];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int c = blockIdx.x * 4 + wave, pic = blockIdx.y;
-  const bool live = c < ctu_count;   // wave-uniform
-  const int ctu = ctu_first + c;
-  if (live) {
-    const MeDirRefsBits& b = dirs.p[pic];
-    auto mvb = [](uint32_t m, int pred_x, int pred_y) -> uint32_t {   // HM's getBits at cost scale 0
-      return me_component_bits((int16_t)(m & 0xffffu) - pred_x) + me_component_bits((int16_t)(m >> 16) - pred_y);
-    };
-    auto gc = [&](uint32_t n) -> uint64_t { return (lambda_q16 * n) >> 16; };   // TComRdCost::getCost: the product wraps in 32 bits
-    auto dist = [&](uint32_t cost, uint32_t bits) -> uint64_t {
-      const uint64_t g = gc(bits);
-      return cost > g ? cost - g : 0;
-    };
+  const MeSelectWave w = me_select_wave(ctu_first, ctu_count);
+  if (w.live) {
+    const MeDirRefsBits& b = dirs.p[w.pic];
     // set (l, r) of the picture: its table row of this CTU, its predictor of this CTU (wave-uniform)
-    auto row = [&](int l, int r) -> long { return ((((long)pic * 2 + l) * n_refs_max + r) * ctu_count + c) * kParts; };
+    auto row = [&](int l, int r) -> long { return ((((long)w.pic * 2 + l) * n_refs_max + r) * ctu_count + w.c) * kParts; };
     auto pred = [&](int l, int r, int& px, int& py) {
       px = 0; py = 0;
       if (pred_q) {
-        const int16_t* pq = pred_q + ((((long)pic * 2 + l) * n_refs_max + r) * n_ctu + ctu) * 2;
+        const int16_t* pq = pred_q + ((((long)w.pic * 2 + l) * n_refs_max + r) * n_ctu + w.ctu) * 2;
         px = pq[0]; py = pq[1];
       }
     };
 #pragma unroll 1
     for (int k = 0; k < kOwn; ++k) {
-      const int i = lane + 64 * k;
+      const int i = w.lane + 64 * k;
       if (i >= kParts) continue;
       uint64_t cu[2] = {0, 0}, cb[2] = {0, 0}, cv = 0;   // cv: list 1's direction-2 candidate
       uint32_t mu[2] = {0, 0}, mb[2] = {0, 0}, mot[2] = {0, 0}, mvv = 0;
@@ -2917,8 +2919,8 @@ me_select_dirs_refs_kernel(const uint32_t* __restrict__ mv_uni, const uint32_t* 
           int px, py;
           pred(l, r, px, py);
           const long at = row(l, r) + i;
-          const uint32_t m = mv_uni[at], bits = mvb(m, px, py);
-          const uint64_t p = dist(cost_uni[at], bits) + gc(b.dir_bits[l] + b.ref_bits[l][r] + bits);
+          const uint32_t m = mv_uni[at], bits = me_select_mv_bits(m, px, py);
+          const uint64_t p = me_select_dist(lambda_q16, cost_uni[at], bits) + me_select_get_cost(lambda_q16, b.dir_bits[l] + b.ref_bits[l][r] + bits);
           if (r == 0 || p < cu[l]) { cu[l] = p; mu[l] = m; ru[l] = r; mot[l] = b.ref_bits[l][r] + bits; }   // strict: the lower index wins ties
           if (l == 1 && ((b.l1_valid_mask >> r) & 1u) && (rv < 0 || p < cv)) { cv = p; mvv = m; rv = r; }
         }
@@ -2930,8 +2932,8 @@ me_select_dirs_refs_kernel(const uint32_t* __restrict__ mv_uni, const uint32_t* 
           int px, py;
           pred(l, r, px, py);
           const long at = row(l, r) + i;
-          const uint32_t m = mv_bi[at], bits = mvb(m, px, py);
-          const uint64_t p = (dist(cost_bi[at], bits) >> 1) + gc(b.dir_bits[2] + b.ref_bits[l][r] + bits + mot[1 - l]);
+          const uint32_t m = mv_bi[at], bits = me_select_mv_bits(m, px, py);
+          const uint64_t p = (me_select_dist(lambda_q16, cost_bi[at], bits) >> 1) + me_select_get_cost(lambda_q16, b.dir_bits[2] + b.ref_bits[l][r] + bits + mot[1 - l]);
           if (r == 0 || p < cb[l]) { cb[l] = p; mb[l] = m; rb[l] = r; }
         }
       }
@@ -2943,23 +2945,17 @@ me_select_dirs_refs_kernel(const uint32_t* __restrict__ mv_uni, const uint32_t* 
       if (cbi <= cu[0] && (rv < 0 || cbi <= cv)) { best = cbi; m = mb[bl]; d = 3 | bl << 2; r0 = rb[0]; r1 = rb[1]; }
       else if (rv < 0 || cu[0] <= cv) { best = cu[0]; m = mu[0]; d = 1; r0 = ru[0]; }
       else { best = cv; m = mvv; d = 2; r1 = rv; }
-      s_cost[wave][i] = best;
-      s_mv[wave][i] = m;
-      s_dir[wave][i] = (uint8_t)d;
-      s_lref[wave][i] = (uint8_t)r0;
-      s_lref[wave][kParts + 3 + i] = (uint8_t)r1;
+      s_cost[w.wave][i] = best;
+      s_mv[w.wave][i] = m;
+      s_dir[w.wave][i] = (uint8_t)d;
+      s_lref[w.wave][i] = (uint8_t)r0;
+      s_lref[w.wave][kParts + 3 + i] = (uint8_t)r1;
     }
   }
   __syncthreads();
-  if (!live) return;
-  const int ctus_x = (pic_w + 63) >> 6;
-  const int ctu_x = (ctu % ctus_x) * 64, ctu_y = (ctu / ctus_x) * 64;
-  MeSelect merged = a;
-  merged.price_mv = 0;   // inside the merged cost already
-  const long lists = (long)n_ctu * 64, at = (long)pic * lists;   // the picture's two lists start at entry 2 * at; its CTU index is at / 64 + ctu
-  me_select_decide_store<true, uint64_t, true, true>(merged, s_cost[wave], s_mv[wave], s_dir[wave], lambda_q16, 0, 0, lane, ctu_x, ctu_y, (long)pic * n_ctu + ctu,
-                                                     pic_w, pic_h, out_field + at, out_dir, out_slot, out_cost, uni_field + at, lists, s_lref[wave],
-                                                     uni_ref + at, out_ref + at);
+  if (!w.live) return;
+  me_select_decide_store<kSelDirsRefs, uint64_t>(a, {s_cost[w.wave], s_mv[w.wave], nullptr, s_dir[w.wave], s_lref[w.wave]},
+                                                 {out_field, out_slot, out_cost, out_ref, out_dir, uni_field, uni_ref}, w, lambda_q16, 0, 0, pic_w, pic_h, n_ctu);
 }
 
 // ---- residual and per-PU / per-CU distortion of a prediction (hmme_residual_pairs_device; the rule: include/hmme.h) -----------------------

@@ -730,27 +730,34 @@ class Engine:
         self._check(self.L.hmme_select_pairs_device(self.h, int(width), int(height), int(n_pairs), C.byref(fp), C.byref(sel), d_mv, d_cost, d_pred,
                                                     d_field, d_slot, d_ctu_cost, stream))
 
-    def _select_frame(self, call, lead, width, height, mv, cost, pred_q, ctu_first, ctu_count, outs):
-        """select_frame (lead = ()) and select_refs_frame (lead = (n_refs,): the dimension mv, cost and pred_q carry in front).  call(fp, *addresses)
-        -> the C entry's return code; outs: (array or None, dtype, shape behind n_ctu) per output of the entry, in its order -> the arrays, zeros
-        where None was passed"""
+    def _select_frame(self, call, lead, width, height, tables, inputs, pred_q, ctu_first, ctu_count, outs):
+        """the four select_*frame methods.  lead: the dimensions the tables and pred_q carry in front -- (), (n_refs,), (2,), (2, R); tables: the MV
+        (int16, [*lead, count, 593, 2]) and cost (uint32, [*lead, count, 593]) tables in the entry's order; inputs: (array, dtype, lead, shape
+        behind n_ctu) per further input; pred_q int16[*lead, n_ctu, 2] or None; outs: (array or None, dtype, lead, shape behind n_ctu) per output.
+        call(fp, *addresses in that order) -> the C entry's return code.  -> the outputs, zeros where None was passed"""
         n = self.L.hmme_num_ctus(width, height)
         count = n - ctu_first if ctu_count < 0 else ctu_count
         fp = FrameParams(1, 0, 8, ctu_first, count)
-        mv = np.ascontiguousarray(mv, dtype=np.int16)
-        cost = np.ascontiguousarray(cost, dtype=np.uint32)
-        assert mv.shape == lead + (count, NUM_PARTS, 2) and cost.shape == lead + (count, NUM_PARTS)
+        ins = []
+        for k, a in enumerate(tables):                                           # MV and cost tables alternate
+            a = np.ascontiguousarray(a, dtype=np.uint32 if k % 2 else np.int16)
+            assert a.shape == lead + (count, NUM_PARTS) + (() if k % 2 else (2,))
+            ins.append(a)
+        for a, dt, front, shape in inputs:
+            a = np.ascontiguousarray(a, dtype=dt)
+            assert a.shape == front + (n,) + shape
+            ins.append(a)
         pptr = None
         if pred_q is not None:
             pq = np.ascontiguousarray(pred_q, dtype=np.int16)
             assert pq.shape == lead + (n, 2)
             pptr = pq.ctypes.data
         arrays = []
-        for a, dt, shape in outs:
-            a = np.zeros((n,) + shape, dt) if a is None else a
-            assert a.dtype == dt and a.shape == (n,) + shape and a.flags.c_contiguous
+        for a, dt, front, shape in outs:
+            a = np.zeros(front + (n,) + shape, dt) if a is None else a
+            assert a.dtype == dt and a.shape == front + (n,) + shape and a.flags.c_contiguous
             arrays.append(a)
-        self._check(call(fp, mv.ctypes.data, cost.ctypes.data, pptr, *[a.ctypes.data for a in arrays]))
+        self._check(call(fp, *[a.ctypes.data for a in ins], pptr, *[a.ctypes.data for a in arrays]))
         return tuple(arrays)
 
     def select_frame(self, width, height, sel, mv, cost, pred_q=None, ctu_first=0, ctu_count=-1, field=None, slot=None, ctu_cost=None):
@@ -759,8 +766,8 @@ class Engine:
         when none is)"""
         per = int(sel.mv_per_ctu)
         call = lambda fp, *a: self.L.hmme_select_frame(self.h, int(width), int(height), C.byref(fp), C.byref(sel), *a)
-        return self._select_frame(call, (), width, height, mv, cost, pred_q, ctu_first, ctu_count,
-                                  ((field, np.int16, (per, 2)), (slot, np.uint16, (per,)), (ctu_cost, np.uint32, ())))
+        return self._select_frame(call, (), width, height, (mv, cost), (), pred_q, ctu_first, ctu_count,
+                                  ((field, np.int16, (), (per, 2)), (slot, np.uint16, (), (per,)), (ctu_cost, np.uint32, (), ())))
 
     # ---- the reference picture per PU, and the prediction from it (include/hmme.h, "the reference picture per PU") ----
     def select_refs_device(self, width, height, n_pics, n_refs, fp, sel, ref_cost, d_mv, d_cost, d_pred, d_field, d_ref, d_slot=None, d_ctu_cost=None,
@@ -780,8 +787,8 @@ class Engine:
         per = int(sel.mv_per_ctu)
         n_refs = np.shape(mv)[0]
         call = lambda fp, *a: self.L.hmme_select_refs_frame(self.h, int(width), int(height), n_refs, C.byref(fp), C.byref(sel), _ref_cost(ref_cost, n_refs), *a)
-        return self._select_frame(call, (n_refs,), width, height, mv, cost, pred_q, ctu_first, ctu_count,
-                                  ((field, np.int16, (per, 2)), (ref, np.uint8, (per,)), (slot, np.uint16, (per,)), (ctu_cost, np.uint32, ())))
+        return self._select_frame(call, (n_refs,), width, height, (mv, cost), (), pred_q, ctu_first, ctu_count,
+                                  ((field, np.int16, (), (per, 2)), (ref, np.uint8, (), (per,)), (slot, np.uint16, (), (per,)), (ctu_cost, np.uint32, (), ())))
 
     def predict_refs_device(self, refs, fp, d_mv_field, d_ref_field, mv_per_ctu, d_out, out_pitch_bytes, stream=0):
         """hmme_predict_refs_device: the luma prediction of one picture, every block from the plane of `refs` its reference index names
@@ -853,31 +860,9 @@ class Engine:
         """hmme_select_dirs_frame: one picture, host arrays.  mv_uni / mv_bi int16[2, count, 593, 2], cost_uni / cost_bi uint32[2, count, 593],
         uni_field int16[2, n_ctu, 64, 2], pred_q int16[2, n_ctu, 2] or None -> (field int16[2, n_ctu, 64, 2], dirs uint8[n_ctu, 64], slot
         uint16[n_ctu, 64], ctu_cost uint32[n_ctu]); entries outside the CTU range keep the values of the arrays passed in (zeros when none is)"""
-        n = self.L.hmme_num_ctus(width, height)
-        count = n - ctu_first if ctu_count < 0 else ctu_count
-        fp = FrameParams(1, 0, 8, ctu_first, count)
-        tabs = []
-        for a, dt, tail in ((mv_uni, np.int16, (NUM_PARTS, 2)), (cost_uni, np.uint32, (NUM_PARTS,)), (mv_bi, np.int16, (NUM_PARTS, 2)),
-                            (cost_bi, np.uint32, (NUM_PARTS,))):
-            a = np.ascontiguousarray(a, dtype=dt)
-            assert a.shape == (2, count) + tail
-            tabs.append(a)
-        uf = np.ascontiguousarray(uni_field, dtype=np.int16)
-        assert uf.shape == (2, n, 64, 2)
-        pptr = None
-        if pred_q is not None:
-            pq = np.ascontiguousarray(pred_q, dtype=np.int16)
-            assert pq.shape == (2, n, 2)
-            pptr = pq.ctypes.data
-        outs = []
-        for a, dt, shape in ((field, np.int16, (2, n, 64, 2)), (dirs, np.uint8, (n, 64)), (slot, np.uint16, (n, 64)), (ctu_cost, np.uint32, (n,))):
-            a = np.zeros(shape, dt) if a is None else a
-            assert a.dtype == dt and a.shape == shape and a.flags.c_contiguous
-            outs.append(a)
-        self._check(self.L.hmme_select_dirs_frame(self.h, int(width), int(height), C.byref(fp), C.byref(sel), C.byref(dir_params), tabs[0].ctypes.data,
-                                                  tabs[1].ctypes.data, tabs[2].ctypes.data, tabs[3].ctypes.data, uf.ctypes.data, pptr,
-                                                  *[a.ctypes.data for a in outs]))
-        return tuple(outs)
+        call = lambda fp, *a: self.L.hmme_select_dirs_frame(self.h, int(width), int(height), C.byref(fp), C.byref(sel), C.byref(dir_params), *a)
+        return self._select_frame(call, (2,), width, height, (mv_uni, cost_uni, mv_bi, cost_bi), ((uni_field, np.int16, (2,), (64, 2)),), pred_q, ctu_first, ctu_count,
+                                  ((field, np.int16, (2,), (64, 2)), (dirs, np.uint8, (), (64,)), (slot, np.uint16, (), (64,)), (ctu_cost, np.uint32, (), ())))
 
     def predict_bi_device(self, refs0, refs1, fp, d_mv_field, d_dir_field, mv_per_ctu, d_outs, out_pitch_bytes, stream=0):
         """hmme_predict_bi_device: the luma prediction of up to 8 pictures whose blocks are L0 (refs0[i]), L1 (refs1[i]) or bi (both, averaged
@@ -970,34 +955,12 @@ class Engine:
         593], uni_field int16[2, n_ctu, 64, 2], uni_ref uint8[2, n_ctu, 64], pred_q int16[2, R, n_ctu, 2] or None -> (field int16[2, n_ctu, 64, 2],
         ref uint8[2, n_ctu, 64], dirs uint8[n_ctu, 64], slot uint16[n_ctu, 64], ctu_cost uint32[n_ctu]); entries outside the CTU range keep the
         values of the arrays passed in (zeros when none is)"""
-        n = self.L.hmme_num_ctus(width, height)
-        count = n - ctu_first if ctu_count < 0 else ctu_count
-        fp = FrameParams(1, 0, 8, ctu_first, count)
         R = int(np.shape(mv_uni)[1])
-        tabs = []
-        for a, dt, tail in ((mv_uni, np.int16, (NUM_PARTS, 2)), (cost_uni, np.uint32, (NUM_PARTS,)), (mv_bi, np.int16, (NUM_PARTS, 2)),
-                            (cost_bi, np.uint32, (NUM_PARTS,))):
-            a = np.ascontiguousarray(a, dtype=dt)
-            assert a.shape == (2, R, count) + tail
-            tabs.append(a)
-        uf = np.ascontiguousarray(uni_field, dtype=np.int16)
-        ur = np.ascontiguousarray(uni_ref, dtype=np.uint8)
-        assert uf.shape == (2, n, 64, 2) and ur.shape == (2, n, 64)
-        pptr = None
-        if pred_q is not None:
-            pq = np.ascontiguousarray(pred_q, dtype=np.int16)
-            assert pq.shape == (2, R, n, 2)
-            pptr = pq.ctypes.data
-        outs = []
-        for a, dt, shape in ((field, np.int16, (2, n, 64, 2)), (ref, np.uint8, (2, n, 64)), (dirs, np.uint8, (n, 64)), (slot, np.uint16, (n, 64)),
-                             (ctu_cost, np.uint32, (n,))):
-            a = np.zeros(shape, dt) if a is None else a
-            assert a.dtype == dt and a.shape == shape and a.flags.c_contiguous
-            outs.append(a)
-        self._check(self.L.hmme_select_dirs_refs_frame(self.h, int(width), int(height), R, C.byref(fp), C.byref(sel), C.byref(dir_params), tabs[0].ctypes.data,
-                                                       tabs[1].ctypes.data, tabs[2].ctypes.data, tabs[3].ctypes.data, uf.ctypes.data, ur.ctypes.data, pptr,
-                                                       *[a.ctypes.data for a in outs]))
-        return tuple(outs)
+        call = lambda fp, *a: self.L.hmme_select_dirs_refs_frame(self.h, int(width), int(height), R, C.byref(fp), C.byref(sel), C.byref(dir_params), *a)
+        return self._select_frame(call, (2, R), width, height, (mv_uni, cost_uni, mv_bi, cost_bi),
+                                  ((uni_field, np.int16, (2,), (64, 2)), (uni_ref, np.uint8, (2,), (64,))), pred_q, ctu_first, ctu_count,
+                                  ((field, np.int16, (2,), (64, 2)), (ref, np.uint8, (2,), (64,)), (dirs, np.uint8, (), (64,)), (slot, np.uint16, (), (64,)),
+                                   (ctu_cost, np.uint32, (), ())))
 
     def predict_bi_refs_device(self, refs0, refs1, fp, d_mv_field, d_dir_field, d_ref_field, mv_per_ctu, d_out, out_pitch_bytes, stream=0):
         """hmme_predict_bi_refs_device: the luma prediction of one B picture, every block from refs0[ref0] (L0), refs1[ref1] (L1) or both (averaged
