@@ -2091,7 +2091,8 @@ int bi_weight_args(int bit_depth, const hmme_weight* wp, const char* which, char
 }
 
 // the other list's weight (TComWeightPrediction.cpp:133-180): ClipBD(((w0 * (P + 8192) + round') >> shift') + offset) with
-// shift' = shift + headRoom and round' = 1 << (shift' - 1); wp->round is not used.  P is a Pel, so P + 8192 lies within [-24 576, 40 959].
+// shift' = shift + headRoom and round' = 1 << (shift' - 1); wp->round is not used.  P is a Pel, so P + 8192 lies within [-24 576, 40 959]
+// (what the reference's filters reach on the worst-case, tap-sign content: luma -25 085 .. 25 079, chroma -14 112 .. 14 106, tests/golden/ref_blocks.npz).
 int other_weight_eval(int bit_depth, const hmme_weight* wp, bool* identity, hmme::MePredWp<1>* pw, char* msg, size_t n, const char* which = "other") {
   const int rc = bi_weight_args(bit_depth, wp, which, msg, n);
   if (rc) return rc;

@@ -2356,7 +2356,9 @@ struct MePredConst {
 
 __device__ __forceinline__ int me_clip_bd(int v, int maxv) { return v < 0 ? 0 : (v > maxv ? maxv : v); }
 // xPredInterUni with bi = true leaves the 14-bit intermediate P = sum >> 6 of the vertical pass (shift 6, offset 0, no clip).  HM keeps it in
-// a Pel: P + 8192 lies within [-24 576, 40 959] whatever the plane holds, |P| < 2^15.
+// a Pel: P + 8192 lies within [-24 576, 40 959] whatever the plane holds, |P| < 2^15.  The reference's own extremes, recorded from its compiled
+// filters on the tap-sign pictures of every phase (tests/golden/ref_blocks.npz): luma -25 085 .. 25 079 (12 bit, phase (2, 2)), chroma
+// -14 112 .. 14 106 -- the cast never wraps.
 __device__ __forceinline__ int me_pel14(int sum) { return (int16_t)(sum >> 6); }
 
 // The four tails take the vertical sum(s) of a sample before any shift and return the sample.

@@ -175,8 +175,93 @@ def ref():
             L.ref_sad_w.argtypes = [C.POINTER(C.c_int16), C.c_int, C.POINTER(C.c_int16), C.c_int] + [C.c_int] * 8
         L.ref_frac_refine_bi.restype = None
         L.ref_frac_refine_bi.argtypes = L.ref_frac_refine.argtypes
+        if hasattr(L, "ref_pred_block"):   # prediction blocks, prediction tails, WP estimator, block distortions
+            p16 = C.POINTER(C.c_int16)
+            L.ref_pred_block.restype = C.c_int
+            L.ref_pred_block.argtypes = [p16, C.c_int] + [C.c_int] * 7 + [_i16p]
+            L.ref_luma_block.restype = C.c_int
+            L.ref_luma_block.argtypes = [p16, C.c_int] + [C.c_int] * 6 + [_i16p]
+            L.ref_add_avg.restype = C.c_int
+            L.ref_add_avg.argtypes = [_i16p, _i16p] + [C.c_int] * 4 + [_i16p]
+            L.ref_add_weight_uni.restype = C.c_int
+            L.ref_add_weight_uni.argtypes = [_i16p] + [C.c_int] * 7 + [_i16p]
+            L.ref_add_weight_bi.restype = C.c_int
+            L.ref_add_weight_bi.argtypes = [_i16p, _i16p] + [C.c_int] * 9 + [_i16p]
+            L.ref_dist.restype = C.c_uint32
+            L.ref_dist.argtypes = [p16, C.c_int, p16, C.c_int] + [C.c_int] * 4
+            L.ref_wp_estimate.restype = C.c_int
+            L.ref_wp_estimate.argtypes = [C.POINTER(C.c_void_p)] + [C.c_int] * 7 + [_i32p, _i32p, _i32p]
         _ref = L
     return _ref
+
+
+# ---------------------------------------------------------------------------------------------
+# the reference's prediction blocks, tails, WP estimator and block distortions
+# ---------------------------------------------------------------------------------------------
+def _blk(a):
+    return np.ascontiguousarray(a, dtype=np.int16)
+
+
+def ref_pred_block(src, w, h, x_frac, y_frac, bd, bi, comp=0):
+    """TComPrediction::xPredInterBlk: src int16 [h + 7, w + 7] (luma: the block's top-left sample is src[3, 3]) or [h + 3, w + 3] (chroma of
+    4:2:0: src[1, 1]); fractions in quarter luma / eighth chroma pels -> int16 [h, w], the clipped sample (bi false) or the Pel intermediate"""
+    src = _blk(src)
+    b = 1 if comp else 3
+    assert src.shape == (h + 2 * b + 1, w + 2 * b + 1)
+    out = np.zeros((h, w), np.int16)
+    rc = ref().ref_pred_block(_addr(src, b * src.shape[1] + b), src.shape[1], w, h, int(x_frac), int(y_frac), int(bd), int(bool(bi)), int(comp), out)
+    assert rc == 0
+    return out
+
+
+def ref_add_avg(p0, p1, bd, comp=0):
+    """TComYuv::addAvg on the Pel intermediates p0, p1 (int16 [h, w]) of component comp -> int16 [h, w]"""
+    p0, p1 = _blk(p0), _blk(p1)
+    out = np.zeros(p0.shape, np.int16)
+    assert ref().ref_add_avg(p0, p1, p0.shape[1], p0.shape[0], int(bd), int(comp), out) == 0
+    return out
+
+
+def ref_add_weight_uni(p, bd, comp, weight, offset, log2_denom):
+    """xWeightedPredictionUni (getWpScaling, addWeightUni) with HM's syntax triple (iWeight, iOffset, uiLog2WeightDenom) of component comp"""
+    p = _blk(p)
+    out = np.zeros(p.shape, np.int16)
+    assert ref().ref_add_weight_uni(p, p.shape[1], p.shape[0], int(bd), int(comp), int(weight), int(offset), int(log2_denom), out) == 0
+    return out
+
+
+def ref_add_weight_bi(p0, p1, bd, comp, weight0, offset0, weight1, offset1, log2_denom):
+    """xWeightedPredictionBi (getWpScaling, addWeightBi), both lists used, one syntax triple per list sharing log2_denom"""
+    p0, p1 = _blk(p0), _blk(p1)
+    out = np.zeros(p0.shape, np.int16)
+    assert ref().ref_add_weight_bi(p0, p1, p0.shape[1], p0.shape[0], int(bd), int(comp), int(weight0), int(offset0), int(weight1), int(offset1),
+                                   int(log2_denom), out) == 0
+    return out
+
+
+DIST_SSE, DIST_HADS, DIST_SAD = 0, 1, 2
+
+
+def ref_dist(org, pred, bd, kind):
+    """TComRdCost::getDistPart(DF_SSE | DF_HADS | DF_SAD) of two int16 blocks [h, w]"""
+    org, pred = _blk(org), _blk(pred)
+    return int(ref().ref_dist(_addr(org), org.shape[1], _addr(pred), pred.shape[1], org.shape[1], org.shape[0], int(bd), int(kind)))
+
+
+def ref_wp_estimate(cur, refs, n_l0, n_l1, bd, log2_denom_start):
+    """HM's slice-level estimator.  cur: a 2-D luma array (4:0:0) or a (y, cb, cr) triple (4:2:0); refs: n_l0 + n_l1 of the same, list 0 first.
+    -> (table int32 [n_refs, 3, 4] = (present, iWeight, iOffset, log2Denom) after initWpScaling, the same after xCheckWPEnable, flags [2])"""
+    is420 = isinstance(cur, (tuple, list))
+    pics = [cur] + list(refs)
+    assert len(pics) == 1 + n_l0 + n_l1
+    planes = [_blk(p) for pic in pics for p in (pic if is420 else [pic])]
+    h, w = planes[0].shape
+    ptrs = (C.c_void_p * len(planes))(*[p.ctypes.data for p in planes])
+    n = n_l0 + n_l1
+    table, final, flags = np.zeros((n, 3, 4), np.int32), np.zeros((n, 3, 4), np.int32), np.zeros(2, np.int32)
+    rc = ref().ref_wp_estimate(ptrs, n_l0, n_l1, w, h, 420 if is420 else 400, int(bd), int(log2_denom_start), table.reshape(-1), final.reshape(-1), flags)
+    assert rc == 0, rc
+    return table, final, flags
 
 
 # ---------------------------------------------------------------------------------------------

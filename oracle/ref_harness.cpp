@@ -13,13 +13,17 @@
 #include "TLibCommon/TComDataCU.h"
 #include "TLibCommon/TComSlice.h"
 #include "TLibEncoder/TEncCfg.h"
+#include "TLibCommon/TComPic.h"
+#include "TLibCommon/TComYuv.h"
 #include "TLibEncoder/TEncSearch.h"
+#include "TLibEncoder/WeightPredAnalysis.h"
 #undef protected
 #undef private
 
 #include <stdint.h>
 #include <string.h>
 #include <new>
+#include <vector>
 
 namespace {
 
@@ -309,6 +313,249 @@ int ref_extend_border(const int16_t* img, int img_stride, int w, int h, int max_
   for (int i = 0; i < stride * total_h; ++i) out[i] = buf[i];
   pic.destroy();
   return margin;
+}
+
+}  // extern "C"
+
+// ---- prediction blocks, prediction tails, the weighted-prediction estimator and the block distortions --------------------------------
+namespace {
+
+// a second rig beside the search's: a CU inside a 4:2:0 picture whose slice carries a WP table, a 64x64 reference picture with margins, and
+// three 64x64 TComYuv.  Heap objects, never destroyed, like Rig's.
+struct TailRig {
+  TComDataCU* cu;
+  TComSlice* slice;
+  TComSPS* sps;
+  TComPPS* pps;
+  TComPic* pic;
+  TComPicYuv* ref;
+  TComYuv *src0, *src1, *dst;
+  TailRig() {
+    rig();   // initROM, the TEncSearch whose TComPrediction / TComWeightPrediction parts are used below
+    cu = new TComDataCU;
+    slice = new TComSlice;
+    sps = new TComSPS;
+    pps = new TComPPS;
+    pic = new TComPic;
+    ref = new TComPicYuv;
+    ref->create(64, 64, CHROMA_420, 64, 64, 4, true);
+    pic->m_apcPicYuv[TComPic::PIC_YUV_ORG] = ref;
+    pic->m_apcPicYuv[TComPic::PIC_YUV_REC] = ref;
+    pic->m_picSym.m_apSlices.push_back(slice);
+    slice->setSPS(sps);
+    slice->setPPS(pps);
+    slice->setPic(pic);
+    pps->setUseWP(true);
+    pps->setWPBiPred(true);
+    cu->m_pcSlice = slice;
+    cu->m_pcPic = pic;
+    cu->m_ctuRsAddr = 0;
+    cu->m_absZIdxInCtu = 0;
+    src0 = new TComYuv; src1 = new TComYuv; dst = new TComYuv;
+    src0->create(64, 64, CHROMA_420);
+    src1->create(64, 64, CHROMA_420);
+    dst->create(64, 64, CHROMA_420);
+    rig().search->initTempBuff(CHROMA_420);
+  }
+  void depth(int bd) {
+    for (int i = 0; i < MAX_NUM_CHANNEL_TYPE; ++i) sps->setBitDepth(ChannelType(i), bd);
+  }
+};
+
+TailRig& tail_rig() {
+  static TailRig* r = new TailRig;
+  return *r;
+}
+
+bool tail_block_ok(int w, int h, int comp) {
+  const int lim = comp ? 32 : 64;
+  return comp >= 0 && comp < 3 && w >= 2 && h >= 1 && w <= lim && h <= lim;
+}
+
+void put_block(TComYuv* yuv, int comp, const int16_t* p, int w, int h) {
+  for (int c = 0; c < 3; ++c) {
+    const ComponentID id = ComponentID(c);
+    memset(yuv->getAddr(id), 0, sizeof(Pel) * yuv->getStride(id) * yuv->getHeight(id));
+  }
+  const ComponentID id = ComponentID(comp);
+  Pel* d = yuv->getAddr(id);
+  for (int y = 0; y < h; ++y)
+    for (int x = 0; x < w; ++x) d[y * yuv->getStride(id) + x] = p[y * w + x];
+}
+
+void get_block(TComYuv* yuv, int comp, int16_t* out, int w, int h) {
+  const ComponentID id = ComponentID(comp);
+  const Pel* s = yuv->getAddr(id);
+  for (int y = 0; y < h; ++y)
+    for (int x = 0; x < w; ++x) out[y * w + x] = s[y * yuv->getStride(id) + x];
+}
+
+// the slice's WP table as the slice header carries it: HM's syntax triple per list for `comp`, the identity at the same denominator for the
+// other components
+void set_wp_table(TComSlice* slice, int comp, int log2_denom, const int* weight, const int* offset) {
+  for (int l = 0; l < 2; ++l)
+    for (int c = 0; c < 3; ++c) {
+      WPScalingParam* p = &slice->m_weightPredTable[l][0][c];
+      memset(p, 0, sizeof *p);
+      p->bPresentFlag = true;
+      p->uiLog2WeightDenom = log2_denom;
+      p->iWeight = c == comp ? weight[l] : 1 << log2_denom;
+      p->iOffset = c == comp ? offset[l] : 0;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+// TComPrediction::xPredInterBlk for one block of component `comp` (0 luma; 1, 2 chroma of a 4:2:0 picture): w x h samples of that component
+// whose top-left sample is `src`, displaced by the fraction (x_frac, y_frac) -- quarter luma pels, eighth chroma pels.  src must have 3 rows /
+// columns before and 4 after the block for luma, 1 and 2 for chroma.  bi = 0: the clipped sample; bi = 1: the Pel intermediate.
+int ref_pred_block(const int16_t* src, int src_stride, int w, int h, int x_frac, int y_frac, int bd, int bi, int comp, int16_t* out) {
+  if (!tail_block_ok(w, h, comp)) return -1;
+  TailRig& t = tail_rig();
+  t.depth(bd);
+  const ComponentID id = ComponentID(comp);
+  const int before = comp ? 1 : 3, after = comp ? 2 : 4, stride = t.ref->getStride(id);
+  Pel* origin = t.ref->getAddr(id);
+  for (int y = -before; y < h + after; ++y)
+    for (int x = -before; x < w + after; ++x) origin[y * stride + x] = src[y * src_stride + x];
+  TComMv mv((Short)x_frac, (Short)y_frac);
+  const int sx = t.ref->getComponentScaleX(id), sy = t.ref->getComponentScaleY(id);
+  rig().search->xPredInterBlk(id, t.cu, t.ref, 0, &mv, w << sx, h << sy, t.dst, bi != 0, bd);
+  get_block(t.dst, comp, out, w, h);
+  return 0;
+}
+
+int ref_luma_block(const int16_t* src, int src_stride, int w, int h, int x_frac, int y_frac, int bd, int bi, int16_t* out) {
+  return ref_pred_block(src, src_stride, w, h, x_frac, y_frac, bd, bi, 0, out);
+}
+
+// TComYuv::addAvg on two TComYuv holding the w x h intermediates p0, p1 (contiguous) in component `comp`
+int ref_add_avg(const int16_t* p0, const int16_t* p1, int w, int h, int bd, int comp, int16_t* out) {
+  if (!tail_block_ok(w, h, comp) || (w & 1)) return -1;
+  TailRig& t = tail_rig();
+  t.depth(bd);
+  put_block(t.src0, comp, p0, w, h);
+  put_block(t.src1, comp, p1, w, h);
+  const ComponentID id = ComponentID(comp);
+  t.dst->addAvg(t.src0, t.src1, 0, w << t.dst->getComponentScaleX(id), h << t.dst->getComponentScaleY(id), t.sps->getBitDepths());
+  get_block(t.dst, comp, out, w, h);
+  return 0;
+}
+
+// TComWeightPrediction::xWeightedPredictionUni -> getWpScaling -> addWeightUni with the slice's WP table set to HM's syntax triple
+int ref_add_weight_uni(const int16_t* p, int w, int h, int bd, int comp, int weight, int offset, int log2_denom, int16_t* out) {
+  if (!tail_block_ok(w, h, comp)) return -1;
+  TailRig& t = tail_rig();
+  t.depth(bd);
+  const int ws[2] = {weight, 1 << log2_denom}, os[2] = {offset, 0};
+  set_wp_table(t.slice, comp, log2_denom, ws, os);
+  put_block(t.src0, comp, p, w, h);
+  const ComponentID id = ComponentID(comp);
+  rig().search->xWeightedPredictionUni(t.cu, t.src0, 0, w << t.dst->getComponentScaleX(id), h << t.dst->getComponentScaleY(id), REF_PIC_LIST_0, t.dst, 0);
+  get_block(t.dst, comp, out, w, h);
+  return 0;
+}
+
+// TComWeightPrediction::xWeightedPredictionBi -> getWpScaling -> addWeightBi, both lists used
+int ref_add_weight_bi(const int16_t* p0, const int16_t* p1, int w, int h, int bd, int comp, int weight0, int offset0, int weight1, int offset1,
+                      int log2_denom, int16_t* out) {
+  if (!tail_block_ok(w, h, comp)) return -1;
+  TailRig& t = tail_rig();
+  t.depth(bd);
+  const int ws[2] = {weight0, weight1}, os[2] = {offset0, offset1};
+  set_wp_table(t.slice, comp, log2_denom, ws, os);
+  put_block(t.src0, comp, p0, w, h);
+  put_block(t.src1, comp, p1, w, h);
+  const ComponentID id = ComponentID(comp);
+  rig().search->xWeightedPredictionBi(t.cu, t.src0, t.src1, 0, 0, 0, w << t.dst->getComponentScaleX(id), h << t.dst->getComponentScaleY(id), t.dst);
+  get_block(t.dst, comp, out, w, h);
+  return 0;
+}
+
+// TComRdCost::getDistPart: kind 0 DF_SSE, 1 DF_HADS, 2 DF_SAD; the reference's own dispatch over its size variants runs
+uint32_t ref_dist(int16_t* org, int org_stride, int16_t* pred, int pred_stride, int w, int h, int bd, int kind) {
+  const DFunc f = kind == 0 ? DF_SSE : kind == 1 ? DF_HADS : DF_SAD;
+  return rig().rd->getDistPart(bd, pred, pred_stride, org, org_stride, w, h, COMPONENT_Y, f);
+}
+
+// the weighted-prediction estimation of TEncSlice::precompressSlice (TEncSlice.cpp:675-694) for one picture and its n_l0 + n_l1 references:
+// xCalcACDCParamSlice on every picture, xEstimateWPParamSlice, initWpScaling, xCheckWPEnable.  planes: the current picture's component
+// planes, then each reference's (list 0 first), every plane contiguous; 1 plane per picture for chroma_format 400, 3 (Y, Cb, Cr; chroma
+// (w / 2) x (h / 2)) for 420.  A reference's org and rec are the same plane.  n_l1 = 0: a P slice, else a B slice.
+// out[(r * 3 + c) * 4 + ...] = bPresentFlag, iWeight, iOffset, uiLog2WeightDenom of reference r (list 0 first), component c, as
+// initWpScaling leaves them; out_final the same after xCheckWPEnable; flags = the slice's m_bTestWeightPred, m_bTestWeightBiPred.
+// log2_denom_start is HM's own choice (6, or 7 with more than three references in list 0): another value is refused (-2).
+int ref_wp_estimate(const int16_t* const* planes, int n_l0, int n_l1, int w, int h, int chroma_format, int bd, int log2_denom_start, int32_t* out,
+                    int32_t* out_final, int32_t* flags) {
+  const int n_refs = n_l0 + n_l1, n_comp = chroma_format == 400 ? 1 : 3;
+  if ((chroma_format != 400 && chroma_format != 420) || n_l0 < 1 || n_l1 < 0 || n_l0 > MAX_NUM_REF || n_l1 > MAX_NUM_REF) return -1;
+  if (log2_denom_start != (n_l0 > 3 ? 7 : 6)) return -2;
+  rig();
+  const ChromaFormat fmt = chroma_format == 400 ? CHROMA_400 : CHROMA_420;
+  TComSPS sps;
+  TComPPS pps;
+  for (int i = 0; i < MAX_NUM_CHANNEL_TYPE; ++i) sps.setBitDepth(ChannelType(i), bd);
+  sps.setChromaFormatIdc(fmt);
+  pps.setUseWP(true);
+  pps.setWPBiPred(true);
+  std::vector<TComPic*> pics;
+  std::vector<TComPicYuv*> yuvs;
+  std::vector<TComSlice*> slices;
+  WeightPredAnalysis wpa;
+  for (int p = 0; p <= n_refs; ++p) {
+    TComPicYuv* yuv = new TComPicYuv;
+    yuv->create(w, h, fmt, 64, 64, 4, true);
+    for (int c = 0; c < n_comp; ++c) {
+      const ComponentID id = ComponentID(c);
+      const int16_t* s = planes[p * n_comp + c];
+      const int cw = yuv->getWidth(id), ch = yuv->getHeight(id);
+      for (int y = 0; y < ch; ++y)
+        for (int x = 0; x < cw; ++x) yuv->getAddr(id)[y * yuv->getStride(id) + x] = s[y * cw + x];
+    }
+    TComPic* pic = new TComPic;
+    TComSlice* slice = new TComSlice;
+    pic->m_apcPicYuv[TComPic::PIC_YUV_ORG] = yuv;
+    pic->m_apcPicYuv[TComPic::PIC_YUV_REC] = yuv;
+    pic->m_picSym.m_apSlices.push_back(slice);
+    slice->setSPS(&sps);
+    slice->setPPS(&pps);
+    slice->setPic(pic);
+    slice->initWpAcDcParam();
+    wpa.xCalcACDCParamSlice(slice);
+    pics.push_back(pic); yuvs.push_back(yuv); slices.push_back(slice);
+  }
+  TComSlice* cur = slices[0];
+  cur->setSliceType(n_l1 ? B_SLICE : P_SLICE);
+  cur->setNumRefIdx(REF_PIC_LIST_0, n_l0);
+  cur->setNumRefIdx(REF_PIC_LIST_1, n_l1);
+  for (int r = 0; r < n_l0; ++r) cur->setRefPic(pics[1 + r], REF_PIC_LIST_0, r);
+  for (int r = 0; r < n_l1; ++r) cur->setRefPic(pics[1 + n_l0 + r], REF_PIC_LIST_1, r);
+  cur->resetWpScaling();
+  wpa.xEstimateWPParamSlice(cur);
+  cur->initWpScaling(&sps);
+  for (int pass = 0; pass < 2; ++pass) {
+    int32_t* o = pass ? out_final : out;
+    for (int r = 0; r < n_refs; ++r)
+      for (int c = 0; c < 3; ++c) {
+        const WPScalingParam* p = &cur->m_weightPredTable[r < n_l0 ? 0 : 1][r < n_l0 ? r : r - n_l0][c];
+        int32_t* e = o + (r * 3 + c) * 4;
+        e[0] = c < n_comp ? p->bPresentFlag : 0; e[1] = c < n_comp ? p->iWeight : 0; e[2] = c < n_comp ? p->iOffset : 0;
+        e[3] = c < n_comp ? (int)p->uiLog2WeightDenom : 0;
+      }
+    if (!pass) wpa.xCheckWPEnable(cur);
+  }
+  flags[0] = cur->m_bTestWeightPred;
+  flags[1] = cur->m_bTestWeightBiPred;
+  for (size_t i = 0; i < pics.size(); ++i) {
+    pics[i]->m_picSym.m_apSlices.clear();
+    delete slices[i];
+    yuvs[i]->destroy();
+    delete yuvs[i];
+    delete pics[i];
+  }
+  return 0;
 }
 
 }  // extern "C"
