@@ -93,7 +93,7 @@ enum Buf {
   kWp0, kWp1, kWp2, kWp3,   // weighted whole-picture calls: u16 copies of the planes of one launch (below)
   kWwin,        // per-CTU calls with weighted prediction: the weighted copy of the staged window (the search's); first use
   kFracCover,   // uint16[]: fractional refinement, the slots covering each 8x8 / 4x4 position, same for every CTU; first use
-  kWpEst,       // hmme_plane_stats / hmme_wp_estimate: the 64-bit sums of one call (kWpStat* below); first use
+  kWpEst,       // hmme_plane_stats / hmme_wp_estimate / hmme_wp_estimate_420: the 64-bit sums of one call (kWpSet* below); first use
   kStage,       // the staging arena of the synchronous, host-array forms (Stage)
   kNumBufs
 };
@@ -3672,17 +3672,15 @@ int hmme_predict_chroma_bi_frame(hmme_ctx* ctx, const hmme_plane* const* ref0, c
 
 // ---- estimating explicit weighted-prediction parameters ----------------------------------------------------------------------------------------
 // WeightPredAnalysis::xCalcACDCParamSlice / xEstimateWPParamSlice / xUpdatingWPParameters / xSelectWP / xCalcSADvalueWP
-// (WeightPredAnalysis.cpp:67-120, :172-351) for luma: the whole-picture sums are kernels (me_plane_stats_kernel, me_wp_sad_kernel), the scalar
-// derivation between and behind them runs here in HM's own double / Int64 arithmetic.  Synchronous, on the context's private stream.
+// (WeightPredAnalysis.cpp:67-120, :172-351) for luma alone and for the three components of a 4:2:0 slice: the whole-picture sums are kernels
+// (me_plane_set_stats_kernel -- for a set of one plane its entry me_plane_stats_kernel -- and me_wp_sad_set_kernel: the 1 + n planes and n
+// pairs of a luma call, the 3 (1 + n) and 3 n of a 4:2:0 call),
+// the scalar derivation between and behind them is two pure functions in HM's own double / Int64 arithmetic (wp_parameters, wp_select).
+// Synchronous, on the context's private stream.
 namespace {
-// kWpEst: [2 i] / [2 i + 1] = sample sum and AC of plane i of the call, then two sums per reference of the SAD pass
-constexpr int kWpStatPlanes = hmme::kMaxRefs + 1;
-constexpr int kWpStatSad = 2 * kWpStatPlanes;
-constexpr int kWpStatWords = kWpStatSad + 2 * hmme::kMaxRefs;
-// hmme_wp_estimate_420 lays the same scratch out for its plane set: two sums per plane, then two per (reference, component)
+// kWpEst: [2 i] / [2 i + 1] = sample sum and AC of plane i of the call, then two sums per (reference, component) of the SAD pass
 constexpr int kWpSetSad = 2 * hmme::kMaxSetPlanes;
 constexpr int kWpSetWords = kWpSetSad + 2 * hmme::kMaxSetPairs;
-static_assert(kWpSetWords >= kWpStatWords, "one allocation serves both layouts");
 constexpr int kWpStatBlocks = 1024;   // workgroups of one launch at most: each ends in one atomic add per sum
 
 // lanes per row (log2) and workgroups of a reduction over the picture area of `pl`, n_y of them side by side (me_kernels.hpp: the geometry
@@ -3697,62 +3695,44 @@ StatGrid stat_grid(const hmme_plane* pl, int n_y) {
   return {l, (unsigned)((row_blocks + rounds - 1) / rounds)};
 }
 
-// the two passes of xCalcACDCParamSlice over one plane into sums[0], sums[1] (zero on entry); pass B reads what pass A left, same stream
-int launch_stats(hmme_ctx* ctx, const hmme_plane* pl, unsigned long long* sums, hipStream_t s) {
-  const StatGrid g = stat_grid(pl, 1);
-  if (pl->bps == 1) {
-    hipLaunchKernelGGL((hmme::me_plane_stats_kernel<uint8_t, 0>), dim3(g.blocks), dim3(256), 0, s, pl->origin(), pl->pitch, pl->width, pl->height, g.lpr_log2, sums);
-    hipLaunchKernelGGL((hmme::me_plane_stats_kernel<uint8_t, 1>), dim3(g.blocks), dim3(256), 0, s, pl->origin(), pl->pitch, pl->width, pl->height, g.lpr_log2, sums);
-  } else {
-    hipLaunchKernelGGL((hmme::me_plane_stats_kernel<uint16_t, 0>), dim3(g.blocks), dim3(256), 0, s, pl->origin(), pl->pitch, pl->width, pl->height, g.lpr_log2, sums);
-    hipLaunchKernelGGL((hmme::me_plane_stats_kernel<uint16_t, 1>), dim3(g.blocks), dim3(256), 0, s, pl->origin(), pl->pitch, pl->width, pl->height, g.lpr_log2, sums);
-  }
-  HIP_TRY(ctx, hipGetLastError());
-  return HMME_OK;
-}
-
-// xCalcSADvalueWP of `cur` against n_refs references of its size and sample type in one launch, two sums per reference (zero on entry)
-int launch_wp_sad(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme::MeWpSad& a, unsigned long long* sums, hipStream_t s) {
-  const StatGrid g = stat_grid(cur, n_refs);
-  RefSet rs = one_ref(refs[0]->origin());
-  for (int r = 0; r < n_refs; ++r) rs.base[r] = refs[r]->origin();
-  if (cur->bps == 1)
-    hipLaunchKernelGGL(hmme::me_wp_sad_kernel<uint8_t>, dim3(g.blocks, (unsigned)n_refs), dim3(256), 0, s, cur->origin(), rs, cur->pitch, cur->width, cur->height, g.lpr_log2, a, sums);
-  else
-    hipLaunchKernelGGL(hmme::me_wp_sad_kernel<uint16_t>, dim3(g.blocks, (unsigned)n_refs), dim3(256), 0, s, cur->origin(), rs, cur->pitch, cur->width, cur->height, g.lpr_log2, a, sums);
-  HIP_TRY(ctx, hipGetLastError());
-  return HMME_OK;
-}
-
-// the plane-set forms (me_kernels.hpp): one table entry per plane, the grid's x extent that of the plane that needs most workgroups
+// one table entry per plane, the grid's x extent that of the plane that needs most workgroups
 hmme::MePlaneDesc plane_desc(const hmme_plane* pl, int n_y, unsigned* blocks) {
   const StatGrid g = stat_grid(pl, n_y);
   *blocks = std::max(*blocks, g.blocks);
   return {pl->origin(), pl->pitch, pl->width, pl->height, g.lpr_log2};
 }
-// the two passes of xCalcACDCParamSlice over n (1..kMaxSetPlanes) planes of one sample type in two launches: sums[2 i], sums[2 i + 1] (zero on entry)
+// the two passes of xCalcACDCParamSlice over n (1..kMaxSetPlanes) planes of one sample type in two launches: sums[2 i], sums[2 i + 1] (zero on
+// entry); pass 1 reads what pass 0 left, same stream.  A set of one plane goes without the table (me_plane_stats_kernel: the same body)
 int launch_stats_set(hmme_ctx* ctx, const hmme_plane* const* pl, int n, unsigned long long* sums, hipStream_t s) {
   hmme::MePlaneSet set = {};
   unsigned blocks = 1;
   for (int i = 0; i < n; ++i) set.p[i] = plane_desc(pl[i], n, &blocks);
-  const dim3 grid(blocks, (unsigned)n);
-  if (pl[0]->bps == 1) {
-    hipLaunchKernelGGL((hmme::me_plane_set_stats_kernel<uint8_t, 0>), grid, dim3(256), 0, s, set, sums);
-    hipLaunchKernelGGL((hmme::me_plane_set_stats_kernel<uint8_t, 1>), grid, dim3(256), 0, s, set, sums);
-  } else {
-    hipLaunchKernelGGL((hmme::me_plane_set_stats_kernel<uint16_t, 0>), grid, dim3(256), 0, s, set, sums);
-    hipLaunchKernelGGL((hmme::me_plane_set_stats_kernel<uint16_t, 1>), grid, dim3(256), 0, s, set, sums);
-  }
+  auto passes = [&](auto one0, auto one1, auto set0, auto set1) {
+    if (n == 1) {
+      hipLaunchKernelGGL(one0, dim3(blocks), dim3(256), 0, s, set.p[0], sums);
+      hipLaunchKernelGGL(one1, dim3(blocks), dim3(256), 0, s, set.p[0], sums);
+    } else {
+      hipLaunchKernelGGL(set0, dim3(blocks, (unsigned)n), dim3(256), 0, s, set, sums);
+      hipLaunchKernelGGL(set1, dim3(blocks, (unsigned)n), dim3(256), 0, s, set, sums);
+    }
+  };
+  if (pl[0]->bps == 1)
+    passes(hmme::me_plane_stats_kernel<uint8_t, 0>, hmme::me_plane_stats_kernel<uint8_t, 1>, hmme::me_plane_set_stats_kernel<uint8_t, 0>, hmme::me_plane_set_stats_kernel<uint8_t, 1>);
+  else
+    passes(hmme::me_plane_stats_kernel<uint16_t, 0>, hmme::me_plane_stats_kernel<uint16_t, 1>, hmme::me_plane_set_stats_kernel<uint16_t, 0>, hmme::me_plane_set_stats_kernel<uint16_t, 1>);
   HIP_TRY(ctx, hipGetLastError());
   return HMME_OK;
 }
-// xCalcSADvalueWP of the three components of `cur` against those of n_refs references in one launch: pair 3 r + c = refs[3 r + c] against
-// cur[c], a.weight / offset / log2_denom filled in by the caller; two sums per pair (zero on entry)
-int launch_wp_sad_set(hmme_ctx* ctx, const hmme_plane* const* cur, const hmme_plane* const* refs, int n_refs, hmme::MeWpSadSet& a, unsigned long long* sums, hipStream_t s) {
+// xCalcSADvalueWP of the comps (1 or 3) components of `cur` against those of n_refs references in one launch: pair comps r + c =
+// refs[comps r + c] against cur[c], a.weight / offset / log2_denom filled in by the caller; two sums per pair (zero on entry)
+int launch_wp_sad_set(hmme_ctx* ctx, const hmme_plane* const* cur, const hmme_plane* const* refs, int comps, int n_refs, hmme::MeWpSadSet& a,
+                      unsigned long long* sums, hipStream_t s) {
+  const int n_pairs = comps * n_refs;
   unsigned blocks = 1;
-  for (int c = 0; c < 3; ++c) a.cur[c] = plane_desc(cur[c], 3 * n_refs, &blocks);
-  for (int i = 0; i < 3 * n_refs; ++i) a.ref[i] = refs[i]->origin();
-  const dim3 grid(blocks, (unsigned)(3 * n_refs));
+  a.comps = comps;
+  for (int c = 0; c < comps; ++c) a.cur[c] = plane_desc(cur[c], n_pairs, &blocks);
+  for (int i = 0; i < n_pairs; ++i) a.ref[i] = refs[i]->origin();
+  const dim3 grid(blocks, (unsigned)n_pairs);
   if (cur[0]->bps == 1) hipLaunchKernelGGL(hmme::me_wp_sad_set_kernel<uint8_t>, grid, dim3(256), 0, s, a, sums);
   else hipLaunchKernelGGL(hmme::me_wp_sad_set_kernel<uint16_t>, grid, dim3(256), 0, s, a, sums);
   HIP_TRY(ctx, hipGetLastError());
@@ -3779,9 +3759,9 @@ int planes_read_end(hmme_ctx* ctx, const hmme_plane* const* planes, int n, hipSt
   return rc ? rc : r3;
 }
 
-// the sums of every plane of the list that has none cached: all their passes enqueued, one download, one wait.  as_set: the planes (of one
-// sample type, up to kMaxSetPlanes) go through the plane-set kernels, two launches for all of them; otherwise two launches per plane
-int collect_stats(hmme_ctx* ctx, const hmme_plane* const* planes, int n, hipStream_t s, bool as_set = false) {
+// the sums of every plane of the list (of one sample type, up to kMaxSetPlanes) that has none cached: two launches for all of them, one
+// download, one wait
+int collect_stats(hmme_ctx* ctx, const hmme_plane* const* planes, int n, hipStream_t s) {
   const hmme_plane* todo[hmme::kMaxSetPlanes];
   int n_todo = 0;
   for (int i = 0; i < n; ++i) {
@@ -3794,14 +3774,11 @@ int collect_stats(hmme_ctx* ctx, const hmme_plane* const* planes, int n, hipStre
   int rc = planes_read_begin(ctx, todo, n_todo, s);
   if (rc) return rc;
   unsigned long long h[2 * hmme::kMaxSetPlanes];
-  hipError_t e = hipMemsetAsync(ctx->buf[kWpEst].as<unsigned long long>(), 0, sizeof(unsigned long long) * 2 * n_todo, s);
+  unsigned long long* d_sums = ctx->buf[kWpEst].as<unsigned long long>();
+  hipError_t e = hipMemsetAsync(d_sums, 0, sizeof(unsigned long long) * 2 * n_todo, s);
   if (e != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "plane statistics: %s", hipGetErrorString(e));
-  if (as_set) {
-    if (rc == HMME_OK) rc = launch_stats_set(ctx, todo, n_todo, ctx->buf[kWpEst].as<unsigned long long>(), s);
-  } else {
-    for (int j = 0; j < n_todo && rc == HMME_OK; ++j) rc = launch_stats(ctx, todo[j], ctx->buf[kWpEst].as<unsigned long long>() + 2 * j, s);
-  }
-  if (rc == HMME_OK && (e = hipMemcpyAsync(h, ctx->buf[kWpEst].as<unsigned long long>(), sizeof(unsigned long long) * 2 * n_todo, hipMemcpyDeviceToHost, s)) != hipSuccess)
+  if (rc == HMME_OK) rc = launch_stats_set(ctx, todo, n_todo, d_sums, s);
+  if (rc == HMME_OK && (e = hipMemcpyAsync(h, d_sums, sizeof(unsigned long long) * 2 * n_todo, hipMemcpyDeviceToHost, s)) != hipSuccess)
     rc = fail(ctx, HMME_ERR_DEVICE, "plane statistics: %s", hipGetErrorString(e));
   rc = planes_read_end(ctx, todo, n_todo, s, rc);
   if (rc) return rc;
@@ -3813,153 +3790,23 @@ int collect_stats(hmme_ctx* ctx, const hmme_plane* const* planes, int n, hipStre
   return HMME_OK;
 }
 
-// what hmme_wp_estimate refuses; fills planes[0] = cur, planes[1 + r] = refs[r]
-int wp_estimate_args(hmme_ctx* ctx, const char* who, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane** planes) {
-  if (!cur || !refs) return fail(ctx, HMME_ERR_ARG, "%s: null plane", who);
-  if (n_refs < 1 || n_refs > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d references outside 1..%d", who, n_refs, hmme::kMaxRefs);
-  if (cur->ctx != ctx) return fail(ctx, HMME_ERR_ARG, "%s: plane belongs to another context", who);
-  planes[0] = cur;
-  for (int r = 0; r < n_refs; ++r) {
-    const hmme_plane* p = refs[r];
-    if (!p) return fail(ctx, HMME_ERR_ARG, "%s: reference %d is null", who, r);
-    if (p->ctx != ctx) return fail(ctx, HMME_ERR_ARG, "%s: reference %d belongs to another context", who, r);
-    if (p->width != cur->width || p->height != cur->height || p->bit_depth != cur->bit_depth)
-      return fail(ctx, HMME_ERR_ARG, "%s: reference %d is %d x %d at %d bits, the current picture %d x %d at %d", who, r, p->width, p->height, p->bit_depth,
-                  cur->width, cur->height, cur->bit_depth);
-    planes[1 + r] = p;
-  }
-  return HMME_OK;
-}
-}  // namespace
+// The estimator's arithmetic: pure functions, no context, no device (hmme_test_wp_parameters / hmme_test_wp_select show them to the CPU tests).
+// comps = 1 (luma alone) or 3 (Y, Cb, Cr of a 4:2:0 slice); plane i of a call is component i % comps of the current picture (i < comps) or of
+// reference i / comps - 1; stats[2 i], stats[2 i + 1] = its (dc_sum, ac), n_samples[c] = the sample count of component c; entry comps r + c
+// belongs to component c of reference r.
 
-int hmme_plane_stats(const hmme_plane* pl, int64_t* dc_sum, int64_t* ac) {
-  if (!pl) return HMME_ERR_ARG;
-  hmme_ctx* ctx = pl->ctx;
-  if (!dc_sum || !ac) return fail(ctx, HMME_ERR_ARG, "hmme_plane_stats: null output");
-  const int rc = collect_stats(ctx, &pl, 1, ctx->stream);
-  if (rc) return rc;
-  *dc_sum = pl->stats_dc; *ac = pl->stats_ac;
-  return HMME_OK;
-}
-
-int hmme_wp_estimate(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, int log2_denom_start, hmme_weight* out_wp,
-                     hmme_wp_info* out_info) {
-  if (!ctx) return HMME_ERR_ARG;
-  if (!out_wp) return fail(ctx, HMME_ERR_ARG, "hmme_wp_estimate: null output");
-  if (log2_denom_start < 3 || log2_denom_start > 7) return fail(ctx, HMME_ERR_ARG, "hmme_wp_estimate: log2_denom_start %d outside 3..7", log2_denom_start);
-  const hmme_plane* planes[kWpStatPlanes];
-  int rc = wp_estimate_args(ctx, "hmme_wp_estimate", cur, refs, n_refs, planes);
-  if (rc) return rc;
-  hipStream_t s = ctx->stream;
-  rc = collect_stats(ctx, planes, 1 + n_refs, s);   // xCalcACDCParamSlice of every picture that has not been through it since its last fill
-  if (rc) return rc;
-
-  // xEstimateWPParamSlice (:172-196): xUpdatingWPParameters (:200-268) from log2_denom_start downwards until every weight is in range
-  const int bd = cur->bit_depth;
-  const int64_t n_samples = (int64_t)cur->width * cur->height;
-  auto norm_dc = [&](int64_t sum) { return (sum + (n_samples >> 1)) / n_samples; };   // :115 without the RExt precision shift
-  const int64_t cur_dc = norm_dc(cur->stats_dc), cur_ac = cur->stats_ac;
-  int d = log2_denom_start, weight[hmme::kMaxRefs], offset[hmme::kMaxRefs];
+// xEstimateWPParamSlice (:172-196): xUpdatingWPParameters (:200-268) from log2_denom_start (3..7) downwards until every weight is in range --
+// reference outer, component inner, the first weight out of range ends a pass.  -> *log2_denom and (weight, clipped offset) of every entry
+void wp_parameters(const int64_t* stats, const int64_t* n_samples, int comps, int n_refs, int bd, int log2_denom_start, int* log2_denom, int* weight,
+                   int* offset) {
+  auto norm_dc = [&](int plane) { const int64_t n = n_samples[plane % comps]; return (stats[2 * plane] + (n >> 1)) / n; };   // :115 without the RExt precision shift
+  int d = log2_denom_start;
   for (;; --d) {   // ends at d = 3 at the latest: dWeight <= 15 puts weight in [0, 120], (1 << 3) - weight in [-112, 8]
     const int real_d = d + (bd - 8);
     bool in_range = true;
-    for (int r = 0; r < n_refs && in_range; ++r) {
-      const int64_t ref_dc = norm_dc(refs[r]->stats_dc), ref_ac = refs[r]->stats_ac;
-      const double dw = ref_ac == 0 ? 1.0 : std::min(std::max(-16.0, (double)cur_ac / (double)ref_ac), 15.0);        // :234
-      const int wgt = (int)(0.5 + dw * (double)(1 << d));                                                             // :235
-      const int off = (int)(((cur_dc << d) - (int64_t)wgt * ref_dc + ((int64_t)1 << (real_d - 1))) >> real_d);        // :236
-      weight[r] = wgt;
-      offset[r] = std::min(std::max(-128, off), 127);                                                                  // :248, range = 128
-      const int delta = (1 << d) - wgt;                                                                                // :252-258
-      in_range = !(delta >= 128 || delta < -128);
-    }
-    if (in_range) break;
-  }
-
-  // xSelectWP (:272-320): xCalcSADvalueWP with the estimated and with the default parameters, one read of the planes for both
-  hmme::MeWpSad a = {};
-  for (int r = 0; r < n_refs; ++r) {
-    a.weight[r] = weight[r];
-    a.offset[r] = offset[r] * (1 << (d + bd - 8));   // iOffset << iRealLog2Denom (:344)
-    a.log2_denom[r] = d;
-  }
-  rc = planes_read_begin(ctx, planes, 1 + n_refs, s);
-  if (rc) return rc;
-  unsigned long long h[2 * hmme::kMaxRefs];
-  unsigned long long* d_sums = ctx->buf[kWpEst].as<unsigned long long>() + kWpStatSad;
-  hipError_t e = hipMemsetAsync(d_sums, 0, sizeof(unsigned long long) * 2 * n_refs, s);
-  if (e != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "hmme_wp_estimate: %s", hipGetErrorString(e));
-  if (rc == HMME_OK) rc = launch_wp_sad(ctx, cur, refs, n_refs, a, d_sums, s);
-  if (rc == HMME_OK && (e = hipMemcpyAsync(h, d_sums, sizeof(unsigned long long) * 2 * n_refs, hipMemcpyDeviceToHost, s)) != hipSuccess)
-    rc = fail(ctx, HMME_ERR_DEVICE, "hmme_wp_estimate: %s", hipGetErrorString(e));
-  rc = planes_read_end(ctx, planes, 1 + n_refs, s, rc);
-  if (rc) return rc;
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-
-  for (int r = 0; r < n_refs; ++r) {
-    const int64_t sad_wp = (int64_t)h[2 * r] / n_samples, sad_nowp = (int64_t)(h[2 * r + 1] << d) / n_samples;   // :350
-    const double ratio = (double)sad_wp / (double)sad_nowp;   // :305 -- 0 / 0 is NaN and NaN >= 0.99 is false: identical pictures keep their (identity) weight present
-    int present = 1;
-    if (ratio >= 0.99) {   // DTHRESH (:46); :306-314
-      present = 0;
-      weight[r] = 1 << d;
-      offset[r] = 0;
-    }
-    // TComSlice::initWpScaling (TComSlice.cpp:1487-1512): what the search and the refinement take
-    const hmme_weight wp = {weight[r], offset[r] * (1 << (bd - 8)), d, d ? 1 << (d - 1) : 0};
-    out_wp[r] = wp;
-    if (out_info) {
-      hmme_wp_info& o = out_info[r];
-      o.cur_dc_sum = cur->stats_dc; o.cur_ac = cur_ac; o.ref_dc_sum = refs[r]->stats_dc; o.ref_ac = refs[r]->stats_ac;
-      o.sad_wp = sad_wp; o.sad_nowp = sad_nowp;
-      o.log2_denom = d; o.weight = weight[r]; o.offset = offset[r];
-      o.present = present;
-      o.served_search = hmme_weight_check(bd, &wp, 0) == HMME_OK ? 1 : 0;
-      o.served_refine = hmme_weight_check(bd, &wp, 1) == HMME_OK ? 1 : 0;
-    }
-  }
-  return HMME_OK;
-}
-
-// xEstimateWPParamSlice for a 4:2:0 slice: the same steps joint over Y, Cb, Cr (the rule: include/hmme.h).  planes[c] = cur[c],
-// planes[3 (1 + r) + c] = refs[3 r + c]; the sums of all of them through the plane-set kernels.
-int hmme_wp_estimate_420(hmme_ctx* ctx, const hmme_plane* const* cur, const hmme_plane* const* refs, int n_refs, int log2_denom_start,
-                         hmme_weight* out_wp_luma, hmme_weight* out_wp_chroma, hmme_wp_info* out_info) {
-  static const char* const who = "hmme_wp_estimate_420";
-  if (!ctx) return HMME_ERR_ARG;
-  if (!cur || !refs || !out_wp_luma || !out_wp_chroma) return fail(ctx, HMME_ERR_ARG, "%s: null argument", who);
-  if (n_refs < 1 || n_refs > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d references outside 1..%d", who, n_refs, hmme::kMaxRefs);
-  if (log2_denom_start < 3 || log2_denom_start > 7) return fail(ctx, HMME_ERR_ARG, "%s: log2_denom_start %d outside 3..7", who, log2_denom_start);
-  const int n_planes = 3 * (1 + n_refs);
-  const hmme_plane* planes[hmme::kMaxSetPlanes];
-  for (int i = 0; i < n_planes; ++i) {
-    planes[i] = i < 3 ? cur[i] : refs[i - 3];
-    if (!planes[i]) return fail(ctx, HMME_ERR_ARG, "%s: null plane", who);
-    if (planes[i]->ctx != ctx) return fail(ctx, HMME_ERR_ARG, "%s: plane belongs to another context", who);
-  }
-  const int w = cur[0]->width, h = cur[0]->height, bd = cur[0]->bit_depth;
-  for (int i = 0; i < n_planes; i += 3) {   // Y, Cb, Cr of one picture: chroma_size is what the hmme_predict_chroma_* calls ask of their planes
-    if (planes[i]->width != w || planes[i]->height != h)
-      return fail(ctx, HMME_ERR_ARG, "%s: reference %d is %d x %d, the current picture %d x %d", who, i / 3 - 1, planes[i]->width, planes[i]->height, w, h);
-    const int rc = chroma_size(ctx, who, planes + i + 1, 2, w, h);
-    if (rc) return rc;
-  }
-  for (int i = 0; i < n_planes; ++i)
-    if (planes[i]->bit_depth != bd) return fail(ctx, HMME_ERR_ARG, "%s: planes of %d and %d bits in one call", who, bd, planes[i]->bit_depth);
-  hipStream_t s = ctx->stream;
-  int rc = collect_stats(ctx, planes, n_planes, s, true);   // xCalcACDCParamSlice of every plane that has not been through it since its last fill
-  if (rc) return rc;
-
-  // xUpdatingWPParameters (:200-268) from log2_denom_start downwards: reference outer, component inner, the first weight out of range ends a pass
-  const int64_t n_samples[3] = {(int64_t)w * h, (int64_t)(w / 2) * (h / 2), (int64_t)(w / 2) * (h / 2)};
-  auto norm_dc = [&](const hmme_plane* p, int c) { return (p->stats_dc + (n_samples[c] >> 1)) / n_samples[c]; };   // :115 without the RExt precision shift
-  int d = log2_denom_start, weight[hmme::kMaxSetPairs], offset[hmme::kMaxSetPairs];
-  for (;; --d) {   // ends at d = 3 at the latest, as in hmme_wp_estimate
-    const int real_d = d + (bd - 8);
-    bool in_range = true;
-    for (int i = 0; i < 3 * n_refs && in_range; ++i) {
-      const int c = i % 3;
-      const int64_t cur_dc = norm_dc(cur[c], c), cur_ac = cur[c]->stats_ac, ref_dc = norm_dc(refs[i], c), ref_ac = refs[i]->stats_ac;
+    for (int i = 0; i < comps * n_refs && in_range; ++i) {
+      const int c = i % comps;
+      const int64_t cur_dc = norm_dc(c), cur_ac = stats[2 * c + 1], ref_dc = norm_dc(comps + i), ref_ac = stats[2 * (comps + i) + 1];
       const double dw = ref_ac == 0 ? 1.0 : std::min(std::max(-16.0, (double)cur_ac / (double)ref_ac), 15.0);        // :234
       const int wgt = (int)(0.5 + dw * (double)(1 << d));                                                             // :235
       const int off = (int)(((cur_dc << d) - (int64_t)wgt * ref_dc + ((int64_t)1 << (real_d - 1))) >> real_d);        // :236
@@ -3976,55 +3823,165 @@ int hmme_wp_estimate_420(hmme_ctx* ctx, const hmme_plane* const* cur, const hmme
     }
     if (in_range) break;
   }
+  *log2_denom = d;
+}
 
-  // xSelectWP (:272-320): both of xCalcSADvalueWP's sums of every (reference, component) in one launch
+// xSelectWP (:272-320) on what wp_parameters gave and the two raw sums per entry as me_wp_sad_set_kernel leaves them (sums[2 i] weighted,
+// sums[2 i + 1] unweighted before its << d), then TComSlice::initWpScaling (TComSlice.cpp:1487-1512: what the search, the refinement and the
+// prediction take) -> wp[i] and, where given, info[i] of every entry
+void wp_select(const int64_t* stats, const int64_t* n_samples, int comps, int n_refs, int bd, int d, const int* weight, const int* offset,
+               const unsigned long long* sums, hmme_weight* wp, hmme_wp_info* info) {
+  for (int r = 0; r < n_refs; ++r) {
+    int64_t sad_wp[3], sad_nowp[3], sum_wp = 0, sum_nowp = 0;   // every component divided by its own size (:350) before they are added (:301-302)
+    for (int c = 0; c < comps; ++c) {
+      const int i = comps * r + c;
+      sad_wp[c] = (int64_t)sums[2 * i] / n_samples[c];
+      sad_nowp[c] = (int64_t)(sums[2 * i + 1] << d) / n_samples[c];
+      sum_wp += sad_wp[c]; sum_nowp += sad_nowp[c];
+    }
+    // :305 -- 0 / 0 is NaN and NaN >= 0.99 is false: identical pictures keep their (identity) weights present; x / 0 is +inf and disables them
+    const double ratio = (double)sum_wp / (double)sum_nowp;
+    const int present = ratio >= 0.99 ? 0 : 1;   // DTHRESH (:46); :306-314: all components of the reference together
+    for (int c = 0; c < comps; ++c) {
+      const int i = comps * r + c, wgt = present ? weight[i] : 1 << d, off = present ? offset[i] : 0;
+      wp[i] = {wgt, off * (1 << (bd - 8)), d, d ? 1 << (d - 1) : 0};
+      if (!info) continue;
+      hmme_wp_info& o = info[i];
+      o.cur_dc_sum = stats[2 * c]; o.cur_ac = stats[2 * c + 1]; o.ref_dc_sum = stats[2 * (comps + i)]; o.ref_ac = stats[2 * (comps + i) + 1];
+      o.sad_wp = sad_wp[c]; o.sad_nowp = sad_nowp[c];
+      o.log2_denom = d; o.weight = wgt; o.offset = off;
+      o.present = present;
+      if (c == 0) {
+        o.served_search = hmme_weight_check(bd, &wp[i], 0) == HMME_OK ? 1 : 0;
+        o.served_refine = hmme_weight_check(bd, &wp[i], 1) == HMME_OK ? 1 : 0;
+      } else {   // what predict_args / frame_checks ask of a component's weight in the hmme_predict_chroma_* calls
+        char msg[256];
+        o.served_search = o.served_refine = other_weight_eval(bd, &wp[i], nullptr, nullptr, msg, sizeof msg) == HMME_OK ? 1 : 0;
+      }
+    }
+  }
+}
+
+// xEstimateWPParamSlice over planes the entry point has checked: planes[c] = component c of the current picture, planes[comps (1 + r) + c] =
+// of reference r.  wp[comps r + c] and, where given, info[comps r + c]; nothing is written before the last wait has succeeded
+int wp_estimate(hmme_ctx* ctx, const char* who, const hmme_plane* const* planes, int comps, int n_refs, int log2_denom_start, hmme_weight* wp,
+                hmme_wp_info* info) {
+  const int n_planes = comps * (1 + n_refs), n_pairs = comps * n_refs, bd = planes[0]->bit_depth;
+  hipStream_t s = ctx->stream;
+  int rc = collect_stats(ctx, planes, n_planes, s);   // xCalcACDCParamSlice of every plane that has not been through it since its last fill
+  if (rc) return rc;
+  int64_t stats[2 * hmme::kMaxSetPlanes], n_samples[3] = {};
+  for (int c = 0; c < comps; ++c) n_samples[c] = (int64_t)planes[c]->width * planes[c]->height;
+  for (int i = 0; i < n_planes; ++i) { stats[2 * i] = planes[i]->stats_dc; stats[2 * i + 1] = planes[i]->stats_ac; }
+  int d, weight[hmme::kMaxSetPairs], offset[hmme::kMaxSetPairs];
+  wp_parameters(stats, n_samples, comps, n_refs, bd, log2_denom_start, &d, weight, offset);
+
+  // xCalcSADvalueWP with the estimated and with the default parameters of every (reference, component): one launch, one read of the planes for both
   hmme::MeWpSadSet a = {};
-  for (int i = 0; i < 3 * n_refs; ++i) {
+  for (int i = 0; i < n_pairs; ++i) {
     a.weight[i] = weight[i];
     a.offset[i] = offset[i] * (1 << (d + bd - 8));   // iOffset << iRealLog2Denom (:344)
     a.log2_denom[i] = d;
   }
   rc = planes_read_begin(ctx, planes, n_planes, s);
   if (rc) return rc;
-  unsigned long long hs[2 * hmme::kMaxSetPairs];
+  unsigned long long h[2 * hmme::kMaxSetPairs];
   unsigned long long* d_sums = ctx->buf[kWpEst].as<unsigned long long>() + kWpSetSad;
-  hipError_t e = hipMemsetAsync(d_sums, 0, sizeof(unsigned long long) * 6 * n_refs, s);
+  hipError_t e = hipMemsetAsync(d_sums, 0, sizeof(unsigned long long) * 2 * n_pairs, s);
   if (e != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
-  if (rc == HMME_OK) rc = launch_wp_sad_set(ctx, cur, refs, n_refs, a, d_sums, s);
-  if (rc == HMME_OK && (e = hipMemcpyAsync(hs, d_sums, sizeof(unsigned long long) * 6 * n_refs, hipMemcpyDeviceToHost, s)) != hipSuccess)
+  if (rc == HMME_OK) rc = launch_wp_sad_set(ctx, planes, planes + comps, comps, n_refs, a, d_sums, s);
+  if (rc == HMME_OK && (e = hipMemcpyAsync(h, d_sums, sizeof(unsigned long long) * 2 * n_pairs, hipMemcpyDeviceToHost, s)) != hipSuccess)
     rc = fail(ctx, HMME_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
   rc = planes_read_end(ctx, planes, n_planes, s, rc);
   if (rc) return rc;
   HIP_TRY(ctx, hipStreamSynchronize(s));
+  wp_select(stats, n_samples, comps, n_refs, bd, d, weight, offset, h, wp, info);
+  return HMME_OK;
+}
 
+// what both entry points refuse of their planes: cur = the comps planes of the current picture, refs = comps per reference, all of this
+// context, of one bit depth and of the current picture's size, Cb and Cr half of it each way (chroma_size: what the hmme_predict_chroma_*
+// calls ask of their planes).  Fills planes[c] = cur[c], planes[comps (1 + r) + c] = refs[comps r + c]
+int wp_estimate_args(hmme_ctx* ctx, const char* who, const hmme_plane* const* cur, const hmme_plane* const* refs, int comps, int n_refs,
+                     const hmme_plane** planes) {
+  if (!cur || !refs) return fail(ctx, HMME_ERR_ARG, "%s: null argument", who);
+  if (n_refs < 1 || n_refs > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d references outside 1..%d", who, n_refs, hmme::kMaxRefs);
+  const int n_planes = comps * (1 + n_refs);
+  for (int i = 0; i < n_planes; ++i) {
+    planes[i] = i < comps ? cur[i] : refs[i - comps];
+    if (!planes[i]) return fail(ctx, HMME_ERR_ARG, "%s: null plane", who);
+    if (planes[i]->ctx != ctx) return fail(ctx, HMME_ERR_ARG, "%s: plane belongs to another context", who);
+  }
+  const int w = planes[0]->width, h = planes[0]->height, bd = planes[0]->bit_depth;
+  for (int i = 0; i < n_planes; i += comps) {
+    if (planes[i]->width != w || planes[i]->height != h)
+      return fail(ctx, HMME_ERR_ARG, "%s: reference %d is %d x %d, the current picture %d x %d", who, i / comps - 1, planes[i]->width, planes[i]->height, w, h);
+    const int rc = comps == 3 ? chroma_size(ctx, who, planes + i + 1, 2, w, h) : HMME_OK;
+    if (rc) return rc;
+  }
+  for (int i = 0; i < n_planes; ++i)
+    if (planes[i]->bit_depth != bd) return fail(ctx, HMME_ERR_ARG, "%s: planes of %d and %d bits in one call", who, bd, planes[i]->bit_depth);
+  return HMME_OK;
+}
+// what the two hooks below refuse of a call's shape
+bool wp_hook_shape(const int64_t* n_samples, int comps, int n_refs, int bd, int d) {
+  if (!n_samples || (comps != 1 && comps != 3) || n_refs < 1 || n_refs > hmme::kMaxRefs || bd < 8 || bd > 12 || d < 3 || d > 7) return false;
+  for (int c = 0; c < comps; ++c)
+    if (n_samples[c] < 1) return false;
+  return true;
+}
+}  // namespace
+
+int hmme_test_wp_parameters(const int64_t* stats, const int64_t* n_samples, int comps, int n_refs, int bit_depth, int log2_denom_start, int* log2_denom,
+                            int* weight, int* offset) {
+  if (!stats || !log2_denom || !weight || !offset || !wp_hook_shape(n_samples, comps, n_refs, bit_depth, log2_denom_start)) return HMME_ERR_ARG;
+  wp_parameters(stats, n_samples, comps, n_refs, bit_depth, log2_denom_start, log2_denom, weight, offset);
+  return HMME_OK;
+}
+int hmme_test_wp_select(const int64_t* stats, const int64_t* n_samples, int comps, int n_refs, int bit_depth, int log2_denom, const int* weight,
+                        const int* offset, const uint64_t* sums, hmme_weight* out_wp, hmme_wp_info* out_info) {
+  if (!stats || !weight || !offset || !sums || !out_wp || !wp_hook_shape(n_samples, comps, n_refs, bit_depth, log2_denom)) return HMME_ERR_ARG;
+  wp_select(stats, n_samples, comps, n_refs, bit_depth, log2_denom, weight, offset, (const unsigned long long*)sums, out_wp, out_info);
+  return HMME_OK;
+}
+
+int hmme_plane_stats(const hmme_plane* pl, int64_t* dc_sum, int64_t* ac) {
+  if (!pl) return HMME_ERR_ARG;
+  hmme_ctx* ctx = pl->ctx;
+  if (!dc_sum || !ac) return fail(ctx, HMME_ERR_ARG, "hmme_plane_stats: null output");
+  const int rc = collect_stats(ctx, &pl, 1, ctx->stream);
+  if (rc) return rc;
+  *dc_sum = pl->stats_dc; *ac = pl->stats_ac;
+  return HMME_OK;
+}
+
+int hmme_wp_estimate(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, int log2_denom_start, hmme_weight* out_wp,
+                     hmme_wp_info* out_info) {
+  static const char* const who = "hmme_wp_estimate";
+  if (!ctx) return HMME_ERR_ARG;
+  if (!out_wp) return fail(ctx, HMME_ERR_ARG, "%s: null output", who);
+  if (log2_denom_start < 3 || log2_denom_start > 7) return fail(ctx, HMME_ERR_ARG, "%s: log2_denom_start %d outside 3..7", who, log2_denom_start);
+  const hmme_plane* planes[hmme::kMaxRefs + 1];
+  const int rc = wp_estimate_args(ctx, who, &cur, refs, 1, n_refs, planes);
+  return rc ? rc : wp_estimate(ctx, who, planes, 1, n_refs, log2_denom_start, out_wp, out_info);
+}
+
+// the estimator joint over Y, Cb, Cr (the rule: include/hmme.h)
+int hmme_wp_estimate_420(hmme_ctx* ctx, const hmme_plane* const* cur, const hmme_plane* const* refs, int n_refs, int log2_denom_start,
+                         hmme_weight* out_wp_luma, hmme_weight* out_wp_chroma, hmme_wp_info* out_info) {
+  static const char* const who = "hmme_wp_estimate_420";
+  if (!ctx) return HMME_ERR_ARG;
+  if (!out_wp_luma || !out_wp_chroma) return fail(ctx, HMME_ERR_ARG, "%s: null output", who);
+  if (log2_denom_start < 3 || log2_denom_start > 7) return fail(ctx, HMME_ERR_ARG, "%s: log2_denom_start %d outside 3..7", who, log2_denom_start);
+  const hmme_plane* planes[hmme::kMaxSetPlanes];
+  int rc = wp_estimate_args(ctx, who, cur, refs, 3, n_refs, planes);
+  if (rc) return rc;
+  hmme_weight wp[hmme::kMaxSetPairs];
+  rc = wp_estimate(ctx, who, planes, 3, n_refs, log2_denom_start, wp, out_info);
+  if (rc) return rc;
   for (int r = 0; r < n_refs; ++r) {
-    int64_t sad_wp[3], sad_nowp[3], sum_wp = 0, sum_nowp = 0;   // every component divided by its own size (:350) before they are added (:301-302)
-    for (int c = 0; c < 3; ++c) {
-      sad_wp[c] = (int64_t)hs[2 * (3 * r + c)] / n_samples[c];
-      sad_nowp[c] = (int64_t)(hs[2 * (3 * r + c) + 1] << d) / n_samples[c];
-      sum_wp += sad_wp[c]; sum_nowp += sad_nowp[c];
-    }
-    const double ratio = (double)sum_wp / (double)sum_nowp;   // :305 -- NaN keeps the weights present, +inf disables them, as in hmme_wp_estimate
-    const int present = ratio >= 0.99 ? 0 : 1;               // DTHRESH (:46); :306-314: all three components together
-    for (int c = 0; c < 3; ++c) {
-      const int i = 3 * r + c;
-      if (!present) { weight[i] = 1 << d; offset[i] = 0; }
-      const hmme_weight wp = {weight[i], offset[i] * (1 << (bd - 8)), d, d ? 1 << (d - 1) : 0};   // TComSlice::initWpScaling (TComSlice.cpp:1487-1512)
-      if (c == 0) out_wp_luma[r] = wp; else out_wp_chroma[2 * r + c - 1] = wp;
-      if (!out_info) continue;
-      hmme_wp_info& o = out_info[i];
-      o.cur_dc_sum = cur[c]->stats_dc; o.cur_ac = cur[c]->stats_ac; o.ref_dc_sum = refs[i]->stats_dc; o.ref_ac = refs[i]->stats_ac;
-      o.sad_wp = sad_wp[c]; o.sad_nowp = sad_nowp[c];
-      o.log2_denom = d; o.weight = weight[i]; o.offset = offset[i];
-      o.present = present;
-      if (c == 0) {
-        o.served_search = hmme_weight_check(bd, &wp, 0) == HMME_OK ? 1 : 0;
-        o.served_refine = hmme_weight_check(bd, &wp, 1) == HMME_OK ? 1 : 0;
-      } else {   // what predict_args / frame_checks ask of a component's weight in the hmme_predict_chroma_* calls
-        char msg[256];
-        o.served_search = o.served_refine = other_weight_eval(bd, &wp, nullptr, nullptr, msg, sizeof msg) == HMME_OK ? 1 : 0;
-      }
-    }
+    out_wp_luma[r] = wp[3 * r];
+    out_wp_chroma[2 * r] = wp[3 * r + 1]; out_wp_chroma[2 * r + 1] = wp[3 * r + 2];
   }
   return HMME_OK;
 }
@@ -4061,19 +4018,20 @@ int hmme_test_time_wp_estimate_passes(hmme_ctx* ctx, const hmme_plane* cur, cons
                                       int reps, float* stats_ms, float* sad_ms) {
   if (!ctx) return HMME_ERR_ARG;
   if (!wp || !stats_ms || !sad_ms || reps < 1 || wp->shift < 0 || wp->shift > 7) return fail(ctx, HMME_ERR_ARG, "hmme_test_time_wp_estimate_passes: bad argument");
-  const hmme_plane* planes[kWpStatPlanes];
-  int rc = wp_estimate_args(ctx, "hmme_test_time_wp_estimate_passes", cur, refs, n_refs, planes);
+  const hmme_plane* planes[hmme::kMaxRefs + 1];
+  int rc = wp_estimate_args(ctx, "hmme_test_time_wp_estimate_passes", &cur, refs, 1, n_refs, planes);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   rc = planes_read_begin(ctx, planes, 1 + n_refs, s);
   if (rc) return rc;
-  hmme::MeWpSad a = {};
+  hmme::MeWpSadSet a = {};
   for (int r = 0; r < n_refs; ++r) { a.weight[r] = wp->w0; a.offset[r] = wp->offset * (1 << wp->shift); a.log2_denom[r] = wp->shift; }
-  const hipError_t e = hipMemsetAsync(ctx->buf[kWpEst].as<unsigned long long>(), 0, sizeof(unsigned long long) * kWpStatWords, s);
+  unsigned long long* d_sums = ctx->buf[kWpEst].as<unsigned long long>();
+  const hipError_t e = hipMemsetAsync(d_sums, 0, sizeof(unsigned long long) * kWpSetWords, s);
   if (e != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "hmme_test_time_wp_estimate_passes: %s", hipGetErrorString(e));
   if (rc == HMME_OK)
-    rc = time_reps(ctx, s, reps, "the estimator's passes", [&] { return launch_stats(ctx, cur, ctx->buf[kWpEst].as<unsigned long long>(), s); }, stats_ms,
-                   [&] { return launch_wp_sad(ctx, cur, refs, n_refs, a, ctx->buf[kWpEst].as<unsigned long long>() + kWpStatSad, s); }, sad_ms);
+    rc = time_reps(ctx, s, reps, "the estimator's passes", [&] { return launch_stats_set(ctx, planes, 1, d_sums, s); }, stats_ms,
+                   [&] { return launch_wp_sad_set(ctx, planes, planes + 1, 1, n_refs, a, d_sums + kWpSetSad, s); }, sad_ms);
   return planes_read_end(ctx, planes, 1 + n_refs, s, rc);
 }
 

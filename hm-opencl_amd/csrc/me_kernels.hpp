@@ -3393,16 +3393,22 @@ me_predict_chroma_kernel(MeChromaSrc src, int ref_pitch, const int16_t* __restri
   }
 }
 
-// ---- estimating explicit weighted-prediction parameters (hmme_plane_stats / hmme_wp_estimate) ---------------------------------------------
+// ---- estimating explicit weighted-prediction parameters (hmme_plane_stats / hmme_wp_estimate / hmme_wp_estimate_420) -------------------------
 // The whole-picture reductions of HM's WeightPredAnalysis (WeightPredAnalysis.cpp:67-120 xCalcACDCParamSlice, :324-351 xCalcSADvalueWP) over
-// the PICTURE AREA of padded planes -- no margin, no replicated edge.  Geometry shared by both kernels: a workgroup of 256 lanes is
-// (256 >> lpr_log2) rows of (1 << lpr_log2) lanes, lpr = the smallest power of two that covers a row's 16-byte vectors (at most 256), so narrow
-// pictures keep their lanes busy and nothing is divided; rows advance by gridDim.x * rows-per-workgroup, a row's vectors by lpr.  The picture's
-// left edge is 128 samples into a pitch that is a multiple of 256 bytes, so every vector is a 16-byte aligned load; the last vector of a row
-// may reach into the right margin (128 samples: always inside the row) and is masked to the row's bytes.
+// the PICTURE AREA of padded planes -- no margin, no replicated edge -- for SEVERAL planes of different sizes in one launch: blockIdx.y names
+// a plane (statistics) or a pair of planes (SAD) of a table passed by value, like RefSet.  A luma call is a set of one plane, of 1 + n planes or
+// of n pairs; a 4:2:0 call with 16 references has 51 planes and 48 pairs.
+// Geometry shared by both kernels: a workgroup of 256 lanes is (256 >> lpr_log2) rows of (1 << lpr_log2) lanes, lpr = the smallest power of two
+// that covers a row's 16-byte vectors (at most 256), so narrow pictures keep their lanes busy and nothing is divided; rows advance by
+// gridDim.x * rows-per-workgroup, a row's vectors by lpr.  Every plane brings its own lpr_log2, so rows per workgroup differ between the
+// planes of a launch.  The picture's left edge is 128 samples into a pitch that is a multiple of 256 bytes, so every vector is a 16-byte
+// aligned load; the last vector of a row may reach into the right margin (128 samples: always inside the row) and is masked to the row's bytes.
+// gridDim.x is sized for the plane that needs most workgroups; a workgroup whose first row lies beyond its (smaller) plane has nothing to add
+// and LEAVES AS A WHOLE, before any barrier (the one of the pass-1 mean, those of me_block_sum_u64): the test is on blockIdx and the plane's
+// table entry only, the same for all 256 lanes.  The sums are zero on entry, so a sum nobody adds to is the right one.
 // Sums: one 32-bit partial per vector (bounds at the kernels), widened into a 64-bit lane sum right away; lanes are folded wave by wave with a
 // butterfly, the four wave sums through LDS, and ONE 64-bit atomic add per workgroup and sum reaches memory.  Integer adds only: the result
-// does not depend on the order of workgroups.
+// does not depend on the order of workgroups, nor on the grid.
 
 // the bytes of dword k that belong to a row of which nb (1..15) bytes lie in the vector
 __device__ __forceinline__ uint32_t me_tail_mask(int nb, int k) {
@@ -3430,128 +3436,20 @@ __device__ __forceinline__ void me_block_sum_u64(uint64_t (&v)[NSUM], unsigned l
     atomicAdd(out + threadIdx.x, (unsigned long long)(s_part[0][threadIdx.x] + s_part[1][threadIdx.x] + s_part[2][threadIdx.x] + s_part[3][threadIdx.x]));
 }
 
-// xCalcACDCParamSlice in two launches on one stream.  PASS 0: sums[0] += sum of the samples (iOrgDC; v_sad against 0).  PASS 1: reads sums[0]
-// as pass 0 left it, normDC = (iOrgDC + (N >> 1)) / N (:99), sums[1] += sum of |sample - normDC| (iOrgAC; v_sad against the replicated mean).
-// A vector's partial is at most 16 * 255 / 8 * 4095.
-template <typename T, int PASS>
-__global__ void __launch_bounds__(256)
-me_plane_stats_kernel(const uint8_t* __restrict__ origin, int pitch, int w, int h, int lpr_log2, unsigned long long* sums) {
-  __shared__ uint32_t s_mean;
-  uint32_t mean = 0;   // the mean in every sample of a dword
-  if (PASS == 1) {
-    if (threadIdx.x == 0) {
-      const unsigned long long n = (unsigned long long)w * (unsigned long long)h;
-      s_mean = (uint32_t)((sums[0] + (n >> 1)) / n);
-    }
-    __syncthreads();
-    mean = s_mean * (sizeof(T) == 1 ? 0x01010101u : 0x00010001u);
-  }
-  const int lpr = 1 << lpr_log2, lx = threadIdx.x & (lpr - 1), ry = threadIdx.x >> lpr_log2, rpb = 256 >> lpr_log2;
-  const int row_bytes = w * (int)sizeof(T), nvec = (row_bytes + 15) >> 4;
-  uint64_t acc[1] = {0};
-  for (int y = blockIdx.x * rpb + ry; y < h; y += gridDim.x * rpb) {
-    const uint8_t* row = origin + (long)y * pitch;
-    for (int v = lx; v < nvec; v += lpr) {
-      const uint4 in = *(const uint4*)(row + 16 * v);
-      const uint32_t d[4] = {in.x, in.y, in.z, in.w};
-      const int nb = row_bytes - 16 * v;
-      uint32_t part = 0;
-      if (nb >= 16) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) part = me_sad_packed<T>(d[k], mean, part);
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const uint32_t m = me_tail_mask(nb, k);
-          part = me_sad_packed<T>(d[k] & m, mean & m, part);
-        }
-      }
-      acc[0] += part;
-    }
-  }
-  me_block_sum_u64<1>(acc, sums + PASS);
-}
-
-// xCalcSADvalueWP for one current picture against up to kMaxRefs references in one launch (blockIdx.y = reference), each with its own
-// (weight, offset, log2Denom); offset arrives as HM's term iOffset << (log2Denom + bitDepth - 8).  Per reference two sums:
-//   sums[2 r]     += sum of |(org << d) - (ref * weight + offset)|      (:344; int32 multiply-add)
-//   sums[2 r + 1] += sum of |org - ref|                                 (packed SAD; HM's unweighted sum is this << d exactly)
-// so one read of the two planes serves both of HM's calls.  Bounds: hmme_wp_estimate hands over weight in [0, 1920] (dWeight clipped to 15, d <= 7),
-// |offset| <= 128 << 11 and d <= 7, so a 12-bit sample's term is below 4095 * 1920 + 2^19 + 2^18 < 2^23 and a vector's partial (8 of them; 16 at
-// 8 bit, each below 2^19) below 2^26 -- far inside 32 bits; the lane sums are 64-bit.
-struct MeWpSad { int weight[kMaxRefs], offset[kMaxRefs], log2_denom[kMaxRefs]; };
-
-template <typename T>
-__global__ void __launch_bounds__(256)
-me_wp_sad_kernel(const uint8_t* __restrict__ cur, RefSet refs, int pitch, int w, int h, int lpr_log2, MeWpSad a, unsigned long long* sums) {
-  constexpr int N = 16 / (int)sizeof(T), PER = 4 / (int)sizeof(T);   // samples per vector / per dword
-  const int r = blockIdx.y;
-  const uint8_t* __restrict__ ref = refs.base[r];
-  const int wt = a.weight[r], off = a.offset[r], d = a.log2_denom[r];
-  const int lpr = 1 << lpr_log2, lx = threadIdx.x & (lpr - 1), ry = threadIdx.x >> lpr_log2, rpb = 256 >> lpr_log2;
-  const int row_bytes = w * (int)sizeof(T), nvec = (row_bytes + 15) >> 4;
-  uint64_t acc[2] = {0, 0};
-  auto sample = [](uint32_t dw, int j) -> int { return sizeof(T) == 1 ? (int)((dw >> (8 * j)) & 0xffu) : (int)((dw >> (16 * j)) & 0xffffu); };
-  for (int y = blockIdx.x * rpb + ry; y < h; y += gridDim.x * rpb) {
-    const long row = (long)y * pitch;
-    for (int v = lx; v < nvec; v += lpr) {
-      const uint4 o4 = *(const uint4*)(cur + row + 16 * v), r4 = *(const uint4*)(ref + row + 16 * v);
-      const uint32_t o[4] = {o4.x, o4.y, o4.z, o4.w}, q[4] = {r4.x, r4.y, r4.z, r4.w};
-      const int nb = row_bytes - 16 * v;
-      uint32_t pw = 0, pn = 0;
-      if (nb >= 16) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          pn = me_sad_packed<T>(o[k], q[k], pn);
-#pragma unroll
-          for (int j = 0; j < PER; ++j) {
-            const int t = (sample(o[k], j) << d) - (sample(q[k], j) * wt + off);
-            pw += (uint32_t)(t < 0 ? -t : t);
-          }
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const uint32_t m = me_tail_mask(nb, k);
-          pn = me_sad_packed<T>(o[k] & m, q[k] & m, pn);
-#pragma unroll
-          for (int j = 0; j < PER; ++j) {
-            const int t = (sample(o[k], j) << d) - (sample(q[k], j) * wt + off);
-            if ((4 * k + j * (int)sizeof(T)) < nb) pw += (uint32_t)(t < 0 ? -t : t);
-          }
-        }
-      }
-      acc[0] += pw;
-      acc[1] += pn;
-    }
-  }
-  me_block_sum_u64<2>(acc, sums + 2 * r);
-}
-
-// ---- the plane-set forms (hmme_wp_estimate_420) ---------------------------------------------------------------------------------------------
-// The two reductions above over SEVERAL planes of different sizes in one launch: blockIdx.y names a plane (statistics) or a pair of planes
-// (SAD) of a table passed by value, like RefSet.  A 4:2:0 call with 16 references has 51 planes and 48 pairs; one launch each replaces 51 and
-// 3.  Geometry and arithmetic are those of the single-plane kernels -- 16-byte vector loads from the aligned picture edge, the last vector of
-// a row masked to the row's bytes, packed SADs, a 32-bit partial per vector into 64-bit lane sums, me_block_sum_u64 -- but every plane brings
-// its own lpr_log2, so rows per workgroup differ between the planes of a launch.  gridDim.x is sized for the plane that needs most
-// workgroups; a workgroup whose first row lies beyond its (smaller) plane has nothing to add and LEAVES AS A WHOLE, before any barrier:
-// the test is on blockIdx and the plane's table entry only, the same for all 256 lanes.  The sums are zero on entry, so a sum nobody adds to
-// is the right one.
 constexpr int kMaxSetPlanes = 3 * (kMaxRefs + 1);   // Y, Cb, Cr of the current picture and of kMaxRefs references
 constexpr int kMaxSetPairs = 3 * kMaxRefs;
 struct MePlaneDesc { const uint8_t* origin; int pitch, w, h, lpr_log2; };
 struct MePlaneSet { MePlaneDesc p[kMaxSetPlanes]; };
 
-// sums[2 p] / sums[2 p + 1] = sample sum / AC of plane p, as me_plane_stats_kernel leaves them for one plane: PASS 1 reads its own plane's
-// PASS 0 sum.  All planes of a launch hold samples of type T (one bit depth per call).  A vector's partial is at most 16 * 255 / 8 * 4095.
+// xCalcACDCParamSlice of one plane of a launch in two launches on one stream, sums[0] / sums[1] = its sample sum / AC.  PASS 0: sums[0] += sum
+// of the samples (iOrgDC; v_sad against 0).  PASS 1: reads the plane's sum as pass 0 left it, normDC = (iOrgDC + (N >> 1)) / N (:99),
+// sums[1] += sum of |sample - normDC| (iOrgAC; v_sad against the replicated mean).  All planes of a launch hold samples of type T (one bit
+// depth per call).  A vector's partial is at most 16 * 255 / 8 * 4095.
 template <typename T, int PASS>
-__global__ void __launch_bounds__(256)
-me_plane_set_stats_kernel(MePlaneSet set, unsigned long long* sums) {
+__device__ __forceinline__ void me_plane_stats_body(const MePlaneDesc& pd, unsigned long long* sums) {
   __shared__ uint32_t s_mean;
-  const MePlaneDesc pd = set.p[blockIdx.y];
   const int lpr = 1 << pd.lpr_log2, lx = threadIdx.x & (lpr - 1), ry = threadIdx.x >> pd.lpr_log2, rpb = 256 >> pd.lpr_log2;
   if ((int)blockIdx.x * rpb >= pd.h) return;   // the whole workgroup: no lane has a row
-  sums += 2 * blockIdx.y;
   uint32_t mean = 0;   // the mean in every sample of a dword
   if (PASS == 1) {
     if (threadIdx.x == 0) {
@@ -3585,14 +3483,32 @@ me_plane_set_stats_kernel(MePlaneSet set, unsigned long long* sums) {
   }
   me_block_sum_u64<1>(acc, sums + PASS);
 }
+// plane p = blockIdx.y of the table: sums[2 p] / sums[2 p + 1]
+template <typename T, int PASS>
+__global__ void __launch_bounds__(256)
+me_plane_set_stats_kernel(MePlaneSet set, unsigned long long* sums) {
+  me_plane_stats_body<T, PASS>(set.p[blockIdx.y], sums + 2 * blockIdx.y);
+}
+// a set of ONE plane without the table: the 1.2 KB argument costs a launch of a single 2160p plane 0.25 us of its 11.5
+template <typename T, int PASS>
+__global__ void __launch_bounds__(256)
+me_plane_stats_kernel(MePlaneDesc pd, unsigned long long* sums) {
+  me_plane_stats_body<T, PASS>(pd, sums);
+}
 
-// xCalcSADvalueWP for up to kMaxSetPairs pairs (current plane, reference plane) in one launch: pair y = 3 * reference + component reads
-// component y % 3 of the current picture (its size, pitch and lpr_log2 are the pair's: a reference plane has its component's size and so
-// its pitch) with the pair's own (weight, offset term, log2Denom).  sums[2 y] / sums[2 y + 1] as me_wp_sad_kernel's.  Its bounds hold for
-// chroma unchanged: hmme_wp_estimate_420 hands over weight in [0, 1920] (dWeight clipped to 15, d <= 7) and a chroma offset that ends in
-// Clip3(-128, 127) like luma's (WeightPredAnalysis.cpp:244), so |offset term| <= 128 << 11 = 2^18, a sample's term is below 2^23 and a
-// vector's partial below 2^26.
+// xCalcSADvalueWP for up to kMaxSetPairs pairs (current plane, reference plane) in one launch: pair y = comps * reference + component reads
+// component y % comps of the current picture -- comps = 1 (a luma call: every pair against cur[0]) or 3 -- whose size, pitch and lpr_log2 are
+// the pair's (a reference plane has its component's size and so its pitch), with the pair's own (weight, offset, log2Denom); offset arrives as
+// HM's term iOffset << (log2Denom + bitDepth - 8).  comps is a kernel argument and y is blockIdx.y: the plane is the same for all 256 lanes.
+// Per pair two sums:
+//   sums[2 y]     += sum of |(org << d) - (ref * weight + offset)|      (:344; int32 multiply-add)
+//   sums[2 y + 1] += sum of |org - ref|                                 (packed SAD; HM's unweighted sum is this << d exactly)
+// so one read of the two planes serves both of HM's calls.  Bounds: the estimator hands over weight in [0, 1920] (dWeight clipped to 15,
+// d <= 7) and an offset, luma's or chroma's, that ends in Clip3(-128, 127) (WeightPredAnalysis.cpp:244, :248), so |offset term| <= 128 << 11 =
+// 2^18 at d <= 7; a 12-bit sample's term is below 4095 * 1920 + 2^19 + 2^18 < 2^23 and a vector's partial (8 of them; 16 at 8 bit, each below
+// 2^19) below 2^26 -- far inside 32 bits; the lane sums are 64-bit.
 struct MeWpSadSet {
+  int comps;
   MePlaneDesc cur[3];
   const uint8_t* ref[kMaxSetPairs];
   int weight[kMaxSetPairs], offset[kMaxSetPairs], log2_denom[kMaxSetPairs];
@@ -3603,7 +3519,7 @@ __global__ void __launch_bounds__(256)
 me_wp_sad_set_kernel(MeWpSadSet a, unsigned long long* sums) {
   constexpr int PER = 4 / (int)sizeof(T);   // samples per dword
   const int pair = blockIdx.y;
-  const MePlaneDesc pd = a.cur[pair % 3];
+  const MePlaneDesc pd = a.cur[a.comps == 1 ? 0 : pair % 3];
   const int lpr = 1 << pd.lpr_log2, lx = threadIdx.x & (lpr - 1), ry = threadIdx.x >> pd.lpr_log2, rpb = 256 >> pd.lpr_log2;
   if ((int)blockIdx.x * rpb >= pd.h) return;   // the whole workgroup: no lane has a row
   const uint8_t* __restrict__ cur = pd.origin;

@@ -1149,8 +1149,8 @@ int hmme_wp_estimate(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* con
  * (W / 2) x (H / 2), any plane whose bit depth differs from cur[0]'s, a reference luma plane of another size.
  * Ordering and caching as hmme_wp_estimate: the context's private stream, planes read after their fills and recorded for refills; the
  * per-plane sums are the ones hmme_plane_stats keeps in the planes (every fill drops them), so a picture that was a reference of the previous
- * call costs nothing the second time.  On the device the planes without cached sums go through two launches together and all
- * (reference, component) pairs through one (me_kernels.hpp, "the plane-set forms"). */
+ * call costs nothing the second time.  On the device, in this call and in hmme_wp_estimate alike, the planes without cached sums go through
+ * two launches together and all (reference, component) pairs through one (me_kernels.hpp, me_plane_set_stats_kernel / me_wp_sad_set_kernel). */
 int hmme_wp_estimate_420(hmme_ctx* ctx, const hmme_plane* const* cur, const hmme_plane* const* refs, int n_refs, int log2_denom_start,
                          hmme_weight* out_wp_luma, hmme_weight* out_wp_chroma, hmme_wp_info* out_info);
 

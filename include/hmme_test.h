@@ -63,11 +63,25 @@ int hmme_test_time_weight_passes(hmme_ctx* ctx, const hmme_plane* cur, const hmm
 int hmme_test_time_bipred_origin(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* other, const void* d_other_mv, int mv_per_ctu, void* stream,
                                  int reps, float* avg_ms);
 
-/* average device time in ms of the estimator's passes on their own, `reps` back-to-back launches each on `stream`: *stats_ms = the two launches
- * of me_plane_stats_kernel over `cur`, *sad_ms = me_wp_sad_kernel of `cur` against the n_refs references, every one with weight wp->w0, offset
- * wp->offset (8-bit units) and denominator wp->shift (<= 7) */
+/* average device time in ms of the estimator's passes on their own, `reps` back-to-back launches each on `stream`, through the launchers every
+ * estimator call uses: *stats_ms = the two statistics launches over a set of one plane, `cur` (me_plane_stats_kernel); *sad_ms = me_wp_sad_set_kernel
+ * over n_refs pairs, `cur` against each reference, every one with weight wp->w0, offset wp->offset (8-bit units) and denominator wp->shift (<= 7) */
 int hmme_test_time_wp_estimate_passes(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_weight* wp, void* stream,
                                       int reps, float* stats_ms, float* sad_ms);
+
+/* The estimator's arithmetic on its own, comps = 1 what hmme_wp_estimate runs and comps = 3 what hmme_wp_estimate_420 runs (hmme.hip wp_parameters /
+ * wp_select; host arithmetic, needs no device).  Plane i of a call is component i % comps of the current picture (i < comps) or of reference
+ * i / comps - 1: stats[2 i], stats[2 i + 1] = its (dc_sum, ac) as hmme_plane_stats gives them, n_samples[c] = the sample count of component c;
+ * entry comps * r + c belongs to component c of reference r.  HMME_ERR_ARG: a null argument (out_info may be null), comps other than 1 or 3,
+ * n_refs outside 1..16, bit_depth outside 8..12, a denominator outside 3..7, a sample count below 1.
+ * hmme_test_wp_parameters: steps 1 and 2 of the rule in include/hmme.h -> *log2_denom = d and (weight, clipped offset) of every entry. */
+int hmme_test_wp_parameters(const int64_t* stats, const int64_t* n_samples, int comps, int n_refs, int bit_depth, int log2_denom_start, int* log2_denom,
+                            int* weight, int* offset);
+/* hmme_test_wp_select: steps 3 and 4 on those parameters and the two sums per entry as me_wp_sad_set_kernel leaves them -- sums[2 i] = the sum of
+ * |(org << d) - (ref * weight + (offset << (d + bit_depth - 8)))|, sums[2 i + 1] = the sum of |org - ref| -> out_wp[i] and, where given,
+ * out_info[i] of every entry */
+int hmme_test_wp_select(const int64_t* stats, const int64_t* n_samples, int comps, int n_refs, int bit_depth, int log2_denom, const int* weight,
+                        const int* offset, const uint64_t* sums, hmme_weight* out_wp, hmme_wp_info* out_info);
 
 #ifdef __cplusplus
 }

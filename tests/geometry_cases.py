@@ -15,6 +15,8 @@ stores go only to samples inside -- and none of it assumes a multiple of anythin
       x 18        luma plane that ends 2k samples past a vector boundary in the same launch
     2048 x 50     4:2:0 with 16 references at 8 bit: 51 planes side by side cap a launch at 20 row blocks per plane, luma has 25 (two rounds:
                   the strided row loop iterates twice) and chroma 7 (its workgroups beyond block 6 leave at once); stat_grid below shows it
+    1033 x 66     luma alone with 16 references at 10 bit: rows of 130 vectors (one row per workgroup, the last vector holds 2 of 16 bytes); 17
+                  planes / 16 pairs side by side cap a launch at 60 / 64 row blocks, the picture has 66 (two rounds of 33 workgroups)
 
 Host arithmetic only; the window rule is restated here from TEncSearch::xSetSearchRange and TComDataCU::clipMv in Python integers."""
 import numpy as np
@@ -31,6 +33,7 @@ STATS_SIZES = tuple((64 + k, 9) for k in range(1, 16))                    # rows
 STATS_SIZES_420 = tuple((128 + 2 * k, 18) for k in range(1, 16))           # luma; chroma (64 + k) x 9: STATS_SIZES, luma 2k samples past a vector boundary
 STAT_BLOCKS = 1024                                                        # kWpStatBlocks of hmme.hip
 ROUNDS_420 = (2048, 50, 16)                                               # luma width, height, references of the 8-bit case whose luma rows take two rounds
+ROUNDS_LUMA = (1033, 66, 16)                                              # width, height, references of the 10-bit luma case whose rows take two rounds
 FAR = 4 * 400                                                             # quarter pels: beyond clipMv's range at every size but the slivers' long side
 DIRECTIONS = ((-1, -1), (0, -1), (1, -1), (-1, 0), (1, 0), (-1, 1), (0, 1), (1, 1))
 FUZZ_SEEDS = tuple(range(3000, 3010))

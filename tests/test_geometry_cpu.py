@@ -60,6 +60,19 @@ def test_the_plane_set_launches_take_the_rounds_the_cases_claim():
                                                                                                   for k, (w, h) in enumerate(gc.STATS_SIZES_420, 1))
 
 
+def test_the_luma_set_launches_take_the_rounds_the_case_claims():
+    """hmme_wp_estimate on 1033 x 66 at 10 bit with 16 distinct references: the statistics of 17 planes and the SADs of 16 pairs share a launch
+    each, both capped below the picture's 66 row blocks -- two rounds of 33 workgroups, so both row loops iterate twice -- and a row's last
+    vector holds 2 of 16 bytes"""
+    w, h, n_refs = gc.ROUNDS_LUMA
+    for n_y, cap in ((1 + n_refs, 60), (n_refs, 64)):
+        g = gc.stat_grid(w, h, 2, n_y)
+        assert (g["lpr_log2"], g["rows_per_block"], g["row_blocks"], g["cap"], g["rounds"], g["blocks"]) == (8, 1, 66, cap, 2, 33), n_y
+        assert g["blocks"] * g["rows_per_block"] < h                              # a second iteration of the row loop has rows to read
+    assert (2 * w + 15) // 16 == 130 and 2 * w - 16 * 129 == 2
+    assert gc.stat_grid(w, h, 2, 1)["rounds"] == 1                              # a plane on its own (hmme_plane_stats) needs one
+
+
 def test_windows_are_clipped_as_the_table_states(api, oracle_lib):
     hmo = oracle_lib.oracle()
     win = [C.c_int() for _ in range(4)]

@@ -762,6 +762,23 @@ def test_wp_estimate_420_over_two_rounds_of_workgroups(engine):
     assert len({(r[0]["ref_ac"], r[0]["sad_nowp"]) for r in es}) == n_refs and all(x["sad_nowp"] > 0 for r in es for x in r)
 
 
+def test_wp_estimate_over_two_rounds_of_workgroups(engine):
+    """16 distinct references of 1033 x 66 at 10 bit: the luma call's 17 planes / 16 pairs side by side cap a launch at 60 / 64 row blocks, the
+    picture has 66 -- both row loops iterate twice -- and a row's last vector holds 2 of 16 bytes (tests/test_geometry_cpu.py asserts this
+    arithmetic against geometry_cases.stat_grid).  Every sum, intermediate and weight against the model"""
+    from test_gpu_wp_estimate import check_estimate, fade, smooth
+    w, h, n_refs = gc.ROUNDS_LUMA
+    stats, sad = gc.stat_grid(w, h, 2, 1 + n_refs), gc.stat_grid(w, h, 2, n_refs)
+    assert stats["rounds"] == sad["rounds"] == 2 and stats["blocks"] == sad["blocks"] and stats["rows_per_block"] == 1
+    cur = smooth(w, h, 10, seed=5170)
+    second = np.arange(h)[:, None] >= stats["blocks"]
+    refs = []
+    for i in range(n_refs):                                                      # the fade of reference i acts on the rows of the second round alone, or of the first
+        refs.append(np.where(second if i % 2 else ~second, fade(cur, 0.6 + 0.05 * i, 2 * i - 10, 10), cur))
+    want = check_estimate(engine, cur, refs, 10, 7)
+    assert len({(e["ref_ac"], e["sad_nowp"]) for e in want}) == n_refs and all(e["sad_nowp"] > 0 for e in want)
+
+
 # ---- 9: the largest sizes ------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("w,h,bd", [gc.SLIVERS[0] + (8,), gc.SLIVERS[1] + (10,)])
 def test_the_largest_sizes(engine, oracle_lib, hmo, w, h, bd):

@@ -177,9 +177,53 @@ def check_estimate(case, entries_of):
         assert (final[:, :ncomp] == (0, 1, 0, 0)).all()
 
 
+def _model_parameters(stats, sizes, comps, bd, start):
+    """the loop over the denominator (:182-189) around the models' update_parameters -> (d, [(weight, clipped offset)] per entry comps r + c)"""
+    cur, refs = stats[:comps], [stats[i:i + comps] for i in range(comps, len(stats), comps)]
+    d = start
+    while True:
+        if comps == 1:
+            ok, params = wm.update_parameters(cur[0], [r[0] for r in refs], sizes[0], bd, d)
+        else:
+            ok, params = wm420.update_parameters(cur, refs, sizes, bd, d)
+            params = [e for ref in params for e in ref]
+        if ok:
+            return d, params
+        d -= 1
+
+
+def _library_estimate(L, pics, comps, bd, start):
+    """hmme_test_wp_parameters and hmme_test_wp_select of libhmme.so -- the arithmetic of hmme_wp_estimate (comps = 1) and hmme_wp_estimate_420
+    (comps = 3) without its kernels -- on the statistics of wp_estimate_model.plane_stats and on the two raw sums per entry, formed here as the
+    comment at me_wp_sad_set_kernel defines them; what the parameter function gives is compared with the models' update_parameters on the way.
+    -> one dict per entry comps r + c: the fields of hmme_wp_info and "wp", the hmme_weight"""
+    from hmme import api
+    planes = [np.asarray(p).astype(np.int64) for pic in pics for p in (pic if comps == 3 else (pic,))]
+    n_refs, n = len(pics) - 1, comps * (len(pics) - 1)
+    model_stats = [wm.plane_stats(p) for p in planes]
+    sizes = [int(p.size) for p in planes[:comps]]
+    stats, c_sizes = (C.c_int64 * (2 * len(planes)))(*[v for st in model_stats for v in st]), (C.c_int64 * 3)(*sizes)
+    c_d, weight, offset = C.c_int(-1), (C.c_int * n)(), (C.c_int * n)()
+    assert L.hmme_test_wp_parameters(stats, c_sizes, comps, n_refs, bd, start, C.byref(c_d), weight, offset) == 0
+    d = c_d.value
+    assert (d, list(zip(weight, offset))) == _model_parameters(model_stats, sizes, comps, bd, start)
+    sums = (C.c_uint64 * (2 * n))()
+    for i in range(n):
+        org, ref = planes[i % comps], planes[comps + i]
+        sums[2 * i] = int(np.abs((org << d) - (ref * weight[i] + offset[i] * (1 << (d + bd - 8)))).sum())
+        sums[2 * i + 1] = int(np.abs(org - ref).sum())
+    wps, infos = (api.Weight * n)(), (api.WpInfo * n)()
+    assert L.hmme_test_wp_select(stats, c_sizes, comps, n_refs, bd, d, weight, offset, sums, wps, infos) == 0
+    return [dict(infos[i].as_dict(), wp=(wps[i].w0, wps[i].offset, wps[i].shift, wps[i].round)) for i in range(n)]
+
+
 def test_wp_estimate_models_match_reference(reference):
-    """wp_estimate_model.estimate (4:0:0) and wp_estimate_420_model.estimate on fades, identical, unrelated and constant pictures, 12-bit extremes,
-    1, 2 and 4 references and the 2 + 2 split of a B slice; each event the cases were built for occurs in the reference's own answer"""
+    """wp_estimate_model.estimate (4:0:0), wp_estimate_420_model.estimate and the library's own arithmetic (_library_estimate) on fades,
+    identical, unrelated and constant pictures, 12-bit extremes, 1, 2 and 4 references and the 2 + 2 split of a B slice; each event the cases
+    were built for occurs in the reference's own answer"""
+    from hmme import api
+    api.build()
+    L = api.load()
     cases = rt.wp_cases()
     names = {c["name"] for c in cases}
     g = rt.load("ref_wp_estimate")
@@ -193,12 +237,20 @@ def test_wp_estimate_models_match_reference(reference):
                                 lambda: np.concatenate([np.ravel(a) for a in oracle_py.ref_wp_estimate(cur, refs, case["n_l0"], case["n_l1"], case["bd"], case["start"])]))
         assert want.size == 2 * case["table"].size + 2
         assert case["start"] == (7 if case["n_l0"] > 3 else 6)      # HM's own choice (WeightPredAnalysis.cpp:174-180)
-        if case["fmt"] == 400:
+        comps = 3 if case["fmt"] == 420 else 1
+        if comps == 1:
             est = wm.estimate(cur, refs, case["bd"], case["start"])
-            check_estimate(case, lambda r, c: est[r])
+            model = lambda r, c: est[r]
         else:
             est = wm420.estimate(cur, refs, case["bd"], case["start"])
-            check_estimate(case, lambda r, c: est[r][c])
+            model = lambda r, c: est[r][c]
+        check_estimate(case, model)
+        lib = _library_estimate(L, case["pics"], comps, case["bd"], case["start"])
+        check_estimate(case, lambda r, c: lib[comps * r + c])
+        for r in range(len(refs)):
+            for c in range(comps):
+                got, e = lib[comps * r + c], model(r, c)
+                assert {k: got[k] for k in wm.INFO_FIELDS} == {k: e[k] for k in wm.INFO_FIELDS}, (case["name"], r, c, got, e)
 
 
 def test_distortions_match_reference(reference, oracle_lib):

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """cost of estimating explicit weighted-prediction parameters at picture size (device-resident planes), for a 2160p 8-bit and a 2160p 10-bit fade:
 
-  stats_ms            the two launches of me_plane_stats_kernel over one plane (device events around `PASS_REPS` back-to-back repeats)
-  sad_ms[n]           me_wp_sad_kernel, one current picture against n = 1, 4, 16 references (the same)
-  estimate_ms[n]      hmme_wp_estimate end to end on the host clock, statistics cached / not cached (fresh uploads are outside the clock)
+  stats_ms            the two statistics launches over a set of one plane, me_plane_stats_kernel (device events around `PASS_REPS` back-to-back repeats)
+  sad_ms[n]           me_wp_sad_set_kernel, one current picture against n = 1, 4, 16 references: n pairs in one launch (the same)
+  estimate_ms[n]      hmme_wp_estimate end to end on the host clock, statistics cached (1 launch: the SAD pass) / not cached (3: two statistics
+                      launches for all 1 + n planes together, then the SAD pass; fresh uploads are outside the clock); the counts are written
+                      beside the times ("launches")
   host_route_ms       the route it replaces: the picture areas of both planes brought to the host (torch, page-locked target) and the numpy
                       model of tests/wp_estimate_model.py on them; nothing uploaded
   copy_ms             a float4 device copy of the bytes ONE pass over one plane reads (torch copy_ of a 16-byte-element tensor): the bandwidth yardstick
@@ -14,9 +16,9 @@ tools/wp_estimate_rate.py --420 [out.json] measures the estimator of a 4:2:0 sli
 bit), each on the host clock around a call that ends in the call's own wait, with the per-plane sums cached ("cached") and dropped by fresh
 uploads outside the clock ("cold"):
 
-  plane_set_ms[n]     hmme_wp_estimate_420: the plane-set kernels -- cold 2 statistics launches for all 3 (n + 1) planes + 1 SAD launch, cached 1
+  plane_set_ms[n]     hmme_wp_estimate_420: the same two kernels -- cold 2 statistics launches for all 3 (n + 1) planes + 1 SAD launch, cached 1
   composition_ms[n]   what the library offered for the same bytes before that call: hmme_plane_stats on every plane, then one hmme_wp_estimate
-                      per component -- cold 2 launches per plane + 3 SAD launches, cached 3.  (It reads what the 4:2:0 call reads and gives its
+                      per component -- cold 2 launches per plane (each plane a set of one) + 3 SAD launches, cached 3.  (It reads what the 4:2:0 call reads and gives its
                       sums, not its decision: the three calls share neither the denominator nor the ratio.)
 
 The two are timed alternately, repeat by repeat; the launch counts are written beside the times.  Before the clock starts the per-plane sums
@@ -146,7 +148,8 @@ for bd in (8, 10):
     for i, r in enumerate(refs):
         up(r, ref_img if i % 2 == 0 else np.clip(ref_img.astype(np.int64) + i, 0, maxv).astype(dt))
     wp = (48, 10, 6, 32)
-    case = {"bit_depth": bd, "plane_bytes": int(w * h * np.dtype(dt).itemsize), "sad_ms": {}, "estimate_cached_ms": {}, "estimate_uncached_ms": {}}
+    case = {"bit_depth": bd, "plane_bytes": int(w * h * np.dtype(dt).itemsize), "sad_ms": {}, "estimate_cached_ms": {}, "estimate_uncached_ms": {},
+            "launches": {"stats": 2, "sad": 1, "estimate_cached": 1, "estimate_uncached": 3}}
     weights, infos = eng.wp_estimate(pc, refs[:1])
     case["estimate"] = {"weight": list(weights[0]), "present": infos[0].present}
     for _ in range(3):          # warm clock
