@@ -437,11 +437,13 @@ int rows_max16(int pdw) {
 }
 
 // strips of candidate rows so that one strip's window rows fit the LDS budget
-int strips_for(int pdw, int wy_max) {
+constexpr int strips_for(int pdw, int wy_max) {
   int n = 1;
-  while (n < wy_max && lds_bytes16(pdw, (wy_max + n - 1) / n) > kLdsBudget16) ++n;   // bounded: one-row strips always fit
+  while (n < wy_max && lds_bytes16_c(pdw, (wy_max + n - 1) / n) > kLdsBudget16) ++n;   // bounded: one-row strips always fit
   return n;
 }
+// 53 candidate rows fit at the largest pitch, so the tallest window takes 5 strips: the per-CTU deal (ctu_deal) never asks for more workgroups than its job table holds
+static_assert(strips_for(kPdw16Large, 2 * HMME_MAX_SEARCH_RANGE + 1) <= kCallMaxJobs, "the strips the LDS needs fit the per-CTU job table");
 
 // f is called with std::integral_constant<int, PDW> of the compiled pitch `pdw` (pick_pdw16)
 template <class F>
@@ -873,66 +875,180 @@ inline void row_pack16(const int16_t* __restrict__ s, int n, int bias, uint16_t*
   for (int x = 0; x < n; ++x) d[x] = (uint16_t)(s[x] + bias);
 }
 
-// One (CTU, reference) call: search (out_mv / out_sad), refinement of the winners or of the caller's integer MVs
-// (refine_had >= 0: out_qmv / out_cost), or both.  With refinement the staged window carries a halo of kRefineHalo samples.
-int ctu_call(hmme_ctx* ctx, const int16_t* ctu, int ctu_stride, const int16_t* ref0, int ref_stride, const hmme_search_params* p,
-             bool do_search, const int16_t* int_mv, int refine_had, int16_t* out_mv, uint32_t* out_sad, int16_t* out_qmv, uint32_t* out_cost,
-             const hmme_weight* wp = nullptr) {
-  if (!ctx) return HMME_ERR_ARG;
-  const bool refine = refine_had >= 0;
-  if (wp && (wp->shift < 0 || wp->shift > 15)) return fail(ctx, HMME_ERR_ARG, "weighted prediction: shift %d outside 0..15", wp->shift);
-  if (!ctu || !ref0 || !p || (do_search && (!out_mv || !out_sad)) || (refine && (!out_qmv || !out_cost)) || (!do_search && !int_mv))
-    return fail(ctx, HMME_ERR_ARG, "hmme_search_ctu: null argument");
-  const int halo = refine ? kRefineHalo : 0;
-  if (p->bit_depth < 8 || p->bit_depth > 12) return fail(ctx, HMME_ERR_UNSUPPORTED, "bit depth %d outside 8..12", p->bit_depth);
+// a refusal: its message into msg, its code back
+static __attribute__((format(printf, 4, 5))) int refuse(char* msg, size_t n, int code, const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(msg, n, fmt, ap);
+  va_end(ap);
+  return code;
+}
+
+// The range rule of a weighted reference, for the per-CTU calls (on the ranges they scan: ctu_plan_window) and the picture-level ones (on
+// nominal ranges: weight_eval) alike.  Reference samples in [rlo, rhi] under weight wp, compared with a block in [blo, bhi], the sums
+// shifted by cost_shift (the kernels' shift_bd - 8): the weighted range and the bias that keeps block and weighted samples unsigned,
+// or the refusal.
+struct WeightRange { long wlo = 0, whi = 0; int bias = 0; };
+static int weight_range(const hmme_weight* wp, long rlo, long rhi, long blo, long bhi, int cost_shift, bool refine, WeightRange* out, char* msg, size_t n) {
+  const long a = (((long)wp->w0 * rlo + wp->round) >> wp->shift) + wp->offset, b = (((long)wp->w0 * rhi + wp->round) >> wp->shift) + wp->offset;   // monotonic between
+  const long wlo = std::min(a, b), whi = std::max(a, b);
+  // HM keeps the weighted sample in a Pel (`const Pel pred`, TComRdCostWeightPrediction.cpp:79): beyond int16 its arithmetic wraps,
+  // which nothing here reproduces -- such a call goes back to the caller
+  if (wlo < -32768 || whi > 32767) return refuse(msg, n, HMME_ERR_UNSUPPORTED, "weighted prediction reaches %ld..%ld, beyond a Pel", wlo, whi);
+  const long bias = std::max(0L, -std::min(wlo, blo));
+  // cannot fire for a block within [-maxv, 2 * maxv] of at most 12 bits (bias <= 32768 and whi <= 32767, 8190 + 4095 otherwise); kept as
+  // the statement of what the u16 staging needs
+  if (std::max(whi, bhi) + bias > 65535) return refuse(msg, n, HMME_ERR_UNSUPPORTED, "weighted prediction: samples span more than 16 bits");
+  // the sums of a weighted search must fit the cost field like any other (the weighted window may be far from the block)
+  const long span = std::max(bhi - wlo, whi - blo);   // largest |block - weighted sample| the two ranges admit
+  if (((4096 * span) >> cost_shift) + 65535 >= (long)hmme::kInvCost16)
+    return refuse(msg, n, HMME_ERR_UNSUPPORTED, "weighted SADs of this block could reach %ld: beyond the cost field", 4096 * span);
+  // the refinement's Hadamard sums are exact in fp32 below 2^24: 64 coefficients of up to 64 * span each
+  if (refine && 4096 * span >= (1L << 24))
+    return refuse(msg, n, HMME_ERR_UNSUPPORTED, "weighted refinement: sample differences up to %ld exceed what the Hadamard sums hold exactly", span);
+  *out = {wlo, whi, (int)bias};
+  return HMME_OK;
+}
+// frac_wp: weight w on current samples staged with `bias` -- org_sub takes the bias off again, with the weight's offset; null: the weight is 1
+inline hmme::FracWp frac_wp(const hmme_weight* w, int bias) {
+  if (!w) return hmme::FracWp{1.f, 0.f, (float)bias};
+  return hmme::FracWp{std::ldexp((float)w->w0, -w->shift), std::ldexp((float)w->round, -w->shift), (float)(bias + w->offset)};
+}
+
+// One (CTU, reference) call: search (out_mv / out_sad), refinement of the winners or of the caller's integer MVs (out_qmv / out_cost), or
+// both.  ctu_call below is the sequence of: the refusals that need no sample (ctu_arg_check), the plan -- pure host arithmetic over the
+// parameters, the weight and the four scanned numbers, in two stages (ctu_plan_block, ctu_plan_window) --, packing (ctu_pack), the
+// launches (ctu_stage, ctu_launch_search, ctu_launch_refine), the wait and the copy-out (ctu_finish).  hmme_test_ctu_plan shows the
+// first two to the CPU tests.  The order of the refusals is part of the boundary (tests/ctu_refusal_cases.py): TEncOpenCL retries on
+// HMME_ERR_RANGE alone.
+enum : int { kCtuSearch = HMME_TEST_CTU_SEARCH, kCtuRefine = HMME_TEST_CTU_REFINE, kCtuHadamard = HMME_TEST_CTU_HADAMARD };   // a call's mode
+
+// null_arg: one of the call's pointers is null, p included
+static int ctu_arg_check(const hmme_search_params* p, const hmme_weight* wp, bool null_arg, char* msg, size_t n) {
+  if (wp && (wp->shift < 0 || wp->shift > 15)) return refuse(msg, n, HMME_ERR_ARG, "weighted prediction: shift %d outside 0..15", wp->shift);
+  if (null_arg) return refuse(msg, n, HMME_ERR_ARG, "hmme_search_ctu: null argument");
+  if (p->bit_depth < 8 || p->bit_depth > 12) return refuse(msg, n, HMME_ERR_UNSUPPORTED, "bit depth %d outside 8..12", p->bit_depth);
   // MeJob carries the window and the predictor as int16 (what TComMv holds, TComMv.h:51-55): anything wider would address
   // the staged window at a truncated offset
-  {
-    const int v[6] = {p->lt_x, p->lt_y, p->rb_x, p->rb_y, p->pred_x, p->pred_y};
-    for (int i = 0; i < 6; ++i)
-      if (v[i] < -32768 || v[i] > 32767) return fail(ctx, HMME_ERR_ARG, "hmme_search_ctu: window / predictor component %d outside int16", v[i]);
+  const int v[6] = {p->lt_x, p->lt_y, p->rb_x, p->rb_y, p->pred_x, p->pred_y};
+  for (int i = 0; i < 6; ++i)
+    if (v[i] < -32768 || v[i] > 32767) return refuse(msg, n, HMME_ERR_ARG, "hmme_search_ctu: window / predictor component %d outside int16", v[i]);
+  return HMME_OK;
+}
+
+struct CtuPlan {
+  int mode = 0, lo = 0, hi = 0;                       // what the call does; the range of its block
+  int wx = 0, wy = 0, halo = 0, rows = 0, cols = 0;   // candidates; the staged window: `halo` samples on every side, rows x cols in all
+  bool wide = false, origin = false;                  // the 16-bit kernels on u16 samples; the block is a bi-prediction origin
+  int bias = 0, shift_bd = 8;                         // added to the staged samples; the kernels shift their sums by (shift_bd - 8)
+  FracBuild build;
+  hmme::FracWp fw = kNoWp;
+  MeJob job;                                          // the whole window
+  int n_wg = 0, pdw = 0, smax = 0, tile_tasks[4] = {0, 0, 0, 0};   // the deal; 8-bit: tasks of tile ty * 2 + tx
+  int bps() const { return wide ? 2 : 1; }
+};
+
+// one CTU alone would keep a few of the 256 CUs busy: its work is dealt to up to 64 workgroups (task ranges and window tiles on
+// the 8-bit path, strips of candidate rows on the 16-bit path) that merge through the 64-bit atomicMin table
+static void ctu_deal(CtuPlan* pl, MeJob16* js) {
+  const MeJob& job = pl->job;
+  if (!(pl->mode & kCtuSearch)) {
+    js[0].j = job; js[0].job = 0; js[0].y0 = js[0].y1 = 0;
+  } else if (!pl->wide) {
+    // windows beyond 129 x 129 candidates: up to 2 x 2 tiles (tile (0,0) first: finalize decodes against its top-left)
+    const int tiles_x = (pl->wx + hmme::kTileStep - 1) / hmme::kTileStep, tiles_y = (pl->wy + hmme::kTileStep - 1) / hmme::kTileStep;
+    const int per_tile = kCallMaxJobs / (tiles_x * tiles_y);
+    for (int ty = 0; ty < tiles_y; ++ty)
+      for (int tx = 0; tx < tiles_x; ++tx) {
+        const MeJob sub = hmme::me_tile_job(job, tx, ty);
+        const int nt = pl->tile_tasks[ty * 2 + tx] = hmme::me_num_tasks(sub.rb_x - sub.lt_x + 1, sub.rb_y - sub.lt_y + 1);
+        const int parts = std::max(1, std::min(per_tile, (nt + 3) / 4));   // 4 tasks = one per wave
+        for (int i = 0; i < parts; ++i, ++pl->n_wg) {
+          MeJob16& w = js[pl->n_wg];
+          w.j = sub; w.job = 0 | tx << 30 | ty << 29;
+          w.y0 = (int16_t)((long)nt * i / parts); w.y1 = (int16_t)((long)nt * (i + 1) / parts);
+        }
+      }
+  } else {
+    pl->pdw = pick_pdw16(pl->wx);
+    // at least as many strips as the LDS needs (never more than kCallMaxJobs: the static_assert beside strips_for), and enough of them
+    // to spread the CTU over the chip: a strip is >= 4 candidate rows (each also stages the 63 rows below it)
+    pl->n_wg = std::max(strips_for(pl->pdw, pl->wy), std::min(kCallMaxJobs, (pl->wy + 3) / 4));
+    for (int i = 0; i < pl->n_wg; ++i) {
+      js[i].j = job; js[i].job = 0;
+      js[i].y0 = (int16_t)((long)pl->wy * i / pl->n_wg); js[i].y1 = (int16_t)((long)pl->wy * (i + 1) / pl->n_wg);
+      pl->smax = std::max(pl->smax, js[i].y1 - js[i].y0);
+    }
   }
+}
+
+// The plan, first stage: what the parameters and the range [lo, hi] of the block decide -- sample width, origin bias, window geometry,
+// the refinement's build and the deal (js: kCallMaxJobs entries).  Pure arithmetic: no context, no device.
+static int ctu_plan_block(const hmme_search_params* p, bool weighted, int mode, int sr_max, int lo, int hi, CtuPlan* pl, MeJob16* js, char* msg, size_t n) {
   const int maxv = (1 << p->bit_depth) - 1;
+  *pl = CtuPlan{};
+  pl->mode = mode; pl->lo = lo; pl->hi = hi;
   // samples outside [0, maxv] are the bi-prediction origin 2*org - pred_other (reference TEncSearch.cpp:3702-3712,
   // TComYuv::removeHighFreq TComYuv.cpp:409-440, unclipped).  They stay exact: the 16-bit kernel runs on samples
-  // biased by 2^bitDepth (|a - b| is unchanged), so pick the kernel after looking at the data.
-  int lo = 32767, hi = -32768;
-  for (int y = 0; y < 64; ++y) row_minmax(ctu + (long)y * ctu_stride, 64, lo, hi);
-  const int wx = p->rb_x - p->lt_x + 1, wy = p->rb_y - p->lt_y + 1;
-  const bool bipred_origin = lo < 0 || hi > maxv;
+  // biased by 2^bitDepth (|a - b| is unchanged), so the kernel is picked after looking at the data.
   if (lo < -maxv || hi > 2 * maxv)
-    return fail(ctx, HMME_ERR_RANGE, "hmme_search_ctu: current-block sample outside [%d, %d] (bit depth %d)", -maxv, 2 * maxv, p->bit_depth);
-  const bool wide = p->bit_depth > 8 || bipred_origin || wp;
-  int bias = bipred_origin ? (1 << p->bit_depth) : 0;
+    return refuse(msg, n, HMME_ERR_RANGE, "hmme_search_ctu: current-block sample outside [%d, %d] (bit depth %d)", -maxv, 2 * maxv, p->bit_depth);
+  pl->wx = p->rb_x - p->lt_x + 1; pl->wy = p->rb_y - p->lt_y + 1;
+  if (pl->wx < 1 || pl->wy < 1 || pl->wx > 2 * sr_max + 1 || pl->wy > 2 * sr_max + 1)
+    return refuse(msg, n, HMME_ERR_ARG, "window %dx%d outside 1..%d", pl->wx, pl->wy, 2 * sr_max + 1);
+  pl->origin = lo < 0 || hi > maxv;
+  pl->wide = p->bit_depth > 8 || pl->origin || weighted;
   // xPatternSearchFracDIF on 2*org - pred_other (the bBi pass, TEncSearch.cpp:3798 with bBi): the refinement kernel runs on the same
-  // biased u16 staging as the search; the bias passes HM's interpolation exactly and shifts its clip bounds (me_kernels.hpp, the evaluation of one work item)
-  const int shift_bd = p->shift_free ? 8 : p->bit_depth;   // the kernels shift by (this - 8)
-  const int sr_cap = ctx->sr_max;
-  if (wx < 1 || wy < 1 || wx > 2 * sr_cap + 1 || wy > 2 * sr_cap + 1)
-    return fail(ctx, HMME_ERR_ARG, "window %dx%d outside 1..%d", wx, wy, 2 * sr_cap + 1);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  // pack CTU and window in pinned memory (the reference copies the same window with a scalar CPU loop,
-  // TEncOpenCL.cpp:275-277); 1 byte per sample on the 8-bit path, 2 otherwise
-  const int bps = wide ? 2 : 1;
+  // biased u16 staging as the search; the bias passes HM's interpolation exactly and shifts its clip bounds (me_kernels.hpp, the
+  // evaluation of one work item).  A weighted call's bias is chosen with its window's range (ctu_plan_window).
+  pl->bias = pl->origin ? (1 << p->bit_depth) : 0;
+  pl->shift_bd = p->shift_free ? 8 : p->bit_depth;
+  pl->halo = (mode & kCtuRefine) ? kRefineHalo : 0;   // what the 8-tap interpolation reaches beyond the window
+  pl->rows = pl->wy + 63 + 2 * pl->halo; pl->cols = pl->wx + 63 + 2 * pl->halo;
+  pl->build = FracBuild{pl->wide ? 1 : 0, (mode & kCtuHadamard) ? 1 : 0, weighted ? 1 : 0};
+  pl->job.ctu_x = 0; pl->job.ctu_y = 0;
+  pl->job.lt_x = (int16_t)p->lt_x; pl->job.lt_y = (int16_t)p->lt_y; pl->job.rb_x = (int16_t)p->rb_x; pl->job.rb_y = (int16_t)p->rb_y;
+  pl->job.pred_x = (int16_t)p->pred_x; pl->job.pred_y = (int16_t)p->pred_y;
+  ctu_deal(pl, js);
+  return HMME_OK;
+}
+
+// The plan, second stage: what the range [vlo, vhi] of the staged window decides.  A weighted call comes here before it packs (block
+// and weighted window share a bias), any other after: its window is scanned in the loop that packs it.
+static int ctu_plan_window(const hmme_search_params* p, const hmme_weight* wp, int vlo, int vhi, CtuPlan* pl, char* msg, size_t n) {
+  const int maxv = (1 << p->bit_depth) - 1;
+  if (vlo < 0 || vhi > maxv) return refuse(msg, n, HMME_ERR_RANGE, "hmme_search_ctu: reference sample outside [0,%d] for bit depth %d", maxv, p->bit_depth);
+  if (wp) {
+    WeightRange wr;
+    const int rc = weight_range(wp, vlo, vhi, pl->lo, pl->hi, pl->shift_bd - 8, (pl->mode & kCtuRefine) != 0, &wr, msg, n);
+    if (rc) return rc;
+    // the interpolated prediction is weighted sample by sample (me_frac_eval0 / me_frac_eval1, FracWp); the current samples carry `bias`, the raw window none
+    pl->bias = wr.bias;
+    pl->fw = frac_wp(wp, wr.bias);
+  }
+  // unshifted sums must fit the 24-bit cost field of the 16-bit kernel's keys (me_kernels.hpp kInvCost16).  The bound is taken
+  // from the samples of THIS call (both scans are made anyway): no |cur - ref| exceeds max(hi - vlo, vhi - lo), so any content whose
+  // 64x64 sum cannot reach the marker is searched, whatever the nominal bit depth says (10-bit bi-prediction origins nominally
+  // reach 4096 * 2046, real ones stay far below)
+  if (p->shift_free && pl->wide) {
+    const long span = std::max<long>((long)pl->hi - vlo, (long)vhi - pl->lo);
+    if (4096 * span + 65535 >= (long)hmme::kInvCost16)
+      return refuse(msg, n, HMME_ERR_UNSUPPORTED, "shift-free SADs of this block could reach %ld (sample difference up to %ld at bit depth %d%s): beyond the cost field",
+                    4096 * span, span, p->bit_depth, pl->origin ? ", bi-prediction origin" : "");
+  }
+  return HMME_OK;
+}
+
+// Block, window and the refinement's inputs into the pinned call block (the reference copies the same window with a scalar CPU loop,
+// TEncOpenCL.cpp:275-277); 1 byte per sample on the 8-bit path, 2 otherwise.  win_range: where the window's range goes, taken in the
+// same pass (null: scanned before, the weighted call -- its window goes up as it is and is weighted on the device).
+static void ctu_pack(hmme_ctx* ctx, const CtuPlan& pl, const int16_t* ctu, int ctu_stride, const int16_t* src, int ref_stride, const int16_t* int_mv, int* win_range) {
   uint8_t* h_ctu = ctx->h_call + kCallCtu;
   uint8_t* h_win = ctx->h_call + kCallWin;
-  const int rows = wy + 63 + 2 * halo, cols = wx + 63 + 2 * halo;
-  const int16_t* src = ref0 + (long)(p->lt_y - halo) * ref_stride + (p->lt_x - halo);
+  // the plan's numbers as locals: the byte stores below may alias anything the compiler cannot see the end of
+  const bool wide = pl.wide, scan = win_range != nullptr;
+  const int rows = pl.rows, cols = pl.cols, bps = pl.bps(), bias = pl.bias, win_bias = pl.build.wp ? 0 : pl.bias;
   int vlo = 32767, vhi = -32768;
-  if (wp)   // the window goes up as it is and is weighted on the device; block and weighted window share a bias chosen below
-    for (int y = 0; y < rows; ++y) row_minmax(src + (long)y * ref_stride, cols, vlo, vhi);
-  long wlo = 0, whi = 0;   // range of the weighted window
-  if (wp) {
-    if (vlo < 0 || vhi > maxv) return fail(ctx, HMME_ERR_RANGE, "hmme_search_ctu: reference sample outside [0,%d] for bit depth %d", maxv, p->bit_depth);
-    const long a = (((long)wp->w0 * vlo + wp->round) >> wp->shift) + wp->offset, b = (((long)wp->w0 * vhi + wp->round) >> wp->shift) + wp->offset;
-    wlo = std::min(a, b); whi = std::max(a, b);
-    // HM keeps the weighted sample in a Pel (`const Pel pred`, TComRdCostWeightPrediction.cpp:79): beyond int16 its arithmetic wraps,
-    // which nothing here reproduces -- such a call goes back to the caller
-    if (wlo < -32768 || whi > 32767) return fail(ctx, HMME_ERR_UNSUPPORTED, "weighted prediction reaches %ld..%ld, beyond a Pel", wlo, whi);
-    const long low = std::min<long>(wlo, lo);
-    bias = low < 0 ? (int)-low : 0;
-    if (std::max<long>(whi, hi) + bias > 65535) return fail(ctx, HMME_ERR_UNSUPPORTED, "weighted prediction: samples span more than 16 bits");
-  }
   for (int y = 0; y < 64; ++y) {
     if (wide) row_pack16(ctu + (long)y * ctu_stride, 64, bias, (uint16_t*)h_ctu + y * 64);
     else row_pack8(ctu + (long)y * ctu_stride, 64, h_ctu + y * 64);
@@ -940,173 +1056,184 @@ int ctu_call(hmme_ctx* ctx, const int16_t* ctu, int ctu_stride, const int16_t* r
   for (int y = 0; y < rows; ++y) {
     uint8_t* row = h_win + (size_t)y * kWinPitch;
     const int16_t* srow = src + (long)y * ref_stride;
-    if (!wp) row_minmax(srow, cols, vlo, vhi);
-    if (wide) row_pack16(srow, cols, wp ? 0 : bias, (uint16_t*)row);
+    if (scan) row_minmax(srow, cols, vlo, vhi);
+    if (wide) row_pack16(srow, cols, win_bias, (uint16_t*)row);
     else row_pack8(srow, cols, row);
     std::memset(row + cols * bps, 0, 16);   // the kernels stage whole dwords past the last sample
   }
-  if (vlo < 0 || vhi > maxv) return fail(ctx, HMME_ERR_RANGE, "hmme_search_ctu: reference sample outside [0,%d] for bit depth %d", maxv, p->bit_depth);
-  if (wp) {   // the sums of a weighted search must fit the cost field like any other (the weighted window may be far from the block)
-    const long span = std::max<long>((long)hi - wlo, whi - (long)lo);
-    if (((4096 * span) >> (shift_bd - 8)) + 65535 >= (long)hmme::kInvCost16)
-      return fail(ctx, HMME_ERR_UNSUPPORTED, "weighted SADs of this block could reach %ld: beyond the cost field", 4096 * span);
-    // the refinement's Hadamard sums are exact in fp32 below 2^24: 64 coefficients of up to 64 * span each
-    if (refine && 4096 * span >= (1L << 24))
-      return fail(ctx, HMME_ERR_UNSUPPORTED, "weighted refinement: sample differences up to %ld exceed what the Hadamard sums hold exactly", span);
-  }
-  // unshifted sums must fit the 24-bit cost field of the 16-bit kernel's keys (me_kernels.hpp kInvCost16).  The bound is taken
-  // from the samples of THIS call (both scans are made anyway): no |cur - ref| exceeds max(hi - vlo, vhi - lo), so any content whose
-  // 64x64 sum cannot reach the marker is searched, whatever the nominal bit depth says (10-bit bi-prediction origins nominally
-  // reach 4096 * 2046, real ones stay far below)
-  if (p->shift_free && wide) {
-    const long span = std::max<long>((long)hi - vlo, (long)vhi - lo);
-    if (4096 * span + 65535 >= (long)hmme::kInvCost16)
-      return fail(ctx, HMME_ERR_UNSUPPORTED, "shift-free SADs of this block could reach %ld (sample difference up to %ld at bit depth %d%s): beyond the cost field",
-                  4096 * span, span, p->bit_depth, bipred_origin ? ", bi-prediction origin" : "");
-  }
-  MeJob job;
-  job.ctu_x = 0; job.ctu_y = 0;
-  job.lt_x = (int16_t)p->lt_x; job.lt_y = (int16_t)p->lt_y; job.rb_x = (int16_t)p->rb_x; job.rb_y = (int16_t)p->rb_y;
-  job.pred_x = (int16_t)p->pred_x; job.pred_y = (int16_t)p->pred_y;
+  if (win_range) { win_range[0] = vlo; win_range[1] = vhi; }
+  if (int_mv) std::memcpy(ctx->h_call + kCallImv, int_mv, sizeof(int16_t) * 2 * HMME_NUM_CTU_PARTS);
+  std::memcpy(ctx->h_call + kCallFracJob, &pl.job, sizeof pl.job);
+}
+
+// the kernels address ref(ctu + lt): the base is biased so that (lt_x, lt_y) lands on the first sample of the window copy at `win`
+inline const uint8_t* ctu_ref_base(const uint8_t* win, const CtuPlan& pl) {
+  return win - (long)(pl.job.lt_y - pl.halo) * kWinPitch - (long)(pl.job.lt_x - pl.halo) * pl.bps();
+}
+
+// the call block to the device; a weighted search runs on a weighted copy of the window, the raw one stays where it is for the refinement's interpolation
+static int ctu_stage(hmme_ctx* ctx, const CtuPlan& pl, const hmme_weight* wp) {
   hipStream_t s = ctx->stream;
-  // one CTU alone would keep a few of the 256 CUs busy: its work is dealt to up to 64 workgroups (task ranges and window tiles on
-  // the 8-bit path, strips of candidate rows on the 16-bit path) that merge through the 64-bit atomicMin table
-  MeJob16* js = (MeJob16*)(ctx->h_call + kCallJobs);
-  int n_wg = 0, pdw = 0, smax = 0;
-  if (!do_search) {
-    js[0].j = job; js[0].job = 0; js[0].y0 = js[0].y1 = 0;
-    std::memcpy(ctx->h_call + kCallImv, int_mv, sizeof(int16_t) * 2 * HMME_NUM_CTU_PARTS);
-  } else if (!wide) {
-    // windows beyond 129 x 129 candidates: up to 2 x 2 tiles (tile (0,0) first: finalize decodes against its top-left)
-    const int tiles_x = (wx + hmme::kTileStep - 1) / hmme::kTileStep, tiles_y = (wy + hmme::kTileStep - 1) / hmme::kTileStep;
-    const int per_tile = kCallMaxJobs / (tiles_x * tiles_y);
-    for (int ty = 0; ty < tiles_y; ++ty)
-      for (int tx = 0; tx < tiles_x; ++tx) {
-        const MeJob sub = hmme::me_tile_job(job, tx, ty);
-        const int nt = hmme::me_num_tasks(sub.rb_x - sub.lt_x + 1, sub.rb_y - sub.lt_y + 1);
-        const int parts = std::max(1, std::min(per_tile, (nt + 3) / 4));   // 4 tasks = one per wave
-        for (int i = 0; i < parts; ++i, ++n_wg) {
-          js[n_wg].j = sub; js[n_wg].job = 0 | tx << 30 | ty << 29;
-          js[n_wg].y0 = (int16_t)((long)nt * i / parts); js[n_wg].y1 = (int16_t)((long)nt * (i + 1) / parts);
-        }
-      }
-  } else {
-    pdw = pick_pdw16(wx);
-    // at least as many strips as the LDS needs, and enough of them to spread the CTU over the chip: a strip is
-    // >= 4 candidate rows (each also stages the 63 rows below it)
-    n_wg = std::max(strips_for(pdw, wy), std::min(kCallMaxJobs, (wy + 3) / 4));
-    if (n_wg > kCallMaxJobs) return fail(ctx, HMME_ERR_UNSUPPORTED, "window needs %d strips", n_wg);
-    for (int i = 0; i < n_wg; ++i) {
-      js[i].j = job; js[i].job = 0;
-      js[i].y0 = (int16_t)((long)wy * i / n_wg); js[i].y1 = (int16_t)((long)wy * (i + 1) / n_wg);
-      if (js[i].y1 - js[i].y0 > smax) smax = js[i].y1 - js[i].y0;
-    }
-  }
-  std::memcpy(ctx->h_call + kCallFracJob, &job, sizeof job);
-  {
-    const int n16 = (int)((kCallWin + (size_t)rows * kWinPitch + 64 + 15) / 16);
-    hipLaunchKernelGGL(hmme::me_stage_call_kernel, dim3((n16 + 255) / 256), dim3(256), 0, s, (const uint4*)ctx->h_call_dev, (uint4*)ctx->d_call(), n16);
-    HIP_TRY(ctx, hipGetLastError());
-    if (wp && do_search) {   // the weighted window the integer search runs on; the raw one stays where it is for the refinement's interpolation
-      bool fresh;   // cleared once: rows below a call's window hold zeros or an earlier call's samples, never what the allocator left
-      const int erc = ensure(ctx, ctx->buf[kWwin], (size_t)kWinRows * kWinPitch + 64, 0, &fresh);
-      if (erc) return erc;
-      if (fresh) HIP_TRY(ctx, hipMemsetAsync(ctx->buf[kWwin].p, 0, (size_t)kWinRows * kWinPitch + 64, s));
-      hipLaunchKernelGGL(hmme::me_weight_window_kernel, dim3((rows * (cols + 8) + 255) / 256), dim3(256), 0, s, (const uint8_t*)(ctx->d_call() + kCallWin), ctx->buf[kWwin].as<uint8_t>(),
-                         (int)kWinPitch, rows, cols, wp->w0, wp->round, wp->shift, wp->offset + bias);
-      HIP_TRY(ctx, hipGetLastError());
-    }
-  }
-  // the kernel addresses ref(ctu + lt): bias the base so that (lt_x, lt_y) lands on the window copy's first sample
-  const uint8_t* ref_base = ctx->d_call() + kCallWin - (long)(p->lt_y - halo) * kWinPitch - (long)(p->lt_x - halo) * bps;
-  const uint8_t* ref_base_search = wp ? ctx->buf[kWwin].as<uint8_t>() - (long)(p->lt_y - halo) * kWinPitch - (long)(p->lt_x - halo) * bps : ref_base;
+  const int n16 = (int)((kCallWin + (size_t)pl.rows * kWinPitch + 64 + 15) / 16);
+  hipLaunchKernelGGL(hmme::me_stage_call_kernel, dim3((n16 + 255) / 256), dim3(256), 0, s, (const uint4*)ctx->h_call_dev, (uint4*)ctx->d_call(), n16);
+  HIP_TRY(ctx, hipGetLastError());
+  if (!wp || !(pl.mode & kCtuSearch)) return HMME_OK;
+  bool fresh;   // cleared once: rows below a call's window hold zeros or an earlier call's samples, never what the allocator left
+  const int erc = ensure(ctx, ctx->buf[kWwin], (size_t)kWinRows * kWinPitch + 64, 0, &fresh);
+  if (erc) return erc;
+  if (fresh) HIP_TRY(ctx, hipMemsetAsync(ctx->buf[kWwin].p, 0, (size_t)kWinRows * kWinPitch + 64, s));
+  hipLaunchKernelGGL(hmme::me_weight_window_kernel, dim3((pl.rows * (pl.cols + 8) + 255) / 256), dim3(256), 0, s, (const uint8_t*)(ctx->d_call() + kCallWin), ctx->buf[kWwin].as<uint8_t>(),
+                     (int)kWinPitch, pl.rows, pl.cols, wp->w0, wp->round, wp->shift, wp->offset + pl.bias);
+  HIP_TRY(ctx, hipGetLastError());
+  return HMME_OK;
+}
+
+// the 4.7 KB of results go straight into pinned host memory (mapped into the device's address space): no download step
+static int ctu_launch_search(hmme_ctx* ctx, const CtuPlan& pl, int fen, bool weighted, uint32_t seq) {
+  hipStream_t s = ctx->stream;
+  const uint8_t* win = weighted ? ctx->buf[kWwin].as<uint8_t>() : ctx->d_call() + kCallWin;
   const MeJob16* d_js = (const MeJob16*)(ctx->d_call() + kCallJobs);
   const int* d_first = (const int*)(ctx->d_call() + kCallFirst);
   unsigned long long* d_best1 = (unsigned long long*)(ctx->d_call() + kCallBest);
-  // the 4.7 KB of results go straight into pinned host memory (mapped into the device's address space): no download step
   int16_t* d_mv1 = (int16_t*)(ctx->d_res + kResMv);
   uint32_t* d_sad1 = (uint32_t*)(ctx->d_res + kResSad);
-  int rc = HMME_OK;
-  const uint32_t seq = ++ctx->call_seq ? ctx->call_seq : ++ctx->call_seq;   // never 0, the words' initial value
-  if (do_search) {
-  if (!wide)
-    rc = launch_search8_split(ctx, one_ref(ctx->d_call() + kCallCtu), 1, one_ref(ref_base), kWinPitch, d_js, d_first, 1, n_wg, p->fen, d_mv1, d_sad1, s, d_best1, false);
+  int rc;
+  if (!pl.wide)
+    rc = launch_search8_split(ctx, one_ref(ctx->d_call() + kCallCtu), 1, one_ref(ctu_ref_base(win, pl)), kWinPitch, d_js, d_first, 1, pl.n_wg, fen, d_mv1, d_sad1, s, d_best1, false);
   else
-    rc = launch_search16(ctx, one_ref(ctx->d_call() + kCallCtu), 1, one_ref(ref_base_search), kWinPitch, d_js, d_first, 1, n_wg, pdw, smax, wp ? 0 : p->fen, shift_bd,   // xGetSADw reads every row
-                         d_mv1, d_sad1, s, d_best1, false);
+    rc = launch_search16(ctx, one_ref(ctx->d_call() + kCallCtu), 1, one_ref(ctu_ref_base(win, pl)), kWinPitch, d_js, d_first, 1, pl.n_wg, pl.pdw, pl.smax, weighted ? 0 : fen,   // xGetSADw reads every row
+                         pl.shift_bd, d_mv1, d_sad1, s, d_best1, false);
   if (rc) return rc;
   hipLaunchKernelGGL(hmme::me_finalize1_kernel, dim3(1), dim3(640), 0, s, d_best1, d_js, ctx->lambda_q16, d_mv1, d_sad1,
                      (volatile uint32_t*)(ctx->d_res + kResDone), seq);
   HIP_TRY(ctx, hipGetLastError());
-  }
-  if (refine) {
-    // xPatternSearchFracDIF for the 593 slots on the block and window that are staged anyway: one more workgroup-sized kernel,
-    // its input the integer tables the finalize kernel just wrote (or the caller's), its output in the same pinned block
-    rc = build_frac_cover(ctx);
-    if (rc) return rc;
-    const int16_t* d_imv = do_search ? d_mv1 : (const int16_t*)(ctx->d_call() + kCallImv);
-    // weighted: the interpolated prediction is weighted sample by sample (me_frac_eval0 / me_frac_eval1, FracWp); the current samples carry `bias`, the raw window none
-    const hmme::FracWp fw = wp ? hmme::FracWp{std::ldexp((float)wp->w0, -wp->shift), std::ldexp((float)wp->round, -wp->shift), (float)(bias + wp->offset)} : kNoWp;
-    const FracBuild build = {wide ? 1 : 0, refine_had ? 1 : 0, wp ? 1 : 0};
-    rc = frac_lds_optin(ctx, build);
-    if (rc) return rc;
-    hipLaunchKernelGGL(frac_kernel(build), dim3(1), dim3(hmme::frac_threads(bps)), hmme::frac_lds_bytes(bps), s, one_ref(ctx->d_call() + kCallCtu),
-                       64 * bps, one_ref(ref_base), kWinPitch, (const MeJob*)(ctx->d_call() + kCallFracJob), kNoPrep, 1, (uint32_t*)nullptr, ctx->buf[kFracCover].as<uint16_t>(), d_imv, ctx->lambda_q16,
-                       p->bit_depth | ((bipred_origin && !wp) ? 0x100 : 0), fw, (int16_t*)(ctx->d_res + kResQmv), (uint32_t*)(ctx->d_res + kResCost));
-    HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(hmme::me_publish_kernel, dim3(1), dim3(1), 0, s, (volatile uint32_t*)(ctx->d_res + kResDone2), seq);
-    HIP_TRY(ctx, hipGetLastError());
-  }
-  volatile uint32_t* done = (volatile uint32_t*)(ctx->h_res + (refine ? kResDone2 : kResDone));
-  // the caller blocks on this call anyway (TEncSearch.cpp:3749-3758): poll the completion word for a while instead of paying the
-  // interrupt wake-up of hipStreamSynchronize, then fall back to it (a faulted kernel never publishes)
+  return HMME_OK;
+}
+
+// xPatternSearchFracDIF for the 593 slots on the block and window that are staged anyway: one more workgroup-sized kernel,
+// its input the integer tables the finalize kernel just wrote (or the caller's), its output in the same pinned block
+static int ctu_launch_refine(hmme_ctx* ctx, const CtuPlan& pl, int bit_depth, uint32_t seq) {
+  hipStream_t s = ctx->stream;
+  int rc = build_frac_cover(ctx);
+  if (rc) return rc;
+  const int16_t* d_imv = (pl.mode & kCtuSearch) ? (const int16_t*)(ctx->d_res + kResMv) : (const int16_t*)(ctx->d_call() + kCallImv);
+  rc = frac_lds_optin(ctx, pl.build);
+  if (rc) return rc;
+  hipLaunchKernelGGL(frac_kernel(pl.build), dim3(1), dim3(hmme::frac_threads(pl.bps())), hmme::frac_lds_bytes(pl.bps()), s, one_ref(ctx->d_call() + kCallCtu),
+                     64 * pl.bps(), one_ref(ctu_ref_base(ctx->d_call() + kCallWin, pl)), kWinPitch, (const MeJob*)(ctx->d_call() + kCallFracJob), kNoPrep, 1, (uint32_t*)nullptr,
+                     ctx->buf[kFracCover].as<uint16_t>(), d_imv, ctx->lambda_q16, bit_depth | ((pl.origin && !pl.build.wp) ? 0x100 : 0), pl.fw,
+                     (int16_t*)(ctx->d_res + kResQmv), (uint32_t*)(ctx->d_res + kResCost));
+  HIP_TRY(ctx, hipGetLastError());
+  hipLaunchKernelGGL(hmme::me_publish_kernel, dim3(1), dim3(1), 0, s, (volatile uint32_t*)(ctx->d_res + kResDone2), seq);
+  HIP_TRY(ctx, hipGetLastError());
+  return HMME_OK;
+}
+
+// the caller blocks on this call anyway (TEncSearch.cpp:3749-3758): poll the completion word for a while instead of paying the
+// interrupt wake-up of hipStreamSynchronize, then fall back to it (a faulted kernel never publishes); then the tables to the caller
+static int ctu_finish(hmme_ctx* ctx, int mode, uint32_t seq, int16_t* out_mv, uint32_t* out_sad, int16_t* out_qmv, uint32_t* out_cost) {
+  volatile uint32_t* done = (volatile uint32_t*)(ctx->h_res + ((mode & kCtuRefine) ? kResDone2 : kResDone));
   for (int spin = 0; *done != seq && spin < 200000; ++spin) __builtin_ia32_pause();
-  if (*done != seq) HIP_TRY(ctx, hipStreamSynchronize(s));
+  if (*done != seq) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (*done != seq) return fail(ctx, HMME_ERR_DEVICE, "hmme_search_ctu: the device did not publish results");
   __atomic_thread_fence(__ATOMIC_ACQUIRE);
-  if (do_search) {
+  if (mode & kCtuSearch) {
     std::memcpy(out_mv, ctx->h_res + kResMv, sizeof(int16_t) * 2 * HMME_NUM_CTU_PARTS);
     std::memcpy(out_sad, ctx->h_res + kResSad, sizeof(uint32_t) * HMME_NUM_CTU_PARTS);
   }
-  if (refine) {
+  if (mode & kCtuRefine) {
     std::memcpy(out_qmv, ctx->h_res + kResQmv, sizeof(int16_t) * 2 * HMME_NUM_CTU_PARTS);
     std::memcpy(out_cost, ctx->h_res + kResCost, sizeof(uint32_t) * HMME_NUM_CTU_PARTS);
   }
   return HMME_OK;
 }
+
+static int ctu_call(hmme_ctx* ctx, const int16_t* ctu, int ctu_stride, const int16_t* ref0, int ref_stride, const hmme_search_params* p, int mode,
+             const int16_t* int_mv, int16_t* out_mv, uint32_t* out_sad, int16_t* out_qmv, uint32_t* out_cost, const hmme_weight* wp = nullptr) {
+  if (!ctx) return HMME_ERR_ARG;
+  const bool search = mode & kCtuSearch, refine = mode & kCtuRefine;
+  char why[256];
+  int rc = ctu_arg_check(p, wp, !ctu || !ref0 || !p || (search && (!out_mv || !out_sad)) || (refine && (!out_qmv || !out_cost)) || (!search && !int_mv), why, sizeof why);
+  if (rc) return fail(ctx, rc, "%s", why);
+  int lo = 32767, hi = -32768, win[2] = {32767, -32768};
+  for (int y = 0; y < 64; ++y) row_minmax(ctu + (long)y * ctu_stride, 64, lo, hi);
+  CtuPlan pl;
+  rc = ctu_plan_block(p, wp != nullptr, mode, ctx->sr_max, lo, hi, &pl, (MeJob16*)(ctx->h_call + kCallJobs), why, sizeof why);
+  if (rc) return fail(ctx, rc, "%s", why);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const int16_t* src = ref0 + (long)(p->lt_y - pl.halo) * ref_stride + (p->lt_x - pl.halo);
+  if (wp) {   // scanned once before the bias is chosen; every other window in the loop that packs it
+    for (int y = 0; y < pl.rows; ++y) row_minmax(src + (long)y * ref_stride, pl.cols, win[0], win[1]);
+    rc = ctu_plan_window(p, wp, win[0], win[1], &pl, why, sizeof why);
+  }
+  if (!rc) ctu_pack(ctx, pl, ctu, ctu_stride, src, ref_stride, search ? nullptr : int_mv, wp ? nullptr : win);
+  if (!rc && !wp) rc = ctu_plan_window(p, wp, win[0], win[1], &pl, why, sizeof why);
+  if (rc) return fail(ctx, rc, "%s", why);
+  const uint32_t seq = ++ctx->call_seq ? ctx->call_seq : ++ctx->call_seq;   // never 0, the words' initial value
+  rc = ctu_stage(ctx, pl, wp);
+  if (!rc && search) rc = ctu_launch_search(ctx, pl, p->fen, wp != nullptr, seq);
+  if (!rc && refine) rc = ctu_launch_refine(ctx, pl, p->bit_depth, seq);
+  return rc ? rc : ctu_finish(ctx, mode, seq, out_mv, out_sad, out_qmv, out_cost);
+}
 }  // namespace
+
+int hmme_test_ctu_plan(int sr_max, const hmme_search_params* p, int mode, const hmme_weight* wp, const int* range, int* out, float* out_fw, int16_t* out_wg, char* msg, int msg_len) {
+  char why[256];
+  why[0] = 0;
+  if (!p || !range || !out || !out_fw || !out_wg || sr_max < 1 || sr_max > HMME_MAX_SEARCH_RANGE || !(mode & (kCtuSearch | kCtuRefine)) ||
+      ((mode & kCtuHadamard) && !(mode & kCtuRefine)))
+    return HMME_ERR_ARG;
+  CtuPlan pl;
+  MeJob16 js[kCallMaxJobs];
+  int rc = ctu_arg_check(p, wp, false, why, sizeof why);
+  if (!rc) rc = ctu_plan_block(p, wp != nullptr, mode, sr_max, range[0], range[1], &pl, js, why, sizeof why);
+  if (!rc) rc = ctu_plan_window(p, wp, range[2], range[3], &pl, why, sizeof why);
+  if (msg && msg_len > 0) snprintf(msg, (size_t)msg_len, "%s", why);
+  if (rc) return rc;
+  const int scalars[17] = {pl.wide, pl.bias, pl.origin, pl.shift_bd, pl.halo, pl.rows, pl.cols, pl.n_wg, pl.pdw, pl.smax, pl.build.wide, pl.build.had, pl.build.wp,
+                           pl.tile_tasks[0], pl.tile_tasks[1], pl.tile_tasks[2], pl.tile_tasks[3]};
+  std::memcpy(out, scalars, sizeof scalars);
+  out_fw[0] = pl.fw.ws; out_fw[1] = pl.fw.rs; out_fw[2] = pl.fw.org_sub;
+  for (int i = 0; i < pl.n_wg; ++i) {
+    const int16_t wg[8] = {js[i].j.lt_x, js[i].j.lt_y, js[i].j.rb_x, js[i].j.rb_y, (int16_t)((js[i].job >> 30) & 1), (int16_t)((js[i].job >> 29) & 1), js[i].y0, js[i].y1};
+    std::memcpy(out_wg + 8 * i, wg, sizeof wg);
+  }
+  return HMME_OK;
+}
+
+static inline int refine_mode(int use_hadamard) { return kCtuRefine | (use_hadamard ? kCtuHadamard : 0); }
 
 int hmme_search_ctu(hmme_ctx* ctx, const int16_t* ctu, int ctu_stride, const int16_t* ref0, int ref_stride,
                     const hmme_search_params* p, int16_t* out_mv, uint32_t* out_sad) {
-  return ctu_call(ctx, ctu, ctu_stride, ref0, ref_stride, p, true, nullptr, -1, out_mv, out_sad, nullptr, nullptr);
+  return ctu_call(ctx, ctu, ctu_stride, ref0, ref_stride, p, kCtuSearch, nullptr, out_mv, out_sad, nullptr, nullptr);
 }
 
 int hmme_search_ctu_w(hmme_ctx* ctx, const int16_t* ctu, int ctu_stride, const int16_t* ref0, int ref_stride,
                       const hmme_search_params* p, const hmme_weight* wp, int16_t* out_mv, uint32_t* out_sad) {
   if (ctx && !wp) return fail(ctx, HMME_ERR_ARG, "hmme_search_ctu_w: null weight");
-  return ctu_call(ctx, ctu, ctu_stride, ref0, ref_stride, p, true, nullptr, -1, out_mv, out_sad, nullptr, nullptr, wp);
+  return ctu_call(ctx, ctu, ctu_stride, ref0, ref_stride, p, kCtuSearch, nullptr, out_mv, out_sad, nullptr, nullptr, wp);
 }
 
 int hmme_search_refine_ctu_w(hmme_ctx* ctx, const int16_t* ctu, int ctu_stride, const int16_t* ref0, int ref_stride, const hmme_search_params* p,
                              const hmme_weight* wp, int use_hadamard, int16_t* out_mv, uint32_t* out_sad, int16_t* out_qmv, uint32_t* out_cost) {
   if (ctx && !wp) return fail(ctx, HMME_ERR_ARG, "hmme_search_refine_ctu_w: null weight");
-  return ctu_call(ctx, ctu, ctu_stride, ref0, ref_stride, p, true, nullptr, use_hadamard ? 1 : 0, out_mv, out_sad, out_qmv, out_cost, wp);
+  return ctu_call(ctx, ctu, ctu_stride, ref0, ref_stride, p, kCtuSearch | refine_mode(use_hadamard), nullptr, out_mv, out_sad, out_qmv, out_cost, wp);
 }
 
 int hmme_search_refine_ctu(hmme_ctx* ctx, const int16_t* ctu, int ctu_stride, const int16_t* ref0, int ref_stride, const hmme_search_params* p,
                            int use_hadamard, int16_t* out_mv, uint32_t* out_sad, int16_t* out_qmv, uint32_t* out_cost) {
-  return ctu_call(ctx, ctu, ctu_stride, ref0, ref_stride, p, true, nullptr, use_hadamard ? 1 : 0, out_mv, out_sad, out_qmv, out_cost);
+  return ctu_call(ctx, ctu, ctu_stride, ref0, ref_stride, p, kCtuSearch | refine_mode(use_hadamard), nullptr, out_mv, out_sad, out_qmv, out_cost);
 }
 
 int hmme_refine_ctu(hmme_ctx* ctx, const int16_t* ctu, int ctu_stride, const int16_t* ref0, int ref_stride, const hmme_search_params* p,
                     const int16_t* int_mv, int use_hadamard, int16_t* out_qmv, uint32_t* out_cost) {
-  return ctu_call(ctx, ctu, ctu_stride, ref0, ref_stride, p, false, int_mv, use_hadamard ? 1 : 0, nullptr, nullptr, out_qmv, out_cost);
+  return ctu_call(ctx, ctu, ctu_stride, ref0, ref_stride, p, refine_mode(use_hadamard), int_mv, nullptr, nullptr, out_qmv, out_cost);
 }
 
 int hmme_refine_ctu_w(hmme_ctx* ctx, const int16_t* ctu, int ctu_stride, const int16_t* ref0, int ref_stride, const hmme_search_params* p,
                       const hmme_weight* wp, const int16_t* int_mv, int use_hadamard, int16_t* out_qmv, uint32_t* out_cost) {
   if (ctx && !wp) return fail(ctx, HMME_ERR_ARG, "hmme_refine_ctu_w: null weight");
-  return ctu_call(ctx, ctu, ctu_stride, ref0, ref_stride, p, false, int_mv, use_hadamard ? 1 : 0, nullptr, nullptr, out_qmv, out_cost, wp);
+  return ctu_call(ctx, ctu, ctu_stride, ref0, ref_stride, p, refine_mode(use_hadamard), int_mv, nullptr, nullptr, out_qmv, out_cost, wp);
 }
 
 // ---- planes ----------------------------------------------------------------------------------------------
@@ -1749,7 +1876,8 @@ struct BlockRange { int lo, hi; };
 constexpr BlockRange kPictureBlock{0, 1};   // samples of a picture: [0, maxv]
 constexpr BlockRange kBiOrigin{-1, 2};      // a bi-prediction origin 2 * org - pred: [-maxv, 2 * maxv]
 
-// what ctu_call decides from the samples it scans, decided from the nominal ranges: the reference in [0, 2^bitDepth - 1], the block in `block`
+// what the per-CTU plan decides from the samples a call scans, decided from the nominal ranges -- the reference in [0, 2^bitDepth - 1],
+// the block in `block` -- by the same rule (weight_range); the two checks on w0 * sample + round are made here alone
 int weight_eval(int bit_depth, const hmme_weight* wp, int refine, BlockRange block, WpInfo* info, char* msg, size_t n) {
   msg[0] = 0;
   if (!wp) { snprintf(msg, n, "null weight"); return HMME_ERR_ARG; }
@@ -1759,34 +1887,16 @@ int weight_eval(int bit_depth, const hmme_weight* wp, int refine, BlockRange blo
   const long maxv = (1L << bit_depth) - 1;
   const long p0 = wp->round, p1 = (long)wp->w0 * maxv + wp->round;   // w0 * ref + round at the two ends of the range (monotonic between)
   // HM forms it in an Int and the device in 32 bits: beyond that nothing is defined
-  if (std::min(p0, p1) < INT32_MIN || std::max(p0, p1) > INT32_MAX) {
-    snprintf(msg, n, "weighted prediction: w0 * sample + round reaches %ld..%ld, beyond 32 bits", std::min(p0, p1), std::max(p0, p1));
-    return HMME_ERR_UNSUPPORTED;
-  }
-  const long a = (p0 >> wp->shift) + wp->offset, b = (p1 >> wp->shift) + wp->offset;
-  const long wlo = std::min(a, b), whi = std::max(a, b);
-  if (wlo < -32768 || whi > 32767) { snprintf(msg, n, "weighted prediction reaches %ld..%ld, beyond a Pel", wlo, whi); return HMME_ERR_UNSUPPORTED; }
-  const long blo = block.lo * maxv, bhi = block.hi * maxv;
-  const long bias = std::max(0L, -std::min(wlo, blo));   // what keeps block and weighted plane unsigned
-  if (std::max(whi, bhi) + bias > 65535) { snprintf(msg, n, "weighted prediction: samples span more than 16 bits"); return HMME_ERR_UNSUPPORTED; }
-  const long span = std::max(bhi - wlo, whi - blo);   // largest |block - weighted sample| the two ranges admit
-  if (((4096 * span) >> (bit_depth - 8)) + 65535 >= (long)hmme::kInvCost16) {
-    snprintf(msg, n, "weighted SADs of a %d-bit block could reach %ld: beyond the cost field", bit_depth, 4096 * span);
-    return HMME_ERR_UNSUPPORTED;
-  }
-  if (refine) {
-    if (4096 * span >= (1L << 24)) {
-      snprintf(msg, n, "weighted refinement: sample differences up to %ld exceed what the Hadamard sums hold exactly", span);
-      return HMME_ERR_UNSUPPORTED;
-    }
-    // me_frac_eval*: fma(w0 * 2^-shift, p, round * 2^-shift) is (w0 * p + round) / 2^shift exactly while the numerator stays below 2^24
-    // (identity weights never meet it: they run the unweighted kernel)
-    if (!identity && std::max(std::labs(p0), std::labs(p1)) >= (1L << 24)) {
-      snprintf(msg, n, "weighted refinement: w0 * sample + round reaches %ld, beyond what fp32 holds exactly", std::max(std::labs(p0), std::labs(p1)));
-      return HMME_ERR_UNSUPPORTED;
-    }
-  }
-  if (info) { info->bias = (int)bias; info->identity = identity; }
+  if (std::min(p0, p1) < INT32_MIN || std::max(p0, p1) > INT32_MAX)
+    return refuse(msg, n, HMME_ERR_UNSUPPORTED, "weighted prediction: w0 * sample + round reaches %ld..%ld, beyond 32 bits", std::min(p0, p1), std::max(p0, p1));
+  WeightRange wr;
+  const int rc = weight_range(wp, 0, maxv, block.lo * maxv, block.hi * maxv, bit_depth - 8, refine != 0, &wr, msg, n);
+  if (rc) return rc;
+  // me_frac_eval*: fma(w0 * 2^-shift, p, round * 2^-shift) is (w0 * p + round) / 2^shift exactly while the numerator stays below 2^24
+  // (identity weights never meet it: they run the unweighted kernel).  The per-CTU calls do not make this check (open points)
+  if (refine && !identity && std::max(std::labs(p0), std::labs(p1)) >= (1L << 24))
+    return refuse(msg, n, HMME_ERR_UNSUPPORTED, "weighted refinement: w0 * sample + round reaches %ld, beyond what fp32 holds exactly", std::max(std::labs(p0), std::labs(p1)));
+  if (info) { info->bias = wr.bias; info->identity = identity; }
   return HMME_OK;
 }
 
@@ -1811,11 +1921,6 @@ inline int run_end(const hmme_weight* wps, int a, int n) {
   int b = wps ? a + 1 : n;
   while (b < n && same_weight(wps[b], wps[a])) ++b;
   return b;
-}
-// frac_wp: weight w on current samples staged with `bias` -- org_sub takes the bias off again, with the weight's offset; null: the weight is 1
-inline hmme::FracWp frac_wp(const hmme_weight* w, int bias) {
-  if (!w) return hmme::FracWp{1.f, 0.f, (float)bias};
-  return hmme::FracWp{std::ldexp((float)w->w0, -w->shift), std::ldexp((float)w->round, -w->shift), (float)(bias + w->offset)};
 }
 
 // geometry of the u16 copies of a launch's planes

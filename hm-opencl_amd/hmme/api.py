@@ -47,7 +47,7 @@ SYMBOLS = ["hmme_create", "hmme_destroy", "hmme_last_error", "hmme_device_info",
 # test / measurement entry points (include/hmme_test.h): not part of the boundary
 TEST_SYMBOLS = ["hmme_test_time_search_kernel", "hmme_test_device_address", "hmme_test_frac_deal", "hmme_test_tail_plan", "hmme_test_stage_layout", "hmme_test_picture_job", "hmme_test_time_weight_passes", "hmme_test_time_bipred_origin",
                 "hmme_test_time_wp_estimate_passes", "hmme_test_pk_gate", "hmme_test_pk_body", "hmme_test_pk_task_marker_free",
-                "hmme_test_wp_parameters", "hmme_test_wp_select"]
+                "hmme_test_wp_parameters", "hmme_test_wp_select", "hmme_test_ctu_plan"]
 ABI_VERSION = 6   # HMME_ABI_VERSION of the include/hmme.h these bindings were written against
 
 
@@ -360,83 +360,52 @@ class Engine:
     def host_unregister(self, array):
         self._check(self.L.hmme_host_unregister(self.h, array.ctypes.data))
 
-    def search_ctu(self, cur_plane, cur_xy, ref_plane, ref_xy, params):
-        """per-CTU drop-in (calcMotionVectors).  planes: 2-D int16; *_xy = CTU origin inside them.
-        -> (mv int16[593,2], sad uint32[593])"""
+    def _ctu(self, fn, cur_plane, cur_xy, ref_plane, ref_xy, params, wp=None, int_mv=None, use_hadamard=None):
+        """the six per-CTU entries.  planes: 2-D int16; *_xy = CTU origin inside them; wp = (w0, offset, shift, round) for a _w entry;
+        int_mv: the caller's integer MVs instead of a search; use_hadamard given: the entry refines.
+        -> the tables of the search (mv int16[593,2], sad uint32[593]), then those of the refinement (qmv int16[593,2] quarter-pel, cost uint32[593])"""
         cur = np.ascontiguousarray(cur_plane, dtype=np.int16)
         ref = np.ascontiguousarray(ref_plane, dtype=np.int16)
-        mv = np.zeros((NUM_PARTS, 2), np.int16)
-        sad = np.zeros(NUM_PARTS, np.uint32)
-        cp = cur.ctypes.data + 2 * (cur_xy[1] * cur.shape[1] + cur_xy[0])
-        rp = ref.ctypes.data + 2 * (ref_xy[1] * ref.shape[1] + ref_xy[0])
-        self._check(self.L.hmme_search_ctu(self.h, cp, cur.shape[1], rp, ref.shape[1], C.byref(params),
-                                           mv.ctypes.data, sad.ctypes.data))
-        return mv, sad
+        args = [self.h, cur.ctypes.data + 2 * (cur_xy[1] * cur.shape[1] + cur_xy[0]), cur.shape[1],
+                ref.ctypes.data + 2 * (ref_xy[1] * ref.shape[1] + ref_xy[0]), ref.shape[1], C.byref(params)]
+        if wp is not None:
+            w = Weight(*[int(v) for v in wp])
+            args.append(C.byref(w))
+        if int_mv is not None:
+            imv = np.ascontiguousarray(int_mv, dtype=np.int16)
+            assert imv.shape == (NUM_PARTS, 2)
+            args.append(imv.ctypes.data)
+        if use_hadamard is not None:
+            args.append(1 if use_hadamard else 0)
+        tables = (int_mv is None) + (use_hadamard is not None)   # a pair of arrays each for the search and the refinement
+        outs = [a for _ in range(tables) for a in (np.zeros((NUM_PARTS, 2), np.int16), np.zeros(NUM_PARTS, np.uint32))]
+        self._check(fn(*args, *[o.ctypes.data for o in outs]))
+        return tuple(outs)
+
+    def search_ctu(self, cur_plane, cur_xy, ref_plane, ref_xy, params):
+        """per-CTU drop-in (calcMotionVectors) -> (mv, sad)"""
+        return self._ctu(self.L.hmme_search_ctu, cur_plane, cur_xy, ref_plane, ref_xy, params)
 
     def search_ctu_w(self, cur_plane, cur_xy, ref_plane, ref_xy, params, wp):
-        """hmme_search_ctu_w: the per-CTU search of a slice with explicit weighted prediction; wp = (w0, offset, shift, round)"""
-        cur = np.ascontiguousarray(cur_plane, dtype=np.int16)
-        ref = np.ascontiguousarray(ref_plane, dtype=np.int16)
-        mv = np.zeros((NUM_PARTS, 2), np.int16)
-        sad = np.zeros(NUM_PARTS, np.uint32)
-        cp = cur.ctypes.data + 2 * (cur_xy[1] * cur.shape[1] + cur_xy[0])
-        rp = ref.ctypes.data + 2 * (ref_xy[1] * ref.shape[1] + ref_xy[0])
-        w = Weight(*[int(v) for v in wp])
-        self._check(self.L.hmme_search_ctu_w(self.h, cp, cur.shape[1], rp, ref.shape[1], C.byref(params), C.byref(w), mv.ctypes.data, sad.ctypes.data))
-        return mv, sad
+        """hmme_search_ctu_w: the per-CTU search of a slice with explicit weighted prediction -> (mv, sad)"""
+        return self._ctu(self.L.hmme_search_ctu_w, cur_plane, cur_xy, ref_plane, ref_xy, params, wp=wp)
 
     def search_refine_ctu_w(self, cur_plane, cur_xy, ref_plane, ref_xy, params, wp, use_hadamard=True):
         """hmme_search_refine_ctu_w: weighted integer search + weighted xPatternSearchFracDIF in one call -> (mv, sad, qmv, cost)"""
-        cur = np.ascontiguousarray(cur_plane, dtype=np.int16)
-        ref = np.ascontiguousarray(ref_plane, dtype=np.int16)
-        mv, qmv = np.zeros((NUM_PARTS, 2), np.int16), np.zeros((NUM_PARTS, 2), np.int16)
-        sad, cost = np.zeros(NUM_PARTS, np.uint32), np.zeros(NUM_PARTS, np.uint32)
-        cp = cur.ctypes.data + 2 * (cur_xy[1] * cur.shape[1] + cur_xy[0])
-        rp = ref.ctypes.data + 2 * (ref_xy[1] * ref.shape[1] + ref_xy[0])
-        w = Weight(*[int(v) for v in wp])
-        self._check(self.L.hmme_search_refine_ctu_w(self.h, cp, cur.shape[1], rp, ref.shape[1], C.byref(params), C.byref(w), 1 if use_hadamard else 0,
-                                                    mv.ctypes.data, sad.ctypes.data, qmv.ctypes.data, cost.ctypes.data))
-        return mv, sad, qmv, cost
+        return self._ctu(self.L.hmme_search_refine_ctu_w, cur_plane, cur_xy, ref_plane, ref_xy, params, wp=wp, use_hadamard=bool(use_hadamard))
 
     def search_refine_ctu(self, cur_plane, cur_xy, ref_plane, ref_xy, params, use_hadamard=True):
-        """hmme_search_ctu + xPatternSearchFracDIF of its winners in one call
-        -> (mv int16[593,2], sad uint32[593], qmv int16[593,2] quarter-pel, cost uint32[593])"""
-        cur = np.ascontiguousarray(cur_plane, dtype=np.int16)
-        ref = np.ascontiguousarray(ref_plane, dtype=np.int16)
-        mv, qmv = np.zeros((NUM_PARTS, 2), np.int16), np.zeros((NUM_PARTS, 2), np.int16)
-        sad, cost = np.zeros(NUM_PARTS, np.uint32), np.zeros(NUM_PARTS, np.uint32)
-        cp = cur.ctypes.data + 2 * (cur_xy[1] * cur.shape[1] + cur_xy[0])
-        rp = ref.ctypes.data + 2 * (ref_xy[1] * ref.shape[1] + ref_xy[0])
-        self._check(self.L.hmme_search_refine_ctu(self.h, cp, cur.shape[1], rp, ref.shape[1], C.byref(params), int(use_hadamard),
-                                                  mv.ctypes.data, sad.ctypes.data, qmv.ctypes.data, cost.ctypes.data))
-        return mv, sad, qmv, cost
+        """hmme_search_ctu + xPatternSearchFracDIF of its winners in one call -> (mv, sad, qmv, cost)"""
+        return self._ctu(self.L.hmme_search_refine_ctu, cur_plane, cur_xy, ref_plane, ref_xy, params, use_hadamard=bool(use_hadamard))
 
     def refine_ctu(self, cur_plane, cur_xy, ref_plane, ref_xy, params, int_mv, use_hadamard=True):
-        """xPatternSearchFracDIF for the 593 slots of one CTU at the caller's integer MVs -> (qmv int16[593,2], cost uint32[593])"""
-        cur = np.ascontiguousarray(cur_plane, dtype=np.int16)
-        ref = np.ascontiguousarray(ref_plane, dtype=np.int16)
-        imv = np.ascontiguousarray(int_mv, dtype=np.int16)
-        assert imv.shape == (NUM_PARTS, 2)
-        qmv, cost = np.zeros((NUM_PARTS, 2), np.int16), np.zeros(NUM_PARTS, np.uint32)
-        cp = cur.ctypes.data + 2 * (cur_xy[1] * cur.shape[1] + cur_xy[0])
-        rp = ref.ctypes.data + 2 * (ref_xy[1] * ref.shape[1] + ref_xy[0])
-        self._check(self.L.hmme_refine_ctu(self.h, cp, cur.shape[1], rp, ref.shape[1], C.byref(params), imv.ctypes.data, int(use_hadamard),
-                                           qmv.ctypes.data, cost.ctypes.data))
-        return qmv, cost
+        """xPatternSearchFracDIF for the 593 slots of one CTU at the caller's integer MVs -> (qmv, cost)"""
+        return self._ctu(self.L.hmme_refine_ctu, cur_plane, cur_xy, ref_plane, ref_xy, params, int_mv=int_mv, use_hadamard=bool(use_hadamard))
 
     def refine_ctu_w(self, cur_plane, cur_xy, ref_plane, ref_xy, params, wp, int_mv, use_hadamard=True):
         """hmme_refine_ctu_w: the weighted xPatternSearchFracDIF alone, at the caller's integer MVs -> (qmv, cost)"""
-        cur = np.ascontiguousarray(cur_plane, dtype=np.int16)
-        ref = np.ascontiguousarray(ref_plane, dtype=np.int16)
-        imv = np.ascontiguousarray(int_mv, dtype=np.int16)
-        assert imv.shape == (NUM_PARTS, 2)
-        qmv, cost = np.zeros((NUM_PARTS, 2), np.int16), np.zeros(NUM_PARTS, np.uint32)
-        cp = cur.ctypes.data + 2 * (cur_xy[1] * cur.shape[1] + cur_xy[0])
-        rp = ref.ctypes.data + 2 * (ref_xy[1] * ref.shape[1] + ref_xy[0])
-        w = Weight(*[int(v) for v in wp])
-        self._check(self.L.hmme_refine_ctu_w(self.h, cp, cur.shape[1], rp, ref.shape[1], C.byref(params), C.byref(w), imv.ctypes.data, int(use_hadamard),
-                                             qmv.ctypes.data, cost.ctypes.data))
-        return qmv, cost
+        return self._ctu(self.L.hmme_refine_ctu_w, cur_plane, cur_xy, ref_plane, ref_xy, params, wp=wp, int_mv=int_mv, use_hadamard=bool(use_hadamard))
+
 
     def search_frame(self, cur, ref, sr, pred_q=None, fen=1, bit_depth=None, ctu_first=0, ctu_count=-1):
         """-> (mv int16[count,593,2], sad uint32[count,593])"""

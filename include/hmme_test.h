@@ -53,6 +53,26 @@ int hmme_test_frac_deal(int k, int n_pairs, int width, int height);
 int hmme_test_picture_job(int job, int ctu_first, int ctu_count, int pic_w, int pic_h, int sr, const int16_t* pred_q, const int16_t* center_q,
                           int16_t* out);
 
+/* The plan of a per-CTU call (hmme_search_ctu, hmme_search_refine_ctu, hmme_refine_ctu and their _w forms) on a context created with sr_max
+ * (hmme.hip ctu_arg_check, ctu_plan_block, ctu_plan_window: the functions the call itself runs; host arithmetic, no device, no context).
+ * mode: HMME_TEST_CTU_SEARCH and / or HMME_TEST_CTU_REFINE, the latter with or without HMME_TEST_CTU_HADAMARD; wp: the weight of a _w
+ * entry, or null; range[4] = the smallest and largest sample of the 64 x 64 block, then of the staged window (what the call scans).
+ * Returns what the call would return for these numbers -- its refusals, in the call's order, with the message in msg (may be null) -- and
+ * for HMME_OK:
+ *   out[17]   = wide (the 16-bit kernels), bias added to the staged samples, 1 for a bi-prediction origin, shift_bd (the sums are shifted by
+ *               shift_bd - 8), halo, rows and columns of the staged window, workgroups n_wg of the search (0: a refinement alone), LDS pitch
+ *               pdw and largest strip smax (16-bit deal; 0 otherwise), the refinement build's (u16 samples, Hadamard, weighted), and the
+ *               task counts of window tiles (0,0), (1,0), (0,1), (1,1) (8-bit deal; 0 otherwise)
+ *   out_fw[3] = the refinement's FracWp (scale, round, what is taken off the current samples); zeros without a weight
+ *   out_wg    = per workgroup 8 values: the window lt_x, lt_y, rb_x, rb_y it searches, its tile's x and y, and its range [y0, y1) -- of
+ *               tasks of that tile (8-bit deal) or of candidate rows (16-bit deal); room for 64 workgroups
+ * HMME_ERR_ARG also for a null p / range / out / out_fw / out_wg, sr_max outside 1..128 or a mode that is none of the six entries'. */
+#define HMME_TEST_CTU_SEARCH 1
+#define HMME_TEST_CTU_REFINE 2
+#define HMME_TEST_CTU_HADAMARD 4
+int hmme_test_ctu_plan(int sr_max, const hmme_search_params* p, int mode, const hmme_weight* wp, const int* range, int* out, float* out_fw,
+                       int16_t* out_wg, char* msg, int msg_len);
+
 /* average device time in ms of the two plane passes of a weighted whole-picture search on their own, `reps` back-to-back launches each on
  * `stream`: *ref_ms = weighting the padded reference plane (me_weight_plane_kernel), *cur_ms = the u16 CTU-blocked copy of the current picture */
 int hmme_test_time_weight_passes(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_weight* wp, void* stream, int reps,

@@ -1,12 +1,15 @@
 // Latency of hmme_search_ctu from C++ (what TEncOpenCL::calcMotionVectors pays per call), without Python in the loop.
 // Build: g++ -O2 -o ctu_latency_cpp tools/ctu_latency.cpp -Iinclude -Lhm-opencl_amd/csrc -lhmme -Wl,-rpath,$PWD/hm-opencl_amd/csrc
+// Usage: ctu_latency_cpp [calls per row, default 200]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 #include "hmme.h"
 
-int main() {
+int main(int argc, char** argv) {
+  const int n = argc > 1 ? atoi(argv[1]) : 200;
+  if (n < 1) { fprintf(stderr, "usage: %s [calls per row]\n", argv[0]); return 1; }
   hmme_ctx* ctx = nullptr;
   if (hmme_create(0, 128, 0, &ctx) != HMME_OK) { fprintf(stderr, "create: %s\n", hmme_last_error(nullptr)); return 1; }
   hmme_set_lambda(ctx, 57.9);
@@ -24,7 +27,6 @@ int main() {
     const int16_t* r0 = ref.data() + (size_t)(c.sr + 8) * side + (c.sr + 8);   // 8 samples of margin: window + refinement halo
     for (int i = 0; i < 5; ++i)
       if (hmme_search_ctu(ctx, cur.data(), 64, r0, side, &p, mv.data(), sad.data()) != HMME_OK) { fprintf(stderr, "%s\n", hmme_last_error(ctx)); return 1; }
-    const int n = 200;
     const auto t0 = std::chrono::steady_clock::now();
     for (int i = 0; i < n; ++i) hmme_search_ctu(ctx, cur.data(), 64, r0, side, &p, mv.data(), sad.data());
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / n;
@@ -64,7 +66,6 @@ int main() {
     hmme_search_params p = {-sr, -sr, sr, sr, 5, -3, 1, 8};
     std::vector<int16_t> mv(2 * HMME_NUM_CTU_PARTS), qmv(2 * HMME_NUM_CTU_PARTS);
     std::vector<uint32_t> sad(HMME_NUM_CTU_PARTS), cost(HMME_NUM_CTU_PARTS);
-    const int n = 200;
     for (int i = 0; i < 5; ++i)
       if (hmme_search_ctu_w(ctx, cur.data(), 64, r0, side, &p, &w, mv.data(), sad.data()) != HMME_OK) { fprintf(stderr, "%s\n", hmme_last_error(ctx)); return 1; }
     auto t0 = std::chrono::steady_clock::now();
