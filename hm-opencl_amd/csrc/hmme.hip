@@ -2327,6 +2327,22 @@ int launch_predict(hmme_ctx* ctx, const hmme_plane* src, const int16_t* d_field,
   HIP_TRY(ctx, hipGetLastError());
   return HMME_OK;
 }
+
+// me_predict4_kernel for CTUs [first, first + count) of a picture like `src`: one MV and one reference index (d_ref_field null: 0) per 4x4
+// block, every plane of `set`; prw: one weight per reference (null: none, and identities)
+int launch_predict4(hmme_ctx* ctx, const hmme_plane* src, const hmme::RefSet& set, int n_refs, const int16_t* d_field, const uint8_t* d_ref_field, int first, int count,
+                    uint8_t* dst, int dst_pitch, hipStream_t s, const hmme::MePredWp<2>* prw) {
+  with_sample_type(src->bps, [&](auto sample) {
+    using T = decltype(sample);
+    const auto go = [&](auto kernel, auto wp) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)count), dim3(256), 0, s, set, n_refs, src->pitch, d_field, d_ref_field, first, src->width, src->height, src->bit_depth, dst,
+                         dst_pitch, wp);
+    };
+    if (prw) go(hmme::me_predict4_kernel<T, 2>, *prw); else go(hmme::me_predict4_kernel<T, 0>, hmme::MePredWp<0>{});
+  });
+  HIP_TRY(ctx, hipGetLastError());
+  return HMME_OK;
+}
 }  // namespace
 
 int hmme_bipred_check(int bit_depth, int refine) {
@@ -2337,13 +2353,15 @@ int hmme_bipred_check(int bit_depth, int refine) {
 namespace {
 // What hmme_predict_pairs_device, _w_device, hmme_predict_refs_device and _w_device check alike, in the order that decides the code returned
 // null_arg: one of the caller's other pointers is null; wps: one weight per plane, or null for none; unit: what a refusal calls plane r
+// the MVs-per-CTU test of a predict entry: the *4 family (four) is the 256 layout and nothing else, every other entry takes 1 or 64
+bool field_form(int mv_per_ctu, bool four) { return four ? mv_per_ctu == 256 : (mv_per_ctu == 1 || mv_per_ctu == 64); }
 struct PredictArgs {
   hmme_frame_params f;   // fp for pairs_begin
   bool identity[hmme::kMaxRefs];
   hmme::MePredWp<1> pw[hmme::kMaxRefs];
 };
 int predict_args(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs, int n, bool null_arg, const hmme_frame_params* fp, const hmme_weight* wps,
-                 const void* d_mv_field, int mv_per_ctu, int out_pitch_bytes, PredictArgs* a, const char* unit = "picture") {
+                 const void* d_mv_field, int mv_per_ctu, int out_pitch_bytes, PredictArgs* a, const char* unit = "picture", bool four = false) {
   int rc = bi_check(ctx, who, fp, 0);
   if (rc) return rc;
   if (!refs || null_arg || n < 1 || n > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d pictures outside 1..%d (or a null argument)", who, n, hmme::kMaxRefs);
@@ -2354,7 +2372,7 @@ int predict_args(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs, 
     rc = other_weight_eval(fp->bit_depth, &wps[r], &a->identity[r], &a->pw[r], msg, sizeof msg);
     if (rc) return fail(ctx, rc, "%s: %s %d: %s", who, unit, r, msg);
   }
-  if (!d_mv_field || (mv_per_ctu != 1 && mv_per_ctu != 64)) return fail(ctx, HMME_ERR_ARG, "%s: null motion field, or %d MVs per CTU (1 or 64)", who, mv_per_ctu);
+  if (!d_mv_field || !field_form(mv_per_ctu, four)) return fail(ctx, HMME_ERR_ARG, "%s: null motion field, or %d MVs per CTU (%s)", who, mv_per_ctu, four ? "256" : "1 or 64");
   for (int r = 0; r < n; ++r)
     if (!refs[r]) return fail(ctx, HMME_ERR_ARG, "%s: null plane", who);
   if (out_pitch_bytes < refs[0]->width * refs[0]->bps) return fail(ctx, HMME_ERR_ARG, "%s: output pitch %d below a picture row", who, out_pitch_bytes);
@@ -2413,6 +2431,9 @@ int launch_chroma(hmme_ctx* ctx, const hmme_plane* p0, const hmme::MeChromaSrc& 
       hipLaunchKernelGGL(kernel, dim3((unsigned)cl.count), dim3(256), 0, s, src, p0->pitch, d_field, cl.first, cl.w, cl.h, p0->bit_depth, (uint8_t*)d_cb, (uint8_t*)d_cr,
                          out_pitch_bytes, wp);
     };
+    if constexpr (FORM == 1) {   // the form with a 4x4 field (hmme_predict_chroma_refs4_device)
+      if (mv_per_ctu == 256) return go(hmme::me_predict_chroma4_kernel<T, WP>);
+    }
     if (mv_per_ctu == 1) go(hmme::me_predict_chroma_kernel<T, FORM, WP, 1>); else go(hmme::me_predict_chroma_kernel<T, FORM, WP, 64>);
   });
   HIP_TRY(ctx, hipGetLastError());
@@ -2456,8 +2477,9 @@ int predict_pairs(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs,
 // sample type, so its depth and every plane's size against the luma size are looked at first.
 bool frame_null_outs(void* const* outs, int comps) { return !outs || !outs[0] || (comps == 2 && !outs[1]); }
 int frame_args(hmme_ctx* ctx, const char* who, const hmme_frame_params* fp, const hmme_plane* const* planes, int n, int comps, bool null_arg, int mv_per_ctu, int width,
-               int height) {
-  if (!planes || null_arg || (mv_per_ctu != 1 && mv_per_ctu != 64)) return fail(ctx, HMME_ERR_ARG, "%s: null argument, or %d MVs per CTU (1 or 64)", who, mv_per_ctu);
+               int height, bool four = false) {
+  if (!planes || null_arg || !field_form(mv_per_ctu, four))
+    return fail(ctx, HMME_ERR_ARG, "%s: null argument, or %d MVs per CTU (%s)", who, mv_per_ctu, four ? "256" : "1 or 64");
   for (int r = 0; r < n; ++r)
     if (!planes[r]) return fail(ctx, HMME_ERR_ARG, "%s: null plane", who);
   if (comps == 1) return HMME_OK;
@@ -2467,14 +2489,14 @@ int frame_args(hmme_ctx* ctx, const char* who, const hmme_frame_params* fp, cons
 // frame_args and the n weights (null: none) of the uni-directional forms.  A luma call answers for a weight before its arguments, a chroma
 // call behind them: what each did when it was written, and what tests/test_gpu_predict_refusal_order.py pins.
 int frame_checks(hmme_ctx* ctx, const char* who, const hmme_frame_params* fp, const hmme_plane* const* planes, int n, int comps, bool null_arg, int mv_per_ctu, int width,
-                 int height, const hmme_weight* wps, const char* unit) {
-  int rc = comps == 2 ? frame_args(ctx, who, fp, planes, n, comps, null_arg, mv_per_ctu, width, height) : HMME_OK;
+                 int height, const hmme_weight* wps, const char* unit, bool four = false) {
+  int rc = comps == 2 ? frame_args(ctx, who, fp, planes, n, comps, null_arg, mv_per_ctu, width, height, four) : HMME_OK;
   for (int r = 0; rc == HMME_OK && wps && r < n; ++r) {
     char msg[256];
     rc = other_weight_eval(fp->bit_depth, &wps[r], nullptr, nullptr, msg, sizeof msg);
     if (rc) return fail(ctx, rc, "%s: %s %d: %s", who, unit, r, msg);
   }
-  if (rc == HMME_OK && comps == 1) rc = frame_args(ctx, who, fp, planes, n, comps, null_arg, mv_per_ctu, width, height);
+  if (rc == HMME_OK && comps == 1) rc = frame_args(ctx, who, fp, planes, n, comps, null_arg, mv_per_ctu, width, height, four);
   return rc;
 }
 // hmme_predict_frame, _w, hmme_predict_refs_frame, hmme_predict_bi_frame and their chroma forms through the staging arena: up go the motion
@@ -3255,12 +3277,15 @@ namespace {
 // hmme_predict_refs_device (wps == null), _w_device and hmme_predict_chroma_refs_device: ONE launch, every block from the plane (pair) its
 // reference index names.  WP = 0 without weights and where every weight is the identity, else 2: every block through addWeightUni with its
 // plane's weight (for an identity weight that is the unweighted sample: nested floors).  d_out_cr: the second image of comps == 2
+// four: hmme_predict_refs4_device and hmme_predict_chroma_refs4_device -- mv_per_ctu is 256, the reference field may be null (every block
+// index 0), and the kernels are me_predict4_kernel / me_predict_chroma4_kernel
 int predict_refs(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs, int n_refs, int comps, int width, int height, const hmme_frame_params* fp,
-                 const hmme_weight* wps, const void* d_mv_field, const void* d_ref_field, int mv_per_ctu, void* d_out, void* d_out_cr, int out_pitch_bytes, void* stream) {
+                 const hmme_weight* wps, const void* d_mv_field, const void* d_ref_field, int mv_per_ctu, void* d_out, void* d_out_cr, int out_pitch_bytes, void* stream,
+                 bool four = false) {
   const int np = comps * n_refs;
   PredictArgs a;
-  int rc = predict_args(ctx, who, refs, np, !d_ref_field || !d_out || (comps == 2 && !d_out_cr), fp, wps, d_mv_field, mv_per_ctu, out_pitch_bytes, &a,
-                        comps == 2 ? "plane" : "reference");
+  int rc = predict_args(ctx, who, refs, np, (!four && !d_ref_field) || !d_out || (comps == 2 && !d_out_cr), fp, wps, d_mv_field, mv_per_ctu, out_pitch_bytes, &a,
+                        comps == 2 ? "plane" : "reference", four);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   PredictLaunch L;
@@ -3274,7 +3299,10 @@ int predict_refs(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs, 
       weighted = weighted || !a.identity[r];
       if (wps) prw.ref[r] = cprw.ref[r] = a.pw[r];
     }
-    if (comps == 1) {
+    if (comps == 1 && four) {
+      rc = launch_predict4(ctx, refs[0], L.pl.refs, n_refs, (const int16_t*)d_mv_field, (const uint8_t*)d_ref_field, L.first, L.count, (uint8_t*)d_out, out_pitch_bytes, s,
+                           weighted ? &prw : nullptr);
+    } else if (comps == 1) {
       const hmme::MePredRefs<1> pr = {L.pl.refs, (const uint8_t*)d_ref_field, n_refs};
       rc = launch_predict(ctx, refs[0], (const int16_t*)d_mv_field, mv_per_ctu, L.first, L.count, false, nullptr, 0, (uint8_t*)d_out, 0, 0, out_pitch_bytes, s, nullptr, &pr,
                           weighted ? &prw : nullptr);
@@ -3287,19 +3315,20 @@ int predict_refs(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs, 
   return pairs_end(ctx, refs, refs, np, s, rc);   // whatever the launch returned: the scratch is acquired
 }
 
-// hmme_predict_refs_frame (wps == null), _w_frame and hmme_predict_chroma_refs_frame
+// hmme_predict_refs_frame (wps == null), _w_frame and hmme_predict_chroma_refs_frame; four: hmme_predict_refs4_frame and
+// hmme_predict_chroma_refs4_frame, as in predict_refs
 int predict_refs_frame(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs, int n_refs, int comps, int width, int height, const hmme_frame_params* fp,
-                       const hmme_weight* wps, const int16_t* mv_field, const uint8_t* ref_field, int mv_per_ctu, void* const* outs, int out_stride) {
+                       const hmme_weight* wps, const int16_t* mv_field, const uint8_t* ref_field, int mv_per_ctu, void* const* outs, int out_stride, bool four = false) {
   int rc = bi_check(ctx, who, fp, 0);
   if (rc) return rc;
   if (!refs || n_refs < 1 || comps * n_refs > hmme::kMaxRefs || !refs[0])
     return fail(ctx, HMME_ERR_ARG, "%s: %d reference pictures outside 1..%d (or a null plane)", who, n_refs, hmme::kMaxRefs / comps);
-  rc = frame_checks(ctx, who, fp, refs, comps * n_refs, comps, !mv_field || !ref_field || frame_null_outs(outs, comps), mv_per_ctu, width, height, wps,
-                    comps == 2 ? "plane" : "reference");
+  rc = frame_checks(ctx, who, fp, refs, comps * n_refs, comps, !mv_field || (!four && !ref_field) || frame_null_outs(outs, comps), mv_per_ctu, width, height, wps,
+                    comps == 2 ? "plane" : "reference", four);
   if (rc) return rc;
   // blocks without a reference, too, come back as they were
   return frame_staged(ctx, who, refs[0], comps, width, height, mv_field, ref_field, mv_per_ctu, outs, out_stride, 1, [&](void* d_field, void* d_ref_field, void* const* d_outs, int pitch, hipStream_t s) {
-    return predict_refs(ctx, who, refs, n_refs, comps, width, height, fp, wps, d_field, d_ref_field, mv_per_ctu, d_outs[0], comps == 2 ? d_outs[1] : nullptr, pitch, s);
+    return predict_refs(ctx, who, refs, n_refs, comps, width, height, fp, wps, d_field, d_ref_field, mv_per_ctu, d_outs[0], comps == 2 ? d_outs[1] : nullptr, pitch, s, four);
   });
 }
 }  // namespace
@@ -3328,6 +3357,33 @@ int hmme_predict_refs_w_frame(hmme_ctx* ctx, const hmme_plane* const* refs, int 
   if (!ctx) return HMME_ERR_ARG;
   if (!wps) return fail(ctx, HMME_ERR_ARG, "hmme_predict_refs_w_frame: null weights");
   return predict_refs_frame(ctx, "hmme_predict_refs_w_frame", refs, n_refs, 1, 0, 0, fp, wps, mv_field, ref_field, mv_per_ctu, &out, out_stride);
+}
+
+// ---- prediction from one MV per 4x4 block: the refs forms on the 256 layout, weights and the reference field optional ---------------------
+int hmme_predict_refs4_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp, const hmme_weight* wps,
+                              const void* d_mv_field, const void* d_ref_field, void* d_out, int out_pitch_bytes, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  return predict_refs(ctx, "hmme_predict_refs4_device", refs, n_refs, 1, 0, 0, fp, wps, d_mv_field, d_ref_field, 256, d_out, nullptr, out_pitch_bytes, stream, true);
+}
+
+int hmme_predict_refs4_frame(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp, const hmme_weight* wps,
+                             const int16_t* mv_field, const uint8_t* ref_field, void* out, int out_stride) {
+  if (!ctx) return HMME_ERR_ARG;
+  return predict_refs_frame(ctx, "hmme_predict_refs4_frame", refs, n_refs, 1, 0, 0, fp, wps, mv_field, ref_field, 256, &out, out_stride, true);
+}
+
+int hmme_predict_chroma_refs4_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, int width, int height, const hmme_frame_params* fp,
+                                     const hmme_weight* wps, const void* d_mv_field, const void* d_ref_field, void* d_out_cb, void* d_out_cr, int out_pitch_bytes,
+                                     void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  return predict_refs(ctx, "hmme_predict_chroma_refs4_device", refs, n_refs, 2, width, height, fp, wps, d_mv_field, d_ref_field, 256, d_out_cb, d_out_cr, out_pitch_bytes,
+                      stream, true);
+}
+
+int hmme_predict_chroma_refs4_frame(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, int width, int height, const hmme_frame_params* fp,
+                                    const hmme_weight* wps, const int16_t* mv_field, const uint8_t* ref_field, void* const* outs, int out_stride) {
+  if (!ctx) return HMME_ERR_ARG;
+  return predict_refs_frame(ctx, "hmme_predict_chroma_refs4_frame", refs, n_refs, 2, width, height, fp, wps, mv_field, ref_field, 256, outs, out_stride, true);
 }
 
 // ---- L0, L1 or bi per PU: the decision over the four table sets of a B picture, and the prediction that follows it ---------------------------

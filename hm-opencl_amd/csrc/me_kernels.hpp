@@ -2504,6 +2504,116 @@ me_predict_kernel(const uint8_t* __restrict__ ref_origin, int ref_pitch, const i
   }
 }
 
+// ---- the luma prediction from one MV per 4x4 block (hmme_predict_refs4_device; the rule: include/hmme.h) ---------------------------------
+// me_predict_kernel<SrcT, 0, WP, 1> with HM's own motion storage: mv_field int16 [n_ctu][256][2], ref_field uint8 [n_ctu][256] (null: every
+// block index 0), entry b the 4x4 block at ((b & 15) * 4, (b >> 4) * 4) of the CTU.  One CTU per workgroup of four waves, a wave one 8x8
+// block at a time, lane (r, c) = (lane >> 3, lane & 7) one sample -- but the block is four QUADRANTS, lane (r, c) in quadrant
+// (r >> 2) * 2 + (c >> 2), each with its own entry: its own clamped MV (me_field_mv: the CTU's clamp, so the sample is the one the 64 form
+// writes when the 8x8 block carries this entry), its own plane, its own weight.
+//   stage       per quadrant the 11 x 11 patch at its MV -- rows / columns -3 .. +7 around the displaced 4x4 block, a subset of the 15 x 15
+//               patch the 64 form reads at that MV, so the planes' margins hold -- into wave-private LDS: four patches of 11 rows, pitch 12.
+//               Quadrant by quadrant, so MV, plane and liveness of a load are scalars (readlane of the quadrant's first lane).
+//   horizontal  the 14-bit intermediate, 11 rows x 4 columns per quadrant, 176 outputs per wave in three steps; the taps are chosen per
+//               lane by the output's quadrant (packed taps in LDS: two dwords per phase)
+//   vertical    lane (r, c): eight rows of its quadrant's intermediate with the taps of its own vertical phase
+//   tail        me_tail_uni (WP = 0) or me_tail_weight_uni with the weight of the lane's reference (WP = 2).  Index and weight are per
+//               lane, not per wave: the weights are staged into LDS, which keeps the kernel arguments out of scratch.
+// Pitch 12, not 11: rows stay dword-aligned and a quadrant's patch starts 66 dwords after the one before, two banks further; with either
+// pitch the 8 rows x 4 lanes of a half-wave's u16 reads span more than 32 banks and wrap once.  Measured: a pitch of 11 gives the same
+// times within 1 % (profiles/predict4_patch_pitch_ab.txt).
+// A quadrant is live if its 4x4 block starts inside the picture and its index is < n_refs; one that is not reads no plane and its lanes
+// write nothing.
+// BARRIER INVARIANT: __syncthreads() is a barrier of the whole workgroup.  Every wave -- live, partly live or wholly dead -- runs all 16
+// iterations and meets the same two barriers in each: stage | barrier | horizontal | barrier | vertical.  Everything that depends on the
+// field (liveness, the plane, the phase) sits INSIDE a stage; no barrier is ever inside a branch, and no wave leaves the loop early.
+template <typename SrcT, int WP>
+__global__ void __launch_bounds__(256)
+me_predict4_kernel(RefSet set, int n_refs, int ref_pitch, const int16_t* __restrict__ mv_field, const uint8_t* __restrict__ ref_field, int ctu_first,
+                   int pic_w, int pic_h, int bit_depth, uint8_t* __restrict__ dst, int dst_pitch, MePredWp<WP> wp) {
+  static_assert(WP == 0 || WP == 2, "one weight per reference, or none");
+  __shared__ int16_t patch[4][4 * 11 * 12];
+  __shared__ int16_t mid[4][4 * 11 * 4];
+  __shared__ uint32_t taps[4][2];   // kLumaTaps, tap j of a phase = signed byte j of the pair; read behind the first barrier
+  __shared__ int s_weights[kMaxRefs * 4];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (threadIdx.x < 8) {
+    uint32_t p = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) p |= (uint32_t)(uint8_t)kLumaTaps[threadIdx.x >> 1][4 * (threadIdx.x & 1) + j] << (8 * j);
+    taps[threadIdx.x >> 1][threadIdx.x & 1] = p;
+  }
+  if constexpr (WP == 2) {
+    if (threadIdx.x < kMaxRefs * 4) s_weights[threadIdx.x] = ((const int*)wp.ref)[threadIdx.x];
+  }
+  const int ctus_x = (pic_w + 63) >> 6;
+  const int ctu = ctu_first + blockIdx.x;
+  const int cx = ctu % ctus_x, cy = ctu / ctus_x, cu_x = cx * 64, cu_y = cy * 64;
+  const MePredConst k(bit_depth);
+  const int r = lane >> 3, c = lane & 7, q = (r >> 2) * 2 + (c >> 2);
+  int16_t* const wpatch = patch[wave];
+  int16_t* const wmid = mid[wave];
+#pragma unroll 1
+  for (int it = 0; it < 16; ++it) {
+    const int b = it * 4 + wave, bx = (b & 7) * 8, by = (b >> 3) * 8;   // the four waves: four 8x8 blocks side by side
+    const int qx = bx + (c & 4), qy = by + (r & 4);                      // this lane's 4x4 block inside the CTU
+    const long e = (long)ctu * 256 + (qy >> 2) * 16 + (qx >> 2);
+    int ri = ref_field ? (int)ref_field[e] : 0;
+    const bool live = cu_x + qx < pic_w && cu_y + qy < pic_h && ri < n_refs;
+    int mx = 0, my = 0;
+    if (live) me_field_mv(mv_field, e, cu_x, cu_y, pic_w, pic_h, mx, my);
+    else ri = 0;
+    // stage: quadrant s from the entry of its first lane
+    int info[4];   // scalars: 4 | horizontal phase of a live quadrant, else 0
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const int from = (s >> 1) * 32 + (s & 1) * 4;
+      const int s_live = __builtin_amdgcn_readlane((int)live, from), s_mx = __builtin_amdgcn_readlane(mx, from);
+      const int s_my = __builtin_amdgcn_readlane(my, from), s_ri = __builtin_amdgcn_readlane(ri, from);
+      info[s] = s_live ? 4 | (s_mx & 3) : 0;
+      if (s_live) {
+        const uint8_t* src = set.base[s_ri] + (long)(cu_y + by + (s >> 1) * 4 + (s_my >> 2) - 3) * ref_pitch +
+                             (long)(cu_x + bx + (s & 1) * 4 + (s_mx >> 2) - 3) * (long)sizeof(SrcT);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int el = lane + 64 * j, pr = el / 11, pc = el - pr * 11;
+          if (el < 121) wpatch[s * 132 + pr * 12 + pc] = (int16_t)((const SrcT*)(src + (long)pr * ref_pitch))[pc];
+        }
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const int o = lane + 64 * j, oq = o / 44, rem = o - oq * 44;   // output (row rem >> 2, column rem & 3) of quadrant oq
+      const int inf = oq == 0 ? info[0] : (oq == 1 ? info[1] : (oq == 2 ? info[2] : info[3]));
+      if (o < 176 && inf) {
+        const uint32_t lo = taps[inf & 3][0], hi = taps[inf & 3][1];
+        const int16_t* p = wpatch + oq * 132 + (rem >> 2) * 12 + (rem & 3);
+        int sum = 0;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) sum += (int)(int8_t)(lo >> (8 * t)) * (int)p[t] + (int)(int8_t)(hi >> (8 * t)) * (int)p[t + 4];
+        wmid[o] = (int16_t)((sum + k.off1) >> k.sh1);
+      }
+    }
+    __syncthreads();
+    if (live) {
+      const uint32_t lo = taps[my & 3][0], hi = taps[my & 3][1];
+      const int16_t* p = wmid + q * 44 + (r & 3) * 4 + (c & 3);
+      int sum = 0;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) sum += (int)(int8_t)(lo >> (8 * t)) * (int)p[4 * t] + (int)(int8_t)(hi >> (8 * t)) * (int)p[4 * (t + 4)];
+      int v;
+      if constexpr (WP == 2) {
+        const int* a = s_weights + 4 * ri;   // {w0, round, shift, offset} of MePredWp<1>
+        v = me_tail_weight_uni(sum, MePredWp<1>{a[0], a[1], a[2], a[3]}, k.maxv);
+      } else {
+        v = me_tail_uni(sum, k);
+      }
+      const int x = cu_x + bx + c, y = cu_y + by + r;
+      if (x < pic_w && y < pic_h) ((SrcT*)(dst + (long)y * dst_pitch))[x] = (SrcT)v;
+    }
+  }
+}
+
 // ---- partition decision and motion field from the 593-slot tables (hmme_select_pairs_device; the rule: include/hmme.h) ------------------
 // hmme_select_params as the kernel takes it
 struct MeSelect {
@@ -3388,6 +3498,102 @@ me_predict_chroma_kernel(MeChromaSrc src, int ref_pitch, const int16_t* __restri
         }
       }
       const int x = x0 + (l16 & 3), y = y0 + (l16 >> 2);
+      if (x < (pic_w >> 1) && y < (pic_h >> 1)) ((SrcT*)(dst + (long)y * dst_pitch))[x] = (SrcT)v;
+    }
+  }
+}
+
+// FORM 1 from one MV per 4x4 LUMA block (hmme_predict_chroma_refs4_device): mv_field int16 [n_ctu][256][2], src.field uint8 [n_ctu][256]
+// (null: every block index 0).  The lanes are those of me_predict_chroma_kernel -- a 16-lane group owns the 4x4 block of one component of
+// one 8x8 luma block, lane l16 = 4 r + c one sample, eight iterations per CTU -- but the block is four 2x2 QUADS, lane (r, c) in quad
+// (r >> 1) * 2 + (c >> 1), each the chroma of one 4x4 luma block with that block's MV (the CTU's clamp), reference index and the
+// component's weight of that reference: sample for sample what the 64 form writes when the 8x8 luma block carries the entry.
+//   stage       per quad the 5 x 5 patch at its MV -- rows / columns -1 .. +3 around the displaced 2x2 block, a subset of the 7 x 7 patch of
+//               the 64 form at that MV -- into the group's LDS, quad by quad; a quad's entry comes from its first lane (__shfl)
+//   horizontal  5 rows x 2 columns per quad, 40 outputs per group in three steps, taps by the output's quad
+//   vertical    lane (r, c): four rows of its quad's intermediate; then me_tail_uni (WP = 0) or me_tail_weight_uni with the weight of plane
+//               2 * index + component (WP = 2), staged into LDS because the index is per lane
+// A quad is live if its 4x4 luma block starts inside the luma picture and its index is < n_refs.  The BARRIER INVARIANT is
+// me_predict4_kernel's: every group of every wave runs all eight iterations and meets the same two barriers in each, whatever the field
+// holds; no barrier is inside a branch.
+template <typename SrcT, int WP>
+__global__ void __launch_bounds__(256)
+me_predict_chroma4_kernel(MeChromaSrc src, int ref_pitch, const int16_t* __restrict__ mv_field, int ctu_first, int pic_w, int pic_h, int bit_depth,
+                          uint8_t* __restrict__ dst_cb, uint8_t* __restrict__ dst_cr, int dst_pitch, MeChromaWp<1, WP> wp) {
+  static_assert(WP == 0 || WP == 2, "one weight per plane, or none");
+  __shared__ int16_t patch[16][4 * 25];
+  __shared__ int16_t mid[16][4 * 10];
+  __shared__ uint32_t taps[8];
+  __shared__ int s_weights[kMaxRefs * 4];
+  const int group = threadIdx.x >> 4, l16 = threadIdx.x & 15, comp = group & 1, lane = threadIdx.x & 63;
+  if (threadIdx.x < 8) taps[threadIdx.x] = kChromaTaps[threadIdx.x];   // read behind the first barrier
+  if constexpr (WP == 2) {
+    if (threadIdx.x < kMaxRefs * 4) s_weights[threadIdx.x] = ((const int*)wp.ref)[threadIdx.x];
+  }
+  const int ctus_x = (pic_w + 63) >> 6;
+  const int ctu = ctu_first + blockIdx.x;
+  const int cx = ctu % ctus_x, cy = ctu / ctus_x, cu_x = cx * 64, cu_y = cy * 64;
+  const MePredConst k(bit_depth);
+  uint8_t* const dst = comp ? dst_cr : dst_cb;
+  const int r = l16 >> 2, c = l16 & 3, q = (r >> 1) * 2 + (c >> 1);
+  int16_t* const gpatch = patch[group];
+  int16_t* const gmid = mid[group];
+#pragma unroll 1
+  for (int it = 0; it < 8; ++it) {
+    const int bx = (group >> 1) * 8, by = it * 8;                        // the group's 8x8 luma block: a block row per iteration
+    const int qx = bx + (c >> 1) * 4, qy = by + (r >> 1) * 4;           // this lane's 4x4 luma block inside the CTU
+    const long e = (long)ctu * 256 + (qy >> 2) * 16 + (qx >> 2);
+    const int x0 = (cu_x + bx) >> 1, y0 = (cu_y + by) >> 1;
+    int sel = src.field ? (int)src.field[e] : 0;
+    const bool live = cu_x + qx < pic_w && cu_y + qy < pic_h && sel < src.n_refs;
+    int mx = 0, my = 0;
+    if (live) me_field_mv(mv_field, e, cu_x, cu_y, pic_w, pic_h, mx, my);
+    else sel = 0;
+    int info[4];   // per group: 8 | horizontal phase of a live quad, else 0
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const int from = (lane & 48) + (s >> 1) * 8 + (s & 1) * 2;
+      const int s_live = __shfl((int)live, from), s_mx = __shfl(mx, from), s_my = __shfl(my, from), s_sel = __shfl(sel, from);
+      info[s] = s_live ? 8 | (s_mx & 7) : 0;
+      if (s_live) {
+        const uint8_t* p = src.set.base[2 * s_sel + comp] + (long)(y0 + (s >> 1) * 2 + (s_my >> 3) - 1) * ref_pitch +
+                           (long)(x0 + (s & 1) * 2 + (s_mx >> 3) - 1) * (long)sizeof(SrcT);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int el = l16 + 16 * j, pr = el / 5, pc = el - pr * 5;
+          if (el < 25) gpatch[s * 25 + el] = (int16_t)((const SrcT*)(p + (long)pr * ref_pitch))[pc];
+        }
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const int o = l16 + 16 * j, oq = o / 10, rem = o - oq * 10;   // output (row rem >> 1, column rem & 1) of quad oq
+      const int inf = oq == 0 ? info[0] : (oq == 1 ? info[1] : (oq == 2 ? info[2] : info[3]));
+      if (o < 40 && inf) {
+        const uint32_t th = taps[inf & 7];
+        const int16_t* p = gpatch + oq * 25 + (rem >> 1) * 5 + (rem & 1);
+        int sum = 0;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) sum += (int)(int8_t)(th >> (8 * t)) * (int)p[t];
+        gmid[o] = (int16_t)((sum + k.off1) >> k.sh1);
+      }
+    }
+    __syncthreads();
+    if (live) {
+      const uint32_t tv = taps[my & 7];
+      const int16_t* p = gmid + q * 10 + (r & 1) * 2 + (c & 1);
+      int sum = 0;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) sum += (int)(int8_t)(tv >> (8 * t)) * (int)p[2 * t];
+      int v;
+      if constexpr (WP == 2) {
+        const int* a = s_weights + 4 * (2 * sel + comp);   // {w0, round, shift, offset} of MePredWp<1>
+        v = me_tail_weight_uni(sum, MePredWp<1>{a[0], a[1], a[2], a[3]}, k.maxv);
+      } else {
+        v = me_tail_uni(sum, k);
+      }
+      const int x = x0 + c, y = y0 + r;
       if (x < (pic_w >> 1) && y < (pic_h >> 1)) ((SrcT*)(dst + (long)y * dst_pitch))[x] = (SrcT)v;
     }
   }

@@ -35,6 +35,7 @@ SYMBOLS = ["hmme_create", "hmme_destroy", "hmme_last_error", "hmme_device_info",
            "hmme_predict_bi_weight_check", "hmme_predict_bi_w_device", "hmme_predict_bi_w_frame", "hmme_predict_refs_w_device", "hmme_predict_refs_w_frame",
            "hmme_plane_stats", "hmme_wp_estimate", "hmme_wp_estimate_420",
            "hmme_predict_chroma_pairs_device", "hmme_predict_chroma_frame", "hmme_predict_chroma_refs_device", "hmme_predict_chroma_refs_frame",
+           "hmme_predict_refs4_device", "hmme_predict_refs4_frame", "hmme_predict_chroma_refs4_device", "hmme_predict_chroma_refs4_frame",
            "hmme_predict_chroma_bi_device", "hmme_predict_chroma_bi_frame",
            "hmme_residual_pairs_device", "hmme_residual_frame",
            "hmme_search_frame_bi_refs_device", "hmme_refine_frame_bi_refs_device", "hmme_search_frame_bi_refs", "hmme_refine_frame_bi_refs",
@@ -230,6 +231,10 @@ def load():
     L.hmme_predict_chroma_frame.argtypes = [vp, C.POINTER(vp), i, i, C.POINTER(FrameParams), pw, vp, i, C.POINTER(vp), i]
     L.hmme_predict_chroma_refs_device.argtypes = [vp, C.POINTER(vp), i, i, i, C.POINTER(FrameParams), pw, vp, vp, i, vp, vp, i, vp]
     L.hmme_predict_chroma_refs_frame.argtypes = [vp, C.POINTER(vp), i, i, i, C.POINTER(FrameParams), pw, vp, vp, i, C.POINTER(vp), i]
+    L.hmme_predict_refs4_device.argtypes = [vp, C.POINTER(vp), i, C.POINTER(FrameParams), pw, vp, vp, vp, i, vp]
+    L.hmme_predict_refs4_frame.argtypes = [vp, C.POINTER(vp), i, C.POINTER(FrameParams), pw, vp, vp, vp, i]
+    L.hmme_predict_chroma_refs4_device.argtypes = [vp, C.POINTER(vp), i, i, i, C.POINTER(FrameParams), pw, vp, vp, vp, vp, i, vp]
+    L.hmme_predict_chroma_refs4_frame.argtypes = [vp, C.POINTER(vp), i, i, i, C.POINTER(FrameParams), pw, vp, vp, C.POINTER(vp), i]
     L.hmme_predict_chroma_bi_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, i, i, C.POINTER(FrameParams), pw, pw, vp, vp, i, C.POINTER(vp), i, vp]
     L.hmme_predict_chroma_bi_frame.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, i, C.POINTER(FrameParams), pw, pw, vp, vp, i, C.POINTER(vp), i]
     L.hmme_residual_pairs_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, i, C.POINTER(FrameParams), vp, i, i, C.POINTER(vp), i, vp, vp, vp, vp]
@@ -1039,6 +1044,53 @@ class Engine:
         cb, cr, oa = self._chroma_images(refs[0], outs)
         self._check(self.L.hmme_predict_chroma_refs_frame(self.h, _handles(refs), len(refs) // 2, int(width), int(height), C.byref(fp),
                                                           self._weights_or_none(weights, len(refs)), f.ctypes.data, rf.ctypes.data, per, oa, cb.shape[1]))
+        return cb, cr
+
+    # ---- prediction from one MV per 4x4 block (include/hmme.h, "prediction from one MV per 4x4 block"): the refs forms on the 256 layout --
+    # what select_frame / select_refs_frame write with mv_per_ctu = 256; the reference field and the weights are optional
+    def _field4(self, width, height, mv_field, ref_field):
+        """host fields of the 256 layout: int16[n_ctu, 256, 2] and uint8[n_ctu, 256] or None -> (field, reference field or None, its address)"""
+        n = self.L.hmme_num_ctus(int(width), int(height))
+        f = np.ascontiguousarray(mv_field, dtype=np.int16)
+        assert f.shape == (n, 256, 2)
+        if ref_field is None:
+            return f, None, None
+        rf = np.ascontiguousarray(ref_field, dtype=np.uint8)
+        assert rf.shape == (n, 256)
+        return f, rf, rf.ctypes.data
+
+    def predict_refs4_device(self, refs, fp, d_mv_field, d_ref_field, d_out, out_pitch_bytes, weights=None, stream=0):
+        """hmme_predict_refs4_device: the luma prediction of one picture from d_mv_field int16[n_ctu, 256, 2] and d_ref_field uint8[n_ctu, 256]
+        (None: every block from refs[0]); weights = one (w0, offset, shift, round) per reference or None; d_out = the device image"""
+        self._check(self.L.hmme_predict_refs4_device(self.h, _handles(refs), len(refs), C.byref(fp), self._weights_or_none(weights, len(refs)), d_mv_field,
+                                                     d_ref_field, d_out, int(out_pitch_bytes), stream))
+
+    def predict_refs4_frame(self, refs, mv_field, ref_field=None, out=None, weights=None, ctu_first=0, ctu_count=-1):
+        """hmme_predict_refs4_frame: predict_refs_frame (with weights: predict_refs_w_frame) from one MV and one reference index per 4x4 block ->
+        [height, width] array of the planes' sample type; `out` keeps its samples outside the CTU range and in blocks that are not live"""
+        r0 = refs[0]
+        f, rf, rf_ptr = self._field4(r0.width, r0.height, mv_field, ref_field)
+        out = self._image(r0, out)
+        fp = FrameParams(1, 0, r0.bit_depth, ctu_first, ctu_count)
+        self._check(self.L.hmme_predict_refs4_frame(self.h, _handles(refs), len(refs), C.byref(fp), self._weights_or_none(weights, len(refs)), f.ctypes.data, rf_ptr,
+                                                    out.ctypes.data, out.shape[1]))
+        return out
+
+    def predict_chroma_refs4_device(self, refs, width, height, fp, d_mv_field, d_ref_field, d_out_cb, d_out_cr, out_pitch_bytes, weights=None, stream=0):
+        """hmme_predict_chroma_refs4_device: predict_chroma_refs_device from the fields of the 256 layout; refs = [cb0, cr0, cb1, ...], up to 8 references"""
+        assert len(refs) % 2 == 0
+        self._check(self.L.hmme_predict_chroma_refs4_device(self.h, _handles(refs), len(refs) // 2, int(width), int(height), C.byref(fp),
+                                                            self._weights_or_none(weights, len(refs)), d_mv_field, d_ref_field, d_out_cb, d_out_cr, int(out_pitch_bytes),
+                                                            stream))
+
+    def predict_chroma_refs4_frame(self, refs, width, height, mv_field, ref_field=None, outs=None, weights=None, ctu_first=0, ctu_count=-1):
+        """hmme_predict_chroma_refs4_frame: predict_refs4_frame for Cb and Cr; refs = [cb0, cr0, cb1, cr1, ...] -> (cb, cr)"""
+        assert len(refs) % 2 == 0
+        f, rf, rf_ptr = self._field4(width, height, mv_field, ref_field)
+        cb, cr, oa = self._chroma_images(refs[0], outs)
+        fp = FrameParams(1, 0, refs[0].bit_depth, ctu_first, ctu_count)
+        self._check(self.L.hmme_predict_chroma_refs4_frame(self.h, _handles(refs), len(refs) // 2, int(width), int(height), C.byref(fp),
+                                                           self._weights_or_none(weights, len(refs)), f.ctypes.data, rf_ptr, oa, cb.shape[1]))
         return cb, cr
 
     def predict_chroma_bi_device(self, refs0, refs1, width, height, fp, d_mv_field, d_dir_field, mv_per_ctu, d_outs, out_pitch_bytes, weights0=None, weights1=None,

@@ -1015,6 +1015,61 @@ int hmme_predict_chroma_bi_refs_frame(hmme_ctx* ctx, const hmme_plane* const* re
                                       const hmme_frame_params* fp, const hmme_weight* wps0, const hmme_weight* wps1, const int16_t* mv_field, const uint8_t* dir_field,
                                       const uint8_t* ref_field, int mv_per_ctu, void* const* outs, int out_stride);
 
+/* ---- prediction from one MV per 4x4 block: all 593 PU shapes of a P picture ------------------------------------------------
+ * hmme_select_pairs_device and hmme_select_refs_device with mv_per_ctu = 256 write HM's own motion storage -- one (MV, reference index)
+ * per 4x4 block -- and only there all 593 slots take part (8x4 / 4x8 PUs of an 8x8 CU, AMP at 16x16).  The calls below compensate such a
+ * decision on the device, for Y and for the Cb / Cr of a 4:2:0 picture, uni-directionally with a reference per block and optional
+ * weights: what a P picture needs between the decision and hmme_residual_pairs_device's 256 form.  New entry points only; no struct and no
+ * existing entry point changed (every existing hmme_predict_* call still refuses 256 MVs per CTU), so HMME_ABI_VERSION stays 6.  THIS
+ * TEXT PLUS THE CITATIONS IS THE RULE (paths below source/Lib/TLibCommon/ of the reference).
+ *
+ * Fields.  There is no mv_per_ctu argument: the family IS the 256 layout.  d_mv_field int16[n_ctu][256][2], quarter-pel luma MVs;
+ * d_ref_field uint8[n_ctu][256], or NULL: every block has index 0.  Entry b of a CTU is the 4x4 luma block at ((b & 15) * 4, (b >> 4) * 4),
+ * as the select calls write it; n_ctu counts all CTUs of the picture.  n_refs is 1..16 for luma and 1..8 for chroma (16 planes per launch,
+ * as in the existing chroma calls).  With n_refs = 1 and a NULL reference field the luma call is the hmme_predict_pairs_device /
+ * hmme_predict_pairs_w_device form for one picture: what hmme_select_pairs_device at 256 feeds.
+ *
+ * Liveness.  A 4x4 block is live if it starts inside the luma picture and its index is < n_refs; 0xFF and every index >= n_refs is not
+ * live.  A block that is not live reads no plane and writes nothing.
+ *
+ * Samples of a live block.  Its MV is clamped exactly as in hmme_predict_refs_device: TComDataCU::clipMv with the CTU's position.  Every
+ * sample of the block is what hmme_predict_refs_device writes for that sample when the 8x8 block that holds it carries this 4x4 block's
+ * (MV, index); with weights it is hmme_predict_refs_w_device's sample.  Identity weights (w0 == 1 << shift, offset 0) run the unweighted
+ * tail.  HM's interpolation is separable and per sample -- TComPrediction::xPredInterBlk (TComPrediction.cpp:669-707) filters a width x
+ * height block with TComInterpolationFilter::filterHor / filterVer (TComInterpolationFilter.cpp:341-404, the loop over width and height:
+ * :172-257), whose every output depends only on the MV and on its own 8 x 8 neighbourhood of the reference -- so this is also what xPredInterBlk writes for an 8x4, 4x8, 16x4 or 4x16 PU
+ * (and for any larger PU whose 4x4 blocks all carry its entry), followed by addWeightUni (TComWeightPrediction.cpp:133-180) in a slice with
+ * weights.
+ *
+ * Chroma (4:2:0, TComPrediction.cpp:669-707 for a chroma component).  A 4x4 luma block is a 2x2 block per component at half its position,
+ * taking the MV, the index and the COMPONENT'S OWN weight of its luma block; planes and weights come in component pairs (entry 2 i: Cb,
+ * 2 i + 1: Cr of reference i), width x height is the LUMA size, as in hmme_predict_chroma_refs_device.  Sample for sample it is what
+ * hmme_predict_chroma_refs_device writes when the 8x8 luma block carries that entry.
+ *
+ * Margins.  The patch a 4x4 block reads (11 x 11 luma, 5 x 5 chroma samples) is a subset of the 15 x 15 / 7 x 7 patch the 64 form reads at
+ * the same MV for the 8x8 block around it, so the planes' 128 / 80-sample margins hold by the argument given for those calls.
+ *
+ * Stores go only inside the picture and inside the CTU range [fp->ctu_first, + ctu_count); samples are of the planes' type.  Weights:
+ * wps NULL for none, else n_refs (chroma: 2 * n_refs) HOST weights, each under the "other weight" line of hmme_bipred_weight_check.
+ * Refusals -- codes and order -- are those of hmme_predict_refs_device / _w_device and hmme_predict_chroma_refs_device (and of their
+ * _frame forms), except that a NULL reference field is an argument, not an error; hmme_last_error names the entry that was called.
+ * Stream ordering, plane ownership and CTU sub-ranges are those of hmme_predict_refs_device.  The _frame forms are synchronous: host
+ * field, host reference field or NULL, host image(s) with out_stride in samples (chroma: outs = {Cb, Cr} of the chroma size); every sample
+ * that is not written comes back as it was.
+ *
+ * Not in this family: the bi / direction forms at 4x4 (hmme_select_dirs_* requires mv_per_ctu = 64; at 4x4 it would first need HM's
+ * isBipredRestriction for 8x4 / 4x8 PUs), the bi-pass origin from a 4x4 field, and 4:2:2 / 4:4:4 chroma. */
+int hmme_predict_refs4_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp,
+                              const hmme_weight* wps /* n_refs HOST weights, or NULL */, const void* d_mv_field /* int16[n_ctu][256][2] */,
+                              const void* d_ref_field /* uint8[n_ctu][256], or NULL: every block index 0 */, void* d_out, int out_pitch_bytes, void* stream);
+int hmme_predict_refs4_frame(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp, const hmme_weight* wps,
+                             const int16_t* mv_field, const uint8_t* ref_field, void* out, int out_stride);
+int hmme_predict_chroma_refs4_device(hmme_ctx* ctx, const hmme_plane* const* refs /* 2 * n_refs: Cb, Cr per reference */, int n_refs, int width,
+                                     int height /* LUMA */, const hmme_frame_params* fp, const hmme_weight* wps /* 2 * n_refs or NULL */,
+                                     const void* d_mv_field, const void* d_ref_field, void* d_out_cb, void* d_out_cr, int out_pitch_bytes, void* stream);
+int hmme_predict_chroma_refs4_frame(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, int width, int height, const hmme_frame_params* fp,
+                                    const hmme_weight* wps, const int16_t* mv_field, const uint8_t* ref_field, void* const* outs, int out_stride);
+
 /* ---- residual and distortion of a prediction ------------------------------------------------------------------------
  * The first things HM does with a prediction, on the device: the residual, what the prediction costs per PU, and what coding no residual
  * would cost per CU -- one pass over the current picture, the predicted image as any hmme_predict_*_device call wrote it, and the covering-slot
