@@ -1504,6 +1504,7 @@ int hmme_test_tail_plan(int width, int height, int search_range, int n_pairs, in
 int hmme_test_pk_gate(uint32_t lambda_q16) { return hmme::me_pk_gate(lambda_q16) ? 1 : 0; }
 int hmme_test_pk_body(uint32_t lambda_q16, int fen) { return hmme::me_pk_body(lambda_q16, fen ? 1 : 0); }
 int hmme_test_pk_task_marker_free(int wx, int wy, int k, int it0, int n_it) { return hmme::me_task_marker_free(wx, wy, k, it0, n_it) ? 1 : 0; }
+int hmme_test_pk_task_full(int wx, int wy, int k, int it0, int n_it) { return hmme::me_task_full(wx, wy, k, it0, n_it) ? 1 : 0; }
 
 // writes the device job table of plan `pl` -- a picture search over CTUs [first, first + count) against n_refs reference pictures -- on `s`;
 // job index = ref * count + ctu.  kWhole8: MeJob[jobs]; kHeadThenSegments8: MeJob[head], then the tail's segment table; kSegments8: one

@@ -52,6 +52,7 @@ constexpr int kMaxRefs = 16;
 struct RefSet { const uint8_t* base[kMaxRefs]; };
 
 #include "me_slotmap.inc"
+#include "me_slotmap3.inc"
 
 // ---- helpers used by the generated tree ------------------------------------------------------
 typedef uint16_t u16x4_t __attribute__((ext_vector_type(4)));
@@ -136,7 +137,8 @@ __host__ __device__ inline bool me_pk_gate(uint32_t lambda_q16) {
   const uint64_t prod = (uint64_t)lambda_q16 * kPkMaxBits;
   return prod <= 0xFFFFFFFFull && (prod >> 16) + kPkSlotMax < kPkMarker;
 }
-// Marker-free twin (PK = 2, me_tree_pk2_fen1.inc; FEN 1 only): the marker exists for the invalid candidates of a PARTLY valid lane, and
+// Marker-free packed minima (PK = 2; FEN 1 only; the bounds of the full-task twin below, which is the body that runs them -- the marker-free
+// tree itself, tools/gen_me_tree.py Tree(1, pk=2), is that body's yardstick and no longer part of the kernel): the marker exists for the invalid candidates of a PARTLY valid lane, and
 // such lanes exist only where a window row's last quad is cut (wx % 4 != 0): in the part that holds that quad, and in the folded
 // iteration of the 32-quad part (me_task_marker_free).  Every other task has only lanes that are wholly valid -- pkm holds four real MV
 // costs -- or wholly invalid -- kInvCost << 10 in ctag drops the lane whatever its packed fields hold, carries between them included.
@@ -144,13 +146,14 @@ __host__ __device__ inline bool me_pk_gate(uint32_t lambda_q16) {
 // 16x8, 8x16 <= 32 640, 16x12, 12x16 <= kPk2SlotMax, + an MV cost of at most 0xFFFF - kPk2SlotMax (me_pk2_gate).  They take ME_PKMIN
 // there, ME_PKMINE where FEN halves the rows (h > 8): the 64-bit add that adds the packed MV costs doubles the even-row sums on the way
 // (v_lshl_add_u64; an even-row sum is at most 24 480, the shift stays inside its u16 field).  min * 1024 + ctag stays inside the key:
-// 65 535 * 1024 + (kInvCost << 10 | 1023) < 2^32.  Tasks with a partly valid lane run the PK = 1 body in the same kernel.
+// 65 535 * 1024 + (kInvCost << 10 | 1023) < 2^32.  Tasks with a partly valid lane run the PK = 1 body in the same kernel, and so do
+// marker-free tasks with a lane outside the window (a part's last, partial lane-iteration on a clipped window): me_task_full.
 constexpr uint32_t kPk2SlotMax = 16 * 12 * 255;           // 48 960: 16x12 / 12x16, every sample difference 255
 __host__ __device__ inline bool me_pk2_gate(uint32_t lambda_q16) {
   const uint64_t prod = (uint64_t)lambda_q16 * kPkMaxBits;
   return prod <= 0xFFFFFFFFull && (prod >> 16) + kPk2SlotMax <= 0xFFFFu;
 }
-// which body an 8-bit search launch runs: 0 the 32-bit tree, 1 the packed-minimum twin, 2 the kernel that holds the twin and its marker-free
+// which body an 8-bit search launch runs: 0 the 32-bit tree, 1 the packed-minimum twin, 2 the kernel that holds the twin and the full-task
 // body.  FEN 0 stays on 1: its tall-family sums are all-row sums of twice the rows, its recovery would read 16 rows per slot, and no
 // benchmark or encoder configuration runs it
 __host__ __device__ inline int me_pk_body(uint32_t lambda_q16, int fen) {
@@ -166,6 +169,16 @@ __host__ __device__ inline bool me_task_marker_free(int wx, int wy, int k, int i
   const bool fold = (quads & 32) && (quads & 31) && (wy & 1);   // me_fold (below)
   return !(fold && k == 5 && 2 * (it0 + n_it) > wy);
 }
+// whether the task runs the full-task twin: a part of at least four quads (k >= 2) that does not hold the row's cut quad, and every lane
+// of every one of its lane-iterations inside the part's rows (the folded iteration of the 32-quad part is not: its second lane row lies
+// below the window).  Every lane is then valid with all four candidates
+__host__ __device__ inline bool me_task_full(int wx, int wy, int k, int it0, int n_it) {
+  if (k < 2) return false;
+  const int quads = (wx + 3) >> 2;
+  if ((wx & 3) && (quads & -quads) == (1 << k)) return false;
+  const bool fold = (quads & 32) && (quads & 31) && (wy & 1);   // me_fold (below)
+  return (it0 + n_it) * (64 >> k) <= ((k == 5 || !fold) ? wy : wy - 1);
+}
 #define ME_PKMIN(r, p) ME_PKMIN_Q(r, (p) + pkm)
 #define ME_PKMINE(r, p) ME_PKMIN_Q(r, ((p) << 1) + pkm)
 #define ME_PKMIN_Q(r, q)                                                                                        \
@@ -176,6 +189,51 @@ __host__ __device__ inline bool me_task_marker_free(int wx, int wy, int k, int i
                  "v_mad_u32_u16 %0, %0, %3, %4"                                                                 \
                  : "=&v"(r) : "v"((uint32_t)r##_q), "v"((uint32_t)(r##_q >> 32)), "s"(mult_a), "v"(ctag));      \
   }
+
+// Full-task twin (PK = 2, me_tree_pk3_fen1.inc): the body of the tasks whose lanes ALL lie inside the window (me_task_full) -- for the
+// 129 x 129 window the 64 lane-iterations of the 32-quad part that come before the folded one.  Their lane layout puts the two lowest
+// bits of the quad index into lane bits 5 and 4: lanes l, l ^ 16, l ^ 32, l ^ 48 hold four adjacent quads, 16 contiguous candidates of
+// one window row starting at a multiple of 16 (every part with k >= 2 starts on one).  The two butterfly levels on those lane bits then
+// merge candidates that one key can stand for, so they run BEFORE the key exists, on the u16 minima themselves:
+//   ME_PKMIN16_LO / _HI   q = p + pkm (one 64-bit add), v_pk_min_u16 of its halves, and one v_min_u16_sdwa that writes the minimum of that
+//                         result's two halves into the low / high half of a register shared with the next packed slot
+//   me_pmerge2 / 3        v_permlane32_swap / v_permlane16_swap of two such registers + v_pk_min_u16: two slots per register merged in the
+//                         two instructions that merge one on keys
+//   ME_KEY16_LO / _HI     key = half * 1024 + ctag, one v_mad_u32_u16 per half, a quarter as many as ME_PKMIN forms.  ctag names the
+//                         16-candidate group (its first quad): me_pk_recover finds the candidate.
+// The four levels on lane bits 3..0 follow on keys as in every body.  Ties between groups are settled by (cost, iteration, ly, lx >> 2),
+// the raster order, as they are between quads in the other bodies: the key's lane field is ly << k | lx, not the physical lane.
+// Every lane of a full task is valid: no marker, no invalid cost in ctag, and the marker-free body's bounds hold (me_pk2_gate).
+// v_permlane*_swap wants 2 wait states after a VALU write of either operand, like a DPP read: the generator spaces the merges from their
+// producers (space_merges) and pads the rest (s_nop 1); the SDWA write of a register half is followed by at least one other instruction
+// before anything reads the register (the _HI form computes its v_pk_min_u16 in between).
+#define ME_PKMIN16_LO(r, q)                                                                                     \
+  uint32_t r;                                                                                                   \
+  {                                                                                                             \
+    const uint64_t r##_q = (q);                                                                                 \
+    asm volatile("v_pk_min_u16 %0, %1, %2\n\t"                                                                  \
+                 "v_min_u16_sdwa %0, %0, %0 dst_sel:WORD_0 dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:WORD_1" \
+                 : "=&v"(r) : "v"((uint32_t)r##_q), "v"((uint32_t)(r##_q >> 32)));                              \
+  }
+#define ME_PKMIN16_HI(r, q)                                                                                     \
+  {                                                                                                             \
+    const uint64_t r##_q = (q);                                                                                 \
+    uint32_t r##_t;                                                                                             \
+    asm volatile("v_pk_min_u16 %1, %2, %3\n\t"                                                                  \
+                 "v_min_u16_sdwa %0, %1, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_0 src1_sel:WORD_1" \
+                 : "+v"(r), "=&v"(r##_t) : "v"((uint32_t)r##_q), "v"((uint32_t)(r##_q >> 32)));                 \
+  }
+#define ME_KEY16_LO(k, r) uint32_t k; asm volatile("v_mad_u32_u16 %0, %1, %2, %3" : "=v"(k) : "v"(r), "s"(mult_a), "v"(ctag))
+#define ME_KEY16_HI(k, r) uint32_t k; asm volatile("v_mad_u32_u16 %0, %1, %2, %3 op_sel:[1,0,0,0]" : "=v"(k) : "v"(r), "s"(mult_a), "v"(ctag))
+#define ME_PMERGE(NAME, PAD, SWAP)                                                                           \
+  __device__ __forceinline__ uint32_t NAME(uint32_t a, uint32_t b) {                                         \
+    asm volatile(PAD SWAP " %0, %1\n\tv_pk_min_u16 %0, %0, %1" : "+v"(a), "+v"(b));                          \
+    return a;                                                                                                \
+  }
+ME_PMERGE(me_pmerge2, "s_nop 1\n\t", "v_permlane32_swap_b32")      // role = lane bit 5
+ME_PMERGE(me_pmerge3, "s_nop 1\n\t", "v_permlane16_swap_b32")      // role = lane bit 4
+ME_PMERGE(me_pmerge2_nn, "", "v_permlane32_swap_b32")
+ME_PMERGE(me_pmerge3_nn, "", "v_permlane16_swap_b32")
 
 // butterfly transpose-reduce: merge two slot registers into one; lanes whose role bit is 0 keep
 // slot a (min over the lane pair), lanes whose role bit is 1 keep slot b.
@@ -225,7 +283,7 @@ __device__ __forceinline__ uint32_t me_mv_cost(uint32_t lambda_q16, int x, int y
 
 // The slots that take the packed minimum in the PK twin (ME_PKMIN) and their rectangles in the CTU: 8x4 halves 0..127, 4x8 halves
 // 128..255, 8x8 CUs 384..447 (tools/gen_me_tree.py slot_2NxN / slot_Nx2N / slot_2Nx2N at size 8).  WIDE (PK = 2): also the twelve slots
-// of every 16x16 CU that the marker-free body packs -- the AMP slots 256..383 (16x4, 16x12, 4x16, 12x16), 16x8 448..479, 8x16 480..511
+// of every 16x16 CU that the full-task body packs -- the AMP slots 256..383 (16x4, 16x12, 4x16, 12x16), 16x8 448..479, 8x16 480..511
 __device__ __forceinline__ bool me_pk_slot(int s, bool wide, int& x, int& y, int& w, int& h) {
   if (s < 128) { x = (s & 7) * 8; y = (s >> 4) * 8 + ((s >> 3) & 1) * 4; w = 8; h = 4; return true; }
   if (s < 256) { x = ((s >> 1) & 7) * 8 + (s & 1) * 4; y = ((s - 128) >> 4) * 8; w = 4; h = 8; return true; }
@@ -253,9 +311,14 @@ __device__ __forceinline__ bool me_pk_slot(int s, bool wide, int& x, int& y, int
 // every load of the slot is issued before the first is used (one round trip: a workgroup of a segment launch runs a few
 // lane-iterations per job, and a byte-wise loop with a load per row cost it 3 %).
 // NR rows, STEP apart: STEP = 2 reads the even rows of a slot taller than 8 under FEN (its cost is twice their sum).
-// PK = 2: a slot of the 16x16 level arrives with j = 0 from a marker-free task and with the winner's j from a task of the PK = 1 body
-// (32-bit keys there).  The quad starts at x & ~3 either way (every quad starts on a multiple of 4), and the key minimum took the
-// smallest j of the lane's equal costs, which is the first j that is found here: one path serves both.
+// PK = 2 (WIDE): a full task's entry names a 16-candidate GROUP -- x is its first quad's, a multiple of 16 -- so an entry with
+// (x & 12) == 0 is recomputed for the group's up to four quads (those that start below wx; dwords (x + rx) / 4 .. + 3 + rw / 4 <= 48 of
+// the row's 49), the first candidate whose cost is the minimum wins.  Such an entry may also come from the PK = 1 body (a quad that
+// happens to be the first of its group; with the winner's j where the slot has 32-bit keys there).  Scanning the whole group is right for
+// it too: an equal-cost valid candidate EARLIER in the same row would have been flushed by its own task with a smaller x and would have
+// won the atomicMin (in a SPLIT launch: the later merge into g_best), so there is none before the entry's own quad; inside that quad the
+// key minimum took the smallest j of the lane's equal costs, which is the first j found here; and the scan stops at the first match,
+// which is therefore the entry's own candidate.  Every other entry keeps its quad's four candidates.
 template <int RW, int NR, int STEP>
 __device__ __forceinline__ void me_pk_sads(const uint32_t* wrow, int pdw, const uint8_t* __restrict__ crow, uint32_t sad[4]) {
   constexpr int ND = RW / 4;
@@ -283,10 +346,15 @@ __device__ __forceinline__ unsigned long long me_pk_recover(unsigned long long v
                                                             const MeJob& job, int wx, uint32_t lambda_q16) {
   int rx, ry, rw, rh;
   if (v == ~0ull || !me_pk_slot(s, WIDE, rx, ry, rw, rh)) return v;
-  const int xq = (int)(v & 0xfffc), y = (int)((v >> 16) & 0xffff);
+  const int x_first = (int)(v & 0xfffc), y = (int)((v >> 16) & 0xffff);
   const uint32_t cost = (uint32_t)(v >> 32);
-  const uint32_t* wrow = win + (y + ry) * pdw + ((xq + rx) >> 2);   // dwords (xq + rx) / 4 .. + rw / 4 <= 48 of a 49-dword row
   const uint8_t* crow = cur_blk + ry * 64 + rx;
+  const uint32_t by = me_component_bits(((job.lt_y + y) << 2) - job.pred_y);
+  const int x_end = (WIDE && !(x_first & 12)) ? min(x_first + 16, wx) : x_first + 4;   // a group of a full task, or one quad
+  v &= ~0xffffull;
+#pragma unroll 1
+  for (int xq = x_first; xq < x_end; xq += 4) {
+  const uint32_t* wrow = win + (y + ry) * pdw + ((xq + rx) >> 2);   // dwords (xq + rx) / 4 .. + rw / 4 <= 48 of a 49-dword row
   uint32_t sad[4] = {0u, 0u, 0u, 0u};
   int sh = 0;
   if (!WIDE || max(rw, rh) <= 8) {
@@ -303,12 +371,11 @@ __device__ __forceinline__ unsigned long long me_pk_recover(unsigned long long v
     else if (rw == 8) me_pk_sads<8, 8, 2>(wrow, pdw, crow, sad);
     else me_pk_sads<12, 8, 2>(wrow, pdw, crow, sad);
   }
-  const uint32_t by = me_component_bits(((job.lt_y + y) << 2) - job.pred_y);
-  v &= ~3ull;
 #pragma unroll
   for (int j = 0; j < 4; ++j)
-    if (xq + j < wx && (sad[j] << sh) + ((lambda_q16 * (me_component_bits(((job.lt_x + xq + j) << 2) - job.pred_x) + by)) >> 16) == cost) return v + (unsigned long long)j;
-  return v;
+    if (xq + j < wx && (sad[j] << sh) + ((lambda_q16 * (me_component_bits(((job.lt_x + xq + j) << 2) - job.pred_x) + by)) >> 16) == cost) return v | (unsigned long long)(xq + j);
+  }
+  return v | (unsigned long long)x_first;
 }
 
 // 16-bit kernel (three candidates per lane, one lane-iteration per task): key = cost << 8 | lane(6) | j(2).  The 24-bit cost field
@@ -483,7 +550,7 @@ constexpr int kTileStep = 129, kTileJobMask = 0x1fffffff;
 // curs: the CTU-blocked copies of the current pictures (above me_prefetch_cur), cur_ctus_x: CTUs per picture row (blocks per block row).
 // PK = 1: the packed-minimum twin (ME_PKMIN above; every <FEN, SPLIT> has one).  Same results, fewer instructions per lane-iteration;
 // only for launches that pass me_pk_gate.
-// PK = 2 (FEN 1 only): the twin and its marker-free body in one kernel, one wave-uniform branch per task (me_task_marker_free); only for
+// PK = 2 (FEN 1 only): the twin and the full-task twin in one kernel, one wave-uniform branch per task (me_task_full); only for
 // launches that pass me_pk2_gate.
 template <int FEN, int SPLIT, int PK>
 __global__ void __launch_bounds__(kThreads, 2)
@@ -656,11 +723,14 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
       }
     }
     const int ty = 64 >> k;
-    const int lx = lane & ((1 << k) - 1), ly = lane >> k;
+    const bool full = PK == 2 && me_task_full(wx, wy, k, it0, n_it);   // wave-uniform: wx, wy of the job, k, it0, n_it of the task
+    // the lane's quad and row inside a lane-iteration.  A full task puts the two lowest bits of the quad index into lane bits 5 and 4
+    // (four adjacent quads in lanes l, l ^ 16, l ^ 32, l ^ 48: the two packed butterfly levels), the rest and ly into bits 0..3
+    int lx = lane & ((1 << k) - 1), ly = lane >> k;
+    if (full) { lx = ((lane >> 5) & 1) | ((lane >> 3) & 2) | ((lane & ((1 << (k - 2)) - 1)) << 2); ly = (lane & 15) >> (k - 2); }
     const bool fold_part = fold && k == 5;
-    const bool marker_free = PK == 2 && me_task_marker_free(wx, wy, k, it0, n_it);   // wave-uniform: wx, wy of the job, k, it0, n_it of the task
 
-    // running minima of the task: register g, lane l <-> slot ME_SLOT_OF[g][l]
+    // running minima of the task: register g, lane l <-> slot ME_SLOT_OF[g][l] (ME_SLOT_OF3 in a full task)
     uint32_t b0 = ME_MAXKEY, b1 = ME_MAXKEY, b2 = ME_MAXKEY, b3 = ME_MAXKEY, b4 = ME_MAXKEY, b5 = ME_MAXKEY,
              b6 = ME_MAXKEY, b7 = ME_MAXKEY, b8 = ME_MAXKEY, b9 = ME_MAXKEY;
 
@@ -672,7 +742,7 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
       // per-candidate constants: (mv cost | invalid marker) << 10 | iteration | lane | j
       const int mvy = job.lt_y + cy, mvx = job.lt_x + cx;
       const uint32_t by = me_component_bits((mvy << 2) - job.pred_y);
-      uint32_t lane_now = (uint32_t)lane;
+      uint32_t lane_now = (uint32_t)(ly << k | lx);   // the key's lane field: raster order inside the lane-iteration (the lane itself but in a full task)
       asm("" : "+v"(lane_now));   // keep `lane << 2` out of the loop-invariant registers: at 255 VGPRs it was the one value spilled
       const uint32_t tag = ((uint32_t)it << 8) | (lane_now << 2);
       uint32_t cc[4];
@@ -691,6 +761,7 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
         const uint32_t m2 = cc[2] < (kInvCost << kIdxBits) ? cc[2] >> kIdxBits : kPkMarker, m3 = cc[3] < (kInvCost << kIdxBits) ? cc[3] >> kIdxBits : kPkMarker;
         pkm = (uint64_t)(m0 | m1 << 16) | (uint64_t)(m2 | m3 << 16) << 32;
         ctag = ((vy && cx < wx) ? 0u : kInvCost << kIdxBits) | tag;   // candidate 0 is valid wherever one of the four is
+        if (full) ctag = tag & ~(3u << 2);                              // every lane valid; the key names the group's first quad
       }
       // lanes outside the window still run (wave-uniform code) on clamped, in-bounds addresses
       const lds_char_t* lpc = (const lds_char_t*)(win + min(cy, wy - 1) * kPDW + (min(cx, wx - 1) >> 2));
@@ -707,9 +778,9 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
                "v"(d12), "v"(d13), "v"(d14), "v"(d15));                                                                             \
   asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(w0), "+s"(w1), "+s"(w2), "+s"(w3), "+s"(w4), "+s"(w5), "+s"(w6), "+s"(w7))
       if constexpr (PK == 2) {
-        static_assert(PK != 2 || FEN == 1, "the marker-free body exists for FEN 1");
-        if (marker_free) {
-#include "me_tree_pk2_fen1.inc"
+        static_assert(PK != 2 || FEN == 1, "the full-task body exists for FEN 1");
+        if (full) {
+#include "me_tree_pk3_fen1.inc"
         } else {
 #include "me_tree_pk_fen1.inc"
         }
@@ -729,7 +800,7 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
     // -- 3. fold the wave's running minima into the CTU table; (cost, y, x) keys give raster-order ties
 #define ME_FLUSH(g, key_)                                                                                          \
     {                                                                                                              \
-      const int slot = ME_SLOT_OF[g][lane];                                                                        \
+      const int slot = full ? ME_SLOT_OF3[g][lane] : ME_SLOT_OF[g][lane];                                          \
       const uint32_t key = (key_);                                                                                 \
       const uint32_t cost = key >> kIdxBits;                                                                       \
       if (slot >= 0 && cost < kInvCost) {                                                                          \

@@ -29,12 +29,17 @@ int hmme_test_tail_plan(int width, int height, int search_range, int n_pairs, in
 int hmme_test_pk_gate(uint32_t lambda_q16);
 
 /* which body an 8-bit search launch at this lambda and FEN runs (me_pk_body; host arithmetic): 0 the 32-bit tree, 1 the packed-minimum
- * twin, 2 the kernel that also holds the twin's marker-free body (FEN 1, the largest MV cost + the largest 16x12 sum within 16 bits) */
+ * twin, 2 the kernel that also holds the full-task body (FEN 1, the largest MV cost + the largest 16x12 sum within 16 bits) */
 int hmme_test_pk_body(uint32_t lambda_q16, int fen);
 
 /* whether a task of that kernel -- part k (2^k quads per lane row), lane-iterations it0 .. it0 + n_it - 1 of a wx x wy window -- runs the
  * marker-free body: 1 where every lane of every one of its lane-iterations is wholly valid or wholly invalid (me_task_marker_free) */
 int hmme_test_pk_task_marker_free(int wx, int wy, int k, int it0, int n_it);
+
+/* whether that task runs the full-task twin, the body whose first two butterfly levels work on packed 16-bit minima (me_task_full): 1 where
+ * k >= 2, the part does not hold the row's cut quad and every lane of every one of its lane-iterations lies inside the part's rows (which
+ * excludes the folded iteration).  Every other task of the kernel runs the packed-minimum twin */
+int hmme_test_pk_task_full(int wx, int wy, int k, int it0, int n_it);
 
 /* where the staging arena of a synchronous, host-array call puts n items of bytes[i] bytes (hmme.hip stage_layout: what every hmme_*_frame*
  * entry point lays its arrays out with; host arithmetic, needs no device): offsets[i] and *total, the arena's size.  Returns the alignment of

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """ISA check for the hand-written DPP instructions (inline asm is not padded by the compiler's hazard recognizer):
 a VALU write of a VGPR must be followed by 2 wait states before a DPP instruction reads that VGPR as its DPP source
-(gfx9 data hazard).  Every instruction the wave issues is one wait state, `s_nop N` is N + 1.
+(gfx9 data hazard), or before a hand-written v_permlane16_swap / v_permlane32_swap reads it as either operand (the packed merges of
+the full-task search body are inline asm too; the swaps the compiler emits for the builtin print with an _e32 suffix and stay its
+hazard recognizer's business, as they always were: 908 of them follow an asm-written operand after one wait state, in every body).  Every instruction the wave issues is one wait state, `s_nop N` is N + 1.
 Control flow: a local label (.LBB*) is a join -- some other path can reach it through a branch whose source the linear scan
 does not see.  Conservatively, every VGPR is taken to have been written by the instruction right before that branch; the
 branch itself is the one wait state in between.  So a DPP read within the first instruction after a label is a violation
@@ -59,9 +61,12 @@ def check(path, names):
             continue
         parts = ln.replace(",", " ").split()
         op, args = parts[0], parts[1:]
-        if op.endswith("_dpp"):
+        swap = re.fullmatch(r"v_permlane(16|32)_swap(_b32)?", op) is not None   # hand-written (no _e32): reads and writes both operands; the same 2 wait states after a VALU write
+        if op.endswith("_dpp") or swap:
             total += 1
             src = regs(args[1]) if len(args) > 1 else set()
+            if swap:
+                src |= regs(args[0])
             need, i = 2, len(hist) - 1
             while need > 0 and i >= 0:
                 ws, written = hist[i]
@@ -78,7 +83,7 @@ def check(path, names):
         else:
             hist.append((1, set()))   # loads write VGPRs too, but their data arrives behind s_waitcnt, not by this hazard
         hist = hist[-4:]
-    print(f"{path}: {total} DPP instructions checked, {bad} hazard(s)")
+    print(f"{path}: {total} DPP and lane-swap instructions checked, {bad} hazard(s)")
     return bad
 
 

@@ -30,6 +30,13 @@ One *lane-iteration* of the kernel evaluates FOUR horizontally adjacent candidat
            <= 48 960; + the MV cost, me_pk2_gate).  They take PKMIN too (PKMINE where FEN halves the rows: the same 64-bit add doubles the
            even-row sums).  16x16 (65 280) keeps its keys; 32x8 and 8x32 form theirs from the packed sum of two strips (5 ops where a union
            of two keys is 4).  PK2_CLASSES holds the count that decides, class by class.
+  full-task twin (Tree(1, pk=3) -> csrc/me_tree_pk3_fen1.inc, written at every build and kept out of git; the body that the kernel's PK = 2 runs in
+           tasks whose lanes all lie inside the window, me_task_full): the 512 packed slots of the marker-free twin leave the lane as 16-bit
+           minima, two slots to a register (PKMIN16), and take the first two butterfly levels -- lane bits 5 and 4, the two lowest bits
+           of the quad index in that body's lane layout -- packed: v_permlane32_swap / v_permlane16_swap + v_pk_min_u16 merge two
+           slots per register in the two instructions that merge one on keys (PMERGE).  Only then is a key formed (KEY16), for a quarter
+           as many values; it names the 16-candidate group, and me_pk_recover finds the candidate.  The 81 slots with 32-bit keys go
+           through the six-level butterfly as before; the body has a slot map of its own (ME_SLOT_OF3).
 
 The slot numbering is the reference's (TComDataCU::getIndexBlock, TComDataCU.cpp:3379-3391 and
 :4676-6461; same offsets in cl/sad.cl:200-365); FEN semantics are TEncSearch.cpp:3853-3859 +
@@ -94,8 +101,13 @@ class Tree:
     def __init__(self, fen, pk=False):
         self.fen = fen
         self.pk = pk               # the five slots of every 8x8 CU take the packed 16-bit minimum (PKMIN) instead of four 32-bit keys
-        assert pk != 2 or fen == 1, "the marker-free twin exists for FEN 1 only (FEN 0 stays on pk = 1)"
-        self.pk2 = pk2_choice() if pk == 2 else {}   # pk = 2: class of 16x16-level slots -> packed or not (marker-free tasks only)
+        assert pk not in (2, 3) or fen == 1, "the marker-free twin exists for FEN 1 only (FEN 0 stays on pk = 1)"
+        self.pk2 = pk2_choice() if pk in (2, 3) else {}   # pk = 2, 3: class of 16x16-level slots -> packed or not (marker-free tasks only)
+        self.pk_open = None        # pk = 3: the pair register whose high half the next packed slot fills
+        self.pend16 = {}           # pk = 3: packed butterfly level (lane bits 5, 4) -> pair register
+        self.pendk = {}            # pk = 3: key butterfly level (lane bits 3, 2, 1, 0) of the packed slots -> var
+        self.n_key = 0             # slots (and padding) pushed into the six-level butterfly
+        self.reg_slot = {}         # per-slot minimum register -> slot id
         self.ops = []
         self.n = 0
         self.emitted = []          # slot ids in emission order (None = padding)
@@ -204,6 +216,8 @@ class Tree:
         u16 costs (sum + packed MV cost), ONE key per lane formed from it -- 4 instructions where KEYS + MIN4 are 6.  The key carries
         the candidate's iteration and lane but not which of the four it was (j = 0): the kernel recovers j from the window once per
         slot and job (me_pk_recover)"""
+        if self.pk == 3:
+            return self._emit_pk16(slot, p, 0)
         r = self.new("r")
         self.ops.append(("PKMIN", r, p))
         self._push(slot, r)
@@ -211,12 +225,54 @@ class Tree:
     def emit_pke(self, slot, p):
         """emit_pk for a packed EVEN-ROW sum of the tall family under FEN: the cost is 2 * sum + MV cost, and the 64-bit add that adds
         the packed MV costs shifts the sums by one on the way (every sum <= 32 640: the shift stays inside each u16 field)"""
+        if self.pk == 3:
+            return self._emit_pk16(slot, p, 1)
         r = self.new("r")
         self.ops.append(("PKMINE", r, p))
         self._push(slot, r)
 
+    # full-task twin (pk = 3): a packed slot's minimum over the lane's four candidates stays a u16 in one half of a register it shares
+    # with the next packed slot; four such registers meet in two packed levels (lane bits 5, 4), the two halves become keys, and sixteen
+    # key registers meet in the four levels on lane bits 3, 2, 1, 0: 64 slots per running-minimum register, as in the six-level butterfly
+    PK16_LEVELS = (("PMERGE", 2), ("PMERGE", 3))
+    PKK_LEVELS = (("MERGE", 0), ("MERGE", 1), ("MERGE", 4), ("MERGE", 5))
+
+    def _emit_pk16(self, slot, p, even):
+        self.emitted.append(slot)
+        if self.pk_open is None:
+            self.pk_open = self.new("h")
+            self.ops.append(("PKMIN16", self.pk_open, p, 0, even, slot))
+            return
+        r, self.pk_open = self.pk_open, None
+        self.ops.append(("PKMIN16", r, p, 1, even, slot))
+        self._bfly(self.pend16, r, self.PK16_LEVELS, self._keys16)
+
+    def _keys16(self, r):
+        for half in (0, 1):
+            k = self.new("r")
+            self.ops.append(("KEY16", k, r, half))
+            self._bfly(self.pendk, k, self.PKK_LEVELS, self._acc)
+
+    def _acc(self, r):
+        self.ops.append(("ACC", self.group, r))
+        self.group += 1
+
+    def _bfly(self, state, r, levels, done):
+        i = 0
+        while i in state:
+            m = self.new("m")
+            self.ops.append((levels[i][0], levels[i][1], m, state.pop(i), r))
+            r = m
+            i += 1
+            if i == len(levels):
+                return done(r)
+        state[i] = r
+
     def _push(self, slot, r):
         self.emitted.append(slot)
+        self.n_key += 1
+        if r is not None:
+            self.reg_slot[r] = slot
         level = 0
         while level in self.pending:
             a = self.pending.pop(level)
@@ -235,9 +291,10 @@ class Tree:
         self.pending[level] = r
 
     def flush(self):
-        while len(self.emitted) % 64:
+        while (self.n_key if self.pk == 3 else len(self.emitted)) % 64:
             self._push(None, None)
         assert not self.pending and self.group == N_GROUPS
+        assert self.pk_open is None and not self.pend16 and not self.pendk
 
     # ---- the tree -------------------------------------------------------------------------------
     def build(self):
@@ -346,7 +403,7 @@ class Tree:
     def level1(self, rx16, ry16, rx, ry, c, U):
         """16x16 region at region coords (rx16, ry16); (rx, ry) = position inside its 32x32"""
         S = 16
-        if self.pk == 2:
+        if self.pk in (2, 3):
             return self.level1_pk2(rx16, ry16, rx, ry, c, U)
         # all-rows family (h <= 8)
         if self.pk:    # no keys below: one packed add of two CUs' sums (<= 32 640) and one KEYS, 5 ops where a LIN of two keys is 4
@@ -429,7 +486,7 @@ class Tree:
         self.emit(slot_Nx2N(S, qx, qy, 0), k_l)
         self.emit(slot_Nx2N(S, qx, qy, 1), k_r)
         self.emit(slot_2Nx2N(S, qx, qy), k_u32)
-        if self.pk == 2:   # the strips below are packed sums: one packed add (<= 65 280) and one KEYS
+        if self.pk in (2, 3):   # the strips below are packed sums: one packed add (<= 65 280) and one KEYS
             self.emit(slot_AMP(S, qx, qy, 0), self.keys(self.pkadd(r[0]["p_a16x8"], r[1]["p_a16x8"]), "A"))
             self.emit(slot_AMP(S, qx, qy, 1), self.keys(self.pkadd(r[2]["p_a16x8"], r[3]["p_a16x8"]), "A"))
         else:
@@ -437,7 +494,7 @@ class Tree:
             self.emit(slot_AMP(S, qx, qy, 1), self.lin(r[2]["k_a16x8"], r[3]["k_a16x8"]))   # 32x8 bottom
         k_u32x8t = self.keys(self.pkadd_as(r[0]["spare"], r[0]["u16x8"], r[1]["u16x8"]), U)
         k_u32x8b = self.keys(self.pkadd_as(r[2]["spare"], r[2]["u16x8"], r[3]["u16x8"]), U)
-        if self.pk == 2:
+        if self.pk in (2, 3):
             k_u8x32l = self.keys(self.pkadd(r[0]["p_ucol"], r[2]["p_ucol"]), U)
             k_u8x32r = self.keys(self.pkadd(r[1]["p_ucol"], r[3]["p_ucol"]), U)
         else:
@@ -475,12 +532,36 @@ class Tree:
     # ---- slot map ---------------------------------------------------------------------------------
     def slot_of_lane(self):
         """[group][lane] -> slot id (or -1): lane l ends up with emission index bitrev6(l)"""
+        if self.pk == 3:
+            return self.slot_of_lane_traced()
         t = np.full((N_GROUPS, 64), -1, np.int32)
         for g in range(N_GROUPS):
             for lane in range(64):
                 e = sum(((lane >> LEVEL_ROLE_BIT[lv]) & 1) << lv for lv in range(6))   # emission index bit lv = role at level lv
                 s = self.emitted[g * 64 + e]
                 t[g, lane] = -1 if s is None else s
+        return t
+
+
+    def slot_of_lane_traced(self):
+        """the same table read off the op list: every merge keeps its first operand's slots in the lanes whose role bit is 0 and its
+        second operand's in the others (any tree; the full-task twin has no closed form)"""
+        t = np.full((N_GROUPS, 64), -1, np.int32)
+        none, val = np.full(64, -1, np.int32), {}
+        for op in self.ops:
+            if op[0] in ("MIN4", "PKMIN", "PKMINE", "KEYMINN"):
+                val[op[1]] = np.full(64, self.reg_slot[op[1]], np.int32)
+            elif op[0] == "PKMIN16":
+                val.setdefault(op[1], np.full((64, 2), -1, np.int32))[:, op[3]] = op[5]
+            elif op[0] == "KEY16":
+                val[op[1]] = val[op[2]][:, op[3]].copy()
+            elif op[0] in ("MERGE", "PMERGE"):
+                _, level, m, a, b = op
+                A, B = (val[x] if x is not None else none for x in (a, b))
+                role = (LANES >> LEVEL_ROLE_BIT[level]) & 1
+                val[m] = np.where((role if A.ndim == 1 else role[:, None]) == 1, B, A)
+            elif op[0] == "ACC":
+                t[op[1]] = val[op[2]]
         return t
 
 
@@ -658,6 +739,14 @@ HEADER_PK2 = """// GENERATED by tools/gen_me_tree.py -- do not edit.  One lane-i
 """
 
 
+HEADER_PK3 = """// GENERATED by tools/gen_me_tree.py -- do not edit.  One lane-iteration of the full-search
+// reduction tree (fen=%d), full-task twin: for tasks whose lanes all lie inside the window, in that body's lane layout (lanes l, l ^ 16,
+// l ^ 32, l ^ 48 hold 16 contiguous candidates of a row).  The packed slots of the marker-free twin leave the lane as u16 minima, two to a
+// register (ME_PKMIN16_LO / _HI), take the levels on lane bits 5 and 4 packed (me_pmerge2 / 3) and become keys afterwards (ME_KEY16_*).
+// Expects in scope what me_tree_pk_fen*.inc expects; pkm needs no marker here, ctag names the lane's 16-candidate group.
+"""
+
+
 HEADER16 = """// GENERATED by tools/gen_me_tree.py -- do not edit.  One lane-iteration of the 16-bit-sample reduction tree
 // (fen=%d): three candidates (x, x+2, x+4) per lane, exact 32-bit sums, v_sad_u16 leaves.
 // Expects in scope: lpd (per-lane LDS byte pointer at the first candidate, window row 0; 4-byte aligned), ME16_PDW (window pitch in
@@ -673,7 +762,7 @@ MASKED_MERGE_LEVELS = (0, 1)   # the two levels done with hand-written bank-mask
 # pair's key constants are one v_lshl_add_u64 each (shift 0: the instruction only shifts by 0..4, which is why the key's shift rides on the
 # first add of two leaf sums), 6 instructions per slot where three separate candidates took 7, 2 per add where they took 3
 PAIR64 = True
-ORDERED_INSTRS = {"KEYS": 4, "LIN": 4, "SUB": 4, "MIN4": 2, "SUBMIN4": 6, "PKMIN": 3, "PKMINE": 3, "KEYMINN": 1 if PAIR64 else 7}
+ORDERED_INSTRS = {"KEYS": 4, "LIN": 4, "SUB": 4, "MIN4": 2, "SUBMIN4": 6, "PKMIN": 3, "PKMINE": 3, "PKMIN16": 2, "KEYMINN": 1 if PAIR64 else 7}
 
 
 def fuse_sub_min(ops):
@@ -706,10 +795,12 @@ def space_merges(ops, enable):
     count = [0]
 
     def inputs(op):
-        return [x for x in (op[3], op[4]) if x is not None] if op[0] == "MERGE" else [op[2]]
+        return [x for x in (op[3], op[4]) if x is not None] if op[0] in ("MERGE", "PMERGE") else [op[2]]
 
     def masked(op):
-        return op[0] == "MERGE" and op[1] in MASKED_MERGE_LEVELS
+        """the merges written as asm: the masked DPP pairs, and the packed swap levels of the full-task twin (v_permlane*_swap wants
+        the same 2 wait states after a VALU write of either operand)"""
+        return (op[0] == "MERGE" and op[1] in MASKED_MERGE_LEVELS) or op[0] == "PMERGE"
 
     def try_flush(force=False):
         progress = True
@@ -725,9 +816,12 @@ def space_merges(ops, enable):
                 pending.remove(op)
                 if masked(op):
                     count[0] += 2
-                if op[0] == "MERGE":
+                if op[0] in ("MERGE", "PMERGE"):
                     # results of the compiler-scheduled levels can land anywhere: treat them as fresh for good
                     where[op[2]] = count[0] if masked(op) else float("inf")
+                if op[0] == "KEY16":      # one asm instruction on a packed merge's result: the first masked level reads it
+                    count[0] += 1
+                    where[op[1]] = count[0]
                 out.append((op, fresh))
                 progress = True
 
@@ -739,7 +833,7 @@ def space_merges(ops, enable):
         count[0] += ORDERED_INSTRS.get(op[0], 0)
         if op[0] in ("KEYS", "LIN", "SUB"):
             key_at[op[1]] = count[0]
-        if op[0] in ("MIN4", "KEYMINN", "SUBMIN4", "PKMIN", "PKMINE"):       # the ops whose result a level-0 merge reads
+        if op[0] in ("MIN4", "KEYMINN", "SUBMIN4", "PKMIN", "PKMINE", "PKMIN16"):       # the ops whose result a level-0 merge reads
             where[op[1]] = count[0]
         out.append((op, False))
 
@@ -751,7 +845,7 @@ def space_merges(ops, enable):
 
     for op in ops:
         try_flush()
-        if op[0] in ("MERGE", "ACC"):
+        if op[0] in ("MERGE", "PMERGE", "KEY16", "ACC"):
             pending.append(op)
             try_flush()
         elif op[0] == "MIN4" and key_at.get(op[2], -1) == count[0]:
@@ -806,6 +900,14 @@ def emit_cpp(tree, path, header=None):
             o.append(f"ME_PKMIN({op[1]}, {op[2]});")
         elif t == "PKMINE":
             o.append(f"ME_PKMINE({op[1]}, {op[2]});")
+        elif t == "PKMIN16":
+            _, r, p, half, even, slot = op
+            o.append(f"ME_PKMIN16_{'HI' if half else 'LO'}({r}, {f'(({p}) << 1)' if even else f'({p})'} + pkm);")
+        elif t == "PMERGE":
+            _, level, m, a, b = op
+            o.append(f"const uint32_t {m} = me_pmerge{level}{'' if padded else '_nn'}({a}, {b});")
+        elif t == "KEY16":
+            o.append(f"ME_KEY16_{'HI' if op[3] else 'LO'}({op[1]}, {op[2]});")
         elif t == "MERGE":
             _, level, m, a, b = op
             a = a if a is not None else "ME_MAXKEY"
@@ -865,11 +967,11 @@ def write_if_changed(path, text):
         f.write(text)
 
 
-def emit_slotmap(tree, path):
+def emit_slotmap(tree, path, name="ME_SLOT_OF", note="Same for fen=0 and fen=1."):
     t = tree.slot_of_lane()
     o = ["// GENERATED by tools/gen_me_tree.py: slot held by lane l of running-minimum register g",
-         "// after the butterfly (-1 = padding).  Same for fen=0 and fen=1.",
-         "static __device__ const short ME_SLOT_OF[%d][64] = {" % N_GROUPS]
+         "// after the butterfly (-1 = padding).  " + note,
+         "static __device__ const short %s[%d][64] = {" % (name, N_GROUPS)]
     for g in range(N_GROUPS):
         o.append("  {" + ", ".join(str(int(v)) for v in t[g]) + "},")
     o.append("};")
@@ -960,7 +1062,8 @@ PK_COST_MAX = PK_MARKER - PK_SLOT_MAX - 1   # ... and every valid cost + sum sta
 # ---- marker-free twin (pk = 2): which classes of 16x16-level slots take the packed minimum ----------------------------------------
 PK2_SLOT_MAX = 16 * 12 * 255            # 48 960: 16x12 / 12x16, the largest sum a PKMIN slot of the marker-free body holds (FEN: even rows x 2)
 PK2_COST_MAX = 0xFFFF - PK2_SLOT_MAX    # 16 575: the largest MV cost with which every packed cost stays below 2^16 (me_pk2_gate)
-OPS = {"PKADD": 1, "PKSUB": 2, "KEYS": 4, "LIN": 4, "SUB": 4, "MIN4": 2, "PKMIN": 4, "PKMINE": 4}   # VALU instructions per IR op
+OPS = {"PKADD": 1, "PKSUB": 2, "KEYS": 4, "LIN": 4, "SUB": 4, "MIN4": 2, "PKMIN": 4, "PKMINE": 4,   # VALU instructions per IR op
+       "PKMIN16": 3, "KEY16": 1, "PMERGE": 2}   # full-task twin: 64-bit add + v_pk_min_u16 + v_min_u16_sdwa; one v_mad_u32_u16; swap + v_pk_min_u16
 # class -> (slots per 16x16 CU, largest cost, ops per 16x16 CU in the pk tree, ops in packed form, ops it adds above per 16x16 CU).
 # Slots whose forms depend on each other are one class: 12x16 is a key difference (whole - 4x16) only while 4x16 forms keys.
 # Above: a 32x32 forms 32x8 (all rows) and 8x32 from the strips of two regions on its edge -- a union of two keys (LIN) today, a packed
@@ -982,14 +1085,22 @@ def pk2_choice():
     return {name: mx <= PK2_SLOT_MAX and new + above < old for name, (n, mx, old, new, above) in PK2_CLASSES.items() if name != "16x16"}
 
 
-def valu_count(tree):
-    """full-rate VALU instructions of one lane-iteration of a Tree (the leaves' v_qsad_pk_u16_u8 not counted)"""
+# VALU instructions of a merge of two key registers, level by level, as the ISA has them: a masked DPP pair, v_permlane*_swap + v_min_u32,
+# two v_cndmask_b32 + v_min_u32_dpp (+ a v_mov_b32_dpp where the compiler does not fold the move: counted as 4)
+MERGE_ISA = (2, 2, 2, 2, 4, 4)
+
+
+def valu_count(tree, isa=False):
+    """full-rate VALU instructions of one lane-iteration of a Tree (the leaves' v_qsad_pk_u16_u8 not counted).  The default prices every
+    merge of levels 2..5 at 4, the figure the stop rules of the packed-minimum twins were written against (it overstates the two swap
+    levels by 2 each); isa=True prices them at MERGE_ISA"""
     counts = {}
     for op in tree.ops:
         counts[op[0]] = counts.get(op[0], 0) + 1
     valu = sum(OPS[t] * counts.get(t, 0) for t in OPS) + counts.get("ACC", 0)
     merges = [sum(1 for op in tree.ops if op[0] == "MERGE" and op[1] == lv) for lv in range(6)]
-    return valu + 2 * (merges[0] + merges[1]) + 4 * sum(merges[2:]), counts, merges
+    price = MERGE_ISA if isa else (2, 2, 4, 4, 4, 4)
+    return valu + sum(p * m for p, m in zip(price, merges)), counts, merges
 
 
 def simulate(tree, window, cur, lane_off, c, best, pk=None):
@@ -1048,6 +1159,22 @@ def simulate(tree, window, cur, lane_off, c, best, pk=None):
             word = sum(int(1 << (16 * j)) * q[:, j].astype(object) for j in range(4))
             q = np.stack([np.array([(int(w) >> (16 * j)) & 0xFFFF for w in word], np.int64) for j in range(4)], axis=1)
             val[op[1]] = (q.min(axis=1) * MULT_A + pk[1].astype(np.int64)).astype(np.uint32)
+        elif t == "PKMIN16":
+            # full tasks only: every lane is valid, no field may overflow.  The minimum of the four u16 costs lands in one half of r
+            _, r, p, half, even, slot = op
+            q = (val[p].astype(np.int64) << even) + pk[0].T.astype(np.int64)
+            assert (q <= 0xFFFF).all(), "a packed cost left its 16 bits"
+            val.setdefault(r, np.zeros((64, 2), np.int64))[:, half] = q.min(axis=1)
+        elif t == "PMERGE":
+            # v_permlane32_swap / v_permlane16_swap of two pair registers, then v_pk_min_u16: lanes whose role bit is 0 keep both slots
+            # of a (minimum over the lane pair), the others both slots of b
+            _, level, m, a, b = op
+            perm, role = _perm_level(level)
+            keep = np.where(role[:, None] == 1, val[b], val[a])
+            give = np.where(role[:, None] == 1, val[a], val[b])
+            val[m] = np.minimum(keep, give[perm])
+        elif t == "KEY16":
+            val[op[1]] = (val[op[2]][:, op[3]] * MULT_A + pk[1].astype(np.int64)).astype(np.uint32)
         elif t == "MERGE":
             _, level, m, a, b = op
             A = val[a] if a is not None else MAXK
@@ -1061,13 +1188,49 @@ def simulate(tree, window, cur, lane_off, c, best, pk=None):
     return best
 
 
+def full_layout(k):
+    """lane -> (lx, ly) in a full task of part k (2..5): lane bits 5, 4 are the two lowest bits of the quad index lx, so that lanes
+    l, l ^ 16, l ^ 32, l ^ 48 hold four adjacent quads (16 contiguous candidates of one row); the other lx bits and ly take lane bits
+    0..3, ly above lx.  The key's lane field is ly << k | lx (raster order), not the physical lane"""
+    lx = ((LANES >> 5) & 1) | (((LANES >> 4) & 1) << 1) | ((LANES & ((1 << (k - 2)) - 1)) << 2)
+    return lx, (LANES & 15) >> (k - 2)
+
+
+def lds_conflicts(lx, ly):
+    """bank conflicts of the body's ds_read2_b32 under a lane layout: the wave's read goes out as lanes 0..31 and lanes 32..63, each
+    dword of the pair on its own; bank = dword mod 32.  -> the largest number of distinct dwords that meet in one bank, over the
+    four accesses (1 = conflict-free)"""
+    worst = 1
+    for half in (LANES < 32, LANES >= 32):
+        for d in (0, 1):
+            dw = set((ly[half] * PDW + lx[half] + d).tolist())
+            banks = {}
+            for x in dw:
+                banks[x % 32] = banks.get(x % 32, 0) + 1
+            worst = max(worst, max(banks.values()))
+    return worst
+
+
+def task_full(wx, wy, k, it0, n_it):
+    """me_task_full (me_kernels.hpp)"""
+    if k < 2:
+        return False
+    quads = (wx + 3) >> 2
+    if wx & 3 and quads & -quads == 1 << k:
+        return False
+    fold = bool(quads & 32) and bool(quads & 31) and bool(wy & 1)
+    return (it0 + n_it) * (64 >> k) <= (wy if k == 5 or not fold else wy - 1)
+
+
 def main():
-    names = {False: "me_tree_fen%d.inc", True: "me_tree_pk_fen%d.inc", 2: "me_tree_pk2_fen%d.inc"}
-    headers = {False: None, True: HEADER_PK, 2: HEADER_PK2}
-    label = {False: "", True: " packed minima", 2: " packed minima, marker-free"}
-    for fen, pk in ((0, False), (1, False), (0, True), (1, True), (1, 2)):
-        tree = Tree(fen, pk).build()
-        emit_cpp(tree, os.path.join(OUT_DIR, names[pk] % fen), headers[pk])
+    names = {False: "me_tree_fen%d.inc", True: "me_tree_pk_fen%d.inc", 3: "me_tree_pk3_fen%d.inc"}
+    headers = {False: None, True: HEADER_PK, 3: HEADER_PK3}
+    label = {False: "", True: " packed minima", 2: " packed minima, marker-free", 3: " packed minima and packed swap levels, full tasks"}
+    tree3 = Tree(1, 3).build()
+    for fen, pk in ((0, False), (1, False), (0, True), (1, True), (1, 2), (1, 3)):
+        tree = tree3 if pk == 3 else Tree(fen, pk).build()
+        if pk != 2:     # the marker-free tree is the full-task twin's yardstick (and its tests' model): no kernel includes it
+            emit_cpp(tree, os.path.join(OUT_DIR, names[pk] % fen), headers[pk])
         # a packed add is ONE v_lshl_add_u64, a packed subtract two v_sub_u32; PKMIN = packed add of the MV costs + 3
         valu, counts, merges = valu_count(tree)
         print(f"fen={fen}{label[pk]}: {len(tree.ops)} IR ops {counts}; merges/level {merges}; ~{valu} full-rate VALU + "
@@ -1075,10 +1238,17 @@ def main():
         if pk == 2:
             print(f"fen={fen}{label[pk]}: {valu_count(Tree(fen, True).build())[0] - valu} VALU instructions below the packed-minimum tree "
                   f"(classes packed: {', '.join(k for k, v in tree.pk2.items() if v)})")
-        if pk:
+        if pk == 3:
+            below = valu_count(Tree(fen, 2).build())[0] - valu
+            print(f"fen={fen}{label[pk]}: {below} VALU instructions below the marker-free tree ({valu_count(tree, isa=True)[0]} against "
+                  f"{valu_count(Tree(fen, 2).build(), isa=True)[0]} with every merge at its ISA price)")
+            assert sorted(tree.slot_of_lane().ravel().tolist())[-593:] == list(range(593)), "the full-task slot map is a permutation"
+        elif pk:
             assert np.array_equal(ref_map, tree.slot_of_lane()), "the packed-minimum tree must use the same slot map"
+            assert np.array_equal(ref_map, tree.slot_of_lane_traced())
         elif fen == 1:
             emit_slotmap(tree, os.path.join(OUT_DIR, "me_slotmap.inc"))
+            emit_slotmap(tree3, os.path.join(OUT_DIR, "me_slotmap3.inc"), "ME_SLOT_OF3", "The full-task twin's (me_tree_pk3_fen1.inc).")
         else:
             ref_map = tree.slot_of_lane()
     assert np.array_equal(ref_map, Tree(1).build().slot_of_lane()), "slot map must not depend on fen"

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """instruction mix of one kernel in the built ISA (hm-opencl_amd/csrc/build/*.s): tools/isa_stats.py <mangled-name prefix> [file]
-prints the opcode histogram, the SGPR-spill traffic (v_readlane / v_writelane) and s_nop counts, in total and inside the largest
-basic block (the generated straight-line body of a lane-iteration)"""
+prints the opcode histogram, the SGPR-spill traffic (v_readlane / v_writelane) and s_nop counts, in total and inside the two largest
+basic blocks (the generated straight-line bodies of a lane-iteration: a PK = 2 kernel holds two, the packed-minimum twin's and the smaller full-task twin's)"""
 import collections, os, re, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "hm-opencl_amd/csrc/build/hmme-hip-amdgcn-amd-amdhsa-gfx950.s")
@@ -12,8 +12,7 @@ body = s[start:end].split("\n")
 op = lambda l: l.strip().split(" ")[0] if l.strip() and not l.strip().startswith((";", ".")) else ""
 idx = [i for i, l in enumerate(body) if re.match(r"^\.LBB\d+_\d+:", l)] + [len(body)]
 blocks = sorted(((b - a, a, b) for a, b in zip([0] + idx[:-1], idx)), reverse=True)
-n, a, b = blocks[0]
-for name, lines in (("whole kernel", body), ("largest basic block", body[a:b])):
+for name, lines in [("whole kernel", body)] + [(f"{'' if i == 0 else 'second '}largest basic block", body[a:b]) for i, (n, a, b) in enumerate(blocks[:2])]:
     c = collections.Counter(op(l) for l in lines if op(l))
     valu = sum(v for k, v in c.items() if k.startswith("v_"))
     nop_cycles = sum(int(l.split()[1]) + 1 for l in lines if op(l) == "s_nop")
