@@ -2155,9 +2155,11 @@ int bi_check(hmme_ctx* ctx, const char* who, const hmme_frame_params* fp, int re
 
 // the argument checks of a bi-prediction launch that pairs_begin does not make
 int bi_args(hmme_ctx* ctx, const char* who, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others, int n_pairs,
-            const hmme_frame_params* fp, const void* d_other_mv, int mv_per_ctu) {
+            const hmme_frame_params* fp, const void* d_other_mv, int mv_per_ctu, bool four = false) {
   if (!curs || !refs || !others || n_pairs < 1 || n_pairs > hmme::kMaxRefs) return fail(ctx, HMME_ERR_ARG, "%s: %d picture pairs outside 1..%d (or a null plane list)", who, n_pairs, hmme::kMaxRefs);
-  if (!d_other_mv || (mv_per_ctu != 1 && mv_per_ctu != 64)) return fail(ctx, HMME_ERR_ARG, "%s: null motion field, or %d MVs per CTU (1 or 64)", who, mv_per_ctu);
+  // the *_bi4 entries (four) are the 256 layout and nothing else; every other entry takes 1 or 64
+  if (!d_other_mv || (four ? mv_per_ctu != 256 : (mv_per_ctu != 1 && mv_per_ctu != 64)))
+    return fail(ctx, HMME_ERR_ARG, "%s: null motion field, or %d MVs per CTU (%s)", who, mv_per_ctu, four ? "256" : "1 or 64");
   for (int r = 0; r < n_pairs; ++r) {
     if (!curs[r] || !refs[r] || !others[r]) return fail(ctx, HMME_ERR_ARG, "%s: null plane", who);
     if (others[r]->ctx != ctx) return fail(ctx, HMME_ERR_ARG, "plane belongs to another context (planes are used with the context that created them)");
@@ -2330,16 +2332,20 @@ int launch_predict(hmme_ctx* ctx, const hmme_plane* src, const int16_t* d_field,
 }
 
 // me_predict4_kernel for CTUs [first, first + count) of a picture like `src`: one MV and one reference index (d_ref_field null: 0) per 4x4
-// block, every plane of `set`; prw: one weight per reference (null: none, and identities)
+// block, every plane of `set`; prw: one weight per reference (null: none, and identities); org: the bi-prediction origin of the *_bi4 calls
+// instead of the prediction (unweighted), dst / dst_pitch then being the origin's
 int launch_predict4(hmme_ctx* ctx, const hmme_plane* src, const hmme::RefSet& set, int n_refs, const int16_t* d_field, const uint8_t* d_ref_field, int first, int count,
-                    uint8_t* dst, int dst_pitch, hipStream_t s, const hmme::MePredWp<2>* prw) {
+                    uint8_t* dst, int dst_pitch, hipStream_t s, const hmme::MePredWp<2>* prw, const hmme::MePred4Origin<1>* org = nullptr) {
   with_sample_type(src->bps, [&](auto sample) {
     using T = decltype(sample);
-    const auto go = [&](auto kernel, auto wp) {
+    const auto go = [&](auto kernel, auto wp, auto origin) {
       hipLaunchKernelGGL(kernel, dim3((unsigned)count), dim3(256), 0, s, set, n_refs, src->pitch, d_field, d_ref_field, first, src->width, src->height, src->bit_depth, dst,
-                         dst_pitch, wp);
+                         dst_pitch, wp, origin);
     };
-    if (prw) go(hmme::me_predict4_kernel<T, 2>, *prw); else go(hmme::me_predict4_kernel<T, 0>, hmme::MePredWp<0>{});
+    const hmme::MePred4Origin<0> none;
+    if (org) go(hmme::me_predict4_kernel<T, 0, 1>, hmme::MePredWp<0>{}, *org);
+    else if (prw) go(hmme::me_predict4_kernel<T, 2>, *prw, none);
+    else go(hmme::me_predict4_kernel<T, 0>, hmme::MePredWp<0>{}, none);
   });
   HIP_TRY(ctx, hipGetLastError());
   return HMME_OK;
@@ -2646,6 +2652,11 @@ int bi_origin(hmme_ctx* ctx, const BiLaunch& B, int r, const PairLaunch& pl, con
   uint8_t* dst = o.dst + o.slot * k;
   *at = dst;
   if (lists && r != B.n - 1) return HMME_OK;
+  if (B.mv_per_ctu == 256) {   // the *_bi4 entries (pairs form, unweighted): the origin from one MV per 4x4 block
+    const hmme::MePred4Origin<1> org = {B.curs[k]->d_blocks, B.bw.bias[k], o.ctu_x, o.ctu_y};
+    return launch_predict4(ctx, B.others[k], one_ref(B.others[k]->origin()), 1, (const int16_t*)B.d_other_mv + (size_t)B.curs[0]->n_ctu * 512 * k, nullptr, pl.first, pl.count,
+                           dst, o.pitch, s, nullptr, &org);
+  }
   hmme::MePredRefs<1> pr = {one_ref(nullptr), (const uint8_t*)B.d_other_ref, B.n_others};
   for (int q = 0; lists && q < B.n_others; ++q) pr.set.base[q] = B.others[q]->origin();
   const size_t field = (size_t)B.curs[0]->n_ctu * B.mv_per_ctu * 2;
@@ -2733,11 +2744,11 @@ int bi_refine(hmme_ctx* ctx, const BiLaunch& B, const hmme_frame_params* fp, con
 
 // What distinguishes the sixteen entries: the name for messages, the form, explicit weights or not, search or refinement, and whether the
 // arrays are the host's (the synchronous forms).  plain: the unweighted device entry, which an all-identity call IS and answers as
-enum : unsigned { kBiLists = 1, kBiWeighted = 2, kBiRefine = 4, kBiHost = 8 };
+enum : unsigned { kBiLists = 1, kBiWeighted = 2, kBiRefine = 4, kBiHost = 8, kBiFour = 16 };   // kBiFour: the field is the 256 layout (pairs form, unweighted)
 struct BiCall {
-  const char* who; const char* plain; bool lists, weighted, refine, host;
+  const char* who; const char* plain; bool lists, weighted, refine, host, four;
   BiCall(const char* who_, unsigned what, const char* plain_ = nullptr)
-      : who(who_), plain(plain_), lists(what & kBiLists), weighted(what & kBiWeighted), refine(what & kBiRefine), host(what & kBiHost) {}
+      : who(who_), plain(plain_), lists(what & kBiLists), weighted(what & kBiWeighted), refine(what & kBiRefine), host(what & kBiHost), four(what & kBiFour) {}
 };
 
 // The refusals of a bi call in the order that decides the code returned: null params, then the weights (without them: the depth), then the
@@ -2754,7 +2765,7 @@ int bi_checks(hmme_ctx* ctx, const BiCall& c, BiLaunch* B, const hmme_frame_para
   if (c.weighted && B->bw.all_identity) { B->wps = nullptr; if (!c.host) who = c.plain; }
   if (!B->wps) B->bw = BiWp::unweighted(f->bit_depth);
   return c.lists ? bi_refs_args(ctx, who, B->cur, B->refs, B->n, B->others, B->n_others, f, B->d_other_mv, B->d_other_ref, B->mv_per_ctu)
-                 : bi_args(ctx, who, B->curs, B->refs, B->others, B->n, f, B->d_other_mv, B->mv_per_ctu);
+                 : bi_args(ctx, who, B->curs, B->refs, B->others, B->n, f, B->d_other_mv, B->mv_per_ctu, c.four);
 }
 
 // Every entry: the checks, then the body on the caller's stream -- or, for the host arrays of a synchronous form, through the staging arena
@@ -2825,6 +2836,39 @@ int hmme_refine_pairs_bi_w_device(hmme_ctx* ctx, const hmme_plane* const* curs, 
   return bi_call(ctx, BiCall("hmme_refine_pairs_bi_w_device", kBiWeighted | kBiRefine, "hmme_refine_pairs_bi_device"),
                  {curs, nullptr, refs, n_pairs, others, n_pairs, d_other_mv, nullptr, mv_per_ctu, wps}, fp, other_wps, d_center_q, d_pred_q, d_int_mv, use_hadamard, d_out_qmv,
                  d_out_cost, stream);
+}
+
+// ... from one MV per 4x4 block (the rule: include/hmme.h, "B pictures from one MV per 4x4 block"): every refusal names the entry, those of
+// the shared checks (the CTU range, plane ownership, a null table), too ...
+int hmme_search_pairs_bi4_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others,
+                                 int n_pairs, const hmme_frame_params* fp, const void* d_other_mv, const void* d_center_q, const void* d_pred_q,
+                                 void* d_out_mv, void* d_out_sad, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  return named(ctx, "hmme_search_pairs_bi4_device", bi_call(ctx, BiCall("hmme_search_pairs_bi4_device", kBiFour), {curs, nullptr, refs, n_pairs, others, n_pairs, d_other_mv, nullptr, 256},
+                 fp, nullptr, d_center_q, d_pred_q, nullptr, 0, d_out_mv, d_out_sad, stream));
+}
+
+int hmme_refine_pairs_bi4_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others,
+                                 int n_pairs, const hmme_frame_params* fp, const void* d_other_mv, const void* d_center_q, const void* d_pred_q,
+                                 const void* d_int_mv, int use_hadamard, void* d_out_qmv, void* d_out_cost, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  return named(ctx, "hmme_refine_pairs_bi4_device", bi_call(ctx, BiCall("hmme_refine_pairs_bi4_device", kBiFour | kBiRefine), {curs, nullptr, refs, n_pairs, others, n_pairs, d_other_mv, nullptr, 256},
+                 fp, nullptr, d_center_q, d_pred_q, d_int_mv, use_hadamard, d_out_qmv, d_out_cost, stream));
+}
+
+int hmme_search_frame_bi4(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
+                          const int16_t* other_mv, const int16_t* center_q, const int16_t* pred_q, int16_t* out_mv, uint32_t* out_sad) {
+  if (!ctx) return HMME_ERR_ARG;
+  return named(ctx, "hmme_search_frame_bi4", bi_call(ctx, BiCall("hmme_search_frame_bi4", kBiFour | kBiHost), {&cur, nullptr, &ref, 1, &other, 1, other_mv, nullptr, 256}, fp, nullptr, center_q,
+                 pred_q, nullptr, 0, out_mv, out_sad, nullptr));
+}
+
+int hmme_refine_frame_bi4(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
+                          const int16_t* other_mv, const int16_t* center_q, const int16_t* pred_q, const int16_t* int_mv, int use_hadamard,
+                          int16_t* out_qmv, uint32_t* out_cost) {
+  if (!ctx) return HMME_ERR_ARG;
+  return named(ctx, "hmme_refine_frame_bi4", bi_call(ctx, BiCall("hmme_refine_frame_bi4", kBiFour | kBiRefine | kBiHost), {&cur, nullptr, &ref, 1, &other, 1, other_mv, nullptr, 256}, fp, nullptr,
+                 center_q, pred_q, int_mv, use_hadamard, out_qmv, out_cost, nullptr));
 }
 
 // ... and one pair of it on host arrays
@@ -2954,20 +2998,21 @@ int select_refs_eval(const hmme_select_params* sel, int n_pics, int n_refs, cons
   return HMME_OK;
 }
 // ... of both B-picture decisions, up to the bit counts: dirs = the caller's hmme_dir_params or hmme_dir_refs_params, for null only
-int select_bi_eval(const hmme_select_params* sel, int n_pics, const void* dirs, char* msg, size_t cap) {
+// per: the layout the entry decides at -- 64, or 256 for hmme_select_dirs4_*
+int select_bi_eval(const hmme_select_params* sel, int n_pics, const void* dirs, char* msg, size_t cap, int per = 64) {
   const int bad = select_eval(sel, msg, cap);
   if (bad) return bad;
-  if (sel->mv_per_ctu != 64 || sel->mv_unit != 0 || sel->price_mv != 0) {
-    snprintf(msg, cap, "mv_per_ctu %d, mv_unit %d, price_mv %d: the direction is decided on quarter-pel refinement tables, one MV per 8x8 block (64, 0, 0)",
-             sel->mv_per_ctu, sel->mv_unit, sel->price_mv);
+  if (sel->mv_per_ctu != per || sel->mv_unit != 0 || sel->price_mv != 0) {
+    snprintf(msg, cap, "mv_per_ctu %d, mv_unit %d, price_mv %d: the direction is decided on quarter-pel refinement tables, one MV per %s block (%d, 0, 0)",
+             sel->mv_per_ctu, sel->mv_unit, sel->price_mv, per == 64 ? "8x8" : "4x4", per);
     return HMME_ERR_ARG;
   }
   if (n_pics < 1 || n_pics > kMaxDirPics) { snprintf(msg, cap, "%d pictures outside 1..%d", n_pics, kMaxDirPics); return HMME_ERR_ARG; }
   if (!dirs) { snprintf(msg, cap, "null direction parameters"); return HMME_ERR_ARG; }
   return HMME_OK;
 }
-int select_dirs_eval(const hmme_select_params* sel, int n_pics, const hmme_dir_params* dirs, char* msg, size_t cap) {
-  const int bad = select_bi_eval(sel, n_pics, dirs, msg, cap);
+int select_dirs_eval(const hmme_select_params* sel, int n_pics, const hmme_dir_params* dirs, char* msg, size_t cap, int per = 64) {
+  const int bad = select_bi_eval(sel, n_pics, dirs, msg, cap, per);
   if (bad) return bad;
   for (int p = 0; p < n_pics; ++p) {
     const uint32_t v[5] = {dirs[p].dir_bits[0], dirs[p].dir_bits[1], dirs[p].dir_bits[2], dirs[p].list_bits[0], dirs[p].list_bits[1]};
@@ -2995,7 +3040,7 @@ int select_dirs_refs_eval(const hmme_select_params* sel, int n_pics, int n_refs_
 }
 
 // One selection call, device or host form.  The buffers in the order they are checked: the family's own, then the ones every family has
-enum SelectFamily { kSelectTable, kSelectRefs, kSelectDirs, kSelectDirsRefs };
+enum SelectFamily { kSelectTable, kSelectRefs, kSelectDirs, kSelectDirsRefs, kSelectDirs4 };   // kSelectDirs4: kSelectDirs at one MV per 4x4 block
 enum SelectBufName { kMvBi, kCostBi, kUniField, kUniRef, kOutRef, kOutDir, kMv, kCost, kPredQ, kOutField, kOutSlot, kOutCost, kSelectBufs };
 enum SelectRole { kInTable, kInPicture, kOut };   // an input over the CTUs of the range / of the picture; an output (of the picture: the range is written)
 struct SelectBuf {
@@ -3015,7 +3060,7 @@ struct SelectCall {
   const hmme_frame_params* fp;
   const hmme_select_params* sel;
   const uint32_t* ref_cost = nullptr;                // kSelectRefs (null: zeros)
-  const hmme_dir_params* dirs = nullptr;             // kSelectDirs
+  const hmme_dir_params* dirs = nullptr;             // kSelectDirs, kSelectDirs4
   const hmme_dir_refs_params* dir_refs = nullptr;    // kSelectDirsRefs
   SelectBuf buf[kSelectBufs];
   SelectCall(const char* who, SelectFamily family, int width, int height, int n_pics, int n_refs, const hmme_frame_params* fp, const hmme_select_params* sel)
@@ -3024,13 +3069,14 @@ struct SelectCall {
     // (sizes matter to select_host alone, behind the evaluation of sel and n_refs)
     const size_t per = sel ? (size_t)sel->mv_per_ctu : 0, row = HMME_NUM_CTU_PARTS * 4, none = 0, one = 1, lists = bi ? 2 : 1;
     const size_t sets = refs ? (size_t)n_refs : multi ? 2 * (size_t)n_refs : lists;
+    const size_t bper = family == kSelectDirs4 ? 256 : 64;   // blocks per CTU of a B-picture decision's own buffers
     const SelectBuf all[kSelectBufs] = {
         {"bi MV table", kInTable, row, bi ? sets : none, 4, true, nullptr},
         {"bi cost table", kInTable, row, bi ? sets : none, 4, true, nullptr},
-        {"input field", kInPicture, 64 * 4, bi ? lists : none, 4, true, nullptr},
+        {"input field", kInPicture, bper * 4, bi ? lists : none, 4, true, nullptr},
         {"input reference", kInPicture, 64, multi ? lists : none, 1, true, nullptr},
         {"reference", kOut, refs ? per : 64, refs ? one : multi ? lists : none, refs ? 2u : 1u, true, nullptr},   // with four MVs per 8x8 block the kernel stores two indices at a time
-        {"direction", kOut, 64, bi ? one : none, multi ? 1u : 2u, true, nullptr},
+        {"direction", kOut, bper, bi ? one : none, multi ? 1u : 2u, true, nullptr},   // kSelectDirs4: two directions per store
         {"MV table", kInTable, row, sets, 4, true, nullptr},   // the kernels move MVs as dwords
         {"cost table", kInTable, row, sets, 4, true, nullptr},
         {"predictor", kInPicture, 4, sets, 2, false, nullptr},
@@ -3059,6 +3105,7 @@ int select_check(hmme_ctx* ctx, const SelectCall& c, bool device, int* n_ctu, in
   int bad;
   if (c.family == kSelectRefs && (bad = buffers(kOutRef, kOutRef + 1))) return bad;   // hmme_select_refs_* look at the reference buffer before the parameters
   if (c.family == kSelectDirs) bad = select_dirs_eval(c.sel, c.n_pics, c.dirs, msg, sizeof msg);
+  else if (c.family == kSelectDirs4) bad = select_dirs_eval(c.sel, c.n_pics, c.dirs, msg, sizeof msg, 256);
   else if (c.family == kSelectDirsRefs) bad = select_dirs_refs_eval(c.sel, c.n_pics, c.n_refs, c.dir_refs, msg, sizeof msg);
   else bad = select_refs_eval(c.sel, c.n_pics, c.n_refs, c.ref_cost, msg, sizeof msg);
   if (bad) return fail(ctx, bad, "%s: %s", c.who, msg);
@@ -3096,11 +3143,14 @@ int select_device(hmme_ctx* ctx, const SelectCall& c, hipStream_t stream) {
     for (int r = 0; c.ref_cost && r < c.n_refs; ++r) price.c[r] = c.ref_cost[r];
     hipLaunchKernelGGL(hmme::me_select_refs_kernel, grid, block, 0, stream, tab(kMv), tab(kCost), pred_q, out_field, bytes(kOutRef), out_slot, out_cost, a, price, c.n_refs, c.width, c.height,
                        n_ctu, first, count, ctx->lambda_q16);
-  } else if (c.family == kSelectDirs) {
+  } else if (c.family == kSelectDirs || c.family == kSelectDirs4) {
     hmme::MeDirParams bits = {};
     memcpy(bits.p, c.dirs, c.n_pics * sizeof *c.dirs);
-    hipLaunchKernelGGL(hmme::me_select_dirs_kernel, grid, block, 0, stream, tab(kMv), tab(kCost), tab(kMvBi), tab(kCostBi), tab(kUniField), pred_q, out_field, bytes(kOutDir),
-                       out_slot, out_cost, a, bits, c.width, c.height, n_ctu, first, count, ctx->lambda_q16);
+    const auto go = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, grid, block, 0, stream, tab(kMv), tab(kCost), tab(kMvBi), tab(kCostBi), tab(kUniField), pred_q, out_field, bytes(kOutDir), out_slot, out_cost, a,
+                         bits, c.width, c.height, n_ctu, first, count, ctx->lambda_q16);
+    };
+    if (c.family == kSelectDirs4) go(hmme::me_select_dirs_kernel<true>); else go(hmme::me_select_dirs_kernel<false>);
   } else {
     hmme::MeDirRefsParams bits = {};
     memcpy(bits.p, c.dir_refs, c.n_pics * sizeof *c.dir_refs);
@@ -3411,6 +3461,32 @@ int hmme_select_dirs_frame(hmme_ctx* ctx, int width, int height, const hmme_fram
                          .with(kOutDir, out_dir).with(kOutSlot, out_slot).with(kOutCost, out_cost));
 }
 
+// ... at one MV per 4x4 block: all 593 slots, with HM's isBipredRestriction (the rule: include/hmme.h)
+int hmme_select_dirs4_check(const hmme_select_params* sel, int n_pics, const hmme_dir_params* dirs) {
+  char msg[256];
+  return select_dirs_eval(sel, n_pics, dirs, msg, sizeof msg, 256);
+}
+
+int hmme_select_dirs4_device(hmme_ctx* ctx, int width, int height, int n_pics, const hmme_frame_params* fp, const hmme_select_params* sel,
+                             const hmme_dir_params* dirs, const void* d_mv_uni, const void* d_cost_uni, const void* d_mv_bi, const void* d_cost_bi,
+                             const void* d_uni_field, const void* d_pred_q, void* d_out_field, void* d_out_dir, void* d_out_slot, void* d_out_cost,
+                             void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  return named(ctx, "hmme_select_dirs4_device", select_device(ctx, SelectCall("hmme_select_dirs4_device", kSelectDirs4, width, height, n_pics, 1, fp, sel).with(dirs).with(kMv, d_mv_uni).with(kCost, d_cost_uni)
+                                .with(kMvBi, d_mv_bi).with(kCostBi, d_cost_bi).with(kUniField, d_uni_field).with(kPredQ, d_pred_q).with(kOutField, d_out_field)
+                                .with(kOutDir, d_out_dir).with(kOutSlot, d_out_slot).with(kOutCost, d_out_cost), (hipStream_t)stream));   // the CTU range's refusal, too, names the entry
+}
+
+int hmme_select_dirs4_frame(hmme_ctx* ctx, int width, int height, const hmme_frame_params* fp, const hmme_select_params* sel,
+                            const hmme_dir_params* dir, const int16_t* mv_uni, const uint32_t* cost_uni, const int16_t* mv_bi, const uint32_t* cost_bi,
+                            const int16_t* uni_field, const int16_t* pred_q, int16_t* out_field, uint8_t* out_dir, uint16_t* out_slot,
+                            uint32_t* out_cost) {
+  if (!ctx) return HMME_ERR_ARG;
+  return named(ctx, "hmme_select_dirs4_frame", select_host(ctx, SelectCall("hmme_select_dirs4_frame", kSelectDirs4, width, height, 1, 1, fp, sel).with(dir).with(kMv, mv_uni).with(kCost, cost_uni)
+                              .with(kMvBi, mv_bi).with(kCostBi, cost_bi).with(kUniField, uni_field).with(kPredQ, pred_q).with(kOutField, out_field)
+                              .with(kOutDir, out_dir).with(kOutSlot, out_slot).with(kOutCost, out_cost)));   // the CTU range's refusal, too, names the entry
+}
+
 // ---- L0, L1 or bi and the reference index per list, per PU: the decision over the table sets of a B picture with several references -----------
 int hmme_select_dirs_refs_check(const hmme_select_params* sel, int n_pics, int n_refs_max, const hmme_dir_refs_params* dirs) {
   char msg[256];
@@ -3454,7 +3530,7 @@ int check_predict_bi_weights(hmme_ctx* ctx, const char* who, const hmme_frame_pa
 // identities only, else 1.  Plane lists, weights and images hold `comps` entries per picture.
 int predict_bi(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs0, const hmme_plane* const* refs1, int n_pics, int comps, int width, int height,
                const hmme_frame_params* fp, const hmme_weight* wps0, const hmme_weight* wps1, bool weighted, const void* d_mv_field, const void* d_dir_field,
-               int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream) {
+               int mv_per_ctu, void* const* d_outs, int out_pitch_bytes, void* stream, bool four = false) {
   const int per_pic = 2 * comps, max_pics = hmme::kMaxRefs / per_pic;
   if (!refs0 || !refs1 || n_pics < 1 || n_pics > max_pics) return fail(ctx, HMME_ERR_ARG, "%s: %d pictures outside 1..%d (or a null plane list)", who, n_pics, max_pics);
   PredBiWp bw[hmme::kMaxRefs / 2];   // entry comps * i + c: component c of picture i
@@ -3464,7 +3540,7 @@ int predict_bi(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs0, c
   for (int i = 0; i < n_pics; ++i)
     for (int c = 0; c < comps; ++c) { planes[per_pic * i + c] = refs0[comps * i + c]; planes[per_pic * i + comps + c] = refs1[comps * i + c]; }
   PredictArgs a;
-  rc = predict_args(ctx, who, planes, per_pic * n_pics, !d_dir_field || !d_outs, fp, nullptr, d_mv_field, mv_per_ctu, out_pitch_bytes, &a, comps == 2 ? "plane" : "picture");
+  rc = predict_args(ctx, who, planes, per_pic * n_pics, !d_dir_field || !d_outs, fp, nullptr, d_mv_field, mv_per_ctu, out_pitch_bytes, &a, comps == 2 ? "plane" : "picture", four);
   if (rc) return rc;
   for (int r = 0; r < comps * n_pics; ++r)
     if (!d_outs[r]) return fail(ctx, HMME_ERR_ARG, "%s: null output image", who);
@@ -3482,6 +3558,14 @@ int predict_bi(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs0, c
       for (int k = 0; k < 4; ++k) src.set.base[k] = planes[4 * i + k]->origin();
       src.field = dirs;
       src.n_ctu = L.n_ctu;
+      if (four) {   // hmme_predict_chroma_bi4_device (unweighted)
+        with_sample_type(p0->bps, [&](auto sample) {
+          hipLaunchKernelGGL(hmme::me_predict_chroma_bi4_kernel<decltype(sample)>, dim3((unsigned)L.count), dim3(256), 0, s, src, p0->pitch, field, L.first, L.w, L.h,
+                             p0->bit_depth, (uint8_t*)d_outs[2 * i], (uint8_t*)d_outs[2 * i + 1], out_pitch_bytes);
+        });
+        if (hipGetLastError() != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "%s: launch failed", who);
+        continue;
+      }
       if (bw[2 * i].identity && bw[2 * i + 1].identity)
         rc = launch_chroma<2, 0>(ctx, p0, src, field, mv_per_ctu, L, d_outs[2 * i], d_outs[2 * i + 1], out_pitch_bytes, s, hmme::MeChromaWp<2, 0>{});
       else
@@ -3490,6 +3574,11 @@ int predict_bi(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs0, c
     }
     with_sample_type(p0->bps, [&](auto sample) {
       using T = decltype(sample);
+      if (four) {   // hmme_predict_bi4_device (unweighted)
+        hipLaunchKernelGGL(hmme::me_predict_bi4_kernel<T>, dim3((unsigned)L.count), dim3(256), 0, s, planes[2 * i]->origin(), planes[2 * i + 1]->origin(), p0->pitch, field, dirs,
+                           L.n_ctu, L.first, L.w, L.h, p0->bit_depth, (uint8_t*)d_outs[i], out_pitch_bytes);
+        return;
+      }
       const auto go = [&](auto kernel, auto wp) {
         hipLaunchKernelGGL(kernel, dim3((unsigned)L.count), dim3(256), 0, s, planes[2 * i]->origin(), planes[2 * i + 1]->origin(), p0->pitch, field, dirs, mv_per_ctu,
                            L.n_ctu, L.first, L.w, L.h, p0->bit_depth, (uint8_t*)d_outs[i], out_pitch_bytes, wp, hmme::MePredBiRefs<0>{});
@@ -3504,16 +3593,16 @@ int predict_bi(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs0, c
 // hmme_predict_bi_frame, _w_frame and hmme_predict_chroma_bi_frame; ref0 / ref1 / outs: `comps` entries each.  The weights answer first.
 int predict_bi_frame(hmme_ctx* ctx, const char* who, const hmme_plane* const* ref0, const hmme_plane* const* ref1, int comps, int width, int height,
                      const hmme_frame_params* fp, const hmme_weight* wp0, const hmme_weight* wp1, bool weighted, const int16_t* mv_field, const uint8_t* dir_field,
-                     int mv_per_ctu, void* const* outs, int out_stride) {
+                     int mv_per_ctu, void* const* outs, int out_stride, bool four = false) {
   int rc = weighted ? check_predict_bi_weights(ctx, who, fp, wp0, wp1, comps, nullptr) : HMME_OK;   // before anything is staged
   if (rc == HMME_OK) rc = bi_check(ctx, who, fp, 0);
-  if (rc == HMME_OK) rc = frame_args(ctx, who, fp, ref0, comps, comps, !ref1 || !mv_field || !dir_field || frame_null_outs(outs, comps), mv_per_ctu, width, height);
+  if (rc == HMME_OK) rc = frame_args(ctx, who, fp, ref0, comps, comps, !ref1 || !mv_field || !dir_field || frame_null_outs(outs, comps), mv_per_ctu, width, height, four);
   for (int c = 0; rc == HMME_OK && c < comps; ++c)
     if (!ref1[c]) rc = fail(ctx, HMME_ERR_ARG, "%s: null plane", who);
   if (rc) return rc;
   // blocks without a direction, too, come back as they were
   return frame_staged(ctx, who, ref0[0], comps, width, height, mv_field, dir_field, mv_per_ctu, outs, out_stride, 2, [&](void* d_field, void* d_dir_field, void* const* d_outs, int pitch, hipStream_t s) {
-    return predict_bi(ctx, who, ref0, ref1, 1, comps, width, height, fp, wp0, wp1, weighted, d_field, d_dir_field, mv_per_ctu, d_outs, pitch, s);
+    return predict_bi(ctx, who, ref0, ref1, 1, comps, width, height, fp, wp0, wp1, weighted, d_field, d_dir_field, mv_per_ctu, d_outs, pitch, s, four);
   });
 }
 }  // namespace
@@ -3551,6 +3640,35 @@ int hmme_predict_bi_w_frame(hmme_ctx* ctx, const hmme_plane* ref0, const hmme_pl
 }
 
 // ---- the prediction of a B picture with several references per list (the rule: include/hmme.h) --------------------------------------------------
+// ... from one MV and one direction per 4x4 block, unweighted, for Y and for the Cb / Cr of a 4:2:0 picture (me_predict_bi4_kernel,
+// me_predict_chroma_bi4_kernel; the rule: include/hmme.h, "B pictures from one MV per 4x4 block")
+int hmme_predict_bi4_device(hmme_ctx* ctx, const hmme_plane* const* refs0, const hmme_plane* const* refs1, int n_pics, const hmme_frame_params* fp,
+                            const void* d_mv_field, const void* d_dir_field, void* const* d_outs, int out_pitch_bytes, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  return predict_bi(ctx, "hmme_predict_bi4_device", refs0, refs1, n_pics, 1, 0, 0, fp, nullptr, nullptr, false, d_mv_field, d_dir_field, 256, d_outs, out_pitch_bytes, stream,
+                    true);
+}
+
+int hmme_predict_bi4_frame(hmme_ctx* ctx, const hmme_plane* ref0, const hmme_plane* ref1, const hmme_frame_params* fp, const int16_t* mv_field,
+                           const uint8_t* dir_field, void* out, int out_stride) {
+  if (!ctx) return HMME_ERR_ARG;
+  return predict_bi_frame(ctx, "hmme_predict_bi4_frame", &ref0, &ref1, 1, 0, 0, fp, nullptr, nullptr, false, mv_field, dir_field, 256, &out, out_stride, true);
+}
+
+int hmme_predict_chroma_bi4_device(hmme_ctx* ctx, const hmme_plane* const* refs0, const hmme_plane* const* refs1, int n_pics, int width, int height,
+                                   const hmme_frame_params* fp, const void* d_mv_field, const void* d_dir_field, void* const* d_outs, int out_pitch_bytes,
+                                   void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  return predict_bi(ctx, "hmme_predict_chroma_bi4_device", refs0, refs1, n_pics, 2, width, height, fp, nullptr, nullptr, false, d_mv_field, d_dir_field, 256, d_outs,
+                    out_pitch_bytes, stream, true);
+}
+
+int hmme_predict_chroma_bi4_frame(hmme_ctx* ctx, const hmme_plane* const* ref0, const hmme_plane* const* ref1, int width, int height, const hmme_frame_params* fp,
+                                  const int16_t* mv_field, const uint8_t* dir_field, void* const* outs, int out_stride) {
+  if (!ctx) return HMME_ERR_ARG;
+  return predict_bi_frame(ctx, "hmme_predict_chroma_bi4_frame", ref0, ref1, 2, width, height, fp, nullptr, nullptr, false, mv_field, dir_field, 256, outs, out_stride, true);
+}
+
 namespace {
 // The weights of one component of such a picture as the kernels take them (hmme_predict_bi_refs_weight_check; the rule: include/hmme.h,
 // "multi-reference B pictures: explicit weights and 4:2:0 chroma"): uni[l][r] is addWeightUni's form of list l's reference r, shift the

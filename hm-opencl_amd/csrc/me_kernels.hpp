@@ -2597,11 +2597,20 @@ me_predict_kernel(const uint8_t* __restrict__ ref_origin, int ref_pitch, const i
 // BARRIER INVARIANT: __syncthreads() is a barrier of the whole workgroup.  Every wave -- live, partly live or wholly dead -- runs all 16
 // iterations and meets the same two barriers in each: stage | barrier | horizontal | barrier | vertical.  Everything that depends on the
 // field (liveness, the plane, the phase) sits INSIDE a stage; no barrier is ever inside a branch, and no wave leaves the loop early.
-template <typename SrcT, int WP>
+//   OUT = 0: the prediction, as described above.  Takes an empty MePred4Origin and compiles to what it did without the parameter.
+//   OUT = 1: the bi-prediction origin 2 * cur - pred + bias as u16 from a 4x4 field (hmme_search_pairs_bi4_device / hmme_refine_pairs_bi4_device;
+//            WP = 0 only, and the callers pass n_refs = 1 with a null ref_field), as me_predict_kernel<SrcT, 1> forms it from a 64 field:
+//            EVERY quadrant is live, those beyond the picture edge included, cur comes from the current picture's CTU-blocked copy, and the
+//            block of CTU (cx, cy) starts at dst + cy * ctu_y + cx * ctu_x with rows dst_pitch bytes apart (the search's CTU blocks or the
+//            refinement's padded plane).  Liveness no longer depends on the field, so the barrier invariant holds as it did.
+template <int OUT> struct MePred4Origin {};
+template <> struct MePred4Origin<1> { const uint8_t* cur_blocks; int bias; long ctu_x, ctu_y; };
+template <typename SrcT, int WP, int OUT = 0>
 __global__ void __launch_bounds__(256)
 me_predict4_kernel(RefSet set, int n_refs, int ref_pitch, const int16_t* __restrict__ mv_field, const uint8_t* __restrict__ ref_field, int ctu_first,
-                   int pic_w, int pic_h, int bit_depth, uint8_t* __restrict__ dst, int dst_pitch, MePredWp<WP> wp) {
+                   int pic_w, int pic_h, int bit_depth, uint8_t* __restrict__ dst, int dst_pitch, MePredWp<WP> wp, MePred4Origin<OUT> org) {
   static_assert(WP == 0 || WP == 2, "one weight per reference, or none");
+  static_assert(OUT == 0 || WP == 0, "the origin from a 4x4 field is unweighted");
   __shared__ int16_t patch[4][4 * 11 * 12];
   __shared__ int16_t mid[4][4 * 11 * 4];
   __shared__ uint32_t taps[4][2];   // kLumaTaps, tap j of a phase = signed byte j of the pair; read behind the first barrier
@@ -2629,7 +2638,8 @@ me_predict4_kernel(RefSet set, int n_refs, int ref_pitch, const int16_t* __restr
     const int qx = bx + (c & 4), qy = by + (r & 4);                      // this lane's 4x4 block inside the CTU
     const long e = (long)ctu * 256 + (qy >> 2) * 16 + (qx >> 2);
     int ri = ref_field ? (int)ref_field[e] : 0;
-    const bool live = cu_x + qx < pic_w && cu_y + qy < pic_h && ri < n_refs;
+    if (OUT == 1 && ri >= n_refs) ri = 0;   // every block of an origin is written; such an index reads reference 0
+    const bool live = OUT == 1 || (cu_x + qx < pic_w && cu_y + qy < pic_h && ri < n_refs);
     int mx = 0, my = 0;
     if (live) me_field_mv(mv_field, e, cu_x, cu_y, pic_w, pic_h, mx, my);
     else ri = 0;
@@ -2679,8 +2689,13 @@ me_predict4_kernel(RefSet set, int n_refs, int ref_pitch, const int16_t* __restr
       } else {
         v = me_tail_uni(sum, k);
       }
-      const int x = cu_x + bx + c, y = cu_y + by + r;
-      if (x < pic_w && y < pic_h) ((SrcT*)(dst + (long)y * dst_pitch))[x] = (SrcT)v;
+      if constexpr (OUT == 0) {
+        const int x = cu_x + bx + c, y = cu_y + by + r;
+        if (x < pic_w && y < pic_h) ((SrcT*)(dst + (long)y * dst_pitch))[x] = (SrcT)v;
+      } else {
+        const int cur = (int)((const SrcT*)org.cur_blocks)[(long)ctu * 4096 + (by + r) * 64 + bx + c];
+        ((uint16_t*)(dst + cy * org.ctu_y + cx * org.ctu_x + (long)(by + r) * dst_pitch))[bx + c] = (uint16_t)(2 * cur - v + org.bias);
+      }
     }
   }
 }
@@ -2838,7 +2853,9 @@ struct MeSelectOut {
 
 // The decision over the CTU's slots in LDS and the stores that follow it: what every select kernel ends in.  Outside kSelTable the MV cost
 // is inside the merged cost already -- against each reference's own predictor -- and is not priced a second time.
-template <MeSelectMode MODE, typename CostT>
+// FOUR (kSelDirs only): the caller is me_select_dirs_kernel<true>, whose a.per is 256 -- the direction stores of the 256 layout exist in
+// that instantiation alone, so that every other one keeps the instructions it had.
+template <MeSelectMode MODE, typename CostT, bool FOUR = false>
 __device__ __forceinline__ void me_select_decide_store(const MeSelect& params, const MeSelectSlots<CostT>& s, const MeSelectOut& out, const MeSelectWave& w,
                                                        uint32_t lambda_q16, int pred_x, int pred_y, int pic_w, int pic_h, int n_ctu) {
   constexpr bool REFS = MODE == kSelRefs, DIRS = MODE == kSelDirs || MODE == kSelDirsRefs, LREFS = MODE == kSelDirsRefs;
@@ -2858,9 +2875,10 @@ __device__ __forceinline__ void me_select_decide_store(const MeSelect& params, c
     const uint32_t m = s.mv[slot];
     return a.mv_unit ? (m << 2) & 0xfffcfffcu : m;
   };
-  if (a.per == 64) {
+  static_assert(!FOUR || MODE == kSelDirs, "several references per list: one MV per 8x8 block only");
+  if (!FOUR && a.per == 64) {
     const int slot = st.leaf_depth < 0 ? 0xffff : me_select_pu_slot_at(st.leaf_depth, st.leaf_ps, bx * 8, by * 8);
-    if constexpr (DIRS) {   // (one MV per 8x8 block only)
+    if constexpr (DIRS) {   // (one MV per 4x4 block: the kSelDirs branch further down)
       const long lists = (long)n_ctu * 64, e = 2 * w.pic * lists + w.ctu * 64 + lane;   // the block in list 0 of its picture; list 1: `lists` further
       const int d = slot == 0xffff ? 0 : (int)s.dir[slot];
       const int dir = d & 3, bl = d >> 2;
@@ -2893,8 +2911,28 @@ __device__ __forceinline__ void me_select_decide_store(const MeSelect& params, c
         mv[i] = slot[i] == 0xffff ? 0u : field_mv(slot[i]);
         if constexpr (REFS) ref[i] = slot[i] == 0xffff ? 0xffu : (uint32_t)s.ref[slot[i]];
       }
-      const long e = o * 256 + (2 * by + j) * 16 + 2 * bx;   // even: 8-byte (MVs) / 4-byte (slots) / 2-byte (references) aligned pairs
-      *(uint2*)(out.field + e) = make_uint2(mv[0], mv[1]);
+      const long e = o * 256 + (2 * by + j) * 16 + 2 * bx;   // even: 8-byte (MVs) / 4-byte (slots) / 2-byte (references, directions) aligned pairs
+      if constexpr (FOUR) {   // hmme_select_dirs4_device: the 64 branch above per 4x4 block, with the paired stores of REFS
+        const long lists = (long)n_ctu * 256, e0 = 2 * w.pic * lists + (long)w.ctu * 256 + (2 * by + j) * 16 + 2 * bx;   // the pair in list 0 of its picture
+        uint32_t f[2][2], dirs[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const int d = slot[i] == 0xffff ? 0 : (int)s.dir[slot[i]];
+          const int dir = d & 3, bl = d >> 2;
+          // the winner's list: the one a bi candidate searched, else the direction's; under direction 3 the other list holds the 4x4
+          // block's own entry of uni_field (a 4-byte aligned input: one dword per block), else (0,0)
+          const int wl = dir == 3 ? bl : dir - 1;
+          const uint32_t other = dir == 3 ? out.uni_field[e0 + i + (1 - bl) * lists] : 0u;
+          f[0][i] = wl == 0 ? mv[i] : other;
+          f[1][i] = wl == 1 ? mv[i] : other;
+          dirs[i] = dir ? (uint32_t)dir : 0xffu;
+        }
+        *(uint2*)(out.field + e0) = make_uint2(f[0][0], f[0][1]);
+        *(uint2*)(out.field + e0 + lists) = make_uint2(f[1][0], f[1][1]);
+        *(uint16_t*)(out.dir + e) = (uint16_t)(dirs[0] | dirs[1] << 8);
+      } else {
+        *(uint2*)(out.field + e) = make_uint2(mv[0], mv[1]);
+      }
       if constexpr (REFS) *(uint16_t*)(out.ref + e) = (uint16_t)(ref[0] | ref[1] << 8);
       if (out.slot) *(uint32_t*)(out.slot + e) = (uint32_t)slot[0] | (uint32_t)slot[1] << 16;
     }
@@ -2999,6 +3037,12 @@ struct MeDirRefsParams { MeDirRefsBits p[4]; };
 // is strictly cheaper (:3183-3186, :3226); bi wins on <= against both lists, list 0 on <= against list 1 (:3291, :3314).  This is the
 // sibling's merge at one reference per list, written out: as one body with it, it measured 15 % slower.
 // uni_field / out_field: int16 [n_pics][2][n_ctu][64][2] as dwords; out_dir uint8 [n_pics][n_ctu][64].
+//   FOUR = false: one MV per 8x8 block (hmme_select_dirs_device); the instructions it had before the parameter existed.
+//   FOUR = true:  one MV per 4x4 block (hmme_select_dirs4_device; a.per == 256, fields and directions [..][256]).  All 593 slots take part,
+//                 so TComDataCU::isBipredRestriction (TComDataCU.cpp:2892-2904, tested at TEncSearch.cpp:3109) applies: the 8x4 / 4x8 PUs of
+//                 an 8x8 CU -- depth 3, PartSize 1 or 2: slots 0..255 (me_slot_of<3>) -- form no bi candidate.  Their bi tables are not even
+//                 loaded, so what those entries hold cannot reach an output.
+template <bool FOUR>
 __global__ void __launch_bounds__(256)
 me_select_dirs_kernel(const uint32_t* __restrict__ mv_uni, const uint32_t* __restrict__ cost_uni, const uint32_t* __restrict__ mv_bi,
                       const uint32_t* __restrict__ cost_bi, const uint32_t* __restrict__ uni_field, const int16_t* __restrict__ pred_q,
@@ -3024,17 +3068,18 @@ me_select_dirs_kernel(const uint32_t* __restrict__ mv_uni, const uint32_t* __res
       if (i >= kParts) continue;
       uint32_t mu[2], mb[2], bu[2], bb[2];
       uint64_t cu[2], cb[2];
+      const bool may_bi = !FOUR || i >= 256;   // FOUR: isBipredRestriction for the slots of 8x4 / 4x8 PUs (wave-uniform: k < 4)
 #pragma unroll
       for (int l = 0; l < 2; ++l) {
         mu[l] = mv_uni[base[l] + i];
-        mb[l] = mv_bi[base[l] + i];
+        mb[l] = may_bi ? mv_bi[base[l] + i] : 0u;
         bu[l] = me_select_mv_bits(mu[l], px[l], py[l]);
         bb[l] = me_select_mv_bits(mb[l], px[l], py[l]);
       }
 #pragma unroll
       for (int l = 0; l < 2; ++l) {
         cu[l] = me_select_dist(lambda_q16, cost_uni[base[l] + i], bu[l]) + me_select_get_cost(lambda_q16, b.dir_bits[l] + b.list_bits[l] + bu[l]);
-        cb[l] = (me_select_dist(lambda_q16, cost_bi[base[l] + i], bb[l]) >> 1) +
+        cb[l] = (me_select_dist(lambda_q16, may_bi ? cost_bi[base[l] + i] : 0u, bb[l]) >> 1) +
                 me_select_get_cost(lambda_q16, b.dir_bits[2] + b.list_bits[0] + b.list_bits[1] + bb[l] + bu[1 - l]);
       }
       const int bl = cb[1] < cb[0] ? 1 : 0;   // strict: list 0 is tried first
@@ -3042,7 +3087,7 @@ me_select_dirs_kernel(const uint32_t* __restrict__ mv_uni, const uint32_t* __res
       uint64_t best;
       uint32_t m;
       int d;
-      if (cbi <= cu[0] && cbi <= cu[1]) { best = cbi; m = mb[bl]; d = 3 | bl << 2; }
+      if (may_bi && cbi <= cu[0] && cbi <= cu[1]) { best = cbi; m = mb[bl]; d = 3 | bl << 2; }
       else if (cu[0] <= cu[1]) { best = cu[0]; m = mu[0]; d = 1; }
       else { best = cu[1]; m = mu[1]; d = 2; }
       s_cost[w.wave][i] = best;
@@ -3052,8 +3097,8 @@ me_select_dirs_kernel(const uint32_t* __restrict__ mv_uni, const uint32_t* __res
   }
   __syncthreads();
   if (!w.live) return;
-  me_select_decide_store<kSelDirs, uint64_t>(a, {s_cost[w.wave], s_mv[w.wave], nullptr, s_dir[w.wave]}, {out_field, out_slot, out_cost, nullptr, out_dir, uni_field}, w,
-                                             lambda_q16, 0, 0, pic_w, pic_h, n_ctu);
+  me_select_decide_store<kSelDirs, uint64_t, FOUR>(a, {s_cost[w.wave], s_mv[w.wave], nullptr, s_dir[w.wave]}, {out_field, out_slot, out_cost, nullptr, out_dir, uni_field},
+                                                   w, lambda_q16, 0, 0, pic_w, pic_h, n_ctu);
 }
 
 // Up to eight references per list: me_select_dirs_kernel with a reference dimension behind the list -- uni / bi tables int16
@@ -3413,6 +3458,105 @@ me_predict_bi_kernel(const uint8_t* __restrict__ ref0, const uint8_t* __restrict
   }
 }
 
+// ---- L0, L1 or bi per 4x4 block (hmme_predict_bi4_device; the rule: include/hmme.h) -------------------------------------------------------
+// One list's pass of me_predict4_kernel for the wave's 8x8 block at CTU position (bx, by): its stage, horizontal and vertical steps with its
+// lanes, patches (11 x 11 per quadrant, pitch 12) and packed taps, on one plane.  live, mx, my are the LANE's -- those of its quadrant, equal
+// in the quadrant's 16 lanes -- and each quadrant is staged from its first lane.  Returns the vertical sum of lane (r, c) before any shift
+// (0 in a lane that is not live).  Two barriers, both outside every branch: stage | barrier | horizontal | barrier | vertical.
+template <typename SrcT>
+__device__ __forceinline__ int me_predict4_pass(bool live, const uint8_t* plane, int ref_pitch, int x0, int y0, int mx, int my, int16_t* wpatch, int16_t* wmid,
+                                                const uint32_t (*taps)[2], int lane, const MePredConst& k) {
+  const int r = lane >> 3, c = lane & 7, q = (r >> 2) * 2 + (c >> 2);
+  int info[4];   // scalars: 4 | horizontal phase of a live quadrant, else 0
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const int from = (s >> 1) * 32 + (s & 1) * 4;
+    const int s_live = __builtin_amdgcn_readlane((int)live, from), s_mx = __builtin_amdgcn_readlane(mx, from), s_my = __builtin_amdgcn_readlane(my, from);
+    info[s] = s_live ? 4 | (s_mx & 3) : 0;
+    if (s_live) {
+      const uint8_t* src = plane + (long)(y0 + (s >> 1) * 4 + (s_my >> 2) - 3) * ref_pitch + (long)(x0 + (s & 1) * 4 + (s_mx >> 2) - 3) * (long)sizeof(SrcT);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int el = lane + 64 * j, pr = el / 11, pc = el - pr * 11;
+        if (el < 121) wpatch[s * 132 + pr * 12 + pc] = (int16_t)((const SrcT*)(src + (long)pr * ref_pitch))[pc];
+      }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int o = lane + 64 * j, oq = o / 44, rem = o - oq * 44;   // output (row rem >> 2, column rem & 3) of quadrant oq
+    const int inf = oq == 0 ? info[0] : (oq == 1 ? info[1] : (oq == 2 ? info[2] : info[3]));
+    if (o < 176 && inf) {
+      const uint32_t lo = taps[inf & 3][0], hi = taps[inf & 3][1];
+      const int16_t* p = wpatch + oq * 132 + (rem >> 2) * 12 + (rem & 3);
+      int sum = 0;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) sum += (int)(int8_t)(lo >> (8 * t)) * (int)p[t] + (int)(int8_t)(hi >> (8 * t)) * (int)p[t + 4];
+      wmid[o] = (int16_t)((sum + k.off1) >> k.sh1);
+    }
+  }
+  __syncthreads();
+  int sum = 0;
+  if (live) {
+    const uint32_t lo = taps[my & 3][0], hi = taps[my & 3][1];
+    const int16_t* p = wmid + q * 44 + (r & 3) * 4 + (c & 3);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) sum += (int)(int8_t)(lo >> (8 * t)) * (int)p[4 * t] + (int)(int8_t)(hi >> (8 * t)) * (int)p[4 * (t + 4)];
+  }
+  return sum;
+}
+
+// me_predict_bi_kernel<SrcT> with HM's own motion storage: mv_field int16 [2][n_ctu][256][2] (list-major), dir_field uint8 [n_ctu][256], entry b
+// the 4x4 block at ((b & 15) * 4, (b >> 4) * 4) of the CTU.  Lanes, patches and taps are me_predict4_kernel's; list 0 and then list 1 go
+// through the same wave-private LDS (me_predict4_pass twice: FOUR barriers per iteration, as me_predict_bi_kernel has).  Direction and both
+// MVs are per QUADRANT, read from the quadrant's first lane: a quadrant is live if its 4x4 block starts inside the picture and its direction
+// is 1, 2 or 3; in a list its direction does not name it stages nothing.  Tail per lane: me_tail_avg when both lists are used, else
+// me_tail_uni -- the sample me_predict_bi_kernel writes when the 8x8 block carries the quadrant's (direction, MV0, MV1).
+// BARRIER INVARIANT (me_predict4_kernel's): __syncthreads() is a barrier of the whole workgroup.  Every wave and every 16-lane group -- live,
+// partly live or wholly dead -- runs all 16 iterations and meets the same four barriers in each.  Everything that depends on the field
+// (direction, liveness, phase) sits INSIDE a stage of me_predict4_pass; no barrier is ever inside a branch, and no wave leaves the loop early.
+template <typename SrcT>
+__global__ void __launch_bounds__(256)
+me_predict_bi4_kernel(const uint8_t* __restrict__ ref0, const uint8_t* __restrict__ ref1, int ref_pitch, const int16_t* __restrict__ mv_field,
+                      const uint8_t* __restrict__ dir_field, int n_ctu, int ctu_first, int pic_w, int pic_h, int bit_depth, uint8_t* __restrict__ dst,
+                      int dst_pitch) {
+  __shared__ int16_t patch[4][4 * 11 * 12];
+  __shared__ int16_t mid[4][4 * 11 * 4];
+  __shared__ uint32_t taps[4][2];   // kLumaTaps, tap j of a phase = signed byte j of the pair; read behind the first barrier
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (threadIdx.x < 8) {
+    uint32_t p = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) p |= (uint32_t)(uint8_t)kLumaTaps[threadIdx.x >> 1][4 * (threadIdx.x & 1) + j] << (8 * j);
+    taps[threadIdx.x >> 1][threadIdx.x & 1] = p;
+  }
+  const int ctus_x = (pic_w + 63) >> 6;
+  const int ctu = ctu_first + blockIdx.x;
+  const int cx = ctu % ctus_x, cy = ctu / ctus_x, cu_x = cx * 64, cu_y = cy * 64;
+  const MePredConst k(bit_depth);
+  const int r = lane >> 3, c = lane & 7;
+#pragma unroll 1
+  for (int it = 0; it < 16; ++it) {
+    const int b = it * 4 + wave, bx = (b & 7) * 8, by = (b >> 3) * 8;   // the four waves: four 8x8 blocks side by side
+    const int qx = bx + (c & 4), qy = by + (r & 4);                      // this lane's 4x4 block inside the CTU
+    const long e = (long)ctu * 256 + (qy >> 2) * 16 + (qx >> 2);
+    const int dir = dir_field[e];
+    const bool live = cu_x + qx < pic_w && cu_y + qy < pic_h && dir >= 1 && dir <= 3;
+    const bool use0 = live && (dir & 1), use1 = live && (dir & 2);
+    int mx0 = 0, my0 = 0, mx1 = 0, my1 = 0;
+    if (use0) me_field_mv(mv_field, e, cu_x, cu_y, pic_w, pic_h, mx0, my0);
+    if (use1) me_field_mv(mv_field, (long)n_ctu * 256 + e, cu_x, cu_y, pic_w, pic_h, mx1, my1);
+    const int sum0 = me_predict4_pass<SrcT>(use0, ref0, ref_pitch, cu_x + bx, cu_y + by, mx0, my0, patch[wave], mid[wave], taps, lane, k);
+    const int sum1 = me_predict4_pass<SrcT>(use1, ref1, ref_pitch, cu_x + bx, cu_y + by, mx1, my1, patch[wave], mid[wave], taps, lane, k);
+    if (live) {
+      const int v = use0 && use1 ? me_tail_avg(sum0, sum1, k) : me_tail_uni(use0 ? sum0 : sum1, k);
+      const int x = cu_x + bx + c, y = cu_y + by + r;
+      if (x < pic_w && y < pic_h) ((SrcT*)(dst + (long)y * dst_pitch))[x] = (SrcT)v;
+    }
+  }
+}
+
 // ---- 4:2:0 chroma motion compensation from the luma motion fields (hmme_predict_chroma_*_device) -------------------------------------------
 // TComPrediction::xPredInterBlk for a chroma component of a 4:2:0 picture (TComPrediction.cpp:669-707): the quarter-pel LUMA MV, clamped like
 // clip_mv_q with the luma picture size and the CTU's luma position, is an eighth-pel chroma MV: integer offset mv >> 3 (arithmetic), phase
@@ -3664,6 +3808,97 @@ me_predict_chroma4_kernel(MeChromaSrc src, int ref_pitch, const int16_t* __restr
       } else {
         v = me_tail_uni(sum, k);
       }
+      const int x = x0 + c, y = y0 + r;
+      if (x < (pic_w >> 1) && y < (pic_h >> 1)) ((SrcT*)(dst + (long)y * dst_pitch))[x] = (SrcT)v;
+    }
+  }
+}
+
+// One list's pass of me_predict_chroma4_kernel for a 16-lane group: the 4x4 block of one component (one 8x8 luma block) at chroma position
+// (x0, y0) as four 2x2 quads, on one plane.  live, mx, my are the LANE's -- those of its quad -- and each quad is staged from its first lane.
+// Returns the vertical sum of lane (r, c) before any shift (0 in a lane that is not live).  Two barriers, both outside every branch.
+template <typename SrcT>
+__device__ __forceinline__ int me_predict_chroma4_pass(bool live, const uint8_t* plane, int ref_pitch, int x0, int y0, int mx, int my, int16_t* gpatch,
+                                                       int16_t* gmid, const uint32_t* taps, int lane, const MePredConst& k) {
+  const int l16 = lane & 15, r = l16 >> 2, c = l16 & 3, q = (r >> 1) * 2 + (c >> 1);
+  int info[4];   // per group: 8 | horizontal phase of a live quad, else 0
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const int from = (lane & 48) + (s >> 1) * 8 + (s & 1) * 2;
+    const int s_live = __shfl((int)live, from), s_mx = __shfl(mx, from), s_my = __shfl(my, from);
+    info[s] = s_live ? 8 | (s_mx & 7) : 0;
+    if (s_live) {
+      const uint8_t* p = plane + (long)(y0 + (s >> 1) * 2 + (s_my >> 3) - 1) * ref_pitch + (long)(x0 + (s & 1) * 2 + (s_mx >> 3) - 1) * (long)sizeof(SrcT);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int el = l16 + 16 * j, pr = el / 5, pc = el - pr * 5;
+        if (el < 25) gpatch[s * 25 + el] = (int16_t)((const SrcT*)(p + (long)pr * ref_pitch))[pc];
+      }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int o = l16 + 16 * j, oq = o / 10, rem = o - oq * 10;   // output (row rem >> 1, column rem & 1) of quad oq
+    const int inf = oq == 0 ? info[0] : (oq == 1 ? info[1] : (oq == 2 ? info[2] : info[3]));
+    if (o < 40 && inf) {
+      const uint32_t th = taps[inf & 7];
+      const int16_t* p = gpatch + oq * 25 + (rem >> 1) * 5 + (rem & 1);
+      int sum = 0;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) sum += (int)(int8_t)(th >> (8 * t)) * (int)p[t];
+      gmid[o] = (int16_t)((sum + k.off1) >> k.sh1);
+    }
+  }
+  __syncthreads();
+  int sum = 0;
+  if (live) {
+    const uint32_t tv = taps[my & 7];
+    const int16_t* p = gmid + q * 10 + (r & 1) * 2 + (c & 1);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) sum += (int)(int8_t)(tv >> (8 * t)) * (int)p[2 * t];
+  }
+  return sum;
+}
+
+// me_predict_chroma4_kernel's sibling for a direction per 4x4 luma block (hmme_predict_chroma_bi4_device): FORM 2 of me_predict_chroma_kernel
+// from the 256 layout, unweighted.  mv_field int16 [2][n_ctu][256][2], src.field = dir_field uint8 [n_ctu][256], src.set.base[0..1] list 0's
+// Cb / Cr, [2..3] list 1's.  Groups, lanes, quads and patches are me_predict_chroma4_kernel's; list 0 and then list 1 go through the group's
+// LDS (me_predict_chroma4_pass twice: FOUR barriers per iteration).  A quad is live if its 4x4 luma block starts inside the luma picture and
+// its direction is 1, 2 or 3.  Tail per lane: me_tail_avg when both lists are used, else me_tail_uni.
+// BARRIER INVARIANT (me_predict4_kernel's): every group of every wave runs all eight iterations and meets the same four barriers in each,
+// whatever the field holds; no barrier is inside a branch, and no wave leaves the loop early.
+template <typename SrcT>
+__global__ void __launch_bounds__(256)
+me_predict_chroma_bi4_kernel(MeChromaSrc src, int ref_pitch, const int16_t* __restrict__ mv_field, int ctu_first, int pic_w, int pic_h, int bit_depth,
+                             uint8_t* __restrict__ dst_cb, uint8_t* __restrict__ dst_cr, int dst_pitch) {
+  __shared__ int16_t patch[16][4 * 25];
+  __shared__ int16_t mid[16][4 * 10];
+  __shared__ uint32_t taps[8];
+  const int group = threadIdx.x >> 4, l16 = threadIdx.x & 15, comp = group & 1, lane = threadIdx.x & 63;
+  if (threadIdx.x < 8) taps[threadIdx.x] = kChromaTaps[threadIdx.x];   // read behind the first barrier
+  const int ctus_x = (pic_w + 63) >> 6;
+  const int ctu = ctu_first + blockIdx.x;
+  const int cx = ctu % ctus_x, cy = ctu / ctus_x, cu_x = cx * 64, cu_y = cy * 64;
+  const MePredConst k(bit_depth);
+  uint8_t* const dst = comp ? dst_cr : dst_cb;
+  const int r = l16 >> 2, c = l16 & 3;
+#pragma unroll 1
+  for (int it = 0; it < 8; ++it) {
+    const int bx = (group >> 1) * 8, by = it * 8;                        // the group's 8x8 luma block: a block row per iteration
+    const int qx = bx + (c >> 1) * 4, qy = by + (r >> 1) * 4;           // this lane's 4x4 luma block inside the CTU
+    const long e = (long)ctu * 256 + (qy >> 2) * 16 + (qx >> 2);
+    const int x0 = (cu_x + bx) >> 1, y0 = (cu_y + by) >> 1;
+    const int dir = src.field[e];
+    const bool live = cu_x + qx < pic_w && cu_y + qy < pic_h && dir >= 1 && dir <= 3;
+    const bool use0 = live && (dir & 1), use1 = live && (dir & 2);
+    int mx0 = 0, my0 = 0, mx1 = 0, my1 = 0;
+    if (use0) me_field_mv(mv_field, e, cu_x, cu_y, pic_w, pic_h, mx0, my0);
+    if (use1) me_field_mv(mv_field, (long)src.n_ctu * 256 + e, cu_x, cu_y, pic_w, pic_h, mx1, my1);
+    const int sum0 = me_predict_chroma4_pass<SrcT>(use0, src.set.base[comp], ref_pitch, x0, y0, mx0, my0, patch[group], mid[group], taps, lane, k);
+    const int sum1 = me_predict_chroma4_pass<SrcT>(use1, src.set.base[2 + comp], ref_pitch, x0, y0, mx1, my1, patch[group], mid[group], taps, lane, k);
+    if (live) {
+      const int v = use0 && use1 ? me_tail_avg(sum0, sum1, k) : me_tail_uni(use0 ? sum0 : sum1, k);
       const int x = x0 + c, y = y0 + r;
       if (x < (pic_w >> 1) && y < (pic_h >> 1)) ((SrcT*)(dst + (long)y * dst_pitch))[x] = (SrcT)v;
     }

@@ -44,7 +44,10 @@ SYMBOLS = ["hmme_create", "hmme_destroy", "hmme_last_error", "hmme_device_info",
            "hmme_bipred_refs_weight_check", "hmme_search_frame_bi_refs_w_device", "hmme_refine_frame_bi_refs_w_device", "hmme_search_frame_bi_refs_w",
            "hmme_refine_frame_bi_refs_w",
            "hmme_predict_bi_refs_weight_check", "hmme_predict_bi_refs_w_device", "hmme_predict_bi_refs_w_frame",
-           "hmme_predict_chroma_bi_refs_device", "hmme_predict_chroma_bi_refs_frame"]
+           "hmme_predict_chroma_bi_refs_device", "hmme_predict_chroma_bi_refs_frame",
+           "hmme_search_pairs_bi4_device", "hmme_refine_pairs_bi4_device", "hmme_search_frame_bi4", "hmme_refine_frame_bi4",
+           "hmme_select_dirs4_check", "hmme_select_dirs4_device", "hmme_select_dirs4_frame",
+           "hmme_predict_bi4_device", "hmme_predict_bi4_frame", "hmme_predict_chroma_bi4_device", "hmme_predict_chroma_bi4_frame"]
 # test / measurement entry points (include/hmme_test.h): not part of the boundary
 TEST_SYMBOLS = ["hmme_test_time_search_kernel", "hmme_test_device_address", "hmme_test_frac_deal", "hmme_test_tail_plan", "hmme_test_stage_layout", "hmme_test_picture_job", "hmme_test_time_weight_passes", "hmme_test_time_bipred_origin",
                 "hmme_test_time_wp_estimate_passes", "hmme_test_pk_gate", "hmme_test_pk_body", "hmme_test_pk_task_marker_free", "hmme_test_pk_task_full",
@@ -235,6 +238,18 @@ def load():
     L.hmme_predict_refs4_frame.argtypes = [vp, C.POINTER(vp), i, C.POINTER(FrameParams), pw, vp, vp, vp, i]
     L.hmme_predict_chroma_refs4_device.argtypes = [vp, C.POINTER(vp), i, i, i, C.POINTER(FrameParams), pw, vp, vp, vp, vp, i, vp]
     L.hmme_predict_chroma_refs4_frame.argtypes = [vp, C.POINTER(vp), i, i, i, C.POINTER(FrameParams), pw, vp, vp, C.POINTER(vp), i]
+    # B pictures from one MV per 4x4 block: the bi, dirs and predict_bi signatures without mv_per_ctu (chroma: without weights, too)
+    L.hmme_search_pairs_bi4_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, C.POINTER(FrameParams), vp, vp, vp, vp, vp, vp]
+    L.hmme_refine_pairs_bi4_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i, C.POINTER(FrameParams), vp, vp, vp, vp, i, vp, vp, vp]
+    L.hmme_search_frame_bi4.argtypes = [vp, vp, vp, vp, C.POINTER(FrameParams), vp, vp, vp, vp, vp]
+    L.hmme_refine_frame_bi4.argtypes = [vp, vp, vp, vp, C.POINTER(FrameParams), vp, vp, vp, vp, i, vp, vp]
+    L.hmme_select_dirs4_check.argtypes = [C.POINTER(SelectParams), i, C.POINTER(DirParams)]
+    L.hmme_select_dirs4_device.argtypes = [vp, i, i, i, C.POINTER(FrameParams), C.POINTER(SelectParams), C.POINTER(DirParams)] + [vp] * 11
+    L.hmme_select_dirs4_frame.argtypes = [vp, i, i, C.POINTER(FrameParams), C.POINTER(SelectParams), C.POINTER(DirParams)] + [vp] * 10
+    L.hmme_predict_bi4_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, C.POINTER(FrameParams), vp, vp, C.POINTER(vp), i, vp]
+    L.hmme_predict_bi4_frame.argtypes = [vp, vp, vp, C.POINTER(FrameParams), vp, vp, vp, i]
+    L.hmme_predict_chroma_bi4_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, i, i, C.POINTER(FrameParams), vp, vp, C.POINTER(vp), i, vp]
+    L.hmme_predict_chroma_bi4_frame.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, i, C.POINTER(FrameParams), vp, vp, C.POINTER(vp), i]
     L.hmme_predict_chroma_bi_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, i, i, C.POINTER(FrameParams), pw, pw, vp, vp, i, C.POINTER(vp), i, vp]
     L.hmme_predict_chroma_bi_frame.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, i, C.POINTER(FrameParams), pw, pw, vp, vp, i, C.POINTER(vp), i]
     L.hmme_residual_pairs_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i, i, C.POINTER(FrameParams), vp, i, i, C.POINTER(vp), i, vp, vp, vp, vp]
@@ -1111,6 +1126,99 @@ class Engine:
                                                         oa, cb.shape[1]))
         return cb, cr
 
+    # ---- B pictures from one MV per 4x4 block (include/hmme.h, "B pictures from one MV per 4x4 block"): the bi pass, the decision and the
+    # prediction on the 256 layout, one reference per list, unweighted
+    def search_pairs_bi4_device(self, curs, refs, others, fp, d_other_mv, d_center, d_pred, d_mv, d_sad, stream=0):
+        """hmme_search_pairs_bi4_device: search_pairs_bi_device against origins built from d_other_mv int16[n_pairs, n_ctu, 256, 2]"""
+        assert len(curs) == len(refs) == len(others)
+        self._check(self.L.hmme_search_pairs_bi4_device(self.h, _handles(curs), _handles(refs), _handles(others), len(refs), C.byref(fp), d_other_mv, d_center, d_pred,
+                                                        d_mv, d_sad, stream))
+
+    def refine_pairs_bi4_device(self, curs, refs, others, fp, d_other_mv, d_center, d_pred, d_int_mv, use_hadamard, d_qmv, d_cost, stream=0):
+        """hmme_refine_pairs_bi4_device: refine_pairs_bi_device against origins built from d_other_mv int16[n_pairs, n_ctu, 256, 2]"""
+        assert len(curs) == len(refs) == len(others)
+        self._check(self.L.hmme_refine_pairs_bi4_device(self.h, _handles(curs), _handles(refs), _handles(others), len(refs), C.byref(fp), d_other_mv, d_center, d_pred,
+                                                        d_int_mv, int(use_hadamard), d_qmv, d_cost, stream))
+
+    def _frame_bi4(self, entry, cur, ref, other, sr, fen, other_mv, int_mv, center_q, pred_q, use_hadamard, ctu_first, ctu_count):
+        """the two *_frame_bi4 methods (_frame_bi on the 256 layout); int_mv: None for a search -> the two result tables"""
+        n = self.L.hmme_num_ctus(cur.width, cur.height)
+        count = n - ctu_first if ctu_count < 0 else ctu_count
+        fp = FrameParams(sr, int(fen), cur.bit_depth, ctu_first, count)
+        f, _, _ = self._field4(cur.width, cur.height, other_mv, None)
+        cq, cptr = self._pq(center_q, n)
+        pq, pptr = self._pq(pred_q, n)
+        args = [f.ctypes.data, cptr, pptr]
+        if int_mv is not None:
+            int_mv = np.ascontiguousarray(int_mv, dtype=np.int16)
+            assert int_mv.shape == (count, NUM_PARTS, 2)
+            args += [int_mv.ctypes.data, int(use_hadamard)]
+        mv = np.zeros((count, NUM_PARTS, 2), np.int16)
+        cost = np.zeros((count, NUM_PARTS), np.uint32)
+        self._check(entry(self.h, cur.h, ref.h, other.h, C.byref(fp), *args, mv.ctypes.data, cost.ctypes.data))
+        return mv, cost
+
+    def search_frame_bi4(self, cur, ref, other, sr, other_mv, center_q=None, pred_q=None, fen=1, ctu_first=0, ctu_count=-1):
+        """hmme_search_frame_bi4: search_frame_bi with other_mv int16[n_ctu, 256, 2], one MV per 4x4 block -> (mv int16[count,593,2], sad uint32[count,593])"""
+        return self._frame_bi4(self.L.hmme_search_frame_bi4, cur, ref, other, sr, fen, other_mv, None, center_q, pred_q, True, ctu_first, ctu_count)
+
+    def refine_frame_bi4(self, cur, ref, other, sr, other_mv, int_mv, center_q=None, pred_q=None, use_hadamard=True, ctu_first=0, ctu_count=-1):
+        """hmme_refine_frame_bi4: refine_frame_bi with other_mv int16[n_ctu, 256, 2] -> (qmv int16[count,593,2], cost uint32[count,593])"""
+        return self._frame_bi4(self.L.hmme_refine_frame_bi4, cur, ref, other, sr, 1, other_mv, int_mv, center_q, pred_q, use_hadamard, ctu_first, ctu_count)
+
+    def select_dirs4_device(self, width, height, n_pics, fp, sel, dirs, d_mv_uni, d_cost_uni, d_mv_bi, d_cost_bi, d_uni_field, d_pred, d_field, d_dir,
+                            d_slot=None, d_ctu_cost=None, stream=0):
+        """hmme_select_dirs4_device: select_dirs_device over all 593 slots (sel.mv_per_ctu == 256; 8x4 / 4x8 PUs never bi): uni fields and motion
+        field int16[n_pics, 2, n_ctu, 256, 2], directions uint8[n_pics, n_ctu, 256], covering slots uint16 of that shape"""
+        self._check(self.L.hmme_select_dirs4_device(self.h, int(width), int(height), int(n_pics), C.byref(fp), C.byref(sel), _dir_params(dirs, n_pics),
+                                                    d_mv_uni, d_cost_uni, d_mv_bi, d_cost_bi, d_uni_field, d_pred, d_field, d_dir, d_slot, d_ctu_cost, stream))
+
+    def select_dirs4_frame(self, width, height, sel, dir_params, mv_uni, cost_uni, mv_bi, cost_bi, uni_field, pred_q=None, ctu_first=0, ctu_count=-1,
+                           field=None, dirs=None, slot=None, ctu_cost=None):
+        """hmme_select_dirs4_frame: select_dirs_frame on the 256 layout: uni_field int16[2, n_ctu, 256, 2] -> (field int16[2, n_ctu, 256, 2], dirs
+        uint8[n_ctu, 256], slot uint16[n_ctu, 256], ctu_cost uint32[n_ctu])"""
+        call = lambda fp, *a: self.L.hmme_select_dirs4_frame(self.h, int(width), int(height), C.byref(fp), C.byref(sel), C.byref(dir_params), *a)
+        return self._select_frame(call, (2,), width, height, (mv_uni, cost_uni, mv_bi, cost_bi), ((uni_field, np.int16, (2,), (256, 2)),), pred_q, ctu_first, ctu_count,
+                                  ((field, np.int16, (2,), (256, 2)), (dirs, np.uint8, (), (256,)), (slot, np.uint16, (), (256,)), (ctu_cost, np.uint32, (), ())))
+
+    def _fields_bi4(self, width, height, mv_field, dir_field):
+        """host fields of a B picture on the 256 layout: int16[2, n_ctu, 256, 2] and uint8[n_ctu, 256] -> contiguous arrays"""
+        n = self.L.hmme_num_ctus(int(width), int(height))
+        f = np.ascontiguousarray(mv_field, dtype=np.int16)
+        df = np.ascontiguousarray(dir_field, dtype=np.uint8)
+        assert f.shape == (2, n, 256, 2) and df.shape == (n, 256)
+        return f, df
+
+    def predict_bi4_device(self, refs0, refs1, fp, d_mv_field, d_dir_field, d_outs, out_pitch_bytes, stream=0):
+        """hmme_predict_bi4_device: predict_bi_device from d_mv_field int16[n_pics, 2, n_ctu, 256, 2] and d_dir_field uint8[n_pics, n_ctu, 256]"""
+        assert len(refs0) == len(refs1) == len(d_outs)
+        self._check(self.L.hmme_predict_bi4_device(self.h, _handles(refs0), _handles(refs1), len(refs0), C.byref(fp), d_mv_field, d_dir_field, self._ptrs(d_outs),
+                                                   int(out_pitch_bytes), stream))
+
+    def predict_bi4_frame(self, ref0, ref1, mv_field, dir_field, out=None, ctu_first=0, ctu_count=-1):
+        """hmme_predict_bi4_frame: predict_bi_frame from one (direction, MV0, MV1) per 4x4 block: mv_field int16[2, n_ctu, 256, 2], dir_field
+        uint8[n_ctu, 256] -> [height, width]; `out` keeps its samples outside the CTU range and in blocks without a direction"""
+        f, df = self._fields_bi4(ref0.width, ref0.height, mv_field, dir_field)
+        out = self._image(ref0, out)
+        fp = FrameParams(1, 0, ref0.bit_depth, ctu_first, ctu_count)
+        self._check(self.L.hmme_predict_bi4_frame(self.h, ref0.h, ref1.h, C.byref(fp), f.ctypes.data, df.ctypes.data, out.ctypes.data, out.shape[1]))
+        return out
+
+    def predict_chroma_bi4_device(self, refs0, refs1, width, height, fp, d_mv_field, d_dir_field, d_outs, out_pitch_bytes, stream=0):
+        """hmme_predict_chroma_bi4_device: predict_chroma_bi_device (no weights) from the fields of the 256 layout; refs0 / refs1 = [cb0, cr0, ...]"""
+        assert len(refs0) == len(refs1) == len(d_outs) and len(refs0) % 2 == 0
+        self._check(self.L.hmme_predict_chroma_bi4_device(self.h, _handles(refs0), _handles(refs1), len(refs0) // 2, int(width), int(height), C.byref(fp), d_mv_field,
+                                                          d_dir_field, self._ptrs(d_outs), int(out_pitch_bytes), stream))
+
+    def predict_chroma_bi4_frame(self, ref0, ref1, width, height, mv_field, dir_field, outs=None, ctu_first=0, ctu_count=-1):
+        """hmme_predict_chroma_bi4_frame: predict_bi4_frame for Cb and Cr; ref0 / ref1 = (cb, cr) of list 0 / list 1 -> (cb, cr)"""
+        f, df = self._fields_bi4(width, height, mv_field, dir_field)
+        cb, cr, oa = self._chroma_images(ref0[0], outs)
+        fp = FrameParams(1, 0, ref0[0].bit_depth, ctu_first, ctu_count)
+        self._check(self.L.hmme_predict_chroma_bi4_frame(self.h, _handles(ref0), _handles(ref1), int(width), int(height), C.byref(fp), f.ctypes.data, df.ctypes.data,
+                                                         oa, cb.shape[1]))
+        return cb, cr
+
     # ---- multi-reference B pictures with explicit weights and in 4:2:0 (include/hmme.h, "multi-reference B pictures: explicit weights and
     # 4:2:0 chroma"): one (w0, offset, shift, round) per reference of each list; chroma: per plane, (Cb, Cr) per reference, or None
     def search_frame_bi_refs_w_device(self, cur, refs, others, fp, weights, other_weights, d_other_mv, d_other_ref, mv_per_ctu, d_center, d_pred, d_mv, d_sad, stream=0):
@@ -1349,6 +1457,16 @@ def select_dirs_check(sel, n_pics, dirs):
         for k, d in enumerate(dirs):
             a[k] = d
     return int(load().hmme_select_dirs_check(C.byref(sel), int(n_pics), a))
+
+
+def select_dirs4_check(sel, n_pics, dirs):
+    """hmme_select_dirs4_check: select_dirs_check for the 256 layout: mv_per_ctu 256, mv_unit 0, price_mv 0 only"""
+    a = None
+    if dirs is not None:
+        a = (DirParams * max(len(dirs), 4))()
+        for k, d in enumerate(dirs):
+            a[k] = d
+    return int(load().hmme_select_dirs4_check(C.byref(sel), int(n_pics), a))
 
 
 def _dir_refs_params(dirs, n_pics):

@@ -1057,8 +1057,8 @@ int hmme_predict_chroma_bi_refs_frame(hmme_ctx* ctx, const hmme_plane* const* re
  * field, host reference field or NULL, host image(s) with out_stride in samples (chroma: outs = {Cb, Cr} of the chroma size); every sample
  * that is not written comes back as it was.
  *
- * Not in this family: the bi / direction forms at 4x4 (hmme_select_dirs_* requires mv_per_ctu = 64; at 4x4 it would first need HM's
- * isBipredRestriction for 8x4 / 4x8 PUs), the bi-pass origin from a 4x4 field, and 4:2:2 / 4:4:4 chroma. */
+ * Not in this family: 4:2:2 / 4:4:4 chroma.  The bi / direction forms at 4x4 and the bi-pass origin from a 4x4 field: "B pictures from one
+ * MV per 4x4 block" below. */
 int hmme_predict_refs4_device(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, const hmme_frame_params* fp,
                               const hmme_weight* wps /* n_refs HOST weights, or NULL */, const void* d_mv_field /* int16[n_ctu][256][2] */,
                               const void* d_ref_field /* uint8[n_ctu][256], or NULL: every block index 0 */, void* d_out, int out_pitch_bytes, void* stream);
@@ -1069,6 +1069,85 @@ int hmme_predict_chroma_refs4_device(hmme_ctx* ctx, const hmme_plane* const* ref
                                      const void* d_mv_field, const void* d_ref_field, void* d_out_cb, void* d_out_cr, int out_pitch_bytes, void* stream);
 int hmme_predict_chroma_refs4_frame(hmme_ctx* ctx, const hmme_plane* const* refs, int n_refs, int width, int height, const hmme_frame_params* fp,
                                     const hmme_weight* wps, const int16_t* mv_field, const uint8_t* ref_field, void* const* outs, int out_stride);
+
+/* ---- B pictures from one MV per 4x4 block: bi pass, decision, prediction ("bi4") ----------------------------------------------
+ * What the refs4 family above is for a P picture, for a B picture with ONE reference per list, unweighted, Y plus the Cb / Cr of 4:2:0: the
+ * bi pass against an origin built from a 4x4 field, the L0 / L1 / bi decision over all 593 slots, and the prediction from its output.  The
+ * chain: hmme_refine_pairs_device (both lists) -> hmme_select_pairs_device at mv_per_ctu = 256 per list -> hmme_refine_pairs_bi4_device per
+ * list -> hmme_select_dirs4_device -> hmme_predict_bi4_device + hmme_predict_chroma_bi4_device -> hmme_residual_pairs_device at 256.  New
+ * entry points only; no struct and no existing entry point changed (hmme_select_dirs_*, the *_bi_* calls and hmme_predict_*bi_* still refuse
+ * 256 MVs per CTU), so HMME_ABI_VERSION stays 6.  THIS TEXT PLUS THE CITATIONS IS THE RULE (paths below source/Lib of the reference).
+ *
+ * Fields.  As in the refs4 family there is no mv_per_ctu argument: the family IS the 256 layout.  Entry b of a CTU is the 4x4 luma block at
+ * ((b & 15) * 4, (b >> 4) * 4); n_ctu counts all CTUs of the picture.
+ *
+ * 1. The bi pass.  hmme_search_pairs_bi4_device, hmme_refine_pairs_bi4_device, hmme_search_frame_bi4, hmme_refine_frame_bi4 are
+ * hmme_search_pairs_bi_device, hmme_refine_pairs_bi_device, hmme_search_frame_bi, hmme_refine_frame_bi with d_other_mv
+ * int16[n_pairs][n_ctu][256][2].  Everything is as in those calls except how the other list's prediction P inside the origin O = 2 B - P is
+ * formed: every 4x4 block of the CTU's 64x64 block -- those beyond the picture edge included, as the 64 form does with its 8x8 blocks -- is
+ * compensated from others[i] at its own entry, clamped with the CTU's clipMv; sample for sample what the 64 form puts there when the
+ * surrounding 8x8 block carries that entry.  The results are, per CTU, what hmme_search_ctu / hmme_refine_ctu return on that origin; with a
+ * field whose four entries per 8x8 block agree the tables are bit for bit those of the 64 form.  Refusals: hmme_bipred_check's and those of
+ * the 64 form, in their order; hmme_last_error names the entry called.
+ *
+ * 2. The decision.  hmme_select_dirs4_check / _device / _frame have the signatures of hmme_select_dirs_*, and the rule of
+ * hmme_select_dirs_device (its inputs, definitions, steps 1-5 and outputs above) holds word for word with three differences:
+ *   a. Layouts.  sel->mv_per_ctu == 256 (mv_unit == 0 and price_mv == 0 as before).  d_uni_field and d_out_field are
+ *      int16[n_pics][2][n_ctu][256][2], d_out_dir uint8[n_pics][n_ctu][256], d_out_slot uint16[n_pics][n_ctu][256].  All 593 slots take part,
+ *      as in hmme_select_pairs_device at 256.
+ *   b. Bi restriction: TComDataCU::isBipredRestriction (TLibCommon/TComDataCU.cpp:2892-2904), tested at TLibEncoder/TEncSearch.cpp:3109.  A
+ *      slot whose hmme_slot_key has depth 3 and part_size 1 or 2 -- an 8x4 or 4x8 PU -- forms no bi candidate: steps 2 and 3 are not
+ *      carried out for it, what mv_bi / cost_bi hold at that slot influences no output, and step 4 reduces to C[0] <= C[1]: direction 1,
+ *      otherwise direction 2.  Every other slot, the AMP slots of a 16x16 CU included, decides as before.
+ *   c. Other-list entry.  Under a direction-3 slot the other list's entry of a block is that 4x4 BLOCK'S OWN ENTRY of d_uni_field[1-l].
+ * Buffers: tables, costs, the input field and slots 4-byte aligned, the output field 8-byte, the directions 2-byte (a lane stores pairs, as
+ * out.ref at 256).  hmme_select_dirs4_check is hmme_select_dirs_check with 256 in place of 64.
+ *
+ * 3. The prediction.  hmme_predict_bi4_device / _frame are hmme_predict_bi_device / _frame without mv_per_ctu: d_mv_field
+ * int16[n_pics][2][n_ctu][256][2], d_dir_field uint8[n_pics][n_ctu][256].  A 4x4 block is live if it starts inside the picture and its
+ * direction is 1, 2 or 3; a block that is not live reads no plane and writes nothing.  Every sample of a live block is what
+ * hmme_predict_bi_device writes for it when the 8x8 block around it carries this block's (direction, MV0, MV1) -- which, by the
+ * separability argument of the refs4 family, is xPredInterBlk + TComYuv::addAvg for a 16x4 / 4x16 / 12x16 / 16x12 PU.  The margins hold:
+ * the 11 x 11 patch is a subset of the 15 x 15 one.
+ * hmme_predict_chroma_bi4_device / _frame are hmme_predict_chroma_bi_device / _frame without mv_per_ctu AND WITHOUT WEIGHTS.  A 4x4 luma
+ * block is a 2x2 block per component; sample for sample the output is what hmme_predict_chroma_bi_device (NULL weights) writes when the 8x8
+ * luma block carries the entry.  Sizes as in the existing chroma calls: an even luma size of at least 16 x 16.
+ * Refusals -- codes and order -- are those of the 64 forms; hmme_last_error names the entry called.
+ *
+ * Every refusal of the entries of this family names the entry in hmme_last_error -- also those of the checks all families share (the CTU
+ * range, a plane of another context, a NULL table), whose messages the 64 forms give bare.
+ *
+ * Not part of this family: explicit weights (_bi4_w), several references per list (hmme_select_dirs_refs_* at 4x4), 4:2:2 / 4:4:4, and the
+ * plumbing into the sequence driver (hmme/sequence.py, run_rank). */
+int hmme_search_pairs_bi4_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others,
+                                 int n_pairs, const hmme_frame_params* fp, const void* d_other_mv /* int16[n_pairs][n_ctu][256][2] */, const void* d_center_q,
+                                 const void* d_pred_q, void* d_out_mv, void* d_out_sad, void* stream);
+int hmme_refine_pairs_bi4_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others,
+                                 int n_pairs, const hmme_frame_params* fp, const void* d_other_mv, const void* d_center_q, const void* d_pred_q,
+                                 const void* d_int_mv, int use_hadamard, void* d_out_qmv, void* d_out_cost, void* stream);
+int hmme_search_frame_bi4(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
+                          const int16_t* other_mv, const int16_t* center_q, const int16_t* pred_q, int16_t* out_mv, uint32_t* out_sad);
+int hmme_refine_frame_bi4(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* ref, const hmme_plane* other, const hmme_frame_params* fp,
+                          const int16_t* other_mv, const int16_t* center_q, const int16_t* pred_q, const int16_t* int_mv, int use_hadamard,
+                          int16_t* out_qmv, uint32_t* out_cost);
+int hmme_select_dirs4_check(const hmme_select_params* sel, int n_pics, const hmme_dir_params* dirs);
+int hmme_select_dirs4_device(hmme_ctx* ctx, int width, int height, int n_pics, const hmme_frame_params* fp, const hmme_select_params* sel,
+                             const hmme_dir_params* dirs, const void* d_mv_uni, const void* d_cost_uni, const void* d_mv_bi, const void* d_cost_bi,
+                             const void* d_uni_field, const void* d_pred_q, void* d_out_field, void* d_out_dir, void* d_out_slot, void* d_out_cost,
+                             void* stream);
+int hmme_select_dirs4_frame(hmme_ctx* ctx, int width, int height, const hmme_frame_params* fp, const hmme_select_params* sel,
+                            const hmme_dir_params* dir, const int16_t* mv_uni, const uint32_t* cost_uni, const int16_t* mv_bi, const uint32_t* cost_bi,
+                            const int16_t* uni_field, const int16_t* pred_q, int16_t* out_field, uint8_t* out_dir, uint16_t* out_slot,
+                            uint32_t* out_cost);
+int hmme_predict_bi4_device(hmme_ctx* ctx, const hmme_plane* const* refs0, const hmme_plane* const* refs1, int n_pics, const hmme_frame_params* fp,
+                            const void* d_mv_field, const void* d_dir_field, void* const* d_outs, int out_pitch_bytes, void* stream);
+int hmme_predict_bi4_frame(hmme_ctx* ctx, const hmme_plane* ref0, const hmme_plane* ref1, const hmme_frame_params* fp, const int16_t* mv_field,
+                           const uint8_t* dir_field, void* out, int out_stride);
+int hmme_predict_chroma_bi4_device(hmme_ctx* ctx, const hmme_plane* const* refs0, const hmme_plane* const* refs1, int n_pics, int width, int height,
+                                   const hmme_frame_params* fp, const void* d_mv_field, const void* d_dir_field, void* const* d_outs, int out_pitch_bytes,
+                                   void* stream);
+int hmme_predict_chroma_bi4_frame(hmme_ctx* ctx, const hmme_plane* const* ref0, const hmme_plane* const* ref1, int width, int height,
+                                  const hmme_frame_params* fp, const int16_t* mv_field, const uint8_t* dir_field, void* const* outs, int out_stride);
 
 /* ---- residual and distortion of a prediction ------------------------------------------------------------------------
  * The first things HM does with a prediction, on the device: the residual, what the prediction costs per PU, and what coding no residual
