@@ -2350,6 +2350,35 @@ int launch_predict4(hmme_ctx* ctx, const hmme_plane* src, const hmme::RefSet& se
   HIP_TRY(ctx, hipGetLastError());
   return HMME_OK;
 }
+
+// me_predict_bi_kernel (mv_per_ctu 1 | 64) or me_predict_bi4_kernel (256: unweighted) for CTUs [first, first + count) of a picture like `src`
+// with a direction per block (d_dirs) and list-major MVs: list 0 from ref0, list 1 from ref1.  pw: the picture's weights (null: none, and
+// identities); pr: a reference per block and list instead of ref0 / ref1 (hmme_predict_bi_refs_device), prw: with one weight per reference
+int launch_predict_bi(hmme_ctx* ctx, const hmme_plane* src, const uint8_t* ref0, const uint8_t* ref1, const int16_t* d_field, const uint8_t* d_dirs, int mv_per_ctu,
+                      int first, int count, uint8_t* dst, int dst_pitch, hipStream_t s, const hmme::MePredBiWp<1>* pw = nullptr,
+                      const hmme::MePredBiRefs<1>* pr = nullptr, const hmme::MePredBiWp<2>* prw = nullptr) {
+  const int n_ctu = hmme_num_ctus(src->width, src->height);
+  with_sample_type(src->bps, [&](auto sample) {
+    using T = decltype(sample);
+    if (mv_per_ctu == 256) {
+      hipLaunchKernelGGL(hmme::me_predict_bi4_kernel<T>, dim3((unsigned)count), dim3(256), 0, s, ref0, ref1, src->pitch, d_field, d_dirs, n_ctu, first, src->width,
+                         src->height, src->bit_depth, dst, dst_pitch);
+      return;
+    }
+    const auto go = [&](auto kernel, auto wp, auto refs) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)count), dim3(256), 0, s, ref0, ref1, src->pitch, d_field, d_dirs, mv_per_ctu, n_ctu, first, src->width, src->height,
+                         src->bit_depth, dst, dst_pitch, wp, refs);
+    };
+    const hmme::MePredBiWp<0> no_wp;
+    const hmme::MePredBiRefs<0> no_refs;
+    if (pr && prw) go(hmme::me_predict_bi_kernel<T, 2, 1>, *prw, *pr);
+    else if (pr) go(hmme::me_predict_bi_kernel<T, 0, 1>, no_wp, *pr);
+    else if (pw) go(hmme::me_predict_bi_kernel<T, 1>, *pw, no_refs);
+    else go(hmme::me_predict_bi_kernel<T, 0>, no_wp, no_refs);
+  });
+  HIP_TRY(ctx, hipGetLastError());
+  return HMME_OK;
+}
 }  // namespace
 
 int hmme_bipred_check(int bit_depth, int refine) {
@@ -2434,14 +2463,17 @@ int launch_chroma(hmme_ctx* ctx, const hmme_plane* p0, const hmme::MeChromaSrc& 
                   int out_pitch_bytes, hipStream_t s, const hmme::MeChromaWp<FORM, WP>& wp) {
   with_sample_type(p0->bps, [&](auto sample) {
     using T = decltype(sample);
-    const auto go = [&](auto kernel) {
+    const auto go = [&](auto kernel, const auto&... weights) {
       hipLaunchKernelGGL(kernel, dim3((unsigned)cl.count), dim3(256), 0, s, src, p0->pitch, d_field, cl.first, cl.w, cl.h, p0->bit_depth, (uint8_t*)d_cb, (uint8_t*)d_cr,
-                         out_pitch_bytes, wp);
+                         out_pitch_bytes, weights...);
     };
-    if constexpr (FORM == 1) {   // the form with a 4x4 field (hmme_predict_chroma_refs4_device)
-      if (mv_per_ctu == 256) return go(hmme::me_predict_chroma4_kernel<T, WP>);
+    if constexpr (FORM == 1) {   // the forms with a 4x4 field: hmme_predict_chroma_refs4_device ...
+      if (mv_per_ctu == 256) return go(hmme::me_predict_chroma4_kernel<T, WP>, wp);
     }
-    if (mv_per_ctu == 1) go(hmme::me_predict_chroma_kernel<T, FORM, WP, 1>); else go(hmme::me_predict_chroma_kernel<T, FORM, WP, 64>);
+    if constexpr (FORM == 2 && WP == 0) {   // ... and hmme_predict_chroma_bi4_device (unweighted: its kernel takes no weights)
+      if (mv_per_ctu == 256) return go(hmme::me_predict_chroma_bi4_kernel<T>);
+    }
+    if (mv_per_ctu == 1) go(hmme::me_predict_chroma_kernel<T, FORM, WP, 1>, wp); else go(hmme::me_predict_chroma_kernel<T, FORM, WP, 64>, wp);
   });
   HIP_TRY(ctx, hipGetLastError());
   return HMME_OK;
@@ -3558,34 +3590,15 @@ int predict_bi(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs0, c
       for (int k = 0; k < 4; ++k) src.set.base[k] = planes[4 * i + k]->origin();
       src.field = dirs;
       src.n_ctu = L.n_ctu;
-      if (four) {   // hmme_predict_chroma_bi4_device (unweighted)
-        with_sample_type(p0->bps, [&](auto sample) {
-          hipLaunchKernelGGL(hmme::me_predict_chroma_bi4_kernel<decltype(sample)>, dim3((unsigned)L.count), dim3(256), 0, s, src, p0->pitch, field, L.first, L.w, L.h,
-                             p0->bit_depth, (uint8_t*)d_outs[2 * i], (uint8_t*)d_outs[2 * i + 1], out_pitch_bytes);
-        });
-        if (hipGetLastError() != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "%s: launch failed", who);
-        continue;
-      }
-      if (bw[2 * i].identity && bw[2 * i + 1].identity)
+      if (bw[2 * i].identity && bw[2 * i + 1].identity)   // the 4x4 form is unweighted: always this one
         rc = launch_chroma<2, 0>(ctx, p0, src, field, mv_per_ctu, L, d_outs[2 * i], d_outs[2 * i + 1], out_pitch_bytes, s, hmme::MeChromaWp<2, 0>{});
       else
         rc = launch_chroma<2, 1>(ctx, p0, src, field, mv_per_ctu, L, d_outs[2 * i], d_outs[2 * i + 1], out_pitch_bytes, s, hmme::MeChromaWp<2, 1>{{bw[2 * i].k, bw[2 * i + 1].k}});
-      continue;
+    } else {
+      rc = launch_predict_bi(ctx, p0, planes[2 * i]->origin(), planes[2 * i + 1]->origin(), field, dirs, mv_per_ctu, L.first, L.count, (uint8_t*)d_outs[i], out_pitch_bytes, s,
+                             bw[i].identity ? nullptr : &bw[i].k);
     }
-    with_sample_type(p0->bps, [&](auto sample) {
-      using T = decltype(sample);
-      if (four) {   // hmme_predict_bi4_device (unweighted)
-        hipLaunchKernelGGL(hmme::me_predict_bi4_kernel<T>, dim3((unsigned)L.count), dim3(256), 0, s, planes[2 * i]->origin(), planes[2 * i + 1]->origin(), p0->pitch, field, dirs,
-                           L.n_ctu, L.first, L.w, L.h, p0->bit_depth, (uint8_t*)d_outs[i], out_pitch_bytes);
-        return;
-      }
-      const auto go = [&](auto kernel, auto wp) {
-        hipLaunchKernelGGL(kernel, dim3((unsigned)L.count), dim3(256), 0, s, planes[2 * i]->origin(), planes[2 * i + 1]->origin(), p0->pitch, field, dirs, mv_per_ctu,
-                           L.n_ctu, L.first, L.w, L.h, p0->bit_depth, (uint8_t*)d_outs[i], out_pitch_bytes, wp, hmme::MePredBiRefs<0>{});
-      };
-      if (bw[i].identity) go(hmme::me_predict_bi_kernel<T, 0>, hmme::MePredBiWp<0>{}); else go(hmme::me_predict_bi_kernel<T, 1>, bw[i].k);
-    });
-    if (hipGetLastError() != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "%s: launch failed", who);
+    rc = named(ctx, who, rc);
   }
   return pairs_end(ctx, planes, planes, per_pic * n_pics, s, rc);   // whatever the launches returned: the scratch is acquired
 }
@@ -3801,23 +3814,15 @@ int predict_bi_refs(hmme_ctx* ctx, const char* who, const hmme_plane* const* ref
   if (rc || !L.acquired) return rc;
   const hmme_plane* p0 = refs0[0];
   const hmme::MePredBiRefs<1> br = {{L.pl.refs, l1.refs}, (const uint8_t*)d_ref_field, {n0, n1}};
-  with_sample_type(p0->bps, [&](auto sample) {
-    using T = decltype(sample);
-    const auto go = [&](auto kernel, auto wp) {
-      hipLaunchKernelGGL(kernel, dim3((unsigned)L.count), dim3(256), 0, s, (const uint8_t*)nullptr, (const uint8_t*)nullptr, p0->pitch, (const int16_t*)d_mv_field,
-                         (const uint8_t*)d_dir_field, mv_per_ctu, L.n_ctu, L.first, L.w, L.h, p0->bit_depth, (uint8_t*)d_out, out_pitch_bytes, wp, br);
-    };
-    if (weighted && !bw[0].identity) {
-      hmme::MePredBiWp<2> kw = {};
-      for (int l = 0; l < 2; ++l)
-        for (int r = 0; r < (l ? n1 : n0); ++r) kw.ref[l][r] = bw[0].uni[l][r];
-      kw.shift = bw[0].shift;
-      go(hmme::me_predict_bi_kernel<T, 2, 1>, kw);
-    } else {
-      go(hmme::me_predict_bi_kernel<T, 0, 1>, hmme::MePredBiWp<0>{});
-    }
-  });
-  if (hipGetLastError() != hipSuccess) rc = fail(ctx, HMME_ERR_DEVICE, "%s: launch failed", who);
+  hmme::MePredBiWp<2> kw = {};
+  const bool wp = weighted && !bw[0].identity;
+  if (wp) {
+    for (int l = 0; l < 2; ++l)
+      for (int r = 0; r < (l ? n1 : n0); ++r) kw.ref[l][r] = bw[0].uni[l][r];
+    kw.shift = bw[0].shift;
+  }
+  rc = named(ctx, who, launch_predict_bi(ctx, p0, nullptr, nullptr, (const int16_t*)d_mv_field, (const uint8_t*)d_dir_field, mv_per_ctu, L.first, L.count, (uint8_t*)d_out,
+                                         out_pitch_bytes, s, nullptr, &br, wp ? &kw : nullptr));
   return lists_end(ctx, refs0, n0, refs1, n1, s, rc);   // whatever the launch returned: the scratch is acquired
 }
 

@@ -2464,6 +2464,51 @@ __device__ __forceinline__ void me_field_mv(const int16_t* __restrict__ mv_field
   clip_mv_q(mx, my, cu_x, cu_y, pic_w, pic_h);
 }
 
+struct MePredCtu { int ctu, cx, cy, cu_x, cu_y; };   // the CTU of a workgroup: its index in the picture, its column and row, its luma position
+__device__ __forceinline__ MePredCtu me_pred_ctu(int ctu_first, int pic_w) {
+  const int ctus_x = (pic_w + 63) >> 6, ctu = ctu_first + blockIdx.x, cx = ctu % ctus_x, cy = ctu / ctus_x;
+  return {ctu, cx, cy, cx * 64, cy * 64};
+}
+
+// kLumaTaps for a choice of phase per LANE, in LDS: tap j of a phase = signed byte j of its pair of dwords.  Read behind a barrier.
+__device__ __forceinline__ void me_stage_luma_taps(uint32_t (*taps)[2]) {
+  if (threadIdx.x < 8) {
+    uint32_t p = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) p |= (uint32_t)(uint8_t)kLumaTaps[threadIdx.x >> 1][4 * (threadIdx.x & 1) + j] << (8 * j);
+    taps[threadIdx.x >> 1][threadIdx.x & 1] = p;
+  }
+}
+
+// kMaxRefs weights for a choice per LANE: from the kernel arguments into LDS (int [kMaxRefs * 4]), which keeps the arguments out of scratch;
+// read back behind a barrier
+__device__ __forceinline__ void me_stage_weights(int* s_weights, const MePredWp<1>* ref) {
+  if (threadIdx.x < kMaxRefs * 4) s_weights[threadIdx.x] = ((const int*)ref)[threadIdx.x];
+}
+__device__ __forceinline__ MePredWp<1> me_staged_weight(const int* s_weights, int i) {
+  const int* a = s_weights + 4 * i;   // {w0, round, shift, offset}
+  return {a[0], a[1], a[2], a[3]};
+}
+
+// the unweighted end of a sample with a direction (use0 || use1): TComYuv::addAvg of both lists, else the rounded sample of the one
+__device__ __forceinline__ int me_tail_dir(bool use0, bool use1, int sum0, int sum1, const MePredConst& k) {
+  return use0 && use1 ? me_tail_avg(sum0, sum1, k) : me_tail_uni(use0 ? sum0 : sum1, k);
+}
+
+// sample v at (x, y) of a pitched image of w x h samples; samples beyond it are not written
+template <typename SrcT>
+__device__ __forceinline__ void me_store_sample(uint8_t* dst, int pitch, int x, int y, int w, int h, int v) {
+  if (x < w && y < h) ((SrcT*)(dst + (long)y * pitch))[x] = (SrcT)v;
+}
+
+// the bi-prediction origin 2 * cur - v + bias as u16 (TEncSearch.cpp:3702-3712, TComYuv::removeHighFreq, unclipped) at (x, y) of the CTU whose
+// origin block starts at `block`, rows pitch bytes apart; cur from the current picture's CTU-blocked copy
+template <typename SrcT>
+__device__ __forceinline__ void me_store_origin(const uint8_t* cur_blocks, int ctu, int x, int y, int v, int bias, uint8_t* block, int pitch) {
+  const int cur = (int)((const SrcT*)cur_blocks)[(long)ctu * 4096 + y * 64 + x];
+  ((uint16_t*)(block + (long)y * pitch))[x] = (uint16_t)(2 * cur - v + bias);
+}
+
 // One plane's two passes for the wave's 8x8 luma block at picture position (x0, y0): the 15 x 15 patch at the clamped MV -- rows / columns
 // -3 .. +11 around the displaced block -- through LDS (rows of 15 consecutive samples per load), the horizontal pass into the 14-bit
 // intermediate (15 rows x 8), the vertical sum of lane (r, c) = (lane >> 3, lane & 7) -- returned before any shift, so that the caller ends it
@@ -2538,9 +2583,7 @@ me_predict_kernel(const uint8_t* __restrict__ ref_origin, int ref_pitch, const i
   __shared__ int16_t patch[4][15 * 16];
   __shared__ int16_t mid[4][15 * 8];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int ctus_x = (pic_w + 63) >> 6;
-  const int ctu = ctu_first + blockIdx.x;
-  const int cx = ctu % ctus_x, cy = ctu / ctus_x, cu_x = cx * 64, cu_y = cy * 64;
+  const auto [ctu, cx, cy, cu_x, cu_y] = me_pred_ctu(ctu_first, pic_w);
   const MePredConst k(bit_depth);
 #pragma unroll 1
   for (int it = 0; it < 16; ++it) {
@@ -2564,13 +2607,8 @@ me_predict_kernel(const uint8_t* __restrict__ ref_origin, int ref_pitch, const i
       else if constexpr (WP == 2) v = me_tail_weight_uni(sum, wp.ref[ri], k.maxv);   // live: ri < n_refs
       else if constexpr (WP == 1) v = me_tail_weight_uni(sum, wp, k.maxv);
       else v = me_tail_uni(sum, k);
-      if (OUT == 0) {
-        const int x = cu_x + bx + c, y = cu_y + by + r;
-        if (x < pic_w && y < pic_h) ((SrcT*)(dst + (long)y * dst_pitch))[x] = (SrcT)v;
-      } else {
-        const int cur = (int)((const SrcT*)cur_blocks)[(long)ctu * 4096 + (by + r) * 64 + bx + c];
-        ((uint16_t*)(dst + cy * dst_ctu_y + cx * dst_ctu_x + (long)(by + r) * dst_pitch))[bx + c] = (uint16_t)(2 * cur - v + bias);
-      }
+      if (OUT == 0) me_store_sample<SrcT>(dst, dst_pitch, cu_x + bx + c, cu_y + by + r, pic_w, pic_h, v);
+      else me_store_origin<SrcT>(cur_blocks, ctu, bx + c, by + r, v, bias, dst + cy * dst_ctu_y + cx * dst_ctu_x, dst_pitch);
     }
   }
 }
@@ -2581,22 +2619,73 @@ me_predict_kernel(const uint8_t* __restrict__ ref_origin, int ref_pitch, const i
 // block at a time, lane (r, c) = (lane >> 3, lane & 7) one sample -- but the block is four QUADRANTS, lane (r, c) in quadrant
 // (r >> 2) * 2 + (c >> 2), each with its own entry: its own clamped MV (me_field_mv: the CTU's clamp, so the sample is the one the 64 form
 // writes when the 8x8 block carries this entry), its own plane, its own weight.
+//
+// me_predict4_pass is one list's pass for the wave's 8x8 block at picture position (x0, y0), and the only place that stages, filters and sums
+// quadrants (me_predict4_kernel: one pass per iteration; me_predict_bi4_kernel: list 0's, then list 1's).  live, mx, my are the LANE's -- those
+// of its quadrant, equal in the quadrant's 16 lanes; plane_of(from) is the plane of the quadrant whose first lane is `from`, wave-uniform.
+// Returns the vertical sum of lane (r, c) before any shift (0 in a lane that is not live), which the caller ends with one of the tails.
 //   stage       per quadrant the 11 x 11 patch at its MV -- rows / columns -3 .. +7 around the displaced 4x4 block, a subset of the 15 x 15
 //               patch the 64 form reads at that MV, so the planes' margins hold -- into wave-private LDS: four patches of 11 rows, pitch 12.
 //               Quadrant by quadrant, so MV, plane and liveness of a load are scalars (readlane of the quadrant's first lane).
 //   horizontal  the 14-bit intermediate, 11 rows x 4 columns per quadrant, 176 outputs per wave in three steps; the taps are chosen per
-//               lane by the output's quadrant (packed taps in LDS: two dwords per phase)
+//               lane by the output's quadrant (me_stage_luma_taps)
 //   vertical    lane (r, c): eight rows of its quadrant's intermediate with the taps of its own vertical phase
-//   tail        me_tail_uni (WP = 0) or me_tail_weight_uni with the weight of the lane's reference (WP = 2).  Index and weight are per
-//               lane, not per wave: the weights are staged into LDS, which keeps the kernel arguments out of scratch.
 // Pitch 12, not 11: rows stay dword-aligned and a quadrant's patch starts 66 dwords after the one before, two banks further; with either
 // pitch the 8 rows x 4 lanes of a half-wave's u16 reads span more than 32 banks and wrap once.  Measured: a pitch of 11 gives the same
 // times within 1 % (profiles/predict4_patch_pitch_ab.txt).
+// BARRIER INVARIANT (of every kernel that calls this pass or me_predict_chroma4_pass): __syncthreads() is a barrier of the whole workgroup.
+// Every wave and every 16-lane group -- live, partly live or wholly dead -- runs all iterations of its kernel's loop and meets the same two
+// barriers in each pass: stage | barrier | horizontal | barrier | vertical.  Everything that depends on the field (liveness, direction, the
+// plane, the phase) sits INSIDE a stage; no barrier is ever inside a branch, a pass is never called inside one, and no wave leaves the loop
+// early.
+template <typename SrcT, class PlaneOf>
+__device__ __forceinline__ int me_predict4_pass(bool live, PlaneOf plane_of, int ref_pitch, int x0, int y0, int mx, int my, int16_t* wpatch, int16_t* wmid,
+                                                const uint32_t (*taps)[2], int lane, const MePredConst& k) {
+  const int r = lane >> 3, c = lane & 7, q = (r >> 2) * 2 + (c >> 2);
+  int info[4];   // scalars: 4 | horizontal phase of a live quadrant, else 0
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const int from = (s >> 1) * 32 + (s & 1) * 4;
+    const int s_live = __builtin_amdgcn_readlane((int)live, from), s_mx = __builtin_amdgcn_readlane(mx, from), s_my = __builtin_amdgcn_readlane(my, from);
+    info[s] = s_live ? 4 | (s_mx & 3) : 0;
+    if (s_live) {
+      const uint8_t* src = plane_of(from) + (long)(y0 + (s >> 1) * 4 + (s_my >> 2) - 3) * ref_pitch + (long)(x0 + (s & 1) * 4 + (s_mx >> 2) - 3) * (long)sizeof(SrcT);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int el = lane + 64 * j, pr = el / 11, pc = el - pr * 11;
+        if (el < 121) wpatch[s * 132 + pr * 12 + pc] = (int16_t)((const SrcT*)(src + (long)pr * ref_pitch))[pc];
+      }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int o = lane + 64 * j, oq = o / 44, rem = o - oq * 44;   // output (row rem >> 2, column rem & 3) of quadrant oq
+    const int inf = oq == 0 ? info[0] : (oq == 1 ? info[1] : (oq == 2 ? info[2] : info[3]));
+    if (o < 176 && inf) {
+      const uint32_t lo = taps[inf & 3][0], hi = taps[inf & 3][1];
+      const int16_t* p = wpatch + oq * 132 + (rem >> 2) * 12 + (rem & 3);
+      int sum = 0;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) sum += (int)(int8_t)(lo >> (8 * t)) * (int)p[t] + (int)(int8_t)(hi >> (8 * t)) * (int)p[t + 4];
+      wmid[o] = (int16_t)((sum + k.off1) >> k.sh1);
+    }
+  }
+  __syncthreads();
+  int sum = 0;
+  if (live) {
+    const uint32_t lo = taps[my & 3][0], hi = taps[my & 3][1];
+    const int16_t* p = wmid + q * 44 + (r & 3) * 4 + (c & 3);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) sum += (int)(int8_t)(lo >> (8 * t)) * (int)p[4 * t] + (int)(int8_t)(hi >> (8 * t)) * (int)p[4 * (t + 4)];
+  }
+  return sum;
+}
+
+// me_predict4_kernel: one pass per iteration, the plane of a quadrant being set.base[its index]; the tail is me_tail_uni (WP = 0) or
+// me_tail_weight_uni with the weight of the lane's reference (WP = 2).  Index and weight are per lane, not per wave: me_stage_weights.
 // A quadrant is live if its 4x4 block starts inside the picture and its index is < n_refs; one that is not reads no plane and its lanes
-// write nothing.
-// BARRIER INVARIANT: __syncthreads() is a barrier of the whole workgroup.  Every wave -- live, partly live or wholly dead -- runs all 16
-// iterations and meets the same two barriers in each: stage | barrier | horizontal | barrier | vertical.  Everything that depends on the
-// field (liveness, the plane, the phase) sits INSIDE a stage; no barrier is ever inside a branch, and no wave leaves the loop early.
+// write nothing.  The barrier invariant is the pass's: the loop has 16 iterations for every wave.
 //   OUT = 0: the prediction, as described above.  Takes an empty MePred4Origin and compiles to what it did without the parameter.
 //   OUT = 1: the bi-prediction origin 2 * cur - pred + bias as u16 from a 4x4 field (hmme_search_pairs_bi4_device / hmme_refine_pairs_bi4_device;
 //            WP = 0 only, and the callers pass n_refs = 1 with a null ref_field), as me_predict_kernel<SrcT, 1> forms it from a 64 field:
@@ -2613,25 +2702,14 @@ me_predict4_kernel(RefSet set, int n_refs, int ref_pitch, const int16_t* __restr
   static_assert(OUT == 0 || WP == 0, "the origin from a 4x4 field is unweighted");
   __shared__ int16_t patch[4][4 * 11 * 12];
   __shared__ int16_t mid[4][4 * 11 * 4];
-  __shared__ uint32_t taps[4][2];   // kLumaTaps, tap j of a phase = signed byte j of the pair; read behind the first barrier
+  __shared__ uint32_t taps[4][2];
   __shared__ int s_weights[kMaxRefs * 4];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (threadIdx.x < 8) {
-    uint32_t p = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) p |= (uint32_t)(uint8_t)kLumaTaps[threadIdx.x >> 1][4 * (threadIdx.x & 1) + j] << (8 * j);
-    taps[threadIdx.x >> 1][threadIdx.x & 1] = p;
-  }
-  if constexpr (WP == 2) {
-    if (threadIdx.x < kMaxRefs * 4) s_weights[threadIdx.x] = ((const int*)wp.ref)[threadIdx.x];
-  }
-  const int ctus_x = (pic_w + 63) >> 6;
-  const int ctu = ctu_first + blockIdx.x;
-  const int cx = ctu % ctus_x, cy = ctu / ctus_x, cu_x = cx * 64, cu_y = cy * 64;
+  me_stage_luma_taps(taps);
+  if constexpr (WP == 2) me_stage_weights(s_weights, wp.ref);
+  const auto [ctu, cx, cy, cu_x, cu_y] = me_pred_ctu(ctu_first, pic_w);
   const MePredConst k(bit_depth);
-  const int r = lane >> 3, c = lane & 7, q = (r >> 2) * 2 + (c >> 2);
-  int16_t* const wpatch = patch[wave];
-  int16_t* const wmid = mid[wave];
+  const int r = lane >> 3, c = lane & 7;
 #pragma unroll 1
   for (int it = 0; it < 16; ++it) {
     const int b = it * 4 + wave, bx = (b & 7) * 8, by = (b >> 3) * 8;   // the four waves: four 8x8 blocks side by side
@@ -2643,59 +2721,14 @@ me_predict4_kernel(RefSet set, int n_refs, int ref_pitch, const int16_t* __restr
     int mx = 0, my = 0;
     if (live) me_field_mv(mv_field, e, cu_x, cu_y, pic_w, pic_h, mx, my);
     else ri = 0;
-    // stage: quadrant s from the entry of its first lane
-    int info[4];   // scalars: 4 | horizontal phase of a live quadrant, else 0
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const int from = (s >> 1) * 32 + (s & 1) * 4;
-      const int s_live = __builtin_amdgcn_readlane((int)live, from), s_mx = __builtin_amdgcn_readlane(mx, from);
-      const int s_my = __builtin_amdgcn_readlane(my, from), s_ri = __builtin_amdgcn_readlane(ri, from);
-      info[s] = s_live ? 4 | (s_mx & 3) : 0;
-      if (s_live) {
-        const uint8_t* src = set.base[s_ri] + (long)(cu_y + by + (s >> 1) * 4 + (s_my >> 2) - 3) * ref_pitch +
-                             (long)(cu_x + bx + (s & 1) * 4 + (s_mx >> 2) - 3) * (long)sizeof(SrcT);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int el = lane + 64 * j, pr = el / 11, pc = el - pr * 11;
-          if (el < 121) wpatch[s * 132 + pr * 12 + pc] = (int16_t)((const SrcT*)(src + (long)pr * ref_pitch))[pc];
-        }
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const int o = lane + 64 * j, oq = o / 44, rem = o - oq * 44;   // output (row rem >> 2, column rem & 3) of quadrant oq
-      const int inf = oq == 0 ? info[0] : (oq == 1 ? info[1] : (oq == 2 ? info[2] : info[3]));
-      if (o < 176 && inf) {
-        const uint32_t lo = taps[inf & 3][0], hi = taps[inf & 3][1];
-        const int16_t* p = wpatch + oq * 132 + (rem >> 2) * 12 + (rem & 3);
-        int sum = 0;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) sum += (int)(int8_t)(lo >> (8 * t)) * (int)p[t] + (int)(int8_t)(hi >> (8 * t)) * (int)p[t + 4];
-        wmid[o] = (int16_t)((sum + k.off1) >> k.sh1);
-      }
-    }
-    __syncthreads();
+    const auto plane_of = [&](int from) { return set.base[__builtin_amdgcn_readlane(ri, from)]; };
+    const int sum = me_predict4_pass<SrcT>(live, plane_of, ref_pitch, cu_x + bx, cu_y + by, mx, my, patch[wave], mid[wave], taps, lane, k);
     if (live) {
-      const uint32_t lo = taps[my & 3][0], hi = taps[my & 3][1];
-      const int16_t* p = wmid + q * 44 + (r & 3) * 4 + (c & 3);
-      int sum = 0;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) sum += (int)(int8_t)(lo >> (8 * t)) * (int)p[4 * t] + (int)(int8_t)(hi >> (8 * t)) * (int)p[4 * (t + 4)];
       int v;
-      if constexpr (WP == 2) {
-        const int* a = s_weights + 4 * ri;   // {w0, round, shift, offset} of MePredWp<1>
-        v = me_tail_weight_uni(sum, MePredWp<1>{a[0], a[1], a[2], a[3]}, k.maxv);
-      } else {
-        v = me_tail_uni(sum, k);
-      }
-      if constexpr (OUT == 0) {
-        const int x = cu_x + bx + c, y = cu_y + by + r;
-        if (x < pic_w && y < pic_h) ((SrcT*)(dst + (long)y * dst_pitch))[x] = (SrcT)v;
-      } else {
-        const int cur = (int)((const SrcT*)org.cur_blocks)[(long)ctu * 4096 + (by + r) * 64 + bx + c];
-        ((uint16_t*)(dst + cy * org.ctu_y + cx * org.ctu_x + (long)(by + r) * dst_pitch))[bx + c] = (uint16_t)(2 * cur - v + org.bias);
-      }
+      if constexpr (WP == 2) v = me_tail_weight_uni(sum, me_staged_weight(s_weights, ri), k.maxv);
+      else v = me_tail_uni(sum, k);
+      if constexpr (OUT == 0) me_store_sample<SrcT>(dst, dst_pitch, cu_x + bx + c, cu_y + by + r, pic_w, pic_h, v);
+      else me_store_origin<SrcT>(org.cur_blocks, ctu, bx + c, by + r, v, org.bias, dst + cy * org.ctu_y + cx * org.ctu_x, dst_pitch);
     }
   }
 }
@@ -3412,9 +3445,7 @@ me_predict_bi_kernel(const uint8_t* __restrict__ ref0, const uint8_t* __restrict
   __shared__ int16_t patch[4][15 * 16];
   __shared__ int16_t mid[4][15 * 8];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int ctus_x = (pic_w + 63) >> 6;
-  const int ctu = ctu_first + blockIdx.x;
-  const int cx = ctu % ctus_x, cy = ctu / ctus_x, cu_x = cx * 64, cu_y = cy * 64;
+  const auto [ctu, cx, cy, cu_x, cu_y] = me_pred_ctu(ctu_first, pic_w);
   const MePredConst k(bit_depth);
 #pragma unroll 1
   for (int it = 0; it < 16; ++it) {
@@ -3449,73 +3480,21 @@ me_predict_bi_kernel(const uint8_t* __restrict__ ref0, const uint8_t* __restrict
         if (use0 && use1) v = me_tail_weight_bi(sum0, sum1, wp.w0, wp.w1, wp.add, wp.shift, k.maxv);
         else v = me_tail_weight_uni(use0 ? sum0 : sum1, use0 ? wp.uni[0] : wp.uni[1], k.maxv);   // wave-uniform
       } else {
-        if (use0 && use1) v = me_tail_avg(sum0, sum1, k);
-        else v = me_tail_uni(use0 ? sum0 : sum1, k);
+        v = me_tail_dir(use0, use1, sum0, sum1, k);
       }
-      const int x = cu_x + bx + (lane & 7), y = cu_y + by + (lane >> 3);
-      if (x < pic_w && y < pic_h) ((SrcT*)(dst + (long)y * dst_pitch))[x] = (SrcT)v;
+      me_store_sample<SrcT>(dst, dst_pitch, cu_x + bx + (lane & 7), cu_y + by + (lane >> 3), pic_w, pic_h, v);
     }
   }
 }
 
 // ---- L0, L1 or bi per 4x4 block (hmme_predict_bi4_device; the rule: include/hmme.h) -------------------------------------------------------
-// One list's pass of me_predict4_kernel for the wave's 8x8 block at CTU position (bx, by): its stage, horizontal and vertical steps with its
-// lanes, patches (11 x 11 per quadrant, pitch 12) and packed taps, on one plane.  live, mx, my are the LANE's -- those of its quadrant, equal
-// in the quadrant's 16 lanes -- and each quadrant is staged from its first lane.  Returns the vertical sum of lane (r, c) before any shift
-// (0 in a lane that is not live).  Two barriers, both outside every branch: stage | barrier | horizontal | barrier | vertical.
-template <typename SrcT>
-__device__ __forceinline__ int me_predict4_pass(bool live, const uint8_t* plane, int ref_pitch, int x0, int y0, int mx, int my, int16_t* wpatch, int16_t* wmid,
-                                                const uint32_t (*taps)[2], int lane, const MePredConst& k) {
-  const int r = lane >> 3, c = lane & 7, q = (r >> 2) * 2 + (c >> 2);
-  int info[4];   // scalars: 4 | horizontal phase of a live quadrant, else 0
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const int from = (s >> 1) * 32 + (s & 1) * 4;
-    const int s_live = __builtin_amdgcn_readlane((int)live, from), s_mx = __builtin_amdgcn_readlane(mx, from), s_my = __builtin_amdgcn_readlane(my, from);
-    info[s] = s_live ? 4 | (s_mx & 3) : 0;
-    if (s_live) {
-      const uint8_t* src = plane + (long)(y0 + (s >> 1) * 4 + (s_my >> 2) - 3) * ref_pitch + (long)(x0 + (s & 1) * 4 + (s_mx >> 2) - 3) * (long)sizeof(SrcT);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int el = lane + 64 * j, pr = el / 11, pc = el - pr * 11;
-        if (el < 121) wpatch[s * 132 + pr * 12 + pc] = (int16_t)((const SrcT*)(src + (long)pr * ref_pitch))[pc];
-      }
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const int o = lane + 64 * j, oq = o / 44, rem = o - oq * 44;   // output (row rem >> 2, column rem & 3) of quadrant oq
-    const int inf = oq == 0 ? info[0] : (oq == 1 ? info[1] : (oq == 2 ? info[2] : info[3]));
-    if (o < 176 && inf) {
-      const uint32_t lo = taps[inf & 3][0], hi = taps[inf & 3][1];
-      const int16_t* p = wpatch + oq * 132 + (rem >> 2) * 12 + (rem & 3);
-      int sum = 0;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) sum += (int)(int8_t)(lo >> (8 * t)) * (int)p[t] + (int)(int8_t)(hi >> (8 * t)) * (int)p[t + 4];
-      wmid[o] = (int16_t)((sum + k.off1) >> k.sh1);
-    }
-  }
-  __syncthreads();
-  int sum = 0;
-  if (live) {
-    const uint32_t lo = taps[my & 3][0], hi = taps[my & 3][1];
-    const int16_t* p = wmid + q * 44 + (r & 3) * 4 + (c & 3);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) sum += (int)(int8_t)(lo >> (8 * t)) * (int)p[4 * t] + (int)(int8_t)(hi >> (8 * t)) * (int)p[4 * (t + 4)];
-  }
-  return sum;
-}
-
 // me_predict_bi_kernel<SrcT> with HM's own motion storage: mv_field int16 [2][n_ctu][256][2] (list-major), dir_field uint8 [n_ctu][256], entry b
 // the 4x4 block at ((b & 15) * 4, (b >> 4) * 4) of the CTU.  Lanes, patches and taps are me_predict4_kernel's; list 0 and then list 1 go
 // through the same wave-private LDS (me_predict4_pass twice: FOUR barriers per iteration, as me_predict_bi_kernel has).  Direction and both
 // MVs are per QUADRANT, read from the quadrant's first lane: a quadrant is live if its 4x4 block starts inside the picture and its direction
 // is 1, 2 or 3; in a list its direction does not name it stages nothing.  Tail per lane: me_tail_avg when both lists are used, else
 // me_tail_uni -- the sample me_predict_bi_kernel writes when the 8x8 block carries the quadrant's (direction, MV0, MV1).
-// BARRIER INVARIANT (me_predict4_kernel's): __syncthreads() is a barrier of the whole workgroup.  Every wave and every 16-lane group -- live,
-// partly live or wholly dead -- runs all 16 iterations and meets the same four barriers in each.  Everything that depends on the field
-// (direction, liveness, phase) sits INSIDE a stage of me_predict4_pass; no barrier is ever inside a branch, and no wave leaves the loop early.
+// The barrier invariant is me_predict4_pass's: both passes of all 16 iterations are met by every wave, whatever the field holds.
 template <typename SrcT>
 __global__ void __launch_bounds__(256)
 me_predict_bi4_kernel(const uint8_t* __restrict__ ref0, const uint8_t* __restrict__ ref1, int ref_pitch, const int16_t* __restrict__ mv_field,
@@ -3523,17 +3502,10 @@ me_predict_bi4_kernel(const uint8_t* __restrict__ ref0, const uint8_t* __restric
                       int dst_pitch) {
   __shared__ int16_t patch[4][4 * 11 * 12];
   __shared__ int16_t mid[4][4 * 11 * 4];
-  __shared__ uint32_t taps[4][2];   // kLumaTaps, tap j of a phase = signed byte j of the pair; read behind the first barrier
+  __shared__ uint32_t taps[4][2];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (threadIdx.x < 8) {
-    uint32_t p = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) p |= (uint32_t)(uint8_t)kLumaTaps[threadIdx.x >> 1][4 * (threadIdx.x & 1) + j] << (8 * j);
-    taps[threadIdx.x >> 1][threadIdx.x & 1] = p;
-  }
-  const int ctus_x = (pic_w + 63) >> 6;
-  const int ctu = ctu_first + blockIdx.x;
-  const int cx = ctu % ctus_x, cy = ctu / ctus_x, cu_x = cx * 64, cu_y = cy * 64;
+  me_stage_luma_taps(taps);
+  const auto [ctu, cx, cy, cu_x, cu_y] = me_pred_ctu(ctu_first, pic_w);
   const MePredConst k(bit_depth);
   const int r = lane >> 3, c = lane & 7;
 #pragma unroll 1
@@ -3547,13 +3519,9 @@ me_predict_bi4_kernel(const uint8_t* __restrict__ ref0, const uint8_t* __restric
     int mx0 = 0, my0 = 0, mx1 = 0, my1 = 0;
     if (use0) me_field_mv(mv_field, e, cu_x, cu_y, pic_w, pic_h, mx0, my0);
     if (use1) me_field_mv(mv_field, (long)n_ctu * 256 + e, cu_x, cu_y, pic_w, pic_h, mx1, my1);
-    const int sum0 = me_predict4_pass<SrcT>(use0, ref0, ref_pitch, cu_x + bx, cu_y + by, mx0, my0, patch[wave], mid[wave], taps, lane, k);
-    const int sum1 = me_predict4_pass<SrcT>(use1, ref1, ref_pitch, cu_x + bx, cu_y + by, mx1, my1, patch[wave], mid[wave], taps, lane, k);
-    if (live) {
-      const int v = use0 && use1 ? me_tail_avg(sum0, sum1, k) : me_tail_uni(use0 ? sum0 : sum1, k);
-      const int x = cu_x + bx + c, y = cu_y + by + r;
-      if (x < pic_w && y < pic_h) ((SrcT*)(dst + (long)y * dst_pitch))[x] = (SrcT)v;
-    }
+    const int sum0 = me_predict4_pass<SrcT>(use0, [=](int) { return ref0; }, ref_pitch, cu_x + bx, cu_y + by, mx0, my0, patch[wave], mid[wave], taps, lane, k);
+    const int sum1 = me_predict4_pass<SrcT>(use1, [=](int) { return ref1; }, ref_pitch, cu_x + bx, cu_y + by, mx1, my1, patch[wave], mid[wave], taps, lane, k);
+    if (live) me_store_sample<SrcT>(dst, dst_pitch, cu_x + bx + c, cu_y + by + r, pic_w, pic_h, me_tail_dir(use0, use1, sum0, sum1, k));
   }
 }
 
@@ -3647,12 +3615,10 @@ me_predict_chroma_kernel(MeChromaSrc src, int ref_pitch, const int16_t* __restri
   const int* s_wp = nullptr;   // FORM 3, WP 2: the planes' weights in LDS, read behind the barriers, too
   if constexpr (FORM == 3 && WP == 2) {
     __shared__ int s_weights[kMaxRefs * 4];
-    if (threadIdx.x < kMaxRefs * 4) s_weights[threadIdx.x] = ((const int*)wp.ref)[threadIdx.x];
+    me_stage_weights(s_weights, wp.ref);
     s_wp = s_weights;
   }
-  const int ctus_x = (pic_w + 63) >> 6;
-  const int ctu = ctu_first + blockIdx.x;
-  const int cx = ctu % ctus_x, cy = ctu / ctus_x, cu_x = cx * 64, cu_y = cy * 64;
+  const auto [ctu, cx, cy, cu_x, cu_y] = me_pred_ctu(ctu_first, pic_w);
   const MePredConst k(bit_depth);
   uint8_t* const dst = comp ? dst_cr : dst_cb;
 #pragma unroll 1
@@ -3691,134 +3657,39 @@ me_predict_chroma_kernel(MeChromaSrc src, int ref_pitch, const int16_t* __restri
     }
     if (use0 || use1) {
       int v;
-      if (FORM >= 2 && use0 && use1) {
-        if constexpr (FORM == 2 && WP == 1) v = me_tail_weight_bi(sum0, sum1, wp.c[comp].w0, wp.c[comp].w1, wp.c[comp].add, wp.c[comp].shift, k.maxv);
-        else if constexpr (FORM == 3 && WP == 2) {
-          const int* a0 = s_wp + 4 * (2 * sel + comp);    // {w0, round, shift, offset} of MePredWp<1>
-          const int* a1 = s_wp + 4 * (2 * sel1 + comp);
+      if constexpr (WP == 0) {
+        v = me_tail_dir(use0, use1, sum0, sum1, k);
+      } else if (FORM >= 2 && use0 && use1) {
+        if constexpr (FORM == 2) v = me_tail_weight_bi(sum0, sum1, wp.c[comp].w0, wp.c[comp].w1, wp.c[comp].add, wp.c[comp].shift, k.maxv);
+        else if constexpr (FORM == 3) {
+          const MePredWp<1> a0 = me_staged_weight(s_wp, 2 * sel + comp), a1 = me_staged_weight(s_wp, 2 * sel1 + comp);
           const int sh = wp.shift[comp];
-          v = me_tail_weight_bi(sum0, sum1, a0[0], a1[0], (1 + a0[3] + a1[3]) * (1 << (sh - 1)), sh, k.maxv);
-        } else v = me_tail_avg(sum0, sum1, k);
-      } else {
-        const int sum = use0 ? sum0 : sum1;
-        if constexpr (WP != 0) {
-          MePredWp<1> w;
-          if constexpr (FORM == 0) w = wp.c[comp];
-          else if constexpr (FORM == 1) w = wp.ref[2 * sel + comp];
-          else if constexpr (FORM == 3) { const int* a = s_wp + 4 * (2 * (use0 ? sel : sel1) + comp); w = MePredWp<1>{a[0], a[1], a[2], a[3]}; }
-          else w = wp.c[comp].uni[use0 ? 0 : 1];
-          v = me_tail_weight_uni(sum, w, k.maxv);
-        } else {
-          v = me_tail_uni(sum, k);
+          v = me_tail_weight_bi(sum0, sum1, a0.w0, a1.w0, (1 + a0.offset + a1.offset) * (1 << (sh - 1)), sh, k.maxv);
         }
+      } else {
+        MePredWp<1> w;
+        if constexpr (FORM == 0) w = wp.c[comp];
+        else if constexpr (FORM == 1) w = wp.ref[2 * sel + comp];
+        else if constexpr (FORM == 3) w = me_staged_weight(s_wp, 2 * (use0 ? sel : sel1) + comp);
+        else w = wp.c[comp].uni[use0 ? 0 : 1];
+        v = me_tail_weight_uni(use0 ? sum0 : sum1, w, k.maxv);
       }
-      const int x = x0 + (l16 & 3), y = y0 + (l16 >> 2);
-      if (x < (pic_w >> 1) && y < (pic_h >> 1)) ((SrcT*)(dst + (long)y * dst_pitch))[x] = (SrcT)v;
+      me_store_sample<SrcT>(dst, dst_pitch, x0 + (l16 & 3), y0 + (l16 >> 2), pic_w >> 1, pic_h >> 1, v);
     }
   }
 }
 
-// FORM 1 from one MV per 4x4 LUMA block (hmme_predict_chroma_refs4_device): mv_field int16 [n_ctu][256][2], src.field uint8 [n_ctu][256]
-// (null: every block index 0).  The lanes are those of me_predict_chroma_kernel -- a 16-lane group owns the 4x4 block of one component of
-// one 8x8 luma block, lane l16 = 4 r + c one sample, eight iterations per CTU -- but the block is four 2x2 QUADS, lane (r, c) in quad
-// (r >> 1) * 2 + (c >> 1), each the chroma of one 4x4 luma block with that block's MV (the CTU's clamp), reference index and the
-// component's weight of that reference: sample for sample what the 64 form writes when the 8x8 luma block carries the entry.
+// me_predict_chroma4_pass is one list's pass for a 16-lane group -- the 4x4 block of one component at chroma position (x0, y0) -- and the only
+// place that stages, filters and sums quads (me_predict_chroma4_kernel: one pass per iteration; me_predict_chroma_bi4_kernel: list 0's, then
+// list 1's).  live, mx, my are the LANE's -- those of its quad; plane_of(from) is the plane of the quad whose first lane is `from`, called
+// by the whole wave for every quad, live or not (a quad that is not live reads nothing from it).  Returns the vertical sum of lane (r, c) before any shift (0 in a lane that is not live).
 //   stage       per quad the 5 x 5 patch at its MV -- rows / columns -1 .. +3 around the displaced 2x2 block, a subset of the 7 x 7 patch of
 //               the 64 form at that MV -- into the group's LDS, quad by quad; a quad's entry comes from its first lane (__shfl)
 //   horizontal  5 rows x 2 columns per quad, 40 outputs per group in three steps, taps by the output's quad
-//   vertical    lane (r, c): four rows of its quad's intermediate; then me_tail_uni (WP = 0) or me_tail_weight_uni with the weight of plane
-//               2 * index + component (WP = 2), staged into LDS because the index is per lane
-// A quad is live if its 4x4 luma block starts inside the luma picture and its index is < n_refs.  The BARRIER INVARIANT is
-// me_predict4_kernel's: every group of every wave runs all eight iterations and meets the same two barriers in each, whatever the field
-// holds; no barrier is inside a branch.
-template <typename SrcT, int WP>
-__global__ void __launch_bounds__(256)
-me_predict_chroma4_kernel(MeChromaSrc src, int ref_pitch, const int16_t* __restrict__ mv_field, int ctu_first, int pic_w, int pic_h, int bit_depth,
-                          uint8_t* __restrict__ dst_cb, uint8_t* __restrict__ dst_cr, int dst_pitch, MeChromaWp<1, WP> wp) {
-  static_assert(WP == 0 || WP == 2, "one weight per plane, or none");
-  __shared__ int16_t patch[16][4 * 25];
-  __shared__ int16_t mid[16][4 * 10];
-  __shared__ uint32_t taps[8];
-  __shared__ int s_weights[kMaxRefs * 4];
-  const int group = threadIdx.x >> 4, l16 = threadIdx.x & 15, comp = group & 1, lane = threadIdx.x & 63;
-  if (threadIdx.x < 8) taps[threadIdx.x] = kChromaTaps[threadIdx.x];   // read behind the first barrier
-  if constexpr (WP == 2) {
-    if (threadIdx.x < kMaxRefs * 4) s_weights[threadIdx.x] = ((const int*)wp.ref)[threadIdx.x];
-  }
-  const int ctus_x = (pic_w + 63) >> 6;
-  const int ctu = ctu_first + blockIdx.x;
-  const int cx = ctu % ctus_x, cy = ctu / ctus_x, cu_x = cx * 64, cu_y = cy * 64;
-  const MePredConst k(bit_depth);
-  uint8_t* const dst = comp ? dst_cr : dst_cb;
-  const int r = l16 >> 2, c = l16 & 3, q = (r >> 1) * 2 + (c >> 1);
-  int16_t* const gpatch = patch[group];
-  int16_t* const gmid = mid[group];
-#pragma unroll 1
-  for (int it = 0; it < 8; ++it) {
-    const int bx = (group >> 1) * 8, by = it * 8;                        // the group's 8x8 luma block: a block row per iteration
-    const int qx = bx + (c >> 1) * 4, qy = by + (r >> 1) * 4;           // this lane's 4x4 luma block inside the CTU
-    const long e = (long)ctu * 256 + (qy >> 2) * 16 + (qx >> 2);
-    const int x0 = (cu_x + bx) >> 1, y0 = (cu_y + by) >> 1;
-    int sel = src.field ? (int)src.field[e] : 0;
-    const bool live = cu_x + qx < pic_w && cu_y + qy < pic_h && sel < src.n_refs;
-    int mx = 0, my = 0;
-    if (live) me_field_mv(mv_field, e, cu_x, cu_y, pic_w, pic_h, mx, my);
-    else sel = 0;
-    int info[4];   // per group: 8 | horizontal phase of a live quad, else 0
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const int from = (lane & 48) + (s >> 1) * 8 + (s & 1) * 2;
-      const int s_live = __shfl((int)live, from), s_mx = __shfl(mx, from), s_my = __shfl(my, from), s_sel = __shfl(sel, from);
-      info[s] = s_live ? 8 | (s_mx & 7) : 0;
-      if (s_live) {
-        const uint8_t* p = src.set.base[2 * s_sel + comp] + (long)(y0 + (s >> 1) * 2 + (s_my >> 3) - 1) * ref_pitch +
-                           (long)(x0 + (s & 1) * 2 + (s_mx >> 3) - 1) * (long)sizeof(SrcT);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int el = l16 + 16 * j, pr = el / 5, pc = el - pr * 5;
-          if (el < 25) gpatch[s * 25 + el] = (int16_t)((const SrcT*)(p + (long)pr * ref_pitch))[pc];
-        }
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const int o = l16 + 16 * j, oq = o / 10, rem = o - oq * 10;   // output (row rem >> 1, column rem & 1) of quad oq
-      const int inf = oq == 0 ? info[0] : (oq == 1 ? info[1] : (oq == 2 ? info[2] : info[3]));
-      if (o < 40 && inf) {
-        const uint32_t th = taps[inf & 7];
-        const int16_t* p = gpatch + oq * 25 + (rem >> 1) * 5 + (rem & 1);
-        int sum = 0;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) sum += (int)(int8_t)(th >> (8 * t)) * (int)p[t];
-        gmid[o] = (int16_t)((sum + k.off1) >> k.sh1);
-      }
-    }
-    __syncthreads();
-    if (live) {
-      const uint32_t tv = taps[my & 7];
-      const int16_t* p = gmid + q * 10 + (r & 1) * 2 + (c & 1);
-      int sum = 0;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) sum += (int)(int8_t)(tv >> (8 * t)) * (int)p[2 * t];
-      int v;
-      if constexpr (WP == 2) {
-        const int* a = s_weights + 4 * (2 * sel + comp);   // {w0, round, shift, offset} of MePredWp<1>
-        v = me_tail_weight_uni(sum, MePredWp<1>{a[0], a[1], a[2], a[3]}, k.maxv);
-      } else {
-        v = me_tail_uni(sum, k);
-      }
-      const int x = x0 + c, y = y0 + r;
-      if (x < (pic_w >> 1) && y < (pic_h >> 1)) ((SrcT*)(dst + (long)y * dst_pitch))[x] = (SrcT)v;
-    }
-  }
-}
-
-// One list's pass of me_predict_chroma4_kernel for a 16-lane group: the 4x4 block of one component (one 8x8 luma block) at chroma position
-// (x0, y0) as four 2x2 quads, on one plane.  live, mx, my are the LANE's -- those of its quad -- and each quad is staged from its first lane.
-// Returns the vertical sum of lane (r, c) before any shift (0 in a lane that is not live).  Two barriers, both outside every branch.
-template <typename SrcT>
-__device__ __forceinline__ int me_predict_chroma4_pass(bool live, const uint8_t* plane, int ref_pitch, int x0, int y0, int mx, int my, int16_t* gpatch,
+//   vertical    lane (r, c): four rows of its quad's intermediate
+// Two barriers, both outside every branch: the BARRIER INVARIANT is stated at me_predict4_pass and holds here word for word.
+template <typename SrcT, class PlaneOf>
+__device__ __forceinline__ int me_predict_chroma4_pass(bool live, PlaneOf plane_of, int ref_pitch, int x0, int y0, int mx, int my, int16_t* gpatch,
                                                        int16_t* gmid, const uint32_t* taps, int lane, const MePredConst& k) {
   const int l16 = lane & 15, r = l16 >> 2, c = l16 & 3, q = (r >> 1) * 2 + (c >> 1);
   int info[4];   // per group: 8 | horizontal phase of a live quad, else 0
@@ -3826,6 +3697,7 @@ __device__ __forceinline__ int me_predict_chroma4_pass(bool live, const uint8_t*
   for (int s = 0; s < 4; ++s) {
     const int from = (lane & 48) + (s >> 1) * 8 + (s & 1) * 2;
     const int s_live = __shfl((int)live, from), s_mx = __shfl(mx, from), s_my = __shfl(my, from);
+    const uint8_t* const plane = plane_of(from);   // in front of the branch: a cross-lane read in it goes out with the three above
     info[s] = s_live ? 8 | (s_mx & 7) : 0;
     if (s_live) {
       const uint8_t* p = plane + (long)(y0 + (s >> 1) * 2 + (s_my >> 3) - 1) * ref_pitch + (long)(x0 + (s & 1) * 2 + (s_mx >> 3) - 1) * (long)sizeof(SrcT);
@@ -3861,13 +3733,59 @@ __device__ __forceinline__ int me_predict_chroma4_pass(bool live, const uint8_t*
   return sum;
 }
 
+// FORM 1 from one MV per 4x4 LUMA block (hmme_predict_chroma_refs4_device): mv_field int16 [n_ctu][256][2], src.field uint8 [n_ctu][256]
+// (null: every block index 0).  The lanes are those of me_predict_chroma_kernel -- a 16-lane group owns the 4x4 block of one component of
+// one 8x8 luma block, lane l16 = 4 r + c one sample, eight iterations per CTU -- but the block is four 2x2 QUADS, lane (r, c) in quad
+// (r >> 1) * 2 + (c >> 1), each the chroma of one 4x4 luma block with that block's MV (the CTU's clamp), reference index and the
+// component's weight of that reference: sample for sample what the 64 form writes when the 8x8 luma block carries the entry.
+// One me_predict_chroma4_pass per iteration, the plane of a quad being set.base[2 * its index + component]; then me_tail_uni (WP = 0) or
+// me_tail_weight_uni with the weight of that plane (WP = 2; me_stage_weights, because the index is per lane).
+// A quad is live if its 4x4 luma block starts inside the luma picture and its index is < n_refs.  The barrier invariant is the pass's: the
+// loop has eight iterations for every group of every wave.
+template <typename SrcT, int WP>
+__global__ void __launch_bounds__(256)
+me_predict_chroma4_kernel(MeChromaSrc src, int ref_pitch, const int16_t* __restrict__ mv_field, int ctu_first, int pic_w, int pic_h, int bit_depth,
+                          uint8_t* __restrict__ dst_cb, uint8_t* __restrict__ dst_cr, int dst_pitch, MeChromaWp<1, WP> wp) {
+  static_assert(WP == 0 || WP == 2, "one weight per plane, or none");
+  __shared__ int16_t patch[16][4 * 25];
+  __shared__ int16_t mid[16][4 * 10];
+  __shared__ uint32_t taps[8];
+  __shared__ int s_weights[kMaxRefs * 4];
+  const int group = threadIdx.x >> 4, l16 = threadIdx.x & 15, comp = group & 1, lane = threadIdx.x & 63;
+  if (threadIdx.x < 8) taps[threadIdx.x] = kChromaTaps[threadIdx.x];   // read behind the first barrier
+  if constexpr (WP == 2) me_stage_weights(s_weights, wp.ref);
+  const auto [ctu, cx, cy, cu_x, cu_y] = me_pred_ctu(ctu_first, pic_w);
+  const MePredConst k(bit_depth);
+  uint8_t* const dst = comp ? dst_cr : dst_cb;
+  const int r = l16 >> 2, c = l16 & 3;
+#pragma unroll 1
+  for (int it = 0; it < 8; ++it) {
+    const int bx = (group >> 1) * 8, by = it * 8;                        // the group's 8x8 luma block: a block row per iteration
+    const int qx = bx + (c >> 1) * 4, qy = by + (r >> 1) * 4;           // this lane's 4x4 luma block inside the CTU
+    const long e = (long)ctu * 256 + (qy >> 2) * 16 + (qx >> 2);
+    const int x0 = (cu_x + bx) >> 1, y0 = (cu_y + by) >> 1;
+    int sel = src.field ? (int)src.field[e] : 0;
+    const bool live = cu_x + qx < pic_w && cu_y + qy < pic_h && sel < src.n_refs;
+    int mx = 0, my = 0;
+    if (live) me_field_mv(mv_field, e, cu_x, cu_y, pic_w, pic_h, mx, my);
+    else sel = 0;
+    const auto plane_of = [&](int from) { return src.set.base[2 * __shfl(sel, from) + comp]; };
+    const int sum = me_predict_chroma4_pass<SrcT>(live, plane_of, ref_pitch, x0, y0, mx, my, patch[group], mid[group], taps, lane, k);
+    if (live) {
+      int v;
+      if constexpr (WP == 2) v = me_tail_weight_uni(sum, me_staged_weight(s_weights, 2 * sel + comp), k.maxv);
+      else v = me_tail_uni(sum, k);
+      me_store_sample<SrcT>(dst, dst_pitch, x0 + c, y0 + r, pic_w >> 1, pic_h >> 1, v);
+    }
+  }
+}
+
 // me_predict_chroma4_kernel's sibling for a direction per 4x4 luma block (hmme_predict_chroma_bi4_device): FORM 2 of me_predict_chroma_kernel
 // from the 256 layout, unweighted.  mv_field int16 [2][n_ctu][256][2], src.field = dir_field uint8 [n_ctu][256], src.set.base[0..1] list 0's
 // Cb / Cr, [2..3] list 1's.  Groups, lanes, quads and patches are me_predict_chroma4_kernel's; list 0 and then list 1 go through the group's
 // LDS (me_predict_chroma4_pass twice: FOUR barriers per iteration).  A quad is live if its 4x4 luma block starts inside the luma picture and
 // its direction is 1, 2 or 3.  Tail per lane: me_tail_avg when both lists are used, else me_tail_uni.
-// BARRIER INVARIANT (me_predict4_kernel's): every group of every wave runs all eight iterations and meets the same four barriers in each,
-// whatever the field holds; no barrier is inside a branch, and no wave leaves the loop early.
+// The barrier invariant is the pass's: both passes of all eight iterations are met by every group of every wave, whatever the field holds.
 template <typename SrcT>
 __global__ void __launch_bounds__(256)
 me_predict_chroma_bi4_kernel(MeChromaSrc src, int ref_pitch, const int16_t* __restrict__ mv_field, int ctu_first, int pic_w, int pic_h, int bit_depth,
@@ -3877,11 +3795,11 @@ me_predict_chroma_bi4_kernel(MeChromaSrc src, int ref_pitch, const int16_t* __re
   __shared__ uint32_t taps[8];
   const int group = threadIdx.x >> 4, l16 = threadIdx.x & 15, comp = group & 1, lane = threadIdx.x & 63;
   if (threadIdx.x < 8) taps[threadIdx.x] = kChromaTaps[threadIdx.x];   // read behind the first barrier
-  const int ctus_x = (pic_w + 63) >> 6;
-  const int ctu = ctu_first + blockIdx.x;
-  const int cx = ctu % ctus_x, cy = ctu / ctus_x, cu_x = cx * 64, cu_y = cy * 64;
+  const auto [ctu, cx, cy, cu_x, cu_y] = me_pred_ctu(ctu_first, pic_w);
   const MePredConst k(bit_depth);
   uint8_t* const dst = comp ? dst_cr : dst_cb;
+  const uint8_t* const plane0 = src.set.base[comp];
+  const uint8_t* const plane1 = src.set.base[2 + comp];
   const int r = l16 >> 2, c = l16 & 3;
 #pragma unroll 1
   for (int it = 0; it < 8; ++it) {
@@ -3895,13 +3813,9 @@ me_predict_chroma_bi4_kernel(MeChromaSrc src, int ref_pitch, const int16_t* __re
     int mx0 = 0, my0 = 0, mx1 = 0, my1 = 0;
     if (use0) me_field_mv(mv_field, e, cu_x, cu_y, pic_w, pic_h, mx0, my0);
     if (use1) me_field_mv(mv_field, (long)src.n_ctu * 256 + e, cu_x, cu_y, pic_w, pic_h, mx1, my1);
-    const int sum0 = me_predict_chroma4_pass<SrcT>(use0, src.set.base[comp], ref_pitch, x0, y0, mx0, my0, patch[group], mid[group], taps, lane, k);
-    const int sum1 = me_predict_chroma4_pass<SrcT>(use1, src.set.base[2 + comp], ref_pitch, x0, y0, mx1, my1, patch[group], mid[group], taps, lane, k);
-    if (live) {
-      const int v = use0 && use1 ? me_tail_avg(sum0, sum1, k) : me_tail_uni(use0 ? sum0 : sum1, k);
-      const int x = x0 + c, y = y0 + r;
-      if (x < (pic_w >> 1) && y < (pic_h >> 1)) ((SrcT*)(dst + (long)y * dst_pitch))[x] = (SrcT)v;
-    }
+    const int sum0 = me_predict_chroma4_pass<SrcT>(use0, [=](int) { return plane0; }, ref_pitch, x0, y0, mx0, my0, patch[group], mid[group], taps, lane, k);
+    const int sum1 = me_predict_chroma4_pass<SrcT>(use1, [=](int) { return plane1; }, ref_pitch, x0, y0, mx1, my1, patch[group], mid[group], taps, lane, k);
+    if (live) me_store_sample<SrcT>(dst, dst_pitch, x0 + c, y0 + r, pic_w >> 1, pic_h >> 1, me_tail_dir(use0, use1, sum0, sum1, k));
   }
 }
 
