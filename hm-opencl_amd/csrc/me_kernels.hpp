@@ -66,9 +66,17 @@ typedef volatile __attribute__((address_space(3), aligned(4))) uint64_t lds_vu64
 // packed-u16 x4 sums never carry between halves (every partial SAD here is <= 65 280), so the packed add is
 // a plain 64-bit add (one v_lshl_add_u64, ~4.6 cycles) and the packed subtract two 32-bit subtracts
 // (v_sub_u32, ~2.7 cycles each) instead of two v_pk_*_u16 (~4.3 each)  [profiles/r01_valu_rates2_ubench.txt]
+// The two subtracts are asm, and the pair they form is opaque: written in C++, a difference that goes on into `(p << 1) + pkm` was
+// rewritten by the compiler, which cannot know that bit 31 of the low half is clear, into a borrow chain and masks (v_subb_co_u32,
+// v_subrev_co_u32, v_and_b32 0x7fffffff: 272 instructions for 64 subtracts and their 64 adds where 192 are designed).
 __device__ __forceinline__ uint64_t me_pkadd(uint64_t a, uint64_t b) { return a + b; }
 __device__ __forceinline__ uint64_t me_pksub(uint64_t a, uint64_t b) {
-  return ((uint64_t)((uint32_t)(a >> 32) - (uint32_t)(b >> 32)) << 32) | (uint64_t)((uint32_t)a - (uint32_t)b);
+  uint32_t lo, hi;
+  asm volatile("v_sub_u32 %0, %1, %2" : "=v"(lo) : "v"((uint32_t)a), "v"((uint32_t)b));
+  asm volatile("v_sub_u32 %0, %1, %2" : "=v"(hi) : "v"((uint32_t)(a >> 32)), "v"((uint32_t)(b >> 32)));
+  uint64_t r = (uint64_t)hi << 32 | lo;
+  asm volatile("" : "+v"(r));   // without it the shift of `(p << 1) + pkm` is split over the two halves again (32 v_lshlrev_b32 and as many moves)
+  return r;
 }
 
 #define ME_MAXKEY 0xFFFFFFFFu
@@ -190,7 +198,7 @@ __host__ __device__ inline bool me_task_full(int wx, int wy, int k, int it0, int
                  : "=&v"(r) : "v"((uint32_t)r##_q), "v"((uint32_t)(r##_q >> 32)), "s"(mult_a), "v"(ctag));      \
   }
 
-// Full-task twin (PK = 2, me_tree_pk3_fen1.inc): the body of the tasks whose lanes ALL lie inside the window (me_task_full) -- for the
+// Full-task twin (PK = 2, me_tree_pk4_fen1.inc): the body of the tasks whose lanes ALL lie inside the window (me_task_full) -- for the
 // 129 x 129 window the 64 lane-iterations of the 32-quad part that come before the folded one.  Their lane layout puts the two lowest
 // bits of the quad index into lane bits 5 and 4: lanes l, l ^ 16, l ^ 32, l ^ 48 hold four adjacent quads, 16 contiguous candidates of
 // one window row starting at a multiple of 16 (every part with k >= 2 starts on one).  The two butterfly levels on those lane bits then
@@ -201,6 +209,13 @@ __host__ __device__ inline bool me_task_full(int wx, int wy, int k, int it0, int
 //                         two instructions that merge one on keys
 //   ME_KEY16_LO / _HI     key = half * 1024 + ctag, one v_mad_u32_u16 per half, a quarter as many as ME_PKMIN forms.  ctag names the
 //                         16-candidate group (its first quad): me_pk_recover finds the candidate.
+// MV costs carried in the sums (tools/gen_me_tree.py Tree(1, pk=4); Tree(1, pk=3), the same body without the carry, stays there as the
+// yardstick): every lane of a full task is valid, so pkm holds four real costs, and a packed sum that contains pkm exactly once IS the
+// slot's packed cost.  The left 8x8 CUs of a 16x16 region add pkm to one leaf sum (top CU: its top-left block, bottom CU: its bottom-left
+// block); their 8x4 / 4x8 / 8x8 sums that contain that block and the region's 16x8 and 16x4 sums go into ME_PKMIN16_* as they stand --
+// 10 of the region's 24 all-rows slots pay no add of their own, for two adds of pkm.  No value exceeds what P + pkm reached: the gate and
+// every bound above stay.  The 16x8 strip a region hands to its 32x32 (two of them reach 65 280 and become keys) gives the costs back
+// with one add of npkm, the 64-bit negation of pkm: no field borrows, each holds at least its cost.
 // The four levels on lane bits 3..0 follow on keys as in every body.  Ties between groups are settled by (cost, iteration, ly, lx >> 2),
 // the raster order, as they are between quads in the other bodies: the key's lane field is ly << k | lx, not the physical lane.
 // Every lane of a full task is valid: no marker, no invalid cost in ctag, and the marker-free body's bounds hold (me_pk2_gate).
@@ -763,6 +778,14 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
         ctag = ((vy && cx < wx) ? 0u : kInvCost << kIdxBits) | tag;   // candidate 0 is valid wherever one of the four is
         if (full) ctag = tag & ~(3u << 2);                              // every lane valid; the key names the group's first quad
       }
+      // full tasks carry the MV costs in the sums (me_tree_pk4_fen1.inc); the strips that leave a 16x16 region as sums give them back
+      // with one add of the 64-bit negation: no field borrows, each holds at least its cost.  Opaque: the compiler would turn the add
+      // of a negation into a 64-bit subtract, two instructions with a borrow between them where the add is one
+      uint64_t npkm = 0;
+      if constexpr (PK == 2) {
+        npkm = 0ull - pkm;
+        asm volatile("" : "+v"(npkm));
+      }
       // lanes outside the window still run (wave-uniform code) on clamped, in-bounds addresses
       const lds_char_t* lpc = (const lds_char_t*)(win + min(cy, wy - 1) * kPDW + (min(cx, wx - 1) >> 2));
       // scalar loads complete out of order: ME8_CUR_WAIT (placed by the generator one CU after the loads, before the next CU's are
@@ -780,7 +803,7 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
       if constexpr (PK == 2) {
         static_assert(PK != 2 || FEN == 1, "the full-task body exists for FEN 1");
         if (full) {
-#include "me_tree_pk3_fen1.inc"
+#include "me_tree_pk4_fen1.inc"
         } else {
 #include "me_tree_pk_fen1.inc"
         }

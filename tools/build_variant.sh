@@ -10,7 +10,7 @@ cd $OUT
 # the same build id recipe as hm-opencl_amd/csrc/Makefile (sources + arch + the variant's flags): hmme_build_id() of a variant is its own,
 # so that a counter summary taken on a variant can never pass for the default library's (bench.py pmc_profile)
 C=$HERE/hm-opencl_amd/csrc
-ID=$( (cat $C/hmme.hip $C/me_kernels.hpp $C/me_tree_fen0.inc $C/me_tree_fen1.inc $C/me_tree_pk_fen0.inc $C/me_tree_pk_fen1.inc $C/me_tree_pk3_fen1.inc $C/me_tree16_fen0.inc $C/me_tree16_fen1.inc $C/me_slotmap.inc $C/me_slotmap3.inc; echo "gfx950 $*") | sha256sum | cut -c1-16)
+ID=$( (cat $C/hmme.hip $C/me_kernels.hpp $C/me_tree_fen0.inc $C/me_tree_fen1.inc $C/me_tree_pk_fen0.inc $C/me_tree_pk_fen1.inc $C/me_tree_pk4_fen1.inc $C/me_tree16_fen0.inc $C/me_tree16_fen1.inc $C/me_slotmap.inc $C/me_slotmap3.inc; echo "gfx950 $*") | sha256sum | cut -c1-16)
 # -save-temps like the Makefile's compile: the phased pipeline it switches on does not generate the same code as the one-step compile (the
 # one-step build of me_search_kernel<1, 0> comes out at 256 VGPRs with spills and fails tools/check_dpp_hazard.py) -- a variant must differ
 # from the default library in its -D flags only.  Temporaries in a directory of the variant's own, the ISA kept beside the library.

@@ -30,13 +30,19 @@ One *lane-iteration* of the kernel evaluates FOUR horizontally adjacent candidat
            <= 48 960; + the MV cost, me_pk2_gate).  They take PKMIN too (PKMINE where FEN halves the rows: the same 64-bit add doubles the
            even-row sums).  16x16 (65 280) keeps its keys; 32x8 and 8x32 form theirs from the packed sum of two strips (5 ops where a union
            of two keys is 4).  PK2_CLASSES holds the count that decides, class by class.
-  full-task twin (Tree(1, pk=3) -> csrc/me_tree_pk3_fen1.inc, written at every build and kept out of git; the body that the kernel's PK = 2 runs in
+  full-task twin (Tree(1, pk=3): the yardstick of the tree below and of its tests' model, no kernel includes it; for
            tasks whose lanes all lie inside the window, me_task_full): the 512 packed slots of the marker-free twin leave the lane as 16-bit
            minima, two slots to a register (PKMIN16), and take the first two butterfly levels -- lane bits 5 and 4, the two lowest bits
            of the quad index in that body's lane layout -- packed: v_permlane32_swap / v_permlane16_swap + v_pk_min_u16 merge two
            slots per register in the two instructions that merge one on keys (PMERGE).  Only then is a key formed (KEY16), for a quarter
            as many values; it names the 16-candidate group, and me_pk_recover finds the candidate.  The 81 slots with 32-bit keys go
            through the six-level butterfly as before; the body has a slot map of its own (ME_SLOT_OF3).
+  MV costs carried in the sums (Tree(1, pk=4) -> csrc/me_tree_pk4_fen1.inc, written at every build and kept out of git; the body that the kernel's
+           PK = 2 runs in full tasks): the full-task twin, but the left 8x8 CUs of every 16x16 region add the packed MV costs to ONE leaf
+           sum (PKADDM), and every all-rows sum that contains it once -- three of the CU's five, the region's 16x8 and 16x4 -- is the slot's
+           packed cost as it stands (PKMIN16M: no add).  The 16x8 strip handed to the 32x32 level gives the costs back (PKSUBM: one add of
+           the 64-bit negation).  16x12 is an 8-row half of the region + the four rows next to it (5 adds where 2 adds and 2 subtract
+           pairs were 6).  128 operations fewer per lane-iteration; emission order and slot map are the full-task twin's.
 
 The slot numbering is the reference's (TComDataCU::getIndexBlock, TComDataCU.cpp:3379-3391 and
 :4676-6461; same offsets in cl/sad.cl:200-365); FEN semantics are TEncSearch.cpp:3853-3859 +
@@ -101,11 +107,13 @@ class Tree:
     def __init__(self, fen, pk=False):
         self.fen = fen
         self.pk = pk               # the five slots of every 8x8 CU take the packed 16-bit minimum (PKMIN) instead of four 32-bit keys
-        assert pk not in (2, 3) or fen == 1, "the marker-free twin exists for FEN 1 only (FEN 0 stays on pk = 1)"
-        self.pk2 = pk2_choice() if pk in (2, 3) else {}   # pk = 2, 3: class of 16x16-level slots -> packed or not (marker-free tasks only)
-        self.pk_open = None        # pk = 3: the pair register whose high half the next packed slot fills
-        self.pend16 = {}           # pk = 3: packed butterfly level (lane bits 5, 4) -> pair register
-        self.pendk = {}            # pk = 3: key butterfly level (lane bits 3, 2, 1, 0) of the packed slots -> var
+        assert pk not in (2, 3, 4) or fen == 1, "the marker-free twin exists for FEN 1 only (FEN 0 stays on pk = 1)"
+        self.pk2 = pk2_choice() if pk in (2, 3, 4) else {}   # pk = 2, 3, 4: class of 16x16-level slots -> packed or not (marker-free tasks only)
+        self.pk16 = pk in (3, 4)   # packed slots leave the lane as 16-bit minima (PKMIN16) and take two packed butterfly levels
+        self.strips = []           # pk = 4: (value, x, y, w, h) of the all-rows 16x8 strips handed to the 32x32 level (they must carry no MV cost)
+        self.pk_open = None        # pk = 3, 4: the pair register whose high half the next packed slot fills
+        self.pend16 = {}           # pk = 3, 4: packed butterfly level (lane bits 5, 4) -> pair register
+        self.pendk = {}            # pk = 3, 4: key butterfly level (lane bits 3, 2, 1, 0) of the packed slots -> var
         self.n_key = 0             # slots (and padding) pushed into the six-level butterfly
         self.reg_slot = {}         # per-slot minimum register -> slot id
         self.ops = []
@@ -190,6 +198,19 @@ class Tree:
         self.ops.append(("PKSUB", v, a, b))
         return v
 
+    def pkaddm(self, a):
+        """a + the lane's four packed MV costs: every sum that contains the result exactly once IS a packed cost (pk = 4)"""
+        v = self.new("p")
+        self.ops.append(("PKADDM", v, a))
+        return v
+
+    def pksubm(self, a):
+        """a packed cost without its MV costs again: one add of the 64-bit negation of pkm, fieldwise exact because every field of a
+        holds at least its cost (pk = 4)"""
+        v = self.new("p")
+        self.ops.append(("PKSUBM", v, a))
+        return v
+
     def keys(self, p, fam):
         v = self.new("k")
         self.ops.append(("KEYS", v, p, fam))
@@ -211,13 +232,14 @@ class Tree:
         self.ops.append(("MIN4", r, k))
         self._push(slot, r)
 
-    def emit_pk(self, slot, p):
+    def emit_pk(self, slot, p, ready=False):
         """a slot whose packed sums exist and feed nothing as keys: the minimum over the lane's four candidates is taken on the packed
         u16 costs (sum + packed MV cost), ONE key per lane formed from it -- 4 instructions where KEYS + MIN4 are 6.  The key carries
         the candidate's iteration and lane but not which of the four it was (j = 0): the kernel recovers j from the window once per
         slot and job (me_pk_recover)"""
-        if self.pk == 3:
-            return self._emit_pk16(slot, p, 0)
+        if self.pk16:
+            return self._emit_pk16(slot, p, 0, ready)
+        assert not ready
         r = self.new("r")
         self.ops.append(("PKMIN", r, p))
         self._push(slot, r)
@@ -225,7 +247,7 @@ class Tree:
     def emit_pke(self, slot, p):
         """emit_pk for a packed EVEN-ROW sum of the tall family under FEN: the cost is 2 * sum + MV cost, and the 64-bit add that adds
         the packed MV costs shifts the sums by one on the way (every sum <= 32 640: the shift stays inside each u16 field)"""
-        if self.pk == 3:
+        if self.pk16:
             return self._emit_pk16(slot, p, 1)
         r = self.new("r")
         self.ops.append(("PKMINE", r, p))
@@ -237,14 +259,17 @@ class Tree:
     PK16_LEVELS = (("PMERGE", 2), ("PMERGE", 3))
     PKK_LEVELS = (("MERGE", 0), ("MERGE", 1), ("MERGE", 4), ("MERGE", 5))
 
-    def _emit_pk16(self, slot, p, even):
+    def _emit_pk16(self, slot, p, even, ready=False):
+        """ready: p already holds the MV costs (PKMIN16M: the minimum is taken on p itself, no add)"""
+        assert not (ready and even)
+        op = "PKMIN16M" if ready else "PKMIN16"
         self.emitted.append(slot)
         if self.pk_open is None:
             self.pk_open = self.new("h")
-            self.ops.append(("PKMIN16", self.pk_open, p, 0, even, slot))
+            self.ops.append((op, self.pk_open, p, 0, even, slot))
             return
         r, self.pk_open = self.pk_open, None
-        self.ops.append(("PKMIN16", r, p, 1, even, slot))
+        self.ops.append((op, r, p, 1, even, slot))
         self._bfly(self.pend16, r, self.PK16_LEVELS, self._keys16)
 
     def _keys16(self, r):
@@ -291,7 +316,7 @@ class Tree:
         self.pending[level] = r
 
     def flush(self):
-        while (self.n_key if self.pk == 3 else len(self.emitted)) % 64:
+        while (self.n_key if self.pk16 else len(self.emitted)) % 64:
             self._push(None, None)
         assert not self.pending and self.group == N_GROUPS
         assert self.pk_open is None and not self.pend16 and not self.pendk
@@ -380,17 +405,29 @@ class Tree:
         """the 8x8 CU of the packed-minimum tree: five packed sums (all rows, <= 64 * 255 = 16 320), five PKMIN, no key.  What the
         16x16 region above needs of them as keys (16x8, 16x4) it forms from the packed sums of two CUs (level1)"""
         (e0, a0), (e1, a1), (e2, a2), (e3, a3) = b0, b1, b2, b3
+        if self.pk == 4 and cx == 0:
+            # MV-cost carry: the left CUs of a 16x16 region add the packed MV costs to ONE leaf sum -- the top CU to its top-left block,
+            # the bottom CU to its bottom-left block -- and the three sums of the CU that contain it, and what level 1 forms from them
+            # (16x8, 16x4), are packed costs as they stand: 8 operations where 5 adds + 5 MV-cost adds are 10
+            if cy == 0:
+                a0 = self.pkaddm(a0)
+            else:
+                a2 = self.pkaddm(a2)
+            ready = {"al", "a8", "at" if cy == 0 else "ab"}
+        else:
+            ready = set()
         at, ab = self.pkadd(a0, a1), self.pkadd(a2, a3)
         al, ar = self.pkadd(a0, a2), self.pkadd(a1, a3)
         a8 = self.pkadd(at, ab)
-        self.emit_pk(slot_2NxN(8, cx8, cy8, 0), at)
-        self.emit_pk(slot_2NxN(8, cx8, cy8, 1), ab)
-        self.emit_pk(slot_Nx2N(8, cx8, cy8, 0), al)
+        self.emit_pk(slot_2NxN(8, cx8, cy8, 0), at, "at" in ready)
+        self.emit_pk(slot_2NxN(8, cx8, cy8, 1), ab, "ab" in ready)
+        self.emit_pk(slot_Nx2N(8, cx8, cy8, 0), al, "al" in ready)
         self.emit_pk(slot_Nx2N(8, cx8, cy8, 1), ar)
-        self.emit_pk(slot_2Nx2N(8, cx8, cy8), a8)
+        self.emit_pk(slot_2Nx2N(8, cx8, cy8), a8, "a8" in ready)
         out = {"a8": a8, "at": at, "ab": ab}
         if self.fen:
             ut, ub = self.pkadd(e0, e1), self.pkadd(e2, e3)
+            out["ut"], out["ub"] = ut, ub
             out["ucol"] = self.pkadd(e0, e2) if cx == 0 else self.pkadd(e1, e3)
             out["u8"] = self.pkadd(ut, ub)
         else:
@@ -403,7 +440,7 @@ class Tree:
     def level1(self, rx16, ry16, rx, ry, c, U):
         """16x16 region at region coords (rx16, ry16); (rx, ry) = position inside its 32x32"""
         S = 16
-        if self.pk in (2, 3):
+        if self.pk in (2, 3, 4):
             return self.level1_pk2(rx16, ry16, rx, ry, c, U)
         # all-rows family (h <= 8)
         if self.pk:    # no keys below: one packed add of two CUs' sums (<= 32 640) and one KEYS, 5 ops where a LIN of two keys is 4
@@ -449,30 +486,45 @@ class Tree:
         level1's (one slot map for every tree)"""
         S = 16
         assert all(self.pk2.values()), "PK2_CLASSES: a class that does not pay would keep level1's form here"
+        carry = self.pk == 4      # the left CUs' sums hold the MV costs (level0_pk): so does every sum of a left and a right CU here
         a_top, a_bot = self.pkadd(c[0]["a8"], c[1]["a8"]), self.pkadd(c[2]["a8"], c[3]["a8"])
         a_t4, a_b4 = self.pkadd(c[0]["at"], c[1]["at"]), self.pkadd(c[2]["ab"], c[3]["ab"])
-        self.emit_pk(slot_2NxN(S, rx16, ry16, 0), a_top)
-        self.emit_pk(slot_2NxN(S, rx16, ry16, 1), a_bot)
-        self.emit_pk(slot_AMP(S, rx16, ry16, 0), a_t4)                             # 16x4 top
-        self.emit_pk(slot_AMP(S, rx16, ry16, 1), a_b4)                             # 16x4 bottom
+        self.emit_pk(slot_2NxN(S, rx16, ry16, 0), a_top, carry)
+        self.emit_pk(slot_2NxN(S, rx16, ry16, 1), a_bot, carry)
+        self.emit_pk(slot_AMP(S, rx16, ry16, 0), a_t4, carry)                      # 16x4 top
+        self.emit_pk(slot_AMP(S, rx16, ry16, 1), a_b4, carry)                      # 16x4 bottom
         left, right = self.pkadd(c[0]["u8"], c[2]["u8"]), self.pkadd(c[1]["u8"], c[3]["u8"])
         u16 = self.pkadd(left, right)
-        t4, b4 = self.pkadd(c[0]["urow"], c[1]["urow"]), self.pkadd(c[2]["urow"], c[3]["urow"])
+        u16x8 = None
+        if self.pk != 4:
+            t4, b4 = self.pkadd(c[0]["urow"], c[1]["urow"]), self.pkadd(c[2]["urow"], c[3]["urow"])
         l4, r4 = self.pkadd(c[0]["ucol"], c[2]["ucol"]), self.pkadd(c[1]["ucol"], c[3]["ucol"])
         self.emit_pke(slot_Nx2N(S, rx16, ry16, 0), left)
         self.emit_pke(slot_Nx2N(S, rx16, ry16, 1), right)
         k_u16 = self.keys(u16, U)
         self.emit(slot_2Nx2N(S, rx16, ry16), k_u16)
-        self.emit_pke(slot_AMP(S, rx16, ry16, 2), self.pksub(u16, b4))             # 16x12 top
-        self.emit_pke(slot_AMP(S, rx16, ry16, 3), self.pksub(u16, t4))             # 16x12 bottom
+        if self.pk == 4:
+            # 16x12 without a subtract: an 8-row half of the region (one of the two is the strip the 32x32 level takes anyway) and the
+            # four rows next to it, 5 adds where 2 adds and 2 subtract pairs are 6
+            top8, bot8 = self.pkadd(c[0]["u8"], c[1]["u8"]), self.pkadd(c[2]["u8"], c[3]["u8"])
+            u16x8 = top8 if ry == 0 else bot8
+            self.emit_pke(slot_AMP(S, rx16, ry16, 2), self.pkadd(top8, self.pkadd(c[2]["ut"], c[3]["ut"])))   # 16x12 top
+            self.emit_pke(slot_AMP(S, rx16, ry16, 3), self.pkadd(bot8, self.pkadd(c[0]["ub"], c[1]["ub"])))   # 16x12 bottom
+        else:
+            self.emit_pke(slot_AMP(S, rx16, ry16, 2), self.pksub(u16, b4))             # 16x12 top
+            self.emit_pke(slot_AMP(S, rx16, ry16, 3), self.pksub(u16, t4))             # 16x12 bottom
         self.emit_pke(slot_AMP(S, rx16, ry16, 4), l4)                              # 4x16 left
         self.emit_pke(slot_AMP(S, rx16, ry16, 5), r4)                              # 4x16 right
         self.emit_pke(slot_AMP(S, rx16, ry16, 6), self.pksub(u16, r4))             # 12x16 left: no keys of 4x16 to take from a key
         self.emit_pke(slot_AMP(S, rx16, ry16, 7), self.pksub(u16, l4))             # 12x16 right
+        strip = a_top if ry == 0 else a_bot
+        if carry:      # two of these strips reach 65 280 at level 2 and become keys there: the MV costs leave again
+            strip = self.pksubm(strip)
+            self.strips.append((strip, rx16 * 16, ry16 * 16 + 8 * ry, 16, 8))
         return {"k_u16": k_u16,
                 "p_ucol": left if rx == 0 else right,                             # packed: level 2 adds two and forms the 8x32 keys
-                "p_a16x8": a_top if ry == 0 else a_bot,                           # packed: likewise 32x8 (all rows, <= 65 280)
-                "u16x8": self.pkadd(c[0]["u8"], c[1]["u8"]) if ry == 0 else self.pkadd(c[2]["u8"], c[3]["u8"]),
+                "p_a16x8": strip,                                                 # packed: likewise 32x8 (all rows, <= 65 280)
+                "u16x8": u16x8 or (self.pkadd(c[0]["u8"], c[1]["u8"]) if ry == 0 else self.pkadd(c[2]["u8"], c[3]["u8"])),
                 "spare": None}
 
     def level2(self, qx, qy, r, U):
@@ -486,7 +538,7 @@ class Tree:
         self.emit(slot_Nx2N(S, qx, qy, 0), k_l)
         self.emit(slot_Nx2N(S, qx, qy, 1), k_r)
         self.emit(slot_2Nx2N(S, qx, qy), k_u32)
-        if self.pk in (2, 3):   # the strips below are packed sums: one packed add (<= 65 280) and one KEYS
+        if self.pk in (2, 3, 4):   # the strips below are packed sums: one packed add (<= 65 280) and one KEYS
             self.emit(slot_AMP(S, qx, qy, 0), self.keys(self.pkadd(r[0]["p_a16x8"], r[1]["p_a16x8"]), "A"))
             self.emit(slot_AMP(S, qx, qy, 1), self.keys(self.pkadd(r[2]["p_a16x8"], r[3]["p_a16x8"]), "A"))
         else:
@@ -494,7 +546,7 @@ class Tree:
             self.emit(slot_AMP(S, qx, qy, 1), self.lin(r[2]["k_a16x8"], r[3]["k_a16x8"]))   # 32x8 bottom
         k_u32x8t = self.keys(self.pkadd_as(r[0]["spare"], r[0]["u16x8"], r[1]["u16x8"]), U)
         k_u32x8b = self.keys(self.pkadd_as(r[2]["spare"], r[2]["u16x8"], r[3]["u16x8"]), U)
-        if self.pk in (2, 3):
+        if self.pk in (2, 3, 4):
             k_u8x32l = self.keys(self.pkadd(r[0]["p_ucol"], r[2]["p_ucol"]), U)
             k_u8x32r = self.keys(self.pkadd(r[1]["p_ucol"], r[3]["p_ucol"]), U)
         else:
@@ -532,7 +584,7 @@ class Tree:
     # ---- slot map ---------------------------------------------------------------------------------
     def slot_of_lane(self):
         """[group][lane] -> slot id (or -1): lane l ends up with emission index bitrev6(l)"""
-        if self.pk == 3:
+        if self.pk16:
             return self.slot_of_lane_traced()
         t = np.full((N_GROUPS, 64), -1, np.int32)
         for g in range(N_GROUPS):
@@ -551,7 +603,7 @@ class Tree:
         for op in self.ops:
             if op[0] in ("MIN4", "PKMIN", "PKMINE", "KEYMINN"):
                 val[op[1]] = np.full(64, self.reg_slot[op[1]], np.int32)
-            elif op[0] == "PKMIN16":
+            elif op[0] in ("PKMIN16", "PKMIN16M"):
                 val.setdefault(op[1], np.full((64, 2), -1, np.int32))[:, op[3]] = op[5]
             elif op[0] == "KEY16":
                 val[op[1]] = val[op[2]][:, op[3]].copy()
@@ -739,11 +791,13 @@ HEADER_PK2 = """// GENERATED by tools/gen_me_tree.py -- do not edit.  One lane-i
 """
 
 
-HEADER_PK3 = """// GENERATED by tools/gen_me_tree.py -- do not edit.  One lane-iteration of the full-search
-// reduction tree (fen=%d), full-task twin: for tasks whose lanes all lie inside the window, in that body's lane layout (lanes l, l ^ 16,
-// l ^ 32, l ^ 48 hold 16 contiguous candidates of a row).  The packed slots of the marker-free twin leave the lane as u16 minima, two to a
-// register (ME_PKMIN16_LO / _HI), take the levels on lane bits 5 and 4 packed (me_pmerge2 / 3) and become keys afterwards (ME_KEY16_*).
-// Expects in scope what me_tree_pk_fen*.inc expects; pkm needs no marker here, ctag names the lane's 16-candidate group.
+HEADER_PK4 = """// GENERATED by tools/gen_me_tree.py -- do not edit.  One lane-iteration of the full-search
+// reduction tree (fen=%d), full-task twin with the MV costs carried in the sums: me_tree_pk3's body (Tree(1, pk=3), the generator's
+// yardstick), but the left 8x8 CUs of every 16x16 region add pkm to ONE leaf sum, and every all-rows sum that contains it once goes into
+// ME_PKMIN16_* as the packed cost it is; the 16x8 strip handed to the 32x32 level gives the costs back (+ npkm).  16x12 is an 8-row
+// half + the four rows next to it, no subtract.
+// Expects in scope what me_tree_pk_fen*.inc expects; pkm needs no marker here, npkm is its 64-bit negation, ctag names the lane's
+// 16-candidate group.
 """
 
 
@@ -762,7 +816,7 @@ MASKED_MERGE_LEVELS = (0, 1)   # the two levels done with hand-written bank-mask
 # pair's key constants are one v_lshl_add_u64 each (shift 0: the instruction only shifts by 0..4, which is why the key's shift rides on the
 # first add of two leaf sums), 6 instructions per slot where three separate candidates took 7, 2 per add where they took 3
 PAIR64 = True
-ORDERED_INSTRS = {"KEYS": 4, "LIN": 4, "SUB": 4, "MIN4": 2, "SUBMIN4": 6, "PKMIN": 3, "PKMINE": 3, "PKMIN16": 2, "KEYMINN": 1 if PAIR64 else 7}
+ORDERED_INSTRS = {"KEYS": 4, "LIN": 4, "SUB": 4, "MIN4": 2, "SUBMIN4": 6, "PKMIN": 3, "PKMINE": 3, "PKMIN16": 2, "PKMIN16M": 2, "KEYMINN": 1 if PAIR64 else 7}
 
 
 def fuse_sub_min(ops):
@@ -833,7 +887,7 @@ def space_merges(ops, enable):
         count[0] += ORDERED_INSTRS.get(op[0], 0)
         if op[0] in ("KEYS", "LIN", "SUB"):
             key_at[op[1]] = count[0]
-        if op[0] in ("MIN4", "KEYMINN", "SUBMIN4", "PKMIN", "PKMINE", "PKMIN16"):       # the ops whose result a level-0 merge reads
+        if op[0] in ("MIN4", "KEYMINN", "SUBMIN4", "PKMIN", "PKMINE", "PKMIN16", "PKMIN16M"):       # the ops whose result a level-0 merge reads
             where[op[1]] = count[0]
         out.append((op, False))
 
@@ -900,9 +954,15 @@ def emit_cpp(tree, path, header=None):
             o.append(f"ME_PKMIN({op[1]}, {op[2]});")
         elif t == "PKMINE":
             o.append(f"ME_PKMINE({op[1]}, {op[2]});")
+        elif t == "PKADDM":
+            o.append(f"const uint64_t {op[1]} = me_pkadd({op[2]}, pkm);")
+        elif t == "PKSUBM":
+            o.append(f"const uint64_t {op[1]} = me_pkadd({op[2]}, npkm);")
         elif t == "PKMIN16":
             _, r, p, half, even, slot = op
             o.append(f"ME_PKMIN16_{'HI' if half else 'LO'}({r}, {f'(({p}) << 1)' if even else f'({p})'} + pkm);")
+        elif t == "PKMIN16M":     # p is a packed cost as it stands
+            o.append(f"ME_PKMIN16_{'HI' if op[3] else 'LO'}({op[1]}, {op[2]});")
         elif t == "PMERGE":
             _, level, m, a, b = op
             o.append(f"const uint32_t {m} = me_pmerge{level}{'' if padded else '_nn'}({a}, {b});")
@@ -1063,7 +1123,8 @@ PK_COST_MAX = PK_MARKER - PK_SLOT_MAX - 1   # ... and every valid cost + sum sta
 PK2_SLOT_MAX = 16 * 12 * 255            # 48 960: 16x12 / 12x16, the largest sum a PKMIN slot of the marker-free body holds (FEN: even rows x 2)
 PK2_COST_MAX = 0xFFFF - PK2_SLOT_MAX    # 16 575: the largest MV cost with which every packed cost stays below 2^16 (me_pk2_gate)
 OPS = {"PKADD": 1, "PKSUB": 2, "KEYS": 4, "LIN": 4, "SUB": 4, "MIN4": 2, "PKMIN": 4, "PKMINE": 4,   # VALU instructions per IR op
-       "PKMIN16": 3, "KEY16": 1, "PMERGE": 2}   # full-task twin: 64-bit add + v_pk_min_u16 + v_min_u16_sdwa; one v_mad_u32_u16; swap + v_pk_min_u16
+       "PKMIN16": 3, "KEY16": 1, "PMERGE": 2,   # full-task twin: 64-bit add + v_pk_min_u16 + v_min_u16_sdwa; one v_mad_u32_u16; swap + v_pk_min_u16
+       "PKADDM": 1, "PKSUBM": 1, "PKMIN16M": 2}   # MV-cost carry: one 64-bit add of pkm / of its negation; PKMIN16 without its add
 # class -> (slots per 16x16 CU, largest cost, ops per 16x16 CU in the pk tree, ops in packed form, ops it adds above per 16x16 CU).
 # Slots whose forms depend on each other are one class: 12x16 is a key difference (whole - 4x16) only while 4x16 forms keys.
 # Above: a 32x32 forms 32x8 (all rows) and 8x32 from the strips of two regions on its edge -- a union of two keys (LIN) today, a packed
@@ -1103,18 +1164,21 @@ def valu_count(tree, isa=False):
     return valu + sum(p * m for p, m in zip(price, merges)), counts, merges
 
 
-def simulate(tree, window, cur, lane_off, c, best, pk=None):
+def simulate(tree, window, cur, lane_off, c, best, pk=None, probe=None):
     """interpret one lane-iteration.
     window: (rows, PDW*4) uint8 LDS image; cur: (64,64) uint8; lane_off[l] = byte offset of lane l's
     (row 0, dword 0) in the flattened window; c: (4, 64) uint32 per-candidate constants;
     best: (N_GROUPS, 64) uint32, updated in place.
     pk (a tree with PKMIN ops): (m, ctag) -- m (4, 64) the candidates' packed u16 MV costs (PK_MARKER where invalid), ctag (64,) uint32
-    the lane's key constant with j = 0 (and the invalid marker of the 32-bit keys where all four candidates are invalid)."""
+    the lane's key constant with j = 0 (and the invalid marker of the 32-bit keys where all four candidates are invalid).
+    probe (a dict): receives every packed value by name ("val") and how many times it contains the packed MV costs ("mvc")."""
     mult = {"A": np.uint32(MULT_A), "E": np.uint32(2 * MULT_A)}
     flat = window.reshape(-1)
     pad = np.zeros(8, np.uint8)
     flat = np.concatenate([flat, pad])
     val = {}
+    mvc = {}                  # packed value -> how many times it contains the packed MV costs (MV-cost carry, pk = 4; 0 where absent)
+    carry = tree.pk == 4      # that tree adds the MV costs to sums that sums are formed from: every packed field is held to its 16 bits
     MAXK = np.full(64, 0xFFFFFFFF, np.uint32)
 
     def bytes_at(row, k):
@@ -1138,10 +1202,25 @@ def simulate(tree, window, cur, lane_off, c, best, pk=None):
                 res = (res + val[acc]) & 0xFFFF
             val[v] = res                                                               # (64, 4) u16 values
         elif t == "PKADD":
+            assert not carry or (val[op[2]].astype(np.int64) + val[op[3]] <= 0xFFFF).all(), "a packed field left its 16 bits"
             val[op[1]] = (val[op[2]] + val[op[3]]) & 0xFFFF
+            mvc[op[1]] = mvc.get(op[2], 0) + mvc.get(op[3], 0)
         elif t == "PKSUB":
+            assert not carry or (val[op[2]] >= val[op[3]]).all(), "a packed field borrowed"
             val[op[1]] = (val[op[2]] - val[op[3]]) & 0xFFFF
+            mvc[op[1]] = mvc.get(op[2], 0) - mvc.get(op[3], 0)
+        elif t == "PKADDM":
+            q = val[op[2]].astype(np.int64) + pk[0].T.astype(np.int64)
+            assert (q <= 0xFFFF).all(), "a packed field left its 16 bits"
+            val[op[1]] = q.astype(val[op[2]].dtype)
+            mvc[op[1]] = mvc.get(op[2], 0) + 1
+        elif t == "PKSUBM":
+            # one 64-bit add of -pkm: the fields come out as their differences because none of them borrows
+            assert mvc.get(op[2], 0) == 1 and (val[op[2]].astype(np.int64) >= pk[0].T.astype(np.int64)).all(), "a field holds less than its MV cost"
+            val[op[1]] = (val[op[2]].astype(np.int64) - pk[0].T.astype(np.int64)).astype(val[op[2]].dtype)
+            mvc[op[1]] = 0
         elif t == "KEYS":
+            assert mvc.get(op[2], 0) == 0, "a key is formed from a sum: its constant brings the MV cost"
             val[op[1]] = (val[op[2]].astype(np.uint32) * mult[op[3]] + c.T).astype(np.uint32)
         elif t == "LIN":
             val[op[1]] = (val[op[2]] + val[op[3]] - c.T).astype(np.uint32)
@@ -1159,10 +1238,12 @@ def simulate(tree, window, cur, lane_off, c, best, pk=None):
             word = sum(int(1 << (16 * j)) * q[:, j].astype(object) for j in range(4))
             q = np.stack([np.array([(int(w) >> (16 * j)) & 0xFFFF for w in word], np.int64) for j in range(4)], axis=1)
             val[op[1]] = (q.min(axis=1) * MULT_A + pk[1].astype(np.int64)).astype(np.uint32)
-        elif t == "PKMIN16":
-            # full tasks only: every lane is valid, no field may overflow.  The minimum of the four u16 costs lands in one half of r
+        elif t in ("PKMIN16", "PKMIN16M"):
+            # full tasks only: every lane is valid, no field may overflow.  The minimum of the four u16 costs lands in one half of r.
+            # PKMIN16M: p holds the MV costs already (exactly once), nothing is added
             _, r, p, half, even, slot = op
-            q = (val[p].astype(np.int64) << even) + pk[0].T.astype(np.int64)
+            assert mvc.get(p, 0) == (1 if t == "PKMIN16M" else 0), "a packed cost holds the MV costs exactly once"
+            q = (val[p].astype(np.int64) << even) + (pk[0].T.astype(np.int64) if t == "PKMIN16" else 0)
             assert (q <= 0xFFFF).all(), "a packed cost left its 16 bits"
             val.setdefault(r, np.zeros((64, 2), np.int64))[:, half] = q.min(axis=1)
         elif t == "PMERGE":
@@ -1185,6 +1266,8 @@ def simulate(tree, window, cur, lane_off, c, best, pk=None):
             val[m] = np.minimum(keep, give[perm])
         elif t == "ACC":
             best[op[1]] = np.minimum(best[op[1]], val[op[2]])
+    if probe is not None:
+        probe.update(val=val, mvc=mvc)
     return best
 
 
@@ -1223,13 +1306,14 @@ def task_full(wx, wy, k, it0, n_it):
 
 
 def main():
-    names = {False: "me_tree_fen%d.inc", True: "me_tree_pk_fen%d.inc", 3: "me_tree_pk3_fen%d.inc"}
-    headers = {False: None, True: HEADER_PK, 3: HEADER_PK3}
-    label = {False: "", True: " packed minima", 2: " packed minima, marker-free", 3: " packed minima and packed swap levels, full tasks"}
+    names = {False: "me_tree_fen%d.inc", True: "me_tree_pk_fen%d.inc", 4: "me_tree_pk4_fen%d.inc"}
+    headers = {False: None, True: HEADER_PK, 4: HEADER_PK4}
+    label = {False: "", True: " packed minima", 2: " packed minima, marker-free", 3: " packed minima and packed swap levels, full tasks",
+             4: " packed minima and packed swap levels, MV costs carried in the sums, full tasks"}
     tree3 = Tree(1, 3).build()
-    for fen, pk in ((0, False), (1, False), (0, True), (1, True), (1, 2), (1, 3)):
+    for fen, pk in ((0, False), (1, False), (0, True), (1, True), (1, 2), (1, 3), (1, 4)):
         tree = tree3 if pk == 3 else Tree(fen, pk).build()
-        if pk != 2:     # the marker-free tree is the full-task twin's yardstick (and its tests' model): no kernel includes it
+        if pk not in (2, 3):     # the marker-free tree and the first full-task twin are the yardsticks of the trees after them (and their tests' models): no kernel includes them
             emit_cpp(tree, os.path.join(OUT_DIR, names[pk] % fen), headers[pk])
         # a packed add is ONE v_lshl_add_u64, a packed subtract two v_sub_u32; PKMIN = packed add of the MV costs + 3
         valu, counts, merges = valu_count(tree)
@@ -1243,6 +1327,10 @@ def main():
             print(f"fen={fen}{label[pk]}: {below} VALU instructions below the marker-free tree ({valu_count(tree, isa=True)[0]} against "
                   f"{valu_count(Tree(fen, 2).build(), isa=True)[0]} with every merge at its ISA price)")
             assert sorted(tree.slot_of_lane().ravel().tolist())[-593:] == list(range(593)), "the full-task slot map is a permutation"
+        elif pk == 4:
+            print(f"fen={fen}{label[pk]}: {valu_count(tree3)[0] - valu} VALU instructions below the full-task twin without the carry "
+                  f"({valu_count(tree, isa=True)[0]} with every merge at its ISA price; + 2 per lane-iteration for the negated MV costs)")
+            assert np.array_equal(tree3.slot_of_lane(), tree.slot_of_lane()), "the carry changes no slot's place (ME_SLOT_OF3)"
         elif pk:
             assert np.array_equal(ref_map, tree.slot_of_lane()), "the packed-minimum tree must use the same slot map"
             assert np.array_equal(ref_map, tree.slot_of_lane_traced())
