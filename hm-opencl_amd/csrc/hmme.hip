@@ -2360,9 +2360,12 @@ int launch_predict_bi(hmme_ctx* ctx, const hmme_plane* src, const uint8_t* ref0,
   const int n_ctu = hmme_num_ctus(src->width, src->height);
   with_sample_type(src->bps, [&](auto sample) {
     using T = decltype(sample);
-    if (mv_per_ctu == 256) {
-      hipLaunchKernelGGL(hmme::me_predict_bi4_kernel<T>, dim3((unsigned)count), dim3(256), 0, s, ref0, ref1, src->pitch, d_field, d_dirs, n_ctu, first, src->width,
-                         src->height, src->bit_depth, dst, dst_pitch);
+    if (mv_per_ctu == 256) {   // unweighted; pr: hmme_predict_bi_refs4_device
+      const auto go4 = [&](auto kernel, auto refs) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)count), dim3(256), 0, s, ref0, ref1, src->pitch, d_field, d_dirs, n_ctu, first, src->width, src->height, src->bit_depth, dst,
+                           dst_pitch, refs);
+      };
+      if (pr) go4(hmme::me_predict_bi4_kernel<T, 1>, *pr); else go4(hmme::me_predict_bi4_kernel<T, 0>, hmme::MePredBiRefs<0>{});
       return;
     }
     const auto go = [&](auto kernel, auto wp, auto refs) {
@@ -2471,7 +2474,10 @@ int launch_chroma(hmme_ctx* ctx, const hmme_plane* p0, const hmme::MeChromaSrc& 
       if (mv_per_ctu == 256) return go(hmme::me_predict_chroma4_kernel<T, WP>, wp);
     }
     if constexpr (FORM == 2 && WP == 0) {   // ... and hmme_predict_chroma_bi4_device (unweighted: its kernel takes no weights)
-      if (mv_per_ctu == 256) return go(hmme::me_predict_chroma_bi4_kernel<T>);
+      if (mv_per_ctu == 256) return go(hmme::me_predict_chroma_bi4_kernel<T>, wp);
+    }
+    if constexpr (FORM == 3 && WP == 0) {   // ... and hmme_predict_chroma_bi_refs4_device: the same kernel with a reference per block and list
+      if (mv_per_ctu == 256) return go(hmme::me_predict_chroma_bi4_kernel<T, 1>, wp);
     }
     if (mv_per_ctu == 1) go(hmme::me_predict_chroma_kernel<T, FORM, WP, 1>, wp); else go(hmme::me_predict_chroma_kernel<T, FORM, WP, 64>, wp);
   });
@@ -2636,11 +2642,12 @@ int check_bi_refs_weights(hmme_ctx* ctx, const char* who, const hmme_frame_param
 }
 // bi_args for the lists form
 int bi_refs_args(hmme_ctx* ctx, const char* who, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
-                 const hmme_frame_params* fp, const void* d_other_mv, const void* d_other_ref, int mv_per_ctu) {
+                 const hmme_frame_params* fp, const void* d_other_mv, const void* d_other_ref, int mv_per_ctu, bool four = false) {
   if (!cur || !refs || !others || n_refs < 1 || n_refs > hmme::kMaxRefs || n_others < 1 || n_others > hmme::kMaxRefs)
     return fail(ctx, HMME_ERR_ARG, "%s: %d / %d reference pictures outside 1..%d (or a null plane or plane list)", who, n_refs, n_others, hmme::kMaxRefs);
-  if (!d_other_mv || !d_other_ref || (mv_per_ctu != 1 && mv_per_ctu != 64))
-    return fail(ctx, HMME_ERR_ARG, "%s: null motion or reference field, or %d MVs per CTU (1 or 64)", who, mv_per_ctu);
+  // the *_bi_refs4 entries (four) are the 256 layout and nothing else; every other entry takes 1 or 64
+  if (!d_other_mv || !d_other_ref || (four ? mv_per_ctu != 256 : (mv_per_ctu != 1 && mv_per_ctu != 64)))
+    return fail(ctx, HMME_ERR_ARG, "%s: null motion or reference field, or %d MVs per CTU (%s)", who, mv_per_ctu, four ? "256" : "1 or 64");
   for (int r = 0; r < n_refs; ++r)
     if (!refs[r]) return fail(ctx, HMME_ERR_ARG, "%s: null plane", who);
   for (int r = 0; r < n_others; ++r) {
@@ -2684,10 +2691,12 @@ int bi_origin(hmme_ctx* ctx, const BiLaunch& B, int r, const PairLaunch& pl, con
   uint8_t* dst = o.dst + o.slot * k;
   *at = dst;
   if (lists && r != B.n - 1) return HMME_OK;
-  if (B.mv_per_ctu == 256) {   // the *_bi4 entries (pairs form, unweighted): the origin from one MV per 4x4 block
+  if (B.mv_per_ctu == 256) {   // the *_bi4 and *_bi_refs4 entries (unweighted): the origin from one MV per 4x4 block
     const hmme::MePred4Origin<1> org = {B.curs[k]->d_blocks, B.bw.bias[k], o.ctu_x, o.ctu_y};
-    return launch_predict4(ctx, B.others[k], one_ref(B.others[k]->origin()), 1, (const int16_t*)B.d_other_mv + (size_t)B.curs[0]->n_ctu * 512 * k, nullptr, pl.first, pl.count,
-                           dst, o.pitch, s, nullptr, &org);
+    RefSet set = one_ref(B.others[k]->origin());   // pairs: the pair's plane; lists: the planes d_other_ref chooses among, per 4x4 block
+    for (int q = 0; lists && q < B.n_others; ++q) set.base[q] = B.others[q]->origin();
+    return launch_predict4(ctx, B.others[k], set, lists ? B.n_others : 1, (const int16_t*)B.d_other_mv + (size_t)B.curs[0]->n_ctu * 512 * k,
+                           lists ? (const uint8_t*)B.d_other_ref : nullptr, pl.first, pl.count, dst, o.pitch, s, nullptr, &org);
   }
   hmme::MePredRefs<1> pr = {one_ref(nullptr), (const uint8_t*)B.d_other_ref, B.n_others};
   for (int q = 0; lists && q < B.n_others; ++q) pr.set.base[q] = B.others[q]->origin();
@@ -2776,7 +2785,7 @@ int bi_refine(hmme_ctx* ctx, const BiLaunch& B, const hmme_frame_params* fp, con
 
 // What distinguishes the sixteen entries: the name for messages, the form, explicit weights or not, search or refinement, and whether the
 // arrays are the host's (the synchronous forms).  plain: the unweighted device entry, which an all-identity call IS and answers as
-enum : unsigned { kBiLists = 1, kBiWeighted = 2, kBiRefine = 4, kBiHost = 8, kBiFour = 16 };   // kBiFour: the field is the 256 layout (pairs form, unweighted)
+enum : unsigned { kBiLists = 1, kBiWeighted = 2, kBiRefine = 4, kBiHost = 8, kBiFour = 16 };   // kBiFour: the field is the 256 layout (either form, unweighted)
 struct BiCall {
   const char* who; const char* plain; bool lists, weighted, refine, host, four;
   BiCall(const char* who_, unsigned what, const char* plain_ = nullptr)
@@ -2796,7 +2805,7 @@ int bi_checks(hmme_ctx* ctx, const BiCall& c, BiLaunch* B, const hmme_frame_para
   if (c.weighted) f->fen = 0;   // xGetSADw reads every row (TComRdCost.cpp:467-469): FEN is not consulted
   if (c.weighted && B->bw.all_identity) { B->wps = nullptr; if (!c.host) who = c.plain; }
   if (!B->wps) B->bw = BiWp::unweighted(f->bit_depth);
-  return c.lists ? bi_refs_args(ctx, who, B->cur, B->refs, B->n, B->others, B->n_others, f, B->d_other_mv, B->d_other_ref, B->mv_per_ctu)
+  return c.lists ? bi_refs_args(ctx, who, B->cur, B->refs, B->n, B->others, B->n_others, f, B->d_other_mv, B->d_other_ref, B->mv_per_ctu, c.four)
                  : bi_args(ctx, who, B->curs, B->refs, B->others, B->n, f, B->d_other_mv, B->mv_per_ctu, c.four);
 }
 
@@ -2996,6 +3005,41 @@ int hmme_refine_frame_bi_refs_w(hmme_ctx* ctx, const hmme_plane* cur, const hmme
                  nullptr);
 }
 
+// ... and from one MV and one reference index per 4x4 block (the rule: include/hmme.h, "B pictures with several references per list from one MV
+// per 4x4 block"): unweighted, the 256 layout and nothing else; every refusal names the entry
+int hmme_search_frame_bi_refs4_device(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others,
+                                      int n_others, const hmme_frame_params* fp, const void* d_other_mv, const void* d_other_ref, const void* d_center_q,
+                                      const void* d_pred_q, void* d_out_mv, void* d_out_sad, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  return named(ctx, "hmme_search_frame_bi_refs4_device", bi_call(ctx, BiCall("hmme_search_frame_bi_refs4_device", kBiLists | kBiFour),
+                 {nullptr, cur, refs, n_refs, others, n_others, d_other_mv, d_other_ref, 256}, fp, nullptr, d_center_q, d_pred_q, nullptr, 0, d_out_mv, d_out_sad, stream));
+}
+
+int hmme_refine_frame_bi_refs4_device(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others,
+                                      int n_others, const hmme_frame_params* fp, const void* d_other_mv, const void* d_other_ref, const void* d_center_q,
+                                      const void* d_pred_q, const void* d_int_mv, int use_hadamard, void* d_out_qmv, void* d_out_cost, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  return named(ctx, "hmme_refine_frame_bi_refs4_device", bi_call(ctx, BiCall("hmme_refine_frame_bi_refs4_device", kBiLists | kBiFour | kBiRefine),
+                 {nullptr, cur, refs, n_refs, others, n_others, d_other_mv, d_other_ref, 256}, fp, nullptr, d_center_q, d_pred_q, d_int_mv, use_hadamard, d_out_qmv, d_out_cost,
+                 stream));
+}
+
+int hmme_search_frame_bi_refs4(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
+                               const hmme_frame_params* fp, const int16_t* other_mv, const uint8_t* other_ref, const int16_t* center_q, const int16_t* pred_q,
+                               int16_t* out_mv, uint32_t* out_sad) {
+  if (!ctx) return HMME_ERR_ARG;
+  return named(ctx, "hmme_search_frame_bi_refs4", bi_call(ctx, BiCall("hmme_search_frame_bi_refs4", kBiLists | kBiFour | kBiHost),
+                 {nullptr, cur, refs, n_refs, others, n_others, other_mv, other_ref, 256}, fp, nullptr, center_q, pred_q, nullptr, 0, out_mv, out_sad, nullptr));
+}
+
+int hmme_refine_frame_bi_refs4(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
+                               const hmme_frame_params* fp, const int16_t* other_mv, const uint8_t* other_ref, const int16_t* center_q, const int16_t* pred_q,
+                               const int16_t* int_mv, int use_hadamard, int16_t* out_qmv, uint32_t* out_cost) {
+  if (!ctx) return HMME_ERR_ARG;
+  return named(ctx, "hmme_refine_frame_bi_refs4", bi_call(ctx, BiCall("hmme_refine_frame_bi_refs4", kBiLists | kBiFour | kBiRefine | kBiHost),
+                 {nullptr, cur, refs, n_refs, others, n_others, other_mv, other_ref, 256}, fp, nullptr, center_q, pred_q, int_mv, use_hadamard, out_qmv, out_cost, nullptr));
+}
+
 // ---- the selection calls: partition decision and motion field from the 593-slot tables, over one table set per picture pair
 // (hmme_select_pairs_device / _frame), the references of a picture (hmme_select_refs_*), the two lists of a B picture (hmme_select_dirs_*)
 // and the references of its two lists (hmme_select_dirs_refs_*).  Every entry fills in a SelectCall; select_device checks and launches it,
@@ -3053,8 +3097,8 @@ int select_dirs_eval(const hmme_select_params* sel, int n_pics, const hmme_dir_p
   }
   return HMME_OK;
 }
-int select_dirs_refs_eval(const hmme_select_params* sel, int n_pics, int n_refs_max, const hmme_dir_refs_params* dirs, char* msg, size_t cap) {
-  const int bad = select_bi_eval(sel, n_pics, dirs, msg, cap);
+int select_dirs_refs_eval(const hmme_select_params* sel, int n_pics, int n_refs_max, const hmme_dir_refs_params* dirs, char* msg, size_t cap, int per = 64) {
+  const int bad = select_bi_eval(sel, n_pics, dirs, msg, cap, per);
   if (bad) return bad;
   if (n_refs_max < 1 || n_refs_max > hmme::kMaxDirRefs) { snprintf(msg, cap, "%d table sets per list outside 1..%d", n_refs_max, hmme::kMaxDirRefs); return HMME_ERR_ARG; }
   for (int p = 0; p < n_pics; ++p) {
@@ -3072,7 +3116,8 @@ int select_dirs_refs_eval(const hmme_select_params* sel, int n_pics, int n_refs_
 }
 
 // One selection call, device or host form.  The buffers in the order they are checked: the family's own, then the ones every family has
-enum SelectFamily { kSelectTable, kSelectRefs, kSelectDirs, kSelectDirsRefs, kSelectDirs4 };   // kSelectDirs4: kSelectDirs at one MV per 4x4 block
+// kSelectDirs4 / kSelectDirsRefs4: kSelectDirs / kSelectDirsRefs at one MV per 4x4 block
+enum SelectFamily { kSelectTable, kSelectRefs, kSelectDirs, kSelectDirsRefs, kSelectDirs4, kSelectDirsRefs4 };
 enum SelectBufName { kMvBi, kCostBi, kUniField, kUniRef, kOutRef, kOutDir, kMv, kCost, kPredQ, kOutField, kOutSlot, kOutCost, kSelectBufs };
 enum SelectRole { kInTable, kInPicture, kOut };   // an input over the CTUs of the range / of the picture; an output (of the picture: the range is written)
 struct SelectBuf {
@@ -3093,22 +3138,23 @@ struct SelectCall {
   const hmme_select_params* sel;
   const uint32_t* ref_cost = nullptr;                // kSelectRefs (null: zeros)
   const hmme_dir_params* dirs = nullptr;             // kSelectDirs, kSelectDirs4
-  const hmme_dir_refs_params* dir_refs = nullptr;    // kSelectDirsRefs
+  const hmme_dir_refs_params* dir_refs = nullptr;    // kSelectDirsRefs, kSelectDirsRefs4
   SelectBuf buf[kSelectBufs];
   SelectCall(const char* who, SelectFamily family, int width, int height, int n_pics, int n_refs, const hmme_frame_params* fp, const hmme_select_params* sel)
       : who(who), family(family), width(width), height(height), n_pics(n_pics), n_refs(n_refs), fp(fp), sel(sel) {
-    const bool refs = family == kSelectRefs, bi = family >= kSelectDirs, multi = family == kSelectDirsRefs;
+    const bool refs = family == kSelectRefs, bi = family >= kSelectDirs, multi = family == kSelectDirsRefs || family == kSelectDirsRefs4;
+    const bool four = family == kSelectDirs4 || family == kSelectDirsRefs4;
     // (sizes matter to select_host alone, behind the evaluation of sel and n_refs)
     const size_t per = sel ? (size_t)sel->mv_per_ctu : 0, row = HMME_NUM_CTU_PARTS * 4, none = 0, one = 1, lists = bi ? 2 : 1;
     const size_t sets = refs ? (size_t)n_refs : multi ? 2 * (size_t)n_refs : lists;
-    const size_t bper = family == kSelectDirs4 ? 256 : 64;   // blocks per CTU of a B-picture decision's own buffers
+    const size_t bper = four ? 256 : 64;   // blocks per CTU of a B-picture decision's own buffers
     const SelectBuf all[kSelectBufs] = {
         {"bi MV table", kInTable, row, bi ? sets : none, 4, true, nullptr},
         {"bi cost table", kInTable, row, bi ? sets : none, 4, true, nullptr},
         {"input field", kInPicture, bper * 4, bi ? lists : none, 4, true, nullptr},
-        {"input reference", kInPicture, 64, multi ? lists : none, 1, true, nullptr},
-        {"reference", kOut, refs ? per : 64, refs ? one : multi ? lists : none, refs ? 2u : 1u, true, nullptr},   // with four MVs per 8x8 block the kernel stores two indices at a time
-        {"direction", kOut, bper, bi ? one : none, multi ? 1u : 2u, true, nullptr},   // kSelectDirs4: two directions per store
+        {"input reference", kInPicture, bper, multi ? lists : none, 1, true, nullptr},
+        {"reference", kOut, refs ? per : bper, refs ? one : multi ? lists : none, refs || four ? 2u : 1u, true, nullptr},   // with four MVs per 8x8 block the kernel stores two indices at a time
+        {"direction", kOut, bper, bi ? one : none, multi && !four ? 1u : 2u, true, nullptr},   // kSelectDirs4, kSelectDirsRefs4: two directions per store
         {"MV table", kInTable, row, sets, 4, true, nullptr},   // the kernels move MVs as dwords
         {"cost table", kInTable, row, sets, 4, true, nullptr},
         {"predictor", kInPicture, 4, sets, 2, false, nullptr},
@@ -3139,6 +3185,7 @@ int select_check(hmme_ctx* ctx, const SelectCall& c, bool device, int* n_ctu, in
   if (c.family == kSelectDirs) bad = select_dirs_eval(c.sel, c.n_pics, c.dirs, msg, sizeof msg);
   else if (c.family == kSelectDirs4) bad = select_dirs_eval(c.sel, c.n_pics, c.dirs, msg, sizeof msg, 256);
   else if (c.family == kSelectDirsRefs) bad = select_dirs_refs_eval(c.sel, c.n_pics, c.n_refs, c.dir_refs, msg, sizeof msg);
+  else if (c.family == kSelectDirsRefs4) bad = select_dirs_refs_eval(c.sel, c.n_pics, c.n_refs, c.dir_refs, msg, sizeof msg, 256);
   else bad = select_refs_eval(c.sel, c.n_pics, c.n_refs, c.ref_cost, msg, sizeof msg);
   if (bad) return fail(ctx, bad, "%s: %s", c.who, msg);
   if ((bad = buffers(0, kMv))) return bad;   // the family's own buffers, then the frame and the buffers every family has
@@ -3186,9 +3233,11 @@ int select_device(hmme_ctx* ctx, const SelectCall& c, hipStream_t stream) {
   } else {
     hmme::MeDirRefsParams bits = {};
     memcpy(bits.p, c.dir_refs, c.n_pics * sizeof *c.dir_refs);
-    hipLaunchKernelGGL(hmme::me_select_dirs_refs_kernel, grid, block, 0, stream, tab(kMv), tab(kCost), tab(kMvBi), tab(kCostBi), tab(kUniField),
-                       (const uint8_t*)bytes(kUniRef), pred_q, out_field, bytes(kOutRef), bytes(kOutDir), out_slot, out_cost, a, bits, c.n_refs, c.width, c.height, n_ctu, first, count,
-                       ctx->lambda_q16);
+    const auto go = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, grid, block, 0, stream, tab(kMv), tab(kCost), tab(kMvBi), tab(kCostBi), tab(kUniField), (const uint8_t*)bytes(kUniRef), pred_q, out_field,
+                         bytes(kOutRef), bytes(kOutDir), out_slot, out_cost, a, bits, c.n_refs, c.width, c.height, n_ctu, first, count, ctx->lambda_q16);
+    };
+    if (c.family == kSelectDirsRefs4) go(hmme::me_select_dirs_refs_kernel<true>); else go(hmme::me_select_dirs_refs_kernel<false>);
   }
   HIP_TRY(ctx, hipGetLastError());
   return HMME_OK;
@@ -3544,6 +3593,36 @@ int hmme_select_dirs_refs_frame(hmme_ctx* ctx, int width, int height, int n_refs
                          .with(kOutField, out_field).with(kOutRef, out_ref).with(kOutDir, out_dir).with(kOutSlot, out_slot).with(kOutCost, out_cost));
 }
 
+// ... at one MV per 4x4 block: all 593 slots, with HM's isBipredRestriction (the rule: include/hmme.h, "B pictures with several references per
+// list from one MV per 4x4 block"); every refusal names the entry, the CTU range's too
+int hmme_select_dirs_refs4_check(const hmme_select_params* sel, int n_pics, int n_refs_max, const hmme_dir_refs_params* dirs) {
+  char msg[256];
+  return select_dirs_refs_eval(sel, n_pics, n_refs_max, dirs, msg, sizeof msg, 256);
+}
+
+int hmme_select_dirs_refs4_device(hmme_ctx* ctx, int width, int height, int n_pics, int n_refs_max, const hmme_frame_params* fp, const hmme_select_params* sel,
+                                  const hmme_dir_refs_params* dirs, const void* d_mv_uni, const void* d_cost_uni, const void* d_mv_bi, const void* d_cost_bi,
+                                  const void* d_uni_field, const void* d_uni_ref, const void* d_pred_q, void* d_out_field, void* d_out_ref, void* d_out_dir,
+                                  void* d_out_slot, void* d_out_cost, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  return named(ctx, "hmme_select_dirs_refs4_device",
+               select_device(ctx, SelectCall("hmme_select_dirs_refs4_device", kSelectDirsRefs4, width, height, n_pics, n_refs_max, fp, sel).with(dirs).with(kMv, d_mv_uni)
+                                      .with(kCost, d_cost_uni).with(kMvBi, d_mv_bi).with(kCostBi, d_cost_bi).with(kUniField, d_uni_field).with(kUniRef, d_uni_ref)
+                                      .with(kPredQ, d_pred_q).with(kOutField, d_out_field).with(kOutRef, d_out_ref).with(kOutDir, d_out_dir).with(kOutSlot, d_out_slot)
+                                      .with(kOutCost, d_out_cost), (hipStream_t)stream));
+}
+
+int hmme_select_dirs_refs4_frame(hmme_ctx* ctx, int width, int height, int n_refs_max, const hmme_frame_params* fp, const hmme_select_params* sel,
+                                 const hmme_dir_refs_params* dir, const int16_t* mv_uni, const uint32_t* cost_uni, const int16_t* mv_bi, const uint32_t* cost_bi,
+                                 const int16_t* uni_field, const uint8_t* uni_ref, const int16_t* pred_q, int16_t* out_field, uint8_t* out_ref, uint8_t* out_dir,
+                                 uint16_t* out_slot, uint32_t* out_cost) {
+  if (!ctx) return HMME_ERR_ARG;
+  return named(ctx, "hmme_select_dirs_refs4_frame",
+               select_host(ctx, SelectCall("hmme_select_dirs_refs4_frame", kSelectDirsRefs4, width, height, 1, n_refs_max, fp, sel).with(dir).with(kMv, mv_uni)
+                                    .with(kCost, cost_uni).with(kMvBi, mv_bi).with(kCostBi, cost_bi).with(kUniField, uni_field).with(kUniRef, uni_ref).with(kPredQ, pred_q)
+                                    .with(kOutField, out_field).with(kOutRef, out_ref).with(kOutDir, out_dir).with(kOutSlot, out_slot).with(kOutCost, out_cost)));
+}
+
 namespace {
 // every picture's two weights before anything is launched; the message names the picture
 int check_predict_bi_weights(hmme_ctx* ctx, const char* who, const hmme_frame_params* fp, const hmme_weight* wps0, const hmme_weight* wps1, int n_pics, PredBiWp* bw) {
@@ -3762,9 +3841,11 @@ int bi_refs_counts(hmme_ctx* ctx, const char* who, const void* refs0, int n0, co
 // after the other (each up to 16 planes), list 1 against list 0's first plane for the size.  4:2:0 (comps == 2; refs_l: (Cb, Cr) per reference):
 // me_predict_chroma_kernel<T, 3, 0 | 2, PER> with list 0's planes, then list 1's, in one set.  weighted: the weights answer first; WP = 0
 // without weights and where every weight is the identity, else every block goes through the weighted tails.
+// four: hmme_predict_bi_refs4_device and hmme_predict_chroma_bi_refs4_device -- mv_per_ctu is 256, no weights; launch_predict_bi and
+// launch_chroma then pick me_predict_bi4_kernel<T, 1> and me_predict_chroma_bi4_kernel<T, 1>.
 int predict_bi_refs(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, int comps, int width, int height,
                     const hmme_frame_params* fp, const hmme_weight* wps0, const hmme_weight* wps1, bool weighted, const void* d_mv_field, const void* d_dir_field,
-                    const void* d_ref_field, int mv_per_ctu, void* d_out, void* d_out_cr, int out_pitch_bytes, void* stream) {
+                    const void* d_ref_field, int mv_per_ctu, void* d_out, void* d_out_cr, int out_pitch_bytes, void* stream, bool four = false) {
   PredBiRefsWp bw[2];
   int rc = weighted ? check_predict_bi_refs_weights(ctx, who, fp, wps0, n0, wps1, n1, comps, bw) : HMME_OK;
   if (rc == HMME_OK) rc = bi_check(ctx, who, fp, 0);
@@ -3779,7 +3860,7 @@ int predict_bi_refs(hmme_ctx* ctx, const char* who, const hmme_plane* const* ref
     const hmme_plane* planes[hmme::kMaxRefs];   // list 0's (Cb, Cr) pairs, then list 1's: the kernel's set
     for (int r = 0; r < 2 * n0; ++r) planes[r] = refs0[r];
     for (int r = 0; r < 2 * n1; ++r) planes[2 * n0 + r] = refs1[r];
-    rc = predict_args(ctx, who, planes, np, null_arg, fp, nullptr, d_mv_field, mv_per_ctu, out_pitch_bytes, &a, "plane");
+    rc = predict_args(ctx, who, planes, np, null_arg, fp, nullptr, d_mv_field, mv_per_ctu, out_pitch_bytes, &a, "plane", four);
     if (rc) return rc;
     rc = predict_begin(ctx, who, planes, np, 2, width, height, fp, a, s, &L);
     if (rc || !L.acquired) return rc;
@@ -3801,7 +3882,7 @@ int predict_bi_refs(hmme_ctx* ctx, const char* who, const hmme_plane* const* ref
     }
     return pairs_end(ctx, planes, planes, np, s, rc);   // whatever the launch returned: the scratch is acquired
   }
-  rc = predict_args(ctx, who, refs0, n0, null_arg, fp, nullptr, d_mv_field, mv_per_ctu, out_pitch_bytes, &a, "reference");
+  rc = predict_args(ctx, who, refs0, n0, null_arg, fp, nullptr, d_mv_field, mv_per_ctu, out_pitch_bytes, &a, "reference", four);
   if (rc) return rc;
   const hmme_plane* first0[hmme::kMaxRefs];
   for (int r = 0; r < n1; ++r) {
@@ -3829,7 +3910,7 @@ int predict_bi_refs(hmme_ctx* ctx, const char* who, const hmme_plane* const* ref
 // the _frame forms of the three; refs_l: `comps` planes per reference, outs: `comps` images.  The weights answer first.
 int predict_bi_refs_frame(hmme_ctx* ctx, const char* who, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, int comps, int width, int height,
                           const hmme_frame_params* fp, const hmme_weight* wps0, const hmme_weight* wps1, bool weighted, const int16_t* mv_field, const uint8_t* dir_field,
-                          const uint8_t* ref_field, int mv_per_ctu, void* const* outs, int out_stride) {
+                          const uint8_t* ref_field, int mv_per_ctu, void* const* outs, int out_stride, bool four = false) {
   int rc = weighted ? check_predict_bi_refs_weights(ctx, who, fp, wps0, n0, wps1, n1, comps, nullptr) : HMME_OK;   // before anything is staged
   if (rc == HMME_OK) rc = bi_check(ctx, who, fp, 0);
   if (rc) return rc;
@@ -3838,8 +3919,8 @@ int predict_bi_refs_frame(hmme_ctx* ctx, const char* who, const hmme_plane* cons
     rc = fail(ctx, HMME_ERR_ARG, "%s: %d / %d reference pictures outside 1..%d (or a null plane)", who, n0, n1, hmme::kMaxRefs);
   if (rc) return rc;
   if (comps == 2 && !refs0[0]) return fail(ctx, HMME_ERR_ARG, "%s: null plane", who);
-  rc = frame_args(ctx, who, fp, refs0, comps * n0, comps, !mv_field || !dir_field || !ref_field || frame_null_outs(outs, comps), mv_per_ctu, width, height);
-  if (rc == HMME_OK) rc = frame_args(ctx, who, fp, refs1, comps * n1, comps, false, mv_per_ctu, width, height);
+  rc = frame_args(ctx, who, fp, refs0, comps * n0, comps, !mv_field || !dir_field || !ref_field || frame_null_outs(outs, comps), mv_per_ctu, width, height, four);
+  if (rc == HMME_OK) rc = frame_args(ctx, who, fp, refs1, comps * n1, comps, false, mv_per_ctu, width, height, four);
   if (rc) return rc;
   const hmme_plane* p0 = refs0[0];
   if (p0->ctx != ctx) return fail(ctx, HMME_ERR_ARG, "%s: plane belongs to another context (planes are used with the context that created them)", who);
@@ -3853,7 +3934,7 @@ int predict_bi_refs_frame(hmme_ctx* ctx, const char* who, const hmme_plane* cons
   rc = st.begin();
   if (rc == HMME_OK)
     rc = predict_bi_refs(ctx, who, refs0, n0, refs1, n1, comps, width, height, fp, wps0, wps1, weighted, st.at(field), st.at(dirs), st.at(rfield), mv_per_ctu, st.at(img),
-                         st.at(img1), (int)row, ctx->stream);
+                         st.at(img1), (int)row, ctx->stream, four);
   return rc ? rc : st.end();
 }
 }  // namespace
@@ -3909,6 +3990,38 @@ int hmme_predict_chroma_bi_refs_frame(hmme_ctx* ctx, const hmme_plane* const* re
   if (!ctx) return HMME_ERR_ARG;
   return predict_bi_refs_frame(ctx, "hmme_predict_chroma_bi_refs_frame", refs0, n0, refs1, n1, 2, width, height, fp, wps0, wps1, wps0 || wps1, mv_field, dir_field, ref_field,
                                mv_per_ctu, outs, out_stride);
+}
+
+// ... from one (direction, MV0, MV1, ref0, ref1) per 4x4 block, unweighted, for Y and for the Cb / Cr of a 4:2:0 picture (me_predict_bi4_kernel<T, 1>,
+// me_predict_chroma_bi4_kernel<T, 1>; the rule: include/hmme.h, "B pictures with several references per list from one MV per 4x4 block")
+int hmme_predict_bi_refs4_device(hmme_ctx* ctx, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, const hmme_frame_params* fp,
+                                 const void* d_mv_field, const void* d_dir_field, const void* d_ref_field, void* d_out, int out_pitch_bytes, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  return named(ctx, "hmme_predict_bi_refs4_device", predict_bi_refs(ctx, "hmme_predict_bi_refs4_device", refs0, n0, refs1, n1, 1, 0, 0, fp, nullptr, nullptr, false, d_mv_field,
+                                                                    d_dir_field, d_ref_field, 256, d_out, nullptr, out_pitch_bytes, stream, true));
+}
+
+int hmme_predict_bi_refs4_frame(hmme_ctx* ctx, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, const hmme_frame_params* fp,
+                                const int16_t* mv_field, const uint8_t* dir_field, const uint8_t* ref_field, void* out, int out_stride) {
+  if (!ctx) return HMME_ERR_ARG;
+  return named(ctx, "hmme_predict_bi_refs4_frame", predict_bi_refs_frame(ctx, "hmme_predict_bi_refs4_frame", refs0, n0, refs1, n1, 1, 0, 0, fp, nullptr, nullptr, false, mv_field,
+                                                                         dir_field, ref_field, 256, &out, out_stride, true));
+}
+
+int hmme_predict_chroma_bi_refs4_device(hmme_ctx* ctx, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, int width, int height,
+                                        const hmme_frame_params* fp, const void* d_mv_field, const void* d_dir_field, const void* d_ref_field, void* d_out_cb,
+                                        void* d_out_cr, int out_pitch_bytes, void* stream) {
+  if (!ctx) return HMME_ERR_ARG;
+  return named(ctx, "hmme_predict_chroma_bi_refs4_device", predict_bi_refs(ctx, "hmme_predict_chroma_bi_refs4_device", refs0, n0, refs1, n1, 2, width, height, fp, nullptr, nullptr,
+                                                                           false, d_mv_field, d_dir_field, d_ref_field, 256, d_out_cb, d_out_cr, out_pitch_bytes, stream, true));
+}
+
+int hmme_predict_chroma_bi_refs4_frame(hmme_ctx* ctx, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, int width, int height,
+                                       const hmme_frame_params* fp, const int16_t* mv_field, const uint8_t* dir_field, const uint8_t* ref_field, void* const* outs,
+                                       int out_stride) {
+  if (!ctx) return HMME_ERR_ARG;
+  return named(ctx, "hmme_predict_chroma_bi_refs4_frame", predict_bi_refs_frame(ctx, "hmme_predict_chroma_bi_refs4_frame", refs0, n0, refs1, n1, 2, width, height, fp, nullptr,
+                                                                                nullptr, false, mv_field, dir_field, ref_field, 256, outs, out_stride, true));
 }
 
 // ---- 4:2:0 chroma motion compensation from the luma motion fields ------------------------------------------------------------------------------

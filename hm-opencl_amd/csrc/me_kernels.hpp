@@ -2711,7 +2711,9 @@ __device__ __forceinline__ int me_predict4_pass(bool live, PlaneOf plane_of, int
 // write nothing.  The barrier invariant is the pass's: the loop has 16 iterations for every wave.
 //   OUT = 0: the prediction, as described above.  Takes an empty MePred4Origin and compiles to what it did without the parameter.
 //   OUT = 1: the bi-prediction origin 2 * cur - pred + bias as u16 from a 4x4 field (hmme_search_pairs_bi4_device / hmme_refine_pairs_bi4_device;
-//            WP = 0 only, and the callers pass n_refs = 1 with a null ref_field), as me_predict_kernel<SrcT, 1> forms it from a 64 field:
+//            WP = 0 only, n_refs = 1 with a null ref_field; hmme_search_frame_bi_refs4_device / hmme_refine_frame_bi_refs4_device: the other
+//            list's set, count and reference field, an index >= n_refs -- 0xFF beyond the picture edge -- clamped to 0 per lane before the
+//            readlane plane lookup, so that every quadrant reads a plane of the set), as me_predict_kernel<SrcT, 1> forms it from a 64 field:
 //            EVERY quadrant is live, those beyond the picture edge included, cur comes from the current picture's CTU-blocked copy, and the
 //            block of CTU (cx, cy) starts at dst + cy * ctu_y + cx * ctu_x with rows dst_pitch bytes apart (the search's CTU blocks or the
 //            refinement's padded plane).  Liveness no longer depends on the field, so the barrier invariant holds as it did.
@@ -2909,8 +2911,9 @@ struct MeSelectOut {
 
 // The decision over the CTU's slots in LDS and the stores that follow it: what every select kernel ends in.  Outside kSelTable the MV cost
 // is inside the merged cost already -- against each reference's own predictor -- and is not priced a second time.
-// FOUR (kSelDirs only): the caller is me_select_dirs_kernel<true>, whose a.per is 256 -- the direction stores of the 256 layout exist in
-// that instantiation alone, so that every other one keeps the instructions it had.
+// FOUR (kSelDirs, kSelDirsRefs): the caller is me_select_dirs_kernel<true> or me_select_dirs_refs_kernel<true>, whose a.per is 256 -- the
+// direction stores of the 256 layout (with kSelDirsRefs: and the per-list reference bytes, as paired 16-bit stores beside the uint2 field
+// stores) exist in those instantiations alone, so that every other one keeps the instructions it had.
 template <MeSelectMode MODE, typename CostT, bool FOUR = false>
 __device__ __forceinline__ void me_select_decide_store(const MeSelect& params, const MeSelectSlots<CostT>& s, const MeSelectOut& out, const MeSelectWave& w,
                                                        uint32_t lambda_q16, int pred_x, int pred_y, int pic_w, int pic_h, int n_ctu) {
@@ -2931,7 +2934,7 @@ __device__ __forceinline__ void me_select_decide_store(const MeSelect& params, c
     const uint32_t m = s.mv[slot];
     return a.mv_unit ? (m << 2) & 0xfffcfffcu : m;
   };
-  static_assert(!FOUR || MODE == kSelDirs, "several references per list: one MV per 8x8 block only");
+  static_assert(!FOUR || DIRS, "the direction stores of the 256 layout: a B-picture decision");
   if (!FOUR && a.per == 64) {
     const int slot = st.leaf_depth < 0 ? 0xffff : me_select_pu_slot_at(st.leaf_depth, st.leaf_ps, bx * 8, by * 8);
     if constexpr (DIRS) {   // (one MV per 4x4 block: the kSelDirs branch further down)
@@ -2968,9 +2971,10 @@ __device__ __forceinline__ void me_select_decide_store(const MeSelect& params, c
         if constexpr (REFS) ref[i] = slot[i] == 0xffff ? 0xffu : (uint32_t)s.ref[slot[i]];
       }
       const long e = o * 256 + (2 * by + j) * 16 + 2 * bx;   // even: 8-byte (MVs) / 4-byte (slots) / 2-byte (references, directions) aligned pairs
-      if constexpr (FOUR) {   // hmme_select_dirs4_device: the 64 branch above per 4x4 block, with the paired stores of REFS
+      if constexpr (FOUR) {   // hmme_select_dirs4_device, hmme_select_dirs_refs4_device: the 64 branch above per 4x4 block, with the paired stores of REFS
         const long lists = (long)n_ctu * 256, e0 = 2 * w.pic * lists + (long)w.ctu * 256 + (2 * by + j) * 16 + 2 * bx;   // the pair in list 0 of its picture
         uint32_t f[2][2], dirs[2];
+        [[maybe_unused]] uint32_t rl[2][2];   // LREFS: the reference index of each list
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
           const int d = slot[i] == 0xffff ? 0 : (int)s.dir[slot[i]];
@@ -2982,10 +2986,20 @@ __device__ __forceinline__ void me_select_decide_store(const MeSelect& params, c
           f[0][i] = wl == 0 ? mv[i] : other;
           f[1][i] = wl == 1 ? mv[i] : other;
           dirs[i] = dir ? (uint32_t)dir : 0xffu;
+          if constexpr (LREFS) {   // hmme_select_dirs_refs4_device: the indices travel with the MVs -- the block's own entry of uni_ref, else 0xFF
+            const uint32_t own = dir ? (uint32_t)s.lref[wl * (kParts + 3) + slot[i]] : 0xffu;
+            const uint32_t other_ref = dir == 3 ? (uint32_t)out.uni_ref[e0 + i + (1 - bl) * lists] : 0xffu;
+            rl[0][i] = wl == 0 ? own : other_ref;
+            rl[1][i] = wl == 1 ? own : other_ref;
+          }
         }
         *(uint2*)(out.field + e0) = make_uint2(f[0][0], f[0][1]);
         *(uint2*)(out.field + e0 + lists) = make_uint2(f[1][0], f[1][1]);
         *(uint16_t*)(out.dir + e) = (uint16_t)(dirs[0] | dirs[1] << 8);
+        if constexpr (LREFS) {
+          *(uint16_t*)(out.ref + e0) = (uint16_t)(rl[0][0] | rl[0][1] << 8);
+          *(uint16_t*)(out.ref + e0 + lists) = (uint16_t)(rl[1][0] | rl[1][1] << 8);
+        }
       } else {
         *(uint2*)(out.field + e) = make_uint2(mv[0], mv[1]);
       }
@@ -3166,6 +3180,13 @@ me_select_dirs_kernel(const uint32_t* __restrict__ mv_uni, const uint32_t* __res
 // minimum (:3226).  Predictors and bit counts are wave-uniform; no LDS traffic, no atomic and no cross-lane step in the reference loops.
 // The two reference indices per slot go to LDS on top of the sibling's (35.8 KB per workgroup).  uni_ref / out_ref: uint8
 // [n_pics][2][n_ctu][64] beside the fields.
+//   FOUR = false: one MV per 8x8 block (hmme_select_dirs_refs_device); the instructions it had before the parameter existed.
+//   FOUR = true:  one MV per 4x4 block (hmme_select_dirs_refs4_device; a.per == 256, fields, reference bytes and directions [..][256]).  All
+//                 593 slots take part, so TComDataCU::isBipredRestriction (TComDataCU.cpp:2892-2904, tested at TEncSearch.cpp:3109) applies
+//                 as in me_select_dirs_kernel<true>: slots 0..255 form no bi candidate for any reference -- the bi pass over the references
+//                 is not run for them (wave-uniform: k < 4), so their bi tables are not loaded -- and decide between list 0's best and list
+//                 1's direction-2 candidate alone.  The LDS is the 64 form's.
+template <bool FOUR = false>
 __global__ void __launch_bounds__(256)
 me_select_dirs_refs_kernel(const uint32_t* __restrict__ mv_uni, const uint32_t* __restrict__ cost_uni, const uint32_t* __restrict__ mv_bi,
                            const uint32_t* __restrict__ cost_bi, const uint32_t* __restrict__ uni_field, const uint8_t* __restrict__ uni_ref,
@@ -3209,10 +3230,11 @@ me_select_dirs_refs_kernel(const uint32_t* __restrict__ mv_uni, const uint32_t* 
           if (l == 1 && ((b.l1_valid_mask >> r) & 1u) && (rv < 0 || p < cv)) { cv = p; mvv = m; rv = r; }
         }
       }
+      const bool may_bi = !FOUR || i >= 256;   // FOUR: isBipredRestriction for the slots of 8x4 / 4x8 PUs (wave-uniform: k < 4)
 #pragma unroll
       for (int l = 0; l < 2; ++l) {
 #pragma unroll 1
-        for (int r = 0; r < b.n_refs[l]; ++r) {
+        for (int r = 0; may_bi && r < b.n_refs[l]; ++r) {
           int px, py;
           pred(l, r, px, py);
           const long at = row(l, r) + i;
@@ -3226,7 +3248,7 @@ me_select_dirs_refs_kernel(const uint32_t* __restrict__ mv_uni, const uint32_t* 
       uint64_t best;
       uint32_t m;
       int d, r0 = 0xff, r1 = 0xff;
-      if (cbi <= cu[0] && (rv < 0 || cbi <= cv)) { best = cbi; m = mb[bl]; d = 3 | bl << 2; r0 = rb[0]; r1 = rb[1]; }
+      if (may_bi && cbi <= cu[0] && (rv < 0 || cbi <= cv)) { best = cbi; m = mb[bl]; d = 3 | bl << 2; r0 = rb[0]; r1 = rb[1]; }
       else if (rv < 0 || cu[0] <= cv) { best = cu[0]; m = mu[0]; d = 1; r0 = ru[0]; }
       else { best = cv; m = mvv; d = 2; r1 = rv; }
       s_cost[w.wave][i] = best;
@@ -3238,7 +3260,7 @@ me_select_dirs_refs_kernel(const uint32_t* __restrict__ mv_uni, const uint32_t* 
   }
   __syncthreads();
   if (!w.live) return;
-  me_select_decide_store<kSelDirsRefs, uint64_t>(a, {s_cost[w.wave], s_mv[w.wave], nullptr, s_dir[w.wave], s_lref[w.wave]},
+  me_select_decide_store<kSelDirsRefs, uint64_t, FOUR>(a, {s_cost[w.wave], s_mv[w.wave], nullptr, s_dir[w.wave], s_lref[w.wave]},
                                                  {out_field, out_slot, out_cost, out_ref, out_dir, uni_field, uni_ref}, w, lambda_q16, 0, 0, pic_w, pic_h, n_ctu);
 }
 
@@ -3518,11 +3540,18 @@ me_predict_bi_kernel(const uint8_t* __restrict__ ref0, const uint8_t* __restrict
 // is 1, 2 or 3; in a list its direction does not name it stages nothing.  Tail per lane: me_tail_avg when both lists are used, else
 // me_tail_uni -- the sample me_predict_bi_kernel writes when the 8x8 block carries the quadrant's (direction, MV0, MV1).
 // The barrier invariant is me_predict4_pass's: both passes of all 16 iterations are met by every wave, whatever the field holds.
-template <typename SrcT>
+//   REFS = 0: one reference per list, ref0 / ref1.  Takes an empty struct and compiles to what it did without the argument.
+//   REFS = 1: a reference picture per 4x4 block and list (hmme_predict_bi_refs4_device): ref_field uint8 [2][n_ctu][256] (list-major, like the
+//            MVs) names the plane of set[l] a block reads in list l (all of one pitch; ref0 / ref1 are not used).  The indices are per
+//            QUADRANT like the direction, so the plane of a quadrant comes through readlane of a per-lane index, as in me_predict4_kernel.
+//            A quadrant that uses a list whose index is >= n[l] (0xFF: no CU) is like one without a direction: it reads no plane and its
+//            lanes write nothing.  The index of a list the quadrant does not use is not compared, and is clamped to 0 before any lookup.
+//            Liveness still sits inside the stages only: the barrier invariant holds as it did.
+template <typename SrcT, int REFS = 0>
 __global__ void __launch_bounds__(256)
 me_predict_bi4_kernel(const uint8_t* __restrict__ ref0, const uint8_t* __restrict__ ref1, int ref_pitch, const int16_t* __restrict__ mv_field,
                       const uint8_t* __restrict__ dir_field, int n_ctu, int ctu_first, int pic_w, int pic_h, int bit_depth, uint8_t* __restrict__ dst,
-                      int dst_pitch) {
+                      int dst_pitch, MePredBiRefs<REFS> refs) {
   __shared__ int16_t patch[4][4 * 11 * 12];
   __shared__ int16_t mid[4][4 * 11 * 4];
   __shared__ uint32_t taps[4][2];
@@ -3537,13 +3566,28 @@ me_predict_bi4_kernel(const uint8_t* __restrict__ ref0, const uint8_t* __restric
     const int qx = bx + (c & 4), qy = by + (r & 4);                      // this lane's 4x4 block inside the CTU
     const long e = (long)ctu * 256 + (qy >> 2) * 16 + (qx >> 2);
     const int dir = dir_field[e];
-    const bool live = cu_x + qx < pic_w && cu_y + qy < pic_h && dir >= 1 && dir <= 3;
+    bool live = cu_x + qx < pic_w && cu_y + qy < pic_h && dir >= 1 && dir <= 3;
+    [[maybe_unused]] int r0 = 0, r1 = 0;   // REFS: the lane's indices, 0 in a list it does not use
+    if constexpr (REFS) {
+      r0 = refs.ref_field[e]; r1 = refs.ref_field[(long)n_ctu * 256 + e];
+      live = live && (!(dir & 1) || r0 < refs.n[0]) && (!(dir & 2) || r1 < refs.n[1]);
+    }
     const bool use0 = live && (dir & 1), use1 = live && (dir & 2);
     int mx0 = 0, my0 = 0, mx1 = 0, my1 = 0;
     if (use0) me_field_mv(mv_field, e, cu_x, cu_y, pic_w, pic_h, mx0, my0);
     if (use1) me_field_mv(mv_field, (long)n_ctu * 256 + e, cu_x, cu_y, pic_w, pic_h, mx1, my1);
-    const int sum0 = me_predict4_pass<SrcT>(use0, [=](int) { return ref0; }, ref_pitch, cu_x + bx, cu_y + by, mx0, my0, patch[wave], mid[wave], taps, lane, k);
-    const int sum1 = me_predict4_pass<SrcT>(use1, [=](int) { return ref1; }, ref_pitch, cu_x + bx, cu_y + by, mx1, my1, patch[wave], mid[wave], taps, lane, k);
+    int sum0, sum1;
+    if constexpr (REFS) {
+      if (!use0) r0 = 0;   // use0: r0 < n[0]
+      if (!use1) r1 = 0;
+      const auto plane0 = [&](int from) { return refs.set[0].base[__builtin_amdgcn_readlane(r0, from)]; };
+      const auto plane1 = [&](int from) { return refs.set[1].base[__builtin_amdgcn_readlane(r1, from)]; };
+      sum0 = me_predict4_pass<SrcT>(use0, plane0, ref_pitch, cu_x + bx, cu_y + by, mx0, my0, patch[wave], mid[wave], taps, lane, k);
+      sum1 = me_predict4_pass<SrcT>(use1, plane1, ref_pitch, cu_x + bx, cu_y + by, mx1, my1, patch[wave], mid[wave], taps, lane, k);
+    } else {
+      sum0 = me_predict4_pass<SrcT>(use0, [=](int) { return ref0; }, ref_pitch, cu_x + bx, cu_y + by, mx0, my0, patch[wave], mid[wave], taps, lane, k);
+      sum1 = me_predict4_pass<SrcT>(use1, [=](int) { return ref1; }, ref_pitch, cu_x + bx, cu_y + by, mx1, my1, patch[wave], mid[wave], taps, lane, k);
+    }
     if (live) me_store_sample<SrcT>(dst, dst_pitch, cu_x + bx + c, cu_y + by + r, pic_w, pic_h, me_tail_dir(use0, use1, sum0, sum1, k));
   }
 }
@@ -3809,10 +3853,15 @@ me_predict_chroma4_kernel(MeChromaSrc src, int ref_pitch, const int16_t* __restr
 // LDS (me_predict_chroma4_pass twice: FOUR barriers per iteration).  A quad is live if its 4x4 luma block starts inside the luma picture and
 // its direction is 1, 2 or 3.  Tail per lane: me_tail_avg when both lists are used, else me_tail_uni.
 // The barrier invariant is the pass's: both passes of all eight iterations are met by every group of every wave, whatever the field holds.
-template <typename SrcT>
+//   REFS = 0: one reference per list (MeChromaWp<2, 0>: empty).  Compiles to what it did without the argument.
+//   REFS = 1: FORM 3 from the 256 layout, unweighted (hmme_predict_chroma_bi_refs4_device): refs.ref_field uint8 [2][n_ctu][256] is read
+//            beside the direction; set.base[2 * r + comp] is list 0's reference r (r < src.n_refs), set.base[2 * (src.n_refs + r) + comp]
+//            list 1's (r < refs.n_refs1).  The plane of a quad comes from its first lane's index (__shfl), as in me_predict_chroma4_kernel.
+//            A quad that uses a list whose index is beyond it is not live; an index that is not used is clamped to 0 before any lookup.
+template <typename SrcT, int REFS = 0>
 __global__ void __launch_bounds__(256)
 me_predict_chroma_bi4_kernel(MeChromaSrc src, int ref_pitch, const int16_t* __restrict__ mv_field, int ctu_first, int pic_w, int pic_h, int bit_depth,
-                             uint8_t* __restrict__ dst_cb, uint8_t* __restrict__ dst_cr, int dst_pitch) {
+                             uint8_t* __restrict__ dst_cb, uint8_t* __restrict__ dst_cr, int dst_pitch, MeChromaWp<REFS ? 3 : 2, 0> refs) {
   __shared__ int16_t patch[16][4 * 25];
   __shared__ int16_t mid[16][4 * 10];
   __shared__ uint32_t taps[8];
@@ -3831,13 +3880,28 @@ me_predict_chroma_bi4_kernel(MeChromaSrc src, int ref_pitch, const int16_t* __re
     const long e = (long)ctu * 256 + (qy >> 2) * 16 + (qx >> 2);
     const int x0 = (cu_x + bx) >> 1, y0 = (cu_y + by) >> 1;
     const int dir = src.field[e];
-    const bool live = cu_x + qx < pic_w && cu_y + qy < pic_h && dir >= 1 && dir <= 3;
+    bool live = cu_x + qx < pic_w && cu_y + qy < pic_h && dir >= 1 && dir <= 3;
+    [[maybe_unused]] int r0 = 0, r1 = 0;   // REFS: the lane's indices, 0 in a list it does not use
+    if constexpr (REFS) {
+      r0 = refs.ref_field[e]; r1 = refs.ref_field[(long)src.n_ctu * 256 + e];
+      live = live && (!(dir & 1) || r0 < src.n_refs) && (!(dir & 2) || r1 < refs.n_refs1);
+    }
     const bool use0 = live && (dir & 1), use1 = live && (dir & 2);
     int mx0 = 0, my0 = 0, mx1 = 0, my1 = 0;
     if (use0) me_field_mv(mv_field, e, cu_x, cu_y, pic_w, pic_h, mx0, my0);
     if (use1) me_field_mv(mv_field, (long)src.n_ctu * 256 + e, cu_x, cu_y, pic_w, pic_h, mx1, my1);
-    const int sum0 = me_predict_chroma4_pass<SrcT>(use0, [=](int) { return plane0; }, ref_pitch, x0, y0, mx0, my0, patch[group], mid[group], taps, lane, k);
-    const int sum1 = me_predict_chroma4_pass<SrcT>(use1, [=](int) { return plane1; }, ref_pitch, x0, y0, mx1, my1, patch[group], mid[group], taps, lane, k);
+    int sum0, sum1;
+    if constexpr (REFS) {
+      if (!use0) r0 = 0;   // use0: r0 < n_refs
+      if (!use1) r1 = 0;
+      const auto of0 = [&](int from) { return src.set.base[2 * __shfl(r0, from) + comp]; };
+      const auto of1 = [&](int from) { return src.set.base[2 * (src.n_refs + __shfl(r1, from)) + comp]; };
+      sum0 = me_predict_chroma4_pass<SrcT>(use0, of0, ref_pitch, x0, y0, mx0, my0, patch[group], mid[group], taps, lane, k);
+      sum1 = me_predict_chroma4_pass<SrcT>(use1, of1, ref_pitch, x0, y0, mx1, my1, patch[group], mid[group], taps, lane, k);
+    } else {
+      sum0 = me_predict_chroma4_pass<SrcT>(use0, [=](int) { return plane0; }, ref_pitch, x0, y0, mx0, my0, patch[group], mid[group], taps, lane, k);
+      sum1 = me_predict_chroma4_pass<SrcT>(use1, [=](int) { return plane1; }, ref_pitch, x0, y0, mx1, my1, patch[group], mid[group], taps, lane, k);
+    }
     if (live) me_store_sample<SrcT>(dst, dst_pitch, x0 + c, y0 + r, pic_w >> 1, pic_h >> 1, me_tail_dir(use0, use1, sum0, sum1, k));
   }
 }

@@ -47,7 +47,10 @@ SYMBOLS = ["hmme_create", "hmme_destroy", "hmme_last_error", "hmme_device_info",
            "hmme_predict_chroma_bi_refs_device", "hmme_predict_chroma_bi_refs_frame",
            "hmme_search_pairs_bi4_device", "hmme_refine_pairs_bi4_device", "hmme_search_frame_bi4", "hmme_refine_frame_bi4",
            "hmme_select_dirs4_check", "hmme_select_dirs4_device", "hmme_select_dirs4_frame",
-           "hmme_predict_bi4_device", "hmme_predict_bi4_frame", "hmme_predict_chroma_bi4_device", "hmme_predict_chroma_bi4_frame"]
+           "hmme_predict_bi4_device", "hmme_predict_bi4_frame", "hmme_predict_chroma_bi4_device", "hmme_predict_chroma_bi4_frame",
+           "hmme_search_frame_bi_refs4_device", "hmme_refine_frame_bi_refs4_device", "hmme_search_frame_bi_refs4", "hmme_refine_frame_bi_refs4",
+           "hmme_select_dirs_refs4_check", "hmme_select_dirs_refs4_device", "hmme_select_dirs_refs4_frame",
+           "hmme_predict_bi_refs4_device", "hmme_predict_bi_refs4_frame", "hmme_predict_chroma_bi_refs4_device", "hmme_predict_chroma_bi_refs4_frame"]
 # test / measurement entry points (include/hmme_test.h): not part of the boundary
 TEST_SYMBOLS = ["hmme_test_time_search_kernel", "hmme_test_device_address", "hmme_test_frac_deal", "hmme_test_tail_plan", "hmme_test_stage_layout", "hmme_test_picture_job", "hmme_test_time_weight_passes", "hmme_test_time_bipred_origin",
                 "hmme_test_time_wp_estimate_passes", "hmme_test_pk_gate", "hmme_test_pk_body", "hmme_test_pk_task_marker_free", "hmme_test_pk_task_full",
@@ -264,6 +267,18 @@ def load():
     L.hmme_select_dirs_refs_frame.argtypes = [vp, i, i, i, pfp, C.POINTER(SelectParams), C.POINTER(DirRefsParams)] + [vp] * 12
     L.hmme_predict_bi_refs_device.argtypes = [vp, pvp, i, pvp, i, pfp, vp, vp, vp, i, vp, i, vp]
     L.hmme_predict_bi_refs_frame.argtypes = [vp, pvp, i, pvp, i, pfp, vp, vp, vp, i, vp, i]
+    # ... from one MV per 4x4 block: the bi_refs signatures without mv_per_ctu (chroma: without weights, too)
+    L.hmme_search_frame_bi_refs4_device.argtypes = [vp, vp, pvp, i, pvp, i, pfp, vp, vp, vp, vp, vp, vp, vp]
+    L.hmme_refine_frame_bi_refs4_device.argtypes = [vp, vp, pvp, i, pvp, i, pfp, vp, vp, vp, vp, vp, i, vp, vp, vp]
+    L.hmme_search_frame_bi_refs4.argtypes = [vp, vp, pvp, i, pvp, i, pfp, vp, vp, vp, vp, vp, vp]
+    L.hmme_refine_frame_bi_refs4.argtypes = [vp, vp, pvp, i, pvp, i, pfp, vp, vp, vp, vp, vp, i, vp, vp]
+    L.hmme_select_dirs_refs4_check.argtypes = [C.POINTER(SelectParams), i, i, C.POINTER(DirRefsParams)]
+    L.hmme_select_dirs_refs4_device.argtypes = [vp, i, i, i, i, pfp, C.POINTER(SelectParams), C.POINTER(DirRefsParams)] + [vp] * 13
+    L.hmme_select_dirs_refs4_frame.argtypes = [vp, i, i, i, pfp, C.POINTER(SelectParams), C.POINTER(DirRefsParams)] + [vp] * 12
+    L.hmme_predict_bi_refs4_device.argtypes = [vp, pvp, i, pvp, i, pfp, vp, vp, vp, vp, i, vp]
+    L.hmme_predict_bi_refs4_frame.argtypes = [vp, pvp, i, pvp, i, pfp, vp, vp, vp, vp, i]
+    L.hmme_predict_chroma_bi_refs4_device.argtypes = [vp, pvp, i, pvp, i, i, i, pfp, vp, vp, vp, vp, vp, i, vp]
+    L.hmme_predict_chroma_bi_refs4_frame.argtypes = [vp, pvp, i, pvp, i, i, i, pfp, vp, vp, vp, pvp, i]
     L.hmme_bipred_refs_weight_check.argtypes = [i, pw, i, pw, i, i]
     L.hmme_search_frame_bi_refs_w_device.argtypes = [vp, vp, pvp, i, pvp, i, pfp, pw, pw, vp, vp, i, vp, vp, vp, vp, vp]
     L.hmme_refine_frame_bi_refs_w_device.argtypes = [vp, vp, pvp, i, pvp, i, pfp, pw, pw, vp, vp, i, vp, vp, vp, i, vp, vp, vp]
@@ -1219,6 +1234,117 @@ class Engine:
                                                          oa, cb.shape[1]))
         return cb, cr
 
+    # ---- B pictures with several references per list from one MV per 4x4 block (include/hmme.h, "B pictures with several references per
+    # list from one MV per 4x4 block"): the bi_refs calls on the 256 layout, unweighted
+    def search_frame_bi_refs4_device(self, cur, refs, others, fp, d_other_mv, d_other_ref, d_center, d_pred, d_mv, d_sad, stream=0):
+        """hmme_search_frame_bi_refs4_device: search_frame_bi_refs_device against the origin built from d_other_mv int16[n_ctu, 256, 2] and
+        d_other_ref uint8[n_ctu, 256]: every 4x4 block from others[its index] (an index >= len(others) reads others[0])"""
+        self._check(self.L.hmme_search_frame_bi_refs4_device(self.h, cur.h, _handles(refs), len(refs), _handles(others), len(others), C.byref(fp), d_other_mv,
+                                                             d_other_ref, d_center, d_pred, d_mv, d_sad, stream))
+
+    def refine_frame_bi_refs4_device(self, cur, refs, others, fp, d_other_mv, d_other_ref, d_center, d_pred, d_int_mv, use_hadamard, d_qmv, d_cost, stream=0):
+        """hmme_refine_frame_bi_refs4_device: refine_frame_bi_refs_device against that origin"""
+        self._check(self.L.hmme_refine_frame_bi_refs4_device(self.h, cur.h, _handles(refs), len(refs), _handles(others), len(others), C.byref(fp), d_other_mv,
+                                                             d_other_ref, d_center, d_pred, d_int_mv, int(use_hadamard), d_qmv, d_cost, stream))
+
+    def _frame_bi_refs4(self, entry, cur, refs, others, sr, fen, other_mv, other_ref, int_mv, center_q, pred_q, use_hadamard, ctu_first, ctu_count):
+        """the two *_frame_bi_refs4 methods (_frame_bi_refs on the 256 layout); int_mv: None for a search -> the two result tables
+        [len(refs), count, 593, ...]"""
+        n = self.L.hmme_num_ctus(cur.width, cur.height)
+        count = n - ctu_first if ctu_count < 0 else ctu_count
+        fp = FrameParams(sr, int(fen), cur.bit_depth, ctu_first, count)
+        f, rf, rf_ptr = self._field4(cur.width, cur.height, other_mv, other_ref)
+        args = [f.ctypes.data, rf_ptr]
+        keep = []
+        for a in (center_q, pred_q):
+            if a is None:
+                args.append(None)
+                continue
+            a = np.ascontiguousarray(a, dtype=np.int16)
+            assert a.shape == (len(refs), n, 2)
+            keep.append(a)
+            args.append(a.ctypes.data)
+        if int_mv is not None:
+            int_mv = np.ascontiguousarray(int_mv, dtype=np.int16)
+            assert int_mv.shape == (len(refs), count, NUM_PARTS, 2)
+            args += [int_mv.ctypes.data, int(use_hadamard)]
+        mv = np.zeros((len(refs), count, NUM_PARTS, 2), np.int16)
+        cost = np.zeros((len(refs), count, NUM_PARTS), np.uint32)
+        self._check(entry(self.h, cur.h, _handles(refs), len(refs), _handles(others), len(others), C.byref(fp), *args, mv.ctypes.data, cost.ctypes.data))
+        return mv, cost
+
+    def search_frame_bi_refs4(self, cur, refs, others, sr, other_mv, other_ref, center_q=None, pred_q=None, fen=1, ctu_first=0, ctu_count=-1):
+        """hmme_search_frame_bi_refs4: search_frame_bi_refs with other_mv int16[n_ctu, 256, 2] and other_ref uint8[n_ctu, 256], one entry per
+        4x4 block (None: refused) -> (mv int16[n_refs,count,593,2], sad uint32[n_refs,count,593])"""
+        return self._frame_bi_refs4(self.L.hmme_search_frame_bi_refs4, cur, refs, others, sr, fen, other_mv, other_ref, None, center_q, pred_q, True, ctu_first,
+                                    ctu_count)
+
+    def refine_frame_bi_refs4(self, cur, refs, others, sr, other_mv, other_ref, int_mv, center_q=None, pred_q=None, use_hadamard=True, ctu_first=0, ctu_count=-1):
+        """hmme_refine_frame_bi_refs4: refine_frame_bi_refs on the 256 layout -> (qmv int16[n_refs,count,593,2], cost uint32[n_refs,count,593])"""
+        return self._frame_bi_refs4(self.L.hmme_refine_frame_bi_refs4, cur, refs, others, sr, 1, other_mv, other_ref, int_mv, center_q, pred_q, use_hadamard,
+                                    ctu_first, ctu_count)
+
+    def select_dirs_refs4_device(self, width, height, n_pics, n_refs_max, fp, sel, dirs, d_mv_uni, d_cost_uni, d_mv_bi, d_cost_bi, d_uni_field, d_uni_ref, d_pred,
+                                 d_field, d_ref, d_dir, d_slot=None, d_ctu_cost=None, stream=0):
+        """hmme_select_dirs_refs4_device: select_dirs_refs_device over all 593 slots (sel.mv_per_ctu == 256; 8x4 / 4x8 PUs never bi): uni fields and
+        motion field int16[n_pics, 2, n_ctu, 256, 2], reference indices uint8[n_pics, 2, n_ctu, 256], directions uint8[n_pics, n_ctu, 256],
+        covering slots uint16 of that shape"""
+        self._check(self.L.hmme_select_dirs_refs4_device(self.h, int(width), int(height), int(n_pics), int(n_refs_max), C.byref(fp), C.byref(sel),
+                                                         _dir_refs_params(dirs, n_pics), d_mv_uni, d_cost_uni, d_mv_bi, d_cost_bi, d_uni_field, d_uni_ref, d_pred,
+                                                         d_field, d_ref, d_dir, d_slot, d_ctu_cost, stream))
+
+    def select_dirs_refs4_frame(self, width, height, sel, dir_params, mv_uni, cost_uni, mv_bi, cost_bi, uni_field, uni_ref, pred_q=None, ctu_first=0, ctu_count=-1,
+                                field=None, ref=None, dirs=None, slot=None, ctu_cost=None):
+        """hmme_select_dirs_refs4_frame: select_dirs_refs_frame on the 256 layout: uni_field int16[2, n_ctu, 256, 2], uni_ref uint8[2, n_ctu, 256] ->
+        (field int16[2, n_ctu, 256, 2], ref uint8[2, n_ctu, 256], dirs uint8[n_ctu, 256], slot uint16[n_ctu, 256], ctu_cost uint32[n_ctu])"""
+        R = int(np.shape(mv_uni)[1])
+        call = lambda fp, *a: self.L.hmme_select_dirs_refs4_frame(self.h, int(width), int(height), R, C.byref(fp), C.byref(sel), C.byref(dir_params), *a)
+        return self._select_frame(call, (2, R), width, height, (mv_uni, cost_uni, mv_bi, cost_bi),
+                                  ((uni_field, np.int16, (2,), (256, 2)), (uni_ref, np.uint8, (2,), (256,))), pred_q, ctu_first, ctu_count,
+                                  ((field, np.int16, (2,), (256, 2)), (ref, np.uint8, (2,), (256,)), (dirs, np.uint8, (), (256,)), (slot, np.uint16, (), (256,)),
+                                   (ctu_cost, np.uint32, (), ())))
+
+    def _fields_bi_refs4(self, width, height, mv_field, dir_field, ref_field):
+        """host fields of a multi-reference B picture on the 256 layout: int16[2, n_ctu, 256, 2], uint8[n_ctu, 256], uint8[2, n_ctu, 256]"""
+        f, df = self._fields_bi4(width, height, mv_field, dir_field)
+        rf = np.ascontiguousarray(ref_field, dtype=np.uint8)
+        assert rf.shape == (2,) + df.shape
+        return f, df, rf
+
+    def predict_bi_refs4_device(self, refs0, refs1, fp, d_mv_field, d_dir_field, d_ref_field, d_out, out_pitch_bytes, stream=0):
+        """hmme_predict_bi_refs4_device: predict_bi_refs_device from d_mv_field int16[2, n_ctu, 256, 2], d_dir_field uint8[n_ctu, 256] and
+        d_ref_field uint8[2, n_ctu, 256]; d_out = the device image"""
+        self._check(self.L.hmme_predict_bi_refs4_device(self.h, _handles(refs0), len(refs0), _handles(refs1), len(refs1), C.byref(fp), d_mv_field, d_dir_field,
+                                                        d_ref_field, d_out, int(out_pitch_bytes), stream))
+
+    def predict_bi_refs4_frame(self, refs0, refs1, mv_field, dir_field, ref_field, out=None, ctu_first=0, ctu_count=-1):
+        """hmme_predict_bi_refs4_frame: predict_bi_refs_frame from one (direction, MV0, MV1, ref0, ref1) per 4x4 block -> [height, width]; `out`
+        keeps its samples outside the CTU range and in blocks that are not live"""
+        r0 = refs0[0]
+        f, df, rf = self._fields_bi_refs4(r0.width, r0.height, mv_field, dir_field, ref_field)
+        out = self._image(r0, out)
+        fp = FrameParams(1, 0, r0.bit_depth, ctu_first, ctu_count)
+        self._check(self.L.hmme_predict_bi_refs4_frame(self.h, _handles(refs0), len(refs0), _handles(refs1), len(refs1), C.byref(fp), f.ctypes.data, df.ctypes.data,
+                                                       rf.ctypes.data, out.ctypes.data, out.shape[1]))
+        return out
+
+    def predict_chroma_bi_refs4_device(self, refs0, refs1, width, height, fp, d_mv_field, d_dir_field, d_ref_field, d_out_cb, d_out_cr, out_pitch_bytes, stream=0):
+        """hmme_predict_chroma_bi_refs4_device: predict_chroma_bi_refs_device (no weights) from the fields of the 256 layout; refs0 / refs1 = [cb0,
+        cr0, cb1, ...], up to 8 references in both lists together"""
+        assert len(refs0) % 2 == 0 and len(refs1) % 2 == 0
+        self._check(self.L.hmme_predict_chroma_bi_refs4_device(self.h, _handles(refs0), len(refs0) // 2, _handles(refs1), len(refs1) // 2, int(width), int(height),
+                                                               C.byref(fp), d_mv_field, d_dir_field, d_ref_field, d_out_cb, d_out_cr, int(out_pitch_bytes), stream))
+
+    def predict_chroma_bi_refs4_frame(self, refs0, refs1, width, height, mv_field, dir_field, ref_field, outs=None, ctu_first=0, ctu_count=-1):
+        """hmme_predict_chroma_bi_refs4_frame: predict_bi_refs4_frame for Cb and Cr; refs0 / refs1 = [cb0, cr0, cb1, cr1, ...] -> (cb, cr)"""
+        assert len(refs0) % 2 == 0 and len(refs1) % 2 == 0
+        f, df, rf = self._fields_bi_refs4(width, height, mv_field, dir_field, ref_field)
+        cb, cr, oa = self._chroma_images(refs0[0], outs)
+        fp = FrameParams(1, 0, refs0[0].bit_depth, ctu_first, ctu_count)
+        self._check(self.L.hmme_predict_chroma_bi_refs4_frame(self.h, _handles(refs0), len(refs0) // 2, _handles(refs1), len(refs1) // 2, int(width), int(height),
+                                                              C.byref(fp), f.ctypes.data, df.ctypes.data, rf.ctypes.data, oa, cb.shape[1]))
+        return cb, cr
+
     # ---- multi-reference B pictures with explicit weights and in 4:2:0 (include/hmme.h, "multi-reference B pictures: explicit weights and
     # 4:2:0 chroma"): one (w0, offset, shift, round) per reference of each list; chroma: per plane, (Cb, Cr) per reference, or None
     def search_frame_bi_refs_w_device(self, cur, refs, others, fp, weights, other_weights, d_other_mv, d_other_ref, mv_per_ctu, d_center, d_pred, d_mv, d_sad, stream=0):
@@ -1488,6 +1614,16 @@ def select_dirs_refs_check(sel, n_pics, n_refs_max, dirs):
         for k, d in enumerate(dirs):
             a[k] = d
     return int(load().hmme_select_dirs_refs_check(C.byref(sel), int(n_pics), int(n_refs_max), a))
+
+
+def select_dirs_refs4_check(sel, n_pics, n_refs_max, dirs):
+    """hmme_select_dirs_refs4_check: select_dirs_refs_check for the 256 layout: mv_per_ctu 256, mv_unit 0, price_mv 0 only"""
+    a = None
+    if dirs is not None:
+        a = (DirRefsParams * max(len(dirs), 4))()
+        for k, d in enumerate(dirs):
+            a[k] = d
+    return int(load().hmme_select_dirs_refs4_check(C.byref(sel), int(n_pics), int(n_refs_max), a))
 
 
 def ocl_compat_params(lt_x, lt_y, sr):

@@ -1117,8 +1117,8 @@ int hmme_predict_chroma_refs4_frame(hmme_ctx* ctx, const hmme_plane* const* refs
  * Every refusal of the entries of this family names the entry in hmme_last_error -- also those of the checks all families share (the CTU
  * range, a plane of another context, a NULL table), whose messages the 64 forms give bare.
  *
- * Not part of this family: explicit weights (_bi4_w), several references per list (hmme_select_dirs_refs_* at 4x4), 4:2:2 / 4:4:4, and the
- * plumbing into the sequence driver (hmme/sequence.py, run_rank). */
+ * Not part of this family: explicit weights (_bi4_w), 4:2:2 / 4:4:4, and the plumbing into the sequence driver (hmme/sequence.py, run_rank).
+ * Several references per list at 4x4: "B pictures with several references per list from one MV per 4x4 block" below. */
 int hmme_search_pairs_bi4_device(hmme_ctx* ctx, const hmme_plane* const* curs, const hmme_plane* const* refs, const hmme_plane* const* others,
                                  int n_pairs, const hmme_frame_params* fp, const void* d_other_mv /* int16[n_pairs][n_ctu][256][2] */, const void* d_center_q,
                                  const void* d_pred_q, void* d_out_mv, void* d_out_sad, void* stream);
@@ -1148,6 +1148,102 @@ int hmme_predict_chroma_bi4_device(hmme_ctx* ctx, const hmme_plane* const* refs0
                                    void* stream);
 int hmme_predict_chroma_bi4_frame(hmme_ctx* ctx, const hmme_plane* const* ref0, const hmme_plane* const* ref1, int width, int height,
                                   const hmme_frame_params* fp, const int16_t* mv_field, const uint8_t* dir_field, void* const* outs, int out_stride);
+
+/* ---- B pictures with several references per list from one MV per 4x4 block ("bi_refs4") -----------------------------------------
+ * The two B-picture families joined: what "B pictures with several references per list" (the 64 form above) is at one MV per 8x8 block, at
+ * full partition depth -- the bi pass against an origin built from a 4x4 field with a reference index per block, the L0 / L1 / bi decision
+ * with the reference index per list over all 593 slots, and the prediction from its output; unweighted, Y plus the Cb / Cr of 4:2:0.  HM's B
+ * configurations have two references per list (random access) or four (low-delay B).  The chain:
+ *   1. hmme_refine_frame_multi_device, once per list;
+ *   2. hmme_select_refs_device at mv_per_ctu = 256 with the two lists as its two pictures: uni_field[2] and uni_ref[2], 256 entries per CTU;
+ *   3. hmme_refine_frame_bi_refs4_device, once per list;
+ *   4. hmme_select_dirs_refs4_device;
+ *   5. hmme_predict_bi_refs4_device + hmme_predict_chroma_bi_refs4_device;
+ *   6. hmme_residual_pairs_device at 256.
+ * New entry points only; no struct (hmme_dir_refs_params is reused as it is) and no existing entry point changed -- hmme_select_dirs_refs_*,
+ * the *_bi_refs* calls and hmme_predict_*bi_refs_* still refuse 256 MVs per CTU --, so HMME_ABI_VERSION stays 6.  THIS TEXT PLUS THE CITATIONS
+ * IS THE RULE (paths below source/Lib of the reference).
+ *
+ * Fields.  As in the refs4 and bi4 families there is no mv_per_ctu argument: the family IS the 256 layout.  Entry b of a CTU is the 4x4 luma
+ * block at ((b & 15) * 4, (b >> 4) * 4); n_ctu counts all CTUs of the picture.
+ *
+ * 1. The bi pass.  hmme_search_frame_bi_refs4_device, hmme_refine_frame_bi_refs4_device, hmme_search_frame_bi_refs4 and
+ * hmme_refine_frame_bi_refs4 are hmme_search_frame_bi_refs_device, hmme_refine_frame_bi_refs_device, hmme_search_frame_bi_refs and
+ * hmme_refine_frame_bi_refs without mv_per_ctu: d_other_mv int16[n_ctu][256][2], d_other_ref uint8[n_ctu][256].  The 64 form's text holds
+ * word for word with one difference -- how the other list's prediction P inside the origin O = 2 B - P (TLibEncoder/TEncSearch.cpp:3702-3712)
+ * is formed: every 4x4 block of the CTU's 64x64 block, those beyond the picture edge included, is compensated from
+ * others[d_other_ref[block]] at its own MV, clamped with the CTU's clipMv; an index >= n_others (the 0xFF of CUs that do not exist
+ * included) reads reference 0.  Sample for sample it is what the 64 form puts there when the surrounding 8x8 block carries that (MV, index).
+ * The origin is built once per call and serves all n_refs searched references.  The results are, per CTU and reference, what hmme_search_ctu
+ * / hmme_refine_ctu return on that origin; with a field and reference field whose four entries per 8x8 block agree the tables are bit for
+ * bit the 64 form's, and with n_others == 1 they are those of hmme_search_frame_bi4 / hmme_refine_frame_bi4.  Refusals: hmme_bipred_check's
+ * and those of the 64 form, in their order; a NULL d_other_ref is HMME_ERR_ARG.
+ *
+ * 2. The decision.  hmme_select_dirs_refs4_check / _device / _frame have the signatures of hmme_select_dirs_refs_*, and the rule of
+ * hmme_select_dirs_refs_device (its inputs, steps 1-4, l1_valid_mask, ref_bits, the 64-bit sums, its outputs) holds word for word with
+ * these differences, which are those of hmme_select_dirs4_device:
+ *   a. Layouts.  sel->mv_per_ctu == 256 (mv_unit == 0 and price_mv == 0 as before).  d_uni_field and d_out_field are
+ *      int16[n_pics][2][n_ctu][256][2], d_uni_ref and d_out_ref uint8[n_pics][2][n_ctu][256], d_out_dir uint8[n_pics][n_ctu][256], d_out_slot
+ *      uint16[n_pics][n_ctu][256].  All 593 slots take part, as in hmme_select_refs_device at 256.
+ *   b. Bi restriction: TComDataCU::isBipredRestriction (TLibCommon/TComDataCU.cpp:2892-2904), tested at TLibEncoder/TEncSearch.cpp:3109.  A
+ *      slot whose hmme_slot_key has depth 3 and part_size 1 or 2 -- an 8x4 or 4x8 PU: slots 0..255 -- forms no bi candidate for any
+ *      reference: step 3 is not carried out for it, its bi tables are not loaded, and what mv_bi / cost_bi hold at that slot reaches no
+ *      output.  Step 4 for it: C_V absent or C[0] <= C_V: direction 1; otherwise direction 2.  Every other slot, the AMP slots of a 16x16 CU
+ *      included, decides as before.
+ *   c. Other-list entry.  Under a direction-3 block, list 1-l's MV and reference index are that 4x4 BLOCK'S OWN ENTRIES of d_uni_field[1-l]
+ *      and d_uni_ref[1-l].
+ * Buffers: tables, costs, the input field and slots 4-byte aligned, the output field 8-byte; d_out_ref and d_out_dir 2-byte (a lane stores
+ * pairs).  hmme_select_dirs_refs4_check is hmme_select_dirs_refs_check with 256 in place of 64.
+ *
+ * 3. The prediction.  hmme_predict_bi_refs4_device / _frame are hmme_predict_bi_refs_device / _frame without mv_per_ctu: ONE picture,
+ * refs0[n0], refs1[n1] (each 1..16 planes), d_mv_field int16[2][n_ctu][256][2], d_dir_field uint8[n_ctu][256], d_ref_field
+ * uint8[2][n_ctu][256].  A 4x4 block is live if it starts inside the picture, its direction is 1, 2 or 3, and every list it uses has an
+ * index below that list's count (the index of a list it does not use is not looked at); a block that is not live reads no plane and writes
+ * nothing.  Every sample of a live block is what hmme_predict_bi_refs_device writes for it when the 8x8 block around it carries this block's
+ * (direction, MV0, MV1, ref0, ref1) -- xPredInterBlk (TLibCommon/TComPrediction.cpp:669-707) + TComYuv::addAvg, by the separability argument
+ * of the refs4 family.  The margins hold: the 11 x 11 patch is a subset of the 15 x 15 one.
+ * hmme_predict_chroma_bi_refs4_device / _frame are hmme_predict_chroma_bi_refs_device / _frame without mv_per_ctu AND WITHOUT WEIGHTS: up to
+ * 4 + 4 references (2 * (n0 + n1) <= 16 planes, refs_l = (Cb, Cr) per reference), an even luma size of at least 16 x 16.  A 4x4 luma block is
+ * a 2x2 block per component; sample for sample the output is what hmme_predict_chroma_bi_refs_device (NULL weights) writes when the 8x8 luma
+ * block carries the entry.
+ * Refusals -- codes and order -- are those of the 64 forms.
+ *
+ * Every refusal of the entries of this family names the entry called in hmme_last_error -- also those of the checks all families share.
+ *
+ * Out of scope: explicit weights (_bi_refs4_w), 4:2:2 / 4:4:4, GPB_SIMPLE_UNI's copy of list-0 results into list 1, MvdL1ZeroFlag, HM's
+ * further bi iterations, and the plumbing into the sequence driver (hmme/sequence.py, run_rank). */
+int hmme_search_frame_bi_refs4_device(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others,
+                                      int n_others, const hmme_frame_params* fp, const void* d_other_mv /* int16[n_ctu][256][2] */,
+                                      const void* d_other_ref /* uint8[n_ctu][256] */, const void* d_center_q, const void* d_pred_q, void* d_out_mv,
+                                      void* d_out_sad, void* stream);
+int hmme_refine_frame_bi_refs4_device(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others,
+                                      int n_others, const hmme_frame_params* fp, const void* d_other_mv, const void* d_other_ref, const void* d_center_q,
+                                      const void* d_pred_q, const void* d_int_mv, int use_hadamard, void* d_out_qmv, void* d_out_cost, void* stream);
+int hmme_search_frame_bi_refs4(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
+                               const hmme_frame_params* fp, const int16_t* other_mv, const uint8_t* other_ref, const int16_t* center_q, const int16_t* pred_q,
+                               int16_t* out_mv, uint32_t* out_sad);
+int hmme_refine_frame_bi_refs4(hmme_ctx* ctx, const hmme_plane* cur, const hmme_plane* const* refs, int n_refs, const hmme_plane* const* others, int n_others,
+                               const hmme_frame_params* fp, const int16_t* other_mv, const uint8_t* other_ref, const int16_t* center_q, const int16_t* pred_q,
+                               const int16_t* int_mv, int use_hadamard, int16_t* out_qmv, uint32_t* out_cost);
+int hmme_select_dirs_refs4_check(const hmme_select_params* sel, int n_pics, int n_refs_max, const hmme_dir_refs_params* dirs);
+int hmme_select_dirs_refs4_device(hmme_ctx* ctx, int width, int height, int n_pics, int n_refs_max, const hmme_frame_params* fp, const hmme_select_params* sel,
+                                  const hmme_dir_refs_params* dirs, const void* d_mv_uni, const void* d_cost_uni, const void* d_mv_bi, const void* d_cost_bi,
+                                  const void* d_uni_field, const void* d_uni_ref, const void* d_pred_q, void* d_out_field, void* d_out_ref, void* d_out_dir,
+                                  void* d_out_slot, void* d_out_cost, void* stream);
+int hmme_select_dirs_refs4_frame(hmme_ctx* ctx, int width, int height, int n_refs_max, const hmme_frame_params* fp, const hmme_select_params* sel,
+                                 const hmme_dir_refs_params* dir, const int16_t* mv_uni, const uint32_t* cost_uni, const int16_t* mv_bi, const uint32_t* cost_bi,
+                                 const int16_t* uni_field, const uint8_t* uni_ref, const int16_t* pred_q, int16_t* out_field, uint8_t* out_ref, uint8_t* out_dir,
+                                 uint16_t* out_slot, uint32_t* out_cost);
+int hmme_predict_bi_refs4_device(hmme_ctx* ctx, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, const hmme_frame_params* fp,
+                                 const void* d_mv_field, const void* d_dir_field, const void* d_ref_field, void* d_out, int out_pitch_bytes, void* stream);
+int hmme_predict_bi_refs4_frame(hmme_ctx* ctx, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, const hmme_frame_params* fp,
+                                const int16_t* mv_field, const uint8_t* dir_field, const uint8_t* ref_field, void* out, int out_stride);
+int hmme_predict_chroma_bi_refs4_device(hmme_ctx* ctx, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, int width, int height,
+                                        const hmme_frame_params* fp, const void* d_mv_field, const void* d_dir_field, const void* d_ref_field, void* d_out_cb,
+                                        void* d_out_cr, int out_pitch_bytes, void* stream);
+int hmme_predict_chroma_bi_refs4_frame(hmme_ctx* ctx, const hmme_plane* const* refs0, int n0, const hmme_plane* const* refs1, int n1, int width, int height,
+                                       const hmme_frame_params* fp, const int16_t* mv_field, const uint8_t* dir_field, const uint8_t* ref_field,
+                                       void* const* outs, int out_stride);
 
 /* ---- residual and distortion of a prediction ------------------------------------------------------------------------
  * The first things HM does with a prediction, on the device: the residual, what the prediction costs per PU, and what coding no residual
