@@ -1505,6 +1505,16 @@ int hmme_test_pk_gate(uint32_t lambda_q16) { return hmme::me_pk_gate(lambda_q16)
 int hmme_test_pk_body(uint32_t lambda_q16, int fen) { return hmme::me_pk_body(lambda_q16, fen ? 1 : 0); }
 int hmme_test_pk_task_marker_free(int wx, int wy, int k, int it0, int n_it) { return hmme::me_task_marker_free(wx, wy, k, it0, n_it) ? 1 : 0; }
 int hmme_test_pk_task_full(int wx, int wy, int k, int it0, int n_it) { return hmme::me_task_full(wx, wy, k, it0, n_it) ? 1 : 0; }
+int hmme_test_task_carry_fits(int wx, int wy, int k, int it0, int n_it) { return hmme::me_task_carry_fits(wx, wy, k, it0, n_it) ? 1 : 0; }
+int hmme_test_carry_index(int k, int row, int group) {
+  if (k < 2 || k > 5 || row < 0 || group < 0 || group >= 1 << (k - 2)) return -1;
+  return (int)hmme::me_carry_index(k, row, group);
+}
+int hmme_test_carry_position(int k, int index, int* out) {
+  if (k < 2 || k > 5 || index < 0 || index >= 1 << hmme::kIdxBits || !out) return -1;
+  hmme::me_carry_position(k, (uint32_t)index, out[0], out[1]);
+  return 0;
+}
 
 // writes the device job table of plan `pl` -- a picture search over CTUs [first, first + count) against n_refs reference pictures -- on `s`;
 // job index = ref * count + ctu.  kWhole8: MeJob[jobs]; kHeadThenSegments8: MeJob[head], then the tail's segment table; kSegments8: one

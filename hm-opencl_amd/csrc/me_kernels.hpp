@@ -187,6 +187,25 @@ __host__ __device__ inline bool me_task_full(int wx, int wy, int k, int it0, int
   const bool fold = (quads & 32) && (quads & 31) && (wy & 1);   // me_fold (below)
   return (it0 + n_it) * (64 >> k) <= ((k == 5 || !fold) ? wy : wy - 1);
 }
+// Packed running minima carried across the full tasks of one part (whole-job launches): the ten low bits of their keys hold the ABSOLUTE
+// lane-iteration above the 16-candidate group inside it, it_abs(6) | lane_now[5:2](4), where the per-task keys hold it - it0 (2 bits), the
+// same four group bits and two zeros.  A group of part k lies at (row, group in the row): a lane-iteration covers 64 >> k rows of
+// 2^(k-2) groups, so the index is (row / ty) << 4 | (row % ty) << (k - 2) | group -- its integer order is the raster order of the part,
+// and a wave's minima over any number of full tasks of one part decode without the task's it0.  Six bits hold every iteration of a full
+// task: its rows end inside a window of at most 129 rows and a lane-iteration has at least two (me_task_carry_fits).
+constexpr int kCarryGroupBits = 4, kCarryItBits = kIdxBits - kCarryGroupBits;
+__host__ __device__ inline bool me_task_carry_fits(int wx, int wy, int k, int it0, int n_it) {
+  return !me_task_full(wx, wy, k, it0, n_it) || it0 + n_it <= (1 << kCarryItBits);
+}
+__host__ __device__ inline uint32_t me_carry_index(int k, int row, int group) {
+  const int ty = 64 >> k;
+  return (uint32_t)((row / ty) << kCarryGroupBits | (row % ty) << (k - 2) | group);
+}
+__host__ __device__ inline void me_carry_position(int k, uint32_t index, int& row, int& group) {
+  const int g4 = (int)(index & ((1u << kCarryGroupBits) - 1));
+  row = (int)(index >> kCarryGroupBits) * (64 >> k) + (g4 >> (k - 2));
+  group = g4 & ((1 << (k - 2)) - 1);
+}
 #define ME_PKMIN(r, p) ME_PKMIN_Q(r, (p) + pkm)
 #define ME_PKMINE(r, p) ME_PKMIN_Q(r, ((p) << 1) + pkm)
 #define ME_PKMIN_Q(r, q)                                                                                        \
@@ -290,6 +309,20 @@ __device__ __forceinline__ uint32_t me_merge_dpp(uint32_t a, uint32_t b, bool ro
 __device__ __forceinline__ uint32_t me_component_bits(int v) {
   const uint32_t t = (v <= 0) ? ((uint32_t)(-v) << 1) + 1u : ((uint32_t)v << 1);
   return 2u * (31u - (uint32_t)__builtin_clz(t)) + 1u;
+}
+// The same, and a negation, without a subtract instruction (v_xad_u32: (a ^ b) + c): for the prologue of a full task's lane-iteration,
+// which shares the full-task body's basic block -- the block's v_sub_u32 are the two per packed subtract of the tree and no other
+// (tests/test_search_isa.py counts them).  ~(2v) + 2 = 1 - 2v
+__device__ __forceinline__ uint32_t me_neg_xad(uint32_t x) {
+  uint32_t r;
+  asm("v_xad_u32 %0, %1, -1, 1" : "=v"(r) : "v"(x));
+  return r;
+}
+__device__ __forceinline__ uint32_t me_component_bits_xad(int v) {
+  const uint32_t v2 = (uint32_t)v << 1;
+  uint32_t t;
+  asm("v_xad_u32 %0, %1, -1, 2" : "=v"(t) : "v"(v2));
+  return 2u * (31u - (uint32_t)__builtin_clz(v > 0 ? v2 : t)) + 1u;
 }
 // TComRdCost::getCost(x, y) with cost scale 2 (reference TComRdCost.h:172-189): uint32 wrap, >> 16
 __device__ __forceinline__ uint32_t me_mv_cost(uint32_t lambda_q16, int x, int y, int pred_x, int pred_y) {
@@ -676,6 +709,13 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
 
   static_assert(SPLIT != 2 || kIterPerTaskSplit == 1, "segment mode counts tasks in lane-iterations");
   int grab_next = 0, grab_end = 0;   // SPLIT = 2: the tasks this wave has drawn and not yet run
+  // running minima: register g, lane l <-> slot ME_SLOT_OF[g][l] (ME_SLOT_OF3 in a full task).  b0..b7 of a full task hold packed slots
+  // only; a whole-job launch keeps them across the wave's full tasks of one part (kCarry: keys of me_carry_index, flushed before a task
+  // that is not full or lies in another part, and when the counter runs dry).  carry_k >= 0: they hold minima of part (carry_k, carry_x0)
+  constexpr bool kCarry = PK == 2 && SPLIT == 0;
+  uint32_t b0 = ME_MAXKEY, b1 = ME_MAXKEY, b2 = ME_MAXKEY, b3 = ME_MAXKEY, b4 = ME_MAXKEY, b5 = ME_MAXKEY,
+           b6 = ME_MAXKEY, b7 = ME_MAXKEY, b8 = ME_MAXKEY, b9 = ME_MAXKEY;
+  int carry_k = -1, carry_x0 = 0;
   while (true) {
     int t = 0;
     if constexpr (SPLIT == 2) {
@@ -698,8 +738,9 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
     } else {
       if (lane == 0) t = atomicAdd(&task_ctr, 1);
       t = __builtin_amdgcn_readfirstlane(t);
-      if (t >= n_tasks) break;
+      if (!kCarry && t >= n_tasks) break;   // kCarry: a dry counter decodes to no task at all (below), which flushes what is carried
     }
+    const bool dry = t >= n_tasks;
     if (prio_state < 4 && (prio_state & 3) < 3) {   // the level's share is used up: one step down
       prio_state += (prio_quarter << 2) + 1;
       if ((prio_state & 3) == 1) __builtin_amdgcn_s_setprio(2);
@@ -739,26 +780,103 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
     }
     const int ty = 64 >> k;
     const bool full = PK == 2 && me_task_full(wx, wy, k, it0, n_it);   // wave-uniform: wx, wy of the job, k, it0, n_it of the task
-    // the lane's quad and row inside a lane-iteration.  A full task puts the two lowest bits of the quad index into lane bits 5 and 4
-    // (four adjacent quads in lanes l, l ^ 16, l ^ 32, l ^ 48: the two packed butterfly levels), the rest and ly into bits 0..3
-    int lx = lane & ((1 << k) - 1), ly = lane >> k;
-    if (full) { lx = ((lane >> 5) & 1) | ((lane >> 3) & 2) | ((lane & ((1 << (k - 2)) - 1)) << 2); ly = (lane & 15) >> (k - 2); }
     const bool fold_part = fold && k == 5;
 
-    // running minima of the task: register g, lane l <-> slot ME_SLOT_OF[g][l] (ME_SLOT_OF3 in a full task)
-    uint32_t b0 = ME_MAXKEY, b1 = ME_MAXKEY, b2 = ME_MAXKEY, b3 = ME_MAXKEY, b4 = ME_MAXKEY, b5 = ME_MAXKEY,
-             b6 = ME_MAXKEY, b7 = ME_MAXKEY, b8 = ME_MAXKEY, b9 = ME_MAXKEY;
+    if constexpr (kCarry) {
+      // what the wave carries belongs to the full tasks of one part: anything else (no task at all included) sends it to the CTU table
+      if (carry_k >= 0 && !(full && k == carry_k && x0 == carry_x0)) {
+#define ME_FLUSH_CARRIED(g, key_)                                                                                  \
+        {                                                                                                          \
+          const int slot = ME_SLOT_OF3[g][lane];                                                                   \
+          const uint32_t key = (key_);                                                                             \
+          const uint32_t cost = key >> kIdxBits;                                                                   \
+          if (slot >= 0 && cost < kInvCost) {                                                                      \
+            int row, group;                                                                                        \
+            me_carry_position(carry_k, key & ((1u << kIdxBits) - 1), row, group);                                  \
+            atomicMin(&best64[slot], ((unsigned long long)cost << 32) | ((unsigned long long)row << 16) |          \
+                                         (unsigned long long)(carry_x0 + 16 * group));                             \
+          }                                                                                                        \
+        }
+        ME_FLUSH_CARRIED(0, b0) ME_FLUSH_CARRIED(1, b1) ME_FLUSH_CARRIED(2, b2) ME_FLUSH_CARRIED(3, b3)
+        ME_FLUSH_CARRIED(4, b4) ME_FLUSH_CARRIED(5, b5) ME_FLUSH_CARRIED(6, b6) ME_FLUSH_CARRIED(7, b7)
+#undef ME_FLUSH_CARRIED
+        carry_k = -1;
+      }
+      if (dry) break;
+    }
+    if (carry_k < 0) b0 = b1 = b2 = b3 = b4 = b5 = b6 = b7 = ME_MAXKEY;
+    b8 = b9 = ME_MAXKEY;
+
+    // A full task's lanes all lie inside the window, on the same columns in every lane-iteration: the x halves of its four MV costs
+    // (me_component_bits <= 37 each, one byte apiece), the key's lane field and the window address of its first lane-iteration are
+    // the task's, and a lane-iteration adds what its rows change (the prologue of the full-task body below)
+    uint32_t f_bx = 0, f_tag = 0;
+    int f_vy = 0;
+    const lds_char_t* f_lpc = (const lds_char_t*)win;
+    if (full) {
+      // the lane's quad and row inside a lane-iteration: a full task puts the two lowest bits of the quad index into lane bits 5 and 4
+      // (four adjacent quads in lanes l, l ^ 16, l ^ 32, l ^ 48: the two packed butterfly levels), the rest and ly into bits 0..3
+      const int lx = ((lane >> 5) & 1) | ((lane >> 3) & 2) | ((lane & ((1 << (k - 2)) - 1)) << 2), ly = (lane & 15) >> (k - 2);
+      const int cx = x0 + 4 * lx, cy = it0 * ty + ly;
+      const int vx = ((job.lt_x + cx) << 2) - job.pred_x;
+      f_bx = me_component_bits(vx) | me_component_bits(vx + 4) << 8 | me_component_bits(vx + 8) << 16 | me_component_bits(vx + 12) << 24;
+      f_tag = (uint32_t)(ly << k | lx) << 2;   // the key's lane field: raster order inside the lane-iteration
+      f_vy = ((job.lt_y + cy) << 2) - job.pred_y;
+      f_lpc = (const lds_char_t*)(win + cy * kPDW + (cx >> 2));
+    }
+    // scalar loads complete out of order: ME8_CUR_WAIT (placed by the generator one CU after the loads, before the next CU's are
+    // issued) waits for the batch; the window dwords of the same batch are named first so that the compiler's LDS wait lands there
+#define ME8_CUR(row, q)                                                                                                            \
+  ({                                                                                                                               \
+    uint64_t w_;                                                                                                                   \
+    asm volatile("s_load_dwordx2 %0, %1, %2" : "=s"(w_) : "s"(curc), "n"((row) * 64 + 8 * (q)));                                    \
+    w_;                                                                                                                            \
+  })
+#define ME8_CUR_WAIT(w0, w1, w2, w3, w4, w5, w6, w7, d0, d1, d2, d3, d4, d5, d6, d7, d8, d9, d10, d11, d12, d13, d14, d15)           \
+  asm volatile("" : : "v"(d0), "v"(d1), "v"(d2), "v"(d3), "v"(d4), "v"(d5), "v"(d6), "v"(d7), "v"(d8), "v"(d9), "v"(d10), "v"(d11),  \
+               "v"(d12), "v"(d13), "v"(d14), "v"(d15));                                                                             \
+  asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(w0), "+s"(w1), "+s"(w2), "+s"(w3), "+s"(w4), "+s"(w5), "+s"(w6), "+s"(w7))
 
     prio_state -= n_it << 2;
     for (int it = 0; it < n_it; ++it) {
+      if (full) {
+        if constexpr (PK == 2) {
+          static_assert(PK != 2 || FEN == 1, "the full-task body exists for FEN 1");
+          // every lane valid with all four candidates: no validity selects, no marker, no clamps.  me_pk2_gate bounds the products
+          // below 2^32 and the costs, their high halves, below 2^16: a byte permute packs two of them
+          const uint32_t by = me_component_bits_xad(f_vy + it * (4 * ty));
+          const uint32_t p0 = lambda_q16 * ((f_bx & 255u) + by), p1 = lambda_q16 * (((f_bx >> 8) & 255u) + by);
+          const uint32_t p2 = lambda_q16 * (((f_bx >> 16) & 255u) + by), p3 = lambda_q16 * ((f_bx >> 24) + by);
+          const uint64_t pkm = (uint64_t)__builtin_amdgcn_perm(p1, p0, 0x07060302u) | (uint64_t)__builtin_amdgcn_perm(p3, p2, 0x07060302u) << 32;
+          // the 64-bit negation of pkm (the strips that leave a 16x16 region as sums give the costs back with one add of it: no field
+          // borrows, each holds at least its cost) as complement + 1: one 64-bit add where 0 - pkm is a borrow pair; opaque on both sides,
+          // or the compiler folds it back, and turns the body's add of a negation into a 64-bit subtract
+          uint64_t npkm = ~pkm;
+          asm volatile("" : "+v"(npkm));
+          npkm += 1;
+          asm volatile("" : "+v"(npkm));
+          const uint32_t tag = ((uint32_t)it << 8) | f_tag;
+          // the key constant of the packed slots names the 16-candidate group (its first quad): per task, or per part where carried
+          const uint32_t ctag = kCarry ? (uint32_t)(it0 + it) << kCarryGroupBits | f_tag >> 4 : tag & ~(3u << 2);
+          const uint32_t c0 = (p0 >> 16) << kIdxBits | tag, c1 = (p1 >> 16) << kIdxBits | tag | 1u;
+          const uint32_t c2 = (p2 >> 16) << kIdxBits | tag | 2u, c3 = (p3 >> 16) << kIdxBits | tag | 3u;
+          const uint32_t nc0 = me_neg_xad(c0), nc1 = me_neg_xad(c1), nc2 = me_neg_xad(c2), nc3 = me_neg_xad(c3);
+          const lds_char_t* lpc = f_lpc + it * (ty * kPDW * 4);
+#include "me_tree_pk4_fen1.inc"
+        }
+        continue;
+      }
+      // the key's lane field, raster order inside the lane-iteration, is the lane itself here: quad lx of row ly.  Opaque, so that neither
+      // they nor `lane << 2` join the loop-invariant registers, which the full-task body would have to carry (at 255 VGPRs the one value spilled)
+      uint32_t lane_now = (uint32_t)lane;
+      asm("" : "+v"(lane_now));
+      const int lx = lane_now & ((1 << k) - 1), ly = lane_now >> k;
       int cx = x0 + 4 * lx, cy = (it0 + it) * ty + ly;
       if (fold_part && cy == wy) { cx += 128; cy = wy - 1; }   // idle second row of the last iteration: leftover quads of the last row
       const bool vy = cy < wy;
       // per-candidate constants: (mv cost | invalid marker) << 10 | iteration | lane | j
       const int mvy = job.lt_y + cy, mvx = job.lt_x + cx;
       const uint32_t by = me_component_bits((mvy << 2) - job.pred_y);
-      uint32_t lane_now = (uint32_t)(ly << k | lx);   // the key's lane field: raster order inside the lane-iteration (the lane itself but in a full task)
-      asm("" : "+v"(lane_now));   // keep `lane << 2` out of the loop-invariant registers: at 255 VGPRs it was the one value spilled
       const uint32_t tag = ((uint32_t)it << 8) | (lane_now << 2);
       uint32_t cc[4];
 #pragma unroll
@@ -776,37 +894,11 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
         const uint32_t m2 = cc[2] < (kInvCost << kIdxBits) ? cc[2] >> kIdxBits : kPkMarker, m3 = cc[3] < (kInvCost << kIdxBits) ? cc[3] >> kIdxBits : kPkMarker;
         pkm = (uint64_t)(m0 | m1 << 16) | (uint64_t)(m2 | m3 << 16) << 32;
         ctag = ((vy && cx < wx) ? 0u : kInvCost << kIdxBits) | tag;   // candidate 0 is valid wherever one of the four is
-        if (full) ctag = tag & ~(3u << 2);                              // every lane valid; the key names the group's first quad
-      }
-      // full tasks carry the MV costs in the sums (me_tree_pk4_fen1.inc); the strips that leave a 16x16 region as sums give them back
-      // with one add of the 64-bit negation: no field borrows, each holds at least its cost.  Opaque: the compiler would turn the add
-      // of a negation into a 64-bit subtract, two instructions with a borrow between them where the add is one
-      uint64_t npkm = 0;
-      if constexpr (PK == 2) {
-        npkm = 0ull - pkm;
-        asm volatile("" : "+v"(npkm));
       }
       // lanes outside the window still run (wave-uniform code) on clamped, in-bounds addresses
       const lds_char_t* lpc = (const lds_char_t*)(win + min(cy, wy - 1) * kPDW + (min(cx, wx - 1) >> 2));
-      // scalar loads complete out of order: ME8_CUR_WAIT (placed by the generator one CU after the loads, before the next CU's are
-      // issued) waits for the batch; the window dwords of the same batch are named first so that the compiler's LDS wait lands there
-#define ME8_CUR(row, q)                                                                                                            \
-  ({                                                                                                                               \
-    uint64_t w_;                                                                                                                   \
-    asm volatile("s_load_dwordx2 %0, %1, %2" : "=s"(w_) : "s"(curc), "n"((row) * 64 + 8 * (q)));                                    \
-    w_;                                                                                                                            \
-  })
-#define ME8_CUR_WAIT(w0, w1, w2, w3, w4, w5, w6, w7, d0, d1, d2, d3, d4, d5, d6, d7, d8, d9, d10, d11, d12, d13, d14, d15)           \
-  asm volatile("" : : "v"(d0), "v"(d1), "v"(d2), "v"(d3), "v"(d4), "v"(d5), "v"(d6), "v"(d7), "v"(d8), "v"(d9), "v"(d10), "v"(d11),  \
-               "v"(d12), "v"(d13), "v"(d14), "v"(d15));                                                                             \
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(w0), "+s"(w1), "+s"(w2), "+s"(w3), "+s"(w4), "+s"(w5), "+s"(w6), "+s"(w7))
       if constexpr (PK == 2) {
-        static_assert(PK != 2 || FEN == 1, "the full-task body exists for FEN 1");
-        if (full) {
-#include "me_tree_pk4_fen1.inc"
-        } else {
 #include "me_tree_pk_fen1.inc"
-        }
       } else if constexpr (PK) {
         if constexpr (FEN) {
 #include "me_tree_pk_fen1.inc"
@@ -835,8 +927,13 @@ me_search_kernel(const RefSet curs, int cur_ctus_x, const RefSet refs, int ref_p
                   ((unsigned long long)cost << 32) | ((unsigned long long)byy << 16) | (unsigned long long)bx);    \
       }                                                                                                            \
     }
-    ME_FLUSH(0, b0) ME_FLUSH(1, b1) ME_FLUSH(2, b2) ME_FLUSH(3, b3) ME_FLUSH(4, b4)
-    ME_FLUSH(5, b5) ME_FLUSH(6, b6) ME_FLUSH(7, b7) ME_FLUSH(8, b8) ME_FLUSH(9, b9)
+    if (!(kCarry && full)) {
+      ME_FLUSH(0, b0) ME_FLUSH(1, b1) ME_FLUSH(2, b2) ME_FLUSH(3, b3)
+      ME_FLUSH(4, b4) ME_FLUSH(5, b5) ME_FLUSH(6, b6) ME_FLUSH(7, b7)
+    } else {      // the packed minima of a full task stay with the wave (above)
+      carry_k = k; carry_x0 = x0;
+    }
+    ME_FLUSH(8, b8) ME_FLUSH(9, b9)
 #undef ME_FLUSH
   }
 #ifdef ME_SEARCH_T_TIMELINE

@@ -54,6 +54,7 @@ SYMBOLS = ["hmme_create", "hmme_destroy", "hmme_last_error", "hmme_device_info",
 # test / measurement entry points (include/hmme_test.h): not part of the boundary
 TEST_SYMBOLS = ["hmme_test_time_search_kernel", "hmme_test_device_address", "hmme_test_frac_deal", "hmme_test_tail_plan", "hmme_test_stage_layout", "hmme_test_picture_job", "hmme_test_time_weight_passes", "hmme_test_time_bipred_origin",
                 "hmme_test_time_wp_estimate_passes", "hmme_test_pk_gate", "hmme_test_pk_body", "hmme_test_pk_task_marker_free", "hmme_test_pk_task_full",
+                "hmme_test_task_carry_fits", "hmme_test_carry_index", "hmme_test_carry_position",
                 "hmme_test_wp_parameters", "hmme_test_wp_select", "hmme_test_ctu_plan"]
 ABI_VERSION = 6   # HMME_ABI_VERSION of the include/hmme.h these bindings were written against
 

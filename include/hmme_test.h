@@ -41,6 +41,17 @@ int hmme_test_pk_task_marker_free(int wx, int wy, int k, int it0, int n_it);
  * excludes the folded iteration).  Every other task of the kernel runs the packed-minimum twin */
 int hmme_test_pk_task_full(int wx, int wy, int k, int it0, int n_it);
 
+/* The packed running minima a wave of a whole-picture launch carries across the full tasks of one part (me_kernels.hpp, above
+ * me_task_carry_fits; host arithmetic, needs no device).  Their keys hold the absolute lane-iteration (6 bits) above the 16-candidate group
+ * inside it (4 bits):
+ *   hmme_test_task_carry_fits   1 unless the task is full and one of its lane-iterations lies beyond the six bits (me_task_carry_fits)
+ *   hmme_test_carry_index       the ten-bit index of the group at window row `row`, `group` groups into part k (2..5) (me_carry_index);
+ *                               -1 for a k or a group the part does not have
+ *   hmme_test_carry_position    out[0], out[1] = the row and group of an index (me_carry_position: what the flush decodes); -1 for a bad argument */
+int hmme_test_task_carry_fits(int wx, int wy, int k, int it0, int n_it);
+int hmme_test_carry_index(int k, int row, int group);
+int hmme_test_carry_position(int k, int index, int* out);
+
 /* where the staging arena of a synchronous, host-array call puts n items of bytes[i] bytes (hmme.hip stage_layout: what every hmme_*_frame*
  * entry point lays its arrays out with; host arithmetic, needs no device): offsets[i] and *total, the arena's size.  Returns the alignment of
  * every item, or a negative value for a null argument */
